@@ -9,7 +9,7 @@ already resident in HBM and the per-angle upwind tables / sweep schedule built b
 depend on the grid and the quadrature only; their one-time cost is reported separately).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4|C2|C3|C5|tiny] [--nlam L]
-                    [--shard lambda|lambda-strong|angle]
+                    [--shard lambda|lambda-strong|angle] [--dump-outputs DIR]
 
 N > 1: one rank per GPU over RCCL.  Launched by `python -m torch.distributed.run ...` (RANK /
 WORLD_SIZE in the environment) the script joins that job; launched bare (`python bench.py --gpus 8`)
@@ -49,6 +49,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E vendor peak, /opt/skills/guides/MI355X_MICROARCH.md
 PROFILE_ROUND = "r5"
+DUMP_BUDGET = 64 * 10**6  # bytes (64 MB), all files of --dump-outputs together
+DUMP_SEED = 20240601    # the site sample of --dump-outputs: the same rows in every run and every build
 
 WORKLOADS = {
     # name: (a, c, quadrature, nlam, alpha per angle, seed)   -- SURVEY.md 8d, BASELINE.md sec. 3
@@ -95,6 +97,9 @@ def parse_args(argv=None):
     ap.add_argument("--alpha0", type=float, default=1.0e-2,
                     help="opacity scale at z_min [1/m] (diagnostics: tiny values take the Taylor branch)")
     ap.add_argument("--dump-J", default="", help="rank 0 saves the (gathered) J of the last step as .npy")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the timed path returned in its last timed step to DIR/<name>.npy "
+                         f"(J; a fixed seeded sample of its sites when the whole would exceed {DUMP_BUDGET // 10**6} MB)")
     return ap.parse_args(argv)
 
 
@@ -147,10 +152,30 @@ def cpu_model() -> str:
     return "unknown"
 
 
+def dump_outputs(dump_dir, J):
+    """--dump-outputs: J (n, nlam) as the caller receives it, in its own dtype (float64, or float32 with --dtype f32).
+    Beyond the budget, a fixed seeded sample of the sites (rows, in ascending site order) -- the same rows for the
+    same workload in every run, so that two builds compare output for output."""
+    import torch
+    n, ncol = J.shape
+    rows_fit = max(1, (DUMP_BUDGET - 4096) // (ncol * J.element_size()))
+    if n > rows_fit:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=rows_fit, replace=False))
+        J = J[torch.as_tensor(rows, device=J.device)]
+        what = f"{rows_fit} of {n} sites (seeded sample, seed {DUMP_SEED})"
+    else:
+        what = f"all {n} sites"
+    os.makedirs(dump_dir, exist_ok=True)
+    out = J.contiguous().cpu().numpy()
+    np.save(os.path.join(dump_dir, "J.npy"), out)
+    print(f"[bench] --dump-outputs: J {out.shape} {out.dtype} ({what}) -> {dump_dir}", file=sys.stderr)
+
+
 def measure(args, workload, torch, dist, vrt, _lib, distributed, synth, rank, world, local, dev, rehearse,
-            steps, warmup, cpu_baseline):
+            steps, warmup, cpu_baseline, dump_dir=""):
     """One workload: setup, warm-up, timed steps, roofline, optional CPU baseline.  Returns the
-    result dict (rank 0 holds the CPU baseline / parity fields)."""
+    result dict (rank 0 holds the CPU baseline / parity fields).  dump_dir: write the J of the last
+    timed step there (dump_outputs)."""
     a, c, quad, nlam_total, per_angle, seed = WORKLOADS[workload]
     if args.nlam > 0 and workload == args.workload:
         nlam_total = args.nlam
@@ -341,6 +366,16 @@ def measure(args, workload, torch, dist, vrt, _lib, distributed, synth, rank, wo
         # J in the caller's layout for the checks below; and the same step over the caller's layout, timed beside it
         plan.J_from_native_dev(nlam, nlam, J_nat[0].data_ptr(), J_nat[1].data_ptr(), J.data_ptr(), stream=stream, f32=f32)
         torch.cuda.synchronize()
+    if dump_dir and rank == 0:
+        # the J of the last timed step, before anything below runs the plan again
+        if groups is not None:
+            J_last = sum(gJ for _, _, _, gJ in groups)
+        elif "buf" in gathered:
+            J_last = distributed.assemble_J_blocks(gathered["buf"], gathered["sizes"])
+        else:
+            J_last = J
+        dump_outputs(dump_dir, J_last)
+        del J_last
     if sj_native and not args.no_caller_layout:
         J_keep = J.clone()
         sweep_keep = plan.last_sweep_timing()
@@ -638,7 +673,7 @@ def main():
     dev = torch.device("cuda", local)
 
     out = measure(args, args.workload, torch, dist, vrt, _lib, distributed, synth, rank, world, local, dev,
-                  rehearse, args.steps, args.warmup, not args.no_cpu_baseline)
+                  rehearse, args.steps, args.warmup, not args.no_cpu_baseline, dump_dir=args.dump_outputs)
     # BASELINE.json configs[1] (the reference's continuum case: ~250k sites x 12 angles x 1 λ) rides
     # along as a secondary measurement of the default single-GPU run; the headline stays the
     # configuration the metric is quoted on (1M sites, 12 angles).

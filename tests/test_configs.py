@@ -460,3 +460,30 @@ def test_bench_two_ranks_default_is_the_fixed_workload(launcher):
         j3 = json.loads([ln for ln in r3.stdout.splitlines() if ln.startswith("{")][-1])
         assert j3["scaling"] == "weak" and "none" in j3["collective"]["op"]
         assert abs(j3["value"] * j3["ms_per_step"] - 2 * u1) < 1e-6 * u2      # weak: both ranks' updates
+
+
+def test_bench_dump_outputs_is_the_J_of_the_timed_steps_and_repeats(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the J of the last timed step (the one --dump-J saves at the end of the
+    run), `--steps` is the number of timed steps, and two runs with the same arguments give the same J bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop("VRT_PATH", None)
+    outs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", "3",
+               "--warmup", "1", "--no-cpu-baseline", "--no-critical-path", "--dump-outputs", str(tmp_path / run),
+               "--dump-J", str(tmp_path / f"J_{run}.npy")]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / run)) == ["J.npy"]
+        J = np.load(tmp_path / run / "J.npy")
+        assert J.dtype == np.float64 and J.shape == (line["config"]["sites"], line["config"]["nlam_per_rank"])
+        assert np.array_equal(J, np.load(tmp_path / f"J_{run}.npy")) and np.isfinite(J).all() and (J > 0).any()
+        outs.append(J)
+    assert np.array_equal(outs[0], outs[1])

@@ -910,3 +910,27 @@ def test_gloo_world_of_one_runs_the_collectives(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29641", WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, str(script), ROOT], env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+
+
+def test_bench_dump_outputs_keeps_the_whole_J_or_a_fixed_sample_within_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: J as the caller receives it, whole while it fits the budget; beyond it a seeded sample of
+    the sites that is the same in every run, under the budget, in the caller's dtype and ascending site order."""
+    import importlib.util
+    import torch
+    monkeypatch.setenv("OMP_WAIT_POLICY", os.environ.get("OMP_WAIT_POLICY", "passive"))   # bench.py sets a default
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    J = torch.arange(3000 * 7, dtype=torch.float64).reshape(3000, 7)
+    bench.dump_outputs(str(tmp_path / "whole"), J)
+    got = np.load(tmp_path / "whole" / "J.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, J.numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4096 + 500 * 7 * 8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), J)
+    a, b = np.load(tmp_path / "a" / "J.npy"), np.load(tmp_path / "b" / "J.npy")
+    assert a.shape == (500, 7) and np.array_equal(a, b)
+    rows = a[:, 0].astype(np.int64) // 7                     # row r of J holds 7r .. 7r + 6
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, J.numpy()[rows])
+    bench.dump_outputs(str(tmp_path / "f32"), J[:10].to(torch.float32))
+    assert np.load(tmp_path / "f32" / "J.npy").dtype == np.float32
