@@ -274,7 +274,7 @@ int vrt_plan_last_path(const vrt_plan *p);
  *   VRT_PAIR_BLOCK = 1 | 2 | 4 | 8 | 16        wavelength pairs of a site side by side in the patch path's planes and
  *                                              in the plan's native alpha (creation only; default 1)
  *   VRT_STEP_K, VRT_STEP_SINGLE, VRT_STEP_PAIRS, VRT_STEP_XCD, VRT_STEP_STREAMS, VRT_STEP_LEVEL_MAP,
- *   VRT_STEP_GROUP_DIR, VRT_TILE_WIDE, VRT_TILE_PRE, VRT_GRAPH     variants of the older paths
+ *   VRT_STEP_GROUP_DIR, VRT_TILE_WIDE, VRT_TILE_PRE                variants of the older paths
  * VRT_EINVAL for an unknown name, a value out of range, or a creation-only option on a live plan. */
 int vrt_plan_set_option(vrt_plan *p, const char *name, const char *value);
 int vrt_grid_set_option(vrt_grid *g, const char *name, const char *value);

@@ -944,11 +944,10 @@ def test_concurrent_single_solves_on_one_handle(grids):
         assert _rel(out[j], ref) < RTOL
 
 
-def test_level_path_with_hipgraph_replay(grids, monkeypatch):
-    """VRT_GRAPH=1: the level-launch sequence is captured once and replayed; same results, also
-    when the buffers (hence the captured arguments) change between calls."""
+def test_level_path_while_buffers_and_nlam_change(grids, monkeypatch):
+    """The level path on one plan, call after call: same results when the buffers and the wavelength
+    count change between calls."""
     monkeypatch.setenv("VRT_PATH", "levels")
-    monkeypatch.setenv("VRT_GRAPH", "1")
     hs, so = grids["bcc"]
     n = so.n
     rng = np.random.default_rng(31)
@@ -1376,3 +1375,117 @@ def test_sweep_order_S_and_J_are_the_caller_layout_results_bit_for_bit(grids, mo
     torch.cuda.synchronize()
     assert torch.equal(J, Jn) and float(J_dn.abs().max()) == 0.0
     plan.close()
+
+
+def _lattice_case(a):
+    """BCC lattice whose site ids follow the lattice rows (2 a^2 sites per layer): along a row, one Gauss-Seidel sweep
+    resolves every in-layer dependency, so the ray (110°, 180°) has in-layer cones of more than the 512 entries of
+    the patch kernel -- the plan has no patch schedule -- while its layer schedule fits the steps / tiles encoding."""
+    pos, nbr, bounds = synth.bcc_grid(a, 3, seed=5, permute_ids=False)
+    return vrt.VoronoiSites(pos, nbr, bounds, device=0), orc.make_sites(pos, nbr, bounds), (110.0, 180.0)
+
+
+@pytest.mark.parametrize("grid, want", [("bcc", "patches"), ("voronoi", "patches"), ("lattice", "steps")])
+@pytest.mark.parametrize("nlam", [1, 2])
+def test_sweep_order_single_solve_runs_on_a_layer_path(grids, monkeypatch, grid, want, nlam):
+    """One angle and one or two wavelengths on small layers: the caller-layout call takes the persistent tiles,
+    which cannot read sweep-order planes, so vrt_plan_execute_native_dev runs on the patch path instead, or on the
+    steps path where the plan has no patch schedule.  Its J equals the caller-layout J of that path bit for bit
+    (per-site and sweep-order per-(site, wavelength) alpha) and the oracle's to the 1e-10 bar."""
+    import torch
+    monkeypatch.delenv("VRT_PATH", raising=False)
+    w, th, ph, nq = vrt.read_quadrature("ul7n12.dat")
+    if grid == "lattice":
+        hs, so, (th1, ph1) = _lattice_case(45)
+        th_sel, ph_sel, w1 = np.array([th1]), np.array([ph1]), np.array([1.0])
+    else:
+        hs, so = grids[grid]
+        sel = [i for i in range(nq) if th[i] > 90][:1]     # one up angle
+        th_sel, ph_sel, w1 = th[sel], ph[sel], w[sel]
+    n = so.n
+    rng = np.random.default_rng(40 + nlam)
+    S = 1.0 + rng.random((n, nlam))
+    al1 = 10.0 ** rng.uniform(-3, 1, n)
+    n1 = int(so.layers_up[1] - 1)
+    I0 = S[so.perm_up[:n1] - 1].copy()
+    plan = vrt.FormalPlan(hs, vrt.quadrature_directions(th_sel, ph_sel), 3)
+    if want == "steps":                                       # the case meant: no patch schedule
+        plan.set_option("VRT_PATH", "patches")
+        with pytest.raises(vrt.VrtError):
+            plan.execute(S, al1, weights=w1, I0_up=I0)
+        plan.set_option("VRT_PATH", "auto")
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream().cuda_stream
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    dS, dA1, dI0 = t(S), t(al1), t(I0)
+    np_ = plan.native_plane_count(nlam)
+    S_up = torch.zeros((np_,), dtype=torch.float64, device=dev)
+    plan.to_native_dev(nlam, nlam, dS.data_ptr(), S_up.data_ptr(), 0, stream=st)
+    J = torch.zeros((n, nlam), dtype=torch.float64, device=dev)
+    plan.execute_dev(nlam, nlam, dS.data_ptr(), dA1.data_ptr(), _lib.ALPHA_SITE, w1, dJ=J.data_ptr(), dI0_up=dI0.data_ptr(), stream=st)
+    assert plan.last_path == "tiles"                         # the case meant: the automatic choice is tiles
+    for mode in ("site", "site_lam"):
+        if mode == "site":
+            dal_caller, dal, am_caller, am = dA1, dA1, _lib.ALPHA_SITE, _lib.ALPHA_SITE
+            al_ref = np.repeat(al1[:, None], nlam, axis=1)
+        else:
+            al_ref = al1[:, None] * (1 + 0.02 * np.arange(nlam)[None, :])
+            dal_caller = t(al_ref)
+            dal = torch.zeros((2 * np_,), dtype=torch.float64, device=dev)
+            plan.to_native_dev(nlam, nlam, dal_caller.data_ptr(), dal.data_ptr(), dal.data_ptr() + 8 * np_, stream=st)
+            am_caller, am = _lib.ALPHA_SITE_LAM, _lib.ALPHA_SITE_LAM_NATIVE
+        plan.set_option("VRT_PATH", want)
+        J = torch.zeros((n, nlam), dtype=torch.float64, device=dev)
+        plan.execute_dev(nlam, nlam, dS.data_ptr(), dal_caller.data_ptr(), am_caller, w1, dJ=J.data_ptr(), dI0_up=dI0.data_ptr(), stream=st)
+        assert plan.last_path == want
+        plan.set_option("VRT_PATH", "auto")
+        J_up, J_dn = (torch.full((np_,), -3.0, dtype=torch.float64, device=dev) for _ in range(2))
+        plan.execute_native_dev(nlam, S_up.data_ptr(), 0, dal.data_ptr(), am, w1, dJ_up=J_up.data_ptr(),
+                                dJ_down=J_dn.data_ptr(), dI0_up=dI0.data_ptr(), stream=st)
+        assert plan.last_path == want
+        Jn = torch.zeros((n, nlam), dtype=torch.float64, device=dev)
+        plan.J_from_native_dev(nlam, nlam, J_up.data_ptr(), J_dn.data_ptr(), Jn.data_ptr(), stream=st)
+        torch.cuda.synchronize()
+        plan.check()
+        assert torch.equal(J, Jn)
+        ref = orc.J_voronoi(w1, th_sel, ph_sel, S, al_ref, so, I0_up=I0, nthreads=4)
+        assert _rel(Jn.cpu().numpy(), ref) < RTOL
+    plan.close()
+    if grid == "lattice":
+        hs.close()
+
+
+def test_sweep_order_call_without_a_layer_path_is_refused_untouched(monkeypatch):
+    """12 800-site layers, more than the fp64 steps kernels hold, and no patch schedule (_lattice_case): sweep-order S
+    and J have no layer path on this plan.  vrt_plan_execute_native_dev is refused before anything runs, and the
+    caller's J planes keep what they held."""
+    import torch
+    monkeypatch.delenv("VRT_PATH", raising=False)
+    hs, so, (th1, ph1) = _lattice_case(80)
+    assert int(np.diff(so.layers_up).max()) == 12800
+    n, nlam = so.n, 2
+    rng = np.random.default_rng(3)
+    S = 1.0 + rng.random((n, nlam))
+    al1 = 10.0 ** rng.uniform(-3, 1, n)
+    plan = vrt.FormalPlan(hs, [vrt.direction(th1, ph1)], 3)
+    for refused in ("patches", "steps"):                       # the case meant: neither layer path holds the grid
+        plan.set_option("VRT_PATH", refused)
+        with pytest.raises(vrt.VrtError):
+            plan.execute(S, al1, weights=[1.0])
+    plan.set_option("VRT_PATH", "auto")
+    plan.execute(S, al1, weights=[1.0])
+    assert plan.last_path == "levels"                           # (the caller-layout call runs)
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream().cuda_stream
+    np_ = plan.native_plane_count(nlam)
+    S_up = torch.ones((np_,), dtype=torch.float64, device=dev)
+    dA = torch.from_numpy(al1).to(dev)
+    J_up, J_dn = (torch.full((np_,), -3.0, dtype=torch.float64, device=dev) for _ in range(2))
+    with pytest.raises(vrt.VrtError):
+        plan.execute_native_dev(nlam, S_up.data_ptr(), 0, dA.data_ptr(), _lib.ALPHA_SITE, [1.0], dJ_up=J_up.data_ptr(),
+                                dJ_down=J_dn.data_ptr(), stream=st)
+    torch.cuda.synchronize()
+    assert float(J_up.min()) == float(J_up.max()) == -3.0
+    assert float(J_dn.min()) == float(J_dn.max()) == -3.0
+    plan.close()
+    hs.close()

@@ -26,7 +26,7 @@ void tuning_from_env(Tuning &t)
 {
     static const char *names[] = {"VRT_PATH", "VRT_STEP_K", "VRT_STEP_SINGLE", "VRT_STEP_PAIRS", "VRT_STEP_XCD",
                                   "VRT_STEP_STREAMS", "VRT_STEP_LEVEL_MAP", "VRT_STEP_GROUP_DIR", "VRT_TILE_WIDE",
-                                  "VRT_TILE_PRE", "VRT_GRAPH", "VRT_PATCH_K", "VRT_PATCH_NT", "VRT_PATCH_OWN",
+                                  "VRT_TILE_PRE", "VRT_PATCH_K", "VRT_PATCH_NT", "VRT_PATCH_OWN",
                                   "VRT_PATCH_Q", "VRT_PATCH_TARGET", "VRT_PATCH_SPLIT", "VRT_PAIR_BLOCK", "VRT_PATCH_QUAD", "VRT_PATCH_LEAN", "VRT_PATCH_CHAIN", "VRT_CHAIN_PAIRS", "VRT_CHAIN_SPIN", "VRT_CHAIN_DATAFLAG", "VRT_CHAIN_STATIC", "VRT_LAMBDA_NATIVE", "VRT_DEBUG_FLAGS", "VRT_DEBUG_SKIP_LEVELS",
                                   "VRT_TILE_DEBUG"};
     for (const char *nm : names) {
@@ -64,7 +64,7 @@ int tuning_set(Tuning &t, const char *name, const char *value, bool created)
         {"VRT_STEP_PAIRS", &t.step_pairs, 0, 64, false}, {"VRT_STEP_XCD", &t.step_xcd, 0, 2, false},
         {"VRT_STEP_STREAMS", &t.step_streams, 1, 4, false}, {"VRT_STEP_LEVEL_MAP", &t.step_level_map, 0, 1, false},
         {"VRT_STEP_GROUP_DIR", &t.step_group_dir, 0, 1, false}, {"VRT_TILE_WIDE", &t.tile_wide, 0, 1, false},
-        {"VRT_TILE_PRE", &t.tile_pre, 0, 1, false}, {"VRT_GRAPH", &t.graph, 0, 1, false},
+        {"VRT_TILE_PRE", &t.tile_pre, 0, 1, false},
         {"VRT_PATCH_K", &t.patch_K, 1, 8, true}, {"VRT_PATCH_NT", &t.patch_NT, 64, 1024, true},
         {"VRT_PATCH_OWN", &t.patch_own, 0, 65535, true}, {"VRT_PATCH_Q", &t.patch_Q, 1, 4, false},
         {"VRT_PATCH_TARGET", &t.patch_target, 0, 1 << 20, false}, {"VRT_PATCH_SPLIT", &t.patch_split, 0, 4096, false}, {"VRT_PAIR_BLOCK", &t.pair_block, 1, 16, true},
@@ -279,7 +279,6 @@ static void free_plan(vrt_plan *p)
         if (l.st) (void)hipStreamDestroy(l.st);
     }
     if (p->copy_done) (void)hipEventDestroy(p->copy_done);
-    if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
     if (p->ev1) (void)hipEventDestroy(p->ev1);
     delete p;
@@ -735,153 +734,119 @@ static int ensure(double *&buf, size_t &cap, size_t count)
     return VRT_OK;
 }
 
-int execute_dev_locked(vrt_plan *p, int64_t nlam, int64_t ld, const void *dS_, const void *dalpha_, int alpha_mode,
-                       const void *dI0_up_, const void *dI0_down_, const double *weights, void *dJ_, void *dI_out_,
-                       hipStream_t st, bool f32)
+// The path of one execute -- 1 levels, 2 tiles, 3 steps, 4 patches -- or a VRT_E* code.  Every rule of the choice is
+// here, and it runs before anything is allocated or launched; it has no effect beyond the error message.
+// Four device paths produce the same results:
+//   "levels"  one launch per dependency level over all angles; any grid;
+//   "tiles"   ONE launch: each (angle, wavelength) workgroup walks all layers itself;
+//   "steps"   two launches per BFS layer: chip-wide coefficient kernel + one workgroup per
+//             (angle, wavelength) running the layer's Gauss-Seidel levels on an LDS tile;
+//   "patches" one fused launch per BFS layer, or every layer in one chained launch (vrt_patch.hip).
+// tiles needs layers of at most 8192 sites, steps of at most 12 288 (fp64) / 18 432 (fp32
+// storage) and both <= 255 levels per layer; patches needs the plan's patch schedule.  Default: tiles while the
+// (angle, wavelength) problems fit one round of workgroups (<= 256) AND the layers are small
+// (<= 4096 sites: the one launch has no per-layer launch cost -- C2, 2738-site layers: 1.2 ms
+// vs 1.8 ms on steps, which is host-launch-bound there); otherwise patches, then steps (its chip-wide
+// coefficient kernel wins once a layer holds more than a few sites per thread -- 1M sites x
+// 12 angles x 1 λ: 5.1 vs 7.8 ms; C4: 11.8 vs 20.5 ms); levels when the grid fits none of them.
+// VRT_PATH selects one explicitly.  Native calls (sweep-order S and J) run on a layer path only.
+static int choose_path(const vrt_plan *p, const ExecArgs &x)
 {
-    const void *dS = dS_, *dalpha = dalpha_;
-    void *dJ = dJ_, *dI_out = dI_out_;
-    vrt_grid *g = p->g;
-    if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
-    if (!dS || !dalpha) return fail(VRT_EINVAL, "S and alpha must not be NULL");
-    if (alpha_mode < 0 || alpha_mode > VRT_ALPHA_SITE_LAM_NATIVE) return fail(VRT_EINVAL, "bad alpha_mode");
-    if (alpha_mode == VRT_ALPHA_SITE_LAM_NATIVE && !p->nat_mode)
+    const int am = x.alpha_mode;
+    const bool f32 = x.f32;
+    int rc;
+    if (x.native) {
+        if ((rc = native_planes_ok(p, f32))) return rc;
+        if ((p->n_up > 0 && !x.S_nat[0]) || (p->n_down > 0 && !x.S_nat[1]))
+            return fail(VRT_EINVAL, "S of a direction with angles must not be NULL");
+        if (!x.J_nat[0] != !x.J_nat[1]) return fail(VRT_EINVAL, "J_up and J_down must be given together (or both NULL)");
+        if (am != VRT_ALPHA_SITE && am != VRT_ALPHA_ANGLE_NATIVE && am != VRT_ALPHA_SITE_LAM_NATIVE)
+            return fail(VRT_EINVAL, "sweep-order S goes with alpha per site (0), native per angle (3) or per (site, wavelength) in sweep order (4): the other layouts carry the caller's leading dimension");
+    }
+    if (x.nlam < 1 || x.ld < x.nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
+    if ((!x.native && !x.S) || !x.alpha) return fail(VRT_EINVAL, "S and alpha must not be NULL");
+    if (am < 0 || am > VRT_ALPHA_SITE_LAM_NATIVE) return fail(VRT_EINVAL, "bad alpha_mode");
+    if (am == VRT_ALPHA_SITE_LAM_NATIVE && !x.native)
         return fail(VRT_EINVAL, "alpha per (site, wavelength) in sweep order goes with sweep-order S and J (vrt_plan_execute_native_dev)");
-    if (dJ && !weights) return fail(VRT_EINVAL, "weights must be given when J is requested");
-    int rc = use_device(g->device);
-    if (rc) return rc;
-    const int64_t n = g->n;
+    if (x.wants_J() && !x.weights) return fail(VRT_EINVAL, "weights must be given when J is requested");
     // the user's per-angle alpha is indexed by USER angle; the plan's by active angle.  They
     // coincide unless a θ = 90 direction was skipped, which per-angle alpha does not support.
-    if (alpha_mode == VRT_ALPHA_ANGLE_SITE_LAM && p->A != (int)p->n_angles_user)
+    if (am == VRT_ALPHA_ANGLE_SITE_LAM && p->A != (int)p->n_angles_user)
         return fail(VRT_EINVAL, "per-angle alpha needs every angle active (no θ = 90 direction)");
     const bool steps_ok = p->tile_ok && p->tile_max_layer_size <= steps_max_layer(f32);
-    if (alpha_mode == VRT_ALPHA_ANGLE_NATIVE && !(p->patch_ok || (steps_ok && !f32)))
+    const bool tiles_ok = steps_ok && !f32 && p->tile_max_layer_size <= 8192;
+    if (am == VRT_ALPHA_ANGLE_NATIVE && !(p->patch_ok || (steps_ok && !f32)))
         return fail(VRT_EINVAL, "native-layout alpha needs a layer path (at most 4 visits per site and 255 levels per layer)");
-    {
-        // Three device paths produce the same results:
-        //   "levels"  one launch per dependency level over all angles; any grid;
-        //   "steps"   two launches per BFS layer: chip-wide coefficient kernel + one workgroup per
-        //             (angle, wavelength) running the layer's Gauss-Seidel levels on an LDS tile;
-        //   "tiles"   ONE launch: each (angle, wavelength) workgroup walks all layers itself.
-        // tiles needs layers of at most 8192 sites, steps of at most 12 288 (fp64) / 18 432 (fp32
-        // storage) and both <= 255 levels per layer.  Default when that holds: tiles while the
-        // (angle, wavelength) problems fit one round of workgroups (<= 256) AND the layers are small
-        // (<= 4096 sites: the one launch has no per-layer launch cost -- C2, 2738-site layers: 1.2 ms
-        // vs 1.8 ms on steps, which is host-launch-bound there); steps otherwise (its chip-wide
-        // coefficient kernel wins once a layer holds more than a few sites per thread -- 1M sites x
-        // 12 angles x 1 λ: 5.1 vs 7.8 ms; C4: 11.8 vs 20.5 ms); levels when the grid does not fit.
-        // VRT_PATH selects one explicitly.
-        const bool tiles_ok = steps_ok && !f32 && p->tile_max_layer_size <= 8192;
-        int path = 1;
-        if (tiles_ok && (int64_t)p->A * nlam <= 2 && p->tile_max_layer_size <= 4096)
+    int path = p->tune.path;
+    if (x.native) {
+        // sweep-order planes are the storage order of steps (fp64, one pair per block: native_planes_ok) and patches
+        if (p->A == 0) return fail(VRT_EINVAL, "sweep-order S and J: the plan has no active angle");
+        if (path == 1 || path == 2 || (f32 && path == 3)) path = 0;     // (VRT_PATH = levels / tiles does not apply)
+        if (path == 0) path = p->patch_ok ? 4 : steps_ok ? 3 : 0;
+        if (path == 0) return fail(VRT_EINVAL, "sweep-order S and J need a layer path: the grid does not fit the steps or patch kernels");
+    } else if (path == 0) {
+        path = 1;
+        if (tiles_ok && (int64_t)p->A * x.nlam <= 2 && p->tile_max_layer_size <= 4096)
             path = 2;                 // a single solve on small layers: two launches in all
         else if (p->patch_ok)
             path = 4;
         else if (steps_ok)
             path = 3;
-        if (p->tune.path) path = p->tune.path;
-        // the native layout IS the storage order of the layer paths
-        // (laid out for the patch path when the grid fits it: then the steps path can only read it with one pair per block)
-        if (alpha_mode == VRT_ALPHA_ANGLE_NATIVE) {
-            const bool steps_can = steps_ok && !f32 && native_lg(p, f32) == 0;
-            if (path == 3 && !steps_can) path = 4;
-            else if (path != 3 && path != 4) path = p->patch_ok ? 4 : 3;
-        }
-        if (p->A == 0) path = 1;      // nothing to solve (every direction skipped): J = 0 via the level path
-        if ((path == 3 && !steps_ok) || (path == 2 && !tiles_ok) || (path == 4 && !p->patch_ok))
-            return fail(VRT_EINVAL, "VRT_PATH = tiles / steps / patches but the grid (or the fp32 storage type) does not fit those kernels");
-        if (path != 1) {
-            p->last_path = path;
-            return execute_tiles(p, nlam, ld, dS_, dalpha_, alpha_mode, dI0_up_, dI0_down_, weights, dJ_,
-                                 dI_out_, st, f32);
-        }
-        p->last_path = 1;
     }
+    // the native per-angle alpha IS the storage order of the layer paths
+    // (laid out for the patch path when the grid fits it: then the steps path can only read it with one pair per block)
+    if (am == VRT_ALPHA_ANGLE_NATIVE) {
+        const bool steps_can = steps_ok && !f32 && native_lg(p, f32) == 0;
+        if (path == 3 && !steps_can) path = 4;
+        else if (path != 3 && path != 4) path = p->patch_ok ? 4 : 3;
+    }
+    if (p->A == 0) path = 1;      // nothing to solve (every direction skipped): J = 0 via the level path
+    if ((path == 3 && !steps_ok) || (path == 2 && !tiles_ok) || (path == 4 && !p->patch_ok))
+        return fail(VRT_EINVAL, "VRT_PATH = tiles / steps / patches but the grid (or the fp32 storage type) does not fit those kernels");
+    return path;
+}
+
+// the level path: the merged level schedule of all angles, one launch per dependency level (caller-layout calls only)
+static int execute_levels(vrt_plan *p, const ExecArgs &x)
+{
+    int rc;
     if ((rc = ensure_level_schedule(p))) return rc;
-    const size_t need = (size_t)std::max(1, p->A) * (size_t)n * (size_t)nlam;
-    if ((rc = ensure(p->d_I, p->I_cap, f32 ? (need + 1) / 2 : need))) return rc;
-    p->I_ld = nlam;
+    const size_t need = (size_t)std::max(1, p->A) * (size_t)p->g->n * (size_t)x.nlam;
+    if ((rc = ensure(p->d_I, p->I_cap, x.f32 ? (need + 1) / 2 : need))) return rc;
+    p->I_ld = x.nlam;
     SweepArgs sa;
-    sa.f32 = f32;
-    sa.n = n;
-    sa.nlam = nlam;
-    sa.ldS = ld;
-    sa.ldA = alpha_mode == VRT_ALPHA_SITE ? 1 : ld;
-    sa.ldI = nlam;
-    sa.S = dS_;
-    sa.alpha = dalpha_;
-    sa.alpha_mode = alpha_mode;
+    sa.f32 = x.f32;
+    sa.n = p->g->n;
+    sa.nlam = x.nlam;
+    sa.ldS = x.ld;
+    sa.ldA = x.alpha_mode == VRT_ALPHA_SITE ? 1 : x.ld;
+    sa.ldI = x.nlam;
+    sa.S = x.S;
+    sa.alpha = x.alpha;
+    sa.alpha_mode = x.alpha_mode;
     sa.I = p->d_I;
-    if ((rc = launch_boundary(p, sa, dI0_up_, dI0_down_, st))) return rc;
-    VRT_HIP_TRY(hipEventRecord(p->ev0, st));
-    {
-        // The level sequence is hundreds to thousands of short dependent launches.  VRT_GRAPH=1
-        // captures it once into a hipGraph and replays it while the arguments stay the same.
-        // Measured on MI355X it changes nothing (C2: 7.57 vs 7.56 ms, C4: 24.87 vs 24.91 ms --
-        // the launches are bound by the dependent-load latency inside each level, not by the
-        // host), so eager launches stay the default.
-        const bool use_graph = p->tune.graph == 1;
-        SweepKey key;
-        key.nlam = sa.nlam; key.ldS = sa.ldS; key.ldA = sa.ldA; key.ldI = sa.ldI;
-        key.S = sa.S; key.alpha = sa.alpha; key.I = sa.I; key.alpha_mode = sa.alpha_mode; key.f32 = sa.f32;
-        bool replayed = false;
-        if (use_graph) {
-            if (!(p->graph_exec && p->graph_key == key)) {
-                if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
-                p->graph_exec = nullptr;
-                hipGraph_t graph = nullptr;
-                if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                    const int rc2 = launch_sweep_levels(p, sa, st, &p->last_launches);
-                    const hipError_t e = hipStreamEndCapture(st, &graph);
-                    if (rc2 == VRT_OK && e == hipSuccess && graph &&
-                        hipGraphInstantiate(&p->graph_exec, graph, nullptr, nullptr, 0) == hipSuccess)
-                        p->graph_key = key;
-                    else
-                        p->graph_exec = nullptr;
-                    if (graph) (void)hipGraphDestroy(graph);
-                }
-                (void)hipGetLastError();
-            }
-            if (p->graph_exec && hipGraphLaunch(p->graph_exec, st) == hipSuccess) replayed = true;
-        }
-        if (!replayed && (rc = launch_sweep_levels(p, sa, st, &p->last_launches))) return rc;
-    }
-    VRT_HIP_TRY(hipEventRecord(p->ev1, st));
+    if ((rc = launch_boundary(p, sa, x.I0[0], x.I0[1], x.st))) return rc;
+    VRT_HIP_TRY(hipEventRecord(p->ev0, x.st));
+    if ((rc = launch_sweep_levels(p, sa, x.st, &p->last_launches))) return rc;
+    VRT_HIP_TRY(hipEventRecord(p->ev1, x.st));
     p->ev_valid = true;
-    if (dJ) {
+    if (x.J) {
         double wact[kMaxAngles];
-        for (int a = 0; a < p->A; a++) wact[a] = weights[p->user_of_active[(size_t)a]];
-        if ((rc = launch_reduce_J(p, sa, wact, dJ_, ld, st))) return rc;
+        for (int a = 0; a < p->A; a++) wact[a] = x.weights[p->user_of_active[(size_t)a]];
+        if ((rc = launch_reduce_J(p, sa, wact, x.J, x.ld, x.st))) return rc;
     }
-    if (dI_out && (rc = launch_copy_I_out(p, sa, dI_out_, ld, st))) return rc;
+    if (x.I_out && (rc = launch_copy_I_out(p, sa, x.I_out, x.ld, x.st))) return rc;
     return VRT_OK;
 }
 
-int execute_native_locked(vrt_plan *p, int64_t nlam, const void *dS_up, const void *dS_down, const void *dalpha, int alpha_mode,
-                          const void *dI0_up, const void *dI0_down, const double *weights, void *dJ_up, void *dJ_down,
-                          hipStream_t st, bool f32)
+int execute_locked(vrt_plan *p, const ExecArgs &x)
 {
-    int rc = native_planes_ok(p, f32);
+    const int path = choose_path(p, x);
+    if (path < 0) return path;
+    int rc = use_device(p->g->device);
     if (rc) return rc;
-    if ((p->n_up > 0 && !dS_up) || (p->n_down > 0 && !dS_down)) return fail(VRT_EINVAL, "S of a direction with angles must not be NULL");
-    if (!dJ_up != !dJ_down) return fail(VRT_EINVAL, "J_up and J_down must be given together (or both NULL)");
-    if (alpha_mode != VRT_ALPHA_SITE && alpha_mode != VRT_ALPHA_ANGLE_NATIVE && alpha_mode != VRT_ALPHA_SITE_LAM_NATIVE)
-        return fail(VRT_EINVAL, "sweep-order S goes with alpha per site (0), native per angle (3) or per (site, wavelength) in sweep order (4): the other layouts carry the caller's leading dimension");
-    // (the level path -- grids whose schedule does not fit the layer kernels -- keeps the caller's layout)
-    const int keep = p->tune.path;
-    if (keep == 1 || keep == 2 || (f32 && keep == 3)) p->tune.path = 0;
-    p->nat_S[0] = dS_up; p->nat_S[1] = dS_down;
-    p->nat_J[0] = dJ_up; p->nat_J[1] = dJ_down;
-    p->nat_mode = true;
-    const void *anyS = dS_up ? dS_up : dS_down;
-    rc = execute_dev_locked(p, nlam, (nlam + 1) / 2 * 2, anyS, dalpha, alpha_mode, dI0_up, dI0_down, weights, dJ_up, nullptr, st, f32);
-    p->nat_mode = false;
-    p->nat_S[0] = p->nat_S[1] = nullptr;
-    p->nat_J[0] = p->nat_J[1] = nullptr;
-    p->tune.path = keep;
-    if (!rc && p->last_path != 3 && p->last_path != 4) return fail(VRT_EINVAL, "sweep-order S and J: the plan did not run on a layer path");
-    return rc;
+    p->last_path = path;
+    return path == 1 ? execute_levels(p, x) : execute_layers(p, x, path);
 }
 
 // the float forms of the sweep-order entry points share this: lock, device, layout check, then `fn`
@@ -1385,8 +1350,8 @@ int vrt_plan_execute_dev(vrt_plan *p, int64_t nlam, int64_t ld, const double *dS
     if (!p) return fail(VRT_EINVAL, "NULL plan");
     try {
         std::lock_guard<std::mutex> lock(p->mu);
-        return execute_dev_locked(p, nlam, ld, dS, dalpha, alpha_mode, dI0_up, dI0_down,
-                                  weights_host, dJ, dI_out, (hipStream_t)stream);
+        return execute_locked(p, caller_args(nlam, ld, dS, dalpha, alpha_mode, dI0_up, dI0_down, weights_host, dJ, dI_out,
+                                             (hipStream_t)stream, false));
     } catch (const std::bad_alloc &) {
         return fail(VRT_ENOMEM, "out of host memory");
     } catch (...) {
@@ -1457,8 +1422,8 @@ int vrt_plan_execute_native_dev(vrt_plan *p, int64_t nlam, const double *dS_up, 
     if (!p) return fail(VRT_EINVAL, "NULL plan");
     try {
         std::lock_guard<std::mutex> lock(p->mu);
-        return execute_native_locked(p, nlam, dS_up, dS_down, dalpha, alpha_mode, dI0_up, dI0_down, weights_host, dJ_up, dJ_down,
-                                     (hipStream_t)stream);
+        return execute_locked(p, native_args(nlam, dS_up, dS_down, dalpha, alpha_mode, dI0_up, dI0_down, weights_host, dJ_up,
+                                             dJ_down, (hipStream_t)stream, false));
     } catch (const std::bad_alloc &) {
         return fail(VRT_ENOMEM, "out of host memory");
     } catch (...) {
@@ -1493,8 +1458,8 @@ int vrt_plan_execute_native_dev_f32(vrt_plan *p, int64_t nlam, const float *dS_u
     if (!p) return fail(VRT_EINVAL, "NULL plan");
     try {
         std::lock_guard<std::mutex> lock(p->mu);
-        return execute_native_locked(p, nlam, dS_up, dS_down, dalpha, alpha_mode, dI0_up, dI0_down, weights_host, dJ_up, dJ_down,
-                                     (hipStream_t)stream, /*f32=*/true);
+        return execute_locked(p, native_args(nlam, dS_up, dS_down, dalpha, alpha_mode, dI0_up, dI0_down, weights_host, dJ_up,
+                                             dJ_down, (hipStream_t)stream, /*f32=*/true));
     } catch (const std::bad_alloc &) {
         return fail(VRT_ENOMEM, "out of host memory");
     } catch (...) {
@@ -1511,8 +1476,8 @@ int vrt_plan_execute_dev_f32(vrt_plan *p, int64_t nlam, int64_t ld, const float 
     if (!p) return fail(VRT_EINVAL, "NULL plan");
     try {
         std::lock_guard<std::mutex> lock(p->mu);
-        return execute_dev_locked(p, nlam, ld, dS, dalpha, alpha_mode, dI0_up, dI0_down, weights_host,
-                                  dJ, dI_out, (hipStream_t)stream, /*f32=*/true);
+        return execute_locked(p, caller_args(nlam, ld, dS, dalpha, alpha_mode, dI0_up, dI0_down, weights_host, dJ, dI_out,
+                                             (hipStream_t)stream, /*f32=*/true));
     } catch (const std::bad_alloc &) {
         return fail(VRT_ENOMEM, "out of host memory");
     } catch (...) {
@@ -1565,8 +1530,7 @@ int vrt_plan_execute(vrt_plan *p, int64_t nlam, int64_t ld, const double *S, con
             if ((rc = ensure(p->d_stage[5], p->stage_cap[5], nS * (size_t)p->n_angles_user))) return rc;
             dIo = p->d_stage[5];
         }
-        rc = execute_dev_locked(p, nlam, ld, p->d_stage[0], p->d_stage[1], alpha_mode, dU, dD,
-                                weights, dJ, dIo, st);
+        rc = execute_locked(p, caller_args(nlam, ld, p->d_stage[0], p->d_stage[1], alpha_mode, dU, dD, weights, dJ, dIo, st, false));
         if (rc) return rc;
         if (J) VRT_HIP_TRY(hipMemcpyAsync(J, dJ, sizeof(double) * nS, hipMemcpyDeviceToHost, st));
         if (I_out)   // (nlam, n, n_angles) with leading dimension ld, skipped angles already zeroed

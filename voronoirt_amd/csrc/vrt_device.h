@@ -246,7 +246,7 @@ struct StepArgs {
     const int32_t *t_rank_s;  // single-wavelength level kernel: storage position -> sorted index
     const uint32_t *t_loc_ss; //   and the upwind tile slots in sorted terms
     int debug_skip_levels;    // diagnostics only (VRT_DEBUG_SKIP_LEVELS=1): wrong results
-    int debug_flags;          // diagnostics only (VRT_DEBUG_FLAGS bit mask): wrong results, see execute_tiles
+    int debug_flags;          // diagnostics only (VRT_DEBUG_FLAGS bit mask): wrong results, see run_steps (vrt_layers.hip)
 };
 
 __device__ __forceinline__ double2 ld2(const double2 *base, unsigned idx)

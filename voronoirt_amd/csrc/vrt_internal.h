@@ -119,7 +119,6 @@ struct Tuning {
     int step_group_dir = 1;       // VRT_STEP_GROUP_DIR: one direction per stream when balanced
     int tile_wide = 1;            // VRT_TILE_WIDE, VRT_TILE_PRE: variants of the persistent tile path
     int tile_pre = 1;
-    int graph = 0;                // VRT_GRAPH: replay the level launches as a hipGraph
     int patch_K = 1, patch_NT = 512;   // VRT_PATCH_K, VRT_PATCH_NT: entries per thread, threads (plan creation only)
     int patch_own = 0;            // VRT_PATCH_OWN: owned sites per patch at most (0: as many as fit; creation only)
     int patch_Q = 1;              // VRT_PATCH_Q: wavelength pairs a patch workgroup solves at a time
@@ -149,18 +148,51 @@ void tuning_from_env(Tuning &t);
 // VRT_OK, or VRT_EINVAL for an unknown name / bad value; `created`: the plan exists already (creation-only options fail)
 int tuning_set(Tuning &t, const char *name, const char *value, bool created);
 
-// arguments a captured level-launch graph was recorded with
-struct SweepKey {
-    int64_t nlam = -1, ldS = 0, ldA = 0, ldI = 0;
-    const void *S = nullptr, *alpha = nullptr, *I = nullptr;
-    int alpha_mode = -1;
-    bool f32 = false;
-    bool operator==(const SweepKey &o) const
-    {
-        return nlam == o.nlam && ldS == o.ldS && ldA == o.ldA && ldI == o.ldI && S == o.S &&
-               alpha == o.alpha && I == o.I && alpha_mode == o.alpha_mode && f32 == o.f32;
-    }
+// The arguments of one execute, filled in by its entry point (vrt_plan_execute[_dev][_f32], vrt_plan_execute_native_dev[_f32],
+// the Λ-iteration and the multi-device session).  Caller-layout calls pass S, J and I_out as (n, ld) rows; native calls
+// (vrt_plan_execute_native_dev) pass S and J as per-direction sweep-order planes (index 0 up, 1 down), read and written in
+// place by the layer paths.  Pointers are device pointers; double, or float when f32.
+struct ExecArgs {
+    int64_t nlam = 0, ld = 0;
+    const void *S = nullptr;                      // caller layout
+    const void *S_nat[2] = {nullptr, nullptr};    // sweep order (native)
+    const void *alpha = nullptr;
+    int alpha_mode = 0;
+    const void *I0[2] = {nullptr, nullptr};       // boundary intensities of the up / down sweeps
+    const double *weights = nullptr;              // host, per user angle
+    void *J = nullptr;                            // caller layout
+    void *J_nat[2] = {nullptr, nullptr};          // sweep order (native)
+    void *I_out = nullptr;                        // caller layout, per user angle
+    bool native = false;
+    bool f32 = false;                             // fp32 storage of S, α, I, J (arithmetic stays fp64)
+    hipStream_t st = nullptr;
+    bool wants_J() const { return native ? J_nat[0] != nullptr : J != nullptr; }
 };
+inline ExecArgs caller_args(int64_t nlam, int64_t ld, const void *S, const void *alpha, int alpha_mode, const void *I0_up,
+                            const void *I0_down, const double *weights, void *J, void *I_out, hipStream_t st, bool f32)
+{
+    ExecArgs x;
+    x.nlam = nlam; x.ld = ld;
+    x.S = S;
+    x.alpha = alpha; x.alpha_mode = alpha_mode;
+    x.I0[0] = I0_up; x.I0[1] = I0_down;
+    x.weights = weights;
+    x.J = J; x.I_out = I_out;
+    x.f32 = f32;
+    x.st = st;
+    return x;
+}
+inline ExecArgs native_args(int64_t nlam, const void *S_up, const void *S_down, const void *alpha, int alpha_mode,
+                            const void *I0_up, const void *I0_down, const double *weights, void *J_up, void *J_down,
+                            hipStream_t st, bool f32)
+{
+    ExecArgs x = caller_args(nlam, (nlam + 1) / 2 * 2, nullptr, alpha, alpha_mode, I0_up, I0_down, weights, nullptr, nullptr,
+                             st, f32);     // (ld: the planes' wavelength count, padded to whole pairs)
+    x.S_nat[0] = S_up; x.S_nat[1] = S_down;
+    x.J_nat[0] = J_up; x.J_nat[1] = J_down;
+    x.native = true;
+    return x;
+}
 
 }  // namespace vrt
 
@@ -307,21 +339,12 @@ struct vrt_plan {
     int patch_work_groups = 0;
     hipStream_t step_stream[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t step_fork = nullptr, step_join[4] = {nullptr, nullptr, nullptr, nullptr};
-    int last_path = 0;                   // 1 = level kernels, 2 = layer tiles
-    // hipGraph of the level-launch sequence, replayed while the arguments stay the same
-    hipGraphExec_t graph_exec = nullptr;
-    vrt::SweepKey graph_key;
+    int last_path = 0;                   // path of the last execute (vrt_plan_last_path): 1 levels, 2 tiles, 3 steps, 4 patches
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool ev_valid = false;
     std::vector<vrt::CopyLane> copy_lanes;      // host-pointer entry points (ensure_copy_lanes)
     hipEvent_t copy_done = nullptr;
     int64_t last_launches = 0;
-    // sweep-order ("native") S and J of the call in progress (vrt_plan_execute_native_dev; set and cleared under `mu`):
-    // per sweep direction (0 up, 1 down) a plane set [pairs][n][2] in that direction's storage order, read / written in
-    // place by the layer paths instead of the workspaces behind the layout changes
-    const void *nat_S[2] = {nullptr, nullptr};
-    void *nat_J[2] = {nullptr, nullptr};
-    bool nat_mode = false;
     std::mutex mu;
 };
 
@@ -442,9 +465,8 @@ int launch_populations_from_shares(vrt_grid *g, const double *d_shares, const do
 
 // ---- entry-point internals shared with vrt_lambda.cpp (vrt_api.cpp) ---------------------------------
 int use_device(int device);
-int execute_dev_locked(vrt_plan *p, int64_t nlam, int64_t ld, const void *dS, const void *dalpha, int alpha_mode,
-                       const void *dI0_up, const void *dI0_down, const double *weights, void *dJ, void *dI_out,
-                       hipStream_t st, bool f32 = false);
+// one execute (caller holds p->mu): checks the arguments, chooses the path, runs it
+int execute_locked(vrt_plan *p, const ExecArgs &x);
 
 // ---- layer paths (vrt_tables.hip, vrt_layers.hip) ----------------------------------------------------------
 int ensure_step_tables(vrt_plan *p);     // sorted-slot tables of the steps / tiles paths, on first use (vrt_api.cpp)
@@ -467,13 +489,8 @@ int J_from_native_f32(vrt_plan *p, int64_t nlam, int64_t ld, const float *dJ_up,
 int planes_to_native(vrt_plan *p, int64_t nlam, int64_t ld, const double *din, double *out_up, double *out_down, hipStream_t st);
 int plane_from_native(vrt_plan *p, int dir_index, int64_t nlam, int64_t ld, const double *din, double *dout, hipStream_t st);
 int J_from_native(vrt_plan *p, int64_t nlam, int64_t ld, const double *dJ_up, const double *dJ_down, double *dJ, hipStream_t st);
-// the sweep with S read from / J reduced into the caller's sweep-order planes (caller holds p->mu)
-int execute_native_locked(vrt_plan *p, int64_t nlam, const void *dS_up, const void *dS_down, const void *dalpha, int alpha_mode,
-                          const void *dI0_up, const void *dI0_down, const double *weights, void *dJ_up, void *dJ_down,
-                          hipStream_t st, bool f32 = false);
-int execute_tiles(vrt_plan *p, int64_t nlam, int64_t ld, const void *dS, const void *dalpha,
-                  int alpha_mode, const void *dI0_up, const void *dI0_down,
-                  const double *weights_user, void *dJ, void *dI_out, hipStream_t st, bool f32);
+// one execute on a layer path (2 tiles, 3 steps, 4 patches) that choose_path (vrt_api.cpp) chose for `x`
+int execute_layers(vrt_plan *p, const ExecArgs &x, int path);
 int64_t steps_max_layer(bool f32);   // largest layer the layer-step level kernels hold
 
 // ---- fused patch path (vrt_patch.hip) ----------------------------------------------------------------

@@ -287,9 +287,9 @@ int vrt_plan_execute_line(vrt_plan *p, int64_t nlam, int64_t ld, const double *l
 #ifdef VRT_DIAG
         const auto t2 = std::chrono::steady_clock::now();
 #endif
-        // (execute_dev_locked reuses ws_AA only for the CALLER-layout per-angle alpha, not for the native one)
-        rc = execute_dev_locked(p, nlam, nlam, p->d_stage[0], p->ws_AA, VRT_ALPHA_ANGLE_NATIVE, dU, dD, weights,
-                                p->d_stage[4], nullptr, st);
+        // (the execute reuses ws_AA only for the CALLER-layout per-angle alpha, not for the native one)
+        rc = execute_locked(p, caller_args(nlam, nlam, p->d_stage[0], p->ws_AA, VRT_ALPHA_ANGLE_NATIVE, dU, dD, weights,
+                                           p->d_stage[4], nullptr, st, false));
         if (rc) return rc;
         VRT_HIP_TRY(hipEventRecord(p->copy_done, st));
 #ifdef VRT_DIAG
@@ -443,8 +443,8 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
         if (s->native) {
             // J_λ (:84-111) from the sweep-order S into the sweep-order J; S_new and the criterion (:261-263, :325-349: the old
             // S is read from the plane the new one is written to); R and the populations (:269, :274) from the same J planes
-            if ((rc = execute_native_locked(p, nlam, s->d_S_nat[0], s->d_S_nat[1], s->d_native, VRT_ALPHA_ANGLE_NATIVE, s->d_I0, nullptr,
-                                            s->weights.data(), s->d_J_nat[0], s->d_J_nat[1], st)))
+            if ((rc = execute_locked(p, native_args(nlam, s->d_S_nat[0], s->d_S_nat[1], s->d_native, VRT_ALPHA_ANGLE_NATIVE, s->d_I0,
+                                                    nullptr, s->weights.data(), s->d_J_nat[0], s->d_J_nat[1], st, false))))
                 return rc;
             if ((rc = launch_lambda_update_native(g, nlam, s->d_J_nat[0], s->d_J_nat[1], s->d_B_up, s->d_eps, s->d_S_nat[0],
                                                   s->d_S_nat[1], s->d_scalars, st)))
@@ -456,8 +456,8 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
                 return rc;
         } else {
         // J_λ (:84-111)
-        if ((rc = execute_dev_locked(p, nlam, nlam, s->d_S_old, s->d_native, VRT_ALPHA_ANGLE_NATIVE, s->d_I0, nullptr,
-                                     s->weights.data(), s->d_J, nullptr, st)))
+        if ((rc = execute_locked(p, caller_args(nlam, nlam, s->d_S_old, s->d_native, VRT_ALPHA_ANGLE_NATIVE, s->d_I0, nullptr,
+                                                s->weights.data(), s->d_J, nullptr, st, false))))
             return rc;
         // S_new = (1 - ε) J + ε B_0 and the criterion's scalar (:261-263, :325-349)
         if ((rc = launch_lambda_update(n, nlam, nlam, s->d_J, s->d_B0, s->d_eps, s->d_S_old, s->d_S_new, s->d_scalars, st)))

@@ -447,7 +447,7 @@ int vrt_multi_execute_line(vrt_multi *mm, int64_t nlam, int64_t ld, const double
             }
             if (me.rc) return;
             if ((me.rc = launch_line_opacity(plan, nb, d_lam, lambda0, c0, d_vel, d_dop, d_gam, d_str, d_ac, me.dA, st)) ||
-                (me.rc = execute_dev_locked(plan, nb, nb, me.dS, me.dA, VRT_ALPHA_ANGLE_NATIVE, dU, dD, weights, me.dJ, nullptr, st))) {
+                (me.rc = execute_locked(plan, caller_args(nb, nb, me.dS, me.dA, VRT_ALPHA_ANGLE_NATIVE, dU, dD, weights, me.dJ, nullptr, st, false)))) {
                 me.err = vrt_last_error();
                 return;
             }
@@ -696,8 +696,8 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
                 // the block's S and J stay in sweep order: no layout change, no copy of S (the update reads the old S where it writes the new)
                 rc = launch_line_terms(n, l.d_gamma_static, l.d_gamma_unsold, l.d_pops, s->strength_const, s->Bij, s->Bji, l.d_gamma, l.d_strength, st);
                 if (!rc) rc = launch_line_opacity(p, nb, l.d_small + l.l0, s->lambda0, s->c0, l.d_velocity, l.d_doppler, l.d_gamma, l.d_strength, l.d_alpha_cont, l.d_native, st);
-                if (!rc) rc = execute_native_locked(p, nb, l.d_S_nat[0], l.d_S_nat[1], l.d_native, VRT_ALPHA_ANGLE_NATIVE, l.d_I0, nullptr, s->weights.data(),
-                                                    l.d_J_nat[0], l.d_J_nat[1], st);
+                if (!rc) rc = execute_locked(p, native_args(nb, l.d_S_nat[0], l.d_S_nat[1], l.d_native, VRT_ALPHA_ANGLE_NATIVE, l.d_I0, nullptr,
+                                                            s->weights.data(), l.d_J_nat[0], l.d_J_nat[1], st, false));
                 if (!rc) rc = launch_lambda_update_native(g, nb, l.d_J_nat[0], l.d_J_nat[1], l.d_B_up, l.d_eps, l.d_S_nat[0], l.d_S_nat[1], l.d_scalars, st);
             } else if (nb > 0) {
                 if (hipMemcpyAsync(l.d_S_old, l.d_S_new, sizeof(double) * (size_t)n * (size_t)nb, hipMemcpyDeviceToDevice, st) != hipSuccess)
@@ -706,7 +706,7 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
                 if (!rc) rc = launch_line_terms(n, l.d_gamma_static, l.d_gamma_unsold, l.d_pops, s->strength_const, s->Bij, s->Bji, l.d_gamma, l.d_strength, st);
                 if (!rc) rc = launch_line_opacity(p, nb, l.d_small + l.l0, s->lambda0, s->c0, l.d_velocity, l.d_doppler, l.d_gamma, l.d_strength, l.d_alpha_cont, l.d_native, st);
                 // J_λ of this block (:84-111)
-                if (!rc) rc = execute_dev_locked(p, nb, nb, l.d_S_old, l.d_native, VRT_ALPHA_ANGLE_NATIVE, l.d_I0, nullptr, s->weights.data(), l.d_J, nullptr, st);
+                if (!rc) rc = execute_locked(p, caller_args(nb, nb, l.d_S_old, l.d_native, VRT_ALPHA_ANGLE_NATIVE, l.d_I0, nullptr, s->weights.data(), l.d_J, nullptr, st, false));
                 // S_new = (1 - ε) J + ε B_0 and this block's share of the criterion (:261-263, :325-349)
                 if (!rc) rc = launch_lambda_update(n, nb, nb, l.d_J, l.d_B0, l.d_eps, l.d_S_old, l.d_S_new, l.d_scalars, st);
             } else {
