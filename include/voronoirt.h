@@ -334,6 +334,55 @@ int vrt_delaunay_up(vrt_grid *g, const double k[3], const double *S, const doubl
 int vrt_delaunay_down(vrt_grid *g, const double k[3], const double *S, const double *I0,
                       int64_t nI0, const double *alpha, int n_sweeps, double *I_out);
 
+/* ---- resampling between the sites and regular rasters --------------------------------------------
+ * The two ends of every reference run: initialise (src/voronoi_utils.jl:687-707, trilinear src/functions.jl:207-248) puts a
+ * raster's fields on the sites; Voronoi_to_Raster (:407-617) and Voronoi_to_Raster_inv_dist (:773-816, inv_dist_itp
+ * :848-860) bring site fields back to a raster, as the searchlight images do (compare_searchlight.jl:116-141).
+ *   distance  d = sqrt((dz*dz + dx*dx) + dy*dy) in (z, x, y); VRT_METRIC_PERIODIC_XY takes dx = qx - px, then
+ *             dx -= Lx if dx > Lx/2, dx += Lx if dx < -Lx/2 (the same for y), and first wraps a query x outside
+ *             [x_min, x_max] to x - Lx*floor((x - x_min)/Lx) (y likewise), so ghost-cell axes (periodic_borders) work
+ *   nearest   the smallest (d, id): on a tie the lowest site id
+ *   k = 2     the two smallest (d, id) in that order
+ *   inv_dist  f = (v1/d1 + v2/d2)/(1/d1 + 1/d2) in inv_dist_itp's order (inv = 1/d; avg += inv; f += v*inv; f/avg);
+ *             d1 == 0 gives v1 (the reference's Inf/Inf = NaN there)
+ *   trilinear the reference's: interval = searchsortedfirst(axis, v) - 1 clamped to [0, n-2] (a site at exactly z[1]
+ *             is no BoundsError), x then y then z with its expressions
+ * PRECONDITION of the nearest search: the neighbour rows are the Voronoi neighbours of the sites in the x/y-periodic box
+ * (vrt_tessellate, voro++, read_cell of a voro++ file; a row missing a neighbour that lists it is completed).  It walks to
+ * ever closer neighbours from a seed site, so on other
+ * graphs (e.g. jittered lattices with fixed lists) it ends at a local minimum; a walk that exceeds its step or tie-set cap
+ * fails the call with VRT_EGRID.  Queries: z in [z_min, z_max]; x, y in the box under VRT_METRIC_EUCLIDEAN.
+ * Every argument is checked before the device is touched (a host-only grid: VRT_EINVAL or VRT_ENODEVICE).  The calls
+ * synchronise (a failed walk is reported as a status).  Option VRT_NEAREST_CELLS = auto | cells per axis
+ * (vrt_grid_set_option): the cell list that seeds the walks; results never depend on it. */
+#define VRT_METRIC_EUCLIDEAN   0  /* plain distance in (z, x, y): the reference's KDTree (voronoi_utils.jl:437-442) */
+#define VRT_METRIC_PERIODIC_XY 1  /* minimum image in x and y: the geometry of the tessellation itself            */
+#define VRT_RASTER_NEAREST     1  /* Voronoi_to_Raster: value of the nearest site                                  */
+#define VRT_RASTER_INV_DIST2   2  /* Voronoi_to_Raster_inv_dist: the two nearest sites, weights 1/d (p = 1, n_k = 2)  */
+/* k = 1 or 2 nearest sites of nq points q (3, nq); idx (k, nq) 1-based, dist (k, nq) may be NULL.  Host pointers. */
+int vrt_grid_nearest(vrt_grid *g, int64_t nq, const double *q_zxy, int metric, int k, int64_t *idx, double *dist);
+/* sites -> raster.  Fields (nf, n) with leading dimension ld (the layout of S in vrt_plan_execute_dev); raster
+ * (nz, nx, ny, nf), element [iz + nz*(ix + nx*(iy + ny*f))]: per field the array layout vrt_regular_execute_dev reads
+ * (S_stride = nz*nx*ny).  Axes (ascending, >= 1 point each) on the host; fields and raster on the device. */
+int vrt_grid_to_raster_dev(vrt_grid *g, int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x,
+                           const double *y, int metric, int mode, int64_t nf, int64_t ld, const double *d_fields,
+                           double *d_raster, void *stream);
+/* raster -> sites, trilinear; axes >= 2 points, every site inside their ranges; fields (nf, n) written with ld */
+int vrt_raster_to_grid_dev(vrt_grid *g, int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x,
+                           const double *y, int64_t nf, const double *d_raster, int64_t ld, double *d_fields,
+                           void *stream);
+/* the same from host arrays, staged through the device */
+int vrt_grid_to_raster(vrt_grid *g, int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x,
+                       const double *y, int metric, int mode, int64_t nf, int64_t ld, const double *fields,
+                       double *raster);
+int vrt_raster_to_grid(vrt_grid *g, int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x,
+                       const double *y, int64_t nf, const double *raster, int64_t ld, double *fields);
+/* the last nearest search of the grid (vrt_grid_nearest or vrt_grid_to_raster*): HIP-event times of the walk and of the
+ * gather (0 for vrt_grid_nearest), queries, walk steps summed over the queries, queries that took the Euclidean
+ * cell-list search; any pointer may be NULL */
+int vrt_grid_raster_stats(const vrt_grid *g, double *nearest_ms, double *gather_ms, int64_t *queries,
+                          int64_t *walk_steps, int64_t *fallbacks);
+
 /* ---- Λ-iteration epilogue on the device (the physics-free part) -----------
  * S_new[l,i] = (1 - eps[i]) J[l,i] + eps[i] B[l,i]           (src/lambda_iteration.jl:261-263)
  * *max_rel_change = max |1 - S_old/S_new|, NaN if any term is NaN  (criterion, :325-349)

@@ -8,11 +8,14 @@ load the shared library; the first call does, and fails loudly if it is missing.
 from .api import (Delaunay_downII, Delaunay_upII, FormalPlan, J_lambda_voronoi, VoronoiSites,  # noqa: F401
                   direction, quadrature_directions, read_cell, read_quadrature, voro, QUADRATURE_DIR,
                   short_characteristics_batch, short_characteristics_down, short_characteristics_up,
-                  RegularSolver, LineCase, Lambda_voronoi, Lambda_voronoi_host, J_lambda_voronoi_line, MultiDevicePlan)
+                  RegularSolver, LineCase, Lambda_voronoi, Lambda_voronoi_host, J_lambda_voronoi_line, MultiDevicePlan,
+                  nearest_sites, Voronoi_to_Raster, Voronoi_to_Raster_inv_dist, initialise, Voronoi_to_Raster_dev,
+                  initialise_dev, raster_stats)
 from ._lib import VrtError  # noqa: F401
 
 __all__ = ["Delaunay_upII", "Delaunay_downII", "FormalPlan", "J_lambda_voronoi", "VoronoiSites",
            "direction", "quadrature_directions", "read_cell", "read_quadrature", "voro", "VrtError",
            "QUADRATURE_DIR", "short_characteristics_up", "short_characteristics_down",
            "short_characteristics_batch", "RegularSolver", "LineCase", "Lambda_voronoi", "Lambda_voronoi_host",
-           "J_lambda_voronoi_line", "MultiDevicePlan"]
+           "J_lambda_voronoi_line", "MultiDevicePlan", "nearest_sites", "Voronoi_to_Raster",
+           "Voronoi_to_Raster_inv_dist", "initialise", "Voronoi_to_Raster_dev", "initialise_dev", "raster_stats"]

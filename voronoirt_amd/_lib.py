@@ -23,6 +23,8 @@ vp = ctypes.c_void_p
 
 VRT_OK, VRT_EINVAL, VRT_EGRID, VRT_ENODEVICE, VRT_ENOMEM, VRT_EIO = 0, -1, -2, -3, -4, -5
 ALPHA_SITE, ALPHA_SITE_LAM, ALPHA_ANGLE_SITE_LAM, ALPHA_ANGLE_NATIVE, ALPHA_SITE_LAM_NATIVE = 0, 1, 2, 3, 4
+METRIC_EUCLIDEAN, METRIC_PERIODIC_XY = 0, 1
+RASTER_NEAREST, RASTER_INV_DIST2 = 1, 2
 
 class LineCaseStruct(ctypes.Structure):
     """vrt_line_case of include/voronoirt.h"""
@@ -141,6 +143,14 @@ PROTOTYPES = {
     "vrt_regular_execute_dev": (ctypes.c_int, [vp, c_i64, p_dbl, p_int, vp, c_i64, vp, c_i64, c_i64, vp,
                                                ctypes.c_int, vp, vp]),
     "vrt_regular_last_solve_ms": (ctypes.c_int, [vp, p_dbl]),
+    "vrt_grid_nearest": (ctypes.c_int, [vp, c_i64, p_dbl, ctypes.c_int, ctypes.c_int, p_i64, p_dbl]),
+    "vrt_grid_to_raster_dev": (ctypes.c_int, [vp, c_i64, c_i64, c_i64, p_dbl, p_dbl, p_dbl, ctypes.c_int, ctypes.c_int,
+                                              c_i64, c_i64, vp, vp, vp]),
+    "vrt_raster_to_grid_dev": (ctypes.c_int, [vp, c_i64, c_i64, c_i64, p_dbl, p_dbl, p_dbl, c_i64, vp, c_i64, vp, vp]),
+    "vrt_grid_to_raster": (ctypes.c_int, [vp, c_i64, c_i64, c_i64, p_dbl, p_dbl, p_dbl, ctypes.c_int, ctypes.c_int,
+                                          c_i64, c_i64, p_dbl, p_dbl]),
+    "vrt_raster_to_grid": (ctypes.c_int, [vp, c_i64, c_i64, c_i64, p_dbl, p_dbl, p_dbl, c_i64, p_dbl, c_i64, p_dbl]),
+    "vrt_grid_raster_stats": (ctypes.c_int, [vp, p_dbl, p_dbl, p_i64, p_i64, p_i64]),
     "vrt_delaunay_up": (ctypes.c_int, [vp, p_dbl, p_dbl, p_dbl, c_i64, p_dbl, ctypes.c_int, p_dbl]),
     "vrt_delaunay_down": (ctypes.c_int, [vp, p_dbl, p_dbl, p_dbl, c_i64, p_dbl, ctypes.c_int, p_dbl]),
 }

@@ -732,6 +732,98 @@ class RegularSolver:
             pass
 
 
+# ---- resampling between the sites and regular rasters -------------------------------------------------
+def _metric(periodic: bool) -> int:
+    return _lib.METRIC_PERIODIC_XY if periodic else _lib.METRIC_EUCLIDEAN
+
+
+def nearest_sites(sites: VoronoiSites, points, k: int = 1, periodic: bool = False):
+    """The k (1 or 2) nearest sites of `points` (nq, 3) [z, x, y] by a walk over the grid's neighbour rows
+    (`vrt_grid_nearest`; exact when the rows are the Voronoi neighbours).  `periodic` = minimum image in x and y;
+    the default is the reference's Euclidean KDTree.  Ties go to the lowest id.  Returns (idx 1-based, dist), each
+    of shape (nq,) for k = 1 and (nq, 2) for k = 2."""
+    q = _f64(points).reshape(-1, 3)
+    nq = q.shape[0]
+    idx = np.zeros((nq, k), dtype=np.int64)
+    dist = np.zeros((nq, k))
+    check(_lib.load().vrt_grid_nearest(sites.handle, nq, _d(q), _metric(periodic), int(k), _i(idx), _d(dist)))
+    return (idx[:, 0], dist[:, 0]) if k == 1 else (idx, dist)
+
+
+def _axes(z, x, y):
+    return _f64(z).ravel(), _f64(x).ravel(), _f64(y).ravel()
+
+
+def _to_raster(sites, fields, z, x, y, periodic, mode):
+    z, x, y = _axes(z, x, y)
+    f = _f64(fields)
+    one = f.ndim == 1
+    f = f.reshape(sites.n, -1)
+    nf = f.shape[1]
+    out = np.zeros((nf, y.size, x.size, z.size))
+    check(_lib.load().vrt_grid_to_raster(sites.handle, z.size, x.size, y.size, _d(z), _d(x), _d(y), _metric(periodic),
+                                         mode, nf, nf, _d(f), _d(out)))
+    return out[0] if one else out
+
+
+def Voronoi_to_Raster(sites: VoronoiSites, fields, z, x, y, periodic: bool = False):
+    """Voronoi_to_Raster (src/voronoi_utils.jl:407-617): the value of the nearest site at every raster point.
+    fields (n, nf) or (n,); returns (nf, ny, nx, nz) -- Julia's (nz, nx, ny, nf) -- or (ny, nx, nz)."""
+    return _to_raster(sites, fields, z, x, y, periodic, _lib.RASTER_NEAREST)
+
+
+def Voronoi_to_Raster_inv_dist(sites: VoronoiSites, fields, z, x, y, periodic: bool = False):
+    """Voronoi_to_Raster_inv_dist (src/voronoi_utils.jl:773-816): the two nearest sites weighted by 1/d
+    (inv_dist_itp, p = 1); a raster point on a site takes that site's value (the reference's NaN).  Shapes as
+    Voronoi_to_Raster."""
+    return _to_raster(sites, fields, z, x, y, periodic, _lib.RASTER_INV_DIST2)
+
+
+def initialise(sites: VoronoiSites, z, x, y, raster_fields):
+    """initialise (src/voronoi_utils.jl:687-707): trilinear interpolation (src/functions.jl:207-248) of raster
+    fields (nf, ny, nx, nz) or (ny, nx, nz) onto the sites; returns (n, nf) or (n,)."""
+    z, x, y = _axes(z, x, y)
+    r = _f64(raster_fields)
+    one = r.ndim == 3
+    r = r.reshape(-1, y.size, x.size, z.size)
+    nf = r.shape[0]
+    out = np.zeros((sites.n, nf))
+    check(_lib.load().vrt_raster_to_grid(sites.handle, z.size, x.size, y.size, _d(z), _d(x), _d(y), nf, _d(r), nf,
+                                         _d(out)))
+    return out[:, 0] if one else out
+
+
+def Voronoi_to_Raster_dev(sites: VoronoiSites, z, x, y, nf: int, ld: int, d_fields: int, d_raster: int,
+                          inv_dist: bool = False, periodic: bool = False, stream: int = 0) -> None:
+    """Device form (`vrt_grid_to_raster_dev`): fields (n, ld) rows of which the first nf are used (torch
+    data_ptr()), raster (nf, ny, nx, nz) -- per field the S array RegularSolver.execute_dev reads.  Synchronises
+    `stream`."""
+    z, x, y = _axes(z, x, y)
+    mode = _lib.RASTER_INV_DIST2 if inv_dist else _lib.RASTER_NEAREST
+    check(_lib.load().vrt_grid_to_raster_dev(sites.handle, z.size, x.size, y.size, _d(z), _d(x), _d(y),
+                                             _metric(periodic), mode, int(nf), int(ld), d_fields, d_raster,
+                                             stream or None))
+
+
+def initialise_dev(sites: VoronoiSites, z, x, y, nf: int, d_raster: int, ld: int, d_fields: int, stream: int = 0) -> None:
+    """Device form of `initialise` (`vrt_raster_to_grid_dev`): raster (nf, ny, nx, nz) -> fields (n, ld), the first
+    nf of every row written.  Synchronises `stream`."""
+    z, x, y = _axes(z, x, y)
+    check(_lib.load().vrt_raster_to_grid_dev(sites.handle, z.size, x.size, y.size, _d(z), _d(x), _d(y), int(nf),
+                                             d_raster, int(ld), d_fields, stream or None))
+
+
+def raster_stats(sites: VoronoiSites) -> dict:
+    """The grid's last nearest search (`vrt_grid_raster_stats`): walk and gather kernel times (ms), queries, summed
+    walk steps, queries that took the Euclidean cell-list search."""
+    ms = (ctypes.c_double(), ctypes.c_double())
+    cnt = (ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64())
+    check(_lib.load().vrt_grid_raster_stats(sites.handle, ctypes.byref(ms[0]), ctypes.byref(ms[1]),
+                                            *[ctypes.byref(c) for c in cnt]))
+    return {"nearest_ms": ms[0].value, "gather_ms": ms[1].value, "queries": cnt[0].value,
+            "walk_steps": cnt[1].value, "fallbacks": cnt[2].value}
+
+
 def lambda_update_dev(sites: VoronoiSites, nlam: int, ld: int, dJ: int, dB: int, deps: int, dS_old: int,
                       dS_new: int, stream: int = 0) -> float:
     """Device-resident Λ-iteration epilogue: S_new = (1 - ε) J + ε B (src/lambda_iteration.jl:261-263)

@@ -130,6 +130,7 @@ static void free_grid(vrt_grid *g)
         delete c;
     }
     g->cache.clear();
+    raster_locator_free(g);
     dev_free(g->d_pos);
     dev_free(g->d_rowptr);
     dev_free(g->d_col);
@@ -1577,6 +1578,20 @@ int vrt_plan_set_option(vrt_plan *p, const char *name, const char *value)
 int vrt_grid_set_option(vrt_grid *g, const char *name, const char *value)
 {
     if (!g) return fail(VRT_EINVAL, "NULL grid");
+    if (name && std::string(name) == "VRT_NEAREST_CELLS") {         // the raster resampling's seeds (vrt_raster.hip)
+        if (!value) return fail(VRT_EINVAL, "NULL value");
+        const std::string v(value);
+        int64_t cells = 0;
+        if (v != "auto") {
+            char *end = nullptr;
+            const long long c = std::strtoll(v.c_str(), &end, 10);
+            if (v.empty() || *end || c < 1 || c > 256) return fail(VRT_EINVAL, "VRT_NEAREST_CELLS: auto or 1..256");
+            cells = c;
+        }
+        std::lock_guard<std::mutex> lock(g->mu);
+        g->nearest_cells = cells;
+        return VRT_OK;
+    }
     Tuning probe;
     int rc = tuning_set(probe, name, value, /*created=*/false);      // validates name and value
     if (rc) return rc;

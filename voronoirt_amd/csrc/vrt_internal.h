@@ -196,6 +196,11 @@ inline ExecArgs native_args(int64_t nlam, const void *S_up, const void *S_down, 
 
 }  // namespace vrt
 
+namespace vrt {
+struct RasterLocator;                // vrt_raster.hip: cell list and seeds of the nearest-site walk, workspaces
+void raster_locator_free(vrt_grid *g);
+}
+
 struct vrt_grid {
     int device = 0;
     int64_t n = 0;
@@ -224,6 +229,9 @@ struct vrt_grid {
     // cache of single-angle plans for vrt_delaunay_up/down
     std::mutex mu;
     std::vector<vrt::PlanCacheEntry *> cache;
+    // nearest-site search of the raster resampling (built on first use, under mu); cells per axis, 0 = auto
+    vrt::RasterLocator *locator = nullptr;
+    int64_t nearest_cells = 0;
 };
 
 struct vrt_plan {
