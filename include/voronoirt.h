@@ -383,6 +383,34 @@ int vrt_raster_to_grid(vrt_grid *g, int64_t nz, int64_t nx, int64_t ny, const do
 int vrt_grid_raster_stats(const vrt_grid *g, double *nearest_ms, double *gather_ms, int64_t *queries,
                           int64_t *walk_steps, int64_t *fallbacks);
 
+/* ---- sites sampled from a raster density (rejection_sampling, src/functions.jl:79-120) --------------------------------
+ * The first step of every reference run (compare_line.jl:51-125): sample_from_invNH_invT & co. (src/sample_grids.jl)
+ * form a quantity on the raster and draw the sites from it by rejection.
+ *   box       z_0 = z[0], dz = z[nz-1] - z[0]; the same for x and y.  q_min = min q, q_max = max q, dq = q_max - q_min
+ *   proposal  j = 0, 1, 2, ...: u_c = U(seed, c, j) for c = 0..3, U = synth.counter_uniform: splitmix64 of
+ *             (j ^ splitmix64(seed * 0x100000001B3 + c)), >> 11, times 2^-53
+ *             zr = u_0*dz + z_0, xr = u_1*dx + x_0, yr = u_2*dy + y_0 (multiply, then add)
+ *   accept    trilinear(q; zr, xr, yr) > u_3*dq + q_min: the reference's test, so the sites are distributed
+ *             proportionally to q - q_min (not to q).  trilinear as vrt_raster_to_grid's (clamped interval, x, y, z)
+ *   result    pos_zxy (n_sites, 3) rows (z, x, y): the first n_sites accepted proposals in increasing j;
+ *             *proposals_used (may be NULL) = 1 + the j of the last of them.  The result is a function of (axes,
+ *             quantity, n_sites, seed) alone: not of batch, launch shape or device.  (The reference draws from Julia's
+ *             global RNG; its stream is not reproduced.)
+ * Axes: >= 2 points, finite, strictly ascending, on the host.  quantity: (ny, nx, nz), element iz + nz*(ix + nx*iy) --
+ * the raster layout of vrt_raster_to_grid; every value finite and q_max > q_min (otherwise the reference never ends).
+ * batch: proposals per device batch, 0 = chosen from the acceptance seen so far (clamped to 2^24).  max_proposals: the
+ * cap, 0 = 1000*n_sites + 2^20; a cap reached before n_sites are accepted is VRT_EINVAL, vrt_last_error giving the
+ * accepted and proposed counts and *proposals_used the proposals made (the _dev form has then written the accepted
+ * rows, the host form nothing).  Every argument check -- for the host form also the quantity's -- runs before the
+ * device is touched; the _dev form takes q_min, q_max and the finiteness from a device reduction.  Synchronous (one
+ * int64 read per batch). */
+int vrt_sample_sites(int device, int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x, const double *y,
+                     const double *quantity, int64_t n_sites, uint64_t seed, int64_t batch, int64_t max_proposals,
+                     double *pos_zxy, int64_t *proposals_used);
+int vrt_sample_sites_dev(int device, int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x,
+                         const double *y, const double *d_quantity, int64_t n_sites, uint64_t seed, int64_t batch,
+                         int64_t max_proposals, double *d_pos_zxy, int64_t *proposals_used, void *stream);
+
 /* ---- Λ-iteration epilogue on the device (the physics-free part) -----------
  * S_new[l,i] = (1 - eps[i]) J[l,i] + eps[i] B[l,i]           (src/lambda_iteration.jl:261-263)
  * *max_rel_change = max |1 - S_old/S_new|, NaN if any term is NaN  (criterion, :325-349)

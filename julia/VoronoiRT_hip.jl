@@ -424,6 +424,28 @@ function regular_solve(up::Bool, k, S_0::AbstractArray{<:Any,3}, I_0::AbstractMa
     return I * I_unit
 end
 
+# ---- rejection_sampling (src/functions.jl:79-120) on the device ---------------------------------------------------------
+# `quantity` is the (nz, nx, ny) array the sample_from_* functions form (src/sample_grids.jl); the sites are drawn by
+# vrt_sample_sites from a counter-based stream keyed by `seed`, so (atmos, quantity, n_sites, seed) fixes the grid.  The
+# reference's Julia RNG stream is not reproduced.  Returns (3, n_sites) positions [z; x; y] in metres, as the reference.
+function rejection_sampling(n_sites::Integer, atmos, quantity::AbstractArray; seed::Integer=0, device::Integer=0,
+                            max_proposals::Integer=0)
+    z = Vector{Float64}(ustrip.(u"m", atmos.z)); x = Vector{Float64}(ustrip.(u"m", atmos.x))
+    y = Vector{Float64}(ustrip.(u"m", atmos.y))
+    q = Array{Float64,3}(ustrip.(quantity))
+    size(q) == (length(z), length(x), length(y)) || error("quantity must be (nz, nx, ny)")
+    p_vec = Matrix{Float64}(undef, 3, n_sites)
+    used = Ref{Int64}(0)
+    GC.@preserve z x y q p_vec begin
+        check(ccall((:vrt_sample_sites, libvrt), Cint,
+                    (Cint, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, UInt64,
+                     Int64, Int64, Ptr{Float64}, Ref{Int64}),
+                    device, length(z), length(x), length(y), z, x, y, q, n_sites, UInt64(seed), 0, max_proposals,
+                    p_vec, used))
+    end
+    return p_vec * u"m"
+end
+
 end # module
 
 # ---- drop-in redefinitions (same signatures as the reference's methods) --------------------------

@@ -10,7 +10,8 @@ from .api import (Delaunay_downII, Delaunay_upII, FormalPlan, J_lambda_voronoi, 
                   short_characteristics_batch, short_characteristics_down, short_characteristics_up,
                   RegularSolver, LineCase, Lambda_voronoi, Lambda_voronoi_host, J_lambda_voronoi_line, MultiDevicePlan,
                   nearest_sites, Voronoi_to_Raster, Voronoi_to_Raster_inv_dist, initialise, Voronoi_to_Raster_dev,
-                  initialise_dev, raster_stats)
+                  initialise_dev, raster_stats, rejection_sampling, rejection_sampling_dev, sample_from_invNH_invT,
+                  sample_from_logNH_invT, sample_from_logNH_invT_rootv, sample_from_temp_gradient)
 from ._lib import VrtError  # noqa: F401
 
 __all__ = ["Delaunay_upII", "Delaunay_downII", "FormalPlan", "J_lambda_voronoi", "VoronoiSites",
@@ -18,4 +19,6 @@ __all__ = ["Delaunay_upII", "Delaunay_downII", "FormalPlan", "J_lambda_voronoi",
            "QUADRATURE_DIR", "short_characteristics_up", "short_characteristics_down",
            "short_characteristics_batch", "RegularSolver", "LineCase", "Lambda_voronoi", "Lambda_voronoi_host",
            "J_lambda_voronoi_line", "MultiDevicePlan", "nearest_sites", "Voronoi_to_Raster",
-           "Voronoi_to_Raster_inv_dist", "initialise", "Voronoi_to_Raster_dev", "initialise_dev", "raster_stats"]
+           "Voronoi_to_Raster_inv_dist", "initialise", "Voronoi_to_Raster_dev", "initialise_dev", "raster_stats",
+           "rejection_sampling", "rejection_sampling_dev", "sample_from_invNH_invT", "sample_from_logNH_invT",
+           "sample_from_logNH_invT_rootv", "sample_from_temp_gradient"]

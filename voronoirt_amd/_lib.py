@@ -151,6 +151,10 @@ PROTOTYPES = {
                                           c_i64, c_i64, p_dbl, p_dbl]),
     "vrt_raster_to_grid": (ctypes.c_int, [vp, c_i64, c_i64, c_i64, p_dbl, p_dbl, p_dbl, c_i64, p_dbl, c_i64, p_dbl]),
     "vrt_grid_raster_stats": (ctypes.c_int, [vp, p_dbl, p_dbl, p_i64, p_i64, p_i64]),
+    "vrt_sample_sites": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64, p_dbl, p_dbl, p_dbl, p_dbl, c_i64,
+                                        ctypes.c_uint64, c_i64, c_i64, p_dbl, p_i64]),
+    "vrt_sample_sites_dev": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64, p_dbl, p_dbl, p_dbl, vp, c_i64,
+                                            ctypes.c_uint64, c_i64, c_i64, vp, p_i64, vp]),
     "vrt_delaunay_up": (ctypes.c_int, [vp, p_dbl, p_dbl, p_dbl, c_i64, p_dbl, ctypes.c_int, p_dbl]),
     "vrt_delaunay_down": (ctypes.c_int, [vp, p_dbl, p_dbl, p_dbl, c_i64, p_dbl, ctypes.c_int, p_dbl]),
 }

@@ -824,6 +824,84 @@ def raster_stats(sites: VoronoiSites) -> dict:
             "walk_steps": cnt[1].value, "fallbacks": cnt[2].value}
 
 
+# ---- sites sampled from a raster density (src/functions.jl:79-120, src/sample_grids.jl) ------------------------------
+def _seed(seed) -> int:
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed must be in [0, 2^64)")
+    return seed
+
+
+def rejection_sampling(n_sites: int, z, x, y, quantity, seed: int, max_proposals: int = 0, batch: int = 0,
+                       device: int = 0, return_proposals: bool = False):
+    """rejection_sampling (src/functions.jl:79-120) on the device (`vrt_sample_sites`), the raster's axes and
+    `quantity` (ny, nx, nz) -- Julia's (nz, nx, ny), the layout `initialise` reads -- in place of `atmos`.
+
+    Proposal j is uniform in the box of the axes' end points and is accepted when the trilinear value of `quantity`
+    there exceeds u*(q_max - q_min) + q_min, u uniform: the reference's test, so the sites are distributed
+    proportionally to q - q_min, not to q.  The uniforms are synth.counter_uniform(seed, c, j), c = 0..3, so the
+    result depends on (axes, quantity, n_sites, seed) only; Julia's RNG stream is not reproduced.  Returns the
+    positions (n_sites, 3) [z, x, y] of the first n_sites accepted proposals, and with `return_proposals` also the
+    proposals used (1 + the j of the last).  `max_proposals` caps the proposals (0: 1000*n_sites + 2^20; reaching
+    it raises VrtError); `batch` is the proposals per device batch (0: the library chooses; the result does not
+    depend on it)."""
+    z, x, y = _axes(z, x, y)
+    q = _f64(quantity)
+    if q.size != z.size * x.size * y.size:
+        raise ValueError("quantity must hold ny*nx*nz values (layout (ny, nx, nz))")
+    pos = np.zeros((max(int(n_sites), 0), 3))
+    used = ctypes.c_int64()
+    check(_lib.load().vrt_sample_sites(int(device), z.size, x.size, y.size, _d(z), _d(x), _d(y), _d(q), int(n_sites),
+                                       _seed(seed), int(batch), int(max_proposals), _d(pos), ctypes.byref(used)))
+    return (pos, used.value) if return_proposals else pos
+
+
+def rejection_sampling_dev(n_sites: int, z, x, y, d_quantity: int, seed: int, d_positions: int,
+                           max_proposals: int = 0, batch: int = 0, device: int = 0, stream: int = 0) -> int:
+    """Device form (`vrt_sample_sites_dev`): quantity (ny, nx, nz) and positions (n_sites, 3) are device pointers
+    (torch data_ptr()); q_min and q_max come from a device reduction.  Returns the proposals used.  Synchronises
+    `stream`."""
+    z, x, y = _axes(z, x, y)
+    used = ctypes.c_int64()
+    check(_lib.load().vrt_sample_sites_dev(int(device), z.size, x.size, y.size, _d(z), _d(x), _d(y), d_quantity,
+                                           int(n_sites), _seed(seed), int(batch), int(max_proposals), d_positions,
+                                           ctypes.byref(used), stream or None))
+    return used.value
+
+
+def sample_from_invNH_invT(z, x, y, N_H, T, n_sites: int, seed: int, **kw):
+    """sample_from_invNH_invT (src/sample_grids.jl:223-230): q = log10(N_H)^-2 * T^(-2/5), formed on the host as
+    written there (Julia's literal ^-2 is inv(v)*inv(v)); arrays (ny, nx, nz).  Keywords go to rejection_sampling."""
+    inv = 1.0 / np.log10(_f64(N_H))
+    return rejection_sampling(n_sites, z, x, y, (inv * inv) * _f64(T) ** (-2 / 5), seed, **kw)
+
+
+def sample_from_logNH_invT(z, x, y, N_H, T, n_sites: int, seed: int, **kw):
+    """sample_from_logNH_invT (src/sample_grids.jl:198-206): q = log10(N_H) * T^(-2/5)."""
+    return rejection_sampling(n_sites, z, x, y, np.log10(_f64(N_H)) * _f64(T) ** (-2 / 5), seed, **kw)
+
+
+def sample_from_logNH_invT_rootv(z, x, y, N_H, T, vx, vy, vz, n_sites: int, seed: int, **kw):
+    """sample_from_logNH_invT_rootv (src/sample_grids.jl:208-221): q = log10(N_H) * T^(-2/5) * (vx^2 + vy^2 +
+    vz^2)^(1/3)."""
+    vx, vy, vz = _f64(vx), _f64(vy), _f64(vz)
+    v_sqrd = vx * vx + vy * vy + vz * vz
+    q = np.log10(_f64(N_H)) * _f64(T) ** (-2 / 5) * v_sqrd ** (1 / 3)
+    return rejection_sampling(n_sites, z, x, y, q, seed, **kw)
+
+
+def sample_from_temp_gradient(z, x, y, T, n_sites: int, seed: int, **kw):
+    """sample_from_temp_gradient (src/sample_grids.jl:97-115): q = |dT/dz| with T (ny, nx, nz); every plane but the
+    last takes the forward difference (T[k+1] - T[k])/(z[k+1] - z[k]), the last the backward one, as there."""
+    z, T = _f64(z).ravel(), _f64(T)
+    if T.shape[-1] != z.size or z.size < 2:
+        raise ValueError("T must be (ny, nx, nz) with nz = len(z) >= 2")
+    g = np.empty_like(T)
+    g[..., :-1] = (T[..., 1:] - T[..., :-1]) / (z[1:] - z[:-1])
+    g[..., -1] = (T[..., -1] - T[..., -2]) / (z[-1] - z[-2])
+    return rejection_sampling(n_sites, z, x, y, np.abs(g), seed, **kw)
+
+
 def lambda_update_dev(sites: VoronoiSites, nlam: int, ld: int, dJ: int, dB: int, deps: int, dS_old: int,
                       dS_new: int, stream: int = 0) -> float:
     """Device-resident Λ-iteration epilogue: S_new = (1 - ε) J + ε B (src/lambda_iteration.jl:261-263)

@@ -2,6 +2,8 @@
 // run.  Voronoi_to_Raster / Voronoi_to_Raster_inv_dist (src/voronoi_utils.jl:407-617, :773-816, inv_dist_itp :848-860)
 // answer a KD-tree query per raster point; initialise (:687-707) interpolates a raster onto the sites with trilinear
 // (src/functions.jl:207-248).
+// The sites themselves are drawn here too: rejection_sampling (src/functions.jl:79-120) from a raster density, with
+// k_trilinear's interpolation (vrt_sample_sites[_dev], below).
 //
 // Nearest search without a tree: a greedy walk over the grid's own neighbour rows (DESIGN.md "Raster resampling").
 // Under the x/y minimum-image metric a walk that moves to a strictly closer Voronoi neighbour ends at the nearest site;
@@ -311,6 +313,22 @@ __device__ __forceinline__ int interval(const double *__restrict__ ax, int n, do
     return i < 0 ? 0 : (i > n - 2 ? n - 2 : i);
 }
 
+// k_trilinear's expressions on one cell (the sampler's; k_trilinear keeps its own copy, whose code this helper would
+// reschedule): r = the cell's (iz, ix, iy) corner, sx / sy the x / y strides of the raster
+__device__ __forceinline__ double trilinear_cell(const double *__restrict__ r, int64_t sx, int64_t sy, double x_d,
+                                                 double y_d, double z_d)
+{
+    const double c000 = r[0], c010 = r[sy], c100 = r[sx], c110 = r[sx + sy];
+    const double c001 = r[1], c011 = r[1 + sy], c101 = r[1 + sx], c111 = r[1 + sx + sy];
+    const double c00 = c000 * (1 - x_d) + c100 * x_d;
+    const double c01 = c001 * (1 - x_d) + c101 * x_d;
+    const double c10 = c010 * (1 - x_d) + c110 * x_d;
+    const double c11 = c011 * (1 - x_d) + c111 * x_d;
+    const double c0 = c00 * (1 - y_d) + c10 * y_d;
+    const double c1 = c01 * (1 - y_d) + c11 * y_d;
+    return c0 * (1 - z_d) + c1 * z_d;
+}
+
 __global__ void __launch_bounds__(kGatherThreads)
 k_trilinear(int64_t n, const double *__restrict__ pos, int nz, int nx, int ny, const double *__restrict__ axes, int use_lds,
             int64_t nf, const double *__restrict__ raster, int64_t ld, double *__restrict__ fields)
@@ -364,6 +382,185 @@ k_trilinear(int64_t n, const double *__restrict__ pos, int nz, int nx, int ny, c
             if (i0 + j < n && f0 + fl < nf) fields[f0 + fl + ld * (i0 + j)] = tw[j * (kChunk + 1) + fl];
         }
         __syncthreads();
+    }
+}
+
+// ---- rejection sampling of sites from a raster density (src/functions.jl:79-120; DESIGN.md "Site sampling") --------
+// Proposal j draws u_c = counter_uniform(seed, c, j), c = 0..3 (synth.counter_uniform), and is accepted iff
+// trilinear(q; u_0*dz + z_0, u_1*dx + x_0, u_2*dy + y_0) > u_3*dq + q_min.  A batch [j0, j0 + count) runs as three
+// launches: flags (one ballot mask and its popcount per 64 proposals), one workgroup scanning the counts, and the
+// write of every accepted proposal at (accepted before the batch) + rank.  No launch depends on workgroup order.
+constexpr int kSampleThreads = 256;
+constexpr int kSampleGrid = 4096;                   // workgroups of a flags / write launch (grid-stride beyond)
+constexpr int kScanThreads = 1024;
+constexpr int kScanPer = 4;                         // counts per scan thread and tile
+constexpr int kSampleLdsAxes = 4096;                // axes (doubles) staged in LDS up to 32 KiB
+constexpr int kMinMaxThreads = 256;
+constexpr int kMinMaxGrid = 1024;
+
+struct SampleArgs {
+    const double *axes;               // z (nz), x (nx), y (ny)
+    const double *q;                  // (ny, nx, nz): element iz + nz*(ix + nx*iy)
+    int nz, nx, ny, use_lds;
+    uint64_t key[4];                  // splitmix64(seed * 0x100000001B3 + c)
+    double z0, dz, x0, dx, y0, dy, qmin, dq;
+};
+
+__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x)
+{
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+__device__ __forceinline__ double uniform01(uint64_t key, uint64_t j)
+{
+    return (double)(splitmix64(j ^ key) >> 11) * (1.0 / 9007199254740992.0);
+}
+
+__global__ void __launch_bounds__(kSampleThreads)
+k_sample_flags(SampleArgs a, uint64_t j0, int64_t count, unsigned long long *__restrict__ masks,
+               int32_t *__restrict__ counts)
+{
+    extern __shared__ double s_axes[];
+    if (a.use_lds) {
+        for (int u = threadIdx.x; u < a.nz + a.nx + a.ny; u += blockDim.x) s_axes[u] = a.axes[u];
+        __syncthreads();
+    }
+    const double *az = a.use_lds ? s_axes : a.axes;
+    const double *ax = az + a.nz, *ay = ax + a.nx;
+    const int64_t sx = a.nz, sy = (int64_t)a.nz * a.nx;
+    // (the loop bound is the same for every thread of the workgroup: the ballot below runs in full waves)
+    for (int64_t base = (int64_t)blockIdx.x * kSampleThreads; base < count; base += (int64_t)gridDim.x * kSampleThreads) {
+        const int64_t t = base + threadIdx.x;
+        bool acc = false;
+        if (t < count) {
+            const uint64_t j = j0 + (uint64_t)t;
+            const double zr = uniform01(a.key[0], j) * a.dz + a.z0;
+            const double xr = uniform01(a.key[1], j) * a.dx + a.x0;
+            const double yr = uniform01(a.key[2], j) * a.dy + a.y0;
+            const double u3 = uniform01(a.key[3], j);
+            const int iz = interval(az, a.nz, zr), ix = interval(ax, a.nx, xr), iy = interval(ay, a.ny, yr);
+            const double x_d = (xr - ax[ix]) / (ax[ix + 1] - ax[ix]);
+            const double y_d = (yr - ay[iy]) / (ay[iy + 1] - ay[iy]);
+            const double z_d = (zr - az[iz]) / (az[iz + 1] - az[iz]);
+            const double v = trilinear_cell(a.q + (iz + (int64_t)a.nz * (ix + (int64_t)a.nx * iy)), sx, sy, x_d, y_d, z_d);
+            acc = v > u3 * a.dq + a.qmin;
+        }
+        const unsigned long long m = __ballot(acc);
+        const int64_t w = t >> 6;
+        if ((threadIdx.x & 63) == 0 && w * 64 < count) {
+            masks[w] = m;
+            counts[w] = __popcll(m);
+        }
+    }
+}
+
+// exclusive scan of the W per-wave counts in place (tiles of kScanThreads * kScanPer); state[1] = accepted before the
+// batch, state[0] += the batch's accepted
+__global__ void __launch_bounds__(kScanThreads) k_sample_scan(int64_t W, int32_t *__restrict__ counts,
+                                                               int64_t *__restrict__ state)
+{
+    __shared__ int32_t s_wave[kScanThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int32_t carry = 0;                                // a batch holds at most kSampleBatchMax proposals
+    for (int64_t t0 = 0; t0 < W; t0 += kScanThreads * kScanPer) {
+        const int64_t i0 = t0 + (int64_t)threadIdx.x * kScanPer;
+        int32_t v[kScanPer], s = 0;
+#pragma unroll
+        for (int k = 0; k < kScanPer; k++) {
+            v[k] = i0 + k < W ? counts[i0 + k] : 0;
+            s += v[k];
+        }
+        int32_t inc = s;                              // inclusive scan over the wave
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int32_t y = __shfl_up(inc, o);
+            if (lane >= o) inc += y;
+        }
+        if (lane == 63) s_wave[wave] = inc;
+        __syncthreads();
+        int32_t before = 0, tile = 0;
+#pragma unroll
+        for (int u = 0; u < kScanThreads / 64; u++) {
+            const int32_t c = s_wave[u];
+            before += u < wave ? c : 0;
+            tile += c;
+        }
+        int32_t run = carry + before + (inc - s);
+#pragma unroll
+        for (int k = 0; k < kScanPer; k++) {
+            if (i0 + k < W) counts[i0 + k] = run;
+            run += v[k];
+        }
+        carry += tile;
+        __syncthreads();                              // s_wave is rewritten by the next tile
+    }
+    if (threadIdx.x == 0) {
+        const int64_t total = state[0];
+        state[1] = total;
+        state[0] = total + carry;
+    }
+}
+
+// every accepted proposal of the batch whose index (state[1] + offset of its wave + rank in the mask) is < n writes
+// its position, recomputed from j; the n-th accepted one records its j in state[2]
+__global__ void __launch_bounds__(kSampleThreads)
+k_sample_write(SampleArgs a, uint64_t j0, int64_t count, const unsigned long long *__restrict__ masks,
+               const int32_t *__restrict__ offsets, int64_t *__restrict__ state, int64_t n, double *__restrict__ pos)
+{
+    const int64_t first = state[1];
+    if (first >= n) return;
+    const int lane = threadIdx.x & 63;
+    for (int64_t t = (int64_t)blockIdx.x * kSampleThreads + threadIdx.x; t < count;
+         t += (int64_t)gridDim.x * kSampleThreads) {
+        const int64_t w = t >> 6;
+        const unsigned long long m = masks[w];
+        if (!((m >> lane) & 1ull)) continue;
+        const int64_t idx = first + offsets[w] + __popcll(m & ((1ull << lane) - 1ull));
+        if (idx >= n) continue;
+        const uint64_t j = j0 + (uint64_t)t;
+        pos[3 * idx] = uniform01(a.key[0], j) * a.dz + a.z0;
+        pos[3 * idx + 1] = uniform01(a.key[1], j) * a.dx + a.x0;
+        pos[3 * idx + 2] = uniform01(a.key[2], j) * a.dy + a.y0;
+        if (idx == n - 1) state[2] = (int64_t)j;
+    }
+}
+
+// per workgroup: min and max of the finite values of q and the number of values that are not finite (exact: the min
+// and max of a set are members of it)
+__global__ void __launch_bounds__(kMinMaxThreads) k_minmax(int64_t P, const double *__restrict__ q,
+                                                           double *__restrict__ part)
+{
+    __shared__ double s[3][kMinMaxThreads / 64];
+    double mn = INFINITY, mx = -INFINITY, bad = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kMinMaxThreads + threadIdx.x; i < P; i += (int64_t)gridDim.x * kMinMaxThreads) {
+        const double v = q[i];
+        if (isfinite(v)) {
+            mn = fmin(mn, v);
+            mx = fmax(mx, v);
+        } else {
+            bad += 1.0;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        mn = fmin(mn, __shfl_xor(mn, o));
+        mx = fmax(mx, __shfl_xor(mx, o));
+        bad += __shfl_xor(bad, o);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { s[0][wave] = mn; s[1][wave] = mx; s[2][wave] = bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int u = 1; u < kMinMaxThreads / 64; u++) {
+            mn = fmin(mn, s[0][u]);
+            mx = fmax(mx, s[1][u]);
+            bad += s[2][u];
+        }
+        part[3 * blockIdx.x] = mn;
+        part[3 * blockIdx.x + 1] = mx;
+        part[3 * blockIdx.x + 2] = bad;
     }
 }
 
@@ -715,6 +912,119 @@ int guarded(Fn fn)
     }
 }
 
+// ---- rejection sampling: host side ----------------------------------------------------------------------------------
+constexpr int64_t kSampleBatchMax = (int64_t)1 << 24;      // proposals per batch: 2 MiB of masks, 1 MiB of counts
+constexpr int64_t kSampleBatchMin = (int64_t)1 << 16;
+
+int sample_checks(int device, int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x, const double *y,
+                  const void *quantity, int64_t n_sites, int64_t batch, int64_t max_proposals, const void *pos)
+{
+    if (!z || !x || !y || !quantity || !pos) return fail(VRT_EINVAL, "NULL argument");
+    if (device < 0) return fail(VRT_EINVAL, "device ordinal must be >= 0");
+    if (nz < 2 || nx < 2 || ny < 2) return fail(VRT_EINVAL, "trilinear needs at least two points on every axis");
+    if (nz > kMaxPoints || nx > kMaxPoints || ny > kMaxPoints || nz * nx > kMaxPoints || nz * nx * ny > kMaxPoints)
+        return fail(VRT_EINVAL, "raster has more than 2^31 - 1 points");
+    if (!finite_ascending(z, nz) || !finite_ascending(x, nx) || !finite_ascending(y, ny))
+        return fail(VRT_EINVAL, "raster axes must be finite and strictly ascending");
+    if (!(z[nz - 1] - z[0] < INFINITY && x[nx - 1] - x[0] < INFINITY && y[ny - 1] - y[0] < INFINITY))
+        return fail(VRT_EINVAL, "raster axis extent overflows");
+    if (n_sites < 1 || n_sites > kMaxPoints) return fail(VRT_EINVAL, "n_sites must be in [1, 2^31 - 1]");
+    if (batch < 0) return fail(VRT_EINVAL, "batch must be >= 0 (0: the library chooses)");
+    if (max_proposals < 0) return fail(VRT_EINVAL, "max_proposals must be >= 0 (0: the default cap)");
+    return VRT_OK;
+}
+
+// q_min, q_max of the quantity: every value finite and q_max > q_min, else the reference's loop never ends
+int check_range(int64_t nonfinite, double qmin, double qmax)
+{
+    if (nonfinite) return fail(VRT_EINVAL, "quantity has " + std::to_string(nonfinite) + " values that are not finite");
+    if (!(qmax - qmin > 0.0) || !(qmax - qmin < INFINITY))
+        return fail(VRT_EINVAL, "quantity is constant (q_max == q_min) or its range overflows: nothing can be accepted");
+    return VRT_OK;
+}
+
+struct SampleWork {
+    double *axes = nullptr;
+    unsigned long long *masks = nullptr;
+    int32_t *counts = nullptr;
+    int64_t *state = nullptr;         // accepted so far, accepted before the batch, j of the n-th accepted
+    ~SampleWork()
+    {
+        dev_free(axes);
+        dev_free(masks);
+        dev_free(counts);
+        dev_free(state);
+    }
+};
+
+// next batch under batch = 0: the proposals that the acceptance seen so far needs for the remaining sites, plus a
+// quarter, or four times the last batch while nothing has been accepted
+int64_t next_batch(int64_t n, int64_t accepted, int64_t proposed, int64_t last)
+{
+    double want;
+    if (proposed == 0) want = 2.0 * (double)n;
+    else if (accepted == 0) want = 4.0 * (double)last;
+    else want = 1.25 * (double)(n - accepted) * ((double)proposed / (double)accepted) + 4096.0;
+    return (int64_t)std::min((double)kSampleBatchMax, std::max((double)kSampleBatchMin, want));
+}
+
+int sample_impl(int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x, const double *y,
+                const double *d_q, double qmin, double qmax, int64_t n, uint64_t seed, int64_t batch,
+                int64_t max_proposals, double *d_pos, int64_t *proposals_used, hipStream_t st)
+{
+    SampleArgs a{};
+    a.q = d_q;
+    a.nz = (int)nz; a.nx = (int)nx; a.ny = (int)ny;
+    for (int c = 0; c < 4; c++) a.key[c] = splitmix64(seed * 0x100000001B3ull + (uint64_t)c);
+    a.z0 = z[0]; a.dz = z[nz - 1] - z[0];
+    a.x0 = x[0]; a.dx = x[nx - 1] - x[0];
+    a.y0 = y[0]; a.dy = y[ny - 1] - y[0];
+    a.qmin = qmin; a.dq = qmax - qmin;
+    const int64_t na = nz + nx + ny;
+    a.use_lds = na <= kSampleLdsAxes;
+    const int64_t cap = max_proposals > 0 ? max_proposals : 1000 * n + ((int64_t)1 << 20);
+    const int64_t bmax = std::min(batch > 0 ? std::min(batch, kSampleBatchMax) : kSampleBatchMax, cap);
+    SampleWork w;
+    int rc;
+    if ((rc = dev_alloc(&w.axes, (size_t)na))) return rc;
+    if ((rc = dev_alloc(&w.masks, (size_t)((bmax + 63) / 64)))) return rc;
+    if ((rc = dev_alloc(&w.counts, (size_t)((bmax + 63) / 64)))) return rc;
+    if ((rc = dev_alloc(&w.state, 3))) return rc;
+    a.axes = w.axes;
+    VRT_HIP_TRY(hipMemcpyAsync(w.axes, z, sizeof(double) * nz, hipMemcpyHostToDevice, st));
+    VRT_HIP_TRY(hipMemcpyAsync(w.axes + nz, x, sizeof(double) * nx, hipMemcpyHostToDevice, st));
+    VRT_HIP_TRY(hipMemcpyAsync(w.axes + nz + nx, y, sizeof(double) * ny, hipMemcpyHostToDevice, st));
+    VRT_HIP_TRY(hipMemsetAsync(w.state, 0, 3 * sizeof(int64_t), st));
+    const size_t lds = a.use_lds ? sizeof(double) * (size_t)na : 0;
+    int64_t proposed = 0, accepted = 0, count = 0;
+    while (accepted < n && proposed < cap) {
+        count = std::min(batch > 0 ? bmax : next_batch(n, accepted, proposed, count), cap - proposed);
+        const unsigned blocks = (unsigned)std::min<int64_t>((count + kSampleThreads - 1) / kSampleThreads, kSampleGrid);
+        hipLaunchKernelGGL(k_sample_flags, dim3(blocks), dim3(kSampleThreads), lds, st, a, (uint64_t)proposed, count,
+                           w.masks, w.counts);
+        VRT_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_sample_scan, dim3(1), dim3(kScanThreads), 0, st, (count + 63) / 64, w.counts, w.state);
+        VRT_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_sample_write, dim3(blocks), dim3(kSampleThreads), 0, st, a, (uint64_t)proposed, count,
+                           w.masks, w.counts, w.state, n, d_pos);
+        VRT_HIP_TRY(hipGetLastError());
+        VRT_HIP_TRY(hipMemcpyAsync(&accepted, w.state, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        VRT_HIP_TRY(hipStreamSynchronize(st));
+        proposed += count;
+    }
+    if (accepted < n) {
+        if (proposals_used) *proposals_used = proposed;
+        return fail(VRT_EINVAL, "rejection sampling: " + std::to_string(accepted) + " of " + std::to_string(n) +
+                                    " sites accepted in " + std::to_string(proposed) +
+                                    " proposals (max_proposals reached)");
+    }
+    int64_t last_j = 0;
+    VRT_HIP_TRY(hipMemcpyAsync(&last_j, w.state + 2, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    VRT_HIP_TRY(hipStreamSynchronize(st));
+    if (proposals_used) *proposals_used = last_j + 1;
+    return VRT_OK;
+}
+
 }  // namespace
 }  // namespace vrt
 
@@ -866,4 +1176,79 @@ extern "C" int vrt_grid_raster_stats(const vrt_grid *g, double *nearest_ms, doub
     if (walk_steps) *walk_steps = L ? (int64_t)L->last_stats[1] : 0;
     if (fallbacks) *fallbacks = L ? (int64_t)L->last_stats[2] : 0;
     return VRT_OK;
+}
+
+extern "C" int vrt_sample_sites(int device, int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x,
+                                const double *y, const double *quantity, int64_t n_sites, uint64_t seed, int64_t batch,
+                                int64_t max_proposals, double *pos_zxy, int64_t *proposals_used)
+{
+    DeviceScope scope;
+    return guarded([&]() -> int {
+        int rc = sample_checks(device, nz, nx, ny, z, x, y, quantity, n_sites, batch, max_proposals, pos_zxy);
+        if (rc) return rc;
+        const int64_t P = nz * nx * ny;
+        double qmin = INFINITY, qmax = -INFINITY;
+        int64_t nonfinite = 0;
+        for (int64_t i = 0; i < P; i++) {
+            const double v = quantity[i];
+            if (!std::isfinite(v)) { nonfinite++; continue; }
+            qmin = std::min(qmin, v);
+            qmax = std::max(qmax, v);
+        }
+        if ((rc = check_range(nonfinite, qmin, qmax))) return rc;
+        if ((rc = use_device(device))) return rc;
+        double *dq = nullptr, *dp = nullptr;
+        if ((rc = dev_alloc(&dq, (size_t)P))) return rc;
+        if ((rc = dev_alloc(&dp, (size_t)n_sites * 3))) { dev_free(dq); return rc; }
+        hipStream_t st = nullptr;
+        if (hipMemcpy(dq, quantity, sizeof(double) * P, hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(VRT_ENODEVICE, "HIP error uploading the quantity");
+        int64_t used = 0;
+        if (!rc) rc = sample_impl(nz, nx, ny, z, x, y, dq, qmin, qmax, n_sites, seed, batch, max_proposals, dp, &used, st);
+        // on an error (a reached cap included) pos_zxy is left as it was
+        if (!rc && hipMemcpy(pos_zxy, dp, sizeof(double) * 3 * n_sites, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(VRT_ENODEVICE, "HIP error downloading the positions");
+        if (proposals_used) *proposals_used = used;
+        dev_free(dq);
+        dev_free(dp);
+        return rc;
+    });
+}
+
+extern "C" int vrt_sample_sites_dev(int device, int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x,
+                                    const double *y, const double *d_quantity, int64_t n_sites, uint64_t seed,
+                                    int64_t batch, int64_t max_proposals, double *d_pos_zxy, int64_t *proposals_used,
+                                    void *stream)
+{
+    DeviceScope scope;
+    return guarded([&]() -> int {
+        int rc = sample_checks(device, nz, nx, ny, z, x, y, d_quantity, n_sites, batch, max_proposals, d_pos_zxy);
+        if (rc) return rc;
+        if ((rc = use_device(device))) return rc;
+        hipStream_t st = (hipStream_t)stream;
+        const int64_t P = nz * nx * ny;
+        const int blocks = (int)std::min<int64_t>((P + kMinMaxThreads - 1) / kMinMaxThreads, kMinMaxGrid);
+        double *dpart = nullptr;
+        if ((rc = dev_alloc(&dpart, (size_t)blocks * 3))) return rc;
+        std::vector<double> part((size_t)blocks * 3);
+        hipLaunchKernelGGL(k_minmax, dim3(blocks), dim3(kMinMaxThreads), 0, st, P, d_quantity, dpart);
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpyAsync(part.data(), dpart, sizeof(double) * part.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            rc = fail(VRT_ENODEVICE, "HIP error in the quantity's min/max reduction");
+        dev_free(dpart);
+        if (rc) return rc;
+        double qmin = INFINITY, qmax = -INFINITY, bad = 0.0;
+        for (int b = 0; b < blocks; b++) {
+            qmin = std::min(qmin, part[3 * (size_t)b]);
+            qmax = std::max(qmax, part[3 * (size_t)b + 1]);
+            bad += part[3 * (size_t)b + 2];
+        }
+        if ((rc = check_range((int64_t)bad, qmin, qmax))) return rc;
+        int64_t used = 0;
+        rc = sample_impl(nz, nx, ny, z, x, y, d_quantity, qmin, qmax, n_sites, seed, batch, max_proposals, d_pos_zxy,
+                         &used, st);
+        if (proposals_used) *proposals_used = used;
+        return rc;
+    });
 }

@@ -355,3 +355,42 @@ def synthetic_fields(positions: np.ndarray, bounds, nlam: int, seed: int, n_angl
         psi = 1.0 + 9.0 * np.exp(-((lamf - centre - shift) / sigma) ** 2)
         alpha[a] = strat[:, None] * (1.0 + 0.1 * uA) * psi[None, :]
     return S, alpha
+
+
+# ---------------------------------------------------------------------------------------------
+# rasters
+# ---------------------------------------------------------------------------------------------
+def atmosphere_raster(nz: int, nx: int, ny: int, seed: int, box_xy: float = BOX_XY, z_min: float = Z_MIN,
+                      z_max: float = 2.5e6):
+    """A seeded, Bifrost-shaped atmosphere raster (the input of the reference's samplers, src/sample_grids.jl) for
+    tests and probes.
+
+    z (nz) is non-uniform, finest at the bottom; x (nx) and y (ny) are uniform on [0, box_xy].  N_H falls by about
+    10^5 over the height (from 1e23 m^-3); T has a photosphere of about 6 500 K, a minimum near 4 000 K and a
+    chromospheric rise to about 2e4 K at the top; both carry small horizontal structure (a few per cent) and
+    counter_uniform noise.  vx, vy, vz are a few km/s.  Arrays are (ny, nx, nz) -- Julia's (nz, nx, ny), the layout
+    `initialise` and `rejection_sampling` read.  Returns a dict with z, x, y, N_H, T, vx, vy, vz."""
+    if nz < 2 or nx < 2 or ny < 2:
+        raise ValueError("atmosphere_raster needs at least two points per axis")
+    s = np.linspace(0.0, 1.0, nz)
+    z = z_min + (z_max - z_min) * (0.4 * s + 0.6 * s * s)
+    x = np.linspace(0.0, box_xy, nx)
+    y = np.linspace(0.0, box_xy, ny)
+    h = (z - z_min) / (z_max - z_min)
+    T_z = 4000.0 + 2500.0 * np.exp(-h / 0.12) + 16000.0 / (1.0 + np.exp(-(h - 0.8) / 0.05))
+    logN_z = 23.0 - 5.0 * h
+    X, Y = x[None, :] / box_xy, y[:, None] / box_xy
+    plane = (np.sin(2 * np.pi * (3 * X + 0.25)) * np.cos(2 * np.pi * (2 * Y)) +
+             0.5 * np.sin(2 * np.pi * (5 * X + 4 * Y)))                             # (ny, nx)
+    idx = np.arange(ny * nx, dtype=np.uint64).reshape(ny, nx)
+    noise = counter_uniform(seed, 10, idx) - 0.5
+    bend = np.sin(2 * np.pi * h)[None, None, :]
+    T = T_z[None, None, :] * (1.0 + 0.04 * plane[:, :, None] * bend + 0.02 * noise[:, :, None])
+    N_H = 10.0 ** (logN_z[None, None, :] + 0.03 * plane[:, :, None] * (1.0 - h)[None, None, :]
+                   + 0.01 * noise[:, :, None])
+    v = []
+    for c in range(3):
+        u = counter_uniform(seed, 11 + c, idx) - 0.5
+        v.append(3.0e3 * (np.cos(2 * np.pi * (X * (c + 1) + Y * (2 - c)))[:, :, None] * (0.5 + h)[None, None, :]
+                          + 0.3 * u[:, :, None]))
+    return {"z": z, "x": x, "y": y, "N_H": N_H, "T": T, "vx": v[0], "vy": v[1], "vz": v[2]}
