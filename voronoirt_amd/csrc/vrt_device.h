@@ -122,7 +122,7 @@ __device__ __forceinline__ double exp_neg(double x)       // exp(-x), 5e-4 <= x 
     return ldexp(p, (int)kf);
 }
 
-// exp(-x) for 0 <= x (the patch kernels call it for 5e-4 <= x <= 50), table-driven: -x = N ln2/32 + r with |r| <= ln2/64, exp(-x) = 2^(N >> 5) T[N & 31] p(r),
+// exp(-x) for 0 <= x <= 745 (the patch kernels call it for 5e-4 <= x <= 50, the rate kernels up to 745), table-driven: -x = N ln2/32 + r with |r| <= ln2/64, exp(-x) = 2^(N >> 5) T[N & 31] p(r),
 // T[j] = 2^(j/32) from a 32-entry LDS table (one 8-byte read per evaluation, conflict-free: the 32 entries cover the
 // 64 banks once) and p the degree-5 Taylor polynomial (remainder r^6/720 < 2.3e-15).  Against the degree-10 polynomial
 // on |r| <= ln2/2 it replaces: four fused multiply-adds fewer per evaluation, and five of its eleven non-inline fp64
@@ -144,10 +144,11 @@ __device__ __forceinline__ void exp2_table_fill()
 {
     if (threadIdx.x < 32) exp2_table()[threadIdx.x] = kExp2_32[threadIdx.x];
 }
-__device__ __forceinline__ double exp_neg_tab(double x)          // exp(-x), 0 <= x <= 700
+// Past x = 708.4 the result is subnormal: the final ldexp rounds it to the subnormal grid (steps of 2^-1074).
+__device__ __forceinline__ double exp_neg_tab(double x)          // exp(-x), 0 <= x <= 745
 {
     const double t = -x;
-    const double nf = rint(t * 46.16624130844683);            // N = round(t 32 / ln 2), |N| <= 2309
+    const double nf = rint(t * 46.16624130844683);            // N = round(t 32 / ln 2), |N| <= 34394
     double r = fma(-nf, 0.021660849335603416, t);             // Cody-Waite: ln2/32 = hi (29 bits) + lo
     r = fma(-nf, 5.689487495325457e-11, r);                   // |r| <= 0.01084
     const int N = (int)nf;

@@ -320,9 +320,12 @@ __device__ __forceinline__ double rcp_newton(double d)
     r = fma(fma(-d, r, 1.0), r, r);
     return fma(fma(-d, r, 1.0), r, r);
 }
+// libm's exp(-x) is exactly 0 from x = 745.1332191019412 (exp(-x) <= 2^-1075) on, and the smallest subnormal 2^-1074 just
+// below it: past the threshold the factor is 0 like the oracle's, below it x is clamped to exp_neg_tab's domain (x <= 745).
 __device__ __forceinline__ double boltzmann(double hc_over_kT, double lam)      // exp(-hc / (λ k T)), rates.jl:473
 {
-    return exp_neg_tab(fmin(hc_over_kT * rcp_newton(lam), 745.0));
+    const double x = hc_over_kT * rcp_newton(lam);
+    return x >= 745.1332191019412 ? 0.0 : exp_neg_tab(fmin(x, 745.0));
 }
 
 // R of site i out, its statistical equilibrium solved (n_levels = 2, populations.jl:191-221)
