@@ -9,7 +9,14 @@ already resident in HBM and the per-angle upwind tables / sweep schedule built b
 depend on the grid and the quadrature only; their one-time cost is reported separately).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4|C2|C3|C5|tiny] [--nlam L]
-                    [--shard lambda|lambda-strong|angle] [--dump-outputs DIR]
+                    [--shard lambda|lambda-strong|angle] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and nothing more: set-up, warm-up, the timed steps, --dump-outputs,
+the JSON line (its roofline figures come from the timed steps themselves).  --full adds what takes runs of
+its own: the caller-layout step timed beside the headline, the one-wavelength-pair critical path, a live
+device triad, the CPU baseline with its full-size parity check against the oracle, and (default C4 command)
+the secondary C2 and C1 configurations; --no-caller-layout / --no-critical-path / --no-cpu-baseline /
+--no-secondary leave single parts of it out.
 
 N > 1: one rank per GPU over RCCL.  Launched by `python -m torch.distributed.run ...` (RANK /
 WORLD_SIZE in the environment) the script joins that job; launched bare (`python bench.py --gpus 8`)
@@ -70,10 +77,13 @@ def parse_args(argv=None):
     ap.add_argument("--workload", default="C4", choices=sorted(WORKLOADS))
     ap.add_argument("--nlam", type=int, default=0, help="override the workload's wavelength count")
     ap.add_argument("--shard", default="auto", choices=["auto", "lambda", "lambda-strong", "angle"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary C2 measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: caller-layout step, critical path, device triad, "
+                         "CPU baseline + full-size parity, secondary C2 / C1 configurations")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity check")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary C2 / C1 measurements")
     ap.add_argument("--no-critical-path", action="store_true",
-                    help="skip the one-wavelength-pair latency-floor measurement (profiling runs)")
+                    help="with --full: skip the one-wavelength-pair latency-floor measurement")
     ap.add_argument("--cpu-lam", type=int, default=0, help="wavelengths in the CPU sample")
     ap.add_argument("--angle-groups", type=int, default=1,
                     help="diagnostics: run the angles in this many sequential groups (separate plans)")
@@ -90,10 +100,9 @@ def parse_args(argv=None):
                          "in the step; 'caller' = (n, nlam) arrays in, J (n, nlam) out (two layout changes per step); "
                          "auto: native on one GPU wherever the library offers it (per-angle alpha in its native layout; "
                          "alpha per (site, wavelength) -- the continuum's, fixed over the iterations -- laid out once in sweep "
-                         "order), the caller-layout time is reported beside it")
+                         "order); with --full the caller-layout time is reported beside it")
     ap.add_argument("--no-caller-layout", action="store_true",
-                    help="with --sj-layout native: do not time the caller-layout step beside it (profiling runs: the process "
-                         "then executes the headline step only)")
+                    help="with --full and --sj-layout native: do not time the caller-layout step beside it")
     ap.add_argument("--alpha0", type=float, default=1.0e-2,
                     help="opacity scale at z_min [1/m] (diagnostics: tiny values take the Taylor branch)")
     ap.add_argument("--dump-J", default="", help="rank 0 saves the (gathered) J of the last step as .npy")
@@ -173,9 +182,10 @@ def dump_outputs(dump_dir, J):
 
 def measure(args, workload, torch, dist, vrt, _lib, distributed, synth, rank, world, local, dev, rehearse,
             steps, warmup, cpu_baseline, dump_dir=""):
-    """One workload: setup, warm-up, timed steps, roofline, optional CPU baseline.  Returns the
-    result dict (rank 0 holds the CPU baseline / parity fields).  dump_dir: write the J of the last
-    timed step there (dump_outputs)."""
+    """One workload: setup, warm-up, timed steps, roofline; with --full the measurements that take runs of
+    their own (caller layout, critical path, triad) and optionally the CPU baseline.  Returns the result dict
+    (rank 0 holds the CPU baseline / parity fields).  dump_dir: write the J of the last timed step there
+    (dump_outputs)."""
     a, c, quad, nlam_total, per_angle, seed = WORKLOADS[workload]
     if args.nlam > 0 and workload == args.workload:
         nlam_total = args.nlam
@@ -376,7 +386,7 @@ def measure(args, workload, torch, dist, vrt, _lib, distributed, synth, rank, wo
             J_last = J
         dump_outputs(dump_dir, J_last)
         del J_last
-    if sj_native and not args.no_caller_layout:
+    if sj_native and args.full and not args.no_caller_layout:
         J_keep = J.clone()
         sweep_keep = plan.last_sweep_timing()
         sj_native = False
@@ -450,7 +460,7 @@ def measure(args, workload, torch, dist, vrt, _lib, distributed, synth, rank, wo
     # ONE wavelength pair, where bandwidth plays no role and only the per-layer launch + Gauss-Seidel
     # level chain of the most inclined angle is left
     floor_ms = None
-    if rank == 0 and world == 1 and groups is None and not f32 and nlam > 2 and not args.no_critical_path:
+    if args.full and rank == 0 and world == 1 and groups is None and not f32 and nlam > 2 and not args.no_critical_path:
         for _ in range(3):
             plan.execute_dev(2, nlam, S.data_ptr(), alpha.data_ptr(), alpha_mode, w_mine,
                              dJ=J.data_ptr(), dI0_up=I0_up.data_ptr(), stream=stream, f32=False)
@@ -463,7 +473,7 @@ def measure(args, workload, torch, dist, vrt, _lib, distributed, synth, rank, wo
     # practical ceiling of this box beside the vendor peak: a device triad b = a + b
     # over 2 x 1 GB (2 reads + 1 write per element), measured live
     triad_gbs = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         ta_ = torch.rand(1 << 27, device=dev, dtype=torch.float64)
         tb_ = torch.rand(1 << 27, device=dev, dtype=torch.float64)
         torch.add(ta_, tb_, out=tb_)
@@ -518,7 +528,8 @@ def measure(args, workload, torch, dist, vrt, _lib, distributed, synth, rank, wo
                 "step; per launch = / launches_per_step); `traffic` = fabric-side bytes of one step from "
                 "the committed rocprofv3 PMC passes, quoted only when that profile was taken with this "
                 "exact library; sweep_only = the sweep launches alone, with bytes that exclude the "
-                "16 B/update J read-modify-write done outside that window",
+                "16 B/update J read-modify-write done outside that window; triad_ceiling_GBs and critical_path_ms "
+                "take runs of their own and are measured with --full only",
     }
 
     # ---- CPU baseline: the oracle, threaded the way the reference is (angles serial, λ split
@@ -673,11 +684,11 @@ def main():
     dev = torch.device("cuda", local)
 
     out = measure(args, args.workload, torch, dist, vrt, _lib, distributed, synth, rank, world, local, dev,
-                  rehearse, args.steps, args.warmup, not args.no_cpu_baseline, dump_dir=args.dump_outputs)
+                  rehearse, args.steps, args.warmup, args.full and not args.no_cpu_baseline, dump_dir=args.dump_outputs)
     # BASELINE.json configs[1] (the reference's continuum case: ~250k sites x 12 angles x 1 λ) rides
-    # along as a secondary measurement of the default single-GPU run; the headline stays the
+    # along as a secondary measurement of the default single-GPU run with --full; the headline stays the
     # configuration the metric is quoted on (1M sites, 12 angles).
-    if world == 1 and args.workload == "C4" and args.nlam == 0 and args.dtype == "f64" \
+    if args.full and world == 1 and args.workload == "C4" and args.nlam == 0 and args.dtype == "f64" \
             and args.angle_groups == 1 and not args.no_secondary:
         sec = measure(args, "C2", torch, dist, vrt, _lib, distributed, synth, rank, world, local, dev,
                       rehearse, 20, 3, not args.no_cpu_baseline)

@@ -487,3 +487,33 @@ def test_bench_dump_outputs_is_the_J_of_the_timed_steps_and_repeats(tmp_path):
         assert np.array_equal(J, np.load(tmp_path / f"J_{run}.npy")) and np.isfinite(J).all() and (J > 0).any()
         outs.append(J)
     assert np.array_equal(outs[0], outs[1])
+
+
+def test_bench_plain_run_leaves_the_extra_measurements_to_full(tmp_path):
+    """A plain `bench.py` run times the steps and stops: no caller-layout step, critical path, triad or CPU baseline.
+    `--full` adds them (the caller-layout J bit for bit the headline's, the CPU oracle in parity with the timed J),
+    and both runs dump the same J of the last timed step."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop("VRT_PATH", None)
+    lines = {}
+    for run, extra in (("plain", []), ("full", ["--full"])):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", "3",
+               "--warmup", "1", "--dump-outputs", str(tmp_path / run)] + extra
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[run] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["roofline"]["step_event_ms"] > 0 and line["roofline"]["sweep_only"]["ms"] > 0
+    assert "caller_layout" not in plain and "cpu_baseline" not in plain and "parity_vs_oracle_max_rel_err" not in plain
+    assert plain["roofline"]["critical_path_ms"] is None and plain["roofline"]["triad_ceiling_GBs"] is None
+    assert full["caller_layout"]["bitwise_equal_J"] and full["caller_layout"]["ms_per_step"] > 0
+    assert full["roofline"]["critical_path_ms"] > 0 and full["roofline"]["triad_ceiling_GBs"] > 0
+    assert full["cpu_baseline"]["value"] > 0 and full["parity_vs_oracle_max_rel_err"] < RTOL
+    assert np.array_equal(np.load(tmp_path / "plain" / "J.npy"), np.load(tmp_path / "full" / "J.npy"))

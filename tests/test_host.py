@@ -934,3 +934,17 @@ def test_bench_dump_outputs_keeps_the_whole_J_or_a_fixed_sample_within_budget(tm
     assert np.all(np.diff(rows) > 0) and np.array_equal(a, J.numpy()[rows])
     bench.dump_outputs(str(tmp_path / "f32"), J[:10].to(torch.float32))
     assert np.load(tmp_path / "f32" / "J.npy").dtype == np.float32
+
+
+def test_bench_extra_measurements_are_opt_in(monkeypatch):
+    """bench.py: a plain run measures the headline only; `--full` opts into the measurements that take runs of their
+    own, and the --no-* switches still leave single parts of it out."""
+    import importlib.util
+    monkeypatch.setenv("OMP_WAIT_POLICY", os.environ.get("OMP_WAIT_POLICY", "passive"))   # bench.py sets a default
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    plain = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert not plain.full and (plain.steps, plain.warmup) == (5, 2)
+    full = bench.parse_args(["--full", "--no-secondary"])
+    assert full.full and full.no_secondary and not full.no_cpu_baseline

@@ -13,7 +13,7 @@ python3 tools/iteration_breakdown.py > gpurun_out/${tag}_iteration_breakdown.txt
 {
 for args in "--workload C2 --steps 50 --warmup 5" "--nlam 1 --steps 30 --warmup 3" "--nlam 3 --steps 30 --warmup 3" "--nlam 7 --steps 30 --warmup 3" "--nlam 13 --steps 20 --warmup 3" "--nlam 26 --steps 20 --warmup 3" "--workload C3 --steps 20 --warmup 3" "--steps 20 --warmup 3"; do
   for lay in native caller; do
-    python3 bench.py $args --sj-layout $lay --no-cpu-baseline --no-secondary --no-caller-layout 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('%-36s S/J %-7s ms/step %7.3f sweep %7.3f launches %4d critical_path_ms %s' % ('$args', '$lay' if 'sweep order' in d['config']['sj_layout'] or '$lay' == 'caller' else 'caller*', d['ms_per_step'], r['sweep_only']['ms'], r['launches_per_step'], r.get('critical_path_ms')))"
+    python3 bench.py --full $args --sj-layout $lay --no-cpu-baseline --no-secondary --no-caller-layout 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('%-36s S/J %-7s ms/step %7.3f sweep %7.3f launches %4d critical_path_ms %s' % ('$args', '$lay' if 'sweep order' in d['config']['sj_layout'] or '$lay' == 'caller' else 'caller*', d['ms_per_step'], r['sweep_only']['ms'], r['launches_per_step'], r.get('critical_path_ms')))"
   done
 done
 } > gpurun_out/${tag}_chain_sweep_final.txt 2>&1

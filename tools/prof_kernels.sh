@@ -2,7 +2,7 @@
 # diagnostics: per-kernel durations (rocprofv3 --kernel-trace --stats) of one bench configuration
 # usage: tools/prof_kernels.sh <tag> [bench args...]; env (VRT_*) is inherited
 tag=$1; shift
-out=gpurun_out/prof_$tag
+out=${VRT_RESULTS:-results}/prof_$tag
 rm -rf $out; mkdir -p $out
 export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o p -- python3 bench.py --workload C4 --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-critical-path --no-caller-layout "$@" > $out/bench.log 2>&1

@@ -2,15 +2,16 @@
 # diagnostics: per-kernel PMC sums (separate rocprofv3 --pmc passes, no tracing alongside) of ONE
 # bench step.  usage: tools/prof_pmc.sh <tag> [bench args...]; env (VRT_*) is inherited
 tag=$1; shift
+res=${VRT_RESULTS:-results}
 export TMPDIR=/tmp
 for pass in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" ${PMC_EXTRA:+"$PMC_EXTRA"}; do
   name=$(echo $pass | cut -d' ' -f1)
-  out=gpurun_out/pmc_${tag}_$name
+  out=$res/pmc_${tag}_$name
   rm -rf $out; mkdir -p $out
   timeout -k 10 300 rocprofv3 --pmc $pass --output-format csv -d $out -o p -- python3 bench.py --workload C4 --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --no-critical-path --no-caller-layout "$@" > $out/bench.log 2>&1 || { echo "pass $name failed"; tail -3 $out/bench.log; if [ "$pass" = "${PMC_EXTRA:-}" ]; then continue; fi; exit 1; }
   echo "pass $name done"
 done
-python3 - gpurun_out/pmc_${tag}_FETCH_SIZE gpurun_out/pmc_${tag}_WRITE_SIZE gpurun_out/pmc_${tag}_TCC_HIT_sum gpurun_out/pmc_${tag}_TCC_EA0_RDREQ_DRAM_sum <<'PY'
+python3 - $res/pmc_${tag}_FETCH_SIZE $res/pmc_${tag}_WRITE_SIZE $res/pmc_${tag}_TCC_HIT_sum $res/pmc_${tag}_TCC_EA0_RDREQ_DRAM_sum <<'PY'
 import csv, sys, glob, collections
 tot = collections.defaultdict(lambda: collections.defaultdict(float))
 calls = collections.Counter()

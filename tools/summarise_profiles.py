@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Copies the judged summaries of a tools/make_profiles.sh run from gpurun_out/ into profiles/<round>/
-(kernel-trace stats csv, bench JSON lines, and the per-kernel PMC sums inside c4_summary.json).
+"""Copies the judged summaries of a tools/make_profiles.sh run from its results folder ($VRT_RESULTS, default results/)
+into profiles/<round>/ (kernel-trace stats csv, bench JSON lines, and the per-kernel PMC sums inside c4_summary.json).
 
     python tools/summarise_profiles.py <tag> <round-dir>     e.g.  r2 r2
 
@@ -21,7 +21,7 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root)
 import bench  # noqa: E402  (source_digest, ONE_TIME_KERNELS)
 
-go, out = os.path.join(root, "gpurun_out"), os.path.join(root, "profiles", rnd)
+go, out = os.path.join(root, os.environ.get("VRT_RESULTS", "results")), os.path.join(root, "profiles", rnd)
 os.makedirs(out, exist_ok=True)
 
 stats_csv = glob.glob(os.path.join(go, f"prof_{tag}_default", "**", "*kernel_stats.csv"), recursive=True)[0]
