@@ -610,6 +610,61 @@ int vrt_regular_execute_dev(vrt_regular *r, int64_t n_solve, const double *k, co
                             int n_sweeps, double *dI_out, void *stream);
 int vrt_regular_last_solve_ms(const vrt_regular *r, double *ms);
 
+/* ---- emergent spectra: opacity / source function, top-plane intensity, tau = 1 heights ------------------------------
+ * The last step of a reference study (write_top_intensity, write_tau_unity and plotter, src/plot_utils.jl:61-140,
+ * :297-355, :434-576) on a regular raster.  Plain numbers in one unit system, constants folded in by the caller.
+ * Raster fields without ghost cells are (nz, nx, ny) Julia order, element [iz + nz*(ix + nx*iy)], one field after the
+ * other (the layout vrt_grid_to_raster_dev writes); the ghosted arrays carry the one-cell periodic border of
+ * periodic_borders (src/atmosphere.jl:191-214): (nz, nx + 2, ny + 2) per wavelength, wavelength slowest.
+ *
+ * vrt_synth_opacity_dev: for one direction k and nlam wavelengths, per raster point
+ *   gamma = gamma_static + gamma_unsold (n1 + n2),  a, v as vrt_line_opacity_dev with v_los = dot(velocity, -k),
+ *   alpha_l = strength_const (n1 Bij - n2 Bji) H(a, v) / (sqrt(pi) dlambda_D),  S_l = src_const / (g_ratio n1/n2 - 1),
+ *   S_c = planck2[l] / (exp(hc_over_kB / (lambda[l] T)) - 1),
+ *   S = (alpha_l S_l + alpha_c S_c) / (alpha_l + alpha_c),  alpha_tot = alpha_l + alpha_c
+ * written to d_S and d_alpha, ghosted; the ghost points hold their wrapped interior values bit for bit.
+ * nz, nx, ny are the interior sizes; velocity is 3 fields (z, x, y), populations >= 2 fields (n1, n2).  lambda and
+ * planck2 [nlam] on the host (chunk wavelengths by passing slices).  Runs on the calling thread's current HIP device,
+ * asynchronous on `stream`.
+ *
+ * vrt_regular_emergent_dev: r is a vrt_regular on the GHOSTED axes; dS, dalpha (nlam ghosted arrays).  Per wavelength
+ * an up solve along k with I_0 = the bottom plane of that wavelength's S; only the top plane's interior is written,
+ * dI_top (nlam, ny - 2, nx - 2) numpy order [l][iy][ix] (r's sizes).  Wavelengths go through in chunks whose workspace
+ * stays under a byte cap (8 GiB; VRT_REG_EMERGENT_BYTES, read at vrt_regular_create); bit-identical to the top interior
+ * plane of vrt_regular_execute_dev on the same inputs, whatever the chunking.  Asynchronous on `stream`.
+ *
+ * vrt_tau_unity_dev: d_alpha ghosted as above on the INTERIOR axes z[nz] (strictly ascending), x[nx], y[ny] (uniform,
+ * periodic with period nx dx, ny dy).  Per wavelength and column the tau of the path from the top plane along the
+ * up solve's characteristic traced back downward (plane iz at x + s k_x, y + s k_y, s = (z_top - z[iz]) / |k_z|,
+ * alpha interpolated bilinearly, trapezoid as cumtrapz); d_height (nlam, ny, nx) = the z of the first argmin
+ * |tau - 1|.  At k = (+-1, 0, 0) this is write_tau_unity(DATA) exactly; the inclined reference's defects are not
+ * reproduced.  Runs on the current HIP device and synchronises `stream`.
+ *
+ * Every argument is checked before the device is touched (k_z = 0 where a march needs it, |k| != 1, nlam < 1, axes,
+ * NULL pointers: VRT_EINVAL).  The host-pointer forms stage the arrays through `device` and return when done. */
+int vrt_synth_opacity_dev(int64_t nz, int64_t nx, int64_t ny, const double *k, int64_t nlam, const double *lambda,
+                          const double *planck2, double lambda0, double c0, double hc_over_kB, double strength_const,
+                          double Bij, double Bji, double src_const, double g_ratio, const double *d_velocity,
+                          const double *d_doppler, const double *d_gamma_static, const double *d_gamma_unsold,
+                          const double *d_temperature, const double *d_alpha_cont, const double *d_populations,
+                          double *d_S, double *d_alpha, void *stream);
+int vrt_synth_opacity(int device, int64_t nz, int64_t nx, int64_t ny, const double *k, int64_t nlam,
+                      const double *lambda, const double *planck2, double lambda0, double c0, double hc_over_kB,
+                      double strength_const, double Bij, double Bji, double src_const, double g_ratio,
+                      const double *velocity, const double *doppler, const double *gamma_static,
+                      const double *gamma_unsold, const double *temperature, const double *alpha_cont,
+                      const double *populations, double *S, double *alpha);
+int vrt_regular_emergent_dev(vrt_regular *r, const double *k, int64_t nlam, const double *dS, const double *dalpha,
+                             int n_sweeps, double *dI_top, void *stream);
+/* nz, nx, ny, z, x, y: the ghosted axes, as vrt_regular_create */
+int vrt_top_intensity(int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x, const double *y,
+                      const double *k, int64_t nlam, const double *S, const double *alpha, int n_sweeps, int device,
+                      double *I_top);
+int vrt_tau_unity_dev(int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x, const double *y,
+                      const double *k, int64_t nlam, const double *d_alpha, double *d_height, void *stream);
+int vrt_tau_unity(int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x, const double *y,
+                  const double *k, int64_t nlam, const double *alpha, int device, double *height);
+
 #ifdef __cplusplus
 }
 #endif

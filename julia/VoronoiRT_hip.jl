@@ -446,6 +446,52 @@ function rejection_sampling(n_sites::Integer, atmos, quantity::AbstractArray; se
     return p_vec * u"m"
 end
 
+# ---- the observable (write_top_intensity / write_tau_unity, src/plot_utils.jl:101-140, :434-576) -------------------------
+# S_λ, α_tot (nλ, nz, nx + 2, ny + 2) as plotter makes them on the periodic atmos (ghost border included); `atmos` gives
+# the axes WITH the border, as short_characteristics_up reads them.  Returns I_top (nλ, nx, ny) in S's unit per
+# steradian, the top plane's interior of each wavelength's up solve with I_0 = the bottom plane of S (vrt_top_intensity).
+function top_intensity(S_λ::AbstractArray{<:Any,4}, α_tot::AbstractArray{<:Any,4}, atmos, θ::Float64, ϕ::Float64;
+                       n_sweeps::Int=3, device::Integer=0)
+    k = [cos(θ*π/180), cos(ϕ*π/180)*sin(θ*π/180), sin(ϕ*π/180)*sin(θ*π/180)]
+    z = Vector{Float64}(ustrip.(u"m", atmos.z)); x = Vector{Float64}(ustrip.(u"m", atmos.x))
+    y = Vector{Float64}(ustrip.(u"m", atmos.y))
+    I_unit = unit(S_λ[1])
+    nl = size(S_λ, 1)
+    S = permutedims(Array{Float64,4}(ustrip.(S_λ)), (2, 3, 4, 1))        # (nz, nx, ny, nλ): one Julia array per λ
+    A = permutedims(Array{Float64,4}(ustrip.(u"m^-1", α_tot)), (2, 3, 4, 1))
+    size(S) == (length(z), length(x), length(y), nl) || error("S_λ must be (nλ, nz, nx, ny) on atmos's axes")
+    I = Array{Float64,3}(undef, length(x) - 2, length(y) - 2, nl)
+    GC.@preserve z x y k S A I begin
+        check(ccall((:vrt_top_intensity, libvrt), Cint,
+                    (Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64},
+                     Ptr{Float64}, Cint, Cint, Ptr{Float64}),
+                    length(z), length(x), length(y), z, x, y, k, nl, S, A, n_sweeps, device, I))
+    end
+    return permutedims(I, (3, 1, 2)) * I_unit
+end
+
+# Heights of τ = 1 (nλ, nx, ny) in metres for α_tot (nλ, nz, nx + 2, ny + 2) with the periodic ghost border; `atmos`
+# gives the INTERIOR axes (periodic = false, as write_tau_unity reads them).  θ = 180° is write_tau_unity(DATA)
+# exactly; an inclined direction follows the solver's characteristic (INTEGRATION.md: the reference's inclined
+# method is not reproduced).
+function tau_unity(α_tot::AbstractArray{<:Any,4}, atmos, θ::Float64, ϕ::Float64; device::Integer=0)
+    k = [cos(θ*π/180), cos(ϕ*π/180)*sin(θ*π/180), sin(ϕ*π/180)*sin(θ*π/180)]
+    θ == 180.0 && (k = [-1.0, 0.0, 0.0])
+    z = Vector{Float64}(ustrip.(u"m", atmos.z)); x = Vector{Float64}(ustrip.(u"m", atmos.x))
+    y = Vector{Float64}(ustrip.(u"m", atmos.y))
+    nl = size(α_tot, 1)
+    A = permutedims(Array{Float64,4}(ustrip.(u"m^-1", α_tot)), (2, 3, 4, 1))
+    size(A) == (length(z), length(x) + 2, length(y) + 2, nl) || error("α_tot must be (nλ, nz, nx + 2, ny + 2)")
+    H = Array{Float64,3}(undef, length(x), length(y), nl)
+    GC.@preserve z x y k A H begin
+        check(ccall((:vrt_tau_unity, libvrt), Cint,
+                    (Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64},
+                     Cint, Ptr{Float64}),
+                    length(z), length(x), length(y), z, x, y, k, nl, A, device, H))
+    end
+    return permutedims(H, (3, 1, 2)) * u"m"
+end
+
 end # module
 
 # ---- drop-in redefinitions (same signatures as the reference's methods) --------------------------

@@ -143,6 +143,17 @@ PROTOTYPES = {
     "vrt_regular_execute_dev": (ctypes.c_int, [vp, c_i64, p_dbl, p_int, vp, c_i64, vp, c_i64, c_i64, vp,
                                                ctypes.c_int, vp, vp]),
     "vrt_regular_last_solve_ms": (ctypes.c_int, [vp, p_dbl]),
+    "vrt_synth_opacity_dev": (ctypes.c_int, [c_i64, c_i64, c_i64, p_dbl, c_i64, p_dbl, p_dbl, c_dbl, c_dbl, c_dbl, c_dbl,
+                                             c_dbl, c_dbl, c_dbl, c_dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "vrt_synth_opacity": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64, p_dbl, c_i64, p_dbl, p_dbl, c_dbl, c_dbl,
+                                         c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, p_dbl, p_dbl, p_dbl, p_dbl, p_dbl,
+                                         p_dbl, p_dbl, p_dbl, p_dbl]),
+    "vrt_regular_emergent_dev": (ctypes.c_int, [vp, p_dbl, c_i64, vp, vp, ctypes.c_int, vp, vp]),
+    "vrt_top_intensity": (ctypes.c_int, [c_i64, c_i64, c_i64, p_dbl, p_dbl, p_dbl, p_dbl, c_i64, p_dbl, p_dbl,
+                                         ctypes.c_int, ctypes.c_int, p_dbl]),
+    "vrt_tau_unity_dev": (ctypes.c_int, [c_i64, c_i64, c_i64, p_dbl, p_dbl, p_dbl, p_dbl, c_i64, vp, vp, vp]),
+    "vrt_tau_unity": (ctypes.c_int, [c_i64, c_i64, c_i64, p_dbl, p_dbl, p_dbl, p_dbl, c_i64, p_dbl, ctypes.c_int,
+                                     p_dbl]),
     "vrt_grid_nearest": (ctypes.c_int, [vp, c_i64, p_dbl, ctypes.c_int, ctypes.c_int, p_i64, p_dbl]),
     "vrt_grid_to_raster_dev": (ctypes.c_int, [vp, c_i64, c_i64, c_i64, p_dbl, p_dbl, p_dbl, ctypes.c_int, ctypes.c_int,
                                               c_i64, c_i64, vp, vp, vp]),

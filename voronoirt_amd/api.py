@@ -732,6 +732,191 @@ class RegularSolver:
             pass
 
 
+# ---- emergent spectra (src/plot_utils.jl: plotter :297-355, write_top_intensity :101-140, write_tau_unity :434-576) ----
+SYNTH_FIELDS = ("velocity", "doppler", "gamma_static", "gamma_unsold", "temperature", "alpha_cont")
+
+
+def periodic_axis(a) -> np.ndarray:
+    """periodic_borders of an axis (src/atmosphere.jl:166-181): one ghost point either side, spaced a[1] - a[0]."""
+    a = _f64(a).ravel()
+    d = a[1] - a[0]
+    return np.concatenate([[a[0] - d], a, [a[-1] + d]])
+
+
+def _synth_consts(case, src_const, g_ratio):
+    return (float(case.lambda0), float(case.c0), float(case.hc_over_kB), float(case.strength_const), float(case.Bij),
+            float(case.Bji), float(src_const), float(g_ratio))
+
+
+def _raster_inputs(raster, populations=None):
+    """the raster's axes and fields as contiguous float64: velocity (3, ny, nx, nz), the others (ny, nx, nz),
+    populations (nf >= 2, ny, nx, nz) of which the first two are used"""
+    z, x, y = _axes(raster["z"], raster["x"], raster["y"])
+    shape = (y.size, x.size, z.size)
+    f = {}
+    for name in SYNTH_FIELDS:
+        a = _f64(raster[name])
+        want = (3,) + shape if name == "velocity" else shape
+        if a.shape != want:
+            raise ValueError(f"raster field {name} has shape {a.shape}, expected {want}")
+        f[name] = a
+    if populations is not None:
+        p = _f64(populations)
+        if p.ndim != 4 or p.shape[0] < 2 or p.shape[1:] != shape:
+            raise ValueError(f"populations have shape {p.shape}, expected (nf >= 2,) + {shape}")
+        f["populations"] = np.ascontiguousarray(p[:2])
+    return z, x, y, f
+
+
+def synth_opacity(k, raster, populations, case, src_const: float, g_ratio: float = 4.0, lam=None, planck2=None,
+                  device: int = 0):
+    """plotter (src/plot_utils.jl:297-355) for one direction k on a raster (`vrt_synth_opacity`): the source function
+    S = (α_l S_l + α_c S_c)/(α_l + α_c) and α_tot = α_l + α_c of every wavelength, with the periodic ghost border of
+    periodic_borders.  `raster`: dict of the axes z, x, y and the fields velocity (3, ny, nx, nz) [z, x, y components],
+    doppler, gamma_static, gamma_unsold, temperature, alpha_cont (ny, nx, nz); populations (nf >= 2, ny, nx, nz) as
+    Voronoi_to_Raster_inv_dist returns them.  `case` gives lambda0, c0, hc_over_kB, strength_const, Bij, Bji and, unless
+    passed, lam and planck2 (a LineCase does); src_const = 2hc²/λ0⁵, g_ratio = g_u/g_l (source_line, line.jl:385-393).
+    Returns S, alpha, each (nlam, ny + 2, nx + 2, nz)."""
+    z, x, y, f = _raster_inputs(raster, populations)
+    lam = _f64(case.lam if lam is None else lam).ravel()
+    planck2 = _f64(case.planck2 if planck2 is None else planck2).ravel()
+    if planck2.size != lam.size:
+        raise ValueError("lam and planck2 must have the same length")
+    k = _f64(k).ravel()
+    shape = (lam.size, y.size + 2, x.size + 2, z.size)
+    S, A = np.zeros(shape), np.zeros(shape)
+    check(_lib.load().vrt_synth_opacity(int(device), z.size, x.size, y.size, _d(k), lam.size, _d(lam), _d(planck2),
+                                        *_synth_consts(case, src_const, g_ratio),
+                                        *[_d(f[n]) for n in SYNTH_FIELDS + ("populations",)], _d(S), _d(A)))
+    return S, A
+
+
+def synth_opacity_dev(k, nz: int, nx: int, ny: int, case, src_const: float, d_fields: dict, d_populations: int,
+                      d_S: int, d_alpha: int, g_ratio: float = 4.0, lam=None, planck2=None, stream: int = 0) -> None:
+    """Device form (`vrt_synth_opacity_dev`, on the current device, asynchronous on `stream`): d_fields maps
+    SYNTH_FIELDS to device pointers (torch data_ptr()) of the layouts of `synth_opacity`; d_S, d_alpha receive
+    (nlam, ny + 2, nx + 2, nz).  Chunk wavelengths by passing slices of lam / planck2."""
+    lam = _f64(case.lam if lam is None else lam).ravel()
+    planck2 = _f64(case.planck2 if planck2 is None else planck2).ravel()
+    if planck2.size != lam.size:
+        raise ValueError("lam and planck2 must have the same length")
+    k = _f64(k).ravel()
+    check(_lib.load().vrt_synth_opacity_dev(int(nz), int(nx), int(ny), _d(k), lam.size, _d(lam), _d(planck2),
+                                            *_synth_consts(case, src_const, g_ratio),
+                                            *[d_fields[n] or None for n in SYNTH_FIELDS], d_populations or None,
+                                            d_S or None, d_alpha or None, stream or None))
+
+
+def top_intensity(k, S, alpha, z, x, y, n_sweeps: int = 3, device: int = 0) -> np.ndarray:
+    """write_top_intensity (src/plot_utils.jl:101-140) for one direction (`vrt_top_intensity`): per wavelength
+    short_characteristics_up with I_0 = the bottom plane of S, of which the top plane's interior is returned,
+    (nlam, ny, nx).  S, alpha (nlam, ny + 2, nx + 2, nz) with the periodic ghost border; z, x, y the raster's own
+    (interior) axes -- the solver's are periodic_axis(x), periodic_axis(y)."""
+    z, xg, yg = _f64(z).ravel(), periodic_axis(x), periodic_axis(y)
+    S, alpha = _f64(S), _f64(alpha)
+    shape = (yg.size, xg.size, z.size)
+    if S.ndim != 4 or S.shape[1:] != shape or alpha.shape != S.shape:
+        raise ValueError(f"S and alpha must be (nlam,) + {shape}, got {S.shape} and {alpha.shape}")
+    nlam = S.shape[0]
+    k = _f64(k).ravel()
+    out = np.zeros((nlam, yg.size - 2, xg.size - 2))
+    check(_lib.load().vrt_top_intensity(z.size, xg.size, yg.size, _d(z), _d(xg), _d(yg), _d(k), nlam, _d(S), _d(alpha),
+                                        int(n_sweeps), int(device), _d(out)))
+    return out
+
+
+def top_intensity_dev(solver: "RegularSolver", k, nlam: int, dS: int, dalpha: int, dI_top: int, n_sweeps: int = 3,
+                      stream: int = 0) -> None:
+    """Device form (`vrt_regular_emergent_dev`): `solver` is a RegularSolver on the ghosted axes, dS / dalpha hold
+    nlam ghosted arrays, dI_top receives (nlam, ny - 2, nx - 2) of the solver's sizes.  Asynchronous on `stream`."""
+    k = _f64(k).ravel()
+    check(_lib.load().vrt_regular_emergent_dev(solver._h, _d(k), int(nlam), dS or None, dalpha or None, int(n_sweeps),
+                                               dI_top or None, stream or None))
+
+
+def tau_unity(k, alpha, z, x, y, device: int = 0) -> np.ndarray:
+    """Heights of τ = 1 (write_tau_unity, src/plot_utils.jl:434-576; `vrt_tau_unity`) along the up solve's
+    characteristic of direction k, traced back from the top plane: alpha (nlam, ny + 2, nx + 2, nz) ghosted, z, x, y
+    the interior axes (x, y uniform, periodic).  Returns (nlam, ny, nx) heights.  At k = (±1, 0, 0) this is
+    write_tau_unity(DATA) exactly; the inclined reference's defects are not reproduced."""
+    z, x, y = _axes(z, x, y)
+    alpha = _f64(alpha)
+    shape = (y.size + 2, x.size + 2, z.size)
+    if alpha.ndim != 4 or alpha.shape[1:] != shape:
+        raise ValueError(f"alpha must be (nlam,) + {shape}, got {alpha.shape}")
+    nlam = alpha.shape[0]
+    k = _f64(k).ravel()
+    out = np.zeros((nlam, y.size, x.size))
+    check(_lib.load().vrt_tau_unity(z.size, x.size, y.size, _d(z), _d(x), _d(y), _d(k), nlam, _d(alpha), int(device),
+                                    _d(out)))
+    return out
+
+
+def tau_unity_dev(k, z, x, y, nlam: int, d_alpha: int, d_height: int, stream: int = 0) -> None:
+    """Device form (`vrt_tau_unity_dev`, on the current device): d_alpha (nlam, ny + 2, nx + 2, nz), d_height
+    (nlam, ny, nx).  Synchronises `stream`."""
+    z, x, y = _axes(z, x, y)
+    k = _f64(k).ravel()
+    check(_lib.load().vrt_tau_unity_dev(z.size, x.size, y.size, _d(z), _d(x), _d(y), _d(k), int(nlam), d_alpha or None,
+                                        d_height or None, stream or None))
+
+
+def emergent_spectrum(sites: "VoronoiSites", populations, raster, case, theta: float, phi: float, *, src_const: float,
+                      g_ratio: float = 4.0, n_sweeps: int = 3, tau: bool = False, chunk: int = 0,
+                      periodic: bool = False, device: int = 0):
+    """The observable of a study, on the device: read_irregular's resampling of the site populations (n, nf >= 2) onto
+    the raster (Voronoi_to_Raster_inv_dist, src/plot_utils.jl:252-295), plotter's S and α_tot for the direction (θ, ϕ)
+    in degrees (:297-355), write_top_intensity's solve (:101-140) and, with `tau`, write_tau_unity's heights
+    (:434-576), wavelength chunk by chunk (`chunk` wavelengths; 0: S and α of a chunk within 4 GiB).  `raster` and
+    `case` as in synth_opacity.  Only the results leave the device: returns I_top (nlam, ny, nx), and with `tau` also
+    the heights (nlam, ny, nx)."""
+    import torch
+
+    z, x, y, f = _raster_inputs(raster)
+    pops = _f64(populations)
+    if pops.ndim != 2 or pops.shape[0] != sites.n or pops.shape[1] < 2:
+        raise ValueError(f"populations must be (n, nf >= 2) with n = {sites.n}, got {pops.shape}")
+    if not all(np.all(np.diff(a) > 0) for a in (z, x, y)) or min(z.size, x.size, y.size) < 2:
+        raise ValueError("the raster axes must be ascending with at least two points each")
+    lam, planck2 = _f64(case.lam).ravel(), _f64(case.planck2).ravel()
+    nz, nx, ny, nlam = z.size, x.size, y.size, lam.size
+    volg = nz * (nx + 2) * (ny + 2)
+    chunk = int(chunk) if chunk > 0 else max(1, (4 << 30) // (16 * volg))
+    chunk = min(chunk, nlam)
+    k = direction(theta, phi)
+    dev = torch.device("cuda", int(device))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+
+        def up(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        d_site = up(pops[:, :2])
+        d_pops = torch.empty((2, ny, nx, nz), dtype=torch.float64, device=dev)
+        Voronoi_to_Raster_dev(sites, z, x, y, 2, 2, d_site.data_ptr(), d_pops.data_ptr(), inv_dist=True,
+                              periodic=periodic, stream=stream)
+        d_f = {n: up(f[n]) for n in SYNTH_FIELDS}
+        ptr = {n: t.data_ptr() for n, t in d_f.items()}
+        d_S = torch.empty((chunk, ny + 2, nx + 2, nz), dtype=torch.float64, device=dev)
+        d_A = torch.empty_like(d_S)
+        I_top = torch.empty((nlam, ny, nx), dtype=torch.float64, device=dev)
+        H = torch.empty_like(I_top) if tau else None
+        solver = RegularSolver(z, periodic_axis(x), periodic_axis(y), device=int(device))
+        try:
+            for l0 in range(0, nlam, chunk):
+                nc = min(chunk, nlam - l0)
+                synth_opacity_dev(k, nz, nx, ny, case, src_const, ptr, d_pops.data_ptr(), d_S.data_ptr(), d_A.data_ptr(),
+                                  g_ratio=g_ratio, lam=lam[l0:l0 + nc], planck2=planck2[l0:l0 + nc], stream=stream)
+                top_intensity_dev(solver, k, nc, d_S.data_ptr(), d_A.data_ptr(), I_top[l0].data_ptr(), n_sweeps,
+                                  stream=stream)
+                if tau:
+                    tau_unity_dev(k, z, x, y, nc, d_A.data_ptr(), H[l0].data_ptr(), stream=stream)
+            torch.cuda.current_stream(dev).synchronize()
+        finally:
+            solver.close()
+        out = I_top.cpu().numpy()
+        return (out, H.cpu().numpy()) if tau else out
+
+
 # ---- resampling between the sites and regular rasters (SURVEY row 14) -------------------------------------------------
 def _metric(periodic: bool) -> int:
     return _lib.METRIC_PERIODIC_XY if periodic else _lib.METRIC_EUCLIDEAN

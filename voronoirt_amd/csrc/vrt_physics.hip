@@ -613,4 +613,175 @@ int launch_rates_populations(vrt_grid *g, int64_t nlam, int64_t ld, const int64_
     return VRT_OK;
 }
 
+// ---- raster opacity and source function for an emergent spectrum (plotter, src/plot_utils.jl:297-355) -------------------
+// One thread per point of the GHOSTED output (nz, nx + 2, ny + 2): a ghost point evaluates the interior point it wraps to
+// (periodic_borders, src/atmosphere.jl:191-214) with the same instructions, so it holds that value bit for bit and the
+// regular solver reads the arrays as they are.  The point's fields are read once and the launch's wavelengths walked;
+// per (point, wavelength) one Voigt profile -- humlicek_w4_re, as k_line_opacity -- and one Planck function:
+//   alpha_l = strength_const (n1 Bij - n2 Bji) H(a, v) / (sqrt(pi) dlambda_D)   line.jl:121-137, :219-225
+//   S_l = src_const / (g_ratio n1 / n2 - 1)      source_line (line.jl:385-393)     S_c = planck2 / (exp(hc/kB / (lambda T)) - 1)
+//   S = (alpha_l S_l + alpha_c S_c) / (alpha_l + alpha_c),  alpha_tot = alpha_l + alpha_c
+// The per-point divisors are folded as in k_line_opacity (last-bit differences from the oracle; contract 1e-12).
+constexpr int kSynthLam = 32;                        // wavelengths of one launch, passed by value
+struct SynthLam { double lam[kSynthLam], planck2[kSynthLam]; };
+struct SynthArgs {
+    int64_t nz, nx, ny;                              // interior raster
+    double k[3], lambda0, c0, hc_over_kB, strength_const, Bij, Bji, src_const, g_ratio;
+    const double *velocity, *doppler, *gamma_static, *gamma_unsold, *temperature, *alpha_cont, *pops;
+    double *S, *alpha;                               // (nlam, ny + 2, nx + 2, nz) numpy order
+};
+
+__global__ void __launch_bounds__(256)
+k_synth_opacity(SynthArgs sa, SynthLam sl, int64_t l0, int nl)
+{
+    exp2_table_fill();
+    __syncthreads();
+    const int64_t nz = sa.nz, nx = sa.nx, ny = sa.ny, nxg = nx + 2, nyg = ny + 2, volg = nz * nxg * nyg;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= volg) return;
+    const int64_t iz = t % nz, gx = (t / nz) % nxg, gy = t / (nz * nxg);
+    const int64_t ix = gx == 0 ? nx - 1 : gx == nxg - 1 ? 0 : gx - 1;      // ghost column 1 = arr[:, end, :] (:200)
+    const int64_t iy = gy == 0 ? ny - 1 : gy == nyg - 1 ? 0 : gy - 1;
+    const int64_t vol = nz * nx * ny, i = iz + nz * (ix + nx * iy);
+    const double n1 = sa.pops[i], n2 = sa.pops[i + vol];
+    // v_los = dot(velocity, -k)   (line.jl:126, :205)
+    const double v_los = sa.velocity[i] * (-sa.k[0]) + sa.velocity[i + vol] * (-sa.k[1]) + sa.velocity[i + 2 * vol] * (-sa.k[2]);
+    const double dD = sa.doppler[i], ac = sa.alpha_cont[i], T = sa.temperature[i];
+    const double gamma = sa.gamma_static[i] + sa.gamma_unsold[i] * (n1 + n2);      // γ_constant, broadening.jl:63-82
+    const double strength = sa.strength_const * (n1 * sa.Bij - n2 * sa.Bji);
+    const double S_l = sa.src_const / (sa.g_ratio * n1 / n2 - 1.0);
+    const double r_dD = 1.0 / dD;
+    const double ga = gamma / (4.0 * kPi * sa.c0 * dD);
+    const double sp = strength / (sqrt(kPi) * dD);
+    const double shift = sa.lambda0 * v_los / sa.c0;
+    for (int l = 0; l < nl; l++) {
+        const double lam = sl.lam[l];
+        const double a = ga * (lam * lam);
+        const double v = (lam - sa.lambda0 + shift) * r_dD;
+        const double al = sp * humlicek_w4_re(v, a);
+        const double S_c = sl.planck2[l] / (exp(sa.hc_over_kB / (lam * T)) - 1.0);
+        const int64_t o = (l0 + l) * volg + t;
+        sa.alpha[o] = al + ac;
+        sa.S[o] = (al * S_l + ac * S_c) / (al + ac);
+    }
+}
+
 }  // namespace vrt
+
+using namespace vrt;
+
+static int synth_opacity_checks(int64_t nz, int64_t nx, int64_t ny, const double *k, int64_t nlam, const double *lambda,
+                                const double *planck2, const void *velocity, const void *doppler, const void *gamma_static,
+                                const void *gamma_unsold, const void *temperature, const void *alpha_cont,
+                                const void *populations, const void *S, const void *alpha)
+{
+    if (!k || !lambda || !planck2 || !velocity || !doppler || !gamma_static || !gamma_unsold || !temperature ||
+        !alpha_cont || !populations || !S || !alpha)
+        return fail(VRT_EINVAL, "NULL argument");
+    if (nz < 1 || nx < 1 || ny < 1) return fail(VRT_EINVAL, "raster sizes must be >= 1");
+    if (nlam < 1) return fail(VRT_EINVAL, "nlam must be >= 1");
+    if (S == alpha) return fail(VRT_EINVAL, "S and alpha must be distinct arrays");
+    const double nrm = std::sqrt(k[0] * k[0] + k[1] * k[1] + k[2] * k[2]);
+    if (!(std::fabs(nrm - 1.0) < 1e-6)) return fail(VRT_EINVAL, "k is not a unit vector");
+    return VRT_OK;
+}
+
+static int current_device(int *dev)
+{
+    int cnt = 0;
+    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0)
+        return fail(VRT_ENODEVICE, "no HIP device available (libvrt_hip has no CPU fallback)");
+    VRT_HIP_TRY(hipGetDevice(dev));
+    (void)hipGetLastError();           // (an earlier call's error is not this entry point's)
+    return VRT_OK;
+}
+
+static int synth_opacity_launch(int64_t nz, int64_t nx, int64_t ny, const double *k, int64_t nlam, const double *lambda,
+                                const double *planck2, double lambda0, double c0, double hc_over_kB, double strength_const,
+                                double Bij, double Bji, double src_const, double g_ratio, const double *d_velocity,
+                                const double *d_doppler, const double *d_gamma_static, const double *d_gamma_unsold,
+                                const double *d_temperature, const double *d_alpha_cont, const double *d_populations,
+                                double *d_S, double *d_alpha, hipStream_t st)
+{
+    SynthArgs sa;
+    sa.nz = nz; sa.nx = nx; sa.ny = ny;
+    for (int j = 0; j < 3; j++) sa.k[j] = k[j];
+    sa.lambda0 = lambda0; sa.c0 = c0; sa.hc_over_kB = hc_over_kB; sa.strength_const = strength_const;
+    sa.Bij = Bij; sa.Bji = Bji; sa.src_const = src_const; sa.g_ratio = g_ratio;
+    sa.velocity = d_velocity; sa.doppler = d_doppler; sa.gamma_static = d_gamma_static; sa.gamma_unsold = d_gamma_unsold;
+    sa.temperature = d_temperature; sa.alpha_cont = d_alpha_cont; sa.pops = d_populations;
+    sa.S = d_S; sa.alpha = d_alpha;
+    const int64_t volg = nz * (nx + 2) * (ny + 2);
+    for (int64_t l0 = 0; l0 < nlam; l0 += kSynthLam) {
+        const int nl = (int)std::min<int64_t>(kSynthLam, nlam - l0);
+        SynthLam sl;
+        std::memset(&sl, 0, sizeof(sl));
+        for (int l = 0; l < nl; l++) {
+            sl.lam[l] = lambda[l0 + l];
+            sl.planck2[l] = planck2[l0 + l];
+        }
+        hipLaunchKernelGGL(k_synth_opacity, dim3((unsigned)((volg + 255) / 256)), dim3(256), 0, st, sa, sl, l0, nl);
+    }
+    VRT_HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+extern "C" int vrt_synth_opacity_dev(int64_t nz, int64_t nx, int64_t ny, const double *k, int64_t nlam,
+                                     const double *lambda, const double *planck2, double lambda0, double c0,
+                                     double hc_over_kB, double strength_const, double Bij, double Bji, double src_const,
+                                     double g_ratio, const double *d_velocity, const double *d_doppler,
+                                     const double *d_gamma_static, const double *d_gamma_unsold,
+                                     const double *d_temperature, const double *d_alpha_cont,
+                                     const double *d_populations, double *d_S, double *d_alpha, void *stream)
+{
+    DeviceScope scope;
+    int rc = synth_opacity_checks(nz, nx, ny, k, nlam, lambda, planck2, d_velocity, d_doppler, d_gamma_static,
+                                  d_gamma_unsold, d_temperature, d_alpha_cont, d_populations, d_S, d_alpha);
+    if (rc) return rc;
+    int dev = 0;
+    if ((rc = current_device(&dev))) return rc;
+    return synth_opacity_launch(nz, nx, ny, k, nlam, lambda, planck2, lambda0, c0, hc_over_kB, strength_const, Bij, Bji,
+                                src_const, g_ratio, d_velocity, d_doppler, d_gamma_static, d_gamma_unsold, d_temperature,
+                                d_alpha_cont, d_populations, d_S, d_alpha, (hipStream_t)stream);
+}
+
+extern "C" int vrt_synth_opacity(int device, int64_t nz, int64_t nx, int64_t ny, const double *k, int64_t nlam,
+                                 const double *lambda, const double *planck2, double lambda0, double c0,
+                                 double hc_over_kB, double strength_const, double Bij, double Bji, double src_const,
+                                 double g_ratio, const double *velocity, const double *doppler, const double *gamma_static,
+                                 const double *gamma_unsold, const double *temperature, const double *alpha_cont,
+                                 const double *populations, double *S, double *alpha)
+{
+    DeviceScope scope;
+    int rc = synth_opacity_checks(nz, nx, ny, k, nlam, lambda, planck2, velocity, doppler, gamma_static, gamma_unsold,
+                                  temperature, alpha_cont, populations, S, alpha);
+    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
+    const size_t vol = (size_t)(nz * nx * ny), out = (size_t)(nz * (nx + 2) * (ny + 2)) * (size_t)nlam;
+    // one device block: velocity (3) | doppler | gamma_static | gamma_unsold | temperature | alpha_cont | populations (2)
+    // | S | alpha
+    double *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, sizeof(double) * (10 * vol + 2 * out));
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
+    const double *src[7] = {velocity, doppler, gamma_static, gamma_unsold, temperature, alpha_cont, populations};
+    const size_t len[7] = {3 * vol, vol, vol, vol, vol, vol, 2 * vol};
+    double *dp[7] = {};
+    size_t off = 0;
+    for (int f = 0; f < 7 && e == hipSuccess; f++) {
+        dp[f] = d + off;
+        e = hipMemcpy(dp[f], src[f], sizeof(double) * len[f], hipMemcpyHostToDevice);
+        off += len[f];
+    }
+    double *dS = d + off, *dA = dS + out;
+    if (e != hipSuccess) rc = fail(VRT_ENODEVICE, std::string("vrt_synth_opacity: ") + hipGetErrorString(e));
+    if (!rc)
+        rc = synth_opacity_launch(nz, nx, ny, k, nlam, lambda, planck2, lambda0, c0, hc_over_kB, strength_const, Bij, Bji,
+                                  src_const, g_ratio, dp[0], dp[1], dp[2], dp[3], dp[4], dp[5], dp[6], dS, dA, nullptr);
+    if (!rc && ((e = hipDeviceSynchronize()) != hipSuccess ||
+                (e = hipMemcpy(S, dS, sizeof(double) * out, hipMemcpyDeviceToHost)) != hipSuccess ||
+                (e = hipMemcpy(alpha, dA, sizeof(double) * out, hipMemcpyDeviceToHost)) != hipSuccess))
+        rc = fail(VRT_ENODEVICE, std::string("vrt_synth_opacity: ") + hipGetErrorString(e));
+    (void)hipFree(d);
+    return rc;
+}

@@ -741,6 +741,32 @@ k_reg_xy_march_lds(RegArgs ra, const double *__restrict__ xy, int64_t solve0)
 
 #undef PL
 
+// ---- emergent intensity (write_top_intensity, src/plot_utils.jl:101-140): per wavelength the bottom plane of S is I_0
+// (:117-118), and of the solution only the top plane's interior is kept (:122)
+// I0[s][iy][ix] = S[s](iz = 0, ix, iy), S in the caller's (nz, nx, ny) order, one array of vol per solve
+__global__ void __launch_bounds__(256)
+k_reg_bottom_plane(int nz, int nx, int ny, int64_t n_solve, const double *__restrict__ S, double *__restrict__ I0)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t plane = (int64_t)nx * ny;
+    if (t >= plane * n_solve) return;
+    const int64_t s = t / plane, p = t - s * plane;      // p = ix + nx*iy
+    I0[t] = S[s * plane * nz + p * nz];
+}
+
+// top[s][iy - 1][ix - 1] = I[s][nz - 1][iy][ix] for the interior points of the plane-major intensities
+__global__ void __launch_bounds__(256)
+k_reg_top_interior(int nz, int nx, int ny, int64_t n_solve, const double *__restrict__ I, double *__restrict__ top)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int mx = nx - 2, my = ny - 2;
+    const int64_t inner = (int64_t)mx * my, plane = (int64_t)nx * ny;
+    if (t >= inner * n_solve) return;
+    const int64_t s = t / inner, q = t - s * inner;
+    const int ix = 1 + (int)(q % mx), iy = 1 + (int)(q / mx);
+    top[t] = I[(s * nz + (nz - 1)) * plane + ix + (int64_t)nx * iy];
+}
+
 }  // namespace vrt
 
 using namespace vrt;
@@ -759,13 +785,16 @@ struct vrt_regular {
     int force_threads = 0;                 // VRT_REG_THREADS, read once at creation (tests: forces the launch shape)
     int xy_split = 1;                      // VRT_REG_XY (creation): 0 = all-xy batches through k_regular_solve too;
                                            //   2 = split, upwind plane read from memory instead of LDS (tests)
+    double *d_I0 = nullptr;                // vrt_regular_emergent_dev: the bottom planes of S of one chunk
+    int64_t cap_I0 = 0;
+    int64_t emergent_bytes = (int64_t)8 << 30;  // VRT_REG_EMERGENT_BYTES (creation): workspace cap of an emergent chunk
 };
 
 static void regular_free(vrt_regular *r)
 {
     if (!r) return;
     for (void *p : {(void *)r->d_g, (void *)r->d_S, (void *)r->d_A, (void *)r->d_I, (void *)r->d_k, (void *)r->d_up,
-                    (void *)r->d_coef, (void *)r->d_xy})
+                    (void *)r->d_coef, (void *)r->d_xy, (void *)r->d_I0})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : r->ev)
         if (e) (void)hipEventDestroy(e);
@@ -787,6 +816,7 @@ extern "C" int vrt_regular_create(int64_t nz, int64_t nx, int64_t ny, const doub
     vrt_regular *r = new vrt_regular;
     if (const char *e = std::getenv("VRT_REG_THREADS")) r->force_threads = std::max(64, std::min(1024, std::atoi(e) / 64 * 64));
     if (const char *e = std::getenv("VRT_REG_XY")) r->xy_split = std::max(0, std::min(2, std::atoi(e)));
+    if (const char *e = std::getenv("VRT_REG_EMERGENT_BYTES")) r->emergent_bytes = std::max<int64_t>(1, std::atoll(e));
     r->device = device;
     r->nz = nz; r->nx = nx; r->ny = ny;
     r->h_g.assign(z, z + nz);
@@ -822,19 +852,8 @@ static int regular_grow(double *&buf, int64_t &cap, int64_t need, size_t per)
     return VRT_OK;
 }
 
-// dS, dalpha, dI0, dI_out: device pointers in the caller's (Julia) layouts; k, up: host
-extern "C" int vrt_regular_execute_dev(vrt_regular *r, int64_t n_solve, const double *k, const int *up,
-                                       const double *dS, int64_t S_stride, const double *dalpha,
-                                       int64_t alpha_stride, int64_t field_period, const double *dI0,
-                                       int n_sweeps, double *dI_out, void *stream)
+static int regular_check_k(int64_t n_solve, const double *k)
 {
-    DeviceScope scope;
-    if (field_period < 0 || field_period > n_solve) return fail(VRT_EINVAL, "field_period must be in [0, n_solve]");
-    if (!r || !k || !up || !dS || !dalpha || !dI0 || !dI_out) return fail(VRT_EINVAL, "NULL argument");
-    if (n_solve < 1 || n_sweeps < 1) return fail(VRT_EINVAL, "bad sizes");
-    const int64_t nz = r->nz, nx = r->nx, ny = r->ny, vol = nz * nx * ny;
-    if ((S_stride != 0 && S_stride != vol) || (alpha_stride != 0 && alpha_stride != vol))
-        return fail(VRT_EINVAL, "S_stride / alpha_stride must be 0 (shared) or nz*nx*ny");
     for (int64_t s = 0; s < n_solve; s++) {
         const double *ks = k + 3 * s;
         const double nrm = std::sqrt(ks[0] * ks[0] + ks[1] * ks[1] + ks[2] * ks[2]);
@@ -842,8 +861,17 @@ extern "C" int vrt_regular_execute_dev(vrt_regular *r, int64_t n_solve, const do
             return fail(VRT_EINVAL, "direction " + std::to_string(s + 1) + " is not a unit vector");
         if (ks[0] == 0.0) return fail(VRT_EINVAL, "horizontal ray (k_z = 0) has no upwind plane");
     }
+    return VRT_OK;
+}
+
+// One checked batch of solves into the handle's plane-major intensities r->d_I ([solve][iz][iy][ix]): all of
+// vrt_regular_execute_dev but the conversion of I to the caller's layout, shared with vrt_regular_emergent_dev.
+static int regular_solve(vrt_regular *r, int64_t n_solve, const double *k, const int *up, const double *dS,
+                         int64_t S_stride, const double *dalpha, int64_t alpha_stride, int64_t field_period,
+                         const double *dI0, int n_sweeps, hipStream_t st)
+{
+    const int64_t nz = r->nz, nx = r->nx, ny = r->ny, vol = nz * nx * ny;
     VRT_HIP_TRY(hipSetDevice(r->device));
-    hipStream_t st = (hipStream_t)stream;
     const int64_t nfield = field_period > 0 ? field_period : n_solve;
     const int64_t nS = S_stride ? nfield : 1, nA = alpha_stride ? nfield : 1;
     int rc;
@@ -938,11 +966,104 @@ extern "C" int vrt_regular_execute_dev(vrt_regular *r, int64_t n_solve, const do
     else
         hipLaunchKernelGGL(k_regular_solve<1024>, dim3((unsigned)n_solve), dim3((unsigned)threads), lds, st, ra);
     VRT_HIP_TRY(hipEventRecord(r->ev[2], st));
+    return VRT_OK;
+}
+
+// dS, dalpha, dI0, dI_out: device pointers in the caller's (Julia) layouts; k, up: host
+extern "C" int vrt_regular_execute_dev(vrt_regular *r, int64_t n_solve, const double *k, const int *up,
+                                       const double *dS, int64_t S_stride, const double *dalpha,
+                                       int64_t alpha_stride, int64_t field_period, const double *dI0,
+                                       int n_sweeps, double *dI_out, void *stream)
+{
+    DeviceScope scope;
+    if (field_period < 0 || field_period > n_solve) return fail(VRT_EINVAL, "field_period must be in [0, n_solve]");
+    if (!r || !k || !up || !dS || !dalpha || !dI0 || !dI_out) return fail(VRT_EINVAL, "NULL argument");
+    if (n_solve < 1 || n_sweeps < 1) return fail(VRT_EINVAL, "bad sizes");
+    const int64_t nz = r->nz, nx = r->nx, ny = r->ny, vol = nz * nx * ny;
+    if ((S_stride != 0 && S_stride != vol) || (alpha_stride != 0 && alpha_stride != vol))
+        return fail(VRT_EINVAL, "S_stride / alpha_stride must be 0 (shared) or nz*nx*ny");
+    int rc = regular_check_k(n_solve, k);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = regular_solve(r, n_solve, k, up, dS, S_stride, dalpha, alpha_stride, field_period, dI0, n_sweeps, st)))
+        return rc;
+    const unsigned tb = (unsigned)((vol + 255) / 256);
     for (int64_t s = 0; s < n_solve; s++)
         hipLaunchKernelGGL(k_reg_from_planes, dim3(tb), dim3(256), 0, st, (int)nz, (int)nx, (int)ny, r->d_I + s * vol, dI_out + s * vol);
     VRT_HIP_TRY(hipGetLastError());
     r->timed = true;
     return VRT_OK;
+}
+
+// Emergent intensity of nlam wavelengths seen along one direction k (write_top_intensity, src/plot_utils.jl:101-140):
+// per wavelength l an up solve of S_l, alpha_l with I_0 = the bottom plane of S_l, of which only the top plane's
+// interior reaches dI_top (nlam, ny - 2, nx - 2).  The wavelengths go through regular_solve in chunks whose
+// workspace (S, alpha and I per solve, the split path's coefficients, the row-march scratch, I_0) stays under the
+// handle's byte cap: each solve is computed exactly as by vrt_regular_execute_dev, so the result is bit-identical to
+// the top plane of its output for any chunking.
+extern "C" int vrt_regular_emergent_dev(vrt_regular *r, const double *k, int64_t nlam, const double *dS,
+                                        const double *dalpha, int n_sweeps, double *dI_top, void *stream)
+{
+    DeviceScope scope;
+    if (!r || !k || !dS || !dalpha || !dI_top) return fail(VRT_EINVAL, "NULL argument");
+    if (nlam < 1 || n_sweeps < 1) return fail(VRT_EINVAL, "bad sizes");
+    int rc = regular_check_k(1, k);
+    if (rc) return rc;
+    const int64_t nz = r->nz, nx = r->nx, ny = r->ny, vol = nz * nx * ny, plane = nx * ny;
+    const int64_t per_solve = (int64_t)sizeof(double) * (6 * vol + 6 * plane);   // S, alpha, I, xy coefficients | coef, I_0
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nlam, r->emergent_bytes / per_solve));
+    std::vector<double> kk(3 * (size_t)chunk);
+    for (int64_t s = 0; s < chunk; s++)
+        for (int j = 0; j < 3; j++) kk[3 * (size_t)s + (size_t)j] = k[j];
+    const std::vector<int> up((size_t)chunk, 1);
+    VRT_HIP_TRY(hipSetDevice(r->device));
+    if ((rc = regular_grow(r->d_I0, r->cap_I0, chunk, (size_t)plane))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t inner = (nx - 2) * (ny - 2);
+    for (int64_t l0 = 0; l0 < nlam; l0 += chunk) {
+        const int64_t cnt = std::min(chunk, nlam - l0);
+        hipLaunchKernelGGL(k_reg_bottom_plane, dim3((unsigned)((plane * cnt + 255) / 256)), dim3(256), 0, st, (int)nz,
+                           (int)nx, (int)ny, cnt, dS + l0 * vol, r->d_I0);
+        if ((rc = regular_solve(r, cnt, kk.data(), up.data(), dS + l0 * vol, vol, dalpha + l0 * vol, vol, 0, r->d_I0,
+                                n_sweeps, st)))
+            return rc;
+        hipLaunchKernelGGL(k_reg_top_interior, dim3((unsigned)((inner * cnt + 255) / 256)), dim3(256), 0, st, (int)nz,
+                           (int)nx, (int)ny, cnt, r->d_I, dI_top + l0 * inner);
+        VRT_HIP_TRY(hipGetLastError());
+    }
+    r->timed = true;
+    return VRT_OK;
+}
+
+// Host-pointer form: S, alpha (nlam, ny, nx, nz) in numpy order on the ghosted axes, I_top (nlam, ny - 2, nx - 2).
+extern "C" int vrt_top_intensity(int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x, const double *y,
+                                 const double *k, int64_t nlam, const double *S, const double *alpha, int n_sweeps,
+                                 int device, double *I_top)
+{
+    DeviceScope scope;
+    if (!z || !x || !y || !k || !S || !alpha || !I_top) return fail(VRT_EINVAL, "NULL argument");
+    if (nz < 2 || nx < 3 || ny < 3 || nlam < 1 || n_sweeps < 1) return fail(VRT_EINVAL, "bad sizes");
+    int rc = regular_check_k(1, k);
+    if (rc) return rc;
+    const int64_t vol = nz * nx * ny, inner = (nx - 2) * (ny - 2);
+    vrt_regular *r = nullptr;
+    if ((rc = vrt_regular_create(nz, nx, ny, z, x, y, device, &r))) return rc;
+    double *d_S = nullptr, *d_A = nullptr, *d_top = nullptr;
+    hipError_t e = hipMalloc((void **)&d_S, sizeof(double) * vol * nlam);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_A, sizeof(double) * vol * nlam);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_top, sizeof(double) * inner * nlam);
+    if (e == hipSuccess) e = hipMemcpy(d_S, S, sizeof(double) * vol * nlam, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_A, alpha, sizeof(double) * vol * nlam, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+        rc = fail(e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE, std::string("vrt_top_intensity: ") + hipGetErrorString(e));
+    if (!rc) rc = vrt_regular_emergent_dev(r, k, nlam, d_S, d_A, n_sweeps, d_top, nullptr);
+    if (!rc && ((e = hipDeviceSynchronize()) != hipSuccess ||
+                (e = hipMemcpy(I_top, d_top, sizeof(double) * inner * nlam, hipMemcpyDeviceToHost)) != hipSuccess))
+        rc = fail(VRT_ENODEVICE, std::string("vrt_top_intensity: ") + hipGetErrorString(e));
+    for (void *p : {(void *)d_S, (void *)d_A, (void *)d_top})
+        if (p) (void)hipFree(p);
+    regular_free(r);
+    return rc;
 }
 
 // milliseconds of the last execute's solve kernel alone (HIP events on its stream); the stream

@@ -394,3 +394,32 @@ def atmosphere_raster(nz: int, nx: int, ny: int, seed: int, box_xy: float = BOX_
         v.append(3.0e3 * (np.cos(2 * np.pi * (X * (c + 1) + Y * (2 - c)))[:, :, None] * (0.5 + h)[None, None, :]
                           + 0.3 * u[:, :, None]))
     return {"z": z, "x": x, "y": y, "N_H": N_H, "T": T, "vx": v[0], "vy": v[1], "vz": v[2]}
+
+
+def line_raster(atm: dict, nlam: int, seed: int, line_to_cont: float = 100.0):
+    """Inputs of an emergent spectrum on an `atmosphere_raster`: the raster dict of api.synth_opacity (axes + velocity
+    (3, ny, nx, nz) [vz, vx, vy], doppler, gamma_static, gamma_unsold, temperature, alpha_cont), raster populations
+    (2, ny, nx, nz), the line's constants (a namespace with lam, planck2, lambda0, c0, hc_over_kB, strength_const, Bij,
+    Bji) and src_const.  Magnitudes in SI: a 500 nm line, nlam wavelengths over +-8 Doppler widths; α_c follows N_H so
+    that the continuum's τ = 1 lies inside the box, and the line centre is about `line_to_cont` times more opaque."""
+    import types
+
+    z, x, y, T, N_H = atm["z"], atm["x"], atm["y"], atm["T"], atm["N_H"]
+    L = z[-1] - z[0]
+    shape = T.shape
+    idx = np.arange(T.size, dtype=np.uint64).reshape(shape)
+    c0, kB, h, m_H = 2.99792458e8, 1.380649e-23, 6.62607015e-34, 1.6735575e-27
+    lambda0 = 500e-9
+    doppler = lambda0 / c0 * np.sqrt(2 * kB * T / m_H)
+    n1 = 1e-6 * N_H * (1.0 + 0.1 * counter_uniform(seed, 20, idx))
+    n2 = n1 * 1e-3 * (1.0 + counter_uniform(seed, 21, idx))
+    alpha_cont = 30.0 / L * N_H / N_H.max()
+    strength_const = line_to_cont * 30.0 / L * np.sqrt(np.pi) * doppler.mean() / (1e-6 * N_H.max())
+    lam = lambda0 + doppler.mean() * np.linspace(-8.0, 8.0, nlam)
+    raster = {"z": z, "x": x, "y": y, "velocity": np.stack([atm["vz"], atm["vx"], atm["vy"]]), "doppler": doppler,
+              "gamma_static": 4.7e8 + 1e8 * counter_uniform(seed, 22, idx),
+              "gamma_unsold": 1e-9 * (1.0 + counter_uniform(seed, 23, idx)), "temperature": T,
+              "alpha_cont": alpha_cont}
+    case = types.SimpleNamespace(lam=lam, planck2=2.0 * (lambda0 / lam) ** 5, lambda0=lambda0, c0=c0,
+                                 hc_over_kB=h * c0 / kB, strength_const=strength_const, Bij=1.0, Bji=0.25)
+    return raster, np.stack([n1, n2]), case, 2.0
