@@ -35,7 +35,7 @@ extern "C" {
 #define VRT_EINVAL (-1)     /* bad argument (null pointer, size mismatch, |k| != 1, ...)      */
 #define VRT_EGRID (-2)      /* malformed grid: id out of range, unreachable site, D >= cap ... */
 #define VRT_ENODEVICE (-3)  /* no HIP device / HIP runtime error                               */
-#define VRT_ENOMEM (-4)
+#define VRT_ENOMEM (-4)     /* out of host or device memory, from every entry point            */
 #define VRT_EIO (-5)        /* neighbour file unreadable / unparsable                          */
 
 typedef struct vrt_grid vrt_grid;   /* replaces struct VoronoiSites, voronoi_utils.jl:7-28 */

@@ -34,6 +34,52 @@ def test_library_exports_every_declared_symbol():
     assert _lib.load().vrt_version() >= 100
 
 
+def test_one_allocator_and_one_exception_guard():
+    """Device memory comes from dev_alloc and exceptions stop in guarded / run_workers, all in vrt_internal.h: no other
+    source of the library calls hipMalloc or catches an exception itself."""
+    csrc = os.path.join(ROOT, "voronoirt_amd", "csrc")
+    for name in sorted(os.listdir(csrc)):
+        if name == "vrt_internal.h":
+            continue
+        text = open(os.path.join(csrc, name)).read()
+        assert "hipMalloc(" not in text, name
+        assert "catch (" not in text, name
+
+
+# the read-only queries that answer 0 for a NULL handle
+ZERO_FOR_NULL = ("vrt_plan_last_path", "vrt_plan_native_pair_block", "vrt_plan_native_pair_block_f32",
+                 "vrt_multi_last_shard", "vrt_multi_uses_rccl")
+
+
+def test_every_entry_point_refuses_null_arguments():
+    """Every int entry point of the C ABI, called with NULL pointers, zero sizes and device 0, returns a VRT_E* code
+    (the read-only queries above: 0) and neither crashes nor lets an exception out.  In a child process, so that a
+    crash is reported here instead of ending the test run."""
+    script = (
+        "import ctypes, sys\n"
+        "sys.path.insert(0, sys.argv[1])\n"
+        "from voronoirt_amd import _lib\n"
+        "lib = _lib.load()\n"
+        "zero = set(sys.argv[2].split(','))\n"
+        "for name, (res, args) in _lib.PROTOTYPES.items():\n"
+        "    if res is not ctypes.c_int or name in ('vrt_version', 'vrt_device_count'):\n"
+        "        continue\n"
+        "    vals = [0 if a in (ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double) else None for a in args]\n"
+        "    print(name, getattr(lib, name)(*vals), flush=True)\n")
+    env = dict(os.environ, VRT_NO_TORCH="1")
+    r = subprocess.run([sys.executable, "-c", script, ROOT, ",".join(ZERO_FOR_NULL)], env=env, capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    rcs = {name: int(rc) for name, rc in (line.split() for line in r.stdout.splitlines())}
+    called = {n for n, (res, _) in _lib.PROTOTYPES.items() if res is ctypes.c_int} - {"vrt_version", "vrt_device_count"}
+    assert set(rcs) == called
+    for name, rc in rcs.items():
+        if name in ZERO_FOR_NULL:
+            assert rc == 0, name
+        else:
+            assert _lib.VRT_EIO <= rc < 0, (name, rc)
+
+
 def test_default_patch_kernels_hold_their_register_budget(tmp_path):
     """The default sweep kernel owes its speed to FOUR 512-thread workgroups per CU: k_patch_lean must fit 64
     VGPRs without scratch (8 bytes of scratch cost 3.5 %, 56 bytes 80 %: DESIGN.md section 5), the 72-register

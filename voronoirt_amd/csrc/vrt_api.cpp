@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <thread>
 
@@ -85,27 +86,6 @@ int tuning_set(Tuning &t, const char *name, const char *value, bool created)
     return fail(VRT_EINVAL, "unknown option " + nm);
 }
 
-template <typename T>
-static int dev_alloc(T **p, size_t count)
-{
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc((void **)p, count * sizeof(T));
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return fail(e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE,
-                    std::string("hipMalloc: ") + hipGetErrorString(e));
-    }
-    return VRT_OK;
-}
-
-template <typename T>
-static void dev_free(T *&p)
-{
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
-}
-
 int use_device(int device)
 {
     if (device < 0)
@@ -119,6 +99,15 @@ int use_device(int device)
     // an error some EARLIER call of this thread left behind (the host application's, or a refused argument of
     // ours) must not be reported by the hipGetLastError() checks behind this entry point's own launches
     (void)hipGetLastError();
+    return VRT_OK;
+}
+
+int use_current_device()
+{
+    int cnt = 0;
+    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0)
+        return fail(VRT_ENODEVICE, "no HIP device available (libvrt_hip has no CPU fallback)");
+    (void)hipGetLastError();           // (an earlier call's error is not this entry point's)
     return VRT_OK;
 }
 
@@ -724,17 +713,6 @@ int vrt::ensure_step_tables(vrt_plan *p)
 
 namespace vrt {
 
-static int ensure(double *&buf, size_t &cap, size_t count)
-{
-    if (count <= cap && buf) return VRT_OK;
-    dev_free(buf);
-    cap = 0;
-    int rc = dev_alloc(&buf, count);
-    if (rc) return rc;
-    cap = count;
-    return VRT_OK;
-}
-
 // The path of one execute -- 1 levels, 2 tiles, 3 steps, 4 patches -- or a VRT_E* code.  Every rule of the choice is
 // here, and it runs before anything is allocated or launched; it has no effect beyond the error message.
 // Four device paths produce the same results:
@@ -813,7 +791,7 @@ static int execute_levels(vrt_plan *p, const ExecArgs &x)
     int rc;
     if ((rc = ensure_level_schedule(p))) return rc;
     const size_t need = (size_t)std::max(1, p->A) * (size_t)p->g->n * (size_t)x.nlam;
-    if ((rc = ensure(p->d_I, p->I_cap, x.f32 ? (need + 1) / 2 : need))) return rc;
+    if ((rc = dev_grow(p->d_I, p->I_cap, x.f32 ? (need + 1) / 2 : need))) return rc;
     p->I_ld = x.nlam;
     SweepArgs sa;
     sa.f32 = x.f32;
@@ -850,22 +828,48 @@ int execute_locked(vrt_plan *p, const ExecArgs &x)
     return path == 1 ? execute_levels(p, x) : execute_layers(p, x, path);
 }
 
-// the float forms of the sweep-order entry points share this: lock, device, layout check, then `fn`
+// the sweep-order layout changes share this: arguments, lock, device, layout check, then `fn`
 template <typename F>
-static int native_f32_call(vrt_plan *p, int64_t nlam, int64_t ld, bool args_ok, F fn)
+static int native_call(vrt_plan *p, int64_t nlam, int64_t ld, bool args_ok, bool f32, F fn)
 {
-    DeviceScope scope;
-    if (!p || !args_ok) return fail(VRT_EINVAL, "NULL argument");
-    if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
-    try {
+    return guarded([&] {
+        if (!p || !args_ok) return fail(VRT_EINVAL, "NULL argument");
+        if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
         std::lock_guard<std::mutex> lock(p->mu);
         int rc = use_device(p->g->device);
-        if (!rc) rc = native_planes_ok(p, true);
-        if (rc) return rc;
-        return fn();
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+        if (!rc) rc = native_planes_ok(p, f32);
+        return rc ? rc : fn();
+    });
+}
+
+// the executes share this: lock, then execute_locked (which checks the arguments and the device)
+static int execute_call(vrt_plan *p, const ExecArgs &x)
+{
+    return guarded([&] {
+        if (!p) return fail(VRT_EINVAL, "NULL plan");
+        std::lock_guard<std::mutex> lock(p->mu);
+        return execute_locked(p, x);
+    });
+}
+
+// S_new and the criterion of the Λ iteration, either layout: `launch` writes the criterion's two words at d_res
+template <typename F>
+static int lambda_update_call(vrt_grid *g, double *max_rel_change, hipStream_t st, const char *what, F launch)
+{
+    int rc = use_device(g->device);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(g->mu);
+    if (!g->d_scalars && (rc = dev_alloc(&g->d_scalars, 2))) return rc;
+    unsigned long long *d_res = g->d_scalars;
+    rc = launch(d_res);
+    unsigned long long h[2] = {0, 0};
+    if (!rc && hipMemcpyAsync(h, d_res, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ENODEVICE;
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = VRT_ENODEVICE;
+    if (rc) return rc == VRT_ENODEVICE ? fail(rc, std::string("HIP error in ") + what) : rc;
+    double d;
+    std::memcpy(&d, &h[0], sizeof(double));
+    *max_rel_change = h[1] ? std::nan("") : d;
+    return VRT_OK;
 }
 
 }  // namespace vrt
@@ -888,21 +892,13 @@ int vrt_device_count(void)
 int vrt_grid_create(int64_t n, const double *pos_zxy, const int64_t *nbr, int64_t D1,
                     const double bounds[6], int device, vrt_grid **out)
 {
-    DeviceScope scope;
-    try {
-        return grid_create_impl(n, pos_zxy, nbr, D1, bounds, device, out);
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    return guarded([&] { return grid_create_impl(n, pos_zxy, nbr, D1, bounds, device, out); });
 }
 
 int vrt_grid_create_from_file(const char *neighbours_file, int64_t n, const double *pos_zxy,
                               const double bounds[6], int device, vrt_grid **out)
 {
-    DeviceScope scope;
-    try {
+    return guarded([&] {
         if (!neighbours_file) return fail(VRT_EINVAL, "NULL file name");
         if (n < 1) return fail(VRT_EINVAL, "n must be positive");
         std::vector<int64_t> M;
@@ -910,11 +906,7 @@ int vrt_grid_create_from_file(const char *neighbours_file, int64_t n, const doub
         int rc = parse_neighbour_file(neighbours_file, n, M, D1);
         if (rc) return rc;
         return grid_create_impl(n, pos_zxy, M.data(), D1, bounds, device, out);
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    });
 }
 
 int vrt_tessellate(int64_t n, const double *pos_zxy, const double bounds[6], int64_t D1, int64_t *nbr,
@@ -923,15 +915,11 @@ int vrt_tessellate(int64_t n, const double *pos_zxy, const double bounds[6], int
     if (!pos_zxy || !bounds || !nbr) return fail(VRT_EINVAL, "NULL argument");
     if (n < 2 || n >= ((int64_t)1 << 30)) return fail(VRT_EINVAL, "n must be in [2, 2^30)");
     if (D1 < 5) return fail(VRT_EINVAL, "D1 must leave room for at least four neighbours");
-    try {
+    return guarded([&] {
         unsigned hw = std::thread::hardware_concurrency();
         const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(hw ? hw : 4), 64, n / 256 + 1}));
         return tessellate_host(n, pos_zxy, bounds, D1, nbr, max_count, nthr);
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    });
 }
 
 int vrt_write_neighbours_file(const char *path, int64_t n, const int64_t *nbr, int64_t D1)
@@ -981,9 +969,8 @@ int vrt_grid_get_perm(const vrt_grid *g, int dir, int64_t *out)
 
 int vrt_grid_get_delaunay_lines(const vrt_grid *g, double *out)
 {
-    DeviceScope scope;
     if (!g || !out) return fail(VRT_EINVAL, "NULL argument");
-    try {
+    return guarded([&] {
         int rc = use_device(g->device);
         if (rc) return rc;
         const size_t nnz = g->col.size();
@@ -1004,9 +991,7 @@ int vrt_grid_get_delaunay_lines(const vrt_grid *g, double *out)
                 o[2] = ly[(size_t)e];
             }
         return VRT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    }
+    });
 }
 
 void vrt_direction(double theta_deg, double phi_deg, double k[3])
@@ -1022,14 +1007,7 @@ void vrt_direction(double theta_deg, double phi_deg, double k[3])
 int vrt_plan_create_ex(vrt_grid *g, int64_t n_angles, const double *k, const int *dirs,
                        int n_sweeps, vrt_plan **out)
 {
-    DeviceScope scope;
-    try {
-        return plan_create_impl(g, n_angles, k, dirs, n_sweeps, out);
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    return guarded([&] { return plan_create_impl(g, n_angles, k, dirs, n_sweeps, out); });
 }
 
 int vrt_plan_create(vrt_grid *g, int64_t n_angles, const double *k, int n_sweeps, vrt_plan **out)
@@ -1044,36 +1022,38 @@ void vrt_plan_destroy(vrt_plan *p)
     free_plan(p);
 }
 
+// the level schedule is built lazily, under the plan's mutex: -1 when that fails
 int64_t vrt_plan_num_levels(const vrt_plan *cp)
 {
     if (!cp) return 0;
-    vrt_plan *p = const_cast<vrt_plan *>(cp);      // the level schedule is built lazily, under the plan's mutex
-    DeviceScope scope;
-    std::lock_guard<std::mutex> lock(p->mu);
-    if (use_device(p->g->device) || ensure_level_schedule(p)) return -1;
-    return (int64_t)p->level_off.size() - 1;
+    vrt_plan *p = const_cast<vrt_plan *>(cp);
+    return guarded([&]() -> int64_t {
+        std::lock_guard<std::mutex> lock(p->mu);
+        if (use_device(p->g->device) || ensure_level_schedule(p)) return -1;
+        return (int64_t)p->level_off.size() - 1;
+    }, -1);
 }
 int64_t vrt_plan_num_nodes(const vrt_plan *cp)
 {
     if (!cp) return 0;
     vrt_plan *p = const_cast<vrt_plan *>(cp);
-    DeviceScope scope;
-    std::lock_guard<std::mutex> lock(p->mu);
-    if (use_device(p->g->device) || ensure_level_schedule(p)) return -1;
-    return p->n_nodes;
+    return guarded([&]() -> int64_t {
+        std::lock_guard<std::mutex> lock(p->mu);
+        if (use_device(p->g->device) || ensure_level_schedule(p)) return -1;
+        return p->n_nodes;
+    }, -1);
 }
 
 int vrt_plan_get_upwind(const vrt_plan *p, int64_t angle, int64_t *up, double *dots, double *w,
                         double *r)
 {
-    DeviceScope scope;
     if (!p) return fail(VRT_EINVAL, "NULL plan");
     if (angle < 0 || angle >= p->n_angles_user) return fail(VRT_EINVAL, "angle out of range");
     int a = -1;
     for (int i = 0; i < p->A; i++)
         if (p->user_of_active[(size_t)i] == (int)angle) a = i;
     if (a < 0) return fail(VRT_EINVAL, "angle is skipped (θ = 90) and has no table");
-    try {
+    return guarded([&] {
         int rc = use_device(p->g->device);
         if (rc) return rc;
         const int64_t n = p->g->n;
@@ -1101,9 +1081,7 @@ int vrt_plan_get_upwind(const vrt_plan *p, int64_t angle, int64_t *up, double *d
             }
         }
         return VRT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    }
+    });
 }
 
 struct vrt_schedule {
@@ -1115,7 +1093,7 @@ int vrt_schedule_build(const vrt_grid *g, int dir, const int64_t *up, int n_swee
     if (!g || !up || !out) return fail(VRT_EINVAL, "NULL argument");
     if (n_sweeps < 1) return fail(VRT_EINVAL, "n_sweeps must be >= 1");
     *out = nullptr;
-    try {
+    return guarded([&] {
         const int64_t n = g->n;
         std::vector<int32_t> u1((size_t)n), u2((size_t)n);
         for (int64_t i = 0; i < n; i++) {
@@ -1124,18 +1102,13 @@ int vrt_schedule_build(const vrt_grid *g, int dir, const int64_t *up, int n_swee
             u1[(size_t)i] = a >= 1 ? (int32_t)(a - 1) : kNoUpwind;
             u2[(size_t)i] = b >= 1 ? (int32_t)(b - 1) : kNoUpwind;
         }
-        vrt_schedule *sc = new vrt_schedule();
+        std::unique_ptr<vrt_schedule> sc(new vrt_schedule());
         build_angle_schedule(direction_of(g, dir), dir > 0, n, n_sweeps, u1.data(), u2.data(), sc->s);
-        if (sc->s.bad_site >= 0) {
-            std::string msg = "site " + std::to_string(sc->s.bad_site + 1) + " has no upwind neighbour";
-            delete sc;
-            return fail(VRT_EGRID, msg);
-        }
-        *out = sc;
+        if (sc->s.bad_site >= 0)
+            return fail(VRT_EGRID, "site " + std::to_string(sc->s.bad_site + 1) + " has no upwind neighbour");
+        *out = sc.release();
         return VRT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    }
+    });
 }
 
 int64_t vrt_schedule_num_nodes(const vrt_schedule *s) { return s ? (int64_t)s->s.site.size() : 0; }
@@ -1159,7 +1132,7 @@ int vrt_layer_schedule(const vrt_grid *g, int dir, const int64_t *up, int n_swee
 {
     if (!g || !up || !vis || !nlev) return fail(VRT_EINVAL, "NULL argument");
     if (n_sweeps < 1) return fail(VRT_EINVAL, "n_sweeps must be >= 1");
-    try {
+    return guarded([&] {
         const int64_t n = g->n;
         std::vector<int32_t> u1((size_t)n), u2((size_t)n);
         for (int64_t i = 0; i < n; i++) {
@@ -1177,15 +1150,13 @@ int vrt_layer_schedule(const vrt_grid *g, int dir, const int64_t *up, int n_swee
         std::copy(ls.nlev.begin(), ls.nlev.end(), nlev);
         if (n_visits) *n_visits = ls.n_visits;
         return VRT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    }
+    });
 }
 
 int vrt_layer_sorted_slots(const vrt_grid *g, int dir, const uint32_t *vis, int64_t *store, int64_t *self)
 {
     if (!g || !vis || !store || !self) return fail(VRT_EINVAL, "NULL argument");
-    try {
+    return guarded([&] {
         const int64_t n = g->n;
         const Direction &d = direction_of(g, dir);
         std::vector<uint32_t> v(vis, vis + n);
@@ -1196,9 +1167,7 @@ int vrt_layer_sorted_slots(const vrt_grid *g, int dir, const uint32_t *vis, int6
             self[i] = (int64_t)s32[(size_t)i];
         }
         return VRT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    }
+    });
 }
 
 struct vrt_patch_schedule {
@@ -1213,7 +1182,7 @@ int vrt_patch_schedule_build(const vrt_grid *g, int dir, const int64_t *up, int 
     if (n_sweeps < 1 || own_target < 1 || entry_cap < 1 || entry_cap > 65535)
         return fail(VRT_EINVAL, "need n_sweeps >= 1, own_target >= 1 and 1 <= entry_cap <= 65535");
     *out = nullptr;
-    try {
+    return guarded([&] {
         const int64_t n = g->n;
         std::vector<int32_t> u1((size_t)n), u2((size_t)n);
         for (int64_t i = 0; i < n; i++) {
@@ -1222,32 +1191,24 @@ int vrt_patch_schedule_build(const vrt_grid *g, int dir, const int64_t *up, int 
             u1[(size_t)i] = a >= 1 ? (int32_t)(a - 1) : kNoUpwind;
             u2[(size_t)i] = b >= 1 ? (int32_t)(b - 1) : kNoUpwind;
         }
-        vrt_patch_schedule *ps = new vrt_patch_schedule();
+        std::unique_ptr<vrt_patch_schedule> ps(new vrt_patch_schedule());
         // (introspection: VRT_HOST_THREADS sets the builder's thread count -- the sanitizer screen drives it with 16)
         int threads = (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
         if (const char *e = std::getenv("VRT_HOST_THREADS")) threads = std::max(1, std::min(64, std::atoi(e)));
         build_patch_schedule(direction_of(g, dir), dir > 0, n, n_sweeps, u1.data(), u2.data(), own_target, entry_cap,
                              ps->s, threads, &ps->layers);
-        if (ps->s.bad_site >= 0) {
-            const std::string msg = "site " + std::to_string(ps->s.bad_site + 1) + " has no upwind neighbour";
-            delete ps;
-            return fail(VRT_EGRID, msg);
-        }
-        if (!ps->s.ok) {
-            delete ps;
-            return fail(VRT_EINVAL, "schedule does not fit the packed patch encoding");
-        }
+        if (ps->s.bad_site >= 0)
+            return fail(VRT_EGRID, "site " + std::to_string(ps->s.bad_site + 1) + " has no upwind neighbour");
+        if (!ps->s.ok) return fail(VRT_EINVAL, "schedule does not fit the packed patch encoding");
         counts[0] = (int64_t)ps->s.patch_own_lo.size();
         counts[1] = (int64_t)ps->s.entry_pos.size();
         counts[2] = ps->s.n_visits;
         counts[3] = ps->s.n_live;
         counts[4] = ps->s.max_entries;
         counts[5] = (int64_t)ps->s.layer_patch_off.size();
-        *out = ps;
+        *out = ps.release();
         return VRT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    }
+    });
 }
 
 int vrt_patch_schedule_get(const vrt_patch_schedule *s, int32_t *layer_patch_off, int32_t *patch_own_lo,
@@ -1306,40 +1267,30 @@ int64_t vrt_plan_native_alpha_count(const vrt_plan *p, int64_t nlam)
     return (int64_t)p->A * ((nlam + 1) / 2 * 2) * p->g->n;
 }
 
+static int alpha_native_call(vrt_plan *p, int64_t nlam, int64_t ld, const void *dalpha, void *dalpha_native, void *stream,
+                             bool f32)
+{
+    return guarded([&] {
+        if (!p || !dalpha || !dalpha_native) return fail(VRT_EINVAL, "NULL argument");
+        if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
+        if (p->A != (int)p->n_angles_user)
+            return fail(VRT_EINVAL, "per-angle alpha needs every angle active (no θ = 90 direction)");
+        std::lock_guard<std::mutex> lock(p->mu);
+        int rc = use_device(p->g->device);
+        return rc ? rc : alpha_to_native(p, nlam, ld, dalpha, dalpha_native, (hipStream_t)stream, f32);
+    });
+}
+
 int vrt_plan_alpha_to_native_dev(vrt_plan *p, int64_t nlam, int64_t ld, const double *dalpha,
                                  double *dalpha_native, void *stream)
 {
-    DeviceScope scope;
-    if (!p || !dalpha || !dalpha_native) return fail(VRT_EINVAL, "NULL argument");
-    if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
-    if (p->A != (int)p->n_angles_user)
-        return fail(VRT_EINVAL, "per-angle alpha needs every angle active (no θ = 90 direction)");
-    try {
-        std::lock_guard<std::mutex> lock(p->mu);
-        int rc = use_device(p->g->device);
-        if (rc) return rc;
-        return alpha_to_native(p, nlam, ld, dalpha, dalpha_native, (hipStream_t)stream, false);
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    return alpha_native_call(p, nlam, ld, dalpha, dalpha_native, stream, false);
 }
 
 int vrt_plan_alpha_to_native_dev_f32(vrt_plan *p, int64_t nlam, int64_t ld, const float *dalpha, float *dalpha_native,
                                      void *stream)
 {
-    DeviceScope scope;
-    if (!p || !dalpha || !dalpha_native) return fail(VRT_EINVAL, "NULL argument");
-    if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
-    if (p->A != (int)p->n_angles_user)
-        return fail(VRT_EINVAL, "per-angle alpha needs every angle active (no θ = 90 direction)");
-    try {
-        std::lock_guard<std::mutex> lock(p->mu);
-        int rc = use_device(p->g->device);
-        if (rc) return rc;
-        return alpha_to_native(p, nlam, ld, dalpha, dalpha_native, (hipStream_t)stream, true);
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    return alpha_native_call(p, nlam, ld, dalpha, dalpha_native, stream, true);
 }
 
 int vrt_plan_execute_dev(vrt_plan *p, int64_t nlam, int64_t ld, const double *dS,
@@ -1347,17 +1298,8 @@ int vrt_plan_execute_dev(vrt_plan *p, int64_t nlam, int64_t ld, const double *dS
                          const double *dI0_down, const double *weights_host, double *dJ,
                          double *dI_out, void *stream)
 {
-    DeviceScope scope;
-    if (!p) return fail(VRT_EINVAL, "NULL plan");
-    try {
-        std::lock_guard<std::mutex> lock(p->mu);
-        return execute_locked(p, caller_args(nlam, ld, dS, dalpha, alpha_mode, dI0_up, dI0_down, weights_host, dJ, dI_out,
-                                             (hipStream_t)stream, false));
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    return execute_call(p, caller_args(nlam, ld, dS, dalpha, alpha_mode, dI0_up, dI0_down, weights_host, dJ, dI_out,
+                                       (hipStream_t)stream, false));
 }
 
 int64_t vrt_plan_native_plane_count(const vrt_plan *p, int64_t nlam)
@@ -1368,104 +1310,56 @@ int64_t vrt_plan_native_plane_count(const vrt_plan *p, int64_t nlam)
 
 int vrt_plan_to_native_dev(vrt_plan *p, int64_t nlam, int64_t ld, const double *d_in, double *d_up, double *d_down, void *stream)
 {
-    DeviceScope scope;
-    if (!p || !d_in || (!d_up && !d_down)) return fail(VRT_EINVAL, "NULL argument");
-    if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
-    try {
-        std::lock_guard<std::mutex> lock(p->mu);
-        int rc = use_device(p->g->device);
-        if (!rc) rc = native_planes_ok(p);
-        if (rc) return rc;
-        return planes_to_native(p, nlam, ld, d_in, d_up, d_down, (hipStream_t)stream);
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    return native_call(p, nlam, ld, d_in && (d_up || d_down), false,
+                       [&] { return planes_to_native(p, nlam, ld, d_in, d_up, d_down, (hipStream_t)stream); });
 }
 
 int vrt_plan_from_native_dev(vrt_plan *p, int dir, int64_t nlam, int64_t ld, const double *d_native, double *d_out, void *stream)
 {
-    DeviceScope scope;
-    if (!p || !d_native || !d_out) return fail(VRT_EINVAL, "NULL argument");
-    if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
-    try {
-        std::lock_guard<std::mutex> lock(p->mu);
-        int rc = use_device(p->g->device);
-        if (!rc) rc = native_planes_ok(p);
-        if (rc) return rc;
-        return plane_from_native(p, dir > 0 ? 0 : 1, nlam, ld, d_native, d_out, (hipStream_t)stream);
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    return native_call(p, nlam, ld, d_native && d_out, false,
+                       [&] { return plane_from_native(p, dir > 0 ? 0 : 1, nlam, ld, d_native, d_out, (hipStream_t)stream); });
 }
 
 int vrt_plan_j_from_native_dev(vrt_plan *p, int64_t nlam, int64_t ld, const double *dJ_up, const double *dJ_down, double *dJ,
                                void *stream)
 {
-    DeviceScope scope;
-    if (!p || !dJ || (!dJ_up && !dJ_down)) return fail(VRT_EINVAL, "NULL argument");
-    if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
-    try {
-        std::lock_guard<std::mutex> lock(p->mu);
-        int rc = use_device(p->g->device);
-        if (!rc) rc = native_planes_ok(p);
-        if (rc) return rc;
-        return J_from_native(p, nlam, ld, dJ_up, dJ_down, dJ, (hipStream_t)stream);
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    return native_call(p, nlam, ld, dJ && (dJ_up || dJ_down), false,
+                       [&] { return J_from_native(p, nlam, ld, dJ_up, dJ_down, dJ, (hipStream_t)stream); });
 }
 
 int vrt_plan_execute_native_dev(vrt_plan *p, int64_t nlam, const double *dS_up, const double *dS_down, const double *dalpha,
                                 int alpha_mode, const double *dI0_up, const double *dI0_down, const double *weights_host,
                                 double *dJ_up, double *dJ_down, void *stream)
 {
-    DeviceScope scope;
-    if (!p) return fail(VRT_EINVAL, "NULL plan");
-    try {
-        std::lock_guard<std::mutex> lock(p->mu);
-        return execute_locked(p, native_args(nlam, dS_up, dS_down, dalpha, alpha_mode, dI0_up, dI0_down, weights_host, dJ_up,
-                                             dJ_down, (hipStream_t)stream, false));
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    return execute_call(p, native_args(nlam, dS_up, dS_down, dalpha, alpha_mode, dI0_up, dI0_down, weights_host, dJ_up,
+                                       dJ_down, (hipStream_t)stream, false));
 }
 
 int vrt_plan_to_native_dev_f32(vrt_plan *p, int64_t nlam, int64_t ld, const float *d_in, float *d_up, float *d_down, void *stream)
 {
-    return native_f32_call(p, nlam, ld, d_in && (d_up || d_down),
-                           [&] { return planes_to_native_f32(p, nlam, ld, d_in, d_up, d_down, (hipStream_t)stream); });
+    return native_call(p, nlam, ld, d_in && (d_up || d_down), true,
+                       [&] { return planes_to_native_f32(p, nlam, ld, d_in, d_up, d_down, (hipStream_t)stream); });
 }
 
 int vrt_plan_from_native_dev_f32(vrt_plan *p, int dir, int64_t nlam, int64_t ld, const float *d_native, float *d_out, void *stream)
 {
-    return native_f32_call(p, nlam, ld, d_native && d_out,
-                           [&] { return plane_from_native_f32(p, dir > 0 ? 0 : 1, nlam, ld, d_native, d_out, (hipStream_t)stream); });
+    return native_call(p, nlam, ld, d_native && d_out, true,
+                       [&] { return plane_from_native_f32(p, dir > 0 ? 0 : 1, nlam, ld, d_native, d_out, (hipStream_t)stream); });
 }
 
 int vrt_plan_j_from_native_dev_f32(vrt_plan *p, int64_t nlam, int64_t ld, const float *dJ_up, const float *dJ_down, float *dJ,
                                    void *stream)
 {
-    return native_f32_call(p, nlam, ld, dJ && (dJ_up || dJ_down),
-                           [&] { return J_from_native_f32(p, nlam, ld, dJ_up, dJ_down, dJ, (hipStream_t)stream); });
+    return native_call(p, nlam, ld, dJ && (dJ_up || dJ_down), true,
+                       [&] { return J_from_native_f32(p, nlam, ld, dJ_up, dJ_down, dJ, (hipStream_t)stream); });
 }
 
 int vrt_plan_execute_native_dev_f32(vrt_plan *p, int64_t nlam, const float *dS_up, const float *dS_down, const float *dalpha,
                                     int alpha_mode, const float *dI0_up, const float *dI0_down, const double *weights_host,
                                     float *dJ_up, float *dJ_down, void *stream)
 {
-    DeviceScope scope;
-    if (!p) return fail(VRT_EINVAL, "NULL plan");
-    try {
-        std::lock_guard<std::mutex> lock(p->mu);
-        return execute_locked(p, native_args(nlam, dS_up, dS_down, dalpha, alpha_mode, dI0_up, dI0_down, weights_host, dJ_up,
-                                             dJ_down, (hipStream_t)stream, /*f32=*/true));
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    return execute_call(p, native_args(nlam, dS_up, dS_down, dalpha, alpha_mode, dI0_up, dI0_down, weights_host, dJ_up,
+                                       dJ_down, (hipStream_t)stream, /*f32=*/true));
 }
 
 int vrt_plan_execute_dev_f32(vrt_plan *p, int64_t nlam, int64_t ld, const float *dS,
@@ -1473,29 +1367,19 @@ int vrt_plan_execute_dev_f32(vrt_plan *p, int64_t nlam, int64_t ld, const float 
                              const float *dI0_down, const double *weights_host, float *dJ,
                              float *dI_out, void *stream)
 {
-    DeviceScope scope;
-    if (!p) return fail(VRT_EINVAL, "NULL plan");
-    try {
-        std::lock_guard<std::mutex> lock(p->mu);
-        return execute_locked(p, caller_args(nlam, ld, dS, dalpha, alpha_mode, dI0_up, dI0_down, weights_host, dJ, dI_out,
-                                             (hipStream_t)stream, /*f32=*/true));
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    return execute_call(p, caller_args(nlam, ld, dS, dalpha, alpha_mode, dI0_up, dI0_down, weights_host, dJ, dI_out,
+                                       (hipStream_t)stream, /*f32=*/true));
 }
 
 int vrt_plan_execute(vrt_plan *p, int64_t nlam, int64_t ld, const double *S, const double *alpha,
                      int alpha_mode, const double *I0_up, const double *I0_down,
                      const double *weights, double *J, double *I_out)
 {
-    DeviceScope scope;
     if (!p) return fail(VRT_EINVAL, "NULL plan");
     if (!S || !alpha) return fail(VRT_EINVAL, "S and alpha must not be NULL");
     if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
     if (alpha_mode < 0 || alpha_mode > 2) return fail(VRT_EINVAL, "bad alpha_mode (host arrays: 0, 1 or 2)");
-    try {
+    return guarded([&] {
         std::lock_guard<std::mutex> lock(p->mu);
         vrt_grid *g = p->g;
         int rc = use_device(g->device);
@@ -1507,28 +1391,28 @@ int vrt_plan_execute(vrt_plan *p, int64_t nlam, int64_t ld, const double *S, con
                                                              : nS * (size_t)p->n_angles_user;
         const size_t nU = (size_t)g->up.n1 * (size_t)nlam, nD = (size_t)g->down.n1 * (size_t)nlam;
         hipStream_t st = g->stream;
-        if ((rc = ensure(p->d_stage[0], p->stage_cap[0], nS))) return rc;
-        if ((rc = ensure(p->d_stage[1], p->stage_cap[1], nA))) return rc;
+        if ((rc = dev_grow(p->d_stage[0], p->stage_cap[0], nS))) return rc;
+        if ((rc = dev_grow(p->d_stage[1], p->stage_cap[1], nA))) return rc;
         VRT_HIP_TRY(hipMemcpyAsync(p->d_stage[0], S, sizeof(double) * nS, hipMemcpyHostToDevice, st));
         VRT_HIP_TRY(hipMemcpyAsync(p->d_stage[1], alpha, sizeof(double) * nA, hipMemcpyHostToDevice, st));
         double *dU = nullptr, *dD = nullptr, *dJ = nullptr;
         if (I0_up && nU) {
-            if ((rc = ensure(p->d_stage[2], p->stage_cap[2], nU))) return rc;
+            if ((rc = dev_grow(p->d_stage[2], p->stage_cap[2], nU))) return rc;
             dU = p->d_stage[2];
             VRT_HIP_TRY(hipMemcpyAsync(dU, I0_up, sizeof(double) * nU, hipMemcpyHostToDevice, st));
         }
         if (I0_down && nD) {
-            if ((rc = ensure(p->d_stage[3], p->stage_cap[3], nD))) return rc;
+            if ((rc = dev_grow(p->d_stage[3], p->stage_cap[3], nD))) return rc;
             dD = p->d_stage[3];
             VRT_HIP_TRY(hipMemcpyAsync(dD, I0_down, sizeof(double) * nD, hipMemcpyHostToDevice, st));
         }
         if (J) {
-            if ((rc = ensure(p->d_stage[4], p->stage_cap[4], nS))) return rc;
+            if ((rc = dev_grow(p->d_stage[4], p->stage_cap[4], nS))) return rc;
             dJ = p->d_stage[4];
         }
         double *dIo = nullptr;
         if (I_out) {
-            if ((rc = ensure(p->d_stage[5], p->stage_cap[5], nS * (size_t)p->n_angles_user))) return rc;
+            if ((rc = dev_grow(p->d_stage[5], p->stage_cap[5], nS * (size_t)p->n_angles_user))) return rc;
             dIo = p->d_stage[5];
         }
         rc = execute_locked(p, caller_args(nlam, ld, p->d_stage[0], p->d_stage[1], alpha_mode, dU, dD, weights, dJ, dIo, st, false));
@@ -1539,31 +1423,31 @@ int vrt_plan_execute(vrt_plan *p, int64_t nlam, int64_t ld, const double *S, con
                                        hipMemcpyDeviceToHost, st));
         VRT_HIP_TRY(hipStreamSynchronize(st));
         return patch_chain_check(p);         // a chained sweep that gave up waiting: THIS call's results are invalid
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    });
 }
 
 int vrt_plan_check(vrt_plan *p)
 {
     if (!p) return fail(VRT_EINVAL, "NULL plan");
-    std::lock_guard<std::mutex> lock(p->mu);
-    return patch_chain_check(p);
+    return guarded([&] {
+        std::lock_guard<std::mutex> lock(p->mu);
+        return patch_chain_check(p);
+    });
 }
 
 int vrt_plan_last_sweep_timing(const vrt_plan *p, double *ms, int64_t *launches)
 {
     if (!p) return fail(VRT_EINVAL, "NULL plan");
     if (!p->ev_valid) return fail(VRT_EINVAL, "no execute has run on this plan yet");
-    VRT_HIP_TRY(hipEventSynchronize(p->ev1));
-    float t = 0.f;
-    VRT_HIP_TRY(hipEventElapsedTime(&t, p->ev0, p->ev1));
-    if (ms) *ms = (double)t;
-    if (launches) *launches = p->last_launches;
-    // the sweep has finished: a chained launch that gave up waiting for a dependency is reported here (or by the next execute)
-    return patch_chain_check(const_cast<vrt_plan *>(p));
+    return guarded([&] {
+        VRT_HIP_TRY(hipEventSynchronize(p->ev1));
+        float t = 0.f;
+        VRT_HIP_TRY(hipEventElapsedTime(&t, p->ev0, p->ev1));
+        if (ms) *ms = (double)t;
+        if (launches) *launches = p->last_launches;
+        // the sweep has finished: a chained launch that gave up waiting for a dependency is reported here (or by the next execute)
+        return patch_chain_check(const_cast<vrt_plan *>(p));
+    });
 }
 
 int vrt_plan_last_path(const vrt_plan *p) { return p ? p->last_path : 0; }
@@ -1571,89 +1455,73 @@ int vrt_plan_last_path(const vrt_plan *p) { return p ? p->last_path : 0; }
 int vrt_plan_set_option(vrt_plan *p, const char *name, const char *value)
 {
     if (!p) return fail(VRT_EINVAL, "NULL plan");
-    std::lock_guard<std::mutex> lock(p->mu);
-    return tuning_set(p->tune, name, value, /*created=*/true);
+    return guarded([&] {
+        std::lock_guard<std::mutex> lock(p->mu);
+        return tuning_set(p->tune, name, value, /*created=*/true);
+    });
 }
 
 int vrt_grid_set_option(vrt_grid *g, const char *name, const char *value)
 {
     if (!g) return fail(VRT_EINVAL, "NULL grid");
-    if (name && std::string(name) == "VRT_NEAREST_CELLS") {         // the raster resampling's seeds (vrt_raster.hip)
-        if (!value) return fail(VRT_EINVAL, "NULL value");
-        const std::string v(value);
-        int64_t cells = 0;
-        if (v != "auto") {
-            char *end = nullptr;
-            const long long c = std::strtoll(v.c_str(), &end, 10);
-            if (v.empty() || *end || c < 1 || c > 256) return fail(VRT_EINVAL, "VRT_NEAREST_CELLS: auto or 1..256");
-            cells = c;
+    return guarded([&] {
+        if (name && std::string(name) == "VRT_NEAREST_CELLS") {         // the raster resampling's seeds (vrt_raster.hip)
+            if (!value) return fail(VRT_EINVAL, "NULL value");
+            const std::string v(value);
+            int64_t cells = 0;
+            if (v != "auto") {
+                char *end = nullptr;
+                const long long c = std::strtoll(v.c_str(), &end, 10);
+                if (v.empty() || *end || c < 1 || c > 256) return fail(VRT_EINVAL, "VRT_NEAREST_CELLS: auto or 1..256");
+                cells = c;
+            }
+            std::lock_guard<std::mutex> lock(g->mu);
+            g->nearest_cells = cells;
+            return VRT_OK;
         }
+        Tuning probe;
+        int rc = tuning_set(probe, name, value, /*created=*/false);      // validates name and value
+        if (rc) return rc;
         std::lock_guard<std::mutex> lock(g->mu);
-        g->nearest_cells = cells;
+        bool found = false;
+        for (auto &o : g->options)
+            if (o.first == name) { o.second = value; found = true; }
+        if (!found) g->options.emplace_back(name, value);
+        for (PlanCacheEntry *c : g->cache) {                             // cached single-solve plans follow where they can
+            std::lock_guard<std::mutex> plock(c->plan->mu);
+            (void)tuning_set(c->plan->tune, name, value, /*created=*/true);
+        }
         return VRT_OK;
-    }
-    Tuning probe;
-    int rc = tuning_set(probe, name, value, /*created=*/false);      // validates name and value
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(g->mu);
-    bool found = false;
-    for (auto &o : g->options)
-        if (o.first == name) { o.second = value; found = true; }
-    if (!found) g->options.emplace_back(name, value);
-    for (PlanCacheEntry *c : g->cache) {                             // cached single-solve plans follow where they can
-        std::lock_guard<std::mutex> plock(c->plan->mu);
-        (void)tuning_set(c->plan->tune, name, value, /*created=*/true);
-    }
-    return VRT_OK;
+    });
 }
 
 int vrt_lambda_update_dev(vrt_grid *g, int64_t nlam, int64_t ld, const double *dJ, const double *dB,
                           const double *deps, const double *dS_old, double *dS_new, double *max_rel_change,
                           void *stream)
 {
-    DeviceScope scope;
-    if (!g || !dJ || !dB || !deps || !dS_old || !dS_new || !max_rel_change)
-        return fail(VRT_EINVAL, "NULL argument");
-    if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
-    int rc = use_device(g->device);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g->mu);
-    if (!g->d_scalars) VRT_HIP_TRY(hipMalloc((void **)&g->d_scalars, 2 * sizeof(unsigned long long)));
-    unsigned long long *d_res = g->d_scalars;
-    rc = launch_lambda_update(g->n, nlam, ld, dJ, dB, deps, dS_old, dS_new, d_res, st);
-    unsigned long long h[2] = {0, 0};
-    if (!rc && hipMemcpyAsync(h, d_res, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ENODEVICE;
-    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = VRT_ENODEVICE;
-    if (rc) return rc == VRT_ENODEVICE ? fail(rc, "HIP error in vrt_lambda_update_dev") : rc;
-    double d;
-    std::memcpy(&d, &h[0], sizeof(double));
-    *max_rel_change = h[1] ? std::nan("") : d;
-    return VRT_OK;
+    return guarded([&] {
+        if (!g || !dJ || !dB || !deps || !dS_old || !dS_new || !max_rel_change)
+            return fail(VRT_EINVAL, "NULL argument");
+        if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
+        hipStream_t st = (hipStream_t)stream;
+        return lambda_update_call(g, max_rel_change, st, "vrt_lambda_update_dev", [&](unsigned long long *d_res) {
+            return launch_lambda_update(g->n, nlam, ld, dJ, dB, deps, dS_old, dS_new, d_res, st);
+        });
+    });
 }
 
 int vrt_lambda_update_native_dev(vrt_grid *g, int64_t nlam, const double *dJ_up, const double *dJ_down, const double *dB_up,
                                  const double *deps, double *dS_up, double *dS_down, double *max_rel_change, void *stream)
 {
-    DeviceScope scope;
-    if (!g || (!dJ_up && !dJ_down) || !dB_up || !deps || !dS_up || !dS_down || !max_rel_change)
-        return fail(VRT_EINVAL, "NULL argument");
-    if (nlam < 1) return fail(VRT_EINVAL, "need nlam >= 1");
-    int rc = use_device(g->device);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g->mu);
-    if (!g->d_scalars) VRT_HIP_TRY(hipMalloc((void **)&g->d_scalars, 2 * sizeof(unsigned long long)));
-    unsigned long long *d_res = g->d_scalars;
-    rc = launch_lambda_update_native(g, nlam, dJ_up, dJ_down, dB_up, deps, dS_up, dS_down, d_res, st);
-    unsigned long long h[2] = {0, 0};
-    if (!rc && hipMemcpyAsync(h, d_res, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ENODEVICE;
-    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = VRT_ENODEVICE;
-    if (rc) return rc == VRT_ENODEVICE ? fail(rc, "HIP error in vrt_lambda_update_native_dev") : rc;
-    double d;
-    std::memcpy(&d, &h[0], sizeof(double));
-    *max_rel_change = h[1] ? std::nan("") : d;
-    return VRT_OK;
+    return guarded([&] {
+        if (!g || (!dJ_up && !dJ_down) || !dB_up || !deps || !dS_up || !dS_down || !max_rel_change)
+            return fail(VRT_EINVAL, "NULL argument");
+        if (nlam < 1) return fail(VRT_EINVAL, "need nlam >= 1");
+        hipStream_t st = (hipStream_t)stream;
+        return lambda_update_call(g, max_rel_change, st, "vrt_lambda_update_native_dev", [&](unsigned long long *d_res) {
+            return launch_lambda_update_native(g, nlam, dJ_up, dJ_down, dB_up, deps, dS_up, dS_down, d_res, st);
+        });
+    });
 }
 
 // wavelength-sized host arrays -> the grid's device scratch (caller holds g->mu).  The scratch is
@@ -1697,13 +1565,12 @@ static int line_opacity_impl(vrt_plan *p, int64_t nlam, const double *lambda, do
                              const double *d_line_strength, const double *d_alpha_cont, void *d_alpha_native,
                              void *stream, bool f32_out)
 {
-    DeviceScope scope;
     if (!p || !lambda || !d_velocity || !d_doppler_width || !d_gamma || !d_line_strength || !d_alpha_cont ||
         !d_alpha_native)
         return fail(VRT_EINVAL, "NULL argument");
     if (nlam < 1) return fail(VRT_EINVAL, "nlam must be >= 1");
     if (!(lambda0 > 0) || !(c0 > 0)) return fail(VRT_EINVAL, "lambda0 and c0 must be positive");
-    try {
+    return guarded([&] {
         vrt_grid *g = p->g;
         int rc = use_device(g->device);
         if (rc) return rc;
@@ -1715,11 +1582,7 @@ static int line_opacity_impl(vrt_plan *p, int64_t nlam, const double *lambda, do
         rc = launch_line_opacity(p, nlam, g->d_small, lambda0, c0, d_velocity, d_doppler_width, d_gamma,
                                  d_line_strength, d_alpha_cont, d_alpha_native, (hipStream_t)stream, f32_out);
         return rc ? rc : small_done(g, (hipStream_t)stream);
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    });
 }
 
 int vrt_line_opacity_dev(vrt_plan *p, int64_t nlam, const double *lambda, double lambda0, double c0,
@@ -1748,7 +1611,6 @@ static int rates_populations_impl(vrt_grid *g, int64_t nlam, int64_t ld, const d
                               double pref_ij, double pref_ji, const double *d_C, const double *d_atom_density,
                               double *d_R, double *d_populations, void *stream)
 {
-    DeviceScope scope;
     if (!g || !lambda || !blocks || (!dJ && !dJ_up && !dJ_down) || !planck2 || !d_doppler_width || !d_gamma || !sigma_bf1 || !sigma_bf2 ||
         !d_temperature || !d_lte_populations || !d_C || !d_atom_density || !d_R || !d_populations)
         return fail(VRT_EINVAL, "NULL argument");
@@ -1756,7 +1618,7 @@ static int rates_populations_impl(vrt_grid *g, int64_t nlam, int64_t ld, const d
     for (int b = 0; b < 3; b++)
         if (blocks[2 * b] < 0 || blocks[2 * b + 1] > nlam || blocks[2 * b + 1] - blocks[2 * b] < 2)
             return fail(VRT_EINVAL, "each wavelength block needs at least two wavelengths inside [0, nlam)");
-    try {
+    return guarded([&] {
         int rc = use_device(g->device);
         if (rc) return rc;
         std::lock_guard<std::mutex> lock(g->mu);
@@ -1771,11 +1633,7 @@ static int rates_populations_impl(vrt_grid *g, int64_t nlam, int64_t ld, const d
                                       pref_ij, pref_ji, d_C, d_atom_density, d_R, d_populations,
                                       (hipStream_t)stream, dJ_up, dJ_down);
         return rc ? rc : small_done(g, (hipStream_t)stream);
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    });
 }
 
 int vrt_rates_populations_dev(vrt_grid *g, int64_t nlam, int64_t ld, const double *lambda,
@@ -1809,14 +1667,13 @@ int vrt_rates_populations_native_dev(vrt_grid *g, int64_t nlam, const double *la
 static int single_solve(vrt_grid *g, int dir, const double k[3], const double *S, const double *I0,
                         int64_t nI0, const double *alpha, int n_sweeps, double *I_out)
 {
-    DeviceScope scope;
     if (!g || !k || !S || !alpha || !I_out) return fail(VRT_EINVAL, "NULL argument");
     const Direction &d = direction_of(g, dir);
     if (nI0 != d.n1)   // Julia: DimensionMismatch at irregular_ray_tracing.jl:35 / :116
         return fail(VRT_EINVAL, "I_0 has " + std::to_string(nI0) + " elements, the boundary layer has " +
                                     std::to_string(d.n1));
     if (nI0 > 0 && !I0) return fail(VRT_EINVAL, "I_0 is NULL");
-    try {
+    return guarded([&] {
         // Only the cache lookup / insertion / eviction runs under the grid's mutex; the solve itself
         // takes the plan's own mutex (vrt_plan_execute), so concurrent callers with different
         // directions (the reference calls these from Threads.@threads) overlap, and callers of the
@@ -1854,11 +1711,7 @@ static int single_solve(vrt_grid *g, int dir, const double k[3], const double *S
             entry->users--;
         }
         return rc;
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    });
 }
 
 int vrt_delaunay_up(vrt_grid *g, const double k[3], const double *S, const double *I0, int64_t nI0,

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <mutex>
+#include <new>
 #include <string>
 #include <thread>
 #include <vector>
@@ -36,6 +37,72 @@ struct DeviceScope {
     }
     DeviceScope(const DeviceScope &) = delete;
     DeviceScope &operator=(const DeviceScope &) = delete;
+};
+
+// The body of an extern "C" entry point that allocates, locks or touches the device: it runs under a DeviceScope, and
+// no exception crosses the C boundary (std::bad_alloc is VRT_ENOMEM, anything else VRT_EINVAL).  The entry point
+// returns that code, or `on_error` when it gives one (the int64_t queries: -1).
+template <typename Body>
+inline auto guarded(Body body, int64_t on_error = 0) -> decltype(body())
+{
+    DeviceScope scope;
+    int rc;
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        rc = fail(VRT_ENOMEM, "out of host memory");
+    } catch (...) {
+        rc = fail(VRT_EINVAL, "unexpected exception");
+    }
+    return on_error ? on_error : rc;
+}
+
+// The device checks of the entry points: use_device for a handle's device (vrt_api.cpp), use_current_device for the
+// *_dev calls that run on the caller's current device.  Both clear an error an earlier call left behind.
+int use_device(int device);
+int use_current_device();
+
+// Device memory for `count` elements (at least one); *p is NULL on failure.  Out of memory is VRT_ENOMEM, any other
+// error VRT_ENODEVICE.  The only place the library calls hipMalloc.
+template <typename T>
+inline int dev_alloc(T **p, size_t count)
+{
+    *p = nullptr;
+    const hipError_t e = hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T));
+    if (e == hipSuccess) return VRT_OK;
+    *p = nullptr;
+    return fail(e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
+}
+
+template <typename T>
+inline void dev_free(T *&p)
+{
+    if (p) (void)hipFree((void *)p);
+    p = nullptr;
+}
+
+// Grow-only workspace: a buffer of fewer than `count` elements is freed and `count` allocated (cap = 0 on failure).
+template <typename T>
+inline int dev_grow(T *&buf, size_t &cap, size_t count)
+{
+    if (buf && count <= cap) return VRT_OK;
+    dev_free(buf);
+    cap = 0;
+    const int rc = dev_alloc(&buf, count);
+    if (!rc) cap = count;
+    return rc;
+}
+
+// Device scratch of one call, freed when it goes out of scope (the staging of the host-pointer entry points).
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); return *this; }
+    ~DevBuf() { dev_free(p); }
+    int alloc(size_t count) { dev_free(p); return dev_alloc(&p, count); }
+    operator T *() const { return p; }
 };
 
 // Runs body(t) for t = 0 .. count-1 on `count` host threads.  A worker must not throw (an exception that leaves a
@@ -472,7 +539,6 @@ int launch_populations_from_shares(vrt_grid *g, const double *d_shares, const do
                                    double *d_R, double *d_populations, hipStream_t st);
 
 // ---- entry-point internals shared with vrt_lambda.cpp (vrt_api.cpp) ---------------------------------
-int use_device(int device);
 // one execute (caller holds p->mu): checks the arguments, chooses the path, runs it
 int execute_locked(vrt_plan *p, const ExecArgs &x);
 

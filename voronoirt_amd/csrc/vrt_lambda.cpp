@@ -10,7 +10,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <new>
+#include <memory>
 #include <thread>
 
 #include "vrt_internal.h"
@@ -18,18 +18,6 @@
 using namespace vrt;
 
 namespace {
-
-template <typename T>
-int dalloc(T **p, size_t count)
-{
-    *p = nullptr;
-    hipError_t e = hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return fail(e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-    }
-    return VRT_OK;
-}
 
 // ---- pageable host arrays at PCIe speed: lanes of (host thread, copy stream, two pinned staging buffers) ----------------
 struct CopyJob {
@@ -135,7 +123,7 @@ int run_copy_jobs(vrt_plan *p, const std::vector<CopyJob> &jobs, bool download, 
 
 int upload(double **d, const double *h, size_t count, hipStream_t st)
 {
-    int rc = dalloc(d, count);
+    int rc = dev_alloc(d, count);
     if (rc) return rc;
     VRT_HIP_TRY(hipMemcpyAsync(*d, h, sizeof(double) * count, hipMemcpyHostToDevice, st));
     return VRT_OK;
@@ -185,13 +173,14 @@ int vrt_line_terms_dev(vrt_grid *g, const double *d_gamma_static, const double *
                        const double *d_populations, double strength_const, double Bij, double Bji, double *d_gamma,
                        double *d_line_strength, void *stream)
 {
-    DeviceScope scope;
     if (!g || !d_populations) return fail(VRT_EINVAL, "NULL argument");
     if (d_gamma && (!d_gamma_static || !d_gamma_unsold)) return fail(VRT_EINVAL, "gamma needs gamma_static and gamma_unsold");
-    int rc = use_device(g->device);
-    if (rc) return rc;
-    return launch_line_terms(g->n, d_gamma_static, d_gamma_unsold, d_populations, strength_const, Bij, Bji, d_gamma,
-                             d_line_strength, (hipStream_t)stream);
+    return guarded([&] {
+        int rc = use_device(g->device);
+        if (rc) return rc;
+        return launch_line_terms(g->n, d_gamma_static, d_gamma_unsold, d_populations, strength_const, Bij, Bji, d_gamma,
+                                 d_line_strength, (hipStream_t)stream);
+    });
 }
 
 int vrt_plan_execute_line(vrt_plan *p, int64_t nlam, int64_t ld, const double *lambda, double lambda0, double c0,
@@ -199,12 +188,11 @@ int vrt_plan_execute_line(vrt_plan *p, int64_t nlam, int64_t ld, const double *l
                           const double *line_strength, const double *alpha_cont, const double *S, const double *I0_up,
                           const double *I0_down, const double *weights, double *J)
 {
-    DeviceScope scope;
     if (!p || !lambda || !velocity || !doppler_width || !gamma || !line_strength || !alpha_cont || !S || !weights || !J)
         return fail(VRT_EINVAL, "NULL argument");
     if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
     if (!(lambda0 > 0) || !(c0 > 0)) return fail(VRT_EINVAL, "lambda0 and c0 must be positive");
-    try {
+    return guarded([&] {
         std::lock_guard<std::mutex> lock(p->mu);
         vrt_grid *g = p->g;
         int rc = use_device(g->device);
@@ -217,30 +205,21 @@ int vrt_plan_execute_line(vrt_plan *p, int64_t nlam, int64_t ld, const double *l
         const size_t nU = (size_t)g->up.n1 * nl, nD = (size_t)g->down.n1 * nl;
         hipStream_t st = g->stream;
         // staging: S | J in the plan's stage buffers; the seven per-site vectors + λ in stage 1; α_tot native in ws_AA
-        auto ensure = [&](double *&buf, size_t &cap, size_t count) -> int {
-            if (buf && count <= cap) return VRT_OK;
-            if (buf) (void)hipFree(buf);
-            buf = nullptr;
-            cap = 0;
-            int r = dalloc(&buf, count);
-            if (!r) cap = count;
-            return r;
-        };
         const size_t vecs = 7 * n + nl;                  // velocity (3n), ΔλD, γ, strength, α_cont, λ
-        if ((rc = ensure(p->d_stage[0], p->stage_cap[0], nS))) return rc;
-        if ((rc = ensure(p->d_stage[1], p->stage_cap[1], vecs))) return rc;
-        if ((rc = ensure(p->d_stage[4], p->stage_cap[4], nS))) return rc;
+        if ((rc = dev_grow(p->d_stage[0], p->stage_cap[0], nS))) return rc;
+        if ((rc = dev_grow(p->d_stage[1], p->stage_cap[1], vecs))) return rc;
+        if ((rc = dev_grow(p->d_stage[4], p->stage_cap[4], nS))) return rc;
         const size_t nnat = (size_t)vrt_plan_native_alpha_count(p, nlam);
-        if ((rc = ensure(p->ws_AA, p->ws_AA_cap, nnat))) return rc;
+        if ((rc = dev_grow(p->ws_AA, p->ws_AA_cap, nnat))) return rc;
         double *dv = p->d_stage[1];
         double *d_vel = dv, *d_dop = dv + 3 * n, *d_gam = dv + 4 * n, *d_str = dv + 5 * n, *d_ac = dv + 6 * n, *d_lam = dv + 7 * n;
         double *dU = nullptr, *dD = nullptr;
         if (I0_up && nU) {
-            if ((rc = ensure(p->d_stage[2], p->stage_cap[2], nU))) return rc;
+            if ((rc = dev_grow(p->d_stage[2], p->stage_cap[2], nU))) return rc;
             dU = p->d_stage[2];
         }
         if (I0_down && nD) {
-            if ((rc = ensure(p->d_stage[3], p->stage_cap[3], nD))) return rc;
+            if ((rc = dev_grow(p->d_stage[3], p->stage_cap[3], nD))) return rc;
             dD = p->d_stage[3];
         }
         // The caller's arrays are pageable: they cross PCIe through copy lanes (a host thread, a copy stream and two pinned
@@ -310,16 +289,11 @@ int vrt_plan_execute_line(vrt_plan *p, int64_t nlam, int64_t ld, const double *l
 #endif
         VRT_HIP_TRY(hipStreamSynchronize(st));
         return patch_chain_check(p);         // a chained sweep that gave up waiting: THIS call's J is invalid
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    });
 }
 
 int vrt_lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *weights, vrt_lambda **out)
 {
-    DeviceScope scope;
     if (!out) return fail(VRT_EINVAL, "out is NULL");
     *out = nullptr;
     if (!p || !lc || !weights) return fail(VRT_EINVAL, "NULL argument");
@@ -333,7 +307,7 @@ int vrt_lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *weight
         if (lc->blocks[2 * b] < 0 || lc->blocks[2 * b + 1] > nlam || lc->blocks[2 * b + 1] - lc->blocks[2 * b] < 2)
             return fail(VRT_EINVAL, "each wavelength block needs at least two wavelengths inside [0, nlam)");
     if (!(lc->lambda0 > 0) || !(lc->c0 > 0)) return fail(VRT_EINVAL, "lambda0 and c0 must be positive");
-    try {
+    return guarded([&] {
         std::lock_guard<std::mutex> lock(p->mu);
         vrt_grid *g = p->g;
         int rc = use_device(g->device);
@@ -342,8 +316,7 @@ int vrt_lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *weight
             return fail(VRT_EINVAL, "the line session needs a layer path (at most 4 visits per site and 255 levels per layer)");
         if (p->A != (int)p->n_angles_user)
             return fail(VRT_EINVAL, "per-angle alpha needs every angle active (no θ = 90 direction)");
-        vrt_lambda *s = new (std::nothrow) vrt_lambda();
-        if (!s) return fail(VRT_ENOMEM, "out of host memory");
+        std::unique_ptr<vrt_lambda, void (*)(vrt_lambda *)> s(new vrt_lambda(), lambda_free);
         s->p = p;
         s->device = g->device;
         s->n = g->n;
@@ -360,7 +333,7 @@ int vrt_lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *weight
         small.insert(small.end(), lc->planck2, lc->planck2 + nl);
         small.insert(small.end(), lc->sigma_bf1, lc->sigma_bf1 + nb1);
         small.insert(small.end(), lc->sigma_bf2, lc->sigma_bf2 + nb2);
-#define VRT_S(expr) do { rc = (expr); if (rc) { lambda_free(s); return rc; } } while (0)
+#define VRT_S(expr) do { if ((rc = (expr))) return rc; } while (0)
         VRT_S(upload(&s->d_small, small.data(), small.size(), st));
         VRT_S(upload(&s->d_velocity, lc->velocity, 3 * n, st));
         VRT_S(upload(&s->d_doppler, lc->doppler_width, n, st));
@@ -378,51 +351,42 @@ int vrt_lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *weight
         if (s->native) {
             const size_t np = (size_t)vrt_plan_native_plane_count(p, nlam);
             for (int d = 0; d < 2; d++) {
-                VRT_S(dalloc(&s->d_S_nat[d], np));
-                VRT_S(dalloc(&s->d_J_nat[d], np));
-                if (hipMemsetAsync(s->d_J_nat[d], 0, sizeof(double) * np, st) != hipSuccess) { lambda_free(s); return fail(VRT_ENODEVICE, "hipMemsetAsync failed"); }
+                VRT_S(dev_alloc(&s->d_S_nat[d], np));
+                VRT_S(dev_alloc(&s->d_J_nat[d], np));
+                if (hipMemsetAsync(s->d_J_nat[d], 0, sizeof(double) * np, st) != hipSuccess) return fail(VRT_ENODEVICE, "hipMemsetAsync failed");
             }
-            VRT_S(dalloc(&s->d_B_up, np));
+            VRT_S(dev_alloc(&s->d_B_up, np));
             VRT_S(planes_to_native(p, nlam, nlam, s->d_B0, s->d_S_nat[0], s->d_S_nat[1], st));      // S_new = B_0, :236-239
             VRT_S(planes_to_native(p, nlam, nlam, s->d_B0, s->d_B_up, nullptr, st));
         } else {
         VRT_S(upload(&s->d_S_new, lc->B0, n * nl, st));                   // S_new = B_0, :236-239
-        VRT_S(dalloc(&s->d_S_old, n * nl));
-        VRT_S(dalloc(&s->d_J, n * nl));
+        VRT_S(dev_alloc(&s->d_S_old, n * nl));
+        VRT_S(dev_alloc(&s->d_J, n * nl));
         }
-        VRT_S(dalloc(&s->d_gamma, n));
-        VRT_S(dalloc(&s->d_strength, n));
-        VRT_S(dalloc(&s->d_pops_new, 3 * n));
-        VRT_S(dalloc(&s->d_R, 9 * n));
-        VRT_S(dalloc(&s->d_I0, (size_t)g->up.n1 * nl));
-        VRT_S(dalloc(&s->d_native, (size_t)vrt_plan_native_alpha_count(p, nlam)));
-        VRT_S(dalloc(&s->d_scalars, 2));
+        VRT_S(dev_alloc(&s->d_gamma, n));
+        VRT_S(dev_alloc(&s->d_strength, n));
+        VRT_S(dev_alloc(&s->d_pops_new, 3 * n));
+        VRT_S(dev_alloc(&s->d_R, 9 * n));
+        VRT_S(dev_alloc(&s->d_I0, (size_t)g->up.n1 * nl));
+        VRT_S(dev_alloc(&s->d_native, (size_t)vrt_plan_native_alpha_count(p, nlam)));
+        VRT_S(dev_alloc(&s->d_scalars, 2));
         if (!s->native &&
             (hipMemsetAsync(s->d_S_old, 0, sizeof(double) * n * nl, st) != hipSuccess ||      // S_old = zero(S_new), :240
-             hipMemsetAsync(s->d_J, 0, sizeof(double) * n * nl, st) != hipSuccess)) {
-            lambda_free(s);
+             hipMemsetAsync(s->d_J, 0, sizeof(double) * n * nl, st) != hipSuccess))
             return fail(VRT_ENODEVICE, "hipMemsetAsync failed");
-        }
         VRT_S(launch_gather_rows(g->up.n1, nlam, nlam, g->up.d_order, s->d_B0, s->d_I0, st));   // I_0 = B_λ(λ_l, T) of the bottom layer, :99-101
 #undef VRT_S
-        if (hipStreamSynchronize(st) != hipSuccess) {                       // the host arrays may go after return
-            lambda_free(s);
+        if (hipStreamSynchronize(st) != hipSuccess)                         // the host arrays may go after return
             return fail(VRT_ENODEVICE, "uploading the line case failed");
-        }
-        *out = s;
+        *out = s.release();
         return VRT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    });
 }
 
 int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
 {
-    DeviceScope scope;
     if (!s || !max_rel_change) return fail(VRT_EINVAL, "NULL argument");
-    try {
+    return guarded([&] {
         vrt_plan *p = s->p;
         std::lock_guard<std::mutex> lock(p->mu);
         vrt_grid *g = p->g;
@@ -478,45 +442,43 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
         *max_rel_change = h[1] ? std::nan("") : d;
         s->iterations++;
         return VRT_OK;
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    });
 }
 
 int vrt_lambda_get(vrt_lambda *s, double *J, double *S, double *populations, double *R, double *gamma)
 {
-    DeviceScope scope;
     if (!s) return fail(VRT_EINVAL, "NULL session");
-    vrt_plan *p = s->p;
-    std::lock_guard<std::mutex> lock(p->mu);
-    int rc = use_device(p->g->device);
-    if (rc) return rc;
-    const size_t n = (size_t)s->n, nl = (size_t)s->nlam;
-    if (s->native && (J || S)) {
-        // the caller's layout is formed here, on request: one scratch array, freed again
-        double *tmp = nullptr;
-        if ((rc = dalloc(&tmp, n * nl))) return rc;
-        hipStream_t st = p->g->stream;
-        if (J) {
-            rc = J_from_native(p, s->nlam, s->nlam, s->d_J_nat[0], s->d_J_nat[1], tmp, st);
-            if (!rc && hipMemcpyAsync(J, tmp, sizeof(double) * n * nl, hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ENODEVICE;
-            if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = VRT_ENODEVICE;
+    return guarded([&] {
+        vrt_plan *p = s->p;
+        std::lock_guard<std::mutex> lock(p->mu);
+        int rc = use_device(p->g->device);
+        if (rc) return rc;
+        const size_t n = (size_t)s->n, nl = (size_t)s->nlam;
+        if (s->native && (J || S)) {
+            // the caller's layout is formed here, on request: one scratch array, freed again
+            DevBuf<double> tmp;
+            if ((rc = tmp.alloc(n * nl))) return rc;
+            hipStream_t st = p->g->stream;
+            if (J) {
+                rc = J_from_native(p, s->nlam, s->nlam, s->d_J_nat[0], s->d_J_nat[1], tmp, st);
+                if (!rc && hipMemcpyAsync(J, tmp, sizeof(double) * n * nl, hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ENODEVICE;
+                if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = VRT_ENODEVICE;
+            }
+            if (!rc && S) {
+                rc = plane_from_native(p, 0, s->nlam, s->nlam, s->d_S_nat[0], tmp, st);
+                if (!rc && hipMemcpyAsync(S, tmp, sizeof(double) * n * nl, hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ENODEVICE;
+                if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = VRT_ENODEVICE;
+            }
+            if (rc) return rc == VRT_ENODEVICE ? fail(rc, "HIP error in vrt_lambda_get") : rc;
+        } else {
+            if (J) VRT_HIP_TRY(hipMemcpy(J, s->d_J, sizeof(double) * n * nl, hipMemcpyDeviceToHost));
+            if (S) VRT_HIP_TRY(hipMemcpy(S, s->d_S_new, sizeof(double) * n * nl, hipMemcpyDeviceToHost));
         }
-        if (!rc && S) {
-            rc = plane_from_native(p, 0, s->nlam, s->nlam, s->d_S_nat[0], tmp, st);
-            if (!rc && hipMemcpyAsync(S, tmp, sizeof(double) * n * nl, hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ENODEVICE;
-            if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = VRT_ENODEVICE;
-        }
-        (void)hipFree(tmp);
-        if (rc) return rc == VRT_ENODEVICE ? fail(rc, "HIP error in vrt_lambda_get") : rc;
-    } else {
-    if (J) VRT_HIP_TRY(hipMemcpy(J, s->d_J, sizeof(double) * n * nl, hipMemcpyDeviceToHost));
-    if (S) VRT_HIP_TRY(hipMemcpy(S, s->d_S_new, sizeof(double) * n * nl, hipMemcpyDeviceToHost));
-    }
-    if (populations) VRT_HIP_TRY(hipMemcpy(populations, s->d_pops, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
-    if (R) VRT_HIP_TRY(hipMemcpy(R, s->d_R, sizeof(double) * 9 * n, hipMemcpyDeviceToHost));
-    if (gamma) VRT_HIP_TRY(hipMemcpy(gamma, s->d_gamma, sizeof(double) * n, hipMemcpyDeviceToHost));
-    return VRT_OK;
+        if (populations) VRT_HIP_TRY(hipMemcpy(populations, s->d_pops, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
+        if (R) VRT_HIP_TRY(hipMemcpy(R, s->d_R, sizeof(double) * 9 * n, hipMemcpyDeviceToHost));
+        if (gamma) VRT_HIP_TRY(hipMemcpy(gamma, s->d_gamma, sizeof(double) * n, hipMemcpyDeviceToHost));
+        return VRT_OK;
+    });
 }
 
 void vrt_lambda_destroy(vrt_lambda *s)

@@ -20,22 +20,6 @@
 namespace vrt {
 
 // ---- host side of one execute on the tile path ---------------------------------------------------
-static int ensure_dev(double *&buf, size_t &cap, size_t count)
-{
-    if (buf && count <= cap) return VRT_OK;
-    if (buf) (void)hipFree(buf);
-    buf = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void **)&buf, std::max<size_t>(count, 1) * sizeof(double));
-    if (e != hipSuccess) {
-        buf = nullptr;
-        return fail(e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE,
-                    std::string("hipMalloc: ") + hipGetErrorString(e));
-    }
-    cap = count;
-    return VRT_OK;
-}
-
 // Block -> (angle, wavelength) map.  Workgroups are dealt round-robin to the 8 XCDs (block b runs
 // on the XCD that also runs b + 8, b + 16, ...: MI355X_MICROARCH.md, speed only), and every
 // XCD has a private 4 MB L2.  The 44-byte-per-site upwind table of an angle is shared by all
@@ -80,12 +64,7 @@ static int build_task_map(vrt_plan *p, int nlam, hipStream_t st)
         }
         p->h_task_map[(size_t)b] = per_xcd[(size_t)x][cur[x]++];
     }
-    if (!p->d_task_map || p->task_map_cap < (size_t)ntask) {
-        if (p->d_task_map) (void)hipFree(p->d_task_map);
-        p->d_task_map = nullptr;
-        VRT_HIP_TRY(hipMalloc((void **)&p->d_task_map, sizeof(int32_t) * (size_t)std::max(ntask, 1)));
-        p->task_map_cap = (size_t)ntask;
-    }
+    if (int rc = dev_grow(p->d_task_map, p->task_map_cap, (size_t)ntask)) return rc;
     VRT_HIP_TRY(hipMemcpyAsync(p->d_task_map, p->h_task_map.data(), sizeof(int32_t) * (size_t)ntask,
                                hipMemcpyHostToDevice, st));
     p->task_map_nlam = nlam;
@@ -232,10 +211,11 @@ static int ensure_step_streams(vrt_plan *p, int G)
         for (int j = gi; j < A; j += G) list.push_back(order[(size_t)j]);
     }
     p->step_group_off[(size_t)G] = (int)list.size();
-    if (!p->d_step_angles) VRT_HIP_TRY(hipMalloc((void **)&p->d_step_angles, sizeof(int32_t) * (size_t)std::max(A, 1)));
+    int rc;
+    if (!p->d_step_angles && (rc = dev_alloc(&p->d_step_angles, (size_t)A))) return rc;
     VRT_HIP_TRY(hipMemcpy(p->d_step_angles, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice));
     p->h_step_angles = list;
-    if (p->d_patch_work) { (void)hipFree(p->d_patch_work); p->d_patch_work = nullptr; }   // work lists follow the groups
+    dev_free(p->d_patch_work);                        // work lists follow the groups
     if (!p->step_fork) VRT_HIP_TRY(hipEventCreateWithFlags(&p->step_fork, hipEventDisableTiming));
     for (int gi = 0; gi < 4; gi++) {
         if (gi >= 1 && gi < G && !p->step_stream[gi]) {      // group 0 advances on the caller's stream
@@ -254,7 +234,7 @@ static int ensure_step_streams(vrt_plan *p, int G)
 static int build_level_map(vrt_plan *p, int G, int units)
 {
     if (p->d_level_map && p->level_map_groups == G && p->level_map_units == units) return VRT_OK;
-    if (p->d_level_map) { (void)hipFree(p->d_level_map); p->d_level_map = nullptr; }
+    dev_free(p->d_level_map);
     double mean_all = 0.0;
     for (double v : p->angle_mean_levels) mean_all += v;
     mean_all = p->angle_mean_levels.empty() ? 1.0 : std::max(1.0, mean_all / (double)p->angle_mean_levels.size());
@@ -289,7 +269,7 @@ static int build_level_map(vrt_plan *p, int G, int units)
             for (int x = 0; x < 8; x++) map.push_back(j < runs[(size_t)x].size() ? runs[(size_t)x][j] : -1);
     }
     p->level_map_off[(size_t)G] = (int)map.size();
-    VRT_HIP_TRY(hipMalloc((void **)&p->d_level_map, sizeof(int32_t) * std::max<size_t>(map.size(), 1)));
+    if (int rc = dev_alloc(&p->d_level_map, map.size())) return rc;
     VRT_HIP_TRY(hipMemcpy(p->d_level_map, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice));
     p->level_map_groups = G;
     p->level_map_units = units;
@@ -387,7 +367,7 @@ static int prepare_inputs(vrt_plan *p, const ExecArgs &x, LayerRun &r)
     const T *dalpha = static_cast<const T *>(x.alpha);
     const hipStream_t st = x.st;
     int rc;
-    if ((rc = ensure_dev(p->d_I, p->I_cap, dcount<T>((size_t)A * r.plane)))) return rc;
+    if ((rc = dev_grow(p->d_I, p->I_cap, dcount<T>((size_t)A * r.plane)))) return rc;
     T *wI = reinterpret_cast<T *>(p->d_I);
     // chained launch with the intensities as their own flags (vrt_patch.hip: chain_data_wait): every plane is filled with
     // the NaN pattern first; the boundary kernel below then writes the boundary layer and the never-visited site's zero
@@ -397,7 +377,7 @@ static int prepare_inputs(vrt_plan *p, const ExecArgs &x, LayerRun &r)
     if (r.chain_df && !r.prep) VRT_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p->d_I, (int)0x7FF87FF8u, (size_t)A * r.plane * sizeof(T) / 4, st));
     ChainPrep cp{};
     for (int d = 0; d < 2; d++)
-        if (r.use_dir[d] && !x.native && (rc = ensure_dev(p->ws_S[d], p->ws_S_cap[d], dcount<T>(r.plane)))) return rc;
+        if (r.use_dir[d] && !x.native && (rc = dev_grow(p->ws_S[d], p->ws_S_cap[d], dcount<T>(r.plane)))) return rc;
     TileArgs &ta = r.ta;
     ta.n = n;
     ta.nlam = (int)nlam;
@@ -450,7 +430,7 @@ static int prepare_inputs(vrt_plan *p, const ExecArgs &x, LayerRun &r)
         const hipStream_t sd = r.dir_st[d];
         const bool with_alpha = alpha_mode == VRT_ALPHA_SITE_LAM;           // S and α of the direction in ONE launch
         if (with_alpha) {
-            if ((rc = ensure_dev(p->ws_A[d], p->ws_A_cap[d], dcount<T>(r.plane)))) return rc;
+            if ((rc = dev_grow(p->ws_A[d], p->ws_A_cap[d], dcount<T>(r.plane)))) return rc;
             ta.alpha[d] = p->ws_A[d];
         }
         const T *in2 = with_alpha ? dalpha : nullptr;
@@ -479,7 +459,7 @@ static int prepare_inputs(vrt_plan *p, const ExecArgs &x, LayerRun &r)
         if (alpha_mode == VRT_ALPHA_SITE_LAM_NATIVE)
             ta.alpha[d] = static_cast<const double *>(x.alpha) + (size_t)d * dcount<T>(r.plane);
         if (alpha_mode == VRT_ALPHA_SITE) {
-            if ((rc = ensure_dev(p->ws_A[d], p->ws_A_cap[d], dcount<T>((size_t)n)))) return rc;
+            if ((rc = dev_grow(p->ws_A[d], p->ws_A_cap[d], dcount<T>((size_t)n)))) return rc;
             hipLaunchKernelGGL(k_gather_vec<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sd, n,
                                dir.d_store, dalpha, reinterpret_cast<T *>(p->ws_A[d]));
             ta.alpha[d] = p->ws_A[d];
@@ -515,7 +495,7 @@ static int prepare_inputs(vrt_plan *p, const ExecArgs &x, LayerRun &r)
         ta.alpha_mode = VRT_ALPHA_ANGLE_SITE_LAM;
         ta.alpha_angle = static_cast<const double *>(x.alpha);
     } else if (alpha_mode == VRT_ALPHA_ANGLE_SITE_LAM) {
-        if ((rc = ensure_dev(p->ws_AA, p->ws_AA_cap, dcount<T>((size_t)A * r.plane)))) return rc;
+        if ((rc = dev_grow(p->ws_AA, p->ws_AA_cap, dcount<T>((size_t)A * r.plane)))) return rc;
         for (int a = 0; a < A; a++) {
             const Direction &dir = p->dir_of_active[(size_t)a] > 0 ? g->up : g->down;
             hipLaunchKernelGGL(k_to_sweep_order<T>, r.tgrid, dim3(256), 0, r.dir_st[p->dir_of_active[(size_t)a] > 0 ? 0 : 1],
@@ -537,7 +517,7 @@ static int run_tiles(vrt_plan *p, const ExecArgs &x, LayerRun &r)
     TileArgs &ta = r.ta;
     int rc;
     long long *d_dbg = nullptr;
-    if (kDiag && p->tune.tile_debug && hipMalloc((void **)&d_dbg, sizeof(long long) * 4 * (size_t)A * (size_t)nlam) == hipSuccess)
+    if (kDiag && p->tune.tile_debug && dev_alloc(&d_dbg, 4 * (size_t)A * (size_t)nlam) == VRT_OK)
         ta.dbg = d_dbg;
     VRT_HIP_TRY(hipEventRecord(p->ev0, st));
     const size_t lds = 2 * (size_t)ta.tile_stride * sizeof(double);
@@ -551,7 +531,7 @@ static int run_tiles(vrt_plan *p, const ExecArgs &x, LayerRun &r)
     r.launches = 1;
     if (pre) {
         const size_t ntask = (size_t)A * (size_t)nlam;
-        if ((rc = ensure_dev(p->ws_cg[0], p->ws_cg_cap[0], 3 * ntask * (size_t)n))) return rc;
+        if ((rc = dev_grow(p->ws_cg[0], p->ws_cg_cap[0], 3 * ntask * (size_t)n))) return rc;
         hipLaunchKernelGGL(k_tile_coeffs, dim3((unsigned)((n + 255) / 256), (unsigned)ntask), dim3(256), 0, st,
                            ta, p->ws_cg[0]);
         const size_t lds_pre = 3 * (size_t)ta.tile_stride * sizeof(double);
@@ -634,8 +614,8 @@ static int run_steps(vrt_plan *p, const ExecArgs &x, LayerRun &r)
     // kernel -> one plane of T per (angle, wavelength)
     const size_t cgn = single ? dcount<T>((size_t)p->A * (size_t)r.nl_pad * (size_t)stride)
                               : (size_t)p->A * (size_t)r.nl_pad * (size_t)stride;
-    if ((rc = ensure_dev(p->ws_cg[0], p->ws_cg_cap[0], cgn))) return rc;
-    if ((rc = ensure_dev(p->ws_cg[1], p->ws_cg_cap[1], 2 * cgn))) return rc;
+    if ((rc = dev_grow(p->ws_cg[0], p->ws_cg_cap[0], cgn))) return rc;
+    if ((rc = dev_grow(p->ws_cg[1], p->ws_cg_cap[1], 2 * cgn))) return rc;
     StepArgs sa;
     sa.ta = r.ta;
     sa.cg_stride = stride;
@@ -735,7 +715,7 @@ static int patch_reduce_template(vrt_plan *p, const ExecArgs &x, const LayerRun 
     int rc;
     for (int a = 0; a < p->A; a++) red.w[a] = x.weights[p->user_of_active[(size_t)a]];
     for (int d = 0; d < 2; d++)
-        if (r.use_dir[d] && !x.native && (rc = ensure_dev(p->ws_J[d], p->ws_J_cap[d], dcount<T>(r.plane)))) return rc;
+        if (r.use_dir[d] && !x.native && (rc = dev_grow(p->ws_J[d], p->ws_J_cap[d], dcount<T>(r.plane)))) return rc;
     return VRT_OK;
 }
 
@@ -864,7 +844,7 @@ static int finish_outputs(vrt_plan *p, const ExecArgs &x, const LayerRun &r)
                 if (x.native && x.J_nat[d]) VRT_HIP_TRY(hipMemsetAsync(x.J_nat[d], 0, r.plane * sizeof(T), st));
                 continue;
             }
-            if (!x.native && (rc = ensure_dev(p->ws_J[d], p->ws_J_cap[d], dcount<T>(r.plane)))) return rc;
+            if (!x.native && (rc = dev_grow(p->ws_J[d], p->ws_J_cap[d], dcount<T>(r.plane)))) return rc;
             DirWeights dw;
             dw.count = 0;
             for (int a = 0; a < A; a++)

@@ -14,7 +14,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <new>
+#include <memory>
 #include <thread>
 
 #include "vrt_internal.h"
@@ -71,21 +71,6 @@ struct Member {
     std::string err;
 };
 
-int ensure(double *&buf, size_t &cap, size_t count)
-{
-    if (buf && count <= cap) return VRT_OK;
-    if (buf) (void)hipFree(buf);
-    buf = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void **)&buf, std::max<size_t>(count, 1) * sizeof(double));
-    if (e != hipSuccess) {
-        buf = nullptr;
-        return fail(e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-    }
-    cap = count;
-    return VRT_OK;
-}
-
 }  // namespace
 
 struct vrt_multi {
@@ -134,15 +119,13 @@ int vrt_multi_create(int n_devices, const int *devices, int64_t n, const double 
                      const double bounds[6], int64_t n_angles, const double *k, const int *dirs, int n_sweeps,
                      vrt_multi **out)
 {
-    DeviceScope scope;
     if (!out) return fail(VRT_EINVAL, "out is NULL");
     *out = nullptr;
     if (!devices || !pos_zxy || !nbr || !bounds || !k) return fail(VRT_EINVAL, "NULL argument");
     if (n_devices < 1 || n_devices > 64) return fail(VRT_EINVAL, "need 1 <= n_devices <= 64");
     if (n_angles < 1) return fail(VRT_EINVAL, "n_angles must be >= 1");
-    try {
-        vrt_multi *mm = new (std::nothrow) vrt_multi();
-        if (!mm) return fail(VRT_ENOMEM, "out of host memory");
+    return guarded([&] {
+        std::unique_ptr<vrt_multi, void (*)(vrt_multi *)> mm(new vrt_multi(), multi_free);
         mm->n = n;
         mm->n_angles = n_angles;
         mm->n_sweeps = n_sweeps;
@@ -166,17 +149,10 @@ int vrt_multi_create(int n_devices, const int *devices, int64_t n, const double 
                                hipStreamCreateWithFlags(&me.stream, hipStreamNonBlocking) != hipSuccess))
                     me.rc = fail(VRT_ENODEVICE, "cannot create a stream");
                 if (me.rc) me.err = vrt_last_error();
-            })) {
-            multi_free(mm);
+            }))
             return fail(VRT_ENOMEM, "out of host memory while creating the per-device plans");
-        }
         for (const Member &me : mm->m)
-            if (me.rc) {
-                const int rc = me.rc;
-                const std::string msg = "device " + std::to_string(me.device) + ": " + me.err;
-                multi_free(mm);
-                return fail(rc, msg);
-            }
+            if (me.rc) return fail(me.rc, "device " + std::to_string(me.device) + ": " + me.err);
         // angles of the "angle" mode: ups and downs dealt round-robin separately (distributed.angle_assignment)
         {
             int ju = 0, jd = 0;
@@ -192,38 +168,32 @@ int vrt_multi_create(int n_devices, const int *devices, int64_t n, const double 
         const char *force = std::getenv("VRT_MULTI_FORCE_RCCL");
         const bool force_rccl = force && force[0] == '1';
         if (mm->distinct && (n_devices > 1 || force_rccl)) {
-            if (!mm->rccl.load()) {
-                multi_free(mm);
-                return fail(VRT_ENODEVICE, "cannot load librccl.so (needed for more than one device)");
-            }
+            if (!mm->rccl.load()) return fail(VRT_ENODEVICE, "cannot load librccl.so (needed for more than one device)");
             mm->comms.assign((size_t)n_devices, nullptr);
             const ncclResult_t r = mm->rccl.CommInitAll(mm->comms.data(), n_devices, devices);
             if (r != ncclSuccess) {
                 const std::string msg = std::string("ncclCommInitAll: ") + mm->rccl.GetErrorString(r);
                 mm->comms.clear();
-                multi_free(mm);
                 return fail(VRT_ENODEVICE, msg);
             }
         }
-        *out = mm;
+        *out = mm.release();
         return VRT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    });
 }
 
 int vrt_multi_set_shard(vrt_multi *mm, const char *mode)
 {
     if (!mm || !mode) return fail(VRT_EINVAL, "NULL argument");
-    const std::string s(mode);
-    std::lock_guard<std::mutex> lock(mm->mu);
-    if (s == "auto") mm->shard = 0;
-    else if (s == "lambda") mm->shard = 1;
-    else if (s == "angle") mm->shard = 2;
-    else return fail(VRT_EINVAL, "shard must be auto, lambda or angle");
-    return VRT_OK;
+    return guarded([&] {
+        const std::string s(mode);
+        std::lock_guard<std::mutex> lock(mm->mu);
+        if (s == "auto") mm->shard = 0;
+        else if (s == "lambda") mm->shard = 1;
+        else if (s == "angle") mm->shard = 2;
+        else return fail(VRT_EINVAL, "shard must be auto, lambda or angle");
+        return VRT_OK;
+    });
 }
 
 int vrt_multi_last_shard(const vrt_multi *mm) { return mm ? mm->last_shard : 0; }
@@ -232,11 +202,10 @@ int vrt_multi_uses_rccl(const vrt_multi *mm) { return mm && !mm->comms.empty() ?
 int vrt_multi_execute(vrt_multi *mm, int64_t nlam, int64_t ld, const double *S, const double *alpha, int alpha_mode,
                       const double *I0_up, const double *I0_down, const double *weights, double *J)
 {
-    DeviceScope scope;
     if (!mm || !S || !alpha || !weights || !J) return fail(VRT_EINVAL, "NULL argument");
     if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
     if (alpha_mode < 0 || alpha_mode > 2) return fail(VRT_EINVAL, "bad alpha_mode (host arrays: 0, 1 or 2)");
-    try {
+    return guarded([&] {
         std::lock_guard<std::mutex> lock(mm->mu);
         const int W = (int)mm->m.size();
         const int64_t n = mm->n, A = mm->n_angles;
@@ -276,7 +245,7 @@ int vrt_multi_execute(vrt_multi *mm, int64_t nlam, int64_t ld, const double *S, 
             const size_t w8 = sizeof(double);
             if (nb <= 0 || (shard == 2 && me.my_angles.empty())) {       // nothing to do here: contributes zeros in angle mode
                 if (shard == 2) {
-                    if ((me.rc = ensure(me.dJ, me.cJ, (size_t)n * (size_t)nlam))) { me.err = vrt_last_error(); return; }
+                    if ((me.rc = dev_grow(me.dJ, me.cJ, (size_t)n * (size_t)nlam))) { me.err = vrt_last_error(); return; }
                     chk(hipMemsetAsync(me.dJ, 0, w8 * (size_t)n * (size_t)nlam, st), "hipMemsetAsync");
                     chk(hipStreamSynchronize(st), "hipStreamSynchronize");      // another member's stream reads these zeros
                 }
@@ -285,7 +254,7 @@ int vrt_multi_execute(vrt_multi *mm, int64_t nlam, int64_t ld, const double *S, 
             vrt_plan *plan = shard == 1 ? me.plan_all : me.plan_part;
             const int64_t nA = shard == 1 ? A : (int64_t)me.my_angles.size();
             // S block (nb, n) dense on the device
-            if ((me.rc = ensure(me.dS, me.cS, (size_t)n * (size_t)nb)) || (me.rc = ensure(me.dJ, me.cJ, (size_t)n * (size_t)nb))) {
+            if ((me.rc = dev_grow(me.dS, me.cS, (size_t)n * (size_t)nb)) || (me.rc = dev_grow(me.dJ, me.cJ, (size_t)n * (size_t)nb))) {
                 me.err = vrt_last_error();
                 return;
             }
@@ -293,13 +262,13 @@ int vrt_multi_execute(vrt_multi *mm, int64_t nlam, int64_t ld, const double *S, 
             // alpha
             const double *dA = nullptr;
             if (alpha_mode == VRT_ALPHA_SITE) {
-                if ((me.rc = ensure(me.dA, me.cA, (size_t)n))) { me.err = vrt_last_error(); return; }
+                if ((me.rc = dev_grow(me.dA, me.cA, (size_t)n))) { me.err = vrt_last_error(); return; }
                 chk(hipMemcpyAsync(me.dA, alpha, w8 * (size_t)n, hipMemcpyHostToDevice, st), "upload alpha");
             } else if (alpha_mode == VRT_ALPHA_SITE_LAM) {
-                if ((me.rc = ensure(me.dA, me.cA, (size_t)n * (size_t)nb))) { me.err = vrt_last_error(); return; }
+                if ((me.rc = dev_grow(me.dA, me.cA, (size_t)n * (size_t)nb))) { me.err = vrt_last_error(); return; }
                 chk(hipMemcpy2DAsync(me.dA, w8 * (size_t)nb, alpha + l0, w8 * (size_t)ld, w8 * (size_t)nb, (size_t)n, hipMemcpyHostToDevice, st), "upload alpha");
             } else {
-                if ((me.rc = ensure(me.dA, me.cA, (size_t)nA * (size_t)n * (size_t)nb))) { me.err = vrt_last_error(); return; }
+                if ((me.rc = dev_grow(me.dA, me.cA, (size_t)nA * (size_t)n * (size_t)nb))) { me.err = vrt_last_error(); return; }
                 for (int64_t j = 0; j < nA; j++) {
                     const int64_t a = shard == 1 ? j : me.my_angles[(size_t)j];
                     chk(hipMemcpy2DAsync(me.dA + (size_t)j * (size_t)n * (size_t)nb, w8 * (size_t)nb,
@@ -310,12 +279,12 @@ int vrt_multi_execute(vrt_multi *mm, int64_t nlam, int64_t ld, const double *S, 
             dA = me.dA;
             double *dU = nullptr, *dD = nullptr;
             if (I0_up && n1u) {
-                if ((me.rc = ensure(me.dU, me.cU, (size_t)n1u * (size_t)nb))) { me.err = vrt_last_error(); return; }
+                if ((me.rc = dev_grow(me.dU, me.cU, (size_t)n1u * (size_t)nb))) { me.err = vrt_last_error(); return; }
                 chk(hipMemcpy2DAsync(me.dU, w8 * (size_t)nb, I0_up + l0, w8 * (size_t)nlam, w8 * (size_t)nb, (size_t)n1u, hipMemcpyHostToDevice, st), "upload I0");
                 dU = me.dU;
             }
             if (I0_down && n1d) {
-                if ((me.rc = ensure(me.dD, me.cD, (size_t)n1d * (size_t)nb))) { me.err = vrt_last_error(); return; }
+                if ((me.rc = dev_grow(me.dD, me.cD, (size_t)n1d * (size_t)nb))) { me.err = vrt_last_error(); return; }
                 chk(hipMemcpy2DAsync(me.dD, w8 * (size_t)nb, I0_down + l0, w8 * (size_t)nlam, w8 * (size_t)nb, (size_t)n1d, hipMemcpyHostToDevice, st), "upload I0");
                 dD = me.dD;
             }
@@ -371,11 +340,7 @@ int vrt_multi_execute(vrt_multi *mm, int64_t nlam, int64_t ld, const double *S, 
             VRT_HIP_TRY(hipStreamSynchronize(m0.stream));
         }
         return VRT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    });
 }
 
 // ---- the line case across several devices ---------------------------------------------------------------------------
@@ -388,12 +353,11 @@ int vrt_multi_execute_line(vrt_multi *mm, int64_t nlam, int64_t ld, const double
                            const double *line_strength, const double *alpha_cont, const double *S, const double *I0_up,
                            const double *I0_down, const double *weights, double *J)
 {
-    DeviceScope scope;
     if (!mm || !lambda || !velocity || !doppler_width || !gamma || !line_strength || !alpha_cont || !S || !weights || !J)
         return fail(VRT_EINVAL, "NULL argument");
     if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
     if (!(lambda0 > 0) || !(c0 > 0)) return fail(VRT_EINVAL, "lambda0 and c0 must be positive");
-    try {
+    return guarded([&] {
         std::lock_guard<std::mutex> lock(mm->mu);
         const int W = (int)mm->m.size();
         const int64_t n = mm->n;
@@ -420,8 +384,8 @@ int vrt_multi_execute_line(vrt_multi *mm, int64_t nlam, int64_t ld, const double
             const size_t w8 = sizeof(double), sn = (size_t)n;
             const size_t nnat = (size_t)vrt_plan_native_alpha_count(plan, nb);
             // S | seven per-site vectors + the block's wavelengths | native alpha | J
-            if ((me.rc = ensure(me.dS, me.cS, sn * (size_t)nb)) || (me.rc = ensure(me.dJ, me.cJ, sn * (size_t)nb)) ||
-                (me.rc = ensure(me.dA, me.cA, nnat)) || (me.rc = ensure(me.dV, me.cV, 7 * sn + (size_t)nb))) {
+            if ((me.rc = dev_grow(me.dS, me.cS, sn * (size_t)nb)) || (me.rc = dev_grow(me.dJ, me.cJ, sn * (size_t)nb)) ||
+                (me.rc = dev_grow(me.dA, me.cA, nnat)) || (me.rc = dev_grow(me.dV, me.cV, 7 * sn + (size_t)nb))) {
                 me.err = vrt_last_error();
                 return;
             }
@@ -436,12 +400,12 @@ int vrt_multi_execute_line(vrt_multi *mm, int64_t nlam, int64_t ld, const double
             chk(hipMemcpyAsync(d_lam, lambda + l0, w8 * (size_t)nb, hipMemcpyHostToDevice, st), "upload lambda");
             double *dU = nullptr, *dD = nullptr;
             if (I0_up && n1u) {
-                if ((me.rc = ensure(me.dU, me.cU, (size_t)n1u * (size_t)nb))) { me.err = vrt_last_error(); return; }
+                if ((me.rc = dev_grow(me.dU, me.cU, (size_t)n1u * (size_t)nb))) { me.err = vrt_last_error(); return; }
                 chk(hipMemcpy2DAsync(me.dU, w8 * (size_t)nb, I0_up + l0, w8 * (size_t)nlam, w8 * (size_t)nb, (size_t)n1u, hipMemcpyHostToDevice, st), "upload I0");
                 dU = me.dU;
             }
             if (I0_down && n1d) {
-                if ((me.rc = ensure(me.dD, me.cD, (size_t)n1d * (size_t)nb))) { me.err = vrt_last_error(); return; }
+                if ((me.rc = dev_grow(me.dD, me.cD, (size_t)n1d * (size_t)nb))) { me.err = vrt_last_error(); return; }
                 chk(hipMemcpy2DAsync(me.dD, w8 * (size_t)nb, I0_down + l0, w8 * (size_t)nlam, w8 * (size_t)nb, (size_t)n1d, hipMemcpyHostToDevice, st), "upload I0");
                 dD = me.dD;
             }
@@ -459,11 +423,7 @@ int vrt_multi_execute_line(vrt_multi *mm, int64_t nlam, int64_t ld, const double
         for (const Member &me : mm->m)
             if (me.rc) return fail(me.rc, "device " + std::to_string(me.device) + ": " + me.err);
         return VRT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    });
 }
 
 }  // extern "C"
@@ -520,19 +480,9 @@ static void multi_lambda_free(vrt_multi_lambda *s)
 
 namespace {
 
-int dmalloc(double **p, size_t count)
-{
-    *p = nullptr;
-    hipError_t e = hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(double));
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return fail(e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-    }
-    return VRT_OK;
-}
 int dupload(double **d, const double *h, size_t count, hipStream_t st)
 {
-    int rc = dmalloc(d, count);
+    int rc = dev_alloc(d, count);
     if (rc) return rc;
     VRT_HIP_TRY(hipMemcpyAsync(*d, h, sizeof(double) * count, hipMemcpyHostToDevice, st));
     return VRT_OK;
@@ -541,7 +491,7 @@ int dupload(double **d, const double *h, size_t count, hipStream_t st)
 int dupload_cols(double **d, const double *h, size_t rows, int64_t nlam, int64_t l0, int64_t l1, hipStream_t st)
 {
     const size_t nb = (size_t)(l1 - l0);
-    int rc = dmalloc(d, rows * nb);
+    int rc = dev_alloc(d, rows * nb);
     if (rc || nb == 0) return rc;
     VRT_HIP_TRY(hipMemcpy2DAsync(*d, sizeof(double) * nb, h + l0, sizeof(double) * (size_t)nlam, sizeof(double) * nb, rows, hipMemcpyHostToDevice, st));
     return VRT_OK;
@@ -553,7 +503,6 @@ extern "C" {
 
 int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double *weights, vrt_multi_lambda **out)
 {
-    DeviceScope scope;
     if (!out) return fail(VRT_EINVAL, "out is NULL");
     *out = nullptr;
     if (!mm || !lc || !weights) return fail(VRT_EINVAL, "NULL argument");
@@ -567,7 +516,7 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
         if (lc->blocks[2 * b] < 0 || lc->blocks[2 * b + 1] > nlam || lc->blocks[2 * b + 1] - lc->blocks[2 * b] < 2)
             return fail(VRT_EINVAL, "each wavelength block needs at least two wavelengths inside [0, nlam)");
     if (!(lc->lambda0 > 0) || !(lc->c0 > 0)) return fail(VRT_EINVAL, "lambda0 and c0 must be positive");
-    try {
+    return guarded([&] {
         std::lock_guard<std::mutex> lock(mm->mu);
         const int W = (int)mm->m.size();
         for (const Member &me : mm->m) {
@@ -577,8 +526,7 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
             if (p->A != (int)p->n_angles_user)
                 return fail(VRT_EINVAL, "per-angle alpha needs every angle active (no θ = 90 direction)");
         }
-        vrt_multi_lambda *s = new (std::nothrow) vrt_multi_lambda();
-        if (!s) return fail(VRT_ENOMEM, "out of host memory");
+        std::unique_ptr<vrt_multi_lambda, void (*)(vrt_multi_lambda *)> s(new vrt_multi_lambda(), multi_lambda_free);
         s->mm = mm;
         s->n = mm->n;
         s->nlam = nlam;
@@ -625,15 +573,15 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
             VRT_S(dupload(&l.d_pops, lc->lte_populations, 3 * n, st));               // populations = copy(LTE_pops), :232
             VRT_S(dupload_cols(&l.d_B0, lc->B0, n, nlam, l.l0, l.l1, st));
             VRT_S(dupload_cols(&l.d_S_new, lc->B0, n, nlam, l.l0, l.l1, st));        // S_new = B_0, :236-239
-            VRT_S(dmalloc(&l.d_S_old, n * nb));
-            VRT_S(dmalloc(&l.d_J, n * nb));
-            VRT_S(dmalloc(&l.d_gamma, n));
-            VRT_S(dmalloc(&l.d_strength, n));
-            VRT_S(dmalloc(&l.d_R, 9 * n));
-            VRT_S(dmalloc(&l.d_shares, 6 * n));
-            VRT_S(dmalloc(&l.d_I0, (size_t)g->up.n1 * nb));
-            VRT_S(dmalloc(&l.d_native, nb ? (size_t)vrt_plan_native_alpha_count(me.plan_all, (int64_t)nb) : 1));
-            if (!rc && hipMalloc((void **)&l.d_scalars, 2 * sizeof(unsigned long long)) != hipSuccess) rc = fail(VRT_ENOMEM, "hipMalloc");
+            VRT_S(dev_alloc(&l.d_S_old, n * nb));
+            VRT_S(dev_alloc(&l.d_J, n * nb));
+            VRT_S(dev_alloc(&l.d_gamma, n));
+            VRT_S(dev_alloc(&l.d_strength, n));
+            VRT_S(dev_alloc(&l.d_R, 9 * n));
+            VRT_S(dev_alloc(&l.d_shares, 6 * n));
+            VRT_S(dev_alloc(&l.d_I0, (size_t)g->up.n1 * nb));
+            VRT_S(dev_alloc(&l.d_native, nb ? (size_t)vrt_plan_native_alpha_count(me.plan_all, (int64_t)nb) : 1));
+            VRT_S(dev_alloc(&l.d_scalars, 2));
             if (!rc && hipEventCreateWithFlags(&l.ev, hipEventDisableTiming) != hipSuccess) rc = fail(VRT_ENODEVICE, "hipEventCreate");
             if (!rc && nb && (hipMemsetAsync(l.d_S_old, 0, sizeof(double) * n * nb, st) != hipSuccess ||
                               hipMemsetAsync(l.d_J, 0, sizeof(double) * n * nb, st) != hipSuccess))
@@ -642,11 +590,11 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
             if (s->native && nb) {
                 const size_t np = (size_t)vrt_plan_native_plane_count(me.plan_all, (int64_t)nb);
                 for (int dd = 0; dd < 2; dd++) {
-                    VRT_S(dmalloc(&l.d_S_nat[dd], np));
-                    VRT_S(dmalloc(&l.d_J_nat[dd], np));
+                    VRT_S(dev_alloc(&l.d_S_nat[dd], np));
+                    VRT_S(dev_alloc(&l.d_J_nat[dd], np));
                     if (!rc && hipMemsetAsync(l.d_J_nat[dd], 0, sizeof(double) * np, st) != hipSuccess) rc = fail(VRT_ENODEVICE, "hipMemsetAsync failed");
                 }
-                VRT_S(dmalloc(&l.d_B_up, np));
+                VRT_S(dev_alloc(&l.d_B_up, np));
                 VRT_S(planes_to_native(me.plan_all, (int64_t)nb, (int64_t)nb, l.d_B0, l.d_S_nat[0], l.d_S_nat[1], st));     // S_new = B_0
                 VRT_S(planes_to_native(me.plan_all, (int64_t)nb, (int64_t)nb, l.d_B0, l.d_B_up, nullptr, st));
             }
@@ -658,24 +606,17 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
         for (int d = 0; d < W; d++)
             if (!ok || rcs[(size_t)d]) {
                 const int rc = ok ? rcs[(size_t)d] : VRT_ENOMEM;
-                const std::string msg = ok ? "device " + std::to_string(mm->m[(size_t)d].device) + ": " + errs[(size_t)d] : "out of host memory";
-                multi_lambda_free(s);
-                return fail(rc, msg);
+                return fail(rc, ok ? "device " + std::to_string(mm->m[(size_t)d].device) + ": " + errs[(size_t)d] : "out of host memory");
             }
-        *out = s;
+        *out = s.release();
         return VRT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    });
 }
 
 int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
 {
-    DeviceScope scope;
     if (!s || !max_rel_change) return fail(VRT_EINVAL, "NULL argument");
-    try {
+    return guarded([&] {
         vrt_multi *mm = s->mm;
         std::lock_guard<std::mutex> lock(mm->mu);
         const int W = (int)mm->m.size();
@@ -776,55 +717,46 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
         *max_rel_change = is_nan ? std::nan("") : worst;
         s->iterations++;
         return VRT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+    });
 }
 
 int vrt_multi_lambda_get(vrt_multi_lambda *s, double *J, double *S, double *populations, double *R, double *gamma)
 {
-    DeviceScope scope;
     if (!s) return fail(VRT_EINVAL, "NULL session");
-    try {
-    vrt_multi *mm = s->mm;
-    std::lock_guard<std::mutex> lock(mm->mu);
-    const size_t n = (size_t)s->n, nl = (size_t)s->nlam, w8 = sizeof(double);
-    for (size_t d = 0; d < mm->m.size(); d++) {
-        const LambdaMember &l = s->lm[d];
-        const size_t nb = (size_t)(l.l1 - l.l0);
-        VRT_HIP_TRY(hipSetDevice(mm->m[d].device));
-        if (s->native && nb && (J || S)) {
-            // the caller's layout is formed here, on request (d_J / d_S_old of the block serve as scratch)
-            vrt_plan *p = mm->m[d].plan_all;
-            hipStream_t st = mm->m[d].stream;
-            std::lock_guard<std::mutex> plock(p->mu);
-            if (J) {
-                if (int rc = J_from_native(p, (int64_t)nb, (int64_t)nb, l.d_J_nat[0], l.d_J_nat[1], l.d_J, st)) return rc;
-                VRT_HIP_TRY(hipMemcpy2DAsync(J + l.l0, w8 * nl, l.d_J, w8 * nb, w8 * nb, n, hipMemcpyDeviceToHost, st));
+    return guarded([&] {
+        vrt_multi *mm = s->mm;
+        std::lock_guard<std::mutex> lock(mm->mu);
+        const size_t n = (size_t)s->n, nl = (size_t)s->nlam, w8 = sizeof(double);
+        for (size_t d = 0; d < mm->m.size(); d++) {
+            const LambdaMember &l = s->lm[d];
+            const size_t nb = (size_t)(l.l1 - l.l0);
+            VRT_HIP_TRY(hipSetDevice(mm->m[d].device));
+            if (s->native && nb && (J || S)) {
+                // the caller's layout is formed here, on request (d_J / d_S_old of the block serve as scratch)
+                vrt_plan *p = mm->m[d].plan_all;
+                hipStream_t st = mm->m[d].stream;
+                std::lock_guard<std::mutex> plock(p->mu);
+                if (J) {
+                    if (int rc = J_from_native(p, (int64_t)nb, (int64_t)nb, l.d_J_nat[0], l.d_J_nat[1], l.d_J, st)) return rc;
+                    VRT_HIP_TRY(hipMemcpy2DAsync(J + l.l0, w8 * nl, l.d_J, w8 * nb, w8 * nb, n, hipMemcpyDeviceToHost, st));
+                }
+                if (S) {
+                    if (int rc = plane_from_native(p, 0, (int64_t)nb, (int64_t)nb, l.d_S_nat[0], l.d_S_old, st)) return rc;
+                    VRT_HIP_TRY(hipMemcpy2DAsync(S + l.l0, w8 * nl, l.d_S_old, w8 * nb, w8 * nb, n, hipMemcpyDeviceToHost, st));
+                }
+                VRT_HIP_TRY(hipStreamSynchronize(st));
+            } else {
+            if (nb && J) VRT_HIP_TRY(hipMemcpy2D(J + l.l0, w8 * nl, l.d_J, w8 * nb, w8 * nb, n, hipMemcpyDeviceToHost));
+            if (nb && S) VRT_HIP_TRY(hipMemcpy2D(S + l.l0, w8 * nl, l.d_S_new, w8 * nb, w8 * nb, n, hipMemcpyDeviceToHost));
             }
-            if (S) {
-                if (int rc = plane_from_native(p, 0, (int64_t)nb, (int64_t)nb, l.d_S_nat[0], l.d_S_old, st)) return rc;
-                VRT_HIP_TRY(hipMemcpy2DAsync(S + l.l0, w8 * nl, l.d_S_old, w8 * nb, w8 * nb, n, hipMemcpyDeviceToHost, st));
+            if (d == 0) {
+                if (populations) VRT_HIP_TRY(hipMemcpy(populations, l.d_pops, w8 * 3 * n, hipMemcpyDeviceToHost));
+                if (R) VRT_HIP_TRY(hipMemcpy(R, l.d_R, w8 * 9 * n, hipMemcpyDeviceToHost));
+                if (gamma) VRT_HIP_TRY(hipMemcpy(gamma, l.d_gamma, w8 * n, hipMemcpyDeviceToHost));
             }
-            VRT_HIP_TRY(hipStreamSynchronize(st));
-        } else {
-        if (nb && J) VRT_HIP_TRY(hipMemcpy2D(J + l.l0, w8 * nl, l.d_J, w8 * nb, w8 * nb, n, hipMemcpyDeviceToHost));
-        if (nb && S) VRT_HIP_TRY(hipMemcpy2D(S + l.l0, w8 * nl, l.d_S_new, w8 * nb, w8 * nb, n, hipMemcpyDeviceToHost));
         }
-        if (d == 0) {
-            if (populations) VRT_HIP_TRY(hipMemcpy(populations, l.d_pops, w8 * 3 * n, hipMemcpyDeviceToHost));
-            if (R) VRT_HIP_TRY(hipMemcpy(R, l.d_R, w8 * 9 * n, hipMemcpyDeviceToHost));
-            if (gamma) VRT_HIP_TRY(hipMemcpy(gamma, l.d_gamma, w8 * n, hipMemcpyDeviceToHost));
-        }
-    }
-    return VRT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
+        return VRT_OK;
+    });
 }
 
 void vrt_multi_lambda_destroy(vrt_multi_lambda *s)

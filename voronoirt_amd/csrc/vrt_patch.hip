@@ -1574,7 +1574,7 @@ int ensure_patch_work(vrt_plan *p, int G, const std::vector<int32_t> &group_angl
             }
         }
     p->patch_work_off.back() = (int64_t)(work.size() / 2);
-    VRT_HIP_TRY(hipMalloc((void **)&p->d_patch_work, sizeof(int4) * std::max<size_t>(work.size(), 1)));
+    if (int rc = dev_alloc(&p->d_patch_work, work.size())) return rc;
     VRT_HIP_TRY(hipMemcpy(p->d_patch_work, work.data(), sizeof(int4) * work.size(), hipMemcpyHostToDevice));
     p->patch_work_groups = G;
     return VRT_OK;
@@ -1881,23 +1881,20 @@ static int ensure_patch_chain(vrt_plan *p, int npair, int lgB, int nsplit, bool 
     if (all.size() / 3 >= (size_t)INT32_MAX) return fail(VRT_EINVAL, "too many items for the chained launch");
     std::vector<int32_t> deps(p->h_patch_deps);
     deps.insert(deps.end(), rdeps.begin(), rdeps.end());
-    if (p->d_chain_items) { (void)hipFree(p->d_chain_items); p->d_chain_items = nullptr; }     // (stashed above: NULL here)
-    if (p->d_chain_deps) { (void)hipFree(p->d_chain_deps); p->d_chain_deps = nullptr; }
-    VRT_HIP_TRY(hipMalloc((void **)&p->d_chain_items, sizeof(int4) * std::max<size_t>(all.size(), 1)));
-    VRT_HIP_TRY(hipMalloc((void **)&p->d_chain_deps, sizeof(int32_t) * std::max<size_t>(deps.size(), 1)));
+    dev_free(p->d_chain_items);                          // (stashed above: NULL here)
+    dev_free(p->d_chain_deps);
+    int rc;
+    if ((rc = dev_alloc(&p->d_chain_items, all.size())) || (rc = dev_alloc(&p->d_chain_deps, deps.size()))) return rc;
     VRT_HIP_TRY(hipMemcpy(p->d_chain_items, all.data(), sizeof(int4) * all.size(), hipMemcpyHostToDevice));
     VRT_HIP_TRY(hipMemcpy(p->d_chain_deps, deps.data(), sizeof(int32_t) * deps.size(), hipMemcpyHostToDevice));
     const size_t words = (size_t)nsplit * (size_t)std::max<int64_t>(n_patches, 1);
     if (words > p->chain_progress_cap) {
-        if (p->d_chain_progress) { (void)hipFree(p->d_chain_progress); p->d_chain_progress = nullptr; }
-        p->chain_progress_cap = 0;
-        VRT_HIP_TRY(hipMalloc((void **)&p->d_chain_progress, sizeof(uint32_t) * words));
-        p->chain_progress_cap = words;
+        if ((rc = dev_grow(p->d_chain_progress, p->chain_progress_cap, words))) return rc;
         p->chain_progress_fresh = true;
     }
     // (epochs keep counting across item sets: a word of an earlier set compares as "behind" whatever it meant there;
     // freshly allocated words are zeroed on the launch stream, ahead of the first launch that polls them)
-    if (!p->d_chain_ctrl) VRT_HIP_TRY(hipMalloc((void **)&p->d_chain_ctrl, sizeof(uint32_t) * (kChainAbortWord + 4)));
+    if (!p->d_chain_ctrl && (rc = dev_alloc(&p->d_chain_ctrl, kChainAbortWord + 4))) return rc;
     if (!p->h_chain_status) {
         VRT_HIP_TRY(hipHostMalloc((void **)&p->h_chain_status, 64, hipHostMallocMapped));
         *p->h_chain_status = 0;
@@ -1974,7 +1971,11 @@ int launch_patch_chain(vrt_plan *p, const TileArgs &ta, int npair, hipStream_t s
     }
     h.dbg = kDiag ? p->tune.debug_flags : 0;
     // the argument block travels only when it has changed (stream-ordered: behind the launches that read the old one)
-    if (!p->d_chain_dev) VRT_HIP_TRY(hipMalloc((void **)&p->d_chain_dev, sizeof(ChainDev)));
+    if (!p->d_chain_dev) {
+        ChainDev *cd = nullptr;
+        if ((rc = dev_alloc(&cd, 1))) return rc;
+        p->d_chain_dev = cd;
+    }
     if (p->h_chain_dev.size() != sizeof(ChainDev) || std::memcmp(p->h_chain_dev.data(), &h, sizeof(h)) != 0) {
         if (!p->h_chain_dev_pinned) VRT_HIP_TRY(hipHostMalloc((void **)&p->h_chain_dev_pinned, sizeof(ChainDev), hipHostMallocDefault));
         // the pinned staging copy may still be in flight for an earlier launch: wait for that copy only

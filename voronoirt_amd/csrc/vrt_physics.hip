@@ -686,16 +686,6 @@ static int synth_opacity_checks(int64_t nz, int64_t nx, int64_t ny, const double
     return VRT_OK;
 }
 
-static int current_device(int *dev)
-{
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0)
-        return fail(VRT_ENODEVICE, "no HIP device available (libvrt_hip has no CPU fallback)");
-    VRT_HIP_TRY(hipGetDevice(dev));
-    (void)hipGetLastError();           // (an earlier call's error is not this entry point's)
-    return VRT_OK;
-}
-
 static int synth_opacity_launch(int64_t nz, int64_t nx, int64_t ny, const double *k, int64_t nlam, const double *lambda,
                                 const double *planck2, double lambda0, double c0, double hc_over_kB, double strength_const,
                                 double Bij, double Bji, double src_const, double g_ratio, const double *d_velocity,
@@ -734,15 +724,14 @@ extern "C" int vrt_synth_opacity_dev(int64_t nz, int64_t nx, int64_t ny, const d
                                      const double *d_temperature, const double *d_alpha_cont,
                                      const double *d_populations, double *d_S, double *d_alpha, void *stream)
 {
-    DeviceScope scope;
-    int rc = synth_opacity_checks(nz, nx, ny, k, nlam, lambda, planck2, d_velocity, d_doppler, d_gamma_static,
-                                  d_gamma_unsold, d_temperature, d_alpha_cont, d_populations, d_S, d_alpha);
-    if (rc) return rc;
-    int dev = 0;
-    if ((rc = current_device(&dev))) return rc;
-    return synth_opacity_launch(nz, nx, ny, k, nlam, lambda, planck2, lambda0, c0, hc_over_kB, strength_const, Bij, Bji,
-                                src_const, g_ratio, d_velocity, d_doppler, d_gamma_static, d_gamma_unsold, d_temperature,
-                                d_alpha_cont, d_populations, d_S, d_alpha, (hipStream_t)stream);
+    return guarded([&] {
+        int rc = synth_opacity_checks(nz, nx, ny, k, nlam, lambda, planck2, d_velocity, d_doppler, d_gamma_static,
+                                      d_gamma_unsold, d_temperature, d_alpha_cont, d_populations, d_S, d_alpha);
+        if (rc || (rc = use_current_device())) return rc;
+        return synth_opacity_launch(nz, nx, ny, k, nlam, lambda, planck2, lambda0, c0, hc_over_kB, strength_const, Bij, Bji,
+                                    src_const, g_ratio, d_velocity, d_doppler, d_gamma_static, d_gamma_unsold, d_temperature,
+                                    d_alpha_cont, d_populations, d_S, d_alpha, (hipStream_t)stream);
+    });
 }
 
 extern "C" int vrt_synth_opacity(int device, int64_t nz, int64_t nx, int64_t ny, const double *k, int64_t nlam,
@@ -752,36 +741,35 @@ extern "C" int vrt_synth_opacity(int device, int64_t nz, int64_t nx, int64_t ny,
                                  const double *gamma_unsold, const double *temperature, const double *alpha_cont,
                                  const double *populations, double *S, double *alpha)
 {
-    DeviceScope scope;
-    int rc = synth_opacity_checks(nz, nx, ny, k, nlam, lambda, planck2, velocity, doppler, gamma_static, gamma_unsold,
-                                  temperature, alpha_cont, populations, S, alpha);
-    if (rc) return rc;
-    if ((rc = use_device(device))) return rc;
-    const size_t vol = (size_t)(nz * nx * ny), out = (size_t)(nz * (nx + 2) * (ny + 2)) * (size_t)nlam;
-    // one device block: velocity (3) | doppler | gamma_static | gamma_unsold | temperature | alpha_cont | populations (2)
-    // | S | alpha
-    double *d = nullptr;
-    hipError_t e = hipMalloc((void **)&d, sizeof(double) * (10 * vol + 2 * out));
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-    const double *src[7] = {velocity, doppler, gamma_static, gamma_unsold, temperature, alpha_cont, populations};
-    const size_t len[7] = {3 * vol, vol, vol, vol, vol, vol, 2 * vol};
-    double *dp[7] = {};
-    size_t off = 0;
-    for (int f = 0; f < 7 && e == hipSuccess; f++) {
-        dp[f] = d + off;
-        e = hipMemcpy(dp[f], src[f], sizeof(double) * len[f], hipMemcpyHostToDevice);
-        off += len[f];
-    }
-    double *dS = d + off, *dA = dS + out;
-    if (e != hipSuccess) rc = fail(VRT_ENODEVICE, std::string("vrt_synth_opacity: ") + hipGetErrorString(e));
-    if (!rc)
-        rc = synth_opacity_launch(nz, nx, ny, k, nlam, lambda, planck2, lambda0, c0, hc_over_kB, strength_const, Bij, Bji,
-                                  src_const, g_ratio, dp[0], dp[1], dp[2], dp[3], dp[4], dp[5], dp[6], dS, dA, nullptr);
-    if (!rc && ((e = hipDeviceSynchronize()) != hipSuccess ||
-                (e = hipMemcpy(S, dS, sizeof(double) * out, hipMemcpyDeviceToHost)) != hipSuccess ||
-                (e = hipMemcpy(alpha, dA, sizeof(double) * out, hipMemcpyDeviceToHost)) != hipSuccess))
-        rc = fail(VRT_ENODEVICE, std::string("vrt_synth_opacity: ") + hipGetErrorString(e));
-    (void)hipFree(d);
-    return rc;
+    return guarded([&] {
+        int rc = synth_opacity_checks(nz, nx, ny, k, nlam, lambda, planck2, velocity, doppler, gamma_static, gamma_unsold,
+                                      temperature, alpha_cont, populations, S, alpha);
+        if (rc || (rc = use_device(device))) return rc;
+        const size_t vol = (size_t)(nz * nx * ny), out = (size_t)(nz * (nx + 2) * (ny + 2)) * (size_t)nlam;
+        // one device block: velocity (3) | doppler | gamma_static | gamma_unsold | temperature | alpha_cont | populations (2)
+        // | S | alpha
+        DevBuf<double> d;
+        if ((rc = d.alloc(10 * vol + 2 * out))) return rc;
+        const double *src[7] = {velocity, doppler, gamma_static, gamma_unsold, temperature, alpha_cont, populations};
+        const size_t len[7] = {3 * vol, vol, vol, vol, vol, vol, 2 * vol};
+        double *dp[7] = {};
+        size_t off = 0;
+        hipError_t e = hipSuccess;
+        for (int f = 0; f < 7 && e == hipSuccess; f++) {
+            dp[f] = d + off;
+            e = hipMemcpy(dp[f], src[f], sizeof(double) * len[f], hipMemcpyHostToDevice);
+            off += len[f];
+        }
+        double *dS = d + off, *dA = dS + out;
+        if (e != hipSuccess) return fail(VRT_ENODEVICE, std::string("vrt_synth_opacity: ") + hipGetErrorString(e));
+        if ((rc = synth_opacity_launch(nz, nx, ny, k, nlam, lambda, planck2, lambda0, c0, hc_over_kB, strength_const, Bij,
+                                       Bji, src_const, g_ratio, dp[0], dp[1], dp[2], dp[3], dp[4], dp[5], dp[6], dS, dA,
+                                       nullptr)))
+            return rc;
+        if ((e = hipDeviceSynchronize()) != hipSuccess ||
+            (e = hipMemcpy(S, dS, sizeof(double) * out, hipMemcpyDeviceToHost)) != hipSuccess ||
+            (e = hipMemcpy(alpha, dA, sizeof(double) * out, hipMemcpyDeviceToHost)) != hipSuccess)
+            return fail(VRT_ENODEVICE, std::string("vrt_synth_opacity: ") + hipGetErrorString(e));
+        return VRT_OK;
+    });
 }

@@ -35,23 +35,6 @@ constexpr double kTieTol = 1e-12;       // relative: a near-tie is searched like
 constexpr int kChunk = 16;              // fields per LDS transpose chunk
 constexpr int kGatherThreads = 256;     // four waves, 64 raster points (or sites) each
 
-template <typename T>
-int dev_alloc(T **p, size_t count)
-{
-    *p = nullptr;
-    const hipError_t e = hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipSuccess) return VRT_OK;
-    *p = nullptr;
-    return fail(e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-}
-
-template <typename T>
-void dev_free(T *&p)
-{
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
-}
-
 struct NearArgs {
     const double *pos;
     const int32_t *adj_ptr, *adj;    // symmetric site adjacency, 0-based (walls dropped)
@@ -574,7 +557,7 @@ struct RasterLocator {
     int32_t *d_cell_start = nullptr, *d_cell_sites = nullptr, *d_seed = nullptr;
     int32_t *d_adj_ptr = nullptr, *d_adj = nullptr;      // symmetric closure of the neighbour rows, 0-based
     unsigned long long *d_stats = nullptr;
-    void *d_work = nullptr;                  // idx1, idx2, d1, d2 of the raster points / queries (grow-only)
+    char *d_work = nullptr;                  // idx1, idx2, d1, d2 of the raster points / queries (grow-only)
     size_t work_cap = 0;
     double *d_axes = nullptr;
     size_t axes_cap = 0;
@@ -594,7 +577,7 @@ void raster_locator_free(vrt_grid *g)
     dev_free(L->d_adj_ptr);
     dev_free(L->d_adj);
     dev_free(L->d_stats);
-    if (L->d_work) (void)hipFree(L->d_work);
+    dev_free(L->d_work);
     dev_free(L->d_axes);
     for (hipEvent_t &e : L->ev)
         if (e) (void)hipEventDestroy(e);
@@ -708,27 +691,6 @@ int build_locator(vrt_grid *g)
     return VRT_OK;
 }
 
-int ensure_work(RasterLocator *L, size_t bytes)
-{
-    if (L->work_cap >= bytes) return VRT_OK;
-    if (L->d_work) (void)hipFree(L->d_work);
-    L->d_work = nullptr;
-    L->work_cap = 0;
-    VRT_HIP_TRY(hipMalloc(&L->d_work, bytes));
-    L->work_cap = bytes;
-    return VRT_OK;
-}
-
-int ensure_axes(RasterLocator *L, size_t count)
-{
-    if (L->axes_cap >= count) return VRT_OK;
-    dev_free(L->d_axes);
-    L->axes_cap = 0;
-    int rc = dev_alloc(&L->d_axes, count);
-    if (!rc) L->axes_cap = count;
-    return rc;
-}
-
 bool finite_ascending(const double *a, int64_t n)
 {
     for (int64_t i = 0; i < n; i++)
@@ -820,8 +782,8 @@ int to_raster_impl(vrt_grid *g, int64_t nz, int64_t nx, int64_t ny, const double
     RasterLocator *L = g->locator;
     const int64_t P = nz * nx * ny;
     const int k = mode == VRT_RASTER_INV_DIST2 ? 2 : 1;
-    if ((rc = ensure_work(L, (size_t)P * (k == 2 ? 24 : 4)))) return rc;
-    if ((rc = ensure_axes(L, (size_t)(nz + nx + ny)))) return rc;
+    if ((rc = dev_grow(L->d_work, L->work_cap, (size_t)P * (k == 2 ? 24 : 4)))) return rc;
+    if ((rc = dev_grow(L->d_axes, L->axes_cap, (size_t)(nz + nx + ny)))) return rc;
     VRT_HIP_TRY(hipMemcpyAsync(L->d_axes, z, sizeof(double) * nz, hipMemcpyHostToDevice, st));
     VRT_HIP_TRY(hipMemcpyAsync(L->d_axes + nz, x, sizeof(double) * nx, hipMemcpyHostToDevice, st));
     VRT_HIP_TRY(hipMemcpyAsync(L->d_axes + nz + nx, y, sizeof(double) * ny, hipMemcpyHostToDevice, st));
@@ -886,7 +848,7 @@ int to_grid_impl(vrt_grid *g, int64_t nz, int64_t nx, int64_t ny, const double *
     if (rc) return rc;
     RasterLocator *L = g->locator;
     const int64_t na = nz + nx + ny;
-    rc = ensure_axes(L, (size_t)na);
+    rc = dev_grow(L->d_axes, L->axes_cap, (size_t)na);
     if (rc) return rc;
     VRT_HIP_TRY(hipMemcpyAsync(L->d_axes, z, sizeof(double) * nz, hipMemcpyHostToDevice, st));
     VRT_HIP_TRY(hipMemcpyAsync(L->d_axes + nz, x, sizeof(double) * nx, hipMemcpyHostToDevice, st));
@@ -898,18 +860,6 @@ int to_grid_impl(vrt_grid *g, int64_t nz, int64_t nx, int64_t ny, const double *
     VRT_HIP_TRY(hipGetLastError());
     VRT_HIP_TRY(hipStreamSynchronize(st));
     return VRT_OK;
-}
-
-template <typename Fn>
-int guarded(Fn fn)
-{
-    try {
-        return fn();
-    } catch (const std::bad_alloc &) {
-        return fail(VRT_ENOMEM, "out of host memory");
-    } catch (...) {
-        return fail(VRT_EINVAL, "unexpected exception");
-    }
 }
 
 // ---- rejection sampling: host side ----------------------------------------------------------------------------------
@@ -943,20 +893,6 @@ int check_range(int64_t nonfinite, double qmin, double qmax)
     return VRT_OK;
 }
 
-struct SampleWork {
-    double *axes = nullptr;
-    unsigned long long *masks = nullptr;
-    int32_t *counts = nullptr;
-    int64_t *state = nullptr;         // accepted so far, accepted before the batch, j of the n-th accepted
-    ~SampleWork()
-    {
-        dev_free(axes);
-        dev_free(masks);
-        dev_free(counts);
-        dev_free(state);
-    }
-};
-
 // next batch under batch = 0: the proposals that the acceptance seen so far needs for the remaining sites, plus a
 // quarter, or four times the last batch while nothing has been accepted
 int64_t next_batch(int64_t n, int64_t accepted, int64_t proposed, int64_t last)
@@ -984,31 +920,33 @@ int sample_impl(int64_t nz, int64_t nx, int64_t ny, const double *z, const doubl
     a.use_lds = na <= kSampleLdsAxes;
     const int64_t cap = max_proposals > 0 ? max_proposals : 1000 * n + ((int64_t)1 << 20);
     const int64_t bmax = std::min(batch > 0 ? std::min(batch, kSampleBatchMax) : kSampleBatchMax, cap);
-    SampleWork w;
+    DevBuf<double> axes;
+    DevBuf<unsigned long long> masks;
+    DevBuf<int32_t> counts;
+    DevBuf<int64_t> state;            // accepted so far, accepted before the batch, j of the n-th accepted
     int rc;
-    if ((rc = dev_alloc(&w.axes, (size_t)na))) return rc;
-    if ((rc = dev_alloc(&w.masks, (size_t)((bmax + 63) / 64)))) return rc;
-    if ((rc = dev_alloc(&w.counts, (size_t)((bmax + 63) / 64)))) return rc;
-    if ((rc = dev_alloc(&w.state, 3))) return rc;
-    a.axes = w.axes;
-    VRT_HIP_TRY(hipMemcpyAsync(w.axes, z, sizeof(double) * nz, hipMemcpyHostToDevice, st));
-    VRT_HIP_TRY(hipMemcpyAsync(w.axes + nz, x, sizeof(double) * nx, hipMemcpyHostToDevice, st));
-    VRT_HIP_TRY(hipMemcpyAsync(w.axes + nz + nx, y, sizeof(double) * ny, hipMemcpyHostToDevice, st));
-    VRT_HIP_TRY(hipMemsetAsync(w.state, 0, 3 * sizeof(int64_t), st));
+    if ((rc = axes.alloc((size_t)na)) || (rc = masks.alloc((size_t)((bmax + 63) / 64))) ||
+        (rc = counts.alloc((size_t)((bmax + 63) / 64))) || (rc = state.alloc(3)))
+        return rc;
+    a.axes = axes;
+    VRT_HIP_TRY(hipMemcpyAsync(axes, z, sizeof(double) * nz, hipMemcpyHostToDevice, st));
+    VRT_HIP_TRY(hipMemcpyAsync(axes + nz, x, sizeof(double) * nx, hipMemcpyHostToDevice, st));
+    VRT_HIP_TRY(hipMemcpyAsync(axes + nz + nx, y, sizeof(double) * ny, hipMemcpyHostToDevice, st));
+    VRT_HIP_TRY(hipMemsetAsync(state, 0, 3 * sizeof(int64_t), st));
     const size_t lds = a.use_lds ? sizeof(double) * (size_t)na : 0;
     int64_t proposed = 0, accepted = 0, count = 0;
     while (accepted < n && proposed < cap) {
         count = std::min(batch > 0 ? bmax : next_batch(n, accepted, proposed, count), cap - proposed);
         const unsigned blocks = (unsigned)std::min<int64_t>((count + kSampleThreads - 1) / kSampleThreads, kSampleGrid);
         hipLaunchKernelGGL(k_sample_flags, dim3(blocks), dim3(kSampleThreads), lds, st, a, (uint64_t)proposed, count,
-                           w.masks, w.counts);
+                           masks, counts);
         VRT_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_sample_scan, dim3(1), dim3(kScanThreads), 0, st, (count + 63) / 64, w.counts, w.state);
+        hipLaunchKernelGGL(k_sample_scan, dim3(1), dim3(kScanThreads), 0, st, (count + 63) / 64, counts, state);
         VRT_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_sample_write, dim3(blocks), dim3(kSampleThreads), 0, st, a, (uint64_t)proposed, count,
-                           w.masks, w.counts, w.state, n, d_pos);
+                           masks, counts, state, n, d_pos);
         VRT_HIP_TRY(hipGetLastError());
-        VRT_HIP_TRY(hipMemcpyAsync(&accepted, w.state, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        VRT_HIP_TRY(hipMemcpyAsync(&accepted, state, sizeof(int64_t), hipMemcpyDeviceToHost, st));
         VRT_HIP_TRY(hipStreamSynchronize(st));
         proposed += count;
     }
@@ -1019,7 +957,7 @@ int sample_impl(int64_t nz, int64_t nx, int64_t ny, const double *z, const doubl
                                     " proposals (max_proposals reached)");
     }
     int64_t last_j = 0;
-    VRT_HIP_TRY(hipMemcpyAsync(&last_j, w.state + 2, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    VRT_HIP_TRY(hipMemcpyAsync(&last_j, state + 2, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     VRT_HIP_TRY(hipStreamSynchronize(st));
     if (proposals_used) *proposals_used = last_j + 1;
     return VRT_OK;
@@ -1033,7 +971,6 @@ using namespace vrt;
 extern "C" int vrt_grid_nearest(vrt_grid *g, int64_t nq, const double *q_zxy, int metric, int k, int64_t *idx,
                                 double *dist)
 {
-    DeviceScope scope;
     return guarded([&]() -> int {
         if (!g || !q_zxy || !idx) return fail(VRT_EINVAL, "NULL argument");
         int rc = check_metric(g, metric);
@@ -1054,7 +991,7 @@ extern "C" int vrt_grid_nearest(vrt_grid *g, int64_t nq, const double *q_zxy, in
         if ((rc = build_locator(g))) return rc;
         RasterLocator *L = g->locator;
         // workspace: queries (3 nq doubles), d1, d2, idx1, idx2
-        if ((rc = ensure_work(L, (size_t)nq * (24 + 16 + 8)))) return rc;
+        if ((rc = dev_grow(L->d_work, L->work_cap, (size_t)nq * (24 + 16 + 8)))) return rc;
         double *dq = (double *)L->d_work;
         NearArgs a = near_args(g, metric, k);
         a.nq = nq;
@@ -1089,7 +1026,6 @@ extern "C" int vrt_grid_to_raster_dev(vrt_grid *g, int64_t nz, int64_t nx, int64
                                       const double *y, int metric, int mode, int64_t nf, int64_t ld, const double *d_fields,
                                       double *d_raster, void *stream)
 {
-    DeviceScope scope;
     return guarded([&]() -> int {
         int rc = to_raster_checks(g, nz, nx, ny, z, x, y, metric, mode, nf, ld, d_fields, d_raster);
         if (rc) return rc;
@@ -1103,24 +1039,19 @@ extern "C" int vrt_grid_to_raster(vrt_grid *g, int64_t nz, int64_t nx, int64_t n
                                   const double *y, int metric, int mode, int64_t nf, int64_t ld, const double *fields,
                                   double *raster)
 {
-    DeviceScope scope;
     return guarded([&]() -> int {
         int rc = to_raster_checks(g, nz, nx, ny, z, x, y, metric, mode, nf, ld, fields, raster);
         if (rc) return rc;
         if ((rc = use_device(g->device))) return rc;
         std::lock_guard<std::mutex> lock(g->mu);
         const size_t nfield = (size_t)ld * (size_t)(g->n - 1) + (size_t)nf, nout = (size_t)(nz * nx * ny) * (size_t)nf;
-        double *df = nullptr, *dr = nullptr;
-        if ((rc = dev_alloc(&df, nfield))) return rc;
-        if ((rc = dev_alloc(&dr, nout))) { dev_free(df); return rc; }
-        hipStream_t st = nullptr;
+        DevBuf<double> df, dr;
+        if ((rc = df.alloc(nfield)) || (rc = dr.alloc(nout))) return rc;
         if (hipMemcpy(df, fields, sizeof(double) * nfield, hipMemcpyHostToDevice) != hipSuccess)
             rc = fail(VRT_ENODEVICE, "HIP error uploading the fields");
-        if (!rc) rc = to_raster_impl(g, nz, nx, ny, z, x, y, metric, mode, nf, ld, df, dr, st);
+        if (!rc) rc = to_raster_impl(g, nz, nx, ny, z, x, y, metric, mode, nf, ld, df, dr, nullptr);
         if (!rc && hipMemcpy(raster, dr, sizeof(double) * nout, hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(VRT_ENODEVICE, "HIP error downloading the raster");
-        dev_free(df);
-        dev_free(dr);
         return rc;
     });
 }
@@ -1129,7 +1060,6 @@ extern "C" int vrt_raster_to_grid_dev(vrt_grid *g, int64_t nz, int64_t nx, int64
                                       const double *y, int64_t nf, const double *d_raster, int64_t ld, double *d_fields,
                                       void *stream)
 {
-    DeviceScope scope;
     return guarded([&]() -> int {
         int rc = to_grid_checks(g, nz, nx, ny, z, x, y, nf, ld, d_raster, d_fields);
         if (rc) return rc;
@@ -1142,16 +1072,14 @@ extern "C" int vrt_raster_to_grid_dev(vrt_grid *g, int64_t nz, int64_t nx, int64
 extern "C" int vrt_raster_to_grid(vrt_grid *g, int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x,
                                   const double *y, int64_t nf, const double *raster, int64_t ld, double *fields)
 {
-    DeviceScope scope;
     return guarded([&]() -> int {
         int rc = to_grid_checks(g, nz, nx, ny, z, x, y, nf, ld, raster, fields);
         if (rc) return rc;
         if ((rc = use_device(g->device))) return rc;
         std::lock_guard<std::mutex> lock(g->mu);
         const size_t nin = (size_t)(nz * nx * ny) * (size_t)nf, nout = (size_t)ld * (size_t)(g->n - 1) + (size_t)nf;
-        double *dr = nullptr, *df = nullptr;
-        if ((rc = dev_alloc(&dr, nin))) return rc;
-        if ((rc = dev_alloc(&df, nout))) { dev_free(dr); return rc; }
+        DevBuf<double> dr, df;
+        if ((rc = dr.alloc(nin)) || (rc = df.alloc(nout))) return rc;
         // the caller's padding between rows (ld > nf) is kept as it is
         if (hipMemcpy(dr, raster, sizeof(double) * nin, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(df, fields, sizeof(double) * nout, hipMemcpyHostToDevice) != hipSuccess)
@@ -1159,8 +1087,6 @@ extern "C" int vrt_raster_to_grid(vrt_grid *g, int64_t nz, int64_t nx, int64_t n
         if (!rc) rc = to_grid_impl(g, nz, nx, ny, z, x, y, nf, dr, ld, df, nullptr);
         if (!rc && hipMemcpy(fields, df, sizeof(double) * nout, hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(VRT_ENODEVICE, "HIP error downloading the fields");
-        dev_free(dr);
-        dev_free(df);
         return rc;
     });
 }
@@ -1182,7 +1108,6 @@ extern "C" int vrt_sample_sites(int device, int64_t nz, int64_t nx, int64_t ny, 
                                 const double *y, const double *quantity, int64_t n_sites, uint64_t seed, int64_t batch,
                                 int64_t max_proposals, double *pos_zxy, int64_t *proposals_used)
 {
-    DeviceScope scope;
     return guarded([&]() -> int {
         int rc = sample_checks(device, nz, nx, ny, z, x, y, quantity, n_sites, batch, max_proposals, pos_zxy);
         if (rc) return rc;
@@ -1197,9 +1122,8 @@ extern "C" int vrt_sample_sites(int device, int64_t nz, int64_t nx, int64_t ny, 
         }
         if ((rc = check_range(nonfinite, qmin, qmax))) return rc;
         if ((rc = use_device(device))) return rc;
-        double *dq = nullptr, *dp = nullptr;
-        if ((rc = dev_alloc(&dq, (size_t)P))) return rc;
-        if ((rc = dev_alloc(&dp, (size_t)n_sites * 3))) { dev_free(dq); return rc; }
+        DevBuf<double> dq, dp;
+        if ((rc = dq.alloc((size_t)P)) || (rc = dp.alloc((size_t)n_sites * 3))) return rc;
         hipStream_t st = nullptr;
         if (hipMemcpy(dq, quantity, sizeof(double) * P, hipMemcpyHostToDevice) != hipSuccess)
             rc = fail(VRT_ENODEVICE, "HIP error uploading the quantity");
@@ -1209,8 +1133,6 @@ extern "C" int vrt_sample_sites(int device, int64_t nz, int64_t nx, int64_t ny, 
         if (!rc && hipMemcpy(pos_zxy, dp, sizeof(double) * 3 * n_sites, hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(VRT_ENODEVICE, "HIP error downloading the positions");
         if (proposals_used) *proposals_used = used;
-        dev_free(dq);
-        dev_free(dp);
         return rc;
     });
 }
@@ -1220,7 +1142,6 @@ extern "C" int vrt_sample_sites_dev(int device, int64_t nz, int64_t nx, int64_t 
                                     int64_t batch, int64_t max_proposals, double *d_pos_zxy, int64_t *proposals_used,
                                     void *stream)
 {
-    DeviceScope scope;
     return guarded([&]() -> int {
         int rc = sample_checks(device, nz, nx, ny, z, x, y, d_quantity, n_sites, batch, max_proposals, d_pos_zxy);
         if (rc) return rc;
@@ -1228,16 +1149,14 @@ extern "C" int vrt_sample_sites_dev(int device, int64_t nz, int64_t nx, int64_t 
         hipStream_t st = (hipStream_t)stream;
         const int64_t P = nz * nx * ny;
         const int blocks = (int)std::min<int64_t>((P + kMinMaxThreads - 1) / kMinMaxThreads, kMinMaxGrid);
-        double *dpart = nullptr;
-        if ((rc = dev_alloc(&dpart, (size_t)blocks * 3))) return rc;
         std::vector<double> part((size_t)blocks * 3);
+        DevBuf<double> dpart;
+        if ((rc = dpart.alloc(part.size()))) return rc;
         hipLaunchKernelGGL(k_minmax, dim3(blocks), dim3(kMinMaxThreads), 0, st, P, d_quantity, dpart);
         if (hipGetLastError() != hipSuccess ||
             hipMemcpyAsync(part.data(), dpart, sizeof(double) * part.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)
-            rc = fail(VRT_ENODEVICE, "HIP error in the quantity's min/max reduction");
-        dev_free(dpart);
-        if (rc) return rc;
+            return fail(VRT_ENODEVICE, "HIP error in the quantity's min/max reduction");
         double qmin = INFINITY, qmax = -INFINITY, bad = 0.0;
         for (int b = 0; b < blocks; b++) {
             qmin = std::min(qmin, part[3 * (size_t)b]);

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <memory>
 #include <vector>
 
 #include "vrt_internal.h"
@@ -779,14 +780,15 @@ struct vrt_regular {
     std::vector<double> h_g;               // the same on the host (launch geometry)
     double *d_S = nullptr, *d_A = nullptr, *d_I = nullptr, *d_k = nullptr, *d_coef = nullptr, *d_xy = nullptr;
     int *d_up = nullptr;
-    int64_t cap_S = 0, cap_A = 0, cap_I = 0, cap_k = 0, cap_coef = 0, cap_xy = 0;      // in solves
+    size_t cap_S = 0, cap_A = 0, cap_I = 0, cap_coef = 0, cap_xy = 0;     // in doubles
+    int64_t cap_k = 0;                     // in solves
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     bool timed = false;
     int force_threads = 0;                 // VRT_REG_THREADS, read once at creation (tests: forces the launch shape)
     int xy_split = 1;                      // VRT_REG_XY (creation): 0 = all-xy batches through k_regular_solve too;
                                            //   2 = split, upwind plane read from memory instead of LDS (tests)
     double *d_I0 = nullptr;                // vrt_regular_emergent_dev: the bottom planes of S of one chunk
-    int64_t cap_I0 = 0;
+    size_t cap_I0 = 0;
     int64_t emergent_bytes = (int64_t)8 << 30;  // VRT_REG_EMERGENT_BYTES (creation): workspace cap of an emergent chunk
 };
 
@@ -801,56 +803,37 @@ static void regular_free(vrt_regular *r)
     delete r;
 }
 
+using RegularPtr = std::unique_ptr<vrt_regular, void (*)(vrt_regular *)>;
+
 extern "C" int vrt_regular_create(int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x,
                                   const double *y, int device, vrt_regular **out)
 {
-    DeviceScope scope;
     if (!z || !x || !y || !out) return fail(VRT_EINVAL, "NULL argument");
     if (nz < 2 || nx < 3 || ny < 3) return fail(VRT_EINVAL, "bad sizes");
     if (nx > 16384 || ny > 16384) return fail(VRT_EINVAL, "nx, ny must be at most 16384");
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0)
-        return fail(VRT_ENODEVICE, "no HIP device available (libvrt_hip has no CPU fallback)");
-    if (device < 0 || device >= cnt) return fail(VRT_EINVAL, "device ordinal out of range");
-    VRT_HIP_TRY(hipSetDevice(device));
-    vrt_regular *r = new vrt_regular;
-    if (const char *e = std::getenv("VRT_REG_THREADS")) r->force_threads = std::max(64, std::min(1024, std::atoi(e) / 64 * 64));
-    if (const char *e = std::getenv("VRT_REG_XY")) r->xy_split = std::max(0, std::min(2, std::atoi(e)));
-    if (const char *e = std::getenv("VRT_REG_EMERGENT_BYTES")) r->emergent_bytes = std::max<int64_t>(1, std::atoll(e));
-    r->device = device;
-    r->nz = nz; r->nx = nx; r->ny = ny;
-    r->h_g.assign(z, z + nz);
-    r->h_g.insert(r->h_g.end(), x, x + nx);
-    r->h_g.insert(r->h_g.end(), y, y + ny);
-    hipError_t e = hipMalloc((void **)&r->d_g, sizeof(double) * (size_t)(nz + nx + ny));
-    if (e == hipSuccess) e = hipMemcpy(r->d_g, z, sizeof(double) * nz, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(r->d_g + nz, x, sizeof(double) * nx, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(r->d_g + nz + nx, y, sizeof(double) * ny, hipMemcpyHostToDevice);
-    for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipEventCreate(&r->ev[i]);
-    if (e != hipSuccess) {
-        regular_free(r);
-        return fail(VRT_ENODEVICE, std::string("vrt_regular_create: ") + hipGetErrorString(e));
-    }
-    *out = r;
-    return VRT_OK;
+    return guarded([&] {
+        int rc = use_current_device();
+        if (!rc) rc = device < 0 ? fail(VRT_EINVAL, "device ordinal out of range") : use_device(device);
+        if (rc) return rc;
+        RegularPtr r(new vrt_regular, regular_free);
+        if (const char *e = std::getenv("VRT_REG_THREADS")) r->force_threads = std::max(64, std::min(1024, std::atoi(e) / 64 * 64));
+        if (const char *e = std::getenv("VRT_REG_XY")) r->xy_split = std::max(0, std::min(2, std::atoi(e)));
+        if (const char *e = std::getenv("VRT_REG_EMERGENT_BYTES")) r->emergent_bytes = std::max<int64_t>(1, std::atoll(e));
+        r->device = device;
+        r->nz = nz; r->nx = nx; r->ny = ny;
+        r->h_g.assign(z, z + nz);
+        r->h_g.insert(r->h_g.end(), x, x + nx);
+        r->h_g.insert(r->h_g.end(), y, y + ny);
+        if ((rc = dev_alloc(&r->d_g, (size_t)(nz + nx + ny)))) return rc;
+        hipError_t e = hipMemcpy(r->d_g, r->h_g.data(), sizeof(double) * r->h_g.size(), hipMemcpyHostToDevice);
+        for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipEventCreate(&r->ev[i]);
+        if (e != hipSuccess) return fail(VRT_ENODEVICE, std::string("vrt_regular_create: ") + hipGetErrorString(e));
+        *out = r.release();
+        return VRT_OK;
+    });
 }
 
 extern "C" void vrt_regular_destroy(vrt_regular *r) { regular_free(r); }
-
-static int regular_grow(double *&buf, int64_t &cap, int64_t need, size_t per)
-{
-    if (buf && need <= cap) return VRT_OK;
-    if (buf) (void)hipFree(buf);
-    buf = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void **)&buf, sizeof(double) * per * (size_t)need);
-    if (e != hipSuccess) {
-        buf = nullptr;
-        return fail(e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-    }
-    cap = need;
-    return VRT_OK;
-}
 
 static int regular_check_k(int64_t n_solve, const double *k)
 {
@@ -875,16 +858,15 @@ static int regular_solve(vrt_regular *r, int64_t n_solve, const double *k, const
     const int64_t nfield = field_period > 0 ? field_period : n_solve;
     const int64_t nS = S_stride ? nfield : 1, nA = alpha_stride ? nfield : 1;
     int rc;
-    if ((rc = regular_grow(r->d_S, r->cap_S, nS, (size_t)vol))) return rc;
-    if ((rc = regular_grow(r->d_A, r->cap_A, nA, (size_t)vol))) return rc;
-    if ((rc = regular_grow(r->d_I, r->cap_I, n_solve, (size_t)vol))) return rc;
-    if ((rc = regular_grow(r->d_coef, r->cap_coef, n_solve, (size_t)(5 * nx * ny)))) return rc;
+    if ((rc = dev_grow(r->d_S, r->cap_S, (size_t)(nS * vol))) || (rc = dev_grow(r->d_A, r->cap_A, (size_t)(nA * vol))) ||
+        (rc = dev_grow(r->d_I, r->cap_I, (size_t)(n_solve * vol))) ||
+        (rc = dev_grow(r->d_coef, r->cap_coef, (size_t)(n_solve * 5 * nx * ny))))
+        return rc;
     if (n_solve > r->cap_k) {
-        if (r->d_k) (void)hipFree(r->d_k);
-        if (r->d_up) (void)hipFree(r->d_up);
-        r->d_k = nullptr; r->d_up = nullptr; r->cap_k = 0;
-        VRT_HIP_TRY(hipMalloc((void **)&r->d_k, sizeof(double) * 3 * (size_t)n_solve));
-        VRT_HIP_TRY(hipMalloc((void **)&r->d_up, sizeof(int) * (size_t)n_solve));
+        dev_free(r->d_k);
+        dev_free(r->d_up);
+        r->cap_k = 0;
+        if ((rc = dev_alloc(&r->d_k, 3 * (size_t)n_solve)) || (rc = dev_alloc(&r->d_up, (size_t)n_solve))) return rc;
         r->cap_k = n_solve;
     }
     VRT_HIP_TRY(hipMemcpyAsync(r->d_k, k, sizeof(double) * 3 * (size_t)n_solve, hipMemcpyHostToDevice, st));
@@ -935,7 +917,7 @@ static int regular_solve(vrt_regular *r, int64_t n_solve, const double *k, const
     if (all_xy && r->xy_split && 24 * vol < ((int64_t)1 << 31) && nz <= 65536) {   // (a solve's coefficients: 32-bit byte offsets; planes = grid.y)
         // coefficients: 3 doubles per point, plane and solve, in chunks of solves of at most 2 GiB
         const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({n_solve, 65535, ((int64_t)1 << 31) / (24 * vol)}));
-        if ((rc = regular_grow(r->d_xy, r->cap_xy, chunk, (size_t)(3 * vol)))) return rc;
+        if ((rc = dev_grow(r->d_xy, r->cap_xy, (size_t)(chunk * 3 * vol)))) return rc;
         // LDS of the march: two planes, the axes and the weight tables (layout: k_reg_xy_march_lds); the planes
         // padded to an even number of doubles so that the 16-byte tables behind them stay aligned
         const size_t planes_d = 2 * (size_t)(nx * ny), lead_d = planes_d + (size_t)(nx + ny);
@@ -975,7 +957,6 @@ extern "C" int vrt_regular_execute_dev(vrt_regular *r, int64_t n_solve, const do
                                        int64_t alpha_stride, int64_t field_period, const double *dI0,
                                        int n_sweeps, double *dI_out, void *stream)
 {
-    DeviceScope scope;
     if (field_period < 0 || field_period > n_solve) return fail(VRT_EINVAL, "field_period must be in [0, n_solve]");
     if (!r || !k || !up || !dS || !dalpha || !dI0 || !dI_out) return fail(VRT_EINVAL, "NULL argument");
     if (n_solve < 1 || n_sweeps < 1) return fail(VRT_EINVAL, "bad sizes");
@@ -984,15 +965,17 @@ extern "C" int vrt_regular_execute_dev(vrt_regular *r, int64_t n_solve, const do
         return fail(VRT_EINVAL, "S_stride / alpha_stride must be 0 (shared) or nz*nx*ny");
     int rc = regular_check_k(n_solve, k);
     if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = regular_solve(r, n_solve, k, up, dS, S_stride, dalpha, alpha_stride, field_period, dI0, n_sweeps, st)))
-        return rc;
-    const unsigned tb = (unsigned)((vol + 255) / 256);
-    for (int64_t s = 0; s < n_solve; s++)
-        hipLaunchKernelGGL(k_reg_from_planes, dim3(tb), dim3(256), 0, st, (int)nz, (int)nx, (int)ny, r->d_I + s * vol, dI_out + s * vol);
-    VRT_HIP_TRY(hipGetLastError());
-    r->timed = true;
-    return VRT_OK;
+    return guarded([&] {
+        hipStream_t st = (hipStream_t)stream;
+        rc = regular_solve(r, n_solve, k, up, dS, S_stride, dalpha, alpha_stride, field_period, dI0, n_sweeps, st);
+        if (rc) return rc;
+        const unsigned tb = (unsigned)((vol + 255) / 256);
+        for (int64_t s = 0; s < n_solve; s++)
+            hipLaunchKernelGGL(k_reg_from_planes, dim3(tb), dim3(256), 0, st, (int)nz, (int)nx, (int)ny, r->d_I + s * vol, dI_out + s * vol);
+        VRT_HIP_TRY(hipGetLastError());
+        r->timed = true;
+        return VRT_OK;
+    });
 }
 
 // Emergent intensity of nlam wavelengths seen along one direction k (write_top_intensity, src/plot_utils.jl:101-140):
@@ -1004,35 +987,36 @@ extern "C" int vrt_regular_execute_dev(vrt_regular *r, int64_t n_solve, const do
 extern "C" int vrt_regular_emergent_dev(vrt_regular *r, const double *k, int64_t nlam, const double *dS,
                                         const double *dalpha, int n_sweeps, double *dI_top, void *stream)
 {
-    DeviceScope scope;
     if (!r || !k || !dS || !dalpha || !dI_top) return fail(VRT_EINVAL, "NULL argument");
     if (nlam < 1 || n_sweeps < 1) return fail(VRT_EINVAL, "bad sizes");
     int rc = regular_check_k(1, k);
     if (rc) return rc;
-    const int64_t nz = r->nz, nx = r->nx, ny = r->ny, vol = nz * nx * ny, plane = nx * ny;
-    const int64_t per_solve = (int64_t)sizeof(double) * (6 * vol + 6 * plane);   // S, alpha, I, xy coefficients | coef, I_0
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nlam, r->emergent_bytes / per_solve));
-    std::vector<double> kk(3 * (size_t)chunk);
-    for (int64_t s = 0; s < chunk; s++)
-        for (int j = 0; j < 3; j++) kk[3 * (size_t)s + (size_t)j] = k[j];
-    const std::vector<int> up((size_t)chunk, 1);
-    VRT_HIP_TRY(hipSetDevice(r->device));
-    if ((rc = regular_grow(r->d_I0, r->cap_I0, chunk, (size_t)plane))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t inner = (nx - 2) * (ny - 2);
-    for (int64_t l0 = 0; l0 < nlam; l0 += chunk) {
-        const int64_t cnt = std::min(chunk, nlam - l0);
-        hipLaunchKernelGGL(k_reg_bottom_plane, dim3((unsigned)((plane * cnt + 255) / 256)), dim3(256), 0, st, (int)nz,
-                           (int)nx, (int)ny, cnt, dS + l0 * vol, r->d_I0);
-        if ((rc = regular_solve(r, cnt, kk.data(), up.data(), dS + l0 * vol, vol, dalpha + l0 * vol, vol, 0, r->d_I0,
-                                n_sweeps, st)))
-            return rc;
-        hipLaunchKernelGGL(k_reg_top_interior, dim3((unsigned)((inner * cnt + 255) / 256)), dim3(256), 0, st, (int)nz,
-                           (int)nx, (int)ny, cnt, r->d_I, dI_top + l0 * inner);
-        VRT_HIP_TRY(hipGetLastError());
-    }
-    r->timed = true;
-    return VRT_OK;
+    return guarded([&] {
+        const int64_t nz = r->nz, nx = r->nx, ny = r->ny, vol = nz * nx * ny, plane = nx * ny;
+        const int64_t per_solve = (int64_t)sizeof(double) * (6 * vol + 6 * plane);   // S, alpha, I, xy coefficients | coef, I_0
+        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nlam, r->emergent_bytes / per_solve));
+        std::vector<double> kk(3 * (size_t)chunk);
+        for (int64_t s = 0; s < chunk; s++)
+            for (int j = 0; j < 3; j++) kk[3 * (size_t)s + (size_t)j] = k[j];
+        const std::vector<int> up((size_t)chunk, 1);
+        VRT_HIP_TRY(hipSetDevice(r->device));
+        if ((rc = dev_grow(r->d_I0, r->cap_I0, (size_t)(chunk * plane)))) return rc;
+        hipStream_t st = (hipStream_t)stream;
+        const int64_t inner = (nx - 2) * (ny - 2);
+        for (int64_t l0 = 0; l0 < nlam; l0 += chunk) {
+            const int64_t cnt = std::min(chunk, nlam - l0);
+            hipLaunchKernelGGL(k_reg_bottom_plane, dim3((unsigned)((plane * cnt + 255) / 256)), dim3(256), 0, st, (int)nz,
+                               (int)nx, (int)ny, cnt, dS + l0 * vol, r->d_I0);
+            if ((rc = regular_solve(r, cnt, kk.data(), up.data(), dS + l0 * vol, vol, dalpha + l0 * vol, vol, 0, r->d_I0,
+                                    n_sweeps, st)))
+                return rc;
+            hipLaunchKernelGGL(k_reg_top_interior, dim3((unsigned)((inner * cnt + 255) / 256)), dim3(256), 0, st, (int)nz,
+                               (int)nx, (int)ny, cnt, r->d_I, dI_top + l0 * inner);
+            VRT_HIP_TRY(hipGetLastError());
+        }
+        r->timed = true;
+        return VRT_OK;
+    });
 }
 
 // Host-pointer form: S, alpha (nlam, ny, nx, nz) in numpy order on the ghosted axes, I_top (nlam, ny - 2, nx - 2).
@@ -1040,30 +1024,25 @@ extern "C" int vrt_top_intensity(int64_t nz, int64_t nx, int64_t ny, const doubl
                                  const double *k, int64_t nlam, const double *S, const double *alpha, int n_sweeps,
                                  int device, double *I_top)
 {
-    DeviceScope scope;
     if (!z || !x || !y || !k || !S || !alpha || !I_top) return fail(VRT_EINVAL, "NULL argument");
     if (nz < 2 || nx < 3 || ny < 3 || nlam < 1 || n_sweeps < 1) return fail(VRT_EINVAL, "bad sizes");
     int rc = regular_check_k(1, k);
     if (rc) return rc;
-    const int64_t vol = nz * nx * ny, inner = (nx - 2) * (ny - 2);
-    vrt_regular *r = nullptr;
-    if ((rc = vrt_regular_create(nz, nx, ny, z, x, y, device, &r))) return rc;
-    double *d_S = nullptr, *d_A = nullptr, *d_top = nullptr;
-    hipError_t e = hipMalloc((void **)&d_S, sizeof(double) * vol * nlam);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_A, sizeof(double) * vol * nlam);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_top, sizeof(double) * inner * nlam);
-    if (e == hipSuccess) e = hipMemcpy(d_S, S, sizeof(double) * vol * nlam, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_A, alpha, sizeof(double) * vol * nlam, hipMemcpyHostToDevice);
-    if (e != hipSuccess)
-        rc = fail(e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE, std::string("vrt_top_intensity: ") + hipGetErrorString(e));
-    if (!rc) rc = vrt_regular_emergent_dev(r, k, nlam, d_S, d_A, n_sweeps, d_top, nullptr);
-    if (!rc && ((e = hipDeviceSynchronize()) != hipSuccess ||
-                (e = hipMemcpy(I_top, d_top, sizeof(double) * inner * nlam, hipMemcpyDeviceToHost)) != hipSuccess))
-        rc = fail(VRT_ENODEVICE, std::string("vrt_top_intensity: ") + hipGetErrorString(e));
-    for (void *p : {(void *)d_S, (void *)d_A, (void *)d_top})
-        if (p) (void)hipFree(p);
-    regular_free(r);
-    return rc;
+    return guarded([&] {
+        const size_t vol = (size_t)(nz * nx * ny) * (size_t)nlam, top = (size_t)((nx - 2) * (ny - 2)) * (size_t)nlam;
+        vrt_regular *raw = nullptr;
+        if ((rc = vrt_regular_create(nz, nx, ny, z, x, y, device, &raw))) return rc;
+        RegularPtr r(raw, regular_free);
+        VRT_HIP_TRY(hipSetDevice(device));
+        DevBuf<double> d_S, d_A, d_top;
+        if ((rc = d_S.alloc(vol)) || (rc = d_A.alloc(vol)) || (rc = d_top.alloc(top))) return rc;
+        VRT_HIP_TRY(hipMemcpy(d_S, S, sizeof(double) * vol, hipMemcpyHostToDevice));
+        VRT_HIP_TRY(hipMemcpy(d_A, alpha, sizeof(double) * vol, hipMemcpyHostToDevice));
+        if ((rc = vrt_regular_emergent_dev(r.get(), k, nlam, d_S, d_A, n_sweeps, d_top, nullptr))) return rc;
+        VRT_HIP_TRY(hipDeviceSynchronize());
+        VRT_HIP_TRY(hipMemcpy(I_top, d_top, sizeof(double) * top, hipMemcpyDeviceToHost));
+        return VRT_OK;
+    });
 }
 
 // milliseconds of the last execute's solve kernel alone (HIP events on its stream); the stream
@@ -1071,10 +1050,12 @@ extern "C" int vrt_top_intensity(int64_t nz, int64_t nx, int64_t ny, const doubl
 extern "C" int vrt_regular_last_solve_ms(const vrt_regular *r, double *ms)
 {
     if (!r || !ms || !r->timed) return fail(VRT_EINVAL, "no timed execute yet");
-    float f = 0;
-    VRT_HIP_TRY(hipEventElapsedTime(&f, r->ev[1], r->ev[2]));
-    *ms = f;
-    return VRT_OK;
+    return guarded([&] {
+        float f = 0;
+        VRT_HIP_TRY(hipEventElapsedTime(&f, r->ev[1], r->ev[2]));
+        *ms = f;
+        return VRT_OK;
+    });
 }
 
 // Host-pointer form: stages the arrays through the device around vrt_regular_execute_dev.
@@ -1084,46 +1065,28 @@ extern "C" int vrt_short_characteristics(int64_t nz, int64_t nx, int64_t ny, con
                                          int64_t S_stride, const double *alpha, int64_t alpha_stride,
                                          const double *I0, int n_sweeps, int device, double *I_out)
 {
-    DeviceScope scope;
     if (!z || !x || !y || !k || !up || !S || !alpha || !I0 || !I_out) return fail(VRT_EINVAL, "NULL argument");
     if (nz < 2 || nx < 3 || ny < 3 || n_solve < 1 || n_sweeps < 1) return fail(VRT_EINVAL, "bad sizes");
     const int64_t vol = nz * nx * ny, plane = nx * ny;
     if ((S_stride != 0 && S_stride != vol) || (alpha_stride != 0 && alpha_stride != vol))
         return fail(VRT_EINVAL, "S_stride / alpha_stride must be 0 (shared) or nz*nx*ny");
-    vrt_regular *r = nullptr;
-    int rc = vrt_regular_create(nz, nx, ny, z, x, y, device, &r);
-    if (rc) return rc;
-    const int64_t nS = S_stride ? n_solve : 1, nA = alpha_stride ? n_solve : 1;
-    double *d_S = nullptr, *d_A = nullptr, *d_I0 = nullptr, *d_out = nullptr;
-    auto cleanup = [&]() {
-        for (void *p : {(void *)d_S, (void *)d_A, (void *)d_I0, (void *)d_out})
-            if (p) (void)hipFree(p);
-        regular_free(r);
-    };
-#define REG_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t _e = (expr);                                                            \
-        if (_e != hipSuccess) {                                                            \
-            cleanup();                                                                     \
-            return fail(_e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE,            \
-                        std::string(#expr) + ": " + hipGetErrorString(_e));                \
-        }                                                                                  \
-    } while (0)
-    REG_TRY(hipMalloc((void **)&d_S, sizeof(double) * vol * nS));
-    REG_TRY(hipMalloc((void **)&d_A, sizeof(double) * vol * nA));
-    REG_TRY(hipMalloc((void **)&d_I0, sizeof(double) * plane * n_solve));
-    REG_TRY(hipMalloc((void **)&d_out, sizeof(double) * vol * n_solve));
-    REG_TRY(hipMemcpy(d_S, S, sizeof(double) * vol * nS, hipMemcpyHostToDevice));
-    REG_TRY(hipMemcpy(d_A, alpha, sizeof(double) * vol * nA, hipMemcpyHostToDevice));
-    REG_TRY(hipMemcpy(d_I0, I0, sizeof(double) * plane * n_solve, hipMemcpyHostToDevice));
-    rc = vrt_regular_execute_dev(r, n_solve, k, up, d_S, S_stride, d_A, alpha_stride, 0, d_I0, n_sweeps, d_out, nullptr);
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-    REG_TRY(hipDeviceSynchronize());
-    REG_TRY(hipMemcpy(I_out, d_out, sizeof(double) * vol * n_solve, hipMemcpyDeviceToHost));
-#undef REG_TRY
-    cleanup();
-    return VRT_OK;
+    return guarded([&] {
+        vrt_regular *raw = nullptr;
+        int rc = vrt_regular_create(nz, nx, ny, z, x, y, device, &raw);
+        if (rc) return rc;
+        RegularPtr r(raw, regular_free);
+        VRT_HIP_TRY(hipSetDevice(device));
+        const size_t nS = (size_t)(vol * (S_stride ? n_solve : 1)), nA = (size_t)(vol * (alpha_stride ? n_solve : 1));
+        const size_t nI0 = (size_t)(plane * n_solve), nout = (size_t)(vol * n_solve);
+        DevBuf<double> d_S, d_A, d_I0, d_out;
+        if ((rc = d_S.alloc(nS)) || (rc = d_A.alloc(nA)) || (rc = d_I0.alloc(nI0)) || (rc = d_out.alloc(nout))) return rc;
+        VRT_HIP_TRY(hipMemcpy(d_S, S, sizeof(double) * nS, hipMemcpyHostToDevice));
+        VRT_HIP_TRY(hipMemcpy(d_A, alpha, sizeof(double) * nA, hipMemcpyHostToDevice));
+        VRT_HIP_TRY(hipMemcpy(d_I0, I0, sizeof(double) * nI0, hipMemcpyHostToDevice));
+        rc = vrt_regular_execute_dev(r.get(), n_solve, k, up, d_S, S_stride, d_A, alpha_stride, 0, d_I0, n_sweeps, d_out, nullptr);
+        if (rc) return rc;
+        VRT_HIP_TRY(hipDeviceSynchronize());
+        VRT_HIP_TRY(hipMemcpy(I_out, d_out, sizeof(double) * nout, hipMemcpyDeviceToHost));
+        return VRT_OK;
+    });
 }

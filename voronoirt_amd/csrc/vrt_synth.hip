@@ -119,22 +119,20 @@ static int tau_checks(int64_t nz, int64_t nx, int64_t ny, const double *z, const
 static int tau_launch(int64_t nz, int64_t nx, int64_t ny, const double *z, const double *k, int64_t nlam, double dx,
                       double dy, const double *d_alpha, double *d_height, hipStream_t st)
 {
-    double *d_z = nullptr;
-    hipError_t e = hipMalloc((void **)&d_z, sizeof(double) * (size_t)nz);
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
+    DevBuf<double> d_z;
+    int rc = d_z.alloc((size_t)nz);
+    if (rc) return rc;
     TauArgs ta;
     ta.nz = nz; ta.nx = nx; ta.ny = ny; ta.nlam = nlam;
     ta.kz = k[0]; ta.kx = k[1]; ta.ky = k[2]; ta.dx = dx; ta.dy = dy;
     ta.z = d_z; ta.alpha = d_alpha; ta.height = d_height;
     const int64_t n = nx * ny * nlam;
-    e = hipMemcpyAsync(d_z, z, sizeof(double) * (size_t)nz, hipMemcpyHostToDevice, st);
+    hipError_t e = hipMemcpyAsync(d_z, z, sizeof(double) * (size_t)nz, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_tau_unity, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ta);
         e = hipGetLastError();
     }
-    const hipError_t e2 = hipStreamSynchronize(st);       // (d_z is freed below)
-    (void)hipFree(d_z);
+    const hipError_t e2 = hipStreamSynchronize(st);       // (d_z is freed on return)
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) return fail(VRT_ENODEVICE, std::string("vrt_tau_unity: ") + hipGetErrorString(e));
     return VRT_OK;
@@ -144,35 +142,30 @@ static int tau_launch(int64_t nz, int64_t nx, int64_t ny, const double *z, const
 extern "C" int vrt_tau_unity_dev(int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x, const double *y,
                                  const double *k, int64_t nlam, const double *d_alpha, double *d_height, void *stream)
 {
-    DeviceScope scope;
-    double dx = 0, dy = 0;
-    int rc = tau_checks(nz, nx, ny, z, x, y, k, nlam, d_alpha, d_height, &dx, &dy);
-    if (rc) return rc;
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0)
-        return fail(VRT_ENODEVICE, "no HIP device available (libvrt_hip has no CPU fallback)");
-    (void)hipGetLastError();
-    return tau_launch(nz, nx, ny, z, k, nlam, dx, dy, d_alpha, d_height, (hipStream_t)stream);
+    return guarded([&] {
+        double dx = 0, dy = 0;
+        int rc = tau_checks(nz, nx, ny, z, x, y, k, nlam, d_alpha, d_height, &dx, &dy);
+        if (!rc) rc = use_current_device();
+        return rc ? rc : tau_launch(nz, nx, ny, z, k, nlam, dx, dy, d_alpha, d_height, (hipStream_t)stream);
+    });
 }
 
 extern "C" int vrt_tau_unity(int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x, const double *y,
                              const double *k, int64_t nlam, const double *alpha, int device, double *height)
 {
-    DeviceScope scope;
-    double dx = 0, dy = 0;
-    int rc = tau_checks(nz, nx, ny, z, x, y, k, nlam, alpha, height, &dx, &dy);
-    if (rc) return rc;
-    if ((rc = use_device(device))) return rc;
-    const size_t na = (size_t)(nz * (nx + 2) * (ny + 2)) * (size_t)nlam, nh = (size_t)(nx * ny) * (size_t)nlam;
-    double *d = nullptr;
-    hipError_t e = hipMalloc((void **)&d, sizeof(double) * (na + nh));
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-    if ((e = hipMemcpy(d, alpha, sizeof(double) * na, hipMemcpyHostToDevice)) != hipSuccess)
-        rc = fail(VRT_ENODEVICE, std::string("vrt_tau_unity: ") + hipGetErrorString(e));
-    if (!rc) rc = tau_launch(nz, nx, ny, z, k, nlam, dx, dy, d, d + na, nullptr);
-    if (!rc && (e = hipMemcpy(height, d + na, sizeof(double) * nh, hipMemcpyDeviceToHost)) != hipSuccess)
-        rc = fail(VRT_ENODEVICE, std::string("vrt_tau_unity: ") + hipGetErrorString(e));
-    (void)hipFree(d);
-    return rc;
+    return guarded([&] {
+        double dx = 0, dy = 0;
+        int rc = tau_checks(nz, nx, ny, z, x, y, k, nlam, alpha, height, &dx, &dy);
+        if (rc || (rc = use_device(device))) return rc;
+        const size_t na = (size_t)(nz * (nx + 2) * (ny + 2)) * (size_t)nlam, nh = (size_t)(nx * ny) * (size_t)nlam;
+        DevBuf<double> d;
+        if ((rc = d.alloc(na + nh))) return rc;
+        hipError_t e;
+        if ((e = hipMemcpy(d, alpha, sizeof(double) * na, hipMemcpyHostToDevice)) != hipSuccess)
+            return fail(VRT_ENODEVICE, std::string("vrt_tau_unity: ") + hipGetErrorString(e));
+        if ((rc = tau_launch(nz, nx, ny, z, k, nlam, dx, dy, d, d + na, nullptr))) return rc;
+        if ((e = hipMemcpy(height, d + na, sizeof(double) * nh, hipMemcpyDeviceToHost)) != hipSuccess)
+            return fail(VRT_ENODEVICE, std::string("vrt_tau_unity: ") + hipGetErrorString(e));
+        return VRT_OK;
+    });
 }
