@@ -610,6 +610,41 @@ int vrt_regular_execute_dev(vrt_regular *r, int64_t n_solve, const double *k, co
                             int n_sweeps, double *dI_out, void *stream);
 int vrt_regular_last_solve_ms(const vrt_regular *r, double *ms);
 
+/* ---- the line Λ-iteration on the regular grid (J_λ_regular, Λ_regular: src/lambda_iteration.jl:1-58, :116-205) ----
+ * The regular half of the reference's comparison, the twin of vrt_plan_execute_line / vrt_lambda_* on a vrt_regular r.
+ * Points are all nz nx ny points of r, the periodic ghost border included, in Julia order i = iz + nz (ix + nx iy); the
+ * arrays are laid out as vrt_line_case's with n = nz nx ny: S, J, B_0 (nlam, n), populations (n, 3), R (3, 3, n).
+ * Directions: k (3, n_angles) unit vectors (z, x, y), dirs[a] = 1 for an up solve (θ > 90), -1 for a down solve
+ * (θ < 90), 0 for an angle that adds nothing (θ = 90; its k is not checked), weights[n_angles].
+ *
+ * vrt_regular_execute_line: J = Σ_a w_a I_a of every (angle, wavelength) solve from host arrays: per angle α_tot =
+ *   line_strength H(a, v) / (√π ΔλD) + alpha_cont with v_los = dot(velocity, -k), as vrt_line_opacity_dev, made on
+ *   the device; the up solves start from I0_up (nx, ny, nlam), element [ix + nx (iy + ny l)]: one bottom plane per
+ *   wavelength, the layout of vrt_short_characteristics' I0 (NULL: zeros); the down solves start from zeros.
+ * vrt_regular_lambda_create / _iterate / _get / _destroy: Λ_regular's loop with the contract of vrt_lambda_*: create
+ *   uploads the line case and starts in LTE with S = B_0; one iterate is γ and the line strength of the current
+ *   populations -> α_tot of every angle -> J (I_0 of the up solves: B_0's bottom plane) -> S_new = (1 - ε) J + ε B_0
+ *   and max |1 - S_old/S_new| (NaN propagates) -> R -> populations; get returns what is asked for (any pointer may be
+ *   NULL; before the first iterate J, R and gamma are zeros).  The session borrows r, which must outlive it; r serves
+ *   one caller at a time.
+ * The solves go through in chunks whose workspace (α_tot, I, coefficients) stays under a byte cap (64 GiB;
+ * VRT_REG_LAMBDA_BYTES, read at vrt_regular_create); J is bit-identical for any chunking.  The workspace lives on r
+ * until vrt_regular_execute_line returns or the session is destroyed.
+ * vrt_regular_last_solve_ms times vrt_regular_execute_dev and vrt_regular_emergent_dev only: after these entries it
+ * answers VRT_EINVAL until the next of those.  Every argument is checked before the device is touched (NULL,
+ * n_angles < 1, dirs outside {-1, 0, 1}, |k| != 1 or k_z = 0 where dirs != 0, nlam < 1 (the session: < 2, and its
+ * wavelength blocks), n_sweeps < 1: VRT_EINVAL). */
+typedef struct vrt_regular_lambda vrt_regular_lambda;
+int vrt_regular_execute_line(vrt_regular *r, int64_t n_angles, const double *k, const int *dirs, const double *weights,
+                             int64_t nlam, const double *lambda, double lambda0, double c0, const double *velocity,
+                             const double *doppler_width, const double *gamma, const double *line_strength,
+                             const double *alpha_cont, const double *S, const double *I0_up, int n_sweeps, double *J);
+int vrt_regular_lambda_create(vrt_regular *r, int64_t n_angles, const double *k, const int *dirs, const double *weights,
+                              const vrt_line_case *lc, int n_sweeps, vrt_regular_lambda **out);
+int vrt_regular_lambda_iterate(vrt_regular_lambda *s, double *max_rel_change);
+int vrt_regular_lambda_get(vrt_regular_lambda *s, double *J, double *S, double *populations, double *R, double *gamma);
+void vrt_regular_lambda_destroy(vrt_regular_lambda *s);
+
 /* ---- emergent spectra: opacity / source function, top-plane intensity, tau = 1 heights ------------------------------
  * The last step of a reference study (write_top_intensity, write_tau_unity and plotter, src/plot_utils.jl:61-140,
  * :297-355, :434-576) on a regular raster.  Plain numbers in one unit system, constants folded in by the caller.

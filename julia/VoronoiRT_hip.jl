@@ -13,7 +13,9 @@
 #     all-reduce of the rate-integral shares per iteration), and
 #   * `Delaunay_upII` / `Delaunay_downII` (src/irregular_ray_tracing.jl:15-82, :96-163) for the
 #     direct call sites in compare_searchlight.jl (:113,129,434),
-#   * `short_characteristics_up/down` (src/characteristics.jl:19-95, :110-180).
+#   * `short_characteristics_up/down` (src/characteristics.jl:19-95, :110-180),
+#   * and adds `Λ_regular` (src/lambda_iteration.jl:116-205) over vrt_regular_lambda_*: the regular half of the
+#     comparison with the same device-resident loop.
 # The physics that produces S, α and I_0 (γ, damping, Voigt profile, αline_λ, B_λ) stays in Julia
 # exactly as the reference writes it; only the formal solves leave the process.
 #
@@ -335,6 +337,105 @@ function Λ(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, line::Hydr
                                       (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
                                       ses[], J, S, pops, C_NULL, C_NULL))
     ccall(dlsym(libvrt_handle(), f_destroy), Cvoid, (Ptr{Cvoid},), ses[])
+    println(i == maxiter ? "Did not converge inside scope" : "Converged in $i iterations")
+    return J * I_unit, S * I_unit, α_cont, pops * 1u"m^-3"
+end
+
+# ---- Λ_regular: src/lambda_iteration.jl:116-205 ---------------------------------------------------
+"""
+    Λ_regular(ϵ, maxiter, atmos, line, quadrature, DATA) -> (J_new, S_new, α_cont, populations)
+
+The reference's Λ_regular with its loop body on the device (vrt_regular_lambda_*).  `atmos` is the periodic
+atmosphere the reference iterates on (get_atmos(...; periodic=true)): every point, ghost border included, is a
+point of the loop.  What Λ_regular derives before the loop (LTE populations, α_cont, ε, B_0, C: :124-157) comes from
+the reference's own functions, as in `Λ` above; each iteration is vrt_regular_lambda_iterate, after which
+populations and S_new are fetched and checkpointed without the ghost border like the reference (:188-189).
+Arrays keep their Julia shapes: (nλ, nz, nx, ny), (nz, nx, ny, 3) and (3, 3, nz, nx, ny) are vrt_line_case's
+(nλ, n), (n, 3) and (3, 3, n) with n = nz nx ny.  Unrun: Julia is not installed where the library is built.
+"""
+function Λ_regular(ϵ::AbstractFloat, maxiter::Integer, atmos, line::HydrogenicLine, quadrature::String, DATA::String)
+    LTE_pops = VoronoiRT.LTE_populations(line, atmos)
+    α_cont = VoronoiRT.α_absorption.(line.λ0, atmos.temperature, atmos.electron_density * 1.0,
+                                     LTE_pops[:, :, :, 1] .+ LTE_pops[:, :, :, 2], LTE_pops[:, :, :, 3]) .+
+             VoronoiRT.α_scattering.(line.λ0, atmos.electron_density, LTE_pops[:, :, :, 1])
+    ελ = VoronoiRT.destruction(LTE_pops, atmos.electron_density, atmos.temperature, line)
+    println("Minimum $(minimum(ελ)) destruction probability")
+    nz, nx, ny = size(atmos.temperature)
+    nλ = length(line.λ)
+    B_0 = Array{Float64,4}(undef, nλ, nz, nx, ny)
+    for l in eachindex(line.λ)
+        B_0[l, :, :, :] = ustrip.(I_unit, VoronoiRT.B_λ.(line.λ[l], atmos.temperature))
+    end
+    C = VoronoiRT.calculate_C(atmos, LTE_pops)
+
+    one_density = fill(1.0u"m^-3", nz, nx, ny)                   # γ_constant split as in Λ above
+    γ_unsold_unit = VoronoiRT.γ_unsold.(VoronoiRT.const_unsold(line), atmos.temperature, one_density)
+    γ_static = VoronoiRT.γ_constant(line, atmos.temperature, 0.0 .* one_density, atmos.electron_density)
+    λ = Vector{Float64}(ustrip.(u"m", line.λ))
+    blocks = (Int64(line.λidx[1]), Int64(line.λidx[2]), Int64(line.λidx[2]), Int64(line.λidx[3]),
+              Int64(line.λidx[3]), Int64(line.λidx[4]))
+    hc = VoronoiRT.h * VoronoiRT.c_0
+    pref_ij = ustrip(u"s^-1", 2π / hc * 1u"m" * 1u"m^2" * 1I_unit * 1u"m") / 1000
+    pref_ji = ustrip(u"s^-1", 2π / hc * 1u"m" * 1u"m^2" * 1I_unit * 1u"m")
+    planck2 = Vector{Float64}(ustrip.(I_unit, 2 * VoronoiRT.h * VoronoiRT.c_0^2 ./ line.λ .^ 5))
+    σ1 = Vector{Float64}(ustrip.(u"m^2", VoronoiRT.σic(1, line, line.λ[line.λidx[2]+1:line.λidx[3]])))
+    σ2 = Vector{Float64}(ustrip.(u"m^2", VoronoiRT.σic(2, line, line.λ[line.λidx[3]+1:line.λidx[4]])))
+    vel = Array{Float64,4}(undef, 3, nz, nx, ny)                 # (3, n) rows z, x, y
+    vel[1, :, :, :] = ustrip.(u"m/s", atmos.velocity_z); vel[2, :, :, :] = ustrip.(u"m/s", atmos.velocity_x)
+    vel[3, :, :, :] = ustrip.(u"m/s", atmos.velocity_y)
+    ΔD = Array{Float64,3}(ustrip.(u"m", line.ΔD))
+    γs = Array{Float64,3}(ustrip.(u"s^-1", γ_static)); γu = Array{Float64,3}(ustrip.(u"s^-1", γ_unsold_unit))
+    αc = Array{Float64,3}(ustrip.(u"m^-1", α_cont)); εv = Array{Float64,3}(ελ)
+    T = Array{Float64,3}(ustrip.(u"K", atmos.temperature))
+    atom = Array{Float64,3}(ustrip.(u"m^-3", atmos.hydrogen_populations))
+    lte = Array{Float64,4}(ustrip.(u"m^-3", LTE_pops)); Cm = Array{Float64,5}(ustrip.(u"s^-1", C))
+    a_i = line_strength(line, [0.0u"m^-3"], [1.0u"m^-3"])[1]
+    a_j = -line_strength(line, [1.0u"m^-3"], [0.0u"m^-3"])[1]
+
+    weights, θ_array, ϕ_array, n_angles = read_quadrature(quadrature)
+    k = Matrix{Float64}(undef, 3, n_angles)
+    for i in 1:n_angles
+        k[:, i] = direction(θ_array[i], ϕ_array[i])              # :23-26
+    end
+    dirs = Cint[θ > 90 ? 1 : (θ < 90 ? -1 : 0) for θ in θ_array]  # θ = 90 adds nothing (:37-55)
+    w = Vector{Float64}(weights)
+    z = Vector{Float64}(ustrip.(u"m", atmos.z)); x = Vector{Float64}(ustrip.(u"m", atmos.x))
+    y = Vector{Float64}(ustrip.(u"m", atmos.y))
+    reg = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve z x y check(ccall((:vrt_regular_create, libvrt), Cint,
+                                   (Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ref{Ptr{Cvoid}}),
+                                   nz, nx, ny, z, x, y, 0, reg))
+    ses = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve λ vel ΔD γs γu αc εv T atom B_0 lte Cm planck2 σ1 σ2 k dirs w begin
+        lc = Ref(LineCase(nλ, pointer(λ), blocks, ustrip(u"m", line.λ0), ustrip(u"m/s", VoronoiRT.c_0), pointer(vel),
+                          pointer(ΔD), pointer(γs), pointer(γu), pointer(αc), pointer(εv), pointer(T), pointer(atom),
+                          pointer(B_0), pointer(lte), pointer(Cm), pointer(planck2), pointer(σ1), pointer(σ2),
+                          1.0, a_i, a_j, ustrip(u"m^3", hc / (4 * π * line.λ0) * line.Bij),
+                          ustrip(u"m*K", hc / VoronoiRT.k_B), pref_ij, pref_ji))
+        check(ccall((:vrt_regular_lambda_create, libvrt), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Cint}, Ptr{Float64}, Ref{LineCase}, Cint, Ref{Ptr{Cvoid}}),
+                    reg[], n_angles, k, dirs, w, lc, 3, ses))
+    end
+    J = Array{Float64,4}(undef, nλ, nz, nx, ny); S = Array{Float64,4}(undef, nλ, nz, nx, ny)
+    pops = Array{Float64,4}(undef, nz, nx, ny, 3)
+    fetch_state(Jp, Sp) = GC.@preserve J S pops check(ccall((:vrt_regular_lambda_get, libvrt), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ses[], Jp, Sp, pops, C_NULL, C_NULL))
+    i = 0
+    diff = Ref{Float64}(1.0)                  # criterion(S_new = B_0, S_old = 0) = 1
+    VoronoiRT.write_to_file(diff[], i + 1, DATA)
+    while diff[] > ϵ && i < maxiter
+        @time check(ccall((:vrt_regular_lambda_iterate, libvrt), Cint, (Ptr{Cvoid}, Ref{Float64}), ses[], diff))
+        isnan(diff[]) && println("NaN DIFF!")
+        println("   Rel. diff.: $(diff[])")
+        fetch_state(C_NULL, pointer(S))
+        VoronoiRT.write_to_file(pops[:, 2:end-1, 2:end-1, :] * 1u"m^-3", DATA)     # the checkpoint, :188-189
+        VoronoiRT.write_to_file(S[:, :, 2:end-1, 2:end-1] * I_unit, DATA)
+        i += 1
+        VoronoiRT.write_to_file(diff[], i + 1, DATA)
+    end
+    fetch_state(pointer(J), pointer(S))
+    ccall((:vrt_regular_lambda_destroy, libvrt), Cvoid, (Ptr{Cvoid},), ses[])
+    ccall((:vrt_regular_destroy, libvrt), Cvoid, (Ptr{Cvoid},), reg[])
     println(i == maxiter ? "Did not converge inside scope" : "Converged in $i iterations")
     return J * I_unit, S * I_unit, α_cont, pops * 1u"m^-3"
 end

@@ -9,6 +9,7 @@ from .api import (Delaunay_downII, Delaunay_upII, FormalPlan, J_lambda_voronoi, 
                   direction, quadrature_directions, read_cell, read_quadrature, voro, QUADRATURE_DIR,
                   short_characteristics_batch, short_characteristics_down, short_characteristics_up,
                   RegularSolver, LineCase, Lambda_voronoi, Lambda_voronoi_host, J_lambda_voronoi_line, MultiDevicePlan,
+                  Lambda_regular, J_lambda_regular_line,
                   nearest_sites, Voronoi_to_Raster, Voronoi_to_Raster_inv_dist, initialise, Voronoi_to_Raster_dev,
                   initialise_dev, raster_stats, rejection_sampling, rejection_sampling_dev, sample_from_invNH_invT,
                   sample_from_logNH_invT, sample_from_logNH_invT_rootv, sample_from_temp_gradient, periodic_axis,
@@ -20,7 +21,7 @@ __all__ = ["Delaunay_upII", "Delaunay_downII", "FormalPlan", "J_lambda_voronoi",
            "direction", "quadrature_directions", "read_cell", "read_quadrature", "voro", "VrtError",
            "QUADRATURE_DIR", "short_characteristics_up", "short_characteristics_down",
            "short_characteristics_batch", "RegularSolver", "LineCase", "Lambda_voronoi", "Lambda_voronoi_host",
-           "J_lambda_voronoi_line", "MultiDevicePlan", "nearest_sites", "Voronoi_to_Raster",
+           "J_lambda_voronoi_line", "MultiDevicePlan", "Lambda_regular", "J_lambda_regular_line", "nearest_sites", "Voronoi_to_Raster",
            "Voronoi_to_Raster_inv_dist", "initialise", "Voronoi_to_Raster_dev", "initialise_dev", "raster_stats",
            "rejection_sampling", "rejection_sampling_dev", "sample_from_invNH_invT", "sample_from_logNH_invT",
            "sample_from_logNH_invT_rootv", "sample_from_temp_gradient", "periodic_axis", "synth_opacity",

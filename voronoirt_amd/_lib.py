@@ -143,6 +143,13 @@ PROTOTYPES = {
     "vrt_regular_execute_dev": (ctypes.c_int, [vp, c_i64, p_dbl, p_int, vp, c_i64, vp, c_i64, c_i64, vp,
                                                ctypes.c_int, vp, vp]),
     "vrt_regular_last_solve_ms": (ctypes.c_int, [vp, p_dbl]),
+    "vrt_regular_execute_line": (ctypes.c_int, [vp, c_i64, p_dbl, p_int, p_dbl, c_i64, p_dbl, c_dbl, c_dbl, p_dbl, p_dbl,
+                                                p_dbl, p_dbl, p_dbl, p_dbl, p_dbl, ctypes.c_int, p_dbl]),
+    "vrt_regular_lambda_create": (ctypes.c_int, [vp, c_i64, p_dbl, p_int, p_dbl, ctypes.POINTER(LineCaseStruct), ctypes.c_int,
+                                                 ctypes.POINTER(vp)]),
+    "vrt_regular_lambda_iterate": (ctypes.c_int, [vp, p_dbl]),
+    "vrt_regular_lambda_get": (ctypes.c_int, [vp, p_dbl, p_dbl, p_dbl, p_dbl, p_dbl]),
+    "vrt_regular_lambda_destroy": (None, [vp]),
     "vrt_synth_opacity_dev": (ctypes.c_int, [c_i64, c_i64, c_i64, p_dbl, c_i64, p_dbl, p_dbl, c_dbl, c_dbl, c_dbl, c_dbl,
                                              c_dbl, c_dbl, c_dbl, c_dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "vrt_synth_opacity": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64, p_dbl, c_i64, p_dbl, p_dbl, c_dbl, c_dbl,

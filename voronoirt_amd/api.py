@@ -1378,3 +1378,82 @@ def Lambda_voronoi(eps_conv: float, maxiter: int, sites: VoronoiSites, case: Lin
         return J.cpu().numpy(), S_new.cpu().numpy(), pops.cpu().numpy(), history
     finally:
         plan.close()
+
+
+# ---- the line Λ-iteration on the regular grid (src/lambda_iteration.jl:1-58 J_λ_regular, :116-205 Λ_regular) ----------
+def _regular_directions(quadrature: str):
+    """weights, k (n_angles, 3) and dirs (1 up for θ > 90, -1 down for θ < 90, 0 for θ = 90, which adds nothing)"""
+    w, th, ph, _ = read_quadrature(quadrature)
+    dirs = np.ascontiguousarray([1 if t > 90 else (-1 if t < 90 else 0) for t in th], dtype=np.int32)
+    return _f64(w), _f64(quadrature_directions(th, ph)), dirs
+
+
+def _regular_solver(z, x, y, n: int, device: int) -> RegularSolver:
+    solver = RegularSolver(z, x, y, device=device)
+    if solver.nz * solver.nx * solver.ny != n:
+        solver.close()
+        raise ValueError(f"the line case has {n} points, the raster nz nx ny = {solver.nz * solver.nx * solver.ny}")
+    return solver
+
+
+def J_lambda_regular_line(S, populations, z, x, y, case: LineCase, quadrature: str, n_sweeps: int = 3,
+                          device: int = 0) -> np.ndarray:
+    """J_λ_regular, line method (src/lambda_iteration.jl:1-58), from HOST arrays through ONE call
+    (`vrt_regular_execute_line`).  z, x, y are the raster's axes with the periodic ghost border, and every one of its
+    n = nz nx ny points is a point of `case` (LineCase, Julia point order i = iz + nz (ix + nx iy), i.e. numpy
+    (ny, nx, nz) C-order flattened).  S (n, nλ); γ and the line strength from `populations` (3, n); α_tot of every
+    angle made on the device; I_0 = B_0's bottom plane for the up rays (:38), zeros for the down rays."""
+    S = _f64(S)
+    n, nlam = S.shape
+    w, k, dirs = _regular_directions(quadrature)
+    pops = np.asarray(populations)
+    gamma = _f64(case.gamma(pops))
+    strength = _f64(case.strength_const * (pops[0] * case.Bij - pops[1] * case.Bji))
+    lam, vel, dop, ac = _f64(case.lam), _f64(case.velocity), _f64(case.doppler), _f64(case.alpha_cont)
+    solver = _regular_solver(z, x, y, n, device)
+    try:
+        # B_0's bottom plane as I_0 (nx, ny, nλ) Julia order = numpy (nλ, ny, nx)
+        I0 = _f64(np.asarray(case.B0).reshape(solver.ny, solver.nx, solver.nz, nlam)[:, :, 0, :].transpose(2, 0, 1))
+        J = np.zeros((n, nlam))
+        check(_lib.load().vrt_regular_execute_line(solver._h, k.shape[0], _d(k), dirs.ctypes.data_as(_lib.p_int), _d(w), nlam,
+                                                   _d(lam), float(case.lambda0), float(case.c0), _d(vel), _d(dop), _d(gamma),
+                                                   _d(strength), _d(ac), _d(S), _d(I0), int(n_sweeps), _d(J)))
+        return J
+    finally:
+        solver.close()
+
+
+def Lambda_regular(eps_conv: float, maxiter: int, z, x, y, case: LineCase, quadrature: str, n_sweeps: int = 3,
+                   device: int = 0):
+    """Λ_regular (src/lambda_iteration.jl:116-205) with library-owned device state (`vrt_regular_lambda_create` /
+    `_iterate` / `_get`): one call per iteration, only the criterion's scalar comes back inside the loop.  The raster
+    and `case` as for `J_lambda_regular_line`; every point, ghost border included, is a point of the loop.  Starts
+    in LTE with S = B_0; stops like `Lambda_voronoi_host` (criterion, NaN).  Returns (J, S_new, populations (3, n),
+    history)."""
+    L = _lib.load()
+    w, k, dirs = _regular_directions(quadrature)
+    lc, keep = case.c_struct()
+    nlam = int(keep["lam"].size)
+    n = int(keep["doppler"].size)
+    solver = _regular_solver(z, x, y, n, device)
+    h = ctypes.c_void_p()
+    try:
+        check(L.vrt_regular_lambda_create(solver._h, k.shape[0], _d(k), dirs.ctypes.data_as(_lib.p_int), _d(w),
+                                          ctypes.byref(lc), int(n_sweeps), ctypes.byref(h)))
+        history, diff, i = [], 1.0, 0                          # criterion(S_new = B, S_old = 0) = 1
+        while diff > eps_conv and i < maxiter:
+            d = ctypes.c_double()
+            check(L.vrt_regular_lambda_iterate(h, ctypes.byref(d)))
+            diff = d.value
+            history.append(diff)
+            i += 1
+            if diff != diff:
+                import warnings
+                warnings.warn(f"Lambda_regular: NaN DIFF! at iteration {i} -- stopping, results are not converged")
+        J, S, pops = np.zeros((n, nlam)), np.zeros((n, nlam)), np.zeros((3, n))
+        check(L.vrt_regular_lambda_get(h, _d(J), _d(S), _d(pops), None, None))
+        return J, S, pops, history
+    finally:
+        if h:
+            L.vrt_regular_lambda_destroy(h)
+        solver.close()

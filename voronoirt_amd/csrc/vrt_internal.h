@@ -529,6 +529,12 @@ int launch_rates_populations(vrt_grid *g, int64_t nlam, int64_t ld, const int64_
                              double pref_ij, double pref_ji, const double *d_C, const double *d_atom_density,
                              double *d_R, double *d_populations, hipStream_t st,
                              const double *dJ_up = nullptr, const double *dJ_down = nullptr);   // sweep-order J instead of dJ
+// the same for n points in their own order, without a grid (the regular-grid Λ-iteration)
+int launch_rates_populations(int64_t n, int64_t nlam, int64_t ld, const int64_t blocks[6], const double *d_small,
+                             const double *dJ, double lambda0, double c0, const double *d_doppler, const double *d_gamma,
+                             double sigma_bb_const, const double *d_temperature, const double *d_lte, double hc_over_kB,
+                             double pref_ij, double pref_ji, const double *d_C, const double *d_atom_density, double *d_R,
+                             double *d_populations, hipStream_t st);
 
 int launch_rates_partial(vrt_grid *g, int64_t nlam, int64_t l0, int64_t l1, int64_t ld, const int64_t blocks[6],
                          const double *d_small, const double *dJ, double lambda0, double c0, const double *d_doppler,

@@ -1,0 +1,47 @@
+// Internal: the regular-grid solver handle and the entry of its solve kernels (vrt_regular.hip), shared with the
+// line Λ-iteration on the raster (vrt_regular_lambda.hip).
+#pragma once
+
+#include <vector>
+
+#include "vrt_internal.h"
+
+// ---- device-resident form: a handle owns the grid axes and the (grow-only) workspaces -----------
+struct vrt_regular {
+    int device = 0;
+    int64_t nz = 0, nx = 0, ny = 0;
+    double *d_g = nullptr;                 // z | x | y
+    std::vector<double> h_g;               // the same on the host (launch geometry)
+    double *d_S = nullptr, *d_A = nullptr, *d_I = nullptr, *d_k = nullptr, *d_coef = nullptr, *d_xy = nullptr;
+    int *d_up = nullptr;
+    size_t cap_S = 0, cap_A = 0, cap_I = 0, cap_coef = 0, cap_xy = 0;     // in doubles
+    int64_t cap_k = 0;                     // in solves
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    bool timed = false;
+    int force_threads = 0;                 // VRT_REG_THREADS, read once at creation (tests: forces the launch shape)
+    int xy_split = 1;                      // VRT_REG_XY (creation): 0 = all-xy batches through k_regular_solve too;
+                                           //   2 = split, upwind plane read from memory instead of LDS (tests)
+    double *d_I0 = nullptr;                // vrt_regular_emergent_dev: the bottom planes of S of one chunk
+    size_t cap_I0 = 0;
+    int64_t emergent_bytes = (int64_t)8 << 30;  // VRT_REG_EMERGENT_BYTES (creation): workspace cap of an emergent chunk
+    int64_t lambda_bytes = (int64_t)64 << 30;   // VRT_REG_LAMBDA_BYTES (creation): workspace cap of a line-J chunk
+                                                //   (smaller chunks run fewer solves at once: DESIGN §7f)
+};
+
+namespace vrt {
+
+// |k| = 1 and k_z != 0 for every one of n_solve directions (host)
+int regular_check_k(int64_t n_solve, const double *k);
+
+// frees the solve workspaces (alpha, I, coefficients) a line pass grew; the next call that needs them allocates again
+void regular_release_workspace(vrt_regular *r);
+
+// n_solve solves whose inputs are already plane-major on the device (no transposes) into r->d_I ([solve][iz][iy][ix]):
+// solve s is direction dk[s] (hk: the same directions on the host, which choose the launch), dup[s] (1 up, 0 down),
+// wavelength l = (s + lam_offset) % lam_period of dS ([l][iz][iy][ix]) and, if up, of dI0 ([l][iy][ix]); a down solve
+// starts from the plane dI0_zero.  dalpha holds one plane-major array per solve.  Asynchronous on st.
+int regular_solve_planes(vrt_regular *r, int64_t n_solve, const double *hk, const double *dk, const int *dup, const double *dS,
+                         int64_t lam_period, int64_t lam_offset, const double *dalpha, const double *dI0,
+                         const double *dI0_zero, int n_sweeps, hipStream_t st);
+
+}  // namespace vrt

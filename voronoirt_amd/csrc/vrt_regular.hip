@@ -23,7 +23,7 @@
 #include <memory>
 #include <vector>
 
-#include "vrt_internal.h"
+#include "vrt_regular.h"
 
 namespace vrt {
 
@@ -121,7 +121,24 @@ struct RegArgs {
     double *coef;             // per solve 5 * nx * ny doubles: row-march coefficients of one plane
     const double *I0;         // (nx, ny) Julia order per solve: I0[ix + nx*iy]
     double *I;                // plane-major [solve][iz][iy][ix]
+    // > 0 (the line Λ-iteration, vrt_regular_lambda.hip): solve s is wavelength (s + lam_offset) % lam_period and reads
+    // that S field and, if up, that I0 plane; a down solve reads the plane I0_zero.  alpha still follows field_period.
+    int64_t lam_period = 0, lam_offset = 0;
+    const double *I0_zero = nullptr;
 };
+
+__device__ __forceinline__ const double *reg_S(const RegArgs &ra, int64_t solve)
+{
+    const int64_t field = ra.lam_period > 0 ? (solve + ra.lam_offset) % ra.lam_period
+                                            : ra.field_period > 0 ? solve % ra.field_period : solve;
+    return ra.S + field * ra.S_stride;
+}
+
+__device__ __forceinline__ const double *reg_I0(const RegArgs &ra, int64_t solve, bool up, int64_t plane)
+{
+    if (ra.lam_period <= 0) return ra.I0 + solve * plane;
+    return up ? ra.I0 + ((solve + ra.lam_offset) % ra.lam_period) * plane : ra.I0_zero;
+}
 
 #define PL(p, ix, iy) (p)[(ix) + nx * (iy)]
 
@@ -258,7 +275,7 @@ k_regular_solve(RegArgs ra)
     const bool up = ra.up[solve] != 0;
     const int64_t plane = (int64_t)nx * ny;
     const int64_t field = ra.field_period > 0 ? solve % ra.field_period : solve;
-    const double *S = ra.S + field * ra.S_stride;
+    const double *S = reg_S(ra, solve);
     const double *Al = ra.alpha + field * ra.A_stride;
     double *I = ra.I + (int64_t)solve * plane * nz;
     double *coef = ra.coef + (int64_t)solve * 5 * plane;
@@ -276,7 +293,7 @@ k_regular_solve(RegArgs ra)
     // boundary plane: I[1,:,:] = I_0 (:61) / I[end,:,:] = I_0 (:146)
     {
         double *Ib = I + (int64_t)(up ? 0 : nz - 1) * plane;
-        const double *I0 = ra.I0 + (int64_t)solve * plane;
+        const double *I0 = reg_I0(ra, solve, up, plane);
         for (int t = tid; t < plane; t += T) Ib[t] = I0[t];      // same (ix + nx*iy) indexing
     }
     __syncthreads();
@@ -463,7 +480,7 @@ k_reg_xy_coefs(RegArgs ra, double *__restrict__ xy, int64_t solve0)
     const bool up = ra.up[solve] != 0;
     const int64_t plane = (int64_t)nx * ny;
     const int64_t field = ra.field_period > 0 ? solve % ra.field_period : solve;
-    const double *S = ra.S + field * ra.S_stride, *Al = ra.alpha + field * ra.A_stride;
+    const double *S = reg_S(ra, solve), *Al = ra.alpha + field * ra.A_stride;
     const double *x = ra.x, *y = ra.y, *z = ra.z;
     int sign_x, sign_y;                                           // xy_intersect, functions.jl:430-457
     if (k1 > 0 && k2 > 0) { sign_x = -1; sign_y = -1; }
@@ -518,7 +535,7 @@ k_reg_xy_march_mem(RegArgs ra, const double *__restrict__ xy, int64_t solve0)
     const int mx = nx - 2, my = ny - 2;
     {                                                             // boundary plane: I[1,:,:] = I_0 (:61) / I[end,:,:] = I_0 (:146)
         double *Ib = I + (int64_t)(up ? 0 : nz - 1) * plane;
-        const double *I0 = ra.I0 + solve * plane;
+        const double *I0 = reg_I0(ra, solve, up, plane);
         for (int64_t t = tid; t < plane; t += T) Ib[t] = I0[t];
     }
     __syncthreads();
@@ -610,7 +627,7 @@ k_reg_xy_march_lds(RegArgs ra, const double *__restrict__ xy, int64_t solve0)
     for (int t = tid; t < nz; t += T) az[t] = ra.z[t];
     {                                                             // boundary plane: I[1,:,:] = I_0 (:61) / I[end,:,:] = I_0 (:146)
         double *Ib = I + (int64_t)(up ? 0 : nz - 1) * plane;
-        const double *I0 = ra.I0 + solve * plane;
+        const double *I0 = reg_I0(ra, solve, up, plane);
         for (int t = tid; t < plane; t += T) {
             const double v = I0[t];
             Ib[t] = v;
@@ -772,26 +789,6 @@ k_reg_top_interior(int nz, int nx, int ny, int64_t n_solve, const double *__rest
 
 using namespace vrt;
 
-// ---- device-resident form: a handle owns the grid axes and the (grow-only) workspaces -----------
-struct vrt_regular {
-    int device = 0;
-    int64_t nz = 0, nx = 0, ny = 0;
-    double *d_g = nullptr;                 // z | x | y
-    std::vector<double> h_g;               // the same on the host (launch geometry)
-    double *d_S = nullptr, *d_A = nullptr, *d_I = nullptr, *d_k = nullptr, *d_coef = nullptr, *d_xy = nullptr;
-    int *d_up = nullptr;
-    size_t cap_S = 0, cap_A = 0, cap_I = 0, cap_coef = 0, cap_xy = 0;     // in doubles
-    int64_t cap_k = 0;                     // in solves
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    bool timed = false;
-    int force_threads = 0;                 // VRT_REG_THREADS, read once at creation (tests: forces the launch shape)
-    int xy_split = 1;                      // VRT_REG_XY (creation): 0 = all-xy batches through k_regular_solve too;
-                                           //   2 = split, upwind plane read from memory instead of LDS (tests)
-    double *d_I0 = nullptr;                // vrt_regular_emergent_dev: the bottom planes of S of one chunk
-    size_t cap_I0 = 0;
-    int64_t emergent_bytes = (int64_t)8 << 30;  // VRT_REG_EMERGENT_BYTES (creation): workspace cap of an emergent chunk
-};
-
 static void regular_free(vrt_regular *r)
 {
     if (!r) return;
@@ -819,6 +816,7 @@ extern "C" int vrt_regular_create(int64_t nz, int64_t nx, int64_t ny, const doub
         if (const char *e = std::getenv("VRT_REG_THREADS")) r->force_threads = std::max(64, std::min(1024, std::atoi(e) / 64 * 64));
         if (const char *e = std::getenv("VRT_REG_XY")) r->xy_split = std::max(0, std::min(2, std::atoi(e)));
         if (const char *e = std::getenv("VRT_REG_EMERGENT_BYTES")) r->emergent_bytes = std::max<int64_t>(1, std::atoll(e));
+        if (const char *e = std::getenv("VRT_REG_LAMBDA_BYTES")) r->lambda_bytes = std::max<int64_t>(1, std::atoll(e));
         r->device = device;
         r->nz = nz; r->nx = nx; r->ny = ny;
         r->h_g.assign(z, z + nz);
@@ -835,7 +833,7 @@ extern "C" int vrt_regular_create(int64_t nz, int64_t nx, int64_t ny, const doub
 
 extern "C" void vrt_regular_destroy(vrt_regular *r) { regular_free(r); }
 
-static int regular_check_k(int64_t n_solve, const double *k)
+int vrt::regular_check_k(int64_t n_solve, const double *k)
 {
     for (int64_t s = 0; s < n_solve; s++) {
         const double *ks = k + 3 * s;
@@ -846,6 +844,8 @@ static int regular_check_k(int64_t n_solve, const double *k)
     }
     return VRT_OK;
 }
+
+static int regular_launch(vrt_regular *r, RegArgs &ra, int64_t n_solve, const double *k, hipStream_t st);
 
 // One checked batch of solves into the handle's plane-major intensities r->d_I ([solve][iz][iy][ix]): all of
 // vrt_regular_execute_dev but the conversion of I to the caller's layout, shared with vrt_regular_emergent_dev.
@@ -885,6 +885,14 @@ static int regular_solve(vrt_regular *r, int64_t n_solve, const double *k, const
     ra.field_period = field_period;
     ra.I0 = dI0; ra.I = r->d_I;
     ra.coef = r->d_coef;
+    return regular_launch(r, ra, n_solve, k, st);
+}
+
+// The solve kernels of one batch (ra complete but for what the launch chooses); k: the batch's directions on the host
+static int regular_launch(vrt_regular *r, RegArgs &ra, int64_t n_solve, const double *k, hipStream_t st)
+{
+    const int64_t nz = r->nz, nx = r->nx, ny = r->ny, vol = nz * nx * ny;
+    int rc;
     const size_t lds = 2 * sizeof(double) * (size_t)std::max(nx, ny);
     VRT_HIP_TRY(hipEventRecord(r->ev[1], st));
     // one thread per point of a row (the yz/xz planes march row by row), at least two waves; many
@@ -949,6 +957,38 @@ static int regular_solve(vrt_regular *r, int64_t n_solve, const double *k, const
         hipLaunchKernelGGL(k_regular_solve<1024>, dim3((unsigned)n_solve), dim3((unsigned)threads), lds, st, ra);
     VRT_HIP_TRY(hipEventRecord(r->ev[2], st));
     return VRT_OK;
+}
+
+void vrt::regular_release_workspace(vrt_regular *r)
+{
+    dev_free(r->d_A);
+    dev_free(r->d_I);
+    dev_free(r->d_coef);
+    dev_free(r->d_xy);
+    r->cap_A = r->cap_I = r->cap_coef = r->cap_xy = 0;
+}
+
+int vrt::regular_solve_planes(vrt_regular *r, int64_t n_solve, const double *hk, const double *dk, const int *dup,
+                              const double *dS, int64_t lam_period, int64_t lam_offset, const double *dalpha,
+                              const double *dI0, const double *dI0_zero, int n_sweeps, hipStream_t st)
+{
+    const int64_t nz = r->nz, nx = r->nx, ny = r->ny, vol = nz * nx * ny;
+    VRT_HIP_TRY(hipSetDevice(r->device));
+    int rc;
+    if ((rc = dev_grow(r->d_I, r->cap_I, (size_t)(n_solve * vol))) ||
+        (rc = dev_grow(r->d_coef, r->cap_coef, (size_t)(n_solve * 5 * nx * ny))))
+        return rc;
+    VRT_HIP_TRY(hipEventRecord(r->ev[0], st));
+    RegArgs ra;
+    ra.nz = (int)nz; ra.nx = (int)nx; ra.ny = (int)ny; ra.n_sweeps = n_sweeps;
+    ra.z = r->d_g; ra.x = r->d_g + nz; ra.y = r->d_g + nz + nx;
+    ra.k = dk; ra.up = dup;
+    ra.S = dS; ra.alpha = dalpha; ra.S_stride = vol; ra.A_stride = vol;
+    ra.field_period = 0;
+    ra.lam_period = lam_period; ra.lam_offset = lam_offset; ra.I0_zero = dI0_zero;
+    ra.I0 = dI0; ra.I = r->d_I;
+    ra.coef = r->d_coef;
+    return regular_launch(r, ra, n_solve, hk, st);
 }
 
 // dS, dalpha, dI0, dI_out: device pointers in the caller's (Julia) layouts; k, up: host

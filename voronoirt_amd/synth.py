@@ -423,3 +423,55 @@ def line_raster(atm: dict, nlam: int, seed: int, line_to_cont: float = 100.0):
     case = types.SimpleNamespace(lam=lam, planck2=2.0 * (lambda0 / lam) ** 5, lambda0=lambda0, c0=c0,
                                  hc_over_kB=h * c0 / kB, strength_const=strength_const, Bij=1.0, Bji=0.25)
     return raster, np.stack([n1, n2]), case, 2.0
+
+
+def regular_line_case(nz: int, nx: int, ny: int, seed: int, nbb: int = 21, nbf: int = 6):
+    """Inputs of Λ_regular's loop (src/lambda_iteration.jl:116-205) on `atmosphere_raster(nz, nx, ny, seed)` with the
+    one-cell periodic ghost border of get_atmos(...; periodic=true): returns z, x, y (the ghosted axes) and the keyword
+    arguments of api.LineCase on all nz (nx + 2) (ny + 2) points in Julia order (numpy (ny + 2, nx + 2, nz) flattened).
+
+    A 2-level + continuum atom: nbb line wavelengths (log-spaced wings), two blocks of nbf bound-free wavelengths;
+    magnitudes chosen so that the raster is optically thick at line centre and thin in the wings, radiative and
+    collisional rates are comparable and the populations stay positive.  The fields are drawn on the interior and
+    wrapped, so that the ghost points hold their interior values."""
+    c0, kB, h_pl, m_H = 2.99792458e8, 1.380649e-23, 6.62607015e-34, 1.6735575e-27
+    atm = atmosphere_raster(nz, nx, ny, seed)
+    z = atm["z"]
+    rng = np.random.default_rng(seed)
+    lambda0 = 121.567e-9
+    q = np.concatenate([-np.geomspace(600, 0.05, nbb // 2), [0.0], np.geomspace(0.05, 600, nbb // 2)])
+    lam = np.concatenate([lambda0 * (1 + q * 2.5e3 / c0), np.linspace(22.8e-9, 91.17e-9, nbf),
+                          np.linspace(91.2e-9, 364.7e-9, nbf)])
+    nlam = lam.size
+    blocks = np.array([0, nbb, nbb, nbb + nbf, nbb + nbf, nbb + 2 * nbf], dtype=np.int64)
+
+    def wrap(a):                                  # (ny, nx, nz, ...) interior -> ghosted, flattened to (n, ...)
+        a = np.asarray(a)
+        pad = [(1, 1), (1, 1)] + [(0, 0)] * (a.ndim - 2)
+        g = np.pad(a, pad, mode="wrap")
+        return g.reshape((-1,) + g.shape[3:])
+
+    shape = (ny, nx, nz)
+    zeta = np.broadcast_to(((z - z[0]) / (z[-1] - z[0]))[None, None, :], shape)
+    T = 6e3 + 6e3 * zeta + 200 * rng.random(shape)
+    doppler = lambda0 / c0 * np.sqrt(2 * kB * T / m_H)
+    n1 = 1e16 * np.exp(-3 * zeta) * (1 + 0.1 * rng.random(shape))
+    lte = np.stack([n1, n1 * 1e-3 * (1 + rng.random(shape)), n1 * 1e-2 * (1 + rng.random(shape))], axis=-1)
+    B0 = (1.0 + zeta)[..., None] * (1 + 0.05 * rng.random(shape + (nlam,)))
+    Cm = 10 ** rng.uniform(-1, 1, shape + (3, 3))
+    for d in range(3):
+        Cm[..., d, d] = 0.0
+    L = z[-1] - z[0]
+    strength_const = 60.0 / L * doppler.mean() / n1.mean()          # line-centre τ of order 100 across the height
+    lte_g = wrap(lte).T.copy()
+    case = dict(
+        lam=lam, blocks=blocks, lambda0=lambda0, c0=c0, velocity=wrap(rng.normal(0, 3e3, shape + (3,))),
+        doppler=wrap(doppler), gamma_static=wrap(4.702e8 + 10 ** rng.uniform(7, 8.7, shape)),
+        gamma_unsold=wrap(10 ** rng.uniform(-8.5, -7.5, shape)), alpha_cont=wrap(0.05 / L * np.exp(-2 * zeta)),
+        eps=wrap(10 ** rng.uniform(-2.5, -0.5, shape)), temperature=wrap(T), atom_density=lte_g.sum(axis=0), B0=wrap(B0),
+        lte=lte_g, C=wrap(Cm), planck2=2.0 * (lambda0 / lam) ** 5,
+        sigma_bf1=1e-21 * (lam[nbb:nbb + nbf] / lam[nbb + nbf - 1]) ** 3,
+        sigma_bf2=2e-21 * (lam[nbb + nbf:] / lam[-1]) ** 3, strength_const=strength_const, Bij=1.0, Bji=0.25,
+        sigma_bb_const=2e-32, hc_over_kB=h_pl * c0 / kB, pref_ij=2e36, pref_ji=2e37)
+    from .api import periodic_axis
+    return z, periodic_axis(atm["x"]), periodic_axis(atm["y"]), case
