@@ -46,6 +46,44 @@ def test_one_allocator_and_one_exception_guard():
         assert "catch (" not in text, name
 
 
+def _code_only(text):
+    """C++ source without its comments and string literals"""
+    text = re.sub(r'"(?:\\.|[^"\\\n])*"', '""', text)
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return re.sub(r"//[^\n]*", "", text)
+
+
+def test_one_header_holds_every_copy_of_linear_weights():
+    """The branch constant 5e-4 of linear_weights appears in code (comments aside) in csrc/vrt_weights.h only: every device
+    copy of the weights, and the wave-uniform dispatch over their branches, is in the one file that tests/probes/
+    weights_probe.hip includes and tests/test_weights_domain.py judges -- a further copy cannot appear unnoticed."""
+    csrc = os.path.join(ROOT, "voronoirt_amd", "csrc")
+    const = re.compile(r"(?<![\w.])(?:5(?:\.0*)?[eE]-0*4|0?\.0005)(?![\w.])")
+    holders = [name for name in sorted(os.listdir(csrc)) if const.search(_code_only(open(os.path.join(csrc, name)).read()))]
+    assert holders == ["vrt_weights.h"], holders
+    assert const.search("if (dtau < 5e-4) {") and const.search("x = 5.0E-04;") and not const.search("// below 5e-4\n".split("//")[0])
+
+
+def test_weights_probe_builds_and_stays_out_of_the_product():
+    """tests/probes/weights_probe.hip compiles for gfx950 with the product's flags into its own library; the product library
+    exports exactly the declared C ABI as before (no probe symbol), and no module of the package other than build.py
+    names the probe."""
+    from voronoirt_amd import build
+    out = build.build_probe()
+    assert os.path.basename(out) == "libvrt_weights_probe.so" and os.path.getsize(out) > 0
+    def exports(path):
+        txt = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        return {line.split()[-1] for line in txt.splitlines() if " T " in line}
+    assert {"probe_exp", "probe_weights", "probe_entry"} <= exports(out)
+    product = {s for s in exports(_lib.LIB_PATH) if not s.startswith("_")}
+    assert product == set(_lib.PROTOTYPES), product ^ set(_lib.PROTOTYPES)
+    pkg = os.path.join(ROOT, "voronoirt_amd")
+    for name in sorted(os.listdir(pkg)):
+        if name.endswith(".py") and name != "build.py":
+            text = open(os.path.join(pkg, name)).read()
+            assert "weights_probe" not in text and "build_probe" not in text and "PROBE_" not in text, name
+
+
 # the read-only queries that answer 0 for a NULL handle
 ZERO_FOR_NULL = ("vrt_plan_last_path", "vrt_plan_native_pair_block", "vrt_plan_native_pair_block_f32",
                  "vrt_multi_last_shard", "vrt_multi_uses_rccl")

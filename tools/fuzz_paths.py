@@ -37,6 +37,8 @@ for case in range(cases):
     mode = int(rng.integers(3))
     S = 1 + rng.random((n, nlam))
     base = 10 ** rng.uniform(-8, -4, (n, 1))
+    if case % 2:                                     # every other case stratified: thin top, thick bottom, all three branches
+        base = 10 ** (9 - 19 * (pos[:, :1] - bounds[0]) / (bounds[1] - bounds[0])) * (1 + 0.1 * rng.random((n, 1)))
     if mode == 0:
         al = base[:, 0].copy()
     elif mode == 1:

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvrt_hip.so")
 SOURCES = ["vrt_api.cpp", "vrt_grid.cpp", "vrt_schedule.cpp", "vrt_patch.cpp", "vrt_lambda.cpp", "vrt_multi.cpp", "vrt_tessellate.cpp", "vrt_kernels.hip", "vrt_tables.hip", "vrt_layers.hip", "vrt_patch.hip", "vrt_regular.hip", "vrt_regular_lambda.hip", "vrt_physics.hip", "vrt_raster.hip", "vrt_synth.hip"]
-HEADERS = [os.path.join(CSRC, h) for h in ("vrt_internal.h", "vrt_device.h", "vrt_regular.h", "vrt_voigt.h", "vrt_layout_kernels.h", "vrt_tile_kernels.h", "vrt_step_kernels.h")] + [os.path.join(ROOT, "include", "voronoirt.h")]
+HEADERS = [os.path.join(CSRC, h) for h in ("vrt_internal.h", "vrt_device.h", "vrt_weights.h", "vrt_regular.h", "vrt_voigt.h", "vrt_layout_kernels.h", "vrt_tile_kernels.h", "vrt_step_kernels.h")] + [os.path.join(ROOT, "include", "voronoirt.h")]
 
 
 def _hipcc() -> str:
@@ -46,7 +46,7 @@ def build_library(force: bool = False, verbose: bool = False, diag: bool = False
     return _build(LIB, [], verbose)
 
 
-def _build(out: str, extra, verbose: bool) -> str:
+def _build(out: str, extra, verbose: bool, sources=None) -> str:
     cmd = [
         _hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
         # build-wide floating-point contract: no FMA contraction on host or device, so neighbour
@@ -55,11 +55,26 @@ def _build(out: str, extra, verbose: bool) -> str:
         "-Wall", "-Wno-unused-result",
         "-I", os.path.join(ROOT, "include"), "-I", CSRC,
         "-o", out,
-    ] + list(extra) + [os.path.join(CSRC, s) for s in SOURCES] + ["-lpthread", "-ldl"]
+    ] + list(extra) + (sources or [os.path.join(CSRC, s) for s in SOURCES]) + ["-lpthread", "-ldl"]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.check_call(cmd)
     return out
+
+
+PROBE_SRC = os.path.join(ROOT, "tests", "probes", "weights_probe.hip")
+PROBE_LIB = os.path.join(HERE, "libvrt_weights_probe.so")
+
+
+def build_probe(force: bool = False, verbose: bool = False) -> str:
+    """Test infrastructure only: compile tests/probes/weights_probe.hip -- direct calls of every function of
+    csrc/vrt_weights.h, for tests/test_weights_domain.py -- into voronoirt_amd/libvrt_weights_probe.so with exactly
+    the flags of the product library.  Rebuilt when the probe source or vrt_weights.h is newer; the product
+    library does not link it and no other module of the package names it."""
+    deps = [PROBE_SRC, os.path.join(CSRC, "vrt_weights.h")]
+    if not force and os.path.exists(PROBE_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(PROBE_LIB) for d in deps):
+        return PROBE_LIB
+    return _build(PROBE_LIB, [], verbose, sources=[PROBE_SRC])
 
 
 if __name__ == "__main__":

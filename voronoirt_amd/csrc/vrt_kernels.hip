@@ -12,6 +12,7 @@
 #include <cmath>
 
 #include "vrt_internal.h"
+#include "vrt_weights.h"
 
 namespace vrt {
 
@@ -256,23 +257,6 @@ int launch_boundary(vrt_plan *p, const SweepArgs &sa, const void *dI0_up, const 
 // Wavelength is the fastest index of S, α and I, so consecutive lanes read consecutive doubles
 // of a site row.
 // --------------------------------------------------------------------------------------------
-__device__ __forceinline__ void linear_weights(double dtau, double &a, double &b, double &e)
-{
-    if (dtau < 5e-4) {
-        e = 1.0 - dtau + 0.5 * (dtau * dtau);
-        a = dtau * (0.5 - dtau / 3.0);
-        b = dtau * (0.5 - dtau / 6.0);
-    } else if (dtau > 50.0) {
-        e = 0.0;
-        a = 1.0 / dtau;
-        b = 1.0 - a;
-    } else {
-        e = exp(-dtau);
-        a = (1.0 - e) / dtau - e;
-        b = 1.0 - a - e;
-    }
-}
-
 // T = storage type of S, α and I (double, or float for the fp32 value path of BASELINE config C5);
 // the arithmetic is always fp64.
 template <typename T, int ALPHA_MODE>
@@ -321,9 +305,9 @@ k_sweep_level(int64_t first, int count, int nlam, int64_t n, int64_t ldS, int64_
     const double I_2 = (meta & 0x200u) ? 0.0 : (double)Ia[(size_t)u2 * ldI + l];
 
     double ca, cb, ce;
-    linear_weights(R1 * (a_c + a_1) / 2.0, ca, cb, ce);
+    linear_weights_ref_order(R1 * (a_c + a_1) / 2.0, ca, cb, ce);
     const double t1 = ((ce * I_1 + ca * S_1) + cb * S_c) * W1;
-    linear_weights(R2 * (a_c + a_2) / 2.0, ca, cb, ce);
+    linear_weights_ref_order(R2 * (a_c + a_2) / 2.0, ca, cb, ce);
     const double t2 = ((ce * I_2 + ca * S_2) + cb * S_c) * W2;
     Ia[(size_t)site * ldI + l] = (T)((0.0 + t1) + t2);
 }

@@ -90,149 +90,7 @@ int launch_patch_entries(vrt_plan *p, int a, int64_t first, int64_t count)
     return VRT_OK;
 }
 
-// exp(-x) for 5e-4 <= x <= 50: the table-driven exp_neg_tab of vrt_device.h (every patch kernel fills the table)
-__device__ __forceinline__ double exp_neg10(double x) { return exp_neg_tab(x); }
-
-// The kernel is bound by its fp64 arithmetic (two exponentials and a dozen weights per site, angle and
-// wavelength; MI355X issues a wave's fp64 instruction in 4 cycles), so the weights are written with explicit
-// fused multiply-adds -- a third fewer instructions than the reference's expression order, results within a few
-// ulp of it (the parity contract is 1e-10; the build-wide -ffp-contract=off stays for the neighbour search).
-//
-// linear_weights (functions.jl:484-500) without control flow inside a lane; `MODE` is wave-uniform:
-//   0  no lane has 5e-4 <= Δτ <= 50: thin or thick only, no exponential (optically thin upper layers and
-//      thick bottom layers are most of a stratified atmosphere; a wave's lanes are neighbouring sites of a layer)
-//   1  no lane is thin: no Taylor branch
-//   2  general
-// The thick branch (Δτ > 50: e = 0, a = 1/Δτ, b = 1 - a) needs no select for a and b: with e = exp(-50) = 2e-22
-// the general formulas round to exactly those values; only e itself is set to 0.
-template <int MODE>
-__device__ __forceinline__ void lin_weights_fma(double dtau, double &a, double &b, double &e)
-{
-    double rc = __builtin_amdgcn_rcp(dtau);                 // only consumed when dtau >= 5e-4
-    rc = fma(fma(-dtau, rc, 1.0), rc, rc);                  // v_rcp_f64 is good to ~2^-23: one Newton step -> 1e-14
-    double e_thin = 0.0, a_thin = 0.0, b_thin = 0.0;
-    if (MODE != 1) {
-        e_thin = fma(dtau, fma(0.5, dtau, -1.0), 1.0);
-        a_thin = dtau * fma(dtau, -1.0 / 3.0, 0.5);
-        b_thin = dtau * fma(dtau, -1.0 / 6.0, 0.5);
-    }
-    const bool thin = dtau < 5e-4;
-    if (MODE == 0) {
-        e = thin ? e_thin : 0.0;
-        a = thin ? a_thin : rc;
-        b = thin ? b_thin : 1.0 - rc;
-        return;
-    }
-    const double ee = exp_neg10(fmin(dtau, 50.0));
-    const double a_mid = fma(1.0 - ee, rc, -ee), b_mid = (1.0 - a_mid) - ee;
-    const double e_mid = dtau > 50.0 ? 0.0 : ee;
-    if (MODE == 1) {
-        e = e_mid; a = a_mid; b = b_mid;
-    } else {
-        e = thin ? e_thin : e_mid;
-        a = thin ? a_thin : a_mid;
-        b = thin ? b_thin : b_mid;
-    }
-}
-
-// one wavelength of an entry: both upwinds' shares of a visit, t_r = ((e_r I_ur + a_r S_ur) + b_r S_c) w_r with
-// I_ur gathered as 0 unless upwind r lies in an earlier layer; g_r = e_r wg_r, wg_r = w_r if upwind r lies in the
-// site's own layer, else 0.  c = t_1 + t_2.  dt_r = r_r (α_c + α_ur) / 2 (trapezoidal, functions.jl:393).
-template <int MODE>
-__device__ __forceinline__ void entry_terms(double dt1, double dt2, double w1, double w2, double wg1, double wg2,
-                                            double S_c, double S_1, double S_2, double I_1, double I_2, double &c,
-                                            double &g1, double &g2)
-{
-    double ca1, cb1, ce1, ca2, cb2, ce2;
-    lin_weights_fma<MODE>(dt1, ca1, cb1, ce1);
-    lin_weights_fma<MODE>(dt2, ca2, cb2, ce2);
-    const double t1 = fma(cb1, S_c, fma(ce1, I_1, ca1 * S_1)) * w1;
-    const double t2 = fma(cb2, S_c, fma(ce2, I_2, ca2 * S_2)) * w2;
-    c = t1 + t2;
-    g1 = ce1 * wg1;
-    g2 = ce2 * wg2;
-}
-
-// the same with the wave-uniform choice of MODE from the two optical depths of every lane
-__device__ __forceinline__ void entry_lambda(double rh1, double rh2, double w1, double w2, double wg1, double wg2,
-                                             double a_c, double a_1, double a_2, double S_c, double S_1, double S_2,
-                                             double I_1, double I_2, double &c, double &g1, double &g2)
-{
-    const double d1 = rh1 * (a_c + a_1), d2 = rh2 * (a_c + a_2);
-    const bool mid = ((d1 >= 5e-4) & (d1 <= 50.0)) | ((d2 >= 5e-4) & (d2 <= 50.0));
-    const bool thin = (d1 < 5e-4) | (d2 < 5e-4);
-    if (__ballot(mid) == 0ull) entry_terms<0>(d1, d2, w1, w2, wg1, wg2, S_c, S_1, S_2, I_1, I_2, c, g1, g2);
-    else if (__ballot(thin) == 0ull) entry_terms<1>(d1, d2, w1, w2, wg1, wg2, S_c, S_1, S_2, I_1, I_2, c, g1, g2);
-    else entry_terms<2>(d1, d2, w1, w2, wg1, wg2, S_c, S_1, S_2, I_1, I_2, c, g1, g2);
-}
-
-// The same, one upwind at a time: `next` (the optical depth the following evaluation starts from) is tied to this
-// one's results by a compiler fence, so that the four evaluations of an entry's pair follow each other instead of
-// being interleaved (the compiler's own order needs 72 registers, this one 64).  The
-// weights w_r are read from the thread's LDS slots where they are used (pw1, pw2), not held.
-template <int MODE>
-__device__ __forceinline__ void entry_terms_seq(double dt1, double dt2, const double *pw1, const double *pw2, bool in1,
-                                                bool in2, double S_c, double S_1, double S_2, double I_1, double I_2,
-                                                double &c, double &g1, double &g2, double &next)
-{
-    double ca, cb, ce;
-    lin_weights_fma<MODE>(dt1, ca, cb, ce);
-    const double w1 = *pw1;
-    double t1 = fma(cb, S_c, fma(ce, I_1, ca * S_1)) * w1;
-    g1 = in1 ? ce * w1 : 0.0;
-    asm volatile("" : "+v"(t1), "+v"(g1), "+v"(dt2));
-    lin_weights_fma<MODE>(dt2, ca, cb, ce);
-    const double w2 = *pw2;
-    const double t2 = fma(cb, S_c, fma(ce, I_2, ca * S_2)) * w2;
-    c = t1 + t2;
-    g2 = in2 ? ce * w2 : 0.0;
-    asm volatile("" : "+v"(c), "+v"(g2), "+v"(next));
-}
-__device__ __forceinline__ void entry_lambda_seq(double d1, double d2, const double *pw1, const double *pw2, bool in1,
-                                                 bool in2, double S_c, double S_1, double S_2, double I_1, double I_2,
-                                                 double &c, double &g1, double &g2, double &next)
-{
-    const bool mid = ((d1 >= 5e-4) & (d1 <= 50.0)) | ((d2 >= 5e-4) & (d2 <= 50.0));
-    const bool thin = (d1 < 5e-4) | (d2 < 5e-4);
-    if (__ballot(mid) == 0ull) entry_terms_seq<0>(d1, d2, pw1, pw2, in1, in2, S_c, S_1, S_2, I_1, I_2, c, g1, g2, next);
-    else if (__ballot(thin) == 0ull) entry_terms_seq<1>(d1, d2, pw1, pw2, in1, in2, S_c, S_1, S_2, I_1, I_2, c, g1, g2, next);
-    else entry_terms_seq<2>(d1, d2, pw1, pw2, in1, in2, S_c, S_1, S_2, I_1, I_2, c, g1, g2, next);
-}
-
-// The same visit with the upwind intensities applied LAST (the data-as-flag chained launch, where a workgroup waits for
-// exactly those): everything that does not need I_1, I_2 -- the four weights, a_r S_ur, the couplings -- is formed while the
-// gathers are in flight or repeated, and what is left behind the wait is three dependent operations per upwind.  The
-// same operations on the same values in the same association as entry_terms_seq: bit-identical.
-struct LateTerms { double ce1, p1, cb1, ce2, p2, cb2; };
-template <int MODE>
-__device__ __forceinline__ void late_coeffs(double dt1, double dt2, double S_1, double S_2, LateTerms &L, double &next)
-{
-    double ca, cb, ce;
-    lin_weights_fma<MODE>(dt1, ca, cb, ce);
-    L.ce1 = ce; L.p1 = ca * S_1; L.cb1 = cb;
-    asm volatile("" : "+v"(L.ce1), "+v"(L.p1), "+v"(L.cb1), "+v"(dt2));
-    lin_weights_fma<MODE>(dt2, ca, cb, ce);
-    L.ce2 = ce; L.p2 = ca * S_2; L.cb2 = cb;
-    asm volatile("" : "+v"(L.ce2), "+v"(L.p2), "+v"(L.cb2), "+v"(next));
-}
-__device__ __forceinline__ void late_lambda(double d1, double d2, double S_1, double S_2, LateTerms &L, double &next)
-{
-    const bool mid = ((d1 >= 5e-4) & (d1 <= 50.0)) | ((d2 >= 5e-4) & (d2 <= 50.0));
-    const bool thin = (d1 < 5e-4) | (d2 < 5e-4);
-    if (__ballot(mid) == 0ull) late_coeffs<0>(d1, d2, S_1, S_2, L, next);
-    else if (__ballot(thin) == 0ull) late_coeffs<1>(d1, d2, S_1, S_2, L, next);
-    else late_coeffs<2>(d1, d2, S_1, S_2, L, next);
-}
-__device__ __forceinline__ void late_apply(const LateTerms &L, const double *pw1, const double *pw2, bool in1, bool in2,
-                                           double S_c, double I_1, double I_2, double &c, double &g1, double &g2)
-{
-    const double w1 = *pw1, w2 = *pw2;
-    const double t1 = fma(L.cb1, S_c, fma(L.ce1, I_1, L.p1)) * w1;
-    const double t2 = fma(L.cb2, S_c, fma(L.ce2, I_2, L.p2)) * w2;
-    c = t1 + t2;
-    g1 = in1 ? L.ce1 * w1 : 0.0;
-    g2 = in2 ? L.ce2 * w2 : 0.0;
-}
+// exp_neg10, lin_weights_fma<MODE>, entry_lambda / entry_lambda_seq / late_lambda + late_apply: vrt_weights.h
 
 // wavelength pair `idx` of a plane: 32-bit byte offset from a wave-uniform base (planes are < 4 GiB: n < 2^28),
 // so the load takes the saddr + voffset form -- one address VGPR, no 64-bit vector arithmetic

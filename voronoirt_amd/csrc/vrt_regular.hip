@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "vrt_regular.h"
+#include "vrt_weights.h"
 
 namespace vrt {
 
@@ -50,23 +51,6 @@ k_reg_from_planes(int nz, int nx, int ny, const double *__restrict__ in, double 
     const int ix = (int)((t / nz) % nx);
     const int iy = (int)(t / ((int64_t)nz * nx));
     out[t] = in[ix + (int64_t)nx * (iy + (int64_t)ny * iz)];
-}
-
-__device__ __forceinline__ void reg_linear_weights(double dtau, double &a, double &b, double &e)
-{
-    if (dtau < 5e-4) {                                   // functions.jl:484-500
-        e = 1.0 - dtau + 0.5 * (dtau * dtau);
-        a = dtau * (0.5 - dtau / 3.0);
-        b = dtau * (0.5 - dtau / 6.0);
-    } else if (dtau > 50.0) {
-        e = 0.0;
-        a = 1.0 / dtau;
-        b = 1.0 - a;
-    } else {
-        e = exp(-dtau);
-        a = (1.0 - e) / dtau - e;
-        b = 1.0 - a - e;
-    }
 }
 
 __device__ __forceinline__ double reg_bilinear(double xm, double ym, double x1, double x2, double y1,
@@ -186,7 +170,7 @@ __device__ __forceinline__ void row_march(int nx, int n_ser, int n_par, int s0, 
         const double dtau = r * (w.a[4] + a_u) / 2.0;
         const double S_u = reg_bilinear_rcp(wz2, wz1, wc2, wc1, rdz, rdc, w.s[0], w.s[1], w.s[2], w.s[3]);
         double a, b, e;
-        reg_linear_weights(dtau, a, b, e);
+        linear_weights_ref_order(dtau, a, b, e);
         o.e = e; o.aS = a * S_u; o.bS = b * w.s[4]; o.q1 = w.q[0]; o.q2 = w.q[1];
     };
     // ---- pass 0: the coefficients of every row of the plane.  They do not depend on the carried
@@ -327,7 +311,7 @@ k_regular_solve(RegArgs ra)
                 const double S_u = reg_bilinear(x_up, y_up, x[xl], x[xu], y[yl], y[yu], PL(Su, xl, yl),
                                                 PL(Su, xl, yu), PL(Su, xu, yl), PL(Su, xu, yu));
                 double a, b, e;
-                reg_linear_weights(dtau, a, b, e);
+                linear_weights_ref_order(dtau, a, b, e);
                 const double I_u = reg_bilinear(x_up, y_up, x[xl], x[xu], y[yl], y[yu], PL(Ip, xl, yl),
                                                 PL(Ip, xl, yu), PL(Ip, xu, yl), PL(Ip, xu, yu));
                 PL(Ic, idx, idy) = (e * I_u + a * S_u) + b * PL(Sc, idx, idy);
@@ -377,7 +361,7 @@ k_regular_solve(RegArgs ra)
                         const double S_u = reg_bilinear(z_up, y_up, zb1, zb2, y[yl], y[yu], PL(S_lo, xu, yl),
                                                         PL(S_lo, xu, yu), PL(S_hi, xu, yl), PL(S_hi, xu, yu));
                         double a, b, e;
-                        reg_linear_weights(dtau, a, b, e);
+                        linear_weights_ref_order(dtau, a, b, e);
                         const double I_u = up ? reg_bilinear(z_up, y_up, zb1, zb2, y[yl], y[yu], PL(Ip, xu, yl),
                                                              PL(Ip, xu, yu), row[yl], row[yu])
                                               : reg_bilinear(z_up, y_up, zb1, zb2, y[yl], y[yu], row[yl], row[yu],
@@ -433,7 +417,7 @@ k_regular_solve(RegArgs ra)
                         const double S_u = reg_bilinear(z_up, x_up, zb1, zb2, x[xl], x[xu], PL(S_lo, xl, yu),
                                                         PL(S_lo, xu, yu), PL(S_hi, xl, yu), PL(S_hi, xu, yu));
                         double a, b, e;
-                        reg_linear_weights(dtau, a, b, e);
+                        linear_weights_ref_order(dtau, a, b, e);
                         const double I_u = up ? reg_bilinear(z_up, x_up, zb1, zb2, x[xl], x[xu], PL(Ip, xl, yu),
                                                              PL(Ip, xu, yu), row[xl], row[xu])
                                               : reg_bilinear(z_up, x_up, zb1, zb2, x[xl], x[xu], row[xl], row[xu],
@@ -503,7 +487,7 @@ k_reg_xy_coefs(RegArgs ra, double *__restrict__ xy, int64_t solve0)
     const double S_u = reg_bilinear(x_up, y_up, x[xl], x[xu], y[yl], y[yu], PL(Su, xl, yl), PL(Su, xl, yu), PL(Su, xu, yl),
                                     PL(Su, xu, yu));
     double a, b, e;
-    reg_linear_weights(dtau, a, b, e);
+    linear_weights_ref_order(dtau, a, b, e);
     double *c = xy + ((int64_t)blockIdx.z * nz + idz) * 3 * plane + (idx + nx * idy);
     c[0] = e;
     c[plane] = a * S_u;

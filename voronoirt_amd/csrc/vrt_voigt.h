@@ -1,7 +1,7 @@
 // Re w4(x + i y), Humlíček's Voigt function, and its complex helpers: ONE device definition for every kernel that
 // evaluates a line profile (vrt_physics.hip: the Voronoi opacity, rates and synthesis kernels; vrt_regular_lambda.hip:
 // the raster opacity of the regular-grid Λ-iteration), so that the paths agree point for point.  Kernels that call it
-// fill the exp2 table first (exp2_table_fill, vrt_device.h).
+// fill the exp2 table first (exp2_table_fill, vrt_weights.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
