@@ -645,6 +645,41 @@ int vrt_regular_lambda_iterate(vrt_regular_lambda *s, double *max_rel_change);
 int vrt_regular_lambda_get(vrt_regular_lambda *s, double *J, double *S, double *populations, double *R, double *gamma);
 void vrt_regular_lambda_destroy(vrt_regular_lambda *s);
 
+/* ---- Ng acceleration of the Λ-iteration (Ng 1974, J. Chem. Phys. 61, 2680; Olson, Auer & Buchler 1986, JQSRT 35, 431) ----
+ * Plain Λ-iteration converges like 1 - ε.  The second-order Ng step extrapolates from the last four iterates x0 (newest)
+ * .. x3 of S along the two slowest error modes; it needs no approximate operator and changes no sweep kernel.  Per element
+ *   w = 1/x0,  q1 = (x0 - 2 x1) + x2,  q2 = ((x0 - x1) - x2) + x3,  q3 = x0 - x1
+ *   A1 = Σ (w q1) q1,  B1 = Σ (w q1) q2,  C1 = Σ (w q1) q3,  B2 = Σ (w q2) q2,  C2 = Σ (w q2) q3
+ *   det = A1 B2 - B1 B1,  a = (C1 B2 - C2 B1)/det,  b = (C2 A1 - C1 B1)/det,  c = (1 - a) - b      (host, double)
+ *   x_acc = (c x0 + a x1) + b x2
+ * in exactly this order of operations.  The sums are formed without floating-point atomics in a fixed order: the same
+ * count gives the same bits run after run.  A step is REJECTED, all or nothing, when a sum or det is not finite, det == 0,
+ * or any x_acc is not finite or not > 0 (a source function stays positive: the criterion divides by it).
+ *
+ * vrt_ng_accelerate_dev, standalone: device pointers on the current HIP device; synchronises `stream`; d_out aliases no
+ * input.  sums[5] = A1 B1 C1 B2 C2, coeffs[2] = a b, *applied = 1, or 0 when rejected (d_out then unspecified). */
+int vrt_ng_accelerate_dev(int64_t count, const double *d_x0, const double *d_x1, const double *d_x2,
+                          const double *d_x3, double *d_out, double sums[5], double coeffs[2], int *applied,
+                          void *stream);
+/* The single-device sessions: order 0 = off (default), 2 = the step above.  The first step is due after iterate number
+ * `start` (>= 4), the next ones after every `period` further iterates (>= 4, so that an extrapolated S never enters a
+ * history).  Anything else: VRT_EINVAL; with order 0, start and period are ignored.  Callable between any two iterates (a
+ * due iterate whose three predecessors were not all recorded takes no step); order 0 frees the history.
+ * vrt_*_iterate returns what it returns without acceleration -- max |1 - S_old/S_new| of the PLAIN update, formed before
+ * any extrapolation; after an accepted step the S the session holds (what the next iterate solves with, what *_get
+ * returns) is x_acc.  Populations, R, γ and J are not extrapolated: the next iterate recomputes them from its J.  Only
+ * S of the three iterates before a due one is copied (three extra S arrays while acceleration is on; none when off, and
+ * a session that never asks for acceleration runs exactly what it ran before).  The Voronoi session forms the sums over
+ * the n nlam physical entries of its up-order copy of S and applies the same a, b to both sweep-order copies.
+ * vrt_multi_lambda_* has NO acceleration entry: its S is split over the devices and the sums would need a collective. */
+int vrt_lambda_set_acceleration(vrt_lambda *s, int order, int start, int period);
+int vrt_regular_lambda_set_acceleration(vrt_regular_lambda *s, int order, int start, int period);
+/* what the LAST iterate did: *applied = 1 taken, 0 none due, -1 due but rejected; sums / coeffs (either may be NULL)
+ * valid unless 0 */
+int vrt_lambda_last_acceleration(const vrt_lambda *s, int *applied, double sums[5], double coeffs[2]);
+int vrt_regular_lambda_last_acceleration(const vrt_regular_lambda *s, int *applied, double sums[5],
+                                         double coeffs[2]);
+
 /* ---- emergent spectra: opacity / source function, top-plane intensity, tau = 1 heights ------------------------------
  * The last step of a reference study (write_top_intensity, write_tau_unity and plotter, src/plot_utils.jl:61-140,
  * :297-355, :434-576) on a regular raster.  Plain numbers in one unit system, constants folded in by the caller.

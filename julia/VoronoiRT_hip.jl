@@ -254,8 +254,12 @@ The reference's Λ_voronoi with its loop body on the device.  Everything Λ_voro
 (LTE populations, α_cont, B_0, ε, C: :217-246) is computed by the reference's own functions; the loop
 (:253-283) is vrt_lambda_iterate; after every iteration populations and S_new are fetched and written to the
 HDF5 file exactly as the reference checkpoints them (:280-281); `criterion` keeps writing the history (:346).
+`ng = (start, period)`: second-order Ng acceleration inside the session (vrt_lambda_set_acceleration; one device
+only -- the multi-device session has no such entry), the first step after iterate `start`, then every `period`
+iterates, both >= 4.  The keyword is unrun: Julia is not installed where the library is built.
 """
-function Λ(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, line::HydrogenicLine, quadrature::String, DATA::String)
+function Λ(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, line::HydrogenicLine, quadrature::String, DATA::String;
+           ng::Union{Nothing,Tuple{Int,Int}}=nothing)
     println("---Iterating---")
     LTE_pops = VoronoiRT.LTE_populations(line, sites)
     populations = copy(LTE_pops)
@@ -318,6 +322,11 @@ function Λ(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, line::Hydr
         check(ccall(dlsym(libvrt_handle(), f_create), Cint, (Ptr{Cvoid}, Ref{LineCase}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
                     plan, lc, w, ses))
     end
+    if ng !== nothing
+        multi && error("Ng acceleration needs the one-device session (vrt_multi_lambda_* has no acceleration entry)")
+        check(ccall((:vrt_lambda_set_acceleration, libvrt), Cint, (Ptr{Cvoid}, Cint, Cint, Cint), ses[], 2, ng[1], ng[2]))
+    end
+    ng_applied = Ref{Cint}(0); ng_coeffs = zeros(2)
     i = 0
     diff = Ref{Float64}(1.0)                  # criterion(S_new = B_0, S_old = 0) = |1 - 0/B| = 1, :325-349
     VoronoiRT.write_to_file(diff[], i + 1, DATA)
@@ -325,6 +334,11 @@ function Λ(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, line::Hydr
         @time check(ccall(dlsym(libvrt_handle(), f_iterate), Cint, (Ptr{Cvoid}, Ref{Float64}), ses[], diff))
         isnan(diff[]) && println("NaN DIFF!")
         println("   Rel. diff.: $(diff[])")
+        if ng !== nothing
+            check(ccall((:vrt_lambda_last_acceleration, libvrt), Cint, (Ptr{Cvoid}, Ref{Cint}, Ptr{Float64}, Ptr{Float64}),
+                        ses[], ng_applied, C_NULL, ng_coeffs))
+            ng_applied[] != 0 && println("   Ng step ", ng_applied[] == 1 ? "taken" : "rejected", ": a = $(ng_coeffs[1]), b = $(ng_coeffs[2])")
+        end
         GC.@preserve S pops check(ccall(dlsym(libvrt_handle(), f_get), Cint,
                                         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
                                         ses[], C_NULL, S, pops, C_NULL, C_NULL))
@@ -351,9 +365,11 @@ point of the loop.  What Λ_regular derives before the loop (LTE populations, α
 the reference's own functions, as in `Λ` above; each iteration is vrt_regular_lambda_iterate, after which
 populations and S_new are fetched and checkpointed without the ghost border like the reference (:188-189).
 Arrays keep their Julia shapes: (nλ, nz, nx, ny), (nz, nx, ny, 3) and (3, 3, nz, nx, ny) are vrt_line_case's
-(nλ, n), (n, 3) and (3, 3, n) with n = nz nx ny.  Unrun: Julia is not installed where the library is built.
+(nλ, n), (n, 3) and (3, 3, n) with n = nz nx ny.  `ng = (start, period)` as for `Λ`
+(vrt_regular_lambda_set_acceleration).  Unrun: Julia is not installed where the library is built.
 """
-function Λ_regular(ϵ::AbstractFloat, maxiter::Integer, atmos, line::HydrogenicLine, quadrature::String, DATA::String)
+function Λ_regular(ϵ::AbstractFloat, maxiter::Integer, atmos, line::HydrogenicLine, quadrature::String, DATA::String;
+                   ng::Union{Nothing,Tuple{Int,Int}}=nothing)
     LTE_pops = VoronoiRT.LTE_populations(line, atmos)
     α_cont = VoronoiRT.α_absorption.(line.λ0, atmos.temperature, atmos.electron_density * 1.0,
                                      LTE_pops[:, :, :, 1] .+ LTE_pops[:, :, :, 2], LTE_pops[:, :, :, 3]) .+
@@ -420,6 +436,9 @@ function Λ_regular(ϵ::AbstractFloat, maxiter::Integer, atmos, line::Hydrogenic
     pops = Array{Float64,4}(undef, nz, nx, ny, 3)
     fetch_state(Jp, Sp) = GC.@preserve J S pops check(ccall((:vrt_regular_lambda_get, libvrt), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ses[], Jp, Sp, pops, C_NULL, C_NULL))
+    ng !== nothing && check(ccall((:vrt_regular_lambda_set_acceleration, libvrt), Cint, (Ptr{Cvoid}, Cint, Cint, Cint),
+                                  ses[], 2, ng[1], ng[2]))
+    ng_applied = Ref{Cint}(0); ng_coeffs = zeros(2)
     i = 0
     diff = Ref{Float64}(1.0)                  # criterion(S_new = B_0, S_old = 0) = 1
     VoronoiRT.write_to_file(diff[], i + 1, DATA)
@@ -427,6 +446,11 @@ function Λ_regular(ϵ::AbstractFloat, maxiter::Integer, atmos, line::Hydrogenic
         @time check(ccall((:vrt_regular_lambda_iterate, libvrt), Cint, (Ptr{Cvoid}, Ref{Float64}), ses[], diff))
         isnan(diff[]) && println("NaN DIFF!")
         println("   Rel. diff.: $(diff[])")
+        if ng !== nothing
+            check(ccall((:vrt_regular_lambda_last_acceleration, libvrt), Cint, (Ptr{Cvoid}, Ref{Cint}, Ptr{Float64}, Ptr{Float64}),
+                        ses[], ng_applied, C_NULL, ng_coeffs))
+            ng_applied[] != 0 && println("   Ng step ", ng_applied[] == 1 ? "taken" : "rejected", ": a = $(ng_coeffs[1]), b = $(ng_coeffs[2])")
+        end
         fetch_state(C_NULL, pointer(S))
         VoronoiRT.write_to_file(pops[:, 2:end-1, 2:end-1, :] * 1u"m^-3", DATA)     # the checkpoint, :188-189
         VoronoiRT.write_to_file(S[:, :, 2:end-1, 2:end-1] * I_unit, DATA)

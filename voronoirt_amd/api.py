@@ -1087,6 +1087,46 @@ def sample_from_temp_gradient(z, x, y, T, n_sites: int, seed: int, **kw):
     return rejection_sampling(n_sites, z, x, y, np.abs(g), seed, **kw)
 
 
+def ng_accelerate_dev(count: int, d_x0: int, d_x1: int, d_x2: int, d_x3: int, d_out: int, stream: int = 0):
+    """Second-order Ng step (`vrt_ng_accelerate_dev`) on device pointers (torch data_ptr()) of `count` doubles, x0 the
+    newest iterate; d_out aliases no input.  Returns (applied, sums (A1, B1, C1, B2, C2), coeffs (a, b)); synchronises."""
+    sums, coeffs, applied = np.zeros(5), np.zeros(2), ctypes.c_int(0)
+    check(_lib.load().vrt_ng_accelerate_dev(int(count), d_x0, d_x1, d_x2, d_x3, d_out, _d(sums), _d(coeffs),
+                                            ctypes.byref(applied), stream or None))
+    return bool(applied.value), sums, coeffs
+
+
+def ng_accelerate(x0, x1, x2, x3, device: int = 0):
+    """Second-order Ng extrapolation (Ng 1974; Olson, Auer & Buchler 1986) from the last four iterates of a positive
+    quantity, x0 the newest: host arrays of one shape, staged through the device.  Returns (x_acc, sums, coeffs) with
+    x_acc = (c x0 + a x1) + b x2, c = (1 - a) - b, or x_acc = None when the step is rejected (a sum or the determinant
+    not finite or zero, or an x_acc that is not finite and positive)."""
+    import torch
+    xs = [np.ascontiguousarray(x, dtype=np.float64) for x in (x0, x1, x2, x3)]
+    if any(x.shape != xs[0].shape for x in xs):
+        raise ValueError("ng_accelerate: the four iterates must have one shape")
+    dev = torch.device("cuda", int(device))
+    with torch.cuda.device(dev):
+        d = [torch.from_numpy(x.reshape(-1)).to(dev) for x in xs]
+        out = torch.empty_like(d[0])
+        applied, sums, coeffs = ng_accelerate_dev(xs[0].size, *(t.data_ptr() for t in d), out.data_ptr(),
+                                                  torch.cuda.current_stream(dev).cuda_stream)
+        return (out.cpu().numpy().reshape(xs[0].shape) if applied else None), sums, coeffs
+
+
+def _ng_settings(ng):
+    start, period = (int(v) for v in ng)
+    return start, period
+
+
+def _ng_last(fn, h, i, steps):
+    """appends (iterate, applied, a, b) of iterate i when a step was due"""
+    applied, coeffs = ctypes.c_int(0), np.zeros(2)
+    check(fn(h, ctypes.byref(applied), None, _d(coeffs)))
+    if applied.value:
+        steps.append((i, applied.value == 1, float(coeffs[0]), float(coeffs[1])))
+
+
 def lambda_update_dev(sites: VoronoiSites, nlam: int, ld: int, dJ: int, dB: int, deps: int, dS_old: int,
                       dS_new: int, stream: int = 0) -> float:
     """Device-resident Λ-iteration epilogue: S_new = (1 - ε) J + ε B (src/lambda_iteration.jl:261-263)
@@ -1285,10 +1325,13 @@ def _Lambda_voronoi_native(eps_conv: float, maxiter: int, sites: VoronoiSites, c
 
 
 def Lambda_voronoi_host(eps_conv: float, maxiter: int, sites: VoronoiSites, case: LineCase, quadrature: str,
-                        n_sweeps: int = 3):
+                        n_sweeps: int = 3, ng=None):
     """Λ_voronoi (src/lambda_iteration.jl:205-300) for a host WITHOUT device arrays: the library owns the device
     state (`vrt_lambda_create` / `_iterate` / `_get`), one call per iteration, only the criterion's scalar
-    comes back inside the loop.  Returns (J, S_new, populations (3, n), history)."""
+    comes back inside the loop.  Returns (J, S_new, populations (3, n), history).
+    ng=(start, period): second-order Ng acceleration inside the session (`vrt_lambda_set_acceleration`), the first
+    step after iterate `start`, then every `period` iterates (both >= 4); the tuple gains a fifth element, the list of
+    (iterate, applied, a, b) of every due step."""
     L = _lib.load()
     plan, w = _quadrature_plan(sites, quadrature, n_sweeps)
     lc, keep = case.c_struct()
@@ -1296,13 +1339,18 @@ def Lambda_voronoi_host(eps_conv: float, maxiter: int, sites: VoronoiSites, case
     check(L.vrt_lambda_create(plan._h, ctypes.byref(lc), _d(_f64(w)), ctypes.byref(h)))
     n, nlam = sites.n, int(keep["lam"].size)
     history, diff, i = [], 1.0, 0                              # criterion(S_new = B, S_old = 0) = 1
+    steps = []
     try:
+        if ng is not None:
+            check(L.vrt_lambda_set_acceleration(h, 2, *_ng_settings(ng)))
         while diff > eps_conv and i < maxiter:
             d = ctypes.c_double()
             check(L.vrt_lambda_iterate(h, ctypes.byref(d)))
             diff = d.value
             history.append(diff)
             i += 1
+            if ng is not None:
+                _ng_last(L.vrt_lambda_last_acceleration, h, i, steps)
             if diff != diff:
                 import warnings
                 warnings.warn(f"Lambda_voronoi_host: NaN DIFF! at iteration {i} -- stopping, results are not converged")
@@ -1311,7 +1359,7 @@ def Lambda_voronoi_host(eps_conv: float, maxiter: int, sites: VoronoiSites, case
         if i == 0:
             S[:] = keep["B0"]
             pops[:] = keep["lte"]
-        return J, S, pops, history
+        return (J, S, pops, history) if ng is None else (J, S, pops, history, steps)
     finally:
         L.vrt_lambda_destroy(h)
 
@@ -1424,12 +1472,13 @@ def J_lambda_regular_line(S, populations, z, x, y, case: LineCase, quadrature: s
 
 
 def Lambda_regular(eps_conv: float, maxiter: int, z, x, y, case: LineCase, quadrature: str, n_sweeps: int = 3,
-                   device: int = 0):
+                   device: int = 0, ng=None):
     """Λ_regular (src/lambda_iteration.jl:116-205) with library-owned device state (`vrt_regular_lambda_create` /
     `_iterate` / `_get`): one call per iteration, only the criterion's scalar comes back inside the loop.  The raster
     and `case` as for `J_lambda_regular_line`; every point, ghost border included, is a point of the loop.  Starts
     in LTE with S = B_0; stops like `Lambda_voronoi_host` (criterion, NaN).  Returns (J, S_new, populations (3, n),
-    history)."""
+    history); ng=(start, period) as for `Lambda_voronoi_host` (`vrt_regular_lambda_set_acceleration`), with the list of
+    (iterate, applied, a, b) as a fifth element."""
     L = _lib.load()
     w, k, dirs = _regular_directions(quadrature)
     lc, keep = case.c_struct()
@@ -1441,18 +1490,23 @@ def Lambda_regular(eps_conv: float, maxiter: int, z, x, y, case: LineCase, quadr
         check(L.vrt_regular_lambda_create(solver._h, k.shape[0], _d(k), dirs.ctypes.data_as(_lib.p_int), _d(w),
                                           ctypes.byref(lc), int(n_sweeps), ctypes.byref(h)))
         history, diff, i = [], 1.0, 0                          # criterion(S_new = B, S_old = 0) = 1
+        steps = []
+        if ng is not None:
+            check(L.vrt_regular_lambda_set_acceleration(h, 2, *_ng_settings(ng)))
         while diff > eps_conv and i < maxiter:
             d = ctypes.c_double()
             check(L.vrt_regular_lambda_iterate(h, ctypes.byref(d)))
             diff = d.value
             history.append(diff)
             i += 1
+            if ng is not None:
+                _ng_last(L.vrt_regular_lambda_last_acceleration, h, i, steps)
             if diff != diff:
                 import warnings
                 warnings.warn(f"Lambda_regular: NaN DIFF! at iteration {i} -- stopping, results are not converged")
         J, S, pops = np.zeros((n, nlam)), np.zeros((n, nlam)), np.zeros((3, n))
         check(L.vrt_regular_lambda_get(h, _d(J), _d(S), _d(pops), None, None))
-        return J, S, pops, history
+        return (J, S, pops, history) if ng is None else (J, S, pops, history, steps)
     finally:
         if h:
             L.vrt_regular_lambda_destroy(h)

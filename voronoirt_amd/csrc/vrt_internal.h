@@ -589,4 +589,25 @@ int launch_patch_chain(vrt_plan *p, const TileArgs &ta, int npair, hipStream_t s
 int chain_ctrl_words();
 int patch_chain_check(vrt_plan *p);
 
+// ---- Ng acceleration of the Λ-iteration sessions (vrt_accel.hip) ----------------------------------------
+// the elements of an S array that take part: `dense` contiguous doubles (even), then `tail` doubles `tstride` apart
+struct NgRange {
+    int64_t dense = 0, tail = 0, tstride = 1;
+};
+// what a session keeps while acceleration is on (order 0: nothing allocated)
+struct NgState {
+    int order = 0, start = 0, period = 0;
+    double *hist[3] = {nullptr, nullptr, nullptr};      // S after the 1, 2, 3 iterates before the next due step (x1, x2, x3)
+    unsigned have = 0;                                  // bit d-1: hist[d-1] holds its iterate
+    double *d_ws = nullptr;                             // partial sums, sums, verdict
+    int last_applied = 0;                               // of the last iterate: 1 taken, 0 none due, -1 rejected
+    double last_sums[5] = {0, 0, 0, 0, 0}, last_coeffs[2] = {0, 0};
+};
+int ng_check_settings(int order, int start, int period);
+int ng_configure(NgState &ng, int order, int start, int period, size_t alloc_count);
+void ng_release(NgState &ng);
+int ng_after_iterate(NgState &ng, int64_t iterate, double *&S, size_t alloc_count, const NgRange &rg, hipStream_t st);
+int ng_report(const NgState &ng, int *applied, double sums[5], double coeffs[2]);
+int launch_ng_mirror(vrt_grid *g, int64_t nlam, const double *dS_up, double *dS_down, hipStream_t st);
+
 }  // namespace vrt

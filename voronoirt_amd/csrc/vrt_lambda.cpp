@@ -153,7 +153,18 @@ struct vrt_lambda {
     // the loop; d_S_new / d_S_old / d_J (the caller's layout) then exist only while vrt_lambda_get fills them
     bool native = false;
     double *d_S_nat[2] = {nullptr, nullptr}, *d_J_nat[2] = {nullptr, nullptr}, *d_B_up = nullptr;
+    NgState ng;                         // vrt_lambda_set_acceleration (off: nothing allocated, nothing run)
 };
+
+// the S buffer a session's acceleration works on: doubles allocated, and which of them are physical entries
+static size_t lambda_S_count(const vrt_lambda *s, NgRange *rg)
+{
+    const int64_t n = s->n, nlam = s->nlam;
+    if (rg) { rg->dense = (nlam / 2) * 2 * n; rg->tail = nlam & 1 ? n : 0; rg->tstride = 2; }
+    if (s->native) return (size_t)vrt_plan_native_plane_count(s->p, nlam);
+    if (rg) { rg->dense = (n * nlam) & ~(int64_t)1; rg->tail = (n * nlam) & 1; rg->tstride = 1; }
+    return (size_t)(n * nlam);
+}
 
 static void lambda_free(vrt_lambda *s)
 {
@@ -164,6 +175,7 @@ static void lambda_free(vrt_lambda *s)
                       s->d_S_nat[1], s->d_J_nat[0], s->d_J_nat[1], s->d_B_up})
         if (q) (void)hipFree(q);
     if (s->d_scalars) (void)hipFree(s->d_scalars);
+    ng_release(s->ng);
     delete s;
 }
 
@@ -441,8 +453,40 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
         std::memcpy(&d, &h[0], sizeof(double));
         *max_rel_change = h[1] ? std::nan("") : d;
         s->iterations++;
+        if (s->ng.order) {
+            // history copy or Ng step on the S of the plain update (the up-order copy); an accepted x_acc becomes that copy
+            // and the down-order copy is rewritten from it, value for value
+            NgRange rg;
+            const size_t count = lambda_S_count(s, &rg);
+            double *&S = s->native ? s->d_S_nat[0] : s->d_S_new;
+            if ((rc = ng_after_iterate(s->ng, s->iterations, S, count, rg, st))) return rc;
+            if (s->ng.last_applied == 1 && s->native) {
+                if ((rc = launch_ng_mirror(g, nlam, s->d_S_nat[0], s->d_S_nat[1], st))) return rc;
+                VRT_HIP_TRY(hipStreamSynchronize(st));
+            }
+        } else
+            s->ng.last_applied = 0;
         return VRT_OK;
     });
+}
+
+int vrt_lambda_set_acceleration(vrt_lambda *s, int order, int start, int period)
+{
+    if (!s) return fail(VRT_EINVAL, "NULL session");
+    int rc = ng_check_settings(order, start, period);
+    if (rc) return rc;
+    return guarded([&] {
+        vrt_plan *p = s->p;
+        std::lock_guard<std::mutex> lock(p->mu);
+        if ((rc = use_device(p->g->device))) return rc;
+        return ng_configure(s->ng, order, start, period, lambda_S_count(s, nullptr));
+    });
+}
+
+int vrt_lambda_last_acceleration(const vrt_lambda *s, int *applied, double sums[5], double coeffs[2])
+{
+    if (!s || !applied) return fail(VRT_EINVAL, "NULL argument");
+    return ng_report(s->ng, applied, sums, coeffs);
 }
 
 int vrt_lambda_get(vrt_lambda *s, double *J, double *S, double *populations, double *R, double *gamma)

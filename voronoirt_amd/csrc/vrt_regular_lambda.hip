@@ -297,8 +297,11 @@ struct vrt_regular_lambda {
     // plane-major, wavelength slowest
     DevBuf<double> d_S_pl, d_J_pl, d_I0_pl, d_zero;
     DevBuf<unsigned long long> d_scalars;
+    int64_t iterations = 0;
+    NgState ng;                         // vrt_regular_lambda_set_acceleration (off: nothing allocated, nothing run)
     ~vrt_regular_lambda()
     {
+        ng_release(ng);
         if (st) (void)hipStreamDestroy(st);
     }
 };
@@ -479,8 +482,39 @@ int vrt_regular_lambda_iterate(vrt_regular_lambda *s, double *max_rel_change)
         std::memcpy(&d, &h[0], sizeof(double));
         *max_rel_change = h[1] ? std::nan("") : d;
         r->timed = false;                                    // (the handle's events saw only the last chunk)
+        s->iterations++;
+        if (s->ng.order) {
+            // history copy or Ng step on the S of the plain update; an accepted x_acc becomes d_S[sc], and the plane-major
+            // copy the next solves read is made again from it
+            NgRange rg;
+            rg.dense = (n * nlam) & ~(int64_t)1; rg.tail = (n * nlam) & 1; rg.tstride = 1;
+            if ((rc = ng_after_iterate(s->ng, s->iterations, s->d_S[s->sc].p, (size_t)(n * nlam), rg, st))) return rc;
+            if (s->ng.last_applied == 1) {
+                if ((rc = launch_to_planes(r, nlam, s->d_S[s->sc], s->d_S_pl, st))) return rc;
+                VRT_HIP_TRY(hipStreamSynchronize(st));
+            }
+        } else
+            s->ng.last_applied = 0;
         return VRT_OK;
     });
+}
+
+int vrt_regular_lambda_set_acceleration(vrt_regular_lambda *s, int order, int start, int period)
+{
+    if (!s) return fail(VRT_EINVAL, "NULL session");
+    int rc = ng_check_settings(order, start, period);
+    if (rc) return rc;
+    return guarded([&] {
+        if ((rc = use_device(s->device))) return rc;
+        VRT_HIP_TRY(hipStreamSynchronize(s->st));
+        return ng_configure(s->ng, order, start, period, (size_t)(s->n * s->nlam));
+    });
+}
+
+int vrt_regular_lambda_last_acceleration(const vrt_regular_lambda *s, int *applied, double sums[5], double coeffs[2])
+{
+    if (!s || !applied) return fail(VRT_EINVAL, "NULL argument");
+    return ng_report(s->ng, applied, sums, coeffs);
 }
 
 int vrt_regular_lambda_get(vrt_regular_lambda *s, double *J, double *S, double *populations, double *R, double *gamma)
