@@ -680,6 +680,78 @@ int vrt_lambda_last_acceleration(const vrt_lambda *s, int *applied, double sums[
 int vrt_regular_lambda_last_acceleration(const vrt_regular_lambda *s, int *applied, double sums[5],
                                          double coeffs[2]);
 
+/* ---- the continuum scattering Λ-iteration on both grids (src/lambda_continuum.jl) --------------------------------------
+ * Λ_voronoi (:109-160) and Λ_regular (:58-107), the loop of the reference's production run (src/compare_continuum.jl), with
+ * library-owned device state: coherent scattering at nlam independent wavelengths (the reference: one, 500 nm), α_cont
+ * fixed over the iterations.  One iterate is one pass of the loop body (:145-150; :92-97 on the regular grid):
+ *   J = Σ_a w_a I_a(S_old)   J_λ_voronoi :27-56 / J_λ_regular :1-24.  I_0 of the up solves is B_0 -- not S -- of the bottom
+ *                            layer perm_up[1 : layers_up[2] - 1] per wavelength (:45-47), on the regular grid B_0's bottom
+ *                            plane (:16); the down solves start from zeros (:51, :19); θ = 90 adds nothing
+ *   S_new = (1 - ε) J + ε B_0   at EVERY entry (:148, :95), ε per (point, wavelength); operations and their order as
+ *                            vrt_lambda_update_dev
+ *   *max_rel_change = max |1 - S_old/S_new| over the THICK entries, ε > eps_thick (strict; thick = ε_λ .> 1e-4, :133, :80;
+ *                            criterion :162-198).  A NaN at a thick entry makes it NaN; a NaN at a thin entry is not seen
+ *                            (Julia indexes before it takes the maximum, :169, :188).  The first iterate compares with S = B_0.
+ * vrt_continuum_case: host arrays (nlam, n) Julia dims as vrt_line_case's B0, element [l + nlam * site]; n = the grid's
+ *   sites, or all nz nx ny points of a vrt_regular (ghost border included, Julia order i = iz + nz (ix + nx iy)).
+ *   vrt_continuum_case_check answers what create would say about the arrays, for n points, without any handle or device:
+ *   VRT_EINVAL for NULL pointers, nlam < 1, eps_thick not finite, α not finite or <= 0, ε outside [0, 1] or not finite,
+ *   B0 not finite, and for a case without a single thick entry (the reference's maximum over an empty set throws).
+ * vrt_continuum_create (p: a plan of the quadrature, weights[n_angles]) / vrt_regular_continuum_create (directions as
+ *   vrt_regular_lambda_create, whose direction checks apply; n_sweeps >= 1): upload the case, S = B_0.  Every argument is
+ *   checked before the device is touched.  The Voronoi session keeps S, J, B_0, ε and α in SWEEP ORDER
+ *   (vrt_plan_to_native_dev once at create, then vrt_plan_execute_native_dev with VRT_ALPHA_SITE_LAM_NATIVE and a masked
+ *   update on the plane sets per iterate: no layout change inside the loop); with VRT_LAMBDA_NATIVE=0, or on a plan
+ *   without a sweep-order form, it keeps the caller's layout (vrt_plan_execute_dev + vrt_continuum_update_dev's kernel).
+ *   Both give the same S, J and scalar bit for bit.  The regular session runs the chunked solves of vrt_regular_lambda_*
+ *   (VRT_REG_LAMBDA_BYTES) with ONE α array per wavelength shared by all angles; J is bit-identical for any chunking.
+ *   The sessions borrow p / r, which must outlive them.
+ * _get: J and S (nlam, n) of the last iterate, either may be NULL; before the first iterate J is zeros and S is B_0.
+ * _set_source: replaces S by a host array (nlam, n) -- a warm start, or the resume of a run of which only S was kept
+ *   (the recover_* use of src/recover_simulation.jl).  An S that is not finite or not > 0 somewhere: VRT_EINVAL, the
+ *   session untouched.  Drops any recorded Ng history; afterwards the session continues exactly as one that had reached
+ *   that S by iterating.
+ * _set_acceleration / _last_acceleration: the contract of vrt_lambda_set_acceleration above (order 0 or 2, start and
+ *   period >= 4, a step all or nothing with the positivity verdict, the returned scalar that of the plain update); the
+ *   sums run over all n nlam physical entries, thin ones included.  A session that never asks allocates and runs nothing
+ *   extra.
+ * vrt_continuum_update_dev: the masked update alone for a caller with its own device arrays on g's device: J, B, eps,
+ *   S_old, S_new (nlam, n) with leading dimension ld (eps per entry, unlike vrt_lambda_update_dev's eps[n]); S_new may
+ *   alias neither S_old nor J.  *n_thick (may be NULL) = the number of entries with eps > eps_thick; none: the scalar is
+ *   0.  Synchronises `stream`.
+ * There is NO multi-device continuum session: vrt_multi_lambda_* splits wavelength blocks over the devices, and the one
+ * wavelength of a continuum run cannot be split that way. */
+typedef struct vrt_continuum vrt_continuum;
+typedef struct vrt_regular_continuum vrt_regular_continuum;
+typedef struct vrt_continuum_case {
+    int64_t nlam;          /* >= 1; the reference uses 1 (500 nm).  Wavelengths are independent (coherent scattering) */
+    const double *alpha;   /* (nlam, n) α_cont = α_s + α_a (:128), fixed over the iterations; finite, > 0 */
+    const double *eps;     /* (nlam, n) ε = α_a / α_cont (:131) */
+    const double *B0;      /* (nlam, n) Planck function (:136); S starts as B0 */
+    double eps_thick;      /* the criterion sees only entries with eps > eps_thick (strict; the reference: 1e-4) */
+} vrt_continuum_case;
+int vrt_continuum_case_check(const vrt_continuum_case *cc, int64_t n);
+int vrt_continuum_create(vrt_plan *p, const vrt_continuum_case *cc, const double *weights, vrt_continuum **out);
+int vrt_continuum_iterate(vrt_continuum *s, double *max_rel_change);
+int vrt_continuum_get(vrt_continuum *s, double *J, double *S);
+int vrt_continuum_set_source(vrt_continuum *s, const double *S);
+int vrt_continuum_set_acceleration(vrt_continuum *s, int order, int start, int period);
+int vrt_continuum_last_acceleration(const vrt_continuum *s, int *applied, double sums[5], double coeffs[2]);
+void vrt_continuum_destroy(vrt_continuum *s);
+int vrt_regular_continuum_create(vrt_regular *r, int64_t n_angles, const double *k, const int *dirs,
+                                 const double *weights, const vrt_continuum_case *cc, int n_sweeps,
+                                 vrt_regular_continuum **out);
+int vrt_regular_continuum_iterate(vrt_regular_continuum *s, double *max_rel_change);
+int vrt_regular_continuum_get(vrt_regular_continuum *s, double *J, double *S);
+int vrt_regular_continuum_set_source(vrt_regular_continuum *s, const double *S);
+int vrt_regular_continuum_set_acceleration(vrt_regular_continuum *s, int order, int start, int period);
+int vrt_regular_continuum_last_acceleration(const vrt_regular_continuum *s, int *applied, double sums[5],
+                                            double coeffs[2]);
+void vrt_regular_continuum_destroy(vrt_regular_continuum *s);
+int vrt_continuum_update_dev(vrt_grid *g, int64_t nlam, int64_t ld, const double *dJ, const double *dB,
+                             const double *deps, double eps_thick, const double *dS_old, double *dS_new,
+                             double *max_rel_change, int64_t *n_thick, void *stream);
+
 /* ---- emergent spectra: opacity / source function, top-plane intensity, tau = 1 heights ------------------------------
  * The last step of a reference study (write_top_intensity, write_tau_unity and plotter, src/plot_utils.jl:61-140,
  * :297-355, :434-576) on a regular raster.  Plain numbers in one unit system, constants folded in by the caller.

@@ -15,7 +15,9 @@
 #     direct call sites in compare_searchlight.jl (:113,129,434),
 #   * `short_characteristics_up/down` (src/characteristics.jl:19-95, :110-180),
 #   * and adds `Λ_regular` (src/lambda_iteration.jl:116-205) over vrt_regular_lambda_*: the regular half of the
-#     comparison with the same device-resident loop.
+#     comparison with the same device-resident loop,
+#   * and the 4-argument `Λ_voronoi` / `Λ_regular` of src/lambda_continuum.jl:109-160, :58-107 (the continuum scattering
+#     loop of compare_continuum.jl) over vrt_continuum_* / vrt_regular_continuum_*: `Λ_continuum`, `Λ_continuum_regular`.
 # The physics that produces S, α and I_0 (γ, damping, Voigt profile, αline_λ, B_λ) stays in Julia
 # exactly as the reference writes it; only the formal solves leave the process.
 #
@@ -479,6 +481,142 @@ function J_continuum(S_λ::AbstractVector, α_cont::AbstractVector, sites::Voron
     return vec(J) * I_unit
 end
 
+# ---- Λ_voronoi / Λ_regular, continuum case: src/lambda_continuum.jl:109-160, :58-107 ------------------------
+# vrt_continuum_case of include/voronoirt.h
+struct ContinuumCase
+    nlam::Int64
+    alpha::Ptr{Float64}
+    eps::Ptr{Float64}
+    B0::Ptr{Float64}
+    eps_thick::Float64
+end
+
+# the loop shared by both grids: `prefix` is :vrt_continuum_ or :vrt_regular_continuum_ spelled out (a ccall's symbol
+# must be a literal), so the two callers pass closures
+function continuum_loop(ϵ, maxiter, iterate, fetch, last_acc, ng)
+    i = 0
+    diff = Ref{Float64}(1.0)                  # criterion(S_new = B_0, S_old = 0) = 1 (:145, :92)
+    ng_applied = Ref{Cint}(0); ng_coeffs = zeros(2)
+    println("Iteration 1...")
+    while diff[] > ϵ && i < maxiter           # criterion: diff > ϵ && i < maxiter (:178, :197)
+        check(iterate(diff))
+        isnan(diff[]) && println("NaN DIFF!")
+        println("   Rel. diff.: $(diff[])")
+        if ng !== nothing
+            check(last_acc(ng_applied, ng_coeffs))
+            ng_applied[] != 0 && println("   Ng step ", ng_applied[] == 1 ? "taken" : "rejected", ": a = $(ng_coeffs[1]), b = $(ng_coeffs[2])")
+        end
+        i += 1
+        println("Iteration $(i+1)...")
+    end
+    check(fetch())
+    println(i == maxiter ? "Did not converge inside scope" : "Converged in $i iterations")
+end
+
+"""
+    Λ_continuum(ϵ, maxiter, sites, quadrature; ng=nothing, S0=nothing) -> (J_new, S_new, α_cont)
+
+The reference's continuum Λ_voronoi (src/lambda_continuum.jl:109-160) with its loop on the device (vrt_continuum_*).
+What it derives before the loop -- LTE populations, α_s, α_a, ε_λ, B_0 at 500 nm (:116-137) -- comes from the reference's
+own functions; every iteration is vrt_continuum_iterate, whose scalar is the maximum over thick = ε_λ .> 1e-4.
+`ng = (start, period)`: vrt_continuum_set_acceleration; `S0`: a source function to resume from
+(vrt_continuum_set_source, the recover_* use of src/recover_simulation.jl).  Unrun: Julia is not installed where the
+library is built.
+"""
+function Λ_continuum(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, quadrature::String;
+                     ng::Union{Nothing,Tuple{Int,Int}}=nothing, S0=nothing)
+    println("---Iterating---")
+    λ = 500u"nm"
+    LTE_pops = VoronoiRT.LTE_populations(sites)
+    α_s = VoronoiRT.α_scattering.(λ, sites.electron_density * 1.0, LTE_pops[:, 1])
+    α_a = VoronoiRT.α_absorption.(λ, sites.temperature, sites.electron_density * 1.0,
+                                  LTE_pops[:, 1] .+ LTE_pops[:, 2], LTE_pops[:, 3])
+    α_cont = α_s + α_a
+    ε_λ = Vector{Float64}(α_a ./ α_cont)
+    B_0 = Vector{Float64}(ustrip.(I_unit, VoronoiRT.blackbody_λ.(λ, sites.temperature)))
+    αc = Vector{Float64}(ustrip.(u"m^-1", α_cont))
+    weights, = read_quadrature(quadrature)
+    w = Vector{Float64}(weights)
+    plan = plan_handle(sites, quadrature, 3)
+    n = length(B_0)
+    ses = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve αc ε_λ B_0 w begin
+        cc = Ref(ContinuumCase(1, pointer(αc), pointer(ε_λ), pointer(B_0), 1e-4))
+        check(ccall((:vrt_continuum_create, libvrt), Cint, (Ptr{Cvoid}, Ref{ContinuumCase}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                    plan, cc, w, ses))
+    end
+    if S0 !== nothing
+        S_in = Vector{Float64}(ustrip.(I_unit, S0))
+        check(ccall((:vrt_continuum_set_source, libvrt), Cint, (Ptr{Cvoid}, Ptr{Float64}), ses[], S_in))
+    end
+    ng !== nothing && check(ccall((:vrt_continuum_set_acceleration, libvrt), Cint, (Ptr{Cvoid}, Cint, Cint, Cint),
+                                  ses[], 2, ng[1], ng[2]))
+    J = Vector{Float64}(undef, n); S = Vector{Float64}(undef, n)
+    continuum_loop(ϵ, maxiter,
+                   d -> ccall((:vrt_continuum_iterate, libvrt), Cint, (Ptr{Cvoid}, Ref{Float64}), ses[], d),
+                   () -> ccall((:vrt_continuum_get, libvrt), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), ses[], J, S),
+                   (a, c) -> ccall((:vrt_continuum_last_acceleration, libvrt), Cint,
+                                   (Ptr{Cvoid}, Ref{Cint}, Ptr{Float64}, Ptr{Float64}), ses[], a, C_NULL, c), ng)
+    ccall((:vrt_continuum_destroy, libvrt), Cvoid, (Ptr{Cvoid},), ses[])
+    return J * I_unit, S * I_unit, α_cont
+end
+
+"""
+    Λ_continuum_regular(ϵ, maxiter, atmos, quadrature; ng=nothing, S0=nothing) -> (J_new, S_new, α_cont)
+
+The reference's continuum Λ_regular (src/lambda_continuum.jl:58-107) on the device (vrt_regular_continuum_*); `atmos` is
+the atmosphere the reference iterates on, every point of it a point of the loop.  (nz, nx, ny) arrays are
+vrt_continuum_case's (1, n) with n = nz nx ny.  Keywords as `Λ_continuum`.  Unrun.
+"""
+function Λ_continuum_regular(ϵ::AbstractFloat, maxiter::Integer, atmos, quadrature::String;
+                             ng::Union{Nothing,Tuple{Int,Int}}=nothing, S0=nothing)
+    λ = 500u"nm"
+    LTE_pops = VoronoiRT.LTE_populations(atmos)
+    α_s = VoronoiRT.α_scattering.(λ, atmos.electron_density * 1.0, LTE_pops[:, :, :, 1])
+    α_a = VoronoiRT.α_absorption.(λ, atmos.temperature, atmos.electron_density * 1.0,
+                                  LTE_pops[:, :, :, 1] .+ LTE_pops[:, :, :, 2], LTE_pops[:, :, :, 3])
+    α_cont = α_s + α_a
+    ε_λ = Array{Float64,3}(α_a ./ α_cont)
+    B_0 = Array{Float64,3}(ustrip.(I_unit, VoronoiRT.blackbody_λ.(λ, atmos.temperature)))
+    αc = Array{Float64,3}(ustrip.(u"m^-1", α_cont))
+    nz, nx, ny = size(B_0)
+    weights, θ_array, ϕ_array, n_angles = read_quadrature(quadrature)
+    k = Matrix{Float64}(undef, 3, n_angles)
+    for i in 1:n_angles
+        k[:, i] = direction(θ_array[i], ϕ_array[i])              # :14
+    end
+    dirs = Cint[θ > 90 ? 1 : (θ < 90 ? -1 : 0) for θ in θ_array]  # θ = 90 adds nothing (:15-21)
+    w = Vector{Float64}(weights)
+    z = Vector{Float64}(ustrip.(u"m", atmos.z)); x = Vector{Float64}(ustrip.(u"m", atmos.x))
+    y = Vector{Float64}(ustrip.(u"m", atmos.y))
+    reg = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve z x y check(ccall((:vrt_regular_create, libvrt), Cint,
+                                   (Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ref{Ptr{Cvoid}}),
+                                   nz, nx, ny, z, x, y, 0, reg))
+    ses = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve αc ε_λ B_0 k dirs w begin
+        cc = Ref(ContinuumCase(1, pointer(αc), pointer(ε_λ), pointer(B_0), 1e-4))
+        check(ccall((:vrt_regular_continuum_create, libvrt), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Cint}, Ptr{Float64}, Ref{ContinuumCase}, Cint, Ref{Ptr{Cvoid}}),
+                    reg[], n_angles, k, dirs, w, cc, 3, ses))
+    end
+    if S0 !== nothing
+        S_in = Array{Float64,3}(ustrip.(I_unit, S0))
+        check(ccall((:vrt_regular_continuum_set_source, libvrt), Cint, (Ptr{Cvoid}, Ptr{Float64}), ses[], S_in))
+    end
+    ng !== nothing && check(ccall((:vrt_regular_continuum_set_acceleration, libvrt), Cint, (Ptr{Cvoid}, Cint, Cint, Cint),
+                                  ses[], 2, ng[1], ng[2]))
+    J = Array{Float64,3}(undef, nz, nx, ny); S = Array{Float64,3}(undef, nz, nx, ny)
+    continuum_loop(ϵ, maxiter,
+                   d -> ccall((:vrt_regular_continuum_iterate, libvrt), Cint, (Ptr{Cvoid}, Ref{Float64}), ses[], d),
+                   () -> ccall((:vrt_regular_continuum_get, libvrt), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), ses[], J, S),
+                   (a, c) -> ccall((:vrt_regular_continuum_last_acceleration, libvrt), Cint,
+                                   (Ptr{Cvoid}, Ref{Cint}, Ptr{Float64}, Ptr{Float64}), ses[], a, C_NULL, c), ng)
+    ccall((:vrt_regular_continuum_destroy, libvrt), Cvoid, (Ptr{Cvoid},), ses[])
+    ccall((:vrt_regular_destroy, libvrt), Cvoid, (Ptr{Cvoid},), reg[])
+    return J * I_unit, S * I_unit, α_cont
+end
+
 # ---- single solves: src/irregular_ray_tracing.jl:15-20, :96-101 ----------------------------------
 # literal-symbol wrappers (the name/library tuple of a ccall must not reference a local variable)
 c_delaunay_up(g, k, S, I0, α, n_sweeps, I) =
@@ -633,6 +771,11 @@ VoronoiRT.J_λ_voronoi(S_λ::AbstractArray, α_cont::AbstractArray, sites::Voron
 VoronoiRT.Λ_voronoi(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiRT.VoronoiSites, line::VoronoiRT.HydrogenicLine,
                     quadrature::String, DATA::String) =
     VoronoiRTHip.Λ(ϵ, maxiter, sites, line, quadrature, DATA)
+# the continuum drivers of compare_continuum.jl (src/lambda_continuum.jl:109-160, :58-107): the 4-argument methods
+VoronoiRT.Λ_voronoi(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiRT.VoronoiSites, quadrature::String) =
+    VoronoiRTHip.Λ_continuum(ϵ, maxiter, sites, quadrature)
+VoronoiRT.Λ_regular(ϵ::AbstractFloat, maxiter::Integer, atmos::VoronoiRT.Atmosphere, quadrature::String) =
+    VoronoiRTHip.Λ_continuum_regular(ϵ, maxiter, atmos, quadrature)
 # preprocessing (compare_line.jl:100, compare_continuum.jl, compare_searchlight.jl): the executable's
 # path is ignored, the tessellation runs inside the library
 VoronoiRT.voro(voro_executable::String, sites_file::String, neighbours_file::String,

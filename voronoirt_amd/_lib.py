@@ -36,6 +36,11 @@ class LineCaseStruct(ctypes.Structure):
                 ("hc_over_kB", c_dbl), ("pref_ij", c_dbl), ("pref_ji", c_dbl)]
 
 
+class ContinuumCaseStruct(ctypes.Structure):
+    """vrt_continuum_case of include/voronoirt.h"""
+    _fields_ = [("nlam", c_i64), ("alpha", p_dbl), ("eps", p_dbl), ("B0", p_dbl), ("eps_thick", c_dbl)]
+
+
 # name -> (restype, argtypes): every symbol include/voronoirt.h declares
 PROTOTYPES = {
     "vrt_last_error": (ctypes.c_char_p, []),
@@ -178,6 +183,23 @@ PROTOTYPES = {
     "vrt_regular_lambda_set_acceleration": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vrt_lambda_last_acceleration": (ctypes.c_int, [vp, p_int, p_dbl, p_dbl]),
     "vrt_regular_lambda_last_acceleration": (ctypes.c_int, [vp, p_int, p_dbl, p_dbl]),
+    "vrt_continuum_case_check": (ctypes.c_int, [ctypes.POINTER(ContinuumCaseStruct), c_i64]),
+    "vrt_continuum_create": (ctypes.c_int, [vp, ctypes.POINTER(ContinuumCaseStruct), p_dbl, ctypes.POINTER(vp)]),
+    "vrt_continuum_iterate": (ctypes.c_int, [vp, p_dbl]),
+    "vrt_continuum_get": (ctypes.c_int, [vp, p_dbl, p_dbl]),
+    "vrt_continuum_set_source": (ctypes.c_int, [vp, p_dbl]),
+    "vrt_continuum_set_acceleration": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "vrt_continuum_last_acceleration": (ctypes.c_int, [vp, p_int, p_dbl, p_dbl]),
+    "vrt_continuum_destroy": (None, [vp]),
+    "vrt_regular_continuum_create": (ctypes.c_int, [vp, c_i64, p_dbl, p_int, p_dbl, ctypes.POINTER(ContinuumCaseStruct),
+                                                    ctypes.c_int, ctypes.POINTER(vp)]),
+    "vrt_regular_continuum_iterate": (ctypes.c_int, [vp, p_dbl]),
+    "vrt_regular_continuum_get": (ctypes.c_int, [vp, p_dbl, p_dbl]),
+    "vrt_regular_continuum_set_source": (ctypes.c_int, [vp, p_dbl]),
+    "vrt_regular_continuum_set_acceleration": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "vrt_regular_continuum_last_acceleration": (ctypes.c_int, [vp, p_int, p_dbl, p_dbl]),
+    "vrt_regular_continuum_destroy": (None, [vp]),
+    "vrt_continuum_update_dev": (ctypes.c_int, [vp, c_i64, c_i64, vp, vp, vp, c_dbl, vp, vp, p_dbl, p_i64, vp]),
     "vrt_delaunay_up": (ctypes.c_int, [vp, p_dbl, p_dbl, p_dbl, c_i64, p_dbl, ctypes.c_int, p_dbl]),
     "vrt_delaunay_down": (ctypes.c_int, [vp, p_dbl, p_dbl, p_dbl, c_i64, p_dbl, ctypes.c_int, p_dbl]),
 }
@@ -211,7 +233,13 @@ def load() -> ctypes.CDLL:
             pass
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in PROTOTYPES.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:
+            # an older build selected with VRT_LIB_PATH (the A/B of tools/ab_libs.sh, tools/continuum_probe.py --bare)
+            # lacks the newer entries: calling one of them fails; the product library must have every one
+            if os.environ.get("VRT_LIB_PATH"):
+                continue
+            raise AttributeError(f"{LIB_PATH} does not export {name}")
         fn.restype = res
         fn.argtypes = args
     _lib = lib

@@ -1511,3 +1511,134 @@ def Lambda_regular(eps_conv: float, maxiter: int, z, x, y, case: LineCase, quadr
         if h:
             L.vrt_regular_lambda_destroy(h)
         solver.close()
+
+
+# ---- the continuum scattering Λ-iteration on both grids (src/lambda_continuum.jl) -------------------------------------
+class ContinuumCase:
+    """The inputs Λ_voronoi / Λ_regular of src/lambda_continuum.jl derive before their loop (:116-137, :63-84), as plain
+    numbers: `alpha` α_cont = α_s + α_a, `eps` ε = α_a / α_cont and `B0` the Planck function, each (n, nλ) -- or (n,) for
+    the reference's single wavelength -- and `eps_thick`: the criterion sees only entries with ε > eps_thick (the
+    reference: 1e-4)."""
+
+    def __init__(self, alpha, eps, B0, eps_thick: float = 1e-4):
+        two = lambda a: (lambda b: b.reshape(-1, 1) if b.ndim == 1 else b)(_f64(a))
+        self.alpha, self.eps, self.B0 = two(alpha), two(eps), two(B0)
+        self.eps_thick = float(eps_thick)
+        if not (self.alpha.shape == self.eps.shape == self.B0.shape) or self.B0.ndim != 2:
+            raise ValueError("ContinuumCase: alpha, eps and B0 must share one (n, nlam) shape")
+
+    @property
+    def n(self) -> int:
+        return self.B0.shape[0]
+
+    @property
+    def nlam(self) -> int:
+        return self.B0.shape[1]
+
+    def thick(self) -> np.ndarray:
+        return self.eps > self.eps_thick
+
+    def c_struct(self):
+        cc = _lib.ContinuumCaseStruct()
+        cc.nlam = self.nlam
+        cc.alpha, cc.eps, cc.B0 = _d(self.alpha), _d(self.eps), _d(self.B0)
+        cc.eps_thick = self.eps_thick
+        return cc
+
+    def check(self) -> None:
+        """`vrt_continuum_case_check`: raises VrtError for what a session would refuse; needs no device"""
+        cc = self.c_struct()
+        check(_lib.load().vrt_continuum_case_check(ctypes.byref(cc), self.n))
+
+
+def continuum_update_dev(sites: VoronoiSites, J, B, eps, S_old, S_new, eps_thick: float = 1e-4, nlam: int | None = None):
+    """The masked update of the continuum Λ-iteration (`vrt_continuum_update_dev`) on torch tensors of sites' device,
+    each (n, ld) float64 and contiguous: S_new = (1 - ε) J + ε B at every entry of the first `nlam` columns (default:
+    all), and the criterion max |1 - S_old/S_new| over the entries with ε > eps_thick (lambda_continuum.jl:148, :188).
+    Returns (that maximum -- NaN if a thick entry's term is NaN --, the number of thick entries); synchronises."""
+    import torch
+    n, ld = S_new.shape
+    for t in (J, B, eps, S_old, S_new):
+        if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != (n, ld):
+            raise ValueError("continuum_update_dev: contiguous float64 tensors of one (n, ld) shape")
+    out, cnt = ctypes.c_double(), ctypes.c_int64()
+    st = torch.cuda.current_stream(S_new.device).cuda_stream
+    check(_lib.load().vrt_continuum_update_dev(sites.handle, int(ld if nlam is None else nlam), int(ld), J.data_ptr(),
+                                               B.data_ptr(), eps.data_ptr(), float(eps_thick), S_old.data_ptr(),
+                                               S_new.data_ptr(), ctypes.byref(out), ctypes.byref(cnt), st or None))
+    return out.value, int(cnt.value)
+
+
+def _continuum_loop(L, prefix: str, h, case: ContinuumCase, eps_conv: float, maxiter: int, ng, S0, who: str):
+    fn = lambda name: getattr(L, prefix + name)
+    steps, history, diff, i = [], [], 1.0, 0                   # criterion(S_new = B, S_old = 0) = 1
+    if S0 is not None:
+        S0 = _f64(S0).reshape(case.n, case.nlam)
+        check(fn("set_source")(h, _d(S0)))
+    if ng is not None:
+        check(fn("set_acceleration")(h, 2, *_ng_settings(ng)))
+    while diff > eps_conv and i < maxiter:                     # criterion: diff > ϵ && i < maxiter, :178, :197
+        d = ctypes.c_double()
+        check(fn("iterate")(h, ctypes.byref(d)))
+        diff = d.value
+        history.append(diff)
+        i += 1
+        if ng is not None:
+            _ng_last(fn("last_acceleration"), h, i, steps)
+        if diff != diff:
+            import warnings
+            warnings.warn(f"{who}: NaN DIFF! at iteration {i} -- stopping, results are not converged")
+    J, S = np.zeros((case.n, case.nlam)), np.zeros((case.n, case.nlam))
+    check(fn("get")(h, _d(J), _d(S)))
+    return (J, S, history) if ng is None else (J, S, history, steps)
+
+
+def Lambda_continuum(eps_conv: float, maxiter: int, sites: VoronoiSites, case: ContinuumCase, quadrature: str, ng=None,
+                     S0=None, native: bool = True, n_sweeps: int = 3):
+    """Λ_voronoi of src/lambda_continuum.jl:109-160 with library-owned device state (`vrt_continuum_create` /
+    `_iterate` / `_get`): one call per iteration, only the criterion's scalar -- the maximum over the thick entries --
+    comes back inside the loop.  Starts from S = B_0, or from S0 (n, nλ) (`vrt_continuum_set_source`: a warm start or a
+    resumed run).  native=False keeps the caller's layout inside the session (VRT_LAMBDA_NATIVE=0): the same bits.
+    Returns (J, S_new, history); ng=(start, period) as for `Lambda_voronoi_host`, with the list of (iterate, applied, a,
+    b) as a fourth element."""
+    L = _lib.load()
+    if case.n != sites.n:
+        raise ValueError(f"the continuum case has {case.n} points, the grid {sites.n}")
+    if native:
+        plan, w = _quadrature_plan(sites, quadrature, n_sweeps)
+        own = None
+    else:                                                      # (the option is read when the session is created)
+        w, th, ph, _ = read_quadrature(quadrature)
+        own = plan = FormalPlan(sites, quadrature_directions(th, ph), n_sweeps,
+                                dirs=[1 if t > 90 else (-1 if t < 90 else 0) for t in th])
+        plan.set_option("VRT_LAMBDA_NATIVE", 0)
+    cc = case.c_struct()
+    h = ctypes.c_void_p()
+    try:
+        check(L.vrt_continuum_create(plan._h, ctypes.byref(cc), _d(_f64(w)), ctypes.byref(h)))
+        return _continuum_loop(L, "vrt_continuum_", h, case, eps_conv, maxiter, ng, S0, "Lambda_continuum")
+    finally:
+        if h:
+            L.vrt_continuum_destroy(h)
+        if own is not None:
+            own.close()
+
+
+def Lambda_continuum_regular(eps_conv: float, maxiter: int, z, x, y, case: ContinuumCase, quadrature: str, ng=None,
+                             S0=None, n_sweeps: int = 3, device: int = 0):
+    """Λ_regular of src/lambda_continuum.jl:58-107 with library-owned device state (`vrt_regular_continuum_*`).  z, x, y
+    are the raster's axes with the periodic ghost border; every one of its nz nx ny points is a point of `case` (Julia
+    order i = iz + nz (ix + nx iy), i.e. numpy (ny, nx, nz) flattened).  Otherwise as `Lambda_continuum`."""
+    L = _lib.load()
+    w, k, dirs = _regular_directions(quadrature)
+    solver = _regular_solver(z, x, y, case.n, device)
+    cc = case.c_struct()
+    h = ctypes.c_void_p()
+    try:
+        check(L.vrt_regular_continuum_create(solver._h, k.shape[0], _d(k), dirs.ctypes.data_as(_lib.p_int), _d(w),
+                                             ctypes.byref(cc), int(n_sweeps), ctypes.byref(h)))
+        return _continuum_loop(L, "vrt_regular_continuum_", h, case, eps_conv, maxiter, ng, S0, "Lambda_continuum_regular")
+    finally:
+        if h:
+            L.vrt_regular_continuum_destroy(h)
+        solver.close()

@@ -859,7 +859,7 @@ static int lambda_update_call(vrt_grid *g, double *max_rel_change, hipStream_t s
     int rc = use_device(g->device);
     if (rc) return rc;
     std::lock_guard<std::mutex> lock(g->mu);
-    if (!g->d_scalars && (rc = dev_alloc(&g->d_scalars, 2))) return rc;
+    if (!g->d_scalars && (rc = dev_alloc(&g->d_scalars, kUpdateWords))) return rc;
     unsigned long long *d_res = g->d_scalars;
     rc = launch(d_res);
     unsigned long long h[2] = {0, 0};

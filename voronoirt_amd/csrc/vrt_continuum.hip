@@ -1,0 +1,671 @@
+// The continuum scattering Λ-iteration on the device, on both grids: Λ_voronoi and Λ_regular of src/lambda_continuum.jl
+// (:109-160, :58-107; J_λ_voronoi :27-56, J_λ_regular :1-24; criterion :162-198), the loop of the reference's production
+// run (src/compare_continuum.jl).  Coherent scattering at nlam independent wavelengths (the reference: one, 500 nm):
+//   J = Σ_a w_a I_a(S_old)          I_0 of the up solves = B_0 of the bottom layer / plane, down solves from zeros
+//   S_new = (1 - ε) J + ε B_0       at EVERY entry, ε per (point, wavelength)
+//   diff = max |1 - S_old / S_new|  over the THICK entries only (ε > eps_thick; the reference: ε_λ .> 1e-4)
+//
+//   vrt_continuum_update_dev       the masked update alone, caller layout (k_continuum_update)
+//   vrt_continuum_*                the loop on a vrt_plan with library-owned device state: S, J, B_0, ε and α in sweep
+//                                  order (vrt_plan_execute_native_dev's plane sets, α as VRT_ALPHA_SITE_LAM_NATIVE; the
+//                                  update is k_continuum_update_native), or -- VRT_LAMBDA_NATIVE=0, a plan without a
+//                                  sweep-order form -- in the caller's layout through k_continuum_update; S, J and the
+//                                  scalar are the same bits either way
+//   vrt_regular_continuum_*        the loop on a vrt_regular: the chunked solve of vrt_regular_lambda.hip with one α array
+//                                  per wavelength shared by all angles, J reduced in quadrature order, the masked update
+//                                  on the raster in the caller's layout
+// The update's operations and their order are those of k_lambda_update (vrt_kernels.hip); Ng acceleration is that of
+// vrt_accel.hip (ng_after_iterate), over all n nlam physical entries, thin ones included.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "vrt_device.h"
+#include "vrt_regular.h"
+
+namespace vrt {
+namespace {
+
+// the criterion of one thread: maximum and NaN flag over its thick entries, and how many those were
+struct Crit {
+    double d = 0.0;
+    bool nan_ = false;
+    unsigned thick = 0;
+};
+
+// Julia indexes with `thick` BEFORE it takes the maximum (lambda_continuum.jl:169, :188): a thin entry is not seen at all,
+// a NaN at a thick one makes the maximum NaN
+__device__ __forceinline__ void crit_entry(Crit &c, double e, double eps_thick, double s_old, double s_new)
+{
+    if (!(e > eps_thick)) return;
+    c.thick++;
+    const double dd = fabs(1.0 - s_old / s_new);
+    if (!(dd == dd)) c.nan_ = true;
+    else c.d = fmax(c.d, dd);
+}
+
+// per wave with shuffles, then ONE integer atomic per workgroup and word (256 threads): the maximum on the IEEE bits
+// (all candidates are >= 0), the NaN flag, the thick count
+__device__ __forceinline__ void crit_reduce(const Crit &c, unsigned long long *__restrict__ result)
+{
+    __shared__ double wmax[4];
+    __shared__ int wnan[4];
+    __shared__ unsigned wcnt[4];
+    double d = c.d;
+    unsigned cnt = c.thick;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        d = fmax(d, __shfl_xor(d, off, 64));
+        cnt += (unsigned)__shfl_xor((int)cnt, off, 64);
+    }
+    const unsigned long long any_nan = __ballot(c.nan_);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { wmax[wave] = d; wnan[wave] = any_nan != 0ull; wcnt[wave] = cnt; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double m = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3]));
+        atomicMax(&result[0], (unsigned long long)__double_as_longlong(m));
+        if (wnan[0] | wnan[1] | wnan[2] | wnan[3]) atomicMax(&result[1], 1ull);
+        atomicAdd(&result[2], (unsigned long long)wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3]);
+    }
+}
+
+// caller layout: J, B, eps, S (n, ld) rows, wavelength fastest; grid-stride over the n nlam entries
+__global__ void __launch_bounds__(256)
+k_continuum_update(int64_t n, int64_t nlam, int64_t ld, const double *__restrict__ J, const double *__restrict__ B,
+                   const double *__restrict__ eps, double eps_thick, const double *__restrict__ S_old,
+                   double *__restrict__ S_new, unsigned long long *__restrict__ result /* max bits, NaN flag, thick count */)
+{
+    const int64_t total = n * nlam;
+    Crit c;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t site = t / nlam, l = t - site * nlam;
+        const size_t o = (size_t)site * ld + l;
+        const double e = eps[o];
+        const double s_new = (1.0 - e) * J[o] + e * B[o];
+        S_new[o] = s_new;
+        crit_entry(c, e, eps_thick, S_old[o], s_new);
+    }
+    crit_reduce(c, result);
+}
+
+// Sweep-order plane sets ([pair][pos][2] per direction): one thread per UP position walks the wavelength pairs.  J = J_up +
+// J_down as k_combine_J forms it, B and ε from the up plane set, the old S read from the up plane it is written back to,
+// the down-order copy of S_new written beside it: the operations of k_continuum_update on the same values.  An odd nlam
+// carries its padding wavelength as zeros, outside both the criterion and the thick count.
+__global__ void __launch_bounds__(256)
+k_continuum_update_native(int64_t n, int npair, int nlam, const int32_t *__restrict__ store_up,
+                          const int32_t *__restrict__ rank_down, const double2 *__restrict__ Ju,
+                          const double2 *__restrict__ Jd, const double2 *__restrict__ Bu, const double2 *__restrict__ Eu,
+                          double eps_thick, double2 *__restrict__ Su, double2 *__restrict__ Sd,
+                          unsigned long long *__restrict__ result)
+{
+    Crit c;
+    for (int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pos < n; pos += (int64_t)gridDim.x * blockDim.x) {
+        const size_t pd = (size_t)rank_down[store_up[pos]];
+        constexpr int U = 2;                                // (five loads per pair: two pairs in flight; the continuum has few)
+        for (int q0 = 0; q0 < npair; q0 += U) {
+            double2 J[U], B[U], E[U], So[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int q = q0 + u < npair ? q0 + u : npair - 1;
+                const size_t t = (size_t)q * (size_t)n + (size_t)pos;
+                const double2 jd = Jd[(size_t)q * (size_t)n + pd];
+                J[u] = Ju[t];
+                J[u].x = J[u].x + jd.x; J[u].y = J[u].y + jd.y;
+                B[u] = Bu[t];
+                E[u] = Eu[t];
+                So[u] = Su[t];
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int q = q0 + u;
+                if (q >= npair) break;
+                const size_t t = (size_t)q * (size_t)n + (size_t)pos;
+                double2 Sn;
+                Sn.x = (1.0 - E[u].x) * J[u].x + E[u].x * B[u].x;
+                Sn.y = (1.0 - E[u].y) * J[u].y + E[u].y * B[u].y;
+                const bool second = 2 * q + 1 < nlam;
+                if (!second) Sn.y = 0.0;
+                Su[t] = Sn;
+                Sd[(size_t)q * (size_t)n + pd] = Sn;
+                crit_entry(c, E[u].x, eps_thick, So[u].x, Sn.x);
+                if (second) crit_entry(c, E[u].y, eps_thick, So[u].y, Sn.y);
+            }
+        }
+    }
+    crit_reduce(c, result);
+}
+
+int launch_continuum_update(int64_t n, int64_t nlam, int64_t ld, const double *dJ, const double *dB, const double *deps,
+                            double eps_thick, const double *dS_old, double *dS_new, unsigned long long *d_result,
+                            hipStream_t st)
+{
+    VRT_HIP_TRY(hipMemsetAsync(d_result, 0, 3 * sizeof(unsigned long long), st));
+    const int64_t blocks = std::min<int64_t>((n * nlam + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(k_continuum_update, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, n, nlam, ld, dJ, dB,
+                       deps, eps_thick, dS_old, dS_new, d_result);
+    VRT_HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+int launch_continuum_update_native(vrt_grid *g, int64_t nlam, const double *dJ_up, const double *dJ_down, const double *dB_up,
+                                   const double *dE_up, double eps_thick, double *dS_up, double *dS_down,
+                                   unsigned long long *d_result, hipStream_t st)
+{
+    VRT_HIP_TRY(hipMemsetAsync(d_result, 0, 3 * sizeof(unsigned long long), st));
+    const int npair = (int)((nlam + 1) / 2);
+    const int64_t blocks = std::min<int64_t>((g->n + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(k_continuum_update_native, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, g->n, npair,
+                       (int)nlam, g->up.d_store, g->down.d_srank, reinterpret_cast<const double2 *>(dJ_up),
+                       reinterpret_cast<const double2 *>(dJ_down), reinterpret_cast<const double2 *>(dB_up),
+                       reinterpret_cast<const double2 *>(dE_up), eps_thick, reinterpret_cast<double2 *>(dS_up),
+                       reinterpret_cast<double2 *>(dS_down), d_result);
+    VRT_HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+// the three words of an update -> the criterion's scalar (NaN like Julia's maximum) and the thick count; synchronises st
+int read_criterion(const unsigned long long *d_result, hipStream_t st, double *max_rel_change, int64_t *n_thick)
+{
+    unsigned long long h[3] = {0, 0, 0};
+    VRT_HIP_TRY(hipMemcpyAsync(h, d_result, sizeof(h), hipMemcpyDeviceToHost, st));
+    VRT_HIP_TRY(hipStreamSynchronize(st));
+    double d;
+    std::memcpy(&d, &h[0], sizeof(double));
+    *max_rel_change = h[1] ? std::nan("") : d;
+    if (n_thick) *n_thick = (int64_t)h[2];
+    return VRT_OK;
+}
+
+// ---- host checks, before the device is touched ------------------------------------------------------------------------
+int check_case(const vrt_continuum_case *cc, int64_t n)
+{
+    if (!cc) return fail(VRT_EINVAL, "the continuum case is NULL");
+    if (cc->nlam < 1) return fail(VRT_EINVAL, "nlam must be >= 1");
+    if (!cc->alpha || !cc->eps || !cc->B0) return fail(VRT_EINVAL, "NULL array in the continuum case");
+    if (!std::isfinite(cc->eps_thick)) return fail(VRT_EINVAL, "eps_thick must be finite");
+    if (n < 1) return fail(VRT_EINVAL, "the case needs at least one point");
+    const int64_t total = n * cc->nlam;
+    int64_t thick = 0;
+    for (int64_t i = 0; i < total; i++) {
+        const double a = cc->alpha[i], e = cc->eps[i];
+        if (!std::isfinite(a) || !(a > 0.0)) return fail(VRT_EINVAL, "alpha must be finite and > 0 everywhere");
+        if (!(e >= 0.0 && e <= 1.0)) return fail(VRT_EINVAL, "eps must lie in [0, 1] everywhere");
+        if (!std::isfinite(cc->B0[i])) return fail(VRT_EINVAL, "B0 must be finite everywhere");
+        thick += e > cc->eps_thick;
+    }
+    // (the reference's maximum over an empty set throws, lambda_continuum.jl:169)
+    if (!thick) return fail(VRT_EINVAL, "no entry has eps > eps_thick: the criterion would be a maximum over nothing");
+    return VRT_OK;
+}
+
+int check_source(const double *S, int64_t count)
+{
+    for (int64_t i = 0; i < count; i++)
+        if (!std::isfinite(S[i]) || !(S[i] > 0.0)) return fail(VRT_EINVAL, "S must be finite and > 0 everywhere");
+    return VRT_OK;
+}
+
+int upload(DevBuf<double> &d, const double *h, size_t count, hipStream_t st)
+{
+    int rc = d.alloc(count);
+    if (rc) return rc;
+    VRT_HIP_TRY(hipMemcpyAsync(d, h, sizeof(double) * count, hipMemcpyHostToDevice, st));
+    return VRT_OK;
+}
+
+}  // namespace
+}  // namespace vrt
+
+using namespace vrt;
+
+struct vrt_continuum {
+    vrt_plan *p = nullptr;
+    int device = 0;                     // of the plan's grid (destroying the session must not look into a plan that may be gone)
+    int64_t n = 0, nlam = 0;
+    double eps_thick = 0;
+    std::vector<double> weights;
+    bool native = false;
+    // sweep order (native): S and J per direction, B_0 and ε in the up order, α of both orders one behind the other
+    DevBuf<double> d_S_nat[2], d_J_nat[2], d_B_up, d_E_up, d_A_nat;
+    // the caller's layout (n, nlam)
+    DevBuf<double> d_S_new, d_S_old, d_J, d_B0, d_eps, d_alpha;
+    DevBuf<double> d_I0;                // B_0 of the bottom layer in perm_up order, (n1, nlam)
+    DevBuf<unsigned long long> d_scalars;
+    int64_t iterations = 0;
+    NgState ng;                         // vrt_continuum_set_acceleration (off: nothing allocated, nothing run)
+    ~vrt_continuum() { ng_release(ng); }
+};
+
+struct vrt_regular_continuum {
+    vrt_regular *r = nullptr;           // borrowed
+    int device = 0, n_sweeps = 3;
+    int64_t n = 0, nlam = 0;
+    double eps_thick = 0;
+    LineSolves ls;
+    hipStream_t st = nullptr;
+    DevBuf<double> d_B0, d_eps, d_J;    // per point, Julia order, (n, nlam)
+    DevBuf<double> d_S[2];              // [sc]: the last S_new
+    int sc = 0;
+    DevBuf<double> d_A_pl, d_S_pl, d_J_pl, d_I0_pl, d_zero;     // plane-major, wavelength slowest
+    DevBuf<unsigned long long> d_scalars;
+    int64_t iterations = 0;
+    NgState ng;
+    ~vrt_regular_continuum()
+    {
+        ng_release(ng);
+        if (st) (void)hipStreamDestroy(st);
+    }
+};
+
+// the S buffer a session's acceleration works on: doubles allocated, and which of them are physical entries
+static size_t continuum_S_count(const vrt_continuum *s, NgRange *rg)
+{
+    const int64_t n = s->n, nlam = s->nlam;
+    if (s->native) {
+        if (rg) { rg->dense = (nlam / 2) * 2 * n; rg->tail = nlam & 1 ? n : 0; rg->tstride = 2; }
+        return (size_t)vrt_plan_native_plane_count(s->p, nlam);
+    }
+    if (rg) { rg->dense = (n * nlam) & ~(int64_t)1; rg->tail = (n * nlam) & 1; rg->tstride = 1; }
+    return (size_t)(n * nlam);
+}
+
+// J_λ (lambda_continuum.jl:1-24) of every (angle, wavelength) solve into dJ_pl, chunk after chunk
+static int continuum_J_pass(vrt_regular_continuum *s, hipStream_t st)
+{
+    vrt_regular *r = s->r;
+    const LineSolves &ls = s->ls;
+    const int64_t vol = s->n, nlam = s->nlam, n_solve = ls.A * nlam;
+    VRT_HIP_TRY(hipMemsetAsync(s->d_J_pl, 0, sizeof(double) * (size_t)(nlam * vol), st));
+    int rc;
+    for (int64_t g0 = 0; g0 < n_solve; g0 += ls.chunk) {
+        const int64_t cnt = std::min(ls.chunk, n_solve - g0);
+        if ((rc = regular_solve_planes(r, cnt, ls.hk.data() + 3 * g0, ls.d_ks + 3 * g0, ls.d_up + g0, s->d_S_pl, nlam, g0,
+                                       s->d_A_pl, s->d_I0_pl, s->d_zero, s->n_sweeps, st, /*alpha_per_lam=*/true)))
+            return rc;
+        if ((rc = launch_reduce_J_planes(r, ls, g0, cnt, s->d_J_pl, st))) return rc;
+    }
+    return VRT_OK;
+}
+
+extern "C" {
+
+int vrt_continuum_case_check(const vrt_continuum_case *cc, int64_t n) { return check_case(cc, n); }
+
+int vrt_continuum_update_dev(vrt_grid *g, int64_t nlam, int64_t ld, const double *dJ, const double *dB, const double *deps,
+                             double eps_thick, const double *dS_old, double *dS_new, double *max_rel_change,
+                             int64_t *n_thick, void *stream)
+{
+    if (!g || !dJ || !dB || !deps || !dS_old || !dS_new || !max_rel_change) return fail(VRT_EINVAL, "NULL argument");
+    if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
+    if (!std::isfinite(eps_thick)) return fail(VRT_EINVAL, "eps_thick must be finite");
+    return guarded([&] {
+        int rc = use_device(g->device);
+        if (rc) return rc;
+        std::lock_guard<std::mutex> lock(g->mu);
+        if (!g->d_scalars && (rc = dev_alloc(&g->d_scalars, kUpdateWords))) return rc;
+        hipStream_t st = (hipStream_t)stream;
+        if ((rc = launch_continuum_update(g->n, nlam, ld, dJ, dB, deps, eps_thick, dS_old, dS_new, g->d_scalars, st))) return rc;
+        return read_criterion(g->d_scalars, st, max_rel_change, n_thick);
+    });
+}
+
+int vrt_continuum_create(vrt_plan *p, const vrt_continuum_case *cc, const double *weights, vrt_continuum **out)
+{
+    if (!out) return fail(VRT_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (!p || !cc || !weights) return fail(VRT_EINVAL, "NULL argument");
+    if (cc->nlam < 1) return fail(VRT_EINVAL, "nlam must be >= 1");
+    if (!cc->alpha || !cc->eps || !cc->B0) return fail(VRT_EINVAL, "NULL array in the continuum case");
+    if (!std::isfinite(cc->eps_thick)) return fail(VRT_EINVAL, "eps_thick must be finite");
+    return guarded([&] {
+        std::lock_guard<std::mutex> lock(p->mu);
+        vrt_grid *g = p->g;
+        int rc = check_case(cc, g->n);
+        if (rc) return rc;
+        if ((rc = use_device(g->device))) return rc;
+        std::unique_ptr<vrt_continuum> s(new vrt_continuum());
+        s->p = p;
+        s->device = g->device;
+        s->n = g->n;
+        s->nlam = cc->nlam;
+        s->eps_thick = cc->eps_thick;
+        s->weights.assign(weights, weights + p->n_angles_user);
+        const int64_t nlam = cc->nlam;
+        const size_t nS = (size_t)g->n * (size_t)nlam;
+        hipStream_t st = g->stream;
+        s->native = p->tune.lambda_native != 0 && p->A > 0 && native_planes_ok(p) == VRT_OK && p->tune.path != 1 &&
+                    p->tune.path != 2;
+#define VRT_S(expr) do { if ((rc = (expr))) return rc; } while (0)
+        DevBuf<double> tmp;                                  // native: the caller-layout arrays exist only here
+        VRT_S(upload(s->d_B0, cc->B0, nS, st));
+        VRT_S(s->d_I0.alloc((size_t)g->up.n1 * (size_t)nlam));
+        // I_0 = B_λ(T) of the bottom layer perm_up[1 : layers_up[2] - 1] (:45-47), fixed over the iterations
+        VRT_S(launch_gather_rows(g->up.n1, nlam, nlam, g->up.d_order, s->d_B0, s->d_I0, st));
+        VRT_S(s->d_scalars.alloc(kUpdateWords));
+        if (s->native) {
+            const size_t np = (size_t)vrt_plan_native_plane_count(p, nlam);
+            for (int d = 0; d < 2; d++) {
+                VRT_S(s->d_S_nat[d].alloc(np));
+                VRT_S(s->d_J_nat[d].alloc(np));
+                VRT_HIP_TRY(hipMemsetAsync(s->d_J_nat[d], 0, sizeof(double) * np, st));
+            }
+            VRT_S(s->d_B_up.alloc(np));
+            VRT_S(s->d_E_up.alloc(np));
+            VRT_S(s->d_A_nat.alloc(2 * np));
+            VRT_S(planes_to_native(p, nlam, nlam, s->d_B0, s->d_S_nat[0], s->d_S_nat[1], st));      // S_new = B_0, :136-137
+            VRT_S(planes_to_native(p, nlam, nlam, s->d_B0, s->d_B_up, nullptr, st));
+            VRT_S(upload(tmp, cc->eps, nS, st));
+            VRT_S(planes_to_native(p, nlam, nlam, tmp, s->d_E_up, nullptr, st));
+            VRT_HIP_TRY(hipStreamSynchronize(st));           // (tmp is uploaded into again)
+            VRT_HIP_TRY(hipMemcpyAsync(tmp, cc->alpha, sizeof(double) * nS, hipMemcpyHostToDevice, st));
+            VRT_S(planes_to_native(p, nlam, nlam, tmp, s->d_A_nat, s->d_A_nat + np, st));
+            VRT_HIP_TRY(hipStreamSynchronize(st));
+            s->d_B0 = DevBuf<double>();                      // (B_0 lives on in the up order)
+        } else {
+            VRT_S(upload(s->d_S_new, cc->B0, nS, st));       // S_new = B_0
+            VRT_S(upload(s->d_eps, cc->eps, nS, st));
+            VRT_S(upload(s->d_alpha, cc->alpha, nS, st));
+            VRT_S(s->d_S_old.alloc(nS));
+            VRT_S(s->d_J.alloc(nS));
+            VRT_HIP_TRY(hipMemsetAsync(s->d_S_old, 0, sizeof(double) * nS, st));                    // S_old = zero(S_new), :139
+            VRT_HIP_TRY(hipMemsetAsync(s->d_J, 0, sizeof(double) * nS, st));
+        }
+#undef VRT_S
+        VRT_HIP_TRY(hipStreamSynchronize(st));               // the host arrays may go after return
+        *out = s.release();
+        return VRT_OK;
+    });
+}
+
+int vrt_continuum_iterate(vrt_continuum *s, double *max_rel_change)
+{
+    if (!s || !max_rel_change) return fail(VRT_EINVAL, "NULL argument");
+    return guarded([&] {
+        vrt_plan *p = s->p;
+        std::lock_guard<std::mutex> lock(p->mu);
+        vrt_grid *g = p->g;
+        int rc = use_device(g->device);
+        if (rc) return rc;
+        hipStream_t st = g->stream;
+        const int64_t n = s->n, nlam = s->nlam;
+        if (s->native) {
+            // J_λ (:27-56) from the sweep-order S into the sweep-order J; S_new and the criterion (:148, :188: the old S is
+            // read from the plane the new one is written to)
+            if ((rc = execute_locked(p, native_args(nlam, s->d_S_nat[0], s->d_S_nat[1], s->d_A_nat, VRT_ALPHA_SITE_LAM_NATIVE,
+                                                    s->d_I0, nullptr, s->weights.data(), s->d_J_nat[0], s->d_J_nat[1], st,
+                                                    false))))
+                return rc;
+            if ((rc = launch_continuum_update_native(g, nlam, s->d_J_nat[0], s->d_J_nat[1], s->d_B_up, s->d_E_up, s->eps_thick,
+                                                     s->d_S_nat[0], s->d_S_nat[1], s->d_scalars, st)))
+                return rc;
+        } else {
+            // S_old = copy(S_new), :146: the current S is read where it is and the new one written to the other buffer; the
+            // two change roles only once both launches are queued (a failure leaves the session's S what it was)
+            if ((rc = execute_locked(p, caller_args(nlam, nlam, s->d_S_new, s->d_alpha, VRT_ALPHA_SITE_LAM, s->d_I0, nullptr,
+                                                    s->weights.data(), s->d_J, nullptr, st, false))))
+                return rc;
+            if ((rc = launch_continuum_update(n, nlam, nlam, s->d_J, s->d_B0, s->d_eps, s->eps_thick, s->d_S_new, s->d_S_old,
+                                              s->d_scalars, st)))
+                return rc;
+            std::swap(s->d_S_old.p, s->d_S_new.p);
+        }
+        if ((rc = read_criterion(s->d_scalars, st, max_rel_change, nullptr))) return rc;
+        if ((rc = patch_chain_check(p))) return rc;          // a chained sweep that gave up: THIS iteration's results are invalid
+        s->iterations++;
+        if (s->ng.order) {
+            // history copy or Ng step on the S of the plain update (native: the up-order copy; an accepted x_acc becomes that
+            // copy and the down-order copy is rewritten from it, value for value)
+            NgRange rg;
+            const size_t count = continuum_S_count(s, &rg);
+            double *&S = s->native ? s->d_S_nat[0].p : s->d_S_new.p;
+            if ((rc = ng_after_iterate(s->ng, s->iterations, S, count, rg, st))) return rc;
+            if (s->ng.last_applied == 1 && s->native) {
+                if ((rc = launch_ng_mirror(g, nlam, s->d_S_nat[0], s->d_S_nat[1], st))) return rc;
+                VRT_HIP_TRY(hipStreamSynchronize(st));
+            }
+        } else
+            s->ng.last_applied = 0;
+        return VRT_OK;
+    });
+}
+
+int vrt_continuum_get(vrt_continuum *s, double *J, double *S)
+{
+    if (!s) return fail(VRT_EINVAL, "NULL session");
+    return guarded([&] {
+        vrt_plan *p = s->p;
+        std::lock_guard<std::mutex> lock(p->mu);
+        int rc = use_device(p->g->device);
+        if (rc) return rc;
+        const size_t bytes = sizeof(double) * (size_t)s->n * (size_t)s->nlam;
+        hipStream_t st = p->g->stream;
+        if (s->native && (J || S)) {
+            DevBuf<double> tmp;                              // the caller's layout is formed here, on request
+            if ((rc = tmp.alloc((size_t)s->n * (size_t)s->nlam))) return rc;
+            if (J) {
+                if ((rc = J_from_native(p, s->nlam, s->nlam, s->d_J_nat[0], s->d_J_nat[1], tmp, st))) return rc;
+                VRT_HIP_TRY(hipMemcpyAsync(J, tmp, bytes, hipMemcpyDeviceToHost, st));
+                VRT_HIP_TRY(hipStreamSynchronize(st));
+            }
+            if (S) {
+                if ((rc = plane_from_native(p, 0, s->nlam, s->nlam, s->d_S_nat[0], tmp, st))) return rc;
+                VRT_HIP_TRY(hipMemcpyAsync(S, tmp, bytes, hipMemcpyDeviceToHost, st));
+                VRT_HIP_TRY(hipStreamSynchronize(st));
+            }
+        } else {
+            if (J) VRT_HIP_TRY(hipMemcpyAsync(J, s->d_J, bytes, hipMemcpyDeviceToHost, st));
+            if (S) VRT_HIP_TRY(hipMemcpyAsync(S, s->d_S_new, bytes, hipMemcpyDeviceToHost, st));
+            VRT_HIP_TRY(hipStreamSynchronize(st));
+        }
+        return VRT_OK;
+    });
+}
+
+int vrt_continuum_set_source(vrt_continuum *s, const double *S)
+{
+    if (!s || !S) return fail(VRT_EINVAL, "NULL argument");
+    int rc = check_source(S, s->n * s->nlam);
+    if (rc) return rc;
+    return guarded([&] {
+        vrt_plan *p = s->p;
+        std::lock_guard<std::mutex> lock(p->mu);
+        if ((rc = use_device(p->g->device))) return rc;
+        const size_t nS = (size_t)s->n * (size_t)s->nlam;
+        hipStream_t st = p->g->stream;
+        if (s->native) {
+            DevBuf<double> tmp;
+            if ((rc = upload(tmp, S, nS, st))) return rc;
+            if ((rc = planes_to_native(p, s->nlam, s->nlam, tmp, s->d_S_nat[0], s->d_S_nat[1], st))) return rc;
+            VRT_HIP_TRY(hipStreamSynchronize(st));
+        } else {
+            VRT_HIP_TRY(hipMemcpyAsync(s->d_S_new, S, sizeof(double) * nS, hipMemcpyHostToDevice, st));
+            VRT_HIP_TRY(hipStreamSynchronize(st));
+        }
+        s->ng.have = 0;                                      // iterates of another S are no history of this one
+        s->ng.last_applied = 0;
+        return VRT_OK;
+    });
+}
+
+int vrt_continuum_set_acceleration(vrt_continuum *s, int order, int start, int period)
+{
+    if (!s) return fail(VRT_EINVAL, "NULL session");
+    int rc = ng_check_settings(order, start, period);
+    if (rc) return rc;
+    return guarded([&] {
+        vrt_plan *p = s->p;
+        std::lock_guard<std::mutex> lock(p->mu);
+        if ((rc = use_device(p->g->device))) return rc;
+        return ng_configure(s->ng, order, start, period, continuum_S_count(s, nullptr));
+    });
+}
+
+int vrt_continuum_last_acceleration(const vrt_continuum *s, int *applied, double sums[5], double coeffs[2])
+{
+    if (!s || !applied) return fail(VRT_EINVAL, "NULL argument");
+    return ng_report(s->ng, applied, sums, coeffs);
+}
+
+void vrt_continuum_destroy(vrt_continuum *s)
+{
+    DeviceScope scope;
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    delete s;
+}
+
+// ---- the regular grid ------------------------------------------------------------------------------------------------------
+int vrt_regular_continuum_create(vrt_regular *r, int64_t n_angles, const double *k, const int *dirs, const double *weights,
+                                 const vrt_continuum_case *cc, int n_sweeps, vrt_regular_continuum **out)
+{
+    if (!out) return fail(VRT_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (!r || !k || !dirs || !weights || !cc) return fail(VRT_EINVAL, "NULL argument");
+    if (cc->nlam < 1) return fail(VRT_EINVAL, "nlam must be >= 1");
+    if (!cc->alpha || !cc->eps || !cc->B0) return fail(VRT_EINVAL, "NULL array in the continuum case");
+    if (!std::isfinite(cc->eps_thick)) return fail(VRT_EINVAL, "eps_thick must be finite");
+    if (n_sweeps < 1) return fail(VRT_EINVAL, "n_sweeps must be >= 1");
+    int rc = check_angles(n_angles, k, dirs);
+    if (rc) return rc;
+    return guarded([&] {
+        const int64_t vol = r->nz * r->nx * r->ny, plane = r->nx * r->ny, nlam = cc->nlam;
+        if ((rc = check_case(cc, vol))) return rc;
+        if ((rc = use_device(r->device))) return rc;
+        std::unique_ptr<vrt_regular_continuum> s(new vrt_regular_continuum());
+        s->r = r;
+        s->device = r->device;
+        s->n_sweeps = n_sweeps;
+        s->n = vol;
+        s->nlam = nlam;
+        s->eps_thick = cc->eps_thick;
+        if ((rc = line_solves_init(s->ls, r, n_angles, k, dirs, weights, nlam))) return rc;
+        VRT_HIP_TRY(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
+        hipStream_t st = s->st;
+        const size_t nS = (size_t)vol * (size_t)nlam;
+#define VRT_S(expr) do { if ((rc = (expr))) return rc; } while (0)
+        DevBuf<double> tmp;
+        VRT_S(upload(s->d_B0, cc->B0, nS, st));
+        VRT_S(upload(s->d_eps, cc->eps, nS, st));
+        VRT_S(upload(s->d_S[0], cc->B0, nS, st));            // S_new = B_0, :83-84
+        VRT_S(upload(tmp, cc->alpha, nS, st));
+        VRT_S(s->d_S[1].alloc(nS));
+        VRT_S(s->d_J.alloc(nS));
+        VRT_S(s->d_A_pl.alloc(nS));
+        VRT_S(s->d_S_pl.alloc(nS));
+        VRT_S(s->d_J_pl.alloc(nS));
+        VRT_S(s->d_I0_pl.alloc((size_t)plane * (size_t)nlam));
+        VRT_S(s->d_zero.alloc((size_t)plane));
+        VRT_S(s->d_scalars.alloc(kUpdateWords));
+        VRT_HIP_TRY(hipMemsetAsync(s->d_J, 0, sizeof(double) * nS, st));
+        VRT_HIP_TRY(hipMemsetAsync(s->d_zero, 0, sizeof(double) * (size_t)plane, st));
+        VRT_S(launch_to_planes(r, nlam, tmp, s->d_A_pl, st));             // α_cont, fixed over the iterations (:76)
+        VRT_S(launch_to_planes(r, nlam, s->d_B0, s->d_S_pl, st));
+        VRT_S(launch_bottom_planes(r, nlam, s->d_B0, s->d_I0_pl, st));    // I_0 = B_λ(T[1, :, :]), :16
+#undef VRT_S
+        VRT_HIP_TRY(hipStreamSynchronize(st));
+        *out = s.release();
+        return VRT_OK;
+    });
+}
+
+int vrt_regular_continuum_iterate(vrt_regular_continuum *s, double *max_rel_change)
+{
+    if (!s || !max_rel_change) return fail(VRT_EINVAL, "NULL argument");
+    return guarded([&] {
+        int rc = use_device(s->device);
+        if (rc) return rc;
+        hipStream_t st = s->st;
+        vrt_regular *r = s->r;
+        const int64_t n = s->n, nlam = s->nlam;
+        // J_λ (:1-24) from S_old = the last S_new (:93-94); S_new = (1 - ε) J + ε B_0 (:95) and the masked criterion (:169);
+        // S_new also plane-major for the next solves
+        if ((rc = continuum_J_pass(s, st))) return rc;
+        if ((rc = launch_from_planes(r, nlam, s->d_J_pl, s->d_J, st))) return rc;
+        if ((rc = launch_continuum_update(n, nlam, nlam, s->d_J, s->d_B0, s->d_eps, s->eps_thick, s->d_S[s->sc], s->d_S[s->sc ^ 1],
+                                          s->d_scalars, st)))
+            return rc;
+        s->sc ^= 1;
+        if ((rc = launch_to_planes(r, nlam, s->d_S[s->sc], s->d_S_pl, st))) return rc;
+        if ((rc = read_criterion(s->d_scalars, st, max_rel_change, nullptr))) return rc;
+        r->timed = false;                                    // (the handle's events saw only the last chunk)
+        s->iterations++;
+        if (s->ng.order) {
+            NgRange rg;
+            rg.dense = (n * nlam) & ~(int64_t)1; rg.tail = (n * nlam) & 1; rg.tstride = 1;
+            if ((rc = ng_after_iterate(s->ng, s->iterations, s->d_S[s->sc].p, (size_t)(n * nlam), rg, st))) return rc;
+            if (s->ng.last_applied == 1) {
+                if ((rc = launch_to_planes(r, nlam, s->d_S[s->sc], s->d_S_pl, st))) return rc;
+                VRT_HIP_TRY(hipStreamSynchronize(st));
+            }
+        } else
+            s->ng.last_applied = 0;
+        return VRT_OK;
+    });
+}
+
+int vrt_regular_continuum_get(vrt_regular_continuum *s, double *J, double *S)
+{
+    if (!s) return fail(VRT_EINVAL, "NULL session");
+    return guarded([&] {
+        int rc = use_device(s->device);
+        if (rc) return rc;
+        const size_t bytes = sizeof(double) * (size_t)s->n * (size_t)s->nlam;
+        VRT_HIP_TRY(hipStreamSynchronize(s->st));
+        if (J) VRT_HIP_TRY(hipMemcpy(J, s->d_J, bytes, hipMemcpyDeviceToHost));
+        if (S) VRT_HIP_TRY(hipMemcpy(S, s->d_S[s->sc], bytes, hipMemcpyDeviceToHost));
+        return VRT_OK;
+    });
+}
+
+int vrt_regular_continuum_set_source(vrt_regular_continuum *s, const double *S)
+{
+    if (!s || !S) return fail(VRT_EINVAL, "NULL argument");
+    int rc = check_source(S, s->n * s->nlam);
+    if (rc) return rc;
+    return guarded([&] {
+        if ((rc = use_device(s->device))) return rc;
+        hipStream_t st = s->st;
+        VRT_HIP_TRY(hipMemcpyAsync(s->d_S[s->sc], S, sizeof(double) * (size_t)s->n * (size_t)s->nlam, hipMemcpyHostToDevice, st));
+        if ((rc = launch_to_planes(s->r, s->nlam, s->d_S[s->sc], s->d_S_pl, st))) return rc;
+        VRT_HIP_TRY(hipStreamSynchronize(st));
+        s->ng.have = 0;
+        s->ng.last_applied = 0;
+        return VRT_OK;
+    });
+}
+
+int vrt_regular_continuum_set_acceleration(vrt_regular_continuum *s, int order, int start, int period)
+{
+    if (!s) return fail(VRT_EINVAL, "NULL session");
+    int rc = ng_check_settings(order, start, period);
+    if (rc) return rc;
+    return guarded([&] {
+        if ((rc = use_device(s->device))) return rc;
+        VRT_HIP_TRY(hipStreamSynchronize(s->st));
+        return ng_configure(s->ng, order, start, period, (size_t)(s->n * s->nlam));
+    });
+}
+
+int vrt_regular_continuum_last_acceleration(const vrt_regular_continuum *s, int *applied, double sums[5], double coeffs[2])
+{
+    if (!s || !applied) return fail(VRT_EINVAL, "NULL argument");
+    return ng_report(s->ng, applied, sums, coeffs);
+}
+
+void vrt_regular_continuum_destroy(vrt_regular_continuum *s)
+{
+    DeviceScope scope;
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    (void)hipStreamSynchronize(s->st);
+    regular_release_workspace(s->r);                         // the chunk workspace goes with the session
+    delete s;
+}
+
+}  // extern "C"

@@ -283,7 +283,7 @@ struct vrt_grid {
     int32_t *d_col = nullptr;
     double *d_lz = nullptr, *d_lx = nullptr, *d_ly = nullptr;   // Delaunay lines, CSR-packed SoA
     hipStream_t stream = nullptr;
-    unsigned long long *d_scalars = nullptr;   // scratch of the Λ-iteration epilogue's reduction
+    unsigned long long *d_scalars = nullptr;   // scratch of the Λ-iteration epilogue's reduction (kUpdateWords)
     double *d_small = nullptr;                 // wavelength-sized host arrays of the physics kernels (λ, 2hc²/λ⁵, σ_bf)
     size_t small_cap = 0;
     double *h_small = nullptr;                 // pinned staging buffer of the same capacity
@@ -505,6 +505,7 @@ int launch_reduce_J(vrt_plan *p, const SweepArgs &sa, const double *weights_acti
                     int64_t ldJ, hipStream_t st);
 int launch_copy_I_out(vrt_plan *p, const SweepArgs &sa, void *dI_out, int64_t ldO, hipStream_t st);
 
+constexpr size_t kUpdateWords = 3;   // a grid's d_scalars: the criterion's maximum, its NaN flag, the continuum's thick count
 int launch_axpy(size_t count, const double *d_src, double *d_dst, hipStream_t st);
 int launch_gather_rows(int64_t rows, int64_t nlam, int64_t ld, const int32_t *d_order, const double *d_src, double *d_dst,
                        hipStream_t st);

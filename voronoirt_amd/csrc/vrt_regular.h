@@ -39,9 +39,29 @@ void regular_release_workspace(vrt_regular *r);
 // n_solve solves whose inputs are already plane-major on the device (no transposes) into r->d_I ([solve][iz][iy][ix]):
 // solve s is direction dk[s] (hk: the same directions on the host, which choose the launch), dup[s] (1 up, 0 down),
 // wavelength l = (s + lam_offset) % lam_period of dS ([l][iz][iy][ix]) and, if up, of dI0 ([l][iy][ix]); a down solve
-// starts from the plane dI0_zero.  dalpha holds one plane-major array per solve.  Asynchronous on st.
+// starts from the plane dI0_zero.  dalpha holds one plane-major array per solve, or (alpha_per_lam: the continuum, whose
+// alpha is the same for every angle) one per wavelength, read like dS.  Asynchronous on st.
 int regular_solve_planes(vrt_regular *r, int64_t n_solve, const double *hk, const double *dk, const int *dup, const double *dS,
                          int64_t lam_period, int64_t lam_offset, const double *dalpha, const double *dI0,
-                         const double *dI0_zero, int n_sweeps, hipStream_t st);
+                         const double *dI0_zero, int n_sweeps, hipStream_t st, bool alpha_per_lam = false);
+
+// ---- pieces of the Λ-iteration on the raster (vrt_regular_lambda.hip) shared with the continuum session (vrt_continuum.hip)
+// (n, nlam) wavelength-fastest in Julia point order <-> plane-major [l][iz][iy][ix]; B_0's bottom planes [l][iy][ix]
+int launch_to_planes(const vrt_regular *r, int64_t nlam, const double *in, double *out, hipStream_t st);
+int launch_from_planes(const vrt_regular *r, int64_t nlam, const double *in, double *out, hipStream_t st);
+int launch_bottom_planes(const vrt_regular *r, int64_t nlam, const double *B0, double *out, hipStream_t st);
+// the checks of a direction set, before the device is touched
+int check_angles(int64_t n_angles, const double *k, const int *dirs);
+// The (angle, wavelength) solves of a direction set: solve g = a nlam + l over the active angles
+struct LineSolves {
+    int64_t A = 0, nlam = 0, chunk = 1;
+    std::vector<double> hk;             // 3 per solve, host (the launch choice of regular_solve_planes)
+    DevBuf<double> d_ka, d_w, d_ks;     // 3 per active angle, 1 per active angle, 3 per solve
+    DevBuf<int> d_up;                   // per solve: 1 up, 0 down
+};
+int line_solves_init(LineSolves &ls, const vrt_regular *r, int64_t n_angles, const double *k, const int *dirs,
+                     const double *weights, int64_t nlam);
+// J[l][p] += w_a I[g - g0][p] over the chunk's solves [g0, g0 + cnt) held in r->d_I, in quadrature order
+int launch_reduce_J_planes(const vrt_regular *r, const LineSolves &ls, int64_t g0, int64_t cnt, double *dJ_pl, hipStream_t st);
 
 }  // namespace vrt

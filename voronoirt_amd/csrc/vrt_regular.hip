@@ -106,7 +106,9 @@ struct RegArgs {
     const double *I0;         // (nx, ny) Julia order per solve: I0[ix + nx*iy]
     double *I;                // plane-major [solve][iz][iy][ix]
     // > 0 (the line Λ-iteration, vrt_regular_lambda.hip): solve s is wavelength (s + lam_offset) % lam_period and reads
-    // that S field and, if up, that I0 plane; a down solve reads the plane I0_zero.  alpha still follows field_period.
+    // that S field and, if up, that I0 plane; a down solve reads the plane I0_zero.  alpha still follows field_period:
+    // one array per solve (0, the line's alpha_tot), or -- field_period = lam_period, the continuum Λ-iteration of
+    // vrt_continuum.hip -- one array per wavelength, shared by every angle.
     int64_t lam_period = 0, lam_offset = 0;
     const double *I0_zero = nullptr;
 };
@@ -116,6 +118,14 @@ __device__ __forceinline__ const double *reg_S(const RegArgs &ra, int64_t solve)
     const int64_t field = ra.lam_period > 0 ? (solve + ra.lam_offset) % ra.lam_period
                                             : ra.field_period > 0 ? solve % ra.field_period : solve;
     return ra.S + field * ra.S_stride;
+}
+
+__device__ __forceinline__ const double *reg_A(const RegArgs &ra, int64_t solve)
+{
+    const int64_t field = ra.field_period <= 0 ? solve
+                          : ra.lam_period > 0  ? (solve + ra.lam_offset) % ra.field_period
+                                               : solve % ra.field_period;
+    return ra.alpha + field * ra.A_stride;
 }
 
 __device__ __forceinline__ const double *reg_I0(const RegArgs &ra, int64_t solve, bool up, int64_t plane)
@@ -258,9 +268,8 @@ k_regular_solve(RegArgs ra)
     const double k0 = ra.k[3 * solve], k1 = ra.k[3 * solve + 1], k2 = ra.k[3 * solve + 2];
     const bool up = ra.up[solve] != 0;
     const int64_t plane = (int64_t)nx * ny;
-    const int64_t field = ra.field_period > 0 ? solve % ra.field_period : solve;
     const double *S = reg_S(ra, solve);
-    const double *Al = ra.alpha + field * ra.A_stride;
+    const double *Al = reg_A(ra, solve);
     double *I = ra.I + (int64_t)solve * plane * nz;
     double *coef = ra.coef + (int64_t)solve * 5 * plane;
     const double *x = ra.x, *y = ra.y, *z = ra.z;
@@ -463,8 +472,7 @@ k_reg_xy_coefs(RegArgs ra, double *__restrict__ xy, int64_t solve0)
     const double k0 = ra.k[3 * solve], k1 = ra.k[3 * solve + 1], k2 = ra.k[3 * solve + 2];
     const bool up = ra.up[solve] != 0;
     const int64_t plane = (int64_t)nx * ny;
-    const int64_t field = ra.field_period > 0 ? solve % ra.field_period : solve;
-    const double *S = reg_S(ra, solve), *Al = ra.alpha + field * ra.A_stride;
+    const double *S = reg_S(ra, solve), *Al = reg_A(ra, solve);
     const double *x = ra.x, *y = ra.y, *z = ra.z;
     int sign_x, sign_y;                                           // xy_intersect, functions.jl:430-457
     if (k1 > 0 && k2 > 0) { sign_x = -1; sign_y = -1; }
@@ -954,7 +962,7 @@ void vrt::regular_release_workspace(vrt_regular *r)
 
 int vrt::regular_solve_planes(vrt_regular *r, int64_t n_solve, const double *hk, const double *dk, const int *dup,
                               const double *dS, int64_t lam_period, int64_t lam_offset, const double *dalpha,
-                              const double *dI0, const double *dI0_zero, int n_sweeps, hipStream_t st)
+                              const double *dI0, const double *dI0_zero, int n_sweeps, hipStream_t st, bool alpha_per_lam)
 {
     const int64_t nz = r->nz, nx = r->nx, ny = r->ny, vol = nz * nx * ny;
     VRT_HIP_TRY(hipSetDevice(r->device));
@@ -968,7 +976,7 @@ int vrt::regular_solve_planes(vrt_regular *r, int64_t n_solve, const double *hk,
     ra.z = r->d_g; ra.x = r->d_g + nz; ra.y = r->d_g + nz + nx;
     ra.k = dk; ra.up = dup;
     ra.S = dS; ra.alpha = dalpha; ra.S_stride = vol; ra.A_stride = vol;
-    ra.field_period = 0;
+    ra.field_period = alpha_per_lam ? lam_period : 0;
     ra.lam_period = lam_period; ra.lam_offset = lam_offset; ra.I0_zero = dI0_zero;
     ra.I0 = dI0; ra.I = r->d_I;
     ra.coef = r->d_coef;

@@ -154,7 +154,9 @@ k_reg_reduce_J(int64_t vol, int nlam, int64_t g0, int64_t cnt, int64_t nl, const
     }
 }
 
-// ---- host side ---------------------------------------------------------------------------------------------------------
+}  // namespace
+
+// ---- host side (the launchers and the solve list are shared with vrt_continuum.hip: vrt_regular.h) -------------------------
 
 int launch_to_planes(const vrt_regular *r, int64_t nlam, const double *in, double *out, hipStream_t st)
 {
@@ -196,14 +198,6 @@ int check_angles(int64_t n_angles, const double *k, const int *dirs)
     }
     return VRT_OK;
 }
-
-// The (angle, wavelength) solves of a direction set: solve g = a nlam + l over the active angles
-struct LineSolves {
-    int64_t A = 0, nlam = 0, chunk = 1;
-    std::vector<double> hk;             // 3 per solve, host (the launch choice of regular_solve_planes)
-    DevBuf<double> d_ka, d_w, d_ks;     // 3 per active angle, 1 per active angle, 3 per solve
-    DevBuf<int> d_up;                   // per solve: 1 up, 0 down
-};
 
 int line_solves_init(LineSolves &ls, const vrt_regular *r, int64_t n_angles, const double *k, const int *dirs,
                      const double *weights, int64_t nlam)
@@ -247,6 +241,17 @@ int line_solves_init(LineSolves &ls, const vrt_regular *r, int64_t n_angles, con
     return VRT_OK;
 }
 
+int launch_reduce_J_planes(const vrt_regular *r, const LineSolves &ls, int64_t g0, int64_t cnt, double *dJ_pl, hipStream_t st)
+{
+    const int64_t vol = r->nz * r->nx * r->ny, nl = std::min(cnt, ls.nlam);
+    hipLaunchKernelGGL(k_reg_reduce_J, dim3((unsigned)((vol + 255) / 256), (unsigned)std::min<int64_t>(nl, 65535)), dim3(256), 0, st,
+                       vol, (int)ls.nlam, g0, cnt, nl, (const double *)ls.d_w, (const double *)r->d_I, dJ_pl);
+    VRT_HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+namespace {
+
 // dJ_pl ([l][iz][iy][ix]) = Σ_a w_a I_a over every solve, from the plane-major S and up-solve I_0 planes
 int line_J_pass(vrt_regular *r, const LineSolves &ls, const LinePoint &lp, const double *dS_pl, const double *dI0_pl,
                 const double *dI0_zero, int n_sweeps, double *dJ_pl, hipStream_t st)
@@ -266,10 +271,7 @@ int line_J_pass(vrt_regular *r, const LineSolves &ls, const LinePoint &lp, const
         if ((rc = regular_solve_planes(r, cnt, ls.hk.data() + 3 * g0, ls.d_ks + 3 * g0, ls.d_up + g0, dS_pl, nlam, g0, r->d_A,
                                        dI0_pl, dI0_zero, n_sweeps, st)))
             return rc;
-        const int64_t nl = std::min(cnt, nlam);
-        hipLaunchKernelGGL(k_reg_reduce_J, dim3(bx, (unsigned)std::min<int64_t>(nl, 65535)), dim3(256), 0, st, vol, (int)nlam, g0,
-                           cnt, nl, (const double *)ls.d_w, (const double *)r->d_I, dJ_pl);
-        VRT_HIP_TRY(hipGetLastError());
+        if ((rc = launch_reduce_J_planes(r, ls, g0, cnt, dJ_pl, st))) return rc;
     }
     return VRT_OK;
 }

@@ -475,3 +475,66 @@ def regular_line_case(nz: int, nx: int, ny: int, seed: int, nbb: int = 21, nbf: 
         sigma_bb_const=2e-32, hc_over_kB=h_pl * c0 / kB, pref_ij=2e36, pref_ji=2e37)
     from .api import periodic_axis
     return z, periodic_axis(atm["x"]), periodic_axis(atm["y"]), case
+
+
+# ---------------------------------------------------------------------------------------------
+# the continuum scattering case (src/lambda_continuum.jl)
+# ---------------------------------------------------------------------------------------------
+def _planck_kW_nm(lam, T):
+    """B_λ(T) in kW nm^-1 m^-2 sr^-1 (the reference's unit), lam in m"""
+    h_pl, c0, kB = 6.62607015e-34, 2.99792458e8, 1.380649e-23
+    return 1e-12 * 2.0 * h_pl * c0 ** 2 / lam ** 5 / np.expm1(h_pl * c0 / (lam * kB * T))
+
+
+def _continuum_fields(h, T, strat, nlam: int, seed: int, idx):
+    """α, ε, B_0 (..., nlam) from the relative height h in [0, 1], the temperature and the α stratification (1 / m)"""
+    lam = 500e-9 * (1.0 + 0.1 * np.arange(nlam))
+    idl = idx[..., None] * np.uint64(nlam) + np.arange(nlam, dtype=np.uint64)
+    colour = 1.0 + 0.3 * np.arange(nlam) / max(nlam, 1)                    # a little redder, a little more opaque
+    alpha = strat[..., None] * colour * (1.0 + 0.1 * counter_uniform(seed, 31, idl))
+    # ε from about 1 at the bottom to about 1e-6 at the top: thick (> 1e-4) below h of about 0.65, thin above
+    eps = 10.0 ** (-6.0 * h[..., None]) * (1.0 - 0.3 * counter_uniform(seed, 32, idl))
+    B0 = _planck_kW_nm(lam, T[..., None] * (1.0 + 0.01 * counter_uniform(seed, 33, idl)))
+    return alpha, eps, B0
+
+
+def continuum_case(positions: np.ndarray, bounds, nlam: int = 1, seed: int = 0, eps_thick: float = 1e-4):
+    """Inputs of Λ_voronoi's continuum loop (src/lambda_continuum.jl:109-160) on the sites of a grid: the keyword
+    arguments of api.ContinuumCase, arrays (n, nlam), wavelengths 500 nm (1 + 0.1 l).
+
+    α falls exponentially with height so that τ = 1 lies inside the box (τ of the whole height about 6); ε = α_a / α_cont
+    runs from about 1 at the bottom to about 1e-6 at the top, so that thin AND thick entries exist at every wavelength
+    and the masked and the unmasked criterion differ; B_0 is the Planck function of a temperature with a photosphere,
+    a minimum and a chromospheric rise, in kW nm^-1 m^-2 sr^-1."""
+    z = positions[:, 0]
+    z_min, z_max = bounds[0], bounds[1]
+    h = (z - z_min) / (z_max - z_min)
+    T = 4000.0 + 2500.0 * np.exp(-h / 0.12) + 6000.0 / (1.0 + np.exp(-(h - 0.8) / 0.05))
+    strat = 40.0 / (z_max - z_min) * np.exp(-h / 0.15)
+    alpha, eps, B0 = _continuum_fields(h, T, strat, nlam, seed, np.arange(z.size, dtype=np.uint64))
+    return dict(alpha=alpha, eps=eps, B0=B0, eps_thick=eps_thick)
+
+
+def regular_continuum_case(nz: int, nx: int, ny: int, seed: int, nlam: int = 1, eps_thick: float = 1e-4):
+    """Inputs of Λ_regular's continuum loop (src/lambda_continuum.jl:58-107) on `atmosphere_raster(nz, nx, ny, seed)` with
+    the one-cell periodic ghost border of get_atmos(...; periodic=true): returns z, x, y (the ghosted axes) and the
+    keyword arguments of api.ContinuumCase on all nz (nx + 2) (ny + 2) points in Julia order (numpy (ny + 2, nx + 2, nz)
+    flattened).  The fields are drawn on the interior and wrapped, so that the ghost points hold their interior values
+    exactly, as `regular_line_case` does.  α follows N_H (τ = 1 inside the box), ε and B_0 as `continuum_case`, B_0 from
+    the raster's temperature capped at 10 000 K."""
+    atm = atmosphere_raster(nz, nx, ny, seed)
+    z = atm["z"]
+    shape = (ny, nx, nz)
+    h = np.broadcast_to(((z - z[0]) / (z[-1] - z[0]))[None, None, :], shape)
+    T = np.minimum(atm["T"], 1.0e4)
+    strat = 30.0 / (z[-1] - z[0]) * atm["N_H"] / atm["N_H"].max()
+    idx = np.arange(ny * nx * nz, dtype=np.uint64).reshape(shape)
+    alpha, eps, B0 = _continuum_fields(h, T, strat, nlam, seed, idx)
+
+    def wrap(a):                                  # (ny, nx, nz, nlam) interior -> ghosted, flattened to (n, nlam)
+        g = np.pad(a, [(1, 1), (1, 1), (0, 0), (0, 0)], mode="wrap")
+        return np.ascontiguousarray(g.reshape(-1, nlam))
+
+    from .api import periodic_axis
+    return z, periodic_axis(atm["x"]), periodic_axis(atm["y"]), dict(alpha=wrap(alpha), eps=wrap(eps), B0=wrap(B0),
+                                                                     eps_thick=eps_thick)
