@@ -661,6 +661,19 @@ void vrt_regular_lambda_destroy(vrt_regular_lambda *s);
 int vrt_ng_accelerate_dev(int64_t count, const double *d_x0, const double *d_x1, const double *d_x2,
                           const double *d_x3, double *d_out, double sums[5], double coeffs[2], int *applied,
                           void *stream);
+/* The pieces of that call, for a caller that holds S in several arrays (blocks of one device, one block per device or
+ * per process): vrt_ng_sums_dev on every piece, the five sums added piece by piece in one fixed order, vrt_ng_coefficients
+ * once, vrt_ng_apply_dev on every piece, and the step taken only if every piece reports good.
+ * vrt_ng_sums_dev: the five sums over `count` elements -- for the same arrays the same bits as vrt_ng_accelerate_dev's.
+ * vrt_ng_coefficients (host only): det, a, b as above into coeffs[2]; returns 1, or 0 with coeffs untouched when a sum or
+ *   det is not finite or det == 0 (VRT_EINVAL for a NULL argument).
+ * vrt_ng_apply_dev: d_out = x_acc for the given a, b; *good = 1, or 0 when any x_acc is not finite or not > 0 (d_out then
+ *   unspecified).  d_out aliases no input.  Both *_dev calls work on the current HIP device and synchronise `stream`. */
+int vrt_ng_sums_dev(int64_t count, const double *d_x0, const double *d_x1, const double *d_x2, const double *d_x3,
+                    double sums[5], void *stream);
+int vrt_ng_coefficients(const double sums[5], double coeffs[2]);
+int vrt_ng_apply_dev(int64_t count, double a, double b, const double *d_x0, const double *d_x1, const double *d_x2,
+                     double *d_out, int *good, void *stream);
 /* The single-device sessions: order 0 = off (default), 2 = the step above.  The first step is due after iterate number
  * `start` (>= 4), the next ones after every `period` further iterates (>= 4, so that an extrapolated S never enters a
  * history).  Anything else: VRT_EINVAL; with order 0, start and period are ignored.  Callable between any two iterates (a
@@ -671,7 +684,8 @@ int vrt_ng_accelerate_dev(int64_t count, const double *d_x0, const double *d_x1,
  * S of the three iterates before a due one is copied (three extra S arrays while acceleration is on; none when off, and
  * a session that never asks for acceleration runs exactly what it ran before).  The Voronoi session forms the sums over
  * the n nlam physical entries of its up-order copy of S and applies the same a, b to both sweep-order copies.
- * vrt_multi_lambda_* has NO acceleration entry: its S is split over the devices and the sums would need a collective. */
+ * vrt_multi_lambda_* has NO acceleration entry: its S is split over the devices.  A caller that holds S in pieces has the
+ * three pieces of the step above (vrt_ng_sums_dev, vrt_ng_coefficients, vrt_ng_apply_dev). */
 int vrt_lambda_set_acceleration(vrt_lambda *s, int order, int start, int period);
 int vrt_regular_lambda_set_acceleration(vrt_regular_lambda *s, int order, int start, int period);
 /* what the LAST iterate did: *applied = 1 taken, 0 none due, -1 due but rejected; sums / coeffs (either may be NULL)

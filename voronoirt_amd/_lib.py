@@ -179,6 +179,9 @@ PROTOTYPES = {
     "vrt_sample_sites_dev": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64, p_dbl, p_dbl, p_dbl, vp, c_i64,
                                             ctypes.c_uint64, c_i64, c_i64, vp, p_i64, vp]),
     "vrt_ng_accelerate_dev": (ctypes.c_int, [c_i64, vp, vp, vp, vp, vp, p_dbl, p_dbl, p_int, vp]),
+    "vrt_ng_sums_dev": (ctypes.c_int, [c_i64, vp, vp, vp, vp, p_dbl, vp]),
+    "vrt_ng_coefficients": (ctypes.c_int, [p_dbl, p_dbl]),
+    "vrt_ng_apply_dev": (ctypes.c_int, [c_i64, c_dbl, c_dbl, vp, vp, vp, vp, p_int, vp]),
     "vrt_lambda_set_acceleration": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vrt_regular_lambda_set_acceleration": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vrt_lambda_last_acceleration": (ctypes.c_int, [vp, p_int, p_dbl, p_dbl]),

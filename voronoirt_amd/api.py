@@ -1114,6 +1114,68 @@ def ng_accelerate(x0, x1, x2, x3, device: int = 0):
         return (out.cpu().numpy().reshape(xs[0].shape) if applied else None), sums, coeffs
 
 
+def ng_sums_dev(count: int, d_x0: int, d_x1: int, d_x2: int, d_x3: int, stream: int = 0) -> np.ndarray:
+    """The five sums (A1, B1, C1, B2, C2) of the Ng step over `count` doubles at device pointers (`vrt_ng_sums_dev`): the
+    bits `ng_accelerate_dev` reports for the same arrays.  A caller that holds S in pieces adds the pieces' sums in one
+    fixed order and hands the total to `ng_coefficients`.  Synchronises."""
+    sums = np.zeros(5)
+    check(_lib.load().vrt_ng_sums_dev(int(count), d_x0, d_x1, d_x2, d_x3, _d(sums), stream or None))
+    return sums
+
+
+def ng_coefficients(sums):
+    """(a, b) of the Ng step from its five sums (`vrt_ng_coefficients`, host only, the library's order of operations), or
+    None when a sum or the determinant is not finite or the determinant is zero."""
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    if s.shape != (5,):
+        raise ValueError("ng_coefficients: five sums (A1, B1, C1, B2, C2)")
+    coeffs = np.zeros(2)
+    rc = _lib.load().vrt_ng_coefficients(_d(s), _d(coeffs))
+    if rc < 0:
+        check(rc)
+    if rc == 0:
+        return None
+    return float(coeffs[0]), float(coeffs[1])
+
+
+def ng_apply_dev(count: int, a: float, b: float, d_x0: int, d_x1: int, d_x2: int, d_out: int, stream: int = 0) -> bool:
+    """x_acc = (c x0 + a x1) + b x2, c = (1 - a) - b, into d_out (`vrt_ng_apply_dev`; aliases no input).  Returns False
+    when some x_acc is not finite or not > 0 (d_out is then unspecified).  Synchronises."""
+    good = ctypes.c_int(0)
+    check(_lib.load().vrt_ng_apply_dev(int(count), float(a), float(b), d_x0, d_x1, d_x2, d_out, ctypes.byref(good),
+                                       stream or None))
+    return bool(good.value)
+
+
+def _ng_staged(arrays, device: int, who: str):
+    import torch
+    xs = [np.ascontiguousarray(x, dtype=np.float64) for x in arrays]
+    if any(x.shape != xs[0].shape for x in xs):
+        raise ValueError(f"{who}: the iterates must have one shape")
+    dev = torch.device("cuda", int(device))
+    return xs[0].shape, dev, [torch.from_numpy(x.reshape(-1)).to(dev) for x in xs]
+
+
+def ng_sums(x0, x1, x2, x3, device: int = 0) -> np.ndarray:
+    """`ng_sums_dev` for host arrays of one shape, staged through the device."""
+    import torch
+    _, dev, d = _ng_staged((x0, x1, x2, x3), device, "ng_sums")
+    with torch.cuda.device(dev):
+        return ng_sums_dev(d[0].numel(), *(t.data_ptr() for t in d), torch.cuda.current_stream(dev).cuda_stream)
+
+
+def ng_apply(a: float, b: float, x0, x1, x2, device: int = 0):
+    """`ng_apply_dev` for host arrays of one shape, staged through the device.  Returns (x_acc, good); x_acc is None when
+    the verdict is bad."""
+    import torch
+    shape, dev, d = _ng_staged((x0, x1, x2), device, "ng_apply")
+    with torch.cuda.device(dev):
+        out = torch.empty_like(d[0])
+        good = ng_apply_dev(d[0].numel(), a, b, *(t.data_ptr() for t in d), out.data_ptr(),
+                            torch.cuda.current_stream(dev).cuda_stream)
+        return (out.cpu().numpy().reshape(shape) if good else None), good
+
+
 def _ng_settings(ng):
     start, period = (int(v) for v in ng)
     return start, period

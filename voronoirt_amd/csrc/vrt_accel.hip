@@ -11,6 +11,10 @@
 // per-workgroup partial sums.  No floating-point atomics: for a given element count the launch shape, the assignment of
 // elements to accumulators and the order of every addition are fixed, so the five sums are the same bits run after run.
 //
+// The sums, the coefficients and the apply are separate steps (ng_sums, ng_coefficients, ng_apply; public as vrt_ng_sums_dev,
+// vrt_ng_coefficients, vrt_ng_apply_dev): vrt_ng_accelerate_dev and ng_after_iterate run the three on one array; a caller
+// that holds S in several arrays runs the first and the last per array and adds the partial sums in one fixed order.
+//
 // Element ranges (NgRange): `dense` contiguous doubles (an even count, read as double2), then `tail` doubles `tstride` apart.
 // A caller-layout array is (count & ~1, count & 1, 1); a sweep-order plane set with an odd wavelength count is every full
 // pair plane dense, then the first halves of the last plane's pairs (stride 2) -- the padding wavelength is never touched.
@@ -340,6 +344,60 @@ int ng_report(const NgState &ng, int *applied, double sums[5], double coeffs[2])
 
 using namespace vrt;
 
+namespace {
+
+// a caller-layout array of `count` doubles
+inline NgRange dense_range(int64_t count)
+{
+    NgRange rg;
+    rg.dense = count & ~(int64_t)1; rg.tail = count & 1; rg.tstride = 1;
+    return rg;
+}
+
+}  // namespace
+
+extern "C" int vrt_ng_sums_dev(int64_t count, const double *d_x0, const double *d_x1, const double *d_x2, const double *d_x3,
+                               double sums[5], void *stream)
+{
+    if (!d_x0 || !d_x1 || !d_x2 || !d_x3 || !sums) return fail(VRT_EINVAL, "NULL argument");
+    if (count < 1) return fail(VRT_EINVAL, "count must be >= 1");
+    return guarded([&] {
+        int rc = use_current_device();
+        if (rc) return rc;
+        DevBuf<double> ws;
+        if ((rc = ws.alloc(kNgWorkspace))) return rc;
+        return ng_sums(dense_range(count), d_x0, d_x1, d_x2, d_x3, ws, sums, (hipStream_t)stream);
+    });
+}
+
+extern "C" int vrt_ng_coefficients(const double sums[5], double coeffs[2])
+{
+    if (!sums || !coeffs) return fail(VRT_EINVAL, "NULL argument");
+    double ab[2];
+    if (!ng_coefficients(sums, ab)) return 0;
+    coeffs[0] = ab[0]; coeffs[1] = ab[1];
+    return 1;
+}
+
+extern "C" int vrt_ng_apply_dev(int64_t count, double a, double b, const double *d_x0, const double *d_x1, const double *d_x2,
+                                double *d_out, int *good, void *stream)
+{
+    if (!d_x0 || !d_x1 || !d_x2 || !d_out || !good) return fail(VRT_EINVAL, "NULL argument");
+    if (count < 1) return fail(VRT_EINVAL, "count must be >= 1");
+    return guarded([&] {
+        int rc = use_current_device();
+        if (rc) return rc;
+        DevBuf<double> ws;
+        if ((rc = ws.alloc(kNgWorkspace))) return rc;
+        bool ok = false;
+        *good = 0;
+        if ((rc = ng_apply(dense_range(count), a, b, d_x0, d_x1, d_x2, d_out, ws, &ok, (hipStream_t)stream))) return rc;
+        *good = ok ? 1 : 0;
+        return VRT_OK;
+    });
+}
+
+// the three pieces above in one call, on one workspace
 extern "C" int vrt_ng_accelerate_dev(int64_t count, const double *d_x0, const double *d_x1, const double *d_x2,
                                      const double *d_x3, double *d_out, double sums[5], double coeffs[2], int *applied,
                                      void *stream)
@@ -352,8 +410,7 @@ extern "C" int vrt_ng_accelerate_dev(int64_t count, const double *d_x0, const do
         hipStream_t st = (hipStream_t)stream;
         DevBuf<double> ws;
         if ((rc = ws.alloc(kNgWorkspace))) return rc;
-        NgRange rg;
-        rg.dense = count & ~(int64_t)1; rg.tail = count & 1; rg.tstride = 1;
+        const NgRange rg = dense_range(count);
         *applied = 0;
         if ((rc = ng_sums(rg, d_x0, d_x1, d_x2, d_x3, ws, sums, st))) return rc;
         if (!ng_coefficients(sums, coeffs)) return VRT_OK;

@@ -129,3 +129,43 @@ def allgather_J_blocks(J_block, nlam_total: int, out=None):
 def assemble_J_blocks(buf, sizes):
     import torch
     return torch.cat([buf[r][:, : b - a] for r, (a, b) in enumerate(sizes)], dim=1)
+
+
+def ng_step(x0, x1, x2, x3, out=None):
+    """Second-order Ng step (csrc/vrt_accel.hip) on an S that is sharded over the ranks: x0 (newest) .. x3 are this rank's
+    pieces of the last four iterates, contiguous float64 tensors on its GPU.  The rank's five partial sums
+    (`vrt_ng_sums_dev`), ONE all-reduce of five doubles, the coefficients on every rank from the same total
+    (`vrt_ng_coefficients`), the rank's x_acc (`vrt_ng_apply_dev`) and an all-reduce(MAX) of the inverted verdict: the
+    step is taken on every rank or on none.  Returns (applied, sums, coeffs, x_acc); coeffs is None when the system is
+    singular, x_acc (`out` when given) is meaningful only when applied.  Without a process group it is the fused call's
+    result bit for bit; across ranks the collective chooses the order of the five additions.  Tested on a world of one
+    rank only (one GPU per machine where the tests run): that every rank of a larger world reaches the same decision
+    rests on the two collectives delivering one value to all ranks, and has not been run."""
+    import torch
+    import torch.distributed as dist
+
+    from . import api
+
+    xs = (x0, x1, x2, x3)
+    if any(t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.shape != x0.shape for t in xs):
+        raise ValueError("ng_step: four contiguous float64 device tensors of one shape")
+    grouped = dist.is_available() and dist.is_initialized()
+    with torch.cuda.device(x0.device):
+        stream = torch.cuda.current_stream(x0.device).cuda_stream
+        count = x0.numel()
+        sums = api.ng_sums_dev(count, *(t.data_ptr() for t in xs), stream) if count else np.zeros(5)
+        if grouped:
+            total = torch.from_numpy(sums).to(x0.device)
+            dist.all_reduce(total, op=dist.ReduceOp.SUM)
+            sums = total.cpu().numpy()
+        coeffs = api.ng_coefficients(sums)
+        if coeffs is None:                           # the same total on every rank: the same decision, no collective needed
+            return False, sums, None, out
+        if out is None:
+            out = torch.empty_like(x0)
+        good = api.ng_apply_dev(count, coeffs[0], coeffs[1], x0.data_ptr(), x1.data_ptr(), x2.data_ptr(), out.data_ptr(),
+                                stream) if count else True
+        bad = torch.tensor([0 if good else 1], dtype=torch.int32, device=x0.device)
+        if grouped:
+            dist.all_reduce(bad, op=dist.ReduceOp.MAX)
+        return int(bad.item()) == 0, sums, np.array(coeffs), out
