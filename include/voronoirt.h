@@ -734,7 +734,41 @@ int vrt_regular_lambda_last_acceleration(const vrt_regular_lambda *s, int *appli
  *   alias neither S_old nor J.  *n_thick (may be NULL) = the number of entries with eps > eps_thick; none: the scalar is
  *   0.  Synchronises `stream`.
  * There is NO multi-device continuum session: vrt_multi_lambda_* splits wavelength blocks over the devices, and the one
- * wavelength of a continuum run cannot be split that way. */
+ * wavelength of a continuum run cannot be split that way.
+ *
+ * Accelerated Λ-iteration (ALI) with a diagonal approximate operator (Olson, Auer & Buchler 1986), Voronoi session only.
+ * Plain Λ-iteration converges like 1 - ε because in thick cells most of J at a site is the site's own S coming straight
+ * back; the local operator Λ* is that part, and the update solves for it instead of lagging behind it.  Ng acceleration
+ * (above) needs no approximate operator; this is the scheme that has one, and the two compose.
+ * vrt_plan_lambda_diagonal_dev: Λ* of a plan and an α in the VRT_ALPHA_SITE_LAM layout (n, ld), into d_diag (n, ld):
+ *     Λ*[i,l] = Σ_a weights[a] · upd(a,i) · ( (w_1 b(Δτ_1)) + (w_2 b(Δτ_2)) )
+ *     Δτ_r    = r_r (α[i,l] + α[up_r,l]) / 2            (trapezoidal, as the sweep)
+ *     b       = third coefficient of linear_weights: Δτ < 5e-4: Δτ (1/2 - Δτ/6); Δτ > 50: 1 - 1/Δτ; else 1 - a - e
+ *   the coefficient of S[i] in the last Gauss-Seidel visit I[i] = Σ_r w_r (e_r I[up_r] + a_r S[up_r] + b_r S[i]), summed
+ *   over the plan's angles in quadrature order (θ = 90 angles are skipped); up_r, w_r, r_r are the entries
+ *   vrt_plan_get_upwind returns for that angle.  upd(a,i) is 1 where the sweep of angle a updates site i and 0 at the
+ *   sites of layer 1 of the angle's direction (their I is I_0, independent of S) and at the never-visited site perm[n] of
+ *   that direction.  A slot 2 that duplicates slot 1 has w_2 = 0 and adds nothing.  Angles in order, slot 1 then slot 2,
+ *   no floating-point atomics: the same inputs give the same bits.  0 <= Λ* <= the true diagonal Λ_ii (every coefficient
+ *   of Λ is >= 0).  weights_host[n_angles] on the host; asynchronous on `stream`; the padding columns of d_diag are not
+ *   written.  vrt_plan_lambda_diagonal: the same from host arrays, which also checks that α is finite and > 0.
+ *   Both check NULL pointers, nlam >= 1 and ld >= nlam before the device is touched.
+ * vrt_continuum_ali_update_dev: the contract of vrt_continuum_update_dev with d_diag (nlam, n; leading dimension ld) = Λ*;
+ *   per entry, with t = 1 - ε:
+ *     num = t (J - Λ* S_old) + ε B0,    den = 1 - t Λ*,    S_new = num / den
+ *   which is S_old + (S_fs - S_old) / den with S_fs the plain update, written so that num >= 0.  The criterion is
+ *   unchanged in kind: max |1 - S_old/S_new| over the entries with ε > eps_thick, the same NaN rule and thick count.
+ * vrt_continuum_set_operator: op 0 = plain Λ-iteration (the default), 1 = the diagonal operator, anything else VRT_EINVAL;
+ *   callable between any two iterates.  Turning it on computes Λ* from the session's α and weights, once (and, in the
+ *   sweep-order session, its up-order plane set), then reduces min den on the device: if that is not > 0 -- only for
+ *   ε = 0 where Λ* rounds to 1 -- VRT_EINVAL, the session untouched.  Turning it off frees Λ*.  A change of the operator
+ *   drops any recorded Ng history, as _set_source does; _set_source keeps the operator.  With Ng on, the step runs on the
+ *   S the ALI update produced, and the returned scalar is that of the ALI update, formed before any extrapolation.  Both
+ *   layouts give the same S, J and scalar bit for bit.  A session that never calls it allocates and runs nothing extra.
+ * vrt_continuum_get_operator: *op, and -- when on and diag is not NULL -- Λ* (nlam, n) Julia dims.
+ * Out of scope: the regular-grid continuum session (its six plane kinds each need their own centre coefficient), the
+ * line sessions (their update goes through the rate equations and needs a preconditioned statistical equilibrium), and
+ * any multi-device form. */
 typedef struct vrt_continuum vrt_continuum;
 typedef struct vrt_regular_continuum vrt_regular_continuum;
 typedef struct vrt_continuum_case {
@@ -765,6 +799,15 @@ void vrt_regular_continuum_destroy(vrt_regular_continuum *s);
 int vrt_continuum_update_dev(vrt_grid *g, int64_t nlam, int64_t ld, const double *dJ, const double *dB,
                              const double *deps, double eps_thick, const double *dS_old, double *dS_new,
                              double *max_rel_change, int64_t *n_thick, void *stream);
+int vrt_plan_lambda_diagonal_dev(vrt_plan *p, int64_t nlam, int64_t ld, const double *d_alpha,
+                                 const double *weights_host, double *d_diag, void *stream);
+int vrt_plan_lambda_diagonal(vrt_plan *p, int64_t nlam, int64_t ld, const double *alpha, const double *weights,
+                             double *diag);
+int vrt_continuum_ali_update_dev(vrt_grid *g, int64_t nlam, int64_t ld, const double *dJ, const double *dB,
+                                 const double *deps, const double *d_diag, double eps_thick, const double *dS_old,
+                                 double *dS_new, double *max_rel_change, int64_t *n_thick, void *stream);
+int vrt_continuum_set_operator(vrt_continuum *s, int op);
+int vrt_continuum_get_operator(vrt_continuum *s, int *op, double *diag /* (nlam, n) Julia dims, may be NULL */);
 
 /* ---- emergent spectra: opacity / source function, top-plane intensity, tau = 1 heights ------------------------------
  * The last step of a reference study (write_top_intensity, write_tau_unity and plotter, src/plot_utils.jl:61-140,

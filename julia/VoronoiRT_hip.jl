@@ -514,17 +514,19 @@ function continuum_loop(ϵ, maxiter, iterate, fetch, last_acc, ng)
 end
 
 """
-    Λ_continuum(ϵ, maxiter, sites, quadrature; ng=nothing, S0=nothing) -> (J_new, S_new, α_cont)
+    Λ_continuum(ϵ, maxiter, sites, quadrature; ng=nothing, S0=nothing, operator=nothing) -> (J_new, S_new, α_cont)
 
 The reference's continuum Λ_voronoi (src/lambda_continuum.jl:109-160) with its loop on the device (vrt_continuum_*).
 What it derives before the loop -- LTE populations, α_s, α_a, ε_λ, B_0 at 500 nm (:116-137) -- comes from the reference's
 own functions; every iteration is vrt_continuum_iterate, whose scalar is the maximum over thick = ε_λ .> 1e-4.
 `ng = (start, period)`: vrt_continuum_set_acceleration; `S0`: a source function to resume from
-(vrt_continuum_set_source, the recover_* use of src/recover_simulation.jl).  Unrun: Julia is not installed where the
-library is built.
+(vrt_continuum_set_source, the recover_* use of src/recover_simulation.jl).  `operator = :diagonal`: accelerated
+Λ-iteration with the local operator Λ* (vrt_continuum_set_operator), which composes with `ng`.  Unrun: Julia is not
+installed where the library is built.
 """
 function Λ_continuum(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, quadrature::String;
-                     ng::Union{Nothing,Tuple{Int,Int}}=nothing, S0=nothing)
+                     ng::Union{Nothing,Tuple{Int,Int}}=nothing, S0=nothing, operator::Union{Nothing,Symbol}=nothing)
+    operator === nothing || operator === :diagonal || throw(ArgumentError("operator must be nothing or :diagonal"))
     println("---Iterating---")
     λ = 500u"nm"
     LTE_pops = VoronoiRT.LTE_populations(sites)
@@ -549,6 +551,7 @@ function Λ_continuum(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, 
         S_in = Vector{Float64}(ustrip.(I_unit, S0))
         check(ccall((:vrt_continuum_set_source, libvrt), Cint, (Ptr{Cvoid}, Ptr{Float64}), ses[], S_in))
     end
+    operator === :diagonal && check(ccall((:vrt_continuum_set_operator, libvrt), Cint, (Ptr{Cvoid}, Cint), ses[], 1))
     ng !== nothing && check(ccall((:vrt_continuum_set_acceleration, libvrt), Cint, (Ptr{Cvoid}, Cint, Cint, Cint),
                                   ses[], 2, ng[1], ng[2]))
     J = Vector{Float64}(undef, n); S = Vector{Float64}(undef, n)

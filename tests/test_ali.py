@@ -1,0 +1,404 @@
+"""Accelerated Λ-iteration with the diagonal operator Λ* on the device: vrt_plan_lambda_diagonal[_dev],
+vrt_continuum_ali_update_dev, vrt_continuum_set_operator / _get_operator and api.lambda_diagonal /
+api.continuum_ali_update_dev / Lambda_continuum(operator="diagonal"), against the numpy restatement of Λ* and the
+oracle-driven ALI loop of tests/test_ali_host.py.
+
+Tolerances: Λ* against its numpy restatement 1e-12 relative (device arithmetic against a CPU restatement of the same
+formula: <= 24 terms of a few ulp each); the session against the oracle loop as tests/test_continuum.py (J and S 1e-9,
+the history rtol 1e-8); the standalone update against numpy 1e-14 relative (five operations of one rounding each)."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import voronoirt_amd as vrt
+from oracle import oracle as orc
+from voronoirt_amd import _lib, api, synth
+from test_continuum_host import QUAD, bcc_case, oracle_J_voronoi, oracle_loop
+from test_continuum import _against_oracle
+from test_ali_host import lambda_star_ref, oracle_ali_loop, oracle_table, scaled_case, updated_mask
+
+pytestmark = pytest.mark.gpu
+
+
+class _Session:
+    """vrt_continuum_* called directly, on the grid's shared plan or -- native=False -- on a caller-layout plan of its own"""
+
+    def __init__(self, sites, case, native=True):
+        self.L, self.case = _lib.load(), case
+        self.own = None
+        if native:
+            plan, w = api._quadrature_plan(sites, QUAD, 3)
+        else:
+            w, th, ph, _ = vrt.read_quadrature(QUAD)
+            self.own = plan = vrt.FormalPlan(sites, vrt.quadrature_directions(th, ph), 3,
+                                             dirs=[1 if t > 90 else (-1 if t < 90 else 0) for t in th])
+            plan.set_option("VRT_LAMBDA_NATIVE", 0)
+        self.cc = case.c_struct()
+        self.w = np.ascontiguousarray(w, dtype=np.float64)
+        self.plan = plan
+        self.h = ctypes.c_void_p()
+        rc = self.L.vrt_continuum_create(plan._h, ctypes.byref(self.cc), self.w.ctypes.data_as(_lib.p_dbl), ctypes.byref(self.h))
+        assert rc == 0, rc
+
+    def iterate(self):
+        d = ctypes.c_double()
+        assert self.L.vrt_continuum_iterate(self.h, ctypes.byref(d)) == 0
+        return d.value
+
+    def get(self):
+        J, S = np.zeros((self.case.n, self.case.nlam)), np.zeros((self.case.n, self.case.nlam))
+        assert self.L.vrt_continuum_get(self.h, J.ctypes.data_as(_lib.p_dbl), S.ctypes.data_as(_lib.p_dbl)) == 0
+        return J, S
+
+    def set_operator(self, op):
+        return self.L.vrt_continuum_set_operator(self.h, op)
+
+    def get_operator(self, want_diag=True):
+        op = ctypes.c_int(-1)
+        diag = np.full((self.case.n, self.case.nlam), -7.0)
+        assert self.L.vrt_continuum_get_operator(self.h, ctypes.byref(op), diag.ctypes.data_as(_lib.p_dbl) if want_diag else None) == 0
+        return op.value, diag
+
+    def set_acceleration(self, start, period):
+        assert self.L.vrt_continuum_set_acceleration(self.h, 2, start, period) == 0
+
+    def close(self):
+        if self.h:
+            self.L.vrt_continuum_destroy(self.h)
+            self.h = ctypes.c_void_p()
+        if self.own is not None:
+            self.own.close()
+            self.own = None
+
+
+def _plan_table(sites, quadrature=QUAD):
+    """the `table` of lambda_star_ref from vrt_plan_get_upwind, and the plan and weights"""
+    plan, w = api._quadrature_plan(sites, quadrature, 3)
+    _, th, _, nq = vrt.read_quadrature(quadrature)
+    table = []
+    for a in range(nq):
+        if th[a] == 90:
+            table.append(None)
+            continue
+        up, _, wt, r = plan.upwind(a)
+        table.append((th[a] > 90, up, wt, r))
+    return table, plan, np.ascontiguousarray(w, dtype=np.float64)
+
+
+@pytest.fixture(scope="module")
+def bcc():
+    """the 648-site grid, its oracle sites and tables, cases per wavelength count and the thick (α × 10) case with its two
+    oracle loops to 1e-4: everything computed once"""
+    pos, nbr, bounds, case1 = bcc_case(1)
+    so = orc.make_sites(pos, nbr, bounds)
+    table, w = oracle_table(so)
+    g = {"pos": pos, "nbr": nbr, "bounds": bounds, "sites": vrt.VoronoiSites(pos, nbr, bounds), "so": so, "table": table,
+         "w": w, "cases": {1: case1}}
+    case10 = scaled_case(case1, 10.0)
+    diag10 = lambda_star_ref(so, table, case10.alpha, w)
+    J_of = lambda S: oracle_J_voronoi(case10, so, S)
+    g["thick"] = {"case": case10, "diag": diag10, "ali": oracle_ali_loop(case10, J_of, diag10, 2000, 1e-4)}
+    return g
+
+
+def _bcc_case(bcc, nlam):
+    if nlam not in bcc["cases"]:
+        bcc["cases"][nlam] = vrt.ContinuumCase(**synth.continuum_case(bcc["pos"], bcc["bounds"], nlam, 11))
+    return bcc["cases"][nlam]
+
+
+@pytest.fixture(scope="module")
+def voro(voro_small):
+    pos, nbr, bounds = voro_small
+    so = orc.make_sites(pos, nbr, bounds)
+    table, w = oracle_table(so)
+    return {"sites": vrt.VoronoiSites(pos, nbr, bounds), "so": so, "table": table, "w": w,
+            "case": vrt.ContinuumCase(**synth.continuum_case(pos, bounds, 2, 3))}
+
+
+def _grid(request, name):
+    return request.getfixturevalue(name)
+
+
+# ---- 4: Λ* against the formula ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("grid", ["bcc", "voro"])
+def test_gpu_lambda_diagonal_matches_the_formula(request, grid):
+    """three columns α · {1e-4, 1, 1e3}: every branch of linear_weights contributes (asserted on the numpy side); then one
+    column in an (n, 3) array, whose padding columns are neither read (they hold NaN) nor written.
+
+    The 1e-12 is applied as tests/test_regular.py applies it to the device's linear_weights against the oracle: to the
+    maximum norm.  Entry by entry it holds only where the formula is well conditioned: in the exponential branch
+    b = 1 - a - e with a = (1 - e)/Δτ - e turns an error δ of e into δ (1/Δτ + 2) of b = Δτ/2 + ..., a relative error
+    2 δ / Δτ², so two correctly written exponentials that differ by one ulp (1.1e-16) differ in b by 9e-10 at
+    Δτ = 5e-4 and by 1e-12 only from Δτ = 0.015 on.  (numpy's exp perturbed by one ulp at random moves Λ* of this case by
+    up to 3.6e-10 in the thin column and 2e-12 in the middle one, 7e-14 in the maximum norm.)  So the entry-wise 1e-12
+    is asserted at the entries whose every exponential-branch Δτ is >= 0.03 -- four ulp of e -- which includes every entry
+    fed by the Taylor and the thick branch alone; the entry-wise figure over all entries is printed."""
+    g = _grid(request, grid)
+    sites, so = g["sites"], g["so"]
+    alpha1 = (g["case"] if grid == "voro" else _bcc_case(g, 1)).alpha[:, :1]
+    table, plan, w = _plan_table(sites)
+    alpha = np.ascontiguousarray(alpha1 * np.array([1e-4, 1.0, 1e3]))
+    ref, branches, mid_min = lambda_star_ref(so, table, alpha, w, return_branches=True)
+    assert branches == {0, 1, 2}
+    got = vrt.lambda_diagonal(sites, alpha, QUAD)
+    assert got.shape == ref.shape
+    err = np.abs(got - ref) / np.where(ref > 0, ref, 1.0)
+    well = mid_min >= 0.03
+    print(f"{grid}: max-norm {np.abs(got - ref).max() / np.abs(ref).max():.3g}; entry-wise {err.max(axis=0)} per column over all "
+          f"entries, {err[well].max():.3g} over the {int(well.sum())} of {well.size} well-conditioned ones")
+    assert np.abs(got - ref).max() <= 1e-12 * np.abs(ref).max()
+    assert well[:, 0].sum() > 100 and well[:, 2].sum() > 100 and err[well].max() <= 1e-12
+    never = ~(updated_mask(so, True) | updated_mask(so, False))
+    assert never.sum() >= 1 and (got[never] == 0.0).all() and (got[~never] > 0).all()
+    assert (got >= 0).all() and (got < 1).all()
+    # the oracle's own upwind tables give the same operator
+    assert np.abs(got - lambda_star_ref(so, g["table"], alpha, g["w"])).max() <= 1e-12 * np.abs(ref).max()
+    # nlam = 1, ld = 3
+    L = _lib.load()
+    wide = np.full((sites.n, 3), np.nan)
+    wide[:, 0] = alpha[:, 1]
+    out = np.full((sites.n, 3), -7.0)
+    d = lambda a: a.ctypes.data_as(_lib.p_dbl)
+    assert L.vrt_plan_lambda_diagonal(plan._h, 1, 3, d(wide), d(w), d(out)) == 0
+    assert np.array_equal(out[:, 0], got[:, 1]) and (out[:, 1:] == -7.0).all()
+    # the same inputs give the same bits
+    assert np.array_equal(vrt.lambda_diagonal(sites, alpha, QUAD), got)
+    # the host form checks α over the columns it reads, before anything is computed
+    for bad in (0.0, -1.0, np.nan, np.inf):
+        wide_bad = wide.copy()
+        wide_bad[5, 0] = bad
+        out_bad = np.full((sites.n, 3), -7.0)
+        assert L.vrt_plan_lambda_diagonal(plan._h, 1, 3, d(wide_bad), d(w), d(out_bad)) == _lib.VRT_EINVAL
+        assert (out_bad == -7.0).all()
+
+
+def test_gpu_lambda_diagonal_dev_on_device_arrays(bcc):
+    """the device-pointer form on torch tensors, with ld > nlam: the bits of the host form"""
+    import torch
+    sites = bcc["sites"]
+    plan, w = api._quadrature_plan(sites, QUAD, 3)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    alpha = _bcc_case(bcc, 3).alpha
+    dev = torch.device("cuda", sites.device)
+    wide = np.full((sites.n, 5), np.nan)
+    wide[:, :3] = alpha
+    d_alpha = torch.from_numpy(wide).to(dev)
+    d_diag = torch.full((sites.n, 5), -7.0, dtype=torch.float64, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    assert _lib.load().vrt_plan_lambda_diagonal_dev(plan._h, 3, 5, d_alpha.data_ptr(), w.ctypes.data_as(_lib.p_dbl),
+                                                    d_diag.data_ptr(), st or None) == 0
+    torch.cuda.synchronize()
+    out = d_diag.cpu().numpy()
+    assert np.array_equal(out[:, :3], vrt.lambda_diagonal(sites, alpha, QUAD)) and (out[:, 3:] == -7.0).all()
+
+
+# ---- 5: Λ* is a lower bound of the true diagonal -------------------------------------------------------------------------------
+def test_gpu_lambda_diagonal_is_a_lower_bound_of_the_true_diagonal(bcc):
+    """the oracle's exact diagonal Λ_ii = J_voronoi(S = e_i, I0_up = 0)[i], all 648 unit sources as the columns of one call"""
+    so, case = bcc["so"], _bcc_case(bcc, 1)
+    w, th, ph, _ = vrt.read_quadrature(QUAD)
+    n1 = int(so.layers_up[1] - 1)
+    J = orc.J_voronoi(w, th, ph, np.eye(so.n), case.alpha[:, 0].copy(), so, I0_up=np.zeros((n1, so.n)), nthreads=4)
+    exact = np.diag(J)
+    got = vrt.lambda_diagonal(bcc["sites"], case.alpha, QUAD)[:, 0]
+    assert (got <= exact * (1 + 1e-12)).all()
+    assert got.sum() > 0.9 * exact.sum()                         # and it is most of it
+
+
+# ---- 6: the session against the oracle-driven ALI loop ---------------------------------------------------------------------------
+@pytest.mark.parametrize("nlam", [1, 2, 3, 5])
+def test_gpu_ali_session_matches_oracle_loop(bcc, nlam):
+    """one half pair; one full pair; two pairs; three pairs"""
+    case, so = _bcc_case(bcc, nlam), bcc["so"]
+    diag = lambda_star_ref(so, bcc["table"], case.alpha, bcc["w"])
+    ref = oracle_ali_loop(case, lambda S: oracle_J_voronoi(case, so, S), diag, 8)
+    got = vrt.Lambda_continuum(0.0, 8, bcc["sites"], case, QUAD, operator="diagonal")
+    _against_oracle(got, ref[:4])
+    plain = vrt.Lambda_continuum(0.0, 8, bcc["sites"], case, QUAD)
+    assert not np.array_equal(plain[1], got[1]) and plain[2][0] != got[2][0]   # (and it is another iteration)
+
+
+def test_gpu_ali_session_matches_oracle_loop_on_a_true_voronoi_grid(voro):
+    case, so = voro["case"], voro["so"]
+    diag = lambda_star_ref(so, voro["table"], case.alpha, voro["w"])
+    ref = oracle_ali_loop(case, lambda S: oracle_J_voronoi(case, so, S), diag, 8)
+    _against_oracle(vrt.Lambda_continuum(0.0, 8, voro["sites"], case, QUAD, operator="diagonal"), ref[:4])
+
+
+# ---- 7: layouts ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nlam", [1, 3, 4])
+def test_gpu_ali_layouts_agree_bit_for_bit(bcc, nlam):
+    """the sweep-order session and the caller-layout session: S, J, the history, and Λ* itself"""
+    case, sites = _bcc_case(bcc, nlam), bcc["sites"]
+    nat = vrt.Lambda_continuum(0.0, 5, sites, case, QUAD, operator="diagonal")
+    cal = vrt.Lambda_continuum(0.0, 5, sites, case, QUAD, operator="diagonal", native=False)
+    assert np.array_equal(nat[0], cal[0]) and np.array_equal(nat[1], cal[1]) and nat[2] == cal[2]
+    want = vrt.lambda_diagonal(sites, case.alpha, QUAD)
+    for native in (True, False):
+        s = _Session(sites, case, native)
+        try:
+            op, diag = s.get_operator()
+            assert op == 0 and (diag == -7.0).all()            # off: diag is not written
+            assert s.set_operator(1) == 0
+            op, diag = s.get_operator()
+            assert op == 1 and np.array_equal(diag, want)
+            assert s.get_operator(want_diag=False)[0] == 1
+            hist = [s.iterate() for _ in range(5)]
+            J, S = s.get()
+            assert hist == nat[2] and np.array_equal(J, nat[0]) and np.array_equal(S, nat[1])
+        finally:
+            s.close()
+
+
+# ---- 8: the standalone update ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nlam,ld", [(3, 5), (1, 1), (4, 4)])
+def test_gpu_ali_update_on_hand_made_arrays(bcc, nlam, ld):
+    """every entry updated, the maximum over the thick ones, their count, NaN seen only there; ld > nlam among the shapes
+    (the padding columns are neither read nor written)"""
+    import torch
+    sites = bcc["sites"]
+    n = sites.n
+    rng = np.random.default_rng(10 + nlam)
+    J, B, S_old = (1.0 + rng.random((n, ld)) for _ in range(3))
+    eps = 10.0 ** rng.uniform(-7, 0, (n, ld))
+    diag = rng.random((n, ld)) * 0.999
+    thick = eps[:, :nlam] > 1e-4
+    S_old[tuple(np.argwhere(~thick)[1])] = 100.0               # the largest term of all sits at a thin entry
+    J += diag * S_old                                          # (J >= Λ* S_old, as every true J is)
+    dev = torch.device("cuda", sites.device)
+    t = lambda a: torch.from_numpy(a).to(dev)
+
+    def run(B_):
+        S_new = torch.full((n, ld), -7.0, dtype=torch.float64, device=dev)
+        diff, cnt = vrt.continuum_ali_update_dev(sites, t(J), t(B_), t(eps), t(diag), t(S_old), S_new, 1e-4, nlam=nlam)
+        return diff, cnt, S_new.cpu().numpy()
+
+    diff, cnt, S_new = run(B)
+    ref = ((1 - eps) * (J - diag * S_old) + eps * B) / (1 - (1 - eps) * diag)
+    assert np.abs(S_new[:, :nlam] / ref[:, :nlam] - 1).max() <= 1e-14 and (S_new[:, nlam:] == -7.0).all()
+    rel = np.abs(1 - S_old / S_new)[:, :nlam]                  # (the criterion of the S the device wrote: exact)
+    assert cnt == int(thick.sum()) and 0 < cnt < n * nlam
+    assert diff == rel[thick].max() and diff != rel.max()
+    thin_at = tuple(np.argwhere(~thick)[0])
+    thick_at = tuple(np.argwhere(thick)[-1])
+    for at, seen in ((thin_at, False), (thick_at, True)):
+        Bn = B.copy()
+        Bn[at] = np.nan
+        d, c, Sn = run(Bn)
+        assert np.isnan(Sn[at]) and c == cnt
+        assert np.isnan(d) if seen else d == diff
+    # Λ* = 0 is the plain update, bit for bit
+    S_plain = torch.full((n, ld), -7.0, dtype=torch.float64, device=dev)
+    d0, c0 = vrt.continuum_update_dev(sites, t(J), t(B), t(eps), t(S_old), S_plain, 1e-4, nlam=nlam)
+    S_zero = torch.full((n, ld), -7.0, dtype=torch.float64, device=dev)
+    d1, c1 = vrt.continuum_ali_update_dev(sites, t(J), t(B), t(eps), t(np.zeros((n, ld))), t(S_old), S_zero, 1e-4, nlam=nlam)
+    assert (d0, c0) == (d1, c1) and torch.equal(S_plain, S_zero)
+
+
+# ---- 9: it pays where cells are thick ------------------------------------------------------------------------------------------------
+def test_gpu_ali_needs_fewer_iterates_on_the_thick_case(bcc):
+    """bcc_case(1) with α × 10, to 1e-4: the ALI session's count is the oracle ALI loop's (± 1 for rounding at the threshold)
+    and strictly smaller than the plain session's"""
+    thick, sites = bcc["thick"], bcc["sites"]
+    ali = vrt.Lambda_continuum(1e-4, 2000, sites, thick["case"], QUAD, operator="diagonal")
+    plain = vrt.Lambda_continuum(1e-4, 2000, sites, thick["case"], QUAD)
+    ref = thick["ali"]
+    print(f"alpha x 10 to 1e-4: plain session {len(plain[2])} iterates, ALI session {len(ali[2])}, oracle ALI loop {len(ref[2])}")
+    assert ali[2][-1] <= 1e-4 and plain[2][-1] <= 1e-4
+    assert abs(len(ali[2]) - len(ref[2])) <= 1
+    assert len(ali[2]) < len(plain[2])
+    assert (ali[1] > 0).all()
+
+
+# ---- 10: the same fixed point, and switching -----------------------------------------------------------------------------------------
+def _passes_the_plain_check(s, last, decade=10.0):
+    """S_fs - S = den (S_ali - S) with den in (0, 1]: from the S an ALI run stopped at, the plain change is never larger than
+    the ALI change.  `last` is the scalar the ALI run stopped with; a decade is left for the two relative denominators."""
+    assert s.set_operator(0) == 0 and s.get_operator(want_diag=False)[0] == 0
+    d_plain = s.iterate()
+    assert d_plain < decade * last, (d_plain, last)
+    assert s.set_operator(1) == 0 and s.get_operator(want_diag=False)[0] == 1
+    d_ali = s.iterate()
+    assert d_ali < decade * last, (d_ali, last)
+    return d_plain, d_ali
+
+
+@pytest.mark.parametrize("native", [True, False])
+def test_gpu_ali_reaches_the_plain_fixed_point_and_switches(bcc, native):
+    """the unscaled bcc_case(1): ALI to a scalar < 1e-10, then one plain iterate returns a scalar < 1e-9, and so does one more
+    ALI iterate after the operator is turned on again"""
+    s = _Session(bcc["sites"], _bcc_case(bcc, 1), native)
+    try:
+        assert s.set_operator(1) == 0
+        d, count = 1.0, 0
+        while d >= 1e-10 and count < 400:
+            d = s.iterate()
+            count += 1
+        assert d < 1e-10                                         # (the oracle ALI loop takes 92 iterates)
+        d_plain, d_ali = _passes_the_plain_check(s, 1e-10)
+        print(f"native={native}: ALI reached {d:.3g} after {count} iterates; one plain iterate {d_plain:.3g}, one more ALI {d_ali:.3g}")
+        assert s.set_operator(2) == _lib.VRT_EINVAL and s.get_operator(want_diag=False)[0] == 1
+    finally:
+        s.close()
+
+
+# ---- 11: ALI with Ng -------------------------------------------------------------------------------------------------------------------
+def test_gpu_ali_composes_with_ng(bcc):
+    thick, sites = bcc["thick"], bcc["sites"]
+    s = _Session(sites, thick["case"])
+    try:
+        assert s.set_operator(1) == 0
+        s.set_acceleration(4, 4)
+        hist, applied = [], []
+        while (not hist or hist[-1] > 1e-4) and len(hist) < 400:
+            hist.append(s.iterate())
+            a = ctypes.c_int()
+            assert s.L.vrt_continuum_last_acceleration(s.h, ctypes.byref(a), None, None) == 0
+            applied.append(a.value)
+            assert (s.get()[1] > 0).all()
+        print(f"alpha x 10 to 1e-4 with ALI and Ng (4, 4): {len(hist)} iterates, steps taken at "
+              f"{[i + 1 for i, a in enumerate(applied) if a == 1]}, rejected at {[i + 1 for i, a in enumerate(applied) if a == -1]}")
+        assert hist[-1] <= 1e-4
+        _passes_the_plain_check(s, 1e-4)
+    finally:
+        s.close()
+    # the api keyword composes the same way, and twice gives the same bits
+    a = vrt.Lambda_continuum(1e-4, 400, sites, thick["case"], QUAD, operator="diagonal", ng=(4, 4))
+    b = vrt.Lambda_continuum(1e-4, 400, sites, thick["case"], QUAD, operator="diagonal", ng=(4, 4))
+    assert a[2] == hist and np.array_equal(a[1], b[1]) and a[3] == b[3]
+
+
+# ---- 12: refusal -----------------------------------------------------------------------------------------------------------------------
+def test_gpu_ali_refuses_a_vanishing_denominator(bcc):
+    """α = 1e17 everywhere: Δτ > 2^53 in every cell, b = 1 - 1/Δτ rounds to 1.0 and Λ* to Σ_a w_a (w_1 + w_2), which is >= 1
+    in rounding at most interior sites of this grid; with ε = 0 at one of them den = 1 - Λ* <= 0 (checked on the numpy
+    side first) and set_operator(1) answers VRT_EINVAL.  The session is untouched: it iterates as a plain one, with the
+    bits of a fresh plain session."""
+    case1, so, sites = _bcc_case(bcc, 1), bcc["so"], bcc["sites"]
+    alpha = np.full_like(case1.alpha, 1e17)
+    diag = lambda_star_ref(so, bcc["table"], alpha, bcc["w"])
+    at = int(np.argmax(diag[:, 0]))
+    eps = case1.eps.copy()
+    eps[at, 0] = 0.0
+    assert 1 - (1 - eps[at, 0]) * diag[at, 0] <= 0
+    case = vrt.ContinuumCase(alpha, eps, case1.B0, case1.eps_thick)
+    case.check()
+    s, fresh = _Session(sites, case), _Session(sites, case)
+    try:
+        assert s.set_operator(1) == _lib.VRT_EINVAL
+        assert s.get_operator(want_diag=False)[0] == 0
+        assert [s.iterate() for _ in range(3)] == [fresh.iterate() for _ in range(3)]
+        (J, S), (Jf, Sf) = s.get(), fresh.get()
+        assert np.array_equal(J, Jf) and np.array_equal(S, Sf)
+    finally:
+        s.close()
+        fresh.close()
+    with pytest.raises(vrt.VrtError) as e:
+        vrt.Lambda_continuum(0.0, 1, sites, case, QUAD, operator="diagonal")
+    assert e.value.code == _lib.VRT_EINVAL
+    # with ε > 0 there the same Λ* is accepted
+    assert ((1 - (1 - case1.eps) * diag) > 0).all()
+    ok = vrt.ContinuumCase(alpha, case1.eps, case1.B0, case1.eps_thick)
+    assert len(vrt.Lambda_continuum(0.0, 1, sites, ok, QUAD, operator="diagonal")[2]) == 1

@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""diagnostics: what the diagonal operator of the continuum Λ-iteration session costs (vrt_continuum_set_operator), at the
+size of BASELINE C2 (246 420 sites x ul7n12 x 1 λ, --a 37 --c 90):
+
+  plain_iterate   wall time of the synchronous vrt_continuum_iterate of a plain session
+  ali_iterate     the same after vrt_continuum_set_operator(s, 1): one more plane-set read in the update kernel
+  set_operator    wall time of vrt_continuum_set_operator(s, 1) itself: Λ* (k_lambda_diagonal), min den, the up-order
+                  plane set; once per session (measured on a fresh session each time)
+  plain_update / ali_update
+                  vrt_continuum_update_dev / vrt_continuum_ali_update_dev alone (caller layout, the same element count;
+                  each reads the scalar back itself)
+
+Median and min..max over the repeats after warm-up; the two iterates are measured in alternating blocks on two sessions
+of one process.  `--plain-only` measures the plain iterate alone and needs no new entry: run it with VRT_LIB_PATH pointing
+at a build of the parent commit for the A/B.  The probe ends itself after --limit seconds.
+
+    python tools/ali_probe.py [--a 37 --c 90] [--nlam 1] [--reps 40] [--blocks 3] [--plain-only] [--json out.json]
+"""
+import argparse
+import ctypes
+import json
+import os
+import signal
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import voronoirt_amd as vrt                     # noqa: E402
+from voronoirt_amd import _lib, api, synth      # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--a", type=int, default=37)
+ap.add_argument("--c", type=int, default=90)
+ap.add_argument("--nlam", type=int, default=1)
+ap.add_argument("--reps", type=int, default=40)
+ap.add_argument("--blocks", type=int, default=3, help="alternating blocks of --reps iterates per session")
+ap.add_argument("--plain-only", action="store_true", help="the plain iterate alone (works with a library of the parent commit)")
+ap.add_argument("--limit", type=int, default=240, help="seconds after which the probe ends itself")
+ap.add_argument("--json", default="")
+args = ap.parse_args()
+signal.alarm(args.limit)
+
+pos, nbr, bounds = synth.bcc_grid(args.a, args.c, seed=2022)
+sites = vrt.VoronoiSites(pos, nbr, bounds, device=0)
+n, nlam = sites.n, args.nlam
+kw = synth.continuum_case(pos, bounds, nlam, seed=5)
+quad = "ul7n12.dat"
+plan, w = api._quadrature_plan(sites, quad, 3)
+L = _lib.load()
+case = vrt.ContinuumCase(**kw)
+cc = case.c_struct()
+wd = np.ascontiguousarray(w, dtype=np.float64)
+
+
+def stats(xs):
+    return {"median_ms": statistics.median(xs), "min_ms": min(xs), "max_ms": max(xs), "reps": len(xs)}
+
+
+def session():
+    h = ctypes.c_void_p()
+    api.check(L.vrt_continuum_create(plan._h, ctypes.byref(cc), wd.ctypes.data_as(_lib.p_dbl), ctypes.byref(h)))
+    return h
+
+
+def iterates(h, reps, out):
+    d = ctypes.c_double()
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        api.check(L.vrt_continuum_iterate(h, ctypes.byref(d)))
+        out.append(1e3 * (time.perf_counter() - t0))
+    return d.value
+
+
+res = {"sites": n, "nlam": nlam, "quadrature": quad, "lib": os.path.basename(_lib.LIB_PATH), "plain_only": args.plain_only}
+plain = session()
+iterates(plain, 5, [])                                         # warm-up
+t_plain, t_ali, t_set = [], [], []
+if args.plain_only:
+    for _ in range(args.blocks):
+        iterates(plain, args.reps, t_plain)
+else:
+    for _ in range(5):                                         # the one-time cost, on fresh sessions
+        h = session()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        api.check(L.vrt_continuum_set_operator(h, 1))
+        t_set.append(1e3 * (time.perf_counter() - t0))
+        L.vrt_continuum_destroy(h)
+    ali = session()
+    api.check(L.vrt_continuum_set_operator(ali, 1))
+    iterates(ali, 5, [])
+    for _ in range(args.blocks):
+        iterates(plain, args.reps, t_plain)
+        res["ali_last_scalar"] = iterates(ali, args.reps, t_ali)
+    res["ali_iterate_wall"] = stats(t_ali)
+    res["set_operator_wall"] = stats(t_set[1:])
+    res["set_operator_first_ms"] = t_set[0]
+    L.vrt_continuum_destroy(ali)
+    # ---- the two update kernels alone, caller layout ---------------------------------------------------------------------
+    dev = torch.device("cuda", 0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    B, J, E, S_old = t(kw["B0"]), t(kw["B0"] * 0.9), t(kw["eps"]), t(kw["B0"])
+    S_new = torch.empty_like(B)
+    D = t(vrt.lambda_diagonal(sites, kw["alpha"], quad))
+
+    def timed(fn, reps, warm=5):
+        out = []
+        for i in range(warm + reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            if i >= warm:
+                out.append(1e3 * (time.perf_counter() - t0))
+        return out
+
+    res["plain_update_wall"] = stats(timed(lambda: vrt.continuum_update_dev(sites, J, B, E, S_old, S_new, 1e-4), args.reps))
+    res["ali_update_wall"] = stats(timed(lambda: vrt.continuum_ali_update_dev(sites, J, B, E, D, S_old, S_new, 1e-4), args.reps))
+    res["ali_minus_plain_iterate_ms"] = res["ali_iterate_wall"]["median_ms"] - statistics.median(t_plain)
+res["plain_iterate_wall"] = stats(t_plain)
+L.vrt_continuum_destroy(plain)
+
+print(json.dumps(res))
+if args.json:
+    os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+    with open(args.json, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")

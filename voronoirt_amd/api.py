@@ -1631,12 +1631,51 @@ def continuum_update_dev(sites: VoronoiSites, J, B, eps, S_old, S_new, eps_thick
     return out.value, int(cnt.value)
 
 
-def _continuum_loop(L, prefix: str, h, case: ContinuumCase, eps_conv: float, maxiter: int, ng, S0, who: str):
+def lambda_diagonal(sites: VoronoiSites, alpha, quadrature: str, n_sweeps: int = 3) -> np.ndarray:
+    """The diagonal approximate operator Λ* of accelerated Λ-iteration (`vrt_plan_lambda_diagonal`): per (site, wavelength)
+    the coefficient of the site's own S in the last Gauss-Seidel visit of every angle of `quadrature`, summed with the
+    quadrature weights.  alpha (n,) or (n, nλ), finite and > 0; returns (n, nλ)."""
+    alpha = _f64(alpha)
+    if alpha.ndim == 1:
+        alpha = alpha.reshape(-1, 1)
+    if alpha.ndim != 2 or alpha.shape[0] != sites.n:
+        raise ValueError(f"lambda_diagonal: alpha must be ({sites.n},) or ({sites.n}, nlam)")
+    plan, w = _quadrature_plan(sites, quadrature, n_sweeps)
+    diag = np.zeros_like(alpha)
+    check(_lib.load().vrt_plan_lambda_diagonal(plan._h, alpha.shape[1], alpha.shape[1], _d(alpha), _d(_f64(w)), _d(diag)))
+    return diag
+
+
+def continuum_ali_update_dev(sites: VoronoiSites, J, B, eps, diag, S_old, S_new, eps_thick: float = 1e-4,
+                             nlam: int | None = None):
+    """`continuum_update_dev` with the diagonal operator (`vrt_continuum_ali_update_dev`): with t = 1 - ε,
+    S_new = (t (J - Λ* S_old) + ε B) / (1 - t Λ*), `diag` = Λ* as one more (n, ld) tensor; the same criterion and
+    return value."""
+    import torch
+    n, ld = S_new.shape
+    for t in (J, B, eps, diag, S_old, S_new):
+        if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != (n, ld):
+            raise ValueError("continuum_ali_update_dev: contiguous float64 tensors of one (n, ld) shape")
+    out, cnt = ctypes.c_double(), ctypes.c_int64()
+    st = torch.cuda.current_stream(S_new.device).cuda_stream
+    check(_lib.load().vrt_continuum_ali_update_dev(sites.handle, int(ld if nlam is None else nlam), int(ld), J.data_ptr(),
+                                                   B.data_ptr(), eps.data_ptr(), diag.data_ptr(), float(eps_thick),
+                                                   S_old.data_ptr(), S_new.data_ptr(), ctypes.byref(out), ctypes.byref(cnt),
+                                                   st or None))
+    return out.value, int(cnt.value)
+
+
+_OPERATORS = {None: 0, "diagonal": 1}
+
+
+def _continuum_loop(L, prefix: str, h, case: ContinuumCase, eps_conv: float, maxiter: int, ng, S0, who: str, operator=None):
     fn = lambda name: getattr(L, prefix + name)
     steps, history, diff, i = [], [], 1.0, 0                   # criterion(S_new = B, S_old = 0) = 1
     if S0 is not None:
         S0 = _f64(S0).reshape(case.n, case.nlam)
         check(fn("set_source")(h, _d(S0)))
+    if operator is not None:
+        check(fn("set_operator")(h, _OPERATORS[operator]))
     if ng is not None:
         check(fn("set_acceleration")(h, 2, *_ng_settings(ng)))
     while diff > eps_conv and i < maxiter:                     # criterion: diff > ϵ && i < maxiter, :178, :197
@@ -1656,16 +1695,19 @@ def _continuum_loop(L, prefix: str, h, case: ContinuumCase, eps_conv: float, max
 
 
 def Lambda_continuum(eps_conv: float, maxiter: int, sites: VoronoiSites, case: ContinuumCase, quadrature: str, ng=None,
-                     S0=None, native: bool = True, n_sweeps: int = 3):
+                     S0=None, native: bool = True, n_sweeps: int = 3, operator=None):
     """Λ_voronoi of src/lambda_continuum.jl:109-160 with library-owned device state (`vrt_continuum_create` /
     `_iterate` / `_get`): one call per iteration, only the criterion's scalar -- the maximum over the thick entries --
     comes back inside the loop.  Starts from S = B_0, or from S0 (n, nλ) (`vrt_continuum_set_source`: a warm start or a
     resumed run).  native=False keeps the caller's layout inside the session (VRT_LAMBDA_NATIVE=0): the same bits.
     Returns (J, S_new, history); ng=(start, period) as for `Lambda_voronoi_host`, with the list of (iterate, applied, a,
-    b) as a fourth element."""
+    b) as a fourth element.  operator="diagonal": accelerated Λ-iteration with the local operator Λ*
+    (`vrt_continuum_set_operator`; `lambda_diagonal` returns that Λ*), which composes with ng."""
     L = _lib.load()
     if case.n != sites.n:
         raise ValueError(f"the continuum case has {case.n} points, the grid {sites.n}")
+    if operator not in _OPERATORS:
+        raise ValueError(f"Lambda_continuum: operator must be None or 'diagonal', not {operator!r}")
     if native:
         plan, w = _quadrature_plan(sites, quadrature, n_sweeps)
         own = None
@@ -1678,7 +1720,7 @@ def Lambda_continuum(eps_conv: float, maxiter: int, sites: VoronoiSites, case: C
     h = ctypes.c_void_p()
     try:
         check(L.vrt_continuum_create(plan._h, ctypes.byref(cc), _d(_f64(w)), ctypes.byref(h)))
-        return _continuum_loop(L, "vrt_continuum_", h, case, eps_conv, maxiter, ng, S0, "Lambda_continuum")
+        return _continuum_loop(L, "vrt_continuum_", h, case, eps_conv, maxiter, ng, S0, "Lambda_continuum", operator)
     finally:
         if h:
             L.vrt_continuum_destroy(h)

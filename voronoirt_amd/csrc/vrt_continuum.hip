@@ -16,6 +16,12 @@
 //                                  on the raster in the caller's layout
 // The update's operations and their order are those of k_lambda_update (vrt_kernels.hip); Ng acceleration is that of
 // vrt_accel.hip (ng_after_iterate), over all n nlam physical entries, thin ones included.
+//
+// Accelerated Λ-iteration (Olson, Auer & Buchler 1986) on the Voronoi session, vrt_continuum_set_operator(s, 1): the local
+// operator Λ*[i,l] = Σ_a w_a upd(a,i) ((w_1 b(Δτ_1)) + (w_2 b(Δτ_2))) is the coefficient of a site's own S in the last
+// Gauss-Seidel visit of every angle (k_lambda_diagonal, once per session: α does not change), and the update becomes
+//   S_new = ((1 - ε) (J - Λ* S_old) + ε B_0) / (1 - (1 - ε) Λ*)
+// in both layouts (the ALI instantiations of the two update kernels; Λ* of the sweep-order one is an up-order plane set).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -74,21 +80,35 @@ __device__ __forceinline__ void crit_reduce(const Crit &c, unsigned long long *_
     }
 }
 
-// caller layout: J, B, eps, S (n, ld) rows, wavelength fastest; grid-stride over the n nlam entries
+// one entry of the update: plain Λ-iteration, or -- ALI -- with the local operator L = Λ*.  The ALI form is
+// S_old + (S_fs - S_old) / den written so that num >= 0: every coefficient of Λ is >= 0 and Λ* <= Λ_ii
+template <bool ALI>
+__device__ __forceinline__ double update_entry(double e, double J, double B, double L, double s_old)
+{
+    if (!ALI) return (1.0 - e) * J + e * B;
+    const double t = 1.0 - e;
+    const double num = t * (J - L * s_old) + e * B;
+    const double den = 1.0 - t * L;
+    return num / den;
+}
+
+// caller layout: J, B, eps, S (and Λ*) (n, ld) rows, wavelength fastest; grid-stride over the n nlam entries
+template <bool ALI>
 __global__ void __launch_bounds__(256)
 k_continuum_update(int64_t n, int64_t nlam, int64_t ld, const double *__restrict__ J, const double *__restrict__ B,
-                   const double *__restrict__ eps, double eps_thick, const double *__restrict__ S_old,
-                   double *__restrict__ S_new, unsigned long long *__restrict__ result /* max bits, NaN flag, thick count */)
+                   const double *__restrict__ eps, const double *__restrict__ diag, double eps_thick,
+                   const double *__restrict__ S_old, double *__restrict__ S_new,
+                   unsigned long long *__restrict__ result /* max bits, NaN flag, thick count */)
 {
     const int64_t total = n * nlam;
     Crit c;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t site = t / nlam, l = t - site * nlam;
         const size_t o = (size_t)site * ld + l;
-        const double e = eps[o];
-        const double s_new = (1.0 - e) * J[o] + e * B[o];
+        const double e = eps[o], s_old = S_old[o];
+        const double s_new = update_entry<ALI>(e, J[o], B[o], ALI ? diag[o] : 0.0, s_old);
         S_new[o] = s_new;
-        crit_entry(c, e, eps_thick, S_old[o], s_new);
+        crit_entry(c, e, eps_thick, s_old, s_new);
     }
     crit_reduce(c, result);
 }
@@ -96,20 +116,22 @@ k_continuum_update(int64_t n, int64_t nlam, int64_t ld, const double *__restrict
 // Sweep-order plane sets ([pair][pos][2] per direction): one thread per UP position walks the wavelength pairs.  J = J_up +
 // J_down as k_combine_J forms it, B and ε from the up plane set, the old S read from the up plane it is written back to,
 // the down-order copy of S_new written beside it: the operations of k_continuum_update on the same values.  An odd nlam
-// carries its padding wavelength as zeros, outside both the criterion and the thick count.
+// carries its padding wavelength as zeros, outside both the criterion and the thick count.  ALI: Λ* from its up-order
+// plane set Lu, one more load per pair.
+template <bool ALI>
 __global__ void __launch_bounds__(256)
 k_continuum_update_native(int64_t n, int npair, int nlam, const int32_t *__restrict__ store_up,
                           const int32_t *__restrict__ rank_down, const double2 *__restrict__ Ju,
                           const double2 *__restrict__ Jd, const double2 *__restrict__ Bu, const double2 *__restrict__ Eu,
-                          double eps_thick, double2 *__restrict__ Su, double2 *__restrict__ Sd,
-                          unsigned long long *__restrict__ result)
+                          const double2 *__restrict__ Lu, double eps_thick, double2 *__restrict__ Su,
+                          double2 *__restrict__ Sd, unsigned long long *__restrict__ result)
 {
     Crit c;
     for (int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pos < n; pos += (int64_t)gridDim.x * blockDim.x) {
         const size_t pd = (size_t)rank_down[store_up[pos]];
         constexpr int U = 2;                                // (five loads per pair: two pairs in flight; the continuum has few)
         for (int q0 = 0; q0 < npair; q0 += U) {
-            double2 J[U], B[U], E[U], So[U];
+            double2 J[U], B[U], E[U], So[U], L[U];
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const int q = q0 + u < npair ? q0 + u : npair - 1;
@@ -120,6 +142,7 @@ k_continuum_update_native(int64_t n, int npair, int nlam, const int32_t *__restr
                 B[u] = Bu[t];
                 E[u] = Eu[t];
                 So[u] = Su[t];
+                L[u] = ALI ? Lu[t] : make_double2(0.0, 0.0);
             }
 #pragma unroll
             for (int u = 0; u < U; u++) {
@@ -127,8 +150,8 @@ k_continuum_update_native(int64_t n, int npair, int nlam, const int32_t *__restr
                 if (q >= npair) break;
                 const size_t t = (size_t)q * (size_t)n + (size_t)pos;
                 double2 Sn;
-                Sn.x = (1.0 - E[u].x) * J[u].x + E[u].x * B[u].x;
-                Sn.y = (1.0 - E[u].y) * J[u].y + E[u].y * B[u].y;
+                Sn.x = update_entry<ALI>(E[u].x, J[u].x, B[u].x, L[u].x, So[u].x);
+                Sn.y = update_entry<ALI>(E[u].y, J[u].y, B[u].y, L[u].y, So[u].y);
                 const bool second = 2 * q + 1 < nlam;
                 if (!second) Sn.y = 0.0;
                 Su[t] = Sn;
@@ -141,32 +164,140 @@ k_continuum_update_native(int64_t n, int npair, int nlam, const int32_t *__restr
     crit_reduce(c, result);
 }
 
+// d_diag: Λ* in the layout of the other arrays, or NULL for the plain update
 int launch_continuum_update(int64_t n, int64_t nlam, int64_t ld, const double *dJ, const double *dB, const double *deps,
-                            double eps_thick, const double *dS_old, double *dS_new, unsigned long long *d_result,
-                            hipStream_t st)
+                            const double *d_diag, double eps_thick, const double *dS_old, double *dS_new,
+                            unsigned long long *d_result, hipStream_t st)
 {
     VRT_HIP_TRY(hipMemsetAsync(d_result, 0, 3 * sizeof(unsigned long long), st));
     const int64_t blocks = std::min<int64_t>((n * nlam + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(k_continuum_update, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, n, nlam, ld, dJ, dB,
-                       deps, eps_thick, dS_old, dS_new, d_result);
+    const dim3 grid((unsigned)std::max<int64_t>(blocks, 1));
+    if (d_diag)
+        hipLaunchKernelGGL(k_continuum_update<true>, grid, dim3(256), 0, st, n, nlam, ld, dJ, dB, deps, d_diag, eps_thick,
+                           dS_old, dS_new, d_result);
+    else
+        hipLaunchKernelGGL(k_continuum_update<false>, grid, dim3(256), 0, st, n, nlam, ld, dJ, dB, deps, d_diag, eps_thick,
+                           dS_old, dS_new, d_result);
     VRT_HIP_TRY(hipGetLastError());
     return VRT_OK;
 }
 
 int launch_continuum_update_native(vrt_grid *g, int64_t nlam, const double *dJ_up, const double *dJ_down, const double *dB_up,
-                                   const double *dE_up, double eps_thick, double *dS_up, double *dS_down,
-                                   unsigned long long *d_result, hipStream_t st)
+                                   const double *dE_up, const double *dL_up, double eps_thick, double *dS_up,
+                                   double *dS_down, unsigned long long *d_result, hipStream_t st)
 {
     VRT_HIP_TRY(hipMemsetAsync(d_result, 0, 3 * sizeof(unsigned long long), st));
     const int npair = (int)((nlam + 1) / 2);
     const int64_t blocks = std::min<int64_t>((g->n + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(k_continuum_update_native, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, g->n, npair,
-                       (int)nlam, g->up.d_store, g->down.d_srank, reinterpret_cast<const double2 *>(dJ_up),
-                       reinterpret_cast<const double2 *>(dJ_down), reinterpret_cast<const double2 *>(dB_up),
-                       reinterpret_cast<const double2 *>(dE_up), eps_thick, reinterpret_cast<double2 *>(dS_up),
-                       reinterpret_cast<double2 *>(dS_down), d_result);
+    const dim3 grid((unsigned)std::max<int64_t>(blocks, 1));
+#define VRT_UPDATE_NATIVE(ALI)                                                                                             \
+    hipLaunchKernelGGL(k_continuum_update_native<ALI>, grid, dim3(256), 0, st, g->n, npair, (int)nlam, g->up.d_store,      \
+                       g->down.d_srank, reinterpret_cast<const double2 *>(dJ_up),                                          \
+                       reinterpret_cast<const double2 *>(dJ_down), reinterpret_cast<const double2 *>(dB_up),               \
+                       reinterpret_cast<const double2 *>(dE_up), reinterpret_cast<const double2 *>(dL_up), eps_thick,      \
+                       reinterpret_cast<double2 *>(dS_up), reinterpret_cast<double2 *>(dS_down), d_result)
+    if (dL_up) VRT_UPDATE_NATIVE(true);
+    else VRT_UPDATE_NATIVE(false);
+#undef VRT_UPDATE_NATIVE
     VRT_HIP_TRY(hipGetLastError());
     return VRT_OK;
+}
+
+// ---- the local operator Λ* --------------------------------------------------------------------------------------------
+// per ACTIVE angle: its quadrature weight and whether it is a down angle (kernel argument, as WeightTable of vrt_kernels.hip)
+struct DiagAngles {
+    double w[kMaxAngles];
+    int down[kMaxAngles];
+};
+
+// Λ*[i,l] = Σ_a w_a upd(a,i) ((w_1 b(Δτ_1)) + (w_2 b(Δτ_2))), Δτ_r = r_r (α[i,l] + α[up_r,l]) / 2 as the sweep forms it
+// (k_sweep_level), b the third coefficient of linear_weights: the coefficient of S[i] in the last visit of site i by every
+// angle.  upd(a,i) = 0 where the sweep of angle a never writes site i: the n1 sites of layer 1 of the angle's direction
+// (their I is I_0) and the never-visited last site perm[n] (sweep positions < n1, and n - 1).  One thread per site, the
+// angles in order, slot 1 then slot 2, the wavelengths inside: the tables [A][n] are read coalesced over the sites, once
+// per angle; the α[up_r] rows are the only gathers.  No atomics: the same inputs give the same bits.  Runs once per
+// session.  alpha and diag are (n, ld) rows; the padding columns are neither read nor written.
+__global__ void __launch_bounds__(256)
+k_lambda_diagonal(int64_t n, int nlam, int64_t ld, int A, DiagAngles ang, int32_t n1_up, int32_t n1_down,
+                  const int32_t *__restrict__ rank_up, const int32_t *__restrict__ rank_down,
+                  const int32_t *__restrict__ up1, const int32_t *__restrict__ up2, const double *__restrict__ w1,
+                  const double *__restrict__ w2, const double *__restrict__ r1, const double *__restrict__ r2,
+                  const double *__restrict__ alpha, double *diag)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t o = (size_t)i * (size_t)ld;
+    for (int l = 0; l < nlam; l++) diag[o + l] = 0.0;
+    const int32_t pos_up = rank_up[i], pos_down = rank_down[i];
+    for (int a = 0; a < A; a++) {
+        const int32_t pos = ang.down[a] ? pos_down : pos_up;
+        if (pos < (ang.down[a] ? n1_down : n1_up) || (int64_t)pos == n - 1) continue;
+        const size_t row = (size_t)a * (size_t)n + (size_t)i;
+        const int32_t u1 = up1[row], u2 = up2[row];
+        const double W1 = w1[row], W2 = w2[row], R1 = r1[row], R2 = r2[row];
+        const bool in1 = u1 >= 0 && (int64_t)u1 < n, in2 = u2 >= 0 && (int64_t)u2 < n;     // (a visited site has both)
+        for (int l = 0; l < nlam; l++) {
+            const double a_c = alpha[o + l];
+            double ca, cb, ce, t1 = 0.0, t2 = 0.0;
+            if (in1) {
+                linear_weights_ref_order(R1 * (a_c + alpha[(size_t)u1 * (size_t)ld + l]) / 2.0, ca, cb, ce);
+                t1 = W1 * cb;
+            }
+            if (in2) {
+                linear_weights_ref_order(R2 * (a_c + alpha[(size_t)u2 * (size_t)ld + l]) / 2.0, ca, cb, ce);
+                t2 = W2 * cb;
+            }
+            diag[o + l] += ang.w[a] * (t1 + t2);
+        }
+    }
+}
+
+// caller holds p->mu and has chosen the device; weights per USER angle (θ = 90 angles have no table and add nothing)
+int launch_lambda_diagonal(vrt_plan *p, int64_t nlam, int64_t ld, const double *d_alpha, const double *weights, double *d_diag,
+                           hipStream_t st)
+{
+    vrt_grid *g = p->g;
+    if (p->A > kMaxAngles) return fail(VRT_EINVAL, "too many active angles");
+    if (nlam > INT32_MAX) return fail(VRT_EINVAL, "nlam too large");
+    DiagAngles ang;
+    for (int a = 0; a < kMaxAngles; a++) {
+        ang.w[a] = a < p->A ? weights[(size_t)p->user_of_active[(size_t)a]] : 0.0;
+        ang.down[a] = a < p->A && p->dir_of_active[(size_t)a] < 0;
+    }
+    const int64_t blocks = (g->n + 255) / 256;
+    hipLaunchKernelGGL(k_lambda_diagonal, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, g->n, (int)nlam, ld,
+                       p->A, ang, (int32_t)g->up.n1, (int32_t)g->down.n1, g->up.d_rank, g->down.d_rank, p->d_up1, p->d_up2,
+                       p->d_w1, p->d_w2, p->d_r1, p->d_r2, d_alpha, d_diag);
+    VRT_HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+// min over the entries of den = 1 - (1 - ε) Λ*: result[0] the minimum's IEEE bits (over the entries with den > 0; preset to
+// all ones), result[1] set when an entry's den is not > 0.  Caller layout, (n, nlam) dense.
+__global__ void __launch_bounds__(256)
+k_ali_min_den(int64_t total, const double *__restrict__ eps, const double *__restrict__ diag,
+              unsigned long long *__restrict__ result)
+{
+    __shared__ double wmin[4];
+    __shared__ int wbad[4];
+    double m = INFINITY;
+    bool bad = false;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const double den = 1.0 - (1.0 - eps[t]) * diag[t];
+        if (den > 0.0) m = fmin(m, den);
+        else bad = true;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off, 64));
+    const unsigned long long any_bad = __ballot(bad);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { wmin[wave] = m; wbad[wave] = any_bad != 0ull; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double mm = fmin(fmin(wmin[0], wmin[1]), fmin(wmin[2], wmin[3]));
+        atomicMin(&result[0], (unsigned long long)__double_as_longlong(mm));
+        if (wbad[0] | wbad[1] | wbad[2] | wbad[3]) atomicMax(&result[1], 1ull);
+    }
 }
 
 // the three words of an update -> the criterion's scalar (NaN like Julia's maximum) and the thick count; synchronises st
@@ -239,6 +370,10 @@ struct vrt_continuum {
     DevBuf<unsigned long long> d_scalars;
     int64_t iterations = 0;
     NgState ng;                         // vrt_continuum_set_acceleration (off: nothing allocated, nothing run)
+    // vrt_continuum_set_operator (0: nothing allocated, nothing run): Λ* in the caller's layout (n, nlam), and -- native --
+    // its up-order plane set
+    int op = 0;
+    DevBuf<double> d_diag, d_L_up;
     ~vrt_continuum() { ng_release(ng); }
 };
 
@@ -310,8 +445,69 @@ int vrt_continuum_update_dev(vrt_grid *g, int64_t nlam, int64_t ld, const double
         std::lock_guard<std::mutex> lock(g->mu);
         if (!g->d_scalars && (rc = dev_alloc(&g->d_scalars, kUpdateWords))) return rc;
         hipStream_t st = (hipStream_t)stream;
-        if ((rc = launch_continuum_update(g->n, nlam, ld, dJ, dB, deps, eps_thick, dS_old, dS_new, g->d_scalars, st))) return rc;
+        if ((rc = launch_continuum_update(g->n, nlam, ld, dJ, dB, deps, nullptr, eps_thick, dS_old, dS_new, g->d_scalars, st)))
+            return rc;
         return read_criterion(g->d_scalars, st, max_rel_change, n_thick);
+    });
+}
+
+int vrt_continuum_ali_update_dev(vrt_grid *g, int64_t nlam, int64_t ld, const double *dJ, const double *dB, const double *deps,
+                                 const double *d_diag, double eps_thick, const double *dS_old, double *dS_new,
+                                 double *max_rel_change, int64_t *n_thick, void *stream)
+{
+    if (!g || !dJ || !dB || !deps || !d_diag || !dS_old || !dS_new || !max_rel_change) return fail(VRT_EINVAL, "NULL argument");
+    if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
+    if (!std::isfinite(eps_thick)) return fail(VRT_EINVAL, "eps_thick must be finite");
+    return guarded([&] {
+        int rc = use_device(g->device);
+        if (rc) return rc;
+        std::lock_guard<std::mutex> lock(g->mu);
+        if (!g->d_scalars && (rc = dev_alloc(&g->d_scalars, kUpdateWords))) return rc;
+        hipStream_t st = (hipStream_t)stream;
+        if ((rc = launch_continuum_update(g->n, nlam, ld, dJ, dB, deps, d_diag, eps_thick, dS_old, dS_new, g->d_scalars, st)))
+            return rc;
+        return read_criterion(g->d_scalars, st, max_rel_change, n_thick);
+    });
+}
+
+int vrt_plan_lambda_diagonal_dev(vrt_plan *p, int64_t nlam, int64_t ld, const double *d_alpha, const double *weights_host,
+                                 double *d_diag, void *stream)
+{
+    if (!p || !d_alpha || !weights_host || !d_diag) return fail(VRT_EINVAL, "NULL argument");
+    if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
+    return guarded([&] {
+        std::lock_guard<std::mutex> lock(p->mu);
+        int rc = use_device(p->g->device);
+        if (rc) return rc;
+        return launch_lambda_diagonal(p, nlam, ld, d_alpha, weights_host, d_diag, (hipStream_t)stream);
+    });
+}
+
+int vrt_plan_lambda_diagonal(vrt_plan *p, int64_t nlam, int64_t ld, const double *alpha, const double *weights, double *diag)
+{
+    if (!p || !alpha || !weights || !diag) return fail(VRT_EINVAL, "NULL argument");
+    if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
+    return guarded([&] {
+        std::lock_guard<std::mutex> lock(p->mu);
+        vrt_grid *g = p->g;
+        for (int64_t i = 0; i < g->n; i++)
+            for (int64_t l = 0; l < nlam; l++) {
+                const double a = alpha[i * ld + l];
+                if (!std::isfinite(a) || !(a > 0.0)) return fail(VRT_EINVAL, "alpha must be finite and > 0 everywhere");
+            }
+        int rc = use_device(g->device);
+        if (rc) return rc;
+        hipStream_t st = g->stream;
+        const size_t count = (size_t)g->n * (size_t)ld;
+        DevBuf<double> d_alpha, d_diag;
+        if ((rc = upload(d_alpha, alpha, count, st))) return rc;
+        if ((rc = d_diag.alloc(count))) return rc;
+        // (the padding columns of diag go back as they came)
+        VRT_HIP_TRY(hipMemcpyAsync(d_diag, diag, sizeof(double) * count, hipMemcpyHostToDevice, st));
+        if ((rc = launch_lambda_diagonal(p, nlam, ld, d_alpha, weights, d_diag, st))) return rc;
+        VRT_HIP_TRY(hipMemcpyAsync(diag, d_diag, sizeof(double) * count, hipMemcpyDeviceToHost, st));
+        VRT_HIP_TRY(hipStreamSynchronize(st));
+        return VRT_OK;
     });
 }
 
@@ -401,8 +597,9 @@ int vrt_continuum_iterate(vrt_continuum *s, double *max_rel_change)
                                                     s->d_I0, nullptr, s->weights.data(), s->d_J_nat[0], s->d_J_nat[1], st,
                                                     false))))
                 return rc;
-            if ((rc = launch_continuum_update_native(g, nlam, s->d_J_nat[0], s->d_J_nat[1], s->d_B_up, s->d_E_up, s->eps_thick,
-                                                     s->d_S_nat[0], s->d_S_nat[1], s->d_scalars, st)))
+            if ((rc = launch_continuum_update_native(g, nlam, s->d_J_nat[0], s->d_J_nat[1], s->d_B_up, s->d_E_up,
+                                                     s->op ? s->d_L_up.p : nullptr, s->eps_thick, s->d_S_nat[0],
+                                                     s->d_S_nat[1], s->d_scalars, st)))
                 return rc;
         } else {
             // S_old = copy(S_new), :146: the current S is read where it is and the new one written to the other buffer; the
@@ -410,8 +607,8 @@ int vrt_continuum_iterate(vrt_continuum *s, double *max_rel_change)
             if ((rc = execute_locked(p, caller_args(nlam, nlam, s->d_S_new, s->d_alpha, VRT_ALPHA_SITE_LAM, s->d_I0, nullptr,
                                                     s->weights.data(), s->d_J, nullptr, st, false))))
                 return rc;
-            if ((rc = launch_continuum_update(n, nlam, nlam, s->d_J, s->d_B0, s->d_eps, s->eps_thick, s->d_S_new, s->d_S_old,
-                                              s->d_scalars, st)))
+            if ((rc = launch_continuum_update(n, nlam, nlam, s->d_J, s->d_B0, s->d_eps, s->op ? s->d_diag.p : nullptr,
+                                              s->eps_thick, s->d_S_new, s->d_S_old, s->d_scalars, st)))
                 return rc;
             std::swap(s->d_S_old.p, s->d_S_new.p);
         }
@@ -512,6 +709,79 @@ int vrt_continuum_last_acceleration(const vrt_continuum *s, int *applied, double
     return ng_report(s->ng, applied, sums, coeffs);
 }
 
+int vrt_continuum_set_operator(vrt_continuum *s, int op)
+{
+    if (!s) return fail(VRT_EINVAL, "NULL session");
+    if (op != 0 && op != 1) return fail(VRT_EINVAL, "operator must be 0 (plain) or 1 (diagonal)");
+    return guarded([&] {
+        vrt_plan *p = s->p;
+        std::lock_guard<std::mutex> lock(p->mu);
+        int rc = use_device(p->g->device);
+        if (rc) return rc;
+        if (op == s->op) return (int)VRT_OK;
+        hipStream_t st = p->g->stream;
+        if (op == 0) {
+            VRT_HIP_TRY(hipStreamSynchronize(st));
+            s->d_diag = DevBuf<double>();
+            s->d_L_up = DevBuf<double>();
+        } else {
+            // Λ* from the session's α and weights, once; everything is built beside the session and moved in at the end
+            const int64_t n = s->n, nlam = s->nlam;
+            const size_t nS = (size_t)n * (size_t)nlam;
+            DevBuf<double> diag, L_up, tmpA, tmpE;
+            const double *alpha = s->d_alpha, *eps = s->d_eps;
+            if ((rc = diag.alloc(nS))) return rc;
+            if (s->native) {                                 // α and ε back in the caller's layout, value for value
+                if ((rc = tmpA.alloc(nS)) || (rc = tmpE.alloc(nS))) return rc;
+                if ((rc = plane_from_native(p, 0, nlam, nlam, s->d_A_nat, tmpA, st))) return rc;
+                if ((rc = plane_from_native(p, 0, nlam, nlam, s->d_E_up, tmpE, st))) return rc;
+                alpha = tmpA; eps = tmpE;
+            }
+            if ((rc = launch_lambda_diagonal(p, nlam, nlam, alpha, s->weights.data(), diag, st))) return rc;
+            // min den = min (1 - (1 - ε) Λ*) must be > 0 (it is not only for ε = 0 with Λ* rounding to 1)
+            VRT_HIP_TRY(hipMemsetAsync(s->d_scalars, 0xFF, sizeof(unsigned long long), st));
+            VRT_HIP_TRY(hipMemsetAsync(s->d_scalars + 1, 0, sizeof(unsigned long long), st));
+            const int64_t blocks = std::min<int64_t>(((int64_t)nS + 255) / 256, 256 * 16);
+            hipLaunchKernelGGL(k_ali_min_den, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, (int64_t)nS, eps,
+                               diag.p, s->d_scalars.p);
+            VRT_HIP_TRY(hipGetLastError());
+            unsigned long long h[2] = {0, 0};
+            VRT_HIP_TRY(hipMemcpyAsync(h, s->d_scalars, sizeof(h), hipMemcpyDeviceToHost, st));
+            VRT_HIP_TRY(hipStreamSynchronize(st));
+            if (h[1]) return fail(VRT_EINVAL, "the diagonal operator has 1 - (1 - eps) Lambda* <= 0 somewhere (eps = 0 in a cell "
+                                              "whose Lambda* rounds to 1)");
+            if (s->native) {
+                const size_t np = (size_t)vrt_plan_native_plane_count(p, nlam);
+                if ((rc = L_up.alloc(np))) return rc;
+                if ((rc = planes_to_native(p, nlam, nlam, diag, L_up, nullptr, st))) return rc;
+                VRT_HIP_TRY(hipStreamSynchronize(st));
+            }
+            s->d_diag = std::move(diag);
+            s->d_L_up = std::move(L_up);
+        }
+        s->op = op;
+        s->ng.have = 0;                                      // iterates of another fixed-point map are no history of this one
+        return (int)VRT_OK;
+    });
+}
+
+int vrt_continuum_get_operator(vrt_continuum *s, int *op, double *diag)
+{
+    if (!s || !op) return fail(VRT_EINVAL, "NULL argument");
+    return guarded([&] {
+        vrt_plan *p = s->p;
+        std::lock_guard<std::mutex> lock(p->mu);
+        *op = s->op;
+        if (!diag || !s->op) return (int)VRT_OK;
+        int rc = use_device(p->g->device);
+        if (rc) return rc;
+        hipStream_t st = p->g->stream;
+        VRT_HIP_TRY(hipMemcpyAsync(diag, s->d_diag, sizeof(double) * (size_t)s->n * (size_t)s->nlam, hipMemcpyDeviceToHost, st));
+        VRT_HIP_TRY(hipStreamSynchronize(st));
+        return (int)VRT_OK;
+    });
+}
+
 void vrt_continuum_destroy(vrt_continuum *s)
 {
     DeviceScope scope;
@@ -587,8 +857,8 @@ int vrt_regular_continuum_iterate(vrt_regular_continuum *s, double *max_rel_chan
         // S_new also plane-major for the next solves
         if ((rc = continuum_J_pass(s, st))) return rc;
         if ((rc = launch_from_planes(r, nlam, s->d_J_pl, s->d_J, st))) return rc;
-        if ((rc = launch_continuum_update(n, nlam, nlam, s->d_J, s->d_B0, s->d_eps, s->eps_thick, s->d_S[s->sc], s->d_S[s->sc ^ 1],
-                                          s->d_scalars, st)))
+        if ((rc = launch_continuum_update(n, nlam, nlam, s->d_J, s->d_B0, s->d_eps, nullptr, s->eps_thick, s->d_S[s->sc],
+                                          s->d_S[s->sc ^ 1], s->d_scalars, st)))
             return rc;
         s->sc ^= 1;
         if ((rc = launch_to_planes(r, nlam, s->d_S[s->sc], s->d_S_pl, st))) return rc;
