@@ -311,6 +311,91 @@ def test_site_without_upwind_is_reported():
     hs.close()
 
 
+def _free_device_bytes():
+    import torch
+    torch.cuda.synchronize()
+    return torch.cuda.mem_get_info(0)[0]
+
+
+def _grid_with_a_site_without_upwind(nx, ny, nz):
+    """test_site_without_upwind_is_reported's grid at any size: plan creation fails with VRT_EGRID after its eight
+    [A][n] upwind tables and its events exist"""
+    pos, nbr, bounds = synth.regular_lattice_grid(nx, ny, nz)
+    nbr = nbr.copy()
+    victim = int(np.argmax((pos[:, 0] > 0.3) & (pos[:, 0] < 0.5)))
+    ids = nbr[1:nbr[0, victim] + 1, victim]
+    above = [v for v in ids if v > 0 and pos[v - 1, 0] > pos[victim, 0]]
+    nbr[1:, victim] = 0
+    nbr[1, victim] = above[0]
+    nbr[0, victim] = 1
+    return pos, nbr, bounds
+
+
+HANDLE_LEAK_ALLOWANCE = 4 << 20
+
+
+def test_handles_give_back_what_they_took(golden):
+    """Device-wide free memory (torch.cuda.mem_get_info after a synchronize) around two loops, each after one warm-up
+    round: (a) 50 plan creations that fail with VRT_EGRID on a 40 x 40 x 25 lattice with a site without an upwind neighbour
+    -- after the plan's upwind tables (160 KB each) and events exist; (b) 10 full cycles on the 2000-site golden grid with
+    12 angles: grid and plan, one execute on each of the four paths (so that the lazily built tables and every workspace
+    exist), a line session (vrt_lambda), a continuum session, a nearest-site query (the raster locator), everything
+    destroyed.  Free memory may drop over a loop by at most HANDLE_LEAK_ALLOWANCE.
+
+    The allowance is max(2 x the drop the same test body showed on the commit before the owner types, 4 MiB); one table
+    leaked per failing creation would cost 50 x 40*40*25 x 4 B = 8 MB, twice the allowance.
+    Measured on one MI355X: the commit before (a) 0 B, (b) 0 B; with the owner types (a) 0 B, (b) 0 B; allowance
+    max(2 x 0, 4 MiB) = 4 MiB."""
+    import torch
+    from test_physics import _lambda_case
+    from voronoirt_amd import api
+    k_up = np.array([-1.0, 0.0, 0.0])
+    bad = vrt.VoronoiSites(*_grid_with_a_site_without_upwind(40, 40, 25), device=0)
+
+    def failing_creations(count):
+        for _ in range(count):
+            with pytest.raises(vrt.VrtError) as e:
+                vrt.FormalPlan(bad, [k_up], 3)
+            assert e.value.code == _lib.VRT_EGRID
+
+    failing_creations(1)
+    before = _free_device_bytes()
+    failing_creations(50)
+    drop_a = before - _free_device_bytes()
+    print(f"\n(a) 50 failing plan creations: free memory dropped by {drop_a} B")
+    bad.close()
+
+    pos, bounds = golden["pos"], golden["bounds"]
+    n = pos.shape[0]
+    line = _lambda_case(pos, bounds, 4)
+    cont = vrt.ContinuumCase(**synth.continuum_case(pos, bounds, 2, 3))
+    w, th, ph, _ = vrt.read_quadrature("ul7n12.dat")
+    S, alpha = np.ones((n, 3)), np.full((n, 3), 2.0)
+    rng = np.random.default_rng(1)
+    points = np.array(bounds[0::2]) + rng.random((500, 3)) * (np.array(bounds[1::2]) - np.array(bounds[0::2]))
+
+    def cycles(count):
+        for _ in range(count):
+            hs = vrt.read_cell(golden["nbr_file"], n, pos, bounds)
+            plan = vrt.FormalPlan(hs, vrt.quadrature_directions(th, ph), 3)
+            for path in ("levels", "tiles", "steps", "patches"):
+                plan.set_option("VRT_PATH", path)
+                plan.execute(S, alpha, weights=w, want_I=True)
+                assert plan.last_path == path
+            api.Lambda_voronoi_host(0.0, 1, hs, line, "ul7n12.dat")
+            vrt.Lambda_continuum(0.0, 1, hs, cont, "ul7n12.dat")
+            vrt.nearest_sites(hs, points, k=2)
+            plan.close()
+            hs.close()
+
+    cycles(1)
+    before = _free_device_bytes()
+    cycles(10)
+    drop_b = before - _free_device_bytes()
+    print(f"(b) 10 create / execute / destroy cycles: free memory dropped by {drop_b} B")
+    assert drop_a <= HANDLE_LEAK_ALLOWANCE and drop_b <= HANDLE_LEAK_ALLOWANCE, (drop_a, drop_b)
+
+
 def test_execute_dev_with_torch_tensors_and_padding(grids, path):
     """Device-pointer entry point on a torch stream, with a padded leading dimension."""
     import torch

@@ -44,6 +44,15 @@ def test_one_allocator_and_one_exception_guard():
         text = open(os.path.join(csrc, name)).read()
         assert "hipMalloc(" not in text, name
         assert "catch (" not in text, name
+        # the release side: device and pinned memory, streams and events are held by the owner types of vrt_internal.h
+        # (DevBuf, DevWork, HostBuf, Stream, Event), which alone create and release them -- no handle has a free list
+        code = _code_only(text)
+        for call in ("hipFree(", "hipHostFree(", "hipHostMalloc(", "hipStreamDestroy(", "hipEventDestroy(",
+                     "hipStreamCreate", "hipEventCreate", "dev_free(", "dev_grow("):
+            assert call not in code, (name, call)
+    for name in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, name)).read()
+        assert "VRT_TRY_FREE" not in text and "VRT_HIP_TRY_FREE" not in text, name
 
 
 def _code_only(text):
@@ -51,6 +60,24 @@ def _code_only(text):
     text = re.sub(r'"(?:\\.|[^"\\\n])*"', '""', text)
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return re.sub(r"//[^\n]*", "", text)
+
+
+def test_owner_types_release_exactly_once(tmp_path):
+    """tests/probes/owners_main.cpp: a stand-alone program over the owner types of csrc/vrt_internal.h against a counting
+    fake of the HIP calls they use, built with ASan + UBSan (runtimes linked in: nothing is preloaded) and run as a child process.  Destruction, moves (onto a
+    non-empty target too), reset(), DevWork::grow (kept / freed then allocated / capacity 0 after a failed allocation) and
+    a unique_ptr of a struct of owners dropped halfway through construction all end with every live count at zero."""
+    exe = tmp_path / "owners_main"
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan",
+                           "-fno-omit-frame-pointer",
+                           "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"), "-I", os.path.join(ROOT, "include"),
+                           "-I", os.path.join(ROOT, "voronoirt_amd", "csrc"), "-Wall", "-Werror",
+                           os.path.join(ROOT, "tests", "probes", "owners_main.cpp"), "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1"))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "all live counts are zero" in r.stdout.strip().splitlines()[-1]
 
 
 def test_one_header_holds_every_copy_of_linear_weights():

@@ -279,8 +279,8 @@ int ng_check_settings(int order, int start, int period)
 
 void ng_release(NgState &ng)
 {
-    for (double *&h : ng.hist) dev_free(h);
-    dev_free(ng.d_ws);
+    for (DevBuf<double> &h : ng.hist) h.reset();
+    ng.d_ws.reset();
     ng.have = 0;
 }
 
@@ -294,9 +294,9 @@ int ng_configure(NgState &ng, int order, int start, int period, size_t alloc_cou
         return VRT_OK;
     }
     int rc;
-    for (double *&h : ng.hist)
-        if (!h && (rc = dev_alloc(&h, alloc_count))) { ng_release(ng); ng.order = 0; return rc; }
-    if (!ng.d_ws && (rc = dev_alloc(&ng.d_ws, kNgWorkspace))) { ng_release(ng); ng.order = 0; return rc; }
+    for (DevBuf<double> &h : ng.hist)
+        if (!h && (rc = h.alloc(alloc_count))) { ng_release(ng); ng.order = 0; return rc; }
+    if (!ng.d_ws && (rc = ng.d_ws.alloc(kNgWorkspace))) { ng_release(ng); ng.order = 0; return rc; }
     ng.order = order; ng.start = start; ng.period = period;
     return VRT_OK;
 }
@@ -304,7 +304,7 @@ int ng_configure(NgState &ng, int order, int start, int period, size_t alloc_cou
 // After the plain update of iterate number `iterate` (1-based): iterates until the next due one d = 1, 2, 3 -> S is kept as
 // x_d; d = 0 with the three before it kept -> the step, x_acc written over x3's buffer, which then BECOMES the session's S
 // (a rejected step leaves S untouched).  alloc_count: doubles of an S buffer (padding included, copied along).
-int ng_after_iterate(NgState &ng, int64_t iterate, double *&S, size_t alloc_count, const NgRange &rg, hipStream_t st)
+int ng_after_iterate(NgState &ng, int64_t iterate, DevBuf<double> &S, size_t alloc_count, const NgRange &rg, hipStream_t st)
 {
     ng.last_applied = 0;
     if (!ng.order) return VRT_OK;

@@ -111,52 +111,18 @@ int use_current_device()
     return VRT_OK;
 }
 
-static void free_grid(vrt_grid *g)
-{
-    if (!g) return;
-    for (PlanCacheEntry *c : g->cache) {
-        vrt_plan_destroy(c->plan);
-        delete c;
-    }
-    g->cache.clear();
-    raster_locator_free(g);
-    dev_free(g->d_pos);
-    dev_free(g->d_rowptr);
-    dev_free(g->d_col);
-    dev_free(g->d_lz);
-    dev_free(g->d_lx);
-    dev_free(g->d_ly);
-    dev_free(g->up.d_order);
-    dev_free(g->down.d_order);
-    dev_free(g->up.d_rank);
-    dev_free(g->down.d_rank);
-    dev_free(g->up.d_lay);
-    dev_free(g->down.d_lay);
-    dev_free(g->d_scalars);
-    dev_free(g->d_small);
-    if (g->small_ev) (void)hipEventDestroy(g->small_ev);
-    if (g->small_copy_ev) (void)hipEventDestroy(g->small_copy_ev);
-    if (g->h_small) (void)hipHostFree(g->h_small);
-    dev_free(g->up.d_store);
-    dev_free(g->down.d_store);
-    dev_free(g->up.d_srank);
-    dev_free(g->down.d_srank);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    delete g;
-}
-
 static int upload_grid(vrt_grid *g)
 {
     const int64_t n = g->n;
     const size_t nnz = g->col.size();
     int rc;
-    if ((rc = dev_alloc(&g->d_pos, (size_t)3 * n))) return rc;
-    if ((rc = dev_alloc(&g->d_rowptr, (size_t)n + 1))) return rc;
-    if ((rc = dev_alloc(&g->d_col, nnz))) return rc;
-    if ((rc = dev_alloc(&g->d_lz, nnz))) return rc;
-    if ((rc = dev_alloc(&g->d_lx, nnz))) return rc;
-    if ((rc = dev_alloc(&g->d_ly, nnz))) return rc;
-    VRT_HIP_TRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+    if ((rc = g->d_pos.alloc((size_t)3 * n))) return rc;
+    if ((rc = g->d_rowptr.alloc((size_t)n + 1))) return rc;
+    if ((rc = g->d_col.alloc(nnz))) return rc;
+    if ((rc = g->d_lz.alloc(nnz))) return rc;
+    if ((rc = g->d_lx.alloc(nnz))) return rc;
+    if ((rc = g->d_ly.alloc(nnz))) return rc;
+    if ((rc = g->stream.create())) return rc;
     VRT_HIP_TRY(hipMemcpy(g->d_pos, g->pos.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice));
     VRT_HIP_TRY(hipMemcpy(g->d_rowptr, g->rowptr.data(), sizeof(int32_t) * (n + 1), hipMemcpyHostToDevice));
     if (nnz)
@@ -165,21 +131,21 @@ static int upload_grid(vrt_grid *g)
         Direction &dir = d == 0 ? g->up : g->down;
         std::vector<int32_t> order((size_t)n);
         for (int64_t i = 0; i < n; i++) order[(size_t)i] = (int32_t)(dir.perm[(size_t)i] - 1);
-        if ((rc = dev_alloc(&dir.d_order, (size_t)n))) return rc;
+        if ((rc = dir.d_order.alloc((size_t)n))) return rc;
         VRT_HIP_TRY(hipMemcpy(dir.d_order, order.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
         std::vector<int32_t> rank((size_t)n);
         for (int64_t i = 0; i < n; i++) rank[(size_t)order[(size_t)i]] = (int32_t)i;
-        if ((rc = dev_alloc(&dir.d_rank, (size_t)n))) return rc;
+        if ((rc = dir.d_rank.alloc((size_t)n))) return rc;
         VRT_HIP_TRY(hipMemcpy(dir.d_rank, rank.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
         std::vector<int32_t> srank((size_t)n);
         for (int64_t i = 0; i < n; i++) srank[(size_t)dir.store[(size_t)i]] = (int32_t)i;
-        if ((rc = dev_alloc(&dir.d_store, (size_t)n))) return rc;
-        if ((rc = dev_alloc(&dir.d_srank, (size_t)n))) return rc;
+        if ((rc = dir.d_store.alloc((size_t)n))) return rc;
+        if ((rc = dir.d_srank.alloc((size_t)n))) return rc;
         VRT_HIP_TRY(hipMemcpy(dir.d_store, dir.store.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
         VRT_HIP_TRY(hipMemcpy(dir.d_srank, srank.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
         std::vector<int32_t> lay(dir.reduced.size());
         for (size_t j = 0; j < lay.size(); j++) lay[j] = (int32_t)(dir.reduced[j] - 1);
-        if ((rc = dev_alloc(&dir.d_lay, lay.size()))) return rc;
+        if ((rc = dir.d_lay.alloc(lay.size()))) return rc;
         VRT_HIP_TRY(hipMemcpy(dir.d_lay, lay.data(), sizeof(int32_t) * lay.size(), hipMemcpyHostToDevice));
     }
     if ((rc = launch_delaunay_lines(g))) return rc;
@@ -195,84 +161,16 @@ static int grid_create_impl(int64_t n, const double *pos, const int64_t *nbr, in
     if (!pos || !nbr || !bounds) return fail(VRT_EINVAL, "NULL argument");
     int rc = device >= 0 ? use_device(device) : VRT_OK;   // device < 0: host-only handle
     if (rc) return rc;
-    vrt_grid *g = new (std::nothrow) vrt_grid();
+    GridPtr g(new (std::nothrow) vrt_grid());
     if (!g) return fail(VRT_ENOMEM, "out of host memory");
     g->device = device;
-    rc = build_grid_host(g, n, pos, nbr, D1, bounds);
-    if (!rc && device >= 0) rc = upload_grid(g);
-    if (rc) {
-        free_grid(g);
-        return rc;
-    }
-    *out = g;
+    if ((rc = build_grid_host(g.get(), n, pos, nbr, D1, bounds))) return rc;
+    if (device >= 0 && (rc = upload_grid(g.get()))) return rc;
+    *out = g.release();
     return VRT_OK;
 }
 
 static const Direction &direction_of(const vrt_grid *g, int dir) { return dir > 0 ? g->up : g->down; }
-
-static void free_plan(vrt_plan *p)
-{
-    if (!p) return;
-    dev_free(p->d_up1);
-    dev_free(p->d_up2);
-    dev_free(p->d_d1);
-    dev_free(p->d_d2);
-    dev_free(p->d_w1);
-    dev_free(p->d_w2);
-    dev_free(p->d_r1);
-    dev_free(p->d_r2);
-    dev_free(p->d_node_site);
-    dev_free(p->d_node_meta);
-    dev_free(p->d_node_u1);
-    dev_free(p->d_node_u2);
-    dev_free(p->d_angles_up);
-    dev_free(p->d_angles_down);
-    dev_free(p->d_I);
-    for (int i = 0; i < 6; i++) dev_free(p->d_stage[i]);
-    dev_free(p->t_u1); dev_free(p->t_u2);
-    dev_free(p->t_w1); dev_free(p->t_w2); dev_free(p->t_r1); dev_free(p->t_r2);
-    dev_free(p->t_vis);
-    dev_free(p->t_loc);
-    dev_free(p->t_self);
-    dev_free(p->t_vis_s);
-    dev_free(p->t_loc_s);
-    dev_free(p->t_gpos);
-    dev_free(p->t_rank_s);
-    dev_free(p->t_loc_ss);
-    dev_free(p->t_code_ss);
-    dev_free(p->d_nlev); dev_free(p->d_angle_dir); dev_free(p->d_task_map);
-    for (int d = 0; d < 2; d++) { dev_free(p->ws_S[d]); dev_free(p->ws_A[d]); dev_free(p->ws_J[d]); }
-    dev_free(p->ws_AA);
-    for (int i = 0; i < 2; i++) dev_free(p->ws_cg[i]);
-    dev_free(p->d_step_angles);
-    dev_free(p->d_level_map);
-    dev_free(p->d_patch_work);
-    dev_free(p->d_chain_items); dev_free(p->d_chain_deps); dev_free(p->d_chain_progress); dev_free(p->d_chain_ctrl);
-    for (auto &cs : p->chain_cache) { dev_free(cs.items); dev_free(cs.deps); }
-    p->chain_cache.clear();
-    if (p->h_chain_status) { (void)hipHostFree(p->h_chain_status); p->h_chain_status = nullptr; }
-    if (p->d_chain_dev) { (void)hipFree(p->d_chain_dev); p->d_chain_dev = nullptr; }
-    if (p->h_chain_dev_pinned) { (void)hipHostFree(p->h_chain_dev_pinned); p->h_chain_dev_pinned = nullptr; }
-    if (p->chain_dev_ev) (void)hipEventDestroy(p->chain_dev_ev);
-    dev_free(p->e_pos); dev_free(p->e_u1); dev_free(p->e_u2); dev_free(p->e_vis); dev_free(p->e_loc);
-    dev_free(p->e_w1); dev_free(p->e_w2); dev_free(p->e_r1); dev_free(p->e_r2);
-    if (p->step_fork) (void)hipEventDestroy(p->step_fork);
-    for (int i = 0; i < 4; i++) {
-        if (p->step_join[i]) (void)hipEventDestroy(p->step_join[i]);
-        if (p->step_stream[i]) (void)hipStreamDestroy(p->step_stream[i]);
-    }
-    for (CopyLane &l : p->copy_lanes) {
-        for (int b = 0; b < 2; b++) {
-            if (l.pin[b]) (void)hipHostFree(l.pin[b]);
-            if (l.ev[b]) (void)hipEventDestroy(l.ev[b]);
-        }
-        if (l.st) (void)hipStreamDestroy(l.st);
-    }
-    if (p->copy_done) (void)hipEventDestroy(p->copy_done);
-    if (p->ev0) (void)hipEventDestroy(p->ev0);
-    if (p->ev1) (void)hipEventDestroy(p->ev1);
-    delete p;
-}
 
 // Global-level schedule of the "levels" path (merged over the active angles), built on first use:
 // plan creation only pays for what the default path of the grid needs.
@@ -310,10 +208,10 @@ static int ensure_level_schedule(vrt_plan *p)
     std::vector<uint32_t> node_site((size_t)total), node_meta((size_t)total);
     std::vector<int32_t> node_u1((size_t)total), node_u2((size_t)total);   // the node's upwind ids ride along:
                                                                            // one dependent load less per launch
-    p->level_off.assign((size_t)max_levels + 1, 0);
+    std::vector<int64_t> level_off((size_t)max_levels + 1, 0);
     int64_t at = 0;
     for (int64_t t = 0; t < max_levels; t++) {
-        p->level_off[(size_t)t] = at;
+        level_off[(size_t)t] = at;
         for (int a = 0; a < A; a++) {
             const AngleSchedule &s = sched[(size_t)a];
             if (t + 1 >= (int64_t)s.level_off.size()) continue;
@@ -335,31 +233,280 @@ static int ensure_level_schedule(vrt_plan *p)
             }
         }
     }
-    p->level_off[(size_t)max_levels] = at;
-    p->n_nodes = total;
-    int rc = VRT_OK;
-    if (!rc) rc = dev_alloc(&p->d_node_site, (size_t)total);
-    if (!rc) rc = dev_alloc(&p->d_node_meta, (size_t)total);
-    if (!rc) rc = dev_alloc(&p->d_node_u1, (size_t)total);
-    if (!rc) rc = dev_alloc(&p->d_node_u2, (size_t)total);
-    if (!rc && total) {
-        const size_t b = sizeof(uint32_t) * (size_t)total;
-        if (hipMemcpy(p->d_node_u1, node_u1.data(), b, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(p->d_node_u2, node_u2.data(), b, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(p->d_node_site, node_site.data(), b, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(p->d_node_meta, node_meta.data(), b, hipMemcpyHostToDevice) != hipSuccess)
-            rc = fail(VRT_ENODEVICE, "uploading the level schedule failed");
-    }
-    if (rc) {                       // leave no half-built schedule behind
-        dev_free(p->d_node_site);
-        dev_free(p->d_node_meta);
-        dev_free(p->d_node_u1);
-        dev_free(p->d_node_u2);
-        p->level_off.clear();
-        p->n_nodes = 0;
+    level_off[(size_t)max_levels] = at;
+    // built into locals and moved into the plan when all of it exists: a failure leaves no half-built schedule behind
+    DevBuf<uint32_t> d_site, d_meta;
+    DevBuf<int32_t> d_u1, d_u2;
+    int rc;
+    if ((rc = d_site.alloc((size_t)total)) || (rc = d_meta.alloc((size_t)total)) || (rc = d_u1.alloc((size_t)total)) ||
+        (rc = d_u2.alloc((size_t)total)))
         return rc;
+    if (total) {
+        const size_t b = sizeof(uint32_t) * (size_t)total;
+        if (hipMemcpy(d_u1, node_u1.data(), b, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_u2, node_u2.data(), b, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_site, node_site.data(), b, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_meta, node_meta.data(), b, hipMemcpyHostToDevice) != hipSuccess)
+            return fail(VRT_ENODEVICE, "uploading the level schedule failed");
     }
+    p->d_node_site = std::move(d_site);
+    p->d_node_meta = std::move(d_meta);
+    p->d_node_u1 = std::move(d_u1);
+    p->d_node_u2 = std::move(d_u2);
+    p->level_off.swap(level_off);
+    p->n_nodes = total;
     p->level_ready = true;
+    return VRT_OK;
+}
+
+// ---- plan creation, stage by stage (plan_create_impl below runs them in this order) ------------------------------------
+
+// the unit vectors are checked and the active angles selected (θ = 90 is skipped)
+static int plan_select_angles(vrt_plan *p, int64_t n_angles, const double *k, const int *dirs)
+{
+    for (int64_t a = 0; a < n_angles; a++) {
+        const double *ka = k + 3 * a;
+        const double nrm = std::sqrt(ka[0] * ka[0] + ka[1] * ka[1] + ka[2] * ka[2]);
+        if (!(std::fabs(nrm - 1.0) < 1e-6))     // functions.jl:432 asserts norm(k) ≈ 1
+            return fail(VRT_EINVAL, "direction " + std::to_string(a + 1) + " is not a unit vector");
+        // θ>90 up, θ<90 down, θ=90 skipped (lambda_iteration.jl:98,104).  cos(90° π/180) is 6.1e-17,
+        // not 0, so a horizontal direction is recognised by |k_z| < 1e-12 (1e-12 rad from horizontal)
+        int d = dirs ? (dirs[a] > 0 ? 1 : (dirs[a] < 0 ? -1 : 0))
+                     : (std::fabs(ka[0]) < 1e-12 ? 0 : (ka[0] < 0 ? 1 : -1));
+        if (d == 0) continue;
+        p->user_of_active.push_back((int)a);
+        p->dir_of_active.push_back(d);
+        p->k.insert(p->k.end(), ka, ka + 3);
+    }
+    p->A = (int)p->user_of_active.size();
+    if (p->A > kMaxAngles) return fail(VRT_EINVAL, "more than 64 active angles in one plan");
+    return VRT_OK;
+}
+
+// the per-angle upwind tables [A][n], built on the device; the upwind ids come back to the host (schedule building)
+static int plan_upwind_tables(vrt_plan *p)
+{
+    const size_t tab = (size_t)p->A * (size_t)p->g->n;
+    int rc;
+    if ((rc = p->d_up1.alloc(tab)) || (rc = p->d_up2.alloc(tab)) || (rc = p->d_d1.alloc(tab)) || (rc = p->d_d2.alloc(tab)) ||
+        (rc = p->d_w1.alloc(tab)) || (rc = p->d_w2.alloc(tab)) || (rc = p->d_r1.alloc(tab)) || (rc = p->d_r2.alloc(tab)))
+        return rc;
+    if ((rc = p->ev0.create()) || (rc = p->ev1.create())) return rc;
+    for (int a = 0; a < p->A; a++)
+        if ((rc = launch_upwind_table(p, a))) return rc;
+    p->h_up1.resize(tab);
+    p->h_up2.resize(tab);
+    VRT_HIP_TRY(hipStreamSynchronize(p->g->stream));
+    if (tab) {
+        VRT_HIP_TRY(hipMemcpy(p->h_up1.data(), p->d_up1, sizeof(int32_t) * tab, hipMemcpyDeviceToHost));
+        VRT_HIP_TRY(hipMemcpy(p->h_up2.data(), p->d_up2, sizeof(int32_t) * tab, hipMemcpyDeviceToHost));
+    }
+    return VRT_OK;
+}
+
+// per-angle layer-local schedules (always needed: they drive the default steps/tiles paths and detect sites without an
+// upwind neighbour) and patch schedules (vrt_patch.cpp), built concurrently on the host.  The global-level schedule of
+// the "levels" path is built on first use (ensure_level_schedule).
+static int plan_host_schedules(vrt_plan *p, std::vector<LayerSchedule> &lsched, std::vector<PatchSchedule> &psched)
+{
+    const vrt_grid *g = p->g;
+    const int64_t n = g->n;
+    const int A = p->A, n_sweeps = p->n_sweeps;
+    lsched.resize((size_t)A);
+    psched.resize((size_t)A);
+    // shape of the patch kernel: K entries per thread x NT threads = largest dependency cone of a patch
+    if (!patch_shape_exists(p->tune.patch_K, p->tune.patch_Q, p->tune.patch_NT)) {
+        p->tune.patch_K = 1; p->tune.patch_NT = 512; p->tune.patch_Q = 1;
+    }
+    p->patch_K = p->tune.patch_K;
+    p->patch_NT = p->tune.patch_NT;
+    p->patch_cap = p->patch_K * p->patch_NT;
+    // pairs of a site side by side in the patch path's planes: a power of two, and a plane block must stay
+    // addressable with 32-bit byte offsets (n sites x 2^lg pairs x 16 bytes)
+    int lg = 0;
+    while ((2 << lg) <= p->tune.pair_block && lg < 4) lg++;
+    while (lg > 0 && ((uint64_t)n << (lg + 4)) > 0xFFFFFFFFull) lg--;
+    p->lg_pair_block = lg;
+    // a patch owns as many consecutive sites as its dependency cone leaves room for (VRT_PATCH_OWN: at most that many)
+    const int patch_own = p->tune.patch_own > 0 ? std::min(p->tune.patch_own, p->patch_cap) : p->patch_cap;
+    // one job per angle, dealt to the host threads; a job splits further by layer (the layers of an angle are analysed
+    // independently, vrt_patch.cpp) when threads are left over.  The patch builder returns the angle's layer schedule
+    // as a by-product -- the same analysis -- so build_layer_schedule itself only runs for an angle whose layers do not
+    // fit the packed encoding (it then says so too; the level kernels take over).
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    // (all angles at once when the host has four threads for each: no second round with most threads idle)
+    const int nthr = std::max(1, (int)std::min<unsigned>(std::min(hw, (unsigned)A * 4u <= hw ? 64u : 16u), (unsigned)A));
+    const int sub_threads = (int)std::max(1u, std::min(16u, hw / (unsigned)nthr));
+    std::atomic<int> next_job(0);
+    // (every schedule build holds a visit trace of up to n_sweeps n entries and a dozen n-sized arrays)
+    if (!run_workers(nthr, [&](int) {
+            for (;;) {
+                const int a = next_job.fetch_add(1);
+                if (a >= A) break;
+                const bool up = p->dir_of_active[(size_t)a] > 0;
+                const int32_t *u1 = p->h_up1.data() + (size_t)a * n, *u2 = p->h_up2.data() + (size_t)a * n;
+                build_patch_schedule(up ? g->up : g->down, /*ascending=*/up, n, n_sweeps, u1, u2, patch_own,
+                                     p->patch_cap, psched[(size_t)a], sub_threads, &lsched[(size_t)a]);
+                if (!lsched[(size_t)a].ok && lsched[(size_t)a].bad_site < 0)
+                    build_layer_schedule(up ? g->up : g->down, /*ascending=*/up, n, n_sweeps, u1, u2, lsched[(size_t)a]);
+            }
+        }))
+        return fail(VRT_ENOMEM, "out of host memory while building the sweep schedules");
+    return VRT_OK;
+}
+
+static int plan_check_upwind(const vrt_plan *p, const std::vector<LayerSchedule> &lsched)
+{
+    for (int a = 0; a < p->A; a++)
+        if (lsched[(size_t)a].bad_site >= 0)
+            return fail(VRT_EGRID, "site " + std::to_string(lsched[(size_t)a].bad_site + 1) +
+                                       " has no neighbour with k . line > -1 for angle " +
+                                       std::to_string(p->user_of_active[(size_t)a] + 1) +
+                                       " (the reference reads an uninitialised index here)");
+    return VRT_OK;
+}
+
+// per-direction lists of the active angle indices (boundary kernel)
+static int plan_angle_lists(vrt_plan *p)
+{
+    std::vector<int32_t> ups, downs;
+    for (int a = 0; a < p->A; a++) (p->dir_of_active[(size_t)a] > 0 ? ups : downs).push_back(a);
+    p->n_up = (int)ups.size();
+    p->n_down = (int)downs.size();
+    int rc;
+    if ((rc = p->d_angles_up.alloc(ups.size())) || (rc = p->d_angles_down.alloc(downs.size()))) return rc;
+    if (!ups.empty())
+        VRT_HIP_TRY(hipMemcpy(p->d_angles_up, ups.data(), sizeof(int32_t) * ups.size(), hipMemcpyHostToDevice));
+    if (!downs.empty())
+        VRT_HIP_TRY(hipMemcpy(p->d_angles_down, downs.data(), sizeof(int32_t) * downs.size(), hipMemcpyHostToDevice));
+    return VRT_OK;
+}
+
+// which layer paths the schedules fit (tile_ok, patch_ok) and the sizes they need
+static void plan_layer_fit(vrt_plan *p, const std::vector<LayerSchedule> &lsched, const std::vector<PatchSchedule> &psched)
+{
+    const vrt_grid *g = p->g;
+    const int A = p->A;
+    bool ok = A > 0;
+    int64_t max_layer = 0, visits = 0;
+    for (int a = 0; a < A; a++) {
+        ok = ok && lsched[(size_t)a].ok;
+        max_layer = std::max(max_layer, lsched[(size_t)a].max_layer_size);
+        visits += lsched[(size_t)a].n_visits;
+    }
+    // the boundary layer is a layer too: k_sweep_tiles_pre keeps it in LDS as the first "previous" layer
+    if (p->n_up > 0) max_layer = std::max(max_layer, g->up.n1);
+    if (p->n_down > 0) max_layer = std::max(max_layer, g->down.n1);
+    if (g->n >= ((int64_t)1 << 28)) ok = false;  // the layer kernels index 16-byte pair planes with 32-bit byte offsets
+    // the layer-step level kernels hold a whole layer per workgroup: 8192 sites as fp64 wavelength
+    // pairs, 12 288 as fp64 single wavelengths, 18 432 as fp32 ones (vrt_step_kernels.h); the fused
+    // patch kernel (vrt_patch.hip) has no such limit
+    const bool tile_ok = ok && max_layer <= steps_max_layer(/*f32=*/true);
+    bool patch_ok = ok;
+    int64_t n_patches = 0, n_entries = 0;
+    for (int a = 0; a < A && patch_ok; a++) {
+        patch_ok = psched[(size_t)a].ok;
+        n_patches += (int64_t)psched[(size_t)a].patch_own_lo.size();
+        n_entries += (int64_t)psched[(size_t)a].entry_pos.size();
+    }
+    if (n_entries >= ((int64_t)1 << 31) - 1 || n_patches >= ((int64_t)1 << 31) - 1) patch_ok = false;
+    p->tile_ok = tile_ok;
+    p->patch_ok = patch_ok;
+    p->tile_max_layer_size = max_layer;
+    p->tile_visits = visits;
+    p->tile_K = max_layer <= 2048 ? 2 : max_layer <= 4096 ? 4 : 8;
+    if (patch_ok) {
+        p->n_patches = n_patches;
+        p->n_patch_entries = n_entries;
+    }
+}
+
+// patch records and entry tables of angle `a` (its entries start at ent_base); the angle's schedule is released
+static int plan_patch_records(vrt_plan *p, int a, PatchSchedule &ps, int maxL, int64_t &ent_base, std::vector<int2> &rec2)
+{
+    int rc2 = VRT_OK;
+    const size_t np_a = ps.patch_own_lo.size(), ne_a = ps.entry_pos.size();
+    const int32_t pbase = (int32_t)p->h_patch_rec.size();
+    int32_t *first = p->h_patch_first.data() + (size_t)a * (size_t)(maxL + 2);
+    for (int l = 0; l <= maxL + 1; l++)
+        first[l] = pbase + ps.layer_patch_off[std::min<size_t>((size_t)l, ps.layer_patch_off.size() - 1)];
+    for (size_t q = 0; q < np_a; q++) {
+        p->h_patch_rec.push_back(make_int4((int)(ent_base + ps.patch_ent_off[q]),
+                                           (int)(ps.patch_ent_off[q + 1] - ps.patch_ent_off[q]),
+                                           ps.patch_own_lo[q], ps.patch_own_cnt[q]));
+        rec2.push_back(make_int2(ps.patch_nlev[q], a));
+        p->h_patch_dep_off.push_back((int64_t)p->h_patch_deps.size());
+        for (int64_t j = ps.dep_off[q]; j < ps.dep_off[q + 1]; j++)
+            p->h_patch_deps.push_back(pbase + ps.dep_list[(size_t)j]);
+    }
+    if (ne_a) {
+        if (hipMemcpy(p->e_pos + ent_base, ps.entry_pos.data(), sizeof(int32_t) * ne_a, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(p->e_vis + ent_base, ps.entry_vis.data(), sizeof(uint32_t) * ne_a, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(p->e_loc + ent_base, ps.entry_loc.data(), sizeof(uint32_t) * ne_a, hipMemcpyHostToDevice) != hipSuccess)
+            rc2 = VRT_ENODEVICE;
+        if (!rc2) rc2 = launch_patch_entries(p, a, ent_base, (int64_t)ne_a);
+    }
+    ent_base += (int64_t)ne_a;
+    p->n_patch_visits += ps.n_visits;
+    ps = PatchSchedule();
+    return rc2;
+}
+
+// layer paths: tables in storage order, per-layer level counts, patch records and entry tables
+static int plan_storage_tables(vrt_plan *p, const std::vector<LayerSchedule> &lsched, std::vector<PatchSchedule> &psched)
+{
+    if (!p->tile_ok && !p->patch_ok) return VRT_OK;
+    vrt_grid *g = p->g;
+    const int64_t n = g->n;
+    const int A = p->A;
+    const size_t tab = (size_t)A * (size_t)n;
+    int rc;
+    if ((rc = p->t_u1.alloc(tab)) || (rc = p->t_u2.alloc(tab)) || (rc = p->t_w1.alloc(tab)) || (rc = p->t_w2.alloc(tab)) ||
+        (rc = p->t_r1.alloc(tab)) || (rc = p->t_r2.alloc(tab)) || (rc = p->t_vis.alloc(tab)) || (rc = p->t_loc.alloc(tab)))
+        return rc;
+    // (the sorted-slot tables of the steps / tiles paths are built when one of those paths first runs:
+    // ensure_step_tables -- the default patch path needs none of them)
+    const int maxL = (int)std::max(g->up.reduced.size(), g->down.reduced.size()) - 1;
+    p->tile_max_layers = maxL;
+    if (p->patch_ok) {
+        const size_t ne = (size_t)p->n_patch_entries;
+        if ((rc = p->e_pos.alloc(ne)) || (rc = p->e_u1.alloc(ne)) || (rc = p->e_u2.alloc(ne)) || (rc = p->e_vis.alloc(ne)) ||
+            (rc = p->e_loc.alloc(ne)) || (rc = p->e_w1.alloc(ne)) || (rc = p->e_w2.alloc(ne)) || (rc = p->e_r1.alloc(ne)) ||
+            (rc = p->e_r2.alloc(ne)))
+            return rc;
+        p->h_patch_first.assign((size_t)A * (size_t)(maxL + 2), 0);
+        p->h_patch_rec.reserve((size_t)p->n_patches);
+    }
+    DevBuf<uint32_t> d_vis_site;
+    if ((rc = d_vis_site.alloc((size_t)n))) return rc;
+    std::vector<int32_t> nlev((size_t)A * (size_t)(maxL + 1), 0), adir((size_t)A);
+    std::vector<int2> rec2;
+    p->angle_visits.assign((size_t)A, 0);
+    int64_t ent_base = 0;
+    for (int a = 0; a < A; a++) {
+        hipError_t e = hipMemcpy(d_vis_site, lsched[(size_t)a].vis.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice);
+        int rc2 = e == hipSuccess ? launch_permute_table(p, a, d_vis_site) : VRT_ENODEVICE;
+        if (!rc2 && p->patch_ok) rc2 = plan_patch_records(p, a, psched[(size_t)a], maxL, ent_base, rec2);
+        if (!rc2 && hipStreamSynchronize(g->stream) != hipSuccess) rc2 = VRT_ENODEVICE;
+        if (rc2) return fail(VRT_ENODEVICE, "building the sweep-order tables failed");
+        const std::vector<int32_t> &nl = lsched[(size_t)a].nlev;
+        for (size_t l = 0; l < nl.size() && l <= (size_t)maxL; l++)
+            nlev[(size_t)a * (size_t)(maxL + 1) + l] = nl[l];
+        adir[(size_t)a] = p->dir_of_active[(size_t)a] > 0 ? 0 : 1;
+        p->angle_visits[(size_t)a] = lsched[(size_t)a].n_visits + n;   // + n: phase 1 touches every site
+        double sum = 0.0;
+        int cntl = 0;
+        for (size_t l = 2; l < nl.size(); l++, cntl++) sum += nl[l];
+        p->angle_mean_levels.push_back(cntl ? sum / cntl : 0.0);
+    }
+    d_vis_site.reset();
+    if ((rc = p->d_nlev.alloc(nlev.size())) || (rc = p->d_angle_dir.alloc((size_t)A))) return rc;
+    VRT_HIP_TRY(hipMemcpy(p->d_nlev, nlev.data(), sizeof(int32_t) * nlev.size(), hipMemcpyHostToDevice));
+    VRT_HIP_TRY(hipMemcpy(p->d_angle_dir, adir.data(), sizeof(int32_t) * A, hipMemcpyHostToDevice));
+    if (p->patch_ok) {
+        p->h_patch_dep_off.push_back((int64_t)p->h_patch_deps.size());
+        p->h_patch_rec2 = rec2;
+    }
     return VRT_OK;
 }
 
@@ -384,9 +531,10 @@ static int plan_create_impl(vrt_grid *g, int64_t n_angles, const double *k, cons
 #else
     auto tick = [](const char *) {};
 #endif
-    vrt_plan *p = new (std::nothrow) vrt_plan();
+    PlanPtr p(new (std::nothrow) vrt_plan());      // (a failure below, an exception included, releases all it holds)
     if (!p) return fail(VRT_ENOMEM, "out of host memory");
     p->g = g;
+    p->device = g->device;
     p->n_sweeps = n_sweeps;
     p->n_angles_user = n_angles;
     tuning_from_env(p->tune);             // the ONLY place the library reads its tuning environment variables
@@ -404,266 +552,19 @@ static int plan_create_impl(vrt_grid *g, int64_t n_angles, const double *k, cons
     }
     if (options)
         for (const auto &o : *options) (void)tuning_set(p->tune, o.first.c_str(), o.second.c_str(), /*created=*/false);
-    for (int64_t a = 0; a < n_angles; a++) {
-        const double *ka = k + 3 * a;
-        const double nrm = std::sqrt(ka[0] * ka[0] + ka[1] * ka[1] + ka[2] * ka[2]);
-        if (!(std::fabs(nrm - 1.0) < 1e-6)) {   // functions.jl:432 asserts norm(k) ≈ 1
-            free_plan(p);
-            return fail(VRT_EINVAL, "direction " + std::to_string(a + 1) + " is not a unit vector");
-        }
-        // θ>90 up, θ<90 down, θ=90 skipped (lambda_iteration.jl:98,104).  cos(90° π/180) is 6.1e-17,
-        // not 0, so a horizontal direction is recognised by |k_z| < 1e-12 (1e-12 rad from horizontal)
-        int d = dirs ? (dirs[a] > 0 ? 1 : (dirs[a] < 0 ? -1 : 0))
-                     : (std::fabs(ka[0]) < 1e-12 ? 0 : (ka[0] < 0 ? 1 : -1));
-        if (d == 0) continue;
-        p->user_of_active.push_back((int)a);
-        p->dir_of_active.push_back(d);
-        p->k.insert(p->k.end(), ka, ka + 3);
-    }
-    p->A = (int)p->user_of_active.size();
-    if (p->A > kMaxAngles) {
-        free_plan(p);
-        return fail(VRT_EINVAL, "more than 64 active angles in one plan");
-    }
-    const int64_t n = g->n;
-    const int A = p->A;
-    const size_t tab = (size_t)A * (size_t)n;
-#define VRT_TRY_FREE(expr)      \
-    do {                        \
-        int _rc = (expr);       \
-        if (_rc) {              \
-            free_plan(p);       \
-            return _rc;         \
-        }                       \
-    } while (0)
-#define VRT_HIP_TRY_FREE(expr)                                                             \
-    do {                                                                                   \
-        hipError_t _e = (expr);                                                            \
-        if (_e != hipSuccess) {                                                            \
-            free_plan(p);                                                                  \
-            return fail(VRT_ENODEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-        }                                                                                  \
-    } while (0)
-    VRT_TRY_FREE(dev_alloc(&p->d_up1, tab));
-    VRT_TRY_FREE(dev_alloc(&p->d_up2, tab));
-    VRT_TRY_FREE(dev_alloc(&p->d_d1, tab));
-    VRT_TRY_FREE(dev_alloc(&p->d_d2, tab));
-    VRT_TRY_FREE(dev_alloc(&p->d_w1, tab));
-    VRT_TRY_FREE(dev_alloc(&p->d_w2, tab));
-    VRT_TRY_FREE(dev_alloc(&p->d_r1, tab));
-    VRT_TRY_FREE(dev_alloc(&p->d_r2, tab));
-    VRT_HIP_TRY_FREE(hipEventCreate(&p->ev0));
-    VRT_HIP_TRY_FREE(hipEventCreate(&p->ev1));
-    for (int a = 0; a < A; a++) VRT_TRY_FREE(launch_upwind_table(p, a));
-    std::vector<int32_t> up1(tab), up2(tab);
-    VRT_HIP_TRY_FREE(hipStreamSynchronize(g->stream));
-    if (tab) {
-        VRT_HIP_TRY_FREE(hipMemcpy(up1.data(), p->d_up1, sizeof(int32_t) * tab, hipMemcpyDeviceToHost));
-        VRT_HIP_TRY_FREE(hipMemcpy(up2.data(), p->d_up2, sizeof(int32_t) * tab, hipMemcpyDeviceToHost));
-    }
-
-    // per-angle layer-local schedules (always needed: they drive the default steps/tiles paths and
-    // detect sites without an upwind neighbour), built concurrently on the host.  The global-level
-    // schedule of the "levels" path is built on first use (ensure_level_schedule).
+    if ((rc = plan_select_angles(p.get(), n_angles, k, dirs))) return rc;
+    if ((rc = plan_upwind_tables(p.get()))) return rc;
     tick("upwind tables (device) + D2H");
-    p->h_up1.swap(up1);
-    p->h_up2.swap(up2);
-    std::vector<LayerSchedule> lsched((size_t)A);
-    std::vector<PatchSchedule> psched((size_t)A);                // fused patch path (vrt_patch.cpp)
-    {
-        // shape of the patch kernel: K entries per thread x NT threads = largest dependency cone of a patch
-        if (!patch_shape_exists(p->tune.patch_K, p->tune.patch_Q, p->tune.patch_NT)) {
-            p->tune.patch_K = 1; p->tune.patch_NT = 512; p->tune.patch_Q = 1;
-        }
-        p->patch_K = p->tune.patch_K;
-        p->patch_NT = p->tune.patch_NT;
-        p->patch_cap = p->patch_K * p->patch_NT;
-        // pairs of a site side by side in the patch path's planes: a power of two, and a plane block must stay
-        // addressable with 32-bit byte offsets (n sites x 2^lg pairs x 16 bytes)
-        int lg = 0;
-        while ((2 << lg) <= p->tune.pair_block && lg < 4) lg++;
-        while (lg > 0 && ((uint64_t)n << (lg + 4)) > 0xFFFFFFFFull) lg--;
-        p->lg_pair_block = lg;
-    }
-    // a patch owns as many consecutive sites as its dependency cone leaves room for (VRT_PATCH_OWN: at most that many)
-    const int patch_own = p->tune.patch_own > 0 ? std::min(p->tune.patch_own, p->patch_cap) : p->patch_cap;
-    {
-        // one job per angle, dealt to the host threads; a job splits further by layer (the layers of an angle are analysed
-        // independently, vrt_patch.cpp) when threads are left over.  The patch builder returns the angle's layer schedule
-        // as a by-product -- the same analysis -- so build_layer_schedule itself only runs for an angle whose layers do not
-        // fit the packed encoding (it then says so too; the level kernels take over).
-        const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-        // (all angles at once when the host has four threads for each: no second round with most threads idle)
-        const int nthr = std::max(1, (int)std::min<unsigned>(std::min(hw, (unsigned)A * 4u <= hw ? 64u : 16u), (unsigned)A));
-        const int sub_threads = (int)std::max(1u, std::min(16u, hw / (unsigned)nthr));
-        std::atomic<int> next_job(0);
-        // (every schedule build holds a visit trace of up to n_sweeps n entries and a dozen n-sized arrays)
-        if (!run_workers(nthr, [&](int) {
-                for (;;) {
-                    const int a = next_job.fetch_add(1);
-                    if (a >= A) break;
-                    const bool up = p->dir_of_active[(size_t)a] > 0;
-                    const int32_t *u1 = p->h_up1.data() + (size_t)a * n, *u2 = p->h_up2.data() + (size_t)a * n;
-                    build_patch_schedule(up ? g->up : g->down, /*ascending=*/up, n, n_sweeps, u1, u2, patch_own,
-                                         p->patch_cap, psched[(size_t)a], sub_threads, &lsched[(size_t)a]);
-                    if (!lsched[(size_t)a].ok && lsched[(size_t)a].bad_site < 0)
-                        build_layer_schedule(up ? g->up : g->down, /*ascending=*/up, n, n_sweeps, u1, u2, lsched[(size_t)a]);
-                }
-            })) {
-            free_plan(p);
-            return fail(VRT_ENOMEM, "out of host memory while building the sweep schedules");
-        }
-    }
+    std::vector<LayerSchedule> lsched;
+    std::vector<PatchSchedule> psched;                // fused patch path (vrt_patch.cpp)
+    if ((rc = plan_host_schedules(p.get(), lsched, psched))) return rc;
     tick("layer + patch schedules");
-    for (int a = 0; a < A; a++) {
-        if (lsched[(size_t)a].bad_site >= 0) {
-            std::string msg = "site " + std::to_string(lsched[(size_t)a].bad_site + 1) +
-                              " has no neighbour with k . line > -1 for angle " +
-                              std::to_string(p->user_of_active[(size_t)a] + 1) +
-                              " (the reference reads an uninitialised index here)";
-            free_plan(p);
-            return fail(VRT_EGRID, msg);
-        }
-    }
-    std::vector<int32_t> ups, downs;
-    for (int a = 0; a < A; a++) (p->dir_of_active[(size_t)a] > 0 ? ups : downs).push_back(a);
-    p->n_up = (int)ups.size();
-    p->n_down = (int)downs.size();
-    VRT_TRY_FREE(dev_alloc(&p->d_angles_up, ups.size()));
-    VRT_TRY_FREE(dev_alloc(&p->d_angles_down, downs.size()));
-    if (!ups.empty())
-        VRT_HIP_TRY_FREE(hipMemcpy(p->d_angles_up, ups.data(), sizeof(int32_t) * ups.size(), hipMemcpyHostToDevice));
-    if (!downs.empty())
-        VRT_HIP_TRY_FREE(hipMemcpy(p->d_angles_down, downs.data(), sizeof(int32_t) * downs.size(), hipMemcpyHostToDevice));
-    // ---- layer paths: tables in storage order, per-layer level counts, patch schedules -------------
-    {
-        bool ok = A > 0;
-        int64_t max_layer = 0, visits = 0;
-        for (int a = 0; a < A; a++) {
-            ok = ok && lsched[(size_t)a].ok;
-            max_layer = std::max(max_layer, lsched[(size_t)a].max_layer_size);
-            visits += lsched[(size_t)a].n_visits;
-        }
-        // the boundary layer is a layer too: k_sweep_tiles_pre keeps it in LDS as the first "previous" layer
-        if (p->n_up > 0) max_layer = std::max(max_layer, g->up.n1);
-        if (p->n_down > 0) max_layer = std::max(max_layer, g->down.n1);
-        if (n >= ((int64_t)1 << 28)) ok = false;  // the layer kernels index 16-byte pair planes with 32-bit byte offsets
-        // the layer-step level kernels hold a whole layer per workgroup: 8192 sites as fp64 wavelength
-        // pairs, 12 288 as fp64 single wavelengths, 18 432 as fp32 ones (vrt_step_kernels.h); the fused
-        // patch kernel (vrt_patch.hip) has no such limit
-        const bool tile_ok = ok && max_layer <= steps_max_layer(/*f32=*/true);
-        bool patch_ok = ok;
-        int64_t n_patches = 0, n_entries = 0;
-        for (int a = 0; a < A && patch_ok; a++) {
-            patch_ok = psched[(size_t)a].ok;
-            n_patches += (int64_t)psched[(size_t)a].patch_own_lo.size();
-            n_entries += (int64_t)psched[(size_t)a].entry_pos.size();
-        }
-        if (n_entries >= ((int64_t)1 << 31) - 1 || n_patches >= ((int64_t)1 << 31) - 1) patch_ok = false;
-        p->tile_ok = tile_ok;
-        p->patch_ok = patch_ok;
-        p->tile_max_layer_size = max_layer;
-        p->tile_visits = visits;
-        p->tile_K = max_layer <= 2048 ? 2 : max_layer <= 4096 ? 4 : 8;
-        if (tile_ok || patch_ok) {
-            VRT_TRY_FREE(dev_alloc(&p->t_u1, tab));
-            VRT_TRY_FREE(dev_alloc(&p->t_u2, tab));
-            VRT_TRY_FREE(dev_alloc(&p->t_w1, tab));
-            VRT_TRY_FREE(dev_alloc(&p->t_w2, tab));
-            VRT_TRY_FREE(dev_alloc(&p->t_r1, tab));
-            VRT_TRY_FREE(dev_alloc(&p->t_r2, tab));
-            VRT_TRY_FREE(dev_alloc(&p->t_vis, tab));
-            VRT_TRY_FREE(dev_alloc(&p->t_loc, tab));
-            // (the sorted-slot tables of the steps / tiles paths are built when one of those paths first runs:
-            // ensure_step_tables -- the default patch path needs none of them)
-            const int maxL = (int)std::max(g->up.reduced.size(), g->down.reduced.size()) - 1;
-            p->tile_max_layers = maxL;
-            if (patch_ok) {
-                const size_t ne = (size_t)n_entries;
-                VRT_TRY_FREE(dev_alloc(&p->e_pos, ne));
-                VRT_TRY_FREE(dev_alloc(&p->e_u1, ne));
-                VRT_TRY_FREE(dev_alloc(&p->e_u2, ne));
-                VRT_TRY_FREE(dev_alloc(&p->e_vis, ne));
-                VRT_TRY_FREE(dev_alloc(&p->e_loc, ne));
-                VRT_TRY_FREE(dev_alloc(&p->e_w1, ne));
-                VRT_TRY_FREE(dev_alloc(&p->e_w2, ne));
-                VRT_TRY_FREE(dev_alloc(&p->e_r1, ne));
-                VRT_TRY_FREE(dev_alloc(&p->e_r2, ne));
-                p->h_patch_first.assign((size_t)A * (size_t)(maxL + 2), 0);
-                p->h_patch_rec.reserve((size_t)n_patches);
-                p->n_patches = n_patches;
-                p->n_patch_entries = n_entries;
-            }
-            uint32_t *d_vis_site = nullptr;
-            VRT_TRY_FREE(dev_alloc(&d_vis_site, (size_t)n));
-            std::vector<int32_t> nlev((size_t)A * (size_t)(maxL + 1), 0), adir((size_t)A);
-            std::vector<int2> rec2;
-            p->angle_visits.assign((size_t)A, 0);
-            int64_t ent_base = 0;
-            for (int a = 0; a < A; a++) {
-                hipError_t e = hipMemcpy(d_vis_site, lsched[(size_t)a].vis.data(), sizeof(uint32_t) * n,
-                                         hipMemcpyHostToDevice);
-                int rc2 = e == hipSuccess ? launch_permute_table(p, a, d_vis_site) : VRT_ENODEVICE;
-                if (!rc2 && patch_ok) {    // patch records + entry tables of this angle
-                    PatchSchedule &ps = psched[(size_t)a];
-                    const size_t np_a = ps.patch_own_lo.size(), ne_a = ps.entry_pos.size();
-                    const int32_t pbase = (int32_t)p->h_patch_rec.size();
-                    int32_t *first = p->h_patch_first.data() + (size_t)a * (size_t)(maxL + 2);
-                    for (int l = 0; l <= maxL + 1; l++)
-                        first[l] = pbase + ps.layer_patch_off[std::min<size_t>((size_t)l, ps.layer_patch_off.size() - 1)];
-                    for (size_t q = 0; q < np_a; q++) {
-                        p->h_patch_rec.push_back(make_int4((int)(ent_base + ps.patch_ent_off[q]),
-                                                           (int)(ps.patch_ent_off[q + 1] - ps.patch_ent_off[q]),
-                                                           ps.patch_own_lo[q], ps.patch_own_cnt[q]));
-                        rec2.push_back(make_int2(ps.patch_nlev[q], a));
-                        p->h_patch_dep_off.push_back((int64_t)p->h_patch_deps.size());
-                        for (int64_t j = ps.dep_off[q]; j < ps.dep_off[q + 1]; j++)
-                            p->h_patch_deps.push_back(pbase + ps.dep_list[(size_t)j]);
-                    }
-                    if (ne_a) {
-                        if (hipMemcpy(p->e_pos + ent_base, ps.entry_pos.data(), sizeof(int32_t) * ne_a, hipMemcpyHostToDevice) != hipSuccess ||
-                            hipMemcpy(p->e_vis + ent_base, ps.entry_vis.data(), sizeof(uint32_t) * ne_a, hipMemcpyHostToDevice) != hipSuccess ||
-                            hipMemcpy(p->e_loc + ent_base, ps.entry_loc.data(), sizeof(uint32_t) * ne_a, hipMemcpyHostToDevice) != hipSuccess)
-                            rc2 = VRT_ENODEVICE;
-                        if (!rc2) rc2 = launch_patch_entries(p, a, ent_base, (int64_t)ne_a);
-                    }
-                    ent_base += (int64_t)ne_a;
-                    p->n_patch_visits += ps.n_visits;
-                    ps = PatchSchedule();
-                }
-                if (!rc2 && hipStreamSynchronize(g->stream) != hipSuccess) rc2 = VRT_ENODEVICE;
-                if (rc2) {
-                    dev_free(d_vis_site);
-                    free_plan(p);
-                    return fail(VRT_ENODEVICE, "building the sweep-order tables failed");
-                }
-                const std::vector<int32_t> &nl = lsched[(size_t)a].nlev;
-                for (size_t l = 0; l < nl.size() && l <= (size_t)maxL; l++)
-                    nlev[(size_t)a * (size_t)(maxL + 1) + l] = nl[l];
-                adir[(size_t)a] = p->dir_of_active[(size_t)a] > 0 ? 0 : 1;
-                p->angle_visits[(size_t)a] = lsched[(size_t)a].n_visits + n;   // + n: phase 1 touches every site
-                {
-                    double sum = 0.0;
-                    int cntl = 0;
-                    for (size_t l = 2; l < nl.size(); l++, cntl++) sum += nl[l];
-                    p->angle_mean_levels.push_back(cntl ? sum / cntl : 0.0);
-                }
-            }
-            dev_free(d_vis_site);
-            VRT_TRY_FREE(dev_alloc(&p->d_nlev, nlev.size()));
-            VRT_TRY_FREE(dev_alloc(&p->d_angle_dir, (size_t)A));
-            VRT_HIP_TRY_FREE(hipMemcpy(p->d_nlev, nlev.data(), sizeof(int32_t) * nlev.size(), hipMemcpyHostToDevice));
-            VRT_HIP_TRY_FREE(hipMemcpy(p->d_angle_dir, adir.data(), sizeof(int32_t) * A, hipMemcpyHostToDevice));
-            if (patch_ok) {
-                p->h_patch_dep_off.push_back((int64_t)p->h_patch_deps.size());
-                p->h_patch_rec2 = rec2;
-            }
-        }
-    }
+    if ((rc = plan_check_upwind(p.get(), lsched))) return rc;
+    if ((rc = plan_angle_lists(p.get()))) return rc;
+    plan_layer_fit(p.get(), lsched, psched);
+    if ((rc = plan_storage_tables(p.get(), lsched, psched))) return rc;
     tick("tables upload + entry kernels");
-#undef VRT_TRY_FREE
-#undef VRT_HIP_TRY_FREE
-    *out = p;
+    *out = p.release();
     return VRT_OK;
 }
 
@@ -682,8 +583,9 @@ int vrt::ensure_step_tables(vrt_plan *p)
     const int A = p->A, n_sweeps = p->n_sweeps;
     const size_t tab = (size_t)A * (size_t)n;
     int rc;
-    // (a table an earlier, failed attempt already allocated is kept: a retry neither leaks it nor overwrites its pointer)
-    auto need = [&](auto *&ptr) -> int { return ptr ? VRT_OK : dev_alloc(&ptr, tab); };
+    // (the launchers below read the tables from the plan, so the plan owns each from the moment it exists; one that an
+    // earlier, failed attempt allocated is kept, and step_tables_ready says when their contents are complete: a retry works)
+    auto need = [&](auto &buf) -> int { return buf ? VRT_OK : buf.alloc(tab); };
     if ((rc = need(p->t_self)) || (rc = need(p->t_vis_s)) || (rc = need(p->t_loc_s)) || (rc = need(p->t_gpos)) ||
         (rc = need(p->t_rank_s)) || (rc = need(p->t_loc_ss)))
         return rc;
@@ -791,7 +693,7 @@ static int execute_levels(vrt_plan *p, const ExecArgs &x)
     int rc;
     if ((rc = ensure_level_schedule(p))) return rc;
     const size_t need = (size_t)std::max(1, p->A) * (size_t)p->g->n * (size_t)x.nlam;
-    if ((rc = dev_grow(p->d_I, p->I_cap, x.f32 ? (need + 1) / 2 : need))) return rc;
+    if ((rc = p->d_I.grow(x.f32 ? (need + 1) / 2 : need))) return rc;
     p->I_ld = x.nlam;
     SweepArgs sa;
     sa.f32 = x.f32;
@@ -859,7 +761,7 @@ static int lambda_update_call(vrt_grid *g, double *max_rel_change, hipStream_t s
     int rc = use_device(g->device);
     if (rc) return rc;
     std::lock_guard<std::mutex> lock(g->mu);
-    if (!g->d_scalars && (rc = dev_alloc(&g->d_scalars, kUpdateWords))) return rc;
+    if (!g->d_scalars && (rc = g->d_scalars.alloc(kUpdateWords))) return rc;
     unsigned long long *d_res = g->d_scalars;
     rc = launch(d_res);
     unsigned long long h[2] = {0, 0};
@@ -941,7 +843,7 @@ void vrt_grid_destroy(vrt_grid *g)
 {
     DeviceScope scope;
     if (g && g->device >= 0) (void)hipSetDevice(g->device);
-    free_grid(g);
+    delete g;
 }
 
 int64_t vrt_grid_n(const vrt_grid *g) { return g ? g->n : 0; }
@@ -1018,8 +920,8 @@ int vrt_plan_create(vrt_grid *g, int64_t n_angles, const double *k, int n_sweeps
 void vrt_plan_destroy(vrt_plan *p)
 {
     DeviceScope scope;
-    if (p && p->g) (void)hipSetDevice(p->g->device);
-    free_plan(p);
+    if (p) (void)hipSetDevice(p->device);
+    delete p;
 }
 
 // the level schedule is built lazily, under the plan's mutex: -1 when that fails
@@ -1391,28 +1293,28 @@ int vrt_plan_execute(vrt_plan *p, int64_t nlam, int64_t ld, const double *S, con
                                                              : nS * (size_t)p->n_angles_user;
         const size_t nU = (size_t)g->up.n1 * (size_t)nlam, nD = (size_t)g->down.n1 * (size_t)nlam;
         hipStream_t st = g->stream;
-        if ((rc = dev_grow(p->d_stage[0], p->stage_cap[0], nS))) return rc;
-        if ((rc = dev_grow(p->d_stage[1], p->stage_cap[1], nA))) return rc;
+        if ((rc = p->d_stage[0].grow(nS))) return rc;
+        if ((rc = p->d_stage[1].grow(nA))) return rc;
         VRT_HIP_TRY(hipMemcpyAsync(p->d_stage[0], S, sizeof(double) * nS, hipMemcpyHostToDevice, st));
         VRT_HIP_TRY(hipMemcpyAsync(p->d_stage[1], alpha, sizeof(double) * nA, hipMemcpyHostToDevice, st));
         double *dU = nullptr, *dD = nullptr, *dJ = nullptr;
         if (I0_up && nU) {
-            if ((rc = dev_grow(p->d_stage[2], p->stage_cap[2], nU))) return rc;
+            if ((rc = p->d_stage[2].grow(nU))) return rc;
             dU = p->d_stage[2];
             VRT_HIP_TRY(hipMemcpyAsync(dU, I0_up, sizeof(double) * nU, hipMemcpyHostToDevice, st));
         }
         if (I0_down && nD) {
-            if ((rc = dev_grow(p->d_stage[3], p->stage_cap[3], nD))) return rc;
+            if ((rc = p->d_stage[3].grow(nD))) return rc;
             dD = p->d_stage[3];
             VRT_HIP_TRY(hipMemcpyAsync(dD, I0_down, sizeof(double) * nD, hipMemcpyHostToDevice, st));
         }
         if (J) {
-            if ((rc = dev_grow(p->d_stage[4], p->stage_cap[4], nS))) return rc;
+            if ((rc = p->d_stage[4].grow(nS))) return rc;
             dJ = p->d_stage[4];
         }
         double *dIo = nullptr;
         if (I_out) {
-            if ((rc = dev_grow(p->d_stage[5], p->stage_cap[5], nS * (size_t)p->n_angles_user))) return rc;
+            if ((rc = p->d_stage[5].grow(nS * (size_t)p->n_angles_user))) return rc;
             dIo = p->d_stage[5];
         }
         rc = execute_locked(p, caller_args(nlam, ld, p->d_stage[0], p->d_stage[1], alpha_mode, dU, dD, weights, dJ, dIo, st, false));
@@ -1487,7 +1389,7 @@ int vrt_grid_set_option(vrt_grid *g, const char *name, const char *value)
         for (auto &o : g->options)
             if (o.first == name) { o.second = value; found = true; }
         if (!found) g->options.emplace_back(name, value);
-        for (PlanCacheEntry *c : g->cache) {                             // cached single-solve plans follow where they can
+        for (auto &c : g->cache) {                                       // cached single-solve plans follow where they can
             std::lock_guard<std::mutex> plock(c->plan->mu);
             (void)tuning_set(c->plan->tune, name, value, /*created=*/true);
         }
@@ -1531,22 +1433,21 @@ int vrt_lambda_update_native_dev(vrt_grid *g, int64_t nlam, const double *dJ_up,
 // host only waits for its OWN previous copy out of that buffer (small_copy_ev, long done by then).
 static int upload_small(vrt_grid *g, const std::vector<double> &h, hipStream_t st)
 {
+    int rc;
     if (g->small_ev_valid) VRT_HIP_TRY(hipStreamWaitEvent(st, g->small_ev, 0));
     if (g->small_copy_valid) VRT_HIP_TRY(hipEventSynchronize(g->small_copy_ev));
     if (!g->d_small || g->small_cap < h.size()) {
         if (g->small_ev_valid) VRT_HIP_TRY(hipEventSynchronize(g->small_ev));   // about to free what it read
-        dev_free(g->d_small);
-        if (g->h_small) { (void)hipHostFree(g->h_small); g->h_small = nullptr; }
+        g->d_small.reset();
+        g->h_small.reset();
         g->small_cap = 0;
         const size_t cap = std::max<size_t>(2 * h.size(), 256);
-        int rc = dev_alloc(&g->d_small, cap);
-        if (rc) return rc;
-        VRT_HIP_TRY(hipHostMalloc((void **)&g->h_small, sizeof(double) * cap, hipHostMallocDefault));
+        if ((rc = g->d_small.alloc(cap)) || (rc = g->h_small.alloc(cap))) return rc;
         g->small_cap = cap;
     }
     std::memcpy(g->h_small, h.data(), sizeof(double) * h.size());
     VRT_HIP_TRY(hipMemcpyAsync(g->d_small, g->h_small, sizeof(double) * h.size(), hipMemcpyHostToDevice, st));
-    if (!g->small_copy_ev) VRT_HIP_TRY(hipEventCreateWithFlags(&g->small_copy_ev, hipEventDisableTiming));
+    if (!g->small_copy_ev && (rc = g->small_copy_ev.create(hipEventDisableTiming))) return rc;
     VRT_HIP_TRY(hipEventRecord(g->small_copy_ev, st));
     g->small_copy_valid = true;
     return VRT_OK;
@@ -1554,7 +1455,7 @@ static int upload_small(vrt_grid *g, const std::vector<double> &h, hipStream_t s
 
 static int small_done(vrt_grid *g, hipStream_t st)
 {
-    if (!g->small_ev) VRT_HIP_TRY(hipEventCreateWithFlags(&g->small_ev, hipEventDisableTiming));
+    if (int rc = g->small_ev ? VRT_OK : g->small_ev.create(hipEventDisableTiming)) return rc;
     VRT_HIP_TRY(hipEventRecord(g->small_ev, st));
     g->small_ev_valid = true;
     return VRT_OK;
@@ -1681,30 +1582,30 @@ static int single_solve(vrt_grid *g, int dir, const double k[3], const double *S
         PlanCacheEntry *entry = nullptr;
         {
             std::lock_guard<std::mutex> lock(g->mu);
-            for (PlanCacheEntry *c : g->cache)
+            for (auto &c : g->cache)
                 if (c->n_sweeps == n_sweeps * dir && c->k[0] == k[0] && c->k[1] == k[1] && c->k[2] == k[2])
-                    entry = c;
+                    entry = c.get();
             if (!entry) {
                 int dirs[1] = {dir};
                 vrt_plan *plan = nullptr;
                 int rc = plan_create_impl(g, 1, k, dirs, n_sweeps, &plan, &g->options);
                 if (rc) return rc;
+                PlanPtr owned(plan);
+                std::unique_ptr<PlanCacheEntry> made(new PlanCacheEntry{{k[0], k[1], k[2]}, n_sweeps * dir, std::move(owned), 0});
                 if (g->cache.size() >= 64)      // drop the oldest entry nobody is using
                     for (size_t i = 0; i < g->cache.size(); i++)
                         if (g->cache[i]->users == 0) {
-                            vrt_plan_destroy(g->cache[i]->plan);
-                            delete g->cache[i];
                             g->cache.erase(g->cache.begin() + (long)i);
                             break;
                         }
-                entry = new PlanCacheEntry{{k[0], k[1], k[2]}, n_sweeps * dir, plan, 0};
-                g->cache.push_back(entry);
+                entry = made.get();
+                g->cache.push_back(std::move(made));
             }
             entry->users++;
         }
         const double one = 1.0;
         // I_out doubles as J with weight 1: J = 0 + 1*I is exact
-        const int rc = vrt_plan_execute(entry->plan, 1, 1, S, alpha, VRT_ALPHA_SITE, dir > 0 ? I0 : nullptr,
+        const int rc = vrt_plan_execute(entry->plan.get(), 1, 1, S, alpha, VRT_ALPHA_SITE, dir > 0 ? I0 : nullptr,
                                         dir > 0 ? nullptr : I0, &one, I_out, nullptr);
         {
             std::lock_guard<std::mutex> lock(g->mu);

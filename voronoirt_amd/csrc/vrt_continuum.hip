@@ -356,7 +356,7 @@ int upload(DevBuf<double> &d, const double *h, size_t count, hipStream_t st)
 using namespace vrt;
 
 struct vrt_continuum {
-    vrt_plan *p = nullptr;
+    vrt_plan *p = nullptr;              // borrowed
     int device = 0;                     // of the plan's grid (destroying the session must not look into a plan that may be gone)
     int64_t n = 0, nlam = 0;
     double eps_thick = 0;
@@ -374,7 +374,6 @@ struct vrt_continuum {
     // its up-order plane set
     int op = 0;
     DevBuf<double> d_diag, d_L_up;
-    ~vrt_continuum() { ng_release(ng); }
 };
 
 struct vrt_regular_continuum {
@@ -383,7 +382,7 @@ struct vrt_regular_continuum {
     int64_t n = 0, nlam = 0;
     double eps_thick = 0;
     LineSolves ls;
-    hipStream_t st = nullptr;
+    Stream st;
     DevBuf<double> d_B0, d_eps, d_J;    // per point, Julia order, (n, nlam)
     DevBuf<double> d_S[2];              // [sc]: the last S_new
     int sc = 0;
@@ -391,11 +390,6 @@ struct vrt_regular_continuum {
     DevBuf<unsigned long long> d_scalars;
     int64_t iterations = 0;
     NgState ng;
-    ~vrt_regular_continuum()
-    {
-        ng_release(ng);
-        if (st) (void)hipStreamDestroy(st);
-    }
 };
 
 // the S buffer a session's acceleration works on: doubles allocated, and which of them are physical entries
@@ -443,7 +437,7 @@ int vrt_continuum_update_dev(vrt_grid *g, int64_t nlam, int64_t ld, const double
         int rc = use_device(g->device);
         if (rc) return rc;
         std::lock_guard<std::mutex> lock(g->mu);
-        if (!g->d_scalars && (rc = dev_alloc(&g->d_scalars, kUpdateWords))) return rc;
+        if (!g->d_scalars && (rc = g->d_scalars.alloc(kUpdateWords))) return rc;
         hipStream_t st = (hipStream_t)stream;
         if ((rc = launch_continuum_update(g->n, nlam, ld, dJ, dB, deps, nullptr, eps_thick, dS_old, dS_new, g->d_scalars, st)))
             return rc;
@@ -462,7 +456,7 @@ int vrt_continuum_ali_update_dev(vrt_grid *g, int64_t nlam, int64_t ld, const do
         int rc = use_device(g->device);
         if (rc) return rc;
         std::lock_guard<std::mutex> lock(g->mu);
-        if (!g->d_scalars && (rc = dev_alloc(&g->d_scalars, kUpdateWords))) return rc;
+        if (!g->d_scalars && (rc = g->d_scalars.alloc(kUpdateWords))) return rc;
         hipStream_t st = (hipStream_t)stream;
         if ((rc = launch_continuum_update(g->n, nlam, ld, dJ, dB, deps, d_diag, eps_thick, dS_old, dS_new, g->d_scalars, st)))
             return rc;
@@ -620,7 +614,7 @@ int vrt_continuum_iterate(vrt_continuum *s, double *max_rel_change)
             // copy and the down-order copy is rewritten from it, value for value)
             NgRange rg;
             const size_t count = continuum_S_count(s, &rg);
-            double *&S = s->native ? s->d_S_nat[0].p : s->d_S_new.p;
+            DevBuf<double> &S = s->native ? s->d_S_nat[0] : s->d_S_new;
             if ((rc = ng_after_iterate(s->ng, s->iterations, S, count, rg, st))) return rc;
             if (s->ng.last_applied == 1 && s->native) {
                 if ((rc = launch_ng_mirror(g, nlam, s->d_S_nat[0], s->d_S_nat[1], st))) return rc;
@@ -815,7 +809,7 @@ int vrt_regular_continuum_create(vrt_regular *r, int64_t n_angles, const double 
         s->nlam = nlam;
         s->eps_thick = cc->eps_thick;
         if ((rc = line_solves_init(s->ls, r, n_angles, k, dirs, weights, nlam))) return rc;
-        VRT_HIP_TRY(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
+        if ((rc = s->st.create())) return rc;
         hipStream_t st = s->st;
         const size_t nS = (size_t)vol * (size_t)nlam;
 #define VRT_S(expr) do { if ((rc = (expr))) return rc; } while (0)
@@ -868,7 +862,7 @@ int vrt_regular_continuum_iterate(vrt_regular_continuum *s, double *max_rel_chan
         if (s->ng.order) {
             NgRange rg;
             rg.dense = (n * nlam) & ~(int64_t)1; rg.tail = (n * nlam) & 1; rg.tstride = 1;
-            if ((rc = ng_after_iterate(s->ng, s->iterations, s->d_S[s->sc].p, (size_t)(n * nlam), rg, st))) return rc;
+            if ((rc = ng_after_iterate(s->ng, s->iterations, s->d_S[s->sc], (size_t)(n * nlam), rg, st))) return rc;
             if (s->ng.last_applied == 1) {
                 if ((rc = launch_to_planes(r, nlam, s->d_S[s->sc], s->d_S_pl, st))) return rc;
                 VRT_HIP_TRY(hipStreamSynchronize(st));

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -74,35 +75,113 @@ inline int dev_alloc(T **p, size_t count)
     return fail(e == hipErrorOutOfMemory ? VRT_ENOMEM : VRT_ENODEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
 }
 
-template <typename T>
-inline void dev_free(T *&p)
-{
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
-}
+// ---- owners: whoever holds one of these releases it exactly once, when it goes out of scope.  All are move-only.  A
+// handle (vrt_grid, vrt_plan, ...) is a struct of them and has no free list of its own; its *_destroy entry point makes
+// the handle's device current and deletes it.  They are the only callers of hipFree, hipHostMalloc / hipHostFree and of
+// the create / destroy calls of streams and events.
 
-// Grow-only workspace: a buffer of fewer than `count` elements is freed and `count` allocated (cap = 0 on failure).
-template <typename T>
-inline int dev_grow(T *&buf, size_t &cap, size_t count)
-{
-    if (buf && count <= cap) return VRT_OK;
-    dev_free(buf);
-    cap = 0;
-    const int rc = dev_alloc(&buf, count);
-    if (!rc) cap = count;
-    return rc;
-}
-
-// Device scratch of one call, freed when it goes out of scope (the staging of the host-pointer entry points).
+// Device memory: alloc() frees what it held; converts to T* wherever a raw (borrowed) pointer is wanted.
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     DevBuf() = default;
     DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
     DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); return *this; }
-    ~DevBuf() { dev_free(p); }
-    int alloc(size_t count) { dev_free(p); return dev_alloc(&p, count); }
+    ~DevBuf() { reset(); }
+    void reset()
+    {
+        if (p) (void)hipFree((void *)p);
+        p = nullptr;
+    }
+    int alloc(size_t count) { reset(); return dev_alloc(&p, count); }
+    T *get() const { return p; }
     operator T *() const { return p; }
+};
+
+// Grow-only workspace: a buffer of fewer than `count` elements is freed and `count` allocated (cap = 0 on failure).
+template <typename T>
+struct DevWork {
+    DevBuf<T> buf;
+    size_t cap = 0;
+    int grow(size_t count)
+    {
+        if (buf.p && count <= cap) return VRT_OK;
+        reset();
+        const int rc = buf.alloc(count);
+        if (!rc) cap = count;
+        return rc;
+    }
+    void reset() { buf.reset(); cap = 0; }
+    T *get() const { return buf.p; }
+    operator T *() const { return buf.p; }
+};
+
+// Pinned (or, with hipHostMallocMapped, mapped) host memory.
+template <typename T>
+struct HostBuf {
+    T *p = nullptr;
+    HostBuf() = default;
+    HostBuf(HostBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+    HostBuf &operator=(HostBuf &&o) noexcept { std::swap(p, o.p); return *this; }
+    ~HostBuf() { reset(); }
+    void reset()
+    {
+        if (p) (void)hipHostFree((void *)p);
+        p = nullptr;
+    }
+    int alloc(size_t count, unsigned flags = hipHostMallocDefault)
+    {
+        reset();
+        const hipError_t e = hipHostMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T), flags);
+        if (e == hipSuccess) return VRT_OK;
+        p = nullptr;
+        return fail(VRT_ENODEVICE, std::string("hipHostMalloc: ") + hipGetErrorString(e));
+    }
+    operator T *() const { return p; }
+};
+
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream &&o) noexcept : s(o.s) { o.s = nullptr; }
+    Stream &operator=(Stream &&o) noexcept { std::swap(s, o.s); return *this; }
+    ~Stream() { reset(); }
+    void reset()
+    {
+        if (s) (void)hipStreamDestroy(s);
+        s = nullptr;
+    }
+    int create(unsigned flags = hipStreamNonBlocking)
+    {
+        reset();
+        const hipError_t e = hipStreamCreateWithFlags(&s, flags);
+        if (e == hipSuccess) return VRT_OK;
+        s = nullptr;
+        return fail(VRT_ENODEVICE, std::string("hipStreamCreateWithFlags: ") + hipGetErrorString(e));
+    }
+    operator hipStream_t() const { return s; }
+};
+
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }
+    ~Event() { reset(); }
+    void reset()
+    {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    int create(unsigned flags = hipEventDefault)      // (timing events: the default; the rest pass hipEventDisableTiming)
+    {
+        reset();
+        const hipError_t err = hipEventCreateWithFlags(&e, flags);
+        if (err == hipSuccess) return VRT_OK;
+        e = nullptr;
+        return fail(VRT_ENODEVICE, std::string("hipEventCreateWithFlags: ") + hipGetErrorString(err));
+    }
+    operator hipEvent_t() const { return e; }
 };
 
 // Runs body(t) for t = 0 .. count-1 on `count` host threads.  A worker must not throw (an exception that leaves a
@@ -148,16 +227,16 @@ struct Direction {
     std::vector<int64_t> perm;       // stable sortperm, 1-based site ids (:72,77)
     std::vector<int64_t> reduced;    // reduce_layers offsets, 1-based, r[end] = n (:253-269)
     int64_t n1 = 0;                  // reduced[1] - 1: sites that receive I_0
-    int32_t *d_order = nullptr;      // device copy of perm, 0-based int32: sweep position -> site
-    int32_t *d_rank = nullptr;       // inverse: site -> sweep position
-    int32_t *d_lay = nullptr;        // 0-based layer boundaries: layer l = [lay[l-1], lay[l]), L+1 entries
+    DevBuf<int32_t> d_order;         // device copy of perm, 0-based int32: sweep position -> site
+    DevBuf<int32_t> d_rank;          // inverse: site -> sweep position
+    DevBuf<int32_t> d_lay;           // 0-based layer boundaries: layer l = [lay[l-1], lay[l]), L+1 entries
     // STORAGE order of the layer-tile path: layers contiguous exactly like the sweep order, but
     // inside a layer the sites are sorted in strips of rows (vrt_grid.cpp; VRT_STORE_ORDER=morton: along a Morton curve over (x, y)) so that spatial
     // neighbours (and therefore upwind gathers) share cache lines; the never-visited last site
     // perm[n] stays at position n-1.  The Gauss-Seidel ORDER is unaffected (it lives in the schedule).
     std::vector<int32_t> store;      // storage position -> site (0-based)
-    int32_t *d_store = nullptr;
-    int32_t *d_srank = nullptr;      // site -> storage position
+    DevBuf<int32_t> d_store;
+    DevBuf<int32_t> d_srank;         // site -> storage position
 };
 
 struct PlanCacheEntry;
@@ -166,9 +245,9 @@ struct PlanCacheEntry;
 // and two pinned staging buffers, filled / drained by a host thread of its own, so that the caller's pageable arrays
 // travel at PCIe speed (a pageable hipMemcpy stages through ONE thread: 0.4 GB of S took 20 ms each way)
 struct CopyLane {
-    hipStream_t st = nullptr;
-    void *pin[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Stream st;
+    HostBuf<char> pin[2];
+    Event ev[2];
 };
 constexpr size_t kCopyChunk = (size_t)8 << 20;      // bytes per staging buffer
 
@@ -265,7 +344,8 @@ inline ExecArgs native_args(int64_t nlam, const void *S_up, const void *S_down, 
 
 namespace vrt {
 struct RasterLocator;                // vrt_raster.hip: cell list and seeds of the nearest-site walk, workspaces
-void raster_locator_free(vrt_grid *g);
+void raster_locator_delete(RasterLocator *L);
+struct RasterLocatorDelete { void operator()(RasterLocator *L) const { raster_locator_delete(L); } };
 }
 
 struct vrt_grid {
@@ -278,31 +358,31 @@ struct vrt_grid {
     std::vector<int32_t> col;        // 1-based ids, walls <= 0, row order preserved
     vrt::Direction up, down;
     // device mirrors
-    double *d_pos = nullptr;
-    int32_t *d_rowptr = nullptr;
-    int32_t *d_col = nullptr;
-    double *d_lz = nullptr, *d_lx = nullptr, *d_ly = nullptr;   // Delaunay lines, CSR-packed SoA
-    hipStream_t stream = nullptr;
-    unsigned long long *d_scalars = nullptr;   // scratch of the Λ-iteration epilogue's reduction (kUpdateWords)
-    double *d_small = nullptr;                 // wavelength-sized host arrays of the physics kernels (λ, 2hc²/λ⁵, σ_bf)
+    vrt::DevBuf<double> d_pos;
+    vrt::DevBuf<int32_t> d_rowptr, d_col;
+    vrt::DevBuf<double> d_lz, d_lx, d_ly;      // Delaunay lines, CSR-packed SoA
+    vrt::Stream stream;
+    vrt::DevBuf<unsigned long long> d_scalars; // scratch of the Λ-iteration epilogue's reduction (kUpdateWords)
+    vrt::DevBuf<double> d_small;               // wavelength-sized host arrays of the physics kernels (λ, 2hc²/λ⁵, σ_bf)
     size_t small_cap = 0;
-    double *h_small = nullptr;                 // pinned staging buffer of the same capacity
-    hipEvent_t small_ev = nullptr;             // last kernel that read d_small
+    vrt::HostBuf<double> h_small;              // pinned staging buffer of the same capacity
+    vrt::Event small_ev;                       // last kernel that read d_small
     bool small_ev_valid = false;
-    hipEvent_t small_copy_ev = nullptr;        // last copy out of h_small
+    vrt::Event small_copy_ev;                  // last copy out of h_small
     bool small_copy_valid = false;
     // options applied to the single-solve plans cached below (vrt_grid_set_option)
     std::vector<std::pair<std::string, std::string>> options;
     // cache of single-angle plans for vrt_delaunay_up/down
     std::mutex mu;
-    std::vector<vrt::PlanCacheEntry *> cache;
+    std::vector<std::unique_ptr<vrt::PlanCacheEntry>> cache;    // (declared after the device mirrors: the plans go first)
     // nearest-site search of the raster resampling (built on first use, under mu); cells per axis, 0 = auto
-    vrt::RasterLocator *locator = nullptr;
+    std::unique_ptr<vrt::RasterLocator, vrt::RasterLocatorDelete> locator;
     int64_t nearest_cells = 0;
 };
 
 struct vrt_plan {
-    vrt_grid *g = nullptr;
+    vrt_grid *g = nullptr;              // borrowed: the caller keeps the grid alive for as long as the plan
+    int device = 0;                     // of the grid (kept here: destroying the plan must not look into a grid that may be gone)
     vrt::Tuning tune;
     int n_sweeps = 3;
     int64_t n_angles_user = 0;
@@ -311,28 +391,26 @@ struct vrt_plan {
     std::vector<int> dir_of_active;     // +1 up, -1 down
     std::vector<double> k;              // (3, A)
     // per-angle upwind tables, [A][n]
-    int32_t *d_up1 = nullptr, *d_up2 = nullptr;     // 0-based ids, kNoUpwind if none
-    double *d_d1 = nullptr, *d_d2 = nullptr;         // dot products (smallest_angle's `dots`)
-    double *d_w1 = nullptr, *d_w2 = nullptr;         // dot_weights, irregular_ray_tracing.jl:51
-    double *d_r1 = nullptr, *d_r2 = nullptr;         // euclidean path lengths, :66
+    vrt::DevBuf<int32_t> d_up1, d_up2;              // 0-based ids, kNoUpwind if none
+    vrt::DevBuf<double> d_d1, d_d2;                  // dot products (smallest_angle's `dots`)
+    vrt::DevBuf<double> d_w1, d_w2;                  // dot_weights, irregular_ray_tracing.jl:51
+    vrt::DevBuf<double> d_r1, d_r2;                  // euclidean path lengths, :66
     // level schedule, merged over the active angles
-    uint32_t *d_node_site = nullptr;    // site id (0-based)
-    uint32_t *d_node_meta = nullptr;    // active angle | zero-read flags
-    int32_t *d_node_u1 = nullptr, *d_node_u2 = nullptr;   // the node's upwind site ids (copied next to it)
+    vrt::DevBuf<uint32_t> d_node_site;  // site id (0-based)
+    vrt::DevBuf<uint32_t> d_node_meta;  // active angle | zero-read flags
+    vrt::DevBuf<int32_t> d_node_u1, d_node_u2;            // the node's upwind site ids (copied next to it)
     std::vector<int64_t> level_off;     // nodes of level t are [level_off[t], level_off[t+1])
     bool level_ready = false;           // the level schedule is built on first use
     std::vector<int32_t> h_up1, h_up2;  // host copies of the upwind ids (schedule building)
     int64_t n_nodes = 0;
     // per-direction lists of active angle indices (for the boundary kernel)
-    int32_t *d_angles_up = nullptr, *d_angles_down = nullptr;
+    vrt::DevBuf<int32_t> d_angles_up, d_angles_down;
     int n_up = 0, n_down = 0;
     std::vector<int64_t> skip_site;     // per active angle: never-updated site perm[n] (0-based)
     // workspaces (grow-only)
-    double *d_I = nullptr;
-    size_t I_cap = 0;
+    vrt::DevWork<double> d_I;
     int64_t I_ld = 0;
-    double *d_stage[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // S, alpha, I0up, I0down, J, I_out
-    size_t stage_cap[6] = {0, 0, 0, 0, 0, 0};
+    vrt::DevWork<double> d_stage[6];    // S, alpha, I0up, I0down, J, I_out
     // layer paths (vrt_layers.hip, vrt_tables.hip): tables in storage order, per-layer level counts
     bool tile_ok = false;
     bool step_tables_ready = false;      // t_self ... t_code_ss exist (ensure_step_tables)
@@ -340,34 +418,30 @@ struct vrt_plan {
     int tile_max_layers = 0;
     int64_t tile_max_layer_size = 0;
     int64_t tile_visits = 0;
-    int32_t *t_u1 = nullptr, *t_u2 = nullptr;
-    double *t_w1 = nullptr, *t_w2 = nullptr, *t_r1 = nullptr, *t_r2 = nullptr;
-    uint32_t *t_vis = nullptr, *t_loc = nullptr;
+    vrt::DevBuf<int32_t> t_u1, t_u2;
+    vrt::DevBuf<double> t_w1, t_w2, t_r1, t_r2;
+    vrt::DevBuf<uint32_t> t_vis, t_loc;
     // layer-step level kernel: sites of a layer dealt to threads sorted by visit pattern
-    int32_t *t_self = nullptr;           // [A][n] sorted index (absolute) -> storage position
-    uint32_t *t_vis_s = nullptr, *t_loc_s = nullptr;   // t_vis / t_loc in sorted order
-    uint32_t *t_gpos = nullptr;          // [A][n] compact in-layer coupling list (k_gpos)
-    int32_t *t_rank_s = nullptr;         // [A][n] storage position -> sorted index (inverse of t_self)
-    uint32_t *t_loc_ss = nullptr;        // [A][n] upwind tile slots of the sorted entries, in SORTED terms
-    uint32_t *t_code_ss = nullptr;       // [A][n] two-launch tile path: upwind slot + kind codes (layers <= 4096 sites)
-    int32_t *d_nlev = nullptr, *d_angle_dir = nullptr;
+    vrt::DevBuf<int32_t> t_self;         // [A][n] sorted index (absolute) -> storage position
+    vrt::DevBuf<uint32_t> t_vis_s, t_loc_s;            // t_vis / t_loc in sorted order
+    vrt::DevBuf<uint32_t> t_gpos;        // [A][n] compact in-layer coupling list (k_gpos)
+    vrt::DevBuf<int32_t> t_rank_s;       // [A][n] storage position -> sorted index (inverse of t_self)
+    vrt::DevBuf<uint32_t> t_loc_ss;      // [A][n] upwind tile slots of the sorted entries, in SORTED terms
+    vrt::DevBuf<uint32_t> t_code_ss;     // [A][n] two-launch tile path: upwind slot + kind codes (layers <= 4096 sites)
+    vrt::DevBuf<int32_t> d_nlev, d_angle_dir;
     std::vector<int64_t> angle_visits;   // surviving visits per active angle (task cost)
     std::vector<int32_t> h_task_map;     // block -> angle | wavelength << 8
-    int32_t *d_task_map = nullptr;
-    size_t task_map_cap = 0;
+    vrt::DevWork<int32_t> d_task_map;
     int task_map_nlam = -1;
-    double *ws_S[2] = {nullptr, nullptr}, *ws_A[2] = {nullptr, nullptr}, *ws_J[2] = {nullptr, nullptr};
-    size_t ws_S_cap[2] = {0, 0}, ws_A_cap[2] = {0, 0}, ws_J_cap[2] = {0, 0};
-    double *ws_AA = nullptr;
-    size_t ws_AA_cap = 0;
-    double *ws_cg[2] = {nullptr, nullptr};   // layer-step coefficient buffers: constant terms, compact couplings
-    size_t ws_cg_cap[2] = {0, 0};
+    vrt::DevWork<double> ws_S[2], ws_A[2], ws_J[2];
+    vrt::DevWork<double> ws_AA;
+    vrt::DevWork<double> ws_cg[2];           // layer-step coefficient buffers: constant terms, compact couplings
     // layer-step path: internal streams and the angle groups they advance through the layers
     int step_groups = 0;
-    int32_t *d_step_angles = nullptr;
+    vrt::DevBuf<int32_t> d_step_angles;
     std::vector<int> step_group_off;
     std::vector<double> angle_mean_levels;   // mean in-layer level count per active angle (level-kernel task cost)
-    int32_t *d_level_map = nullptr;      // block -> task of the layer-step level kernels, per stream group (build_level_map)
+    vrt::DevBuf<int32_t> d_level_map;    // block -> task of the layer-step level kernels, per stream group (build_level_map)
     std::vector<int> level_map_off;      //   offsets of the groups' maps (+ end); 8 ceil-blocks each
     int level_map_units = 0, level_map_groups = 0;
     std::vector<int32_t> h_step_angles;  // host copy of d_step_angles
@@ -378,22 +452,24 @@ struct vrt_plan {
     int64_t n_patches = 0, n_patch_entries = 0, n_patch_visits = 0;
     std::vector<int32_t> h_patch_first;  // [A][tile_max_layers + 2]: index of the first patch of (angle, layer)
     std::vector<int4> h_patch_rec;       // per patch: first entry, entries, first owned position, owned sites
-    int32_t *e_pos = nullptr, *e_u1 = nullptr, *e_u2 = nullptr;
-    uint32_t *e_vis = nullptr, *e_loc = nullptr;
-    double *e_w1 = nullptr, *e_w2 = nullptr, *e_r1 = nullptr, *e_r2 = nullptr;
+    vrt::DevBuf<int32_t> e_pos, e_u1, e_u2;
+    vrt::DevBuf<uint32_t> e_vis, e_loc;
+    vrt::DevBuf<double> e_w1, e_w2, e_r1, e_r2;
     std::vector<int2> h_patch_rec2;      // per patch: levels, active angle
     std::vector<int64_t> h_patch_dep_off;   // per patch: the patches (plan-wide indices) whose stored intensities it gathers
     std::vector<int32_t> h_patch_deps;      //   (vrt_patch.cpp: dep_list) -- what the chained launch waits on
     // chained launch (vrt_patch.hip: k_patch_chain): items per XCD queue, dependency lists, progress words
-    int4 *d_chain_items = nullptr;
-    int32_t *d_chain_deps = nullptr;
-    uint32_t *d_chain_progress = nullptr, *d_chain_ctrl = nullptr;
-    uint32_t *h_chain_status = nullptr, *d_chain_status = nullptr;   // mapped host word: a launch gave up
-    void *d_chain_dev = nullptr, *h_chain_dev_pinned = nullptr;       // the launch's argument block (ChainDev) and its staging copy
+    vrt::DevBuf<int4> d_chain_items;
+    vrt::DevBuf<int32_t> d_chain_deps;
+    vrt::DevWork<uint32_t> d_chain_progress;
+    vrt::DevBuf<uint32_t> d_chain_ctrl;
+    vrt::HostBuf<uint32_t> h_chain_status;                            // mapped host word: a launch gave up
+    uint32_t *d_chain_status = nullptr;                               //   its device address (borrowed from h_chain_status)
+    vrt::DevBuf<char> d_chain_dev;                                    // the launch's argument block (ChainDev)
+    vrt::HostBuf<char> h_chain_dev_pinned;                            //   and its staging copy
     std::vector<char> h_chain_dev;                                    //   what the device copy holds
-    hipEvent_t chain_dev_ev = nullptr;
+    vrt::Event chain_dev_ev;
     bool chain_dev_ev_valid = false;
-    size_t chain_progress_cap = 0;
     bool chain_progress_fresh = false;   // allocated since the last launch: zero it on the launch stream
     int chain_q_off[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     int chain_npair = -1, chain_lgB = -1, chain_nsplit = -1, chain_reduce = -1;
@@ -402,33 +478,38 @@ struct vrt_plan {
     // wavelength counts, or J and no J, switches between them instead of rebuilding (and freeing: a device synchronisation)
     struct ChainSet {
         int npair = -1, lgB = -1, nsplit = -1, reduce = -1;
-        int4 *items = nullptr;
-        int32_t *deps = nullptr;
+        vrt::DevBuf<int4> items;
+        vrt::DevBuf<int32_t> deps;
         int q_off[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         int64_t n_items = 0;
     };
     std::vector<ChainSet> chain_cache;
     uint32_t chain_epoch = 0;
-    int4 *d_patch_work = nullptr;        // work lists of the launches: two int4 per slot (ensure_patch_work, PatchArgs::wrec)
+    vrt::DevBuf<int4> d_patch_work;      // work lists of the launches: two int4 per slot (ensure_patch_work, PatchArgs::wrec)
     std::vector<int64_t> patch_work_off; //   [group][layer] offsets into it
     int patch_work_groups = 0;
-    hipStream_t step_stream[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t step_fork = nullptr, step_join[4] = {nullptr, nullptr, nullptr, nullptr};
+    vrt::Stream step_stream[4];
+    vrt::Event step_fork, step_join[4];
     int last_path = 0;                   // path of the last execute (vrt_plan_last_path): 1 levels, 2 tiles, 3 steps, 4 patches
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    vrt::Event ev0, ev1;
     bool ev_valid = false;
     std::vector<vrt::CopyLane> copy_lanes;      // host-pointer entry points (ensure_copy_lanes)
-    hipEvent_t copy_done = nullptr;
+    vrt::Event copy_done;
     int64_t last_launches = 0;
     std::mutex mu;
 };
 
 namespace vrt {
 
+struct PlanDelete { void operator()(vrt_plan *p) const { vrt_plan_destroy(p); } };   // (makes the plan's device current)
+using PlanPtr = std::unique_ptr<vrt_plan, PlanDelete>;
+struct GridDelete { void operator()(vrt_grid *g) const { vrt_grid_destroy(g); } };
+using GridPtr = std::unique_ptr<vrt_grid, GridDelete>;
+
 struct PlanCacheEntry {
     double k[3];
     int n_sweeps;
-    vrt_plan *plan;
+    PlanPtr plan;
     int users;          // single solves running on the plan right now (guarded by the grid's mutex)
 };
 
@@ -598,16 +679,16 @@ struct NgRange {
 // what a session keeps while acceleration is on (order 0: nothing allocated)
 struct NgState {
     int order = 0, start = 0, period = 0;
-    double *hist[3] = {nullptr, nullptr, nullptr};      // S after the 1, 2, 3 iterates before the next due step (x1, x2, x3)
+    DevBuf<double> hist[3];                             // S after the 1, 2, 3 iterates before the next due step (x1, x2, x3)
     unsigned have = 0;                                  // bit d-1: hist[d-1] holds its iterate
-    double *d_ws = nullptr;                             // partial sums, sums, verdict
+    DevBuf<double> d_ws;                                // partial sums, sums, verdict
     int last_applied = 0;                               // of the last iterate: 1 taken, 0 none due, -1 rejected
     double last_sums[5] = {0, 0, 0, 0, 0}, last_coeffs[2] = {0, 0};
 };
 int ng_check_settings(int order, int start, int period);
 int ng_configure(NgState &ng, int order, int start, int period, size_t alloc_count);
 void ng_release(NgState &ng);
-int ng_after_iterate(NgState &ng, int64_t iterate, double *&S, size_t alloc_count, const NgRange &rg, hipStream_t st);
+int ng_after_iterate(NgState &ng, int64_t iterate, DevBuf<double> &S, size_t alloc_count, const NgRange &rg, hipStream_t st);
 int ng_report(const NgState &ng, int *applied, double sums[5], double coeffs[2]);
 int launch_ng_mirror(vrt_grid *g, int64_t nlam, const double *dS_up, double *dS_down, hipStream_t st);
 

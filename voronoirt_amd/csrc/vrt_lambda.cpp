@@ -30,15 +30,14 @@ struct CopyJob {
 int ensure_copy_lanes(vrt_plan *p, int lanes)
 {
     if ((int)p->copy_lanes.size() >= lanes && p->copy_done) return VRT_OK;
-    if (!p->copy_done) VRT_HIP_TRY(hipEventCreateWithFlags(&p->copy_done, hipEventDisableTiming));
+    int rc;
+    if (!p->copy_done && (rc = p->copy_done.create(hipEventDisableTiming))) return rc;
     while ((int)p->copy_lanes.size() < lanes) {
         CopyLane l;
-        VRT_HIP_TRY(hipStreamCreateWithFlags(&l.st, hipStreamNonBlocking));
-        for (int b = 0; b < 2; b++) {
-            VRT_HIP_TRY(hipHostMalloc(&l.pin[b], kCopyChunk, hipHostMallocDefault));
-            VRT_HIP_TRY(hipEventCreateWithFlags(&l.ev[b], hipEventDisableTiming));
-        }
-        p->copy_lanes.push_back(l);
+        if ((rc = l.st.create())) return rc;
+        for (int b = 0; b < 2; b++)
+            if ((rc = l.pin[b].alloc(kCopyChunk)) || (rc = l.ev[b].create(hipEventDisableTiming))) return rc;
+        p->copy_lanes.push_back(std::move(l));
     }
     return VRT_OK;
 }
@@ -88,13 +87,13 @@ int run_copy_jobs(vrt_plan *p, const std::vector<CopyJob> &jobs, bool download, 
                 if (!ok(hipEventSynchronize(l.ev[slot]))) return;
                 if (download) {
                     const CopyJob &o = jobs[(size_t)pending[slot]];
-                    rows_copy(o.host_dst, o.hstride, (const char *)l.pin[slot], o.width, o.rows, o.width);
+                    rows_copy(o.host_dst, o.hstride, l.pin[slot], o.width, o.rows, o.width);
                 }
             }
             if (download) {
                 if (!ok(hipMemcpyAsync(l.pin[slot], j.dev, bytes, hipMemcpyDeviceToHost, l.st))) return;
             } else {
-                rows_copy((char *)l.pin[slot], j.width, j.host_src, j.hstride, j.rows, j.width);
+                rows_copy(l.pin[slot], j.width, j.host_src, j.hstride, j.rows, j.width);
                 if (!ok(hipMemcpyAsync(j.dev, l.pin[slot], bytes, hipMemcpyHostToDevice, l.st))) return;
             }
             if (!ok(hipEventRecord(l.ev[slot], l.st))) return;
@@ -106,7 +105,7 @@ int run_copy_jobs(vrt_plan *p, const std::vector<CopyJob> &jobs, bool download, 
             if (download) {
                 if (!ok(hipEventSynchronize(l.ev[sl]))) return;
                 const CopyJob &o = jobs[(size_t)pending[sl]];
-                rows_copy(o.host_dst, o.hstride, (const char *)l.pin[sl], o.width, o.rows, o.width);
+                rows_copy(o.host_dst, o.hstride, l.pin[sl], o.width, o.rows, o.width);
             }
         }
     };
@@ -121,18 +120,18 @@ int run_copy_jobs(vrt_plan *p, const std::vector<CopyJob> &jobs, bool download, 
     return VRT_OK;
 }
 
-int upload(double **d, const double *h, size_t count, hipStream_t st)
+int upload(DevBuf<double> &d, const double *h, size_t count, hipStream_t st)
 {
-    int rc = dev_alloc(d, count);
+    int rc = d.alloc(count);
     if (rc) return rc;
-    VRT_HIP_TRY(hipMemcpyAsync(*d, h, sizeof(double) * count, hipMemcpyHostToDevice, st));
+    VRT_HIP_TRY(hipMemcpyAsync(d, h, sizeof(double) * count, hipMemcpyHostToDevice, st));
     return VRT_OK;
 }
 
 }  // namespace
 
 struct vrt_lambda {
-    vrt_plan *p = nullptr;
+    vrt_plan *p = nullptr;              // borrowed: the caller keeps the plan alive for as long as the session
     int device = 0;                     // of the plan's grid (kept here: destroying the session must not look into a plan that may be gone)
     int64_t n = 0, nlam = 0;
     int64_t blocks[6] = {0, 0, 0, 0, 0, 0};
@@ -140,19 +139,18 @@ struct vrt_lambda {
            pref_ji = 0;
     std::vector<double> weights;
     // device state
-    double *d_small = nullptr;          // lambda | planck2 | sigma_bf1 | sigma_bf2
-    double *d_velocity = nullptr, *d_doppler = nullptr, *d_gamma_static = nullptr, *d_gamma_unsold = nullptr,
-           *d_alpha_cont = nullptr, *d_eps = nullptr, *d_temperature = nullptr, *d_atom = nullptr, *d_B0 = nullptr,
-           *d_lte = nullptr, *d_C = nullptr;
-    double *d_gamma = nullptr, *d_strength = nullptr, *d_pops = nullptr, *d_pops_new = nullptr, *d_R = nullptr;
-    double *d_S_old = nullptr, *d_S_new = nullptr, *d_J = nullptr, *d_I0 = nullptr, *d_native = nullptr;
-    unsigned long long *d_scalars = nullptr;
+    DevBuf<double> d_small;             // lambda | planck2 | sigma_bf1 | sigma_bf2
+    DevBuf<double> d_velocity, d_doppler, d_gamma_static, d_gamma_unsold, d_alpha_cont, d_eps, d_temperature, d_atom, d_B0,
+        d_lte, d_C;
+    DevBuf<double> d_gamma, d_strength, d_pops, d_pops_new, d_R;
+    DevBuf<double> d_S_old, d_S_new, d_J, d_I0, d_native;
+    DevBuf<unsigned long long> d_scalars;
     int iterations = 0;
     // S and J in sweep order between the steps of an iteration (VRT_LAMBDA_NATIVE, default): the update kernel writes S where
     // the sweep reads it, the sweep reduces J where the update and the rate integrals read it -- no layout change inside
     // the loop; d_S_new / d_S_old / d_J (the caller's layout) then exist only while vrt_lambda_get fills them
     bool native = false;
-    double *d_S_nat[2] = {nullptr, nullptr}, *d_J_nat[2] = {nullptr, nullptr}, *d_B_up = nullptr;
+    DevBuf<double> d_S_nat[2], d_J_nat[2], d_B_up;
     NgState ng;                         // vrt_lambda_set_acceleration (off: nothing allocated, nothing run)
 };
 
@@ -166,18 +164,7 @@ static size_t lambda_S_count(const vrt_lambda *s, NgRange *rg)
     return (size_t)(n * nlam);
 }
 
-static void lambda_free(vrt_lambda *s)
-{
-    if (!s) return;
-    for (double *q : {s->d_small, s->d_velocity, s->d_doppler, s->d_gamma_static, s->d_gamma_unsold, s->d_alpha_cont,
-                      s->d_eps, s->d_temperature, s->d_atom, s->d_B0, s->d_lte, s->d_C, s->d_gamma, s->d_strength,
-                      s->d_pops, s->d_pops_new, s->d_R, s->d_S_old, s->d_S_new, s->d_J, s->d_I0, s->d_native, s->d_S_nat[0],
-                      s->d_S_nat[1], s->d_J_nat[0], s->d_J_nat[1], s->d_B_up})
-        if (q) (void)hipFree(q);
-    if (s->d_scalars) (void)hipFree(s->d_scalars);
-    ng_release(s->ng);
-    delete s;
-}
+struct LambdaDelete { void operator()(vrt_lambda *s) const { vrt_lambda_destroy(s); } };
 
 extern "C" {
 
@@ -218,20 +205,20 @@ int vrt_plan_execute_line(vrt_plan *p, int64_t nlam, int64_t ld, const double *l
         hipStream_t st = g->stream;
         // staging: S | J in the plan's stage buffers; the seven per-site vectors + λ in stage 1; α_tot native in ws_AA
         const size_t vecs = 7 * n + nl;                  // velocity (3n), ΔλD, γ, strength, α_cont, λ
-        if ((rc = dev_grow(p->d_stage[0], p->stage_cap[0], nS))) return rc;
-        if ((rc = dev_grow(p->d_stage[1], p->stage_cap[1], vecs))) return rc;
-        if ((rc = dev_grow(p->d_stage[4], p->stage_cap[4], nS))) return rc;
+        if ((rc = p->d_stage[0].grow(nS))) return rc;
+        if ((rc = p->d_stage[1].grow(vecs))) return rc;
+        if ((rc = p->d_stage[4].grow(nS))) return rc;
         const size_t nnat = (size_t)vrt_plan_native_alpha_count(p, nlam);
-        if ((rc = dev_grow(p->ws_AA, p->ws_AA_cap, nnat))) return rc;
+        if ((rc = p->ws_AA.grow(nnat))) return rc;
         double *dv = p->d_stage[1];
         double *d_vel = dv, *d_dop = dv + 3 * n, *d_gam = dv + 4 * n, *d_str = dv + 5 * n, *d_ac = dv + 6 * n, *d_lam = dv + 7 * n;
         double *dU = nullptr, *dD = nullptr;
         if (I0_up && nU) {
-            if ((rc = dev_grow(p->d_stage[2], p->stage_cap[2], nU))) return rc;
+            if ((rc = p->d_stage[2].grow(nU))) return rc;
             dU = p->d_stage[2];
         }
         if (I0_down && nD) {
-            if ((rc = dev_grow(p->d_stage[3], p->stage_cap[3], nD))) return rc;
+            if ((rc = p->d_stage[3].grow(nD))) return rc;
             dD = p->d_stage[3];
         }
         // The caller's arrays are pageable: they cross PCIe through copy lanes (a host thread, a copy stream and two pinned
@@ -328,7 +315,7 @@ int vrt_lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *weight
             return fail(VRT_EINVAL, "the line session needs a layer path (at most 4 visits per site and 255 levels per layer)");
         if (p->A != (int)p->n_angles_user)
             return fail(VRT_EINVAL, "per-angle alpha needs every angle active (no θ = 90 direction)");
-        std::unique_ptr<vrt_lambda, void (*)(vrt_lambda *)> s(new vrt_lambda(), lambda_free);
+        std::unique_ptr<vrt_lambda, LambdaDelete> s(new vrt_lambda());
         s->p = p;
         s->device = g->device;
         s->n = g->n;
@@ -346,42 +333,42 @@ int vrt_lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *weight
         small.insert(small.end(), lc->sigma_bf1, lc->sigma_bf1 + nb1);
         small.insert(small.end(), lc->sigma_bf2, lc->sigma_bf2 + nb2);
 #define VRT_S(expr) do { if ((rc = (expr))) return rc; } while (0)
-        VRT_S(upload(&s->d_small, small.data(), small.size(), st));
-        VRT_S(upload(&s->d_velocity, lc->velocity, 3 * n, st));
-        VRT_S(upload(&s->d_doppler, lc->doppler_width, n, st));
-        VRT_S(upload(&s->d_gamma_static, lc->gamma_static, n, st));
-        VRT_S(upload(&s->d_gamma_unsold, lc->gamma_unsold, n, st));
-        VRT_S(upload(&s->d_alpha_cont, lc->alpha_cont, n, st));
-        VRT_S(upload(&s->d_eps, lc->eps, n, st));
-        VRT_S(upload(&s->d_temperature, lc->temperature, n, st));
-        VRT_S(upload(&s->d_atom, lc->atom_density, n, st));
-        VRT_S(upload(&s->d_B0, lc->B0, n * nl, st));
-        VRT_S(upload(&s->d_lte, lc->lte_populations, 3 * n, st));
-        VRT_S(upload(&s->d_C, lc->C, 9 * n, st));
-        VRT_S(upload(&s->d_pops, lc->lte_populations, 3 * n, st));        // populations = copy(LTE_pops), :232
+        VRT_S(upload(s->d_small, small.data(), small.size(), st));
+        VRT_S(upload(s->d_velocity, lc->velocity, 3 * n, st));
+        VRT_S(upload(s->d_doppler, lc->doppler_width, n, st));
+        VRT_S(upload(s->d_gamma_static, lc->gamma_static, n, st));
+        VRT_S(upload(s->d_gamma_unsold, lc->gamma_unsold, n, st));
+        VRT_S(upload(s->d_alpha_cont, lc->alpha_cont, n, st));
+        VRT_S(upload(s->d_eps, lc->eps, n, st));
+        VRT_S(upload(s->d_temperature, lc->temperature, n, st));
+        VRT_S(upload(s->d_atom, lc->atom_density, n, st));
+        VRT_S(upload(s->d_B0, lc->B0, n * nl, st));
+        VRT_S(upload(s->d_lte, lc->lte_populations, 3 * n, st));
+        VRT_S(upload(s->d_C, lc->C, 9 * n, st));
+        VRT_S(upload(s->d_pops, lc->lte_populations, 3 * n, st));        // populations = copy(LTE_pops), :232
         s->native = p->tune.lambda_native != 0 && native_planes_ok(p) == VRT_OK && p->tune.path != 1 && p->tune.path != 2;
         if (s->native) {
             const size_t np = (size_t)vrt_plan_native_plane_count(p, nlam);
             for (int d = 0; d < 2; d++) {
-                VRT_S(dev_alloc(&s->d_S_nat[d], np));
-                VRT_S(dev_alloc(&s->d_J_nat[d], np));
+                VRT_S(s->d_S_nat[d].alloc(np));
+                VRT_S(s->d_J_nat[d].alloc(np));
                 if (hipMemsetAsync(s->d_J_nat[d], 0, sizeof(double) * np, st) != hipSuccess) return fail(VRT_ENODEVICE, "hipMemsetAsync failed");
             }
-            VRT_S(dev_alloc(&s->d_B_up, np));
+            VRT_S(s->d_B_up.alloc(np));
             VRT_S(planes_to_native(p, nlam, nlam, s->d_B0, s->d_S_nat[0], s->d_S_nat[1], st));      // S_new = B_0, :236-239
             VRT_S(planes_to_native(p, nlam, nlam, s->d_B0, s->d_B_up, nullptr, st));
         } else {
-        VRT_S(upload(&s->d_S_new, lc->B0, n * nl, st));                   // S_new = B_0, :236-239
-        VRT_S(dev_alloc(&s->d_S_old, n * nl));
-        VRT_S(dev_alloc(&s->d_J, n * nl));
+        VRT_S(upload(s->d_S_new, lc->B0, n * nl, st));                   // S_new = B_0, :236-239
+        VRT_S(s->d_S_old.alloc(n * nl));
+        VRT_S(s->d_J.alloc(n * nl));
         }
-        VRT_S(dev_alloc(&s->d_gamma, n));
-        VRT_S(dev_alloc(&s->d_strength, n));
-        VRT_S(dev_alloc(&s->d_pops_new, 3 * n));
-        VRT_S(dev_alloc(&s->d_R, 9 * n));
-        VRT_S(dev_alloc(&s->d_I0, (size_t)g->up.n1 * nl));
-        VRT_S(dev_alloc(&s->d_native, (size_t)vrt_plan_native_alpha_count(p, nlam)));
-        VRT_S(dev_alloc(&s->d_scalars, 2));
+        VRT_S(s->d_gamma.alloc(n));
+        VRT_S(s->d_strength.alloc(n));
+        VRT_S(s->d_pops_new.alloc(3 * n));
+        VRT_S(s->d_R.alloc(9 * n));
+        VRT_S(s->d_I0.alloc((size_t)g->up.n1 * nl));
+        VRT_S(s->d_native.alloc((size_t)vrt_plan_native_alpha_count(p, nlam)));
+        VRT_S(s->d_scalars.alloc(2));
         if (!s->native &&
             (hipMemsetAsync(s->d_S_old, 0, sizeof(double) * n * nl, st) != hipSuccess ||      // S_old = zero(S_new), :240
              hipMemsetAsync(s->d_J, 0, sizeof(double) * n * nl, st) != hipSuccess))
@@ -458,7 +445,7 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
             // and the down-order copy is rewritten from it, value for value
             NgRange rg;
             const size_t count = lambda_S_count(s, &rg);
-            double *&S = s->native ? s->d_S_nat[0] : s->d_S_new;
+            DevBuf<double> &S = s->native ? s->d_S_nat[0] : s->d_S_new;
             if ((rc = ng_after_iterate(s->ng, s->iterations, S, count, rg, st))) return rc;
             if (s->ng.last_applied == 1 && s->native) {
                 if ((rc = launch_ng_mirror(g, nlam, s->d_S_nat[0], s->d_S_nat[1], st))) return rc;
@@ -529,7 +516,7 @@ void vrt_lambda_destroy(vrt_lambda *s)
 {
     DeviceScope scope;
     if (s) (void)hipSetDevice(s->device);
-    lambda_free(s);
+    delete s;
 }
 
 }  // extern "C"

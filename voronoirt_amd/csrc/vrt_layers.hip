@@ -64,7 +64,7 @@ static int build_task_map(vrt_plan *p, int nlam, hipStream_t st)
         }
         p->h_task_map[(size_t)b] = per_xcd[(size_t)x][cur[x]++];
     }
-    if (int rc = dev_grow(p->d_task_map, p->task_map_cap, (size_t)ntask)) return rc;
+    if (int rc = p->d_task_map.grow((size_t)ntask)) return rc;
     VRT_HIP_TRY(hipMemcpyAsync(p->d_task_map, p->h_task_map.data(), sizeof(int32_t) * (size_t)ntask,
                                hipMemcpyHostToDevice, st));
     p->task_map_nlam = nlam;
@@ -212,15 +212,14 @@ static int ensure_step_streams(vrt_plan *p, int G)
     }
     p->step_group_off[(size_t)G] = (int)list.size();
     int rc;
-    if (!p->d_step_angles && (rc = dev_alloc(&p->d_step_angles, (size_t)A))) return rc;
+    if (!p->d_step_angles && (rc = p->d_step_angles.alloc((size_t)A))) return rc;
     VRT_HIP_TRY(hipMemcpy(p->d_step_angles, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice));
     p->h_step_angles = list;
-    dev_free(p->d_patch_work);                        // work lists follow the groups
-    if (!p->step_fork) VRT_HIP_TRY(hipEventCreateWithFlags(&p->step_fork, hipEventDisableTiming));
+    p->d_patch_work.reset();                          // work lists follow the groups
+    if (!p->step_fork && (rc = p->step_fork.create(hipEventDisableTiming))) return rc;
     for (int gi = 0; gi < 4; gi++) {
         if (gi >= 1 && gi < G && !p->step_stream[gi]) {      // group 0 advances on the caller's stream
-            VRT_HIP_TRY(hipStreamCreateWithFlags(&p->step_stream[gi], hipStreamNonBlocking));
-            VRT_HIP_TRY(hipEventCreateWithFlags(&p->step_join[gi], hipEventDisableTiming));
+            if ((rc = p->step_stream[gi].create()) || (rc = p->step_join[gi].create(hipEventDisableTiming))) return rc;
         }
     }
     p->step_groups = G;
@@ -234,7 +233,7 @@ static int ensure_step_streams(vrt_plan *p, int G)
 static int build_level_map(vrt_plan *p, int G, int units)
 {
     if (p->d_level_map && p->level_map_groups == G && p->level_map_units == units) return VRT_OK;
-    dev_free(p->d_level_map);
+    p->d_level_map.reset();
     double mean_all = 0.0;
     for (double v : p->angle_mean_levels) mean_all += v;
     mean_all = p->angle_mean_levels.empty() ? 1.0 : std::max(1.0, mean_all / (double)p->angle_mean_levels.size());
@@ -269,7 +268,7 @@ static int build_level_map(vrt_plan *p, int G, int units)
             for (int x = 0; x < 8; x++) map.push_back(j < runs[(size_t)x].size() ? runs[(size_t)x][j] : -1);
     }
     p->level_map_off[(size_t)G] = (int)map.size();
-    if (int rc = dev_alloc(&p->d_level_map, map.size())) return rc;
+    if (int rc = p->d_level_map.alloc(map.size())) return rc;
     VRT_HIP_TRY(hipMemcpy(p->d_level_map, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice));
     p->level_map_groups = G;
     p->level_map_units = units;
@@ -367,8 +366,8 @@ static int prepare_inputs(vrt_plan *p, const ExecArgs &x, LayerRun &r)
     const T *dalpha = static_cast<const T *>(x.alpha);
     const hipStream_t st = x.st;
     int rc;
-    if ((rc = dev_grow(p->d_I, p->I_cap, dcount<T>((size_t)A * r.plane)))) return rc;
-    T *wI = reinterpret_cast<T *>(p->d_I);
+    if ((rc = p->d_I.grow(dcount<T>((size_t)A * r.plane)))) return rc;
+    T *wI = reinterpret_cast<T *>(p->d_I.get());
     // chained launch with the intensities as their own flags (vrt_patch.hip: chain_data_wait): every plane is filled with
     // the NaN pattern first; the boundary kernel below then writes the boundary layer and the never-visited site's zero
     r.chain_df = r.chain && patch_chain_dataflag(p, r.npair, kF32);
@@ -377,7 +376,7 @@ static int prepare_inputs(vrt_plan *p, const ExecArgs &x, LayerRun &r)
     if (r.chain_df && !r.prep) VRT_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p->d_I, (int)0x7FF87FF8u, (size_t)A * r.plane * sizeof(T) / 4, st));
     ChainPrep cp{};
     for (int d = 0; d < 2; d++)
-        if (r.use_dir[d] && !x.native && (rc = dev_grow(p->ws_S[d], p->ws_S_cap[d], dcount<T>(r.plane)))) return rc;
+        if (r.use_dir[d] && !x.native && (rc = p->ws_S[d].grow(dcount<T>(r.plane)))) return rc;
     TileArgs &ta = r.ta;
     ta.n = n;
     ta.nlam = (int)nlam;
@@ -430,14 +429,14 @@ static int prepare_inputs(vrt_plan *p, const ExecArgs &x, LayerRun &r)
         const hipStream_t sd = r.dir_st[d];
         const bool with_alpha = alpha_mode == VRT_ALPHA_SITE_LAM;           // S and α of the direction in ONE launch
         if (with_alpha) {
-            if ((rc = dev_grow(p->ws_A[d], p->ws_A_cap[d], dcount<T>(r.plane)))) return rc;
+            if ((rc = p->ws_A[d].grow(dcount<T>(r.plane)))) return rc;
             ta.alpha[d] = p->ws_A[d];
         }
         const T *in2 = with_alpha ? dalpha : nullptr;
-        T *out2 = with_alpha ? reinterpret_cast<T *>(p->ws_A[d]) : nullptr;
+        T *out2 = with_alpha ? reinterpret_cast<T *>(p->ws_A[d].get()) : nullptr;
         // (sweep-order S of the caller: read in place, no layout change; a caller-layout alpha still has its own)
         const T *inS = x.native ? (with_alpha ? in2 : nullptr) : static_cast<const T *>(x.S);
-        T *outS = x.native ? out2 : reinterpret_cast<T *>(p->ws_S[d]);
+        T *outS = x.native ? out2 : reinterpret_cast<T *>(p->ws_S[d].get());
         const T *inB = x.native ? nullptr : in2;
         T *outB = x.native ? nullptr : out2;
         if (r.prep) {
@@ -459,9 +458,9 @@ static int prepare_inputs(vrt_plan *p, const ExecArgs &x, LayerRun &r)
         if (alpha_mode == VRT_ALPHA_SITE_LAM_NATIVE)
             ta.alpha[d] = static_cast<const double *>(x.alpha) + (size_t)d * dcount<T>(r.plane);
         if (alpha_mode == VRT_ALPHA_SITE) {
-            if ((rc = dev_grow(p->ws_A[d], p->ws_A_cap[d], dcount<T>((size_t)n)))) return rc;
+            if ((rc = p->ws_A[d].grow(dcount<T>((size_t)n)))) return rc;
             hipLaunchKernelGGL(k_gather_vec<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sd, n,
-                               dir.d_store, dalpha, reinterpret_cast<T *>(p->ws_A[d]));
+                               dir.d_store, dalpha, reinterpret_cast<T *>(p->ws_A[d].get()));
             ta.alpha[d] = p->ws_A[d];
         }
         const int cnt = d == 0 ? p->n_up : p->n_down;
@@ -495,12 +494,12 @@ static int prepare_inputs(vrt_plan *p, const ExecArgs &x, LayerRun &r)
         ta.alpha_mode = VRT_ALPHA_ANGLE_SITE_LAM;
         ta.alpha_angle = static_cast<const double *>(x.alpha);
     } else if (alpha_mode == VRT_ALPHA_ANGLE_SITE_LAM) {
-        if ((rc = dev_grow(p->ws_AA, p->ws_AA_cap, dcount<T>((size_t)A * r.plane)))) return rc;
+        if ((rc = p->ws_AA.grow(dcount<T>((size_t)A * r.plane)))) return rc;
         for (int a = 0; a < A; a++) {
             const Direction &dir = p->dir_of_active[(size_t)a] > 0 ? g->up : g->down;
             hipLaunchKernelGGL(k_to_sweep_order<T>, r.tgrid, dim3(256), 0, r.dir_st[p->dir_of_active[(size_t)a] > 0 ? 0 : 1],
                                n, (int)nlam, ld, r.lb, dir.d_store, dalpha + (size_t)a * (size_t)n * (size_t)ld,
-                               reinterpret_cast<T *>(p->ws_AA) + (size_t)a * r.plane, (const T *)nullptr, (T *)nullptr);
+                               reinterpret_cast<T *>(p->ws_AA.get()) + (size_t)a * r.plane, (const T *)nullptr, (T *)nullptr);
         }
         ta.alpha_angle = p->ws_AA;
     }
@@ -516,8 +515,8 @@ static int run_tiles(vrt_plan *p, const ExecArgs &x, LayerRun &r)
     const hipStream_t st = x.st;
     TileArgs &ta = r.ta;
     int rc;
-    long long *d_dbg = nullptr;
-    if (kDiag && p->tune.tile_debug && dev_alloc(&d_dbg, 4 * (size_t)A * (size_t)nlam) == VRT_OK)
+    DevBuf<long long> d_dbg;
+    if (kDiag && p->tune.tile_debug && d_dbg.alloc(4 * (size_t)A * (size_t)nlam) == VRT_OK)
         ta.dbg = d_dbg;
     VRT_HIP_TRY(hipEventRecord(p->ev0, st));
     const size_t lds = 2 * (size_t)ta.tile_stride * sizeof(double);
@@ -531,7 +530,7 @@ static int run_tiles(vrt_plan *p, const ExecArgs &x, LayerRun &r)
     r.launches = 1;
     if (pre) {
         const size_t ntask = (size_t)A * (size_t)nlam;
-        if ((rc = dev_grow(p->ws_cg[0], p->ws_cg_cap[0], 3 * ntask * (size_t)n))) return rc;
+        if ((rc = p->ws_cg[0].grow(3 * ntask * (size_t)n))) return rc;
         hipLaunchKernelGGL(k_tile_coeffs, dim3((unsigned)((n + 255) / 256), (unsigned)ntask), dim3(256), 0, st,
                            ta, p->ws_cg[0]);
         const size_t lds_pre = 3 * (size_t)ta.tile_stride * sizeof(double);
@@ -559,7 +558,7 @@ static int run_tiles(vrt_plan *p, const ExecArgs &x, LayerRun &r)
         (void)hipStreamSynchronize(st);
         std::vector<long long> h(4 * (size_t)A * (size_t)nlam);
         (void)hipMemcpy(h.data(), d_dbg, sizeof(long long) * h.size(), hipMemcpyDeviceToHost);
-        (void)hipFree(d_dbg);
+        d_dbg.reset();
         double s1 = 0, s2 = 0, s3 = 0;
         for (size_t t = 0; t < (size_t)A * (size_t)nlam; t++) { s1 += h[4 * t]; s2 += h[4 * t + 1]; s3 += h[4 * t + 2]; }
         const double nt = (double)A * (double)nlam;
@@ -614,14 +613,14 @@ static int run_steps(vrt_plan *p, const ExecArgs &x, LayerRun &r)
     // kernel -> one plane of T per (angle, wavelength)
     const size_t cgn = single ? dcount<T>((size_t)p->A * (size_t)r.nl_pad * (size_t)stride)
                               : (size_t)p->A * (size_t)r.nl_pad * (size_t)stride;
-    if ((rc = dev_grow(p->ws_cg[0], p->ws_cg_cap[0], cgn))) return rc;
-    if ((rc = dev_grow(p->ws_cg[1], p->ws_cg_cap[1], 2 * cgn))) return rc;
+    if ((rc = p->ws_cg[0].grow(cgn))) return rc;
+    if ((rc = p->ws_cg[1].grow(2 * cgn))) return rc;
     StepArgs sa;
     sa.ta = r.ta;
     sa.cg_stride = stride;
     sa.npair = npair;
-    sa.cg_c = reinterpret_cast<double2 *>(p->ws_cg[0]);
-    sa.cg_g = reinterpret_cast<double2 *>(p->ws_cg[1]);
+    sa.cg_c = reinterpret_cast<double2 *>(p->ws_cg[0].get());
+    sa.cg_g = reinterpret_cast<double2 *>(p->ws_cg[1].get());
     sa.t_rank_s = p->t_rank_s;
     sa.t_loc_ss = p->t_loc_ss;
     // pairs per coefficient thread: 4 to 6, whichever leaves the last group of an angle fullest (10
@@ -715,7 +714,7 @@ static int patch_reduce_template(vrt_plan *p, const ExecArgs &x, const LayerRun 
     int rc;
     for (int a = 0; a < p->A; a++) red.w[a] = x.weights[p->user_of_active[(size_t)a]];
     for (int d = 0; d < 2; d++)
-        if (r.use_dir[d] && !x.native && (rc = dev_grow(p->ws_J[d], p->ws_J_cap[d], dcount<T>(r.plane)))) return rc;
+        if (r.use_dir[d] && !x.native && (rc = p->ws_J[d].grow(dcount<T>(r.plane)))) return rc;
     return VRT_OK;
 }
 
@@ -834,7 +833,7 @@ static int finish_outputs(vrt_plan *p, const ExecArgs &x, const LayerRun &r)
     const int64_t n = g->n, nlam = x.nlam, ld = x.ld;
     const int A = p->A;
     const hipStream_t st = x.st;
-    const T *wI = reinterpret_cast<const T *>(p->d_I);
+    const T *wI = reinterpret_cast<const T *>(p->d_I.get());
     int rc;
     if (x.wants_J()) {
         T *Jd[2] = {nullptr, nullptr};
@@ -844,7 +843,7 @@ static int finish_outputs(vrt_plan *p, const ExecArgs &x, const LayerRun &r)
                 if (x.native && x.J_nat[d]) VRT_HIP_TRY(hipMemsetAsync(x.J_nat[d], 0, r.plane * sizeof(T), st));
                 continue;
             }
-            if (!x.native && (rc = dev_grow(p->ws_J[d], p->ws_J_cap[d], dcount<T>(r.plane)))) return rc;
+            if (!x.native && (rc = p->ws_J[d].grow(dcount<T>(r.plane)))) return rc;
             DirWeights dw;
             dw.count = 0;
             for (int a = 0; a < A; a++)

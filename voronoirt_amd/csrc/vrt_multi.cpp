@@ -58,17 +58,27 @@ struct Rccl {
     }
 };
 
+// One device's share.  Its members go in reverse order of declaration -- workspaces, stream, the part plan, the
+// all-angle plan, then the grid the plans borrow -- after the destructor made the device current and gave back the
+// communicator.
 struct Member {
     int device = 0;
-    vrt_grid *grid = nullptr;
-    vrt_plan *plan_all = nullptr;          // every angle (lambda mode)
-    vrt_plan *plan_part = nullptr;         // this device's angles (angle mode), built on first use
+    GridPtr grid;
+    PlanPtr plan_all;                      // every angle (lambda mode)
+    PlanPtr plan_part;                     // this device's angles (angle mode), built on first use
     std::vector<int> my_angles;
-    hipStream_t stream = nullptr;
-    double *dS = nullptr, *dA = nullptr, *dU = nullptr, *dD = nullptr, *dJ = nullptr, *dV = nullptr;
-    size_t cS = 0, cA = 0, cU = 0, cD = 0, cJ = 0, cV = 0;
+    Stream stream;
+    DevWork<double> dS, dA, dU, dD, dJ, dV;
+    ncclComm_t comm = nullptr;             // RCCL rank of this device (NULL: the same-device rehearsal, or one device)
+    ncclResult_t (*comm_destroy)(ncclComm_t) = nullptr;
     int rc = VRT_OK;
     std::string err;
+    ~Member()
+    {
+        if (!grid && !stream) return;      // never got a device (creation failed there)
+        (void)hipSetDevice(device);
+        if (comm && comm_destroy) (void)comm_destroy(comm);
+    }
 };
 
 }  // namespace
@@ -81,29 +91,13 @@ struct vrt_multi {
     std::vector<int> dirs;
     bool distinct = true;                   // all devices different: RCCL; otherwise the same-device rehearsal
     Rccl rccl;
-    std::vector<ncclComm_t> comms;
+    bool uses_rccl() const { return !m.empty() && m[0].comm; }
     int shard = 0;                          // 0 auto, 1 lambda, 2 angle
     int last_shard = 0;
     std::mutex mu;
 };
 
-static void multi_free(vrt_multi *mm)
-{
-    if (!mm) return;
-    for (size_t d = 0; d < mm->m.size(); d++) {
-        Member &me = mm->m[d];
-        if (!me.grid && !me.stream) continue;                // never got a device (creation failed there)
-        (void)hipSetDevice(me.device);
-        if (d < mm->comms.size() && mm->comms[d] && mm->rccl.CommDestroy) (void)mm->rccl.CommDestroy(mm->comms[d]);
-        for (double *q : {me.dS, me.dA, me.dU, me.dD, me.dJ, me.dV})
-            if (q) (void)hipFree(q);
-        if (me.stream) (void)hipStreamDestroy(me.stream);
-        if (me.plan_part) vrt_plan_destroy(me.plan_part);
-        if (me.plan_all) vrt_plan_destroy(me.plan_all);
-        if (me.grid) vrt_grid_destroy(me.grid);
-    }
-    delete mm;
-}
+struct MultiDelete { void operator()(vrt_multi *mm) const { vrt_multi_destroy(mm); } };
 
 // contiguous block partition: the first n_units % world ranks get one extra unit (distributed.partition)
 static void block_of(int64_t n_units, int world, int rank, int64_t &start, int64_t &stop)
@@ -125,7 +119,7 @@ int vrt_multi_create(int n_devices, const int *devices, int64_t n, const double 
     if (n_devices < 1 || n_devices > 64) return fail(VRT_EINVAL, "need 1 <= n_devices <= 64");
     if (n_angles < 1) return fail(VRT_EINVAL, "n_angles must be >= 1");
     return guarded([&] {
-        std::unique_ptr<vrt_multi, void (*)(vrt_multi *)> mm(new vrt_multi(), multi_free);
+        std::unique_ptr<vrt_multi, MultiDelete> mm(new vrt_multi());
         mm->n = n;
         mm->n_angles = n_angles;
         mm->n_sweeps = n_sweeps;
@@ -134,7 +128,7 @@ int vrt_multi_create(int n_devices, const int *devices, int64_t n, const double 
         for (int64_t a = 0; a < n_angles; a++)
             mm->dirs[(size_t)a] = dirs ? (dirs[a] > 0 ? 1 : (dirs[a] < 0 ? -1 : 0))
                                        : (std::fabs(k[3 * a]) < 1e-12 ? 0 : (k[3 * a] < 0 ? 1 : -1));
-        mm->m.resize((size_t)n_devices);
+        mm->m = std::vector<Member>((size_t)n_devices);
         for (int d = 0; d < n_devices; d++) {
             mm->m[(size_t)d].device = devices[d];
             for (int e = 0; e < d; e++)
@@ -143,10 +137,13 @@ int vrt_multi_create(int n_devices, const int *devices, int64_t n, const double 
         // one grid + all-angle plan per device, built concurrently (plan creation is host-side schedule work)
         if (!run_workers(n_devices, [&](int d) {
                 Member &me = mm->m[(size_t)d];
-                me.rc = vrt_grid_create(n, pos_zxy, nbr, D1, bounds, me.device, &me.grid);
-                if (!me.rc) me.rc = vrt_plan_create_ex(me.grid, n_angles, k, mm->dirs.data(), n_sweeps, &me.plan_all);
-                if (!me.rc && (hipSetDevice(me.device) != hipSuccess ||
-                               hipStreamCreateWithFlags(&me.stream, hipStreamNonBlocking) != hipSuccess))
+                vrt_grid *grid = nullptr;
+                vrt_plan *plan = nullptr;
+                me.rc = vrt_grid_create(n, pos_zxy, nbr, D1, bounds, me.device, &grid);
+                me.grid.reset(grid);
+                if (!me.rc) me.rc = vrt_plan_create_ex(grid, n_angles, k, mm->dirs.data(), n_sweeps, &plan);
+                me.plan_all.reset(plan);
+                if (!me.rc && (hipSetDevice(me.device) != hipSuccess || me.stream.create()))
                     me.rc = fail(VRT_ENODEVICE, "cannot create a stream");
                 if (me.rc) me.err = vrt_last_error();
             }))
@@ -169,12 +166,12 @@ int vrt_multi_create(int n_devices, const int *devices, int64_t n, const double 
         const bool force_rccl = force && force[0] == '1';
         if (mm->distinct && (n_devices > 1 || force_rccl)) {
             if (!mm->rccl.load()) return fail(VRT_ENODEVICE, "cannot load librccl.so (needed for more than one device)");
-            mm->comms.assign((size_t)n_devices, nullptr);
-            const ncclResult_t r = mm->rccl.CommInitAll(mm->comms.data(), n_devices, devices);
-            if (r != ncclSuccess) {
-                const std::string msg = std::string("ncclCommInitAll: ") + mm->rccl.GetErrorString(r);
-                mm->comms.clear();
-                return fail(VRT_ENODEVICE, msg);
+            std::vector<ncclComm_t> comms((size_t)n_devices, nullptr);
+            const ncclResult_t r = mm->rccl.CommInitAll(comms.data(), n_devices, devices);
+            if (r != ncclSuccess) return fail(VRT_ENODEVICE, std::string("ncclCommInitAll: ") + mm->rccl.GetErrorString(r));
+            for (int d = 0; d < n_devices; d++) {
+                mm->m[(size_t)d].comm = comms[(size_t)d];
+                mm->m[(size_t)d].comm_destroy = mm->rccl.CommDestroy;
             }
         }
         *out = mm.release();
@@ -197,7 +194,7 @@ int vrt_multi_set_shard(vrt_multi *mm, const char *mode)
 }
 
 int vrt_multi_last_shard(const vrt_multi *mm) { return mm ? mm->last_shard : 0; }
-int vrt_multi_uses_rccl(const vrt_multi *mm) { return mm && !mm->comms.empty() ? 1 : 0; }
+int vrt_multi_uses_rccl(const vrt_multi *mm) { return mm && mm->uses_rccl() ? 1 : 0; }
 
 int vrt_multi_execute(vrt_multi *mm, int64_t nlam, int64_t ld, const double *S, const double *alpha, int alpha_mode,
                       const double *I0_up, const double *I0_down, const double *weights, double *J)
@@ -224,7 +221,9 @@ int vrt_multi_execute(vrt_multi *mm, int64_t nlam, int64_t ld, const double *S, 
                         kk.insert(kk.end(), mm->k.begin() + 3 * a, mm->k.begin() + 3 * a + 3);
                         dd.push_back(mm->dirs[(size_t)a]);
                     }
-                    int rc = vrt_plan_create_ex(me.grid, (int64_t)me.my_angles.size(), kk.data(), dd.data(), mm->n_sweeps, &me.plan_part);
+                    vrt_plan *part = nullptr;
+                    int rc = vrt_plan_create_ex(me.grid.get(), (int64_t)me.my_angles.size(), kk.data(), dd.data(), mm->n_sweeps, &part);
+                    me.plan_part.reset(part);
                     if (rc) return rc;
                 }
         auto work = [&](int d) {
@@ -245,16 +244,16 @@ int vrt_multi_execute(vrt_multi *mm, int64_t nlam, int64_t ld, const double *S, 
             const size_t w8 = sizeof(double);
             if (nb <= 0 || (shard == 2 && me.my_angles.empty())) {       // nothing to do here: contributes zeros in angle mode
                 if (shard == 2) {
-                    if ((me.rc = dev_grow(me.dJ, me.cJ, (size_t)n * (size_t)nlam))) { me.err = vrt_last_error(); return; }
+                    if ((me.rc = me.dJ.grow((size_t)n * (size_t)nlam))) { me.err = vrt_last_error(); return; }
                     chk(hipMemsetAsync(me.dJ, 0, w8 * (size_t)n * (size_t)nlam, st), "hipMemsetAsync");
                     chk(hipStreamSynchronize(st), "hipStreamSynchronize");      // another member's stream reads these zeros
                 }
                 return;
             }
-            vrt_plan *plan = shard == 1 ? me.plan_all : me.plan_part;
+            vrt_plan *plan = shard == 1 ? me.plan_all.get() : me.plan_part.get();
             const int64_t nA = shard == 1 ? A : (int64_t)me.my_angles.size();
             // S block (nb, n) dense on the device
-            if ((me.rc = dev_grow(me.dS, me.cS, (size_t)n * (size_t)nb)) || (me.rc = dev_grow(me.dJ, me.cJ, (size_t)n * (size_t)nb))) {
+            if ((me.rc = me.dS.grow((size_t)n * (size_t)nb)) || (me.rc = me.dJ.grow((size_t)n * (size_t)nb))) {
                 me.err = vrt_last_error();
                 return;
             }
@@ -262,13 +261,13 @@ int vrt_multi_execute(vrt_multi *mm, int64_t nlam, int64_t ld, const double *S, 
             // alpha
             const double *dA = nullptr;
             if (alpha_mode == VRT_ALPHA_SITE) {
-                if ((me.rc = dev_grow(me.dA, me.cA, (size_t)n))) { me.err = vrt_last_error(); return; }
+                if ((me.rc = me.dA.grow((size_t)n))) { me.err = vrt_last_error(); return; }
                 chk(hipMemcpyAsync(me.dA, alpha, w8 * (size_t)n, hipMemcpyHostToDevice, st), "upload alpha");
             } else if (alpha_mode == VRT_ALPHA_SITE_LAM) {
-                if ((me.rc = dev_grow(me.dA, me.cA, (size_t)n * (size_t)nb))) { me.err = vrt_last_error(); return; }
+                if ((me.rc = me.dA.grow((size_t)n * (size_t)nb))) { me.err = vrt_last_error(); return; }
                 chk(hipMemcpy2DAsync(me.dA, w8 * (size_t)nb, alpha + l0, w8 * (size_t)ld, w8 * (size_t)nb, (size_t)n, hipMemcpyHostToDevice, st), "upload alpha");
             } else {
-                if ((me.rc = dev_grow(me.dA, me.cA, (size_t)nA * (size_t)n * (size_t)nb))) { me.err = vrt_last_error(); return; }
+                if ((me.rc = me.dA.grow((size_t)nA * (size_t)n * (size_t)nb))) { me.err = vrt_last_error(); return; }
                 for (int64_t j = 0; j < nA; j++) {
                     const int64_t a = shard == 1 ? j : me.my_angles[(size_t)j];
                     chk(hipMemcpy2DAsync(me.dA + (size_t)j * (size_t)n * (size_t)nb, w8 * (size_t)nb,
@@ -279,12 +278,12 @@ int vrt_multi_execute(vrt_multi *mm, int64_t nlam, int64_t ld, const double *S, 
             dA = me.dA;
             double *dU = nullptr, *dD = nullptr;
             if (I0_up && n1u) {
-                if ((me.rc = dev_grow(me.dU, me.cU, (size_t)n1u * (size_t)nb))) { me.err = vrt_last_error(); return; }
+                if ((me.rc = me.dU.grow((size_t)n1u * (size_t)nb))) { me.err = vrt_last_error(); return; }
                 chk(hipMemcpy2DAsync(me.dU, w8 * (size_t)nb, I0_up + l0, w8 * (size_t)nlam, w8 * (size_t)nb, (size_t)n1u, hipMemcpyHostToDevice, st), "upload I0");
                 dU = me.dU;
             }
             if (I0_down && n1d) {
-                if ((me.rc = dev_grow(me.dD, me.cD, (size_t)n1d * (size_t)nb))) { me.err = vrt_last_error(); return; }
+                if ((me.rc = me.dD.grow((size_t)n1d * (size_t)nb))) { me.err = vrt_last_error(); return; }
                 chk(hipMemcpy2DAsync(me.dD, w8 * (size_t)nb, I0_down + l0, w8 * (size_t)nlam, w8 * (size_t)nb, (size_t)n1d, hipMemcpyHostToDevice, st), "upload I0");
                 dD = me.dD;
             }
@@ -308,7 +307,7 @@ int vrt_multi_execute(vrt_multi *mm, int64_t nlam, int64_t ld, const double *S, 
             // J = Σ over the devices' partial sums, wanted on ONE device only (the host array is filled from device 0):
             // one RCCL reduce to rank 0 over xGMI -- half the bytes of an all-reduce -- or, on a shared device, adds
             const size_t cnt = (size_t)n * (size_t)nlam;
-            if (!mm->comms.empty()) {
+            if (mm->uses_rccl()) {
                 // (nothing may return between GroupStart and GroupEnd: an open group poisons every later call)
                 ncclResult_t r = mm->rccl.GroupStart();
                 hipError_t he = hipSuccess;
@@ -316,7 +315,7 @@ int vrt_multi_execute(vrt_multi *mm, int64_t nlam, int64_t ld, const double *S, 
                     Member &me = mm->m[(size_t)d];
                     he = hipSetDevice(me.device);
                     if (he == hipSuccess)
-                        r = mm->rccl.Reduce(me.dJ, me.dJ, cnt, ncclDouble, ncclSum, 0, mm->comms[(size_t)d], me.stream);
+                        r = mm->rccl.Reduce(me.dJ, me.dJ, cnt, ncclDouble, ncclSum, 0, mm->m[(size_t)d].comm, me.stream);
                 }
                 const ncclResult_t r2 = mm->rccl.GroupEnd();
                 if (he != hipSuccess) return fail(VRT_ENODEVICE, std::string("hipSetDevice: ") + hipGetErrorString(he));
@@ -379,13 +378,13 @@ int vrt_multi_execute_line(vrt_multi *mm, int64_t nlam, int64_t ld, const double
             chk(hipSetDevice(me.device), "hipSetDevice");
             if (me.rc) return;
             hipStream_t st = me.stream;
-            vrt_plan *plan = me.plan_all;
+            vrt_plan *plan = me.plan_all.get();
             std::lock_guard<std::mutex> plock(plan->mu);
             const size_t w8 = sizeof(double), sn = (size_t)n;
             const size_t nnat = (size_t)vrt_plan_native_alpha_count(plan, nb);
             // S | seven per-site vectors + the block's wavelengths | native alpha | J
-            if ((me.rc = dev_grow(me.dS, me.cS, sn * (size_t)nb)) || (me.rc = dev_grow(me.dJ, me.cJ, sn * (size_t)nb)) ||
-                (me.rc = dev_grow(me.dA, me.cA, nnat)) || (me.rc = dev_grow(me.dV, me.cV, 7 * sn + (size_t)nb))) {
+            if ((me.rc = me.dS.grow(sn * (size_t)nb)) || (me.rc = me.dJ.grow(sn * (size_t)nb)) ||
+                (me.rc = me.dA.grow(nnat)) || (me.rc = me.dV.grow(7 * sn + (size_t)nb))) {
                 me.err = vrt_last_error();
                 return;
             }
@@ -400,12 +399,12 @@ int vrt_multi_execute_line(vrt_multi *mm, int64_t nlam, int64_t ld, const double
             chk(hipMemcpyAsync(d_lam, lambda + l0, w8 * (size_t)nb, hipMemcpyHostToDevice, st), "upload lambda");
             double *dU = nullptr, *dD = nullptr;
             if (I0_up && n1u) {
-                if ((me.rc = dev_grow(me.dU, me.cU, (size_t)n1u * (size_t)nb))) { me.err = vrt_last_error(); return; }
+                if ((me.rc = me.dU.grow((size_t)n1u * (size_t)nb))) { me.err = vrt_last_error(); return; }
                 chk(hipMemcpy2DAsync(me.dU, w8 * (size_t)nb, I0_up + l0, w8 * (size_t)nlam, w8 * (size_t)nb, (size_t)n1u, hipMemcpyHostToDevice, st), "upload I0");
                 dU = me.dU;
             }
             if (I0_down && n1d) {
-                if ((me.rc = dev_grow(me.dD, me.cD, (size_t)n1d * (size_t)nb))) { me.err = vrt_last_error(); return; }
+                if ((me.rc = me.dD.grow((size_t)n1d * (size_t)nb))) { me.err = vrt_last_error(); return; }
                 chk(hipMemcpy2DAsync(me.dD, w8 * (size_t)nb, I0_down + l0, w8 * (size_t)nlam, w8 * (size_t)nb, (size_t)n1d, hipMemcpyHostToDevice, st), "upload I0");
                 dD = me.dD;
             }
@@ -438,20 +437,19 @@ int vrt_multi_execute_line(vrt_multi *mm, int64_t nlam, int64_t ld, const double
 struct LambdaMember {
     int device = 0;
     int64_t l0 = 0, l1 = 0;
-    double *d_small = nullptr;          // lambda | planck2 | sigma_bf1 | sigma_bf2 of ALL wavelengths
-    double *d_velocity = nullptr, *d_doppler = nullptr, *d_gamma_static = nullptr, *d_gamma_unsold = nullptr,
-           *d_alpha_cont = nullptr, *d_eps = nullptr, *d_temperature = nullptr, *d_atom = nullptr, *d_lte = nullptr,
-           *d_C = nullptr;
-    double *d_B0 = nullptr, *d_S_old = nullptr, *d_S_new = nullptr, *d_J = nullptr, *d_I0 = nullptr, *d_native = nullptr;   // this block's columns
-    double *d_gamma = nullptr, *d_strength = nullptr, *d_pops = nullptr, *d_R = nullptr, *d_shares = nullptr;
-    unsigned long long *d_scalars = nullptr;
-    hipEvent_t ev = nullptr;
+    DevBuf<double> d_small;             // lambda | planck2 | sigma_bf1 | sigma_bf2 of ALL wavelengths
+    DevBuf<double> d_velocity, d_doppler, d_gamma_static, d_gamma_unsold, d_alpha_cont, d_eps, d_temperature, d_atom, d_lte, d_C;
+    DevBuf<double> d_B0, d_S_old, d_S_new, d_J, d_I0, d_native;   // this block's columns
+    DevBuf<double> d_gamma, d_strength, d_pops, d_R, d_shares;
+    DevBuf<unsigned long long> d_scalars;
+    Event ev;
     // the block's S and J in sweep order between the steps (as the one-device session keeps them: vrt_lambda.cpp)
-    double *d_S_nat[2] = {nullptr, nullptr}, *d_J_nat[2] = {nullptr, nullptr}, *d_B_up = nullptr;
+    DevBuf<double> d_S_nat[2], d_J_nat[2], d_B_up;
+    ~LambdaMember() { (void)hipSetDevice(device); }    // (its own copy: the vrt_multi may be gone already); then the members go
 };
 
 struct vrt_multi_lambda {
-    vrt_multi *mm = nullptr;
+    vrt_multi *mm = nullptr;            // borrowed
     int64_t n = 0, nlam = 0;
     int64_t blocks[6] = {0, 0, 0, 0, 0, 0};
     double lambda0 = 0, c0 = 0, strength_const = 0, Bij = 0, Bji = 0, sigma_bb_const = 0, hc_over_kB = 0, pref_ij = 0,
@@ -462,38 +460,22 @@ struct vrt_multi_lambda {
     bool native = false;                // every member keeps its block in sweep order (VRT_LAMBDA_NATIVE, all plans fit)
 };
 
-static void multi_lambda_free(vrt_multi_lambda *s)
-{
-    if (!s) return;
-    for (size_t d = 0; d < s->lm.size(); d++) {
-        LambdaMember &l = s->lm[d];
-        (void)hipSetDevice(l.device);                        // (its own copy: the vrt_multi may be gone already)
-        for (double *q : {l.d_small, l.d_velocity, l.d_doppler, l.d_gamma_static, l.d_gamma_unsold, l.d_alpha_cont, l.d_eps,
-                          l.d_temperature, l.d_atom, l.d_lte, l.d_C, l.d_B0, l.d_S_old, l.d_S_new, l.d_J, l.d_I0, l.d_native,
-                          l.d_gamma, l.d_strength, l.d_pops, l.d_R, l.d_shares, l.d_S_nat[0], l.d_S_nat[1], l.d_J_nat[0], l.d_J_nat[1], l.d_B_up})
-            if (q) (void)hipFree(q);
-        if (l.d_scalars) (void)hipFree(l.d_scalars);
-        if (l.ev) (void)hipEventDestroy(l.ev);
-    }
-    delete s;
-}
-
 namespace {
 
-int dupload(double **d, const double *h, size_t count, hipStream_t st)
+int dupload(DevBuf<double> &d, const double *h, size_t count, hipStream_t st)
 {
-    int rc = dev_alloc(d, count);
+    int rc = d.alloc(count);
     if (rc) return rc;
-    VRT_HIP_TRY(hipMemcpyAsync(*d, h, sizeof(double) * count, hipMemcpyHostToDevice, st));
+    VRT_HIP_TRY(hipMemcpyAsync(d, h, sizeof(double) * count, hipMemcpyHostToDevice, st));
     return VRT_OK;
 }
 // columns [l0, l1) of a host array (rows, nlam) into a dense device block (rows, l1 - l0)
-int dupload_cols(double **d, const double *h, size_t rows, int64_t nlam, int64_t l0, int64_t l1, hipStream_t st)
+int dupload_cols(DevBuf<double> &d, const double *h, size_t rows, int64_t nlam, int64_t l0, int64_t l1, hipStream_t st)
 {
     const size_t nb = (size_t)(l1 - l0);
-    int rc = dev_alloc(d, rows * nb);
+    int rc = d.alloc(rows * nb);
     if (rc || nb == 0) return rc;
-    VRT_HIP_TRY(hipMemcpy2DAsync(*d, sizeof(double) * nb, h + l0, sizeof(double) * (size_t)nlam, sizeof(double) * nb, rows, hipMemcpyHostToDevice, st));
+    VRT_HIP_TRY(hipMemcpy2DAsync(d, sizeof(double) * nb, h + l0, sizeof(double) * (size_t)nlam, sizeof(double) * nb, rows, hipMemcpyHostToDevice, st));
     return VRT_OK;
 }
 
@@ -520,13 +502,13 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
         std::lock_guard<std::mutex> lock(mm->mu);
         const int W = (int)mm->m.size();
         for (const Member &me : mm->m) {
-            const vrt_plan *p = me.plan_all;
+            const vrt_plan *p = me.plan_all.get();
             if (!p->patch_ok && (!p->tile_ok || p->tile_max_layer_size > steps_max_layer(false)))
                 return fail(VRT_EINVAL, "the line session needs a layer path (at most 4 visits per site and 255 levels per layer)");
             if (p->A != (int)p->n_angles_user)
                 return fail(VRT_EINVAL, "per-angle alpha needs every angle active (no θ = 90 direction)");
         }
-        std::unique_ptr<vrt_multi_lambda, void (*)(vrt_multi_lambda *)> s(new vrt_multi_lambda(), multi_lambda_free);
+        std::unique_ptr<vrt_multi_lambda> s(new vrt_multi_lambda());
         s->mm = mm;
         s->n = mm->n;
         s->nlam = nlam;
@@ -534,10 +516,10 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
         s->lambda0 = lc->lambda0; s->c0 = lc->c0; s->strength_const = lc->strength_const; s->Bij = lc->Bij; s->Bji = lc->Bji;
         s->sigma_bb_const = lc->sigma_bb_const; s->hc_over_kB = lc->hc_over_kB; s->pref_ij = lc->pref_ij; s->pref_ji = lc->pref_ji;
         s->weights.assign(weights, weights + mm->n_angles);
-        s->lm.resize((size_t)W);
+        s->lm = std::vector<LambdaMember>((size_t)W);
         s->native = true;
         for (const Member &me : mm->m)
-            s->native = s->native && me.plan_all->tune.lambda_native != 0 && native_planes_ok(me.plan_all) == VRT_OK &&
+            s->native = s->native && me.plan_all->tune.lambda_native != 0 && native_planes_ok(me.plan_all.get()) == VRT_OK &&
                         me.plan_all->tune.path != 1 && me.plan_all->tune.path != 2;
         const size_t n = (size_t)mm->n, nl = (size_t)nlam;
         const size_t nb1 = (size_t)(lc->blocks[3] - lc->blocks[2]), nb2 = (size_t)(lc->blocks[5] - lc->blocks[4]);
@@ -557,46 +539,46 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
             int rc = VRT_OK;
             if (hipSetDevice(me.device) != hipSuccess) { rcs[(size_t)d] = VRT_ENODEVICE; errs[(size_t)d] = "hipSetDevice"; return; }
             hipStream_t st = me.stream;
-            vrt_grid *g = me.grid;
+            vrt_grid *g = me.grid.get();
 #define VRT_S(expr) do { if (!rc) rc = (expr); } while (0)
-            VRT_S(dupload(&l.d_small, small.data(), small.size(), st));
-            VRT_S(dupload(&l.d_velocity, lc->velocity, 3 * n, st));
-            VRT_S(dupload(&l.d_doppler, lc->doppler_width, n, st));
-            VRT_S(dupload(&l.d_gamma_static, lc->gamma_static, n, st));
-            VRT_S(dupload(&l.d_gamma_unsold, lc->gamma_unsold, n, st));
-            VRT_S(dupload(&l.d_alpha_cont, lc->alpha_cont, n, st));
-            VRT_S(dupload(&l.d_eps, lc->eps, n, st));
-            VRT_S(dupload(&l.d_temperature, lc->temperature, n, st));
-            VRT_S(dupload(&l.d_atom, lc->atom_density, n, st));
-            VRT_S(dupload(&l.d_lte, lc->lte_populations, 3 * n, st));
-            VRT_S(dupload(&l.d_C, lc->C, 9 * n, st));
-            VRT_S(dupload(&l.d_pops, lc->lte_populations, 3 * n, st));               // populations = copy(LTE_pops), :232
-            VRT_S(dupload_cols(&l.d_B0, lc->B0, n, nlam, l.l0, l.l1, st));
-            VRT_S(dupload_cols(&l.d_S_new, lc->B0, n, nlam, l.l0, l.l1, st));        // S_new = B_0, :236-239
-            VRT_S(dev_alloc(&l.d_S_old, n * nb));
-            VRT_S(dev_alloc(&l.d_J, n * nb));
-            VRT_S(dev_alloc(&l.d_gamma, n));
-            VRT_S(dev_alloc(&l.d_strength, n));
-            VRT_S(dev_alloc(&l.d_R, 9 * n));
-            VRT_S(dev_alloc(&l.d_shares, 6 * n));
-            VRT_S(dev_alloc(&l.d_I0, (size_t)g->up.n1 * nb));
-            VRT_S(dev_alloc(&l.d_native, nb ? (size_t)vrt_plan_native_alpha_count(me.plan_all, (int64_t)nb) : 1));
-            VRT_S(dev_alloc(&l.d_scalars, 2));
-            if (!rc && hipEventCreateWithFlags(&l.ev, hipEventDisableTiming) != hipSuccess) rc = fail(VRT_ENODEVICE, "hipEventCreate");
+            VRT_S(dupload(l.d_small, small.data(), small.size(), st));
+            VRT_S(dupload(l.d_velocity, lc->velocity, 3 * n, st));
+            VRT_S(dupload(l.d_doppler, lc->doppler_width, n, st));
+            VRT_S(dupload(l.d_gamma_static, lc->gamma_static, n, st));
+            VRT_S(dupload(l.d_gamma_unsold, lc->gamma_unsold, n, st));
+            VRT_S(dupload(l.d_alpha_cont, lc->alpha_cont, n, st));
+            VRT_S(dupload(l.d_eps, lc->eps, n, st));
+            VRT_S(dupload(l.d_temperature, lc->temperature, n, st));
+            VRT_S(dupload(l.d_atom, lc->atom_density, n, st));
+            VRT_S(dupload(l.d_lte, lc->lte_populations, 3 * n, st));
+            VRT_S(dupload(l.d_C, lc->C, 9 * n, st));
+            VRT_S(dupload(l.d_pops, lc->lte_populations, 3 * n, st));               // populations = copy(LTE_pops), :232
+            VRT_S(dupload_cols(l.d_B0, lc->B0, n, nlam, l.l0, l.l1, st));
+            VRT_S(dupload_cols(l.d_S_new, lc->B0, n, nlam, l.l0, l.l1, st));        // S_new = B_0, :236-239
+            VRT_S(l.d_S_old.alloc(n * nb));
+            VRT_S(l.d_J.alloc(n * nb));
+            VRT_S(l.d_gamma.alloc(n));
+            VRT_S(l.d_strength.alloc(n));
+            VRT_S(l.d_R.alloc(9 * n));
+            VRT_S(l.d_shares.alloc(6 * n));
+            VRT_S(l.d_I0.alloc((size_t)g->up.n1 * nb));
+            VRT_S(l.d_native.alloc(nb ? (size_t)vrt_plan_native_alpha_count(me.plan_all.get(), (int64_t)nb) : 1));
+            VRT_S(l.d_scalars.alloc(2));
+            VRT_S(l.ev.create(hipEventDisableTiming));
             if (!rc && nb && (hipMemsetAsync(l.d_S_old, 0, sizeof(double) * n * nb, st) != hipSuccess ||
                               hipMemsetAsync(l.d_J, 0, sizeof(double) * n * nb, st) != hipSuccess))
                 rc = fail(VRT_ENODEVICE, "hipMemsetAsync failed");
             if (!rc && nb) VRT_S(launch_gather_rows(g->up.n1, (int64_t)nb, (int64_t)nb, g->up.d_order, l.d_B0, l.d_I0, st));   // I_0 = B_λ of the bottom layer, :99-101
             if (s->native && nb) {
-                const size_t np = (size_t)vrt_plan_native_plane_count(me.plan_all, (int64_t)nb);
+                const size_t np = (size_t)vrt_plan_native_plane_count(me.plan_all.get(), (int64_t)nb);
                 for (int dd = 0; dd < 2; dd++) {
-                    VRT_S(dev_alloc(&l.d_S_nat[dd], np));
-                    VRT_S(dev_alloc(&l.d_J_nat[dd], np));
+                    VRT_S(l.d_S_nat[dd].alloc(np));
+                    VRT_S(l.d_J_nat[dd].alloc(np));
                     if (!rc && hipMemsetAsync(l.d_J_nat[dd], 0, sizeof(double) * np, st) != hipSuccess) rc = fail(VRT_ENODEVICE, "hipMemsetAsync failed");
                 }
-                VRT_S(dev_alloc(&l.d_B_up, np));
-                VRT_S(planes_to_native(me.plan_all, (int64_t)nb, (int64_t)nb, l.d_B0, l.d_S_nat[0], l.d_S_nat[1], st));     // S_new = B_0
-                VRT_S(planes_to_native(me.plan_all, (int64_t)nb, (int64_t)nb, l.d_B0, l.d_B_up, nullptr, st));
+                VRT_S(l.d_B_up.alloc(np));
+                VRT_S(planes_to_native(me.plan_all.get(), (int64_t)nb, (int64_t)nb, l.d_B0, l.d_S_nat[0], l.d_S_nat[1], st));     // S_new = B_0
+                VRT_S(planes_to_native(me.plan_all.get(), (int64_t)nb, (int64_t)nb, l.d_B0, l.d_B_up, nullptr, st));
             }
 #undef VRT_S
             if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(VRT_ENODEVICE, "uploading the line case failed");
@@ -629,8 +611,8 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
             const int64_t nb = l.l1 - l.l0;
             if (hipSetDevice(me.device) != hipSuccess) { me.rc = VRT_ENODEVICE; me.err = "hipSetDevice"; return; }
             hipStream_t st = me.stream;
-            vrt_plan *p = me.plan_all;
-            vrt_grid *g = me.grid;
+            vrt_plan *p = me.plan_all.get();
+            vrt_grid *g = me.grid.get();
             std::lock_guard<std::mutex> plock(p->mu);
             int rc = VRT_OK;
             if (nb > 0 && s->native) {
@@ -658,7 +640,7 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
             const bool natJ = s->native && nb > 0;
             if (!rc) rc = launch_rates_partial(g, nlam, l.l0, l.l1, std::max<int64_t>(nb, 1), s->blocks, l.d_small, l.d_J, s->lambda0, s->c0, l.d_doppler,
                                                l.d_gamma, s->sigma_bb_const, l.d_temperature, l.d_lte, s->hc_over_kB, s->pref_ij, s->pref_ji, l.d_shares, st,
-                                               natJ ? l.d_J_nat[0] : nullptr, natJ ? l.d_J_nat[1] : nullptr);
+                                               natJ ? l.d_J_nat[0].p : nullptr, natJ ? l.d_J_nat[1].p : nullptr);
             if (rc) { me.rc = rc; me.err = vrt_last_error(); }
         };
         if (!run_workers(W, work)) return fail(VRT_ENOMEM, "out of host memory in a device worker");
@@ -666,13 +648,13 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
             if (me.rc) return fail(me.rc, "device " + std::to_string(me.device) + ": " + me.err);
         // ---- the shares summed over the devices: ONE all-reduce of 6 n doubles (in place), stream-ordered ---------------
         const size_t cnt = 6 * (size_t)n;
-        if (!mm->comms.empty()) {
+        if (mm->uses_rccl()) {
             ncclResult_t r = mm->rccl.GroupStart();
             hipError_t he = hipSuccess;
             for (int d = 0; d < W && r == ncclSuccess && he == hipSuccess; d++) {
                 he = hipSetDevice(mm->m[(size_t)d].device);
                 if (he == hipSuccess)
-                    r = mm->rccl.AllReduce(s->lm[(size_t)d].d_shares, s->lm[(size_t)d].d_shares, cnt, ncclDouble, ncclSum, mm->comms[(size_t)d], mm->m[(size_t)d].stream);
+                    r = mm->rccl.AllReduce(s->lm[(size_t)d].d_shares, s->lm[(size_t)d].d_shares, cnt, ncclDouble, ncclSum, mm->m[(size_t)d].comm, mm->m[(size_t)d].stream);
             }
             const ncclResult_t r2 = mm->rccl.GroupEnd();
             if (he != hipSuccess) return fail(VRT_ENODEVICE, std::string("hipSetDevice: ") + hipGetErrorString(he));
@@ -700,7 +682,7 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
             LambdaMember &l = s->lm[(size_t)d];
             VRT_HIP_TRY(hipSetDevice(me.device));
             (void)hipGetLastError();
-            if (int rc = launch_populations_from_shares(me.grid, l.d_shares, l.d_C, l.d_atom, l.d_R, l.d_pops, me.stream)) return rc;
+            if (int rc = launch_populations_from_shares(me.grid.get(), l.d_shares, l.d_C, l.d_atom, l.d_R, l.d_pops, me.stream)) return rc;
             VRT_HIP_TRY(hipMemcpyAsync(h.data() + 2 * d, l.d_scalars, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, me.stream));
         }
         double worst = 0.0;
@@ -708,7 +690,7 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
         for (int d = 0; d < W; d++) {
             VRT_HIP_TRY(hipSetDevice(mm->m[(size_t)d].device));
             VRT_HIP_TRY(hipStreamSynchronize(mm->m[(size_t)d].stream));
-            if (int rcc = patch_chain_check(mm->m[(size_t)d].plan_all)) return rcc;     // this iteration's sweep gave up on that device
+            if (int rcc = patch_chain_check(mm->m[(size_t)d].plan_all.get())) return rcc;     // this iteration's sweep gave up on that device
             double v;
             std::memcpy(&v, &h[(size_t)(2 * d)], sizeof(double));
             worst = std::max(worst, v);
@@ -733,7 +715,7 @@ int vrt_multi_lambda_get(vrt_multi_lambda *s, double *J, double *S, double *popu
             VRT_HIP_TRY(hipSetDevice(mm->m[d].device));
             if (s->native && nb && (J || S)) {
                 // the caller's layout is formed here, on request (d_J / d_S_old of the block serve as scratch)
-                vrt_plan *p = mm->m[d].plan_all;
+                vrt_plan *p = mm->m[d].plan_all.get();
                 hipStream_t st = mm->m[d].stream;
                 std::lock_guard<std::mutex> plock(p->mu);
                 if (J) {
@@ -762,13 +744,13 @@ int vrt_multi_lambda_get(vrt_multi_lambda *s, double *J, double *S, double *popu
 void vrt_multi_lambda_destroy(vrt_multi_lambda *s)
 {
     DeviceScope scope;
-    multi_lambda_free(s);
+    delete s;
 }
 
 void vrt_multi_destroy(vrt_multi *mm)
 {
     DeviceScope scope;
-    multi_free(mm);
+    delete mm;
 }
 
 }  // extern "C"

@@ -1396,7 +1396,7 @@ bool patch_shape_exists(int K, int Q, int NT)
 int ensure_patch_work(vrt_plan *p, int G, const std::vector<int32_t> &group_angles, const std::vector<int> &group_off)
 {
     if (p->d_patch_work && p->patch_work_groups == G) return VRT_OK;
-    if (p->d_patch_work) { (void)hipFree(p->d_patch_work); p->d_patch_work = nullptr; }
+    p->d_patch_work.reset();
     const int maxL = p->tile_max_layers;
     std::vector<int4> work;           // two per slot (PatchArgs::wrec)
     p->patch_work_off.assign((size_t)G * (size_t)(maxL + 2) + 1, 0);
@@ -1432,7 +1432,7 @@ int ensure_patch_work(vrt_plan *p, int G, const std::vector<int32_t> &group_angl
             }
         }
     p->patch_work_off.back() = (int64_t)(work.size() / 2);
-    if (int rc = dev_alloc(&p->d_patch_work, work.size())) return rc;
+    if (int rc = p->d_patch_work.alloc(work.size())) return rc;
     VRT_HIP_TRY(hipMemcpy(p->d_patch_work, work.data(), sizeof(int4) * work.size(), hipMemcpyHostToDevice));
     p->patch_work_groups = G;
     return VRT_OK;
@@ -1599,27 +1599,24 @@ static int ensure_patch_chain(vrt_plan *p, int npair, int lgB, int nsplit, bool 
             if (!p->d_chain_items) return;
             vrt_plan::ChainSet cs;
             cs.npair = p->chain_npair; cs.lgB = p->chain_lgB; cs.nsplit = p->chain_nsplit; cs.reduce = p->chain_reduce;
-            cs.items = p->d_chain_items; cs.deps = p->d_chain_deps; cs.n_items = p->chain_items;
+            cs.items = std::move(p->d_chain_items); cs.deps = std::move(p->d_chain_deps); cs.n_items = p->chain_items;
             for (int x = 0; x <= 8; x++) cs.q_off[x] = p->chain_q_off[x];
-            p->d_chain_items = nullptr; p->d_chain_deps = nullptr;
             p->chain_npair = -1;
-            p->chain_cache.push_back(cs);
-            if (p->chain_cache.size() > 3) {                  // (the oldest goes: hipFree waits for the device)
-                (void)hipFree(p->chain_cache.front().items);
-                (void)hipFree(p->chain_cache.front().deps);
+            p->chain_cache.push_back(std::move(cs));
+            if (p->chain_cache.size() > 3)                    // (the oldest goes: freeing it waits for the device)
                 p->chain_cache.erase(p->chain_cache.begin());
-            }
         };
         for (size_t c = 0; c < p->chain_cache.size(); c++) {
-            const vrt_plan::ChainSet cs = p->chain_cache[c];
-            if (cs.npair == npair && cs.lgB == lgB && cs.nsplit == nsplit && cs.reduce == (with_reduce ? 1 : 0)) {
+            if (p->chain_cache[c].npair == npair && p->chain_cache[c].lgB == lgB && p->chain_cache[c].nsplit == nsplit &&
+                p->chain_cache[c].reduce == (with_reduce ? 1 : 0)) {
+                vrt_plan::ChainSet cs = std::move(p->chain_cache[c]);
                 p->chain_cache.erase(p->chain_cache.begin() + (long)c);
                 stash();
-                p->d_chain_items = cs.items; p->d_chain_deps = cs.deps; p->chain_items = cs.n_items;
+                p->d_chain_items = std::move(cs.items); p->d_chain_deps = std::move(cs.deps); p->chain_items = cs.n_items;
                 for (int x = 0; x <= 8; x++) p->chain_q_off[x] = cs.q_off[x];
                 p->chain_npair = npair; p->chain_lgB = lgB; p->chain_nsplit = nsplit; p->chain_reduce = with_reduce ? 1 : 0;
                 const size_t words = (size_t)nsplit * (size_t)std::max<int64_t>(p->n_patches, 1);
-                if (words <= p->chain_progress_cap) return VRT_OK;
+                if (words <= p->d_chain_progress.cap) return VRT_OK;
                 break;                                       // (cannot happen: the progress words only grow; rebuild below)
             }
         }
@@ -1739,24 +1736,22 @@ static int ensure_patch_chain(vrt_plan *p, int npair, int lgB, int nsplit, bool 
     if (all.size() / 3 >= (size_t)INT32_MAX) return fail(VRT_EINVAL, "too many items for the chained launch");
     std::vector<int32_t> deps(p->h_patch_deps);
     deps.insert(deps.end(), rdeps.begin(), rdeps.end());
-    dev_free(p->d_chain_items);                          // (stashed above: NULL here)
-    dev_free(p->d_chain_deps);
-    int rc;
-    if ((rc = dev_alloc(&p->d_chain_items, all.size())) || (rc = dev_alloc(&p->d_chain_deps, deps.size()))) return rc;
+    int rc;                                              // (the set in use was stashed above: nothing to free here)
+    if ((rc = p->d_chain_items.alloc(all.size())) || (rc = p->d_chain_deps.alloc(deps.size()))) return rc;
     VRT_HIP_TRY(hipMemcpy(p->d_chain_items, all.data(), sizeof(int4) * all.size(), hipMemcpyHostToDevice));
     VRT_HIP_TRY(hipMemcpy(p->d_chain_deps, deps.data(), sizeof(int32_t) * deps.size(), hipMemcpyHostToDevice));
     const size_t words = (size_t)nsplit * (size_t)std::max<int64_t>(n_patches, 1);
-    if (words > p->chain_progress_cap) {
-        if ((rc = dev_grow(p->d_chain_progress, p->chain_progress_cap, words))) return rc;
+    if (words > p->d_chain_progress.cap) {
+        if ((rc = p->d_chain_progress.grow(words))) return rc;
         p->chain_progress_fresh = true;
     }
     // (epochs keep counting across item sets: a word of an earlier set compares as "behind" whatever it meant there;
     // freshly allocated words are zeroed on the launch stream, ahead of the first launch that polls them)
-    if (!p->d_chain_ctrl && (rc = dev_alloc(&p->d_chain_ctrl, kChainAbortWord + 4))) return rc;
+    if (!p->d_chain_ctrl && (rc = p->d_chain_ctrl.alloc(kChainAbortWord + 4))) return rc;
     if (!p->h_chain_status) {
-        VRT_HIP_TRY(hipHostMalloc((void **)&p->h_chain_status, 64, hipHostMallocMapped));
+        if ((rc = p->h_chain_status.alloc(16, hipHostMallocMapped))) return rc;
         *p->h_chain_status = 0;
-        VRT_HIP_TRY(hipHostGetDevicePointer((void **)&p->d_chain_status, p->h_chain_status, 0));
+        VRT_HIP_TRY(hipHostGetDevicePointer((void **)&p->d_chain_status, p->h_chain_status.p, 0));
     }
     p->chain_npair = npair;
     p->chain_lgB = lgB;
@@ -1829,18 +1824,14 @@ int launch_patch_chain(vrt_plan *p, const TileArgs &ta, int npair, hipStream_t s
     }
     h.dbg = kDiag ? p->tune.debug_flags : 0;
     // the argument block travels only when it has changed (stream-ordered: behind the launches that read the old one)
-    if (!p->d_chain_dev) {
-        ChainDev *cd = nullptr;
-        if ((rc = dev_alloc(&cd, 1))) return rc;
-        p->d_chain_dev = cd;
-    }
+    if (!p->d_chain_dev && (rc = p->d_chain_dev.alloc(sizeof(ChainDev)))) return rc;
     if (p->h_chain_dev.size() != sizeof(ChainDev) || std::memcmp(p->h_chain_dev.data(), &h, sizeof(h)) != 0) {
-        if (!p->h_chain_dev_pinned) VRT_HIP_TRY(hipHostMalloc((void **)&p->h_chain_dev_pinned, sizeof(ChainDev), hipHostMallocDefault));
+        if (!p->h_chain_dev_pinned && (rc = p->h_chain_dev_pinned.alloc(sizeof(ChainDev)))) return rc;
         // the pinned staging copy may still be in flight for an earlier launch: wait for that copy only
         if (p->chain_dev_ev_valid) VRT_HIP_TRY(hipEventSynchronize(p->chain_dev_ev));
         std::memcpy(p->h_chain_dev_pinned, &h, sizeof(h));
         VRT_HIP_TRY(hipMemcpyAsync(p->d_chain_dev, p->h_chain_dev_pinned, sizeof(h), hipMemcpyHostToDevice, st));
-        if (!p->chain_dev_ev) VRT_HIP_TRY(hipEventCreateWithFlags(&p->chain_dev_ev, hipEventDisableTiming));
+        if (!p->chain_dev_ev && (rc = p->chain_dev_ev.create(hipEventDisableTiming))) return rc;
         VRT_HIP_TRY(hipEventRecord(p->chain_dev_ev, st));
         p->chain_dev_ev_valid = true;
         p->h_chain_dev.assign(reinterpret_cast<const char *>(&h), reinterpret_cast<const char *>(&h) + sizeof(h));
@@ -1849,7 +1840,7 @@ int launch_patch_chain(vrt_plan *p, const TileArgs &ta, int npair, hipStream_t s
     p->chain_epoch++;
     if ((p->chain_epoch & 0x3FFFFFu) == 0u || p->chain_progress_fresh) {
         // stream-ordered (the plan's streams do not synchronise with the null stream)
-        VRT_HIP_TRY(hipMemsetAsync(p->d_chain_progress, 0, sizeof(uint32_t) * p->chain_progress_cap, st));
+        VRT_HIP_TRY(hipMemsetAsync(p->d_chain_progress, 0, sizeof(uint32_t) * p->d_chain_progress.cap, st));
         if ((p->chain_epoch & 0x3FFFFFu) == 0u) p->chain_epoch = 1;
         p->chain_progress_fresh = false;
     }
@@ -1857,7 +1848,7 @@ int launch_patch_chain(vrt_plan *p, const TileArgs &ta, int npair, hipStream_t s
     if (!ctrl_zeroed) VRT_HIP_TRY(hipMemsetAsync(p->d_chain_ctrl, 0, sizeof(uint32_t) * (kChainAbortWord + 4), st));
     const size_t lds = (size_t)(quad ? 2 : 1) * (size_t)(p->patch_cap + 1) * sizeof(double2) + (size_t)p->patch_cap * (4 * sizeof(double) + 5 * sizeof(int32_t)) +
                        sizeof(uint32_t) * (kCtlWords + 64 + kChainDepLds);
-    const ChainDev *cd = reinterpret_cast<const ChainDev *>(p->d_chain_dev);
+    const ChainDev *cd = reinterpret_cast<const ChainDev *>(p->d_chain_dev.p);
     switch (ta.alpha_mode) {
     case VRT_ALPHA_SITE:
         rc = f32 ? launch_chain_mode<float, VRT_ALPHA_SITE>(quad, dataflag, p->chain_items, lds, st, h, cd, base)

@@ -554,45 +554,26 @@ struct RasterLocator {
     int64_t requested = -1;                  // g->nearest_cells it was built for
     int nc[3] = {1, 1, 1};
     double lo[3] = {0, 0, 0}, h[3] = {1, 1, 1};
-    int32_t *d_cell_start = nullptr, *d_cell_sites = nullptr, *d_seed = nullptr;
-    int32_t *d_adj_ptr = nullptr, *d_adj = nullptr;      // symmetric closure of the neighbour rows, 0-based
-    unsigned long long *d_stats = nullptr;
-    char *d_work = nullptr;                  // idx1, idx2, d1, d2 of the raster points / queries (grow-only)
-    size_t work_cap = 0;
-    double *d_axes = nullptr;
-    size_t axes_cap = 0;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    DevBuf<int32_t> d_cell_start, d_cell_sites, d_seed;
+    DevBuf<int32_t> d_adj_ptr, d_adj;        // symmetric closure of the neighbour rows, 0-based
+    DevBuf<unsigned long long> d_stats;
+    DevWork<char> d_work;                    // idx1, idx2, d1, d2 of the raster points / queries (grow-only)
+    DevWork<double> d_axes;
+    Event ev[3];
     double last_ms[2] = {0, 0};
     unsigned long long last_stats[3] = {0, 0, 0};
     int64_t last_nq = 0;
 };
 
-void raster_locator_free(vrt_grid *g)
-{
-    RasterLocator *L = g ? g->locator : nullptr;
-    if (!L) return;
-    dev_free(L->d_cell_start);
-    dev_free(L->d_cell_sites);
-    dev_free(L->d_seed);
-    dev_free(L->d_adj_ptr);
-    dev_free(L->d_adj);
-    dev_free(L->d_stats);
-    dev_free(L->d_work);
-    dev_free(L->d_axes);
-    for (hipEvent_t &e : L->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete L;
-    g->locator = nullptr;
-}
+void raster_locator_delete(RasterLocator *L) { delete L; }
 
 namespace {
 
 int build_locator(vrt_grid *g)
 {
     if (g->locator && g->locator->requested == g->nearest_cells) return VRT_OK;
-    raster_locator_free(g);
-    RasterLocator *L = new RasterLocator();
-    g->locator = L;
+    g->locator.reset();
+    std::unique_ptr<RasterLocator, RasterLocatorDelete> L(new RasterLocator());     // (the grid gets it when it is complete)
     L->requested = g->nearest_cells;
     const int64_t n = g->n;
     // the cells cover the box and every site (a site is inside its cell, which the ring search's bound relies on)
@@ -676,18 +657,20 @@ int build_locator(vrt_grid *g)
         adj.resize((size_t)w);
     }
     int rc;
-    if ((rc = dev_alloc(&L->d_adj_ptr, (size_t)n + 1))) return rc;
-    if ((rc = dev_alloc(&L->d_adj, adj.size()))) return rc;
+    if ((rc = L->d_adj_ptr.alloc((size_t)n + 1))) return rc;
+    if ((rc = L->d_adj.alloc(adj.size()))) return rc;
     VRT_HIP_TRY(hipMemcpy(L->d_adj_ptr, adj_ptr.data(), sizeof(int32_t) * adj_ptr.size(), hipMemcpyHostToDevice));
     if (!adj.empty()) VRT_HIP_TRY(hipMemcpy(L->d_adj, adj.data(), sizeof(int32_t) * adj.size(), hipMemcpyHostToDevice));
-    if ((rc = dev_alloc(&L->d_cell_start, (size_t)ncell + 1))) return rc;
-    if ((rc = dev_alloc(&L->d_cell_sites, (size_t)n))) return rc;
-    if ((rc = dev_alloc(&L->d_seed, (size_t)ncell))) return rc;
-    if ((rc = dev_alloc(&L->d_stats, 3))) return rc;
+    if ((rc = L->d_cell_start.alloc((size_t)ncell + 1))) return rc;
+    if ((rc = L->d_cell_sites.alloc((size_t)n))) return rc;
+    if ((rc = L->d_seed.alloc((size_t)ncell))) return rc;
+    if ((rc = L->d_stats.alloc(3))) return rc;
     VRT_HIP_TRY(hipMemcpy(L->d_cell_start, start.data(), sizeof(int32_t) * start.size(), hipMemcpyHostToDevice));
     VRT_HIP_TRY(hipMemcpy(L->d_cell_sites, sites.data(), sizeof(int32_t) * sites.size(), hipMemcpyHostToDevice));
     VRT_HIP_TRY(hipMemcpy(L->d_seed, seed.data(), sizeof(int32_t) * seed.size(), hipMemcpyHostToDevice));
-    for (hipEvent_t &e : L->ev) VRT_HIP_TRY(hipEventCreate(&e));
+    for (Event &e : L->ev)
+        if ((rc = e.create())) return rc;
+    g->locator = std::move(L);
     return VRT_OK;
 }
 
@@ -726,7 +709,7 @@ int check_metric(const vrt_grid *g, int metric)
 
 NearArgs near_args(vrt_grid *g, int metric, int k)
 {
-    const RasterLocator *L = g->locator;
+    const RasterLocator *L = g->locator.get();
     NearArgs a{};
     a.pos = g->d_pos; a.adj_ptr = L->d_adj_ptr; a.adj = L->d_adj;
     a.cell_start = L->d_cell_start; a.cell_sites = L->d_cell_sites; a.seed = L->d_seed;
@@ -779,11 +762,11 @@ int to_raster_impl(vrt_grid *g, int64_t nz, int64_t nx, int64_t ny, const double
 {
     int rc = build_locator(g);
     if (rc) return rc;
-    RasterLocator *L = g->locator;
+    RasterLocator *L = g->locator.get();
     const int64_t P = nz * nx * ny;
     const int k = mode == VRT_RASTER_INV_DIST2 ? 2 : 1;
-    if ((rc = dev_grow(L->d_work, L->work_cap, (size_t)P * (k == 2 ? 24 : 4)))) return rc;
-    if ((rc = dev_grow(L->d_axes, L->axes_cap, (size_t)(nz + nx + ny)))) return rc;
+    if ((rc = L->d_work.grow((size_t)P * (k == 2 ? 24 : 4)))) return rc;
+    if ((rc = L->d_axes.grow((size_t)(nz + nx + ny)))) return rc;
     VRT_HIP_TRY(hipMemcpyAsync(L->d_axes, z, sizeof(double) * nz, hipMemcpyHostToDevice, st));
     VRT_HIP_TRY(hipMemcpyAsync(L->d_axes + nz, x, sizeof(double) * nx, hipMemcpyHostToDevice, st));
     VRT_HIP_TRY(hipMemcpyAsync(L->d_axes + nz + nx, y, sizeof(double) * ny, hipMemcpyHostToDevice, st));
@@ -846,9 +829,9 @@ int to_grid_impl(vrt_grid *g, int64_t nz, int64_t nx, int64_t ny, const double *
 {
     int rc = build_locator(g);      // (holds the axes' workspace)
     if (rc) return rc;
-    RasterLocator *L = g->locator;
+    RasterLocator *L = g->locator.get();
     const int64_t na = nz + nx + ny;
-    rc = dev_grow(L->d_axes, L->axes_cap, (size_t)na);
+    rc = L->d_axes.grow((size_t)na);
     if (rc) return rc;
     VRT_HIP_TRY(hipMemcpyAsync(L->d_axes, z, sizeof(double) * nz, hipMemcpyHostToDevice, st));
     VRT_HIP_TRY(hipMemcpyAsync(L->d_axes + nz, x, sizeof(double) * nx, hipMemcpyHostToDevice, st));
@@ -989,10 +972,10 @@ extern "C" int vrt_grid_nearest(vrt_grid *g, int64_t nq, const double *q_zxy, in
         if (nq == 0) return VRT_OK;
         std::lock_guard<std::mutex> lock(g->mu);
         if ((rc = build_locator(g))) return rc;
-        RasterLocator *L = g->locator;
+        RasterLocator *L = g->locator.get();
         // workspace: queries (3 nq doubles), d1, d2, idx1, idx2
-        if ((rc = dev_grow(L->d_work, L->work_cap, (size_t)nq * (24 + 16 + 8)))) return rc;
-        double *dq = (double *)L->d_work;
+        if ((rc = L->d_work.grow((size_t)nq * (24 + 16 + 8)))) return rc;
+        double *dq = (double *)L->d_work.get();
         NearArgs a = near_args(g, metric, k);
         a.nq = nq;
         a.q = dq;
@@ -1095,7 +1078,7 @@ extern "C" int vrt_grid_raster_stats(const vrt_grid *g, double *nearest_ms, doub
                                      int64_t *walk_steps, int64_t *fallbacks)
 {
     if (!g) return fail(VRT_EINVAL, "NULL grid");
-    const RasterLocator *L = g->locator;
+    const RasterLocator *L = g->locator.get();
     if (nearest_ms) *nearest_ms = L ? L->last_ms[0] : 0.0;
     if (gather_ms) *gather_ms = L ? L->last_ms[1] : 0.0;
     if (queries) *queries = L ? L->last_nq : 0;

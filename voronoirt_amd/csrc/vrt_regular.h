@@ -10,19 +10,18 @@
 struct vrt_regular {
     int device = 0;
     int64_t nz = 0, nx = 0, ny = 0;
-    double *d_g = nullptr;                 // z | x | y
+    vrt::DevBuf<double> d_g;               // z | x | y
     std::vector<double> h_g;               // the same on the host (launch geometry)
-    double *d_S = nullptr, *d_A = nullptr, *d_I = nullptr, *d_k = nullptr, *d_coef = nullptr, *d_xy = nullptr;
-    int *d_up = nullptr;
-    size_t cap_S = 0, cap_A = 0, cap_I = 0, cap_coef = 0, cap_xy = 0;     // in doubles
-    int64_t cap_k = 0;                     // in solves
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    vrt::DevWork<double> d_S, d_A, d_I, d_coef, d_xy;                      // capacities in doubles
+    vrt::DevBuf<double> d_k;
+    vrt::DevBuf<int> d_up;
+    int64_t cap_k = 0;                     // of d_k and d_up, in solves
+    vrt::Event ev[3];
     bool timed = false;
     int force_threads = 0;                 // VRT_REG_THREADS, read once at creation (tests: forces the launch shape)
     int xy_split = 1;                      // VRT_REG_XY (creation): 0 = all-xy batches through k_regular_solve too;
                                            //   2 = split, upwind plane read from memory instead of LDS (tests)
-    double *d_I0 = nullptr;                // vrt_regular_emergent_dev: the bottom planes of S of one chunk
-    size_t cap_I0 = 0;
+    vrt::DevWork<double> d_I0;             // vrt_regular_emergent_dev: the bottom planes of S of one chunk
     int64_t emergent_bytes = (int64_t)8 << 30;  // VRT_REG_EMERGENT_BYTES (creation): workspace cap of an emergent chunk
     int64_t lambda_bytes = (int64_t)64 << 30;   // VRT_REG_LAMBDA_BYTES (creation): workspace cap of a line-J chunk
                                                 //   (smaller chunks run fewer solves at once: DESIGN §7f)

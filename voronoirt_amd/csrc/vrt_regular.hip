@@ -781,18 +781,8 @@ k_reg_top_interior(int nz, int nx, int ny, int64_t n_solve, const double *__rest
 
 using namespace vrt;
 
-static void regular_free(vrt_regular *r)
-{
-    if (!r) return;
-    for (void *p : {(void *)r->d_g, (void *)r->d_S, (void *)r->d_A, (void *)r->d_I, (void *)r->d_k, (void *)r->d_up,
-                    (void *)r->d_coef, (void *)r->d_xy, (void *)r->d_I0})
-        if (p) (void)hipFree(p);
-    for (hipEvent_t e : r->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete r;
-}
-
-using RegularPtr = std::unique_ptr<vrt_regular, void (*)(vrt_regular *)>;
+struct RegularDelete { void operator()(vrt_regular *r) const { vrt_regular_destroy(r); } };
+using RegularPtr = std::unique_ptr<vrt_regular, RegularDelete>;
 
 extern "C" int vrt_regular_create(int64_t nz, int64_t nx, int64_t ny, const double *z, const double *x,
                                   const double *y, int device, vrt_regular **out)
@@ -804,7 +794,7 @@ extern "C" int vrt_regular_create(int64_t nz, int64_t nx, int64_t ny, const doub
         int rc = use_current_device();
         if (!rc) rc = device < 0 ? fail(VRT_EINVAL, "device ordinal out of range") : use_device(device);
         if (rc) return rc;
-        RegularPtr r(new vrt_regular, regular_free);
+        RegularPtr r(new vrt_regular);
         if (const char *e = std::getenv("VRT_REG_THREADS")) r->force_threads = std::max(64, std::min(1024, std::atoi(e) / 64 * 64));
         if (const char *e = std::getenv("VRT_REG_XY")) r->xy_split = std::max(0, std::min(2, std::atoi(e)));
         if (const char *e = std::getenv("VRT_REG_EMERGENT_BYTES")) r->emergent_bytes = std::max<int64_t>(1, std::atoll(e));
@@ -814,16 +804,22 @@ extern "C" int vrt_regular_create(int64_t nz, int64_t nx, int64_t ny, const doub
         r->h_g.assign(z, z + nz);
         r->h_g.insert(r->h_g.end(), x, x + nx);
         r->h_g.insert(r->h_g.end(), y, y + ny);
-        if ((rc = dev_alloc(&r->d_g, (size_t)(nz + nx + ny)))) return rc;
+        if ((rc = r->d_g.alloc((size_t)(nz + nx + ny)))) return rc;
         hipError_t e = hipMemcpy(r->d_g, r->h_g.data(), sizeof(double) * r->h_g.size(), hipMemcpyHostToDevice);
-        for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipEventCreate(&r->ev[i]);
         if (e != hipSuccess) return fail(VRT_ENODEVICE, std::string("vrt_regular_create: ") + hipGetErrorString(e));
+        for (Event &ev : r->ev)
+            if ((rc = ev.create())) return rc;
         *out = r.release();
         return VRT_OK;
     });
 }
 
-extern "C" void vrt_regular_destroy(vrt_regular *r) { regular_free(r); }
+extern "C" void vrt_regular_destroy(vrt_regular *r)
+{
+    DeviceScope scope;
+    if (r) (void)hipSetDevice(r->device);
+    delete r;
+}
 
 int vrt::regular_check_k(int64_t n_solve, const double *k)
 {
@@ -850,15 +846,13 @@ static int regular_solve(vrt_regular *r, int64_t n_solve, const double *k, const
     const int64_t nfield = field_period > 0 ? field_period : n_solve;
     const int64_t nS = S_stride ? nfield : 1, nA = alpha_stride ? nfield : 1;
     int rc;
-    if ((rc = dev_grow(r->d_S, r->cap_S, (size_t)(nS * vol))) || (rc = dev_grow(r->d_A, r->cap_A, (size_t)(nA * vol))) ||
-        (rc = dev_grow(r->d_I, r->cap_I, (size_t)(n_solve * vol))) ||
-        (rc = dev_grow(r->d_coef, r->cap_coef, (size_t)(n_solve * 5 * nx * ny))))
+    if ((rc = r->d_S.grow((size_t)(nS * vol))) || (rc = r->d_A.grow((size_t)(nA * vol))) ||
+        (rc = r->d_I.grow((size_t)(n_solve * vol))) ||
+        (rc = r->d_coef.grow((size_t)(n_solve * 5 * nx * ny))))
         return rc;
     if (n_solve > r->cap_k) {
-        dev_free(r->d_k);
-        dev_free(r->d_up);
         r->cap_k = 0;
-        if ((rc = dev_alloc(&r->d_k, 3 * (size_t)n_solve)) || (rc = dev_alloc(&r->d_up, (size_t)n_solve))) return rc;
+        if ((rc = r->d_k.alloc(3 * (size_t)n_solve)) || (rc = r->d_up.alloc((size_t)n_solve))) return rc;
         r->cap_k = n_solve;
     }
     VRT_HIP_TRY(hipMemcpyAsync(r->d_k, k, sizeof(double) * 3 * (size_t)n_solve, hipMemcpyHostToDevice, st));
@@ -917,7 +911,7 @@ static int regular_launch(vrt_regular *r, RegArgs &ra, int64_t n_solve, const do
     if (all_xy && r->xy_split && 24 * vol < ((int64_t)1 << 31) && nz <= 65536) {   // (a solve's coefficients: 32-bit byte offsets; planes = grid.y)
         // coefficients: 3 doubles per point, plane and solve, in chunks of solves of at most 2 GiB
         const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({n_solve, 65535, ((int64_t)1 << 31) / (24 * vol)}));
-        if ((rc = dev_grow(r->d_xy, r->cap_xy, (size_t)(chunk * 3 * vol)))) return rc;
+        if ((rc = r->d_xy.grow((size_t)(chunk * 3 * vol)))) return rc;
         // LDS of the march: two planes, the axes and the weight tables (layout: k_reg_xy_march_lds); the planes
         // padded to an even number of doubles so that the 16-byte tables behind them stay aligned
         const size_t planes_d = 2 * (size_t)(nx * ny), lead_d = planes_d + (size_t)(nx + ny);
@@ -953,11 +947,10 @@ static int regular_launch(vrt_regular *r, RegArgs &ra, int64_t n_solve, const do
 
 void vrt::regular_release_workspace(vrt_regular *r)
 {
-    dev_free(r->d_A);
-    dev_free(r->d_I);
-    dev_free(r->d_coef);
-    dev_free(r->d_xy);
-    r->cap_A = r->cap_I = r->cap_coef = r->cap_xy = 0;
+    r->d_A.reset();
+    r->d_I.reset();
+    r->d_coef.reset();
+    r->d_xy.reset();
 }
 
 int vrt::regular_solve_planes(vrt_regular *r, int64_t n_solve, const double *hk, const double *dk, const int *dup,
@@ -967,8 +960,8 @@ int vrt::regular_solve_planes(vrt_regular *r, int64_t n_solve, const double *hk,
     const int64_t nz = r->nz, nx = r->nx, ny = r->ny, vol = nz * nx * ny;
     VRT_HIP_TRY(hipSetDevice(r->device));
     int rc;
-    if ((rc = dev_grow(r->d_I, r->cap_I, (size_t)(n_solve * vol))) ||
-        (rc = dev_grow(r->d_coef, r->cap_coef, (size_t)(n_solve * 5 * nx * ny))))
+    if ((rc = r->d_I.grow((size_t)(n_solve * vol))) ||
+        (rc = r->d_coef.grow((size_t)(n_solve * 5 * nx * ny))))
         return rc;
     VRT_HIP_TRY(hipEventRecord(r->ev[0], st));
     RegArgs ra;
@@ -1032,7 +1025,7 @@ extern "C" int vrt_regular_emergent_dev(vrt_regular *r, const double *k, int64_t
             for (int j = 0; j < 3; j++) kk[3 * (size_t)s + (size_t)j] = k[j];
         const std::vector<int> up((size_t)chunk, 1);
         VRT_HIP_TRY(hipSetDevice(r->device));
-        if ((rc = dev_grow(r->d_I0, r->cap_I0, (size_t)(chunk * plane)))) return rc;
+        if ((rc = r->d_I0.grow((size_t)(chunk * plane)))) return rc;
         hipStream_t st = (hipStream_t)stream;
         const int64_t inner = (nx - 2) * (ny - 2);
         for (int64_t l0 = 0; l0 < nlam; l0 += chunk) {
@@ -1064,7 +1057,7 @@ extern "C" int vrt_top_intensity(int64_t nz, int64_t nx, int64_t ny, const doubl
         const size_t vol = (size_t)(nz * nx * ny) * (size_t)nlam, top = (size_t)((nx - 2) * (ny - 2)) * (size_t)nlam;
         vrt_regular *raw = nullptr;
         if ((rc = vrt_regular_create(nz, nx, ny, z, x, y, device, &raw))) return rc;
-        RegularPtr r(raw, regular_free);
+        RegularPtr r(raw);
         VRT_HIP_TRY(hipSetDevice(device));
         DevBuf<double> d_S, d_A, d_top;
         if ((rc = d_S.alloc(vol)) || (rc = d_A.alloc(vol)) || (rc = d_top.alloc(top))) return rc;
@@ -1106,7 +1099,7 @@ extern "C" int vrt_short_characteristics(int64_t nz, int64_t nx, int64_t ny, con
         vrt_regular *raw = nullptr;
         int rc = vrt_regular_create(nz, nx, ny, z, x, y, device, &raw);
         if (rc) return rc;
-        RegularPtr r(raw, regular_free);
+        RegularPtr r(raw);
         VRT_HIP_TRY(hipSetDevice(device));
         const size_t nS = (size_t)(vol * (S_stride ? n_solve : 1)), nA = (size_t)(vol * (alpha_stride ? n_solve : 1));
         const size_t nI0 = (size_t)(plane * n_solve), nout = (size_t)(vol * n_solve);

@@ -263,7 +263,7 @@ int line_J_pass(vrt_regular *r, const LineSolves &ls, const LinePoint &lp, const
     int rc;
     for (int64_t g0 = 0; g0 < n_solve; g0 += ls.chunk) {
         const int64_t cnt = std::min(ls.chunk, n_solve - g0);
-        if ((rc = dev_grow(r->d_A, r->cap_A, (size_t)(cnt * vol)))) return rc;
+        if ((rc = r->d_A.grow((size_t)(cnt * vol)))) return rc;
         const int64_t a0 = g0 / nlam, na = (g0 + cnt - 1) / nlam - a0 + 1;
         hipLaunchKernelGGL(k_reg_line_opacity, dim3(bx, (unsigned)std::min<int64_t>(na, 65535)), dim3(256), 0, st, (int)nz,
                            (int)nx, (int)ny, (int)nlam, g0, cnt, a0, na, (const double *)ls.d_ka, lp, r->d_A);
@@ -289,7 +289,7 @@ struct vrt_regular_lambda {
     double lambda0 = 0, c0 = 0, strength_const = 0, Bij = 0, Bji = 0, sigma_bb_const = 0, hc_over_kB = 0, pref_ij = 0,
            pref_ji = 0;
     LineSolves ls;
-    hipStream_t st = nullptr;
+    Stream st;
     // per point, Julia order
     DevBuf<double> d_small;             // lambda | planck2 | sigma_bf1 | sigma_bf2
     DevBuf<double> d_velocity, d_doppler, d_gamma_static, d_gamma_unsold, d_alpha_cont, d_eps, d_temperature, d_atom, d_B0,
@@ -301,11 +301,6 @@ struct vrt_regular_lambda {
     DevBuf<unsigned long long> d_scalars;
     int64_t iterations = 0;
     NgState ng;                         // vrt_regular_lambda_set_acceleration (off: nothing allocated, nothing run)
-    ~vrt_regular_lambda()
-    {
-        ng_release(ng);
-        if (st) (void)hipStreamDestroy(st);
-    }
 };
 
 extern "C" {
@@ -392,7 +387,7 @@ int vrt_regular_lambda_create(vrt_regular *r, int64_t n_angles, const double *k,
         s->lambda0 = lc->lambda0; s->c0 = lc->c0; s->strength_const = lc->strength_const; s->Bij = lc->Bij; s->Bji = lc->Bji;
         s->sigma_bb_const = lc->sigma_bb_const; s->hc_over_kB = lc->hc_over_kB; s->pref_ij = lc->pref_ij; s->pref_ji = lc->pref_ji;
         if ((rc = line_solves_init(s->ls, r, n_angles, k, dirs, weights, nlam))) return rc;
-        VRT_HIP_TRY(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
+        if ((rc = s->st.create())) return rc;
         const size_t n = (size_t)vol, nl = (size_t)nlam, nS = n * nl;
         const size_t nb1 = (size_t)(lc->blocks[3] - lc->blocks[2]), nb2 = (size_t)(lc->blocks[5] - lc->blocks[4]);
         std::vector<double> small;
@@ -490,7 +485,7 @@ int vrt_regular_lambda_iterate(vrt_regular_lambda *s, double *max_rel_change)
             // copy the next solves read is made again from it
             NgRange rg;
             rg.dense = (n * nlam) & ~(int64_t)1; rg.tail = (n * nlam) & 1; rg.tstride = 1;
-            if ((rc = ng_after_iterate(s->ng, s->iterations, s->d_S[s->sc].p, (size_t)(n * nlam), rg, st))) return rc;
+            if ((rc = ng_after_iterate(s->ng, s->iterations, s->d_S[s->sc], (size_t)(n * nlam), rg, st))) return rc;
             if (s->ng.last_applied == 1) {
                 if ((rc = launch_to_planes(r, nlam, s->d_S[s->sc], s->d_S_pl, st))) return rc;
                 VRT_HIP_TRY(hipStreamSynchronize(st));
