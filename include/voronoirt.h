@@ -694,6 +694,31 @@ int vrt_lambda_last_acceleration(const vrt_lambda *s, int *applied, double sums[
 int vrt_regular_lambda_last_acceleration(const vrt_regular_lambda *s, int *applied, double sums[5],
                                          double coeffs[2]);
 
+/* ---- resuming a line session from saved S and populations (src/recover_simulation.jl: recover_voronoi, recover_regular) ----
+ * The reference writes populations and S_new after every pass (src/lambda_iteration.jl:280-281) and reads the two back to
+ * carry on.  They are the complete state of a line session: every iterate begins by recomputing γ and the line strength
+ * from the current populations and reads S from where the last update wrote it; everything else is a constant of the case.
+ * vrt_*_lambda_set_state replaces that state by host arrays with the dims the matching *_get writes: S (nlam, n),
+ * populations (n, 3); for the regular session n = nz nx ny, ghost border included.  Either pointer may be NULL: that part
+ * of the state stays as it is; both NULL is VRT_EINVAL.  S must be finite and > 0 everywhere (the rule of
+ * vrt_continuum_set_source), the populations finite and >= 0: both are checked on the host before the device is touched
+ * (VRT_EINVAL).  On any failure, an allocation failure included, the session is untouched -- its next iterate is the one it
+ * would have run anyway: the new state is built in device copies beside the session and moved in once they are complete.
+ * The call returns after its copies have completed (the host arrays may go).
+ * Afterwards the session continues exactly as one that had reached this state by iterating: with acceleration off, a fresh
+ * session given the *_get output of another session after k iterates returns, from its first iterate on, the scalar, J, S,
+ * populations, R and γ of the other's iterates k+1, k+2, ... bit for bit.  J, R and γ as *_get returns them are NOT
+ * changed by this call: they stay those of the last iterate THIS session ran (zeros before its first).  A recorded Ng
+ * history is dropped as vrt_continuum_set_source drops it (a step that falls due before three further iterates are
+ * recorded is not taken; *_last_acceleration reports 0 until the next iterate); the acceleration settings and the
+ * iterate counter stay.  The state *_get returns right after an accepted Ng step is the extrapolated S in both sweep-order
+ * copies, and resumes like any other.  vrt_lambda_set_state takes the plan's lock as vrt_lambda_iterate does;
+ * vrt_multi_lambda_set_state gives every device the columns of its wavelength block of S and a full copy of the
+ * populations.  A session that never calls these entries allocates and runs nothing extra. */
+int vrt_lambda_set_state(vrt_lambda *s, const double *S, const double *populations);
+int vrt_regular_lambda_set_state(vrt_regular_lambda *s, const double *S, const double *populations);
+int vrt_multi_lambda_set_state(vrt_multi_lambda *s, const double *S, const double *populations);
+
 /* ---- the continuum scattering Λ-iteration on both grids (src/lambda_continuum.jl) --------------------------------------
  * Λ_voronoi (:109-160) and Λ_regular (:58-107), the loop of the reference's production run (src/compare_continuum.jl), with
  * library-owned device state: coherent scattering at nlam independent wavelengths (the reference: one, 500 nm), α_cont

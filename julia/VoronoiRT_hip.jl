@@ -249,6 +249,23 @@ struct LineCase
     pref_ji::Float64
 end
 
+# ---- the state a line session resumes from (vrt_*_lambda_set_state; src/recover_simulation.jl) -- unrun ----------------
+# `a` (nothing, plain numbers or a Unitful array) as a dense Float64 array of the session's dims
+function plain_array(a, unit, dims)
+    a === nothing && return nothing
+    out = Array{Float64}(eltype(a) <: Real ? a : ustrip.(unit, a))
+    size(out) == dims || error("the saved state has dims $(size(out)), the case needs $dims")
+    return out
+end
+
+# S (nλ, n) and populations (n, 3) into the session; `nothing` leaves that half as it is, both `nothing` is no call
+function set_state(f::Symbol, ses::Ptr{Cvoid}, S, pops)
+    S === nothing && pops === nothing && return
+    GC.@preserve S pops check(ccall(dlsym(libvrt_handle(), f), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), ses,
+                                    S === nothing ? Ptr{Float64}(C_NULL) : pointer(S),
+                                    pops === nothing ? Ptr{Float64}(C_NULL) : pointer(pops)))
+end
+
 """
     Λ(ϵ, maxiter, sites, line, quadrature, DATA) -> (J_new, S_new, α_cont, populations)
 
@@ -259,9 +276,12 @@ HDF5 file exactly as the reference checkpoints them (:280-281); `criterion` keep
 `ng = (start, period)`: second-order Ng acceleration inside the session (vrt_lambda_set_acceleration; one device
 only -- the multi-device session has no such entry), the first step after iterate `start`, then every `period`
 iterates, both >= 4.  The keyword is unrun: Julia is not installed where the library is built.
+`S0` (nλ, n), `populations0` (n, 3), with or without units: the loop starts from them instead of LTE with S = B_0
+(vrt_lambda_set_state / vrt_multi_lambda_set_state; the state the reference checkpoints, :280-281) and continues bit for
+bit as the run that wrote them; either alone replaces that half.  Unrun as well.
 """
 function Λ(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, line::HydrogenicLine, quadrature::String, DATA::String;
-           ng::Union{Nothing,Tuple{Int,Int}}=nothing)
+           ng::Union{Nothing,Tuple{Int,Int}}=nothing, S0=nothing, populations0=nothing)
     println("---Iterating---")
     LTE_pops = VoronoiRT.LTE_populations(line, sites)
     populations = copy(LTE_pops)
@@ -328,6 +348,8 @@ function Λ(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, line::Hydr
         multi && error("Ng acceleration needs the one-device session (vrt_multi_lambda_* has no acceleration entry)")
         check(ccall((:vrt_lambda_set_acceleration, libvrt), Cint, (Ptr{Cvoid}, Cint, Cint, Cint), ses[], 2, ng[1], ng[2]))
     end
+    set_state(multi ? :vrt_multi_lambda_set_state : :vrt_lambda_set_state, ses[], plain_array(S0, I_unit, (nλ, n)),
+              plain_array(populations0, u"m^-3", (n, 3)))
     ng_applied = Ref{Cint}(0); ng_coeffs = zeros(2)
     i = 0
     diff = Ref{Float64}(1.0)                  # criterion(S_new = B_0, S_old = 0) = |1 - 0/B| = 1, :325-349
@@ -368,10 +390,11 @@ the reference's own functions, as in `Λ` above; each iteration is vrt_regular_l
 populations and S_new are fetched and checkpointed without the ghost border like the reference (:188-189).
 Arrays keep their Julia shapes: (nλ, nz, nx, ny), (nz, nx, ny, 3) and (3, 3, nz, nx, ny) are vrt_line_case's
 (nλ, n), (n, 3) and (3, 3, n) with n = nz nx ny.  `ng = (start, period)` as for `Λ`
-(vrt_regular_lambda_set_acceleration).  Unrun: Julia is not installed where the library is built.
+(vrt_regular_lambda_set_acceleration).  `S0` (nλ, nz, nx, ny), `populations0` (nz, nx, ny, 3), ghost border included,
+as for `Λ` (vrt_regular_lambda_set_state).  Unrun: Julia is not installed where the library is built.
 """
 function Λ_regular(ϵ::AbstractFloat, maxiter::Integer, atmos, line::HydrogenicLine, quadrature::String, DATA::String;
-                   ng::Union{Nothing,Tuple{Int,Int}}=nothing)
+                   ng::Union{Nothing,Tuple{Int,Int}}=nothing, S0=nothing, populations0=nothing)
     LTE_pops = VoronoiRT.LTE_populations(line, atmos)
     α_cont = VoronoiRT.α_absorption.(line.λ0, atmos.temperature, atmos.electron_density * 1.0,
                                      LTE_pops[:, :, :, 1] .+ LTE_pops[:, :, :, 2], LTE_pops[:, :, :, 3]) .+
@@ -440,6 +463,8 @@ function Λ_regular(ϵ::AbstractFloat, maxiter::Integer, atmos, line::Hydrogenic
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ses[], Jp, Sp, pops, C_NULL, C_NULL))
     ng !== nothing && check(ccall((:vrt_regular_lambda_set_acceleration, libvrt), Cint, (Ptr{Cvoid}, Cint, Cint, Cint),
                                   ses[], 2, ng[1], ng[2]))
+    set_state(:vrt_regular_lambda_set_state, ses[], plain_array(S0, I_unit, (nλ, nz, nx, ny)),
+              plain_array(populations0, u"m^-3", (nz, nx, ny, 3)))
     ng_applied = Ref{Cint}(0); ng_coeffs = zeros(2)
     i = 0
     diff = Ref{Float64}(1.0)                  # criterion(S_new = B_0, S_old = 0) = 1
@@ -464,6 +489,39 @@ function Λ_regular(ϵ::AbstractFloat, maxiter::Integer, atmos, line::Hydrogenic
     ccall((:vrt_regular_destroy, libvrt), Cvoid, (Ptr{Cvoid},), reg[])
     println(i == maxiter ? "Did not converge inside scope" : "Converged in $i iterations")
     return J * I_unit, S * I_unit, α_cont, pops * 1u"m^-3"
+end
+
+# ---- recover_voronoi / recover_regular: src/recover_simulation.jl -- unrun -----------------------------------------------
+"""
+    recover_voronoi(ϵ, maxiter, quadrature, DATA; ng=nothing) -> (J_new, S_new, α_cont, populations)
+
+The reference's recover_voronoi (src/recover_simulation.jl:103-206): `read_sites(DATA)` (:213-277) rebuilds the sites and
+reads the datasets "source_function" (nλ, n) and "populations" (n, 3) the last pass wrote, and `Λ` carries on from them.
+`line` is made as the reference makes it there (test_atom(nλ_bb, nλ_bf) on the sites' temperature).  Unrun.
+"""
+function recover_voronoi(ϵ::AbstractFloat, maxiter::Integer, quadrature::String, DATA::String; ng=nothing)
+    println("---Recovering simulation---")
+    sites, S_new, populations = VoronoiRT.read_sites(DATA)
+    line = HydrogenicLine(VoronoiRT.test_atom(VoronoiRT.nλ_bb, VoronoiRT.nλ_bf)..., sites.temperature)
+    return Λ(ϵ, maxiter, sites, line, quadrature, DATA; ng=ng, S0=S_new, populations0=populations)
+end
+
+"""
+    recover_regular(ϵ, maxiter, quadrature, DATA; ng=nothing) -> (J_new, S_new, α_cont, populations)
+
+The reference's recover_regular (src/recover_simulation.jl:4-101) on the periodic atmosphere of `read_quantities(DATA;
+periodic=true)`, whose populations carry the ghost border.  The dataset "source_function" is stored without the border
+(src/lambda_iteration.jl:188-189) and gets it back here the way the reference gives it to every field
+(`periodic_borders`): the interior resumes exactly, the border points start from their periodic images.  Unrun.
+"""
+function recover_regular(ϵ::AbstractFloat, maxiter::Integer, quadrature::String, DATA::String; ng=nothing)
+    println("---Recovering simulation---")
+    atmos, populations, _ = VoronoiRT.read_quantities(DATA; periodic=true)
+    S_new = VoronoiRT.h5open(DATA, "r") do file
+        VoronoiRT.periodic_borders(read(file, "source_function")[:, :, :, :] * I_unit)
+    end
+    line = HydrogenicLine(VoronoiRT.test_atom(VoronoiRT.nλ_bb, VoronoiRT.nλ_bf)..., atmos.temperature)
+    return Λ_regular(ϵ, maxiter, atmos, line, quadrature, DATA; ng=ng, S0=S_new, populations0=populations)
 end
 
 # ---- J_λ_voronoi, continuum case: src/lambda_continuum.jl:27-56 ---------------------------------

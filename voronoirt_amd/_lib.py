@@ -186,6 +186,9 @@ PROTOTYPES = {
     "vrt_regular_lambda_set_acceleration": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vrt_lambda_last_acceleration": (ctypes.c_int, [vp, p_int, p_dbl, p_dbl]),
     "vrt_regular_lambda_last_acceleration": (ctypes.c_int, [vp, p_int, p_dbl, p_dbl]),
+    "vrt_lambda_set_state": (ctypes.c_int, [vp, p_dbl, p_dbl]),
+    "vrt_regular_lambda_set_state": (ctypes.c_int, [vp, p_dbl, p_dbl]),
+    "vrt_multi_lambda_set_state": (ctypes.c_int, [vp, p_dbl, p_dbl]),
     "vrt_continuum_case_check": (ctypes.c_int, [ctypes.POINTER(ContinuumCaseStruct), c_i64]),
     "vrt_continuum_create": (ctypes.c_int, [vp, ctypes.POINTER(ContinuumCaseStruct), p_dbl, ctypes.POINTER(vp)]),
     "vrt_continuum_iterate": (ctypes.c_int, [vp, p_dbl]),

@@ -476,30 +476,24 @@ class MultiDevicePlan:
                                                  _d(_f64(weights)), _d(J)))
         return J
 
-    def lambda_iteration(self, eps_conv: float, maxiter: int, case, weights):
+    def lambda_iteration(self, eps_conv: float, maxiter: int, case, weights, S0=None, populations0=None, checkpoint=None,
+                         checkpoint_every: int = 1, resume=None):
         """Λ_voronoi (src/lambda_iteration.jl:205-300) across the devices (`vrt_multi_lambda_*`): wavelength blocks per
-        device, one all-reduce of the rate-integral shares per iteration.  Returns (J, S_new, populations (3, n), history)."""
+        device, one all-reduce of the rate-integral shares per iteration.  Returns (J, S_new, populations (3, n), history).
+        S0, populations0, checkpoint, checkpoint_every, resume as for `Lambda_voronoi_host`
+        (`vrt_multi_lambda_set_state`: every device takes its wavelength block of S and all the populations)."""
         L = _lib.load()
         lc, keep = case.c_struct()
+        n, nlam = self.n, int(keep["lam"].size)
+        start = _start_state(S0, populations0, resume, checkpoint_every, n, nlam, "lambda_iteration")
         h = ctypes.c_void_p()
         check(L.vrt_multi_lambda_create(self._h, ctypes.byref(lc), _d(_f64(weights)), ctypes.byref(h)))
-        n, nlam = self.n, int(keep["lam"].size)
-        history, diff, i = [], 1.0, 0
         try:
-            while diff > eps_conv and i < maxiter:
-                d = ctypes.c_double()
-                check(L.vrt_multi_lambda_iterate(h, ctypes.byref(d)))
-                diff = d.value
-                history.append(diff)
-                i += 1
-                if diff != diff:
-                    import warnings
-                    warnings.warn(f"lambda_iteration: NaN DIFF! at iteration {i} -- stopping, results are not converged")
-            J, S, pops = np.zeros((n, nlam)), np.zeros((n, nlam)), np.zeros((3, n))
-            check(L.vrt_multi_lambda_get(h, _d(J), _d(S), _d(pops), None, None))
+            J, S, pops, history, _, i = _session_loop(L, "multi_lambda", h, n, nlam, eps_conv, maxiter, start, checkpoint,
+                                                      checkpoint_every, None, "lambda_iteration")
             if i == 0:
-                S[:] = keep["B0"]
-                pops[:] = keep["lte"]
+                S[:] = keep["B0"] if start[0] is None else start[0]
+                pops[:] = keep["lte"] if start[1] is None else start[1]
             return J, S, pops, history
         finally:
             L.vrt_multi_lambda_destroy(h)
@@ -1299,6 +1293,105 @@ class LineCase:
         return lc, keep
 
 
+# ---- resuming a line Λ-iteration: the state is (S, populations) (src/recover_simulation.jl; vrt_*_lambda_set_state) ----
+CHECKPOINT_KEYS = ("S", "populations", "iterate", "history")
+
+
+def write_checkpoint(path, S, populations, iterate: int, history) -> None:
+    """The checkpoint of a line Λ-iteration as an .npz with the keys `S` (n, nλ), `populations` (3, n), `iterate` (the
+    number of iterates done in total) and `history` (every scalar so far).  Written under a temporary name in the
+    directory of `path` and moved over it with os.replace: a run killed in between leaves the previous file whole."""
+    path = os.fspath(path)
+    tmp = f"{path}.{os.getpid()}.tmp.npz"          # (numpy appends .npz to a name that does not end in it)
+    try:
+        np.savez(tmp, S=_f64(S), populations=_f64(populations), iterate=np.int64(iterate), history=_f64(history).reshape(-1))
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+
+
+def _check_state_shapes(S, populations, n: int, nlam: int, who: str):
+    """S (n, nλ) and populations (3, n) as contiguous float64 (None stays None); ValueError for any other shape"""
+    if S is not None:
+        S = _f64(S)
+        if S.shape != (n, nlam):
+            raise ValueError(f"{who}: S has shape {S.shape}, the case needs {(n, nlam)}")
+    if populations is not None:
+        populations = _f64(populations)
+        if populations.shape != (3, n):
+            raise ValueError(f"{who}: the populations have shape {populations.shape}, the case needs {(3, n)}")
+    return S, populations
+
+
+def read_checkpoint(path, n: int | None = None, nlam: int | None = None) -> dict:
+    """The four keys of `write_checkpoint` (S, populations as float64 arrays, iterate as int, history as a list).  With
+    n and nλ given, a file whose shapes do not match them raises ValueError."""
+    with np.load(os.fspath(path)) as f:
+        missing = [k for k in CHECKPOINT_KEYS if k not in f.files]
+        if missing:
+            raise ValueError(f"{path}: not a Λ-iteration checkpoint, no {missing}")
+        S, pops = _f64(f["S"]), _f64(f["populations"])
+        iterate, history = int(f["iterate"]), [float(v) for v in np.asarray(f["history"]).reshape(-1)]
+    if S.ndim != 2 or pops.shape != (3, S.shape[0]):
+        raise ValueError(f"{path}: S {S.shape} and populations {pops.shape} are not (n, nλ) and (3, n)")
+    if n is not None and nlam is not None:
+        _check_state_shapes(S, pops, n, nlam, os.fspath(path))
+    return {"S": S, "populations": pops, "iterate": iterate, "history": history}
+
+
+def _start_state(S0, populations0, resume, checkpoint_every, n: int, nlam: int, who: str):
+    """What a session-backed driver starts from, checked before any device work: (S0, populations0, iterate0, history0)"""
+    if int(checkpoint_every) < 1:
+        raise ValueError(f"{who}: checkpoint_every must be >= 1")
+    if resume is None:
+        S0, populations0 = _check_state_shapes(S0, populations0, n, nlam, who)
+        return S0, populations0, 0, []
+    if S0 is not None or populations0 is not None:
+        raise ValueError(f"{who}: give either resume or S0 / populations0")
+    ck = read_checkpoint(resume, n, nlam)
+    return ck["S"], ck["populations"], ck["iterate"], ck["history"]
+
+
+def _session_loop(L, prefix: str, h, n: int, nlam: int, eps_conv: float, maxiter: int, start, checkpoint, checkpoint_every: int,
+                  ng, who: str):
+    """The loop every session-backed line driver runs on its session `h` (vrt_<prefix>_iterate / _get / _set_state):
+    returns (J, S, populations, history, steps, new iterates)."""
+    fn = lambda name: getattr(L, f"vrt_{prefix}_{name}")
+    S0, pops0, iterate0, history0 = start
+    if S0 is not None or pops0 is not None:
+        check(fn("set_state")(h, _d(S0), _d(pops0)))
+    history, steps, i = list(history0), [], 0
+    diff = history[-1] if history else 1.0                 # criterion(S_new = B, S_old = 0) = 1
+    S, pops = np.zeros((n, nlam)), np.zeros((3, n))
+
+    def save():
+        check(fn("get")(h, None, _d(S), _d(pops), None, None))       # (J, R and γ are not part of the state)
+        write_checkpoint(checkpoint, S, pops, iterate0 + i, history)
+
+    saved = -1
+    while diff > eps_conv and i < maxiter:
+        d = ctypes.c_double()
+        check(fn("iterate")(h, ctypes.byref(d)))
+        diff = d.value
+        history.append(diff)
+        i += 1
+        if ng is not None:
+            _ng_last(fn("last_acceleration"), h, i, steps)
+        if checkpoint is not None and i % int(checkpoint_every) == 0:
+            save()
+            saved = i
+        if diff != diff:
+            import warnings
+            warnings.warn(f"{who}: NaN DIFF! at iteration {i} -- stopping, results are not converged")
+    if checkpoint is not None and i > 0 and saved != i:
+        save()
+    J = np.zeros((n, nlam))
+    check(fn("get")(h, _d(J), _d(S), _d(pops), None, None))
+    return J, S, pops, history, steps, i
+
+
 def _quadrature_plan(sites: VoronoiSites, quadrature: str, n_sweeps: int):
     w, th, ph, _ = read_quadrature(quadrature)
     key = (os.path.basename(quadrature), int(n_sweeps))
@@ -1331,7 +1424,8 @@ def J_lambda_voronoi_line(S_lambda, populations, sites: VoronoiSites, case: Line
     return J
 
 
-def _Lambda_voronoi_native(eps_conv: float, maxiter: int, sites: VoronoiSites, case: LineCase, quadrature: str, n_sweeps: int):
+def _Lambda_voronoi_native(eps_conv: float, maxiter: int, sites: VoronoiSites, case: LineCase, quadrature: str, n_sweeps: int,
+                           S0=None, populations0=None):
     import torch
     w, th, ph, nq = read_quadrature(quadrature)
     dev = torch.device("cuda", sites.device)
@@ -1342,11 +1436,12 @@ def _Lambda_voronoi_native(eps_conv: float, maxiter: int, sites: VoronoiSites, c
                                                   ("velocity", "doppler", "gamma_static", "gamma_unsold", "alpha_cont", "eps",
                                                    "temperature"))
     d_B, d_lte, d_C, d_atom = t(case.B0), t(case.lte), t(case.C), t(case.atom_density)
-    pops = d_lte.clone()
+    pops = d_lte.clone() if populations0 is None else t(populations0)
+    d_S0 = d_B if S0 is None else t(S0)
     st = torch.cuda.current_stream().cuda_stream
     cnt = plan.native_plane_count(nlam)
     S_up, S_dn, B_up, J_up, J_dn = (torch.zeros(cnt, dtype=torch.float64, device=dev) for _ in range(5))
-    plan.to_native_dev(nlam, nlam, d_B.data_ptr(), S_up.data_ptr(), S_dn.data_ptr(), stream=st)      # S_new = B_0
+    plan.to_native_dev(nlam, nlam, d_S0.data_ptr(), S_up.data_ptr(), S_dn.data_ptr(), stream=st)     # S_new = B_0 (or S0)
     plan.to_native_dev(nlam, nlam, d_B.data_ptr(), B_up.data_ptr(), 0, stream=st)
     native = torch.empty(plan.native_alpha_count(nlam), dtype=torch.float64, device=dev)
     d_R = torch.empty((n, 3, 3), dtype=torch.float64, device=dev)
@@ -1387,47 +1482,41 @@ def _Lambda_voronoi_native(eps_conv: float, maxiter: int, sites: VoronoiSites, c
 
 
 def Lambda_voronoi_host(eps_conv: float, maxiter: int, sites: VoronoiSites, case: LineCase, quadrature: str,
-                        n_sweeps: int = 3, ng=None):
+                        n_sweeps: int = 3, ng=None, S0=None, populations0=None, checkpoint=None, checkpoint_every: int = 1,
+                        resume=None):
     """Λ_voronoi (src/lambda_iteration.jl:205-300) for a host WITHOUT device arrays: the library owns the device
     state (`vrt_lambda_create` / `_iterate` / `_get`), one call per iteration, only the criterion's scalar
     comes back inside the loop.  Returns (J, S_new, populations (3, n), history).
     ng=(start, period): second-order Ng acceleration inside the session (`vrt_lambda_set_acceleration`), the first
     step after iterate `start`, then every `period` iterates (both >= 4); the tuple gains a fifth element, the list of
-    (iterate, applied, a, b) of every due step."""
+    (iterate, applied, a, b) of every due step.
+    S0 (n, nλ), populations0 (3, n): start from this state instead of LTE with S = B_0 (`vrt_lambda_set_state`, the
+    reference's recover_voronoi); either alone replaces that half.  The run continues bit for bit as the one that
+    produced them.  checkpoint="run.npz": `write_checkpoint` after every `checkpoint_every`-th iterate and after the
+    last.  resume="run.npz": start from such a file; the returned history is the file's followed by the new scalars,
+    `maxiter` counts the new iterates; a file whose shapes do not match the case raises ValueError before any device work."""
     L = _lib.load()
-    plan, w = _quadrature_plan(sites, quadrature, n_sweeps)
     lc, keep = case.c_struct()
+    n, nlam = sites.n, int(keep["lam"].size)
+    start = _start_state(S0, populations0, resume, checkpoint_every, n, nlam, "Lambda_voronoi_host")
+    plan, w = _quadrature_plan(sites, quadrature, n_sweeps)
     h = ctypes.c_void_p()
     check(L.vrt_lambda_create(plan._h, ctypes.byref(lc), _d(_f64(w)), ctypes.byref(h)))
-    n, nlam = sites.n, int(keep["lam"].size)
-    history, diff, i = [], 1.0, 0                              # criterion(S_new = B, S_old = 0) = 1
-    steps = []
     try:
         if ng is not None:
             check(L.vrt_lambda_set_acceleration(h, 2, *_ng_settings(ng)))
-        while diff > eps_conv and i < maxiter:
-            d = ctypes.c_double()
-            check(L.vrt_lambda_iterate(h, ctypes.byref(d)))
-            diff = d.value
-            history.append(diff)
-            i += 1
-            if ng is not None:
-                _ng_last(L.vrt_lambda_last_acceleration, h, i, steps)
-            if diff != diff:
-                import warnings
-                warnings.warn(f"Lambda_voronoi_host: NaN DIFF! at iteration {i} -- stopping, results are not converged")
-        J, S, pops = np.zeros((n, nlam)), np.zeros((n, nlam)), np.zeros((3, n))
-        check(L.vrt_lambda_get(h, _d(J), _d(S), _d(pops), None, None))
+        J, S, pops, history, steps, i = _session_loop(L, "lambda", h, n, nlam, eps_conv, maxiter, start, checkpoint,
+                                                      checkpoint_every, ng, "Lambda_voronoi_host")
         if i == 0:
-            S[:] = keep["B0"]
-            pops[:] = keep["lte"]
+            S[:] = keep["B0"] if start[0] is None else start[0]
+            pops[:] = keep["lte"] if start[1] is None else start[1]
         return (J, S, pops, history) if ng is None else (J, S, pops, history, steps)
     finally:
         L.vrt_lambda_destroy(h)
 
 
 def Lambda_voronoi(eps_conv: float, maxiter: int, sites: VoronoiSites, case: LineCase, quadrature: str,
-                   n_sweeps: int = 3, native: bool = False):
+                   n_sweeps: int = 3, native: bool = False, S0=None, populations0=None):
     """Λ_voronoi (src/lambda_iteration.jl:205-300) with everything between two convergence checks on
     the device, over the device-pointer entry points: per iteration `vrt_line_terms_dev` (γ and the line
     strength of the current populations, :72-75), `vrt_line_opacity_dev` (α_tot of every angle, :72-96),
@@ -1437,10 +1526,17 @@ def Lambda_voronoi(eps_conv: float, maxiter: int, sites: VoronoiSites, case: Lin
     native=True: S and J stay in the sweep's own per-direction plane sets between the steps
     (`vrt_plan_execute_native_dev`, `vrt_lambda_update_native_dev`, `vrt_rates_populations_native_dev`): no layout
     change inside the loop, the same results bit for bit.
+    S0 (n, nλ), populations0 (3, n): the loop starts from them instead (S finite and > 0, populations finite and >= 0;
+    ValueError otherwise) and continues bit for bit as the run that produced them.
     Returns (J, S_new, populations (3, n), history of the criterion's differences) as numpy arrays."""
     import torch
+    S0, populations0 = _check_state_shapes(S0, populations0, sites.n, int(np.asarray(case.lam).size), "Lambda_voronoi")
+    if S0 is not None and not (np.isfinite(S0).all() and (S0 > 0).all()):
+        raise ValueError("Lambda_voronoi: S0 must be finite and > 0 everywhere")
+    if populations0 is not None and not (np.isfinite(populations0).all() and (populations0 >= 0).all()):
+        raise ValueError("Lambda_voronoi: populations0 must be finite and >= 0 everywhere")
     if native:
-        return _Lambda_voronoi_native(eps_conv, maxiter, sites, case, quadrature, n_sweeps)
+        return _Lambda_voronoi_native(eps_conv, maxiter, sites, case, quadrature, n_sweeps, S0, populations0)
     w, th, ph, nq = read_quadrature(quadrature)
     dev = torch.device("cuda", sites.device)
     n, nlam = sites.n, int(np.asarray(case.lam).size)
@@ -1450,8 +1546,8 @@ def Lambda_voronoi(eps_conv: float, maxiter: int, sites: VoronoiSites, case: Lin
                                                   ("velocity", "doppler", "gamma_static", "gamma_unsold", "alpha_cont", "eps",
                                                    "temperature"))
     d_B, d_lte, d_C, d_atom = t(case.B0), t(case.lte), t(case.C), t(case.atom_density)
-    pops = d_lte.clone()                                       # populations = copy(LTE_pops)
-    S_new, S_old, J = d_B.clone(), torch.zeros_like(d_B), torch.zeros_like(d_B)
+    pops = d_lte.clone() if populations0 is None else t(populations0)       # populations = copy(LTE_pops)
+    S_new, S_old, J = d_B.clone() if S0 is None else t(S0), torch.zeros_like(d_B), torch.zeros_like(d_B)
     native = torch.empty(plan.native_alpha_count(nlam), dtype=torch.float64, device=dev)
     d_R = torch.empty((n, 3, 3), dtype=torch.float64, device=dev)
     d_gam, strength = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
@@ -1534,40 +1630,30 @@ def J_lambda_regular_line(S, populations, z, x, y, case: LineCase, quadrature: s
 
 
 def Lambda_regular(eps_conv: float, maxiter: int, z, x, y, case: LineCase, quadrature: str, n_sweeps: int = 3,
-                   device: int = 0, ng=None):
+                   device: int = 0, ng=None, S0=None, populations0=None, checkpoint=None, checkpoint_every: int = 1,
+                   resume=None):
     """Λ_regular (src/lambda_iteration.jl:116-205) with library-owned device state (`vrt_regular_lambda_create` /
     `_iterate` / `_get`): one call per iteration, only the criterion's scalar comes back inside the loop.  The raster
     and `case` as for `J_lambda_regular_line`; every point, ghost border included, is a point of the loop.  Starts
     in LTE with S = B_0; stops like `Lambda_voronoi_host` (criterion, NaN).  Returns (J, S_new, populations (3, n),
     history); ng=(start, period) as for `Lambda_voronoi_host` (`vrt_regular_lambda_set_acceleration`), with the list of
-    (iterate, applied, a, b) as a fifth element."""
+    (iterate, applied, a, b) as a fifth element.  S0, populations0, checkpoint, checkpoint_every, resume as for
+    `Lambda_voronoi_host` (`vrt_regular_lambda_set_state`, the reference's recover_regular)."""
     L = _lib.load()
     w, k, dirs = _regular_directions(quadrature)
     lc, keep = case.c_struct()
     nlam = int(keep["lam"].size)
     n = int(keep["doppler"].size)
+    start = _start_state(S0, populations0, resume, checkpoint_every, n, nlam, "Lambda_regular")
     solver = _regular_solver(z, x, y, n, device)
     h = ctypes.c_void_p()
     try:
         check(L.vrt_regular_lambda_create(solver._h, k.shape[0], _d(k), dirs.ctypes.data_as(_lib.p_int), _d(w),
                                           ctypes.byref(lc), int(n_sweeps), ctypes.byref(h)))
-        history, diff, i = [], 1.0, 0                          # criterion(S_new = B, S_old = 0) = 1
-        steps = []
         if ng is not None:
             check(L.vrt_regular_lambda_set_acceleration(h, 2, *_ng_settings(ng)))
-        while diff > eps_conv and i < maxiter:
-            d = ctypes.c_double()
-            check(L.vrt_regular_lambda_iterate(h, ctypes.byref(d)))
-            diff = d.value
-            history.append(diff)
-            i += 1
-            if ng is not None:
-                _ng_last(L.vrt_regular_lambda_last_acceleration, h, i, steps)
-            if diff != diff:
-                import warnings
-                warnings.warn(f"Lambda_regular: NaN DIFF! at iteration {i} -- stopping, results are not converged")
-        J, S, pops = np.zeros((n, nlam)), np.zeros((n, nlam)), np.zeros((3, n))
-        check(L.vrt_regular_lambda_get(h, _d(J), _d(S), _d(pops), None, None))
+        J, S, pops, history, steps, _ = _session_loop(L, "regular_lambda", h, n, nlam, eps_conv, maxiter, start, checkpoint,
+                                                      checkpoint_every, ng, "Lambda_regular")
         return (J, S, pops, history) if ng is None else (J, S, pops, history, steps)
     finally:
         if h:

@@ -23,6 +23,31 @@ int fail(int code, const std::string &msg)
     return code;
 }
 
+int check_source(const double *S, int64_t count)
+{
+    for (int64_t i = 0; i < count; i++)
+        if (!std::isfinite(S[i]) || !(S[i] > 0.0)) return fail(VRT_EINVAL, "S must be finite and > 0 everywhere");
+    return VRT_OK;
+}
+
+int check_state_pointers(const void *session, const double *S, const double *populations)
+{
+    if (!session) return fail(VRT_EINVAL, "NULL session");
+    if (!S && !populations) return fail(VRT_EINVAL, "S and populations are both NULL: nothing to set");
+    return VRT_OK;
+}
+
+int check_state(int64_t n, int64_t nlam, const double *S, const double *populations)
+{
+    if (S)
+        if (int rc = check_source(S, n * nlam)) return rc;
+    if (populations)
+        for (int64_t i = 0; i < 3 * n; i++)
+            if (!std::isfinite(populations[i]) || !(populations[i] >= 0.0))
+                return fail(VRT_EINVAL, "the populations must be finite and >= 0 everywhere");
+    return VRT_OK;
+}
+
 void tuning_from_env(Tuning &t)
 {
     static const char *names[] = {"VRT_PATH", "VRT_STEP_K", "VRT_STEP_SINGLE", "VRT_STEP_PAIRS", "VRT_STEP_XCD",

@@ -335,13 +335,6 @@ int check_case(const vrt_continuum_case *cc, int64_t n)
     return VRT_OK;
 }
 
-int check_source(const double *S, int64_t count)
-{
-    for (int64_t i = 0; i < count; i++)
-        if (!std::isfinite(S[i]) || !(S[i] > 0.0)) return fail(VRT_EINVAL, "S must be finite and > 0 everywhere");
-    return VRT_OK;
-}
-
 int upload(DevBuf<double> &d, const double *h, size_t count, hipStream_t st)
 {
     int rc = d.alloc(count);

@@ -19,6 +19,14 @@ namespace vrt {
 void set_error(const std::string &msg);
 int fail(int code, const std::string &msg);
 
+// Host checks of a session state handed back by the caller (*_set_source, *_set_state), before the device is touched:
+// S finite and > 0 (the criterion divides by it), populations finite and >= 0.  The three *_lambda_set_state entries call
+// check_state_pointers (a session and at least one of the two arrays; the session is not dereferenced), then check_state
+// on the arrays that were given: S (nlam, n), populations (n, 3).
+int check_source(const double *S, int64_t count);
+int check_state_pointers(const void *session, const double *S, const double *populations);
+int check_state(int64_t n, int64_t nlam, const double *S, const double *populations);
+
 #define VRT_HIP_TRY(expr)                                                                  \
     do {                                                                                   \
         hipError_t _e = (expr);                                                            \

@@ -512,6 +512,40 @@ int vrt_lambda_get(vrt_lambda *s, double *J, double *S, double *populations, dou
     });
 }
 
+int vrt_lambda_set_state(vrt_lambda *s, const double *S, const double *populations)
+{
+    int rc = check_state_pointers(s, S, populations);
+    if (rc || (rc = check_state(s->n, s->nlam, S, populations))) return rc;
+    return guarded([&] {
+        vrt_plan *p = s->p;
+        std::lock_guard<std::mutex> lock(p->mu);
+        if ((rc = use_device(p->g->device))) return rc;
+        hipStream_t st = p->g->stream;
+        const size_t n = (size_t)s->n, nS = n * (size_t)s->nlam;
+        // staged copies beside the session: it is untouched until every one of them is complete
+        DevBuf<double> tmp, S_up, S_down, pops;
+        if (S && s->native) {
+            // both plane sets, the padding wavelength of an odd nlam zero as at create
+            const size_t np = (size_t)vrt_plan_native_plane_count(p, s->nlam);
+            if ((rc = upload(tmp, S, nS, st)) || (rc = S_up.alloc(np)) || (rc = S_down.alloc(np))) return rc;
+            if ((rc = planes_to_native(p, s->nlam, s->nlam, tmp, S_up, S_down, st))) return rc;
+        } else if (S) {
+            if ((rc = upload(S_up, S, nS, st))) return rc;
+        }
+        if (populations && (rc = upload(pops, populations, 3 * n, st))) return rc;
+        VRT_HIP_TRY(hipStreamSynchronize(st));               // the host arrays may go after return
+        if (S && s->native) {
+            std::swap(s->d_S_nat[0], S_up);
+            std::swap(s->d_S_nat[1], S_down);
+        } else if (S)
+            std::swap(s->d_S_new, S_up);
+        if (populations) std::swap(s->d_pops, pops);
+        s->ng.have = 0;                                      // iterates of another state are no history of this one
+        s->ng.last_applied = 0;
+        return VRT_OK;
+    });
+}
+
 void vrt_lambda_destroy(vrt_lambda *s)
 {
     DeviceScope scope;

@@ -741,6 +741,68 @@ int vrt_multi_lambda_get(vrt_multi_lambda *s, double *J, double *S, double *popu
     });
 }
 
+int vrt_multi_lambda_set_state(vrt_multi_lambda *s, const double *S, const double *populations)
+{
+    int rc = check_state_pointers(s, S, populations);
+    if (rc || (rc = check_state(s->n, s->nlam, S, populations))) return rc;
+    return guarded([&] {
+        vrt_multi *mm = s->mm;
+        std::lock_guard<std::mutex> lock(mm->mu);
+        const int W = (int)mm->m.size();
+        const size_t n = (size_t)s->n;
+        // staged copies beside the session, one set per device: it is untouched until every one of them is complete
+        struct Staged {
+            int device = 0;
+            DevBuf<double> tmp, S_up, S_down, pops;
+            ~Staged() { (void)hipSetDevice(device); }        // then the members go, on their device
+        };
+        std::vector<Staged> staged((size_t)W);
+        std::vector<int> rcs((size_t)W, VRT_OK);
+        std::vector<std::string> errs((size_t)W);
+        auto work = [&](int d) {
+            Member &me = mm->m[(size_t)d];
+            const LambdaMember &l = s->lm[(size_t)d];
+            Staged &sg = staged[(size_t)d];
+            sg.device = me.device;
+            const int64_t nb = l.l1 - l.l0;
+            if (hipSetDevice(me.device) != hipSuccess) { rcs[(size_t)d] = VRT_ENODEVICE; errs[(size_t)d] = "hipSetDevice"; return; }
+            hipStream_t st = me.stream;
+            vrt_plan *p = me.plan_all.get();
+            std::lock_guard<std::mutex> plock(p->mu);
+            int rc = VRT_OK;
+            if (S && nb > 0 && s->native) {
+                // this block's columns into both plane sets, the padding wavelength of an odd block zero as at create
+                const size_t np = (size_t)vrt_plan_native_plane_count(p, nb);
+                rc = dupload_cols(sg.tmp, S, n, s->nlam, l.l0, l.l1, st);
+                if (!rc) rc = sg.S_up.alloc(np);
+                if (!rc) rc = sg.S_down.alloc(np);
+                if (!rc) rc = planes_to_native(p, nb, nb, sg.tmp, sg.S_up, sg.S_down, st);
+            } else if (S && nb > 0)
+                rc = dupload_cols(sg.S_up, S, n, s->nlam, l.l0, l.l1, st);
+            if (!rc && populations) rc = dupload(sg.pops, populations, 3 * n, st);       // every device holds a full copy
+            if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(VRT_ENODEVICE, "uploading the state failed");
+            if (rc) { rcs[(size_t)d] = rc; errs[(size_t)d] = vrt_last_error(); }
+        };
+        const bool ok = run_workers(W, work);
+        for (int d = 0; d < W; d++)
+            if (!ok || rcs[(size_t)d]) {
+                const int rc = ok ? rcs[(size_t)d] : VRT_ENOMEM;
+                return fail(rc, ok ? "device " + std::to_string(mm->m[(size_t)d].device) + ": " + errs[(size_t)d] : "out of host memory");
+            }
+        for (int d = 0; d < W; d++) {
+            LambdaMember &l = s->lm[(size_t)d];
+            Staged &sg = staged[(size_t)d];
+            if (S && l.l1 > l.l0 && s->native) {
+                std::swap(l.d_S_nat[0], sg.S_up);
+                std::swap(l.d_S_nat[1], sg.S_down);
+            } else if (S && l.l1 > l.l0)
+                std::swap(l.d_S_new, sg.S_up);
+            if (populations) std::swap(l.d_pops, sg.pops);
+        }
+        return (int)VRT_OK;
+    });
+}
+
 void vrt_multi_lambda_destroy(vrt_multi_lambda *s)
 {
     DeviceScope scope;

@@ -531,6 +531,37 @@ int vrt_regular_lambda_get(vrt_regular_lambda *s, double *J, double *S, double *
     });
 }
 
+int vrt_regular_lambda_set_state(vrt_regular_lambda *s, const double *S, const double *populations)
+{
+    int rc = check_state_pointers(s, S, populations);
+    if (rc || (rc = check_state(s->n, s->nlam, S, populations))) return rc;
+    return guarded([&] {
+        if ((rc = use_device(s->device))) return rc;
+        hipStream_t st = s->st;
+        const size_t n = (size_t)s->n, nS = n * (size_t)s->nlam;
+        // staged copies beside the session: it is untouched until every one of them is complete
+        DevBuf<double> S_new, S_pl, pops;
+        if (S) {
+            if ((rc = S_new.alloc(nS)) || (rc = S_pl.alloc(nS))) return rc;
+            VRT_HIP_TRY(hipMemcpyAsync(S_new, S, sizeof(double) * nS, hipMemcpyHostToDevice, st));
+            if ((rc = launch_to_planes(s->r, s->nlam, S_new, S_pl, st))) return rc;      // what the next solves read
+        }
+        if (populations) {
+            if ((rc = pops.alloc(3 * n))) return rc;
+            VRT_HIP_TRY(hipMemcpyAsync(pops, populations, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
+        }
+        VRT_HIP_TRY(hipStreamSynchronize(st));               // the host arrays may go after return
+        if (S) {
+            std::swap(s->d_S[s->sc], S_new);
+            std::swap(s->d_S_pl, S_pl);
+        }
+        if (populations) std::swap(s->d_pops[s->pc], pops);
+        s->ng.have = 0;                                      // iterates of another state are no history of this one
+        s->ng.last_applied = 0;
+        return VRT_OK;
+    });
+}
+
 void vrt_regular_lambda_destroy(vrt_regular_lambda *s)
 {
     DeviceScope scope;
