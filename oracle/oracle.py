@@ -78,6 +78,16 @@ def lib():
                                     _p_dbl, _p_i64, _c_i64, _p_i64, _p_i64, _c_i64, _p_i64,
                                     _c_i64, ctypes.c_int, _p_dbl]
         L.orc_J_voronoi.restype = ctypes.c_int
+        L.orc_delaunay_model.argtypes = [ctypes.c_int, _p_dbl, _p_dbl, _p_dbl, _p_dbl, _p_dbl, _p_i64,
+                                         _c_i64, _c_i64, _p_dbl, _p_i64, _c_i64, _p_i64, _c_i64,
+                                         ctypes.c_int, ctypes.c_int, _c_dbl, _p_dbl]
+        L.orc_delaunay_model.restype = ctypes.c_int
+        L.orc_J_voronoi_model.argtypes = [_c_i64, _p_dbl, _p_dbl, _p_dbl, _c_i64, _p_dbl, _p_dbl,
+                                          ctypes.c_int, _p_dbl, _p_dbl, _p_dbl, _p_i64, _c_i64, _c_i64,
+                                          _p_dbl, _p_i64, _c_i64, _p_i64, _p_i64, _c_i64, _p_i64,
+                                          _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dbl,
+                                          ctypes.c_int, _p_dbl, _p_dbl, _p_dbl, _p_dbl]
+        L.orc_J_voronoi_model.restype = ctypes.c_int
         L.orc_short_characteristics.argtypes = [ctypes.c_int, _p_dbl, _p_dbl, _p_dbl, _p_dbl, _p_dbl,
                                                 _p_dbl, _p_dbl, _c_i64, _c_i64, _c_i64, _c_i64, _p_dbl,
                                                 ctypes.POINTER(ctypes.c_int)]
@@ -294,6 +304,58 @@ def J_voronoi(weights, theta, phi, S, alpha, sites: OracleSites, I0_up=None, I0_
     if rc:
         raise RuntimeError("site without upwind neighbour")
     return J
+
+
+# ---- storage model of the fp32 storage path (vrt_oracle.c: orc_delaunay_model) ----------------------
+STORE = {"f64": 0, "layer": 1, "visit": 2}     # where I is rounded to float: never / per finished layer / per visit
+COEF = {"f64": 0, "f32": 1}                    # the per-site c, g_1, g_2 of a layer kept as float or not formed at all
+JSUM = {"f64": 0, "single": 1, "dir": 2}       # J: double sum / one float sum / float sums per direction, then combined
+
+
+def Delaunay_model(direction_sign, k, S, I_0, alpha, sites: OracleSites, n_sweeps: int = 3,
+                   store: str = "f64", coef: str = "f64", exp_eps: float = 0.0):
+    """Delaunay_upII (+1) / Delaunay_downII (-1) with the storage model; the defaults are _solve bit for bit.
+    Returned as float64 (with store != "f64" every value is exactly a float32)."""
+    k, S, I_0, alpha = _f64(k), _f64(S), _f64(I_0), _f64(alpha)
+    layers, perm = (sites.layers_up, sites.perm_up) if direction_sign > 0 else \
+        (sites.layers_down, sites.perm_down)
+    if I_0.size != layers[1] - 1:
+        raise ValueError(f"I_0 has length {I_0.size}, boundary layer has {layers[1] - 1} sites")
+    out = np.zeros(sites.n)
+    rc = lib().orc_delaunay_model(direction_sign, _d(k), _d(S), _d(I_0), _d(alpha), _d(sites.positions),
+                                  _i(sites.neighbours), sites.n, sites.D, _d(sites.delaunay_lines),
+                                  _i(layers), layers.size, _i(perm), n_sweeps, STORE[store], COEF[coef],
+                                  float(exp_eps), _d(out))
+    if rc:
+        raise RuntimeError("site without upwind neighbour")
+    return out
+
+
+def J_voronoi_model(weights, theta, phi, S, alpha, sites: OracleSites, I0_up=None, I0_down=None,
+                    n_sweeps: int = 3, nthreads: int = 1, store: str = "f64", coef: str = "f64",
+                    jsum: str = "f64", exp_eps: float = 0.0):
+    """J_voronoi with the storage model.  Returns (J, I, J_up, J_down): J (n, nlam), the per-angle
+    intensities I (n_angles, n, nlam; zero for a skipped angle) and the per-direction sums."""
+    weights, theta, phi, S = _f64(weights), _f64(theta), _f64(phi), _f64(S)
+    if S.ndim == 1:
+        S = S.reshape(-1, 1)
+    n, nlam = S.shape
+    alpha = _f64(alpha)
+    alpha_mode = {1: 0, 2: 1, 3: 2}[alpha.ndim]
+    I0u = _f64(I0_up) if I0_up is not None else None
+    I0d = _f64(I0_down) if I0_down is not None else None
+    J, Ju, Jd = np.zeros((n, nlam)), np.zeros((n, nlam)), np.zeros((n, nlam))
+    I = np.zeros((weights.size, n, nlam))
+    rc = lib().orc_J_voronoi_model(weights.size, _d(weights), _d(theta), _d(phi), nlam, _d(S), _d(alpha),
+                                   alpha_mode, _d(I0u), _d(I0d), _d(sites.positions),
+                                   _i(sites.neighbours), n, sites.D, _d(sites.delaunay_lines),
+                                   _i(sites.layers_up), sites.layers_up.size, _i(sites.perm_up),
+                                   _i(sites.layers_down), sites.layers_down.size, _i(sites.perm_down),
+                                   n_sweeps, nthreads, STORE[store], COEF[coef], float(exp_eps), JSUM[jsum],
+                                   _d(I), _d(Ju), _d(Jd), _d(J))
+    if rc:
+        raise RuntimeError("site without upwind neighbour")
+    return J, I, Ju, Jd
 
 
 def max_threads() -> int:

@@ -8,6 +8,7 @@ Follows: src/voronoi_utils.jl:93-130,138-174 (_sort_by_layer_*), :186-245 (calc_
 :484-500 (linear_weights); src/irregular_ray_tracing.jl:15-82,96-163 (Delaunay_upII/downII).
 """
 import math
+import struct
 
 
 def sort_by_layer(neighbours, n_sites, boundary):
@@ -156,4 +157,93 @@ def delaunay(up, k, S, I_0, alpha, positions, neighbours, lines, layers, perm, n
                     dtau = r * (alpha[idx] + alpha[u]) / 2
                     a, b, e = linear_weights(dtau)
                     I[idx] += (e * I[u] + a * S[u] + b * S[idx]) * w[rn]
+    return I
+
+
+# ---- storage model of the product's fp32 storage path (second transcription of orc_delaunay_model) ----
+# Written from the description in vrt_oracle.c, not from its code: the geometry of a site (upwind ids, weights,
+# path lengths) is hoisted per layer, the sweeps run on those terms.  Every floating-point expression keeps the
+# association of the reference's line (irregular_ray_tracing.jl:66-76, functions.jl:484-500), with squares
+# written as products, so that the two transcriptions can be compared bit for bit.
+def through_float(v):
+    """double -> nearest float32 (ties to even, gradual underflow) -> double"""
+    return struct.unpack("f", struct.pack("f", v))[0]
+
+
+def linear_weights_eps(dtau, exp_eps=0.0):
+    """linear_weights with every exp(-dtau) multiplied by (1 + exp_eps)"""
+    if dtau < 5e-4:
+        e = 1 - dtau + 0.5 * (dtau * dtau)
+        a = dtau * (1 / 2 - dtau / 3)
+        b = dtau * (1 / 2 - dtau / 6)
+    elif dtau > 50:
+        e = 0.0
+        a = 1 / dtau
+        b = 1.0 - a
+    else:
+        e = math.exp(-dtau) * (1.0 + exp_eps)
+        a = (1 - e) / dtau - e
+        b = 1 - a - e
+    return a, b, e
+
+
+def delaunay_model(up, k, S, I_0, alpha, positions, neighbours, lines, layers, perm, n_sweeps,
+                   store="f64", coef="f64", exp_eps=0.0):
+    """Delaunay_upII / Delaunay_downII with the intensities rounded to float32 never (store "f64"), when a
+    layer's last sweep is done ("layer") or at every site update ("visit"); coef "f32": the constant term and
+    the two in-layer couplings of a site are formed once per layer, rounded to float32, and reused by the
+    sweeps.  All sequences 1-based with a dummy first element, as in delaunay()."""
+    p = 7.0
+    n = len(S) - 1
+    I = [0.0] * (n + 1)
+    rank = [0] * (n + 1)
+    for t in range(1, n + 1):
+        rank[perm[t]] = t
+    for t in range(1, layers[2]):
+        I[perm[t]] = I_0[t]                      # the boundary layer takes I_0 as given
+    for layer in range(2, len(layers) - 1):
+        lo, hi = layers[layer], layers[layer + 1]
+        terms = {}
+        for i in range(lo, hi):
+            idx = perm[i]
+            n_nb = neighbours[idx][1]
+            nbs = [0] + [neighbours[idx][j] for j in range(2, n_nb + 2)]
+            dots, upwind = smallest_angle(idx, nbs, k, lines)
+            s = dots[1] ** p + dots[2] ** p
+            site = []
+            for rn in (1, 2):
+                u = upwind[rn]
+                dz = positions[idx][1] - positions[u][1]
+                dx = positions[idx][2] - positions[u][2]
+                dy = positions[idx][3] - positions[u][3]
+                r = math.sqrt((dz * dz + dx * dx) + dy * dy)
+                a, b, e = linear_weights_eps(r * (alpha[idx] + alpha[u]) / 2, exp_eps)
+                site.append((u, dots[rn] ** p / s, a, b, e))
+            terms[idx] = site
+        kept = {}
+        if coef == "f32":
+            for idx, site in terms.items():
+                t, g = [], []
+                for u, w, a, b, e in site:
+                    if rank[u] < lo:             # earlier layer: its intensity is final
+                        t.append((e * I[u] + a * S[u] + b * S[idx]) * w)
+                    else:
+                        t.append((a * S[u] + b * S[idx]) * w)
+                    g.append(through_float(e * w if lo <= rank[u] < hi else 0.0))
+                kept[idx] = (through_float(t[0] + t[1]), g[0], g[1])
+        for _sweep in range(n_sweeps):
+            for i in (range(lo, hi) if up else range(hi - 1, lo - 1, -1)):
+                idx = perm[i]
+                site = terms[idx]
+                if coef == "f32":
+                    c, g1, g2 = kept[idx]
+                    v = c + g1 * I[site[0][0]] + g2 * I[site[1][0]]
+                else:
+                    v = 0.0
+                    for u, w, a, b, e in site:
+                        v += (e * I[u] + a * S[u] + b * S[idx]) * w
+                I[idx] = through_float(v) if store == "visit" else v
+        if store == "layer":
+            for i in range(lo, hi):
+                I[perm[i]] = through_float(I[perm[i]])
     return I

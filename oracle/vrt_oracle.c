@@ -422,6 +422,214 @@ int orc_J_voronoi(i64 n_angles, const double *weights, const double *theta, cons
     return rc_all;
 }
 
+/* ==========================================================================================
+ * STORAGE MODEL of the product's fp32 storage path (S, α, I_0, I, J held as float, arithmetic
+ * fp64).  Not part of the reference: the sweep of orc_delaunay with the intensities -- and,
+ * optionally, the per-site numbers the sweeps reuse -- passed through float at the places where
+ * a device path keeps them as float, so that a test can say WHERE a kernel rounds, not only that
+ * it stays near the fp64 result.  Two independent switches:
+ *   store  ORC_STORE_F64    I is never rounded
+ *          ORC_STORE_LAYER  I of a BFS layer is rounded once, when the layer's last sweep is done:
+ *                           a site sees float intensities of earlier layers and unrounded doubles
+ *                           of its own layer (the patch kernels: fp64 tile, one float store)
+ *          ORC_STORE_VISIT  I is rounded at every site update (a float tile, or one launch per
+ *                           dependency level with float I in memory)
+ *   coef_f32  0: a visit evaluates the reference's expression, as orc_delaunay does
+ *             1: per layer and site, c = t_1 + t_2 with t_r = ((e_r I_ur + a_r S_ur) + b_r S_c) w_r
+ *                for an upwind in an EARLIER layer, (a_r S_ur + b_r S_c) w_r otherwise, and
+ *                g_r = e_r w_r for an upwind in the site's OWN layer (else 0) are formed once,
+ *                rounded to float, and every visit is (c + g_1 I_u1) + g_2 I_u2 (the layer-step
+ *                path's hand-off between its coefficient and its level kernel)
+ * exp_eps multiplies every exp(-Δτ) by (1 + exp_eps): a copy of the model with a slightly
+ * different exponential, to measure how often a float rounding boundary is straddled.
+ * What the reference keeps on purpose stays: the boundary layer takes I_0 as given, later-layer
+ * reads are 0, the never-visited last site is 0.
+ * (store, coef_f32, exp_eps) = (F64, 0, 0) is orc_delaunay bit for bit (tests/test_f32_model_host.py).
+ * ========================================================================================== */
+enum { ORC_STORE_F64 = 0, ORC_STORE_LAYER = 1, ORC_STORE_VISIT = 2 };
+enum { ORC_JSUM_F64 = 0, ORC_JSUM_SINGLE = 1, ORC_JSUM_DIR = 2 };
+
+static double orc_through_float(double v)
+{
+    return (double)(float)v;      /* round to nearest even, gradual underflow */
+}
+
+static void orc_linear_weights_eps(double dtau, double exp_eps, double *a, double *b, double *e)
+{
+    orc_linear_weights(dtau, a, b, e);
+    if (exp_eps != 0.0 && !(dtau < 5e-4) && !(dtau > 50)) {
+        *e = exp(-dtau) * (1.0 + exp_eps);
+        *a = (1 - *e) / dtau - *e;
+        *b = 1 - *a - *e;
+    }
+}
+
+int orc_delaunay_model(int dir, const double *k, const double *S, const double *I0,
+                       const double *alpha, const double *pos, const i64 *nbr, i64 n, i64 D,
+                       const double *lines, const i64 *layers, i64 nl, const i64 *perm,
+                       i64 n_sweeps, int store, int coef_f32, double exp_eps, double *I)
+{
+    const double p = 7.0;
+    for (i64 i = 0; i < n; i++) I[i] = 0.0;
+    i64 lower = layers[1] - 1;
+    for (i64 i = 0; i < lower; i++) I[perm[i] - 1] = I0[i];      /* I_0 as given */
+    i64 *rank = (i64 *)malloc(sizeof(i64) * (size_t)n);           /* site -> 1-based sweep position */
+    for (i64 t = 0; t < n; t++) rank[perm[t] - 1] = t + 1;
+    double *c = NULL, *g = NULL;
+    if (coef_f32) {
+        c = (double *)malloc(sizeof(double) * (size_t)n);
+        g = (double *)malloc(sizeof(double) * 2 * (size_t)n);
+    }
+    int rc = 0;
+    for (i64 layer = 2; layer <= nl - 1; layer++) {
+        i64 lo = layers[layer - 1], hi = layers[layer];           /* positions lo .. hi-1 */
+        if (coef_f32) {
+            for (i64 posn = lo; posn < hi; posn++) {
+                i64 idx = perm[posn - 1] - 1;
+                double dots[2]; i64 up[2];
+                c[idx] = g[2 * idx] = g[2 * idx + 1] = 0.0;
+                if (orc_smallest_angle(idx, nbr, n, D, lines, k, dots, up)) { rc = -1; continue; }
+                double p1 = pow(dots[0], p), p2 = pow(dots[1], p);
+                double sum = p1 + p2;
+                double w[2] = { p1 / sum, p2 / sum };
+                double t[2];
+                for (int rn = 0; rn < 2; rn++) {
+                    i64 u = up[rn] - 1;
+                    double dz = pos[3 * idx + 0] - pos[3 * u + 0];
+                    double dx = pos[3 * idx + 1] - pos[3 * u + 1];
+                    double dy = pos[3 * idx + 2] - pos[3 * u + 2];
+                    double r = sqrt((dz * dz + dx * dx) + dy * dy);
+                    double dtau = r * (alpha[idx] + alpha[u]) / 2;
+                    double a, b, e;
+                    orc_linear_weights_eps(dtau, exp_eps, &a, &b, &e);
+                    int early = rank[u] < lo, inl = rank[u] >= lo && rank[u] < hi;
+                    t[rn] = early ? ((e * I[u] + a * S[u]) + b * S[idx]) * w[rn]
+                                  : (a * S[u] + b * S[idx]) * w[rn];
+                    g[2 * idx + rn] = orc_through_float(inl ? e * w[rn] : 0.0);
+                }
+                c[idx] = orc_through_float(t[0] + t[1]);
+            }
+        }
+        for (i64 sweep = 0; sweep < n_sweeps; sweep++) {
+            i64 cnt = hi - lo;
+            for (i64 t = 0; t < cnt; t++) {
+                i64 posn = (dir > 0) ? (lo + t) : (hi - 1 - t);
+                i64 idx = perm[posn - 1] - 1;
+                double dots[2]; i64 up[2];
+                if (orc_smallest_angle(idx, nbr, n, D, lines, k, dots, up)) { rc = -1; continue; }
+                double v;
+                if (coef_f32) {
+                    /* a coupling of 0 (upwind outside the layer) multiplies a finite value */
+                    v = (c[idx] + g[2 * idx] * I[up[0] - 1]) + g[2 * idx + 1] * I[up[1] - 1];
+                } else {
+                    double p1 = pow(dots[0], p), p2 = pow(dots[1], p);
+                    double sum = p1 + p2;
+                    double w[2] = { p1 / sum, p2 / sum };
+                    v = 0.0;
+                    for (int rn = 0; rn < 2; rn++) {
+                        i64 u = up[rn] - 1;
+                        double dz = pos[3 * idx + 0] - pos[3 * u + 0];
+                        double dx = pos[3 * idx + 1] - pos[3 * u + 1];
+                        double dy = pos[3 * idx + 2] - pos[3 * u + 2];
+                        double r = sqrt((dz * dz + dx * dx) + dy * dy);
+                        double dtau = r * (alpha[idx] + alpha[u]) / 2;
+                        double a, b, e;
+                        orc_linear_weights_eps(dtau, exp_eps, &a, &b, &e);
+                        v += ((e * I[u] + a * S[u]) + b * S[idx]) * w[rn];
+                    }
+                }
+                I[idx] = store == ORC_STORE_VISIT ? orc_through_float(v) : v;
+            }
+        }
+        if (store == ORC_STORE_LAYER)
+            for (i64 posn = lo; posn < hi; posn++) {
+                i64 idx = perm[posn - 1] - 1;
+                I[idx] = orc_through_float(I[idx]);
+            }
+    }
+    free(rank); free(c); free(g);
+    return rc;
+}
+
+/* J_λ_voronoi with the storage model: orc_J_voronoi's loops around orc_delaunay_model, and J formed
+ * from the (stored) intensities the way the device forms it:
+ *   ORC_JSUM_F64     J = Σ_angles w I in double, the reference's angle order (= orc_J_voronoi)
+ *   ORC_JSUM_SINGLE  the same sum, rounded to float once (one reduction over every angle)
+ *   ORC_JSUM_DIR     per direction J_d = float(Σ_{angles of d} w I), the reference's order inside the
+ *                    direction, then J = float(J_up + J_down) (the layer paths: sweep-order float
+ *                    planes per direction, combined afterwards)
+ * I_out [n_angles][n][nlam] (skipped angles stay 0), J_up / J_down [n][nlam]: optional outputs. */
+int orc_J_voronoi_model(i64 n_angles, const double *weights, const double *theta, const double *phi,
+                        i64 nlam, const double *S, const double *alpha, int alpha_mode,
+                        const double *I0_up, const double *I0_down,
+                        const double *pos, const i64 *nbr, i64 n, i64 D, const double *lines,
+                        const i64 *layers_up, i64 nl_up, const i64 *perm_up,
+                        const i64 *layers_down, i64 nl_down, const i64 *perm_down,
+                        i64 n_sweeps, int nthreads, int store, int coef_f32, double exp_eps, int jsum,
+                        double *I_out, double *J_up, double *J_down, double *J)
+{
+    double *Jd[2];
+    Jd[0] = (double *)calloc((size_t)(n * nlam), sizeof(double));
+    Jd[1] = (double *)calloc((size_t)(n * nlam), sizeof(double));
+    for (i64 t = 0; t < n * nlam; t++) J[t] = 0.0;
+    if (I_out) for (i64 t = 0; t < n_angles * n * nlam; t++) I_out[t] = 0.0;
+    int rc_all = 0;
+    if (nthreads < 1) nthreads = 1;
+    i64 n1_up = layers_up[1] - 1, n1_down = layers_down[1] - 1;
+    i64 n1_max = n1_up > n1_down ? n1_up : n1_down;
+    for (i64 a = 0; a < n_angles; a++) {
+        double k[3];
+        orc_direction(theta[a], phi[a], k);
+        int up = theta[a] > 90, down = theta[a] < 90;
+        if (!up && !down) continue;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static) num_threads(nthreads)
+#endif
+        for (i64 l = 0; l < nlam; l++) {
+            double *Sl = (double *)malloc(sizeof(double) * (size_t)n);
+            double *al = (double *)malloc(sizeof(double) * (size_t)n);
+            double *Il = (double *)malloc(sizeof(double) * (size_t)n);
+            double *I0 = (double *)calloc((size_t)(n1_max > 0 ? n1_max : 1), sizeof(double));
+            for (i64 i = 0; i < n; i++) Sl[i] = S[l + nlam * i];
+            if (alpha_mode == 0)      for (i64 i = 0; i < n; i++) al[i] = alpha[i];
+            else if (alpha_mode == 1) for (i64 i = 0; i < n; i++) al[i] = alpha[l + nlam * i];
+            else for (i64 i = 0; i < n; i++) al[i] = alpha[(size_t)a * n * nlam + l + nlam * i];
+            const double *I0_dir = up ? I0_up : I0_down;
+            i64 n1 = up ? n1_up : n1_down;
+            if (I0_dir) for (i64 i = 0; i < n1; i++) I0[i] = I0_dir[l + nlam * i];
+            int rc = orc_delaunay_model(up ? +1 : -1, k, Sl, I0, al, pos, nbr, n, D, lines,
+                                        up ? layers_up : layers_down, up ? nl_up : nl_down,
+                                        up ? perm_up : perm_down, n_sweeps, store, coef_f32, exp_eps, Il);
+            if (rc) {
+#ifdef _OPENMP
+#pragma omp atomic write
+#endif
+                rc_all = -1;
+            }
+            double w = weights[a];
+            double *Jdir = Jd[up ? 0 : 1];
+            for (i64 i = 0; i < n; i++) {
+                J[l + nlam * i] += w * Il[i];
+                Jdir[l + nlam * i] += w * Il[i];
+                if (I_out) I_out[((size_t)a * n + i) * nlam + l] = Il[i];
+            }
+            free(Sl); free(al); free(Il); free(I0);
+        }
+    }
+    for (i64 t = 0; t < n * nlam; t++) {
+        if (jsum != ORC_JSUM_F64) {
+            Jd[0][t] = orc_through_float(Jd[0][t]);
+            Jd[1][t] = orc_through_float(Jd[1][t]);
+        }
+        if (jsum == ORC_JSUM_SINGLE) J[t] = orc_through_float(J[t]);
+        else if (jsum == ORC_JSUM_DIR) J[t] = orc_through_float(Jd[0][t] + Jd[1][t]);
+        if (J_up) J_up[t] = Jd[0][t];
+        if (J_down) J_down[t] = Jd[1][t];
+    }
+    free(Jd[0]); free(Jd[1]);
+    return rc_all;
+}
+
 int orc_max_threads(void)
 {
 #ifdef _OPENMP
