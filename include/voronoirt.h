@@ -761,7 +761,7 @@ int vrt_multi_lambda_set_state(vrt_multi_lambda *s, const double *S, const doubl
  * There is NO multi-device continuum session: vrt_multi_lambda_* splits wavelength blocks over the devices, and the one
  * wavelength of a continuum run cannot be split that way.
  *
- * Accelerated Λ-iteration (ALI) with a diagonal approximate operator (Olson, Auer & Buchler 1986), Voronoi session only.
+ * Accelerated Λ-iteration (ALI) with a diagonal approximate operator (Olson, Auer & Buchler 1986), on both grids.
  * Plain Λ-iteration converges like 1 - ε because in thick cells most of J at a site is the site's own S coming straight
  * back; the local operator Λ* is that part, and the update solves for it instead of lagging behind it.  Ng acceleration
  * (above) needs no approximate operator; this is the scheme that has one, and the two compose.
@@ -791,9 +791,33 @@ int vrt_multi_lambda_set_state(vrt_multi_lambda *s, const double *S, const doubl
  *   S the ALI update produced, and the returned scalar is that of the ALI update, formed before any extrapolation.  Both
  *   layouts give the same S, J and scalar bit for bit.  A session that never calls it allocates and runs nothing extra.
  * vrt_continuum_get_operator: *op, and -- when on and diag is not NULL -- Λ* (nlam, n) Julia dims.
- * Out of scope: the regular-grid continuum session (its six plane kinds each need their own centre coefficient), the
- * line sessions (their update goes through the rate equations and needs a preconditioned statistical equilibrium), and
- * any multi-device form. */
+ * The raster: vrt_regular_lambda_diagonal_dev / vrt_regular_lambda_diagonal / vrt_regular_continuum_select_operator /
+ * _get_operator are the same four entries on a vrt_regular (directions, dirs and weights per angle as
+ * vrt_regular_continuum_create, whose direction checks apply; alpha and diag (nlam, n) Julia dims over all nz nx ny
+ * points, leading dimension ld).  There
+ *     Λ*[p,l] = Σ_a weights[a] · c_a(p,l),    c_a = the coefficient of S[p] in I_a[p] after ONE sweep of the raster solve
+ *   summed over the angles in quadrature order (dirs = 0 skipped), from the reference's arithmetic (bilinear, linear_weights)
+ *   with Δτ = r (α_c + α_u) / 2, the cut argmin(r_z, r_x, r_y) and the interpolation indices exactly as
+ *   vrt_regular_execute_dev forms them for the point's plane:
+ *     xy plane:                  c = b(Δτ)          (S_u and I_u come from the upwind plane)
+ *     yz plane, xz plane (up):   c = b(Δτ) + e(Δτ) · v · a(Δτ_q) · u      the second term is the point's S coming back through
+ *                                the row marched just before it, q: u the weight of the point in q's interpolated S_u, v that
+ *                                of q in the point's I_u (the carried row); 0 in the first row of the march
+ *     xz plane (down):           c = e(Δτ) · v · a(Δτ_q) · u              xz_down_ray reads its centre S and α from the plane
+ *                                above, so the point's own S has no b term there
+ *   c_a = 0 on the boundary plane of the angle's direction (iz = 0 up, iz = nz - 1 down: I is I_0) and at every ghost point
+ *   (ix = 0, nx - 1 or iy = 0, ny - 1: I there is a copy of an interior point's I), so Λ* is exactly 0 on the ghost border.
+ *   This is the diagonal of the one-sweep Λ: it does not depend on n_sweeps, and 0 <= Λ* <= the diagonal for any number of
+ *   sweeps.  More than 64 active angles: VRT_EINVAL.  The same inputs give the same bits.  The _dev form runs on the null
+ *   stream and returns when Λ* is written; padding columns are neither read nor written.  The host form also checks that α
+ *   is finite and > 0.  Both check NULL pointers, nlam >= 1, ld >= nlam and the directions before the device is touched.
+ *   vrt_regular_continuum_select_operator / _get_operator: the contract of the Voronoi entries (Λ* from the session's α, min
+ *   den checked before anything is moved in, a change drops the Ng history, _set_source keeps the operator, a session that
+ *   never calls it allocates and runs nothing extra); the update is vrt_continuum_ali_update_dev's kernel.
+ *   The setter is named _select_operator here, not _set_operator.
+ * Out of scope: the regular-grid continuum session with the exact diagonal of its n_sweeps-sweep operator (its Λ* is the
+ * one-sweep diagonal, a lower bound of it), the line sessions (their update goes through the rate equations and needs a
+ * preconditioned statistical equilibrium), and any multi-device form. */
 typedef struct vrt_continuum vrt_continuum;
 typedef struct vrt_regular_continuum vrt_regular_continuum;
 typedef struct vrt_continuum_case {
@@ -833,6 +857,14 @@ int vrt_continuum_ali_update_dev(vrt_grid *g, int64_t nlam, int64_t ld, const do
                                  double *dS_new, double *max_rel_change, int64_t *n_thick, void *stream);
 int vrt_continuum_set_operator(vrt_continuum *s, int op);
 int vrt_continuum_get_operator(vrt_continuum *s, int *op, double *diag /* (nlam, n) Julia dims, may be NULL */);
+int vrt_regular_lambda_diagonal_dev(vrt_regular *r, int64_t n_angles, const double *k, const int *dirs,
+                                    const double *weights, int64_t nlam, int64_t ld, const double *d_alpha,
+                                    double *d_diag);
+int vrt_regular_lambda_diagonal(vrt_regular *r, int64_t n_angles, const double *k, const int *dirs,
+                                const double *weights, int64_t nlam, int64_t ld, const double *alpha, double *diag);
+int vrt_regular_continuum_select_operator(vrt_regular_continuum *s, int op);
+int vrt_regular_continuum_get_operator(vrt_regular_continuum *s, int *op,
+                                       double *diag /* (nlam, n) Julia dims, may be NULL */);
 
 /* ---- emergent spectra: opacity / source function, top-plane intensity, tau = 1 heights ------------------------------
  * The last step of a reference study (write_top_intensity, write_tau_unity and plotter, src/plot_utils.jl:61-140,

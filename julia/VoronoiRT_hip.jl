@@ -623,14 +623,16 @@ function Λ_continuum(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, 
 end
 
 """
-    Λ_continuum_regular(ϵ, maxiter, atmos, quadrature; ng=nothing, S0=nothing) -> (J_new, S_new, α_cont)
+    Λ_continuum_regular(ϵ, maxiter, atmos, quadrature; ng=nothing, S0=nothing, operator=nothing) -> (J_new, S_new, α_cont)
 
 The reference's continuum Λ_regular (src/lambda_continuum.jl:58-107) on the device (vrt_regular_continuum_*); `atmos` is
 the atmosphere the reference iterates on, every point of it a point of the loop.  (nz, nx, ny) arrays are
-vrt_continuum_case's (1, n) with n = nz nx ny.  Keywords as `Λ_continuum`.  Unrun.
+vrt_continuum_case's (1, n) with n = nz nx ny.  Keywords as `Λ_continuum`, `operator = :diagonal`
+(vrt_regular_continuum_select_operator) included.  Unrun.
 """
 function Λ_continuum_regular(ϵ::AbstractFloat, maxiter::Integer, atmos, quadrature::String;
-                             ng::Union{Nothing,Tuple{Int,Int}}=nothing, S0=nothing)
+                             ng::Union{Nothing,Tuple{Int,Int}}=nothing, S0=nothing, operator::Union{Nothing,Symbol}=nothing)
+    operator === nothing || operator === :diagonal || throw(ArgumentError("operator must be nothing or :diagonal"))
     λ = 500u"nm"
     LTE_pops = VoronoiRT.LTE_populations(atmos)
     α_s = VoronoiRT.α_scattering.(λ, atmos.electron_density * 1.0, LTE_pops[:, :, :, 1])
@@ -665,6 +667,7 @@ function Λ_continuum_regular(ϵ::AbstractFloat, maxiter::Integer, atmos, quadra
         S_in = Array{Float64,3}(ustrip.(I_unit, S0))
         check(ccall((:vrt_regular_continuum_set_source, libvrt), Cint, (Ptr{Cvoid}, Ptr{Float64}), ses[], S_in))
     end
+    operator === :diagonal && check(ccall((:vrt_regular_continuum_select_operator, libvrt), Cint, (Ptr{Cvoid}, Cint), ses[], 1))
     ng !== nothing && check(ccall((:vrt_regular_continuum_set_acceleration, libvrt), Cint, (Ptr{Cvoid}, Cint, Cint, Cint),
                                   ses[], 2, ng[1], ng[2]))
     J = Array{Float64,3}(undef, nz, nx, ny); S = Array{Float64,3}(undef, nz, nx, ny)
@@ -676,6 +679,37 @@ function Λ_continuum_regular(ϵ::AbstractFloat, maxiter::Integer, atmos, quadra
     ccall((:vrt_regular_continuum_destroy, libvrt), Cvoid, (Ptr{Cvoid},), ses[])
     ccall((:vrt_regular_destroy, libvrt), Cvoid, (Ptr{Cvoid},), reg[])
     return J * I_unit, S * I_unit, α_cont
+end
+
+"""
+    lambda_diagonal_regular(z, x, y, α, quadrature) -> Λ*
+
+The diagonal approximate operator of accelerated Λ-iteration on a raster (vrt_regular_lambda_diagonal): per point the
+coefficient of its own S in its intensity after one sweep of the raster solve, summed over the quadrature; 0 on the ghost
+border.  z, x, y: the ghosted axes in metres; α (nz, nx, ny) in m^-1, finite and > 0.  Unrun.
+"""
+function lambda_diagonal_regular(z::Vector{Float64}, x::Vector{Float64}, y::Vector{Float64}, α::Array{Float64,3},
+                                 quadrature::String)
+    nz, nx, ny = size(α)
+    (nz, nx, ny) == (length(z), length(x), length(y)) || throw(ArgumentError("α must be (nz, nx, ny) of the axes"))
+    weights, θ_array, ϕ_array, n_angles = read_quadrature(quadrature)
+    k = Matrix{Float64}(undef, 3, n_angles)
+    for i in 1:n_angles
+        k[:, i] = direction(θ_array[i], ϕ_array[i])
+    end
+    dirs = Cint[θ > 90 ? 1 : (θ < 90 ? -1 : 0) for θ in θ_array]
+    w = Vector{Float64}(weights)
+    reg = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:vrt_regular_create, libvrt), Cint,
+                (Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ref{Ptr{Cvoid}}),
+                nz, nx, ny, z, x, y, 0, reg))
+    diag = zeros(Float64, nz, nx, ny)
+    rc = ccall((:vrt_regular_lambda_diagonal, libvrt), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Cint}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}),
+               reg[], n_angles, k, dirs, w, 1, 1, α, diag)
+    ccall((:vrt_regular_destroy, libvrt), Cvoid, (Ptr{Cvoid},), reg[])
+    check(rc)
+    return diag
 end
 
 # ---- single solves: src/irregular_ray_tracing.jl:15-20, :96-101 ----------------------------------

@@ -14,7 +14,12 @@ Median and min..max over the repeats after warm-up; the two iterates are measure
 of one process.  `--plain-only` measures the plain iterate alone and needs no new entry: run it with VRT_LIB_PATH pointing
 at a build of the parent commit for the A/B.  The probe ends itself after --limit seconds.
 
+`--regular`: the same three figures for the raster session (vrt_regular_continuum_select_operator) at bench_regular.py's
+raster size (--shape 215 128 128 interior points, ghosted to 215 x 130 x 130) x ul7n12 x --nlam; the two update kernels
+are those of the Voronoi session and are not timed again.
+
     python tools/ali_probe.py [--a 37 --c 90] [--nlam 1] [--reps 40] [--blocks 3] [--plain-only] [--json out.json]
+    python tools/ali_probe.py --regular [--shape 215 128 128] [--nlam 1] [--reps 10] [--blocks 3] [--plain-only]
 """
 import argparse
 import ctypes
@@ -41,8 +46,91 @@ ap.add_argument("--blocks", type=int, default=3, help="alternating blocks of --r
 ap.add_argument("--plain-only", action="store_true", help="the plain iterate alone (works with a library of the parent commit)")
 ap.add_argument("--limit", type=int, default=240, help="seconds after which the probe ends itself")
 ap.add_argument("--json", default="")
+ap.add_argument("--regular", action="store_true", help="the raster session instead of the Voronoi one")
+ap.add_argument("--shape", type=int, nargs=3, default=[215, 128, 128], help="--regular: nz nx ny interior points")
 args = ap.parse_args()
 signal.alarm(args.limit)
+
+
+def stats(xs):
+    return {"median_ms": statistics.median(xs), "min_ms": min(xs), "max_ms": max(xs), "reps": len(xs)}
+
+
+def regular_probe():
+    nz, nx, ny = args.shape
+    z, x, y, kw = synth.regular_continuum_case(nz, nx, ny, 5, args.nlam)
+    case = vrt.ContinuumCase(**kw)
+    cc = case.c_struct()
+    quad = "ul7n12.dat"
+    w, k, dirs = api._regular_directions(quad)
+    L = _lib.load()
+    solvers = []
+
+    def session():
+        solver = api._regular_solver(z, x, y, case.n, 0)         # (a session's chunk workspace lives on its solver)
+        solvers.append(solver)
+        h = ctypes.c_void_p()
+        api.check(L.vrt_regular_continuum_create(solver._h, k.shape[0], k.ctypes.data_as(_lib.p_dbl),
+                                                 dirs.ctypes.data_as(_lib.p_int), w.ctypes.data_as(_lib.p_dbl), ctypes.byref(cc), 3,
+                                                 ctypes.byref(h)))
+        return h
+
+    def iterates(h, reps, out):
+        d = ctypes.c_double()
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            api.check(L.vrt_regular_continuum_iterate(h, ctypes.byref(d)))
+            out.append(1e3 * (time.perf_counter() - t0))
+        return d.value
+
+    res = {"grid": "regular", "points": case.n, "shape_ghosted": [int(z.size), int(x.size), int(y.size)], "nlam": args.nlam,
+           "quadrature": quad, "lib": os.path.basename(_lib.LIB_PATH), "plain_only": args.plain_only}
+    plain = session()
+    iterates(plain, 2, [])                                     # warm-up
+    t_plain, t_ali, t_set = [], [], []
+    if args.plain_only:
+        for _ in range(args.blocks):
+            iterates(plain, args.reps, t_plain)
+    else:
+        for _ in range(4):                                     # the one-time cost, on fresh sessions
+            h = session()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            api.check(L.vrt_regular_continuum_select_operator(h, 1))
+            t_set.append(1e3 * (time.perf_counter() - t0))
+            L.vrt_regular_continuum_destroy(h)
+            solvers.pop().close()
+        ali = session()
+        api.check(L.vrt_regular_continuum_select_operator(ali, 1))
+        iterates(ali, 2, [])
+        for _ in range(args.blocks):
+            iterates(plain, args.reps, t_plain)
+            res["ali_last_scalar"] = iterates(ali, args.reps, t_ali)
+        res["ali_iterate_wall"] = stats(t_ali)
+        res["set_operator_wall"] = stats(t_set[1:])
+        res["set_operator_first_ms"] = t_set[0]
+        res["ali_minus_plain_iterate_ms"] = res["ali_iterate_wall"]["median_ms"] - statistics.median(t_plain)
+        L.vrt_regular_continuum_destroy(ali)
+    res["plain_iterate_wall"] = stats(t_plain)
+    L.vrt_regular_continuum_destroy(plain)
+    for solver in solvers:
+        solver.close()
+    return res
+
+
+def finish(res):
+    print(json.dumps(res))
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+if args.regular:
+    finish(regular_probe())
+    sys.exit(0)
 
 pos, nbr, bounds = synth.bcc_grid(args.a, args.c, seed=2022)
 sites = vrt.VoronoiSites(pos, nbr, bounds, device=0)
@@ -54,10 +142,6 @@ L = _lib.load()
 case = vrt.ContinuumCase(**kw)
 cc = case.c_struct()
 wd = np.ascontiguousarray(w, dtype=np.float64)
-
-
-def stats(xs):
-    return {"median_ms": statistics.median(xs), "min_ms": min(xs), "max_ms": max(xs), "reps": len(xs)}
 
 
 def session():
@@ -124,9 +208,4 @@ else:
 res["plain_iterate_wall"] = stats(t_plain)
 L.vrt_continuum_destroy(plain)
 
-print(json.dumps(res))
-if args.json:
-    os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-    with open(args.json, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+finish(res)

@@ -211,6 +211,10 @@ PROTOTYPES = {
     "vrt_continuum_ali_update_dev": (ctypes.c_int, [vp, c_i64, c_i64, vp, vp, vp, vp, c_dbl, vp, vp, p_dbl, p_i64, vp]),
     "vrt_continuum_set_operator": (ctypes.c_int, [vp, ctypes.c_int]),
     "vrt_continuum_get_operator": (ctypes.c_int, [vp, p_int, p_dbl]),
+    "vrt_regular_lambda_diagonal_dev": (ctypes.c_int, [vp, c_i64, p_dbl, p_int, p_dbl, c_i64, c_i64, vp, vp]),
+    "vrt_regular_lambda_diagonal": (ctypes.c_int, [vp, c_i64, p_dbl, p_int, p_dbl, c_i64, c_i64, p_dbl, p_dbl]),
+    "vrt_regular_continuum_select_operator": (ctypes.c_int, [vp, ctypes.c_int]),
+    "vrt_regular_continuum_get_operator": (ctypes.c_int, [vp, p_int, p_dbl]),
     "vrt_delaunay_up": (ctypes.c_int, [vp, p_dbl, p_dbl, p_dbl, c_i64, p_dbl, ctypes.c_int, p_dbl]),
     "vrt_delaunay_down": (ctypes.c_int, [vp, p_dbl, p_dbl, p_dbl, c_i64, p_dbl, ctypes.c_int, p_dbl]),
 }

@@ -1761,7 +1761,8 @@ def _continuum_loop(L, prefix: str, h, case: ContinuumCase, eps_conv: float, max
         S0 = _f64(S0).reshape(case.n, case.nlam)
         check(fn("set_source")(h, _d(S0)))
     if operator is not None:
-        check(fn("set_operator")(h, _OPERATORS[operator]))
+        # (the raster session's setter is vrt_regular_continuum_select_operator)
+        check(fn("select_operator" if prefix == "vrt_regular_continuum_" else "set_operator")(h, _OPERATORS[operator]))
     if ng is not None:
         check(fn("set_acceleration")(h, 2, *_ng_settings(ng)))
     while diff > eps_conv and i < maxiter:                     # criterion: diff > ϵ && i < maxiter, :178, :197
@@ -1814,12 +1815,37 @@ def Lambda_continuum(eps_conv: float, maxiter: int, sites: VoronoiSites, case: C
             own.close()
 
 
+def lambda_diagonal_regular(z, x, y, alpha, quadrature: str, device: int = 0) -> np.ndarray:
+    """The diagonal approximate operator Λ* of accelerated Λ-iteration on a raster (`vrt_regular_lambda_diagonal`): per
+    (point, wavelength) the coefficient of the point's own S in its intensity after one sweep of the raster solve, summed
+    over the angles of `quadrature` with their weights; exactly 0 on the ghost border.  z, x, y are the axes with the
+    periodic ghost border, alpha (n,) or (n, nλ) over all nz nx ny points in Julia order, finite and > 0; returns (n, nλ)."""
+    alpha = _f64(alpha)
+    if alpha.ndim == 1:
+        alpha = alpha.reshape(-1, 1)
+    n = int(np.size(z)) * int(np.size(x)) * int(np.size(y))
+    if alpha.ndim != 2 or alpha.shape[0] != n:
+        raise ValueError(f"lambda_diagonal_regular: alpha must be ({n},) or ({n}, nlam)")
+    w, k, dirs = _regular_directions(quadrature)
+    solver = _regular_solver(z, x, y, n, device)
+    try:
+        diag = np.zeros_like(alpha)
+        check(_lib.load().vrt_regular_lambda_diagonal(solver._h, k.shape[0], _d(k), dirs.ctypes.data_as(_lib.p_int), _d(w),
+                                                      alpha.shape[1], alpha.shape[1], _d(alpha), _d(diag)))
+        return diag
+    finally:
+        solver.close()
+
+
 def Lambda_continuum_regular(eps_conv: float, maxiter: int, z, x, y, case: ContinuumCase, quadrature: str, ng=None,
-                             S0=None, n_sweeps: int = 3, device: int = 0):
+                             S0=None, n_sweeps: int = 3, device: int = 0, operator=None):
     """Λ_regular of src/lambda_continuum.jl:58-107 with library-owned device state (`vrt_regular_continuum_*`).  z, x, y
     are the raster's axes with the periodic ghost border; every one of its nz nx ny points is a point of `case` (Julia
-    order i = iz + nz (ix + nx iy), i.e. numpy (ny, nx, nz) flattened).  Otherwise as `Lambda_continuum`."""
+    order i = iz + nz (ix + nx iy), i.e. numpy (ny, nx, nz) flattened).  Otherwise as `Lambda_continuum`, operator="diagonal"
+    included (`vrt_regular_continuum_select_operator`; `lambda_diagonal_regular` returns that Λ*)."""
     L = _lib.load()
+    if operator not in _OPERATORS:
+        raise ValueError(f"Lambda_continuum_regular: operator must be None or 'diagonal', not {operator!r}")
     w, k, dirs = _regular_directions(quadrature)
     solver = _regular_solver(z, x, y, case.n, device)
     cc = case.c_struct()
@@ -1827,7 +1853,8 @@ def Lambda_continuum_regular(eps_conv: float, maxiter: int, z, x, y, case: Conti
     try:
         check(L.vrt_regular_continuum_create(solver._h, k.shape[0], _d(k), dirs.ctypes.data_as(_lib.p_int), _d(w),
                                              ctypes.byref(cc), int(n_sweeps), ctypes.byref(h)))
-        return _continuum_loop(L, "vrt_regular_continuum_", h, case, eps_conv, maxiter, ng, S0, "Lambda_continuum_regular")
+        return _continuum_loop(L, "vrt_regular_continuum_", h, case, eps_conv, maxiter, ng, S0, "Lambda_continuum_regular",
+                               operator)
     finally:
         if h:
             L.vrt_regular_continuum_destroy(h)

@@ -22,6 +22,9 @@
 // Gauss-Seidel visit of every angle (k_lambda_diagonal, once per session: α does not change), and the update becomes
 //   S_new = ((1 - ε) (J - Λ* S_old) + ε B_0) / (1 - (1 - ε) Λ*)
 // in both layouts (the ALI instantiations of the two update kernels; Λ* of the sweep-order one is an up-order plane set).
+// On the raster session, vrt_regular_continuum_select_operator(s, 1): Λ* is the diagonal of one sweep of the raster's Λ
+// (k_regular_lambda_diagonal, vrt_regular.hip, from the session's plane-major α), exactly 0 on the ghost border, and the
+// update is the same k_continuum_update<true> in the caller's layout.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -300,6 +303,23 @@ k_ali_min_den(int64_t total, const double *__restrict__ eps, const double *__res
     }
 }
 
+// min den of an operator about to be moved into a session: VRT_EINVAL if it is not > 0 somewhere; synchronises st
+int check_min_den(int64_t total, const double *d_eps, const double *d_diag, unsigned long long *d_scalars, hipStream_t st)
+{
+    VRT_HIP_TRY(hipMemsetAsync(d_scalars, 0xFF, sizeof(unsigned long long), st));
+    VRT_HIP_TRY(hipMemsetAsync(d_scalars + 1, 0, sizeof(unsigned long long), st));
+    const int64_t blocks = std::min<int64_t>((total + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(k_ali_min_den, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, total, d_eps, d_diag,
+                       d_scalars);
+    VRT_HIP_TRY(hipGetLastError());
+    unsigned long long h[2] = {0, 0};
+    VRT_HIP_TRY(hipMemcpyAsync(h, d_scalars, sizeof(h), hipMemcpyDeviceToHost, st));
+    VRT_HIP_TRY(hipStreamSynchronize(st));
+    if (h[1]) return fail(VRT_EINVAL, "the diagonal operator has 1 - (1 - eps) Lambda* <= 0 somewhere (eps = 0 in a cell "
+                                      "whose Lambda* rounds to 1)");
+    return VRT_OK;
+}
+
 // the three words of an update -> the criterion's scalar (NaN like Julia's maximum) and the thick count; synchronises st
 int read_criterion(const unsigned long long *d_result, hipStream_t st, double *max_rel_change, int64_t *n_thick)
 {
@@ -383,7 +403,48 @@ struct vrt_regular_continuum {
     DevBuf<unsigned long long> d_scalars;
     int64_t iterations = 0;
     NgState ng;
+    // vrt_regular_continuum_select_operator (0: nothing allocated, nothing run): Λ* in the caller's layout (n, nlam), formed
+    // from the directions the session was created with (per user angle, host)
+    int op = 0;
+    DevBuf<double> d_diag;
+    std::vector<double> k, weights;
+    std::vector<int> dirs;
 };
+
+// Λ* of a raster from its plane-major α into d_diag, dense (n, nlam) in Julia point order
+static int regular_diagonal(const vrt_regular *r, int64_t n_angles, const double *k, const int *dirs, const double *weights,
+                            int64_t nlam, const double *d_alpha_pl, double *d_diag, hipStream_t st)
+{
+    DevBuf<double> diag_pl;
+    int rc = diag_pl.alloc((size_t)(r->nz * r->nx * r->ny) * (size_t)nlam);
+    if (rc) return rc;
+    if ((rc = launch_regular_lambda_diagonal(r, n_angles, k, dirs, weights, nlam, d_alpha_pl, diag_pl, st))) return rc;
+    if ((rc = launch_from_planes(r, nlam, diag_pl, d_diag, st))) return rc;
+    VRT_HIP_TRY(hipStreamSynchronize(st));                   // (diag_pl goes here)
+    return VRT_OK;
+}
+
+// the same from (n, ld) rows on the device, of which only the first nlam columns are read and written; synchronises st
+static int regular_diagonal_rows(const vrt_regular *r, int64_t n_angles, const double *k, const int *dirs,
+                                 const double *weights, int64_t nlam, int64_t ld, const double *d_alpha, double *d_diag,
+                                 hipStream_t st)
+{
+    const int64_t n = r->nz * r->nx * r->ny;
+    const size_t nS = (size_t)n * (size_t)nlam, row = sizeof(double) * (size_t)nlam, pitch = sizeof(double) * (size_t)ld;
+    DevBuf<double> a_dense, a_pl, g_dense;
+    int rc;
+    if ((rc = a_pl.alloc(nS)) || (rc = g_dense.alloc(nS))) return rc;
+    if (ld != nlam) {
+        if ((rc = a_dense.alloc(nS))) return rc;
+        VRT_HIP_TRY(hipMemcpy2DAsync(a_dense, row, d_alpha, pitch, row, (size_t)n, hipMemcpyDeviceToDevice, st));
+        d_alpha = a_dense;
+    }
+    if ((rc = launch_to_planes(r, nlam, d_alpha, a_pl, st))) return rc;
+    if ((rc = regular_diagonal(r, n_angles, k, dirs, weights, nlam, a_pl, g_dense, st))) return rc;
+    VRT_HIP_TRY(hipMemcpy2DAsync(d_diag, pitch, g_dense, row, row, (size_t)n, hipMemcpyDeviceToDevice, st));
+    VRT_HIP_TRY(hipStreamSynchronize(st));
+    return VRT_OK;
+}
 
 // the S buffer a session's acceleration works on: doubles allocated, and which of them are physical entries
 static size_t continuum_S_count(const vrt_continuum *s, NgRange *rg)
@@ -726,17 +787,7 @@ int vrt_continuum_set_operator(vrt_continuum *s, int op)
             }
             if ((rc = launch_lambda_diagonal(p, nlam, nlam, alpha, s->weights.data(), diag, st))) return rc;
             // min den = min (1 - (1 - ε) Λ*) must be > 0 (it is not only for ε = 0 with Λ* rounding to 1)
-            VRT_HIP_TRY(hipMemsetAsync(s->d_scalars, 0xFF, sizeof(unsigned long long), st));
-            VRT_HIP_TRY(hipMemsetAsync(s->d_scalars + 1, 0, sizeof(unsigned long long), st));
-            const int64_t blocks = std::min<int64_t>(((int64_t)nS + 255) / 256, 256 * 16);
-            hipLaunchKernelGGL(k_ali_min_den, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, (int64_t)nS, eps,
-                               diag.p, s->d_scalars.p);
-            VRT_HIP_TRY(hipGetLastError());
-            unsigned long long h[2] = {0, 0};
-            VRT_HIP_TRY(hipMemcpyAsync(h, s->d_scalars, sizeof(h), hipMemcpyDeviceToHost, st));
-            VRT_HIP_TRY(hipStreamSynchronize(st));
-            if (h[1]) return fail(VRT_EINVAL, "the diagonal operator has 1 - (1 - eps) Lambda* <= 0 somewhere (eps = 0 in a cell "
-                                              "whose Lambda* rounds to 1)");
+            if ((rc = check_min_den((int64_t)nS, eps, diag, s->d_scalars, st))) return rc;
             if (s->native) {
                 const size_t np = (size_t)vrt_plan_native_plane_count(p, nlam);
                 if ((rc = L_up.alloc(np))) return rc;
@@ -802,6 +853,9 @@ int vrt_regular_continuum_create(vrt_regular *r, int64_t n_angles, const double 
         s->nlam = nlam;
         s->eps_thick = cc->eps_thick;
         if ((rc = line_solves_init(s->ls, r, n_angles, k, dirs, weights, nlam))) return rc;
+        s->k.assign(k, k + 3 * n_angles);
+        s->dirs.assign(dirs, dirs + n_angles);
+        s->weights.assign(weights, weights + n_angles);
         if ((rc = s->st.create())) return rc;
         hipStream_t st = s->st;
         const size_t nS = (size_t)vol * (size_t)nlam;
@@ -844,8 +898,8 @@ int vrt_regular_continuum_iterate(vrt_regular_continuum *s, double *max_rel_chan
         // S_new also plane-major for the next solves
         if ((rc = continuum_J_pass(s, st))) return rc;
         if ((rc = launch_from_planes(r, nlam, s->d_J_pl, s->d_J, st))) return rc;
-        if ((rc = launch_continuum_update(n, nlam, nlam, s->d_J, s->d_B0, s->d_eps, nullptr, s->eps_thick, s->d_S[s->sc],
-                                          s->d_S[s->sc ^ 1], s->d_scalars, st)))
+        if ((rc = launch_continuum_update(n, nlam, nlam, s->d_J, s->d_B0, s->d_eps, s->op ? s->d_diag.p : nullptr,
+                                          s->eps_thick, s->d_S[s->sc], s->d_S[s->sc ^ 1], s->d_scalars, st)))
             return rc;
         s->sc ^= 1;
         if ((rc = launch_to_planes(r, nlam, s->d_S[s->sc], s->d_S_pl, st))) return rc;
@@ -913,6 +967,90 @@ int vrt_regular_continuum_last_acceleration(const vrt_regular_continuum *s, int 
 {
     if (!s || !applied) return fail(VRT_EINVAL, "NULL argument");
     return ng_report(s->ng, applied, sums, coeffs);
+}
+
+int vrt_regular_continuum_select_operator(vrt_regular_continuum *s, int op)
+{
+    if (!s) return fail(VRT_EINVAL, "NULL session");
+    if (op != 0 && op != 1) return fail(VRT_EINVAL, "operator must be 0 (plain) or 1 (diagonal)");
+    return guarded([&] {
+        int rc = use_device(s->device);
+        if (rc) return rc;
+        if (op == s->op) return (int)VRT_OK;
+        hipStream_t st = s->st;
+        if (op == 0) {
+            VRT_HIP_TRY(hipStreamSynchronize(st));
+            s->d_diag = DevBuf<double>();
+        } else {
+            // Λ* from the session's α and directions, once; built beside the session and moved in at the end
+            const size_t nS = (size_t)s->n * (size_t)s->nlam;
+            DevBuf<double> diag;
+            if ((rc = diag.alloc(nS))) return rc;
+            if ((rc = regular_diagonal(s->r, (int64_t)s->dirs.size(), s->k.data(), s->dirs.data(), s->weights.data(), s->nlam,
+                                       s->d_A_pl, diag, st)))
+                return rc;
+            if ((rc = check_min_den((int64_t)nS, s->d_eps, diag, s->d_scalars, st))) return rc;
+            s->d_diag = std::move(diag);
+        }
+        s->op = op;
+        s->ng.have = 0;                                      // iterates of another fixed-point map are no history of this one
+        return (int)VRT_OK;
+    });
+}
+
+int vrt_regular_continuum_get_operator(vrt_regular_continuum *s, int *op, double *diag)
+{
+    if (!s || !op) return fail(VRT_EINVAL, "NULL argument");
+    return guarded([&] {
+        *op = s->op;
+        if (!diag || !s->op) return (int)VRT_OK;
+        int rc = use_device(s->device);
+        if (rc) return rc;
+        hipStream_t st = s->st;
+        VRT_HIP_TRY(hipMemcpyAsync(diag, s->d_diag, sizeof(double) * (size_t)s->n * (size_t)s->nlam, hipMemcpyDeviceToHost, st));
+        VRT_HIP_TRY(hipStreamSynchronize(st));
+        return (int)VRT_OK;
+    });
+}
+
+int vrt_regular_lambda_diagonal_dev(vrt_regular *r, int64_t n_angles, const double *k, const int *dirs, const double *weights,
+                                    int64_t nlam, int64_t ld, const double *d_alpha, double *d_diag)
+{
+    if (!r || !k || !dirs || !weights || !d_alpha || !d_diag) return fail(VRT_EINVAL, "NULL argument");
+    if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
+    int rc = check_angles(n_angles, k, dirs);
+    if (rc) return rc;
+    return guarded([&] {
+        if ((rc = use_device(r->device))) return rc;
+        return regular_diagonal_rows(r, n_angles, k, dirs, weights, nlam, ld, d_alpha, d_diag, nullptr);
+    });
+}
+
+int vrt_regular_lambda_diagonal(vrt_regular *r, int64_t n_angles, const double *k, const int *dirs, const double *weights,
+                                int64_t nlam, int64_t ld, const double *alpha, double *diag)
+{
+    if (!r || !k || !dirs || !weights || !alpha || !diag) return fail(VRT_EINVAL, "NULL argument");
+    if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
+    int rc = check_angles(n_angles, k, dirs);
+    if (rc) return rc;
+    return guarded([&] {
+        const int64_t n = r->nz * r->nx * r->ny;
+        for (int64_t i = 0; i < n; i++)
+            for (int64_t l = 0; l < nlam; l++) {
+                const double a = alpha[i * ld + l];
+                if (!std::isfinite(a) || !(a > 0.0)) return fail(VRT_EINVAL, "alpha must be finite and > 0 everywhere");
+            }
+        if ((rc = use_device(r->device))) return rc;
+        const size_t count = (size_t)n * (size_t)ld;
+        DevBuf<double> d_alpha, d_diag;
+        if ((rc = upload(d_alpha, alpha, count, nullptr))) return rc;
+        if ((rc = d_diag.alloc(count))) return rc;
+        // (the padding columns of diag go back as they came)
+        VRT_HIP_TRY(hipMemcpyAsync(d_diag, diag, sizeof(double) * count, hipMemcpyHostToDevice, nullptr));
+        if ((rc = regular_diagonal_rows(r, n_angles, k, dirs, weights, nlam, ld, d_alpha, d_diag, nullptr))) return rc;
+        VRT_HIP_TRY(hipMemcpy(diag, d_diag, sizeof(double) * count, hipMemcpyDeviceToHost));
+        return VRT_OK;
+    });
 }
 
 void vrt_regular_continuum_destroy(vrt_regular_continuum *s)

@@ -62,5 +62,11 @@ int line_solves_init(LineSolves &ls, const vrt_regular *r, int64_t n_angles, con
                      const double *weights, int64_t nlam);
 // J[l][p] += w_a I[g - g0][p] over the chunk's solves [g0, g0 + cnt) held in r->d_I, in quadrature order
 int launch_reduce_J_planes(const vrt_regular *r, const LineSolves &ls, int64_t g0, int64_t cnt, double *dJ_pl, hipStream_t st);
+// Λ* of accelerated Λ-iteration (k_regular_lambda_diagonal, vrt_regular.hip) from a plane-major α into a plane-major
+// d_diag_pl, both [l][iz][iy][ix]; k, dirs, weights per USER angle on the host (dirs = 0 is skipped; more than kMaxAngles
+// active ones: VRT_EINVAL)
+int launch_regular_lambda_diagonal(const vrt_regular *r, int64_t n_angles, const double *k, const int *dirs,
+                                   const double *weights, int64_t nlam, const double *d_alpha_pl, double *d_diag_pl,
+                                   hipStream_t st);
 
 }  // namespace vrt

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <vector>
 
@@ -775,6 +776,156 @@ k_reg_top_interior(int nz, int nx, int ny, int64_t n_solve, const double *__rest
     const int64_t s = t / inner, q = t - s * inner;
     const int ix = 1 + (int)(q % mx), iy = 1 + (int)(q / mx);
     top[t] = I[(s * nz + (nz - 1)) * plane + ix + (int64_t)nx * iy];
+}
+
+// ---- the local operator Λ* of accelerated Λ-iteration on the raster (vrt_regular_continuum_select_operator) ------------------
+// per ACTIVE angle: direction, quadrature weight, 1 = up (kernel argument, as DiagAngles of vrt_continuum.hip)
+struct RegDiagAngles {
+    double k[kMaxAngles][3];
+    double w[kMaxAngles];
+    int up[kMaxAngles];
+};
+
+// What one point of a yz / xz plane contributes: the coefficient of its own S in ONE sweep of the row march of
+// k_regular_solve (the same indices, reg_bilinear instead of reg_bilinear_rcp: the reference's arithmetic).
+//   serial index sc, parallel index pc, as row_march: YZ: (ix, iy); XZ: (iy, ix)
+//   I_c = (e I_u + a S_u) + b S_cen
+// S_cen is the point's own S except in xz_down_ray, which reads it from the plane above (:794): no centre term there.
+// S_u is interpolated in the row sc + sgn and never holds the point.  I_u is interpolated between the upwind plane and
+// the CARRIED row, which in the first sweep is the row marched just before, sc - sgn -- and that row's S_u was
+// interpolated in row sc: the point's S comes back through its neighbour (sc - sgn, pc) within the same sweep, as
+// e · (weight of the neighbour in I_u) · a_q · (weight of the point in the neighbour's S_u).  The first marched row
+// carries zeros.  Both corners of I_u are walked with their periodic images, so rows of one or two points are right too.
+template <bool YZ>
+__device__ __forceinline__ double reg_diag_row(int nx, int n_par, int sc, int pc, int s0, int sgn, int h, bool up,
+                                               bool own_centre, bool own_lo, double r, double z_up, double inc, double zb1,
+                                               double zb2, const double *__restrict__ par, const double *__restrict__ A_lo,
+                                               const double *__restrict__ A_hi, const double *__restrict__ A_cen)
+{
+#define AT(arr, sidx, pidx) (YZ ? (arr)[(sidx) + nx * (pidx)] : (arr)[(pidx) + nx * (sidx)])
+    // (a, b, e) of the point (s_, p_) of this plane
+    auto weights_at = [&](int s_, int p_, double &a, double &b, double &e) {
+        const int pl_ = p_ - h, pu_ = pl_ + 1, su_ = s_ + sgn;
+        const double a_u = reg_bilinear(z_up, par[p_] + inc, zb1, zb2, par[pl_], par[pu_], AT(A_lo, su_, pl_),
+                                        AT(A_lo, su_, pu_), AT(A_hi, su_, pl_), AT(A_hi, su_, pu_));
+        linear_weights_ref_order(r * (AT(A_cen, s_, p_) + a_u) / 2.0, a, b, e);
+    };
+    double a, b, e;
+    weights_at(sc, pc, a, b, e);
+    const int pl = pc - h, pu = pl + 1;
+    double dI[2] = {0.0, 0.0};                                    // what the carried row holds of the point's S
+    if (sc != s0) {
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const int corner = j ? pu : pl;
+            const int q = corner == 0 ? n_par - 2 : corner == n_par - 1 ? 1 : corner;     // the ghost's interior image
+            const int ql = q - h, qu = ql + 1;
+            const double i_l = ql == pc ? 1.0 : 0.0, i_u = qu == pc ? 1.0 : 0.0;
+            if (i_l == 0.0 && i_u == 0.0) continue;
+            double qa, qb, qe;
+            weights_at(sc - sgn, q, qa, qb, qe);
+            const double S_u = own_lo ? reg_bilinear(z_up, par[q] + inc, zb1, zb2, par[ql], par[qu], i_l, i_u, 0.0, 0.0)
+                                      : reg_bilinear(z_up, par[q] + inc, zb1, zb2, par[ql], par[qu], 0.0, 0.0, i_l, i_u);
+            dI[j] = qa * S_u;
+        }
+    }
+    const double I_u = up ? reg_bilinear(z_up, par[pc] + inc, zb1, zb2, par[pl], par[pu], 0.0, 0.0, dI[0], dI[1])
+                          : reg_bilinear(z_up, par[pc] + inc, zb1, zb2, par[pl], par[pu], dI[0], dI[1], 0.0, 0.0);
+    return own_centre ? e * I_u + b : e * I_u;
+#undef AT
+}
+
+// Λ*[l][p] = Σ_a w_a · (the coefficient of S[p] in I_a[p] after one sweep), the angles in order: the diagonal of one
+// sweep of the raster's Λ, which does not depend on n_sweeps and is <= the diagonal of any number of sweeps (every
+// coefficient of Λ is >= 0).  In an xy plane that coefficient is b(Δτ) alone (S_u and I_u come from the upwind plane);
+// the row-marched planes: reg_diag_row.  Nothing where the angle never updates the point from its own S: the boundary
+// plane of the angle's direction (I = I_0) and every ghost point (a copy of an interior point's I), so Λ* is exactly 0
+// on the ghost border.  Δτ, the cut and the interpolation indices are those of k_regular_solve for the point's plane.
+// alpha and diag plane-major [l][iz][iy][ix]; one thread per point, ix fastest, grid.y the wavelength.  No atomics: the
+// same inputs give the same bits.  Runs once per session.
+__global__ void __launch_bounds__(256)
+k_regular_lambda_diagonal(int nz, int nx, int ny, int A, RegDiagAngles ang, const double *__restrict__ z,
+                          const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ alpha,
+                          double *__restrict__ diag)
+{
+#define PL(p, ix, iy) (p)[(ix) + nx * (iy)]
+    const int64_t plane = (int64_t)nx * ny, vol = plane * nz;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= vol) return;
+    const int idx = (int)(t % nx), idy = (int)((t / nx) % ny), idz = (int)(t / plane);
+    double *out = diag + (int64_t)blockIdx.y * vol + t;
+    if (idx == 0 || idx == nx - 1 || idy == 0 || idy == ny - 1) { *out = 0.0; return; }
+    const double *Al = alpha + (int64_t)blockIdx.y * vol;
+    double acc = 0.0;
+    for (int a = 0; a < A; a++) {
+        const double k0 = ang.k[a][0], k1 = ang.k[a][1], k2 = ang.k[a][2];
+        const bool up = ang.up[a] != 0;
+        if (idz == (up ? 0 : nz - 1)) continue;                   // I = I_0 there (:61, :146)
+        int sign_x, sign_y;                                       // xy_intersect, functions.jl:430-457
+        if (k1 > 0 && k2 > 0) { sign_x = -1; sign_y = -1; }
+        else if (k1 < 0 && k2 > 0) { sign_x = 1; sign_y = -1; }
+        else if (k1 < 0 && k2 < 0) { sign_x = 1; sign_y = 1; }
+        else if (k1 > 0 && k2 < 0) { sign_x = -1; sign_y = 1; }
+        else { sign_x = 1; sign_y = 1; }
+        const int hx = (sign_x + 1) / 2, hy = (sign_y + 1) / 2;
+        const double r_x = fabs((x[1] - x[0]) / k1), r_y = fabs((y[1] - y[0]) / k2);   // (a vertical ray: inf, cut = 1)
+        const int idz_u = up ? idz - 1 : idz + 1;
+        const double dzp = up ? z[idz] - z[idz - 1] : z[idz + 1] - z[idz];
+        const double r_z = fabs(dzp / k0);
+        int cut = 1;                                              // argmin([r_z, r_x, r_y]) (:72)
+        double m = r_z;
+        if (r_x < m) { m = r_x; cut = 2; }
+        if (r_y < m) { m = r_y; cut = 3; }
+        const double *Ac = Al + (int64_t)idz * plane, *Au = Al + (int64_t)idz_u * plane;
+        double c;
+        if (cut == 1) {
+            const double r = fabs((z[idz_u] - z[idz]) / k0);
+            const int xl = idx - hx, xu = xl + 1, yl = idy - hy, yu = yl + 1;
+            const double a_u = reg_bilinear(x[idx] + r * k1, y[idy] + r * k2, x[xl], x[xu], y[yl], y[yu], PL(Au, xl, yl),
+                                            PL(Au, xl, yu), PL(Au, xu, yl), PL(Au, xu, yu));
+            double ca, ce;
+            linear_weights_ref_order(r * (PL(Ac, idx, idy) + a_u) / 2.0, ca, c, ce);
+        } else {
+            const double zb1 = up ? z[idz_u] : z[idz], zb2 = up ? z[idz] : z[idz_u];
+            const double *A_lo = up ? Au : Ac, *A_hi = up ? Ac : Au;
+            if (cut == 2) {
+                const double r = fabs((x[1] - x[0]) / k1);
+                c = reg_diag_row<true>(nx, ny, idx, idy, sign_x == 1 ? 1 : nx - 2, sign_x, hy, up, true, !up, r,
+                                       z[idz] + r * k0, r * k2, zb1, zb2, y, A_lo, A_hi, Ac);
+            } else {
+                const double r = fabs((y[1] - y[0]) / k2);
+                c = reg_diag_row<false>(nx, nx, idy, idx, sign_y == 1 ? 1 : ny - 2, sign_y, hx, up, up, !up, r,
+                                        z[idz] + r * k0, r * k1, zb1, zb2, x, A_lo, A_hi, A_hi);
+            }
+        }
+        acc = acc + ang.w[a] * c;
+    }
+    *out = acc;
+#undef PL
+}
+
+int launch_regular_lambda_diagonal(const vrt_regular *r, int64_t n_angles, const double *k, const int *dirs,
+                                   const double *weights, int64_t nlam, const double *d_alpha_pl, double *d_diag_pl,
+                                   hipStream_t st)
+{
+    RegDiagAngles ang;
+    std::memset(&ang, 0, sizeof(ang));
+    int A = 0;
+    for (int64_t a = 0; a < n_angles; a++) {
+        if (dirs[a] == 0) continue;                               // θ = 90: the reference adds nothing
+        if (A == kMaxAngles) return fail(VRT_EINVAL, "too many active angles");
+        for (int j = 0; j < 3; j++) ang.k[A][j] = k[3 * a + j];
+        ang.w[A] = weights[a];
+        ang.up[A] = dirs[a] > 0;
+        A++;
+    }
+    if (nlam > 65535) return fail(VRT_EINVAL, "nlam too large");
+    const int64_t vol = r->nz * r->nx * r->ny;
+    hipLaunchKernelGGL(k_regular_lambda_diagonal, dim3((unsigned)((vol + 255) / 256), (unsigned)nlam), dim3(256), 0, st,
+                       (int)r->nz, (int)r->nx, (int)r->ny, A, ang, (const double *)r->d_g, r->d_g + r->nz,
+                       r->d_g + r->nz + r->nx, d_alpha_pl, d_diag_pl);
+    VRT_HIP_TRY(hipGetLastError());
+    return VRT_OK;
 }
 
 }  // namespace vrt
