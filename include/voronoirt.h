@@ -242,6 +242,10 @@ int vrt_plan_execute_dev_f32(vrt_plan *p, int64_t nlam, int64_t ld, const float 
  * waiting for a dependency -- a bounded spin expired: the results of that execute are invalid; also reported by the
  * next execute of the plan) */
 int vrt_plan_last_sweep_timing(const vrt_plan *p, double *ms, int64_t *launches);
+/* how the patch path cut this plan (introspection for the tests only: nothing in a solve needs it): out[0] = patches of all angles and layers, out[1] = the fewest patches
+ * any (angle, layer >= 2) has, out[2] = slots of the work lists of the per-layer launches and out[3] = how many of them are
+ * padding (both 0 until a per-layer execute has built the lists) */
+int vrt_plan_patch_layout(const vrt_plan *p, int64_t *out);
 /* VRT_OK, or the give-up of a chained patch launch that has finished since the last check (VRT_ENODEVICE: the results of
  * that execute are invalid).  The entry points that synchronise themselves (vrt_plan_execute, vrt_plan_execute_line,
  * vrt_lambda_iterate, vrt_multi_*) report it from the call it spoiled; a caller of the ASYNCHRONOUS entry points

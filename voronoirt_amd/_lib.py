@@ -119,6 +119,7 @@ PROTOTYPES = {
                                                  c_dbl, p_dbl, p_dbl, vp, vp, c_dbl, c_dbl, c_dbl, vp, vp, vp,
                                                  vp, vp]),
     "vrt_plan_last_sweep_timing": (ctypes.c_int, [vp, p_dbl, p_i64]),
+    "vrt_plan_patch_layout": (ctypes.c_int, [vp, p_i64]),
     "vrt_plan_last_path": (ctypes.c_int, [vp]),
     "vrt_plan_set_option": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_char_p]),
     "vrt_grid_set_option": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_char_p]),

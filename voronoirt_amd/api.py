@@ -387,6 +387,14 @@ class FormalPlan:
         return ms.value, launches.value
 
     @property
+    def patch_layout(self) -> dict:
+        """How the patch path cut this plan: patches, the fewest patches of any (angle, layer), slots of the per-layer
+        launches' work lists and how many of them are padding (0 until a per-layer execute has built the lists)."""
+        out = (ctypes.c_int64 * 4)()
+        check(_lib.load().vrt_plan_patch_layout(self._h, out))
+        return {"patches": out[0], "fewest_per_angle_layer": out[1], "work_slots": out[2], "padding_slots": out[3]}
+
+    @property
     def last_launches(self) -> int:
         """Kernel launches of the last execute's sweep (1: the chained patch launch); waits for it to finish and
         raises if a chained launch gave up waiting for a dependency."""

@@ -1362,6 +1362,27 @@ int vrt_plan_check(vrt_plan *p)
     });
 }
 
+int vrt_plan_patch_layout(const vrt_plan *p, int64_t *out)
+{
+    if (!p || !out) return fail(VRT_EINVAL, "NULL plan or output");
+    const int maxL = p->tile_max_layers;
+    int64_t fewest = 0;
+    if (p->patch_ok && !p->h_patch_first.empty()) {
+        fewest = INT64_MAX;
+        for (int a = 0; a < p->A; a++)
+            for (int layer = 2; layer <= maxL; layer++) {
+                const int32_t *first = p->h_patch_first.data() + (size_t)a * (size_t)(maxL + 2);
+                fewest = std::min<int64_t>(fewest, first[layer + 1] - first[layer]);
+            }
+        if (fewest == INT64_MAX) fewest = 0;
+    }
+    out[0] = p->patch_ok ? p->n_patches : 0;
+    out[1] = fewest;
+    out[2] = p->patch_work_off.empty() ? 0 : p->patch_work_off.back();
+    out[3] = p->patch_work_padding;
+    return VRT_OK;
+}
+
 int vrt_plan_last_sweep_timing(const vrt_plan *p, double *ms, int64_t *launches)
 {
     if (!p) return fail(VRT_EINVAL, "NULL plan");

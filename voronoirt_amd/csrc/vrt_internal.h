@@ -496,6 +496,7 @@ struct vrt_plan {
     vrt::DevBuf<int4> d_patch_work;      // work lists of the launches: two int4 per slot (ensure_patch_work, PatchArgs::wrec)
     std::vector<int64_t> patch_work_off; //   [group][layer] offsets into it
     int patch_work_groups = 0;
+    int64_t patch_work_padding = 0;      //   slots of it that hold no patch (a layer's items are dealt to 8 runs of one length)
     vrt::Stream step_stream[4];
     vrt::Event step_fork, step_join[4];
     int last_path = 0;                   // path of the last execute (vrt_plan_last_path): 1 levels, 2 tiles, 3 steps, 4 patches

@@ -32,6 +32,7 @@ namespace vrt {
 enum : int {
     kDiagNoLevels = 1, kDiagCentreGathers = 2, kDiagNoWeights = 4, kDiagNoStores = 8, kDiagNoGatherI = 16, kDiagNoGatherAlpha = 32,
     kDiagNoGatherS = 64, kDiagNoReduce = 128, kDiagNoWait = 256, kDiagPlainLoadI = 512, kDiagPlainStoreI = 1024, kDiagNoPairLoop = 2048,
+    kDiagDirectTable = 4096,
 };
 __host__ __device__ __forceinline__ constexpr bool diag(int dbg, int flag) { return kDiag && (dbg & flag) != 0; }
 
@@ -39,13 +40,19 @@ struct PatchArgs {
     TileArgs ta;              // n, nlam, alpha_mode, angle_dir, lay, nlayers, S, alpha, alpha_angle, I (pair planes)
     int npair;                // ceil(nlam / 2)
     int layer;                // 1-based BFS layer being solved
-    int ngrp;                 // workgroups per work item = siblings (1 << lgB) x splits
+    int ngrp;                 // workgroups per work item = siblings (1 << lgB) x splits: gridDim.x = 8 ngrp
+    int nrow;                 // rows of the grid that solve patches (work-list slots / 8); the rows behind them reduce
     int nsplit, Q;            // the pair blocks are dealt to nsplit workgroups per sibling in steps of Q blocks (split_blocks)
+    int sbase, srem;          //   steps per split and the splits that take one more (set_split: no division in the kernel)
     int lgB;                  // log2 of the pairs per block of the storage layout (vrt_device.h: pair_block_at)
     int stride;               // tile slots per pair plane (> largest entry count: + the zero slot)
     int cap;                  // entries per patch at most (K * NT): length of the LDS table arrays
     int quad;                 // fp32 storage: k_patch_quad (two neighbouring pairs of a block per workgroup)
     int lean;                 // k_patch_lean (64 registers: four workgroups per CU)
+    int dbg_ent0, dbg_ent_stride, dbg_ent_last;   // diagnostics 4096 (kDiagDirectTable): the entry table is read at an address that
+                              //   depends on no loaded value -- (launch's first slot + slot) x mean entries per slot, the WRONG
+                              //   table -- and its loads are issued ahead of the item's record: what a table laid out in
+                              //   work-list order could save at most
     int dbg;                  // timing diagnostics (-DVRT_DIAG build only, WRONG results): 1 no levels, 2 gathers ->
                               //   coalesced centre reads, 4 no weights arithmetic, 8 no stores, 16 / 32 / 64 no upwind gathers
                               //   of I / alpha / S, 128 no J reduction
@@ -106,10 +113,15 @@ template <> struct Log2Size<float2> { static constexpr int value = 3; };
 
 // blocks [b0, b1) of split number `split`: the steps (Q blocks each) are dealt evenly, the first (steps % nsplit)
 // splits taking one more (26 pairs over 5 splits: 6, 5, 5, 5, 5 -- not 6, 6, 6, 6, 2)
-__host__ __device__ __forceinline__ void split_blocks(const PatchArgs &pa, int split, int nblock, int &b0, int &b1)
+static void set_split(PatchArgs &pa, int nblock)          // host: pa.nsplit and pa.Q are set
 {
     const int nstep = (nblock + pa.Q - 1) / pa.Q;
-    const int base = nstep / pa.nsplit, rem = nstep - base * pa.nsplit;
+    pa.sbase = nstep / pa.nsplit;
+    pa.srem = nstep - pa.sbase * pa.nsplit;
+}
+__host__ __device__ __forceinline__ void split_blocks(const PatchArgs &pa, int split, int nblock, int &b0, int &b1)
+{
+    const int base = pa.sbase, rem = pa.srem;
     const int s0 = split * base + (split < rem ? split : rem), s1 = s0 + base + (split < rem ? 1 : 0);
     b0 = s0 * pa.Q;
     b1 = nblock < s1 * pa.Q ? nblock : s1 * pa.Q;
@@ -121,13 +133,19 @@ __host__ __device__ __forceinline__ void split_blocks(const PatchArgs &pa, int s
 #ifndef VRT_REDUCE_LAST
 #define VRT_REDUCE_LAST 1
 #endif
+// The grid is two-dimensional so that a workgroup finds its place without dividing by launch constants: blockIdx.x =
+// XCD lane + 8 x (split, sibling) with gridDim.x = 8 ngrp, blockIdx.y = row of the work list.  Blocks are dispatched x
+// first: block x + 8 (grp + ngrp sj) of the linear order is (x + 8 grp, sj), on the XCD its lane names.  The reduction
+// blocks fill rows of their own, padded to gridDim.x (a block past the last one returns at once).
 __device__ __forceinline__ int reduce_block_index(const PatchArgs &pa)      // >= 0: this block reduces
 {
-    return VRT_REDUCE_LAST ? (int)blockIdx.x - ((int)gridDim.x - pa.red.nred) : ((int)blockIdx.x < pa.red.nred ? (int)blockIdx.x : -1);
+    const int rows = (int)gridDim.y - pa.nrow;                // reduction rows
+    const int y = VRT_REDUCE_LAST ? (int)blockIdx.y - pa.nrow : ((int)blockIdx.y < rows ? (int)blockIdx.y : -1);
+    return y < 0 ? -1 : y * (int)gridDim.x + (int)blockIdx.x;
 }
-__device__ __forceinline__ int patch_block_index(const PatchArgs &pa)
+__device__ __forceinline__ int patch_row(const PatchArgs &pa)
 {
-    return VRT_REDUCE_LAST ? (int)blockIdx.x : (int)blockIdx.x - pa.red.nred;
+    return VRT_REDUCE_LAST ? (int)blockIdx.y : (int)blockIdx.y - ((int)gridDim.y - pa.nrow);
 }
 template <typename T, int NT>
 __device__ __forceinline__ void patch_reduce_role(const PatchArgs &pa)
@@ -223,9 +241,9 @@ k_patch_solve(PatchArgs pa)
         patch_reduce_role<T, NT>(pa);
         return;
     }
-    const int bid = patch_block_index(pa);
-    const int x = bid & 7, rr = bid >> 3;
-    const int grp = rr % pa.ngrp, sj = rr / pa.ngrp;
+    const int x = (int)blockIdx.x & 7, grp = (int)blockIdx.x >> 3, sj = patch_row(pa);
+    // (this kernel of the non-default shapes keeps its two vector loads of the record and its table loop as they were:
+    // the start-up work of patch_item / EntryTable went into the kernels the defaults run)
     const int4 rec = pa.wrec[2 * (sj * 8 + x)], rec2 = pa.wrec[2 * (sj * 8 + x) + 1];
     if (rec.y <= 0) return;
     // sibling sib solves pair k0 + sib of every block [k0, k0 + 2^lw) with 2^lw > sib among blocks b0 .. b1-1: the
@@ -397,6 +415,12 @@ k_patch_solve(PatchArgs pa)
 
 // ---- what the one-entry-per-thread kernels (k_patch_lean, k_patch_quad, k_patch_chain) share --------------------------
 // the work of this workgroup: patch, sibling number inside a pair block, blocks [b0, b1), the patch's record
+// A slot of the work list as ONE 32-byte scalar load.  The constant address space is a promise: the list is written by the
+// host only (ensure_patch_work, a synchronous copy ahead of every launch that reads it) and NEVER by a kernel -- a scalar
+// load is served by the scalar cache, which is invalidated when a kernel starts and not while it runs.
+typedef int vrt_i32x8 __attribute__((ext_vector_type(8)));
+typedef const __attribute__((address_space(4))) vrt_i32x8 WorkRec;
+static_assert(2 * sizeof(int4) == 32 && sizeof(vrt_i32x8) == 32, "a work-list slot is two int4: 32 bytes, 32-byte aligned");
 struct PatchItem {
     int sib, b0, b1;
     int ent_off, n_ent, own_lo, own_cnt, nlev, a, d, lo, hi;
@@ -405,10 +429,12 @@ struct PatchItem {
 // false: a padding slot, or nothing of the item for this workgroup
 __device__ __forceinline__ bool patch_item(const PatchArgs &pa, int lgS, PatchItem &it)
 {
-    const int bid = patch_block_index(pa);
-    const int x = bid & 7, rr = bid >> 3;
-    const int grp = rr % pa.ngrp, sj = rr / pa.ngrp;
-    const int4 rec = pa.wrec[2 * (sj * 8 + x)], rec2 = pa.wrec[2 * (sj * 8 + x) + 1];
+    const int x = (int)blockIdx.x & 7, grp = (int)blockIdx.x >> 3, sj = patch_row(pa);
+    // both halves of the record in ONE scalar load: the work list is written by the host before the launch and its
+    // address is the block's alone (the constant address space says so; as a vector load the second half was
+    // issued only behind the test of the first)
+    const vrt_i32x8 r8 = *((const WorkRec *)(uintptr_t)pa.wrec + (sj * 8 + x));
+    const int4 rec = make_int4(r8[0], r8[1], r8[2], r8[3]), rec2 = make_int4(r8[4], r8[5], r8[6], r8[7]);
     if (rec.y <= 0) return false;
     it.sib = grp & ((1 << lgS) - 1);
     split_blocks(pa, grp >> lgS, pair_block_count(pa.npair, pa.lgB), it.b0, it.b1);
@@ -436,19 +462,37 @@ struct EntryTable {
         vis = reinterpret_cast<uint32_t *>(u2 + CAP);
         loc = vis + CAP;
     }
+    // entry e of the tables in registers: the nine loads in flight together (ONE round trip: written one array after the
+    // other, the LDS stores between them and the branch around the visit levels cut them into three)
+    struct Regs {
+        int p0, a1, a2;
+        uint32_t vs, lc;
+        double x1, x2, y1, y2;
+    };
     template <typename Tables>       // PatchArgs, or any record with its e_* pointers
+    static __device__ __forceinline__ Regs load(const Tables &pa, int e)
+    {
+        Regs r;
+        r.p0 = pa.e_pos[e]; r.a1 = pa.e_u1[e]; r.a2 = pa.e_u2[e];
+        r.vs = pa.e_vis[e]; r.lc = pa.e_loc[e];
+        r.x1 = pa.e_w1[e]; r.x2 = pa.e_w2[e]; r.y1 = pa.e_r1[e]; r.y2 = pa.e_r2[e];
+        return r;
+    }
+    __device__ __forceinline__ void store(const Regs &r, const PatchItem &it, int tid) const
+    {
+        pos[tid] = r.p0;
+        u1[tid] = r.a1;
+        u2[tid] = r.a2;
+        vis[tid] = tid < it.n_ent ? r.vs : 0u;
+        // an upwind outside the cone reads the zero slot (coupling x a finite 0)
+        const uint32_t l1 = r.lc & 0xFFFFu, l2 = r.lc >> 16;
+        loc[tid] = (l1 == 0xFFFFu ? (uint32_t)it.n_ent : l1) | ((l2 == 0xFFFFu ? (uint32_t)it.n_ent : l2) << 16);
+        w1[tid] = r.x1; w2[tid] = r.x2; r1[tid] = r.y1; r2[tid] = r.y2;
+    }
+    template <typename Tables>
     __device__ __forceinline__ void park(const Tables &pa, const PatchItem &it, int tid) const
     {
-        const bool ok = tid < it.n_ent;
-        const int e = it.ent_off + (ok ? tid : it.n_ent - 1);
-        pos[tid] = pa.e_pos[e];
-        u1[tid] = pa.e_u1[e];
-        u2[tid] = pa.e_u2[e];
-        vis[tid] = ok ? pa.e_vis[e] : 0u;
-        // an upwind outside the cone reads the zero slot (coupling x a finite 0)
-        const uint32_t lc = pa.e_loc[e], l1 = lc & 0xFFFFu, l2 = lc >> 16;
-        loc[tid] = (l1 == 0xFFFFu ? (uint32_t)it.n_ent : l1) | ((l2 == 0xFFFFu ? (uint32_t)it.n_ent : l2) << 16);
-        w1[tid] = pa.e_w1[e]; w2[tid] = pa.e_w2[e]; r1[tid] = pa.e_r1[e]; r2[tid] = pa.e_r2[e];
+        store(load(pa, it.ent_off + (tid < it.n_ent ? tid : it.n_ent - 1)), it, tid);
     }
 };
 
@@ -894,13 +938,18 @@ k_patch_lean(PatchArgs pa)
         patch_reduce_role<T, NT>(pa);
         return;
     }
+    const double e2 = exp2_table_load();                        // (in flight beside the item's record and entry table)
+    typename EntryTable<NT>::Regs early{};
+    if (diag(pa.dbg, kDiagDirectTable))                         // diagnostics: SOME table, at an address no load decides
+        early = EntryTable<NT>::load(pa, min(pa.dbg_ent0 + (patch_row(pa) * 8 + ((int)blockIdx.x & 7)) * pa.dbg_ent_stride + tid, pa.dbg_ent_last));
     PatchItem it;
     if (!patch_item(pa, pa.lgB, it)) return;
     if (diag(pa.dbg, kDiagNoPairLoop)) it.b1 = it.b0;           // diagnostics: the item's overhead alone
     const EntryTable<NT> tab(ptile, 1);
-    tab.park(pa, it, tid);
     if (tid == 0) ptile[it.n_ent] = make_double2(0.0, 0.0);  // the zero slot
-    exp2_table_fill();
+    if (diag(pa.dbg, kDiagDirectTable)) tab.store(early, it, tid);
+    else tab.park(pa, it, tid);
+    exp2_table_store(e2);
     __syncthreads();
     lean_pairs<T, AM, NT, 0>(pair_io<AM>(pa, it.d), it, tab, ptile);
 }
@@ -1053,15 +1102,16 @@ k_patch_quad(PatchArgs pa)
         return;
     }
     // workgroup (item, sib2, split): the pairs 2 sib2, 2 sib2 + 1 of every block among blocks b0 .. b1-1
+    const double e2 = exp2_table_load();                     // (in flight beside the item's record and entry table)
     PatchItem it;
     if (!patch_item(pa, pa.lgB - 1, it)) return;
     const EntryTable<NT> tab(ptile, 2);
-    tab.park(pa, it, tid);
     if (tid == 0) {
         ptile[it.n_ent] = make_double2(0.0, 0.0);            // the zero slots
         ptile[NT + 1 + it.n_ent] = make_double2(0.0, 0.0);
     }
-    exp2_table_fill();
+    tab.park(pa, it, tid);
+    exp2_table_store(e2);
     __syncthreads();
     quad_pairs<AM, NT, false>(pair_io<AM>(pa, it.d), it, tab, ptile);
 }
@@ -1397,6 +1447,7 @@ int ensure_patch_work(vrt_plan *p, int G, const std::vector<int32_t> &group_angl
 {
     if (p->d_patch_work && p->patch_work_groups == G) return VRT_OK;
     p->d_patch_work.reset();
+    p->patch_work_padding = 0;
     const int maxL = p->tile_max_layers;
     std::vector<int4> work;           // two per slot (PatchArgs::wrec)
     p->patch_work_off.assign((size_t)G * (size_t)(maxL + 2) + 1, 0);
@@ -1418,6 +1469,7 @@ int ensure_patch_work(vrt_plan *p, int G, const std::vector<int32_t> &group_angl
             const size_t slots = (m + 7) / 8;
             const size_t base = work.size();
             work.resize(base + slots * 8 * 2, make_int4(0, 0, 0, 0));      // (entries = 0: padding)
+            p->patch_work_padding += (int64_t)(slots * 8 - m);
             for (int x = 0; x < 8; x++) {
                 const size_t b0 = m * (size_t)x / 8, b1 = m * (size_t)(x + 1) / 8;
                 for (size_t t = b0; t < b1; t++) {
@@ -1527,14 +1579,31 @@ int launch_patch_layer(vrt_plan *p, const TileArgs &ta, int npair, int layer, in
         pa.nsplit = nsplit;
         pa.ngrp = nsplit << lgS;
     }
+    set_split(pa, pair_block_count(npair, pa.lgB));
     pa.stride = p->patch_cap + 1;
     pa.cap = p->patch_cap;
     pa.dbg = kDiag ? p->tune.debug_flags : 0;
+    {
+        const int64_t slots = std::max<int64_t>(1, p->patch_work_off.back());
+        pa.dbg_ent_stride = (int)std::max<int64_t>(1, p->n_patch_entries / slots);
+        pa.dbg_ent0 = (int)(w0 * pa.dbg_ent_stride);
+        pa.dbg_ent_last = (int)std::max<int64_t>(0, p->n_patch_entries - 1);
+    }
     pa.wrec = p->d_patch_work + 2 * w0;
     pa.e_pos = p->e_pos; pa.e_u1 = p->e_u1; pa.e_u2 = p->e_u2;
     pa.e_vis = p->e_vis; pa.e_loc = p->e_loc;
     pa.e_w1 = p->e_w1; pa.e_w2 = p->e_w2; pa.e_r1 = p->e_r1; pa.e_r2 = p->e_r2;
-    const dim3 grid((unsigned)(pa.red.nred + (w1 - w0) * pa.ngrp));
+    // the grid: (w1 - w0) / 8 rows of 8 ngrp patch blocks, then the reduction blocks in rows of the same width (a launch
+    // that only reduces is free to choose its width: as wide as the row limit asks)
+    pa.nrow = (int)((w1 - w0) / 8);
+    int64_t gx = 8 * (int64_t)pa.ngrp;
+    if (pa.nrow == 0) gx = std::max<int64_t>(gx, (((int64_t)pa.red.nred + 65534) / 65535 + 7) / 8 * 8);
+    const int64_t gy = pa.nrow + (pa.red.nred + gx - 1) / gx;
+    // (65 535 rows: > 524 000 work-list slots, or as many reduction rows behind fewer, in ONE layer -- a layer of some
+    // 10^8 sites; the one-dimensional grid before had no such limit, DESIGN.md section 5 names it)
+    if (gy > 65535 || gx > INT32_MAX)
+        return fail(VRT_EINVAL, "a layer of this size needs more than 65535 rows of patch and reduction blocks in one launch");
+    const dim3 grid((unsigned)gx, (unsigned)gy);
     const size_t lds = (size_t)(pa.quad ? 2 : Q) * (size_t)pa.stride * sizeof(double2) + (size_t)pa.cap * (4 * sizeof(double) + 5 * sizeof(int32_t));
     const int rc = f32 ? launch_mode<float>(ta.alpha_mode, p->patch_K, Q, p->patch_NT, grid, lds, st, pa)
                        : launch_mode<double>(ta.alpha_mode, p->patch_K, Q, p->patch_NT, grid, lds, st, pa);
@@ -1627,9 +1696,10 @@ static int ensure_patch_chain(vrt_plan *p, int npair, int lgB, int nsplit, bool 
     const int64_t n = g->n, n_patches = p->n_patches;
     const int nblock = pair_block_count(npair, lgB);
     if ((int64_t)nsplit * n_patches >= ((int64_t)1 << 31)) return fail(VRT_EINVAL, "too many (split, patch) progress words");
-    PatchArgs sp;                     // split_blocks reads nsplit and Q only
+    PatchArgs sp;                     // set_split / split_blocks read nsplit and Q only
     sp.nsplit = nsplit;
     sp.Q = 1;
+    set_split(sp, nblock);
     std::vector<int> steps((size_t)nsplit);
     for (int s = 0; s < nsplit; s++) {
         int b0, b1;

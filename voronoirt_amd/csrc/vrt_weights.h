@@ -78,6 +78,10 @@ __device__ __forceinline__ void exp2_table_fill()
 {
     if (threadIdx.x < 32) exp2_table()[threadIdx.x] = kExp2_32[threadIdx.x];
 }
+// the two halves of the fill for a kernel with other loads to wait for at its start: the table's load beside them, the
+// write behind them (every thread writes: no branch for the load to sink into)
+__device__ __forceinline__ double exp2_table_load() { return kExp2_32[threadIdx.x & 31u]; }
+__device__ __forceinline__ void exp2_table_store(double v) { exp2_table()[threadIdx.x & 31u] = v; }
 // Past x = 708.4 the result is subnormal: the final ldexp rounds it to the subnormal grid (steps of 2^-1074).
 __device__ __forceinline__ double exp_neg_tab(double x)          // exp(-x), 0 <= x <= 745
 {
