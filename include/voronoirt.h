@@ -227,6 +227,27 @@ int vrt_rates_populations_native_dev(vrt_grid *g, int64_t nlam, const double *la
                                      const double *d_temperature, const double *d_lte_populations, double hc_over_kB,
                                      double pref_ij, double pref_ji, const double *d_C, const double *d_atom_density,
                                      double *d_R, double *d_populations, void *stream);
+/* The same two on FLOAT sweep-order plane sets (vrt_plan_to_native_dev_f32, vrt_plan_execute_native_dev_f32).  They take the
+ * PLAN: the float layout depends on vrt_plan_native_pair_block_f32(p); VRT_EINVAL before anything is launched on a plan
+ * that is not on the patch path.  Arithmetic in double; the update rounds in exactly these places:
+ *   J     = (float)((double)J_up + (double)J_down)      the J vrt_plan_j_from_native_dev_f32 delivers: the J a caller
+ *                                                        downloads is the J that S was formed from
+ *   S_new = (float)((1 - ε) (double)J + ε (double)B)
+ *   d     = |1 - (double)S_old / (double)S_new|          over the nlam physical wavelengths only
+ * The pad wavelength of an odd nlam is written as 0 and takes no part in the maximum.  B in the up order, the old S read
+ * from dS_up and overwritten there, the down-order copy written to dS_down, either J pointer NULL for a direction without
+ * angles, NaN -> NaN, as vrt_lambda_update_native_dev.  The rates read the same rounded float J, widened, and from there
+ * run the arithmetic of vrt_rates_populations_native_dev; R and the populations stay double. */
+int vrt_lambda_update_native_dev_f32(vrt_plan *p, int64_t nlam, const float *dJ_up, const float *dJ_down,
+                                     const float *dB_up, const double *deps, float *dS_up, float *dS_down,
+                                     double *max_rel_change, void *stream);
+int vrt_rates_populations_native_dev_f32(vrt_plan *p, int64_t nlam, const double *lambda, const int64_t blocks[6],
+                                         const float *dJ_up, const float *dJ_down, const double *planck2,
+                                         double lambda0, double c0, const double *d_doppler_width, const double *d_gamma,
+                                         double sigma_bb_const, const double *sigma_bf1, const double *sigma_bf2,
+                                         const double *d_temperature, const double *d_lte_populations, double hc_over_kB,
+                                         double pref_ij, double pref_ji, const double *d_C, const double *d_atom_density,
+                                         double *d_R, double *d_populations, void *stream);
 
 /* fp32 VALUE path (BASELINE config C5): S, alpha, I_0, J and the per-angle intensities are stored
  * as float, halving the bytes of this bandwidth-bound path; the geometry tables and all
@@ -510,6 +531,19 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change);
 /* J, S (nlam, n), populations (n, 3), R (3, 3, n), gamma [n] of the last iteration; any pointer may be NULL */
 int vrt_lambda_get(vrt_lambda *s, double *J, double *S, double *populations, double *R, double *gamma);
 void vrt_lambda_destroy(vrt_lambda *s);
+/* The same session with FLOAT storage (the fp32 value path: arithmetic in double).  S and J in both sweep orders, B in
+ * the up order, I_0 and the native α are held as float; the double B_0 of the case is staged, converted and freed, so
+ * that after create the session holds no double array of size nλ·n or nλ·n·angles.  An iterate runs the line terms, the
+ * float opacity prologue, vrt_plan_execute_native_dev_f32, vrt_lambda_update_native_dev_f32 and
+ * vrt_rates_populations_native_dev_f32 (their roundings: above); only the criterion's scalar comes back.
+ * VRT_EINVAL on a plan that is not on the patch path or with VRT_LAMBDA_NATIVE=0: there is no fp64 fallback.
+ * vrt_lambda_get returns J and S as doubles holding exactly the float values (J the combined rounded sum);
+ * vrt_lambda_set_state validates as for a double session, then rounds S to float (an S that came from vrt_lambda_get of
+ * such a session is float-representable: it continues bit for bit); vrt_lambda_set_acceleration returns VRT_EINVAL and
+ * changes nothing -- the Ng kernels are written for the [pair][pos][2] double layout, float variants are a later step.
+ * vrt_lambda_storage: the bytes per stored value of a session, 8 or 4 (VRT_EINVAL for NULL). */
+int vrt_lambda_create_f32(vrt_plan *p, const vrt_line_case *lc, const double *weights, vrt_lambda **out);
+int vrt_lambda_storage(const vrt_lambda *s);
 
 /* ---- several GPUs of a node from ONE host process -------------------------------------
  * The object owns a grid + plan per device and -- when the devices are distinct -- an in-process RCCL

@@ -8,7 +8,12 @@
 HIP-event time of each call on the launch stream + the bytes each one has to move (its own floor).
 Synthetic inputs with physical magnitudes (tests/test_physics.py's Ly-α-like atom).
 
-    python tools/iteration_breakdown.py [--a 59 --c 143] [--reps 5]
+    python tools/iteration_breakdown.py [--a 59 --c 143] [--reps 5] [--dtype f32]
+
+--dtype f32: the same table for the float-storage loop (S, J, B, I_0 and α held as float, arithmetic fp64), which exists
+in sweep order only: vrt_line_opacity_dev_f32 -> vrt_plan_execute_native_dev_f32 -> vrt_lambda_update_native_dev_f32 ->
+vrt_rates_populations_native_dev_f32, then the session (vrt_lambda_create_f32 + vrt_lambda_iterate).
+Every time is the median of --reps single timed calls after a warm-up call, with the smallest and largest beside it.
 """
 import argparse
 import os
@@ -27,6 +32,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--a", type=int, default=59)
 ap.add_argument("--c", type=int, default=143)
 ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--dtype", default="f64", choices=["f64", "f32"], help="what S, J, B, I_0 and α are stored as")
 ap.add_argument("--velocity", default="noise", choices=["noise", "smooth"],
                 help="noise: independent normal 8 km/s per SITE (the field of every earlier round: neighbouring sites of a wave fall into "
                      "different regions of the Voigt function's four-region form); smooth: 8 km/s of large-scale flow (a few Fourier modes of "
@@ -114,8 +120,112 @@ def rates():
                               d_pop.data_ptr(), stream=st)
 
 
+def table(steps, what):
+    """one warm-up call, then args.reps calls timed one by one with HIP events: median (min ... max)"""
+    total = 0.0
+    for name, fn, nbytes in steps:
+        fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(args.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        med = float(np.median(ms))
+        total += med
+        print(f"{name:36s} {med:8.3f} ms ({min(ms):.3f} ... {max(ms):.3f})   {nbytes / 1e9:7.2f} GB it must move -> "
+              f"{nbytes / med / 1e6:7.1f} GB/s of those")
+    print(f"{'one iteration':36s} {total:8.3f} ms   ({what})")
+    return total
+
+
+def session_iterate_ms(create, label):
+    """the library-owned session at all 91 wavelengths: wall time of vrt_lambda_iterate, median (min ... max) of args.reps"""
+    import ctypes
+    import time
+    L = _lib.load()
+    plan_h, wq = api._quadrature_plan(sites, "ul7n12.dat", 3)
+    lc, keep = case.c_struct()
+    h = ctypes.c_void_p()
+    api.check(getattr(L, create)(plan_h._h, ctypes.byref(lc), api._d(api._f64(wq)), ctypes.byref(h)))
+    d = ctypes.c_double()
+    api.check(L.vrt_lambda_iterate(h, ctypes.byref(d)))
+    ms = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        api.check(L.vrt_lambda_iterate(h, ctypes.byref(d)))
+        ms.append((time.perf_counter() - t0) * 1e3)
+    print(f"{label}: {np.median(ms):.1f} ms ({min(ms):.1f} ... {max(ms):.1f}) per Λ-iteration at {nlam_all} wavelengths "
+          f"(only the criterion's scalar crosses PCIe); criterion {d.value:.6g}")
+    L.vrt_lambda_destroy(h)
+
+
+def line_case():
+    return vrt.LineCase(lam=lam, blocks=blocks, lambda0=lambda0, c0=C0, velocity=velocity, doppler=doppler,
+                        gamma_static=gamma, gamma_unsold=1e-9 * np.ones(n), alpha_cont=alpha_cont,
+                        eps=10 ** rng.uniform(-2.5, -0.5, n), temperature=T, atom_density=atom,
+                        B0=(1.0 + (z - bounds[0]) / (bounds[1] - bounds[0]))[:, None] * np.ones((1, nlam_all)), lte=lte, C=Cmat,
+                        planck2=planck2, sigma_bf1=sig1, sigma_bf2=sig2,
+                        strength_const=float(np.median(strength / lte[0])), Bij=1.0, Bji=0.25,
+                        sigma_bb_const=H_PLANCK * C0 / (4 * np.pi * lambda0) * 4.5e20, hc_over_kB=H_PLANCK * C0 / K_B,
+                        pref_ij=2 * np.pi / (H_PLANCK * C0) / 1000.0, pref_ji=2 * np.pi / (H_PLANCK * C0))
+
+
 Jline = torch.zeros((n, nbb), device=dev, dtype=torch.float64)
 A = nq
+if args.dtype == "f32":
+    # ---- the float-storage loop: sweep-order float plane sets, no caller-layout form ------------------------------------
+    f4 = torch.float32
+    cnt = plan.native_plane_count(nbb)
+    S_nat = [torch.empty(cnt, device=dev, dtype=f4) for _ in range(2)]
+    B_up = torch.empty(cnt, device=dev, dtype=f4)
+    Jn = [torch.zeros(cnt, device=dev, dtype=f4) for _ in range(2)]
+    plan.to_native_dev(nbb, nbb, S.to(f4).data_ptr(), S_nat[0].data_ptr(), S_nat[1].data_ptr(), stream=st, f32=True)
+    plan.to_native_dev(nbb, nbb, B.to(f4).data_ptr(), B_up.data_ptr(), 0, stream=st, f32=True)
+    eps_site = eps[:, 0].contiguous()
+    cnt_all = plan.native_plane_count(nlam_all)
+    J_all = [torch.zeros(cnt_all, device=dev, dtype=f4) for _ in range(2)]
+    plan.to_native_dev(nlam_all, nlam_all, J.to(f4).data_ptr(), J_all[0].data_ptr(), 0, stream=st, f32=True)
+    native4 = torch.empty(plan.native_alpha_count(nbb), device=dev, dtype=f4)
+    I04 = I0.to(f4)
+    consts = (H_PLANCK * C0 / (4 * np.pi * lambda0) * 4.5e20, H_PLANCK * C0 / K_B, 2 * np.pi / (H_PLANCK * C0) / 1000.0,
+              2 * np.pi / (H_PLANCK * C0))
+
+    def opacity_f32():
+        plan.line_opacity_dev(lam[:nbb], lambda0, C0, d_vel.data_ptr(), d_dop.data_ptr(), d_gam.data_ptr(),
+                              d_str.data_ptr(), d_ac.data_ptr(), native4.data_ptr(), stream=st, f32=True)
+
+    def solve_f32():
+        plan.execute_native_dev(nbb, S_nat[0].data_ptr(), S_nat[1].data_ptr(), native4.data_ptr(), _lib.ALPHA_ANGLE_NATIVE, w,
+                                dJ_up=Jn[0].data_ptr(), dJ_down=Jn[1].data_ptr(), dI0_up=I04.data_ptr(), stream=st, f32=True)
+
+    def update_f32():
+        api.lambda_update_native_dev_f32(plan, nbb, Jn[0].data_ptr(), Jn[1].data_ptr(), B_up.data_ptr(), eps_site.data_ptr(),
+                                         S_nat[0].data_ptr(), S_nat[1].data_ptr(), stream=st)
+
+    def rates_f32():
+        api.rates_populations_native_dev_f32(plan, lam, blocks, J_all[0].data_ptr(), J_all[1].data_ptr(), planck2, lambda0, C0,
+                                             d_dop.data_ptr(), d_gam.data_ptr(), consts[0], sig1, sig2, d_T.data_ptr(),
+                                             d_lte.data_ptr(), consts[1], consts[2], consts[3], d_C.data_ptr(), d_atom.data_ptr(),
+                                             d_R.data_ptr(), d_pop.data_ptr(), stream=st)
+
+    print(f"{n} sites, {A} angles, {nbb} line + {2 * nbf} continuum wavelengths, float storage "
+          f"({plan.native_pair_block_f32} pairs per block)")
+    table((("vrt_line_opacity_dev_f32", opacity_f32, 4.0 * A * n * (nbb + 1) + 8.0 * 8 * n),
+           ("vrt_plan_execute_native_dev_f32", solve_f32, float(n) * A * nbb * (20.0 + 40.0 / nbb)),
+           # J_up, J_down, B, S_old in; S_up, S_down out: 4 float reads + 2 writes per element (+ ε and the two index words per site)
+           ("vrt_lambda_update_native_dev_f32", update_f32, 4.0 * 6 * n * (nbb + 1) + 16.0 * n),
+           ("vrt_rates_populations_native_f32", rates_f32, 4.0 * 2 * n * (nlam_all + 1) + 8.0 * 30 * n)),
+          f"path {plan.last_path}; float S and J in sweep order")
+    assert all(torch.isfinite(x).all() for x in Jn) and torch.isfinite(d_pop).all()
+    plan.close()
+    case = line_case()
+    session_iterate_ms("vrt_lambda_create_f32", "vrt_lambda_iterate, float storage")
+    sites.close()
+    sys.exit(0)
 steps = (
     ("vrt_line_opacity_dev", opacity, 8.0 * (A * n * (nbb + 1) + 8 * n)),               # writes α of every angle
     ("vrt_plan_execute_dev (J)", solve, float(n) * A * nbb * (40.0 + 40.0 / nbb)),      # §8d algorithmic bytes
@@ -123,20 +233,7 @@ steps = (
     ("vrt_rates_populations_dev", rates, 8.0 * (n * nlam_all + 30 * n)),               # J in; R, populations, C out
 )
 print(f"{n} sites, {A} angles, {nbb} line + {2 * nbf} continuum wavelengths")
-total = 0.0
-for name, fn, nbytes in steps:
-    fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(args.reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / args.reps
-    total += ms
-    print(f"{name:28s} {ms:8.3f} ms   {nbytes / 1e9:7.2f} GB it must move -> {nbytes / ms / 1e6:7.1f} GB/s of those")
-print(f"{'one iteration':28s} {total:8.3f} ms   (path {plan.last_path}; S and J in the caller's (n, nlam) layout)")
+table(steps, f"path {plan.last_path}; S and J in the caller's (n, nlam) layout")
 assert torch.isfinite(Jline).all() and torch.isfinite(d_pop).all()
 
 # ---- the same iteration with S and J kept in SWEEP ORDER between the steps (what vrt_lambda_iterate does) ------------------
@@ -176,33 +273,13 @@ steps_n = (
     ("vrt_lambda_update_native_dev", update_native, 8.0 * (6 * n * nbb + n)),              # J_up, J_down, B, S_old in; S_up, S_down out
     ("vrt_rates_populations_native", rates_native, 8.0 * (2 * n * nlam_all + 30 * n)),
 )
-total_n = 0.0
-for name, fn, nbytes in steps_n:
-    fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(args.reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / args.reps
-    total_n += ms
-    print(f"{name:28s} {ms:8.3f} ms   {nbytes / 1e9:7.2f} GB it must move -> {nbytes / ms / 1e6:7.1f} GB/s of those")
-print(f"{'one iteration':28s} {total_n:8.3f} ms   (path {plan.last_path}; S and J in sweep order: no layout change inside the loop)")
+table(steps_n, f"path {plan.last_path}; S and J in sweep order: no layout change inside the loop")
 assert all(torch.isfinite(x).all() for x in Jn) and torch.isfinite(d_pop).all()
 plan.close()
 
 # ---- the same from HOST arrays (what the Julia shim calls): PCIe-inclusive wall times ------------------
 import time  # noqa: E402
-case = vrt.LineCase(lam=lam, blocks=blocks, lambda0=lambda0, c0=C0, velocity=velocity, doppler=doppler,
-                    gamma_static=gamma, gamma_unsold=1e-9 * np.ones(n), alpha_cont=alpha_cont,
-                    eps=10 ** rng.uniform(-2.5, -0.5, n), temperature=T, atom_density=atom,
-                    B0=(1.0 + (z - bounds[0]) / (bounds[1] - bounds[0]))[:, None] * np.ones((1, nlam_all)), lte=lte, C=Cmat,
-                    planck2=planck2, sigma_bf1=sig1, sigma_bf2=sig2,
-                    strength_const=float(np.median(strength / lte[0])), Bij=1.0, Bji=0.25,
-                    sigma_bb_const=H_PLANCK * C0 / (4 * np.pi * lambda0) * 4.5e20, hc_over_kB=H_PLANCK * C0 / K_B,
-                    pref_ij=2 * np.pi / (H_PLANCK * C0) / 1000.0, pref_ji=2 * np.pi / (H_PLANCK * C0))
+case = line_case()
 S_h = np.ascontiguousarray(case.B0[:, :nbb])
 line_only = vrt.LineCase(**{**{k: getattr(case, k) for k in vrt.LineCase.FIELDS}, "lam": lam[:nbb], "B0": S_h})
 vrt.J_lambda_voronoi_line(S_h, lte, sites, line_only, "ul7n12.dat")            # warm-up: plan, staging buffers
@@ -233,17 +310,5 @@ t0 = time.perf_counter()
 Jl, Sl, pl, hist = vrt.Lambda_voronoi_host(0.0, 4, sites, case, "ul7n12.dat")
 dt = time.perf_counter() - t0
 print(f"vrt_lambda_create + 4 x vrt_lambda_iterate + vrt_lambda_get ({nlam_all} wavelengths): {dt * 1e3:.0f} ms in all; history {hist}")
-L = _lib.load()
-import ctypes  # noqa: E402
-plan_h, wq = api._quadrature_plan(sites, "ul7n12.dat", 3)
-lc, keep = case.c_struct()
-h = ctypes.c_void_p()
-api.check(L.vrt_lambda_create(plan_h._h, ctypes.byref(lc), api._d(api._f64(wq)), ctypes.byref(h)))
-d = ctypes.c_double()
-api.check(L.vrt_lambda_iterate(h, ctypes.byref(d)))
-t0 = time.perf_counter()
-for _ in range(3):
-    api.check(L.vrt_lambda_iterate(h, ctypes.byref(d)))
-print(f"vrt_lambda_iterate: {(time.perf_counter() - t0) / 3 * 1e3:.1f} ms per Λ-iteration at {nlam_all} wavelengths (only the criterion's scalar crosses PCIe)")
-L.vrt_lambda_destroy(h)
+session_iterate_ms("vrt_lambda_create", "vrt_lambda_iterate")
 sites.close()

@@ -87,6 +87,10 @@ PROTOTYPES = {
     "vrt_rates_populations_native_dev": (ctypes.c_int, [vp, c_i64, p_dbl, p_i64, vp, vp, p_dbl, c_dbl, c_dbl, vp, vp,
                                                         c_dbl, p_dbl, p_dbl, vp, vp, c_dbl, c_dbl, c_dbl, vp, vp, vp,
                                                         vp, vp]),
+    "vrt_lambda_update_native_dev_f32": (ctypes.c_int, [vp, c_i64, vp, vp, vp, vp, vp, vp, p_dbl, vp]),
+    "vrt_rates_populations_native_dev_f32": (ctypes.c_int, [vp, c_i64, p_dbl, p_i64, vp, vp, p_dbl, c_dbl, c_dbl, vp, vp,
+                                                            c_dbl, p_dbl, p_dbl, vp, vp, c_dbl, c_dbl, c_dbl, vp, vp, vp,
+                                                            vp, vp]),
     "vrt_grid_get_storage_order": (ctypes.c_int, [vp, ctypes.c_int, p_i64]),
     "vrt_plan_native_alpha_count": (c_i64, [vp, c_i64]),
     "vrt_plan_native_pair_block": (ctypes.c_int, [vp]),
@@ -99,6 +103,8 @@ PROTOTYPES = {
                                              p_dbl, p_dbl, p_dbl, p_dbl, p_dbl]),
     "vrt_line_terms_dev": (ctypes.c_int, [vp, vp, vp, vp, c_dbl, c_dbl, c_dbl, vp, vp, vp]),
     "vrt_lambda_create": (ctypes.c_int, [vp, ctypes.POINTER(LineCaseStruct), p_dbl, ctypes.POINTER(vp)]),
+    "vrt_lambda_create_f32": (ctypes.c_int, [vp, ctypes.POINTER(LineCaseStruct), p_dbl, ctypes.POINTER(vp)]),
+    "vrt_lambda_storage": (ctypes.c_int, [vp]),
     "vrt_lambda_iterate": (ctypes.c_int, [vp, p_dbl]),
     "vrt_lambda_get": (ctypes.c_int, [vp, p_dbl, p_dbl, p_dbl, p_dbl, p_dbl]),
     "vrt_lambda_destroy": (None, [vp]),

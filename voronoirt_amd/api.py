@@ -1227,6 +1227,32 @@ def rates_populations_native_dev(sites: VoronoiSites, lam, blocks, dJ_up: int, d
                                                        d_R, d_populations, stream or None))
 
 
+def lambda_update_native_dev_f32(plan: "FormalPlan", nlam: int, dJ_up: int, dJ_down: int, dB_up: int, deps: int, dS_up: int,
+                                 dS_down: int, stream: int = 0) -> float:
+    """`lambda_update_native_dev` on the plan's float32 plane sets (`vrt_lambda_update_native_dev_f32`; ε stays float64):
+    J = f32(J_up + J_down), S_new = f32((1 - ε) J + ε B), the criterion from the stored float32 values."""
+    out = ctypes.c_double()
+    check(_lib.load().vrt_lambda_update_native_dev_f32(plan._h, nlam, dJ_up or None, dJ_down or None, dB_up, deps, dS_up,
+                                                       dS_down, ctypes.byref(out), stream or None))
+    return out.value
+
+
+def rates_populations_native_dev_f32(plan: "FormalPlan", lam, blocks, dJ_up: int, dJ_down: int, planck2, lambda0: float, c0: float,
+                                     d_doppler: int, d_gamma: int, sigma_bb_const: float, sigma_bf1, sigma_bf2,
+                                     d_temperature: int, d_lte: int, hc_over_kB: float, pref_ij: float, pref_ji: float,
+                                     d_C: int, d_atom_density: int, d_R: int, d_populations: int, stream: int = 0) -> None:
+    """`rates_populations_native_dev` with J read from the plan's float32 plane sets (`vrt_rates_populations_native_dev_f32`):
+    J = f32(J_up + J_down) widened; R and the populations are float64."""
+    lam, planck2 = _f64(lam), _f64(planck2)
+    blocks = np.ascontiguousarray(blocks, dtype=np.int64)
+    s1, s2 = _f64(sigma_bf1), _f64(sigma_bf2)
+    check(_lib.load().vrt_rates_populations_native_dev_f32(plan._h, lam.size, _d(lam), _i(blocks), dJ_up or None, dJ_down or None,
+                                                           _d(planck2), float(lambda0), float(c0), d_doppler, d_gamma,
+                                                           float(sigma_bb_const), _d(s1), _d(s2), d_temperature, d_lte,
+                                                           float(hc_over_kB), float(pref_ij), float(pref_ji), d_C, d_atom_density,
+                                                           d_R, d_populations, stream or None))
+
+
 def rates_populations_dev(sites: VoronoiSites, lam, blocks, ld: int, dJ: int, planck2, lambda0: float, c0: float,
                           d_doppler: int, d_gamma: int, sigma_bb_const: float, sigma_bf1, sigma_bf2,
                           d_temperature: int, d_lte: int, hc_over_kB: float, pref_ij: float, pref_ji: float,
@@ -1432,9 +1458,16 @@ def J_lambda_voronoi_line(S_lambda, populations, sites: VoronoiSites, case: Line
     return J
 
 
+def _storage_f32(storage, who: str) -> bool:
+    if storage not in ("f64", "f32"):
+        raise ValueError(f"{who}: storage must be 'f64' or 'f32'")
+    return storage == "f32"
+
+
 def _Lambda_voronoi_native(eps_conv: float, maxiter: int, sites: VoronoiSites, case: LineCase, quadrature: str, n_sweeps: int,
-                           S0=None, populations0=None):
+                           S0=None, populations0=None, f32: bool = False):
     import torch
+    vt = torch.float32 if f32 else torch.float64                # what S, J, B, I_0 and α are stored as
     w, th, ph, nq = read_quadrature(quadrature)
     dev = torch.device("cuda", sites.device)
     n, nlam = sites.n, int(np.asarray(case.lam).size)
@@ -1446,16 +1479,19 @@ def _Lambda_voronoi_native(eps_conv: float, maxiter: int, sites: VoronoiSites, c
     d_B, d_lte, d_C, d_atom = t(case.B0), t(case.lte), t(case.C), t(case.atom_density)
     pops = d_lte.clone() if populations0 is None else t(populations0)
     d_S0 = d_B if S0 is None else t(S0)
+    d_Bv, d_S0v = d_B.to(vt), d_S0.to(vt)
     st = torch.cuda.current_stream().cuda_stream
     cnt = plan.native_plane_count(nlam)
-    S_up, S_dn, B_up, J_up, J_dn = (torch.zeros(cnt, dtype=torch.float64, device=dev) for _ in range(5))
-    plan.to_native_dev(nlam, nlam, d_S0.data_ptr(), S_up.data_ptr(), S_dn.data_ptr(), stream=st)     # S_new = B_0 (or S0)
-    plan.to_native_dev(nlam, nlam, d_B.data_ptr(), B_up.data_ptr(), 0, stream=st)
-    native = torch.empty(plan.native_alpha_count(nlam), dtype=torch.float64, device=dev)
+    S_up, S_dn, B_up, J_up, J_dn = (torch.zeros(cnt, dtype=vt, device=dev) for _ in range(5))
+    plan.to_native_dev(nlam, nlam, d_S0v.data_ptr(), S_up.data_ptr(), S_dn.data_ptr(), stream=st, f32=f32)     # S_new = B_0 (or S0)
+    plan.to_native_dev(nlam, nlam, d_Bv.data_ptr(), B_up.data_ptr(), 0, stream=st, f32=f32)
+    native = torch.empty(plan.native_alpha_count(nlam), dtype=vt, device=dev)
     d_R = torch.empty((n, 3, 3), dtype=torch.float64, device=dev)
     d_gam, strength = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
     n1 = int(sites.layers_up[1] - 1)
-    I0_up = d_B[torch.as_tensor(sites.perm_up[:n1] - 1, device=dev)].contiguous()
+    I0_up = d_Bv[torch.as_tensor(sites.perm_up[:n1] - 1, device=dev)].contiguous()
+    update, rates, owner = ((lambda_update_native_dev_f32, rates_populations_native_dev_f32, plan) if f32 else
+                            (lambda_update_native_dev, rates_populations_native_dev, sites))
     history = []
     diff, i = 1.0, 0
     try:
@@ -1463,35 +1499,35 @@ def _Lambda_voronoi_native(eps_conv: float, maxiter: int, sites: VoronoiSites, c
             line_terms_dev(sites, d_gs.data_ptr(), d_gu.data_ptr(), pops.data_ptr(), case.strength_const, case.Bij, case.Bji,
                            d_gam.data_ptr(), strength.data_ptr(), stream=st)
             plan.line_opacity_dev(case.lam, case.lambda0, case.c0, d_vel.data_ptr(), d_dop.data_ptr(), d_gam.data_ptr(),
-                                  strength.data_ptr(), d_ac.data_ptr(), native.data_ptr(), stream=st)
+                                  strength.data_ptr(), d_ac.data_ptr(), native.data_ptr(), stream=st, f32=f32)
             plan.execute_native_dev(nlam, S_up.data_ptr(), S_dn.data_ptr(), native.data_ptr(), _lib.ALPHA_ANGLE_NATIVE, w,
-                                    dJ_up=J_up.data_ptr(), dJ_down=J_dn.data_ptr(), dI0_up=I0_up.data_ptr(), stream=st)
-            diff = lambda_update_native_dev(sites, nlam, J_up.data_ptr(), J_dn.data_ptr(), B_up.data_ptr(), d_eps.data_ptr(),
-                                            S_up.data_ptr(), S_dn.data_ptr(), stream=st)
+                                    dJ_up=J_up.data_ptr(), dJ_down=J_dn.data_ptr(), dI0_up=I0_up.data_ptr(), stream=st, f32=f32)
+            diff = update(owner, nlam, J_up.data_ptr(), J_dn.data_ptr(), B_up.data_ptr(), d_eps.data_ptr(),
+                          S_up.data_ptr(), S_dn.data_ptr(), stream=st)
             new_pops = torch.empty_like(pops)
-            rates_populations_native_dev(sites, case.lam, case.blocks, J_up.data_ptr(), J_dn.data_ptr(), case.planck2, case.lambda0,
-                                         case.c0, d_dop.data_ptr(), d_gam.data_ptr(), case.sigma_bb_const, case.sigma_bf1,
-                                         case.sigma_bf2, d_T.data_ptr(), d_lte.data_ptr(), case.hc_over_kB, case.pref_ij,
-                                         case.pref_ji, d_C.data_ptr(), d_atom.data_ptr(), d_R.data_ptr(), new_pops.data_ptr(), stream=st)
+            rates(owner, case.lam, case.blocks, J_up.data_ptr(), J_dn.data_ptr(), case.planck2, case.lambda0,
+                  case.c0, d_dop.data_ptr(), d_gam.data_ptr(), case.sigma_bb_const, case.sigma_bf1,
+                  case.sigma_bf2, d_T.data_ptr(), d_lte.data_ptr(), case.hc_over_kB, case.pref_ij,
+                  case.pref_ji, d_C.data_ptr(), d_atom.data_ptr(), d_R.data_ptr(), new_pops.data_ptr(), stream=st)
             pops = new_pops
             history.append(diff)
             i += 1
             if diff != diff:
                 import warnings
                 warnings.warn(f"Lambda_voronoi: NaN DIFF! at iteration {i} -- stopping, results are not converged")
-        J, S = torch.zeros((n, nlam), dtype=torch.float64, device=dev), torch.zeros((n, nlam), dtype=torch.float64, device=dev)
-        plan.J_from_native_dev(nlam, nlam, J_up.data_ptr(), J_dn.data_ptr(), J.data_ptr(), stream=st)
-        plan.from_native_dev(1, nlam, nlam, S_up.data_ptr(), S.data_ptr(), stream=st)
+        J, S = torch.zeros((n, nlam), dtype=vt, device=dev), torch.zeros((n, nlam), dtype=vt, device=dev)
+        plan.J_from_native_dev(nlam, nlam, J_up.data_ptr(), J_dn.data_ptr(), J.data_ptr(), stream=st, f32=f32)
+        plan.from_native_dev(1, nlam, nlam, S_up.data_ptr(), S.data_ptr(), stream=st, f32=f32)
         torch.cuda.synchronize()
         plan.check()
-        return J.cpu().numpy(), S.cpu().numpy(), pops.cpu().numpy(), history
+        return J.double().cpu().numpy(), S.double().cpu().numpy(), pops.cpu().numpy(), history
     finally:
         plan.close()
 
 
 def Lambda_voronoi_host(eps_conv: float, maxiter: int, sites: VoronoiSites, case: LineCase, quadrature: str,
                         n_sweeps: int = 3, ng=None, S0=None, populations0=None, checkpoint=None, checkpoint_every: int = 1,
-                        resume=None):
+                        resume=None, storage: str = "f64"):
     """Λ_voronoi (src/lambda_iteration.jl:205-300) for a host WITHOUT device arrays: the library owns the device
     state (`vrt_lambda_create` / `_iterate` / `_get`), one call per iteration, only the criterion's scalar
     comes back inside the loop.  Returns (J, S_new, populations (3, n), history).
@@ -1502,14 +1538,20 @@ def Lambda_voronoi_host(eps_conv: float, maxiter: int, sites: VoronoiSites, case
     reference's recover_voronoi); either alone replaces that half.  The run continues bit for bit as the one that
     produced them.  checkpoint="run.npz": `write_checkpoint` after every `checkpoint_every`-th iterate and after the
     last.  resume="run.npz": start from such a file; the returned history is the file's followed by the new scalars,
-    `maxiter` counts the new iterates; a file whose shapes do not match the case raises ValueError before any device work."""
+    `maxiter` counts the new iterates; a file whose shapes do not match the case raises ValueError before any device work.
+    storage="f32": the session holds S, J, B, I_0 and α as float32 (`vrt_lambda_create_f32`; arithmetic stays float64, the
+    patch path only); the returned J and S are float64 arrays of float32-representable values, checkpoints work unchanged,
+    and `ng` raises ValueError before any device work (the Ng kernels work on float64 planes)."""
     L = _lib.load()
+    f32 = _storage_f32(storage, "Lambda_voronoi_host")
+    if f32 and ng is not None:
+        raise ValueError("Lambda_voronoi_host: ng is not available with storage='f32'")
     lc, keep = case.c_struct()
     n, nlam = sites.n, int(keep["lam"].size)
     start = _start_state(S0, populations0, resume, checkpoint_every, n, nlam, "Lambda_voronoi_host")
     plan, w = _quadrature_plan(sites, quadrature, n_sweeps)
     h = ctypes.c_void_p()
-    check(L.vrt_lambda_create(plan._h, ctypes.byref(lc), _d(_f64(w)), ctypes.byref(h)))
+    check((L.vrt_lambda_create_f32 if f32 else L.vrt_lambda_create)(plan._h, ctypes.byref(lc), _d(_f64(w)), ctypes.byref(h)))
     try:
         if ng is not None:
             check(L.vrt_lambda_set_acceleration(h, 2, *_ng_settings(ng)))
@@ -1517,6 +1559,8 @@ def Lambda_voronoi_host(eps_conv: float, maxiter: int, sites: VoronoiSites, case
                                                       checkpoint_every, ng, "Lambda_voronoi_host")
         if i == 0:
             S[:] = keep["B0"] if start[0] is None else start[0]
+            if f32:
+                S[:] = S.astype(np.float32)
             pops[:] = keep["lte"] if start[1] is None else start[1]
         return (J, S, pops, history) if ng is None else (J, S, pops, history, steps)
     finally:
@@ -1524,7 +1568,7 @@ def Lambda_voronoi_host(eps_conv: float, maxiter: int, sites: VoronoiSites, case
 
 
 def Lambda_voronoi(eps_conv: float, maxiter: int, sites: VoronoiSites, case: LineCase, quadrature: str,
-                   n_sweeps: int = 3, native: bool = False, S0=None, populations0=None):
+                   n_sweeps: int = 3, native: bool = False, S0=None, populations0=None, storage: str = "f64"):
     """Λ_voronoi (src/lambda_iteration.jl:205-300) with everything between two convergence checks on
     the device, over the device-pointer entry points: per iteration `vrt_line_terms_dev` (γ and the line
     strength of the current populations, :72-75), `vrt_line_opacity_dev` (α_tot of every angle, :72-96),
@@ -1536,15 +1580,22 @@ def Lambda_voronoi(eps_conv: float, maxiter: int, sites: VoronoiSites, case: Lin
     change inside the loop, the same results bit for bit.
     S0 (n, nλ), populations0 (3, n): the loop starts from them instead (S finite and > 0, populations finite and >= 0;
     ValueError otherwise) and continues bit for bit as the run that produced them.
+    storage="f32" (with native=True; ValueError otherwise): the plane sets, I_0 and α are float32 torch tensors and the loop
+    runs the `_f32` entry points (`vrt_line_opacity_dev_f32`, `vrt_plan_execute_native_dev_f32`,
+    `vrt_lambda_update_native_dev_f32`, `vrt_rates_populations_native_dev_f32`); J and S come back as float64 arrays of
+    float32-representable values, the same as `Lambda_voronoi_host(storage="f32")` bit for bit.
     Returns (J, S_new, populations (3, n), history of the criterion's differences) as numpy arrays."""
     import torch
+    f32 = _storage_f32(storage, "Lambda_voronoi")
+    if f32 and not native:
+        raise ValueError("Lambda_voronoi: storage='f32' needs native=True (the float loop runs on sweep-order plane sets)")
     S0, populations0 = _check_state_shapes(S0, populations0, sites.n, int(np.asarray(case.lam).size), "Lambda_voronoi")
     if S0 is not None and not (np.isfinite(S0).all() and (S0 > 0).all()):
         raise ValueError("Lambda_voronoi: S0 must be finite and > 0 everywhere")
     if populations0 is not None and not (np.isfinite(populations0).all() and (populations0 >= 0).all()):
         raise ValueError("Lambda_voronoi: populations0 must be finite and >= 0 everywhere")
     if native:
-        return _Lambda_voronoi_native(eps_conv, maxiter, sites, case, quadrature, n_sweeps, S0, populations0)
+        return _Lambda_voronoi_native(eps_conv, maxiter, sites, case, quadrature, n_sweeps, S0, populations0, f32)
     w, th, ph, nq = read_quadrature(quadrature)
     dev = torch.device("cuda", sites.device)
     n, nlam = sites.n, int(np.asarray(case.lam).size)

@@ -1472,6 +1472,21 @@ int vrt_lambda_update_native_dev(vrt_grid *g, int64_t nlam, const double *dJ_up,
     });
 }
 
+int vrt_lambda_update_native_dev_f32(vrt_plan *p, int64_t nlam, const float *dJ_up, const float *dJ_down, const float *dB_up,
+                                     const double *deps, float *dS_up, float *dS_down, double *max_rel_change, void *stream)
+{
+    return guarded([&] {
+        if (!p || (!dJ_up && !dJ_down) || !dB_up || !deps || !dS_up || !dS_down || !max_rel_change)
+            return fail(VRT_EINVAL, "NULL argument");
+        if (nlam < 1) return fail(VRT_EINVAL, "need nlam >= 1");
+        if (int rc = native_planes_ok(p, true)) return rc;
+        hipStream_t st = (hipStream_t)stream;
+        return lambda_update_call(p->g, max_rel_change, st, "vrt_lambda_update_native_dev_f32", [&](unsigned long long *d_res) {
+            return launch_lambda_update_native_f32(p, nlam, dJ_up, dJ_down, dB_up, deps, dS_up, dS_down, d_res, st);
+        });
+    });
+}
+
 // wavelength-sized host arrays -> the grid's device scratch (caller holds g->mu).  The scratch is
 // shared by successive calls, possibly on different streams: the copy first waits for the kernel of
 // the previous call that read it (small_ev, recorded by small_done after that launch).  The values
@@ -1556,9 +1571,10 @@ static int rates_populations_impl(vrt_grid *g, int64_t nlam, int64_t ld, const d
                               double sigma_bb_const, const double *sigma_bf1, const double *sigma_bf2,
                               const double *d_temperature, const double *d_lte_populations, double hc_over_kB,
                               double pref_ij, double pref_ji, const double *d_C, const double *d_atom_density,
-                              double *d_R, double *d_populations, void *stream)
+                              double *d_R, double *d_populations, void *stream,
+                              vrt_plan *p32 = nullptr, const float *fJ_up = nullptr, const float *fJ_down = nullptr)   // float plane sets of p32
 {
-    if (!g || !lambda || !blocks || (!dJ && !dJ_up && !dJ_down) || !planck2 || !d_doppler_width || !d_gamma || !sigma_bf1 || !sigma_bf2 ||
+    if (!g || !lambda || !blocks || (!dJ && !dJ_up && !dJ_down && !fJ_up && !fJ_down) || !planck2 || !d_doppler_width || !d_gamma || !sigma_bf1 || !sigma_bf2 ||
         !d_temperature || !d_lte_populations || !d_C || !d_atom_density || !d_R || !d_populations)
         return fail(VRT_EINVAL, "NULL argument");
     if (nlam < 2 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 2 and ld >= nlam");
@@ -1568,6 +1584,7 @@ static int rates_populations_impl(vrt_grid *g, int64_t nlam, int64_t ld, const d
     return guarded([&] {
         int rc = use_device(g->device);
         if (rc) return rc;
+        if (p32 && (rc = native_planes_ok(p32, true))) return rc;
         std::lock_guard<std::mutex> lock(g->mu);
         std::vector<double> h;
         h.insert(h.end(), lambda, lambda + nlam);
@@ -1575,6 +1592,11 @@ static int rates_populations_impl(vrt_grid *g, int64_t nlam, int64_t ld, const d
         h.insert(h.end(), sigma_bf1, sigma_bf1 + (blocks[3] - blocks[2]));
         h.insert(h.end(), sigma_bf2, sigma_bf2 + (blocks[5] - blocks[4]));
         if ((rc = upload_small(g, h, (hipStream_t)stream))) return rc;
+        if (p32)
+            rc = launch_rates_populations_f32(p32, nlam, blocks, g->d_small, lambda0, c0, d_doppler_width, d_gamma, sigma_bb_const,
+                                              d_temperature, d_lte_populations, hc_over_kB, pref_ij, pref_ji, d_C, d_atom_density,
+                                              d_R, d_populations, (hipStream_t)stream, fJ_up, fJ_down);
+        else
         rc = launch_rates_populations(g, nlam, ld, blocks, g->d_small, dJ, lambda0, c0, d_doppler_width,
                                       d_gamma, sigma_bb_const, d_temperature, d_lte_populations, hc_over_kB,
                                       pref_ij, pref_ji, d_C, d_atom_density, d_R, d_populations,
@@ -1609,6 +1631,20 @@ int vrt_rates_populations_native_dev(vrt_grid *g, int64_t nlam, const double *la
     return rates_populations_impl(g, nlam, nlam, lambda, blocks, nullptr, dJ_up, dJ_down, planck2, lambda0, c0, d_doppler_width, d_gamma,
                                   sigma_bb_const, sigma_bf1, sigma_bf2, d_temperature, d_lte_populations, hc_over_kB, pref_ij, pref_ji,
                                   d_C, d_atom_density, d_R, d_populations, stream);
+}
+
+int vrt_rates_populations_native_dev_f32(vrt_plan *p, int64_t nlam, const double *lambda, const int64_t blocks[6],
+                                         const float *dJ_up, const float *dJ_down, const double *planck2,
+                                         double lambda0, double c0, const double *d_doppler_width, const double *d_gamma,
+                                         double sigma_bb_const, const double *sigma_bf1, const double *sigma_bf2,
+                                         const double *d_temperature, const double *d_lte_populations, double hc_over_kB,
+                                         double pref_ij, double pref_ji, const double *d_C, const double *d_atom_density,
+                                         double *d_R, double *d_populations, void *stream)
+{
+    if (!p || (!dJ_up && !dJ_down)) return fail(VRT_EINVAL, "NULL argument");
+    return rates_populations_impl(p->g, nlam, nlam, lambda, blocks, nullptr, nullptr, nullptr, planck2, lambda0, c0, d_doppler_width,
+                                  d_gamma, sigma_bb_const, sigma_bf1, sigma_bf2, d_temperature, d_lte_populations, hc_over_kB,
+                                  pref_ij, pref_ji, d_C, d_atom_density, d_R, d_populations, stream, p, dJ_up, dJ_down);
 }
 
 static int single_solve(vrt_grid *g, int dir, const double k[3], const double *S, const double *I0,

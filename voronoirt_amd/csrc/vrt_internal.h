@@ -599,12 +599,19 @@ constexpr size_t kUpdateWords = 3;   // a grid's d_scalars: the criterion's maxi
 int launch_axpy(size_t count, const double *d_src, double *d_dst, hipStream_t st);
 int launch_gather_rows(int64_t rows, int64_t nlam, int64_t ld, const int32_t *d_order, const double *d_src, double *d_dst,
                        hipStream_t st);
+int launch_gather_rows_f32(int64_t rows, int64_t nlam, int64_t ld, const int32_t *d_order, const double *d_src, float *d_dst,
+                           hipStream_t st);                                            // the same rows, rounded to float
+int launch_round_to_f32(size_t count, const double *d_src, float *d_dst, hipStream_t st);    // dst = (float)src
+int launch_widen_f32(size_t count, const float *d_src, double *d_dst, hipStream_t st);       // dst = (double)src, exact
 int launch_lambda_update(int64_t n, int64_t nlam, int64_t ld, const double *dJ, const double *dB,
                          const double *deps, const double *dS_old, double *dS_new,
                          unsigned long long *d_result, hipStream_t st);
 // the same on sweep-order planes (J_up, J_down in, B in the up order, S_up updated in place, S_down written)
 int launch_lambda_update_native(vrt_grid *g, int64_t nlam, const double *dJ_up, const double *dJ_down, const double *dB_up,
                                 const double *deps, double *dS_up, double *dS_down, unsigned long long *d_result, hipStream_t st);
+// the same on the plan's FLOAT plane sets (pair blocks of native_lg(p, true); the roundings: include/voronoirt.h)
+int launch_lambda_update_native_f32(vrt_plan *p, int64_t nlam, const float *dJ_up, const float *dJ_down, const float *dB_up,
+                                    const double *deps, float *dS_up, float *dS_down, unsigned long long *d_result, hipStream_t st);
 
 // ---- physics either side of the formal solve (vrt_physics.hip) -------------------------------------
 int launch_line_opacity(vrt_plan *p, int64_t nlam, const double *d_lambda, double lambda0, double c0,
@@ -620,6 +627,12 @@ int launch_rates_populations(vrt_grid *g, int64_t nlam, int64_t ld, const int64_
                              double pref_ij, double pref_ji, const double *d_C, const double *d_atom_density,
                              double *d_R, double *d_populations, hipStream_t st,
                              const double *dJ_up = nullptr, const double *dJ_down = nullptr);   // sweep-order J instead of dJ
+// the same with J in the plan's FLOAT sweep-order plane sets: J = (float)(J_up + J_down), widened
+int launch_rates_populations_f32(vrt_plan *p, int64_t nlam, const int64_t blocks[6], const double *d_small, double lambda0,
+                                 double c0, const double *d_doppler, const double *d_gamma, double sigma_bb_const,
+                                 const double *d_temperature, const double *d_lte, double hc_over_kB, double pref_ij,
+                                 double pref_ji, const double *d_C, const double *d_atom_density, double *d_R,
+                                 double *d_populations, hipStream_t st, const float *dJ_up, const float *dJ_down);
 // the same for n points in their own order, without a grid (the regular-grid Λ-iteration)
 int launch_rates_populations(int64_t n, int64_t nlam, int64_t ld, const int64_t blocks[6], const double *d_small,
                              const double *dJ, double lambda0, double c0, const double *d_doppler, const double *d_gamma,

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "vrt_device.h"
 #include "vrt_internal.h"
 #include "vrt_weights.h"
 
@@ -551,6 +552,114 @@ int launch_lambda_update_native(vrt_grid *g, int64_t nlam, const double *dJ_up, 
     return VRT_OK;
 }
 
+// The same on FLOAT plane sets (vrt_plan_execute_native_dev_f32): pairs in the plan's blocks (pair_block_at), arithmetic in
+// double, rounded to float exactly where include/voronoirt.h says: J = (float)(J_up + J_down) as k_combine_J<float> delivers
+// it, S_new = (float)((1 - ε) J + ε B), the criterion from the stored floats.  One thread per up position; a UNIT is W
+// neighbouring pairs of one block taken as ONE access of 8 W bytes (W = 2: a quad, 16 bytes -- every block of two pairs or
+// more is a run of quads, its first pair even), U units in flight per array.
+template <int W> struct alignas(8 * W) FUnit { float a[2 * W]; };
+
+template <int W>
+__device__ __forceinline__ void update_units_f32(int q_begin, int q_end, int64_t n, int npair, int nlam, int lgB, size_t pos, size_t pd,
+                                                 double e, const float2 *__restrict__ Ju, const float2 *__restrict__ Jd,
+                                                 const float2 *__restrict__ Bu, float2 *__restrict__ Su, float2 *__restrict__ Sd,
+                                                 double &d, bool &isnan_)
+{
+    typedef FUnit<W> V;
+    constexpr int U = 4;
+    for (int q0 = q_begin; q0 < q_end; q0 += U * W) {
+        V Jup[U], Jdn[U], B[U], So[U];
+        size_t tu[U], td[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int q = q0 + u * W < q_end ? q0 + u * W : q_end - W;     // (past the end: the last unit again, unused)
+            int k0, lw;
+            pair_block_at(q, npair, lgB, k0, lw);
+            tu[u] = (size_t)k0 * (size_t)n + (pos << lw) + (size_t)(q - k0);
+            td[u] = (size_t)k0 * (size_t)n + (pd << lw) + (size_t)(q - k0);
+            if (Ju) Jup[u] = *reinterpret_cast<const V *>(Ju + tu[u]);
+            if (Jd) Jdn[u] = *reinterpret_cast<const V *>(Jd + td[u]);
+            B[u] = *reinterpret_cast<const V *>(Bu + tu[u]);
+            So[u] = *reinterpret_cast<const V *>(Su + tu[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int q = q0 + u * W;
+            if (q >= q_end) break;
+            V Sn;
+#pragma unroll
+            for (int c = 0; c < 2 * W; c++) {
+                double j = 0.0;
+                if (Ju) j = (double)Jup[u].a[c];
+                if (Jd) j = j + (double)Jdn[u].a[c];
+                const float jf = (float)j;
+                float sn = (float)((1.0 - e) * (double)jf + e * (double)B[u].a[c]);
+                const bool physical = 2 * q + c < nlam;            // (an odd count: the padding wavelength is carried as zero)
+                if (!physical) sn = 0.0f;
+                Sn.a[c] = sn;
+                if (physical) {
+                    const double dd = fabs(1.0 - (double)So[u].a[c] / (double)sn);
+                    if (!(dd == dd)) isnan_ = true;
+                    else d = fmax(d, dd);
+                }
+            }
+            *reinterpret_cast<V *>(Su + tu[u]) = Sn;
+            *reinterpret_cast<V *>(Sd + td[u]) = Sn;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_lambda_update_native_f32(int64_t n, int npair, int nlam, int lgB, const int32_t *__restrict__ store_up,
+                           const int32_t *__restrict__ rank_down, const float2 *__restrict__ Ju, const float2 *__restrict__ Jd,
+                           const float2 *__restrict__ Bu, const double *__restrict__ eps, float2 *__restrict__ Su,
+                           float2 *__restrict__ Sd, unsigned long long *__restrict__ result)
+{
+    __shared__ double wmax[4];
+    __shared__ int wnan[4];
+    double d = 0.0;
+    bool isnan_ = false;
+    // blocks of two pairs or more cover the even pairs' quads [0, 2 nquad); what is left are one-pair blocks
+    const int nquad = lgB >= 1 ? npair >> 1 : 0;
+    for (int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pos < n; pos += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t site = store_up[pos];
+        const size_t pd = (size_t)rank_down[site];
+        const double e = eps[site];
+        update_units_f32<2>(0, 2 * nquad, n, npair, nlam, lgB, (size_t)pos, pd, e, Ju, Jd, Bu, Su, Sd, d, isnan_);
+        update_units_f32<1>(2 * nquad, npair, n, npair, nlam, lgB, (size_t)pos, pd, e, Ju, Jd, Bu, Su, Sd, d, isnan_);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) d = fmax(d, __shfl_xor(d, off, 64));
+    const unsigned long long any_nan = __ballot(isnan_);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { wmax[wave] = d; wnan[wave] = any_nan != 0ull; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double m = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3]));
+        atomicMax(&result[0], (unsigned long long)__double_as_longlong(m));
+        if (wnan[0] | wnan[1] | wnan[2] | wnan[3]) atomicMax(&result[1], 1ull);
+    }
+}
+
+int launch_lambda_update_native_f32(vrt_plan *p, int64_t nlam, const float *dJ_up, const float *dJ_down, const float *dB_up,
+                                    const double *deps, float *dS_up, float *dS_down, unsigned long long *d_result, hipStream_t st)
+{
+    vrt_grid *g = p->g;
+    const int lgB = native_lg(p, true);
+    if (lgB >= 1)                                        // the quads are 16-byte accesses
+        for (const void *ptr : {(const void *)dJ_up, (const void *)dJ_down, (const void *)dB_up, (const void *)dS_up, (const void *)dS_down})
+            if ((uintptr_t)ptr & 15) return fail(VRT_EINVAL, "float sweep-order plane sets must be 16-byte aligned");
+    VRT_HIP_TRY(hipMemsetAsync(d_result, 0, 2 * sizeof(unsigned long long), st));
+    const int npair = (int)((nlam + 1) / 2);
+    const int64_t blocks = std::min<int64_t>((g->n + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(k_lambda_update_native_f32, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, g->n, npair, (int)nlam,
+                       lgB, g->up.d_store, g->down.d_srank, reinterpret_cast<const float2 *>(dJ_up),
+                       reinterpret_cast<const float2 *>(dJ_down), reinterpret_cast<const float2 *>(dB_up), deps,
+                       reinterpret_cast<float2 *>(dS_up), reinterpret_cast<float2 *>(dS_down), d_result);
+    VRT_HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
 // dst += src (partial J's of two handles on one device: vrt_multi's same-device rehearsal)
 __global__ void __launch_bounds__(256)
 k_axpy(size_t count, const double *__restrict__ src, double *__restrict__ dst)
@@ -569,21 +678,53 @@ int launch_axpy(size_t count, const double *d_src, double *d_dst, hipStream_t st
 
 // dst[j][l] = src[order[j]][l]: rows of a caller-layout (nlam, n) array picked by a site list (the boundary
 // intensity B_λ(T) of the bottom layer in perm_up order, lambda_iteration.jl:99-101)
+// (T = float: the rows rounded to float, the I_0 of a float-storage session)
+template <typename T>
 __global__ void __launch_bounds__(256)
 k_gather_rows(int64_t rows, int64_t nlam, int64_t ld, const int32_t *__restrict__ order, const double *__restrict__ src,
-              double *__restrict__ dst)
+              T *__restrict__ dst)
 {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= rows * nlam) return;
     const int64_t j = t / nlam, l = t % nlam;
-    dst[t] = src[(size_t)order[j] * (size_t)ld + (size_t)l];
+    dst[t] = (T)src[(size_t)order[j] * (size_t)ld + (size_t)l];
 }
+
+int launch_gather_rows_f32(int64_t rows, int64_t nlam, int64_t ld, const int32_t *d_order, const double *d_src, float *d_dst,
+                           hipStream_t st)
+{
+    if (rows * nlam <= 0) return VRT_OK;
+    hipLaunchKernelGGL(k_gather_rows<float>, dim3((unsigned)((rows * nlam + 255) / 256)), dim3(256), 0, st, rows, nlam, ld, d_order,
+                       d_src, d_dst);
+    VRT_HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+// dst = (B)src, element for element: double -> float rounds to nearest, float -> double is exact
+template <typename A, typename B>
+__global__ void __launch_bounds__(256)
+k_convert(size_t count, const A *__restrict__ src, B *__restrict__ dst)
+{
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (size_t)gridDim.x * blockDim.x) dst[t] = (B)src[t];
+}
+
+template <typename A, typename B>
+static int launch_convert(size_t count, const A *d_src, B *d_dst, hipStream_t st)
+{
+    if (!count) return VRT_OK;
+    const size_t blocks = std::min<size_t>((count + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL((k_convert<A, B>), dim3((unsigned)blocks), dim3(256), 0, st, count, d_src, d_dst);
+    VRT_HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+int launch_round_to_f32(size_t count, const double *d_src, float *d_dst, hipStream_t st) { return launch_convert(count, d_src, d_dst, st); }
+int launch_widen_f32(size_t count, const float *d_src, double *d_dst, hipStream_t st) { return launch_convert(count, d_src, d_dst, st); }
 
 int launch_gather_rows(int64_t rows, int64_t nlam, int64_t ld, const int32_t *d_order, const double *d_src, double *d_dst,
                        hipStream_t st)
 {
     if (rows * nlam <= 0) return VRT_OK;
-    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((rows * nlam + 255) / 256)), dim3(256), 0, st, rows, nlam, ld, d_order,
+    hipLaunchKernelGGL(k_gather_rows<double>, dim3((unsigned)((rows * nlam + 255) / 256)), dim3(256), 0, st, rows, nlam, ld, d_order,
                        d_src, d_dst);
     VRT_HIP_TRY(hipGetLastError());
     return VRT_OK;

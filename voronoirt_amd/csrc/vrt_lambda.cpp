@@ -151,6 +151,10 @@ struct vrt_lambda {
     // the loop; d_S_new / d_S_old / d_J (the caller's layout) then exist only while vrt_lambda_get fills them
     bool native = false;
     DevBuf<double> d_S_nat[2], d_J_nat[2], d_B_up;
+    // float storage (vrt_lambda_create_f32; always native): these replace d_S_nat, d_J_nat, d_B_up, d_I0, d_native and d_B0 --
+    // no double array of size nλ·n or nλ·n·angles exists in such a session
+    bool f32 = false;
+    DevBuf<float> f_S_nat[2], f_J_nat[2], f_B_up, f_I0, f_native;
     NgState ng;                         // vrt_lambda_set_acceleration (off: nothing allocated, nothing run)
 };
 
@@ -291,7 +295,7 @@ int vrt_plan_execute_line(vrt_plan *p, int64_t nlam, int64_t ld, const double *l
     });
 }
 
-int vrt_lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *weights, vrt_lambda **out)
+static int lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *weights, vrt_lambda **out, bool f32)
 {
     if (!out) return fail(VRT_EINVAL, "out is NULL");
     *out = nullptr;
@@ -315,8 +319,14 @@ int vrt_lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *weight
             return fail(VRT_EINVAL, "the line session needs a layer path (at most 4 visits per site and 255 levels per layer)");
         if (p->A != (int)p->n_angles_user)
             return fail(VRT_EINVAL, "per-angle alpha needs every angle active (no θ = 90 direction)");
+        if (f32) {                                      // float planes exist on the patch path only: no fp64 fallback
+            if ((rc = native_planes_ok(p, true))) return rc;
+            if (p->tune.lambda_native == 0 || (p->tune.path != 0 && p->tune.path != 4))
+                return fail(VRT_EINVAL, "the float-storage line session keeps S and J in the patch path's sweep order: not with VRT_LAMBDA_NATIVE=0 or a VRT_PATH other than patches");
+        }
         std::unique_ptr<vrt_lambda, LambdaDelete> s(new vrt_lambda());
         s->p = p;
+        s->f32 = f32;
         s->device = g->device;
         s->n = g->n;
         s->nlam = nlam;
@@ -346,8 +356,28 @@ int vrt_lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *weight
         VRT_S(upload(s->d_lte, lc->lte_populations, 3 * n, st));
         VRT_S(upload(s->d_C, lc->C, 9 * n, st));
         VRT_S(upload(s->d_pops, lc->lte_populations, 3 * n, st));        // populations = copy(LTE_pops), :232
-        s->native = p->tune.lambda_native != 0 && native_planes_ok(p) == VRT_OK && p->tune.path != 1 && p->tune.path != 2;
-        if (s->native) {
+        s->native = f32 || (p->tune.lambda_native != 0 && native_planes_ok(p) == VRT_OK && p->tune.path != 1 && p->tune.path != 2);
+        if (f32) {
+            // B_0 rounded to float once: S_new = B_0 in both orders, B in the up order, I_0 of the bottom layer; the double
+            // copy and the caller-layout float copy are staging only
+            const size_t np = (size_t)vrt_plan_native_plane_count(p, nlam);
+            DevBuf<float> B0f;
+            VRT_S(B0f.alloc(n * nl));
+            VRT_S(launch_round_to_f32(n * nl, s->d_B0, B0f, st));
+            for (int d = 0; d < 2; d++) {
+                VRT_S(s->f_S_nat[d].alloc(np));
+                VRT_S(s->f_J_nat[d].alloc(np));
+                if (hipMemsetAsync(s->f_J_nat[d], 0, sizeof(float) * np, st) != hipSuccess) return fail(VRT_ENODEVICE, "hipMemsetAsync failed");
+            }
+            VRT_S(s->f_B_up.alloc(np));
+            VRT_S(planes_to_native_f32(p, nlam, nlam, B0f, s->f_S_nat[0], s->f_S_nat[1], st));
+            VRT_S(planes_to_native_f32(p, nlam, nlam, B0f, s->f_B_up, nullptr, st));
+            VRT_S(s->f_I0.alloc((size_t)g->up.n1 * nl));
+            VRT_S(launch_gather_rows_f32(g->up.n1, nlam, nlam, g->up.d_order, s->d_B0, s->f_I0, st));
+            VRT_S(s->f_native.alloc((size_t)vrt_plan_native_alpha_count(p, nlam)));
+            if (hipStreamSynchronize(st) != hipSuccess) return fail(VRT_ENODEVICE, "uploading the line case failed");
+            s->d_B0.reset();
+        } else if (s->native) {
             const size_t np = (size_t)vrt_plan_native_plane_count(p, nlam);
             for (int d = 0; d < 2; d++) {
                 VRT_S(s->d_S_nat[d].alloc(np));
@@ -366,14 +396,16 @@ int vrt_lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *weight
         VRT_S(s->d_strength.alloc(n));
         VRT_S(s->d_pops_new.alloc(3 * n));
         VRT_S(s->d_R.alloc(9 * n));
+        if (!f32) {
         VRT_S(s->d_I0.alloc((size_t)g->up.n1 * nl));
         VRT_S(s->d_native.alloc((size_t)vrt_plan_native_alpha_count(p, nlam)));
+        }
         VRT_S(s->d_scalars.alloc(2));
         if (!s->native &&
             (hipMemsetAsync(s->d_S_old, 0, sizeof(double) * n * nl, st) != hipSuccess ||      // S_old = zero(S_new), :240
              hipMemsetAsync(s->d_J, 0, sizeof(double) * n * nl, st) != hipSuccess))
             return fail(VRT_ENODEVICE, "hipMemsetAsync failed");
-        VRT_S(launch_gather_rows(g->up.n1, nlam, nlam, g->up.d_order, s->d_B0, s->d_I0, st));   // I_0 = B_λ(λ_l, T) of the bottom layer, :99-101
+        if (!f32) VRT_S(launch_gather_rows(g->up.n1, nlam, nlam, g->up.d_order, s->d_B0, s->d_I0, st));   // I_0 = B_λ(λ_l, T) of the bottom layer, :99-101
 #undef VRT_S
         if (hipStreamSynchronize(st) != hipSuccess)                         // the host arrays may go after return
             return fail(VRT_ENODEVICE, "uploading the line case failed");
@@ -381,6 +413,18 @@ int vrt_lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *weight
         return VRT_OK;
     });
 }
+
+int vrt_lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *weights, vrt_lambda **out)
+{
+    return lambda_create(p, lc, weights, out, false);
+}
+
+int vrt_lambda_create_f32(vrt_plan *p, const vrt_line_case *lc, const double *weights, vrt_lambda **out)
+{
+    return lambda_create(p, lc, weights, out, true);
+}
+
+int vrt_lambda_storage(const vrt_lambda *s) { return !s ? fail(VRT_EINVAL, "NULL session") : s->f32 ? 4 : 8; }
 
 int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
 {
@@ -401,9 +445,23 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
                                     s->Bji, s->d_gamma, s->d_strength, st)))
             return rc;
         if ((rc = launch_line_opacity(p, nlam, s->d_small, s->lambda0, s->c0, s->d_velocity, s->d_doppler, s->d_gamma,
-                                      s->d_strength, s->d_alpha_cont, s->d_native, st)))
+                                      s->d_strength, s->d_alpha_cont, s->f32 ? (void *)s->f_native.get() : (void *)s->d_native.get(), st,
+                                      s->f32)))
             return rc;
-        if (s->native) {
+        if (s->f32) {
+            // the same three steps on the float plane sets (the roundings: include/voronoirt.h)
+            if ((rc = execute_locked(p, native_args(nlam, s->f_S_nat[0], s->f_S_nat[1], s->f_native, VRT_ALPHA_ANGLE_NATIVE, s->f_I0,
+                                                    nullptr, s->weights.data(), s->f_J_nat[0], s->f_J_nat[1], st, true))))
+                return rc;
+            if ((rc = launch_lambda_update_native_f32(p, nlam, s->f_J_nat[0], s->f_J_nat[1], s->f_B_up, s->d_eps, s->f_S_nat[0],
+                                                      s->f_S_nat[1], s->d_scalars, st)))
+                return rc;
+            if ((rc = launch_rates_populations_f32(p, nlam, s->blocks, s->d_small, s->lambda0, s->c0, s->d_doppler, s->d_gamma,
+                                                   s->sigma_bb_const, s->d_temperature, s->d_lte, s->hc_over_kB, s->pref_ij,
+                                                   s->pref_ji, s->d_C, s->d_atom, s->d_R, s->d_pops_new, st, s->f_J_nat[0],
+                                                   s->f_J_nat[1])))
+                return rc;
+        } else if (s->native) {
             // J_λ (:84-111) from the sweep-order S into the sweep-order J; S_new and the criterion (:261-263, :325-349: the old
             // S is read from the plane the new one is written to); R and the populations (:269, :274) from the same J planes
             if ((rc = execute_locked(p, native_args(nlam, s->d_S_nat[0], s->d_S_nat[1], s->d_native, VRT_ALPHA_ANGLE_NATIVE, s->d_I0,
@@ -465,6 +523,8 @@ int vrt_lambda_set_acceleration(vrt_lambda *s, int order, int start, int period)
     return guarded([&] {
         vrt_plan *p = s->p;
         std::lock_guard<std::mutex> lock(p->mu);
+        if (s->f32)                                          // the Ng kernels and NgRange: the [pair][pos][2] double layout
+            return fail(VRT_EINVAL, "vrt_lambda_set_acceleration: not on a float-storage session (the Ng kernels work on double planes)");
         if ((rc = use_device(p->g->device))) return rc;
         return ng_configure(s->ng, order, start, period, lambda_S_count(s, nullptr));
     });
@@ -485,7 +545,23 @@ int vrt_lambda_get(vrt_lambda *s, double *J, double *S, double *populations, dou
         int rc = use_device(p->g->device);
         if (rc) return rc;
         const size_t n = (size_t)s->n, nl = (size_t)s->nlam;
-        if (s->native && (J || S)) {
+        if (s->f32 && (J || S)) {
+            // the float values in the caller's layout, widened on the device (exact), one array at a time
+            DevBuf<float> tf;
+            DevBuf<double> tmp;
+            if ((rc = tf.alloc(n * nl)) || (rc = tmp.alloc(n * nl))) return rc;
+            hipStream_t st = p->g->stream;
+            for (int which = 0; which < 2 && !rc; which++) {
+                double *host = which == 0 ? J : S;
+                if (!host) continue;
+                rc = which == 0 ? J_from_native_f32(p, s->nlam, s->nlam, s->f_J_nat[0], s->f_J_nat[1], tf, st)
+                                : plane_from_native_f32(p, 0, s->nlam, s->nlam, s->f_S_nat[0], tf, st);
+                if (!rc) rc = launch_widen_f32(n * nl, tf, tmp, st);
+                if (!rc && hipMemcpyAsync(host, tmp, sizeof(double) * n * nl, hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ENODEVICE;
+                if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = VRT_ENODEVICE;
+            }
+            if (rc) return rc == VRT_ENODEVICE ? fail(rc, "HIP error in vrt_lambda_get") : rc;
+        } else if (s->native && (J || S)) {
             // the caller's layout is formed here, on request: one scratch array, freed again
             DevBuf<double> tmp;
             if ((rc = tmp.alloc(n * nl))) return rc;
@@ -524,7 +600,14 @@ int vrt_lambda_set_state(vrt_lambda *s, const double *S, const double *populatio
         const size_t n = (size_t)s->n, nS = n * (size_t)s->nlam;
         // staged copies beside the session: it is untouched until every one of them is complete
         DevBuf<double> tmp, S_up, S_down, pops;
-        if (S && s->native) {
+        DevBuf<float> Sf, Sf_up, Sf_down;
+        if (S && s->f32) {
+            // rounded to float, then both plane sets (the padding wavelength of an odd nlam zero as at create)
+            const size_t np = (size_t)vrt_plan_native_plane_count(p, s->nlam);
+            if ((rc = upload(tmp, S, nS, st)) || (rc = Sf.alloc(nS)) || (rc = Sf_up.alloc(np)) || (rc = Sf_down.alloc(np))) return rc;
+            if ((rc = launch_round_to_f32(nS, tmp, Sf, st))) return rc;
+            if ((rc = planes_to_native_f32(p, s->nlam, s->nlam, Sf, Sf_up, Sf_down, st))) return rc;
+        } else if (S && s->native) {
             // both plane sets, the padding wavelength of an odd nlam zero as at create
             const size_t np = (size_t)vrt_plan_native_plane_count(p, s->nlam);
             if ((rc = upload(tmp, S, nS, st)) || (rc = S_up.alloc(np)) || (rc = S_down.alloc(np))) return rc;
@@ -534,7 +617,10 @@ int vrt_lambda_set_state(vrt_lambda *s, const double *S, const double *populatio
         }
         if (populations && (rc = upload(pops, populations, 3 * n, st))) return rc;
         VRT_HIP_TRY(hipStreamSynchronize(st));               // the host arrays may go after return
-        if (S && s->native) {
+        if (S && s->f32) {
+            std::swap(s->f_S_nat[0], Sf_up);
+            std::swap(s->f_S_nat[1], Sf_down);
+        } else if (S && s->native) {
             std::swap(s->d_S_nat[0], S_up);
             std::swap(s->d_S_nat[1], S_down);
         } else if (S)

@@ -158,6 +158,9 @@ struct RatesArgs {
     double lambda0, c0, sigma_bb_const, hc_over_kB, pref_ij, pref_ji;
     const double *doppler, *gamma, *temperature, *lte, *C, *atom_density;
     double *R, *populations;
+    // ... or the same two plane sets stored as float (vrt_plan_execute_native_dev_f32), pairs in blocks of 2^lgB
+    const float *Jf_up = nullptr, *Jf_down = nullptr;
+    int lgB = 0, npair = 0;
 };
 
 __device__ __forceinline__ void solve2(const double A[4], const double b[2], double x[2])
@@ -223,7 +226,9 @@ __device__ __forceinline__ void populations_from_rates(const RatesArgs &ra, int6
 // NATIVE: J comes per sweep direction in sweep order; a thread takes the site at up position blockIdx * 256 + tid, so that
 // the J_up loads of a wave are contiguous (and the J_down loads piecewise contiguous: layers are the units of both orders) --
 // the per-site inputs become gathers instead, 25 values against the 2 x nlam of J.  The arithmetic of a site is the same.
-template <bool NATIVE>
+// T = float: the plane sets hold floats in the plan's pair blocks; J = (float)(J_up + J_down), the J that
+// vrt_plan_j_from_native_dev_f32 delivers, widened -- everything after that is the same arithmetic.
+template <bool NATIVE, typename T = double>
 __global__ void __launch_bounds__(256)
 k_rates_populations(RatesArgs ra)
 {
@@ -241,12 +246,21 @@ k_rates_populations(RatesArgs ra)
         // J = J_up + J_down as k_combine_J forms it; the two wavelengths of a pair come with one 16-byte load per direction
         const int64_t q = l >> 1;
         if (q != pair_have) {
-            const size_t o = (size_t)q * (size_t)n;
             double2 v = make_double2(0.0, 0.0);
+            if constexpr (sizeof(T) == 8) {
+            const size_t o = (size_t)q * (size_t)n;
             if (ra.J_up) v = reinterpret_cast<const double2 *>(ra.J_up)[o + (size_t)slot];
             if (ra.J_down) {
                 const double2 u = reinterpret_cast<const double2 *>(ra.J_down)[o + (size_t)pdn];
                 v.x = v.x + u.x; v.y = v.y + u.y;
+            }
+            } else {
+                if (ra.Jf_up) v = to_d2(reinterpret_cast<const float2 *>(ra.Jf_up)[pair_index((int)q, slot, n, ra.lgB, ra.npair)]);
+                if (ra.Jf_down) {
+                    const double2 u = to_d2(reinterpret_cast<const float2 *>(ra.Jf_down)[pair_index((int)q, pdn, n, ra.lgB, ra.npair)]);
+                    v.x = v.x + u.x; v.y = v.y + u.y;
+                }
+                v = to_d2(from_d2<float>(v));
             }
             pair_J = v;
             pair_have = q;
@@ -474,6 +488,24 @@ int launch_rates_populations(vrt_grid *g, int64_t nlam, int64_t ld, const int64_
         hipLaunchKernelGGL(k_rates_populations<true>, dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, st, ra);
     } else
     hipLaunchKernelGGL(k_rates_populations<false>, dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, st, ra);
+    VRT_HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+int launch_rates_populations_f32(vrt_plan *p, int64_t nlam, const int64_t blocks[6], const double *d_small, double lambda0,
+                                 double c0, const double *d_doppler, const double *d_gamma, double sigma_bb_const,
+                                 const double *d_temperature, const double *d_lte, double hc_over_kB, double pref_ij,
+                                 double pref_ji, const double *d_C, const double *d_atom_density, double *d_R,
+                                 double *d_populations, hipStream_t st, const float *dJ_up, const float *dJ_down)
+{
+    vrt_grid *g = p->g;
+    RatesArgs ra;
+    fill_rates_args(ra, g->n, nlam, nlam, blocks, d_small, nullptr, lambda0, c0, d_doppler, d_gamma, sigma_bb_const, d_temperature,
+                    d_lte, hc_over_kB, pref_ij, pref_ji, d_C, d_atom_density, d_R, d_populations);
+    ra.Jf_up = dJ_up; ra.Jf_down = dJ_down;
+    ra.lgB = native_lg(p, true); ra.npair = (int)((nlam + 1) / 2);
+    ra.store_up = g->up.d_store; ra.rank_down = g->down.d_srank;
+    hipLaunchKernelGGL((k_rates_populations<true, float>), dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, st, ra);
     VRT_HIP_TRY(hipGetLastError());
     return VRT_OK;
 }
