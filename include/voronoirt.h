@@ -267,6 +267,20 @@ int vrt_plan_last_sweep_timing(const vrt_plan *p, double *ms, int64_t *launches)
  * any (angle, layer >= 2) has, out[2] = slots of the work lists of the per-layer launches and out[3] = how many of them are
  * padding (both 0 until a per-layer execute has built the lists) */
 int vrt_plan_patch_layout(const vrt_plan *p, int64_t *out);
+/* which block of a per-layer patch launch does what (introspection for the tests only; host only): the grid of a launch
+ * with `nrow` rows of the work list, `nsplit` workgroups per item and sibling (an item has `steps` >= nsplit pair steps),
+ * 1 << lg_siblings siblings and `nred` reduction blocks, in dispatch order `order` (option VRT_PATCH_ORDER: 0 interleaved,
+ * 1 share-major).  dims[4] = gridDim.x, gridDim.y, the order taken (0 where share-major order would pass 65 535 grid rows,
+ * or with one split) and the rows that hold patch blocks; blocks (or NULL) = six numbers per block in the grid's linear
+ * order (x first): role (0 patch, 1 reduction), XCD lane, work-list row, split, sibling, share in pair steps -- a
+ * reduction block: 1, its index among the reduction blocks, zeros. */
+int vrt_patch_dispatch_map(int order, int nrow, int nsplit, int lg_siblings, int64_t nred, int steps, int64_t *dims, int32_t *blocks);
+/* timeline of the last sweep's per-layer patch launches (diagnostics build of the library with option VRT_PATCH_TIMELINE=1
+ * only; VRT_EINVAL otherwise): waits for the device, then launches[12 per launch] = layer, stream group, gridDim.x,
+ * gridDim.y, work-list rows, splits, log2 siblings, order, patch rows, reduction blocks, first block, pair steps of an
+ * item; stamps[3 per block, linear grid order] = start, end (wall clock ticks), share in pair steps (| 1 << 32: a
+ * reduction block); counts[3] = launches, blocks, wall clock rate in kHz */
+int vrt_plan_patch_timeline(vrt_plan *p, int64_t cap_launches, int64_t cap_blocks, int64_t *launches, uint64_t *stamps, int64_t *counts);
 /* VRT_OK, or the give-up of a chained patch launch that has finished since the last check (VRT_ENODEVICE: the results of
  * that execute are invalid).  The entry points that synchronise themselves (vrt_plan_execute, vrt_plan_execute_line,
  * vrt_lambda_iterate, vrt_multi_*) report it from the call it spoiled; a caller of the ASYNCHRONOUS entry points
@@ -284,7 +298,10 @@ int vrt_plan_last_path(const vrt_plan *p);
  * live plan; vrt_grid_set_option sets it for the plans vrt_delaunay_up / _down cache inside the grid.
  *   VRT_PATH = auto | levels | tiles | steps | patches
  *   VRT_PATCH_Q, VRT_PATCH_TARGET              wavelength pairs at a time / workgroups per launch of the patch kernel
- *   VRT_PATCH_K, VRT_PATCH_NT, VRT_PATCH_OWN   entries per thread, threads, owned sites per patch (creation only)
+ *   VRT_PATCH_ORDER = 0 | 1                    dispatch order of the workgroups of a per-layer patch launch: an item's
+ *                                              workgroups side by side, or share-major -- every item's longest share of
+ *                                              wavelength-pair steps first (default 1)
+ *   VRT_PATCH_K, VRT_PATCH_NT, VRT_PATCH_OWN  entries per thread, threads, owned sites per patch (creation only)
  *   VRT_PATCH_LEAN = 0 | 1                     the 64-register patch kernel, four workgroups per CU (default 1)
  *   VRT_PATCH_CHAIN = 0 | 1 | 2                every layer inside ONE launch, ordered by the data's own dependencies: never
  *                                              (one launch per layer and direction), wherever the kernel exists, auto

@@ -293,6 +293,11 @@ struct Tuning {
     int patch_split = 0;          // VRT_PATCH_SPLIT: workgroups per item of a per-layer launch, fixed (0: from VRT_PATCH_TARGET)
     int patch_target = 0;         // VRT_PATCH_TARGET: workgroups per launch aimed at when the pair steps of an item are split
                                   //   (0: a balanced split chosen per launch, launch_patch_layer)
+    int patch_order = 1;          // VRT_PATCH_ORDER: dispatch order of the patch blocks of a per-layer launch: 0 = the workgroups of an
+                                  //   item side by side (interleaved), 1 = share-major, every item's longest share first
+                                  //   (vrt_patch.hip: patch_block_of; default since profiles/order/INDEX.md)
+    int patch_timeline = 0;       // VRT_PATCH_TIMELINE: the blocks of the per-layer launches leave their start and end stamps
+                                  //   (-DVRT_DIAG build only: tools/patch_timeline.py)
     int chain_static = 1;         // VRT_CHAIN_STATIC: the progress-word form of the chained launch maps block -> item statically (0: tickets)
     int lambda_native = 1;        // VRT_LAMBDA_NATIVE: the Λ-iteration session keeps S and J in sweep order between its steps
                                   //   (read when a session is created; 0: the caller's layout, two layout changes per iteration)
@@ -497,6 +502,9 @@ struct vrt_plan {
     std::vector<int64_t> patch_work_off; //   [group][layer] offsets into it
     int patch_work_groups = 0;
     int64_t patch_work_padding = 0;      //   slots of it that hold no patch (a layer's items are dealt to 8 runs of one length)
+    vrt::DevBuf<unsigned long long> d_patch_tl;   // timeline of the -DVRT_DIAG build (VRT_PATCH_TIMELINE): three words per block
+    std::vector<int64_t> patch_tl_launches;       //   kPatchTimelineRec numbers per recorded launch of the last sweep
+    int64_t patch_tl_blocks = 0;                  //   blocks recorded so far
     vrt::Stream step_stream[4];
     vrt::Event step_fork, step_join[4];
     int last_path = 0;                   // path of the last execute (vrt_plan_last_path): 1 levels, 2 tiles, 3 steps, 4 patches
@@ -685,6 +693,13 @@ int launch_patch_entries(vrt_plan *p, int a, int64_t first, int64_t count);
 int ensure_patch_work(vrt_plan *p, int G, const std::vector<int32_t> &group_angles, const std::vector<int> &group_off);
 int launch_patch_layer(vrt_plan *p, const TileArgs &ta, int npair, int layer, int group, int Q, hipStream_t st,
                        bool f32, const PatchReduce *reduce);
+// numbers per launch of the timeline: layer, stream group, gridDim.x, gridDim.y, work-list rows, splits, log2 siblings,
+// order, patch rows, reduction blocks, first block in the stamps, pair steps of an item
+constexpr int kPatchTimelineRec = 12;
+void patch_timeline_begin(vrt_plan *p);          // a sweep of per-layer launches starts: forget the last one's records
+int patch_timeline_read(vrt_plan *p, int64_t cap_launches, int64_t cap_blocks, int64_t *launches, uint64_t *stamps, int64_t *counts);
+// the grid of a per-layer launch and, with `blocks`, what each of its blocks does (vrt_patch_dispatch_map)
+int patch_dispatch_map(int order, int nrow, int nsplit, int lg_siblings, int64_t nred, int steps, int64_t *dims, int32_t *blocks);
 bool patch_chain_possible(const vrt_plan *p, int npair, bool f32);
 bool patch_chain_dataflag(const vrt_plan *p, int npair, bool f32);
 // ctrl_zeroed: the launch's control words (chain_ctrl_words() of them at p->d_chain_ctrl) were zeroed on `st` by the caller

@@ -41,7 +41,10 @@ struct PatchArgs {
     int npair;                // ceil(nlam / 2)
     int layer;                // 1-based BFS layer being solved
     int ngrp;                 // workgroups per work item = siblings (1 << lgB) x splits: gridDim.x = 8 ngrp
-    int nrow;                 // rows of the grid that solve patches (work-list slots / 8); the rows behind them reduce
+    int nrow;                 // rows of the work list (slots / 8)
+    int order;                // dispatch order of the patch blocks (patch_block_of): 0 interleaved, 1 share-major
+    int prow;                 // rows of the grid that solve patches (order 0: nrow, order 1: nsplit x nrow); the rows behind them reduce
+    unsigned row_rcp;         // order 1: ceil(2^31 / nrow) -- a grid row's split without a division (patch_block_of)
     int nsplit, Q;            // the pair blocks are dealt to nsplit workgroups per sibling in steps of Q blocks (split_blocks)
     int sbase, srem;          //   steps per split and the splits that take one more (set_split: no division in the kernel)
     int lgB;                  // log2 of the pairs per block of the storage layout (vrt_device.h: pair_block_at)
@@ -56,6 +59,8 @@ struct PatchArgs {
     int dbg;                  // timing diagnostics (-DVRT_DIAG build only, WRONG results): 1 no levels, 2 gathers ->
                               //   coalesced centre reads, 4 no weights arithmetic, 8 no stores, 16 / 32 / 64 no upwind gathers
                               //   of I / alpha / S, 128 no J reduction
+    unsigned long long *tl;   // timeline of the -DVRT_DIAG build (VRT_PATCH_TIMELINE, BlockStamp): three words per block of
+                              //   this launch in the grid's linear order, or nullptr
     // J reduction riding along (lagged by one layer): the first nred blocks of the launch do not solve a patch
     // but form J_dir = Σ_a w_a I_a (reference's angle order inside the direction) over storage positions
     // [red_lo, red_hi) of up to two directions -- layers the stream's previous launch has made final
@@ -133,20 +138,114 @@ __host__ __device__ __forceinline__ void split_blocks(const PatchArgs &pa, int s
 #ifndef VRT_REDUCE_LAST
 #define VRT_REDUCE_LAST 1
 #endif
-// The grid is two-dimensional so that a workgroup finds its place without dividing by launch constants: blockIdx.x =
-// XCD lane + 8 x (split, sibling) with gridDim.x = 8 ngrp, blockIdx.y = row of the work list.  Blocks are dispatched x
-// first: block x + 8 (grp + ngrp sj) of the linear order is (x + 8 grp, sj), on the XCD its lane names.  The reduction
-// blocks fill rows of their own, padded to gridDim.x (a block past the last one returns at once).
+// ---- which block of a per-layer launch does what ------------------------------------------------------------------------
+// The grid is two-dimensional so that a workgroup finds its place without dividing by launch constants.  Blocks are
+// dispatched x first: block (bx, by) is number bx + gridDim.x by of the linear order, and gridDim.x is a multiple of 8, so
+// that number mod 8 -- the XCD the block runs on -- is bx & 7, its lane, in both orders.
+//   order 0 (interleaved): bx = lane + 8 x (split, sibling) with gridDim.x = 8 ngrp, by = row of the work list: the
+//     workgroups of an item side by side, long and short shares alternating through the whole dispatch order.
+//   order 1 (share-major): bx = lane + 8 x sibling with gridDim.x = 8 << lgS, by = split x nrow + row: every item's split 0,
+//     then every item's split 1, ...; inside a split the work-list order (position, angle: the angles of a position
+//     still meet in one L2 and share S), the siblings of a pair block still adjacent.  INVARIANT: split_blocks gives the
+//     first `srem` splits the longer share, so ascending split is descending share -- the share never grows along the
+//     linear order, and of a launch that offers more workgroups than its stream's half of the chip holds the ones that
+//     start late carry the short shares (longest processing time first).
+// The reduction blocks fill rows of their own behind the `prow` patch rows, padded to gridDim.x (a block past the last
+// one returns at once).
+struct PatchBlock { int lane, row, split, sib; };
+__host__ __device__ __forceinline__ PatchBlock patch_block_of(int order, int nrow, unsigned row_rcp, int lgS, unsigned bx, unsigned y)
+{
+    PatchBlock b;
+    const int grp = (int)(bx >> 3);
+    b.lane = (int)(bx & 7u);
+    if (order == 0) {
+        b.row = (int)y;
+        b.split = grp >> lgS;
+        b.sib = grp & ((1 << lgS) - 1);
+    } else {
+        // y / nrow by a multiply-high with row_rcp = ceil(2^31 / nrow): exact while y (row_rcp nrow - 2^31) < 2^31, which
+        // y < 65535 and nrow <= 32767 guarantee (patch_grid takes order 1 for two and more splits only)
+        b.split = (int)(((unsigned long long)(2u * y) * row_rcp) >> 32);
+        b.row = (int)y - b.split * nrow;
+        b.sib = grp;
+    }
+    return b;
+}
+// the grid of a launch: `order` as asked for, nrow work-list rows, nsplit splits x (1 << lgS) siblings per item, nred
+// reduction blocks.  Share-major order needs nsplit x nrow grid rows: where those and the reduction rows behind them pass
+// the 65 535 rows a grid may have, the launch keeps the interleaved order (one split is the same grid in both).
+struct PatchGrid {
+    int order = 0, prow = 0;
+    unsigned row_rcp = 0;
+    int64_t gx = 0, gy = 0;
+};
+static PatchGrid patch_grid(int order, int nrow, int nsplit, int lgS, int64_t nred)
+{
+    PatchGrid g;
+    if (order == 1 && nsplit >= 2 && nrow >= 1) {
+        g.gx = (int64_t)8 << lgS;
+        g.prow = nsplit * nrow;
+        g.gy = (int64_t)nsplit * nrow + (nred + g.gx - 1) / g.gx;
+        if (g.gy <= 65535) {
+            g.order = 1;
+            g.row_rcp = (unsigned)((((uint64_t)1 << 31) + (uint64_t)nrow - 1) / (uint64_t)nrow);
+            return g;
+        }
+    }
+    // interleaved: nrow rows of 8 ngrp patch blocks, then the reduction blocks in rows of the same width (a launch that
+    // only reduces is free to choose its width: as wide as the row limit asks)
+    g.order = 0;
+    g.prow = nrow;
+    g.row_rcp = 0;
+    g.gx = (int64_t)8 * ((int64_t)nsplit << lgS);
+    if (nrow == 0) g.gx = std::max<int64_t>(g.gx, ((nred + 65534) / 65535 + 7) / 8 * 8);
+    g.gy = nrow + (nred + g.gx - 1) / g.gx;
+    return g;
+}
 __device__ __forceinline__ int reduce_block_index(const PatchArgs &pa)      // >= 0: this block reduces
 {
-    const int rows = (int)gridDim.y - pa.nrow;                // reduction rows
-    const int y = VRT_REDUCE_LAST ? (int)blockIdx.y - pa.nrow : ((int)blockIdx.y < rows ? (int)blockIdx.y : -1);
+    const int rows = (int)gridDim.y - pa.prow;                // reduction rows
+    const int y = VRT_REDUCE_LAST ? (int)blockIdx.y - pa.prow : ((int)blockIdx.y < rows ? (int)blockIdx.y : -1);
     return y < 0 ? -1 : y * (int)gridDim.x + (int)blockIdx.x;
 }
-__device__ __forceinline__ int patch_row(const PatchArgs &pa)
+// (lane, work-list row, split, sibling) of a patch block; lgS: log2 of the sibling workgroups per pair block
+__device__ __forceinline__ PatchBlock patch_block(const PatchArgs &pa, int lgS)
 {
-    return VRT_REDUCE_LAST ? (int)blockIdx.y : (int)blockIdx.y - ((int)gridDim.y - pa.nrow);
+    const int y = VRT_REDUCE_LAST ? (int)blockIdx.y : (int)blockIdx.y - ((int)gridDim.y - pa.prow);
+    return patch_block_of(pa.order, pa.nrow, pa.row_rcp, lgS, blockIdx.x, (unsigned)y);
 }
+__device__ __forceinline__ int patch_row(const PatchArgs &pa) { return patch_block(pa, 0).row; }
+// Timeline of the -DVRT_DIAG build (VRT_PATCH_TIMELINE=1, tools/patch_timeline.py): every block of a per-layer launch
+// leaves {start stamp, end stamp, share} at its place in the grid's linear order -- wall_clock64() when the kernel is
+// entered and when thread 0 leaves it, whichever return it takes; share = pair steps of a patch block, | 1 << 32 for a
+// reduction block (0 steps: padding, or nothing of the item for this block).  In the product build the object is empty.
+struct BlockStamp {
+    unsigned long long *slot = nullptr;
+    unsigned long long t0 = 0, share = 0;
+    __device__ __forceinline__ explicit BlockStamp(const PatchArgs &pa)
+    {
+        if (kDiag && pa.tl) {
+            slot = pa.tl + 3 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
+            t0 = wall_clock64();
+        }
+    }
+    __device__ __forceinline__ void steps(const PatchArgs &pa, int b0, int b1)
+    {
+        if (kDiag) share = (unsigned long long)((b1 - b0 + pa.Q - 1) / pa.Q);
+    }
+    __device__ __forceinline__ void reduces()
+    {
+        if (kDiag) share = 1ull << 32;
+    }
+    __device__ __forceinline__ ~BlockStamp()
+    {
+        if (kDiag && slot && threadIdx.x == 0) {
+            slot[0] = t0;
+            slot[1] = wall_clock64();
+            slot[2] = share;
+        }
+    }
+};
 template <typename T, int NT>
 __device__ __forceinline__ void patch_reduce_role(const PatchArgs &pa)
 {
@@ -237,27 +336,31 @@ k_patch_solve(PatchArgs pa)
     // block -> (work item, pair group): blocks b, b + 8, ... share an XCD (MI355X_MICROARCH.md, speed
     // only); the pair groups of an item follow each other on ONE XCD and read its entry tables
     // through that L2, and consecutive items of an XCD are neighbouring patches / angles of a patch
+    BlockStamp stamp(pa);
     if (reduce_block_index(pa) >= 0) {
+        stamp.reduces();
         patch_reduce_role<T, NT>(pa);
         return;
     }
-    const int x = (int)blockIdx.x & 7, grp = (int)blockIdx.x >> 3, sj = patch_row(pa);
+    const PatchBlock blk = patch_block(pa, pa.lgB);
+    const int x = blk.lane, sj = blk.row;
     // (this kernel of the non-default shapes keeps its two vector loads of the record and its table loop as they were:
     // the start-up work of patch_item / EntryTable went into the kernels the defaults run)
     const int4 rec = pa.wrec[2 * (sj * 8 + x)], rec2 = pa.wrec[2 * (sj * 8 + x) + 1];
     if (rec.y <= 0) return;
     // sibling sib solves pair k0 + sib of every block [k0, k0 + 2^lw) with 2^lw > sib among blocks b0 .. b1-1: the
     // 2^lgB siblings of an item run side by side on one XCD and use a gathered line (one site's pairs) whole
-    const int sib = grp & ((1 << pa.lgB) - 1);
+    const int sib = blk.sib;
     const int nblock = pair_block_count(pa.npair, pa.lgB);
     int b0, b1;
-    split_blocks(pa, grp >> pa.lgB, nblock, b0, b1);
+    split_blocks(pa, blk.split, nblock, b0, b1);
     if (b0 >= b1) return;
     {
         int k0, lw;
         pair_block_of(b0, pa.npair, pa.lgB, k0, lw);
         if (sib >= (1 << lw)) return;                           // block widths only shrink: nothing for this sibling
     }
+    stamp.steps(pa, b0, b1);
     const int ent_off = rec.x, n_ent = rec.y, own_lo = rec.z, own_cnt = rec.w;
     const int dbg = kDiag ? pa.dbg : 0;
     const int nlev = diag(dbg, kDiagNoLevels) ? 0 : rec2.x, a = rec2.y & 0xFFFF;
@@ -429,15 +532,16 @@ struct PatchItem {
 // false: a padding slot, or nothing of the item for this workgroup
 __device__ __forceinline__ bool patch_item(const PatchArgs &pa, int lgS, PatchItem &it)
 {
-    const int x = (int)blockIdx.x & 7, grp = (int)blockIdx.x >> 3, sj = patch_row(pa);
+    const PatchBlock blk = patch_block(pa, lgS);
+    const int x = blk.lane, sj = blk.row;
     // both halves of the record in ONE scalar load: the work list is written by the host before the launch and its
     // address is the block's alone (the constant address space says so; as a vector load the second half was
     // issued only behind the test of the first)
     const vrt_i32x8 r8 = *((const WorkRec *)(uintptr_t)pa.wrec + (sj * 8 + x));
     const int4 rec = make_int4(r8[0], r8[1], r8[2], r8[3]), rec2 = make_int4(r8[4], r8[5], r8[6], r8[7]);
     if (rec.y <= 0) return false;
-    it.sib = grp & ((1 << lgS) - 1);
-    split_blocks(pa, grp >> lgS, pair_block_count(pa.npair, pa.lgB), it.b0, it.b1);
+    it.sib = blk.sib;
+    split_blocks(pa, blk.split, pair_block_count(pa.npair, pa.lgB), it.b0, it.b1);
     if (it.b0 >= it.b1) return false;
     it.ent_off = rec.x; it.n_ent = rec.y; it.own_lo = rec.z; it.own_cnt = rec.w;
     it.nlev = rec2.x; it.a = rec2.y & 0xFFFF;
@@ -934,7 +1038,9 @@ k_patch_lean(PatchArgs pa)
 {
     extern __shared__ __attribute__((aligned(16))) double2 ptile[];
     const int tid = threadIdx.x;
+    BlockStamp stamp(pa);
     if (reduce_block_index(pa) >= 0) {
+        stamp.reduces();
         patch_reduce_role<T, NT>(pa);
         return;
     }
@@ -944,6 +1050,7 @@ k_patch_lean(PatchArgs pa)
         early = EntryTable<NT>::load(pa, min(pa.dbg_ent0 + (patch_row(pa) * 8 + ((int)blockIdx.x & 7)) * pa.dbg_ent_stride + tid, pa.dbg_ent_last));
     PatchItem it;
     if (!patch_item(pa, pa.lgB, it)) return;
+    stamp.steps(pa, it.b0, it.b1);
     if (diag(pa.dbg, kDiagNoPairLoop)) it.b1 = it.b0;           // diagnostics: the item's overhead alone
     const EntryTable<NT> tab(ptile, 1);
     if (tid == 0) ptile[it.n_ent] = make_double2(0.0, 0.0);  // the zero slot
@@ -1097,7 +1204,9 @@ k_patch_quad(PatchArgs pa)
 {
     extern __shared__ __attribute__((aligned(16))) double2 ptile[];
     const int tid = threadIdx.x;
+    BlockStamp stamp(pa);
     if (reduce_block_index(pa) >= 0) {
+        stamp.reduces();
         patch_reduce_role<float, NT>(pa);
         return;
     }
@@ -1105,6 +1214,7 @@ k_patch_quad(PatchArgs pa)
     const double e2 = exp2_table_load();                     // (in flight beside the item's record and entry table)
     PatchItem it;
     if (!patch_item(pa, pa.lgB - 1, it)) return;
+    stamp.steps(pa, it.b0, it.b1);
     const EntryTable<NT> tab(ptile, 2);
     if (tid == 0) {
         ptile[it.n_ent] = make_double2(0.0, 0.0);            // the zero slots
@@ -1558,6 +1668,9 @@ int launch_patch_layer(vrt_plan *p, const TileArgs &ta, int npair, int layer, in
         // time); short items tolerate, and for the launch's tail want, more and smaller workgroups -- but never less than that
         // one round.  Measured on C4's grid, 108 items per launch (profiles/r5/split_table.txt): 8 / 10 / 13 / 18 / 26 / 35 / 50
         // steps are fastest at 8 / 10 / 7 / 6 / 6 / 5 / 5 workgroups per item, C3 (10 steps, 180 items) at 5: what this picks.
+        // Re-measured under the share-major dispatch order (profiles/order/split_table_order1.txt, order 0 beside it in the
+        // same session): fastest at 8 / 10 / 7 / 6 / 6 / 6 / 5 -- the same picks except 35 steps, where 6 workgroups now lead 5
+        // by 0.9 % (9.130 against 9.215 ms, one run each; under order 0 5 led 6 by as much): the constants stay.
         // VRT_PATCH_TARGET > 0: the fixed workgroup count per launch of rounds 3-5 (768); VRT_PATCH_SPLIT: s itself.
         int nsplit;
         if (p->tune.patch_split > 0) nsplit = std::min(steps_all, p->tune.patch_split);
@@ -1579,7 +1692,6 @@ int launch_patch_layer(vrt_plan *p, const TileArgs &ta, int npair, int layer, in
         pa.nsplit = nsplit;
         pa.ngrp = nsplit << lgS;
     }
-    set_split(pa, pair_block_count(npair, pa.lgB));
     pa.stride = p->patch_cap + 1;
     pa.cap = p->patch_cap;
     pa.dbg = kDiag ? p->tune.debug_flags : 0;
@@ -1593,21 +1705,94 @@ int launch_patch_layer(vrt_plan *p, const TileArgs &ta, int npair, int layer, in
     pa.e_pos = p->e_pos; pa.e_u1 = p->e_u1; pa.e_u2 = p->e_u2;
     pa.e_vis = p->e_vis; pa.e_loc = p->e_loc;
     pa.e_w1 = p->e_w1; pa.e_w2 = p->e_w2; pa.e_r1 = p->e_r1; pa.e_r2 = p->e_r2;
-    // the grid: (w1 - w0) / 8 rows of 8 ngrp patch blocks, then the reduction blocks in rows of the same width (a launch
-    // that only reduces is free to choose its width: as wide as the row limit asks)
+    // the grid (patch_grid): the patch blocks in the plan's dispatch order, the reduction rows behind them
     pa.nrow = (int)((w1 - w0) / 8);
-    int64_t gx = 8 * (int64_t)pa.ngrp;
-    if (pa.nrow == 0) gx = std::max<int64_t>(gx, (((int64_t)pa.red.nred + 65534) / 65535 + 7) / 8 * 8);
-    const int64_t gy = pa.nrow + (pa.red.nred + gx - 1) / gx;
+    const PatchGrid pg = patch_grid(p->tune.patch_order, pa.nrow, pa.nsplit, lgS, pa.red.nred);
+    pa.order = pg.order;
+    pa.prow = pg.prow;
+    pa.row_rcp = pg.row_rcp;
+    set_split(pa, pair_block_count(npair, pa.lgB));
+    const int64_t gx = pg.gx, gy = pg.gy;
     // (65 535 rows: > 524 000 work-list slots, or as many reduction rows behind fewer, in ONE layer -- a layer of some
     // 10^8 sites; the one-dimensional grid before had no such limit, DESIGN.md section 5 names it)
     if (gy > 65535 || gx > INT32_MAX)
         return fail(VRT_EINVAL, "a layer of this size needs more than 65535 rows of patch and reduction blocks in one launch");
+    pa.tl = nullptr;
+    if (kDiag && p->tune.patch_timeline) {
+        // timeline of this launch's blocks (BlockStamp) behind those of the step's earlier launches; a launch the buffer
+        // has no room for is not recorded
+        const int64_t cap = (int64_t)1 << 20, blocks = gx * gy;
+        if (!p->d_patch_tl && p->d_patch_tl.alloc((size_t)(3 * cap)) != VRT_OK) return VRT_ENOMEM;
+        if (p->patch_tl_blocks + blocks <= cap) {
+            pa.tl = p->d_patch_tl + 3 * p->patch_tl_blocks;
+            const int64_t rec[kPatchTimelineRec] = {layer, group, gx, gy, pa.nrow, pa.nsplit, lgS, pa.order, pa.prow, pa.red.nred,
+                                                    p->patch_tl_blocks, (pair_block_count(npair, pa.lgB) + Q - 1) / Q};
+            p->patch_tl_launches.insert(p->patch_tl_launches.end(), rec, rec + kPatchTimelineRec);
+            p->patch_tl_blocks += blocks;
+        }
+    }
     const dim3 grid((unsigned)gx, (unsigned)gy);
     const size_t lds = (size_t)(pa.quad ? 2 : Q) * (size_t)pa.stride * sizeof(double2) + (size_t)pa.cap * (4 * sizeof(double) + 5 * sizeof(int32_t));
     const int rc = f32 ? launch_mode<float>(ta.alpha_mode, p->patch_K, Q, p->patch_NT, grid, lds, st, pa)
                        : launch_mode<double>(ta.alpha_mode, p->patch_K, Q, p->patch_NT, grid, lds, st, pa);
     return rc;
+}
+
+// ---- timeline of the per-layer launches (-DVRT_DIAG build) and the dispatch map, for tools and tests -------------------------
+void patch_timeline_begin(vrt_plan *p)
+{
+    p->patch_tl_launches.clear();
+    p->patch_tl_blocks = 0;
+}
+
+// launches[kPatchTimelineRec x launch], stamps[3 x block] (BlockStamp) of the last sweep, after waiting for the device;
+// counts = {launches, blocks, wall clock rate in kHz}
+int patch_timeline_read(vrt_plan *p, int64_t cap_launches, int64_t cap_blocks, int64_t *launches, uint64_t *stamps, int64_t *counts)
+{
+    if (!kDiag) return fail(VRT_EINVAL, "the timeline of the patch launches exists in the -DVRT_DIAG build only");
+    const int64_t nl = (int64_t)p->patch_tl_launches.size() / kPatchTimelineRec, nb = p->patch_tl_blocks;
+    if (nl > cap_launches || nb > cap_blocks) return fail(VRT_EINVAL, "timeline buffers too small");
+    VRT_HIP_TRY(hipDeviceSynchronize());
+    int khz = 0;
+    VRT_HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, p->device));
+    counts[0] = nl; counts[1] = nb; counts[2] = khz;
+    std::copy(p->patch_tl_launches.begin(), p->patch_tl_launches.end(), launches);
+    if (nb > 0) VRT_HIP_TRY(hipMemcpy(stamps, p->d_patch_tl, sizeof(uint64_t) * 3 * (size_t)nb, hipMemcpyDeviceToHost));
+    return VRT_OK;
+}
+
+// dims = {gridDim.x, gridDim.y, order taken, patch rows}; blocks (or NULL): per block of the grid's linear order
+// {role: 0 patch / 1 reduction, lane, work-list row, split, sibling, share in steps} -- a reduction block: {1, its index, ...0}.
+// The same patch_grid, patch_block_of and split_blocks the launcher and the kernels go through.
+int patch_dispatch_map(int order, int nrow, int nsplit, int lg_siblings, int64_t nred, int steps, int64_t *dims, int32_t *blocks)
+{
+    if (!dims) return fail(VRT_EINVAL, "NULL output");
+    if (order < 0 || order > 1 || nrow < 0 || nrow > 65535 || nsplit < 1 || nsplit > 4096 || lg_siblings < 0 || lg_siblings > 4 ||
+        nred < 0 || nred > INT32_MAX || steps < nsplit)
+        return fail(VRT_EINVAL, "dispatch map: argument out of range");
+    const PatchGrid pg = patch_grid(order, nrow, nsplit, lg_siblings, nred);
+    if (pg.gy > 65535) return fail(VRT_EINVAL, "more than 65535 rows of patch and reduction blocks");
+    dims[0] = pg.gx; dims[1] = pg.gy; dims[2] = pg.order; dims[3] = pg.prow;
+    if (!blocks) return VRT_OK;
+    PatchArgs sp;                     // set_split / split_blocks read nsplit, Q, sbase and srem only
+    sp.nsplit = nsplit;
+    sp.Q = 1;
+    set_split(sp, steps);
+    for (int64_t by = 0; by < pg.gy; by++)
+        for (int64_t bx = 0; bx < pg.gx; bx++) {
+            int32_t *o = blocks + 6 * (by * pg.gx + bx);
+            std::fill(o, o + 6, 0);
+            if (by >= pg.prow) {
+                o[0] = 1;
+                o[1] = (int32_t)((by - pg.prow) * pg.gx + bx);
+                continue;
+            }
+            const PatchBlock b = patch_block_of(pg.order, nrow, pg.row_rcp, lg_siblings, (unsigned)bx, (unsigned)by);
+            int b0, b1;
+            split_blocks(sp, b.split, steps, b0, b1);
+            o[1] = b.lane; o[2] = b.row; o[3] = b.split; o[4] = b.sib; o[5] = b1 - b0;
+        }
+    return VRT_OK;
 }
 
 // ---- the chained launch: host side ------------------------------------------------------------------------------------
