@@ -739,8 +739,11 @@ int vrt_ng_apply_dev(int64_t count, double a, double b, const double *d_x0, cons
  * S of the three iterates before a due one is copied (three extra S arrays while acceleration is on; none when off, and
  * a session that never asks for acceleration runs exactly what it ran before).  The Voronoi session forms the sums over
  * the n nlam physical entries of its up-order copy of S and applies the same a, b to both sweep-order copies.
- * vrt_multi_lambda_* has NO acceleration entry: its S is split over the devices.  A caller that holds S in pieces has the
- * three pieces of the step above (vrt_ng_sums_dev, vrt_ng_coefficients, vrt_ng_apply_dev). */
+ * vrt_multi_lambda_* has NO acceleration entry in this file: its S is split over the devices, and the two entries that take
+ * the step over the members' blocks (vrt_multi_lambda_set_acceleration, vrt_multi_lambda_last_acceleration) stand with their
+ * contract in voronoirt_multi_accel.h, which this header includes at its end; the companion library
+ * libvrt_hip_multi_accel.so exports them (libvrt_hip.so exports what THIS file declares).  A caller that holds S in
+ * pieces of its own has the three pieces of the step above (vrt_ng_sums_dev, vrt_ng_coefficients, vrt_ng_apply_dev). */
 int vrt_lambda_set_acceleration(vrt_lambda *s, int order, int start, int period);
 int vrt_regular_lambda_set_acceleration(vrt_regular_lambda *s, int order, int start, int period);
 /* what the LAST iterate did: *applied = 1 taken, 0 none due, -1 due but rejected; sums / coeffs (either may be NULL)
@@ -979,4 +982,5 @@ int vrt_tau_unity(int64_t nz, int64_t nx, int64_t ny, const double *z, const dou
 #ifdef __cplusplus
 }
 #endif
+#include "voronoirt_multi_accel.h"
 #endif /* VORONOIRT_H */

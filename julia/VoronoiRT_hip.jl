@@ -45,6 +45,14 @@ const libvrt = get(ENV, "VRT_LIB", joinpath(@__DIR__, "..", "voronoirt_amd", "li
 
 # entry points chosen at run time (one device or several: Λ below) are called through dlsym'd function pointers
 const LIBVRT_HANDLE = Ref{Ptr{Cvoid}}(C_NULL)
+# the companion library of include/voronoirt_multi_accel.h (it links libvrt_hip.so): vrt_multi_lambda_set_acceleration / _last_acceleration
+const libvrt_multi_accel = joinpath(dirname(abspath(libvrt)), "libvrt_hip_multi_accel.so")   # beside the library it links
+const LIBVRT_MULTI_ACCEL_HANDLE = Ref{Ptr{Cvoid}}(C_NULL)
+function libvrt_multi_accel_handle()
+    libvrt_handle()
+    LIBVRT_MULTI_ACCEL_HANDLE[] == C_NULL && (LIBVRT_MULTI_ACCEL_HANDLE[] = dlopen(libvrt_multi_accel))
+    return LIBVRT_MULTI_ACCEL_HANDLE[]
+end
 function libvrt_handle()
     LIBVRT_HANDLE[] == C_NULL && (LIBVRT_HANDLE[] = dlopen(libvrt))
     return LIBVRT_HANDLE[]
@@ -273,8 +281,8 @@ The reference's Λ_voronoi with its loop body on the device.  Everything Λ_voro
 (LTE populations, α_cont, B_0, ε, C: :217-246) is computed by the reference's own functions; the loop
 (:253-283) is vrt_lambda_iterate; after every iteration populations and S_new are fetched and written to the
 HDF5 file exactly as the reference checkpoints them (:280-281); `criterion` keeps writing the history (:346).
-`ng = (start, period)`: second-order Ng acceleration inside the session (vrt_lambda_set_acceleration; one device
-only -- the multi-device session has no such entry), the first step after iterate `start`, then every `period`
+`ng = (start, period)`: second-order Ng acceleration inside the session (vrt_lambda_set_acceleration, or
+vrt_multi_lambda_set_acceleration when several devices are listed), the first step after iterate `start`, then every `period`
 iterates, both >= 4.  The keyword is unrun: Julia is not installed where the library is built.
 `S0` (nλ, n), `populations0` (n, 3), with or without units: the loop starts from them instead of LTE with S = B_0
 (vrt_lambda_set_state / vrt_multi_lambda_set_state; the state the reference checkpoints, :280-281) and continues bit for
@@ -351,8 +359,9 @@ function Λ(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, line::Hydr
                     plan, lc, w, ses))
     end
     if ng !== nothing
-        multi && error("Ng acceleration needs the one-device session (vrt_multi_lambda_* has no acceleration entry)")
-        check(ccall((:vrt_lambda_set_acceleration, libvrt), Cint, (Ptr{Cvoid}, Cint, Cint, Cint), ses[], 2, ng[1], ng[2]))
+        f_accel = multi ? :vrt_multi_lambda_set_acceleration : :vrt_lambda_set_acceleration
+        check(ccall(dlsym(multi ? libvrt_multi_accel_handle() : libvrt_handle(), f_accel), Cint, (Ptr{Cvoid}, Cint, Cint, Cint),
+                    ses[], 2, ng[1], ng[2]))
     end
     set_state(multi ? :vrt_multi_lambda_set_state : :vrt_lambda_set_state, ses[], plain_array(S0, I_unit, (nλ, n)),
               plain_array(populations0, u"m^-3", (n, 3)))
@@ -365,7 +374,8 @@ function Λ(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, line::Hydr
         isnan(diff[]) && println("NaN DIFF!")
         println("   Rel. diff.: $(diff[])")
         if ng !== nothing
-            check(ccall((:vrt_lambda_last_acceleration, libvrt), Cint, (Ptr{Cvoid}, Ref{Cint}, Ptr{Float64}, Ptr{Float64}),
+            f_last = multi ? :vrt_multi_lambda_last_acceleration : :vrt_lambda_last_acceleration
+            check(ccall(dlsym(multi ? libvrt_multi_accel_handle() : libvrt_handle(), f_last), Cint, (Ptr{Cvoid}, Ref{Cint}, Ptr{Float64}, Ptr{Float64}),
                         ses[], ng_applied, C_NULL, ng_coeffs))
             ng_applied[] != 0 && println("   Ng step ", ng_applied[] == 1 ? "taken" : "rejected", ": a = $(ng_coeffs[1]), b = $(ng_coeffs[2])")
         end

@@ -13,6 +13,13 @@ back), median and min..max over the repeats after warm-up.  The kernels alone: r
 `rocprofv3 --kernel-trace --stats -- python tools/accel_probe.py` and read k_ng_sums / k_ng_apply / k_ng_mirror.
 
     python tools/accel_probe.py [--a 59 --c 143] [--reps 24] [--json out.json]
+
+--multi W: the same three kinds of iterate, (a)-(c), of the MULTI-device session (vrt_multi_lambda_*) with device 0 listed W
+times -- W wavelength blocks, W histories, W sets of five sums added on the host, one (a, b), the step on every member or
+on none -- and nothing else.  A library selected with VRT_LIB_PATH that has no vrt_multi_lambda_set_acceleration (an older
+build, for the A/B of (a)) reports (a) only.
+
+    python tools/accel_probe.py --multi 2 [--reps 7] [--json out.json]
 """
 import argparse
 import ctypes
@@ -36,11 +43,12 @@ ap.add_argument("--a", type=int, default=59)
 ap.add_argument("--c", type=int, default=143)
 ap.add_argument("--reps", type=int, default=24, help="repeats per kind of iterate (>= 20)")
 ap.add_argument("--json", default="")
+ap.add_argument("--multi", type=int, default=0, help="time the multi-device session with device 0 listed this many times")
 args = ap.parse_args()
 
 pos, nbr, bounds = synth.bcc_grid(args.a, args.c, seed=2022)
-sites = vrt.VoronoiSites(pos, nbr, bounds, device=0)
-n = sites.n
+sites = None if args.multi else vrt.VoronoiSites(pos, nbr, bounds, device=0)
+n = pos.shape[0]
 rng = np.random.default_rng(7)
 nbb, nbf = 51, 20
 lambda0 = 121.567e-9
@@ -74,16 +82,25 @@ case = vrt.LineCase(lam=lam, blocks=blocks, lambda0=lambda0, c0=C0, velocity=vel
                     pref_ij=2 * np.pi / (H_PLANCK * C0) / 1000.0, pref_ji=2 * np.pi / (H_PLANCK * C0))
 
 L = _lib.load()
-plan, wq = api._quadrature_plan(sites, "ul7n12.dat", 3)
 lc, keep = case.c_struct()
 h = ctypes.c_void_p()
-api.check(L.vrt_lambda_create(plan._h, ctypes.byref(lc), api._d(api._f64(wq)), ctypes.byref(h)))
+if args.multi:
+    wq, th, ph, _ = vrt.read_quadrature("ul7n12.dat")
+    mp = vrt.MultiDevicePlan(pos, nbr, bounds, vrt.quadrature_directions(th, ph), dirs=[1 if t > 90 else -1 for t in th],
+                             devices=(0,) * args.multi)
+    api.check(L.vrt_multi_lambda_create(mp._h, ctypes.byref(lc), api._d(api._f64(wq)), ctypes.byref(h)))
+    prefix = "vrt_multi_lambda"
+else:
+    plan, wq = api._quadrature_plan(sites, "ul7n12.dat", 3)
+    api.check(L.vrt_lambda_create(plan._h, ctypes.byref(lc), api._d(api._f64(wq)), ctypes.byref(h)))
+    prefix = "vrt_lambda"
+fn = lambda name: getattr(L, f"{prefix}_{name}")
 d = ctypes.c_double()
 
 
 def iterate():
     t0 = time.perf_counter()
-    api.check(L.vrt_lambda_iterate(h, ctypes.byref(d)))
+    api.check(fn("iterate")(h, ctypes.byref(d)))
     return (time.perf_counter() - t0) * 1e3
 
 
@@ -91,26 +108,46 @@ def stats(ms):
     return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "repeats": len(ms)}
 
 
+def report(res):
+    for k, val in res.items():
+        print(k, val)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 for _ in range(3):
     iterate()
 off = [iterate() for _ in range(args.reps)]
-api.check(L.vrt_lambda_set_acceleration(h, 2, 4, 4))
+if not hasattr(L, f"{prefix}_set_acceleration"):         # an older build: (a) is all it has
+    fn("destroy")(h)
+    report({"library": _lib.LIB_PATH, "members": args.multi, "sites": int(n), "wavelengths": int(nlam_all), "iterate_off": stats(off)})
+    (mp if args.multi else sites).close()
+    sys.exit(0)
+api.check(fn("set_acceleration")(h, 2, 4, 4))
 record, step, verdicts = [], [], {1: 0, -1: 0}
 applied, coeffs = ctypes.c_int(0), np.zeros(2)
 it = 3 + args.reps
 while len(step) < args.reps:
     ms = iterate()
     it += 1
-    api.check(L.vrt_lambda_last_acceleration(h, ctypes.byref(applied), None, api._d(coeffs)))
+    api.check(fn("last_acceleration")(h, ctypes.byref(applied), None, api._d(coeffs)))
     if applied.value:
         if verdicts[1] + verdicts[-1] > 0:          # (the first due iterate: an incomplete history, and the warm-up of the kernels)
             step.append(ms)
         verdicts[applied.value] += 1
     elif it % 4:
         record.append(ms)
-api.check(L.vrt_lambda_set_acceleration(h, 0, 0, 0))
+api.check(fn("set_acceleration")(h, 0, 0, 0))
 off2 = [iterate() for _ in range(args.reps)]
-L.vrt_lambda_destroy(h)
+fn("destroy")(h)
+if args.multi:
+    report({"library": _lib.LIB_PATH, "members": args.multi, "sites": int(n), "wavelengths": int(nlam_all),
+            "S_bytes": 8 * n * nlam_all, "iterate_off": stats(off), "iterate_off_after": stats(off2),
+            "iterate_recording": stats(record), "iterate_with_step": stats(step), "steps_taken": verdicts[1],
+            "steps_rejected": verdicts[-1]})
+    mp.close()
+    sys.exit(0)
 
 # (d) the standalone entry on arrays of the session's S size
 dev = torch.device("cuda", 0)
@@ -138,9 +175,5 @@ res = {"sites": int(n), "wavelengths": int(nlam_all), "S_bytes": 8 * count,
        "iterate_off": stats(off), "iterate_off_after": stats(off2), "iterate_recording": stats(record),
        "iterate_with_step": stats(step), "steps_taken": verdicts[1], "steps_rejected": verdicts[-1],
        "ng_accelerate_dev": dict(stats(alone), bytes=nbytes, GBps_at_median=nbytes / statistics.median(alone) / 1e6)}
-for k, val in res.items():
-    print(k, val)
-if args.json:
-    with open(args.json, "w") as f:
-        json.dump(res, f, indent=1)
+report(res)
 sites.close()

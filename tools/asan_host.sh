@@ -30,6 +30,8 @@ cat $out/undef.txt $out/declared.txt | sort -u | comm -23 - $out/defined.txt > $
 { echo '.text'; while read sym; do printf '.globl %s\n.type %s,@function\n%s:\n  movl $-3, %%eax\n  ret\n' $sym $sym $sym; done < $out/to_stub.txt; echo '.section .note.GNU-stack,"",@progbits'; } > $out/stubs_auto.s
 g++ -c $out/stubs_auto.s -o $out/stubs_auto.o
 g++ -shared $san $out/*.o -L/opt/rocm/lib -lamdhip64 -lpthread -ldl -Wl,-rpath,/opt/rocm/lib -o $out/libvrt_hip.so
+# the companion of include/voronoirt_multi_accel.h beside it (voronoirt_amd/_lib.py binds it from there)
+g++ $flags -shared voronoirt_amd/csrc/vrt_multi_accel.cpp -L$out -lvrt_hip -Wl,-rpath,'$ORIGIN' -o $out/libvrt_hip_multi_accel.so
 echo "[$mode] built $out/libvrt_hip.so: $(wc -l < $out/to_stub.txt) device-side symbols stubbed"
 if [ $mode = check ]; then
   python3 -c "import ctypes, sys; ctypes.CDLL('$PWD/$out/libvrt_hip.so'); print('[check] loads with every symbol resolved')"

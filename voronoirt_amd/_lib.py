@@ -229,6 +229,15 @@ PROTOTYPES = {
 }
 
 
+# the same for include/voronoirt_multi_accel.h (voronoirt.h includes it): the acceleration entries of vrt_multi_lambda_*,
+# exported by the companion library libvrt_hip_multi_accel.so beside LIB_PATH and bound onto the object load() returns
+ACCEL_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(LIB_PATH)), "libvrt_hip_multi_accel.so")
+MULTI_ACCEL_PROTOTYPES = {
+    "vrt_multi_lambda_set_acceleration": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "vrt_multi_lambda_last_acceleration": (ctypes.c_int, [vp, p_int, p_dbl, p_dbl]),
+}
+
+
 class VrtError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"libvrt_hip error {code}: {message}")
@@ -266,6 +275,18 @@ def load() -> ctypes.CDLL:
             raise AttributeError(f"{LIB_PATH} does not export {name}")
         fn.restype = res
         fn.argtypes = args
+    # the companion stands beside the library it was built against and links that one; a build without it (an older one
+    # selected with VRT_LIB_PATH) has no acceleration of the multi-device session: MultiDevicePlan.lambda_iteration(ng=) says so
+    accel_path = ACCEL_LIB_PATH
+    if os.path.exists(accel_path):
+        accel = ctypes.CDLL(accel_path)
+        for name, (res, args) in MULTI_ACCEL_PROTOTYPES.items():
+            fn = getattr(accel, name)
+            fn.restype = res
+            fn.argtypes = args
+            setattr(lib, name, fn)
+    elif not os.environ.get("VRT_LIB_PATH"):
+        raise ImportError(f"{accel_path} is missing: build it with `python -m voronoirt_amd.build`")
     _lib = lib
     return lib
 

@@ -485,11 +485,14 @@ class MultiDevicePlan:
         return J
 
     def lambda_iteration(self, eps_conv: float, maxiter: int, case, weights, S0=None, populations0=None, checkpoint=None,
-                         checkpoint_every: int = 1, resume=None):
+                         checkpoint_every: int = 1, resume=None, ng=None):
         """Λ_voronoi (src/lambda_iteration.jl:205-300) across the devices (`vrt_multi_lambda_*`): wavelength blocks per
         device, one all-reduce of the rate-integral shares per iteration.  Returns (J, S_new, populations (3, n), history).
         S0, populations0, checkpoint, checkpoint_every, resume as for `Lambda_voronoi_host`
-        (`vrt_multi_lambda_set_state`: every device takes its wavelength block of S and all the populations)."""
+        (`vrt_multi_lambda_set_state`: every device takes its wavelength block of S and all the populations).
+        ng=(start, period) as for `Lambda_voronoi_host` (`vrt_multi_lambda_set_acceleration`: every device keeps the history
+        of its own block, the five sums are added on the host in device order, the step is taken on every device or on
+        none); the tuple gains a fifth element, the list of (iterate, applied, a, b) of every due step."""
         L = _lib.load()
         lc, keep = case.c_struct()
         n, nlam = self.n, int(keep["lam"].size)
@@ -497,12 +500,16 @@ class MultiDevicePlan:
         h = ctypes.c_void_p()
         check(L.vrt_multi_lambda_create(self._h, ctypes.byref(lc), _d(_f64(weights)), ctypes.byref(h)))
         try:
-            J, S, pops, history, _, i = _session_loop(L, "multi_lambda", h, n, nlam, eps_conv, maxiter, start, checkpoint,
-                                                      checkpoint_every, None, "lambda_iteration")
+            if ng is not None:
+                if not hasattr(L, "vrt_multi_lambda_set_acceleration"):
+                    raise ImportError(f"lambda_iteration: ng needs {_lib.ACCEL_LIB_PATH}, which this build of the library lacks")
+                check(L.vrt_multi_lambda_set_acceleration(h, 2, *_ng_settings(ng)))
+            J, S, pops, history, steps, i = _session_loop(L, "multi_lambda", h, n, nlam, eps_conv, maxiter, start, checkpoint,
+                                                          checkpoint_every, ng, "lambda_iteration")
             if i == 0:
                 S[:] = keep["B0"] if start[0] is None else start[0]
                 pops[:] = keep["lte"] if start[1] is None else start[1]
-            return J, S, pops, history
+            return (J, S, pops, history) if ng is None else (J, S, pops, history, steps)
         finally:
             L.vrt_multi_lambda_destroy(h)
 

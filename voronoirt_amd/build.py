@@ -14,7 +14,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvrt_hip.so")
 SOURCES = ["vrt_api.cpp", "vrt_grid.cpp", "vrt_schedule.cpp", "vrt_patch.cpp", "vrt_lambda.cpp", "vrt_multi.cpp", "vrt_tessellate.cpp", "vrt_kernels.hip", "vrt_tables.hip", "vrt_layers.hip", "vrt_patch.hip", "vrt_regular.hip", "vrt_regular_lambda.hip", "vrt_physics.hip", "vrt_raster.hip", "vrt_synth.hip", "vrt_accel.hip", "vrt_continuum.hip"]
-HEADERS = [os.path.join(CSRC, h) for h in ("vrt_internal.h", "vrt_device.h", "vrt_weights.h", "vrt_regular.h", "vrt_voigt.h", "vrt_layout_kernels.h", "vrt_tile_kernels.h", "vrt_step_kernels.h")] + [os.path.join(ROOT, "include", "voronoirt.h")]
+HEADERS = [os.path.join(CSRC, h) for h in ("vrt_internal.h", "vrt_device.h", "vrt_weights.h", "vrt_regular.h", "vrt_voigt.h", "vrt_layout_kernels.h", "vrt_tile_kernels.h", "vrt_step_kernels.h")] + [os.path.join(ROOT, "include", h) for h in ("voronoirt.h", "voronoirt_multi_accel.h")]
 
 
 def _hipcc() -> str:
@@ -41,12 +41,27 @@ def build_library(force: bool = False, verbose: bool = False, diag: bool = False
     VRT_LIB_PATH; nothing else loads it."""
     if diag:
         return _build(os.path.join(HERE, "libvrt_hip_diag.so"), ["-DVRT_DIAG"], verbose)
-    if not force and not is_stale():
-        return LIB
-    return _build(LIB, [], verbose)
+    if force or is_stale():
+        _build(LIB, [], verbose)
+    build_multi_accel(force, verbose)
+    return LIB
 
 
-def _build(out: str, extra, verbose: bool, sources=None) -> str:
+ACCEL_SRC = os.path.join(CSRC, "vrt_multi_accel.cpp")
+ACCEL_LIB = os.path.join(HERE, "libvrt_hip_multi_accel.so")
+
+
+def build_multi_accel(force: bool = False, verbose: bool = False) -> str:
+    """The companion library of include/voronoirt_multi_accel.h: csrc/vrt_multi_accel.cpp, two C entries that forward into
+    libvrt_hip.so, which it links (found beside it at run time).  Rebuilt when its source, a header or libvrt_hip.so is
+    newer."""
+    deps = [ACCEL_SRC, LIB] + HEADERS
+    if not force and os.path.exists(ACCEL_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(ACCEL_LIB) for d in deps):
+        return ACCEL_LIB
+    return _build(ACCEL_LIB, ["-L", HERE, "-Wl,-rpath,$ORIGIN"], verbose, sources=[ACCEL_SRC], libs=["-lvrt_hip"])
+
+
+def _build(out: str, extra, verbose: bool, sources=None, libs=()) -> str:
     cmd = [
         _hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
         # build-wide floating-point contract: no FMA contraction on host or device, so neighbour
@@ -55,7 +70,7 @@ def _build(out: str, extra, verbose: bool, sources=None) -> str:
         "-Wall", "-Wno-unused-result",
         "-I", os.path.join(ROOT, "include"), "-I", CSRC,
         "-o", out,
-    ] + list(extra) + (sources or [os.path.join(CSRC, s) for s in SOURCES]) + ["-lpthread", "-ldl"]
+    ] + list(extra) + (sources or [os.path.join(CSRC, s) for s in SOURCES]) + list(libs) + ["-lpthread", "-ldl"]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.check_call(cmd)

@@ -13,7 +13,8 @@
 //
 // The sums, the coefficients and the apply are separate steps (ng_sums, ng_coefficients, ng_apply; public as vrt_ng_sums_dev,
 // vrt_ng_coefficients, vrt_ng_apply_dev): vrt_ng_accelerate_dev and ng_after_iterate run the three on one array; a caller
-// that holds S in several arrays runs the first and the last per array and adds the partial sums in one fixed order.
+// that holds S in several arrays runs the first and the last per array and adds the partial sums in one fixed order
+// (vrt_multi_lambda_iterate does, one array per member, over the phases of vrt_internal.h).
 //
 // Element ranges (NgRange): `dense` contiguous doubles (an even count, read as double2), then `tail` doubles `tstride` apart.
 // A caller-layout array is (count & ~1, count & 1, 1); a sweep-order plane set with an odd wavelength count is every full
@@ -301,32 +302,24 @@ int ng_configure(NgState &ng, int order, int start, int period, size_t alloc_cou
     return VRT_OK;
 }
 
-// After the plain update of iterate number `iterate` (1-based): iterates until the next due one d = 1, 2, 3 -> S is kept as
-// x_d; d = 0 with the three before it kept -> the step, x_acc written over x3's buffer, which then BECOMES the session's S
-// (a rejected step leaves S untouched).  alloc_count: doubles of an S buffer (padding included, copied along).
+// After the plain update of iterate number `iterate` (1-based), for a session that holds S in ONE array: the phases of
+// vrt_internal.h in turn.  A recording iterate keeps S as x_d; a due one with the three before it kept takes the step, x_acc
+// written over x3's buffer, which then BECOMES the session's S (a rejected step leaves S untouched).
 int ng_after_iterate(NgState &ng, int64_t iterate, DevBuf<double> &S, size_t alloc_count, const NgRange &rg, hipStream_t st)
 {
     ng.last_applied = 0;
-    if (!ng.order) return VRT_OK;
-    const int64_t d = iterate < ng.start ? ng.start - iterate : (ng.period - (iterate - ng.start) % ng.period) % ng.period;
-    if (d >= 1 && d <= 3) {
-        VRT_HIP_TRY(hipMemcpyAsync(ng.hist[d - 1], S, sizeof(double) * alloc_count, hipMemcpyDeviceToDevice, st));
-        ng.have |= 1u << (d - 1);
-        return VRT_OK;
-    }
-    if (d != 0) return VRT_OK;
-    const bool complete = ng.have == 7u;
-    ng.have = 0;
-    if (!complete) return VRT_OK;               // switched on too late for this one: nothing due
+    const int due = ng_due(ng, iterate);
+    if (due == kNgNothing) return VRT_OK;
+    if (due != kNgStep) return ng_record(ng, due, S, alloc_count, st);
+    if (!ng_take_history(ng)) return VRT_OK;    // switched on too late for this one: nothing due
     int rc;
     if ((rc = ng_sums(rg, S, ng.hist[0], ng.hist[1], ng.hist[2], ng.d_ws, ng.last_sums, st))) return rc;
     ng.last_applied = -1;
-    if (!ng_coefficients(ng.last_sums, ng.last_coeffs)) return VRT_OK;
-    bool ok = false;
-    if ((rc = ng_apply(rg, ng.last_coeffs[0], ng.last_coeffs[1], S, ng.hist[0], ng.hist[1], ng.hist[2], ng.d_ws, &ok, st))) return rc;
-    if (!ok) return VRT_OK;
-    std::swap(S, ng.hist[2]);
-    ng.last_applied = 1;
+    const bool valid = ng_coefficients(ng.last_sums, ng.last_coeffs);
+    NgPiece piece{&ng, &S, false};
+    if (valid && (rc = ng_apply(rg, ng.last_coeffs[0], ng.last_coeffs[1], S, ng.hist[0], ng.hist[1], ng.hist[2], ng.d_ws, &piece.good, st)))
+        return rc;
+    if (ng_commit(&piece, 1, valid)) ng.last_applied = 1;
     return VRT_OK;
 }
 
@@ -344,18 +337,7 @@ int ng_report(const NgState &ng, int *applied, double sums[5], double coeffs[2])
 
 using namespace vrt;
 
-namespace {
-
-// a caller-layout array of `count` doubles
-inline NgRange dense_range(int64_t count)
-{
-    NgRange rg;
-    rg.dense = count & ~(int64_t)1; rg.tail = count & 1; rg.tstride = 1;
-    return rg;
-}
-
-}  // namespace
-
+// (a caller-layout array of `count` doubles: ng_S_range(count, 1, false))
 extern "C" int vrt_ng_sums_dev(int64_t count, const double *d_x0, const double *d_x1, const double *d_x2, const double *d_x3,
                                double sums[5], void *stream)
 {
@@ -366,7 +348,7 @@ extern "C" int vrt_ng_sums_dev(int64_t count, const double *d_x0, const double *
         if (rc) return rc;
         DevBuf<double> ws;
         if ((rc = ws.alloc(kNgWorkspace))) return rc;
-        return ng_sums(dense_range(count), d_x0, d_x1, d_x2, d_x3, ws, sums, (hipStream_t)stream);
+        return ng_sums(ng_S_range(count, 1, false), d_x0, d_x1, d_x2, d_x3, ws, sums, (hipStream_t)stream);
     });
 }
 
@@ -391,7 +373,7 @@ extern "C" int vrt_ng_apply_dev(int64_t count, double a, double b, const double 
         if ((rc = ws.alloc(kNgWorkspace))) return rc;
         bool ok = false;
         *good = 0;
-        if ((rc = ng_apply(dense_range(count), a, b, d_x0, d_x1, d_x2, d_out, ws, &ok, (hipStream_t)stream))) return rc;
+        if ((rc = ng_apply(ng_S_range(count, 1, false), a, b, d_x0, d_x1, d_x2, d_out, ws, &ok, (hipStream_t)stream))) return rc;
         *good = ok ? 1 : 0;
         return VRT_OK;
     });
@@ -410,7 +392,7 @@ extern "C" int vrt_ng_accelerate_dev(int64_t count, const double *d_x0, const do
         hipStream_t st = (hipStream_t)stream;
         DevBuf<double> ws;
         if ((rc = ws.alloc(kNgWorkspace))) return rc;
-        const NgRange rg = dense_range(count);
+        const NgRange rg = ng_S_range(count, 1, false);
         *applied = 0;
         if ((rc = ng_sums(rg, d_x0, d_x1, d_x2, d_x3, ws, sums, st))) return rc;
         if (!ng_coefficients(sums, coeffs)) return VRT_OK;

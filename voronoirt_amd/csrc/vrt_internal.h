@@ -722,11 +722,80 @@ struct NgState {
     int last_applied = 0;                               // of the last iterate: 1 taken, 0 none due, -1 rejected
     double last_sums[5] = {0, 0, 0, 0, 0}, last_coeffs[2] = {0, 0};
 };
+// the physical entries of a session's S of `nlam` wavelengths at `n` sites: a sweep-order plane set is every full pair
+// plane dense, then the first halves of an odd nlam's last plane (stride 2; the padding wavelength is never touched);
+// the caller's layout is n nlam contiguous doubles
+inline NgRange ng_S_range(int64_t n, int64_t nlam, bool sweep_order)
+{
+    NgRange rg;
+    if (sweep_order) { rg.dense = (nlam / 2) * 2 * n; rg.tail = nlam & 1 ? n : 0; rg.tstride = 2; }
+    else { rg.dense = (n * nlam) & ~(int64_t)1; rg.tail = (n * nlam) & 1; rg.tstride = 1; }
+    return rg;
+}
 int ng_check_settings(int order, int start, int period);
 int ng_configure(NgState &ng, int order, int start, int period, size_t alloc_count);
 void ng_release(NgState &ng);
+// The device halves of a step on one array (they synchronise `st`): the five sums of x0 .. x3 into sums[5]; x_acc of
+// (a, b) into `out` with *ok = every x_acc finite and > 0.  d_ws: the NgState's workspace.  ng_coefficients: host only.
+int ng_sums(const NgRange &rg, const double *x0, const double *x1, const double *x2, const double *x3, double *d_ws,
+            double sums[5], hipStream_t st);
+bool ng_coefficients(const double sums[5], double coeffs[2]);
+int ng_apply(const NgRange &rg, double a, double b, const double *x0, const double *x1, const double *x2, double *out,
+             double *d_ws, bool *ok, hipStream_t st);
+// ---- the phases of what follows a plain update, shared by the sessions that hold S in one array (ng_after_iterate) and
+// the multi-device session, whose S is one array per member (vrt_multi.cpp): due -> record | history, sums, apply, commit.
+// They are host code and live here, so that a host-only build runs them too (tests/probes/ng_phases_main.cpp).
+enum { kNgNothing = 0, kNgRecord1 = 1, kNgRecord2 = 2, kNgRecord3 = 3, kNgStep = 4 };
+// what iterate number `iterate` (1-based) calls for -- THE schedule: with d iterates to go until the next due one,
+// d = 1, 2, 3 -> S is kept as x_d (kNgRecord1..3 = d); d = 0 -> kNgStep; anything else, or order 0 -> kNgNothing
+inline int ng_due(const NgState &ng, int64_t iterate)
+{
+    if (!ng.order) return kNgNothing;
+    const int64_t d = iterate < ng.start ? ng.start - iterate : (ng.period - (iterate - ng.start) % ng.period) % ng.period;
+    return d == 0 ? kNgStep : (d <= 3 ? (int)d : kNgNothing);
+}
+// S kept as x_d, enqueued on `st`.  alloc_count: doubles of an S buffer (padding included, copied along).
+inline int ng_record(NgState &ng, int d, const double *S, size_t alloc_count, hipStream_t st)
+{
+    VRT_HIP_TRY(hipMemcpyAsync(ng.hist[d - 1], S, sizeof(double) * alloc_count, hipMemcpyDeviceToDevice, st));
+    ng.have |= 1u << (d - 1);
+    return VRT_OK;
+}
+// a step is due: the history is used up either way; false when it was not complete (switched on too late, or dropped by
+// *_set_state): nothing is due then
+inline bool ng_take_history(NgState &ng)
+{
+    const bool complete = ng.have == 7u;
+    ng.have = 0;
+    return complete;
+}
+// the session's sums from its members': added in the order of the calls, the first one copied
+inline void ng_add_sums(double total[5], const double part[5], bool first)
+{
+    for (int k = 0; k < 5; k++) total[k] = first ? part[k] : total[k] + part[k];
+}
+// One array of S with its history and the verdict of its apply (x_acc stands in ng->hist[2], x3's buffer).
+struct NgPiece {
+    NgState *ng;
+    DevBuf<double> *S;
+    bool good;
+};
+// ALL OR NOTHING: with valid coefficients and every verdict good, every piece's x_acc buffer BECOMES its S (true);
+// otherwise no S changes (false).  Every verdict is looked at before the first swap.
+inline bool ng_commit(NgPiece *pieces, int count, bool coeffs_valid)
+{
+    if (!coeffs_valid) return false;
+    for (int i = 0; i < count; i++)
+        if (!pieces[i].good) return false;
+    for (int i = 0; i < count; i++) std::swap(*pieces[i].S, pieces[i].ng->hist[2]);
+    return true;
+}
 int ng_after_iterate(NgState &ng, int64_t iterate, DevBuf<double> &S, size_t alloc_count, const NgRange &rg, hipStream_t st);
 int ng_report(const NgState &ng, int *applied, double sums[5], double coeffs[2]);
 int launch_ng_mirror(vrt_grid *g, int64_t nlam, const double *dS_up, double *dS_down, hipStream_t st);
+// the multi-device session's acceleration (vrt_multi.cpp); the C entries of voronoirt_multi_accel.h are built into the
+// companion library libvrt_hip_multi_accel.so (vrt_multi_accel.cpp) and forward to these
+int multi_lambda_set_acceleration(vrt_multi_lambda *s, int order, int start, int period);
+int multi_lambda_last_acceleration(const vrt_multi_lambda *s, int *applied, double sums[5], double coeffs[2]);
 
 }  // namespace vrt

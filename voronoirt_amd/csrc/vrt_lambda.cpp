@@ -161,11 +161,8 @@ struct vrt_lambda {
 // the S buffer a session's acceleration works on: doubles allocated, and which of them are physical entries
 static size_t lambda_S_count(const vrt_lambda *s, NgRange *rg)
 {
-    const int64_t n = s->n, nlam = s->nlam;
-    if (rg) { rg->dense = (nlam / 2) * 2 * n; rg->tail = nlam & 1 ? n : 0; rg->tstride = 2; }
-    if (s->native) return (size_t)vrt_plan_native_plane_count(s->p, nlam);
-    if (rg) { rg->dense = (n * nlam) & ~(int64_t)1; rg->tail = (n * nlam) & 1; rg->tstride = 1; }
-    return (size_t)(n * nlam);
+    if (rg) *rg = ng_S_range(s->n, s->nlam, s->native);
+    return s->native ? (size_t)vrt_plan_native_plane_count(s->p, s->nlam) : (size_t)(s->n * s->nlam);
 }
 
 struct LambdaDelete { void operator()(vrt_lambda *s) const { vrt_lambda_destroy(s); } };

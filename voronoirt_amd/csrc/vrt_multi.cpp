@@ -445,6 +445,7 @@ struct LambdaMember {
     Event ev;
     // the block's S and J in sweep order between the steps (as the one-device session keeps them: vrt_lambda.cpp)
     DevBuf<double> d_S_nat[2], d_J_nat[2], d_B_up;
+    NgState ng;                         // this block's history and workspace (vrt_multi_lambda_set_acceleration; off: nothing)
     ~LambdaMember() { (void)hipSetDevice(device); }    // (its own copy: the vrt_multi may be gone already); then the members go
 };
 
@@ -458,6 +459,8 @@ struct vrt_multi_lambda {
     std::vector<LambdaMember> lm;
     int iterations = 0;
     bool native = false;                // every member keeps its block in sweep order (VRT_LAMBDA_NATIVE, all plans fit)
+    NgState ng;                         // the settings and the last report; the buffers are the members'
+    bool ng_torn = false;               // an accepted step whose down-order copy could not be rewritten: S is inconsistent
 };
 
 namespace {
@@ -476,6 +479,97 @@ int dupload_cols(DevBuf<double> &d, const double *h, size_t rows, int64_t nlam, 
     int rc = d.alloc(rows * nb);
     if (rc || nb == 0) return rc;
     VRT_HIP_TRY(hipMemcpy2DAsync(d, sizeof(double) * nb, h + l0, sizeof(double) * (size_t)nlam, sizeof(double) * nb, rows, hipMemcpyHostToDevice, st));
+    return VRT_OK;
+}
+
+// ---- Ng acceleration of the session (vrt_multi_lambda_set_acceleration): the phases of vrt_internal.h, each over every
+// member that holds wavelengths.  A member's S is its up-order plane set (sweep-order session) or its d_S_new columns.
+DevBuf<double> &ng_member_S(vrt_multi_lambda *s, LambdaMember &l) { return s->native ? l.d_S_nat[0] : l.d_S_new; }
+size_t ng_member_count(const vrt_multi_lambda *s, const vrt_plan *p, int64_t nb)
+{
+    return s->native ? (size_t)vrt_plan_native_plane_count(p, nb) : (size_t)(s->n * nb);
+}
+
+// body(d, member, its share of the session) -> rc on every member with wavelengths, one host thread each, the member's
+// device current and its plan locked
+template <typename Body>
+int ng_on_members(vrt_multi_lambda *s, Body body)
+{
+    vrt_multi *mm = s->mm;
+    auto work = [&](int d) {
+        Member &me = mm->m[(size_t)d];
+        LambdaMember &l = s->lm[(size_t)d];
+        me.rc = VRT_OK;
+        if (l.l1 <= l.l0) return;
+        if (hipSetDevice(me.device) != hipSuccess) { me.rc = VRT_ENODEVICE; me.err = "hipSetDevice"; return; }
+        std::lock_guard<std::mutex> plock(me.plan_all->mu);
+        if ((me.rc = body(d, me, l))) me.err = vrt_last_error();
+    };
+    if (!run_workers((int)mm->m.size(), work)) return fail(VRT_ENOMEM, "out of host memory in a device worker");
+    for (const Member &me : mm->m)
+        if (me.rc) return fail(me.rc, "device " + std::to_string(me.device) + ": " + me.err);
+    return VRT_OK;
+}
+
+// After the plain update of iterate s->iterations (every stream is synchronised, mm->mu is held).  A due step: every member's
+// five sums, added on the host in member order; ONE (a, b); x_acc of every member into its oldest history buffer; and only
+// with every verdict in and good do the buffers become the members' S.
+int multi_ng_after_iterate(vrt_multi_lambda *s)
+{
+    const int W = (int)s->lm.size();
+    s->ng.last_applied = 0;
+    const int due = ng_due(s->ng, s->iterations);
+    if (due == kNgNothing) return VRT_OK;
+    if (due != kNgStep)
+        return ng_on_members(s, [&](int, Member &me, LambdaMember &l) {
+            int rc = ng_record(l.ng, due, ng_member_S(s, l), ng_member_count(s, me.plan_all.get(), l.l1 - l.l0), me.stream);
+            if (!rc && hipStreamSynchronize(me.stream) != hipSuccess) rc = fail(VRT_ENODEVICE, "copying S into the history failed");
+            return rc;
+        });
+    bool complete = true;
+    for (LambdaMember &l : s->lm)
+        if (l.l1 > l.l0 && !ng_take_history(l.ng)) complete = false;
+    if (!complete) return VRT_OK;               // switched on too late for this one, or the state was replaced: nothing due
+    std::vector<double> part(5 * (size_t)W, 0.0);
+    int rc = ng_on_members(s, [&](int d, Member &me, LambdaMember &l) {
+        return ng_sums(ng_S_range(s->n, l.l1 - l.l0, s->native), ng_member_S(s, l), l.ng.hist[0], l.ng.hist[1], l.ng.hist[2],
+                       l.ng.d_ws, &part[5 * (size_t)d], me.stream);
+    });
+    if (rc) return rc;
+    // ((s_0 + s_1) + s_2) + ... over the members that hold wavelengths: never the order in which the workers finished
+    std::vector<NgPiece> pieces;
+    std::vector<int> piece_of((size_t)W, -1);
+    for (int d = 0; d < W; d++) {
+        LambdaMember &l = s->lm[(size_t)d];
+        if (l.l1 <= l.l0) continue;
+        ng_add_sums(s->ng.last_sums, &part[5 * (size_t)d], pieces.empty());
+        piece_of[(size_t)d] = (int)pieces.size();
+        pieces.push_back(NgPiece{&l.ng, &ng_member_S(s, l), false});
+    }
+    s->ng.last_applied = -1;
+    const bool valid = ng_coefficients(s->ng.last_sums, s->ng.last_coeffs);
+    if (valid) {
+        const double a = s->ng.last_coeffs[0], b = s->ng.last_coeffs[1];
+        rc = ng_on_members(s, [&](int d, Member &me, LambdaMember &l) {
+            return ng_apply(ng_S_range(s->n, l.l1 - l.l0, s->native), a, b, ng_member_S(s, l), l.ng.hist[0], l.ng.hist[1], l.ng.hist[2],
+                            l.ng.d_ws, &pieces[(size_t)piece_of[(size_t)d]].good, me.stream);
+        });
+        if (rc) return rc;
+    }
+    if (!ng_commit(pieces.data(), (int)pieces.size(), valid)) return VRT_OK;
+    if (s->native) {
+        // the down-order copies from the new up-order ones, value for value
+        rc = ng_on_members(s, [&](int, Member &me, LambdaMember &l) {
+            int r = launch_ng_mirror(me.grid.get(), l.l1 - l.l0, l.d_S_nat[0], l.d_S_nat[1], me.stream);
+            if (!r && hipStreamSynchronize(me.stream) != hipSuccess) r = fail(VRT_ENODEVICE, "rewriting the down-order S failed");
+            return r;
+        });
+        if (rc) {                               // the up-order copies are x_acc, a down-order copy is not: no further iterate
+            s->ng_torn = true;
+            return rc;
+        }
+    }
+    s->ng.last_applied = 1;
     return VRT_OK;
 }
 
@@ -601,6 +695,9 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
     return guarded([&] {
         vrt_multi *mm = s->mm;
         std::lock_guard<std::mutex> lock(mm->mu);
+        if (s->ng_torn)
+            return fail(VRT_ENODEVICE, "an accepted Ng step failed while rewriting the down-order S: the session's S is inconsistent, "
+                                       "replace it with vrt_multi_lambda_set_state or destroy the session");
         const int W = (int)mm->m.size();
         const int64_t n = s->n, nlam = s->nlam;
         // ---- every device: its wavelengths' share of the iteration, enqueued on its stream ----------------------------
@@ -698,9 +795,56 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
         }
         *max_rel_change = is_nan ? std::nan("") : worst;
         s->iterations++;
+        if (s->ng.order) return multi_ng_after_iterate(s);       // history copies or the step, on the S of the plain update
+        s->ng.last_applied = 0;
         return VRT_OK;
     });
 }
+
+}  // extern "C"
+
+// (the C entries vrt_multi_lambda_set_acceleration / _last_acceleration call these two: vrt_multi_accel.cpp)
+int vrt::multi_lambda_set_acceleration(vrt_multi_lambda *s, int order, int start, int period)
+{
+    if (!s) return fail(VRT_EINVAL, "NULL session");
+    int rc = ng_check_settings(order, start, period);
+    if (rc) return rc;
+    return guarded([&] {
+        vrt_multi *mm = s->mm;
+        std::lock_guard<std::mutex> lock(mm->mu);
+        const int W = (int)mm->m.size();
+        s->ng.last_applied = 0;
+        // every member with wavelengths: three copies of ITS block of S and a workspace (order 0: released)
+        for (int d = 0; d < W && !rc; d++) {
+            Member &me = mm->m[(size_t)d];
+            LambdaMember &l = s->lm[(size_t)d];
+            if (l.l1 <= l.l0) continue;
+            if (hipSetDevice(me.device) != hipSuccess) { rc = fail(VRT_ENODEVICE, "hipSetDevice failed"); break; }
+            std::lock_guard<std::mutex> plock(me.plan_all->mu);
+            rc = ng_configure(l.ng, order, start, period, ng_member_count(s, me.plan_all.get(), l.l1 - l.l0));
+        }
+        if (rc) {
+            // one member could not: no member keeps a history, and the session goes on as a plain one
+            for (int d = 0; d < W; d++) {
+                (void)hipSetDevice(mm->m[(size_t)d].device);
+                (void)ng_configure(s->lm[(size_t)d].ng, 0, 0, 0, 0);
+            }
+            order = 0;
+        }
+        s->ng.order = order;
+        s->ng.start = order ? start : 0;
+        s->ng.period = order ? period : 0;
+        return rc;
+    });
+}
+
+int vrt::multi_lambda_last_acceleration(const vrt_multi_lambda *s, int *applied, double sums[5], double coeffs[2])
+{
+    if (!s || !applied) return fail(VRT_EINVAL, "NULL argument");
+    return ng_report(s->ng, applied, sums, coeffs);
+}
+
+extern "C" {
 
 int vrt_multi_lambda_get(vrt_multi_lambda *s, double *J, double *S, double *populations, double *R, double *gamma)
 {
@@ -798,7 +942,10 @@ int vrt_multi_lambda_set_state(vrt_multi_lambda *s, const double *S, const doubl
             } else if (S && l.l1 > l.l0)
                 std::swap(l.d_S_new, sg.S_up);
             if (populations) std::swap(l.d_pops, sg.pops);
+            l.ng.have = 0;                                   // iterates of another state are no history of this one
         }
+        s->ng.last_applied = 0;
+        if (S) s->ng_torn = false;                           // both sweep-order copies of every member are new
         return (int)VRT_OK;
     });
 }
