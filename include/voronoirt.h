@@ -665,6 +665,25 @@ int vrt_regular_execute_dev(vrt_regular *r, int64_t n_solve, const double *k, co
                             int n_sweeps, double *dI_out, void *stream);
 int vrt_regular_last_solve_ms(const vrt_regular *r, double *ms);
 
+/* What the last batch of solves on r was launched as (read-only host bookkeeping; any entry that solves on r sets it,
+ * the Λ-iteration sessions included; before the first solve: VRT_EINVAL).  *form = one of the kernels below; for the
+ * two k_regular_solve forms OR-ed with the row flags: set where the rows of a yz plane (ny - 2 points) / of an xz plane
+ * (nx - 2 points) fit one point per thread and take the pipelined row march, clear where they take the strided row
+ * loop.  *threads = the workgroup size of that kernel. */
+enum {
+    VRT_REG_FORM_SOLVE256 = 0,          /* k_regular_solve<256>: one workgroup walks all planes of a solve */
+    VRT_REG_FORM_SOLVE1024 = 1,         /* k_regular_solve<1024> */
+    VRT_REG_FORM_XY_MARCH_LDS1 = 2,     /* all-xy batch: k_reg_xy_coefs + k_reg_xy_march_lds<1> (points per thread) */
+    VRT_REG_FORM_XY_MARCH_LDS2 = 3,     /* ... <2> */
+    VRT_REG_FORM_XY_MARCH_LDS4 = 4,     /* ... <4> */
+    VRT_REG_FORM_XY_MARCH_LDS0 = 5,     /* ... <0>: any number of points per thread, coefficients loaded where used */
+    VRT_REG_FORM_XY_MARCH_MEM = 6,      /* k_reg_xy_coefs + k_reg_xy_march_mem: upwind plane read back from memory */
+    VRT_REG_FORM_KERNEL_MASK = 0xff,
+    VRT_REG_FORM_YZ_ROW_MARCH = 0x100,
+    VRT_REG_FORM_XZ_ROW_MARCH = 0x200
+};
+int vrt_regular_last_launch_form(const vrt_regular *r, int *form, int *threads);
+
 /* ---- the line Λ-iteration on the regular grid (J_λ_regular, Λ_regular: src/lambda_iteration.jl:1-58, :116-205) ----
  * The regular half of the reference's comparison, the twin of vrt_plan_execute_line / vrt_lambda_* on a vrt_regular r.
  * Points are all nz nx ny points of r, the periodic ghost border included, in Julia order i = iz + nz (ix + nx iy); the

@@ -78,6 +78,8 @@ def test_emergent_argument_checks_before_the_device():
     L = _lib.load()
     k = np.ascontiguousarray(K)
     assert L.vrt_regular_emergent_dev(None, _d(k), 2, DUMMY, DUMMY, 3, DUMMY, None) == E     # no handle
+    form, threads = ctypes.c_int(), ctypes.c_int()
+    assert L.vrt_regular_last_launch_form(None, ctypes.byref(form), ctypes.byref(threads)) == E
     z, xg, yg = Z, api.periodic_axis(X), api.periodic_axis(Y)
     S = np.zeros(6 * 7 * 6)
     out = np.zeros(5 * 4)

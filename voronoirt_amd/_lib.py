@@ -25,6 +25,10 @@ VRT_OK, VRT_EINVAL, VRT_EGRID, VRT_ENODEVICE, VRT_ENOMEM, VRT_EIO = 0, -1, -2, -
 ALPHA_SITE, ALPHA_SITE_LAM, ALPHA_ANGLE_SITE_LAM, ALPHA_ANGLE_NATIVE, ALPHA_SITE_LAM_NATIVE = 0, 1, 2, 3, 4
 METRIC_EUCLIDEAN, METRIC_PERIODIC_XY = 0, 1
 RASTER_NEAREST, RASTER_INV_DIST2 = 1, 2
+# vrt_regular_last_launch_form: kernel codes (VRT_REG_FORM_*) by name, and the two row flags of the solve forms
+REG_FORMS = ("solve<256>", "solve<1024>", "xy_march_lds<1>", "xy_march_lds<2>", "xy_march_lds<4>", "xy_march_lds<0>",
+             "xy_march_mem")
+REG_FORM_KERNEL_MASK, REG_FORM_YZ_ROW_MARCH, REG_FORM_XZ_ROW_MARCH = 0xff, 0x100, 0x200
 
 class LineCaseStruct(ctypes.Structure):
     """vrt_line_case of include/voronoirt.h"""
@@ -157,6 +161,7 @@ PROTOTYPES = {
     "vrt_regular_execute_dev": (ctypes.c_int, [vp, c_i64, p_dbl, p_int, vp, c_i64, vp, c_i64, c_i64, vp,
                                                ctypes.c_int, vp, vp]),
     "vrt_regular_last_solve_ms": (ctypes.c_int, [vp, p_dbl]),
+    "vrt_regular_last_launch_form": (ctypes.c_int, [vp, p_int, p_int]),
     "vrt_regular_execute_line": (ctypes.c_int, [vp, c_i64, p_dbl, p_int, p_dbl, c_i64, p_dbl, c_dbl, c_dbl, p_dbl, p_dbl,
                                                 p_dbl, p_dbl, p_dbl, p_dbl, p_dbl, ctypes.c_int, p_dbl]),
     "vrt_regular_lambda_create": (ctypes.c_int, [vp, c_i64, p_dbl, p_int, p_dbl, ctypes.POINTER(LineCaseStruct), ctypes.c_int,

@@ -729,6 +729,19 @@ class RegularSolver:
         check(_lib.load().vrt_regular_last_solve_ms(self._h, ctypes.byref(out)))
         return out.value
 
+    def last_launch_form(self):
+        """What the last batch of solves was launched as (`vrt_regular_last_launch_form`): (form, threads, rows) with
+        form one of `_lib.REG_FORMS`, threads the workgroup size, and rows -- the solve forms only, else None -- a dict
+        {"yz": ..., "xz": ...} of "row_march" / "strided": the row loop a plane of that kind takes in this launch."""
+        form, threads = ctypes.c_int(), ctypes.c_int()
+        check(_lib.load().vrt_regular_last_launch_form(self._h, ctypes.byref(form), ctypes.byref(threads)))
+        name = _lib.REG_FORMS[form.value & _lib.REG_FORM_KERNEL_MASK]
+        rows = None
+        if name.startswith("solve"):
+            rows = {"yz": "row_march" if form.value & _lib.REG_FORM_YZ_ROW_MARCH else "strided",
+                    "xz": "row_march" if form.value & _lib.REG_FORM_XZ_ROW_MARCH else "strided"}
+        return name, threads.value, rows
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             _lib.load().vrt_regular_destroy(self._h)

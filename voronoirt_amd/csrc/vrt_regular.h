@@ -18,6 +18,7 @@ struct vrt_regular {
     int64_t cap_k = 0;                     // of d_k and d_up, in solves
     vrt::Event ev[3];
     bool timed = false;
+    int last_form = -1, last_threads = 0;  // what regular_launch chose last (vrt_regular_last_launch_form); -1: nothing yet
     int force_threads = 0;                 // VRT_REG_THREADS, read once at creation (tests: forces the launch shape)
     int xy_split = 1;                      // VRT_REG_XY (creation): 0 = all-xy batches through k_regular_solve too;
                                            //   2 = split, upwind plane read from memory instead of LDS (tests)

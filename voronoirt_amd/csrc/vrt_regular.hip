@@ -1088,10 +1088,21 @@ static int regular_launch(vrt_regular *r, RegArgs &ra, int64_t n_solve, const do
             else VRT_XY_MARCH(0);
         }
 #undef VRT_XY_MARCH
-    } else if (threads <= 256)
-        hipLaunchKernelGGL(k_regular_solve<256>, dim3((unsigned)n_solve), dim3((unsigned)threads), lds, st, ra);
-    else
-        hipLaunchKernelGGL(k_regular_solve<1024>, dim3((unsigned)n_solve), dim3((unsigned)threads), lds, st, ra);
+        r->last_form = !in_lds ? VRT_REG_FORM_XY_MARCH_MEM
+                       : npt <= 1 && fits ? VRT_REG_FORM_XY_MARCH_LDS1
+                       : npt <= 2 && fits ? VRT_REG_FORM_XY_MARCH_LDS2
+                       : npt <= 4 && fits ? VRT_REG_FORM_XY_MARCH_LDS4 : VRT_REG_FORM_XY_MARCH_LDS0;
+        r->last_threads = mt;
+    } else {
+        if (threads <= 256)
+            hipLaunchKernelGGL(k_regular_solve<256>, dim3((unsigned)n_solve), dim3((unsigned)threads), lds, st, ra);
+        else
+            hipLaunchKernelGGL(k_regular_solve<1024>, dim3((unsigned)n_solve), dim3((unsigned)threads), lds, st, ra);
+        // the kernel's own tests: a yz plane marches rows of ny points, an xz plane rows of nx (row_march or the strided loop)
+        r->last_form = (threads <= 256 ? VRT_REG_FORM_SOLVE256 : VRT_REG_FORM_SOLVE1024) |
+                       (ny - 2 <= threads ? VRT_REG_FORM_YZ_ROW_MARCH : 0) | (nx - 2 <= threads ? VRT_REG_FORM_XZ_ROW_MARCH : 0);
+        r->last_threads = threads;
+    }
     VRT_HIP_TRY(hipEventRecord(r->ev[2], st));
     return VRT_OK;
 }
@@ -1232,6 +1243,16 @@ extern "C" int vrt_regular_last_solve_ms(const vrt_regular *r, double *ms)
         *ms = f;
         return VRT_OK;
     });
+}
+
+// what regular_launch chose for the last batch of solves (host bookkeeping only: no device call, no synchronisation)
+extern "C" int vrt_regular_last_launch_form(const vrt_regular *r, int *form, int *threads)
+{
+    if (!r || !form || !threads) return fail(VRT_EINVAL, "NULL argument");
+    if (r->last_form < 0) return fail(VRT_EINVAL, "no solve launched yet");
+    *form = r->last_form;
+    *threads = r->last_threads;
+    return VRT_OK;
 }
 
 // Host-pointer form: stages the arrays through the device around vrt_regular_execute_dev.
