@@ -54,6 +54,16 @@ def reduce_layers(sorted_layers):
     return reduced
 
 
+def _fdiv(a, b):
+    """Float64 `/` as Julia evaluates it: x / 0.0 is +-Inf and 0.0 / 0.0 is NaN where Python raises."""
+    try:
+        return a / b
+    except ZeroDivisionError:
+        if a != a or a == 0.0:
+            return math.nan
+        return math.copysign(math.inf, a) * math.copysign(1.0, b)
+
+
 def calc_delaunay_lines(positions, neighbours, n_sites, x_min, x_max, y_min, y_max):
     """positions[i] = [_, z, x, y] (1-based components) -- voronoi_utils.jl:186-245."""
     lines = {}
@@ -82,7 +92,7 @@ def calc_delaunay_lines(positions, neighbours, n_sites, x_min, x_max, y_min, y_m
                     p_n[3] = y_min + y_max - p_n[3]
                 p_d = [0.0, p_n[1] - position[1], p_n[2] - position[2], p_n[3] - position[3]]
                 nrm = math.sqrt((p_d[1] * p_d[1] + p_d[2] * p_d[2]) + p_d[3] * p_d[3])
-                lines[(j, i)] = [0.0, p_d[1] / nrm, p_d[2] / nrm, p_d[3] / nrm]
+                lines[(j, i)] = [0.0, _fdiv(p_d[1], nrm), _fdiv(p_d[2], nrm), _fdiv(p_d[3], nrm)]
     return lines
 
 

@@ -70,6 +70,9 @@ def test_grid_and_delaunay_lines_bit_exact(grids, name):
 @pytest.mark.parametrize("name", ["bcc", "voronoi"])
 @pytest.mark.parametrize("quad", ["ul7n12.dat", "ul9n20.dat", "n1.dat"])
 def test_upwind_table_bit_exact(grids, name, quad):
+    """Grids in general position (jittered BCC, random Voronoi sites) and tabulated quadratures: no comparison of the
+    search sees equal operands here.  Ties, exact zeros and -1, the collapse on D2 == 0, NaN lines and the periodic
+    test's equality are in tests/test_upwind_domain_host.py (inputs) and tests/test_upwind_domain.py (device)."""
     hs, so = grids[name]
     w, th, ph, nq = vrt.read_quadrature(quad)
     ks = vrt.quadrature_directions(th, ph)
