@@ -19,9 +19,9 @@ from test_resume_host import small_lambda_case
 pytestmark = pytest.mark.gpu
 
 QUAD = "ul7n12.dat"
-BLOCKS = {9: (5, 2), 10: (6, 2)}            # nλ -> (line wavelengths, wavelengths per continuum block)
+BLOCKS = {9: (5, 2), 10: (6, 2), 6: (2, 2)}           # nλ -> (line wavelengths, wavelengths per continuum block)
 FORMS = [("native", 9), ("native", 10), ("caller", 9), ("caller", 10), ("regular", 0), ("multi1", 9), ("multi1", 10),
-         ("multi2", 9), ("multi2caller", 9)]
+         ("multi2", 9), ("multi2caller", 9), ("multi7", 6)]
 NG_FORMS = [("native", 9), ("native", 10), ("caller", 9), ("regular", 0)]       # the multi-device session has no acceleration
 
 
@@ -124,7 +124,7 @@ class _World:
             create = lambda out: L.vrt_lambda_create(plan._h, ctypes.byref(lc), wd.ctypes.data_as(_lib.p_dbl), out)
             self.args = ("vrt_lambda", create, pos.shape[0], nlam)
         else:
-            self.devices = (0,) if form == "multi1" else (0, 0)
+            self.devices = (0,) * {"multi1": 1, "multi7": 7}.get(form, 2)
             dirs = [1 if t > 90 else -1 for t in th]
             self.weights = w
             self.mp = vrt.MultiDevicePlan(pos, nbr, bounds, vrt.quadrature_directions(th, ph), dirs=dirs, devices=self.devices)

@@ -1552,8 +1552,7 @@ static int line_opacity_impl(vrt_plan *p, int64_t nlam, const double *lambda, do
         vrt_grid *g = p->g;
         int rc = use_device(g->device);
         if (rc) return rc;
-        if (!p->patch_ok && (!p->tile_ok || p->tile_max_layer_size > steps_max_layer(false)))
-            return fail(VRT_EINVAL, "the native alpha layout needs a layer path (at most 4 visits per site and 255 levels per layer)");
+        if ((rc = line_path_ok(p, "the native alpha layout"))) return rc;
         std::lock_guard<std::mutex> lock(g->mu);
         std::vector<double> h(lambda, lambda + nlam);
         if ((rc = upload_small(g, h, (hipStream_t)stream))) return rc;

@@ -6,11 +6,12 @@
 //   diff = max |1 - S_old / S_new|  over the THICK entries only (ε > eps_thick; the reference: ε_λ .> 1e-4)
 //
 //   vrt_continuum_update_dev       the masked update alone, caller layout (k_continuum_update)
-//   vrt_continuum_*                the loop on a vrt_plan with library-owned device state: S, J, B_0, ε and α in sweep
-//                                  order (vrt_plan_execute_native_dev's plane sets, α as VRT_ALPHA_SITE_LAM_NATIVE; the
-//                                  update is k_continuum_update_native), or -- VRT_LAMBDA_NATIVE=0, a plan without a
-//                                  sweep-order form -- in the caller's layout through k_continuum_update; S, J and the
-//                                  scalar are the same bits either way
+//   vrt_continuum_*                the loop on a vrt_plan with library-owned device state: S and J in a SourceStore
+//                                  (vrt_source_store.h), B_0, ε and α beside them in its order -- sweep order
+//                                  (vrt_plan_execute_native_dev's plane sets, α as VRT_ALPHA_SITE_LAM_NATIVE; the update is
+//                                  k_continuum_update_native), or -- VRT_LAMBDA_NATIVE=0, a plan without a sweep-order
+//                                  form -- the caller's layout through k_continuum_update; S, J and the scalar are the
+//                                  same bits either way
 //   vrt_regular_continuum_*        the loop on a vrt_regular: the chunked solve of vrt_regular_lambda.hip with one α array
 //                                  per wavelength shared by all angles, J reduced in quadrature order, the masked update
 //                                  on the raster in the caller's layout
@@ -35,6 +36,7 @@
 
 #include "vrt_device.h"
 #include "vrt_regular.h"
+#include "vrt_source_store.h"
 
 namespace vrt {
 namespace {
@@ -355,14 +357,6 @@ int check_case(const vrt_continuum_case *cc, int64_t n)
     return VRT_OK;
 }
 
-int upload(DevBuf<double> &d, const double *h, size_t count, hipStream_t st)
-{
-    int rc = d.alloc(count);
-    if (rc) return rc;
-    VRT_HIP_TRY(hipMemcpyAsync(d, h, sizeof(double) * count, hipMemcpyHostToDevice, st));
-    return VRT_OK;
-}
-
 }  // namespace
 }  // namespace vrt
 
@@ -374,19 +368,20 @@ struct vrt_continuum {
     int64_t n = 0, nlam = 0;
     double eps_thick = 0;
     std::vector<double> weights;
-    bool native = false;
-    // sweep order (native): S and J per direction, B_0 and ε in the up order, α of both orders one behind the other
-    DevBuf<double> d_S_nat[2], d_J_nat[2], d_B_up, d_E_up, d_A_nat;
-    // the caller's layout (n, nlam)
-    DevBuf<double> d_S_new, d_S_old, d_J, d_B0, d_eps, d_alpha;
+    // S and J (rows, or sweep order: vrt_source_store.h); beside them, in the store's order, B_0 and ε (rows, or their
+    // up-order plane sets) and α as the sweeps take it (rows, or both orders one behind the other: alpha_mode)
+    SourceStore sj;
+    DevBuf<double> d_B0, d_eps, d_alpha;
+    int alpha_mode = VRT_ALPHA_SITE_LAM;
     DevBuf<double> d_I0;                // B_0 of the bottom layer in perm_up order, (n1, nlam)
     DevBuf<unsigned long long> d_scalars;
     int64_t iterations = 0;
     NgState ng;                         // vrt_continuum_set_acceleration (off: nothing allocated, nothing run)
-    // vrt_continuum_set_operator (0: nothing allocated, nothing run): Λ* in the caller's layout (n, nlam), and -- native --
-    // its up-order plane set
+    // vrt_continuum_set_operator (0: nothing allocated, nothing run): Λ* in the caller's layout (n, nlam), and in the
+    // store's order beside S (sweep order only: in rows d_diag itself is read)
     int op = 0;
     DevBuf<double> d_diag, d_L_up;
+    const double *diag() const { return !op ? nullptr : d_L_up ? d_L_up.p : d_diag.p; }
 };
 
 struct vrt_regular_continuum {
@@ -444,18 +439,6 @@ static int regular_diagonal_rows(const vrt_regular *r, int64_t n_angles, const d
     VRT_HIP_TRY(hipMemcpy2DAsync(d_diag, pitch, g_dense, row, row, (size_t)n, hipMemcpyDeviceToDevice, st));
     VRT_HIP_TRY(hipStreamSynchronize(st));
     return VRT_OK;
-}
-
-// the S buffer a session's acceleration works on: doubles allocated, and which of them are physical entries
-static size_t continuum_S_count(const vrt_continuum *s, NgRange *rg)
-{
-    const int64_t n = s->n, nlam = s->nlam;
-    if (s->native) {
-        if (rg) { rg->dense = (nlam / 2) * 2 * n; rg->tail = nlam & 1 ? n : 0; rg->tstride = 2; }
-        return (size_t)vrt_plan_native_plane_count(s->p, nlam);
-    }
-    if (rg) { rg->dense = (n * nlam) & ~(int64_t)1; rg->tail = (n * nlam) & 1; rg->tstride = 1; }
-    return (size_t)(n * nlam);
 }
 
 // J_λ (lambda_continuum.jl:1-24) of every (angle, wavelength) solve into dJ_pl, chunk after chunk
@@ -583,43 +566,19 @@ int vrt_continuum_create(vrt_plan *p, const vrt_continuum_case *cc, const double
         const int64_t nlam = cc->nlam;
         const size_t nS = (size_t)g->n * (size_t)nlam;
         hipStream_t st = g->stream;
-        s->native = p->tune.lambda_native != 0 && p->A > 0 && native_planes_ok(p) == VRT_OK && p->tune.path != 1 &&
-                    p->tune.path != 2;
+        const SourceStore::Form form = SourceStore::plan_keeps_planes(p) ? SourceStore::kPlanes : SourceStore::kRows;
 #define VRT_S(expr) do { if ((rc = (expr))) return rc; } while (0)
-        DevBuf<double> tmp;                                  // native: the caller-layout arrays exist only here
         VRT_S(upload(s->d_B0, cc->B0, nS, st));
         VRT_S(s->d_I0.alloc((size_t)g->up.n1 * (size_t)nlam));
         // I_0 = B_λ(T) of the bottom layer perm_up[1 : layers_up[2] - 1] (:45-47), fixed over the iterations
         VRT_S(launch_gather_rows(g->up.n1, nlam, nlam, g->up.d_order, s->d_B0, s->d_I0, st));
         VRT_S(s->d_scalars.alloc(kUpdateWords));
-        if (s->native) {
-            const size_t np = (size_t)vrt_plan_native_plane_count(p, nlam);
-            for (int d = 0; d < 2; d++) {
-                VRT_S(s->d_S_nat[d].alloc(np));
-                VRT_S(s->d_J_nat[d].alloc(np));
-                VRT_HIP_TRY(hipMemsetAsync(s->d_J_nat[d], 0, sizeof(double) * np, st));
-            }
-            VRT_S(s->d_B_up.alloc(np));
-            VRT_S(s->d_E_up.alloc(np));
-            VRT_S(s->d_A_nat.alloc(2 * np));
-            VRT_S(planes_to_native(p, nlam, nlam, s->d_B0, s->d_S_nat[0], s->d_S_nat[1], st));      // S_new = B_0, :136-137
-            VRT_S(planes_to_native(p, nlam, nlam, s->d_B0, s->d_B_up, nullptr, st));
-            VRT_S(upload(tmp, cc->eps, nS, st));
-            VRT_S(planes_to_native(p, nlam, nlam, tmp, s->d_E_up, nullptr, st));
-            VRT_HIP_TRY(hipStreamSynchronize(st));           // (tmp is uploaded into again)
-            VRT_HIP_TRY(hipMemcpyAsync(tmp, cc->alpha, sizeof(double) * nS, hipMemcpyHostToDevice, st));
-            VRT_S(planes_to_native(p, nlam, nlam, tmp, s->d_A_nat, s->d_A_nat + np, st));
-            VRT_HIP_TRY(hipStreamSynchronize(st));
-            s->d_B0 = DevBuf<double>();                      // (B_0 lives on in the up order)
-        } else {
-            VRT_S(upload(s->d_S_new, cc->B0, nS, st));       // S_new = B_0
-            VRT_S(upload(s->d_eps, cc->eps, nS, st));
-            VRT_S(upload(s->d_alpha, cc->alpha, nS, st));
-            VRT_S(s->d_S_old.alloc(nS));
-            VRT_S(s->d_J.alloc(nS));
-            VRT_HIP_TRY(hipMemsetAsync(s->d_S_old, 0, sizeof(double) * nS, st));                    // S_old = zero(S_new), :139
-            VRT_HIP_TRY(hipMemsetAsync(s->d_J, 0, sizeof(double) * nS, st));
-        }
+        VRT_S(s->sj.create(p, nlam, form, s->d_B0, st));     // S_new = B_0, S_old = zero(S_new), :136-139
+        VRT_S(s->sj.to_up_order(s->d_B0, st));
+        VRT_S(upload(s->d_eps, cc->eps, nS, st));
+        VRT_S(s->sj.to_up_order(s->d_eps, st));
+        VRT_S(upload(s->d_alpha, cc->alpha, nS, st));
+        VRT_S(s->sj.to_sweep_alpha(s->d_alpha, &s->alpha_mode, st));
 #undef VRT_S
         VRT_HIP_TRY(hipStreamSynchronize(st));               // the host arrays may go after return
         *out = s.release();
@@ -638,27 +597,22 @@ int vrt_continuum_iterate(vrt_continuum *s, double *max_rel_change)
         if (rc) return rc;
         hipStream_t st = g->stream;
         const int64_t n = s->n, nlam = s->nlam;
-        if (s->native) {
-            // J_λ (:27-56) from the sweep-order S into the sweep-order J; S_new and the criterion (:148, :188: the old S is
-            // read from the plane the new one is written to)
-            if ((rc = execute_locked(p, native_args(nlam, s->d_S_nat[0], s->d_S_nat[1], s->d_A_nat, VRT_ALPHA_SITE_LAM_NATIVE,
-                                                    s->d_I0, nullptr, s->weights.data(), s->d_J_nat[0], s->d_J_nat[1], st,
-                                                    false))))
-                return rc;
-            if ((rc = launch_continuum_update_native(g, nlam, s->d_J_nat[0], s->d_J_nat[1], s->d_B_up, s->d_E_up,
-                                                     s->op ? s->d_L_up.p : nullptr, s->eps_thick, s->d_S_nat[0],
-                                                     s->d_S_nat[1], s->d_scalars, st)))
+        SourceStore &sj = s->sj;
+        // J_λ (:27-56) from S, in the store's form
+        if ((rc = execute_locked(p, sj.exec_args(s->d_alpha, s->alpha_mode, s->d_I0, s->weights.data(), st)))) return rc;
+        // S_new and the criterion (:148, :188)
+        if (sj.form() == SourceStore::kPlanes) {
+            // the old S is read from the plane the new one is written to
+            if ((rc = launch_continuum_update_native(g, nlam, sj.J_plane(0), sj.J_plane(1), s->d_B0, s->d_eps, s->diag(),
+                                                     s->eps_thick, sj.S_plane(0), sj.S_plane(1), s->d_scalars, st)))
                 return rc;
         } else {
             // S_old = copy(S_new), :146: the current S is read where it is and the new one written to the other buffer; the
             // two change roles only once both launches are queued (a failure leaves the session's S what it was)
-            if ((rc = execute_locked(p, caller_args(nlam, nlam, s->d_S_new, s->d_alpha, VRT_ALPHA_SITE_LAM, s->d_I0, nullptr,
-                                                    s->weights.data(), s->d_J, nullptr, st, false))))
+            if ((rc = launch_continuum_update(n, nlam, nlam, sj.J_rows(), s->d_B0, s->d_eps, s->diag(), s->eps_thick, sj.S_new(),
+                                              sj.S_old(), s->d_scalars, st)))
                 return rc;
-            if ((rc = launch_continuum_update(n, nlam, nlam, s->d_J, s->d_B0, s->d_eps, s->op ? s->d_diag.p : nullptr,
-                                              s->eps_thick, s->d_S_new, s->d_S_old, s->d_scalars, st)))
-                return rc;
-            std::swap(s->d_S_old.p, s->d_S_new.p);
+            sj.swap_rows();
         }
         if ((rc = read_criterion(s->d_scalars, st, max_rel_change, nullptr))) return rc;
         if ((rc = patch_chain_check(p))) return rc;          // a chained sweep that gave up: THIS iteration's results are invalid
@@ -666,12 +620,9 @@ int vrt_continuum_iterate(vrt_continuum *s, double *max_rel_change)
         if (s->ng.order) {
             // history copy or Ng step on the S of the plain update (native: the up-order copy; an accepted x_acc becomes that
             // copy and the down-order copy is rewritten from it, value for value)
-            NgRange rg;
-            const size_t count = continuum_S_count(s, &rg);
-            DevBuf<double> &S = s->native ? s->d_S_nat[0] : s->d_S_new;
-            if ((rc = ng_after_iterate(s->ng, s->iterations, S, count, rg, st))) return rc;
-            if (s->ng.last_applied == 1 && s->native) {
-                if ((rc = launch_ng_mirror(g, nlam, s->d_S_nat[0], s->d_S_nat[1], st))) return rc;
+            if ((rc = ng_after_iterate(s->ng, s->iterations, sj.ng_S(), sj.ng_count(), sj.ng_range(), st))) return rc;
+            if (s->ng.last_applied == 1 && sj.two_orders()) {
+                if ((rc = sj.mirror_down(st))) return rc;
                 VRT_HIP_TRY(hipStreamSynchronize(st));
             }
         } else
@@ -688,27 +639,7 @@ int vrt_continuum_get(vrt_continuum *s, double *J, double *S)
         std::lock_guard<std::mutex> lock(p->mu);
         int rc = use_device(p->g->device);
         if (rc) return rc;
-        const size_t bytes = sizeof(double) * (size_t)s->n * (size_t)s->nlam;
-        hipStream_t st = p->g->stream;
-        if (s->native && (J || S)) {
-            DevBuf<double> tmp;                              // the caller's layout is formed here, on request
-            if ((rc = tmp.alloc((size_t)s->n * (size_t)s->nlam))) return rc;
-            if (J) {
-                if ((rc = J_from_native(p, s->nlam, s->nlam, s->d_J_nat[0], s->d_J_nat[1], tmp, st))) return rc;
-                VRT_HIP_TRY(hipMemcpyAsync(J, tmp, bytes, hipMemcpyDeviceToHost, st));
-                VRT_HIP_TRY(hipStreamSynchronize(st));
-            }
-            if (S) {
-                if ((rc = plane_from_native(p, 0, s->nlam, s->nlam, s->d_S_nat[0], tmp, st))) return rc;
-                VRT_HIP_TRY(hipMemcpyAsync(S, tmp, bytes, hipMemcpyDeviceToHost, st));
-                VRT_HIP_TRY(hipStreamSynchronize(st));
-            }
-        } else {
-            if (J) VRT_HIP_TRY(hipMemcpyAsync(J, s->d_J, bytes, hipMemcpyDeviceToHost, st));
-            if (S) VRT_HIP_TRY(hipMemcpyAsync(S, s->d_S_new, bytes, hipMemcpyDeviceToHost, st));
-            VRT_HIP_TRY(hipStreamSynchronize(st));
-        }
-        return VRT_OK;
+        return s->sj.download(J, S, s->nlam, 0, p->g->stream);
     });
 }
 
@@ -721,17 +652,11 @@ int vrt_continuum_set_source(vrt_continuum *s, const double *S)
         vrt_plan *p = s->p;
         std::lock_guard<std::mutex> lock(p->mu);
         if ((rc = use_device(p->g->device))) return rc;
-        const size_t nS = (size_t)s->n * (size_t)s->nlam;
         hipStream_t st = p->g->stream;
-        if (s->native) {
-            DevBuf<double> tmp;
-            if ((rc = upload(tmp, S, nS, st))) return rc;
-            if ((rc = planes_to_native(p, s->nlam, s->nlam, tmp, s->d_S_nat[0], s->d_S_nat[1], st))) return rc;
-            VRT_HIP_TRY(hipStreamSynchronize(st));
-        } else {
-            VRT_HIP_TRY(hipMemcpyAsync(s->d_S_new, S, sizeof(double) * nS, hipMemcpyHostToDevice, st));
-            VRT_HIP_TRY(hipStreamSynchronize(st));
-        }
+        SourceStore::Staged staged;                          // beside the session: it is untouched until the copies are complete
+        if ((rc = s->sj.stage(S, s->nlam, 0, staged, st))) return rc;
+        VRT_HIP_TRY(hipStreamSynchronize(st));
+        s->sj.adopt(staged);
         s->ng.have = 0;                                      // iterates of another S are no history of this one
         s->ng.last_applied = 0;
         return VRT_OK;
@@ -747,7 +672,7 @@ int vrt_continuum_set_acceleration(vrt_continuum *s, int order, int start, int p
         vrt_plan *p = s->p;
         std::lock_guard<std::mutex> lock(p->mu);
         if ((rc = use_device(p->g->device))) return rc;
-        return ng_configure(s->ng, order, start, period, continuum_S_count(s, nullptr));
+        return ng_configure(s->ng, order, start, period, s->sj.ng_count());
     });
 }
 
@@ -777,23 +702,14 @@ int vrt_continuum_set_operator(vrt_continuum *s, int op)
             const int64_t n = s->n, nlam = s->nlam;
             const size_t nS = (size_t)n * (size_t)nlam;
             DevBuf<double> diag, L_up, tmpA, tmpE;
-            const double *alpha = s->d_alpha, *eps = s->d_eps;
+            const double *alpha, *eps;                       // α and ε back in the caller's layout, value for value
             if ((rc = diag.alloc(nS))) return rc;
-            if (s->native) {                                 // α and ε back in the caller's layout, value for value
-                if ((rc = tmpA.alloc(nS)) || (rc = tmpE.alloc(nS))) return rc;
-                if ((rc = plane_from_native(p, 0, nlam, nlam, s->d_A_nat, tmpA, st))) return rc;
-                if ((rc = plane_from_native(p, 0, nlam, nlam, s->d_E_up, tmpE, st))) return rc;
-                alpha = tmpA; eps = tmpE;
-            }
+            if ((rc = s->sj.rows_of(s->d_alpha, tmpA, &alpha, st)) || (rc = s->sj.rows_of(s->d_eps, tmpE, &eps, st))) return rc;
             if ((rc = launch_lambda_diagonal(p, nlam, nlam, alpha, s->weights.data(), diag, st))) return rc;
             // min den = min (1 - (1 - ε) Λ*) must be > 0 (it is not only for ε = 0 with Λ* rounding to 1)
             if ((rc = check_min_den((int64_t)nS, eps, diag, s->d_scalars, st))) return rc;
-            if (s->native) {
-                const size_t np = (size_t)vrt_plan_native_plane_count(p, nlam);
-                if ((rc = L_up.alloc(np))) return rc;
-                if ((rc = planes_to_native(p, nlam, nlam, diag, L_up, nullptr, st))) return rc;
-                VRT_HIP_TRY(hipStreamSynchronize(st));
-            }
+            if ((rc = s->sj.up_order_of(diag, L_up, st))) return rc;
+            if (L_up) VRT_HIP_TRY(hipStreamSynchronize(st));
             s->d_diag = std::move(diag);
             s->d_L_up = std::move(L_up);
         }

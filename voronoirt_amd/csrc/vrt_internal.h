@@ -106,6 +106,15 @@ struct DevBuf {
     operator T *() const { return p; }
 };
 
+// `count` doubles of a host array into d (allocated here), enqueued on `st`
+inline int upload(DevBuf<double> &d, const double *h, size_t count, hipStream_t st)
+{
+    int rc = d.alloc(count);
+    if (rc) return rc;
+    VRT_HIP_TRY(hipMemcpyAsync(d, h, sizeof(double) * count, hipMemcpyHostToDevice, st));
+    return VRT_OK;
+}
+
 // Grow-only workspace: a buffer of fewer than `count` elements is freed and `count` allocated (cap = 0 on failure).
 template <typename T>
 struct DevWork {
@@ -684,6 +693,13 @@ int J_from_native(vrt_plan *p, int64_t nlam, int64_t ld, const double *dJ_up, co
 // one execute on a layer path (2 tiles, 3 steps, 4 patches) that choose_path (vrt_api.cpp) chose for `x`
 int execute_layers(vrt_plan *p, const ExecArgs &x, int path);
 int64_t steps_max_layer(bool f32);   // largest layer the layer-step level kernels hold
+// the per-angle native α of the line case exists on the layer paths only; `who`: the subject of the refusal
+inline int line_path_ok(const vrt_plan *p, const char *who)
+{
+    if (!p->patch_ok && (!p->tile_ok || p->tile_max_layer_size > steps_max_layer(false)))
+        return fail(VRT_EINVAL, std::string(who) + " needs a layer path (at most 4 visits per site and 255 levels per layer)");
+    return VRT_OK;
+}
 
 // ---- fused patch path (vrt_patch.hip) ----------------------------------------------------------------
 struct TileArgs;

@@ -4,7 +4,9 @@
 //   vrt_plan_execute_line  the body of J_λ_voronoi, line case (src/lambda_iteration.jl:72-111): per-site line
 //                          vectors + S in, J out; α_tot is made on the device and never exists on the host
 //   vrt_lambda_*           Λ_voronoi's loop (src/lambda_iteration.jl:205-300) with library-owned device state:
-//                          per iteration only the criterion's scalar comes back
+//                          per iteration only the criterion's scalar comes back.  S and J live in a SourceStore
+//                          (vrt_source_store.h: rows, sweep-order planes or float planes); the session sees the form
+//                          only where vrt_lambda_iterate picks the update and rate kernels
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -14,6 +16,7 @@
 #include <thread>
 
 #include "vrt_internal.h"
+#include "vrt_source_store.h"
 
 using namespace vrt;
 
@@ -120,14 +123,6 @@ int run_copy_jobs(vrt_plan *p, const std::vector<CopyJob> &jobs, bool download, 
     return VRT_OK;
 }
 
-int upload(DevBuf<double> &d, const double *h, size_t count, hipStream_t st)
-{
-    int rc = d.alloc(count);
-    if (rc) return rc;
-    VRT_HIP_TRY(hipMemcpyAsync(d, h, sizeof(double) * count, hipMemcpyHostToDevice, st));
-    return VRT_OK;
-}
-
 }  // namespace
 
 struct vrt_lambda {
@@ -143,27 +138,16 @@ struct vrt_lambda {
     DevBuf<double> d_velocity, d_doppler, d_gamma_static, d_gamma_unsold, d_alpha_cont, d_eps, d_temperature, d_atom, d_B0,
         d_lte, d_C;
     DevBuf<double> d_gamma, d_strength, d_pops, d_pops_new, d_R;
-    DevBuf<double> d_S_old, d_S_new, d_J, d_I0, d_native;
+    DevBuf<double> d_I0, d_native;
     DevBuf<unsigned long long> d_scalars;
     int iterations = 0;
-    // S and J in sweep order between the steps of an iteration (VRT_LAMBDA_NATIVE, default): the update kernel writes S where
-    // the sweep reads it, the sweep reduces J where the update and the rate integrals read it -- no layout change inside
-    // the loop; d_S_new / d_S_old / d_J (the caller's layout) then exist only while vrt_lambda_get fills them
-    bool native = false;
-    DevBuf<double> d_S_nat[2], d_J_nat[2], d_B_up;
-    // float storage (vrt_lambda_create_f32; always native): these replace d_S_nat, d_J_nat, d_B_up, d_I0, d_native and d_B0 --
+    // S and J, in rows or in sweep order (VRT_LAMBDA_NATIVE, default); B_0 stands in d_B0 in the store's order: rows, or its
+    // up-order plane set.  Float storage (vrt_lambda_create_f32): f_B0, f_I0 and f_native replace d_B0, d_I0 and d_native --
     // no double array of size nλ·n or nλ·n·angles exists in such a session
-    bool f32 = false;
-    DevBuf<float> f_S_nat[2], f_J_nat[2], f_B_up, f_I0, f_native;
+    SourceStore sj;
+    DevBuf<float> f_B0, f_I0, f_native;
     NgState ng;                         // vrt_lambda_set_acceleration (off: nothing allocated, nothing run)
 };
-
-// the S buffer a session's acceleration works on: doubles allocated, and which of them are physical entries
-static size_t lambda_S_count(const vrt_lambda *s, NgRange *rg)
-{
-    if (rg) *rg = ng_S_range(s->n, s->nlam, s->native);
-    return s->native ? (size_t)vrt_plan_native_plane_count(s->p, s->nlam) : (size_t)(s->n * s->nlam);
-}
 
 struct LambdaDelete { void operator()(vrt_lambda *s) const { vrt_lambda_destroy(s); } };
 
@@ -197,8 +181,7 @@ int vrt_plan_execute_line(vrt_plan *p, int64_t nlam, int64_t ld, const double *l
         vrt_grid *g = p->g;
         int rc = use_device(g->device);
         if (rc) return rc;
-        if (!p->patch_ok && (!p->tile_ok || p->tile_max_layer_size > steps_max_layer(false)))
-            return fail(VRT_EINVAL, "the line entry needs a layer path (at most 4 visits per site and 255 levels per layer)");
+        if ((rc = line_path_ok(p, "the line entry"))) return rc;
         if (p->A != (int)p->n_angles_user)
             return fail(VRT_EINVAL, "per-angle alpha needs every angle active (no θ = 90 direction)");
         const size_t n = (size_t)g->n, nl = (size_t)nlam, nS = n * nl;           // dense (n, nlam) on the device
@@ -312,8 +295,7 @@ static int lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *wei
         vrt_grid *g = p->g;
         int rc = use_device(g->device);
         if (rc) return rc;
-        if (!p->patch_ok && (!p->tile_ok || p->tile_max_layer_size > steps_max_layer(false)))
-            return fail(VRT_EINVAL, "the line session needs a layer path (at most 4 visits per site and 255 levels per layer)");
+        if ((rc = line_path_ok(p, "the line session"))) return rc;
         if (p->A != (int)p->n_angles_user)
             return fail(VRT_EINVAL, "per-angle alpha needs every angle active (no θ = 90 direction)");
         if (f32) {                                      // float planes exist on the patch path only: no fp64 fallback
@@ -323,7 +305,6 @@ static int lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *wei
         }
         std::unique_ptr<vrt_lambda, LambdaDelete> s(new vrt_lambda());
         s->p = p;
-        s->f32 = f32;
         s->device = g->device;
         s->n = g->n;
         s->nlam = nlam;
@@ -353,56 +334,25 @@ static int lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *wei
         VRT_S(upload(s->d_lte, lc->lte_populations, 3 * n, st));
         VRT_S(upload(s->d_C, lc->C, 9 * n, st));
         VRT_S(upload(s->d_pops, lc->lte_populations, 3 * n, st));        // populations = copy(LTE_pops), :232
-        s->native = f32 || (p->tune.lambda_native != 0 && native_planes_ok(p) == VRT_OK && p->tune.path != 1 && p->tune.path != 2);
+        const SourceStore::Form form = f32 ? SourceStore::kPlanesF32
+                                           : SourceStore::plan_keeps_planes(p) ? SourceStore::kPlanes : SourceStore::kRows;
+        VRT_S(s->sj.create(p, nlam, form, s->d_B0, st));                 // S_new = B_0, S_old = zero(S_new), :236-240
+        // I_0 = B_λ(λ_l, T) of the bottom layer (:99-101) and α_tot of every angle, in the sweep's storage type
         if (f32) {
-            // B_0 rounded to float once: S_new = B_0 in both orders, B in the up order, I_0 of the bottom layer; the double
-            // copy and the caller-layout float copy are staging only
-            const size_t np = (size_t)vrt_plan_native_plane_count(p, nlam);
-            DevBuf<float> B0f;
-            VRT_S(B0f.alloc(n * nl));
-            VRT_S(launch_round_to_f32(n * nl, s->d_B0, B0f, st));
-            for (int d = 0; d < 2; d++) {
-                VRT_S(s->f_S_nat[d].alloc(np));
-                VRT_S(s->f_J_nat[d].alloc(np));
-                if (hipMemsetAsync(s->f_J_nat[d], 0, sizeof(float) * np, st) != hipSuccess) return fail(VRT_ENODEVICE, "hipMemsetAsync failed");
-            }
-            VRT_S(s->f_B_up.alloc(np));
-            VRT_S(planes_to_native_f32(p, nlam, nlam, B0f, s->f_S_nat[0], s->f_S_nat[1], st));
-            VRT_S(planes_to_native_f32(p, nlam, nlam, B0f, s->f_B_up, nullptr, st));
             VRT_S(s->f_I0.alloc((size_t)g->up.n1 * nl));
             VRT_S(launch_gather_rows_f32(g->up.n1, nlam, nlam, g->up.d_order, s->d_B0, s->f_I0, st));
             VRT_S(s->f_native.alloc((size_t)vrt_plan_native_alpha_count(p, nlam)));
-            if (hipStreamSynchronize(st) != hipSuccess) return fail(VRT_ENODEVICE, "uploading the line case failed");
-            s->d_B0.reset();
-        } else if (s->native) {
-            const size_t np = (size_t)vrt_plan_native_plane_count(p, nlam);
-            for (int d = 0; d < 2; d++) {
-                VRT_S(s->d_S_nat[d].alloc(np));
-                VRT_S(s->d_J_nat[d].alloc(np));
-                if (hipMemsetAsync(s->d_J_nat[d], 0, sizeof(double) * np, st) != hipSuccess) return fail(VRT_ENODEVICE, "hipMemsetAsync failed");
-            }
-            VRT_S(s->d_B_up.alloc(np));
-            VRT_S(planes_to_native(p, nlam, nlam, s->d_B0, s->d_S_nat[0], s->d_S_nat[1], st));      // S_new = B_0, :236-239
-            VRT_S(planes_to_native(p, nlam, nlam, s->d_B0, s->d_B_up, nullptr, st));
         } else {
-        VRT_S(upload(s->d_S_new, lc->B0, n * nl, st));                   // S_new = B_0, :236-239
-        VRT_S(s->d_S_old.alloc(n * nl));
-        VRT_S(s->d_J.alloc(n * nl));
+            VRT_S(s->d_I0.alloc((size_t)g->up.n1 * nl));
+            VRT_S(launch_gather_rows(g->up.n1, nlam, nlam, g->up.d_order, s->d_B0, s->d_I0, st));
+            VRT_S(s->d_native.alloc((size_t)vrt_plan_native_alpha_count(p, nlam)));
         }
+        VRT_S(s->sj.to_up_order(s->d_B0, s->f_B0, st));
         VRT_S(s->d_gamma.alloc(n));
         VRT_S(s->d_strength.alloc(n));
         VRT_S(s->d_pops_new.alloc(3 * n));
         VRT_S(s->d_R.alloc(9 * n));
-        if (!f32) {
-        VRT_S(s->d_I0.alloc((size_t)g->up.n1 * nl));
-        VRT_S(s->d_native.alloc((size_t)vrt_plan_native_alpha_count(p, nlam)));
-        }
         VRT_S(s->d_scalars.alloc(2));
-        if (!s->native &&
-            (hipMemsetAsync(s->d_S_old, 0, sizeof(double) * n * nl, st) != hipSuccess ||      // S_old = zero(S_new), :240
-             hipMemsetAsync(s->d_J, 0, sizeof(double) * n * nl, st) != hipSuccess))
-            return fail(VRT_ENODEVICE, "hipMemsetAsync failed");
-        if (!f32) VRT_S(launch_gather_rows(g->up.n1, nlam, nlam, g->up.d_order, s->d_B0, s->d_I0, st));   // I_0 = B_λ(λ_l, T) of the bottom layer, :99-101
 #undef VRT_S
         if (hipStreamSynchronize(st) != hipSuccess)                         // the host arrays may go after return
             return fail(VRT_ENODEVICE, "uploading the line case failed");
@@ -421,7 +371,10 @@ int vrt_lambda_create_f32(vrt_plan *p, const vrt_line_case *lc, const double *we
     return lambda_create(p, lc, weights, out, true);
 }
 
-int vrt_lambda_storage(const vrt_lambda *s) { return !s ? fail(VRT_EINVAL, "NULL session") : s->f32 ? 4 : 8; }
+int vrt_lambda_storage(const vrt_lambda *s)
+{
+    return !s ? fail(VRT_EINVAL, "NULL session") : s->sj.form() == SourceStore::kPlanesF32 ? 4 : 8;
+}
 
 int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
 {
@@ -434,58 +387,47 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
         if (rc) return rc;
         hipStream_t st = g->stream;
         const int64_t n = s->n, nlam = s->nlam;
-        const size_t bytes = sizeof(double) * (size_t)n * (size_t)nlam;
-        if (!s->native)
-            VRT_HIP_TRY(hipMemcpyAsync(s->d_S_old, s->d_S_new, bytes, hipMemcpyDeviceToDevice, st));     // S_old = copy(S_new), :258
+        SourceStore &sj = s->sj;
+        const bool f32 = sj.form() == SourceStore::kPlanesF32;
+        if (sj.form() == SourceStore::kRows)                 // S_old = copy(S_new), :258
+            VRT_HIP_TRY(hipMemcpyAsync(sj.S_old(), sj.S_new(), sizeof(double) * (size_t)n * (size_t)nlam, hipMemcpyDeviceToDevice, st));
         // γ and the line strength of the current populations (:72-75, line.jl:219-225), α_tot of every angle (:89-96)
         if ((rc = launch_line_terms(n, s->d_gamma_static, s->d_gamma_unsold, s->d_pops, s->strength_const, s->Bij,
                                     s->Bji, s->d_gamma, s->d_strength, st)))
             return rc;
+        void *alpha = f32 ? (void *)s->f_native.get() : (void *)s->d_native.get();
         if ((rc = launch_line_opacity(p, nlam, s->d_small, s->lambda0, s->c0, s->d_velocity, s->d_doppler, s->d_gamma,
-                                      s->d_strength, s->d_alpha_cont, s->f32 ? (void *)s->f_native.get() : (void *)s->d_native.get(), st,
-                                      s->f32)))
+                                      s->d_strength, s->d_alpha_cont, alpha, st, f32)))
             return rc;
-        if (s->f32) {
-            // the same three steps on the float plane sets (the roundings: include/voronoirt.h)
-            if ((rc = execute_locked(p, native_args(nlam, s->f_S_nat[0], s->f_S_nat[1], s->f_native, VRT_ALPHA_ANGLE_NATIVE, s->f_I0,
-                                                    nullptr, s->weights.data(), s->f_J_nat[0], s->f_J_nat[1], st, true))))
-                return rc;
-            if ((rc = launch_lambda_update_native_f32(p, nlam, s->f_J_nat[0], s->f_J_nat[1], s->f_B_up, s->d_eps, s->f_S_nat[0],
-                                                      s->f_S_nat[1], s->d_scalars, st)))
-                return rc;
-            if ((rc = launch_rates_populations_f32(p, nlam, s->blocks, s->d_small, s->lambda0, s->c0, s->d_doppler, s->d_gamma,
-                                                   s->sigma_bb_const, s->d_temperature, s->d_lte, s->hc_over_kB, s->pref_ij,
-                                                   s->pref_ji, s->d_C, s->d_atom, s->d_R, s->d_pops_new, st, s->f_J_nat[0],
-                                                   s->f_J_nat[1])))
-                return rc;
-        } else if (s->native) {
-            // J_λ (:84-111) from the sweep-order S into the sweep-order J; S_new and the criterion (:261-263, :325-349: the old
-            // S is read from the plane the new one is written to); R and the populations (:269, :274) from the same J planes
-            if ((rc = execute_locked(p, native_args(nlam, s->d_S_nat[0], s->d_S_nat[1], s->d_native, VRT_ALPHA_ANGLE_NATIVE, s->d_I0,
-                                                    nullptr, s->weights.data(), s->d_J_nat[0], s->d_J_nat[1], st, false))))
-                return rc;
-            if ((rc = launch_lambda_update_native(g, nlam, s->d_J_nat[0], s->d_J_nat[1], s->d_B_up, s->d_eps, s->d_S_nat[0],
-                                                  s->d_S_nat[1], s->d_scalars, st)))
-                return rc;
-            if ((rc = launch_rates_populations(g, nlam, nlam, s->blocks, s->d_small, nullptr, s->lambda0, s->c0, s->d_doppler,
-                                               s->d_gamma, s->sigma_bb_const, s->d_temperature, s->d_lte, s->hc_over_kB,
-                                               s->pref_ij, s->pref_ji, s->d_C, s->d_atom, s->d_R, s->d_pops_new, st,
-                                               s->d_J_nat[0], s->d_J_nat[1])))
-                return rc;
-        } else {
-        // J_λ (:84-111)
-        if ((rc = execute_locked(p, caller_args(nlam, nlam, s->d_S_old, s->d_native, VRT_ALPHA_ANGLE_NATIVE, s->d_I0, nullptr,
-                                                s->weights.data(), s->d_J, nullptr, st, false))))
-            return rc;
-        // S_new = (1 - ε) J + ε B_0 and the criterion's scalar (:261-263, :325-349)
-        if ((rc = launch_lambda_update(n, nlam, nlam, s->d_J, s->d_B0, s->d_eps, s->d_S_old, s->d_S_new, s->d_scalars, st)))
-            return rc;
-        // R, populations (:269, :274)
-        if ((rc = launch_rates_populations(g, nlam, nlam, s->blocks, s->d_small, s->d_J, s->lambda0, s->c0, s->d_doppler,
-                                           s->d_gamma, s->sigma_bb_const, s->d_temperature, s->d_lte, s->hc_over_kB,
-                                           s->pref_ij, s->pref_ji, s->d_C, s->d_atom, s->d_R, s->d_pops_new, st)))
-            return rc;
+        // J_λ (:84-111) from S, in the store's form
+        const void *I0 = f32 ? (const void *)s->f_I0.get() : (const void *)s->d_I0.get();
+        if ((rc = execute_locked(p, sj.exec_args(alpha, VRT_ALPHA_ANGLE_NATIVE, I0, s->weights.data(), st)))) return rc;
+        // S_new = (1 - ε) J + ε B_0 and the criterion's scalar (:261-263, :325-349); in sweep order the old S is read from the
+        // plane the new one is written to
+        switch (sj.form()) {
+        case SourceStore::kPlanesF32:                        // (the roundings: include/voronoirt.h)
+            rc = launch_lambda_update_native_f32(p, nlam, sj.J_plane<float>(0), sj.J_plane<float>(1), s->f_B0, s->d_eps,
+                                                 sj.S_plane<float>(0), sj.S_plane<float>(1), s->d_scalars, st);
+            break;
+        case SourceStore::kPlanes:
+            rc = launch_lambda_update_native(g, nlam, sj.J_plane(0), sj.J_plane(1), s->d_B0, s->d_eps, sj.S_plane(0),
+                                             sj.S_plane(1), s->d_scalars, st);
+            break;
+        case SourceStore::kRows:
+            rc = launch_lambda_update(n, nlam, nlam, sj.J_rows(), s->d_B0, s->d_eps, sj.S_old(), sj.S_new(), s->d_scalars, st);
+            break;
         }
+        if (rc) return rc;
+        // R, populations (:269, :274) from the same J (rows, or its planes)
+        rc = f32 ? launch_rates_populations_f32(p, nlam, s->blocks, s->d_small, s->lambda0, s->c0, s->d_doppler, s->d_gamma,
+                                                s->sigma_bb_const, s->d_temperature, s->d_lte, s->hc_over_kB, s->pref_ij,
+                                                s->pref_ji, s->d_C, s->d_atom, s->d_R, s->d_pops_new, st, sj.J_plane<float>(0),
+                                                sj.J_plane<float>(1))
+                 : launch_rates_populations(g, nlam, nlam, s->blocks, s->d_small, sj.J_rows(), s->lambda0, s->c0, s->d_doppler,
+                                            s->d_gamma, s->sigma_bb_const, s->d_temperature, s->d_lte, s->hc_over_kB,
+                                            s->pref_ij, s->pref_ji, s->d_C, s->d_atom, s->d_R, s->d_pops_new, st,
+                                            sj.J_plane(0), sj.J_plane(1));
+        if (rc) return rc;
         std::swap(s->d_pops, s->d_pops_new);
         unsigned long long h[2] = {0, 0};
         VRT_HIP_TRY(hipMemcpyAsync(h, s->d_scalars, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -498,12 +440,9 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
         if (s->ng.order) {
             // history copy or Ng step on the S of the plain update (the up-order copy); an accepted x_acc becomes that copy
             // and the down-order copy is rewritten from it, value for value
-            NgRange rg;
-            const size_t count = lambda_S_count(s, &rg);
-            DevBuf<double> &S = s->native ? s->d_S_nat[0] : s->d_S_new;
-            if ((rc = ng_after_iterate(s->ng, s->iterations, S, count, rg, st))) return rc;
-            if (s->ng.last_applied == 1 && s->native) {
-                if ((rc = launch_ng_mirror(g, nlam, s->d_S_nat[0], s->d_S_nat[1], st))) return rc;
+            if ((rc = ng_after_iterate(s->ng, s->iterations, sj.ng_S(), sj.ng_count(), sj.ng_range(), st))) return rc;
+            if (s->ng.last_applied == 1 && sj.two_orders()) {
+                if ((rc = sj.mirror_down(st))) return rc;
                 VRT_HIP_TRY(hipStreamSynchronize(st));
             }
         } else
@@ -520,10 +459,8 @@ int vrt_lambda_set_acceleration(vrt_lambda *s, int order, int start, int period)
     return guarded([&] {
         vrt_plan *p = s->p;
         std::lock_guard<std::mutex> lock(p->mu);
-        if (s->f32)                                          // the Ng kernels and NgRange: the [pair][pos][2] double layout
-            return fail(VRT_EINVAL, "vrt_lambda_set_acceleration: not on a float-storage session (the Ng kernels work on double planes)");
-        if ((rc = use_device(p->g->device))) return rc;
-        return ng_configure(s->ng, order, start, period, lambda_S_count(s, nullptr));
+        if ((rc = s->sj.ng_check()) || (rc = use_device(p->g->device))) return rc;
+        return ng_configure(s->ng, order, start, period, s->sj.ng_count());
     });
 }
 
@@ -541,43 +478,8 @@ int vrt_lambda_get(vrt_lambda *s, double *J, double *S, double *populations, dou
         std::lock_guard<std::mutex> lock(p->mu);
         int rc = use_device(p->g->device);
         if (rc) return rc;
-        const size_t n = (size_t)s->n, nl = (size_t)s->nlam;
-        if (s->f32 && (J || S)) {
-            // the float values in the caller's layout, widened on the device (exact), one array at a time
-            DevBuf<float> tf;
-            DevBuf<double> tmp;
-            if ((rc = tf.alloc(n * nl)) || (rc = tmp.alloc(n * nl))) return rc;
-            hipStream_t st = p->g->stream;
-            for (int which = 0; which < 2 && !rc; which++) {
-                double *host = which == 0 ? J : S;
-                if (!host) continue;
-                rc = which == 0 ? J_from_native_f32(p, s->nlam, s->nlam, s->f_J_nat[0], s->f_J_nat[1], tf, st)
-                                : plane_from_native_f32(p, 0, s->nlam, s->nlam, s->f_S_nat[0], tf, st);
-                if (!rc) rc = launch_widen_f32(n * nl, tf, tmp, st);
-                if (!rc && hipMemcpyAsync(host, tmp, sizeof(double) * n * nl, hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ENODEVICE;
-                if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = VRT_ENODEVICE;
-            }
-            if (rc) return rc == VRT_ENODEVICE ? fail(rc, "HIP error in vrt_lambda_get") : rc;
-        } else if (s->native && (J || S)) {
-            // the caller's layout is formed here, on request: one scratch array, freed again
-            DevBuf<double> tmp;
-            if ((rc = tmp.alloc(n * nl))) return rc;
-            hipStream_t st = p->g->stream;
-            if (J) {
-                rc = J_from_native(p, s->nlam, s->nlam, s->d_J_nat[0], s->d_J_nat[1], tmp, st);
-                if (!rc && hipMemcpyAsync(J, tmp, sizeof(double) * n * nl, hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ENODEVICE;
-                if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = VRT_ENODEVICE;
-            }
-            if (!rc && S) {
-                rc = plane_from_native(p, 0, s->nlam, s->nlam, s->d_S_nat[0], tmp, st);
-                if (!rc && hipMemcpyAsync(S, tmp, sizeof(double) * n * nl, hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ENODEVICE;
-                if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = VRT_ENODEVICE;
-            }
-            if (rc) return rc == VRT_ENODEVICE ? fail(rc, "HIP error in vrt_lambda_get") : rc;
-        } else {
-            if (J) VRT_HIP_TRY(hipMemcpy(J, s->d_J, sizeof(double) * n * nl, hipMemcpyDeviceToHost));
-            if (S) VRT_HIP_TRY(hipMemcpy(S, s->d_S_new, sizeof(double) * n * nl, hipMemcpyDeviceToHost));
-        }
+        const size_t n = (size_t)s->n;
+        if ((rc = s->sj.download(J, S, s->nlam, 0, p->g->stream))) return rc;
         if (populations) VRT_HIP_TRY(hipMemcpy(populations, s->d_pops, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
         if (R) VRT_HIP_TRY(hipMemcpy(R, s->d_R, sizeof(double) * 9 * n, hipMemcpyDeviceToHost));
         if (gamma) VRT_HIP_TRY(hipMemcpy(gamma, s->d_gamma, sizeof(double) * n, hipMemcpyDeviceToHost));
@@ -594,34 +496,13 @@ int vrt_lambda_set_state(vrt_lambda *s, const double *S, const double *populatio
         std::lock_guard<std::mutex> lock(p->mu);
         if ((rc = use_device(p->g->device))) return rc;
         hipStream_t st = p->g->stream;
-        const size_t n = (size_t)s->n, nS = n * (size_t)s->nlam;
         // staged copies beside the session: it is untouched until every one of them is complete
-        DevBuf<double> tmp, S_up, S_down, pops;
-        DevBuf<float> Sf, Sf_up, Sf_down;
-        if (S && s->f32) {
-            // rounded to float, then both plane sets (the padding wavelength of an odd nlam zero as at create)
-            const size_t np = (size_t)vrt_plan_native_plane_count(p, s->nlam);
-            if ((rc = upload(tmp, S, nS, st)) || (rc = Sf.alloc(nS)) || (rc = Sf_up.alloc(np)) || (rc = Sf_down.alloc(np))) return rc;
-            if ((rc = launch_round_to_f32(nS, tmp, Sf, st))) return rc;
-            if ((rc = planes_to_native_f32(p, s->nlam, s->nlam, Sf, Sf_up, Sf_down, st))) return rc;
-        } else if (S && s->native) {
-            // both plane sets, the padding wavelength of an odd nlam zero as at create
-            const size_t np = (size_t)vrt_plan_native_plane_count(p, s->nlam);
-            if ((rc = upload(tmp, S, nS, st)) || (rc = S_up.alloc(np)) || (rc = S_down.alloc(np))) return rc;
-            if ((rc = planes_to_native(p, s->nlam, s->nlam, tmp, S_up, S_down, st))) return rc;
-        } else if (S) {
-            if ((rc = upload(S_up, S, nS, st))) return rc;
-        }
-        if (populations && (rc = upload(pops, populations, 3 * n, st))) return rc;
+        SourceStore::Staged staged;
+        DevBuf<double> pops;
+        if (S && (rc = s->sj.stage(S, s->nlam, 0, staged, st))) return rc;
+        if (populations && (rc = upload(pops, populations, 3 * (size_t)s->n, st))) return rc;
         VRT_HIP_TRY(hipStreamSynchronize(st));               // the host arrays may go after return
-        if (S && s->f32) {
-            std::swap(s->f_S_nat[0], Sf_up);
-            std::swap(s->f_S_nat[1], Sf_down);
-        } else if (S && s->native) {
-            std::swap(s->d_S_nat[0], S_up);
-            std::swap(s->d_S_nat[1], S_down);
-        } else if (S)
-            std::swap(s->d_S_new, S_up);
+        if (S) s->sj.adopt(staged);
         if (populations) std::swap(s->d_pops, pops);
         s->ng.have = 0;                                      // iterates of another state are no history of this one
         s->ng.last_applied = 0;

@@ -18,6 +18,7 @@
 #include <thread>
 
 #include "vrt_internal.h"
+#include "vrt_source_store.h"
 
 using namespace vrt;
 
@@ -433,18 +434,19 @@ int vrt_multi_execute_line(vrt_multi *mm, int64_t nlam, int64_t ld, const double
 // angle, the sweep, S_new with its share of the convergence maximum, and its share of the six λ-integrals of the
 // radiative rates (rates.jl:154-201).  The shares are summed by ONE all-reduce of 6 n doubles over xGMI (SURVEY 8e:
 // "only R and one scalar are reduced"); J never travels.  Every device then solves the statistical equilibrium of
-// every site itself (populations.jl:191-221), so the next iteration's opacity needs no further exchange.
+// every site itself (populations.jl:191-221), so the next iteration's opacity needs no further exchange.  A member's S and
+// J live in a SourceStore (vrt_source_store.h), in rows or in sweep order, all members alike.
 struct LambdaMember {
     int device = 0;
     int64_t l0 = 0, l1 = 0;
     DevBuf<double> d_small;             // lambda | planck2 | sigma_bf1 | sigma_bf2 of ALL wavelengths
     DevBuf<double> d_velocity, d_doppler, d_gamma_static, d_gamma_unsold, d_alpha_cont, d_eps, d_temperature, d_atom, d_lte, d_C;
-    DevBuf<double> d_B0, d_S_old, d_S_new, d_J, d_I0, d_native;   // this block's columns
+    DevBuf<double> d_B0, d_I0, d_native;   // this block's columns (B_0 in the store's order: rows, or its up-order plane set)
     DevBuf<double> d_gamma, d_strength, d_pops, d_R, d_shares;
     DevBuf<unsigned long long> d_scalars;
     Event ev;
-    // the block's S and J in sweep order between the steps (as the one-device session keeps them: vrt_lambda.cpp)
-    DevBuf<double> d_S_nat[2], d_J_nat[2], d_B_up;
+    SourceStore sj;                     // the block's S and J, as the one-device session keeps them (a member without
+                                        // wavelengths: never created, holds nothing)
     NgState ng;                         // this block's history and workspace (vrt_multi_lambda_set_acceleration; off: nothing)
     ~LambdaMember() { (void)hipSetDevice(device); }    // (its own copy: the vrt_multi may be gone already); then the members go
 };
@@ -458,20 +460,12 @@ struct vrt_multi_lambda {
     std::vector<double> weights;
     std::vector<LambdaMember> lm;
     int iterations = 0;
-    bool native = false;                // every member keeps its block in sweep order (VRT_LAMBDA_NATIVE, all plans fit)
     NgState ng;                         // the settings and the last report; the buffers are the members'
     bool ng_torn = false;               // an accepted step whose down-order copy could not be rewritten: S is inconsistent
 };
 
 namespace {
 
-int dupload(DevBuf<double> &d, const double *h, size_t count, hipStream_t st)
-{
-    int rc = d.alloc(count);
-    if (rc) return rc;
-    VRT_HIP_TRY(hipMemcpyAsync(d, h, sizeof(double) * count, hipMemcpyHostToDevice, st));
-    return VRT_OK;
-}
 // columns [l0, l1) of a host array (rows, nlam) into a dense device block (rows, l1 - l0)
 int dupload_cols(DevBuf<double> &d, const double *h, size_t rows, int64_t nlam, int64_t l0, int64_t l1, hipStream_t st)
 {
@@ -483,12 +477,7 @@ int dupload_cols(DevBuf<double> &d, const double *h, size_t rows, int64_t nlam, 
 }
 
 // ---- Ng acceleration of the session (vrt_multi_lambda_set_acceleration): the phases of vrt_internal.h, each over every
-// member that holds wavelengths.  A member's S is its up-order plane set (sweep-order session) or its d_S_new columns.
-DevBuf<double> &ng_member_S(vrt_multi_lambda *s, LambdaMember &l) { return s->native ? l.d_S_nat[0] : l.d_S_new; }
-size_t ng_member_count(const vrt_multi_lambda *s, const vrt_plan *p, int64_t nb)
-{
-    return s->native ? (size_t)vrt_plan_native_plane_count(p, nb) : (size_t)(s->n * nb);
-}
+// member that holds wavelengths, on the S of its store.
 
 // body(d, member, its share of the session) -> rc on every member with wavelengths, one host thread each, the member's
 // device current and its plan locked
@@ -522,7 +511,7 @@ int multi_ng_after_iterate(vrt_multi_lambda *s)
     if (due == kNgNothing) return VRT_OK;
     if (due != kNgStep)
         return ng_on_members(s, [&](int, Member &me, LambdaMember &l) {
-            int rc = ng_record(l.ng, due, ng_member_S(s, l), ng_member_count(s, me.plan_all.get(), l.l1 - l.l0), me.stream);
+            int rc = ng_record(l.ng, due, l.sj.ng_S(), l.sj.ng_count(), me.stream);
             if (!rc && hipStreamSynchronize(me.stream) != hipSuccess) rc = fail(VRT_ENODEVICE, "copying S into the history failed");
             return rc;
         });
@@ -532,7 +521,7 @@ int multi_ng_after_iterate(vrt_multi_lambda *s)
     if (!complete) return VRT_OK;               // switched on too late for this one, or the state was replaced: nothing due
     std::vector<double> part(5 * (size_t)W, 0.0);
     int rc = ng_on_members(s, [&](int d, Member &me, LambdaMember &l) {
-        return ng_sums(ng_S_range(s->n, l.l1 - l.l0, s->native), ng_member_S(s, l), l.ng.hist[0], l.ng.hist[1], l.ng.hist[2],
+        return ng_sums(l.sj.ng_range(), l.sj.ng_S(), l.ng.hist[0], l.ng.hist[1], l.ng.hist[2],
                        l.ng.d_ws, &part[5 * (size_t)d], me.stream);
     });
     if (rc) return rc;
@@ -544,23 +533,23 @@ int multi_ng_after_iterate(vrt_multi_lambda *s)
         if (l.l1 <= l.l0) continue;
         ng_add_sums(s->ng.last_sums, &part[5 * (size_t)d], pieces.empty());
         piece_of[(size_t)d] = (int)pieces.size();
-        pieces.push_back(NgPiece{&l.ng, &ng_member_S(s, l), false});
+        pieces.push_back(NgPiece{&l.ng, &l.sj.ng_S(), false});
     }
     s->ng.last_applied = -1;
     const bool valid = ng_coefficients(s->ng.last_sums, s->ng.last_coeffs);
     if (valid) {
         const double a = s->ng.last_coeffs[0], b = s->ng.last_coeffs[1];
         rc = ng_on_members(s, [&](int d, Member &me, LambdaMember &l) {
-            return ng_apply(ng_S_range(s->n, l.l1 - l.l0, s->native), a, b, ng_member_S(s, l), l.ng.hist[0], l.ng.hist[1], l.ng.hist[2],
+            return ng_apply(l.sj.ng_range(), a, b, l.sj.ng_S(), l.ng.hist[0], l.ng.hist[1], l.ng.hist[2],
                             l.ng.d_ws, &pieces[(size_t)piece_of[(size_t)d]].good, me.stream);
         });
         if (rc) return rc;
     }
     if (!ng_commit(pieces.data(), (int)pieces.size(), valid)) return VRT_OK;
-    if (s->native) {
+    if (s->lm[0].sj.two_orders()) {             // (every member with wavelengths keeps the form of the first)
         // the down-order copies from the new up-order ones, value for value
         rc = ng_on_members(s, [&](int, Member &me, LambdaMember &l) {
-            int r = launch_ng_mirror(me.grid.get(), l.l1 - l.l0, l.d_S_nat[0], l.d_S_nat[1], me.stream);
+            int r = l.sj.mirror_down(me.stream);
             if (!r && hipStreamSynchronize(me.stream) != hipSuccess) r = fail(VRT_ENODEVICE, "rewriting the down-order S failed");
             return r;
         });
@@ -597,8 +586,7 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
         const int W = (int)mm->m.size();
         for (const Member &me : mm->m) {
             const vrt_plan *p = me.plan_all.get();
-            if (!p->patch_ok && (!p->tile_ok || p->tile_max_layer_size > steps_max_layer(false)))
-                return fail(VRT_EINVAL, "the line session needs a layer path (at most 4 visits per site and 255 levels per layer)");
+            if (int rc = line_path_ok(p, "the line session")) return rc;
             if (p->A != (int)p->n_angles_user)
                 return fail(VRT_EINVAL, "per-angle alpha needs every angle active (no θ = 90 direction)");
         }
@@ -611,10 +599,10 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
         s->sigma_bb_const = lc->sigma_bb_const; s->hc_over_kB = lc->hc_over_kB; s->pref_ij = lc->pref_ij; s->pref_ji = lc->pref_ji;
         s->weights.assign(weights, weights + mm->n_angles);
         s->lm = std::vector<LambdaMember>((size_t)W);
-        s->native = true;
+        // every member keeps its block in sweep order, or none does (VRT_LAMBDA_NATIVE, all plans fit)
+        SourceStore::Form form = SourceStore::kPlanes;
         for (const Member &me : mm->m)
-            s->native = s->native && me.plan_all->tune.lambda_native != 0 && native_planes_ok(me.plan_all.get()) == VRT_OK &&
-                        me.plan_all->tune.path != 1 && me.plan_all->tune.path != 2;
+            if (!SourceStore::plan_keeps_planes(me.plan_all.get())) form = SourceStore::kRows;
         const size_t n = (size_t)mm->n, nl = (size_t)nlam;
         const size_t nb1 = (size_t)(lc->blocks[3] - lc->blocks[2]), nb2 = (size_t)(lc->blocks[5] - lc->blocks[4]);
         std::vector<double> small;
@@ -635,22 +623,20 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
             hipStream_t st = me.stream;
             vrt_grid *g = me.grid.get();
 #define VRT_S(expr) do { if (!rc) rc = (expr); } while (0)
-            VRT_S(dupload(l.d_small, small.data(), small.size(), st));
-            VRT_S(dupload(l.d_velocity, lc->velocity, 3 * n, st));
-            VRT_S(dupload(l.d_doppler, lc->doppler_width, n, st));
-            VRT_S(dupload(l.d_gamma_static, lc->gamma_static, n, st));
-            VRT_S(dupload(l.d_gamma_unsold, lc->gamma_unsold, n, st));
-            VRT_S(dupload(l.d_alpha_cont, lc->alpha_cont, n, st));
-            VRT_S(dupload(l.d_eps, lc->eps, n, st));
-            VRT_S(dupload(l.d_temperature, lc->temperature, n, st));
-            VRT_S(dupload(l.d_atom, lc->atom_density, n, st));
-            VRT_S(dupload(l.d_lte, lc->lte_populations, 3 * n, st));
-            VRT_S(dupload(l.d_C, lc->C, 9 * n, st));
-            VRT_S(dupload(l.d_pops, lc->lte_populations, 3 * n, st));               // populations = copy(LTE_pops), :232
+            VRT_S(upload(l.d_small, small.data(), small.size(), st));
+            VRT_S(upload(l.d_velocity, lc->velocity, 3 * n, st));
+            VRT_S(upload(l.d_doppler, lc->doppler_width, n, st));
+            VRT_S(upload(l.d_gamma_static, lc->gamma_static, n, st));
+            VRT_S(upload(l.d_gamma_unsold, lc->gamma_unsold, n, st));
+            VRT_S(upload(l.d_alpha_cont, lc->alpha_cont, n, st));
+            VRT_S(upload(l.d_eps, lc->eps, n, st));
+            VRT_S(upload(l.d_temperature, lc->temperature, n, st));
+            VRT_S(upload(l.d_atom, lc->atom_density, n, st));
+            VRT_S(upload(l.d_lte, lc->lte_populations, 3 * n, st));
+            VRT_S(upload(l.d_C, lc->C, 9 * n, st));
+            VRT_S(upload(l.d_pops, lc->lte_populations, 3 * n, st));               // populations = copy(LTE_pops), :232
             VRT_S(dupload_cols(l.d_B0, lc->B0, n, nlam, l.l0, l.l1, st));
-            VRT_S(dupload_cols(l.d_S_new, lc->B0, n, nlam, l.l0, l.l1, st));        // S_new = B_0, :236-239
-            VRT_S(l.d_S_old.alloc(n * nb));
-            VRT_S(l.d_J.alloc(n * nb));
+            if (nb) VRT_S(l.sj.create(me.plan_all.get(), (int64_t)nb, form, l.d_B0, st));      // S_new = B_0, S_old = zero(S_new), :236-240
             VRT_S(l.d_gamma.alloc(n));
             VRT_S(l.d_strength.alloc(n));
             VRT_S(l.d_R.alloc(9 * n));
@@ -659,20 +645,9 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
             VRT_S(l.d_native.alloc(nb ? (size_t)vrt_plan_native_alpha_count(me.plan_all.get(), (int64_t)nb) : 1));
             VRT_S(l.d_scalars.alloc(2));
             VRT_S(l.ev.create(hipEventDisableTiming));
-            if (!rc && nb && (hipMemsetAsync(l.d_S_old, 0, sizeof(double) * n * nb, st) != hipSuccess ||
-                              hipMemsetAsync(l.d_J, 0, sizeof(double) * n * nb, st) != hipSuccess))
-                rc = fail(VRT_ENODEVICE, "hipMemsetAsync failed");
-            if (!rc && nb) VRT_S(launch_gather_rows(g->up.n1, (int64_t)nb, (int64_t)nb, g->up.d_order, l.d_B0, l.d_I0, st));   // I_0 = B_λ of the bottom layer, :99-101
-            if (s->native && nb) {
-                const size_t np = (size_t)vrt_plan_native_plane_count(me.plan_all.get(), (int64_t)nb);
-                for (int dd = 0; dd < 2; dd++) {
-                    VRT_S(l.d_S_nat[dd].alloc(np));
-                    VRT_S(l.d_J_nat[dd].alloc(np));
-                    if (!rc && hipMemsetAsync(l.d_J_nat[dd], 0, sizeof(double) * np, st) != hipSuccess) rc = fail(VRT_ENODEVICE, "hipMemsetAsync failed");
-                }
-                VRT_S(l.d_B_up.alloc(np));
-                VRT_S(planes_to_native(me.plan_all.get(), (int64_t)nb, (int64_t)nb, l.d_B0, l.d_S_nat[0], l.d_S_nat[1], st));     // S_new = B_0
-                VRT_S(planes_to_native(me.plan_all.get(), (int64_t)nb, (int64_t)nb, l.d_B0, l.d_B_up, nullptr, st));
+            if (nb) {
+                VRT_S(launch_gather_rows(g->up.n1, (int64_t)nb, (int64_t)nb, g->up.d_order, l.d_B0, l.d_I0, st));   // I_0 = B_λ of the bottom layer, :99-101
+                VRT_S(l.sj.to_up_order(l.d_B0, st));
             }
 #undef VRT_S
             if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(VRT_ENODEVICE, "uploading the line case failed");
@@ -712,32 +687,29 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
             vrt_grid *g = me.grid.get();
             std::lock_guard<std::mutex> plock(p->mu);
             int rc = VRT_OK;
-            if (nb > 0 && s->native) {
-                // the block's S and J stay in sweep order: no layout change, no copy of S (the update reads the old S where it writes the new)
-                rc = launch_line_terms(n, l.d_gamma_static, l.d_gamma_unsold, l.d_pops, s->strength_const, s->Bij, s->Bji, l.d_gamma, l.d_strength, st);
-                if (!rc) rc = launch_line_opacity(p, nb, l.d_small + l.l0, s->lambda0, s->c0, l.d_velocity, l.d_doppler, l.d_gamma, l.d_strength, l.d_alpha_cont, l.d_native, st);
-                if (!rc) rc = execute_locked(p, native_args(nb, l.d_S_nat[0], l.d_S_nat[1], l.d_native, VRT_ALPHA_ANGLE_NATIVE, l.d_I0, nullptr,
-                                                            s->weights.data(), l.d_J_nat[0], l.d_J_nat[1], st, false));
-                if (!rc) rc = launch_lambda_update_native(g, nb, l.d_J_nat[0], l.d_J_nat[1], l.d_B_up, l.d_eps, l.d_S_nat[0], l.d_S_nat[1], l.d_scalars, st);
-            } else if (nb > 0) {
-                if (hipMemcpyAsync(l.d_S_old, l.d_S_new, sizeof(double) * (size_t)n * (size_t)nb, hipMemcpyDeviceToDevice, st) != hipSuccess)
-                    rc = fail(VRT_ENODEVICE, "hipMemcpyAsync");                                                  // S_old = copy(S_new), :258
-                // γ and the line strength of the current populations (:72-75, line.jl:219-225), α_tot of every angle (:89-96)
-                if (!rc) rc = launch_line_terms(n, l.d_gamma_static, l.d_gamma_unsold, l.d_pops, s->strength_const, s->Bij, s->Bji, l.d_gamma, l.d_strength, st);
-                if (!rc) rc = launch_line_opacity(p, nb, l.d_small + l.l0, s->lambda0, s->c0, l.d_velocity, l.d_doppler, l.d_gamma, l.d_strength, l.d_alpha_cont, l.d_native, st);
+            SourceStore &sj = l.sj;
+            if (nb == 0 && hipMemsetAsync(l.d_scalars, 0, 2 * sizeof(unsigned long long), st) != hipSuccess)
+                rc = fail(VRT_ENODEVICE, "hipMemsetAsync");
+            if (nb > 0 && sj.form() == SourceStore::kRows &&
+                hipMemcpyAsync(sj.S_old(), sj.S_new(), sizeof(double) * (size_t)n * (size_t)nb, hipMemcpyDeviceToDevice, st) != hipSuccess)
+                rc = fail(VRT_ENODEVICE, "hipMemcpyAsync");                                                      // S_old = copy(S_new), :258
+            // γ and the line strength of the current populations (:72-75, line.jl:219-225), α_tot of every angle (:89-96)
+            if (!rc) rc = launch_line_terms(n, l.d_gamma_static, l.d_gamma_unsold, l.d_pops, s->strength_const, s->Bij, s->Bji, l.d_gamma, l.d_strength, st);
+            if (!rc && nb > 0) {
+                rc = launch_line_opacity(p, nb, l.d_small + l.l0, s->lambda0, s->c0, l.d_velocity, l.d_doppler, l.d_gamma, l.d_strength, l.d_alpha_cont, l.d_native, st);
                 // J_λ of this block (:84-111)
-                if (!rc) rc = execute_locked(p, caller_args(nb, nb, l.d_S_old, l.d_native, VRT_ALPHA_ANGLE_NATIVE, l.d_I0, nullptr, s->weights.data(), l.d_J, nullptr, st, false));
-                // S_new = (1 - ε) J + ε B_0 and this block's share of the criterion (:261-263, :325-349)
-                if (!rc) rc = launch_lambda_update(n, nb, nb, l.d_J, l.d_B0, l.d_eps, l.d_S_old, l.d_S_new, l.d_scalars, st);
-            } else {
-                if (hipMemsetAsync(l.d_scalars, 0, 2 * sizeof(unsigned long long), st) != hipSuccess) rc = fail(VRT_ENODEVICE, "hipMemsetAsync");
-                if (!rc) rc = launch_line_terms(n, l.d_gamma_static, l.d_gamma_unsold, l.d_pops, s->strength_const, s->Bij, s->Bji, l.d_gamma, l.d_strength, st);
+                if (!rc) rc = execute_locked(p, sj.exec_args(l.d_native, VRT_ALPHA_ANGLE_NATIVE, l.d_I0, s->weights.data(), st));
+                // S_new = (1 - ε) J + ε B_0 and this block's share of the criterion (:261-263, :325-349); in sweep order the
+                // update reads the old S where it writes the new
+                if (!rc && sj.form() == SourceStore::kPlanes)
+                    rc = launch_lambda_update_native(g, nb, sj.J_plane(0), sj.J_plane(1), l.d_B0, l.d_eps, sj.S_plane(0), sj.S_plane(1), l.d_scalars, st);
+                else if (!rc)
+                    rc = launch_lambda_update(n, nb, nb, sj.J_rows(), l.d_B0, l.d_eps, sj.S_old(), sj.S_new(), l.d_scalars, st);
             }
-            // this block's share of the six rate integrals (rates.jl:154-201)
-            const bool natJ = s->native && nb > 0;
-            if (!rc) rc = launch_rates_partial(g, nlam, l.l0, l.l1, std::max<int64_t>(nb, 1), s->blocks, l.d_small, l.d_J, s->lambda0, s->c0, l.d_doppler,
+            // this block's share of the six rate integrals (rates.jl:154-201), from J in rows or in its planes
+            if (!rc) rc = launch_rates_partial(g, nlam, l.l0, l.l1, std::max<int64_t>(nb, 1), s->blocks, l.d_small, sj.J_rows(), s->lambda0, s->c0, l.d_doppler,
                                                l.d_gamma, s->sigma_bb_const, l.d_temperature, l.d_lte, s->hc_over_kB, s->pref_ij, s->pref_ji, l.d_shares, st,
-                                               natJ ? l.d_J_nat[0].p : nullptr, natJ ? l.d_J_nat[1].p : nullptr);
+                                               sj.J_plane(0), sj.J_plane(1));
             if (rc) { me.rc = rc; me.err = vrt_last_error(); }
         };
         if (!run_workers(W, work)) return fail(VRT_ENOMEM, "out of host memory in a device worker");
@@ -821,7 +793,7 @@ int vrt::multi_lambda_set_acceleration(vrt_multi_lambda *s, int order, int start
             if (l.l1 <= l.l0) continue;
             if (hipSetDevice(me.device) != hipSuccess) { rc = fail(VRT_ENODEVICE, "hipSetDevice failed"); break; }
             std::lock_guard<std::mutex> plock(me.plan_all->mu);
-            rc = ng_configure(l.ng, order, start, period, ng_member_count(s, me.plan_all.get(), l.l1 - l.l0));
+            rc = ng_configure(l.ng, order, start, period, l.sj.ng_count());
         }
         if (rc) {
             // one member could not: no member keeps a history, and the session goes on as a plain one
@@ -852,28 +824,13 @@ int vrt_multi_lambda_get(vrt_multi_lambda *s, double *J, double *S, double *popu
     return guarded([&] {
         vrt_multi *mm = s->mm;
         std::lock_guard<std::mutex> lock(mm->mu);
-        const size_t n = (size_t)s->n, nl = (size_t)s->nlam, w8 = sizeof(double);
+        const size_t n = (size_t)s->n, w8 = sizeof(double);
         for (size_t d = 0; d < mm->m.size(); d++) {
             const LambdaMember &l = s->lm[d];
-            const size_t nb = (size_t)(l.l1 - l.l0);
             VRT_HIP_TRY(hipSetDevice(mm->m[d].device));
-            if (s->native && nb && (J || S)) {
-                // the caller's layout is formed here, on request (d_J / d_S_old of the block serve as scratch)
-                vrt_plan *p = mm->m[d].plan_all.get();
-                hipStream_t st = mm->m[d].stream;
-                std::lock_guard<std::mutex> plock(p->mu);
-                if (J) {
-                    if (int rc = J_from_native(p, (int64_t)nb, (int64_t)nb, l.d_J_nat[0], l.d_J_nat[1], l.d_J, st)) return rc;
-                    VRT_HIP_TRY(hipMemcpy2DAsync(J + l.l0, w8 * nl, l.d_J, w8 * nb, w8 * nb, n, hipMemcpyDeviceToHost, st));
-                }
-                if (S) {
-                    if (int rc = plane_from_native(p, 0, (int64_t)nb, (int64_t)nb, l.d_S_nat[0], l.d_S_old, st)) return rc;
-                    VRT_HIP_TRY(hipMemcpy2DAsync(S + l.l0, w8 * nl, l.d_S_old, w8 * nb, w8 * nb, n, hipMemcpyDeviceToHost, st));
-                }
-                VRT_HIP_TRY(hipStreamSynchronize(st));
-            } else {
-            if (nb && J) VRT_HIP_TRY(hipMemcpy2D(J + l.l0, w8 * nl, l.d_J, w8 * nb, w8 * nb, n, hipMemcpyDeviceToHost));
-            if (nb && S) VRT_HIP_TRY(hipMemcpy2D(S + l.l0, w8 * nl, l.d_S_new, w8 * nb, w8 * nb, n, hipMemcpyDeviceToHost));
+            {   // this block's columns, in the caller's layout
+                std::lock_guard<std::mutex> plock(mm->m[d].plan_all->mu);
+                if (int rc = l.sj.download(J, S, s->nlam, l.l0, mm->m[d].stream)) return rc;
             }
             if (d == 0) {
                 if (populations) VRT_HIP_TRY(hipMemcpy(populations, l.d_pops, w8 * 3 * n, hipMemcpyDeviceToHost));
@@ -897,7 +854,8 @@ int vrt_multi_lambda_set_state(vrt_multi_lambda *s, const double *S, const doubl
         // staged copies beside the session, one set per device: it is untouched until every one of them is complete
         struct Staged {
             int device = 0;
-            DevBuf<double> tmp, S_up, S_down, pops;
+            SourceStore::Staged S;
+            DevBuf<double> pops;
             ~Staged() { (void)hipSetDevice(device); }        // then the members go, on their device
         };
         std::vector<Staged> staged((size_t)W);
@@ -914,16 +872,8 @@ int vrt_multi_lambda_set_state(vrt_multi_lambda *s, const double *S, const doubl
             vrt_plan *p = me.plan_all.get();
             std::lock_guard<std::mutex> plock(p->mu);
             int rc = VRT_OK;
-            if (S && nb > 0 && s->native) {
-                // this block's columns into both plane sets, the padding wavelength of an odd block zero as at create
-                const size_t np = (size_t)vrt_plan_native_plane_count(p, nb);
-                rc = dupload_cols(sg.tmp, S, n, s->nlam, l.l0, l.l1, st);
-                if (!rc) rc = sg.S_up.alloc(np);
-                if (!rc) rc = sg.S_down.alloc(np);
-                if (!rc) rc = planes_to_native(p, nb, nb, sg.tmp, sg.S_up, sg.S_down, st);
-            } else if (S && nb > 0)
-                rc = dupload_cols(sg.S_up, S, n, s->nlam, l.l0, l.l1, st);
-            if (!rc && populations) rc = dupload(sg.pops, populations, 3 * n, st);       // every device holds a full copy
+            if (S && nb > 0) rc = l.sj.stage(S, s->nlam, l.l0, sg.S, st);      // this block's columns
+            if (!rc && populations) rc = upload(sg.pops, populations, 3 * n, st);       // every device holds a full copy
             if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(VRT_ENODEVICE, "uploading the state failed");
             if (rc) { rcs[(size_t)d] = rc; errs[(size_t)d] = vrt_last_error(); }
         };
@@ -936,11 +886,7 @@ int vrt_multi_lambda_set_state(vrt_multi_lambda *s, const double *S, const doubl
         for (int d = 0; d < W; d++) {
             LambdaMember &l = s->lm[(size_t)d];
             Staged &sg = staged[(size_t)d];
-            if (S && l.l1 > l.l0 && s->native) {
-                std::swap(l.d_S_nat[0], sg.S_up);
-                std::swap(l.d_S_nat[1], sg.S_down);
-            } else if (S && l.l1 > l.l0)
-                std::swap(l.d_S_new, sg.S_up);
+            if (S && l.l1 > l.l0) l.sj.adopt(sg.S);
             if (populations) std::swap(l.d_pops, sg.pops);
             l.ng.have = 0;                                   // iterates of another state are no history of this one
         }
