@@ -11,6 +11,7 @@
 #include <thread>
 
 #include "vrt_internal.h"
+#include "vrt_line_case.h"
 
 namespace vrt {
 
@@ -1593,29 +1594,24 @@ static int rates_populations_impl(vrt_grid *g, int64_t nlam, int64_t ld, const d
         !d_temperature || !d_lte_populations || !d_C || !d_atom_density || !d_R || !d_populations)
         return fail(VRT_EINVAL, "NULL argument");
     if (nlam < 2 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 2 and ld >= nlam");
-    for (int b = 0; b < 3; b++)
-        if (blocks[2 * b] < 0 || blocks[2 * b + 1] > nlam || blocks[2 * b + 1] - blocks[2 * b] < 2)
-            return fail(VRT_EINVAL, "each wavelength block needs at least two wavelengths inside [0, nlam)");
+    if (int rc = check_blocks(blocks, nlam)) return rc;
     return guarded([&] {
         int rc = use_device(g->device);
         if (rc) return rc;
         if (p32 && (rc = native_planes_ok(p32, true))) return rc;
         std::lock_guard<std::mutex> lock(g->mu);
-        std::vector<double> h;
-        h.insert(h.end(), lambda, lambda + nlam);
-        h.insert(h.end(), planck2, planck2 + nlam);
-        h.insert(h.end(), sigma_bf1, sigma_bf1 + (blocks[3] - blocks[2]));
-        h.insert(h.end(), sigma_bf2, sigma_bf2 + (blocks[5] - blocks[4]));
-        if ((rc = upload_small(g, h, (hipStream_t)stream))) return rc;
-        if (p32)
-            rc = launch_rates_populations_f32(p32, nlam, blocks, g->d_small, lambda0, c0, d_doppler_width, d_gamma, sigma_bb_const,
-                                              d_temperature, d_lte_populations, hc_over_kB, pref_ij, pref_ji, d_C, d_atom_density,
-                                              d_R, d_populations, (hipStream_t)stream, fJ_up, fJ_down);
-        else
-        rc = launch_rates_populations(g, nlam, ld, blocks, g->d_small, dJ, lambda0, c0, d_doppler_width,
-                                      d_gamma, sigma_bb_const, d_temperature, d_lte_populations, hc_over_kB,
-                                      pref_ij, pref_ji, d_C, d_atom_density, d_R, d_populations,
-                                      (hipStream_t)stream, dJ_up, dJ_down);
+        if ((rc = upload_small(g, pack_small(nlam, blocks, lambda, planck2, sigma_bf1, sigma_bf2), (hipStream_t)stream))) return rc;
+        RatesIn in;
+        in.n = g->n; in.nlam = nlam;
+        for (int q = 0; q < 6; q++) in.k.blocks[q] = blocks[q];
+        in.k.lambda0 = lambda0; in.k.c0 = c0; in.k.sigma_bb_const = sigma_bb_const; in.k.hc_over_kB = hc_over_kB;
+        in.k.pref_ij = pref_ij; in.k.pref_ji = pref_ji;
+        in.small = small_view(g->d_small, nlam, blocks);
+        in.doppler = d_doppler_width; in.gamma = d_gamma; in.temperature = d_temperature; in.lte = d_lte_populations;
+        in.C = d_C; in.atom_density = d_atom_density;
+        const RatesJ J = p32 ? RatesJ::from_planes_f32(p32, fJ_up, fJ_down)
+                         : dJ_up || dJ_down ? RatesJ::from_planes(g, dJ_up, dJ_down) : RatesJ::from_rows(dJ, ld);
+        rc = launch_rates_populations(in, J, d_R, d_populations, (hipStream_t)stream);
         return rc ? rc : small_done(g, (hipStream_t)stream);
     });
 }

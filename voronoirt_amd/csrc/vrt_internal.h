@@ -637,33 +637,7 @@ int launch_line_opacity(vrt_plan *p, int64_t nlam, const double *d_lambda, doubl
                         bool f32_out = false);
 int launch_line_terms(int64_t n, const double *d_gamma_static, const double *d_gamma_unsold, const double *d_pops,
                       double strength_const, double Bij, double Bji, double *d_gamma, double *d_strength, hipStream_t st);
-int launch_rates_populations(vrt_grid *g, int64_t nlam, int64_t ld, const int64_t blocks[6],
-                             const double *d_small, const double *dJ, double lambda0, double c0,
-                             const double *d_doppler, const double *d_gamma, double sigma_bb_const,
-                             const double *d_temperature, const double *d_lte, double hc_over_kB,
-                             double pref_ij, double pref_ji, const double *d_C, const double *d_atom_density,
-                             double *d_R, double *d_populations, hipStream_t st,
-                             const double *dJ_up = nullptr, const double *dJ_down = nullptr);   // sweep-order J instead of dJ
-// the same with J in the plan's FLOAT sweep-order plane sets: J = (float)(J_up + J_down), widened
-int launch_rates_populations_f32(vrt_plan *p, int64_t nlam, const int64_t blocks[6], const double *d_small, double lambda0,
-                                 double c0, const double *d_doppler, const double *d_gamma, double sigma_bb_const,
-                                 const double *d_temperature, const double *d_lte, double hc_over_kB, double pref_ij,
-                                 double pref_ji, const double *d_C, const double *d_atom_density, double *d_R,
-                                 double *d_populations, hipStream_t st, const float *dJ_up, const float *dJ_down);
-// the same for n points in their own order, without a grid (the regular-grid Λ-iteration)
-int launch_rates_populations(int64_t n, int64_t nlam, int64_t ld, const int64_t blocks[6], const double *d_small,
-                             const double *dJ, double lambda0, double c0, const double *d_doppler, const double *d_gamma,
-                             double sigma_bb_const, const double *d_temperature, const double *d_lte, double hc_over_kB,
-                             double pref_ij, double pref_ji, const double *d_C, const double *d_atom_density, double *d_R,
-                             double *d_populations, hipStream_t st);
-
-int launch_rates_partial(vrt_grid *g, int64_t nlam, int64_t l0, int64_t l1, int64_t ld, const int64_t blocks[6],
-                         const double *d_small, const double *dJ, double lambda0, double c0, const double *d_doppler,
-                         const double *d_gamma, double sigma_bb_const, const double *d_temperature, const double *d_lte,
-                         double hc_over_kB, double pref_ij, double pref_ji, double *d_shares, hipStream_t st,
-                         const double *dJ_up = nullptr, const double *dJ_down = nullptr);   // this device's columns as sweep-order planes
-int launch_populations_from_shares(vrt_grid *g, const double *d_shares, const double *d_C, const double *d_atom_density,
-                                   double *d_R, double *d_populations, hipStream_t st);
+// (the rate launches and their named arguments: vrt_line_case.h)
 
 // ---- entry-point internals shared with vrt_lambda.cpp (vrt_api.cpp) ---------------------------------
 // one execute (caller holds p->mu): checks the arguments, chooses the path, runs it

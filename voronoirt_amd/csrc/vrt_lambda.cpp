@@ -16,6 +16,7 @@
 #include <thread>
 
 #include "vrt_internal.h"
+#include "vrt_line_case.h"
 #include "vrt_source_store.h"
 
 using namespace vrt;
@@ -129,15 +130,10 @@ struct vrt_lambda {
     vrt_plan *p = nullptr;              // borrowed: the caller keeps the plan alive for as long as the session
     int device = 0;                     // of the plan's grid (kept here: destroying the session must not look into a plan that may be gone)
     int64_t n = 0, nlam = 0;
-    int64_t blocks[6] = {0, 0, 0, 0, 0, 0};
-    double lambda0 = 0, c0 = 0, strength_const = 0, Bij = 0, Bji = 0, sigma_bb_const = 0, hc_over_kB = 0, pref_ij = 0,
-           pref_ji = 0;
     std::vector<double> weights;
     // device state
-    DevBuf<double> d_small;             // lambda | planck2 | sigma_bf1 | sigma_bf2
-    DevBuf<double> d_velocity, d_doppler, d_gamma_static, d_gamma_unsold, d_alpha_cont, d_eps, d_temperature, d_atom, d_B0,
-        d_lte, d_C;
-    DevBuf<double> d_gamma, d_strength, d_pops, d_pops_new, d_R;
+    LineCaseDev line;                   // the uploaded case, γ, the line strength and R (vrt_line_case.h)
+    DevBuf<double> d_B0, d_pops, d_pops_new;
     DevBuf<double> d_I0, d_native;
     DevBuf<unsigned long long> d_scalars;
     int iterations = 0;
@@ -280,16 +276,8 @@ static int lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *wei
     if (!out) return fail(VRT_EINVAL, "out is NULL");
     *out = nullptr;
     if (!p || !lc || !weights) return fail(VRT_EINVAL, "NULL argument");
+    if (int rc = check_line_case(lc)) return rc;
     const int64_t nlam = lc->nlam;
-    if (nlam < 2) return fail(VRT_EINVAL, "nlam must be >= 2");
-    if (!lc->lambda || !lc->velocity || !lc->doppler_width || !lc->gamma_static || !lc->gamma_unsold || !lc->alpha_cont ||
-        !lc->eps || !lc->temperature || !lc->atom_density || !lc->B0 || !lc->lte_populations || !lc->C || !lc->planck2 ||
-        !lc->sigma_bf1 || !lc->sigma_bf2)
-        return fail(VRT_EINVAL, "NULL array in the line case");
-    for (int b = 0; b < 3; b++)
-        if (lc->blocks[2 * b] < 0 || lc->blocks[2 * b + 1] > nlam || lc->blocks[2 * b + 1] - lc->blocks[2 * b] < 2)
-            return fail(VRT_EINVAL, "each wavelength block needs at least two wavelengths inside [0, nlam)");
-    if (!(lc->lambda0 > 0) || !(lc->c0 > 0)) return fail(VRT_EINVAL, "lambda0 and c0 must be positive");
     return guarded([&] {
         std::lock_guard<std::mutex> lock(p->mu);
         vrt_grid *g = p->g;
@@ -308,31 +296,12 @@ static int lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *wei
         s->device = g->device;
         s->n = g->n;
         s->nlam = nlam;
-        for (int q = 0; q < 6; q++) s->blocks[q] = lc->blocks[q];
-        s->lambda0 = lc->lambda0; s->c0 = lc->c0; s->strength_const = lc->strength_const; s->Bij = lc->Bij; s->Bji = lc->Bji;
-        s->sigma_bb_const = lc->sigma_bb_const; s->hc_over_kB = lc->hc_over_kB; s->pref_ij = lc->pref_ij; s->pref_ji = lc->pref_ji;
         s->weights.assign(weights, weights + p->n_angles_user);
         const size_t n = (size_t)g->n, nl = (size_t)nlam;
         hipStream_t st = g->stream;
-        const size_t nb1 = (size_t)(lc->blocks[3] - lc->blocks[2]), nb2 = (size_t)(lc->blocks[5] - lc->blocks[4]);
-        std::vector<double> small;
-        small.insert(small.end(), lc->lambda, lc->lambda + nl);
-        small.insert(small.end(), lc->planck2, lc->planck2 + nl);
-        small.insert(small.end(), lc->sigma_bf1, lc->sigma_bf1 + nb1);
-        small.insert(small.end(), lc->sigma_bf2, lc->sigma_bf2 + nb2);
 #define VRT_S(expr) do { if ((rc = (expr))) return rc; } while (0)
-        VRT_S(upload(s->d_small, small.data(), small.size(), st));
-        VRT_S(upload(s->d_velocity, lc->velocity, 3 * n, st));
-        VRT_S(upload(s->d_doppler, lc->doppler_width, n, st));
-        VRT_S(upload(s->d_gamma_static, lc->gamma_static, n, st));
-        VRT_S(upload(s->d_gamma_unsold, lc->gamma_unsold, n, st));
-        VRT_S(upload(s->d_alpha_cont, lc->alpha_cont, n, st));
-        VRT_S(upload(s->d_eps, lc->eps, n, st));
-        VRT_S(upload(s->d_temperature, lc->temperature, n, st));
-        VRT_S(upload(s->d_atom, lc->atom_density, n, st));
+        VRT_S(s->line.create(lc, g->n, st));
         VRT_S(upload(s->d_B0, lc->B0, n * nl, st));
-        VRT_S(upload(s->d_lte, lc->lte_populations, 3 * n, st));
-        VRT_S(upload(s->d_C, lc->C, 9 * n, st));
         VRT_S(upload(s->d_pops, lc->lte_populations, 3 * n, st));        // populations = copy(LTE_pops), :232
         const SourceStore::Form form = f32 ? SourceStore::kPlanesF32
                                            : SourceStore::plan_keeps_planes(p) ? SourceStore::kPlanes : SourceStore::kRows;
@@ -348,10 +317,7 @@ static int lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *wei
             VRT_S(s->d_native.alloc((size_t)vrt_plan_native_alpha_count(p, nlam)));
         }
         VRT_S(s->sj.to_up_order(s->d_B0, s->f_B0, st));
-        VRT_S(s->d_gamma.alloc(n));
-        VRT_S(s->d_strength.alloc(n));
         VRT_S(s->d_pops_new.alloc(3 * n));
-        VRT_S(s->d_R.alloc(9 * n));
         VRT_S(s->d_scalars.alloc(2));
 #undef VRT_S
         if (hipStreamSynchronize(st) != hipSuccess)                         // the host arrays may go after return
@@ -392,42 +358,34 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
         if (sj.form() == SourceStore::kRows)                 // S_old = copy(S_new), :258
             VRT_HIP_TRY(hipMemcpyAsync(sj.S_old(), sj.S_new(), sizeof(double) * (size_t)n * (size_t)nlam, hipMemcpyDeviceToDevice, st));
         // γ and the line strength of the current populations (:72-75, line.jl:219-225), α_tot of every angle (:89-96)
-        if ((rc = launch_line_terms(n, s->d_gamma_static, s->d_gamma_unsold, s->d_pops, s->strength_const, s->Bij,
-                                    s->Bji, s->d_gamma, s->d_strength, st)))
-            return rc;
+        if ((rc = s->line.terms(s->d_pops, st))) return rc;
         void *alpha = f32 ? (void *)s->f_native.get() : (void *)s->d_native.get();
-        if ((rc = launch_line_opacity(p, nlam, s->d_small, s->lambda0, s->c0, s->d_velocity, s->d_doppler, s->d_gamma,
-                                      s->d_strength, s->d_alpha_cont, alpha, st, f32)))
-            return rc;
+        if ((rc = s->line.opacity(p, nlam, 0, alpha, st, f32))) return rc;
         // J_λ (:84-111) from S, in the store's form
         const void *I0 = f32 ? (const void *)s->f_I0.get() : (const void *)s->d_I0.get();
         if ((rc = execute_locked(p, sj.exec_args(alpha, VRT_ALPHA_ANGLE_NATIVE, I0, s->weights.data(), st)))) return rc;
         // S_new = (1 - ε) J + ε B_0 and the criterion's scalar (:261-263, :325-349); in sweep order the old S is read from the
         // plane the new one is written to
+        RatesJ J;
         switch (sj.form()) {
         case SourceStore::kPlanesF32:                        // (the roundings: include/voronoirt.h)
-            rc = launch_lambda_update_native_f32(p, nlam, sj.J_plane<float>(0), sj.J_plane<float>(1), s->f_B0, s->d_eps,
+            rc = launch_lambda_update_native_f32(p, nlam, sj.J_plane<float>(0), sj.J_plane<float>(1), s->f_B0, s->line.d_eps,
                                                  sj.S_plane<float>(0), sj.S_plane<float>(1), s->d_scalars, st);
+            J = RatesJ::from_planes_f32(p, sj.J_plane<float>(0), sj.J_plane<float>(1));
             break;
         case SourceStore::kPlanes:
-            rc = launch_lambda_update_native(g, nlam, sj.J_plane(0), sj.J_plane(1), s->d_B0, s->d_eps, sj.S_plane(0),
+            rc = launch_lambda_update_native(g, nlam, sj.J_plane(0), sj.J_plane(1), s->d_B0, s->line.d_eps, sj.S_plane(0),
                                              sj.S_plane(1), s->d_scalars, st);
+            J = RatesJ::from_planes(g, sj.J_plane(0), sj.J_plane(1));
             break;
         case SourceStore::kRows:
-            rc = launch_lambda_update(n, nlam, nlam, sj.J_rows(), s->d_B0, s->d_eps, sj.S_old(), sj.S_new(), s->d_scalars, st);
+            rc = launch_lambda_update(n, nlam, nlam, sj.J_rows(), s->d_B0, s->line.d_eps, sj.S_old(), sj.S_new(), s->d_scalars, st);
+            J = RatesJ::from_rows(sj.J_rows(), nlam);
             break;
         }
         if (rc) return rc;
-        // R, populations (:269, :274) from the same J (rows, or its planes)
-        rc = f32 ? launch_rates_populations_f32(p, nlam, s->blocks, s->d_small, s->lambda0, s->c0, s->d_doppler, s->d_gamma,
-                                                s->sigma_bb_const, s->d_temperature, s->d_lte, s->hc_over_kB, s->pref_ij,
-                                                s->pref_ji, s->d_C, s->d_atom, s->d_R, s->d_pops_new, st, sj.J_plane<float>(0),
-                                                sj.J_plane<float>(1))
-                 : launch_rates_populations(g, nlam, nlam, s->blocks, s->d_small, sj.J_rows(), s->lambda0, s->c0, s->d_doppler,
-                                            s->d_gamma, s->sigma_bb_const, s->d_temperature, s->d_lte, s->hc_over_kB,
-                                            s->pref_ij, s->pref_ji, s->d_C, s->d_atom, s->d_R, s->d_pops_new, st,
-                                            sj.J_plane(0), sj.J_plane(1));
-        if (rc) return rc;
+        // R, populations (:269, :274) from the same J
+        if ((rc = launch_rates_populations(s->line.rates_in(), J, s->line.d_R, s->d_pops_new, st))) return rc;
         std::swap(s->d_pops, s->d_pops_new);
         unsigned long long h[2] = {0, 0};
         VRT_HIP_TRY(hipMemcpyAsync(h, s->d_scalars, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -481,8 +439,8 @@ int vrt_lambda_get(vrt_lambda *s, double *J, double *S, double *populations, dou
         const size_t n = (size_t)s->n;
         if ((rc = s->sj.download(J, S, s->nlam, 0, p->g->stream))) return rc;
         if (populations) VRT_HIP_TRY(hipMemcpy(populations, s->d_pops, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
-        if (R) VRT_HIP_TRY(hipMemcpy(R, s->d_R, sizeof(double) * 9 * n, hipMemcpyDeviceToHost));
-        if (gamma) VRT_HIP_TRY(hipMemcpy(gamma, s->d_gamma, sizeof(double) * n, hipMemcpyDeviceToHost));
+        if (R) VRT_HIP_TRY(hipMemcpy(R, s->line.d_R, sizeof(double) * 9 * n, hipMemcpyDeviceToHost));
+        if (gamma) VRT_HIP_TRY(hipMemcpy(gamma, s->line.d_gamma, sizeof(double) * n, hipMemcpyDeviceToHost));
         return VRT_OK;
     });
 }

@@ -18,6 +18,7 @@
 #include <thread>
 
 #include "vrt_internal.h"
+#include "vrt_line_case.h"
 #include "vrt_source_store.h"
 
 using namespace vrt;
@@ -439,10 +440,9 @@ int vrt_multi_execute_line(vrt_multi *mm, int64_t nlam, int64_t ld, const double
 struct LambdaMember {
     int device = 0;
     int64_t l0 = 0, l1 = 0;
-    DevBuf<double> d_small;             // lambda | planck2 | sigma_bf1 | sigma_bf2 of ALL wavelengths
-    DevBuf<double> d_velocity, d_doppler, d_gamma_static, d_gamma_unsold, d_alpha_cont, d_eps, d_temperature, d_atom, d_lte, d_C;
+    LineCaseDev line;                   // the whole case (every site, ALL wavelengths), γ, the line strength and R (vrt_line_case.h)
     DevBuf<double> d_B0, d_I0, d_native;   // this block's columns (B_0 in the store's order: rows, or its up-order plane set)
-    DevBuf<double> d_gamma, d_strength, d_pops, d_R, d_shares;
+    DevBuf<double> d_pops, d_shares;
     DevBuf<unsigned long long> d_scalars;
     Event ev;
     SourceStore sj;                     // the block's S and J, as the one-device session keeps them (a member without
@@ -454,9 +454,6 @@ struct LambdaMember {
 struct vrt_multi_lambda {
     vrt_multi *mm = nullptr;            // borrowed
     int64_t n = 0, nlam = 0;
-    int64_t blocks[6] = {0, 0, 0, 0, 0, 0};
-    double lambda0 = 0, c0 = 0, strength_const = 0, Bij = 0, Bji = 0, sigma_bb_const = 0, hc_over_kB = 0, pref_ij = 0,
-           pref_ji = 0;
     std::vector<double> weights;
     std::vector<LambdaMember> lm;
     int iterations = 0;
@@ -571,16 +568,8 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
     if (!out) return fail(VRT_EINVAL, "out is NULL");
     *out = nullptr;
     if (!mm || !lc || !weights) return fail(VRT_EINVAL, "NULL argument");
+    if (int rc = check_line_case(lc)) return rc;
     const int64_t nlam = lc->nlam;
-    if (nlam < 2) return fail(VRT_EINVAL, "nlam must be >= 2");
-    if (!lc->lambda || !lc->velocity || !lc->doppler_width || !lc->gamma_static || !lc->gamma_unsold || !lc->alpha_cont ||
-        !lc->eps || !lc->temperature || !lc->atom_density || !lc->B0 || !lc->lte_populations || !lc->C || !lc->planck2 ||
-        !lc->sigma_bf1 || !lc->sigma_bf2)
-        return fail(VRT_EINVAL, "NULL array in the line case");
-    for (int b = 0; b < 3; b++)
-        if (lc->blocks[2 * b] < 0 || lc->blocks[2 * b + 1] > nlam || lc->blocks[2 * b + 1] - lc->blocks[2 * b] < 2)
-            return fail(VRT_EINVAL, "each wavelength block needs at least two wavelengths inside [0, nlam)");
-    if (!(lc->lambda0 > 0) || !(lc->c0 > 0)) return fail(VRT_EINVAL, "lambda0 and c0 must be positive");
     return guarded([&] {
         std::lock_guard<std::mutex> lock(mm->mu);
         const int W = (int)mm->m.size();
@@ -594,22 +583,13 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
         s->mm = mm;
         s->n = mm->n;
         s->nlam = nlam;
-        for (int q = 0; q < 6; q++) s->blocks[q] = lc->blocks[q];
-        s->lambda0 = lc->lambda0; s->c0 = lc->c0; s->strength_const = lc->strength_const; s->Bij = lc->Bij; s->Bji = lc->Bji;
-        s->sigma_bb_const = lc->sigma_bb_const; s->hc_over_kB = lc->hc_over_kB; s->pref_ij = lc->pref_ij; s->pref_ji = lc->pref_ji;
         s->weights.assign(weights, weights + mm->n_angles);
         s->lm = std::vector<LambdaMember>((size_t)W);
         // every member keeps its block in sweep order, or none does (VRT_LAMBDA_NATIVE, all plans fit)
         SourceStore::Form form = SourceStore::kPlanes;
         for (const Member &me : mm->m)
             if (!SourceStore::plan_keeps_planes(me.plan_all.get())) form = SourceStore::kRows;
-        const size_t n = (size_t)mm->n, nl = (size_t)nlam;
-        const size_t nb1 = (size_t)(lc->blocks[3] - lc->blocks[2]), nb2 = (size_t)(lc->blocks[5] - lc->blocks[4]);
-        std::vector<double> small;
-        small.insert(small.end(), lc->lambda, lc->lambda + nl);
-        small.insert(small.end(), lc->planck2, lc->planck2 + nl);
-        small.insert(small.end(), lc->sigma_bf1, lc->sigma_bf1 + nb1);
-        small.insert(small.end(), lc->sigma_bf2, lc->sigma_bf2 + nb2);
+        const size_t n = (size_t)mm->n;
         std::vector<int> rcs((size_t)W, VRT_OK);
         std::vector<std::string> errs((size_t)W);
         auto work = [&](int d) {
@@ -623,23 +603,10 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
             hipStream_t st = me.stream;
             vrt_grid *g = me.grid.get();
 #define VRT_S(expr) do { if (!rc) rc = (expr); } while (0)
-            VRT_S(upload(l.d_small, small.data(), small.size(), st));
-            VRT_S(upload(l.d_velocity, lc->velocity, 3 * n, st));
-            VRT_S(upload(l.d_doppler, lc->doppler_width, n, st));
-            VRT_S(upload(l.d_gamma_static, lc->gamma_static, n, st));
-            VRT_S(upload(l.d_gamma_unsold, lc->gamma_unsold, n, st));
-            VRT_S(upload(l.d_alpha_cont, lc->alpha_cont, n, st));
-            VRT_S(upload(l.d_eps, lc->eps, n, st));
-            VRT_S(upload(l.d_temperature, lc->temperature, n, st));
-            VRT_S(upload(l.d_atom, lc->atom_density, n, st));
-            VRT_S(upload(l.d_lte, lc->lte_populations, 3 * n, st));
-            VRT_S(upload(l.d_C, lc->C, 9 * n, st));
+            VRT_S(l.line.create(lc, mm->n, st));
             VRT_S(upload(l.d_pops, lc->lte_populations, 3 * n, st));               // populations = copy(LTE_pops), :232
             VRT_S(dupload_cols(l.d_B0, lc->B0, n, nlam, l.l0, l.l1, st));
             if (nb) VRT_S(l.sj.create(me.plan_all.get(), (int64_t)nb, form, l.d_B0, st));      // S_new = B_0, S_old = zero(S_new), :236-240
-            VRT_S(l.d_gamma.alloc(n));
-            VRT_S(l.d_strength.alloc(n));
-            VRT_S(l.d_R.alloc(9 * n));
             VRT_S(l.d_shares.alloc(6 * n));
             VRT_S(l.d_I0.alloc((size_t)g->up.n1 * nb));
             VRT_S(l.d_native.alloc(nb ? (size_t)vrt_plan_native_alpha_count(me.plan_all.get(), (int64_t)nb) : 1));
@@ -674,7 +641,7 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
             return fail(VRT_ENODEVICE, "an accepted Ng step failed while rewriting the down-order S: the session's S is inconsistent, "
                                        "replace it with vrt_multi_lambda_set_state or destroy the session");
         const int W = (int)mm->m.size();
-        const int64_t n = s->n, nlam = s->nlam;
+        const int64_t n = s->n;
         // ---- every device: its wavelengths' share of the iteration, enqueued on its stream ----------------------------
         auto work = [&](int d) {
             Member &me = mm->m[(size_t)d];
@@ -694,22 +661,23 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
                 hipMemcpyAsync(sj.S_old(), sj.S_new(), sizeof(double) * (size_t)n * (size_t)nb, hipMemcpyDeviceToDevice, st) != hipSuccess)
                 rc = fail(VRT_ENODEVICE, "hipMemcpyAsync");                                                      // S_old = copy(S_new), :258
             // γ and the line strength of the current populations (:72-75, line.jl:219-225), α_tot of every angle (:89-96)
-            if (!rc) rc = launch_line_terms(n, l.d_gamma_static, l.d_gamma_unsold, l.d_pops, s->strength_const, s->Bij, s->Bji, l.d_gamma, l.d_strength, st);
+            if (!rc) rc = l.line.terms(l.d_pops, st);
             if (!rc && nb > 0) {
-                rc = launch_line_opacity(p, nb, l.d_small + l.l0, s->lambda0, s->c0, l.d_velocity, l.d_doppler, l.d_gamma, l.d_strength, l.d_alpha_cont, l.d_native, st);
+                rc = l.line.opacity(p, nb, l.l0, l.d_native, st);
                 // J_λ of this block (:84-111)
                 if (!rc) rc = execute_locked(p, sj.exec_args(l.d_native, VRT_ALPHA_ANGLE_NATIVE, l.d_I0, s->weights.data(), st));
                 // S_new = (1 - ε) J + ε B_0 and this block's share of the criterion (:261-263, :325-349); in sweep order the
                 // update reads the old S where it writes the new
                 if (!rc && sj.form() == SourceStore::kPlanes)
-                    rc = launch_lambda_update_native(g, nb, sj.J_plane(0), sj.J_plane(1), l.d_B0, l.d_eps, sj.S_plane(0), sj.S_plane(1), l.d_scalars, st);
+                    rc = launch_lambda_update_native(g, nb, sj.J_plane(0), sj.J_plane(1), l.d_B0, l.line.d_eps, sj.S_plane(0), sj.S_plane(1), l.d_scalars, st);
                 else if (!rc)
-                    rc = launch_lambda_update(n, nb, nb, sj.J_rows(), l.d_B0, l.d_eps, sj.S_old(), sj.S_new(), l.d_scalars, st);
+                    rc = launch_lambda_update(n, nb, nb, sj.J_rows(), l.d_B0, l.line.d_eps, sj.S_old(), sj.S_new(), l.d_scalars, st);
             }
             // this block's share of the six rate integrals (rates.jl:154-201), from J in rows or in its planes
-            if (!rc) rc = launch_rates_partial(g, nlam, l.l0, l.l1, std::max<int64_t>(nb, 1), s->blocks, l.d_small, sj.J_rows(), s->lambda0, s->c0, l.d_doppler,
-                                               l.d_gamma, s->sigma_bb_const, l.d_temperature, l.d_lte, s->hc_over_kB, s->pref_ij, s->pref_ji, l.d_shares, st,
-                                               sj.J_plane(0), sj.J_plane(1));
+            // (a member without wavelengths: an empty range of rows)
+            const RatesJ J = sj.form() == SourceStore::kPlanes ? RatesJ::from_planes(g, sj.J_plane(0), sj.J_plane(1))
+                                                               : RatesJ::from_rows(sj.J_rows(), std::max<int64_t>(nb, 1));
+            if (!rc) rc = launch_rates_partial(l.line.rates_in(), J, l.l0, l.l1, l.d_shares, st);
             if (rc) { me.rc = rc; me.err = vrt_last_error(); }
         };
         if (!run_workers(W, work)) return fail(VRT_ENOMEM, "out of host memory in a device worker");
@@ -751,7 +719,7 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
             LambdaMember &l = s->lm[(size_t)d];
             VRT_HIP_TRY(hipSetDevice(me.device));
             (void)hipGetLastError();
-            if (int rc = launch_populations_from_shares(me.grid.get(), l.d_shares, l.d_C, l.d_atom, l.d_R, l.d_pops, me.stream)) return rc;
+            if (int rc = launch_populations_from_shares(n, l.d_shares, l.line.d_C, l.line.d_atom, l.line.d_R, l.d_pops, me.stream)) return rc;
             VRT_HIP_TRY(hipMemcpyAsync(h.data() + 2 * d, l.d_scalars, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, me.stream));
         }
         double worst = 0.0;
@@ -834,8 +802,8 @@ int vrt_multi_lambda_get(vrt_multi_lambda *s, double *J, double *S, double *popu
             }
             if (d == 0) {
                 if (populations) VRT_HIP_TRY(hipMemcpy(populations, l.d_pops, w8 * 3 * n, hipMemcpyDeviceToHost));
-                if (R) VRT_HIP_TRY(hipMemcpy(R, l.d_R, w8 * 9 * n, hipMemcpyDeviceToHost));
-                if (gamma) VRT_HIP_TRY(hipMemcpy(gamma, l.d_gamma, w8 * n, hipMemcpyDeviceToHost));
+                if (R) VRT_HIP_TRY(hipMemcpy(R, l.line.d_R, w8 * 9 * n, hipMemcpyDeviceToHost));
+                if (gamma) VRT_HIP_TRY(hipMemcpy(gamma, l.line.d_gamma, w8 * n, hipMemcpyDeviceToHost));
             }
         }
         return VRT_OK;

@@ -26,6 +26,7 @@
 
 #include "vrt_device.h"
 #include "vrt_internal.h"
+#include "vrt_line_case.h"
 #include "vrt_voigt.h"
 
 namespace vrt {
@@ -418,110 +419,69 @@ k_populations_from_shares(RatesArgs ra, const double *__restrict__ shares)
     populations_from_rates(ra, i, R);
 }
 
-static void fill_rates_args(RatesArgs &ra, int64_t n, int64_t nlam, int64_t ld, const int64_t blocks[6], const double *d_small,
-                            const double *dJ, double lambda0, double c0, const double *d_doppler, const double *d_gamma,
-                            double sigma_bb_const, const double *d_temperature, const double *d_lte, double hc_over_kB,
-                            double pref_ij, double pref_ji, const double *d_C, const double *d_atom_density, double *d_R,
-                            double *d_populations)
+// the kernels' arguments from the launches' named ones (vrt_line_case.h); R and the populations are the launch's to add
+static RatesArgs rates_args(const RatesIn &in, const RatesJ &J)
 {
-    ra.n = n; ra.nlam = nlam; ra.ld = ld;
-    for (int q = 0; q < 6; q++) ra.blocks[q] = blocks[q];
-    ra.lambda = d_small;
-    ra.planck2 = d_small + nlam;
-    ra.sigma_bf1 = d_small + 2 * nlam;
-    ra.sigma_bf2 = ra.sigma_bf1 + (blocks[3] - blocks[2]);
-    ra.J = dJ;
-    ra.lambda0 = lambda0; ra.c0 = c0; ra.sigma_bb_const = sigma_bb_const; ra.hc_over_kB = hc_over_kB;
-    ra.pref_ij = pref_ij; ra.pref_ji = pref_ji;
-    ra.doppler = d_doppler; ra.gamma = d_gamma; ra.temperature = d_temperature; ra.lte = d_lte;
-    ra.C = d_C; ra.atom_density = d_atom_density; ra.R = d_R; ra.populations = d_populations;
+    RatesArgs ra{};
+    ra.n = in.n; ra.nlam = in.nlam; ra.ld = J.ld;
+    for (int q = 0; q < 6; q++) ra.blocks[q] = in.k.blocks[q];
+    ra.lambda = in.small.lambda; ra.planck2 = in.small.planck2;
+    ra.sigma_bf1 = in.small.sigma_bf1; ra.sigma_bf2 = in.small.sigma_bf2;
+    ra.lambda0 = in.k.lambda0; ra.c0 = in.k.c0; ra.sigma_bb_const = in.k.sigma_bb_const; ra.hc_over_kB = in.k.hc_over_kB;
+    ra.pref_ij = in.k.pref_ij; ra.pref_ji = in.k.pref_ji;
+    ra.doppler = in.doppler; ra.gamma = in.gamma; ra.temperature = in.temperature; ra.lte = in.lte;
+    ra.C = in.C; ra.atom_density = in.atom_density;
+    ra.J = J.rows;
+    ra.J_up = J.up; ra.J_down = J.down;
+    ra.Jf_up = J.up_f; ra.Jf_down = J.down_f;
+    if (J.plan) {
+        ra.lgB = native_lg(J.plan, true); ra.npair = (int)((in.nlam + 1) / 2);
+    }
+    if (const vrt_grid *g = J.plan ? J.plan->g : J.grid) {          // the orders the plane sets are stored in
+        ra.store_up = g->up.d_store; ra.rank_down = g->down.d_srank;
+    }
+    return ra;
 }
 
-// this device's share of the rate integrals: wavelengths [l0, l1) of the FULL wavelength arrays in d_small
-// (λ | planck2 | σ_bf1 | σ_bf2 for all nlam wavelengths); dJ holds those columns only (ld values per site)
-int launch_rates_partial(vrt_grid *g, int64_t nlam, int64_t l0, int64_t l1, int64_t ld, const int64_t blocks[6],
-                         const double *d_small, const double *dJ, double lambda0, double c0, const double *d_doppler,
-                         const double *d_gamma, double sigma_bb_const, const double *d_temperature, const double *d_lte,
-                         double hc_over_kB, double pref_ij, double pref_ji, double *d_shares, hipStream_t st,
-                         const double *dJ_up, const double *dJ_down)
+// this device's share of the rate integrals: wavelengths [l0, l1) of the FULL wavelength arrays of `in`; J holds those
+// columns only (J.ld values per site, or sweep-order planes of l1 - l0 wavelengths)
+int launch_rates_partial(const RatesIn &in, const RatesJ &J, int64_t l0, int64_t l1, double *d_shares, hipStream_t st)
 {
-    RatesArgs ra;
-    fill_rates_args(ra, g->n, nlam, ld, blocks, d_small, dJ, lambda0, c0, d_doppler, d_gamma, sigma_bb_const, d_temperature, d_lte,
-                    hc_over_kB, pref_ij, pref_ji, nullptr, nullptr, nullptr, nullptr);
-    if (dJ_up || dJ_down) {
-        ra.J_up = dJ_up; ra.J_down = dJ_down;
-        ra.store_up = g->up.d_store; ra.rank_down = g->down.d_srank;
-        hipLaunchKernelGGL(k_rates_partial<true>, dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, st, ra, l0, l1, d_shares);
-    } else
-    hipLaunchKernelGGL(k_rates_partial<false>, dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, st, ra, l0, l1, d_shares);
+    const RatesArgs ra = rates_args(in, J);
+    const dim3 grid((unsigned)((in.n + 255) / 256));
+    if (J.up || J.down)
+        hipLaunchKernelGGL(k_rates_partial<true>, grid, dim3(256), 0, st, ra, l0, l1, d_shares);
+    else
+        hipLaunchKernelGGL(k_rates_partial<false>, grid, dim3(256), 0, st, ra, l0, l1, d_shares);
     VRT_HIP_TRY(hipGetLastError());
     return VRT_OK;
 }
 
 // R (9 n) and the populations (3 n) from the summed shares
-int launch_populations_from_shares(vrt_grid *g, const double *d_shares, const double *d_C, const double *d_atom_density,
+int launch_populations_from_shares(int64_t n, const double *d_shares, const double *d_C, const double *d_atom_density,
                                    double *d_R, double *d_populations, hipStream_t st)
 {
-    RatesArgs ra;
-    const int64_t zero[6] = {0, 0, 0, 0, 0, 0};
-    fill_rates_args(ra, g->n, 0, 0, zero, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 0, d_C, d_atom_density,
-                    d_R, d_populations);
-    hipLaunchKernelGGL(k_populations_from_shares, dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, st, ra, d_shares);
+    RatesArgs ra{};
+    ra.n = n;
+    ra.C = d_C; ra.atom_density = d_atom_density; ra.R = d_R; ra.populations = d_populations;
+    hipLaunchKernelGGL(k_populations_from_shares, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ra, d_shares);
     VRT_HIP_TRY(hipGetLastError());
     return VRT_OK;
 }
 
-int launch_rates_populations(vrt_grid *g, int64_t nlam, int64_t ld, const int64_t blocks[6],
-                             const double *d_small /* lambda | planck2 | sigma_bf1 | sigma_bf2 */,
-                             const double *dJ, double lambda0, double c0, const double *d_doppler,
-                             const double *d_gamma, double sigma_bb_const, const double *d_temperature,
-                             const double *d_lte, double hc_over_kB, double pref_ij, double pref_ji,
-                             const double *d_C, const double *d_atom_density, double *d_R,
-                             double *d_populations, hipStream_t st, const double *dJ_up, const double *dJ_down)
+// J in rows (a grid's sites, or n points without a grid: the regular-grid Λ-iteration), in a grid's sweep-order planes,
+// or in a plan's float plane sets: J = (float)(J_up + J_down), widened
+int launch_rates_populations(const RatesIn &in, const RatesJ &J, double *d_R, double *d_populations, hipStream_t st)
 {
-    RatesArgs ra;
-    fill_rates_args(ra, g->n, nlam, ld, blocks, d_small, dJ, lambda0, c0, d_doppler, d_gamma, sigma_bb_const, d_temperature, d_lte,
-                    hc_over_kB, pref_ij, pref_ji, d_C, d_atom_density, d_R, d_populations);
-    if (dJ_up || dJ_down) {
-        ra.J_up = dJ_up; ra.J_down = dJ_down;
-        ra.store_up = g->up.d_store; ra.rank_down = g->down.d_srank;
-        hipLaunchKernelGGL(k_rates_populations<true>, dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, st, ra);
-    } else
-    hipLaunchKernelGGL(k_rates_populations<false>, dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, st, ra);
-    VRT_HIP_TRY(hipGetLastError());
-    return VRT_OK;
-}
-
-int launch_rates_populations_f32(vrt_plan *p, int64_t nlam, const int64_t blocks[6], const double *d_small, double lambda0,
-                                 double c0, const double *d_doppler, const double *d_gamma, double sigma_bb_const,
-                                 const double *d_temperature, const double *d_lte, double hc_over_kB, double pref_ij,
-                                 double pref_ji, const double *d_C, const double *d_atom_density, double *d_R,
-                                 double *d_populations, hipStream_t st, const float *dJ_up, const float *dJ_down)
-{
-    vrt_grid *g = p->g;
-    RatesArgs ra;
-    fill_rates_args(ra, g->n, nlam, nlam, blocks, d_small, nullptr, lambda0, c0, d_doppler, d_gamma, sigma_bb_const, d_temperature,
-                    d_lte, hc_over_kB, pref_ij, pref_ji, d_C, d_atom_density, d_R, d_populations);
-    ra.Jf_up = dJ_up; ra.Jf_down = dJ_down;
-    ra.lgB = native_lg(p, true); ra.npair = (int)((nlam + 1) / 2);
-    ra.store_up = g->up.d_store; ra.rank_down = g->down.d_srank;
-    hipLaunchKernelGGL((k_rates_populations<true, float>), dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, st, ra);
-    VRT_HIP_TRY(hipGetLastError());
-    return VRT_OK;
-}
-
-// the same for n points without a grid (the regular-grid Λ-iteration, vrt_regular_lambda.hip): J (nlam, n) of leading
-// dimension ld, in the points' own order
-int launch_rates_populations(int64_t n, int64_t nlam, int64_t ld, const int64_t blocks[6], const double *d_small,
-                             const double *dJ, double lambda0, double c0, const double *d_doppler, const double *d_gamma,
-                             double sigma_bb_const, const double *d_temperature, const double *d_lte, double hc_over_kB,
-                             double pref_ij, double pref_ji, const double *d_C, const double *d_atom_density, double *d_R,
-                             double *d_populations, hipStream_t st)
-{
-    RatesArgs ra;
-    fill_rates_args(ra, n, nlam, ld, blocks, d_small, dJ, lambda0, c0, d_doppler, d_gamma, sigma_bb_const, d_temperature, d_lte,
-                    hc_over_kB, pref_ij, pref_ji, d_C, d_atom_density, d_R, d_populations);
-    hipLaunchKernelGGL(k_rates_populations<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ra);
+    RatesArgs ra = rates_args(in, J);
+    ra.R = d_R; ra.populations = d_populations;
+    const dim3 grid((unsigned)((in.n + 255) / 256));
+    if (J.up || J.down)
+        hipLaunchKernelGGL(k_rates_populations<true>, grid, dim3(256), 0, st, ra);
+    else if (!J.up_f && !J.down_f)
+        hipLaunchKernelGGL(k_rates_populations<false>, grid, dim3(256), 0, st, ra);
+    else
+        hipLaunchKernelGGL((k_rates_populations<true, float>), grid, dim3(256), 0, st, ra);
     VRT_HIP_TRY(hipGetLastError());
     return VRT_OK;
 }

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "vrt_device.h"
+#include "vrt_line_case.h"
 #include "vrt_regular.h"
 #include "vrt_voigt.h"
 
@@ -285,15 +286,11 @@ struct vrt_regular_lambda {
     vrt_regular *r = nullptr;           // borrowed
     int device = 0, n_sweeps = 3;
     int64_t n = 0, nlam = 0;
-    int64_t blocks[6] = {0, 0, 0, 0, 0, 0};
-    double lambda0 = 0, c0 = 0, strength_const = 0, Bij = 0, Bji = 0, sigma_bb_const = 0, hc_over_kB = 0, pref_ij = 0,
-           pref_ji = 0;
     LineSolves ls;
     Stream st;
     // per point, Julia order
-    DevBuf<double> d_small;             // lambda | planck2 | sigma_bf1 | sigma_bf2
-    DevBuf<double> d_velocity, d_doppler, d_gamma_static, d_gamma_unsold, d_alpha_cont, d_eps, d_temperature, d_atom, d_B0,
-        d_lte, d_C, d_gamma, d_strength, d_R, d_J;
+    LineCaseDev line;                   // the uploaded case, γ, the line strength and R (vrt_line_case.h)
+    DevBuf<double> d_B0, d_J;
     DevBuf<double> d_pops[2], d_S[2];   // [cur]: the current populations, the last S_new
     int pc = 0, sc = 0;
     // plane-major, wavelength slowest
@@ -362,18 +359,10 @@ int vrt_regular_lambda_create(vrt_regular *r, int64_t n_angles, const double *k,
     *out = nullptr;
     if (!r || !k || !dirs || !weights || !lc) return fail(VRT_EINVAL, "NULL argument");
     const int64_t nlam = lc->nlam;
-    if (nlam < 2) return fail(VRT_EINVAL, "nlam must be >= 2");
-    if (n_sweeps < 1) return fail(VRT_EINVAL, "n_sweeps must be >= 1");
-    if (!lc->lambda || !lc->velocity || !lc->doppler_width || !lc->gamma_static || !lc->gamma_unsold || !lc->alpha_cont ||
-        !lc->eps || !lc->temperature || !lc->atom_density || !lc->B0 || !lc->lte_populations || !lc->C || !lc->planck2 ||
-        !lc->sigma_bf1 || !lc->sigma_bf2)
-        return fail(VRT_EINVAL, "NULL array in the line case");
-    for (int b = 0; b < 3; b++)
-        if (lc->blocks[2 * b] < 0 || lc->blocks[2 * b + 1] > nlam || lc->blocks[2 * b + 1] - lc->blocks[2 * b] < 2)
-            return fail(VRT_EINVAL, "each wavelength block needs at least two wavelengths inside [0, nlam)");
-    if (!(lc->lambda0 > 0) || !(lc->c0 > 0)) return fail(VRT_EINVAL, "lambda0 and c0 must be positive");
-    int rc = check_angles(n_angles, k, dirs);
-    if (rc) return rc;
+    // (n_sweeps is reported after nlam and before the rest of the case, as it always was)
+    if (nlam >= 2 && n_sweeps < 1) return fail(VRT_EINVAL, "n_sweeps must be >= 1");
+    int rc = check_line_case(lc);
+    if (rc || (rc = check_angles(n_angles, k, dirs))) return rc;
     return guarded([&] {
         if ((rc = use_device(r->device))) return rc;
         std::unique_ptr<vrt_regular_lambda> s(new vrt_regular_lambda());
@@ -383,60 +372,32 @@ int vrt_regular_lambda_create(vrt_regular *r, int64_t n_angles, const double *k,
         const int64_t vol = r->nz * r->nx * r->ny, plane = r->nx * r->ny;
         s->n = vol;
         s->nlam = nlam;
-        for (int q = 0; q < 6; q++) s->blocks[q] = lc->blocks[q];
-        s->lambda0 = lc->lambda0; s->c0 = lc->c0; s->strength_const = lc->strength_const; s->Bij = lc->Bij; s->Bji = lc->Bji;
-        s->sigma_bb_const = lc->sigma_bb_const; s->hc_over_kB = lc->hc_over_kB; s->pref_ij = lc->pref_ij; s->pref_ji = lc->pref_ji;
         if ((rc = line_solves_init(s->ls, r, n_angles, k, dirs, weights, nlam))) return rc;
         if ((rc = s->st.create())) return rc;
         const size_t n = (size_t)vol, nl = (size_t)nlam, nS = n * nl;
-        const size_t nb1 = (size_t)(lc->blocks[3] - lc->blocks[2]), nb2 = (size_t)(lc->blocks[5] - lc->blocks[4]);
-        std::vector<double> small;
-        small.insert(small.end(), lc->lambda, lc->lambda + nl);
-        small.insert(small.end(), lc->planck2, lc->planck2 + nl);
-        small.insert(small.end(), lc->sigma_bf1, lc->sigma_bf1 + nb1);
-        small.insert(small.end(), lc->sigma_bf2, lc->sigma_bf2 + nb2);
-        auto up = [&](DevBuf<double> &d, const double *h, size_t count) {
-            int e = d.alloc(count);
-            if (!e && hipMemcpy(d, h, sizeof(double) * count, hipMemcpyHostToDevice) != hipSuccess)
-                e = fail(VRT_ENODEVICE, "uploading the line case failed");
-            return e;
-        };
+        hipStream_t st = s->st;
 #define VRT_S(expr) do { if ((rc = (expr))) return rc; } while (0)
-        VRT_S(up(s->d_small, small.data(), small.size()));
-        VRT_S(up(s->d_velocity, lc->velocity, 3 * n));
-        VRT_S(up(s->d_doppler, lc->doppler_width, n));
-        VRT_S(up(s->d_gamma_static, lc->gamma_static, n));
-        VRT_S(up(s->d_gamma_unsold, lc->gamma_unsold, n));
-        VRT_S(up(s->d_alpha_cont, lc->alpha_cont, n));
-        VRT_S(up(s->d_eps, lc->eps, n));
-        VRT_S(up(s->d_temperature, lc->temperature, n));
-        VRT_S(up(s->d_atom, lc->atom_density, n));
-        VRT_S(up(s->d_B0, lc->B0, nS));
-        VRT_S(up(s->d_lte, lc->lte_populations, 3 * n));
-        VRT_S(up(s->d_C, lc->C, 9 * n));
-        VRT_S(up(s->d_pops[0], lc->lte_populations, 3 * n));        // populations = copy(LTE_pops), :127
-        VRT_S(up(s->d_S[0], lc->B0, nS));                           // S_new = B_0, :150
+        VRT_S(s->line.create(lc, vol, st));
+        VRT_S(upload(s->d_B0, lc->B0, nS, st));
+        VRT_S(upload(s->d_pops[0], lc->lte_populations, 3 * n, st));        // populations = copy(LTE_pops), :127
+        VRT_S(upload(s->d_S[0], lc->B0, nS, st));                           // S_new = B_0, :150
         VRT_S(s->d_pops[1].alloc(3 * n));
         VRT_S(s->d_S[1].alloc(nS));
         VRT_S(s->d_J.alloc(nS));
-        VRT_S(s->d_gamma.alloc(n));
-        VRT_S(s->d_strength.alloc(n));
-        VRT_S(s->d_R.alloc(9 * n));
         VRT_S(s->d_S_pl.alloc(nS));
         VRT_S(s->d_J_pl.alloc(nS));
         VRT_S(s->d_I0_pl.alloc((size_t)plane * nl));
         VRT_S(s->d_zero.alloc((size_t)plane));
         VRT_S(s->d_scalars.alloc(2));
-        hipStream_t st = s->st;
         // (J, R and γ are those of "no iteration yet": zeros)
         VRT_HIP_TRY(hipMemsetAsync(s->d_J, 0, sizeof(double) * nS, st));
-        VRT_HIP_TRY(hipMemsetAsync(s->d_R, 0, sizeof(double) * 9 * n, st));
-        VRT_HIP_TRY(hipMemsetAsync(s->d_gamma, 0, sizeof(double) * n, st));
+        VRT_HIP_TRY(hipMemsetAsync(s->line.d_R, 0, sizeof(double) * 9 * n, st));
+        VRT_HIP_TRY(hipMemsetAsync(s->line.d_gamma, 0, sizeof(double) * n, st));
         VRT_HIP_TRY(hipMemsetAsync(s->d_zero, 0, sizeof(double) * (size_t)plane, st));
         VRT_S(launch_to_planes(r, nlam, s->d_B0, s->d_S_pl, st));
         VRT_S(launch_bottom_planes(r, nlam, s->d_B0, s->d_I0_pl, st));    // I_0 = B_λ(λ_l, T[1, :, :]), :38
 #undef VRT_S
-        VRT_HIP_TRY(hipStreamSynchronize(st));
+        VRT_HIP_TRY(hipStreamSynchronize(st));               // the host arrays may go after return
         *out = s.release();
         return VRT_OK;
     });
@@ -452,24 +413,22 @@ int vrt_regular_lambda_iterate(vrt_regular_lambda *s, double *max_rel_change)
         vrt_regular *r = s->r;
         const int64_t n = s->n, nlam = s->nlam;
         // γ and the line strength of the current populations (:13-16, line.jl:219-225)
-        if ((rc = launch_line_terms(n, s->d_gamma_static, s->d_gamma_unsold, s->d_pops[s->pc], s->strength_const, s->Bij, s->Bji,
-                                    s->d_gamma, s->d_strength, st)))
-            return rc;
+        LineCaseDev &line = s->line;
+        if ((rc = line.terms(s->d_pops[s->pc], st))) return rc;
         // α_tot of every angle, J_λ (:22-55) from S_old = the last S_new (:165-167)
         LinePoint lp;
-        lp.lambda = s->d_small; lp.velocity = s->d_velocity; lp.doppler = s->d_doppler; lp.gamma = s->d_gamma;
-        lp.strength = s->d_strength; lp.alpha_cont = s->d_alpha_cont; lp.lambda0 = s->lambda0; lp.c0 = s->c0;
+        lp.lambda = small_view(line.d_small, nlam, line.k.blocks).lambda; lp.velocity = line.d_velocity; lp.doppler = line.d_doppler;
+        lp.gamma = line.d_gamma; lp.strength = line.d_strength; lp.alpha_cont = line.d_alpha_cont; lp.lambda0 = line.k.lambda0;
+        lp.c0 = line.k.c0;
         if ((rc = line_J_pass(r, s->ls, lp, s->d_S_pl, s->d_I0_pl, s->d_zero, s->n_sweeps, s->d_J_pl, st))) return rc;
         if ((rc = launch_from_planes(r, nlam, s->d_J_pl, s->d_J, st))) return rc;
         // S_new = (1 - ε) J + ε B_0 (:169-171) and the criterion's scalar; S_new also plane-major for the next solves
-        if ((rc = launch_lambda_update(n, nlam, nlam, s->d_J, s->d_B0, s->d_eps, s->d_S[s->sc], s->d_S[s->sc ^ 1], s->d_scalars, st)))
+        if ((rc = launch_lambda_update(n, nlam, nlam, s->d_J, s->d_B0, line.d_eps, s->d_S[s->sc], s->d_S[s->sc ^ 1], s->d_scalars, st)))
             return rc;
         s->sc ^= 1;
         if ((rc = launch_to_planes(r, nlam, s->d_S[s->sc], s->d_S_pl, st))) return rc;
         // R, populations (:176, :181)
-        if ((rc = launch_rates_populations(n, nlam, nlam, s->blocks, s->d_small, s->d_J, s->lambda0, s->c0, s->d_doppler,
-                                           s->d_gamma, s->sigma_bb_const, s->d_temperature, s->d_lte, s->hc_over_kB, s->pref_ij,
-                                           s->pref_ji, s->d_C, s->d_atom, s->d_R, s->d_pops[s->pc ^ 1], st)))
+        if ((rc = launch_rates_populations(line.rates_in(), RatesJ::from_rows(s->d_J, nlam), line.d_R, s->d_pops[s->pc ^ 1], st)))
             return rc;
         s->pc ^= 1;
         unsigned long long h[2] = {0, 0};
@@ -525,8 +484,8 @@ int vrt_regular_lambda_get(vrt_regular_lambda *s, double *J, double *S, double *
         if (J) VRT_HIP_TRY(hipMemcpy(J, s->d_J, sizeof(double) * nS, hipMemcpyDeviceToHost));
         if (S) VRT_HIP_TRY(hipMemcpy(S, s->d_S[s->sc], sizeof(double) * nS, hipMemcpyDeviceToHost));
         if (populations) VRT_HIP_TRY(hipMemcpy(populations, s->d_pops[s->pc], sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
-        if (R) VRT_HIP_TRY(hipMemcpy(R, s->d_R, sizeof(double) * 9 * n, hipMemcpyDeviceToHost));
-        if (gamma) VRT_HIP_TRY(hipMemcpy(gamma, s->d_gamma, sizeof(double) * n, hipMemcpyDeviceToHost));
+        if (R) VRT_HIP_TRY(hipMemcpy(R, s->line.d_R, sizeof(double) * 9 * n, hipMemcpyDeviceToHost));
+        if (gamma) VRT_HIP_TRY(hipMemcpy(gamma, s->line.d_gamma, sizeof(double) * n, hipMemcpyDeviceToHost));
         return VRT_OK;
     });
 }
