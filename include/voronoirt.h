@@ -248,6 +248,34 @@ int vrt_rates_populations_native_dev_f32(vrt_plan *p, int64_t nlam, const double
                                          const double *d_temperature, const double *d_lte_populations, double hc_over_kB,
                                          double pref_ij, double pref_ji, const double *d_C, const double *d_atom_density,
                                          double *d_R, double *d_populations, void *stream);
+/* The rates step split over wavelength ranges (what a member of vrt_multi_lambda runs; a one-process-per-GPU caller builds
+ * the same loop from these).  vrt_rate_shares_native_dev[_f32]: the share of the wavelengths [l0, l1) of the case's nlam in
+ * the six λ-integrals of a site, the trapezoid sums regrouped per wavelength -- Σ_l W_l f_l with
+ * W_l = (λ_l - λ_l-1) [l > lo] + (λ_l+1 - λ_l) [l < hi - 1] inside each block [lo, hi), the prefactor applied last -- so that
+ * the shares of a partition of [0, nlam), added, are the integrals of vrt_rates_populations_native_dev to the rounding of
+ * that regrouping (1e-12).  lambda, blocks, planck2, sigma_bf1 / sigma_bf2 describe ALL nlam wavelengths; the J plane sets
+ * hold the l1 - l0 wavelengths of the range only, wavelength l at local index l - l0: doubles in the grid's two orders
+ * (vrt_plan_native_plane_count(p, l1 - l0) each), or floats in the plan's float layout of l1 - l0 wavelengths, J formed as
+ * (float)(J_up + J_down) and widened, as vrt_rates_populations_native_dev_f32 forms it.  The padding wavelength of an odd
+ * l1 - l0 is never used, whatever it holds.  Either J pointer may be NULL for a direction without angles.
+ * d_shares [6][n]: (bf1 ij, bf1 ji, bf2 ij, bf2 ji, bb ij, bb ji) of site i at [q n + i].  0 <= l0 <= l1 <= nlam; l0 == l1
+ * gives six zero planes (both J pointers may then be NULL); a transition without a wavelength in [l0, l1) gets exactly 0.
+ * vrt_populations_from_shares_dev: R (3, 3, n) and the populations (n, 3) from the SUMMED shares, on the current device
+ * (src/populations.jl:191-221). */
+int vrt_rate_shares_native_dev(vrt_grid *g, int64_t nlam, int64_t l0, int64_t l1, const double *lambda,
+                               const int64_t blocks[6], const double *dJ_up, const double *dJ_down, const double *planck2,
+                               double lambda0, double c0, const double *d_doppler_width, const double *d_gamma,
+                               double sigma_bb_const, const double *sigma_bf1, const double *sigma_bf2,
+                               const double *d_temperature, const double *d_lte_populations, double hc_over_kB,
+                               double pref_ij, double pref_ji, double *d_shares, void *stream);
+int vrt_rate_shares_native_dev_f32(vrt_plan *p, int64_t nlam, int64_t l0, int64_t l1, const double *lambda,
+                                   const int64_t blocks[6], const float *dJ_up, const float *dJ_down, const double *planck2,
+                                   double lambda0, double c0, const double *d_doppler_width, const double *d_gamma,
+                                   double sigma_bb_const, const double *sigma_bf1, const double *sigma_bf2,
+                                   const double *d_temperature, const double *d_lte_populations, double hc_over_kB,
+                                   double pref_ij, double pref_ji, double *d_shares, void *stream);
+int vrt_populations_from_shares_dev(int64_t n, const double *d_shares, const double *d_C, const double *d_atom_density,
+                                    double *d_R, double *d_populations, void *stream);
 
 /* fp32 VALUE path (BASELINE config C5): S, alpha, I_0, J and the per-angle intensities are stored
  * as float, halving the bytes of this bandwidth-bound path; the geometry tables and all
@@ -605,6 +633,20 @@ int vrt_multi_lambda_create(vrt_multi *m, const vrt_line_case *lc, const double 
 int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change);
 int vrt_multi_lambda_get(vrt_multi_lambda *s, double *J, double *S, double *populations, double *R, double *gamma);
 void vrt_multi_lambda_destroy(vrt_multi_lambda *s);
+/* The same session with FLOAT storage, as vrt_lambda_create_f32 is to vrt_lambda_create.  Every device keeps S and J of
+ * ITS wavelength block in both sweep orders, B_0 of the block in the up order (rounded once), I_0 and the native α as
+ * float; the staged double B_0 is freed, so that after create no device holds a double array of size nλ_block·n or
+ * nλ_block·n·angles.  An iterate of a device: the line terms, the float opacity prologue at its wavelength offset,
+ * vrt_plan_execute_native_dev_f32, vrt_lambda_update_native_dev_f32 and vrt_rate_shares_native_dev_f32 on its block; the
+ * all-reduce of 6 n doubles and the statistical equilibrium are those of the double session.  Every wavelength is solved by
+ * exactly one device and a solve does not see the other wavelengths of its block: J and S of an iterate equal the
+ * one-device float session's on the same populations bit for bit; the populations differ from its by the 1e-12 regrouping.
+ * VRT_EINVAL when ANY device's plan is not on the patch path or with VRT_LAMBDA_NATIVE=0: there is no fp64 fallback.
+ * vrt_multi_lambda_get returns J and S as doubles holding exactly the float values; vrt_multi_lambda_set_state validates
+ * as for a double session, then rounds S to float; vrt_multi_lambda_set_acceleration (voronoirt_multi_accel.h) returns
+ * VRT_EINVAL on a float session and changes nothing.  vrt_multi_lambda_storage: 8 or 4 (VRT_EINVAL for NULL). */
+int vrt_multi_lambda_create_f32(vrt_multi *m, const vrt_line_case *lc, const double *weights, vrt_multi_lambda **out);
+int vrt_multi_lambda_storage(const vrt_multi_lambda *s);
 
 /* ---- rates + populations of the Λ-iteration epilogue on the device --------
  * calculate_R (src/rates.jl:154-201: Rij / Rji λ-trapezoids :226-364, σij with the site's static

@@ -287,9 +287,11 @@ iterates, both >= 4.  The keyword is unrun: Julia is not installed where the lib
 `S0` (nλ, n), `populations0` (n, 3), with or without units: the loop starts from them instead of LTE with S = B_0
 (vrt_lambda_set_state / vrt_multi_lambda_set_state; the state the reference checkpoints, :280-281) and continues bit for
 bit as the run that wrote them; either alone replaces that half.  Unrun as well.
-`storage = :f32`: the session holds S, J, B_0, I_0 and α_tot as Float32 (vrt_lambda_create_f32; arithmetic stays Float64;
-one device, the patch path only -- the library refuses anything else, there is no Float64 fallback).  J_new and S_new come
-back as Float64 arrays of Float32 values; `ng` is an error with it (the Ng kernels work on Float64 planes).  Unrun as well.
+`storage = :f32`: the session holds S, J, B_0, I_0 and α_tot as Float32 (vrt_lambda_create_f32, or
+vrt_multi_lambda_create_f32 when several devices are listed: every device then holds its wavelength block as Float32;
+arithmetic stays Float64; the patch path only -- the library refuses anything else, there is no Float64 fallback).  J_new
+and S_new come back as Float64 arrays of Float32 values; `ng` is an error with it (the Ng kernels work on Float64 planes).
+Unrun as well.
 """
 function Λ(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, line::HydrogenicLine, quadrature::String, DATA::String;
            ng::Union{Nothing,Tuple{Int,Int}}=nothing, S0=nothing, populations0=nothing, storage::Symbol=:f64)
@@ -340,9 +342,9 @@ function Λ(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, line::Hydr
     a_j = -line_strength(line, [1.0u"m^-3"], [0.0u"m^-3"])[1]
     # one device: vrt_lambda_* on the plan; ENV["VRT_DEVICES"] lists several: vrt_multi_lambda_* (same arguments)
     multi = length(vrt_devices()) > 1
-    multi && storage == :f32 && error("storage = :f32 needs the one-device session (vrt_multi_lambda_* holds Float64)")
     plan = multi ? multi_handle(sites, quadrature, 3) : plan_handle(sites, quadrature, 3)
-    f_create = multi ? :vrt_multi_lambda_create : storage == :f32 ? :vrt_lambda_create_f32 : :vrt_lambda_create
+    f_create = multi ? (storage == :f32 ? :vrt_multi_lambda_create_f32 : :vrt_multi_lambda_create) :
+               storage == :f32 ? :vrt_lambda_create_f32 : :vrt_lambda_create
     f_iterate = multi ? :vrt_multi_lambda_iterate : :vrt_lambda_iterate
     f_get = multi ? :vrt_multi_lambda_get : :vrt_lambda_get
     f_destroy = multi ? :vrt_multi_lambda_destroy : :vrt_lambda_destroy

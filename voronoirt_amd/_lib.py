@@ -95,6 +95,11 @@ PROTOTYPES = {
     "vrt_rates_populations_native_dev_f32": (ctypes.c_int, [vp, c_i64, p_dbl, p_i64, vp, vp, p_dbl, c_dbl, c_dbl, vp, vp,
                                                             c_dbl, p_dbl, p_dbl, vp, vp, c_dbl, c_dbl, c_dbl, vp, vp, vp,
                                                             vp, vp]),
+    "vrt_rate_shares_native_dev": (ctypes.c_int, [vp, c_i64, c_i64, c_i64, p_dbl, p_i64, vp, vp, p_dbl, c_dbl, c_dbl, vp, vp,
+                                                  c_dbl, p_dbl, p_dbl, vp, vp, c_dbl, c_dbl, c_dbl, vp, vp]),
+    "vrt_rate_shares_native_dev_f32": (ctypes.c_int, [vp, c_i64, c_i64, c_i64, p_dbl, p_i64, vp, vp, p_dbl, c_dbl, c_dbl, vp, vp,
+                                                      c_dbl, p_dbl, p_dbl, vp, vp, c_dbl, c_dbl, c_dbl, vp, vp]),
+    "vrt_populations_from_shares_dev": (ctypes.c_int, [c_i64, vp, vp, vp, vp, vp, vp]),
     "vrt_grid_get_storage_order": (ctypes.c_int, [vp, ctypes.c_int, p_i64]),
     "vrt_plan_native_alpha_count": (c_i64, [vp, c_i64]),
     "vrt_plan_native_pair_block": (ctypes.c_int, [vp]),
@@ -122,6 +127,8 @@ PROTOTYPES = {
     "vrt_multi_execute_line": (ctypes.c_int, [vp, c_i64, c_i64, p_dbl, c_dbl, c_dbl, p_dbl, p_dbl, p_dbl, p_dbl, p_dbl, p_dbl,
                                               p_dbl, p_dbl, p_dbl, p_dbl]),
     "vrt_multi_lambda_create": (ctypes.c_int, [vp, ctypes.POINTER(LineCaseStruct), p_dbl, ctypes.POINTER(vp)]),
+    "vrt_multi_lambda_create_f32": (ctypes.c_int, [vp, ctypes.POINTER(LineCaseStruct), p_dbl, ctypes.POINTER(vp)]),
+    "vrt_multi_lambda_storage": (ctypes.c_int, [vp]),
     "vrt_multi_lambda_iterate": (ctypes.c_int, [vp, p_dbl]),
     "vrt_multi_lambda_get": (ctypes.c_int, [vp, p_dbl, p_dbl, p_dbl, p_dbl, p_dbl]),
     "vrt_multi_lambda_destroy": (None, [vp]),

@@ -485,20 +485,28 @@ class MultiDevicePlan:
         return J
 
     def lambda_iteration(self, eps_conv: float, maxiter: int, case, weights, S0=None, populations0=None, checkpoint=None,
-                         checkpoint_every: int = 1, resume=None, ng=None):
+                         checkpoint_every: int = 1, resume=None, ng=None, storage: str = "f64"):
         """Λ_voronoi (src/lambda_iteration.jl:205-300) across the devices (`vrt_multi_lambda_*`): wavelength blocks per
         device, one all-reduce of the rate-integral shares per iteration.  Returns (J, S_new, populations (3, n), history).
         S0, populations0, checkpoint, checkpoint_every, resume as for `Lambda_voronoi_host`
         (`vrt_multi_lambda_set_state`: every device takes its wavelength block of S and all the populations).
         ng=(start, period) as for `Lambda_voronoi_host` (`vrt_multi_lambda_set_acceleration`: every device keeps the history
         of its own block, the five sums are added on the host in device order, the step is taken on every device or on
-        none); the tuple gains a fifth element, the list of (iterate, applied, a, b) of every due step."""
+        none); the tuple gains a fifth element, the list of (iterate, applied, a, b) of every due step.
+        storage="f32": every device holds its block of S, J, B, I_0 and α as float32 (`vrt_multi_lambda_create_f32`; the
+        shares, the all-reduce and the populations stay float64, the patch path only); the returned J and S are float64
+        arrays of float32-representable values, checkpoints work unchanged, and `ng` raises ValueError before any device
+        work, as for `Lambda_voronoi_host`."""
+        f32 = _storage_f32(storage, "lambda_iteration")
+        if f32 and ng is not None:
+            raise ValueError("lambda_iteration: ng is not available with storage='f32'")
         L = _lib.load()
         lc, keep = case.c_struct()
         n, nlam = self.n, int(keep["lam"].size)
         start = _start_state(S0, populations0, resume, checkpoint_every, n, nlam, "lambda_iteration")
         h = ctypes.c_void_p()
-        check(L.vrt_multi_lambda_create(self._h, ctypes.byref(lc), _d(_f64(weights)), ctypes.byref(h)))
+        check((L.vrt_multi_lambda_create_f32 if f32 else L.vrt_multi_lambda_create)(self._h, ctypes.byref(lc), _d(_f64(weights)),
+                                                                                    ctypes.byref(h)))
         try:
             if ng is not None:
                 if not hasattr(L, "vrt_multi_lambda_set_acceleration"):
@@ -508,6 +516,8 @@ class MultiDevicePlan:
                                                           checkpoint_every, ng, "lambda_iteration")
             if i == 0:
                 S[:] = keep["B0"] if start[0] is None else start[0]
+                if f32:
+                    S[:] = S.astype(np.float32)
                 pops[:] = keep["lte"] if start[1] is None else start[1]
             return (J, S, pops, history) if ng is None else (J, S, pops, history, steps)
         finally:
@@ -1271,6 +1281,47 @@ def rates_populations_native_dev_f32(plan: "FormalPlan", lam, blocks, dJ_up: int
                                                            float(sigma_bb_const), _d(s1), _d(s2), d_temperature, d_lte,
                                                            float(hc_over_kB), float(pref_ij), float(pref_ji), d_C, d_atom_density,
                                                            d_R, d_populations, stream or None))
+
+
+def _rate_shares(entry, handle, lam, blocks, l0, l1, dJ_up, dJ_down, planck2, lambda0, c0, d_doppler, d_gamma, sigma_bb_const,
+                 sigma_bf1, sigma_bf2, d_temperature, d_lte, hc_over_kB, pref_ij, pref_ji, d_shares, stream):
+    lam, planck2 = _f64(lam), _f64(planck2)
+    blocks = np.ascontiguousarray(blocks, dtype=np.int64)
+    s1, s2 = _f64(sigma_bf1), _f64(sigma_bf2)
+    check(entry(handle, lam.size, int(l0), int(l1), _d(lam), _i(blocks), dJ_up or None, dJ_down or None, _d(planck2),
+                float(lambda0), float(c0), d_doppler, d_gamma, float(sigma_bb_const), _d(s1), _d(s2), d_temperature, d_lte,
+                float(hc_over_kB), float(pref_ij), float(pref_ji), d_shares, stream or None))
+
+
+def rate_shares_native_dev(sites: VoronoiSites, lam, blocks, l0: int, l1: int, dJ_up: int, dJ_down: int, planck2, lambda0: float,
+                           c0: float, d_doppler: int, d_gamma: int, sigma_bb_const: float, sigma_bf1, sigma_bf2,
+                           d_temperature: int, d_lte: int, hc_over_kB: float, pref_ij: float, pref_ji: float, d_shares: int,
+                           stream: int = 0) -> None:
+    """The share of the wavelengths [l0, l1) of `lam` in the six rate integrals of every site (`vrt_rate_shares_native_dev`),
+    into d_shares (6, n) float64.  dJ_up / dJ_down: float64 sweep-order plane sets of those l1 - l0 wavelengths only
+    (wavelength l at local index l - l0).  The shares of a partition of the wavelengths, added, go to
+    `populations_from_shares_dev`."""
+    _rate_shares(_lib.load().vrt_rate_shares_native_dev, sites.handle, lam, blocks, l0, l1, dJ_up, dJ_down, planck2, lambda0, c0,
+                 d_doppler, d_gamma, sigma_bb_const, sigma_bf1, sigma_bf2, d_temperature, d_lte, hc_over_kB, pref_ij, pref_ji,
+                 d_shares, stream)
+
+
+def rate_shares_native_dev_f32(plan: "FormalPlan", lam, blocks, l0: int, l1: int, dJ_up: int, dJ_down: int, planck2,
+                               lambda0: float, c0: float, d_doppler: int, d_gamma: int, sigma_bb_const: float, sigma_bf1,
+                               sigma_bf2, d_temperature: int, d_lte: int, hc_over_kB: float, pref_ij: float, pref_ji: float,
+                               d_shares: int, stream: int = 0) -> None:
+    """`rate_shares_native_dev` with J read from float32 plane sets of l1 - l0 wavelengths in the plan's float layout
+    (`vrt_rate_shares_native_dev_f32`): J = f32(J_up + J_down) widened; the shares are float64."""
+    _rate_shares(_lib.load().vrt_rate_shares_native_dev_f32, plan._h, lam, blocks, l0, l1, dJ_up, dJ_down, planck2, lambda0, c0,
+                 d_doppler, d_gamma, sigma_bb_const, sigma_bf1, sigma_bf2, d_temperature, d_lte, hc_over_kB, pref_ij, pref_ji,
+                 d_shares, stream)
+
+
+def populations_from_shares_dev(n: int, d_shares: int, d_C: int, d_atom_density: int, d_R: int, d_populations: int,
+                                stream: int = 0) -> None:
+    """R (n, 3, 3) and the populations (3, n) of every site from the summed shares (6, n) of `rate_shares_native_dev[_f32]`
+    (`vrt_populations_from_shares_dev`), on the current device."""
+    check(_lib.load().vrt_populations_from_shares_dev(int(n), d_shares, d_C, d_atom_density, d_R, d_populations, stream or None))
 
 
 def rates_populations_dev(sites: VoronoiSites, lam, blocks, ld: int, dJ: int, planck2, lambda0: float, c0: float,

@@ -1658,6 +1658,84 @@ int vrt_rates_populations_native_dev_f32(vrt_plan *p, int64_t nlam, const double
                                   pref_ij, pref_ji, d_C, d_atom_density, d_R, d_populations, stream, p, dJ_up, dJ_down);
 }
 
+// the share of wavelengths [l0, l1) in the six rate integrals, from plane sets of those l1 - l0 wavelengths: doubles in
+// the grid's orders, or floats in the float layout of p32
+static int rate_shares_impl(vrt_grid *g, int64_t nlam, int64_t l0, int64_t l1, const double *lambda, const int64_t blocks[6],
+                            const double *dJ_up, const double *dJ_down, const double *planck2, double lambda0, double c0,
+                            const double *d_doppler_width, const double *d_gamma, double sigma_bb_const,
+                            const double *sigma_bf1, const double *sigma_bf2, const double *d_temperature,
+                            const double *d_lte_populations, double hc_over_kB, double pref_ij, double pref_ji,
+                            double *d_shares, void *stream,
+                            vrt_plan *p32 = nullptr, const float *fJ_up = nullptr, const float *fJ_down = nullptr)
+{
+    if (!g || !lambda || !blocks || !planck2 || !d_doppler_width || !d_gamma || !sigma_bf1 || !sigma_bf2 || !d_temperature ||
+        !d_lte_populations || !d_shares)
+        return fail(VRT_EINVAL, "NULL argument");
+    if (nlam < 2) return fail(VRT_EINVAL, "need nlam >= 2");
+    if (int rc = check_blocks(blocks, nlam)) return rc;
+    if (l0 < 0 || l0 > l1 || l1 > nlam) return fail(VRT_EINVAL, "need 0 <= l0 <= l1 <= nlam");
+    if (l0 < l1 && !dJ_up && !dJ_down && !fJ_up && !fJ_down) return fail(VRT_EINVAL, "NULL argument");
+    return guarded([&] {
+        int rc = use_device(g->device);
+        if (rc) return rc;
+        if (p32 && (rc = native_planes_ok(p32, true))) return rc;
+        hipStream_t st = (hipStream_t)stream;
+        if (l0 == l1) {                                     // no wavelength, no J: six zero planes
+            VRT_HIP_TRY(hipMemsetAsync(d_shares, 0, sizeof(double) * 6 * (size_t)g->n, st));
+            return (int)VRT_OK;
+        }
+        std::lock_guard<std::mutex> lock(g->mu);
+        if ((rc = upload_small(g, pack_small(nlam, blocks, lambda, planck2, sigma_bf1, sigma_bf2), st))) return rc;
+        RatesIn in;
+        in.n = g->n; in.nlam = nlam;
+        for (int q = 0; q < 6; q++) in.k.blocks[q] = blocks[q];
+        in.k.lambda0 = lambda0; in.k.c0 = c0; in.k.sigma_bb_const = sigma_bb_const; in.k.hc_over_kB = hc_over_kB;
+        in.k.pref_ij = pref_ij; in.k.pref_ji = pref_ji;
+        in.small = small_view(g->d_small, nlam, blocks);
+        in.doppler = d_doppler_width; in.gamma = d_gamma; in.temperature = d_temperature; in.lte = d_lte_populations;
+        const RatesJ J = p32 ? RatesJ::from_planes_f32(p32, fJ_up, fJ_down) : RatesJ::from_planes(g, dJ_up, dJ_down);
+        rc = launch_rates_partial(in, J, l0, l1, d_shares, st);
+        return rc ? rc : small_done(g, st);
+    });
+}
+
+int vrt_rate_shares_native_dev(vrt_grid *g, int64_t nlam, int64_t l0, int64_t l1, const double *lambda, const int64_t blocks[6],
+                               const double *dJ_up, const double *dJ_down, const double *planck2,
+                               double lambda0, double c0, const double *d_doppler_width, const double *d_gamma,
+                               double sigma_bb_const, const double *sigma_bf1, const double *sigma_bf2,
+                               const double *d_temperature, const double *d_lte_populations, double hc_over_kB,
+                               double pref_ij, double pref_ji, double *d_shares, void *stream)
+{
+    return rate_shares_impl(g, nlam, l0, l1, lambda, blocks, dJ_up, dJ_down, planck2, lambda0, c0, d_doppler_width, d_gamma,
+                            sigma_bb_const, sigma_bf1, sigma_bf2, d_temperature, d_lte_populations, hc_over_kB, pref_ij, pref_ji,
+                            d_shares, stream);
+}
+
+int vrt_rate_shares_native_dev_f32(vrt_plan *p, int64_t nlam, int64_t l0, int64_t l1, const double *lambda, const int64_t blocks[6],
+                                   const float *dJ_up, const float *dJ_down, const double *planck2,
+                                   double lambda0, double c0, const double *d_doppler_width, const double *d_gamma,
+                                   double sigma_bb_const, const double *sigma_bf1, const double *sigma_bf2,
+                                   const double *d_temperature, const double *d_lte_populations, double hc_over_kB,
+                                   double pref_ij, double pref_ji, double *d_shares, void *stream)
+{
+    if (!p) return fail(VRT_EINVAL, "NULL argument");
+    return rate_shares_impl(p->g, nlam, l0, l1, lambda, blocks, nullptr, nullptr, planck2, lambda0, c0, d_doppler_width, d_gamma,
+                            sigma_bb_const, sigma_bf1, sigma_bf2, d_temperature, d_lte_populations, hc_over_kB, pref_ij, pref_ji,
+                            d_shares, stream, p, dJ_up, dJ_down);
+}
+
+int vrt_populations_from_shares_dev(int64_t n, const double *d_shares, const double *d_C, const double *d_atom_density,
+                                    double *d_R, double *d_populations, void *stream)
+{
+    if (!d_shares || !d_C || !d_atom_density || !d_R || !d_populations) return fail(VRT_EINVAL, "NULL argument");
+    if (n < 1) return fail(VRT_EINVAL, "n must be >= 1");
+    return guarded([&] {
+        int rc = use_current_device();
+        if (rc) return rc;
+        return launch_populations_from_shares(n, d_shares, d_C, d_atom_density, d_R, d_populations, (hipStream_t)stream);
+    });
+}
+
 static int single_solve(vrt_grid *g, int dir, const double k[3], const double *S, const double *I0,
                         int64_t nI0, const double *alpha, int n_sweeps, double *I_out)
 {

@@ -105,7 +105,8 @@ struct RatesJ {
 };
 // R (9 n) and the populations (3 n) of every site from J (rates.jl:154-201, populations.jl:191-221)
 int launch_rates_populations(const RatesIn &in, const RatesJ &J, double *d_R, double *d_populations, hipStream_t st);
-// one device's share of the six rate integrals: wavelengths [l0, l1) of the nlam; J holds those columns only
+// one device's share of the six rate integrals: wavelengths [l0, l1) of the nlam; J holds those columns only (plane sets:
+// l1 - l0 wavelengths at local index l - l0, float ones in the pair blocks the plan gives l1 - l0 wavelengths)
 int launch_rates_partial(const RatesIn &in, const RatesJ &J, int64_t l0, int64_t l1, double *d_shares, hipStream_t st);
 // R and the populations from the summed shares
 int launch_populations_from_shares(int64_t n, const double *d_shares, const double *d_C, const double *d_atom_density,

@@ -436,12 +436,16 @@ int vrt_multi_execute_line(vrt_multi *mm, int64_t nlam, int64_t ld, const double
 // radiative rates (rates.jl:154-201).  The shares are summed by ONE all-reduce of 6 n doubles over xGMI (SURVEY 8e:
 // "only R and one scalar are reduced"); J never travels.  Every device then solves the statistical equilibrium of
 // every site itself (populations.jl:191-221), so the next iteration's opacity needs no further exchange.  A member's S and
-// J live in a SourceStore (vrt_source_store.h), in rows or in sweep order, all members alike.
+// J live in a SourceStore (vrt_source_store.h), in rows or in sweep order, all members alike.  Float storage
+// (vrt_multi_lambda_create_f32): every member's store is kPlanesF32 and f_B0, f_I0 and f_native replace d_B0, d_I0 and
+// d_native -- no member holds a double array of size nλ_block·n or nλ_block·n·angles; the shares, the all-reduce and the
+// statistical equilibrium are the same doubles.
 struct LambdaMember {
     int device = 0;
     int64_t l0 = 0, l1 = 0;
     LineCaseDev line;                   // the whole case (every site, ALL wavelengths), γ, the line strength and R (vrt_line_case.h)
     DevBuf<double> d_B0, d_I0, d_native;   // this block's columns (B_0 in the store's order: rows, or its up-order plane set)
+    DevBuf<float> f_B0, f_I0, f_native;    // float storage: B_0 rounded once in the up order, I_0, the native α
     DevBuf<double> d_pops, d_shares;
     DevBuf<unsigned long long> d_scalars;
     Event ev;
@@ -456,6 +460,7 @@ struct vrt_multi_lambda {
     int64_t n = 0, nlam = 0;
     std::vector<double> weights;
     std::vector<LambdaMember> lm;
+    bool f32 = false;                   // float storage, every member (a member without wavelengths has no store to ask)
     int iterations = 0;
     NgState ng;                         // the settings and the last report; the buffers are the members'
     bool ng_torn = false;               // an accepted step whose down-order copy could not be rewritten: S is inconsistent
@@ -563,7 +568,7 @@ int multi_ng_after_iterate(vrt_multi_lambda *s)
 
 extern "C" {
 
-int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double *weights, vrt_multi_lambda **out)
+static int multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double *weights, vrt_multi_lambda **out, bool f32)
 {
     if (!out) return fail(VRT_EINVAL, "out is NULL");
     *out = nullptr;
@@ -578,17 +583,23 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
             if (int rc = line_path_ok(p, "the line session")) return rc;
             if (p->A != (int)p->n_angles_user)
                 return fail(VRT_EINVAL, "per-angle alpha needs every angle active (no θ = 90 direction)");
+            if (f32) {                                  // float planes exist on the patch path only: no fp64 fallback
+                if (int rc = native_planes_ok(p, true)) return rc;
+                if (p->tune.lambda_native == 0 || (p->tune.path != 0 && p->tune.path != 4))
+                    return fail(VRT_EINVAL, "the float-storage line session keeps S and J in the patch path's sweep order: not with VRT_LAMBDA_NATIVE=0 or a VRT_PATH other than patches");
+            }
         }
         std::unique_ptr<vrt_multi_lambda> s(new vrt_multi_lambda());
         s->mm = mm;
+        s->f32 = f32;
         s->n = mm->n;
         s->nlam = nlam;
         s->weights.assign(weights, weights + mm->n_angles);
         s->lm = std::vector<LambdaMember>((size_t)W);
         // every member keeps its block in sweep order, or none does (VRT_LAMBDA_NATIVE, all plans fit)
-        SourceStore::Form form = SourceStore::kPlanes;
+        SourceStore::Form form = f32 ? SourceStore::kPlanesF32 : SourceStore::kPlanes;
         for (const Member &me : mm->m)
-            if (!SourceStore::plan_keeps_planes(me.plan_all.get())) form = SourceStore::kRows;
+            if (!f32 && !SourceStore::plan_keeps_planes(me.plan_all.get())) form = SourceStore::kRows;
         const size_t n = (size_t)mm->n;
         std::vector<int> rcs((size_t)W, VRT_OK);
         std::vector<std::string> errs((size_t)W);
@@ -608,13 +619,24 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
             VRT_S(dupload_cols(l.d_B0, lc->B0, n, nlam, l.l0, l.l1, st));
             if (nb) VRT_S(l.sj.create(me.plan_all.get(), (int64_t)nb, form, l.d_B0, st));      // S_new = B_0, S_old = zero(S_new), :236-240
             VRT_S(l.d_shares.alloc(6 * n));
-            VRT_S(l.d_I0.alloc((size_t)g->up.n1 * nb));
-            VRT_S(l.d_native.alloc(nb ? (size_t)vrt_plan_native_alpha_count(me.plan_all.get(), (int64_t)nb) : 1));
             VRT_S(l.d_scalars.alloc(2));
             VRT_S(l.ev.create(hipEventDisableTiming));
-            if (nb) {
-                VRT_S(launch_gather_rows(g->up.n1, (int64_t)nb, (int64_t)nb, g->up.d_order, l.d_B0, l.d_I0, st));   // I_0 = B_λ of the bottom layer, :99-101
-                VRT_S(l.sj.to_up_order(l.d_B0, st));
+            // I_0 = B_λ of the bottom layer (:99-101) and α_tot of every angle in the sweep's storage type; B_0 into the store's order
+            const size_t nnat = nb ? (size_t)vrt_plan_native_alpha_count(me.plan_all.get(), (int64_t)nb) : 1;
+            if (f32) {
+                VRT_S(l.f_I0.alloc((size_t)g->up.n1 * nb));
+                VRT_S(l.f_native.alloc(nnat));
+                if (nb) {
+                    VRT_S(launch_gather_rows_f32(g->up.n1, (int64_t)nb, (int64_t)nb, g->up.d_order, l.d_B0, l.f_I0, st));
+                    VRT_S(l.sj.to_up_order(l.d_B0, l.f_B0, st));         // (rounded once; the staged doubles go)
+                }
+            } else {
+                VRT_S(l.d_I0.alloc((size_t)g->up.n1 * nb));
+                VRT_S(l.d_native.alloc(nnat));
+                if (nb) {
+                    VRT_S(launch_gather_rows(g->up.n1, (int64_t)nb, (int64_t)nb, g->up.d_order, l.d_B0, l.d_I0, st));
+                    VRT_S(l.sj.to_up_order(l.d_B0, st));
+                }
             }
 #undef VRT_S
             if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(VRT_ENODEVICE, "uploading the line case failed");
@@ -629,6 +651,21 @@ int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double
         *out = s.release();
         return VRT_OK;
     });
+}
+
+int vrt_multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const double *weights, vrt_multi_lambda **out)
+{
+    return multi_lambda_create(mm, lc, weights, out, false);
+}
+
+int vrt_multi_lambda_create_f32(vrt_multi *mm, const vrt_line_case *lc, const double *weights, vrt_multi_lambda **out)
+{
+    return multi_lambda_create(mm, lc, weights, out, true);
+}
+
+int vrt_multi_lambda_storage(const vrt_multi_lambda *s)
+{
+    return !s ? fail(VRT_EINVAL, "NULL session") : s->f32 ? 4 : 8;
 }
 
 int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
@@ -663,20 +700,26 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
             // γ and the line strength of the current populations (:72-75, line.jl:219-225), α_tot of every angle (:89-96)
             if (!rc) rc = l.line.terms(l.d_pops, st);
             if (!rc && nb > 0) {
-                rc = l.line.opacity(p, nb, l.l0, l.d_native, st);
+                void *alpha = s->f32 ? (void *)l.f_native.get() : (void *)l.d_native.get();
+                const void *I0 = s->f32 ? (const void *)l.f_I0.get() : (const void *)l.d_I0.get();
+                rc = l.line.opacity(p, nb, l.l0, alpha, st, s->f32);
                 // J_λ of this block (:84-111)
-                if (!rc) rc = execute_locked(p, sj.exec_args(l.d_native, VRT_ALPHA_ANGLE_NATIVE, l.d_I0, s->weights.data(), st));
+                if (!rc) rc = execute_locked(p, sj.exec_args(alpha, VRT_ALPHA_ANGLE_NATIVE, I0, s->weights.data(), st));
                 // S_new = (1 - ε) J + ε B_0 and this block's share of the criterion (:261-263, :325-349); in sweep order the
                 // update reads the old S where it writes the new
-                if (!rc && sj.form() == SourceStore::kPlanes)
+                if (!rc && sj.form() == SourceStore::kPlanesF32)      // (the roundings: include/voronoirt.h)
+                    rc = launch_lambda_update_native_f32(p, nb, sj.J_plane<float>(0), sj.J_plane<float>(1), l.f_B0, l.line.d_eps,
+                                                         sj.S_plane<float>(0), sj.S_plane<float>(1), l.d_scalars, st);
+                else if (!rc && sj.form() == SourceStore::kPlanes)
                     rc = launch_lambda_update_native(g, nb, sj.J_plane(0), sj.J_plane(1), l.d_B0, l.line.d_eps, sj.S_plane(0), sj.S_plane(1), l.d_scalars, st);
                 else if (!rc)
                     rc = launch_lambda_update(n, nb, nb, sj.J_rows(), l.d_B0, l.line.d_eps, sj.S_old(), sj.S_new(), l.d_scalars, st);
             }
             // this block's share of the six rate integrals (rates.jl:154-201), from J in rows or in its planes
             // (a member without wavelengths: an empty range of rows)
-            const RatesJ J = sj.form() == SourceStore::kPlanes ? RatesJ::from_planes(g, sj.J_plane(0), sj.J_plane(1))
-                                                               : RatesJ::from_rows(sj.J_rows(), std::max<int64_t>(nb, 1));
+            const RatesJ J = sj.form() == SourceStore::kPlanesF32 ? RatesJ::from_planes_f32(p, sj.J_plane<float>(0), sj.J_plane<float>(1))
+                             : sj.form() == SourceStore::kPlanes ? RatesJ::from_planes(g, sj.J_plane(0), sj.J_plane(1))
+                                                                 : RatesJ::from_rows(sj.J_rows(), std::max<int64_t>(nb, 1));
             if (!rc) rc = launch_rates_partial(l.line.rates_in(), J, l.l0, l.l1, l.d_shares, st);
             if (rc) { me.rc = rc; me.err = vrt_last_error(); }
         };
@@ -749,6 +792,8 @@ int vrt::multi_lambda_set_acceleration(vrt_multi_lambda *s, int order, int start
     if (!s) return fail(VRT_EINVAL, "NULL session");
     int rc = ng_check_settings(order, start, period);
     if (rc) return rc;
+    if (s->f32)                                 // the Ng kernels and NgRange: the [pair][pos][2] double layout
+        return fail(VRT_EINVAL, "vrt_multi_lambda_set_acceleration: not on a float-storage session (the Ng kernels work on double planes)");
     return guarded([&] {
         vrt_multi *mm = s->mm;
         std::lock_guard<std::mutex> lock(mm->mu);

@@ -342,7 +342,10 @@ k_rates_populations(RatesArgs ra)
 // the statistical equilibrium of every site itself (k_populations_from_shares).
 // shares[q][i], q = (bf1 ij, bf1 ji, bf2 ij, bf2 ji, bb ij, bb ji); J: this device's columns, (l1 - l0) per site
 // NATIVE: this device's columns of J as sweep-order plane sets (local wavelength l - l0), threads on up positions
-template <bool NATIVE>
+// T = float: those plane sets hold floats in the plan's pair blocks, npair = ceil((l1 - l0) / 2) pairs of them;
+// J = (float)(J_up + J_down) widened, as k_rates_populations<true, float> forms it -- everything after that is the same
+// arithmetic.  The padding wavelength of an odd l1 - l0 rides along in the last pair's load and is never handed out.
+template <bool NATIVE, typename T = double>
 __global__ void __launch_bounds__(256)
 k_rates_partial(RatesArgs ra, int64_t l0, int64_t l1, double *__restrict__ shares)
 {
@@ -360,12 +363,21 @@ k_rates_partial(RatesArgs ra, int64_t l0, int64_t l1, double *__restrict__ share
         if constexpr (!NATIVE) return Ji[l];
         const int64_t ll = l - l0, q = ll >> 1;
         if (q != pair_have) {                                   // J = J_up + J_down as k_combine_J forms it
-            const size_t o = (size_t)q * (size_t)n;
             double2 v = make_double2(0.0, 0.0);
+            if constexpr (sizeof(T) == 8) {
+            const size_t o = (size_t)q * (size_t)n;
             if (ra.J_up) v = reinterpret_cast<const double2 *>(ra.J_up)[o + (size_t)slot];
             if (ra.J_down) {
                 const double2 u = reinterpret_cast<const double2 *>(ra.J_down)[o + (size_t)pdn];
                 v.x = v.x + u.x; v.y = v.y + u.y;
+            }
+            } else {
+                if (ra.Jf_up) v = to_d2(reinterpret_cast<const float2 *>(ra.Jf_up)[pair_index((int)q, slot, n, ra.lgB, ra.npair)]);
+                if (ra.Jf_down) {
+                    const double2 u = to_d2(reinterpret_cast<const float2 *>(ra.Jf_down)[pair_index((int)q, pdn, n, ra.lgB, ra.npair)]);
+                    v.x = v.x + u.x; v.y = v.y + u.y;
+                }
+                v = to_d2(from_d2<float>(v));
             }
             pair_J = v;
             pair_have = q;
@@ -419,8 +431,9 @@ k_populations_from_shares(RatesArgs ra, const double *__restrict__ shares)
     populations_from_rates(ra, i, R);
 }
 
-// the kernels' arguments from the launches' named ones (vrt_line_case.h); R and the populations are the launch's to add
-static RatesArgs rates_args(const RatesIn &in, const RatesJ &J)
+// the kernels' arguments from the launches' named ones (vrt_line_case.h); R and the populations are the launch's to add.
+// nplane: the wavelengths the plane sets of J hold (all of the case, or a device's block)
+static RatesArgs rates_args(const RatesIn &in, const RatesJ &J, int64_t nplane)
 {
     RatesArgs ra{};
     ra.n = in.n; ra.nlam = in.nlam; ra.ld = J.ld;
@@ -435,7 +448,7 @@ static RatesArgs rates_args(const RatesIn &in, const RatesJ &J)
     ra.J_up = J.up; ra.J_down = J.down;
     ra.Jf_up = J.up_f; ra.Jf_down = J.down_f;
     if (J.plan) {
-        ra.lgB = native_lg(J.plan, true); ra.npair = (int)((in.nlam + 1) / 2);
+        ra.lgB = native_lg(J.plan, true); ra.npair = (int)((nplane + 1) / 2);
     }
     if (const vrt_grid *g = J.plan ? J.plan->g : J.grid) {          // the orders the plane sets are stored in
         ra.store_up = g->up.d_store; ra.rank_down = g->down.d_srank;
@@ -444,13 +457,16 @@ static RatesArgs rates_args(const RatesIn &in, const RatesJ &J)
 }
 
 // this device's share of the rate integrals: wavelengths [l0, l1) of the FULL wavelength arrays of `in`; J holds those
-// columns only (J.ld values per site, or sweep-order planes of l1 - l0 wavelengths)
+// columns only (J.ld values per site, or sweep-order planes of l1 - l0 wavelengths: doubles, or floats in the pair
+// blocks of J.plan's float layout)
 int launch_rates_partial(const RatesIn &in, const RatesJ &J, int64_t l0, int64_t l1, double *d_shares, hipStream_t st)
 {
-    const RatesArgs ra = rates_args(in, J);
+    const RatesArgs ra = rates_args(in, J, l1 - l0);
     const dim3 grid((unsigned)((in.n + 255) / 256));
     if (J.up || J.down)
         hipLaunchKernelGGL(k_rates_partial<true>, grid, dim3(256), 0, st, ra, l0, l1, d_shares);
+    else if (J.up_f || J.down_f)
+        hipLaunchKernelGGL((k_rates_partial<true, float>), grid, dim3(256), 0, st, ra, l0, l1, d_shares);
     else
         hipLaunchKernelGGL(k_rates_partial<false>, grid, dim3(256), 0, st, ra, l0, l1, d_shares);
     VRT_HIP_TRY(hipGetLastError());
@@ -473,7 +489,7 @@ int launch_populations_from_shares(int64_t n, const double *d_shares, const doub
 // or in a plan's float plane sets: J = (float)(J_up + J_down), widened
 int launch_rates_populations(const RatesIn &in, const RatesJ &J, double *d_R, double *d_populations, hipStream_t st)
 {
-    RatesArgs ra = rates_args(in, J);
+    RatesArgs ra = rates_args(in, J, in.nlam);
     ra.R = d_R; ra.populations = d_populations;
     const dim3 grid((unsigned)((in.n + 255) / 256));
     if (J.up || J.down)
