@@ -169,6 +169,36 @@ def test_kernel_variants_agree_bit_for_bit(grids, f32, monkeypatch):
         assert np.array_equal(got[name][1], got["lean"][1]), name
 
 
+def test_chained_item_sets_evicted_and_rebuilt_while_the_plan_lives(grids, monkeypatch):
+    """One plan on the chained launch, the wavelength count cycling through 1 .. 6 twice, a call that asks for J alternating
+    with one that asks for the intensities only: six (pair count, split, reduce) combinations, each requested again after
+    five others, over the plan's four item sets -- from the fifth call on every call evicts the least recently used set and
+    builds its own anew.  Every result equals, bit for bit, what a freshly created plan returns for the same inputs."""
+    hs, so = grids["voronoi"]
+    monkeypatch.setenv("VRT_PATH", "patches")
+    monkeypatch.setenv("VRT_PATCH_CHAIN", "1")
+    w, th, ph, nq = vrt.read_quadrature("ul7n12.dat")
+    make_plan = lambda: vrt.FormalPlan(hs, vrt.quadrature_directions(th, ph), 3, dirs=[1 if t > 90 else -1 for t in th])
+
+    def run(plan, nlam):
+        S, al, I0u, I0d = _case(so, nlam, 60 + nlam)
+        want_J = nlam % 2 == 1
+        J, I = plan.execute(S, al, weights=w, I0_up=I0u, I0_down=I0d, want_J=want_J, want_I=not want_J)
+        assert plan.last_path == "patches" and plan.last_launches == 1
+        return J if want_J else I
+
+    fresh = {}
+    for nlam in range(1, 7):
+        plan = make_plan()
+        fresh[nlam] = run(plan, nlam)
+        plan.close()
+    plan = make_plan()
+    for rep in range(12):
+        nlam = rep % 6 + 1
+        assert np.array_equal(run(plan, nlam), fresh[nlam]), rep
+    plan.close()
+
+
 @pytest.mark.parametrize("pair_block", [1, 4])
 @pytest.mark.parametrize("mode", ["site", "site_lam", "angle"])
 def test_fp32_quad_kernel_equals_pair_kernel(grids, pair_block, mode, monkeypatch):

@@ -12,7 +12,5 @@ bool patch_shape_exists(int K, int Q, int NT)
 }
 int64_t steps_max_layer(bool f32) { return f32 ? 18432 : 12288; }
 int chain_ctrl_words() { return 8 * 32 + 4; }
-bool patch_chain_possible(const vrt_plan *, int, bool) { return false; }
-bool patch_chain_dataflag(const vrt_plan *, int, bool) { return false; }
 int patch_chain_check(vrt_plan *) { return VRT_OK; }
 }  // namespace vrt

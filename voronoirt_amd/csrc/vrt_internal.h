@@ -294,7 +294,7 @@ struct Tuning {
                                   //   default for two and more wavelength pairs)
     int patch_chain = 2;          // VRT_PATCH_CHAIN: every layer inside ONE chained launch (k_patch_chain) instead of one launch
                                   //   per layer and direction: 0 never, 1 wherever it exists, 2 = auto: where a layer
-                                  //   alone cannot fill the chip (patch_chain_possible)
+                                  //   alone cannot fill the chip (patch_shape)
     int chain_pairs = 9;          // VRT_CHAIN_PAIRS: wavelength-pair blocks an item of the chained launch solves at most
     int chain_spin = 2048;        // VRT_CHAIN_SPIN: polls (x 1024) after which a waiting workgroup gives up (~2 s)
     int chain_dataflag = 2;       // VRT_CHAIN_DATAFLAG: the chained launch's intensities as their own flags: 0 never, 1 wherever
@@ -361,6 +361,55 @@ inline ExecArgs native_args(int64_t nlam, const void *S_up, const void *S_down, 
     x.native = true;
     return x;
 }
+
+// ---- the chained launch of the fused patch path: everything a plan keeps for it (vrt_patch.hip: launch_patch_chain) ----
+// One item set on the device: eight XCD queues of items and the dependency lists they point into, built for one
+// (pair count, block, split, reduce) combination (vrt_patch.cpp: build_chain_items).
+struct ChainItems {
+    int npair = -1, lgB = -1, nsplit = -1, reduce = -1;
+    DevBuf<int4> items;
+    DevBuf<int32_t> deps;
+    int q_off[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // queue x: items [q_off[x], q_off[x + 1])
+    bool segments_even = false;          // every queue holds the same number of items in every segment (build_chain_items)
+};
+struct ChainLaunch {
+    // The item sets this plan has run, most recently used first: sets[0] is the one in use.  A caller that alternates
+    // wavelength counts, or J and no J, switches between them instead of rebuilding (and freeing: a device synchronisation).
+    static constexpr size_t kSets = 4;
+    std::vector<ChainItems> sets;
+    DevWork<uint32_t> progress;          // one word per (split, patch); they only grow
+    bool progress_fresh = false;         //   allocated since the last launch: zero them on the launch stream
+    DevBuf<uint32_t> ctrl;               // queue heads and the give-up word (chain_ctrl_words() of them)
+    HostBuf<uint32_t> h_status;          // mapped host word: a launch gave up
+    uint32_t *d_status = nullptr;        //   its device address (borrowed from h_status)
+    DevBuf<char> d_args;                 // the launch's argument block (ChainDev)
+    HostBuf<char> h_args_pinned;         //   and its staging copy
+    std::vector<char> h_args;            //   what the device copy holds
+    Event args_ev;                       //   the last copy out of the staging copy
+    bool args_ev_valid = false;
+    uint32_t epoch = 0;                  // counts the launches; stale progress words compare as "behind"
+
+    // The control words, or NULL before the plan's first chained launch.
+    uint32_t *ctrl_words() const { return ctrl; }
+    // The set of this combination to the front: one of the sets, or -- after the least recently used of kSets has gone
+    // (freeing it waits for the device) -- what make(ChainItems &) builds.  A make that fails leaves the sets as they were.
+    template <typename Make>
+    int select(int npair, int lgB, int nsplit, bool reduce, Make make)
+    {
+        for (size_t c = 0; c < sets.size(); c++)
+            if (sets[c].npair == npair && sets[c].lgB == lgB && sets[c].nsplit == nsplit && sets[c].reduce == (reduce ? 1 : 0)) {
+                std::rotate(sets.begin(), sets.begin() + (long)c, sets.begin() + (long)c + 1);
+                return VRT_OK;
+            }
+        sets.reserve(kSets);
+        if (sets.size() == kSets) sets.pop_back();
+        ChainItems cs;
+        if (int rc = make(cs)) return rc;
+        cs.npair = npair; cs.lgB = lgB; cs.nsplit = nsplit; cs.reduce = reduce ? 1 : 0;
+        sets.insert(sets.begin(), std::move(cs));
+        return VRT_OK;
+    }
+};
 
 }  // namespace vrt
 
@@ -480,33 +529,7 @@ struct vrt_plan {
     std::vector<int2> h_patch_rec2;      // per patch: levels, active angle
     std::vector<int64_t> h_patch_dep_off;   // per patch: the patches (plan-wide indices) whose stored intensities it gathers
     std::vector<int32_t> h_patch_deps;      //   (vrt_patch.cpp: dep_list) -- what the chained launch waits on
-    // chained launch (vrt_patch.hip: k_patch_chain): items per XCD queue, dependency lists, progress words
-    vrt::DevBuf<int4> d_chain_items;
-    vrt::DevBuf<int32_t> d_chain_deps;
-    vrt::DevWork<uint32_t> d_chain_progress;
-    vrt::DevBuf<uint32_t> d_chain_ctrl;
-    vrt::HostBuf<uint32_t> h_chain_status;                            // mapped host word: a launch gave up
-    uint32_t *d_chain_status = nullptr;                               //   its device address (borrowed from h_chain_status)
-    vrt::DevBuf<char> d_chain_dev;                                    // the launch's argument block (ChainDev)
-    vrt::HostBuf<char> h_chain_dev_pinned;                            //   and its staging copy
-    std::vector<char> h_chain_dev;                                    //   what the device copy holds
-    vrt::Event chain_dev_ev;
-    bool chain_dev_ev_valid = false;
-    bool chain_progress_fresh = false;   // allocated since the last launch: zero it on the launch stream
-    int chain_q_off[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int chain_npair = -1, chain_lgB = -1, chain_nsplit = -1, chain_reduce = -1;
-    int64_t chain_items = 0;
-    // item sets of other (pair count, block, split, reduce) combinations this plan has run: a caller that alternates
-    // wavelength counts, or J and no J, switches between them instead of rebuilding (and freeing: a device synchronisation)
-    struct ChainSet {
-        int npair = -1, lgB = -1, nsplit = -1, reduce = -1;
-        vrt::DevBuf<int4> items;
-        vrt::DevBuf<int32_t> deps;
-        int q_off[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        int64_t n_items = 0;
-    };
-    std::vector<ChainSet> chain_cache;
-    uint32_t chain_epoch = 0;
+    vrt::ChainLaunch chain;              // chained launch (vrt_patch.hip: k_patch_chain)
     vrt::DevBuf<int4> d_patch_work;      // work lists of the launches: two int4 per slot (ensure_patch_work, PatchArgs::wrec)
     std::vector<int64_t> patch_work_off; //   [group][layer] offsets into it
     int patch_work_groups = 0;
@@ -679,9 +702,41 @@ inline int line_path_ok(const vrt_plan *p, const char *who)
 struct TileArgs;
 struct PatchReduce;
 bool patch_shape_exists(int K, int Q, int NT);
+// The kernel shape of a patch launch of `npair` wavelength pairs: THE place that decides it (vrt_patch.cpp).  Q_asked:
+// pairs a workgroup is asked to solve at a time (the plan's VRT_PATCH_Q; 1 for a launch that only reduces).
+// lgB: log2 of the pairs per block of the planes (native_lg); quad: fp32 storage, k_patch_quad, two neighbouring pairs of a
+// block per workgroup; lean: k_patch_lean, the 64-register form of the (1, 1, NT) kernel; lgS: log2 of the sibling
+// workgroups per pair block; Q: pairs a workgroup solves at a time; chain: every layer inside ONE chained launch
+// (k_patch_chain); chain_dataflag: ... with the intensities as their own flags (chain_data_wait).
+struct PatchShape {
+    int lgB = 0, quad = 0, lean = 0, lgS = 0, Q = 1;
+    bool chain = false, chain_dataflag = false;
+};
+PatchShape patch_shape(const vrt_plan *p, int npair, bool f32, int Q_asked);
+// The plan's patch index as the item builders read it (vrt_patch.cpp; nothing of it is copied).
+struct PatchIndex {
+    const std::vector<int32_t> &first;      // h_patch_first
+    const std::vector<int4> &rec;           // h_patch_rec
+    const std::vector<int2> &rec2;          // h_patch_rec2
+    const std::vector<int64_t> &dep_off;    // h_patch_dep_off
+    const std::vector<int32_t> &deps;       // h_patch_deps
+    const std::vector<int> &dir_of_active;
+    const std::vector<int64_t> *reduced[2]; // the directions' reduce_layers offsets (0 up, 1 down)
+    int max_layers;                         // tile_max_layers
+    int64_t n;
+};
+// Work lists of the per-layer launches, two int4 per slot (PatchArgs::wrec): `off` [group][layer] (+ end) in slots,
+// `padding` the slots that hold no patch.
+void build_patch_work(const PatchIndex &ix, int G, const std::vector<int32_t> &group_angles, const std::vector<int> &group_off,
+                      std::vector<int4> &work, std::vector<int64_t> &off, int64_t &padding);
+// Items of the chained launch, three int4 each, queue x at [set.q_off[x], set.q_off[x + 1]); `deps`: the patches' dependency
+// lists with those of the J_dir items behind them; set.segments_even: every queue holds the same number of items in every
+// (layer, direction) and J_dir segment.
+int build_chain_items(const PatchIndex &ix, int nblock, int nsplit, bool with_reduce, std::vector<int4> &items,
+                      std::vector<int32_t> &deps, ChainItems &set);
 int launch_patch_entries(vrt_plan *p, int a, int64_t first, int64_t count);
 int ensure_patch_work(vrt_plan *p, int G, const std::vector<int32_t> &group_angles, const std::vector<int> &group_off);
-int launch_patch_layer(vrt_plan *p, const TileArgs &ta, int npair, int layer, int group, int Q, hipStream_t st,
+int launch_patch_layer(vrt_plan *p, const TileArgs &ta, int npair, int layer, int group, const PatchShape &shape, hipStream_t st,
                        bool f32, const PatchReduce *reduce);
 // numbers per launch of the timeline: layer, stream group, gridDim.x, gridDim.y, work-list rows, splits, log2 siblings,
 // order, patch rows, reduction blocks, first block in the stamps, pair steps of an item
@@ -690,11 +745,9 @@ void patch_timeline_begin(vrt_plan *p);          // a sweep of per-layer launche
 int patch_timeline_read(vrt_plan *p, int64_t cap_launches, int64_t cap_blocks, int64_t *launches, uint64_t *stamps, int64_t *counts);
 // the grid of a per-layer launch and, with `blocks`, what each of its blocks does (vrt_patch_dispatch_map)
 int patch_dispatch_map(int order, int nrow, int nsplit, int lg_siblings, int64_t nred, int steps, int64_t *dims, int32_t *blocks);
-bool patch_chain_possible(const vrt_plan *p, int npair, bool f32);
-bool patch_chain_dataflag(const vrt_plan *p, int npair, bool f32);
-// ctrl_zeroed: the launch's control words (chain_ctrl_words() of them at p->d_chain_ctrl) were zeroed on `st` by the caller
-int launch_patch_chain(vrt_plan *p, const TileArgs &ta, int npair, hipStream_t st, bool f32, const PatchReduce *reduce,
-                       bool dataflag, bool ctrl_zeroed = false);
+// ctrl_zeroed: the launch's control words (chain_ctrl_words() of them at p->chain.ctrl_words()) were zeroed on `st` by the caller
+int launch_patch_chain(vrt_plan *p, const TileArgs &ta, int npair, const PatchShape &shape, hipStream_t st, bool f32,
+                       const PatchReduce *reduce, bool ctrl_zeroed = false);
 int chain_ctrl_words();
 int patch_chain_check(vrt_plan *p);
 

@@ -314,9 +314,8 @@ static size_t dcount(size_t elems) { return (elems * sizeof(T) + 7) / 8; }
 // (The layer paths run only with at least one active angle: choose_path sends A == 0 to the level path.)
 struct LayerRun {
     int path = 0;                    // 2 tiles, 3 steps, 4 patches
-    bool chain = false;              // patches: every layer inside ONE chained launch (vrt_patch.hip: k_patch_chain)
-    bool chain_df = false;           //   ... with the intensities as their own flags (chain_data_wait)
-    bool prep = false;               //   ... prepared by ONE k_chain_prepare launch
+    PatchShape shape;                // patches: the kernel shape of the execute's launches (patch_shape), chained or per layer
+    bool prep = false;               //   a chained launch with the intensities as their own flags, prepared by ONE k_chain_prepare launch
     bool prep_ctrl = false;          //   ... which also zeroed the launch's control words
     // storage layout: wavelength pairs side by side on the layer-step paths, plain planes on the
     // persistent tile path (sw_index); planes are padded to a whole number of blocks
@@ -370,10 +369,9 @@ static int prepare_inputs(vrt_plan *p, const ExecArgs &x, LayerRun &r)
     T *wI = reinterpret_cast<T *>(p->d_I.get());
     // chained launch with the intensities as their own flags (vrt_patch.hip: chain_data_wait): every plane is filled with
     // the NaN pattern first; the boundary kernel below then writes the boundary layer and the never-visited site's zero
-    r.chain_df = r.chain && patch_chain_dataflag(p, r.npair, kF32);
     // ... in ONE launch with the step's other preparations where those are a few microseconds each (k_chain_prepare)
-    r.prep = r.chain_df && !kF32 && r.lb == 2 && nlam <= 16 && alpha_mode != VRT_ALPHA_ANGLE_SITE_LAM;
-    if (r.chain_df && !r.prep) VRT_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p->d_I, (int)0x7FF87FF8u, (size_t)A * r.plane * sizeof(T) / 4, st));
+    r.prep = r.shape.chain_dataflag && !kF32 && r.lb == 2 && nlam <= 16 && alpha_mode != VRT_ALPHA_ANGLE_SITE_LAM;
+    if (r.shape.chain_dataflag && !r.prep) VRT_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p->d_I, (int)0x7FF87FF8u, (size_t)A * r.plane * sizeof(T) / 4, st));
     ChainPrep cp{};
     for (int d = 0; d < 2; d++)
         if (r.use_dir[d] && !x.native && (rc = p->ws_S[d].grow(dcount<T>(r.plane)))) return rc;
@@ -407,7 +405,7 @@ static int prepare_inputs(vrt_plan *p, const ExecArgs &x, LayerRun &r)
         bool forked = false;
         // (not for a chained step of a few wavelengths: its layout changes are a few microseconds each, less than the
         // event round trip that brings the second stream back)
-        const bool tiny = r.narrow && r.chain;
+        const bool tiny = r.narrow && r.shape.chain;
         for (int d = 0; d < 2 && !tiny; d++) {
             if (!r.use_dir[d]) continue;
             for (int gi = 1; gi < r.G; gi++) {
@@ -480,7 +478,7 @@ static int prepare_inputs(vrt_plan *p, const ExecArgs &x, LayerRun &r)
             cp.I = p->d_I;
             for (int a = 0; a < A; a++) cp.down[a] = p->dir_of_active[(size_t)a] > 0 ? 0 : 1;
             cp.fill = 0x7FF87FF8u;
-            cp.ctrl = p->d_chain_ctrl;                 // (exists from the plan's first chained launch on)
+            cp.ctrl = p->chain.ctrl_words();           // (exists from the plan's first chained launch on)
             cp.nctrl = chain_ctrl_words();
             r.prep_ctrl = cp.ctrl != nullptr;
             const unsigned blocks = (unsigned)cp.njob * cp.tblocks + (unsigned)A * cp.fblocks + (unsigned)((cp.nctrl + 255) / 256);
@@ -773,19 +771,17 @@ static int run_patch_layers(vrt_plan *p, const ExecArgs &x, LayerRun &r)
         for (int gi = 0; gi < G; gi++) {
             hipStream_t sg = gi == 0 ? st : p->step_stream[gi];     // group 0 on the caller's stream: one hardware queue less
             if (p->step_group_off[gi + 1] == p->step_group_off[gi]) continue;
-            // pairs per workgroup: the plan's Q, or 1 when that would leave half of every group empty
-            int Q = p->tune.patch_Q;
-            if (!patch_shape_exists(p->patch_K, Q, p->patch_NT) || (npair % Q != 0 && npair < 2 * Q)) Q = 1;
             PatchReduce red;
             const bool have_red = make_reduce(gi, layer - 1, false, red);
-            if ((rc = launch_patch_layer(p, r.ta, npair, layer, gi, Q, sg, kF32, have_red ? &red : nullptr))) return rc;
+            if ((rc = launch_patch_layer(p, r.ta, npair, layer, gi, r.shape, sg, kF32, have_red ? &red : nullptr))) return rc;
             r.launches += 1;
         }
-    // the last layers (and the never-visited site n - 1, whose intensity is 0)
+    // the last layers (and the never-visited site n - 1, whose intensity is 0): a launch that only reduces
+    const PatchShape tail = patch_shape(p, npair, kF32, 1);
     for (int gi = 0; gi < G; gi++) {
         PatchReduce red;
         if (!make_reduce(gi, 0, true, red)) continue;
-        if ((rc = launch_patch_layer(p, r.ta, npair, p->tile_max_layers + 1, gi, 1, gi == 0 ? st : p->step_stream[gi], kF32, &red)))
+        if ((rc = launch_patch_layer(p, r.ta, npair, p->tile_max_layers + 1, gi, tail, gi == 0 ? st : p->step_stream[gi], kF32, &red)))
             return rc;
         r.launches += 1;
     }
@@ -819,7 +815,7 @@ static int run_patch_chain(vrt_plan *p, const ExecArgs &x, LayerRun &r)
                 if ((p->dir_of_active[(size_t)a] > 0) == (d == 0)) red.angles[d][red.count[d]++] = a;
             r.fused_dir[d] = r.use_dir[d];
         }
-    if ((rc = launch_patch_chain(p, r.ta, r.npair, st, kF32, x.wants_J() ? &red : nullptr, r.chain_df, r.prep_ctrl))) return rc;
+    if ((rc = launch_patch_chain(p, r.ta, r.npair, r.shape, st, kF32, x.wants_J() ? &red : nullptr, r.prep_ctrl))) return rc;
     r.launches = 1;
     VRT_HIP_TRY(hipEventRecord(p->ev1, st));
     return VRT_OK;
@@ -898,7 +894,7 @@ static int execute_layers_t(vrt_plan *p, const ExecArgs &x, int path)
     r.nl_pad = r.lb == 1 ? nlam : (nlam + 1) / 2 * 2;
     r.npair = (int)(r.nl_pad / 2);
     r.plane = (size_t)r.nl_pad * (size_t)n;
-    r.chain = path == 4 && patch_chain_possible(p, r.npair, kF32);
+    if (path == 4) r.shape = patch_shape(p, r.npair, kF32, p->tune.patch_Q);
     r.use_dir[0] = p->n_up > 0;
     r.use_dir[1] = p->n_down > 0;
     // The angles are dealt (heaviest first) to a few internal streams that advance through
@@ -919,7 +915,7 @@ static int execute_layers_t(vrt_plan *p, const ExecArgs &x, int path)
     if (!rc)
         rc = path == 2 ? run_tiles(p, x, r)         // (fp64 storage only: choose_path never picks tiles for fp32)
            : path == 3 ? run_steps<T>(p, x, r)
-           : r.chain   ? run_patch_chain<T>(p, x, r)
+           : r.shape.chain ? run_patch_chain<T>(p, x, r)
                        : run_patch_layers<T>(p, x, r);
     if (rc) return rc;
     p->ev_valid = true;

@@ -387,4 +387,205 @@ void build_patch_schedule(const Direction &dir, bool ascending, int64_t n, int n
     }
 }
 
+// ---- the kernel shape of a patch launch ---------------------------------------------------------------------------------
+PatchShape patch_shape(const vrt_plan *p, int npair, bool f32, int Q_asked)
+{
+    PatchShape s;
+    s.lgB = native_lg(p, f32);
+    // fp32 storage: two neighbouring pairs of a block per workgroup as 16-byte accesses (k_patch_quad) when the pair
+    // count is even (every block then holds >= 2 pairs and every plane starts 16-byte aligned; else the pair kernel)
+    s.quad = (f32 && s.lgB >= 1 && p->patch_K == 1 && p->tune.patch_quad != 0 && (npair & 1) == 0) ? 1 : 0;
+    // pairs per workgroup: the plan's Q, or 1 when that would leave half of every group empty
+    s.Q = Q_asked;
+    if (s.quad || !patch_shape_exists(p->patch_K, s.Q, p->patch_NT) || (npair % s.Q != 0 && npair < 2 * s.Q)) s.Q = 1;
+    // (a lone pair per workgroup is a latency chain: the plain kernel's single gather phase is 3 % shorter there)
+    s.lean = (p->tune.patch_lean != 0 && p->patch_K == 1 && s.Q == 1 && !s.quad && npair >= 2) ? 1 : 0;
+    s.lgS = s.lgB - s.quad;
+    // The chained launch.  (1 << lgS) sibling workgroups per pair block exist only in the pair-block layouts
+    // (VRT_PAIR_BLOCK > 1 with doubles, an odd pair count with floats): those, the other kernel shapes and thread counts
+    // keep the per-layer launches.
+    const bool exists = p->patch_ok && p->tune.patch_chain != 0 && p->patch_K == 1 && p->patch_NT == 512 && s.lgS == 0 &&
+                        (f32 || p->tune.patch_lean != 0) &&            // VRT_PATCH_LEAN=0 asks for the 72-register kernel
+                        p->tile_max_layers < 65535 && p->A <= 63;      // item encoding
+    // auto: the chained launch where a layer alone cannot fill the chip -- its items cost ~5 us more than those of a
+    // per-layer launch (ticket, item record, the final drain before the progress word), which pays while the per-layer
+    // launches are bound by their 286-launch chain (C2 0.85 -> 0.54 ms, 1 M sites x 7 wavelengths 2.10 -> 1.73 ms)
+    // and not when the pair loops saturate the chip (C4 7.5 -> 8.4 ms).  Measured crossover:
+    // patches of a layer (both directions) x wavelength-pair blocks ~ 1400 (C4's grid, 217 patches per layer: 6 pairs chained 2.30 ms
+    // against 2.36 on per-layer launches, 7 pairs 2.59 against 2.53: profiles/r5/chain_crossover.txt).  fp32 storage: on request only.
+    const double per_layer = (double)p->n_patches / (double)std::max(1, p->tile_max_layers);
+    const bool pays = !f32 && per_layer * (double)(npair >> s.quad) <= 1400.0;         // (lgS == 0: npair >> quad pair blocks)
+    s.chain = exists && (p->tune.patch_chain == 1 || pays);
+    // the chained launch's hand-off by the data itself (chain_data_wait): fp64 pair kernel only; auto: one or two wavelength
+    // pairs -- the fill of the planes costs 16 bytes per (site, angle, pair) and step, the progress words two fabric round
+    // trips per LAYER (C2: 0.54 -> see DESIGN.md section 5)
+    s.chain_dataflag = s.chain && !f32 && p->tune.chain_dataflag != 0 && s.lgB == 0 && (p->tune.chain_dataflag == 1 || npair <= 2);
+    return s;
+}
+
+// ---- the item builders of the patch launches: host arithmetic over the plan's patch index --------------------------------
+namespace {
+
+// The patches of `layer` of the angles angles[0 .. count), sorted by (first owned position, place in `angles`).  Both launch
+// forms cut them into eight runs of equal count, run x = [run_cut(m, x), run_cut(m, x + 1)) of the m: XCD x (blocks x,
+// x + 8, ...) walks run x, so that neighbouring patches -- and the angles of one patch, which read the same S lines --
+// meet in one L2.
+using LayerItems = std::vector<std::pair<int64_t, int32_t>>;
+void sorted_layer_patches(const PatchIndex &ix, const int32_t *angles, int count, int layer, LayerItems &items)
+{
+    items.clear();
+    for (int j = 0; j < count; j++) {
+        const int32_t *first = ix.first.data() + (size_t)angles[j] * (size_t)(ix.max_layers + 2);
+        for (int32_t q = first[layer]; q < first[layer + 1]; q++) items.push_back({(int64_t)ix.rec[(size_t)q].z * 64 + j, q});
+    }
+    std::sort(items.begin(), items.end());
+}
+size_t run_cut(size_t m, int x) { return m * (size_t)x / 8; }
+
+}  // namespace
+
+// per (stream group, layer) the patches of the group's angles; slot t * 8 + x of a list holds item t of run x
+void build_patch_work(const PatchIndex &ix, int G, const std::vector<int32_t> &group_angles, const std::vector<int> &group_off,
+                      std::vector<int4> &work, std::vector<int64_t> &off, int64_t &padding)
+{
+    const int maxL = ix.max_layers;
+    work.clear();
+    padding = 0;
+    off.assign((size_t)G * (size_t)(maxL + 2) + 1, 0);
+    LayerItems items;
+    for (int gi = 0; gi < G; gi++)
+        for (int layer = 0; layer <= maxL + 1; layer++) {
+            off[(size_t)gi * (size_t)(maxL + 2) + (size_t)layer] = (int64_t)(work.size() / 2);
+            if (layer < 2 || layer > maxL) continue;
+            const int j0 = group_off[(size_t)gi];
+            sorted_layer_patches(ix, group_angles.data() + j0, group_off[(size_t)gi + 1] - j0, layer, items);
+            const size_t m = items.size();
+            if (m == 0) continue;
+            const size_t slots = (m + 7) / 8;
+            const size_t base = work.size();
+            work.resize(base + slots * 8 * 2, make_int4(0, 0, 0, 0));      // (entries = 0: padding)
+            padding += (int64_t)(slots * 8 - m);
+            for (int x = 0; x < 8; x++) {
+                const size_t b0 = run_cut(m, x), b1 = run_cut(m, x + 1);
+                for (size_t t = b0; t < b1; t++) {
+                    const int32_t q = items[t].second;
+                    const int2 r2 = ix.rec2[(size_t)q];
+                    const int d = ix.dir_of_active[(size_t)r2.y] > 0 ? 0 : 1;
+                    const std::vector<int64_t> &reduced = *ix.reduced[d];
+                    const size_t slot = base + 2 * ((t - b0) * 8 + (size_t)x);
+                    work[slot] = ix.rec[(size_t)q];
+                    work[slot + 1] = make_int4(r2.x, r2.y | (d << 16), (int)(reduced[(size_t)layer - 1] - 1), (int)(reduced[(size_t)layer] - 1));
+                }
+            }
+        }
+    off.back() = (int64_t)(work.size() / 2);
+}
+
+// Items of the chained launch for pair blocks dealt to `nsplit` items per patch (`nblock` blocks: the first
+// nblock % nsplit splits take one more, as split_blocks deals them): eight queues (XCD x takes queue x first), each in
+// layer order: the solve items of a layer's patches -- sorted and cut into 8 runs as the per-layer work lists are, the
+// splits of a patch next to each other -- followed by the J_dir items of the layer before (lagged: their dependencies
+// have then long been claimed).
+int build_chain_items(const PatchIndex &ix, int nblock, int nsplit, bool with_reduce, std::vector<int4> &all,
+                      std::vector<int32_t> &deps, ChainItems &out)
+{
+    const int maxL = ix.max_layers, A = (int)ix.dir_of_active.size();
+    const int64_t n = ix.n;
+    auto steps = [&](int s) { return nblock / nsplit + (s < nblock % nsplit ? 1 : 0); };
+    std::vector<int4> q[8];
+    std::vector<int32_t> rdeps;       // dependency lists of the J_dir items (patch ids), appended behind the patches' own
+    const size_t dep_base = ix.deps.size();
+    LayerItems items;
+    std::vector<int32_t> dir_angles[2];
+    for (int a = 0; a < A; a++) dir_angles[ix.dir_of_active[(size_t)a] > 0 ? 0 : 1].push_back(a);
+    // first owned position of each XCD run of (layer, direction): J_dir items follow the patches of their positions
+    std::vector<int32_t> run_start((size_t)(maxL + 2) * 2 * 8, 0);
+    auto first_of = [&](int a, int layer) { return ix.first[(size_t)a * (size_t)(maxL + 2) + (size_t)layer]; };
+    // Every queue holds the same number of items per (layer, direction) segment (padding items end at once), so the
+    // queues advance through the layers in step however the blocks of the grid are dealt to them: the blocks
+    // x, x + 8, ... take queue x in order, a workgroup only waits for items of EARLIER layers, and with static
+    // block -> XCD dealing (what the hardware does) the slots an XCD frees go to its own queue's next items.
+    // segments_even records that the padding did so: the static block -> item mapping relies on it.
+    out.segments_even = true;
+    auto push = [](std::vector<int4> &v, int4 a, int4 b, int4 c) { v.insert(v.end(), {a, b, c}); };      // an item: three int4
+    auto level_queues = [&]() {
+        size_t longest = 0;
+        for (int x = 0; x < 8; x++) longest = std::max(longest, q[x].size());
+        for (int x = 0; x < 8; x++) {
+            while (q[x].size() < longest) push(q[x], make_int4(0, 0, 0x40000000, 0), make_int4(0, 0, 0, 0), make_int4(0, 0, 0, 0));
+            out.segments_even = out.segments_even && q[x].size() == longest;
+        }
+    };
+    auto emit_reduce = [&](int layer) {
+        if (!with_reduce) return;
+        for (int d = 0; d < 2; d++) {
+            const std::vector<int64_t> &reduced = *ix.reduced[d];
+            const int Ld = (int)reduced.size() - 1;
+            if (dir_angles[d].empty() || layer < 1 || layer > Ld) continue;
+            const int64_t lo = reduced[(size_t)layer - 1] - 1;
+            const int64_t hi = layer == Ld ? n : reduced[(size_t)layer] - 1;      // + the never-visited last site (I = 0)
+            const int32_t *rs = run_start.data() + ((size_t)layer * 2 + (size_t)d) * 8;
+            constexpr int64_t R = 512;
+            for (int64_t clo = lo; clo < hi; clo += R) {
+                const int64_t chi = std::min(hi, clo + R);
+                int x = 0;
+                if (layer >= 2) { while (x < 7 && rs[x + 1] <= clo) x++; }
+                else x = (int)std::min<int64_t>(7, 8 * (clo - lo) / std::max<int64_t>(1, hi - lo));
+                const size_t d0 = rdeps.size();
+                if (layer >= 2)
+                    for (int a : dir_angles[d])
+                        for (int32_t pq = first_of(a, layer); pq < first_of(a, layer + 1); pq++) {
+                            const int4 &rec = ix.rec[(size_t)pq];
+                            if (rec.z < chi && rec.z + rec.w > clo) rdeps.push_back(pq);
+                        }
+                for (int s = 0; s < nsplit; s++) {
+                    push(q[x], make_int4((int)clo, (int)chi, (int)0x80000000u, (d << 6) | (s << 7)),
+                         make_int4((int)(dep_base + d0), (int)(rdeps.size() - d0), 0, steps(s)), make_int4(0, 0, 0, 0));
+                }
+            }
+        }
+    };
+    for (int layer = 2; layer <= maxL; layer++) {
+        for (int d = 0; d < 2; d++) {
+            const std::vector<int64_t> &reduced = *ix.reduced[d];
+            if (layer > (int)reduced.size() - 1) continue;
+            sorted_layer_patches(ix, dir_angles[d].data(), (int)dir_angles[d].size(), layer, items);
+            const size_t m = items.size();
+            int32_t *rs = run_start.data() + ((size_t)layer * 2 + (size_t)d) * 8;
+            for (int x = 0; x < 8; x++) {
+                const size_t t0 = run_cut(m, x), t1 = run_cut(m, x + 1);
+                rs[x] = t0 < m ? ix.rec[(size_t)items[t0].second].z : INT32_MAX;
+                for (size_t t = t0; t < t1; t++) {
+                    const int32_t pq = items[t].second;
+                    const int4 &rec = ix.rec[(size_t)pq];
+                    const int2 &rec2 = ix.rec2[(size_t)pq];
+                    const int64_t o0 = ix.dep_off[(size_t)pq], o1 = ix.dep_off[(size_t)pq + 1];
+                    for (int s = 0; s < nsplit; s++) {
+                        push(q[x], make_int4(rec.x, rec.z, rec.y | (rec.w << 10) | (rec2.x << 20), rec2.y | (d << 6) | (s << 7) | (layer << 16)),
+                             make_int4((int)o0, (int)(o1 - o0), pq, 0),
+                             make_int4((int)(reduced[(size_t)layer - 1] - 1), (int)(reduced[(size_t)layer] - 1), 0, 0));
+                    }
+                }
+            }
+            level_queues();
+        }
+        emit_reduce(layer - 1);
+        level_queues();
+    }
+    emit_reduce(maxL);
+    if (maxL < 1) emit_reduce(1);                         // (a grid of one layer: its J_dir items, once)
+    level_queues();
+    all.clear();
+    for (int x = 0; x < 8; x++) {
+        out.q_off[x] = (int)(all.size() / 3);
+        all.insert(all.end(), q[x].begin(), q[x].end());
+        std::vector<int4>().swap(q[x]);
+    }
+    out.q_off[8] = (int)(all.size() / 3);
+    if (all.size() / 3 >= (size_t)INT32_MAX) return fail(VRT_EINVAL, "too many items for the chained launch");
+    deps = ix.deps;
+    deps.insert(deps.end(), rdeps.begin(), rdeps.end());
+    return VRT_OK;
+}
+
 }  // namespace vrt

@@ -1354,9 +1354,13 @@ __device__ __forceinline__ void chain_reduce(const ChainDev &cd, const ChainDev 
 
 // ONE item per workgroup: the workgroup takes the next ticket of its queue when it starts and ends with its item --
 // the hardware's workgroup dispatcher is the loop (a persistent loop around the solver would have to keep its state
-// in scalar registers the solver needs: 28 of them spilled, and with them a vector register of the 64).  Tickets are
-// taken in order by workgroups that are running, so the argument about progress above holds whatever order the
-// blocks of the grid start in; the grid has exactly one block per item.
+// in scalar registers the solver needs: 28 of them spilled, and with them a vector register of the 64).  The grid has
+// exactly one block per item.  Tickets are taken in order by workgroups that are running, so under them the argument
+// about progress above holds whatever order the blocks of the grid start in.  The static mapping (static_items, the
+// default of the progress-word launches) ASSUMES that the blocks of an XCD start in increasing index: a block that
+// waits for an item whose block has not started would spin to its limit and the execute fail with a give-up.  The host
+// sets it only for an item set whose queues hold the same number of items in every (layer, direction) segment
+// (ChainItems::segments_even), so that "earlier layer" is "lower block index" in every queue.
 template <typename T, int AM, int NT, bool QUAD, int MODE>
 __device__ __forceinline__ void chain_item(const ChainDev &ca, const ChainDev *cd, uint32_t base, double2 *ptile)
 {
@@ -1549,51 +1553,20 @@ bool patch_shape_exists(int K, int Q, int NT)
     return false;
 }
 
-// work lists of the launches: per (stream group, layer) the patches of the group's angles, sorted by
-// (first owned position, angle) and cut into 8 runs of equal count; XCD x (blocks x, x + 8, ...)
-// walks run x, so that neighbouring patches -- and the angles of one patch, which read the same S
-// lines -- meet in one L2
+// the plan's patch index as the item builders read it
+static PatchIndex patch_index(const vrt_plan *p)
+{
+    return PatchIndex{p->h_patch_first, p->h_patch_rec, p->h_patch_rec2, p->h_patch_dep_off, p->h_patch_deps, p->dir_of_active,
+                      {&p->g->up.reduced, &p->g->down.reduced}, p->tile_max_layers, p->g->n};
+}
+
+// work lists of the per-layer launches (vrt_patch.cpp: build_patch_work), uploaded when the stream groups change
 int ensure_patch_work(vrt_plan *p, int G, const std::vector<int32_t> &group_angles, const std::vector<int> &group_off)
 {
     if (p->d_patch_work && p->patch_work_groups == G) return VRT_OK;
     p->d_patch_work.reset();
-    p->patch_work_padding = 0;
-    const int maxL = p->tile_max_layers;
-    std::vector<int4> work;           // two per slot (PatchArgs::wrec)
-    p->patch_work_off.assign((size_t)G * (size_t)(maxL + 2) + 1, 0);
-    std::vector<std::pair<int64_t, int32_t>> items;
-    for (int gi = 0; gi < G; gi++)
-        for (int layer = 0; layer <= maxL + 1; layer++) {
-            p->patch_work_off[(size_t)gi * (size_t)(maxL + 2) + (size_t)layer] = (int64_t)(work.size() / 2);
-            if (layer < 2 || layer > maxL) continue;
-            items.clear();
-            for (int j = group_off[(size_t)gi]; j < group_off[(size_t)gi + 1]; j++) {
-                const int a = group_angles[(size_t)j];
-                const int32_t *first = p->h_patch_first.data() + (size_t)a * (size_t)(maxL + 2);
-                for (int32_t q = first[layer]; q < first[layer + 1]; q++)
-                    items.push_back({(int64_t)p->h_patch_rec[(size_t)q].z * 64 + (j - group_off[(size_t)gi]), q});
-            }
-            std::sort(items.begin(), items.end());
-            const size_t m = items.size();
-            if (m == 0) continue;
-            const size_t slots = (m + 7) / 8;
-            const size_t base = work.size();
-            work.resize(base + slots * 8 * 2, make_int4(0, 0, 0, 0));      // (entries = 0: padding)
-            p->patch_work_padding += (int64_t)(slots * 8 - m);
-            for (int x = 0; x < 8; x++) {
-                const size_t b0 = m * (size_t)x / 8, b1 = m * (size_t)(x + 1) / 8;
-                for (size_t t = b0; t < b1; t++) {
-                    const int32_t q = items[t].second;
-                    const int2 r2 = p->h_patch_rec2[(size_t)q];
-                    const int d = p->dir_of_active[(size_t)r2.y] > 0 ? 0 : 1;
-                    const Direction &dir = d == 0 ? p->g->up : p->g->down;
-                    const size_t slot = base + 2 * ((t - b0) * 8 + (size_t)x);
-                    work[slot] = p->h_patch_rec[(size_t)q];
-                    work[slot + 1] = make_int4(r2.x, r2.y | (d << 16), (int)(dir.reduced[(size_t)layer - 1] - 1), (int)(dir.reduced[(size_t)layer] - 1));
-                }
-            }
-        }
-    p->patch_work_off.back() = (int64_t)(work.size() / 2);
+    std::vector<int4> work;
+    build_patch_work(patch_index(p), G, group_angles, group_off, work, p->patch_work_off, p->patch_work_padding);
     if (int rc = p->d_patch_work.alloc(work.size())) return rc;
     VRT_HIP_TRY(hipMemcpy(p->d_patch_work, work.data(), sizeof(int4) * work.size(), hipMemcpyHostToDevice));
     p->patch_work_groups = G;
@@ -1627,9 +1600,10 @@ static void size_reduce(PatchReduce &red, int npair, int lgB, int NT)
     red.nred = (red.nred + 7) / 8 * 8;
 }
 
-int launch_patch_layer(vrt_plan *p, const TileArgs &ta, int npair, int layer, int group, int Q, hipStream_t st,
+int launch_patch_layer(vrt_plan *p, const TileArgs &ta, int npair, int layer, int group, const PatchShape &shape, hipStream_t st,
                        bool f32, const PatchReduce *reduce)
 {
+    const int Q = shape.Q, lgS = shape.lgS;
     // workgroups per launch when VRT_PATCH_TARGET fixes them (0: the split is chosen below)
     const int target_wgs = p->tune.patch_target;
     const int maxL = p->tile_max_layers;
@@ -1638,20 +1612,15 @@ int launch_patch_layer(vrt_plan *p, const TileArgs &ta, int npair, int layer, in
     PatchArgs pa;
     if (reduce) {
         pa.red = *reduce;
-        size_reduce(pa.red, npair, native_lg(p, f32), p->patch_NT);
+        size_reduce(pa.red, npair, shape.lgB, p->patch_NT);
     }
     if (w1 <= w0 && pa.red.nred == 0) return VRT_OK;
     pa.ta = ta;
     pa.npair = npair;
     pa.layer = layer;
-    pa.lgB = native_lg(p, f32);
-    // fp32 storage: two neighbouring pairs of a block per workgroup as 16-byte accesses (k_patch_quad) when the pair
-    // count is even (every block then holds >= 2 pairs and every plane starts 16-byte aligned; else the pair kernel)
-    pa.quad = (f32 && pa.lgB >= 1 && p->patch_K == 1 && p->tune.patch_quad != 0 && (npair & 1) == 0) ? 1 : 0;
-    if (pa.quad) Q = 1;
-    // (a lone pair per workgroup is a latency chain: the plain kernel's single gather phase is 3 % shorter there)
-    pa.lean = (p->tune.patch_lean != 0 && p->patch_K == 1 && Q == 1 && !pa.quad && npair >= 2) ? 1 : 0;
-    const int lgS = pa.lgB - pa.quad;                          // log2 of the sibling workgroups per block
+    pa.lgB = shape.lgB;
+    pa.quad = shape.quad;
+    pa.lean = shape.lean;
     pa.Q = Q;
     pa.nsplit = 1;
     pa.ngrp = 1 << lgS;
@@ -1796,37 +1765,6 @@ int patch_dispatch_map(int order, int nrow, int nsplit, int lg_siblings, int64_t
 }
 
 // ---- the chained launch: host side ------------------------------------------------------------------------------------
-// (1 << lgS) sibling workgroups per pair block exist only in the pair-block layouts (VRT_PAIR_BLOCK > 1 with doubles,
-// an odd pair count with floats): those, the other kernel shapes and thread counts keep the per-layer launches.
-bool patch_chain_possible(const vrt_plan *p, int npair, bool f32)
-{
-    if (!p->patch_ok || p->tune.patch_chain == 0 || p->patch_K != 1 || p->patch_NT != 512) return false;
-    const int lgB = native_lg(p, f32);
-    const bool quad = f32 && lgB >= 1 && p->tune.patch_quad != 0 && (npair & 1) == 0;
-    if (lgB - (quad ? 1 : 0) != 0) return false;
-    if (!f32 && p->tune.patch_lean == 0) return false;             // VRT_PATCH_LEAN=0 asks for the 72-register kernel
-    if (p->tile_max_layers >= 65535 || p->A > 63) return false;    // item encoding
-    if (p->tune.patch_chain == 1) return true;
-    // auto: the chained launch where a layer alone cannot fill the chip -- its items cost ~5 us more than those of a
-    // per-layer launch (ticket, item record, the final drain before the progress word), which pays while the per-layer
-    // launches are bound by their 286-launch chain (C2 0.85 -> 0.54 ms, 1 M sites x 7 wavelengths 2.10 -> 1.73 ms)
-    // and not when the pair loops saturate the chip (C4 7.5 -> 8.4 ms).  Measured crossover:
-    // patches of a layer (both directions) x wavelength-pair blocks ~ 1400 (C4's grid, 217 patches per layer: 6 pairs chained 2.30 ms
-    // against 2.36 on per-layer launches, 7 pairs 2.59 against 2.53: profiles/r5/chain_crossover.txt).  fp32 storage: on request only.
-    if (f32) return false;
-    const double per_layer = (double)p->n_patches / (double)std::max(1, p->tile_max_layers);
-    return per_layer * (double)pair_block_count(npair, lgB) <= 1400.0;
-}
-
-// the chained launch's hand-off by the data itself (chain_data_wait): fp64 pair kernel only; auto: one or two wavelength
-// pairs -- the fill of the planes costs 16 bytes per (site, angle, pair) and step, the progress words two fabric round
-// trips per LAYER (C2: 0.54 -> see DESIGN.md section 5)
-bool patch_chain_dataflag(const vrt_plan *p, int npair, bool f32)
-{
-    if (f32 || p->tune.chain_dataflag == 0 || native_lg(p, f32) != 0) return false;
-    return p->tune.chain_dataflag == 1 || npair <= 2;
-}
-
 // Items per patch: enough that ONE layer (both directions) offers about as many items as the chip holds workgroups
 // (1024: a workgroup takes its item in queue order and, if the item's layer is not ready, waits for it while holding
 // its place -- items of a later layer started early are slots spent waiting), and at most VRT_CHAIN_PAIRS blocks each
@@ -1836,184 +1774,6 @@ static int chain_nsplit(const vrt_plan *p, int nblock)
     const double per_layer = (double)p->n_patches / (double)std::max(1, p->tile_max_layers);
     const int fill = (int)std::ceil(1024.0 / std::max(1.0, per_layer));
     return std::max(1, std::min({std::max((nblock + per - 1) / per, fill), nblock, 511}));
-}
-
-// Items of the chained launch for `npair` pairs in blocks of 2^lgB, `nsplit` items per patch: eight queues (XCD x
-// takes queue x first), each in layer order: the solve items of a layer's patches -- sorted by (first owned position,
-// angle) and cut into 8 runs as the per-layer work lists are, the splits of a patch next to each other -- followed
-// by the J_dir items of the layer before (lagged: their dependencies have then long been claimed).
-static int ensure_patch_chain(vrt_plan *p, int npair, int lgB, int nsplit, bool with_reduce)
-{
-    if (p->d_chain_items && p->chain_npair == npair && p->chain_lgB == lgB && p->chain_nsplit == nsplit &&
-        p->chain_reduce == (with_reduce ? 1 : 0))
-        return VRT_OK;
-    {
-        // the set in use goes to the plan's small cache, a cached set of this combination comes back (no rebuild, no free)
-        auto stash = [&]() {
-            if (!p->d_chain_items) return;
-            vrt_plan::ChainSet cs;
-            cs.npair = p->chain_npair; cs.lgB = p->chain_lgB; cs.nsplit = p->chain_nsplit; cs.reduce = p->chain_reduce;
-            cs.items = std::move(p->d_chain_items); cs.deps = std::move(p->d_chain_deps); cs.n_items = p->chain_items;
-            for (int x = 0; x <= 8; x++) cs.q_off[x] = p->chain_q_off[x];
-            p->chain_npair = -1;
-            p->chain_cache.push_back(std::move(cs));
-            if (p->chain_cache.size() > 3)                    // (the oldest goes: freeing it waits for the device)
-                p->chain_cache.erase(p->chain_cache.begin());
-        };
-        for (size_t c = 0; c < p->chain_cache.size(); c++) {
-            if (p->chain_cache[c].npair == npair && p->chain_cache[c].lgB == lgB && p->chain_cache[c].nsplit == nsplit &&
-                p->chain_cache[c].reduce == (with_reduce ? 1 : 0)) {
-                vrt_plan::ChainSet cs = std::move(p->chain_cache[c]);
-                p->chain_cache.erase(p->chain_cache.begin() + (long)c);
-                stash();
-                p->d_chain_items = std::move(cs.items); p->d_chain_deps = std::move(cs.deps); p->chain_items = cs.n_items;
-                for (int x = 0; x <= 8; x++) p->chain_q_off[x] = cs.q_off[x];
-                p->chain_npair = npair; p->chain_lgB = lgB; p->chain_nsplit = nsplit; p->chain_reduce = with_reduce ? 1 : 0;
-                const size_t words = (size_t)nsplit * (size_t)std::max<int64_t>(p->n_patches, 1);
-                if (words <= p->d_chain_progress.cap) return VRT_OK;
-                break;                                       // (cannot happen: the progress words only grow; rebuild below)
-            }
-        }
-        stash();
-    }
-    const vrt_grid *g = p->g;
-    const int maxL = p->tile_max_layers, A = p->A;
-    const int64_t n = g->n, n_patches = p->n_patches;
-    const int nblock = pair_block_count(npair, lgB);
-    if ((int64_t)nsplit * n_patches >= ((int64_t)1 << 31)) return fail(VRT_EINVAL, "too many (split, patch) progress words");
-    PatchArgs sp;                     // set_split / split_blocks read nsplit and Q only
-    sp.nsplit = nsplit;
-    sp.Q = 1;
-    set_split(sp, nblock);
-    std::vector<int> steps((size_t)nsplit);
-    for (int s = 0; s < nsplit; s++) {
-        int b0, b1;
-        split_blocks(sp, s, nblock, b0, b1);
-        steps[(size_t)s] = b1 - b0;
-    }
-    std::vector<int4> q[8];
-    std::vector<int32_t> rdeps;       // dependency lists of the J_dir items (patch ids), appended behind the patches' own
-    const size_t dep_base = p->h_patch_deps.size();
-    std::vector<std::pair<int64_t, int32_t>> items;
-    std::vector<int> dir_angles[2];
-    for (int a = 0; a < A; a++) dir_angles[p->dir_of_active[(size_t)a] > 0 ? 0 : 1].push_back(a);
-    // first owned position of each XCD run of (layer, direction): J_dir items follow the patches of their positions
-    std::vector<int32_t> run_start((size_t)(maxL + 2) * 2 * 8, 0);
-    auto first_of = [&](int a, int layer) { return p->h_patch_first[(size_t)a * (size_t)(maxL + 2) + (size_t)layer]; };
-    // Every queue holds the same number of items per (layer, direction) segment (padding items end at once), so the
-    // queues advance through the layers in step however the blocks of the grid are dealt to them: the blocks
-    // x, x + 8, ... take queue x in order, a workgroup only waits for items of EARLIER layers, and with static
-    // block -> XCD dealing (what the hardware does) the slots an XCD frees go to its own queue's next items.
-    auto level_queues = [&]() {
-        size_t longest = 0;
-        for (int x = 0; x < 8; x++) longest = std::max(longest, q[x].size());
-        for (int x = 0; x < 8; x++)
-            while (q[x].size() < longest) {
-                q[x].push_back(make_int4(0, 0, 0x40000000, 0));
-                q[x].push_back(make_int4(0, 0, 0, 0));
-                q[x].push_back(make_int4(0, 0, 0, 0));
-            }
-    };
-    auto emit_reduce = [&](int layer) {
-        if (!with_reduce) return;
-        for (int d = 0; d < 2; d++) {
-            const Direction &dir = d == 0 ? g->up : g->down;
-            const int Ld = (int)dir.reduced.size() - 1;
-            if (dir_angles[d].empty() || layer < 1 || layer > Ld) continue;
-            const int64_t lo = dir.reduced[(size_t)layer - 1] - 1;
-            const int64_t hi = layer == Ld ? n : dir.reduced[(size_t)layer] - 1;      // + the never-visited last site (I = 0)
-            const int32_t *rs = run_start.data() + ((size_t)layer * 2 + (size_t)d) * 8;
-            constexpr int64_t R = 512;
-            for (int64_t clo = lo; clo < hi; clo += R) {
-                const int64_t chi = std::min(hi, clo + R);
-                int x = 0;
-                if (layer >= 2) { while (x < 7 && rs[x + 1] <= clo) x++; }
-                else x = (int)std::min<int64_t>(7, 8 * (clo - lo) / std::max<int64_t>(1, hi - lo));
-                const size_t d0 = rdeps.size();
-                if (layer >= 2)
-                    for (int a : dir_angles[d])
-                        for (int32_t pq = first_of(a, layer); pq < first_of(a, layer + 1); pq++) {
-                            const int4 &rec = p->h_patch_rec[(size_t)pq];
-                            if (rec.z < chi && rec.z + rec.w > clo) rdeps.push_back(pq);
-                        }
-                for (int s = 0; s < nsplit; s++) {
-                    q[x].push_back(make_int4((int)clo, (int)chi, (int)0x80000000u, (d << 6) | (s << 7)));
-                    q[x].push_back(make_int4((int)(dep_base + d0), (int)(rdeps.size() - d0), 0, steps[(size_t)s]));
-                    q[x].push_back(make_int4(0, 0, 0, 0));
-                }
-            }
-        }
-    };
-    for (int layer = 2; layer <= maxL; layer++) {
-        for (int d = 0; d < 2; d++) {
-            const Direction &dir = d == 0 ? g->up : g->down;
-            if (layer > (int)dir.reduced.size() - 1) continue;
-            items.clear();
-            for (size_t j = 0; j < dir_angles[d].size(); j++) {
-                const int a = dir_angles[d][j];
-                for (int32_t pq = first_of(a, layer); pq < first_of(a, layer + 1); pq++)
-                    items.push_back({(int64_t)p->h_patch_rec[(size_t)pq].z * 64 + (int64_t)j, pq});
-            }
-            std::sort(items.begin(), items.end());
-            const size_t m = items.size();
-            int32_t *rs = run_start.data() + ((size_t)layer * 2 + (size_t)d) * 8;
-            for (int x = 0; x < 8; x++) {
-                const size_t t0 = m * (size_t)x / 8, t1 = m * (size_t)(x + 1) / 8;
-                rs[x] = t0 < m ? p->h_patch_rec[(size_t)items[t0].second].z : INT32_MAX;
-                for (size_t t = t0; t < t1; t++) {
-                    const int32_t pq = items[t].second;
-                    const int4 &rec = p->h_patch_rec[(size_t)pq];
-                    const int2 &rec2 = p->h_patch_rec2[(size_t)pq];
-                    const int64_t o0 = p->h_patch_dep_off[(size_t)pq], o1 = p->h_patch_dep_off[(size_t)pq + 1];
-                    for (int s = 0; s < nsplit; s++) {
-                        q[x].push_back(make_int4(rec.x, rec.z, rec.y | (rec.w << 10) | (rec2.x << 20),
-                                                 rec2.y | (d << 6) | (s << 7) | (layer << 16)));
-                        q[x].push_back(make_int4((int)o0, (int)(o1 - o0), pq, 0));
-                        q[x].push_back(make_int4((int)(dir.reduced[(size_t)layer - 1] - 1), (int)(dir.reduced[(size_t)layer] - 1), 0, 0));
-                    }
-                }
-            }
-            level_queues();
-        }
-        emit_reduce(layer - 1);
-        level_queues();
-    }
-    emit_reduce(maxL);
-    if (maxL < 1) emit_reduce(1);                         // (a grid of one layer: its J_dir items, once)
-    level_queues();
-    std::vector<int4> all;
-    for (int x = 0; x < 8; x++) {
-        p->chain_q_off[x] = (int)(all.size() / 3);
-        all.insert(all.end(), q[x].begin(), q[x].end());
-        std::vector<int4>().swap(q[x]);
-    }
-    p->chain_q_off[8] = (int)(all.size() / 3);
-    if (all.size() / 3 >= (size_t)INT32_MAX) return fail(VRT_EINVAL, "too many items for the chained launch");
-    std::vector<int32_t> deps(p->h_patch_deps);
-    deps.insert(deps.end(), rdeps.begin(), rdeps.end());
-    int rc;                                              // (the set in use was stashed above: nothing to free here)
-    if ((rc = p->d_chain_items.alloc(all.size())) || (rc = p->d_chain_deps.alloc(deps.size()))) return rc;
-    VRT_HIP_TRY(hipMemcpy(p->d_chain_items, all.data(), sizeof(int4) * all.size(), hipMemcpyHostToDevice));
-    VRT_HIP_TRY(hipMemcpy(p->d_chain_deps, deps.data(), sizeof(int32_t) * deps.size(), hipMemcpyHostToDevice));
-    const size_t words = (size_t)nsplit * (size_t)std::max<int64_t>(n_patches, 1);
-    if (words > p->d_chain_progress.cap) {
-        if ((rc = p->d_chain_progress.grow(words))) return rc;
-        p->chain_progress_fresh = true;
-    }
-    // (epochs keep counting across item sets: a word of an earlier set compares as "behind" whatever it meant there;
-    // freshly allocated words are zeroed on the launch stream, ahead of the first launch that polls them)
-    if (!p->d_chain_ctrl && (rc = p->d_chain_ctrl.alloc(kChainAbortWord + 4))) return rc;
-    if (!p->h_chain_status) {
-        if ((rc = p->h_chain_status.alloc(16, hipHostMallocMapped))) return rc;
-        *p->h_chain_status = 0;
-        VRT_HIP_TRY(hipHostGetDevicePointer((void **)&p->d_chain_status, p->h_chain_status.p, 0));
-    }
-    p->chain_npair = npair;
-    p->chain_lgB = lgB;
-    p->chain_nsplit = nsplit;
-    p->chain_reduce = with_reduce ? 1 : 0;
-    p->chain_items = (int64_t)(all.size() / 3);
-    return VRT_OK;
 }
 
 template <typename T, int AM>
@@ -2040,18 +1800,45 @@ static int launch_chain_mode(bool quad, bool dataflag, int64_t items, size_t lds
 // angle lists [0] = up, [1] = down and J_dir planes)
 int chain_ctrl_words() { return kChainAbortWord + 4; }
 
-int launch_patch_chain(vrt_plan *p, const TileArgs &ta, int npair, hipStream_t st, bool f32, const PatchReduce *reduce, bool dataflag,
-                       bool ctrl_zeroed)
+int launch_patch_chain(vrt_plan *p, const TileArgs &ta, int npair, const PatchShape &shape, hipStream_t st, bool f32,
+                       const PatchReduce *reduce, bool ctrl_zeroed)
 {
     // a give-up of an EARLIER chained launch of this plan (its results were wrong) is reported here at the latest
     if (int rc0 = patch_chain_check(p)) return rc0;
-    const int lgB = native_lg(p, f32);
-    const bool quad = f32 && lgB >= 1 && p->tune.patch_quad != 0 && (npair & 1) == 0;
-    const int nblock = pair_block_count(npair, lgB);
-    const int nsplit = chain_nsplit(p, nblock);
-    int rc;
-    if ((rc = ensure_patch_chain(p, npair, lgB, nsplit, reduce != nullptr))) return rc;
-    if (p->chain_items == 0) return VRT_OK;
+    const bool quad = shape.quad != 0, dataflag = shape.chain_dataflag;
+    const int nsplit = chain_nsplit(p, pair_block_count(npair, shape.lgB));
+    // the item set of (npair, lgB, nsplit, reduce) in front of the plan's sets: built (vrt_patch.cpp: build_chain_items) and
+    // uploaded when it is not among them
+    ChainLaunch &cl = p->chain;
+    int rc = cl.select(npair, shape.lgB, nsplit, reduce != nullptr, [&](ChainItems &cs) -> int {
+        if ((int64_t)nsplit * p->n_patches >= ((int64_t)1 << 31)) return fail(VRT_EINVAL, "too many (split, patch) progress words");
+        std::vector<int4> items;
+        std::vector<int32_t> deps;
+        int rcb;
+        if ((rcb = build_chain_items(patch_index(p), pair_block_count(npair, shape.lgB), nsplit, reduce != nullptr, items, deps, cs))) return rcb;
+        if ((rcb = cs.items.alloc(items.size())) || (rcb = cs.deps.alloc(deps.size()))) return rcb;
+        VRT_HIP_TRY(hipMemcpy(cs.items, items.data(), sizeof(int4) * items.size(), hipMemcpyHostToDevice));
+        VRT_HIP_TRY(hipMemcpy(cs.deps, deps.data(), sizeof(int32_t) * deps.size(), hipMemcpyHostToDevice));
+        return VRT_OK;
+    });
+    if (rc) return rc;
+    // progress words for it (epochs keep counting across item sets: a word of an earlier set compares as "behind" whatever
+    // it meant there; freshly allocated words are zeroed on the launch stream, ahead of the first launch that polls them.
+    // A set that comes back finds its words there unless a growth has failed since: they only grow), and the launch's
+    // control and status words
+    const size_t words = (size_t)nsplit * (size_t)std::max<int64_t>(p->n_patches, 1);
+    if (words > cl.progress.cap) {
+        if ((rc = cl.progress.grow(words))) return rc;
+        cl.progress_fresh = true;
+    }
+    if (!cl.ctrl && (rc = cl.ctrl.alloc(kChainAbortWord + 4))) return rc;
+    if (!cl.h_status) {
+        if ((rc = cl.h_status.alloc(16, hipHostMallocMapped))) return rc;
+        *cl.h_status = 0;
+        VRT_HIP_TRY(hipHostGetDevicePointer((void **)&cl.d_status, cl.h_status.p, 0));
+    }
+    const ChainItems &set = cl.sets.front();
+    if (set.q_off[8] == 0) return VRT_OK;
     static_assert(std::is_trivially_copyable<ChainDev>::value, "ChainDev is uploaded byte for byte");
     ChainDev h;
     std::memset(&h, 0, sizeof(h));
@@ -2063,59 +1850,55 @@ int launch_patch_chain(vrt_plan *p, const TileArgs &ta, int npair, hipStream_t s
     h.e_vis = p->e_vis; h.e_loc = p->e_loc;
     h.e_w1 = p->e_w1; h.e_w2 = p->e_w2; h.e_r1 = p->e_r1; h.e_r2 = p->e_r2;
     if (reduce) h.red = *reduce;
-    h.items = p->d_chain_items;
-    for (int x = 0; x <= 8; x++) h.q_off[x] = p->chain_q_off[x];
-    h.deps = p->d_chain_deps;
-    h.progress = p->d_chain_progress;
-    h.ctrl = p->d_chain_ctrl;
-    h.host_status = p->d_chain_status;
+    h.items = set.items;
+    for (int x = 0; x <= 8; x++) h.q_off[x] = set.q_off[x];
+    h.deps = set.deps;
+    h.progress = cl.progress;
+    h.ctrl = cl.ctrl;
+    h.host_status = cl.d_status;
     h.n_patches = p->n_patches;
     h.spin_limit = (uint32_t)std::max(1, p->tune.chain_spin) << 10;
-    {
-        // (static only while every queue holds the same number of items: ensure_patch_chain pads them so)
-        bool even = true;
-        for (int x = 1; x < 8; x++) even = even && (p->chain_q_off[x + 1] - p->chain_q_off[x]) == (p->chain_q_off[1] - p->chain_q_off[0]);
-        h.static_items = (!dataflag && even && p->tune.chain_static != 0) ? 1 : 0;
-    }
+    // (static only while every queue holds the same number of items in every segment: build_chain_items pads them so)
+    h.static_items = (!dataflag && set.segments_even && p->tune.chain_static != 0) ? 1 : 0;
     h.dbg = kDiag ? p->tune.debug_flags : 0;
     // the argument block travels only when it has changed (stream-ordered: behind the launches that read the old one)
-    if (!p->d_chain_dev && (rc = p->d_chain_dev.alloc(sizeof(ChainDev)))) return rc;
-    if (p->h_chain_dev.size() != sizeof(ChainDev) || std::memcmp(p->h_chain_dev.data(), &h, sizeof(h)) != 0) {
-        if (!p->h_chain_dev_pinned && (rc = p->h_chain_dev_pinned.alloc(sizeof(ChainDev)))) return rc;
+    if (!cl.d_args && (rc = cl.d_args.alloc(sizeof(ChainDev)))) return rc;
+    if (cl.h_args.size() != sizeof(ChainDev) || std::memcmp(cl.h_args.data(), &h, sizeof(h)) != 0) {
+        if (!cl.h_args_pinned && (rc = cl.h_args_pinned.alloc(sizeof(ChainDev)))) return rc;
         // the pinned staging copy may still be in flight for an earlier launch: wait for that copy only
-        if (p->chain_dev_ev_valid) VRT_HIP_TRY(hipEventSynchronize(p->chain_dev_ev));
-        std::memcpy(p->h_chain_dev_pinned, &h, sizeof(h));
-        VRT_HIP_TRY(hipMemcpyAsync(p->d_chain_dev, p->h_chain_dev_pinned, sizeof(h), hipMemcpyHostToDevice, st));
-        if (!p->chain_dev_ev && (rc = p->chain_dev_ev.create(hipEventDisableTiming))) return rc;
-        VRT_HIP_TRY(hipEventRecord(p->chain_dev_ev, st));
-        p->chain_dev_ev_valid = true;
-        p->h_chain_dev.assign(reinterpret_cast<const char *>(&h), reinterpret_cast<const char *>(&h) + sizeof(h));
+        if (cl.args_ev_valid) VRT_HIP_TRY(hipEventSynchronize(cl.args_ev));
+        std::memcpy(cl.h_args_pinned, &h, sizeof(h));
+        VRT_HIP_TRY(hipMemcpyAsync(cl.d_args, cl.h_args_pinned, sizeof(h), hipMemcpyHostToDevice, st));
+        if (!cl.args_ev && (rc = cl.args_ev.create(hipEventDisableTiming))) return rc;
+        VRT_HIP_TRY(hipEventRecord(cl.args_ev, st));
+        cl.args_ev_valid = true;
+        cl.h_args.assign(reinterpret_cast<const char *>(&h), reinterpret_cast<const char *>(&h) + sizeof(h));
     }
-    // epochs count the launches of this item set; stale words compare as "behind" while epochs differ by < 2^22
-    p->chain_epoch++;
-    if ((p->chain_epoch & 0x3FFFFFu) == 0u || p->chain_progress_fresh) {
+    // epochs count the launches of this plan; stale words compare as "behind" while epochs differ by < 2^22
+    cl.epoch++;
+    if ((cl.epoch & 0x3FFFFFu) == 0u || cl.progress_fresh) {
         // stream-ordered (the plan's streams do not synchronise with the null stream)
-        VRT_HIP_TRY(hipMemsetAsync(p->d_chain_progress, 0, sizeof(uint32_t) * p->d_chain_progress.cap, st));
-        if ((p->chain_epoch & 0x3FFFFFu) == 0u) p->chain_epoch = 1;
-        p->chain_progress_fresh = false;
+        VRT_HIP_TRY(hipMemsetAsync(cl.progress, 0, sizeof(uint32_t) * cl.progress.cap, st));
+        if ((cl.epoch & 0x3FFFFFu) == 0u) cl.epoch = 1;
+        cl.progress_fresh = false;
     }
-    const uint32_t base = p->chain_epoch << 8;
-    if (!ctrl_zeroed) VRT_HIP_TRY(hipMemsetAsync(p->d_chain_ctrl, 0, sizeof(uint32_t) * (kChainAbortWord + 4), st));
+    const uint32_t base = cl.epoch << 8;
+    if (!ctrl_zeroed) VRT_HIP_TRY(hipMemsetAsync(cl.ctrl, 0, sizeof(uint32_t) * (kChainAbortWord + 4), st));
     const size_t lds = (size_t)(quad ? 2 : 1) * (size_t)(p->patch_cap + 1) * sizeof(double2) + (size_t)p->patch_cap * (4 * sizeof(double) + 5 * sizeof(int32_t)) +
                        sizeof(uint32_t) * (kCtlWords + 64 + kChainDepLds);
-    const ChainDev *cd = reinterpret_cast<const ChainDev *>(p->d_chain_dev.p);
+    const ChainDev *cd = reinterpret_cast<const ChainDev *>(cl.d_args.p);
     switch (ta.alpha_mode) {
     case VRT_ALPHA_SITE:
-        rc = f32 ? launch_chain_mode<float, VRT_ALPHA_SITE>(quad, dataflag, p->chain_items, lds, st, h, cd, base)
-                 : launch_chain_mode<double, VRT_ALPHA_SITE>(quad, dataflag, p->chain_items, lds, st, h, cd, base);
+        rc = f32 ? launch_chain_mode<float, VRT_ALPHA_SITE>(quad, dataflag, set.q_off[8], lds, st, h, cd, base)
+                 : launch_chain_mode<double, VRT_ALPHA_SITE>(quad, dataflag, set.q_off[8], lds, st, h, cd, base);
         break;
     case VRT_ALPHA_SITE_LAM:
-        rc = f32 ? launch_chain_mode<float, VRT_ALPHA_SITE_LAM>(quad, dataflag, p->chain_items, lds, st, h, cd, base)
-                 : launch_chain_mode<double, VRT_ALPHA_SITE_LAM>(quad, dataflag, p->chain_items, lds, st, h, cd, base);
+        rc = f32 ? launch_chain_mode<float, VRT_ALPHA_SITE_LAM>(quad, dataflag, set.q_off[8], lds, st, h, cd, base)
+                 : launch_chain_mode<double, VRT_ALPHA_SITE_LAM>(quad, dataflag, set.q_off[8], lds, st, h, cd, base);
         break;
     default:
-        rc = f32 ? launch_chain_mode<float, VRT_ALPHA_ANGLE_SITE_LAM>(quad, dataflag, p->chain_items, lds, st, h, cd, base)
-                 : launch_chain_mode<double, VRT_ALPHA_ANGLE_SITE_LAM>(quad, dataflag, p->chain_items, lds, st, h, cd, base);
+        rc = f32 ? launch_chain_mode<float, VRT_ALPHA_ANGLE_SITE_LAM>(quad, dataflag, set.q_off[8], lds, st, h, cd, base)
+                 : launch_chain_mode<double, VRT_ALPHA_ANGLE_SITE_LAM>(quad, dataflag, set.q_off[8], lds, st, h, cd, base);
         break;
     }
     if (rc) return rc;
@@ -2126,13 +1909,14 @@ int launch_patch_chain(vrt_plan *p, const TileArgs &ta, int npair, hipStream_t s
 // VRT_OK, or the give-up of a chained launch that has finished since the last check (introspection; no synchronisation)
 int patch_chain_check(vrt_plan *p)
 {
-    if (p->h_chain_status && *p->h_chain_status) {
-        volatile uint32_t *hs = p->h_chain_status;
+    uint32_t *status = p->chain.h_status;
+    if (status && *status) {
+        volatile uint32_t *hs = status;
         char msg[384];
         std::snprintf(msg, sizeof(msg),
                       "a chained patch launch gave up waiting for a dependency of item %u (the results of that execute are "
                       "invalid; VRT_PATCH_CHAIN=0 selects the per-layer launches)", hs[1]);
-        *p->h_chain_status = 0;
+        *status = 0;
         return fail(VRT_ENODEVICE, msg);
     }
     return VRT_OK;
