@@ -935,8 +935,8 @@ int vrt_multi_lambda_set_state(vrt_multi_lambda *s, const double *S, const doubl
  *   never calls it allocates and runs nothing extra); the update is vrt_continuum_ali_update_dev's kernel.
  *   The setter is named _select_operator here, not _set_operator.
  * Out of scope: the regular-grid continuum session with the exact diagonal of its n_sweeps-sweep operator (its Λ* is the
- * one-sweep diagonal, a lower bound of it), the line sessions (their update goes through the rate equations and needs a
- * preconditioned statistical equilibrium), and any multi-device form. */
+ * one-sweep diagonal, a lower bound of it), the line sessions other than the Voronoi one on one device with double
+ * storage (that one has its own operator entries, below: vrt_lambda_use_operator), and any multi-device form. */
 typedef struct vrt_continuum vrt_continuum;
 typedef struct vrt_regular_continuum vrt_regular_continuum;
 typedef struct vrt_continuum_case {
@@ -984,6 +984,50 @@ int vrt_regular_lambda_diagonal(vrt_regular *r, int64_t n_angles, const double *
 int vrt_regular_continuum_select_operator(vrt_regular_continuum *s, int op);
 int vrt_regular_continuum_get_operator(vrt_regular_continuum *s, int *op,
                                        double *diag /* (nlam, n) Julia dims, may be NULL */);
+
+/* ---- accelerated Λ-iteration of the LINE session on a Voronoi plan ---------------------------------------------------
+ * The reference multiplies every collisional rate by BOOST = 2.0e9 "instead of developing operator splitting"
+ * (src/rates.jl:1-3): with physical rates ε is 1e-4 ... 1e-6 at line centre and the plain loop does not converge in any
+ * affordable number of iterates.  Here the line session takes the same diagonal operator as the continuum session.
+ * In the line loop α_tot differs per angle (v_los = dot(velocity, -k)) and follows the populations, so Λ* is formed every
+ * iterate from the α the sweep of that iterate reads:
+ *     Λ*[i,l] = Σ_a w_a upd(a,i) (W_1(a,i) b(Δτ_1) + W_2(a,i) b(Δτ_2)),   Δτ_r = R_r(a,i) (α_a[i,l] + α_a[up_r(a,i),l]) / 2
+ * upd, the tables, b, the angle order and the operation order are those of vrt_plan_lambda_diagonal_dev above; α_a is
+ * angle a's block of the native per-angle buffer (VRT_ALPHA_ANGLE_NATIVE: vrt_line_opacity_dev,
+ * vrt_plan_alpha_to_native_dev).  With one angle's weight alone the result is vrt_plan_lambda_diagonal_dev's bit for bit.
+ * vrt_line_lambda_diagonal_dev: Λ* into d_diag, (nlam, n) with leading dimension ld, padding columns neither read nor
+ *   written; any pair block of the plan, an odd nlam included; weights_host[n_angles]; asynchronous on `stream`; no
+ *   floating-point atomics: the same inputs give the same bits.  VRT_EINVAL for NULL pointers, nlam < 1, ld < nlam
+ *   (before the device is touched) and for a plan with an inactive (θ = 90) angle, as vrt_lambda_create.
+ * vrt_lambda_ali_update_dev / vrt_lambda_ali_update_native_dev: the contracts of vrt_lambda_update_dev and
+ *   vrt_lambda_update_native_dev with Λ* beside the other arrays (rows; the UP-order plane set of vrt_plan_to_native_dev).
+ *   Per entry, with t = 1 - ε[site]:
+ *     num = t (J - Λ* S_old) + ε B,    den = 1 - t Λ*,    S_new = num / den
+ *   An entry whose den is not > 0 -- only ε = 0 in a cell whose Λ* rounds to 1 -- takes the plain update
+ *   (1 - ε) J + ε B and is counted in *fallback_entries: any per-entry choice of a local operator leaves the fixed point
+ *   where it is, and S is updated in place, so the update never refuses half way.  The criterion is unchanged:
+ *   max |1 - S_old/S_new|, NaN -> NaN.
+ * vrt_lambda_use_operator: op 0 = plain Λ-iteration (the default), 1 = the diagonal operator; callable between any two
+ *   iterates.  On: one array of the size of S beside the session; every vrt_lambda_iterate then forms Λ* after the
+ *   opacity, on the session's stream, and runs the ALI update; the fallback count comes home with the criterion's words.
+ *   Rates and populations come from the iterate's J as before, Ng acceleration sees the ALI S as it sees the plain one.
+ *   Λ* is a pure function of the populations and is kept over no iterate: vrt_lambda_set_state resumes an ALI run bit for
+ *   bit with nothing more to save (select the operator in the new session).  Off: the array is freed.  A session that never
+ *   calls it runs the launches it ran before.  VRT_EINVAL, nothing changed: NULL, op outside {0, 1}, a float-storage
+ *   session (vrt_lambda_storage == 4).  (The setter is named _use_operator: the names _set_operator and _select_operator
+ *   stay free on the line and multi-device sessions, as the host tests of the continuum operators require.)
+ * vrt_lambda_get_operator: *op and -- may be NULL -- the fallback count of the last iterate.
+ * Out of scope: the float-storage, the multi-device and the regular-grid line sessions. */
+int vrt_line_lambda_diagonal_dev(vrt_plan *p, int64_t nlam, const double *d_alpha_native, const double *weights_host,
+                                 int64_t ld, double *d_diag, void *stream);
+int vrt_lambda_ali_update_dev(vrt_grid *g, int64_t nlam, int64_t ld, const double *dJ, const double *dB,
+                              const double *deps, const double *d_diag, const double *dS_old, double *dS_new,
+                              double *max_rel_change, int64_t *fallback_entries, void *stream);
+int vrt_lambda_ali_update_native_dev(vrt_grid *g, int64_t nlam, const double *dJ_up, const double *dJ_down,
+                                     const double *dB_up, const double *deps, const double *d_diag_up, double *dS_up,
+                                     double *dS_down, double *max_rel_change, int64_t *fallback_entries, void *stream);
+int vrt_lambda_use_operator(vrt_lambda *s, int op);
+int vrt_lambda_get_operator(const vrt_lambda *s, int *op, int64_t *fallback_entries_last_iterate);
 
 /* ---- emergent spectra: opacity / source function, top-plane intensity, tau = 1 heights ------------------------------
  * The last step of a reference study (write_top_intensity, write_tau_unity and plotter, src/plot_utils.jl:61-140,

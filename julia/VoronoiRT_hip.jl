@@ -292,11 +292,19 @@ vrt_multi_lambda_create_f32 when several devices are listed: every device then h
 arithmetic stays Float64; the patch path only -- the library refuses anything else, there is no Float64 fallback).  J_new
 and S_new come back as Float64 arrays of Float32 values; `ng` is an error with it (the Ng kernels work on Float64 planes).
 Unrun as well.
+`operator = :diagonal`: accelerated Λ-iteration with the diagonal operator Λ* formed on the device from every iterate's
+α_tot (vrt_lambda_use_operator): the same fixed point in fewer iterates where ε is small -- what src/rates.jl:1-3 sets
+BOOST for.  One device and Float64 storage only (an error with `storage = :f32` or several devices); composes with `ng`,
+`S0` and `populations0`.  Unrun as well.
 """
 function Λ(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, line::HydrogenicLine, quadrature::String, DATA::String;
-           ng::Union{Nothing,Tuple{Int,Int}}=nothing, S0=nothing, populations0=nothing, storage::Symbol=:f64)
+           ng::Union{Nothing,Tuple{Int,Int}}=nothing, S0=nothing, populations0=nothing, storage::Symbol=:f64,
+           operator::Union{Nothing,Symbol}=nothing)
     storage in (:f64, :f32) || error("storage must be :f64 or :f32")
     storage == :f32 && ng !== nothing && error("Ng acceleration is not available with storage = :f32")
+    operator in (nothing, :diagonal) || error("operator must be nothing or :diagonal")
+    operator !== nothing && storage == :f32 && error("operator = :diagonal is not available with storage = :f32")
+    operator !== nothing && length(vrt_devices()) > 1 && error("operator = :diagonal is not available on several devices")
     println("---Iterating---")
     LTE_pops = VoronoiRT.LTE_populations(line, sites)
     populations = copy(LTE_pops)
@@ -365,6 +373,7 @@ function Λ(ϵ::AbstractFloat, maxiter::Integer, sites::VoronoiSites, line::Hydr
         check(ccall(dlsym(multi ? libvrt_multi_accel_handle() : libvrt_handle(), f_accel), Cint, (Ptr{Cvoid}, Cint, Cint, Cint),
                     ses[], 2, ng[1], ng[2]))
     end
+    operator === :diagonal && check(ccall(dlsym(libvrt_handle(), :vrt_lambda_use_operator), Cint, (Ptr{Cvoid}, Cint), ses[], 1))
     set_state(multi ? :vrt_multi_lambda_set_state : :vrt_lambda_set_state, ses[], plain_array(S0, I_unit, (nλ, n)),
               plain_array(populations0, u"m^-3", (n, 3)))
     ng_applied = Ref{Cint}(0); ng_coeffs = zeros(2)

@@ -20,6 +20,12 @@ are those of the Voronoi session and are not timed again.
 
     python tools/ali_probe.py [--a 37 --c 90] [--nlam 1] [--reps 40] [--blocks 3] [--plain-only] [--json out.json]
     python tools/ali_probe.py --regular [--shape 215 128 128] [--nlam 1] [--reps 10] [--blocks 3] [--plain-only]
+
+`--line`: the LINE session (vrt_lambda_use_operator).  Iterate counts and wall times of Lambda_voronoi_host to --tol on
+a hard two-level case (the atom of tests/test_physics.py's _lambda_case with ε x 1e-2 and the line strength x 10; 21 line +
+2 x 6 continuum wavelengths): plain, operator="diagonal", and that with ng=(4, 4); at most --maxiter iterates each.
+
+    python tools/ali_probe.py --line [--a 59 --c 143] [--tol 1e-3] [--maxiter 400] [--plain-only]
 """
 import argparse
 import ctypes
@@ -48,6 +54,9 @@ ap.add_argument("--limit", type=int, default=240, help="seconds after which the 
 ap.add_argument("--json", default="")
 ap.add_argument("--regular", action="store_true", help="the raster session instead of the Voronoi one")
 ap.add_argument("--shape", type=int, nargs=3, default=[215, 128, 128], help="--regular: nz nx ny interior points")
+ap.add_argument("--line", action="store_true", help="the line session: iterate counts plain / diagonal / diagonal + Ng")
+ap.add_argument("--tol", type=float, default=1e-3, help="--line: the criterion the runs stop at")
+ap.add_argument("--maxiter", type=int, default=400, help="--line: iterates per run at most")
 args = ap.parse_args()
 signal.alarm(args.limit)
 
@@ -128,8 +137,54 @@ def finish(res):
             f.write("\n")
 
 
+def line_probe():
+    C0, H_PLANCK, K_B = 2.99792458e8, 6.62607015e-34, 1.380649e-23
+    pos, nbr, bounds = synth.bcc_grid(args.a, args.c, seed=2022)
+    sites = vrt.VoronoiSites(pos, nbr, bounds, device=0)
+    n = sites.n
+    rng = np.random.default_rng(11)
+    nbb, nbf, lambda0 = 21, 6, 121.567e-9
+    q = np.concatenate([-np.geomspace(600, 0.05, nbb // 2), [0.0], np.geomspace(0.05, 600, nbb // 2)])
+    lam = np.concatenate([lambda0 * (1 + q * 2.5e3 / C0), np.linspace(22.8e-9, 91.17e-9, nbf), np.linspace(91.2e-9, 364.7e-9, nbf)])
+    nlam = lam.size
+    z = (pos[:, 0] - bounds[0]) / (bounds[1] - bounds[0])
+    box = bounds[1] - bounds[0]
+    T = 6e3 + 6e3 * z + 200 * rng.random(n)
+    doppler = lambda0 / C0 * np.sqrt(2 * K_B * T / 1.6735575e-27)
+    n1 = 1e16 * np.exp(-3 * z) * (1 + 0.1 * rng.random(n))
+    lte = np.stack([n1, n1 * 1e-3 * (1 + rng.random(n)), n1 * 1e-2 * (1 + rng.random(n))])
+    Cm = 10 ** rng.uniform(-1, 1, (n, 3, 3))
+    for d in range(3):
+        Cm[:, d, d] = 0.0
+    case = vrt.LineCase(
+        lam=lam, blocks=np.array([0, nbb, nbb, nbb + nbf, nbb + nbf, nbb + 2 * nbf], dtype=np.int64), lambda0=lambda0, c0=C0,
+        velocity=rng.normal(0, 3e3, (n, 3)), doppler=doppler, gamma_static=4.702e8 + 10 ** rng.uniform(7, 8.7, n),
+        gamma_unsold=10 ** rng.uniform(-8.5, -7.5, n), alpha_cont=0.05 / box * np.exp(-2 * z),
+        eps=1e-2 * 10 ** rng.uniform(-2.5, -0.5, n), temperature=T, atom_density=lte.sum(axis=0),
+        B0=(1.0 + z)[:, None] * (1 + 0.05 * rng.random((n, nlam))), lte=lte, C=Cm, planck2=2.0 * (lambda0 / lam) ** 5,
+        sigma_bf1=1e-21 * (lam[21:27] / lam[26]) ** 3, sigma_bf2=2e-21 * (lam[27:33] / lam[32]) ** 3,
+        strength_const=10.0 * 60.0 / box * doppler.mean() / n1.mean(), Bij=1.0, Bji=0.25, sigma_bb_const=2e-32,
+        hc_over_kB=H_PLANCK * C0 / K_B, pref_ij=2e36, pref_ji=2e37)
+    res = {"n": n, "nlam": nlam, "tol": args.tol, "maxiter": args.maxiter}
+    runs = [("plain", {})] if args.plain_only else [("plain", {}), ("diagonal", {"operator": "diagonal"}),
+                                                    ("diagonal_ng", {"operator": "diagonal", "ng": (4, 4)})]
+    for name, kw in runs:
+        t0 = time.perf_counter()
+        out = vrt.Lambda_voronoi_host(args.tol, args.maxiter, sites, case, "ul7n12.dat", **kw)
+        hist = out[3]
+        res[name] = {"iterates": len(hist), "last": hist[-1], "converged": bool(hist[-1] <= args.tol),
+                     "wall_s": time.perf_counter() - t0, "history_head": hist[:40], "S_min": float(out[1].min()),
+                     "S_max": float(out[1].max()), "populations_min": float(out[2].min())}
+        print(f"{name}: {len(hist)} iterates, criterion {hist[-1]:.4g}, {res[name]['wall_s']:.1f} s in all", file=sys.stderr)
+    sites.close()
+    return res
+
+
 if args.regular:
     finish(regular_probe())
+    sys.exit(0)
+if args.line:
+    finish(line_probe())
     sys.exit(0)
 
 pos, nbr, bounds = synth.bcc_grid(args.a, args.c, seed=2022)

@@ -8,11 +8,14 @@
 HIP-event time of each call on the launch stream + the bytes each one has to move (its own floor).
 Synthetic inputs with physical magnitudes (tests/test_physics.py's Ly-α-like atom).
 
-    python tools/iteration_breakdown.py [--a 59 --c 143] [--reps 5] [--dtype f32]
+    python tools/iteration_breakdown.py [--a 59 --c 143] [--reps 5] [--dtype f32] [--operator diagonal]
 
 --dtype f32: the same table for the float-storage loop (S, J, B, I_0 and α held as float, arithmetic fp64), which exists
 in sweep order only: vrt_line_opacity_dev_f32 -> vrt_plan_execute_native_dev_f32 -> vrt_lambda_update_native_dev_f32 ->
 vrt_rates_populations_native_dev_f32, then the session (vrt_lambda_create_f32 + vrt_lambda_iterate).
+--operator diagonal: the accelerated iteration (fp64 only) -- vrt_line_lambda_diagonal_dev (Λ* from the α just written) and
+vrt_lambda_ali_update_native_dev take their places in the sweep-order table, and the session runs with
+vrt_lambda_use_operator(s, 1) beside the plain one.
 Every time is the median of --reps single timed calls after a warm-up call, with the smallest and largest beside it.
 """
 import argparse
@@ -33,6 +36,7 @@ ap.add_argument("--a", type=int, default=59)
 ap.add_argument("--c", type=int, default=143)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--dtype", default="f64", choices=["f64", "f32"], help="what S, J, B, I_0 and α are stored as")
+ap.add_argument("--operator", default="none", choices=["none", "diagonal"], help="diagonal: the ALI iteration beside the plain one (f64)")
 ap.add_argument("--velocity", default="noise", choices=["noise", "smooth"],
                 help="noise: independent normal 8 km/s per SITE (the field of every earlier round: neighbouring sites of a wave fall into "
                      "different regions of the Voigt function's four-region form); smooth: 8 km/s of large-scale flow (a few Fourier modes of "
@@ -142,7 +146,7 @@ def table(steps, what):
     return total
 
 
-def session_iterate_ms(create, label):
+def session_iterate_ms(create, label, operator=0):
     """the library-owned session at all 91 wavelengths: wall time of vrt_lambda_iterate, median (min ... max) of args.reps"""
     import ctypes
     import time
@@ -151,6 +155,8 @@ def session_iterate_ms(create, label):
     lc, keep = case.c_struct()
     h = ctypes.c_void_p()
     api.check(getattr(L, create)(plan_h._h, ctypes.byref(lc), api._d(api._f64(wq)), ctypes.byref(h)))
+    if operator:
+        api.check(L.vrt_lambda_use_operator(h, operator))
     d = ctypes.c_double()
     api.check(L.vrt_lambda_iterate(h, ctypes.byref(d)))
     ms = []
@@ -275,6 +281,33 @@ steps_n = (
 )
 table(steps_n, f"path {plan.last_path}; S and J in sweep order: no layout change inside the loop")
 assert all(torch.isfinite(x).all() for x in Jn) and torch.isfinite(d_pop).all()
+
+if args.operator == "diagonal":
+    # ---- the accelerated iteration: Λ* of this iterate's α (rows; the session writes the up-order plane set itself), the ALI update
+    L_rows = torch.zeros((n, nbb), device=dev, dtype=torch.float64)
+    L_up = torch.zeros(cnt, device=dev, dtype=torch.float64)
+
+    def diagonal():
+        plan.line_lambda_diagonal_dev(nbb, native.data_ptr(), w, nbb, L_rows.data_ptr(), stream=st)
+
+    def update_ali():
+        api.lambda_ali_update_native_dev(sites, nbb, Jn[0].data_ptr(), Jn[1].data_ptr(), B_up.data_ptr(), eps_site.data_ptr(),
+                                         L_up.data_ptr(), S_nat[0].data_ptr(), S_nat[1].data_ptr(), stream=st)
+
+    diagonal()
+    plan.to_native_dev(nbb, nbb, L_rows.data_ptr(), L_up.data_ptr(), 0, stream=st)
+    # Λ*: the native α of every angle once (the centre pairs), the six table rows per (angle, site) once per group of 4 pairs,
+    # Λ* out; the two upwind pairs per (angle, site, pair) are gathers of the same buffer: up to twice the α bytes again
+    groups = ((nbb + 1) // 2 + 3) // 4
+    diag_bytes = 8.0 * A * n * (nbb + 1) + 40.0 * A * n * groups + 8.0 * n * nbb
+    table((("vrt_line_opacity_dev", opacity, 8.0 * (A * n * (nbb + 1) + 8 * n)),
+           ("vrt_line_lambda_diagonal_dev", diagonal, diag_bytes),
+           ("vrt_plan_execute_native_dev", solve_native, float(n) * A * nbb * (40.0 + 40.0 / nbb)),
+           ("vrt_lambda_ali_update_native_dev", update_ali, 8.0 * (7 * n * nbb + n)),           # ... and Λ* in
+           ("vrt_rates_populations_native", rates_native, 8.0 * (2 * n * nlam_all + 30 * n))),
+          f"path {plan.last_path}; operator diagonal, S and J in sweep order")
+    print(f"  (vrt_line_lambda_diagonal_dev with its gathers counted as traffic: {diag_bytes / 1e9 + 16.0 * A * n * (nbb + 1) / 1e9:.2f} GB)")
+    assert torch.isfinite(L_rows).all() and float(L_rows.min()) >= 0.0 and float(L_rows.max()) < 1.0
 plan.close()
 
 # ---- the same from HOST arrays (what the Julia shim calls): PCIe-inclusive wall times ------------------
@@ -311,4 +344,6 @@ Jl, Sl, pl, hist = vrt.Lambda_voronoi_host(0.0, 4, sites, case, "ul7n12.dat")
 dt = time.perf_counter() - t0
 print(f"vrt_lambda_create + 4 x vrt_lambda_iterate + vrt_lambda_get ({nlam_all} wavelengths): {dt * 1e3:.0f} ms in all; history {hist}")
 session_iterate_ms("vrt_lambda_create", "vrt_lambda_iterate")
+if args.operator == "diagonal":
+    session_iterate_ms("vrt_lambda_create", "vrt_lambda_iterate, operator diagonal", operator=1)
 sites.close()

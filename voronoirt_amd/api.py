@@ -374,6 +374,12 @@ class FormalPlan:
         check(fn(self._h, lam.size, _d(lam), float(lambda0), float(c0), d_velocity, d_doppler, d_gamma, d_line_strength,
                  d_alpha_cont, d_alpha_native, stream or None))
 
+    def line_lambda_diagonal_dev(self, nlam: int, d_alpha_native: int, weights, ld: int, d_diag: int, stream: int = 0) -> None:
+        """Λ* of the line Λ-iteration (`vrt_line_lambda_diagonal_dev`) from this plan's native per-angle α (what
+        `line_opacity_dev` or `alpha_to_native_dev` wrote) into d_diag, (n, ld) rows; asynchronous on `stream`."""
+        check(_lib.load().vrt_line_lambda_diagonal_dev(self._h, nlam, d_alpha_native, _d(_f64(weights)), ld, d_diag,
+                                                       stream or None))
+
     def set_option(self, name: str, value) -> None:
         """Tuning option of this plan (`vrt_plan_set_option`); results never depend on it."""
         if getattr(self, "_h", None):
@@ -1242,6 +1248,28 @@ def lambda_update_native_dev(sites: VoronoiSites, nlam: int, dJ_up: int, dJ_down
     return out.value
 
 
+def lambda_ali_update_dev(sites: VoronoiSites, nlam: int, ld: int, dJ: int, dB: int, deps: int, d_diag: int, dS_old: int,
+                          dS_new: int, stream: int = 0):
+    """`lambda_update_dev` with the diagonal operator (`vrt_lambda_ali_update_dev`): with t = 1 - ε,
+    S_new = (t (J - Λ* S_old) + ε B) / (1 - t Λ*), d_diag = Λ* as one more (n, ld) array; an entry whose denominator is not
+    > 0 takes the plain update.  Returns (the criterion's maximum, the number of such entries)."""
+    out, cnt = ctypes.c_double(), ctypes.c_int64()
+    check(_lib.load().vrt_lambda_ali_update_dev(sites.handle, nlam, ld, dJ, dB, deps, d_diag, dS_old, dS_new,
+                                                ctypes.byref(out), ctypes.byref(cnt), stream or None))
+    return out.value, int(cnt.value)
+
+
+def lambda_ali_update_native_dev(sites: VoronoiSites, nlam: int, dJ_up: int, dJ_down: int, dB_up: int, deps: int,
+                                 d_diag_up: int, dS_up: int, dS_down: int, stream: int = 0):
+    """`lambda_ali_update_dev` on sweep-order plane sets (`vrt_lambda_ali_update_native_dev`): Λ* as an up-order plane
+    set like B."""
+    out, cnt = ctypes.c_double(), ctypes.c_int64()
+    check(_lib.load().vrt_lambda_ali_update_native_dev(sites.handle, nlam, dJ_up or None, dJ_down or None, dB_up, deps,
+                                                       d_diag_up, dS_up, dS_down, ctypes.byref(out), ctypes.byref(cnt),
+                                                       stream or None))
+    return out.value, int(cnt.value)
+
+
 def rates_populations_native_dev(sites: VoronoiSites, lam, blocks, dJ_up: int, dJ_down: int, planck2, lambda0: float, c0: float,
                                  d_doppler: int, d_gamma: int, sigma_bb_const: float, sigma_bf1, sigma_bf2,
                                  d_temperature: int, d_lte: int, hc_over_kB: float, pref_ij: float, pref_ji: float,
@@ -1535,8 +1563,17 @@ def _storage_f32(storage, who: str) -> bool:
     return storage == "f32"
 
 
+def _line_operator(operator, f32: bool, who: str) -> bool:
+    """operator=None | "diagonal" of the line drivers, checked before any device work"""
+    if operator not in _OPERATORS:
+        raise ValueError(f"{who}: operator must be None or 'diagonal'")
+    if operator is not None and f32:
+        raise ValueError(f"{who}: operator='diagonal' is not available with storage='f32' (the ALI update works on float64 arrays)")
+    return operator is not None
+
+
 def _Lambda_voronoi_native(eps_conv: float, maxiter: int, sites: VoronoiSites, case: LineCase, quadrature: str, n_sweeps: int,
-                           S0=None, populations0=None, f32: bool = False):
+                           S0=None, populations0=None, f32: bool = False, ali: bool = False):
     import torch
     vt = torch.float32 if f32 else torch.float64                # what S, J, B, I_0 and α are stored as
     w, th, ph, nq = read_quadrature(quadrature)
@@ -1563,6 +1600,8 @@ def _Lambda_voronoi_native(eps_conv: float, maxiter: int, sites: VoronoiSites, c
     I0_up = d_Bv[torch.as_tensor(sites.perm_up[:n1] - 1, device=dev)].contiguous()
     update, rates, owner = ((lambda_update_native_dev_f32, rates_populations_native_dev_f32, plan) if f32 else
                             (lambda_update_native_dev, rates_populations_native_dev, sites))
+    if ali:                                                     # Λ* of every iterate's α: rows, then its up-order plane set
+        L_rows, L_up = torch.zeros((n, nlam), dtype=vt, device=dev), torch.zeros(cnt, dtype=vt, device=dev)
     history = []
     diff, i = 1.0, 0
     try:
@@ -1573,8 +1612,15 @@ def _Lambda_voronoi_native(eps_conv: float, maxiter: int, sites: VoronoiSites, c
                                   strength.data_ptr(), d_ac.data_ptr(), native.data_ptr(), stream=st, f32=f32)
             plan.execute_native_dev(nlam, S_up.data_ptr(), S_dn.data_ptr(), native.data_ptr(), _lib.ALPHA_ANGLE_NATIVE, w,
                                     dJ_up=J_up.data_ptr(), dJ_down=J_dn.data_ptr(), dI0_up=I0_up.data_ptr(), stream=st, f32=f32)
-            diff = update(owner, nlam, J_up.data_ptr(), J_dn.data_ptr(), B_up.data_ptr(), d_eps.data_ptr(),
-                          S_up.data_ptr(), S_dn.data_ptr(), stream=st)
+            if ali:
+                plan.line_lambda_diagonal_dev(nlam, native.data_ptr(), w, nlam, L_rows.data_ptr(), stream=st)
+                plan.to_native_dev(nlam, nlam, L_rows.data_ptr(), L_up.data_ptr(), 0, stream=st)
+                diff, _ = lambda_ali_update_native_dev(sites, nlam, J_up.data_ptr(), J_dn.data_ptr(), B_up.data_ptr(),
+                                                       d_eps.data_ptr(), L_up.data_ptr(), S_up.data_ptr(), S_dn.data_ptr(),
+                                                       stream=st)
+            else:
+                diff = update(owner, nlam, J_up.data_ptr(), J_dn.data_ptr(), B_up.data_ptr(), d_eps.data_ptr(),
+                              S_up.data_ptr(), S_dn.data_ptr(), stream=st)
             new_pops = torch.empty_like(pops)
             rates(owner, case.lam, case.blocks, J_up.data_ptr(), J_dn.data_ptr(), case.planck2, case.lambda0,
                   case.c0, d_dop.data_ptr(), d_gam.data_ptr(), case.sigma_bb_const, case.sigma_bf1,
@@ -1598,7 +1644,7 @@ def _Lambda_voronoi_native(eps_conv: float, maxiter: int, sites: VoronoiSites, c
 
 def Lambda_voronoi_host(eps_conv: float, maxiter: int, sites: VoronoiSites, case: LineCase, quadrature: str,
                         n_sweeps: int = 3, ng=None, S0=None, populations0=None, checkpoint=None, checkpoint_every: int = 1,
-                        resume=None, storage: str = "f64"):
+                        resume=None, storage: str = "f64", operator=None):
     """Λ_voronoi (src/lambda_iteration.jl:205-300) for a host WITHOUT device arrays: the library owns the device
     state (`vrt_lambda_create` / `_iterate` / `_get`), one call per iteration, only the criterion's scalar
     comes back inside the loop.  Returns (J, S_new, populations (3, n), history).
@@ -1612,9 +1658,14 @@ def Lambda_voronoi_host(eps_conv: float, maxiter: int, sites: VoronoiSites, case
     `maxiter` counts the new iterates; a file whose shapes do not match the case raises ValueError before any device work.
     storage="f32": the session holds S, J, B, I_0 and α as float32 (`vrt_lambda_create_f32`; arithmetic stays float64, the
     patch path only); the returned J and S are float64 arrays of float32-representable values, checkpoints work unchanged,
-    and `ng` raises ValueError before any device work (the Ng kernels work on float64 planes)."""
+    and `ng` raises ValueError before any device work (the Ng kernels work on float64 planes).
+    operator="diagonal": accelerated Λ-iteration with the diagonal operator Λ* formed from every iterate's α
+    (`vrt_lambda_use_operator`): the same fixed point in fewer iterates where ε is small; composes with `ng`,
+    checkpoints and `resume` (nothing more is saved: Λ* is a function of the populations).  ValueError with storage="f32"
+    before any device work."""
     L = _lib.load()
     f32 = _storage_f32(storage, "Lambda_voronoi_host")
+    ali = _line_operator(operator, f32, "Lambda_voronoi_host")
     if f32 and ng is not None:
         raise ValueError("Lambda_voronoi_host: ng is not available with storage='f32'")
     lc, keep = case.c_struct()
@@ -1626,6 +1677,8 @@ def Lambda_voronoi_host(eps_conv: float, maxiter: int, sites: VoronoiSites, case
     try:
         if ng is not None:
             check(L.vrt_lambda_set_acceleration(h, 2, *_ng_settings(ng)))
+        if ali:
+            check(L.vrt_lambda_use_operator(h, 1))
         J, S, pops, history, steps, i = _session_loop(L, "lambda", h, n, nlam, eps_conv, maxiter, start, checkpoint,
                                                       checkpoint_every, ng, "Lambda_voronoi_host")
         if i == 0:
@@ -1639,7 +1692,7 @@ def Lambda_voronoi_host(eps_conv: float, maxiter: int, sites: VoronoiSites, case
 
 
 def Lambda_voronoi(eps_conv: float, maxiter: int, sites: VoronoiSites, case: LineCase, quadrature: str,
-                   n_sweeps: int = 3, native: bool = False, S0=None, populations0=None, storage: str = "f64"):
+                   n_sweeps: int = 3, native: bool = False, S0=None, populations0=None, storage: str = "f64", operator=None):
     """Λ_voronoi (src/lambda_iteration.jl:205-300) with everything between two convergence checks on
     the device, over the device-pointer entry points: per iteration `vrt_line_terms_dev` (γ and the line
     strength of the current populations, :72-75), `vrt_line_opacity_dev` (α_tot of every angle, :72-96),
@@ -1655,18 +1708,22 @@ def Lambda_voronoi(eps_conv: float, maxiter: int, sites: VoronoiSites, case: Lin
     runs the `_f32` entry points (`vrt_line_opacity_dev_f32`, `vrt_plan_execute_native_dev_f32`,
     `vrt_lambda_update_native_dev_f32`, `vrt_rates_populations_native_dev_f32`); J and S come back as float64 arrays of
     float32-representable values, the same as `Lambda_voronoi_host(storage="f32")` bit for bit.
+    operator="diagonal" (both `native` forms; ValueError with storage="f32"): per iteration also
+    `vrt_line_lambda_diagonal_dev` (Λ* from the α just written) and `vrt_lambda_ali_update_dev` /
+    `vrt_lambda_ali_update_native_dev` in place of the plain update -- `Lambda_voronoi_host(operator="diagonal")` bit for bit.
     Returns (J, S_new, populations (3, n), history of the criterion's differences) as numpy arrays."""
     import torch
     f32 = _storage_f32(storage, "Lambda_voronoi")
     if f32 and not native:
         raise ValueError("Lambda_voronoi: storage='f32' needs native=True (the float loop runs on sweep-order plane sets)")
+    ali = _line_operator(operator, f32, "Lambda_voronoi")
     S0, populations0 = _check_state_shapes(S0, populations0, sites.n, int(np.asarray(case.lam).size), "Lambda_voronoi")
     if S0 is not None and not (np.isfinite(S0).all() and (S0 > 0).all()):
         raise ValueError("Lambda_voronoi: S0 must be finite and > 0 everywhere")
     if populations0 is not None and not (np.isfinite(populations0).all() and (populations0 >= 0).all()):
         raise ValueError("Lambda_voronoi: populations0 must be finite and >= 0 everywhere")
     if native:
-        return _Lambda_voronoi_native(eps_conv, maxiter, sites, case, quadrature, n_sweeps, S0, populations0, f32)
+        return _Lambda_voronoi_native(eps_conv, maxiter, sites, case, quadrature, n_sweeps, S0, populations0, f32, ali)
     w, th, ph, nq = read_quadrature(quadrature)
     dev = torch.device("cuda", sites.device)
     n, nlam = sites.n, int(np.asarray(case.lam).size)
@@ -1684,6 +1741,7 @@ def Lambda_voronoi(eps_conv: float, maxiter: int, sites: VoronoiSites, case: Lin
     n1 = int(sites.layers_up[1] - 1)
     bottom = torch.as_tensor(sites.perm_up[:n1] - 1, device=dev)
     I0_up = d_B[bottom].contiguous()                           # B_λ(λ_l, T) of the bottom layer, :99-101
+    d_L = torch.zeros_like(d_B) if ali else None               # Λ* of every iterate's α
     st = torch.cuda.current_stream().cuda_stream
     history = []
     diff, i = 1.0, 0                                           # criterion(S_new = B, S_old = 0) = |1 - 0/B| = 1
@@ -1697,8 +1755,13 @@ def Lambda_voronoi(eps_conv: float, maxiter: int, sites: VoronoiSites, case: Lin
                                   strength.data_ptr(), d_ac.data_ptr(), native.data_ptr(), stream=st)
             plan.execute_dev(nlam, nlam, S_old.data_ptr(), native.data_ptr(), _lib.ALPHA_ANGLE_NATIVE, w,
                              dJ=J.data_ptr(), dI0_up=I0_up.data_ptr(), stream=st)
-            diff = lambda_update_dev(sites, nlam, nlam, J.data_ptr(), d_B.data_ptr(), d_eps.data_ptr(), S_old.data_ptr(),
-                                     S_new.data_ptr(), stream=st)
+            if ali:
+                plan.line_lambda_diagonal_dev(nlam, native.data_ptr(), w, nlam, d_L.data_ptr(), stream=st)
+                diff, _ = lambda_ali_update_dev(sites, nlam, nlam, J.data_ptr(), d_B.data_ptr(), d_eps.data_ptr(), d_L.data_ptr(),
+                                                S_old.data_ptr(), S_new.data_ptr(), stream=st)
+            else:
+                diff = lambda_update_dev(sites, nlam, nlam, J.data_ptr(), d_B.data_ptr(), d_eps.data_ptr(), S_old.data_ptr(),
+                                         S_new.data_ptr(), stream=st)
             new_pops = torch.empty_like(pops)
             rates_populations_dev(sites, case.lam, case.blocks, nlam, J.data_ptr(), case.planck2, case.lambda0, case.c0,
                                   d_dop.data_ptr(), d_gam.data_ptr(), case.sigma_bb_const, case.sigma_bf1, case.sigma_bf2,
@@ -1860,6 +1923,27 @@ def lambda_diagonal(sites: VoronoiSites, alpha, quadrature: str, n_sweeps: int =
     diag = np.zeros_like(alpha)
     check(_lib.load().vrt_plan_lambda_diagonal(plan._h, alpha.shape[1], alpha.shape[1], _d(alpha), _d(_f64(w)), _d(diag)))
     return diag
+
+
+def line_lambda_diagonal(sites: VoronoiSites, alpha_per_angle, quadrature: str, n_sweeps: int = 3) -> np.ndarray:
+    """Λ* of the line Λ-iteration (`vrt_line_lambda_diagonal_dev`): `lambda_diagonal` with an α of its own per angle,
+    alpha_per_angle (n_angles, n, nλ) in quadrature order (the Doppler-shifted α_tot of the line loop), brought into the
+    plan's native per-angle layout on the device.  Every angle of `quadrature` must be active (no θ = 90).  Returns (n, nλ)."""
+    import torch
+    alpha = _f64(alpha_per_angle)
+    plan, w = _quadrature_plan(sites, quadrature, n_sweeps)
+    if alpha.ndim != 3 or alpha.shape[0] != len(w) or alpha.shape[1] != sites.n:
+        raise ValueError(f"line_lambda_diagonal: alpha_per_angle must be ({len(w)}, {sites.n}, nlam)")
+    nlam = alpha.shape[2]
+    dev = torch.device("cuda", sites.device)
+    d_alpha = torch.from_numpy(alpha).to(dev)
+    native = torch.empty(plan.native_alpha_count(nlam), dtype=torch.float64, device=dev)
+    diag = torch.zeros((sites.n, nlam), dtype=torch.float64, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    plan.alpha_to_native_dev(nlam, nlam, d_alpha.data_ptr(), native.data_ptr(), stream=st)
+    plan.line_lambda_diagonal_dev(nlam, native.data_ptr(), w, nlam, diag.data_ptr(), stream=st)
+    torch.cuda.synchronize(dev)
+    return diag.cpu().numpy()
 
 
 def continuum_ali_update_dev(sites: VoronoiSites, J, B, eps, diag, S_old, S_new, eps_thick: float = 1e-4,

@@ -783,7 +783,8 @@ static int execute_call(vrt_plan *p, const ExecArgs &x)
 
 // S_new and the criterion of the Λ iteration, either layout: `launch` writes the criterion's two words at d_res
 template <typename F>
-static int lambda_update_call(vrt_grid *g, double *max_rel_change, hipStream_t st, const char *what, F launch)
+static int lambda_update_call(vrt_grid *g, double *max_rel_change, hipStream_t st, const char *what, F launch,
+                              int64_t *fallback_entries = nullptr /* the ALI updates' third word */)
 {
     int rc = use_device(g->device);
     if (rc) return rc;
@@ -791,13 +792,15 @@ static int lambda_update_call(vrt_grid *g, double *max_rel_change, hipStream_t s
     if (!g->d_scalars && (rc = g->d_scalars.alloc(kUpdateWords))) return rc;
     unsigned long long *d_res = g->d_scalars;
     rc = launch(d_res);
-    unsigned long long h[2] = {0, 0};
-    if (!rc && hipMemcpyAsync(h, d_res, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ENODEVICE;
+    unsigned long long h[3] = {0, 0, 0};
+    const size_t words = fallback_entries ? 3 : 2;
+    if (!rc && hipMemcpyAsync(h, d_res, words * sizeof(h[0]), hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ENODEVICE;
     if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = VRT_ENODEVICE;
     if (rc) return rc == VRT_ENODEVICE ? fail(rc, std::string("HIP error in ") + what) : rc;
     double d;
     std::memcpy(&d, &h[0], sizeof(double));
     *max_rel_change = h[1] ? std::nan("") : d;
+    if (fallback_entries) *fallback_entries = (int64_t)h[2];
     return VRT_OK;
 }
 
@@ -1486,6 +1489,36 @@ int vrt_lambda_update_native_dev(vrt_grid *g, int64_t nlam, const double *dJ_up,
         return lambda_update_call(g, max_rel_change, st, "vrt_lambda_update_native_dev", [&](unsigned long long *d_res) {
             return launch_lambda_update_native(g, nlam, dJ_up, dJ_down, dB_up, deps, dS_up, dS_down, d_res, st);
         });
+    });
+}
+
+int vrt_lambda_ali_update_dev(vrt_grid *g, int64_t nlam, int64_t ld, const double *dJ, const double *dB, const double *deps,
+                              const double *d_diag, const double *dS_old, double *dS_new, double *max_rel_change,
+                              int64_t *fallback_entries, void *stream)
+{
+    return guarded([&] {
+        if (!g || !dJ || !dB || !deps || !d_diag || !dS_old || !dS_new || !max_rel_change || !fallback_entries)
+            return fail(VRT_EINVAL, "NULL argument");
+        if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
+        hipStream_t st = (hipStream_t)stream;
+        return lambda_update_call(g, max_rel_change, st, "vrt_lambda_ali_update_dev", [&](unsigned long long *d_res) {
+            return launch_lambda_update(g->n, nlam, ld, dJ, dB, deps, dS_old, dS_new, d_res, st, d_diag);
+        }, fallback_entries);
+    });
+}
+
+int vrt_lambda_ali_update_native_dev(vrt_grid *g, int64_t nlam, const double *dJ_up, const double *dJ_down, const double *dB_up,
+                                     const double *deps, const double *d_diag_up, double *dS_up, double *dS_down,
+                                     double *max_rel_change, int64_t *fallback_entries, void *stream)
+{
+    return guarded([&] {
+        if (!g || (!dJ_up && !dJ_down) || !dB_up || !deps || !d_diag_up || !dS_up || !dS_down || !max_rel_change || !fallback_entries)
+            return fail(VRT_EINVAL, "NULL argument");
+        if (nlam < 1) return fail(VRT_EINVAL, "need nlam >= 1");
+        hipStream_t st = (hipStream_t)stream;
+        return lambda_update_call(g, max_rel_change, st, "vrt_lambda_ali_update_native_dev", [&](unsigned long long *d_res) {
+            return launch_lambda_update_native(g, nlam, dJ_up, dJ_down, dB_up, deps, dS_up, dS_down, d_res, st, d_diag_up);
+        }, fallback_entries);
     });
 }
 

@@ -208,13 +208,7 @@ int launch_continuum_update_native(vrt_grid *g, int64_t nlam, const double *dJ_u
     return VRT_OK;
 }
 
-// ---- the local operator Λ* --------------------------------------------------------------------------------------------
-// per ACTIVE angle: its quadrature weight and whether it is a down angle (kernel argument, as WeightTable of vrt_kernels.hip)
-struct DiagAngles {
-    double w[kMaxAngles];
-    int down[kMaxAngles];
-};
-
+// ---- the local operator Λ* (DiagAngles: vrt_device.h) ------------------------------------------------------------------
 // Λ*[i,l] = Σ_a w_a upd(a,i) ((w_1 b(Δτ_1)) + (w_2 b(Δτ_2))), Δτ_r = r_r (α[i,l] + α[up_r,l]) / 2 as the sweep forms it
 // (k_sweep_level), b the third coefficient of linear_weights: the coefficient of S[i] in the last visit of site i by every
 // angle.  upd(a,i) = 0 where the sweep of angle a never writes site i: the n1 sites of layer 1 of the angle's direction
@@ -264,11 +258,7 @@ int launch_lambda_diagonal(vrt_plan *p, int64_t nlam, int64_t ld, const double *
     vrt_grid *g = p->g;
     if (p->A > kMaxAngles) return fail(VRT_EINVAL, "too many active angles");
     if (nlam > INT32_MAX) return fail(VRT_EINVAL, "nlam too large");
-    DiagAngles ang;
-    for (int a = 0; a < kMaxAngles; a++) {
-        ang.w[a] = a < p->A ? weights[(size_t)p->user_of_active[(size_t)a]] : 0.0;
-        ang.down[a] = a < p->A && p->dir_of_active[(size_t)a] < 0;
-    }
+    const DiagAngles ang = diag_angles(p, weights);
     const int64_t blocks = (g->n + 255) / 256;
     hipLaunchKernelGGL(k_lambda_diagonal, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, g->n, (int)nlam, ld,
                        p->A, ang, (int32_t)g->up.n1, (int32_t)g->down.n1, g->up.d_rank, g->down.d_rank, p->d_up1, p->d_up2,

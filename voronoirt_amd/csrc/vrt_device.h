@@ -145,6 +145,23 @@ struct DirWeights {
     int count;
 };
 
+// per ACTIVE angle of a plan: its quadrature weight and whether it is a down angle (kernel argument of the Λ* kernels:
+// k_lambda_diagonal of vrt_continuum.hip, k_line_lambda_diagonal of vrt_line_ali.hip)
+struct DiagAngles {
+    double w[kMaxAngles];
+    int down[kMaxAngles];
+};
+// weights per USER angle (θ = 90 angles have no table and add nothing); the caller has checked p->A <= kMaxAngles
+inline DiagAngles diag_angles(const vrt_plan *p, const double *weights)
+{
+    DiagAngles ang;
+    for (int a = 0; a < kMaxAngles; a++) {
+        ang.w[a] = a < p->A ? weights[(size_t)p->user_of_active[(size_t)a]] : 0.0;
+        ang.down[a] = a < p->A && p->dir_of_active[(size_t)a] < 0;
+    }
+    return ang;
+}
+
 struct StepArgs {
     TileArgs ta;              // S, alpha, I in pair layout; ta.nlam = the caller's wavelength count
     int npair;                // ceil(nlam / 2)

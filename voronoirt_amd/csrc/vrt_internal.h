@@ -636,6 +636,7 @@ int launch_reduce_J(vrt_plan *p, const SweepArgs &sa, const double *weights_acti
 int launch_copy_I_out(vrt_plan *p, const SweepArgs &sa, void *dI_out, int64_t ldO, hipStream_t st);
 
 constexpr size_t kUpdateWords = 3;   // a grid's d_scalars: the criterion's maximum, its NaN flag, the continuum's thick count
+                                     //   (the line ALI updates: the entries that fell back to the plain update)
 int launch_axpy(size_t count, const double *d_src, double *d_dst, hipStream_t st);
 int launch_gather_rows(int64_t rows, int64_t nlam, int64_t ld, const int32_t *d_order, const double *d_src, double *d_dst,
                        hipStream_t st);
@@ -643,12 +644,19 @@ int launch_gather_rows_f32(int64_t rows, int64_t nlam, int64_t ld, const int32_t
                            hipStream_t st);                                            // the same rows, rounded to float
 int launch_round_to_f32(size_t count, const double *d_src, float *d_dst, hipStream_t st);    // dst = (float)src
 int launch_widen_f32(size_t count, const float *d_src, double *d_dst, hipStream_t st);       // dst = (double)src, exact
+// d_diag: Λ* of this iterate's α in the layout of the other arrays (the ALI update; d_result then has a third word, the
+// entries that fell back to the plain update), or NULL: the plain update, two words
 int launch_lambda_update(int64_t n, int64_t nlam, int64_t ld, const double *dJ, const double *dB,
                          const double *deps, const double *dS_old, double *dS_new,
-                         unsigned long long *d_result, hipStream_t st);
-// the same on sweep-order planes (J_up, J_down in, B in the up order, S_up updated in place, S_down written)
+                         unsigned long long *d_result, hipStream_t st, const double *d_diag = nullptr);
+// the same on sweep-order planes (J_up, J_down in, B in the up order, S_up updated in place, S_down written; Λ* up order)
 int launch_lambda_update_native(vrt_grid *g, int64_t nlam, const double *dJ_up, const double *dJ_down, const double *dB_up,
-                                const double *deps, double *dS_up, double *dS_down, unsigned long long *d_result, hipStream_t st);
+                                const double *deps, double *dS_up, double *dS_down, unsigned long long *d_result, hipStream_t st,
+                                const double *dL_up = nullptr);
+// Λ* of the line case (vrt_line_ali.hip) from the plan's native per-angle α: into (n, ld) rows, or into an up-order plane
+// set (a plan whose double planes exist: native_planes_ok).  Caller holds p->mu and has chosen the device.
+int launch_line_lambda_diagonal(vrt_plan *p, int64_t nlam, const double *d_alpha_native, const double *weights, int64_t ld,
+                                double *d_rows, double *d_up_planes, hipStream_t st);
 // the same on the plan's FLOAT plane sets (pair blocks of native_lg(p, true); the roundings: include/voronoirt.h)
 int launch_lambda_update_native_f32(vrt_plan *p, int64_t nlam, const float *dJ_up, const float *dJ_down, const float *dB_up,
                                     const double *deps, float *dS_up, float *dS_down, unsigned long long *d_result, hipStream_t st);

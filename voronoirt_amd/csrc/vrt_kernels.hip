@@ -428,12 +428,47 @@ int launch_copy_I_out(vrt_plan *p, const SweepArgs &sa, void *dI_out, int64_t ld
 // One pass over (site, λ); the maximum is reduced per wave with shuffles and merged with an
 // integer atomicMax on the IEEE bits (all candidates are >= 0, so the bit pattern orders like
 // the value); a NaN anywhere makes the result NaN as Julia's `maximum` does.
+//
+// ALI (vrt_lambda_use_operator, vrt_lambda_ali_update_dev): with the local operator L = Λ* of this iterate's α
+// (k_line_lambda_diagonal, vrt_line_ali.hip) and t = 1 - ε,
+//   S_new = (t (J - L S_old) + ε B) / (1 - t L)
+// in the operation order of k_continuum_update<true>.  An entry whose denominator is not > 0 (ε = 0 in a cell whose Λ*
+// rounds to 1) takes the plain update and is counted in result[2]: any per-entry choice of local operator leaves the
+// fixed point where it is, and S is updated in place, so an update cannot refuse half way.
 // --------------------------------------------------------------------------------------------
+template <bool ALI>
+__device__ __forceinline__ double line_update_entry(double e, double J, double B, double L, double s_old, unsigned &fallback)
+{
+    const double plain = (1.0 - e) * J + e * B;
+    if (!ALI) return plain;
+    const double t = 1.0 - e;
+    const double num = t * (J - L * s_old) + e * B;
+    const double den = 1.0 - t * L;
+    if (den > 0.0) return num / den;
+    fallback++;
+    return plain;
+}
+
+// the ALI updates' third word: entries that took the plain update, one atomic per workgroup that has any
+__device__ __forceinline__ void fallback_reduce(unsigned fallback, unsigned long long *__restrict__ result)
+{
+    __shared__ unsigned wfb[4];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) fallback += (unsigned)__shfl_xor((int)fallback, off, 64);
+    if ((threadIdx.x & 63) == 0) wfb[threadIdx.x >> 6] = fallback;
+    __syncthreads();
+    if (threadIdx.x == 0 && (wfb[0] | wfb[1] | wfb[2] | wfb[3]))
+        atomicAdd(&result[2], (unsigned long long)wfb[0] + wfb[1] + wfb[2] + wfb[3]);
+}
+
+// (diag stands last: the kernel arguments of the plain instantiation are where they were)
+template <bool ALI>
 __global__ void __launch_bounds__(256)
 k_lambda_update(int64_t n, int64_t nlam, int64_t ld, const double *__restrict__ J,
                 const double *__restrict__ B, const double *__restrict__ eps,
                 const double *__restrict__ S_old, double *__restrict__ S_new,
-                unsigned long long *__restrict__ result /* [0] max bits, [1] NaN flag */)
+                unsigned long long *__restrict__ result /* [0] max bits, [1] NaN flag, ALI: [2] fallback entries */,
+                const double *__restrict__ diag /* ALI: Λ* (n, ld) rows */)
 {
     // grid-stride over the n * nlam elements; ONE atomic per workgroup (an atomic per wave on a single
     // address serialises at the memory side: 9.0 ms for C4's 50.8 M elements against 0.5 ms of traffic)
@@ -442,11 +477,12 @@ k_lambda_update(int64_t n, int64_t nlam, int64_t ld, const double *__restrict__ 
     const int64_t total = n * nlam;
     double d = 0.0;
     bool isnan_ = false;
+    unsigned fallback = 0;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t site = t / nlam, l = t - site * nlam;
         const size_t o = (size_t)site * ld + l;
         const double e = eps[site];
-        const double s_new = (1.0 - e) * J[o] + e * B[o];
+        const double s_new = line_update_entry<ALI>(e, J[o], B[o], ALI ? diag[o] : 0.0, ALI ? S_old[o] : 0.0, fallback);
         S_new[o] = s_new;
         const double dd = fabs(1.0 - S_old[o] / s_new);
         if (!(dd == dd)) isnan_ = true;
@@ -463,17 +499,20 @@ k_lambda_update(int64_t n, int64_t nlam, int64_t ld, const double *__restrict__ 
         atomicMax(&result[0], (unsigned long long)__double_as_longlong(m));     // m >= 0: bit order = value order
         if (wnan[0] | wnan[1] | wnan[2] | wnan[3]) atomicMax(&result[1], 1ull);
     }
+    if (ALI) fallback_reduce(fallback, result);
 }
 
 // The same on sweep-order planes (vrt_plan_execute_native_dev): one thread per (wavelength pair, up position).  J = J_up +
 // J_down as k_combine_J forms it, S_new = (1 - ε) J + ε B with B in the up order, the old S read from the plane it is
 // written back to, the down-order copy of S_new written beside it -- the operations of k_lambda_update on the same values,
 // so S, J and the criterion are those of the caller-layout loop bit for bit, without either layout change.
+// ALI: Λ* from its up-order plane set Lu, one more load per pair.
+template <bool ALI>
 __global__ void __launch_bounds__(256)
 k_lambda_update_native(int64_t n, int npair, int nlam, const int32_t *__restrict__ store_up, const int32_t *__restrict__ rank_down,
                        const double2 *__restrict__ Ju, const double2 *__restrict__ Jd, const double2 *__restrict__ Bu,
                        const double *__restrict__ eps, double2 *__restrict__ Su, double2 *__restrict__ Sd,
-                       unsigned long long *__restrict__ result)
+                       unsigned long long *__restrict__ result, const double2 *__restrict__ Lu)
 {
     // one thread per UP position, walking the wavelength pairs: the site, its down position and its ε are looked up once; per
     // pair four loads and two stores, independent from pair to pair (several in flight).  Neighbouring lanes are neighbouring
@@ -482,13 +521,14 @@ k_lambda_update_native(int64_t n, int npair, int nlam, const int32_t *__restrict
     __shared__ int wnan[4];
     double d = 0.0;
     bool isnan_ = false;
+    unsigned fallback = 0;
     for (int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pos < n; pos += (int64_t)gridDim.x * blockDim.x) {
         const int32_t site = store_up[pos];
         const size_t pd = (size_t)rank_down[site];
         const double e = eps[site];
         constexpr int U = 4;
         for (int q0 = 0; q0 < npair; q0 += U) {
-            double2 J[U], B[U], So[U];
+            double2 J[U], B[U], So[U], L[U];
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const int q = q0 + u < npair ? q0 + u : npair - 1;
@@ -501,6 +541,7 @@ k_lambda_update_native(int64_t n, int npair, int nlam, const int32_t *__restrict
                 }
                 B[u] = Bu[t];
                 So[u] = Su[t];
+                if (ALI) L[u] = Lu[t];
             }
 #pragma unroll
             for (int u = 0; u < U; u++) {
@@ -508,10 +549,12 @@ k_lambda_update_native(int64_t n, int npair, int nlam, const int32_t *__restrict
                 if (q >= npair) break;
                 const size_t t = (size_t)q * (size_t)n + (size_t)pos;
                 double2 Sn;
-                Sn.x = (1.0 - e) * J[u].x + e * B[u].x;
-                Sn.y = (1.0 - e) * J[u].y + e * B[u].y;
+                Sn.x = line_update_entry<ALI>(e, J[u].x, B[u].x, ALI ? L[u].x : 0.0, So[u].x, fallback);
+                unsigned fallback_y = 0;
+                Sn.y = line_update_entry<ALI>(e, J[u].y, B[u].y, ALI ? L[u].y : 0.0, So[u].y, fallback_y);
                 const bool second = 2 * q + 1 < nlam;              // (an odd count: the padding wavelength is carried as zeros)
                 if (!second) Sn.y = 0.0;
+                else fallback += fallback_y;                       // (the padding wavelength is no entry of the count)
                 Su[t] = Sn;
                 Sd[(size_t)q * (size_t)n + pd] = Sn;
                 const double dx = fabs(1.0 - So[u].x / Sn.x);
@@ -536,18 +579,26 @@ k_lambda_update_native(int64_t n, int npair, int nlam, const int32_t *__restrict
         atomicMax(&result[0], (unsigned long long)__double_as_longlong(m));
         if (wnan[0] | wnan[1] | wnan[2] | wnan[3]) atomicMax(&result[1], 1ull);
     }
+    if (ALI) fallback_reduce(fallback, result);
 }
 
+// dL_up: Λ* as an up-order plane set, or NULL for the plain update (two result words; with Λ* three)
 int launch_lambda_update_native(vrt_grid *g, int64_t nlam, const double *dJ_up, const double *dJ_down, const double *dB_up,
-                                const double *deps, double *dS_up, double *dS_down, unsigned long long *d_result, hipStream_t st)
+                                const double *deps, double *dS_up, double *dS_down, unsigned long long *d_result, hipStream_t st,
+                                const double *dL_up)
 {
-    VRT_HIP_TRY(hipMemsetAsync(d_result, 0, 2 * sizeof(unsigned long long), st));
+    VRT_HIP_TRY(hipMemsetAsync(d_result, 0, (dL_up ? 3 : 2) * sizeof(unsigned long long), st));
     const int npair = (int)((nlam + 1) / 2);
     const int64_t blocks = std::min<int64_t>((g->n + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(k_lambda_update_native, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, g->n, npair, (int)nlam,
-                       g->up.d_store, g->down.d_srank, reinterpret_cast<const double2 *>(dJ_up), reinterpret_cast<const double2 *>(dJ_down),
-                       reinterpret_cast<const double2 *>(dB_up), deps, reinterpret_cast<double2 *>(dS_up),
-                       reinterpret_cast<double2 *>(dS_down), d_result);
+#define VRT_UPDATE_NATIVE(ALI)                                                                                             \
+    hipLaunchKernelGGL(k_lambda_update_native<ALI>, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, g->n,  \
+                       npair, (int)nlam, g->up.d_store, g->down.d_srank, reinterpret_cast<const double2 *>(dJ_up),         \
+                       reinterpret_cast<const double2 *>(dJ_down), reinterpret_cast<const double2 *>(dB_up), deps,         \
+                       reinterpret_cast<double2 *>(dS_up), reinterpret_cast<double2 *>(dS_down), d_result,                 \
+                       reinterpret_cast<const double2 *>(dL_up))
+    if (dL_up) VRT_UPDATE_NATIVE(true);
+    else VRT_UPDATE_NATIVE(false);
+#undef VRT_UPDATE_NATIVE
     VRT_HIP_TRY(hipGetLastError());
     return VRT_OK;
 }
@@ -732,13 +783,15 @@ int launch_gather_rows(int64_t rows, int64_t nlam, int64_t ld, const int32_t *d_
 
 int launch_lambda_update(int64_t n, int64_t nlam, int64_t ld, const double *dJ, const double *dB,
                          const double *deps, const double *dS_old, double *dS_new,
-                         unsigned long long *d_result, hipStream_t st)
+                         unsigned long long *d_result, hipStream_t st, const double *d_diag)
 {
-    VRT_HIP_TRY(hipMemsetAsync(d_result, 0, 2 * sizeof(unsigned long long), st));
+    VRT_HIP_TRY(hipMemsetAsync(d_result, 0, (d_diag ? 3 : 2) * sizeof(unsigned long long), st));
     const int64_t total = n * nlam;
-    const int64_t blocks = std::min<int64_t>((total + 255) / 256, 256 * 16);     // 16 workgroups per CU
-    hipLaunchKernelGGL(k_lambda_update, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, n, nlam, ld,
-                       dJ, dB, deps, dS_old, dS_new, d_result);
+    const dim3 grid((unsigned)std::max<int64_t>(std::min<int64_t>((total + 255) / 256, 256 * 16), 1));     // 16 workgroups per CU
+    if (d_diag)
+        hipLaunchKernelGGL(k_lambda_update<true>, grid, dim3(256), 0, st, n, nlam, ld, dJ, dB, deps, dS_old, dS_new, d_result, d_diag);
+    else
+        hipLaunchKernelGGL(k_lambda_update<false>, grid, dim3(256), 0, st, n, nlam, ld, dJ, dB, deps, dS_old, dS_new, d_result, d_diag);
     VRT_HIP_TRY(hipGetLastError());
     return VRT_OK;
 }

@@ -143,6 +143,11 @@ struct vrt_lambda {
     SourceStore sj;
     DevBuf<float> f_B0, f_I0, f_native;
     NgState ng;                         // vrt_lambda_set_acceleration (off: nothing allocated, nothing run)
+    // vrt_lambda_use_operator (0: nothing allocated, nothing run): Λ* of the current iterate's α in the store's form
+    // (rows, or one up-order plane set), rewritten by every iterate -- no operator state survives an iterate
+    int op = 0;
+    DevBuf<double> d_diag;
+    int64_t fallback_last = 0;          // entries of the last iterate that took the plain update (den not > 0)
 };
 
 struct LambdaDelete { void operator()(vrt_lambda *s) const { vrt_lambda_destroy(s); } };
@@ -318,7 +323,7 @@ static int lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *wei
         }
         VRT_S(s->sj.to_up_order(s->d_B0, s->f_B0, st));
         VRT_S(s->d_pops_new.alloc(3 * n));
-        VRT_S(s->d_scalars.alloc(2));
+        VRT_S(s->d_scalars.alloc(kUpdateWords));
 #undef VRT_S
         if (hipStreamSynchronize(st) != hipSuccess)                         // the host arrays may go after return
             return fail(VRT_ENODEVICE, "uploading the line case failed");
@@ -361,11 +366,16 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
         if ((rc = s->line.terms(s->d_pops, st))) return rc;
         void *alpha = f32 ? (void *)s->f_native.get() : (void *)s->d_native.get();
         if ((rc = s->line.opacity(p, nlam, 0, alpha, st, f32))) return rc;
+        // Λ* of this iterate's α (vrt_line_ali.hip), beside the sweep that reads the same buffer
+        if (s->op && (rc = launch_line_lambda_diagonal(p, nlam, s->d_native, s->weights.data(), nlam,
+                                                       sj.form() == SourceStore::kRows ? s->d_diag.get() : nullptr,
+                                                       sj.form() == SourceStore::kRows ? nullptr : s->d_diag.get(), st)))
+            return rc;
         // J_λ (:84-111) from S, in the store's form
         const void *I0 = f32 ? (const void *)s->f_I0.get() : (const void *)s->d_I0.get();
         if ((rc = execute_locked(p, sj.exec_args(alpha, VRT_ALPHA_ANGLE_NATIVE, I0, s->weights.data(), st)))) return rc;
         // S_new = (1 - ε) J + ε B_0 and the criterion's scalar (:261-263, :325-349); in sweep order the old S is read from the
-        // plane the new one is written to
+        // plane the new one is written to.  With the operator on (d_diag is NULL otherwise): the ALI update
         RatesJ J;
         switch (sj.form()) {
         case SourceStore::kPlanesF32:                        // (the roundings: include/voronoirt.h)
@@ -375,11 +385,12 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
             break;
         case SourceStore::kPlanes:
             rc = launch_lambda_update_native(g, nlam, sj.J_plane(0), sj.J_plane(1), s->d_B0, s->line.d_eps, sj.S_plane(0),
-                                             sj.S_plane(1), s->d_scalars, st);
+                                             sj.S_plane(1), s->d_scalars, st, s->d_diag);
             J = RatesJ::from_planes(g, sj.J_plane(0), sj.J_plane(1));
             break;
         case SourceStore::kRows:
-            rc = launch_lambda_update(n, nlam, nlam, sj.J_rows(), s->d_B0, s->line.d_eps, sj.S_old(), sj.S_new(), s->d_scalars, st);
+            rc = launch_lambda_update(n, nlam, nlam, sj.J_rows(), s->d_B0, s->line.d_eps, sj.S_old(), sj.S_new(), s->d_scalars, st,
+                                      s->d_diag);
             J = RatesJ::from_rows(sj.J_rows(), nlam);
             break;
         }
@@ -387,13 +398,14 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
         // R, populations (:269, :274) from the same J
         if ((rc = launch_rates_populations(s->line.rates_in(), J, s->line.d_R, s->d_pops_new, st))) return rc;
         std::swap(s->d_pops, s->d_pops_new);
-        unsigned long long h[2] = {0, 0};
-        VRT_HIP_TRY(hipMemcpyAsync(h, s->d_scalars, sizeof(h), hipMemcpyDeviceToHost, st));
+        unsigned long long h[kUpdateWords] = {0, 0, 0};      // (the third word: the ALI update's, in the same copy)
+        VRT_HIP_TRY(hipMemcpyAsync(h, s->d_scalars, (s->op ? 3 : 2) * sizeof(h[0]), hipMemcpyDeviceToHost, st));
         VRT_HIP_TRY(hipStreamSynchronize(st));
         if ((rc = patch_chain_check(p))) return rc;          // a chained sweep that gave up: THIS iteration's results are invalid
         double d;
         std::memcpy(&d, &h[0], sizeof(double));
         *max_rel_change = h[1] ? std::nan("") : d;
+        s->fallback_last = (int64_t)h[2];
         s->iterations++;
         if (s->ng.order) {
             // history copy or Ng step on the S of the plain update (the up-order copy); an accepted x_acc becomes that copy
@@ -420,6 +432,36 @@ int vrt_lambda_set_acceleration(vrt_lambda *s, int order, int start, int period)
         if ((rc = s->sj.ng_check()) || (rc = use_device(p->g->device))) return rc;
         return ng_configure(s->ng, order, start, period, s->sj.ng_count());
     });
+}
+
+int vrt_lambda_use_operator(vrt_lambda *s, int op)
+{
+    if (!s) return fail(VRT_EINVAL, "NULL session");
+    if (op != 0 && op != 1) return fail(VRT_EINVAL, "operator must be 0 (plain) or 1 (diagonal)");
+    return guarded([&] {
+        vrt_plan *p = s->p;
+        std::lock_guard<std::mutex> lock(p->mu);
+        if (s->sj.form() == SourceStore::kPlanesF32)
+            return fail(VRT_EINVAL, "vrt_lambda_use_operator: not on a float-storage session (the ALI update works on double arrays)");
+        int rc = use_device(p->g->device);
+        if (rc) return rc;
+        if (op == s->op) return (int)VRT_OK;
+        if (op) {
+            if ((rc = s->sj.alloc_beside(s->d_diag))) return rc;
+        } else
+            s->d_diag.reset();
+        s->op = op;
+        s->fallback_last = 0;
+        return (int)VRT_OK;
+    });
+}
+
+int vrt_lambda_get_operator(const vrt_lambda *s, int *op, int64_t *fallback_entries_last_iterate)
+{
+    if (!s || !op) return fail(VRT_EINVAL, "NULL argument");
+    *op = s->op;
+    if (fallback_entries_last_iterate) *fallback_entries_last_iterate = s->fallback_last;
+    return VRT_OK;
 }
 
 int vrt_lambda_last_acceleration(const vrt_lambda *s, int *applied, double sums[5], double coeffs[2])

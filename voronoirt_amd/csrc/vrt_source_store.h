@@ -81,6 +81,12 @@ struct SourceStore {
         int rc = up.alloc(planes_);
         return rc ? rc : planes_to_native(p_, nlam_, nlam_, rows, up, nullptr, st);
     }
+    // Room for an array that a kernel writes in this store's form (a line session's Λ*): rows, or one up-order plane set
+    int alloc_beside(DevBuf<double> &a) const
+    {
+        if (form_ == kPlanesF32) return fail(VRT_EINVAL, "a float-storage store has no double planes");
+        return a.alloc(form_ == kRows ? rows_ : planes_);
+    }
     // The same in place: `a` holds rows and -- kPlanes -- is replaced by its up-order plane set.  kPlanesF32: rounded to
     // float once, the up-order plane set of that in `af`, `a` released.  Synchronises `st` where a buffer goes.
     int to_up_order(DevBuf<double> &a, DevBuf<float> &af, hipStream_t st) const
