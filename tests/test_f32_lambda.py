@@ -13,6 +13,7 @@ import pytest
 import voronoirt_amd as vrt
 from f32_lambda_model import deviations, f32, oracle_runs, update_model
 from oracle.f32_model import float_compare, within_conditions
+from oracle.layout_ref import pair_index as _pair_index
 from voronoirt_amd import _lib, api
 
 pytestmark = pytest.mark.gpu
@@ -54,24 +55,6 @@ def plans(sites):
     yield get
     for p in made.values():
         p.close()
-
-
-def _pair_index(q, p, n, B, npair):
-    """pair_index of csrc/vrt_device.h: blocks of B pairs, then one block per set bit of the remainder, widest first"""
-    full = npair // B * B
-    if q < full:
-        k0, w = q // B * B, B
-    else:
-        k0, w = full, B
-        while True:
-            w //= 2
-            if w == 0:
-                raise IndexError(q)
-            if (npair - full) & w:
-                if q < k0 + w:
-                    break
-                k0 += w
-    return k0 * n + p * w + (q - k0)
 
 
 class _Planes:

@@ -16,6 +16,7 @@ from multi_f32_model import (CASES, REGROUPING, oracle_R, partition, partitions,
                              rel_per_transition, small_lambda_case, widened_J)
 from oracle import oracle as orc
 from oracle.f32_model import within_conditions
+from oracle.layout_ref import pair_index as _pair_index
 from voronoirt_amd import _lib, api
 
 pytestmark = pytest.mark.gpu
@@ -56,24 +57,6 @@ def plans(sites):
     yield get
     for p in made.values():
         p.close()
-
-
-def _pair_index(q, p, n, B, npair):
-    """pair_index of csrc/vrt_device.h: blocks of B pairs, then one block per set bit of the remainder, widest first"""
-    full = npair // B * B
-    if q < full:
-        k0, w = q // B * B, B
-    else:
-        k0, w = full, B
-        while True:
-            w //= 2
-            if w == 0:
-                raise IndexError(q)
-            if (npair - full) & w:
-                if q < k0 + w:
-                    break
-                k0 += w
-    return k0 * n + p * w + (q - k0)
 
 
 class _Planes:

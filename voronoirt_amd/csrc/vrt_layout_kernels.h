@@ -222,6 +222,7 @@ k_reduce_dir(int64_t total, int64_t stride_angle, DirWeights dw, const T *__rest
 
 // J[site][l] = J_up[l][rank_up[site]] + J_down[l][rank_down[site]], walking sites in up order so
 // the J_up reads are coalesced and the J_down reads are piecewise contiguous on stratified grids.
+// A direction without angles (NULL) counts as the +0 planes vrt_plan_execute_native_dev hands back for it: x + 0.0.
 template <typename T>
 __global__ void __launch_bounds__(256)
 k_combine_J(int64_t n, int nlam, int64_t ldJ, int lb, const int32_t *__restrict__ order_up,
@@ -242,10 +243,10 @@ k_combine_J(int64_t n, int nlam, int64_t ldJ, int lb, const int32_t *__restrict_
         for (int c = ty; c < 64; c += 4) {
             const int l = l0 + c;
             if (l < nlam && p < n) {
-                double v = 0.0;
+                double v = 0.0, u = 0.0;
                 if (Ju) v = (double)Ju[(size_t)l * n + p];
-                if (Jdn) v = v + (double)Jdn[(size_t)l * n + pd];
-                tile[tx][c] = (T)v;
+                if (Jdn) u = (double)Jdn[(size_t)l * n + pd];
+                tile[tx][c] = (T)(v + u);
             }
         }
     } else {                                   // pair accesses, a site's block of pairs by consecutive lanes
@@ -260,14 +261,11 @@ k_combine_J(int64_t n, int nlam, int64_t ldJ, int lb, const int32_t *__restrict_
             const int pb = e & ((1 << lgB) - 1), px = (e >> lgB) & 63, bt = e >> (lgB + 6);
             const int c = 2 * ((bt << lgB) + pb), l = l0 + c;
             if (l < nlam && p0 + px < n) {
-                double2 v = make_double2(0.0, 0.0);
+                double2 v = make_double2(0.0, 0.0), u = v;
                 if (Ju) v = to_d2(reinterpret_cast<const T2 *>(Ju)[pair_index(l >> 1, p0 + px, n, lgB, npair)]);
-                if (Jdn) {
-                    const double2 u = to_d2(reinterpret_cast<const T2 *>(Jdn)[pair_index(l >> 1, pds[px], n, lgB, npair)]);
-                    v.x = v.x + u.x; v.y = v.y + u.y;
-                }
-                tile[px][c] = (T)v.x;
-                tile[px][c + 1] = (T)v.y;
+                if (Jdn) u = to_d2(reinterpret_cast<const T2 *>(Jdn)[pair_index(l >> 1, pds[px], n, lgB, npair)]);
+                tile[px][c] = (T)(v.x + u.x);
+                tile[px][c + 1] = (T)(v.y + u.y);
             }
         }
     }
@@ -290,15 +288,12 @@ k_combine_J_narrow(int64_t n, int nlam, int64_t ldJ, int lgB, int lgP, const int
     const int pr = (int)(e & ((1 << lgP) - 1)), npair = (nlam + 1) >> 1;
     if (pos >= n || pr >= npair) return;
     const int32_t site = order_up[pos];
-    double2 v = make_double2(0.0, 0.0);
+    double2 v = make_double2(0.0, 0.0), u = v;
     if (Ju) v = to_d2(reinterpret_cast<const T2 *>(Ju)[pair_index(pr, pos, n, lgB, npair)]);
-    if (Jdn) {
-        const double2 u = to_d2(reinterpret_cast<const T2 *>(Jdn)[pair_index(pr, rank_down[site], n, lgB, npair)]);
-        v.x = v.x + u.x; v.y = v.y + u.y;
-    }
+    if (Jdn) u = to_d2(reinterpret_cast<const T2 *>(Jdn)[pair_index(pr, rank_down[site], n, lgB, npair)]);
     T *row = J + (size_t)site * ldJ;
-    row[2 * pr] = (T)v.x;
-    if (2 * pr + 1 < nlam) row[2 * pr + 1] = (T)v.y;
+    row[2 * pr] = (T)(v.x + u.x);
+    if (2 * pr + 1 < nlam) row[2 * pr + 1] = (T)(v.y + u.y);
 }
 
 // out[order[p]][l] = in[l][p]  (sweep order, wavelength-major -> caller's site-major rows)
