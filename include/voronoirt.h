@@ -1029,6 +1029,44 @@ int vrt_lambda_ali_update_native_dev(vrt_grid *g, int64_t nlam, const double *dJ
 int vrt_lambda_use_operator(vrt_lambda *s, int op);
 int vrt_lambda_get_operator(const vrt_lambda *s, int *op, int64_t *fallback_entries_last_iterate);
 
+/* ---- accelerated Λ-iteration of the LINE session on a regular grid ----------------------------------------------------
+ * The regular-grid line session (vrt_regular_lambda_*, the raster half of the reference's compare_line.jl) has these
+ * entries of its own: the same diagonal operator, so that both halves of the comparison can run the same method.  Its Λ*
+ * is the raster's one-sweep diagonal (vrt_regular_lambda_diagonal_dev above) with an α of its own per angle, formed every
+ * iterate from the α_tot the solves of that iterate read:
+ *     Λ*[p,l] = Σ_a weights[a] · c_a(p; α_a[l])
+ * over the ACTIVE angles in quadrature order (dirs = 0 skipped and never read); c_a is exactly the per-angle coefficient of
+ * vrt_regular_lambda_diagonal_dev (one function on the device serves both) taken with angle a's α planes of wavelength l.
+ * Exactly 0 on the ghost border and on the angle's boundary plane.  With one α for every angle the result is
+ * vrt_regular_lambda_diagonal's bit for bit, and with one angle active it is that entry's with that angle alone.  Any
+ * number of active angles.  No atomics: the same inputs give the same bits.
+ * vrt_regular_line_lambda_diagonal_dev: d_alpha_pl plane-major per ACTIVE angle in order, [a][l][iz][iy][ix]; d_diag_pl
+ *   [l][iz][iy][ix], every element written; asynchronous work on `stream`, which is synchronised before return.
+ * vrt_regular_line_lambda_diagonal: the same from host arrays.  alpha (nlam, n, n_angles) Julia dims -- C order
+ *   (n_angles, n, ld) -- in Julia point order for every USER angle, the blocks of inactive angles are never read; diag
+ *   (nlam, n) with leading dimension ld, padding columns neither read nor written.  Also checks that the α that is read is
+ *   finite and > 0.
+ *   Both check NULL pointers, nlam >= 1 (the host form: ld >= nlam) and the directions, as vrt_regular_lambda_diagonal[_dev]
+ *   does, before the device is touched.
+ * vrt_regular_lambda_use_operator: op 0 = plain Λ-iteration (the default), 1 = the diagonal operator; callable between any
+ *   two iterates.  On: two arrays of the size of S beside the session (Λ* plane-major as the solves' chunks leave it, and as
+ *   rows for the update).  Every vrt_regular_lambda_iterate then zeroes the planes, forms Λ* chunk by chunk right after the
+ *   chunk's opacity while that α stands in the workspace (bit-identical for any VRT_REG_LAMBDA_BYTES), and runs the update of
+ *   vrt_lambda_ali_update_dev -- the fallback rule and count included, which come home with the criterion's words.  Rates
+ *   and populations come from the iterate's J as before; Ng acceleration sees the ALI S; a change of the operator drops any
+ *   recorded Ng history.  Nothing of Λ* survives an iterate: vrt_regular_lambda_set_state resumes an ALI run bit for bit
+ *   (select the operator in the new session).  Off: both arrays are freed and the session runs as one that never called
+ *   this.  VRT_EINVAL, nothing changed: NULL, op outside {0, 1}.  (Named _use_operator as on the Voronoi line session.)
+ * vrt_regular_lambda_get_operator: *op and -- may be NULL -- the fallback count of the last iterate.
+ * Still without an operator: the float-storage and the multi-device line sessions. */
+int vrt_regular_line_lambda_diagonal_dev(vrt_regular *r, int64_t n_angles, const double *k, const int *dirs,
+                                         const double *weights, int64_t nlam, const double *d_alpha_pl,
+                                         double *d_diag_pl, void *stream);
+int vrt_regular_line_lambda_diagonal(vrt_regular *r, int64_t n_angles, const double *k, const int *dirs,
+                                     const double *weights, int64_t nlam, int64_t ld, const double *alpha, double *diag);
+int vrt_regular_lambda_use_operator(vrt_regular_lambda *s, int op);
+int vrt_regular_lambda_get_operator(const vrt_regular_lambda *s, int *op, int64_t *fallback_entries_last_iterate);
+
 /* ---- emergent spectra: opacity / source function, top-plane intensity, tau = 1 heights ------------------------------
  * The last step of a reference study (write_top_intensity, write_tau_unity and plotter, src/plot_utils.jl:61-140,
  * :297-355, :434-576) on a regular raster.  Plain numbers in one unit system, constants folded in by the caller.

@@ -418,10 +418,14 @@ populations and S_new are fetched and checkpointed without the ghost border like
 Arrays keep their Julia shapes: (nλ, nz, nx, ny), (nz, nx, ny, 3) and (3, 3, nz, nx, ny) are vrt_line_case's
 (nλ, n), (n, 3) and (3, 3, n) with n = nz nx ny.  `ng = (start, period)` as for `Λ`
 (vrt_regular_lambda_set_acceleration).  `S0` (nλ, nz, nx, ny), `populations0` (nz, nx, ny, 3), ghost border included,
-as for `Λ` (vrt_regular_lambda_set_state).  Unrun: Julia is not installed where the library is built.
+as for `Λ` (vrt_regular_lambda_set_state).  `operator = :diagonal`: accelerated Λ-iteration with the raster's one-sweep
+diagonal Λ* formed on the device from every iterate's per-angle α_tot (vrt_regular_lambda_use_operator), as for `Λ`; it
+composes with `ng`, `S0` and `populations0`.  Unrun: Julia is not installed where the library is built.
 """
 function Λ_regular(ϵ::AbstractFloat, maxiter::Integer, atmos, line::HydrogenicLine, quadrature::String, DATA::String;
-                   ng::Union{Nothing,Tuple{Int,Int}}=nothing, S0=nothing, populations0=nothing)
+                   ng::Union{Nothing,Tuple{Int,Int}}=nothing, S0=nothing, populations0=nothing,
+                   operator::Union{Nothing,Symbol}=nothing)
+    operator in (nothing, :diagonal) || error("operator must be nothing or :diagonal")
     LTE_pops = VoronoiRT.LTE_populations(line, atmos)
     α_cont = VoronoiRT.α_absorption.(line.λ0, atmos.temperature, atmos.electron_density * 1.0,
                                      LTE_pops[:, :, :, 1] .+ LTE_pops[:, :, :, 2], LTE_pops[:, :, :, 3]) .+
@@ -490,6 +494,7 @@ function Λ_regular(ϵ::AbstractFloat, maxiter::Integer, atmos, line::Hydrogenic
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ses[], Jp, Sp, pops, C_NULL, C_NULL))
     ng !== nothing && check(ccall((:vrt_regular_lambda_set_acceleration, libvrt), Cint, (Ptr{Cvoid}, Cint, Cint, Cint),
                                   ses[], 2, ng[1], ng[2]))
+    operator === :diagonal && check(ccall((:vrt_regular_lambda_use_operator, libvrt), Cint, (Ptr{Cvoid}, Cint), ses[], 1))
     set_state(:vrt_regular_lambda_set_state, ses[], plain_array(S0, I_unit, (nλ, nz, nx, ny)),
               plain_array(populations0, u"m^-3", (nz, nx, ny, 3)))
     ng_applied = Ref{Cint}(0); ng_coeffs = zeros(2)
@@ -734,6 +739,38 @@ function lambda_diagonal_regular(z::Vector{Float64}, x::Vector{Float64}, y::Vect
     rc = ccall((:vrt_regular_lambda_diagonal, libvrt), Cint,
                (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Cint}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}),
                reg[], n_angles, k, dirs, w, 1, 1, α, diag)
+    ccall((:vrt_regular_destroy, libvrt), Cvoid, (Ptr{Cvoid},), reg[])
+    check(rc)
+    return diag
+end
+
+"""
+    line_lambda_diagonal_regular(z, x, y, α, quadrature) -> Λ*
+
+Λ* of the line Λ-iteration on a raster (vrt_regular_line_lambda_diagonal): `lambda_diagonal_regular` with an α of its own
+per angle.  z, x, y: the ghosted axes in metres; α (nλ, nz, nx, ny, n_angles) in m^-1 for every angle of the quadrature in
+order, finite and > 0 (the block of a θ = 90 angle is not read).  Returns (nλ, nz, nx, ny).  Unrun.
+"""
+function line_lambda_diagonal_regular(z::Vector{Float64}, x::Vector{Float64}, y::Vector{Float64}, α::Array{Float64,5},
+                                      quadrature::String)
+    nλ, nz, nx, ny, na = size(α)
+    (nz, nx, ny) == (length(z), length(x), length(y)) || throw(ArgumentError("α must be (nλ, nz, nx, ny, n_angles) of the axes"))
+    weights, θ_array, ϕ_array, n_angles = read_quadrature(quadrature)
+    na == n_angles || throw(ArgumentError("α needs one block per angle of the quadrature"))
+    k = Matrix{Float64}(undef, 3, n_angles)
+    for i in 1:n_angles
+        k[:, i] = direction(θ_array[i], ϕ_array[i])
+    end
+    dirs = Cint[θ > 90 ? 1 : (θ < 90 ? -1 : 0) for θ in θ_array]
+    w = Vector{Float64}(weights)
+    reg = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:vrt_regular_create, libvrt), Cint,
+                (Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ref{Ptr{Cvoid}}),
+                nz, nx, ny, z, x, y, 0, reg))
+    diag = zeros(Float64, nλ, nz, nx, ny)
+    rc = ccall((:vrt_regular_line_lambda_diagonal, libvrt), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Cint}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}),
+               reg[], n_angles, k, dirs, w, nλ, nλ, α, diag)
     ccall((:vrt_regular_destroy, libvrt), Cvoid, (Ptr{Cvoid},), reg[])
     check(rc)
     return diag

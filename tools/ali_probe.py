@@ -26,6 +26,13 @@ a hard two-level case (the atom of tests/test_physics.py's _lambda_case with ε 
 2 x 6 continuum wavelengths): plain, operator="diagonal", and that with ng=(4, 4); at most --maxiter iterates each.
 
     python tools/ali_probe.py --line [--a 59 --c 143] [--tol 1e-3] [--maxiter 400] [--plain-only]
+
+`--regular-line`: the Λ* kernel of the raster LINE session alone (vrt_regular_line_lambda_diagonal_dev: the planes zeroed,
+then k_regular_line_lambda_diagonal over all 12 x --nlam solves as one chunk) on random per-angle α planes made on the
+device, at --size^3 interior points: wall time of the synchronous call and the bytes per second of what it must move
+(α read once, Λ* zeroed, read and written).  The iterate itself, operator off and on: tools/regular_lambda_probe.py.
+
+    python tools/ali_probe.py --regular-line [--size 128] [--nlam 91] [--reps 7]
 """
 import argparse
 import ctypes
@@ -57,6 +64,8 @@ ap.add_argument("--shape", type=int, nargs=3, default=[215, 128, 128], help="--r
 ap.add_argument("--line", action="store_true", help="the line session: iterate counts plain / diagonal / diagonal + Ng")
 ap.add_argument("--tol", type=float, default=1e-3, help="--line: the criterion the runs stop at")
 ap.add_argument("--maxiter", type=int, default=400, help="--line: iterates per run at most")
+ap.add_argument("--regular-line", action="store_true", help="the Λ* kernel of the raster line session alone")
+ap.add_argument("--size", type=int, default=128, help="--regular-line: interior points per axis")
 args = ap.parse_args()
 signal.alarm(args.limit)
 
@@ -180,6 +189,42 @@ def line_probe():
     return res
 
 
+def regular_line_probe():
+    z, x, y, _ = synth.regular_line_case(args.size, args.size, args.size, seed=5, nbb=5, nbf=2)    # (the ghosted axes only)
+    n = z.size * x.size * y.size
+    quad = "ul7n12.dat"
+    w, k, dirs = api._regular_directions(quad)
+    A = int((dirs != 0).sum())
+    L = _lib.load()
+    solver = api._regular_solver(z, x, y, n, 0)
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev).manual_seed(5)
+    dz = float(np.diff(z).mean())
+    d_alpha = torch.empty((A, args.nlam, n), dtype=torch.float64, device=dev)
+    for a in range(A):                                         # Δτ = α dz from 1e-3 to 1e3
+        d_alpha[a] = 10.0 ** (6.0 * torch.rand((args.nlam, n), dtype=torch.float64, device=dev, generator=gen) - 3.0) / dz
+    d_diag = torch.empty((args.nlam, n), dtype=torch.float64, device=dev)
+    out = []
+    for i in range(1 + args.reps):                             # one warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        api.check(L.vrt_regular_line_lambda_diagonal_dev(solver._h, k.shape[0], k.ctypes.data_as(_lib.p_dbl),
+                                                         dirs.ctypes.data_as(_lib.p_int), w.ctypes.data_as(_lib.p_dbl), args.nlam,
+                                                         d_alpha.data_ptr(), d_diag.data_ptr(), None))
+        if i:
+            out.append(1e3 * (time.perf_counter() - t0))
+    nbytes = 8 * n * args.nlam * (A + 3)
+    res = {"grid": "regular line", "points": n, "shape_ghosted": [int(z.size), int(x.size), int(y.size)], "nlam": args.nlam,
+           "active_angles": A, "lambda_star_wall": stats(out), "bytes": nbytes,
+           "GB_per_s_at_median": nbytes / statistics.median(out) / 1e6, "diag_max": float(d_diag.max()),
+           "diag_min_interior_is_positive": bool((d_diag.view(args.nlam, z.size, y.size, x.size)[:, 1:-1, 1:-1, 1:-1] > 0).all())}
+    solver.close()
+    return res
+
+
+if args.regular_line:
+    finish(regular_line_probe())
+    sys.exit(0)
 if args.regular:
     finish(regular_probe())
     sys.exit(0)

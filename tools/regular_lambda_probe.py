@@ -7,6 +7,10 @@ at a size it finishes in.
   rocprofv3 --kernel-trace -d OUT -o run -- python tools/regular_lambda_probe.py --size 128 --iters 2
   python tools/regular_lambda_probe.py --phases OUT/run_results.db --iters 2
       the kernel time of an iteration split into its phases (opacity, solves, J reduction, layout, update, rates)
+  python tools/regular_lambda_probe.py --size 128 --iters 8 --operator diagonal
+      the same with vrt_regular_lambda_use_operator(1): Λ* of every iterate's α (k_regular_line_lambda_diagonal) and the ALI
+      update; --hard for ε × 1e-2 and strength × 10, --ng START PERIOD
+      (VRT_LIB_PATH=<an older build> with the operator off times that build: the alternating A/B of profiles/regular_line_ali)
   python tools/regular_lambda_probe.py --oracle --size 32 --iters 1
       the same loop driven by the oracle (orc.line_terms, orc.line_opacity, orc.short_characteristics_up/down,
       orc.calculate_R, orc.revised_populations) on the CPU, one thread
@@ -28,22 +32,26 @@ sys.path.insert(0, ROOT)
 PHASES = (("opacity", ("k_reg_line_opacity",)),
           ("solves", ("k_regular_solve", "k_reg_xy_coefs", "k_reg_xy_march")),
           ("J reduction", ("k_reg_reduce_J",)),
+          ("Λ*", ("k_regular_line_lambda_diagonal",)),
           ("layout", ("k_reg_lam_to_planes", "k_reg_lam_from_planes")),
           ("update", ("k_lambda_update",)),
           ("rates", ("k_rates_populations", "k_line_terms")))
 
 
-def _case(size: int, seed: int):
+def _case(size: int, seed: int, hard: bool = False):
     import voronoirt_amd as vrt
     from voronoirt_amd import synth
     z, x, y, kw = synth.regular_line_case(size, size, size, seed=seed, nbb=51, nbf=20)
+    if hard:                                   # the recipe of tests/test_line_ali_host.hard_case
+        kw["eps"] = np.asarray(kw["eps"]) * 1e-2
+        kw["strength_const"] = kw["strength_const"] * 10.0
     return z, x, y, vrt.LineCase(**kw)
 
 
-def device_run(size: int, iters: int, seed: int) -> dict:
+def device_run(size: int, iters: int, seed: int, operator: str = "", hard: bool = False, ng=None) -> dict:
     import voronoirt_amd as vrt
     from voronoirt_amd import _lib, api
-    z, x, y, case = _case(size, seed)
+    z, x, y, case = _case(size, seed, hard)
     L = _lib.load()
     w, k, dirs = api._regular_directions("ul7n12.dat")
     lc, keep = case.c_struct()
@@ -53,17 +61,32 @@ def device_run(size: int, iters: int, seed: int) -> dict:
     _lib.check(L.vrt_regular_lambda_create(solver._h, k.shape[0], api._d(k), dirs.ctypes.data_as(_lib.p_int), api._d(w),
                                            ctypes.byref(lc), 3, ctypes.byref(h)))
     create_ms = (time.perf_counter() - t0) * 1e3
-    ms, hist = [], []
-    for _ in range(iters):
+    if ng:
+        _lib.check(L.vrt_regular_lambda_set_acceleration(h, 2, int(ng[0]), int(ng[1])))
+    if operator:
+        _lib.check(L.vrt_regular_lambda_use_operator(h, 1))
+    ms, hist, fallback, applied = [], [], 0, []
+    for i in range(iters):
         d = ctypes.c_double()
         t0 = time.perf_counter()
         _lib.check(L.vrt_regular_lambda_iterate(h, ctypes.byref(d)))
         ms.append((time.perf_counter() - t0) * 1e3)
         hist.append(d.value)
+        if operator:
+            op, cnt = ctypes.c_int(), ctypes.c_int64()
+            _lib.check(L.vrt_regular_lambda_get_operator(h, ctypes.byref(op), ctypes.byref(cnt)))
+            fallback += cnt.value
+        if ng:
+            ok = ctypes.c_int()
+            _lib.check(L.vrt_regular_lambda_last_acceleration(h, ctypes.byref(ok), None, None))
+            if ok.value == 1:
+                applied.append(i + 1)
     L.vrt_regular_lambda_destroy(h)
     solver.close()
     n, nlam = case.doppler.size, int(np.asarray(case.lam).size)
     return {"points": n, "shape": [z.size, x.size, y.size], "nlam": nlam, "solves_per_iteration": int((dirs != 0).sum()) * nlam,
+            "operator": operator or "plain", "hard": hard, "ng": list(ng) if ng else None, "ng_applied_after": applied,
+            "fallback_entries": fallback, "library": os.environ.get("VRT_LIB_PATH", "this tree"),
             "create_ms": round(create_ms, 1), "iterate_ms": [round(v, 2) for v in ms], "history": hist}
 
 
@@ -131,13 +154,16 @@ def main() -> None:
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--oracle", action="store_true")
     ap.add_argument("--phases", default="")
+    ap.add_argument("--operator", default="", choices=["", "diagonal"])
+    ap.add_argument("--hard", action="store_true")
+    ap.add_argument("--ng", type=int, nargs=2, default=None, metavar=("START", "PERIOD"))
     a = ap.parse_args()
     if a.phases:
         res = phases(a.phases, a.iters)
     elif a.oracle:
         res = oracle_run(a.size, a.iters, a.seed)
     else:
-        res = device_run(a.size, a.iters, a.seed)
+        res = device_run(a.size, a.iters, a.seed, a.operator, a.hard, a.ng)
     print(json.dumps(res))
 
 

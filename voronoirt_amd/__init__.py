@@ -16,7 +16,7 @@ from .api import (Delaunay_downII, Delaunay_upII, FormalPlan, J_lambda_voronoi, 
                   synth_opacity, synth_opacity_dev, top_intensity, top_intensity_dev, tau_unity, tau_unity_dev,
                   emergent_spectrum, ContinuumCase, Lambda_continuum, Lambda_continuum_regular, continuum_update_dev,
                   lambda_diagonal, continuum_ali_update_dev, lambda_diagonal_regular, line_lambda_diagonal,
-                  lambda_ali_update_dev, lambda_ali_update_native_dev)
+                  line_lambda_diagonal_regular, lambda_ali_update_dev, lambda_ali_update_native_dev)
 from ._lib import VrtError  # noqa: F401
 
 __all__ = ["Delaunay_upII", "Delaunay_downII", "FormalPlan", "J_lambda_voronoi", "VoronoiSites",
@@ -29,5 +29,5 @@ __all__ = ["Delaunay_upII", "Delaunay_downII", "FormalPlan", "J_lambda_voronoi",
            "sample_from_logNH_invT_rootv", "sample_from_temp_gradient", "periodic_axis", "synth_opacity",
            "synth_opacity_dev", "top_intensity", "top_intensity_dev", "tau_unity", "tau_unity_dev", "emergent_spectrum",
            "ContinuumCase", "Lambda_continuum", "Lambda_continuum_regular", "continuum_update_dev", "lambda_diagonal",
-           "continuum_ali_update_dev", "lambda_diagonal_regular", "line_lambda_diagonal", "lambda_ali_update_dev",
-           "lambda_ali_update_native_dev"]
+           "continuum_ali_update_dev", "lambda_diagonal_regular", "line_lambda_diagonal", "line_lambda_diagonal_regular",
+           "lambda_ali_update_dev", "lambda_ali_update_native_dev"]

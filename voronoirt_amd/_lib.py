@@ -241,6 +241,10 @@ PROTOTYPES = {
     "vrt_lambda_ali_update_native_dev": (ctypes.c_int, [vp, c_i64, vp, vp, vp, vp, vp, vp, vp, p_dbl, p_i64, vp]),
     "vrt_lambda_use_operator": (ctypes.c_int, [vp, ctypes.c_int]),
     "vrt_lambda_get_operator": (ctypes.c_int, [vp, p_int, p_i64]),
+    "vrt_regular_line_lambda_diagonal_dev": (ctypes.c_int, [vp, c_i64, p_dbl, p_int, p_dbl, c_i64, vp, vp, vp]),
+    "vrt_regular_line_lambda_diagonal": (ctypes.c_int, [vp, c_i64, p_dbl, p_int, p_dbl, c_i64, c_i64, p_dbl, p_dbl]),
+    "vrt_regular_lambda_use_operator": (ctypes.c_int, [vp, ctypes.c_int]),
+    "vrt_regular_lambda_get_operator": (ctypes.c_int, [vp, p_int, p_i64]),
     "vrt_delaunay_up": (ctypes.c_int, [vp, p_dbl, p_dbl, p_dbl, c_i64, p_dbl, ctypes.c_int, p_dbl]),
     "vrt_delaunay_down": (ctypes.c_int, [vp, p_dbl, p_dbl, p_dbl, c_i64, p_dbl, ctypes.c_int, p_dbl]),
 }

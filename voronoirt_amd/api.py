@@ -1824,14 +1824,18 @@ def J_lambda_regular_line(S, populations, z, x, y, case: LineCase, quadrature: s
 
 def Lambda_regular(eps_conv: float, maxiter: int, z, x, y, case: LineCase, quadrature: str, n_sweeps: int = 3,
                    device: int = 0, ng=None, S0=None, populations0=None, checkpoint=None, checkpoint_every: int = 1,
-                   resume=None):
+                   resume=None, operator=None):
     """Λ_regular (src/lambda_iteration.jl:116-205) with library-owned device state (`vrt_regular_lambda_create` /
     `_iterate` / `_get`): one call per iteration, only the criterion's scalar comes back inside the loop.  The raster
     and `case` as for `J_lambda_regular_line`; every point, ghost border included, is a point of the loop.  Starts
     in LTE with S = B_0; stops like `Lambda_voronoi_host` (criterion, NaN).  Returns (J, S_new, populations (3, n),
     history); ng=(start, period) as for `Lambda_voronoi_host` (`vrt_regular_lambda_set_acceleration`), with the list of
     (iterate, applied, a, b) as a fifth element.  S0, populations0, checkpoint, checkpoint_every, resume as for
-    `Lambda_voronoi_host` (`vrt_regular_lambda_set_state`, the reference's recover_regular)."""
+    `Lambda_voronoi_host` (`vrt_regular_lambda_set_state`, the reference's recover_regular).
+    operator="diagonal": accelerated Λ-iteration with the raster's one-sweep diagonal Λ* formed from every iterate's
+    per-angle α (`vrt_regular_lambda_use_operator`; `line_lambda_diagonal_regular` returns such a Λ*), as
+    `Lambda_voronoi_host(operator="diagonal")` on the other grid; composes with `ng`, checkpoints and `resume`."""
+    ali = _line_operator(operator, False, "Lambda_regular")
     L = _lib.load()
     w, k, dirs = _regular_directions(quadrature)
     lc, keep = case.c_struct()
@@ -1845,6 +1849,8 @@ def Lambda_regular(eps_conv: float, maxiter: int, z, x, y, case: LineCase, quadr
                                           ctypes.byref(lc), int(n_sweeps), ctypes.byref(h)))
         if ng is not None:
             check(L.vrt_regular_lambda_set_acceleration(h, 2, *_ng_settings(ng)))
+        if ali:
+            check(L.vrt_regular_lambda_use_operator(h, 1))
         J, S, pops, history, steps, _ = _session_loop(L, "regular_lambda", h, n, nlam, eps_conv, maxiter, start, checkpoint,
                                                       checkpoint_every, ng, "Lambda_regular")
         return (J, S, pops, history) if ng is None else (J, S, pops, history, steps)
@@ -2046,6 +2052,26 @@ def lambda_diagonal_regular(z, x, y, alpha, quadrature: str, device: int = 0) ->
         diag = np.zeros_like(alpha)
         check(_lib.load().vrt_regular_lambda_diagonal(solver._h, k.shape[0], _d(k), dirs.ctypes.data_as(_lib.p_int), _d(w),
                                                       alpha.shape[1], alpha.shape[1], _d(alpha), _d(diag)))
+        return diag
+    finally:
+        solver.close()
+
+
+def line_lambda_diagonal_regular(z, x, y, alpha_per_angle, quadrature: str, device: int = 0) -> np.ndarray:
+    """Λ* of the line Λ-iteration on a raster (`vrt_regular_line_lambda_diagonal`): `lambda_diagonal_regular` with an α of its
+    own per angle, alpha_per_angle (n_angles, n, nλ) in quadrature order over all nz nx ny points in Julia order (the
+    Doppler-shifted α_tot of the line loop), finite and > 0; the block of a θ = 90 angle is never read.  Returns (n, nλ)."""
+    alpha = _f64(alpha_per_angle)
+    n = int(np.size(z)) * int(np.size(x)) * int(np.size(y))
+    w, k, dirs = _regular_directions(quadrature)
+    if alpha.ndim != 3 or alpha.shape[0] != len(w) or alpha.shape[1] != n:
+        raise ValueError(f"line_lambda_diagonal_regular: alpha_per_angle must be ({len(w)}, {n}, nlam)")
+    nlam = alpha.shape[2]
+    solver = _regular_solver(z, x, y, n, device)
+    try:
+        diag = np.zeros((n, nlam))
+        check(_lib.load().vrt_regular_line_lambda_diagonal(solver._h, k.shape[0], _d(k), dirs.ctypes.data_as(_lib.p_int), _d(w),
+                                                           nlam, nlam, _d(alpha), _d(diag)))
         return diag
     finally:
         solver.close()

@@ -69,5 +69,10 @@ int launch_reduce_J_planes(const vrt_regular *r, const LineSolves &ls, int64_t g
 int launch_regular_lambda_diagonal(const vrt_regular *r, int64_t n_angles, const double *k, const int *dirs,
                                    const double *weights, int64_t nlam, const double *d_alpha_pl, double *d_diag_pl,
                                    hipStream_t st);
+// Λ* of the line Λ-iteration (k_regular_line_lambda_diagonal): d_diag_pl[l][p] += w_a c_a(p; α_a[l]) over the chunk's solves
+// [g0, g0 + cnt), whose α stands in d_alpha_chunk as [g - g0][iz][iy][ix]; in quadrature order, bit-identical for any
+// chunking.  The caller zeroes d_diag_pl before the first chunk.
+int launch_regular_line_lambda_diagonal(const vrt_regular *r, const LineSolves &ls, int64_t g0, int64_t cnt,
+                                        const double *d_alpha_chunk, double *d_diag_pl, hipStream_t st);
 
 }  // namespace vrt

@@ -835,12 +835,64 @@ __device__ __forceinline__ double reg_diag_row(int nx, int n_par, int sc, int pc
 #undef AT
 }
 
+// c_a(p; α): the coefficient of S[p] in I_a[p] after one sweep of angle a (direction k0, k1, k2; up) at the interior
+// point (idx, idy, idz), from that angle's α planes Al ([iz][iy][ix]).  In an xy plane it is b(Δτ) alone (S_u and I_u come
+// from the upwind plane); the row-marched planes: reg_diag_row.  false where the angle never updates the point from its own
+// S: the boundary plane of the angle's direction (I = I_0).  Δτ, the cut and the interpolation indices are those of
+// k_regular_solve for the point's plane.  Shared by the continuum's Λ* (one α for every angle) and the line session's
+// (an α per angle): the same inputs give the same bits in both.
+__device__ __forceinline__ bool reg_diag_angle(int nz, int nx, int ny, int idx, int idy, int idz, double k0, double k1, double k2,
+                                               bool up, const double *__restrict__ z, const double *__restrict__ x,
+                                               const double *__restrict__ y, const double *__restrict__ Al, double &c)
+{
+#define PL(p, ix, iy) (p)[(ix) + nx * (iy)]
+    if (idz == (up ? 0 : nz - 1)) return false;                   // I = I_0 there (:61, :146)
+    const int64_t plane = (int64_t)nx * ny;
+    int sign_x, sign_y;                                           // xy_intersect, functions.jl:430-457
+    if (k1 > 0 && k2 > 0) { sign_x = -1; sign_y = -1; }
+    else if (k1 < 0 && k2 > 0) { sign_x = 1; sign_y = -1; }
+    else if (k1 < 0 && k2 < 0) { sign_x = 1; sign_y = 1; }
+    else if (k1 > 0 && k2 < 0) { sign_x = -1; sign_y = 1; }
+    else { sign_x = 1; sign_y = 1; }
+    const int hx = (sign_x + 1) / 2, hy = (sign_y + 1) / 2;
+    const double r_x = fabs((x[1] - x[0]) / k1), r_y = fabs((y[1] - y[0]) / k2);   // (a vertical ray: inf, cut = 1)
+    const int idz_u = up ? idz - 1 : idz + 1;
+    const double dzp = up ? z[idz] - z[idz - 1] : z[idz + 1] - z[idz];
+    const double r_z = fabs(dzp / k0);
+    int cut = 1;                                                  // argmin([r_z, r_x, r_y]) (:72)
+    double m = r_z;
+    if (r_x < m) { m = r_x; cut = 2; }
+    if (r_y < m) { m = r_y; cut = 3; }
+    const double *Ac = Al + (int64_t)idz * plane, *Au = Al + (int64_t)idz_u * plane;
+    if (cut == 1) {
+        const double r = fabs((z[idz_u] - z[idz]) / k0);
+        const int xl = idx - hx, xu = xl + 1, yl = idy - hy, yu = yl + 1;
+        const double a_u = reg_bilinear(x[idx] + r * k1, y[idy] + r * k2, x[xl], x[xu], y[yl], y[yu], PL(Au, xl, yl),
+                                        PL(Au, xl, yu), PL(Au, xu, yl), PL(Au, xu, yu));
+        double ca, ce;
+        linear_weights_ref_order(r * (PL(Ac, idx, idy) + a_u) / 2.0, ca, c, ce);
+    } else {
+        const double zb1 = up ? z[idz_u] : z[idz], zb2 = up ? z[idz] : z[idz_u];
+        const double *A_lo = up ? Au : Ac, *A_hi = up ? Ac : Au;
+        if (cut == 2) {
+            const double r = fabs((x[1] - x[0]) / k1);
+            c = reg_diag_row<true>(nx, ny, idx, idy, sign_x == 1 ? 1 : nx - 2, sign_x, hy, up, true, !up, r,
+                                   z[idz] + r * k0, r * k2, zb1, zb2, y, A_lo, A_hi, Ac);
+        } else {
+            const double r = fabs((y[1] - y[0]) / k2);
+            c = reg_diag_row<false>(nx, nx, idy, idx, sign_y == 1 ? 1 : ny - 2, sign_y, hx, up, up, !up, r,
+                                    z[idz] + r * k0, r * k1, zb1, zb2, x, A_lo, A_hi, A_hi);
+        }
+    }
+    return true;
+#undef PL
+}
+
 // Λ*[l][p] = Σ_a w_a · (the coefficient of S[p] in I_a[p] after one sweep), the angles in order: the diagonal of one
 // sweep of the raster's Λ, which does not depend on n_sweeps and is <= the diagonal of any number of sweeps (every
-// coefficient of Λ is >= 0).  In an xy plane that coefficient is b(Δτ) alone (S_u and I_u come from the upwind plane);
-// the row-marched planes: reg_diag_row.  Nothing where the angle never updates the point from its own S: the boundary
-// plane of the angle's direction (I = I_0) and every ghost point (a copy of an interior point's I), so Λ* is exactly 0
-// on the ghost border.  Δτ, the cut and the interpolation indices are those of k_regular_solve for the point's plane.
+// coefficient of Λ is >= 0): reg_diag_angle per angle.  Nothing where the angle never updates the point from its own S:
+// the boundary plane of the angle's direction and every ghost point (a copy of an interior point's I), so Λ* is exactly 0
+// on the ghost border.
 // alpha and diag plane-major [l][iz][iy][ix]; one thread per point, ix fastest, grid.y the wavelength.  No atomics: the
 // same inputs give the same bits.  Runs once per session.
 __global__ void __launch_bounds__(256)
@@ -848,7 +900,6 @@ k_regular_lambda_diagonal(int nz, int nx, int ny, int A, RegDiagAngles ang, cons
                           const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ alpha,
                           double *__restrict__ diag)
 {
-#define PL(p, ix, iy) (p)[(ix) + nx * (iy)]
     const int64_t plane = (int64_t)nx * ny, vol = plane * nz;
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= vol) return;
@@ -858,50 +909,58 @@ k_regular_lambda_diagonal(int nz, int nx, int ny, int A, RegDiagAngles ang, cons
     const double *Al = alpha + (int64_t)blockIdx.y * vol;
     double acc = 0.0;
     for (int a = 0; a < A; a++) {
-        const double k0 = ang.k[a][0], k1 = ang.k[a][1], k2 = ang.k[a][2];
-        const bool up = ang.up[a] != 0;
-        if (idz == (up ? 0 : nz - 1)) continue;                   // I = I_0 there (:61, :146)
-        int sign_x, sign_y;                                       // xy_intersect, functions.jl:430-457
-        if (k1 > 0 && k2 > 0) { sign_x = -1; sign_y = -1; }
-        else if (k1 < 0 && k2 > 0) { sign_x = 1; sign_y = -1; }
-        else if (k1 < 0 && k2 < 0) { sign_x = 1; sign_y = 1; }
-        else if (k1 > 0 && k2 < 0) { sign_x = -1; sign_y = 1; }
-        else { sign_x = 1; sign_y = 1; }
-        const int hx = (sign_x + 1) / 2, hy = (sign_y + 1) / 2;
-        const double r_x = fabs((x[1] - x[0]) / k1), r_y = fabs((y[1] - y[0]) / k2);   // (a vertical ray: inf, cut = 1)
-        const int idz_u = up ? idz - 1 : idz + 1;
-        const double dzp = up ? z[idz] - z[idz - 1] : z[idz + 1] - z[idz];
-        const double r_z = fabs(dzp / k0);
-        int cut = 1;                                              // argmin([r_z, r_x, r_y]) (:72)
-        double m = r_z;
-        if (r_x < m) { m = r_x; cut = 2; }
-        if (r_y < m) { m = r_y; cut = 3; }
-        const double *Ac = Al + (int64_t)idz * plane, *Au = Al + (int64_t)idz_u * plane;
         double c;
-        if (cut == 1) {
-            const double r = fabs((z[idz_u] - z[idz]) / k0);
-            const int xl = idx - hx, xu = xl + 1, yl = idy - hy, yu = yl + 1;
-            const double a_u = reg_bilinear(x[idx] + r * k1, y[idy] + r * k2, x[xl], x[xu], y[yl], y[yu], PL(Au, xl, yl),
-                                            PL(Au, xl, yu), PL(Au, xu, yl), PL(Au, xu, yu));
-            double ca, ce;
-            linear_weights_ref_order(r * (PL(Ac, idx, idy) + a_u) / 2.0, ca, c, ce);
-        } else {
-            const double zb1 = up ? z[idz_u] : z[idz], zb2 = up ? z[idz] : z[idz_u];
-            const double *A_lo = up ? Au : Ac, *A_hi = up ? Ac : Au;
-            if (cut == 2) {
-                const double r = fabs((x[1] - x[0]) / k1);
-                c = reg_diag_row<true>(nx, ny, idx, idy, sign_x == 1 ? 1 : nx - 2, sign_x, hy, up, true, !up, r,
-                                       z[idz] + r * k0, r * k2, zb1, zb2, y, A_lo, A_hi, Ac);
-            } else {
-                const double r = fabs((y[1] - y[0]) / k2);
-                c = reg_diag_row<false>(nx, nx, idy, idx, sign_y == 1 ? 1 : ny - 2, sign_y, hx, up, up, !up, r,
-                                        z[idz] + r * k0, r * k1, zb1, zb2, x, A_lo, A_hi, A_hi);
-            }
-        }
+        if (!reg_diag_angle(nz, nx, ny, idx, idy, idz, ang.k[a][0], ang.k[a][1], ang.k[a][2], ang.up[a] != 0, z, x, y, Al, c))
+            continue;
         acc = acc + ang.w[a] * c;
     }
     *out = acc;
-#undef PL
+}
+
+// The same with an α of its own per angle, for the line session (vrt_regular_lambda_use_operator), whose α_tot changes
+// with every iterate and stands only in the chunk workspace: Λ*[l][p] += w_a c_a(p; α_a[l]) over the chunk's solves
+// g = a nlam + l in [g0, g0 + cnt), alpha = [g - g0][iz][iy][ix].  Accumulated like k_reg_reduce_J: one thread per point
+// and wavelength of the chunk (grid.y), which reads diag[l][p], adds the chunk's angles of that wavelength in quadrature
+// order and writes once, so that Λ* is bit-identical for any chunking (the planes are zeroed before the first chunk; the
+// ghost border is never written).  ka, w per active angle, up per solve (LineSolves).  ix fastest over the lanes: the
+// stencil reads of neighbouring lanes fall into the same lines; no gathers, no atomics.
+__global__ void __launch_bounds__(256)
+k_regular_line_lambda_diagonal(int nz, int nx, int ny, int nlam, int64_t g0, int64_t cnt, int64_t nl,
+                               const double *__restrict__ ka, const double *__restrict__ w, const int *__restrict__ up,
+                               const double *__restrict__ z, const double *__restrict__ x, const double *__restrict__ y,
+                               const double *__restrict__ alpha, double *__restrict__ diag)
+{
+    const int64_t plane = (int64_t)nx * ny, vol = plane * nz;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= vol) return;
+    const int idx = (int)(t % nx), idy = (int)((t / nx) % ny), idz = (int)(t / plane);
+    if (idx == 0 || idx == nx - 1 || idy == 0 || idy == ny - 1) return;
+    for (int64_t yy = blockIdx.y; yy < nl; yy += gridDim.y) {
+        const int64_t g1 = g0 + yy;                               // the chunk's first solve of wavelength g1 % nlam
+        double *out = diag + (g1 % nlam) * vol + t;
+        double acc = *out;
+        for (int64_t g = g1; g < g0 + cnt; g += nlam) {
+            const int64_t a = g / nlam;
+            double c;
+            if (!reg_diag_angle(nz, nx, ny, idx, idy, idz, ka[3 * a], ka[3 * a + 1], ka[3 * a + 2], up[g] != 0, z, x, y,
+                                alpha + (g - g0) * vol, c))
+                continue;
+            acc = acc + w[a] * c;
+        }
+        *out = acc;
+    }
+}
+
+int launch_regular_line_lambda_diagonal(const vrt_regular *r, const LineSolves &ls, int64_t g0, int64_t cnt,
+                                        const double *d_alpha_chunk, double *d_diag_pl, hipStream_t st)
+{
+    const int64_t vol = r->nz * r->nx * r->ny, nl = std::min(cnt, ls.nlam);
+    hipLaunchKernelGGL(k_regular_line_lambda_diagonal, dim3((unsigned)((vol + 255) / 256), (unsigned)std::min<int64_t>(nl, 65535)),
+                       dim3(256), 0, st, (int)r->nz, (int)r->nx, (int)r->ny, (int)ls.nlam, g0, cnt, nl, (const double *)ls.d_ka,
+                       (const double *)ls.d_w, (const int *)ls.d_up, (const double *)r->d_g, r->d_g + r->nz,
+                       r->d_g + r->nz + r->nx, d_alpha_chunk, d_diag_pl);
+    VRT_HIP_TRY(hipGetLastError());
+    return VRT_OK;
 }
 
 int launch_regular_lambda_diagonal(const vrt_regular *r, int64_t n_angles, const double *k, const int *dirs,

@@ -16,6 +16,11 @@
 // solves (regular_solve_planes: no transposes, I_0 per solve = B_0's bottom plane or zeros), and the reduction of
 // the chunk's I into J (k_reg_reduce_J).  J[l] is summed angle after angle in quadrature order (J_λ .+= weights[i]
 // .* I, :39, :47), each element by one thread, so that J is bit-identical for any chunking.  I never leaves the device.
+//
+// The diagonal operator (vrt_regular_lambda_use_operator).  With it on, every chunk also adds its solves' share
+// of Λ* = Σ_a w_a c_a(p; α_a[l]) right after its opacity, from the α the chunk's solves read
+// (launch_regular_line_lambda_diagonal, vrt_regular.hip: the same one-thread-per-element order, so Λ* is bit-identical
+// for any chunking too), and the update is the ALI one of the Voronoi line session.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -253,12 +258,15 @@ int launch_reduce_J_planes(const vrt_regular *r, const LineSolves &ls, int64_t g
 
 namespace {
 
-// dJ_pl ([l][iz][iy][ix]) = Σ_a w_a I_a over every solve, from the plane-major S and up-solve I_0 planes
+// dJ_pl ([l][iz][iy][ix]) = Σ_a w_a I_a over every solve, from the plane-major S and up-solve I_0 planes.  d_diag_pl, if
+// not NULL: also Λ* of this pass's per-angle α_tot into those planes (launch_regular_line_lambda_diagonal), chunk after
+// chunk while the chunk's α stands in the workspace; NULL: no launch more than without it
 int line_J_pass(vrt_regular *r, const LineSolves &ls, const LinePoint &lp, const double *dS_pl, const double *dI0_pl,
-                const double *dI0_zero, int n_sweeps, double *dJ_pl, hipStream_t st)
+                const double *dI0_zero, int n_sweeps, double *dJ_pl, hipStream_t st, double *d_diag_pl = nullptr)
 {
     const int64_t nz = r->nz, nx = r->nx, ny = r->ny, vol = nz * nx * ny, nlam = ls.nlam;
     VRT_HIP_TRY(hipMemsetAsync(dJ_pl, 0, sizeof(double) * (size_t)(nlam * vol), st));
+    if (d_diag_pl) VRT_HIP_TRY(hipMemsetAsync(d_diag_pl, 0, sizeof(double) * (size_t)(nlam * vol), st));
     const int64_t n_solve = ls.A * nlam;
     const unsigned bx = (unsigned)((vol + 255) / 256);
     int rc;
@@ -269,6 +277,7 @@ int line_J_pass(vrt_regular *r, const LineSolves &ls, const LinePoint &lp, const
         hipLaunchKernelGGL(k_reg_line_opacity, dim3(bx, (unsigned)std::min<int64_t>(na, 65535)), dim3(256), 0, st, (int)nz,
                            (int)nx, (int)ny, (int)nlam, g0, cnt, a0, na, (const double *)ls.d_ka, lp, r->d_A);
         VRT_HIP_TRY(hipGetLastError());
+        if (d_diag_pl && (rc = launch_regular_line_lambda_diagonal(r, ls, g0, cnt, r->d_A, d_diag_pl, st))) return rc;
         if ((rc = regular_solve_planes(r, cnt, ls.hk.data() + 3 * g0, ls.d_ks + 3 * g0, ls.d_up + g0, dS_pl, nlam, g0, r->d_A,
                                        dI0_pl, dI0_zero, n_sweeps, st)))
             return rc;
@@ -298,6 +307,11 @@ struct vrt_regular_lambda {
     DevBuf<unsigned long long> d_scalars;
     int64_t iterations = 0;
     NgState ng;                         // vrt_regular_lambda_set_acceleration (off: nothing allocated, nothing run)
+    // vrt_regular_lambda_use_operator (0: nothing allocated, nothing run): Λ* of the current iterate's α, plane-major as
+    // the chunks leave it and as (n, nlam) rows for the update; nothing of it survives an iterate
+    int op = 0;
+    DevBuf<double> d_diag_pl, d_diag;
+    int64_t fallback_last = 0;          // entries of the last iterate that took the plain update (den not > 0)
 };
 
 extern "C" {
@@ -388,7 +402,7 @@ int vrt_regular_lambda_create(vrt_regular *r, int64_t n_angles, const double *k,
         VRT_S(s->d_J_pl.alloc(nS));
         VRT_S(s->d_I0_pl.alloc((size_t)plane * nl));
         VRT_S(s->d_zero.alloc((size_t)plane));
-        VRT_S(s->d_scalars.alloc(2));
+        VRT_S(s->d_scalars.alloc(kUpdateWords));
         // (J, R and γ are those of "no iteration yet": zeros)
         VRT_HIP_TRY(hipMemsetAsync(s->d_J, 0, sizeof(double) * nS, st));
         VRT_HIP_TRY(hipMemsetAsync(s->line.d_R, 0, sizeof(double) * 9 * n, st));
@@ -420,10 +434,16 @@ int vrt_regular_lambda_iterate(vrt_regular_lambda *s, double *max_rel_change)
         lp.lambda = small_view(line.d_small, nlam, line.k.blocks).lambda; lp.velocity = line.d_velocity; lp.doppler = line.d_doppler;
         lp.gamma = line.d_gamma; lp.strength = line.d_strength; lp.alpha_cont = line.d_alpha_cont; lp.lambda0 = line.k.lambda0;
         lp.c0 = line.k.c0;
-        if ((rc = line_J_pass(r, s->ls, lp, s->d_S_pl, s->d_I0_pl, s->d_zero, s->n_sweeps, s->d_J_pl, st))) return rc;
+        // (with the operator on also Λ* of that α, formed beside the solves that read the same workspace)
+        if ((rc = line_J_pass(r, s->ls, lp, s->d_S_pl, s->d_I0_pl, s->d_zero, s->n_sweeps, s->d_J_pl, st,
+                              s->op ? s->d_diag_pl.get() : nullptr)))
+            return rc;
         if ((rc = launch_from_planes(r, nlam, s->d_J_pl, s->d_J, st))) return rc;
-        // S_new = (1 - ε) J + ε B_0 (:169-171) and the criterion's scalar; S_new also plane-major for the next solves
-        if ((rc = launch_lambda_update(n, nlam, nlam, s->d_J, s->d_B0, line.d_eps, s->d_S[s->sc], s->d_S[s->sc ^ 1], s->d_scalars, st)))
+        if (s->op && (rc = launch_from_planes(r, nlam, s->d_diag_pl, s->d_diag, st))) return rc;
+        // S_new = (1 - ε) J + ε B_0 (:169-171) and the criterion's scalar; S_new also plane-major for the next solves.  With
+        // the operator on (d_diag is NULL otherwise): the ALI update
+        if ((rc = launch_lambda_update(n, nlam, nlam, s->d_J, s->d_B0, line.d_eps, s->d_S[s->sc], s->d_S[s->sc ^ 1], s->d_scalars, st,
+                                       s->op ? s->d_diag.get() : nullptr)))
             return rc;
         s->sc ^= 1;
         if ((rc = launch_to_planes(r, nlam, s->d_S[s->sc], s->d_S_pl, st))) return rc;
@@ -431,12 +451,13 @@ int vrt_regular_lambda_iterate(vrt_regular_lambda *s, double *max_rel_change)
         if ((rc = launch_rates_populations(line.rates_in(), RatesJ::from_rows(s->d_J, nlam), line.d_R, s->d_pops[s->pc ^ 1], st)))
             return rc;
         s->pc ^= 1;
-        unsigned long long h[2] = {0, 0};
-        VRT_HIP_TRY(hipMemcpyAsync(h, s->d_scalars, sizeof(h), hipMemcpyDeviceToHost, st));
+        unsigned long long h[kUpdateWords] = {0, 0, 0};      // (the third word: the ALI update's, in the same copy)
+        VRT_HIP_TRY(hipMemcpyAsync(h, s->d_scalars, (s->op ? 3 : 2) * sizeof(h[0]), hipMemcpyDeviceToHost, st));
         VRT_HIP_TRY(hipStreamSynchronize(st));
         double d;
         std::memcpy(&d, &h[0], sizeof(double));
         *max_rel_change = h[1] ? std::nan("") : d;
+        s->fallback_last = (int64_t)h[2];
         r->timed = false;                                    // (the handle's events saw only the last chunk)
         s->iterations++;
         if (s->ng.order) {
@@ -464,6 +485,110 @@ int vrt_regular_lambda_set_acceleration(vrt_regular_lambda *s, int order, int st
         if ((rc = use_device(s->device))) return rc;
         VRT_HIP_TRY(hipStreamSynchronize(s->st));
         return ng_configure(s->ng, order, start, period, (size_t)(s->n * s->nlam));
+    });
+}
+
+int vrt_regular_lambda_use_operator(vrt_regular_lambda *s, int op)
+{
+    if (!s) return fail(VRT_EINVAL, "NULL session");
+    if (op != 0 && op != 1) return fail(VRT_EINVAL, "operator must be 0 (plain) or 1 (diagonal)");
+    return guarded([&] {
+        int rc = use_device(s->device);
+        if (rc) return rc;
+        if (op == s->op) return (int)VRT_OK;
+        VRT_HIP_TRY(hipStreamSynchronize(s->st));
+        if (op) {
+            // both arrays beside the session: it is untouched unless both exist
+            const size_t nS = (size_t)s->n * (size_t)s->nlam;
+            DevBuf<double> pl, rows;
+            if ((rc = pl.alloc(nS)) || (rc = rows.alloc(nS))) return rc;
+            s->d_diag_pl = std::move(pl);
+            s->d_diag = std::move(rows);
+        } else {
+            s->d_diag_pl = DevBuf<double>();
+            s->d_diag = DevBuf<double>();
+        }
+        s->op = op;
+        s->fallback_last = 0;
+        s->ng.have = 0;                                      // iterates of another fixed-point map are no history of this one
+        return (int)VRT_OK;
+    });
+}
+
+int vrt_regular_lambda_get_operator(const vrt_regular_lambda *s, int *op, int64_t *fallback_entries_last_iterate)
+{
+    if (!s || !op) return fail(VRT_EINVAL, "NULL argument");
+    *op = s->op;
+    if (fallback_entries_last_iterate) *fallback_entries_last_iterate = s->fallback_last;
+    return VRT_OK;
+}
+
+// Λ* of per-angle α planes [a][l][iz][iy][ix] (active angles in order) into d_diag_pl [l][iz][iy][ix]: the session's kernel
+// on the whole solve list as one chunk
+static int line_diagonal_planes(vrt_regular *r, int64_t n_angles, const double *k, const int *dirs, const double *weights,
+                                int64_t nlam, const double *d_alpha_pl, double *d_diag_pl, hipStream_t st)
+{
+    LineSolves ls;
+    int rc = line_solves_init(ls, r, n_angles, k, dirs, weights, nlam);
+    if (rc) return rc;
+    const int64_t vol = r->nz * r->nx * r->ny;
+    VRT_HIP_TRY(hipMemsetAsync(d_diag_pl, 0, sizeof(double) * (size_t)(nlam * vol), st));
+    if (ls.A > 0 && (rc = launch_regular_line_lambda_diagonal(r, ls, 0, ls.A * nlam, d_alpha_pl, d_diag_pl, st))) return rc;
+    VRT_HIP_TRY(hipStreamSynchronize(st));                   // (the solve list goes here)
+    return VRT_OK;
+}
+
+int vrt_regular_line_lambda_diagonal_dev(vrt_regular *r, int64_t n_angles, const double *k, const int *dirs, const double *weights,
+                                         int64_t nlam, const double *d_alpha_pl, double *d_diag_pl, void *stream)
+{
+    if (!r || !k || !dirs || !weights || !d_alpha_pl || !d_diag_pl) return fail(VRT_EINVAL, "NULL argument");
+    if (nlam < 1) return fail(VRT_EINVAL, "need nlam >= 1");
+    int rc = check_angles(n_angles, k, dirs);
+    if (rc) return rc;
+    return guarded([&] {
+        if ((rc = use_device(r->device))) return rc;
+        return line_diagonal_planes(r, n_angles, k, dirs, weights, nlam, d_alpha_pl, d_diag_pl, (hipStream_t)stream);
+    });
+}
+
+int vrt_regular_line_lambda_diagonal(vrt_regular *r, int64_t n_angles, const double *k, const int *dirs, const double *weights,
+                                     int64_t nlam, int64_t ld, const double *alpha, double *diag)
+{
+    if (!r || !k || !dirs || !weights || !alpha || !diag) return fail(VRT_EINVAL, "NULL argument");
+    if (nlam < 1 || ld < nlam) return fail(VRT_EINVAL, "need nlam >= 1 and ld >= nlam");
+    int rc = check_angles(n_angles, k, dirs);
+    if (rc) return rc;
+    return guarded([&] {
+        const int64_t n = r->nz * r->nx * r->ny;
+        int64_t A = 0;
+        for (int64_t a = 0; a < n_angles; a++) {
+            if (dirs[a] == 0) continue;                      // (never read)
+            A++;
+            for (int64_t i = 0; i < n; i++)
+                for (int64_t l = 0; l < nlam; l++) {
+                    const double v = alpha[(a * n + i) * ld + l];
+                    if (!std::isfinite(v) || !(v > 0.0)) return fail(VRT_EINVAL, "alpha must be finite and > 0 everywhere");
+                }
+        }
+        if ((rc = use_device(r->device))) return rc;
+        const size_t nS = (size_t)n * (size_t)nlam, row = sizeof(double) * (size_t)nlam, pitch = sizeof(double) * (size_t)ld;
+        DevBuf<double> d_rows, d_alpha_pl, d_diag_pl;
+        if ((rc = d_rows.alloc(nS)) || (rc = d_alpha_pl.alloc(nS * (size_t)std::max<int64_t>(A, 1))) || (rc = d_diag_pl.alloc(nS)))
+            return rc;
+        hipStream_t st = nullptr;
+        int64_t b = 0;
+        for (int64_t a = 0; a < n_angles; a++) {             // the active angles' rows, one after the other, into planes
+            if (dirs[a] == 0) continue;
+            VRT_HIP_TRY(hipMemcpy2DAsync(d_rows, row, alpha + a * n * ld, pitch, row, (size_t)n, hipMemcpyHostToDevice, st));
+            if ((rc = launch_to_planes(r, nlam, d_rows, d_alpha_pl + (size_t)b * nS, st))) return rc;
+            b++;
+        }
+        if ((rc = line_diagonal_planes(r, n_angles, k, dirs, weights, nlam, d_alpha_pl, d_diag_pl, st))) return rc;
+        if ((rc = launch_from_planes(r, nlam, d_diag_pl, d_rows, st))) return rc;
+        VRT_HIP_TRY(hipStreamSynchronize(st));
+        // (the padding columns of diag stay as they came)
+        VRT_HIP_TRY(hipMemcpy2D(diag, pitch, d_rows, row, row, (size_t)n, hipMemcpyDeviceToHost));
+        return VRT_OK;
     });
 }
 
