@@ -1095,7 +1095,9 @@ int vrt_regular_lambda_get_operator(const vrt_regular_lambda *s, int *op, int64_
  * up solve's characteristic traced back downward (plane iz at x + s k_x, y + s k_y, s = (z_top - z[iz]) / |k_z|,
  * alpha interpolated bilinearly, trapezoid as cumtrapz); d_height (nlam, ny, nx) = the z of the first argmin
  * |tau - 1|.  At k = (+-1, 0, 0) this is write_tau_unity(DATA) exactly; the inclined reference's defects are not
- * reproduced.  Runs on the current HIP device and synchronises `stream`.
+ * reproduced.  Non-finite alpha follows Julia's argmin: the first plane from the top whose tau is NaN
+ * is the minimum, and a lateral fraction of exactly 0 takes the grid value without reading the other node, so that at
+ * k = (+-1, 0, 0) a column depends on its own values alone.  Runs on the current HIP device and synchronises `stream`.
  *
  * Every argument is checked before the device is touched (k_z = 0 where a march needs it, |k| != 1, nlam < 1, axes,
  * NULL pointers: VRT_EINVAL).  The host-pointer forms stage the arrays through `device` and return when done. */

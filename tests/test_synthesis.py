@@ -216,6 +216,13 @@ def test_tau_unity_inclined_matches_corrected_geometry(small, fields, th, ph):
     clear = (d[..., 1] - d[..., 0]) > 1e-9
     assert clear.mean() > 0.9
     assert np.array_equal(H[clear], ref[clear])
+    # every column, none left out: the plane is one of the exact reference's candidates (oracle/synth_ref.py)
+    from oracle import synth_ref
+    dx, dy = (x[-1] - x[0]) / (x.size - 1), (y[-1] - y[0]) / (y.size - 1)
+    cands = synth_ref.tau_candidates(*synth_ref.tau_exact(A[:, 1:-1, 1:-1], z, dx, dy, k))
+    planes = np.searchsorted(z, H).ravel()
+    assert np.array_equal(z[planes], H.ravel())
+    assert all(int(p) in c for p, c in zip(planes, cands))
 
 
 def test_tau_unity_uniform_alpha_is_vertical_of_alpha_over_mu(small):

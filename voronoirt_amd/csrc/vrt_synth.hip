@@ -8,10 +8,12 @@
 // FIRST argmin |tau - 1| (Julia's argmin), top plane first.
 //
 // At k = (+-1, 0, 0) the lateral offsets are exactly zero, every alpha is a grid value and the steps are |dz|: the
-// result is write_tau_unity(DATA) (:434-490) bit for bit.  The inclined reference (:492-576) is NOT reproduced in three
-// respects, all defects there: its lateral offset uses the step r of the current plane instead of the path s
-// accumulated from the top, its horizontal sign (x - r k_x) is opposite to the solver's upwind point (x + s k_x), and
-// its upper wrap assigns to misspelled variables (x_mrx, y_mrx), so a point past the upper edge is never wrapped.
+// result is write_tau_unity(DATA) (:434-490) bit for bit, non-finite alpha included: the first plane whose tau is NaN
+// is the minimum (Julia's argmin), and a zero fraction does not read the neighbouring column.  The inclined reference
+// (:492-576) is NOT reproduced in three respects, all defects there: its lateral offset uses the step r of the current
+// plane instead of the path s accumulated from the top, its horizontal sign (x - r k_x) is opposite to the solver's
+// upwind point (x + s k_x), and its upper wrap assigns to misspelled variables (x_mrx, y_mrx), so a point past the
+// upper edge is never wrapped.
 //
 // One thread per (wavelength, column); alpha in the ghosted layout of vrt_synth_opacity_dev (nlam, ny + 2, nx + 2, nz)
 // numpy order, z fastest: a thread walks its own column downward, and the neighbouring columns of the bilinear
@@ -70,12 +72,22 @@ k_tau_unity(TauArgs ta)
         double tx, ty;
         tau_cell(s * ta.kx / ta.dx, ix, nx, i0, i1, tx);
         tau_cell(s * ta.ky / ta.dy, iy, ny, j0, j1, ty);
-        const double q00 = node(i0, j0, iz), q10 = node(i1, j0, iz), q01 = node(i0, j1, iz), q11 = node(i1, j1, iz);
-        const double f0 = q00 + tx * (q10 - q00), f1 = q01 + tx * (q11 - q01);   // (a zero fraction: the grid value)
-        const double a = f0 + ty * (f1 - f0);
+        // a zero fraction takes the grid value and does not read the other node: q + 0 (q' - q) is q for finite q',
+        // but NaN for a NaN or Inf q' that the algorithm never uses (at k = (+-1, 0, 0): the neighbouring column)
+        auto along_x = [&](int64_t j) {
+            const double q0 = node(i0, j, iz);
+            return tx != 0.0 ? q0 + tx * (node(i1, j, iz) - q0) : q0;
+        };
+        const double f0 = along_x(j0);
+        double a = f0;
+        if (ty != 0.0) a = f0 + ty * (along_x(j1) - f0);
         const double r = fabs((z[iz + 1] - z[iz]) / ta.kz);
         tau = tau + 0.5 * r * (a + prev);                        // cumtrapz: 0.5*abs(X[i] - X[i-1])*(Y[i] + Y[i-1])
         const double d = fabs(tau - 1.0);
+        if (d != d) {                                            // Julia's argmin: the first NaN is the minimum
+            arg = iz;
+            break;
+        }
         if (d < best) {
             best = d;
             arg = iz;
