@@ -959,6 +959,8 @@ int vrt_regular_continuum_create(vrt_regular *r, int64_t n_angles, const double 
                                  vrt_regular_continuum **out);
 int vrt_regular_continuum_iterate(vrt_regular_continuum *s, double *max_rel_change);
 int vrt_regular_continuum_get(vrt_regular_continuum *s, double *J, double *S);
+/* The new S and its plane-major copy are staged beside the session and swapped in once both are complete: a failure
+ * leaves the session as it was, at the price of two transient n·nλ arrays during the call. */
 int vrt_regular_continuum_set_source(vrt_regular_continuum *s, const double *S);
 int vrt_regular_continuum_set_acceleration(vrt_regular_continuum *s, int order, int start, int period);
 int vrt_regular_continuum_last_acceleration(const vrt_regular_continuum *s, int *applied, double sums[5],

@@ -449,6 +449,21 @@ def test_gpu_regular_session_takes_an_ng_step(raster):
         solver.close()
 
 
+@pytest.mark.gpu
+def test_gpu_regular_session_takes_an_ng_step_on_a_raster_of_odd_size():
+    """5 x 5 x 5 ghosted points x 3 wavelengths (synth.three_wavelength_line_case): n nλ = 375 is odd, so the range the step
+    works on ends in a tail entry behind the dense pairs (the 16 x 12 x 11 x 33 raster above has an even count)"""
+    z, x, y, kw = synth.three_wavelength_line_case(5, 3, 3, seed=7)
+    solver, case, (plain, acc), _ = _regular_sessions((z, x, y, vrt.LineCase(**kw)), 2)
+    try:
+        assert (plain.n, plain.nlam) == (125, 3)
+        _check_session_step(plain, acc, lambda S, pops: _regular_oracle_step(case, z, x, y, S, pops), "regular, odd")
+    finally:
+        plain.close()
+        acc.close()
+        solver.close()
+
+
 # ---- 7: it pays -----------------------------------------------------------------------------------------------------------------
 def _pays(plain, fast):
     J0, S0, p0, h0 = plain

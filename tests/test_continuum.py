@@ -367,3 +367,13 @@ def test_gpu_continuum_converges_with_ng_on_the_raster(raster):
     z, x, y, case = raster
     run = lambda **kw: vrt.Lambda_continuum_regular(1e-4, 400, z, x, y, case, QUAD, **kw)
     _pays("raster 16 x 12 x 11 x 2", run(), run(ng=(4, 4)), run(ng=(4, 4)), case.thick())
+
+
+def test_gpu_continuum_converges_with_ng_on_a_raster_of_odd_size():
+    """5 x 5 x 5 ghosted points x 3 wavelengths: n nλ = 375 is odd, so the range Ng works on ends in a tail entry behind the
+    dense pairs (every other raster case here has an even count)"""
+    z, x, y, kw = synth.regular_continuum_case(5, 3, 3, 7, 3)
+    case = vrt.ContinuumCase(**kw)
+    assert (case.n, case.nlam) == (125, 3)
+    run = lambda **kw: vrt.Lambda_continuum_regular(1e-4, 400, z, x, y, case, QUAD, **kw)
+    _pays("raster 5 x 5 x 5 x 3", run(), run(ng=(4, 4)), run(ng=(4, 4)), case.thick())

@@ -792,16 +792,8 @@ static int lambda_update_call(vrt_grid *g, double *max_rel_change, hipStream_t s
     if (!g->d_scalars && (rc = g->d_scalars.alloc(kUpdateWords))) return rc;
     unsigned long long *d_res = g->d_scalars;
     rc = launch(d_res);
-    unsigned long long h[3] = {0, 0, 0};
-    const size_t words = fallback_entries ? 3 : 2;
-    if (!rc && hipMemcpyAsync(h, d_res, words * sizeof(h[0]), hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ENODEVICE;
-    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = VRT_ENODEVICE;
-    if (rc) return rc == VRT_ENODEVICE ? fail(rc, std::string("HIP error in ") + what) : rc;
-    double d;
-    std::memcpy(&d, &h[0], sizeof(double));
-    *max_rel_change = h[1] ? std::nan("") : d;
-    if (fallback_entries) *fallback_entries = (int64_t)h[2];
-    return VRT_OK;
+    if (!rc) rc = read_criterion(d_res, fallback_entries ? 3 : 2, st, max_rel_change, fallback_entries);
+    return rc == VRT_ENODEVICE ? fail(rc, std::string("HIP error in ") + what) : rc;
 }
 
 }  // namespace vrt

@@ -35,7 +35,7 @@
 #include <vector>
 
 #include "vrt_device.h"
-#include "vrt_regular.h"
+#include "vrt_raster_store.h"
 #include "vrt_source_store.h"
 
 namespace vrt {
@@ -312,19 +312,6 @@ int check_min_den(int64_t total, const double *d_eps, const double *d_diag, unsi
     return VRT_OK;
 }
 
-// the three words of an update -> the criterion's scalar (NaN like Julia's maximum) and the thick count; synchronises st
-int read_criterion(const unsigned long long *d_result, hipStream_t st, double *max_rel_change, int64_t *n_thick)
-{
-    unsigned long long h[3] = {0, 0, 0};
-    VRT_HIP_TRY(hipMemcpyAsync(h, d_result, sizeof(h), hipMemcpyDeviceToHost, st));
-    VRT_HIP_TRY(hipStreamSynchronize(st));
-    double d;
-    std::memcpy(&d, &h[0], sizeof(double));
-    *max_rel_change = h[1] ? std::nan("") : d;
-    if (n_thick) *n_thick = (int64_t)h[2];
-    return VRT_OK;
-}
-
 // ---- host checks, before the device is touched ------------------------------------------------------------------------
 int check_case(const vrt_continuum_case *cc, int64_t n)
 {
@@ -381,10 +368,9 @@ struct vrt_regular_continuum {
     double eps_thick = 0;
     LineSolves ls;
     Stream st;
-    DevBuf<double> d_B0, d_eps, d_J;    // per point, Julia order, (n, nlam)
-    DevBuf<double> d_S[2];              // [sc]: the last S_new
-    int sc = 0;
-    DevBuf<double> d_A_pl, d_S_pl, d_J_pl, d_I0_pl, d_zero;     // plane-major, wavelength slowest
+    RasterStore sj;                     // S and J, rows and planes, and what the solves start from (vrt_raster_store.h)
+    DevBuf<double> d_B0, d_eps;         // per point, Julia order, (n, nlam)
+    DevBuf<double> d_A_pl;              // α plane-major, wavelength slowest
     DevBuf<unsigned long long> d_scalars;
     int64_t iterations = 0;
     NgState ng;
@@ -436,15 +422,16 @@ static int continuum_J_pass(vrt_regular_continuum *s, hipStream_t st)
 {
     vrt_regular *r = s->r;
     const LineSolves &ls = s->ls;
+    const RasterStore &sj = s->sj;
     const int64_t vol = s->n, nlam = s->nlam, n_solve = ls.A * nlam;
-    VRT_HIP_TRY(hipMemsetAsync(s->d_J_pl, 0, sizeof(double) * (size_t)(nlam * vol), st));
+    VRT_HIP_TRY(hipMemsetAsync(sj.J_planes(), 0, sizeof(double) * (size_t)(nlam * vol), st));
     int rc;
     for (int64_t g0 = 0; g0 < n_solve; g0 += ls.chunk) {
         const int64_t cnt = std::min(ls.chunk, n_solve - g0);
-        if ((rc = regular_solve_planes(r, cnt, ls.hk.data() + 3 * g0, ls.d_ks + 3 * g0, ls.d_up + g0, s->d_S_pl, nlam, g0,
-                                       s->d_A_pl, s->d_I0_pl, s->d_zero, s->n_sweeps, st, /*alpha_per_lam=*/true)))
+        if ((rc = regular_solve_planes(r, cnt, ls.hk.data() + 3 * g0, ls.d_ks + 3 * g0, ls.d_up + g0, sj.S_planes(), nlam, g0,
+                                       s->d_A_pl, sj.I0_planes(), sj.zero_plane(), s->n_sweeps, st, /*alpha_per_lam=*/true)))
             return rc;
-        if ((rc = launch_reduce_J_planes(r, ls, g0, cnt, s->d_J_pl, st))) return rc;
+        if ((rc = launch_reduce_J_planes(r, ls, g0, cnt, sj.J_planes(), st))) return rc;
     }
     return VRT_OK;
 }
@@ -468,7 +455,7 @@ int vrt_continuum_update_dev(vrt_grid *g, int64_t nlam, int64_t ld, const double
         hipStream_t st = (hipStream_t)stream;
         if ((rc = launch_continuum_update(g->n, nlam, ld, dJ, dB, deps, nullptr, eps_thick, dS_old, dS_new, g->d_scalars, st)))
             return rc;
-        return read_criterion(g->d_scalars, st, max_rel_change, n_thick);
+        return read_criterion(g->d_scalars, 3, st, max_rel_change, n_thick);
     });
 }
 
@@ -487,7 +474,7 @@ int vrt_continuum_ali_update_dev(vrt_grid *g, int64_t nlam, int64_t ld, const do
         hipStream_t st = (hipStream_t)stream;
         if ((rc = launch_continuum_update(g->n, nlam, ld, dJ, dB, deps, d_diag, eps_thick, dS_old, dS_new, g->d_scalars, st)))
             return rc;
-        return read_criterion(g->d_scalars, st, max_rel_change, n_thick);
+        return read_criterion(g->d_scalars, 3, st, max_rel_change, n_thick);
     });
 }
 
@@ -604,20 +591,12 @@ int vrt_continuum_iterate(vrt_continuum *s, double *max_rel_change)
                 return rc;
             sj.swap_rows();
         }
-        if ((rc = read_criterion(s->d_scalars, st, max_rel_change, nullptr))) return rc;
+        if ((rc = read_criterion(s->d_scalars, 3, st, max_rel_change))) return rc;
         if ((rc = patch_chain_check(p))) return rc;          // a chained sweep that gave up: THIS iteration's results are invalid
         s->iterations++;
-        if (s->ng.order) {
-            // history copy or Ng step on the S of the plain update (native: the up-order copy; an accepted x_acc becomes that
-            // copy and the down-order copy is rewritten from it, value for value)
-            if ((rc = ng_after_iterate(s->ng, s->iterations, sj.ng_S(), sj.ng_count(), sj.ng_range(), st))) return rc;
-            if (s->ng.last_applied == 1 && sj.two_orders()) {
-                if ((rc = sj.mirror_down(st))) return rc;
-                VRT_HIP_TRY(hipStreamSynchronize(st));
-            }
-        } else
-            s->ng.last_applied = 0;
-        return VRT_OK;
+        // history copy or Ng step on the S of the plain update (native: the up-order copy; an accepted x_acc becomes that copy
+        // and the down-order copy is rewritten from it, value for value)
+        return ng_after_update(s->ng, s->iterations, sj, st);
     });
 }
 
@@ -748,7 +727,7 @@ int vrt_regular_continuum_create(vrt_regular *r, int64_t n_angles, const double 
     int rc = check_angles(n_angles, k, dirs);
     if (rc) return rc;
     return guarded([&] {
-        const int64_t vol = r->nz * r->nx * r->ny, plane = r->nx * r->ny, nlam = cc->nlam;
+        const int64_t vol = r->nz * r->nx * r->ny, nlam = cc->nlam;
         if ((rc = check_case(cc, vol))) return rc;
         if ((rc = use_device(r->device))) return rc;
         std::unique_ptr<vrt_regular_continuum> s(new vrt_regular_continuum());
@@ -769,21 +748,11 @@ int vrt_regular_continuum_create(vrt_regular *r, int64_t n_angles, const double 
         DevBuf<double> tmp;
         VRT_S(upload(s->d_B0, cc->B0, nS, st));
         VRT_S(upload(s->d_eps, cc->eps, nS, st));
-        VRT_S(upload(s->d_S[0], cc->B0, nS, st));            // S_new = B_0, :83-84
+        VRT_S(s->sj.create(r, nlam, s->d_B0, st));           // S_new = B_0, :83-84; I_0 = B_λ(T[1, :, :]), :16
         VRT_S(upload(tmp, cc->alpha, nS, st));
-        VRT_S(s->d_S[1].alloc(nS));
-        VRT_S(s->d_J.alloc(nS));
         VRT_S(s->d_A_pl.alloc(nS));
-        VRT_S(s->d_S_pl.alloc(nS));
-        VRT_S(s->d_J_pl.alloc(nS));
-        VRT_S(s->d_I0_pl.alloc((size_t)plane * (size_t)nlam));
-        VRT_S(s->d_zero.alloc((size_t)plane));
         VRT_S(s->d_scalars.alloc(kUpdateWords));
-        VRT_HIP_TRY(hipMemsetAsync(s->d_J, 0, sizeof(double) * nS, st));
-        VRT_HIP_TRY(hipMemsetAsync(s->d_zero, 0, sizeof(double) * (size_t)plane, st));
         VRT_S(launch_to_planes(r, nlam, tmp, s->d_A_pl, st));             // α_cont, fixed over the iterations (:76)
-        VRT_S(launch_to_planes(r, nlam, s->d_B0, s->d_S_pl, st));
-        VRT_S(launch_bottom_planes(r, nlam, s->d_B0, s->d_I0_pl, st));    // I_0 = B_λ(T[1, :, :]), :16
 #undef VRT_S
         VRT_HIP_TRY(hipStreamSynchronize(st));
         *out = s.release();
@@ -798,31 +767,19 @@ int vrt_regular_continuum_iterate(vrt_regular_continuum *s, double *max_rel_chan
         int rc = use_device(s->device);
         if (rc) return rc;
         hipStream_t st = s->st;
-        vrt_regular *r = s->r;
-        const int64_t n = s->n, nlam = s->nlam;
         // J_λ (:1-24) from S_old = the last S_new (:93-94); S_new = (1 - ε) J + ε B_0 (:95) and the masked criterion (:169);
         // S_new also plane-major for the next solves
+        RasterStore &sj = s->sj;
         if ((rc = continuum_J_pass(s, st))) return rc;
-        if ((rc = launch_from_planes(r, nlam, s->d_J_pl, s->d_J, st))) return rc;
-        if ((rc = launch_continuum_update(n, nlam, nlam, s->d_J, s->d_B0, s->d_eps, s->op ? s->d_diag.p : nullptr,
-                                          s->eps_thick, s->d_S[s->sc], s->d_S[s->sc ^ 1], s->d_scalars, st)))
+        if ((rc = sj.J_home(st))) return rc;
+        if ((rc = launch_continuum_update(s->n, s->nlam, s->nlam, sj.J_rows(), s->d_B0, s->d_eps, s->op ? s->d_diag.p : nullptr,
+                                          s->eps_thick, sj.S_rows(), sj.S_next(), s->d_scalars, st)))
             return rc;
-        s->sc ^= 1;
-        if ((rc = launch_to_planes(r, nlam, s->d_S[s->sc], s->d_S_pl, st))) return rc;
-        if ((rc = read_criterion(s->d_scalars, st, max_rel_change, nullptr))) return rc;
-        r->timed = false;                                    // (the handle's events saw only the last chunk)
+        if ((rc = sj.S_written(st))) return rc;
+        if ((rc = read_criterion(s->d_scalars, 3, st, max_rel_change))) return rc;
+        s->r->timed = false;                                 // (the handle's events saw only the last chunk)
         s->iterations++;
-        if (s->ng.order) {
-            NgRange rg;
-            rg.dense = (n * nlam) & ~(int64_t)1; rg.tail = (n * nlam) & 1; rg.tstride = 1;
-            if ((rc = ng_after_iterate(s->ng, s->iterations, s->d_S[s->sc], (size_t)(n * nlam), rg, st))) return rc;
-            if (s->ng.last_applied == 1) {
-                if ((rc = launch_to_planes(r, nlam, s->d_S[s->sc], s->d_S_pl, st))) return rc;
-                VRT_HIP_TRY(hipStreamSynchronize(st));
-            }
-        } else
-            s->ng.last_applied = 0;
-        return VRT_OK;
+        return ng_after_update(s->ng, s->iterations, sj, st);
     });
 }
 
@@ -832,11 +789,7 @@ int vrt_regular_continuum_get(vrt_regular_continuum *s, double *J, double *S)
     return guarded([&] {
         int rc = use_device(s->device);
         if (rc) return rc;
-        const size_t bytes = sizeof(double) * (size_t)s->n * (size_t)s->nlam;
-        VRT_HIP_TRY(hipStreamSynchronize(s->st));
-        if (J) VRT_HIP_TRY(hipMemcpy(J, s->d_J, bytes, hipMemcpyDeviceToHost));
-        if (S) VRT_HIP_TRY(hipMemcpy(S, s->d_S[s->sc], bytes, hipMemcpyDeviceToHost));
-        return VRT_OK;
+        return s->sj.download(J, S, s->st);
     });
 }
 
@@ -848,9 +801,10 @@ int vrt_regular_continuum_set_source(vrt_regular_continuum *s, const double *S)
     return guarded([&] {
         if ((rc = use_device(s->device))) return rc;
         hipStream_t st = s->st;
-        VRT_HIP_TRY(hipMemcpyAsync(s->d_S[s->sc], S, sizeof(double) * (size_t)s->n * (size_t)s->nlam, hipMemcpyHostToDevice, st));
-        if ((rc = launch_to_planes(s->r, s->nlam, s->d_S[s->sc], s->d_S_pl, st))) return rc;
+        RasterStore::Staged staged;                          // beside the session: it is untouched until the copies are complete
+        if ((rc = s->sj.stage(S, staged, st))) return rc;
         VRT_HIP_TRY(hipStreamSynchronize(st));
+        s->sj.adopt(staged);
         s->ng.have = 0;
         s->ng.last_applied = 0;
         return VRT_OK;
@@ -865,7 +819,7 @@ int vrt_regular_continuum_set_acceleration(vrt_regular_continuum *s, int order, 
     return guarded([&] {
         if ((rc = use_device(s->device))) return rc;
         VRT_HIP_TRY(hipStreamSynchronize(s->st));
-        return ng_configure(s->ng, order, start, period, (size_t)(s->n * s->nlam));
+        return ng_configure(s->ng, order, start, period, s->sj.ng_count());
     });
 }
 

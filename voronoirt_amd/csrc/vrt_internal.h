@@ -4,7 +4,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -637,6 +639,21 @@ int launch_copy_I_out(vrt_plan *p, const SweepArgs &sa, void *dI_out, int64_t ld
 
 constexpr size_t kUpdateWords = 3;   // a grid's d_scalars: the criterion's maximum, its NaN flag, the continuum's thick count
                                      //   (the line ALI updates: the entries that fell back to the plain update)
+// The words of an update, home: the criterion's scalar (NaN like Julia's maximum) and, if asked for, the third word.
+// `words`: 2 or 3, as many as the update defined (a plain line update clears and writes two: its third is never read, and
+// *third stays what it was).  Synchronises `st`.
+inline int read_criterion(const unsigned long long *d_result, size_t words, hipStream_t st, double *max_rel_change,
+                          int64_t *third = nullptr)
+{
+    unsigned long long h[kUpdateWords] = {0, 0, 0};
+    VRT_HIP_TRY(hipMemcpyAsync(h, d_result, words * sizeof(h[0]), hipMemcpyDeviceToHost, st));
+    VRT_HIP_TRY(hipStreamSynchronize(st));
+    double d;
+    std::memcpy(&d, &h[0], sizeof(double));
+    *max_rel_change = h[1] ? std::nan("") : d;
+    if (third && words > 2) *third = (int64_t)h[2];
+    return VRT_OK;
+}
 int launch_axpy(size_t count, const double *d_src, double *d_dst, hipStream_t st);
 int launch_gather_rows(int64_t rows, int64_t nlam, int64_t ld, const int32_t *d_order, const double *d_src, double *d_dst,
                        hipStream_t st);
@@ -842,6 +859,23 @@ inline bool ng_commit(NgPiece *pieces, int count, bool coeffs_valid)
     return true;
 }
 int ng_after_iterate(NgState &ng, int64_t iterate, DevBuf<double> &S, size_t alloc_count, const NgRange &rg, hipStream_t st);
+// What follows the update of iterate number `iterate` in a session whose S stands behind a store (SourceStore, RasterStore):
+// acceleration off -> no step; otherwise ng_after_iterate on the store's S, and after an accepted step the store makes
+// again what follows S (its down-order copy, its plane-major copy); `st` is synchronised only where that queued work.
+template <typename Store>
+inline int ng_after_update(NgState &ng, int64_t iterate, Store &store, hipStream_t st)
+{
+    if (!ng.order) {
+        ng.last_applied = 0;
+        return VRT_OK;
+    }
+    int rc = ng_after_iterate(ng, iterate, store.ng_S(), store.ng_count(), store.ng_range(), st);
+    if (rc || ng.last_applied != 1) return rc;
+    bool queued = false;
+    if ((rc = store.ng_refresh(st, &queued)) || !queued) return rc;
+    VRT_HIP_TRY(hipStreamSynchronize(st));
+    return VRT_OK;
+}
 int ng_report(const NgState &ng, int *applied, double sums[5], double coeffs[2]);
 int launch_ng_mirror(vrt_grid *g, int64_t nlam, const double *dS_up, double *dS_down, hipStream_t st);
 // the multi-device session's acceleration (vrt_multi.cpp); the C entries of voronoirt_multi_accel.h are built into the

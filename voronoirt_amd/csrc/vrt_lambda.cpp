@@ -398,26 +398,16 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
         // R, populations (:269, :274) from the same J
         if ((rc = launch_rates_populations(s->line.rates_in(), J, s->line.d_R, s->d_pops_new, st))) return rc;
         std::swap(s->d_pops, s->d_pops_new);
-        unsigned long long h[kUpdateWords] = {0, 0, 0};      // (the third word: the ALI update's, in the same copy)
-        VRT_HIP_TRY(hipMemcpyAsync(h, s->d_scalars, (s->op ? 3 : 2) * sizeof(h[0]), hipMemcpyDeviceToHost, st));
-        VRT_HIP_TRY(hipStreamSynchronize(st));
+        double crit;
+        int64_t fallback = 0;                                // (the third word: the ALI update's, in the same copy)
+        if ((rc = read_criterion(s->d_scalars, s->op ? 3 : 2, st, &crit, &fallback))) return rc;
         if ((rc = patch_chain_check(p))) return rc;          // a chained sweep that gave up: THIS iteration's results are invalid
-        double d;
-        std::memcpy(&d, &h[0], sizeof(double));
-        *max_rel_change = h[1] ? std::nan("") : d;
-        s->fallback_last = (int64_t)h[2];
+        *max_rel_change = crit;
+        s->fallback_last = fallback;
         s->iterations++;
-        if (s->ng.order) {
-            // history copy or Ng step on the S of the plain update (the up-order copy); an accepted x_acc becomes that copy
-            // and the down-order copy is rewritten from it, value for value
-            if ((rc = ng_after_iterate(s->ng, s->iterations, sj.ng_S(), sj.ng_count(), sj.ng_range(), st))) return rc;
-            if (s->ng.last_applied == 1 && sj.two_orders()) {
-                if ((rc = sj.mirror_down(st))) return rc;
-                VRT_HIP_TRY(hipStreamSynchronize(st));
-            }
-        } else
-            s->ng.last_applied = 0;
-        return VRT_OK;
+        // history copy or Ng step on the S of the plain update (the up-order copy); an accepted x_acc becomes that copy and
+        // the down-order copy is rewritten from it, value for value
+        return ng_after_update(s->ng, s->iterations, sj, st);
     });
 }
 

@@ -1,5 +1,6 @@
 // Internal: the regular-grid solver handle and the entry of its solve kernels (vrt_regular.hip), shared with the
-// line Λ-iteration on the raster (vrt_regular_lambda.hip).
+// line Λ-iteration on the raster (vrt_regular_lambda.hip).  The S and J of a raster session stand behind RasterStore
+// (vrt_raster_store.h), which includes this header for the layout launches below.
 #pragma once
 
 #include <vector>

@@ -8,7 +8,8 @@
 // (point i = iz + nz (ix + nx iy), wavelength fastest: S[i nlam + l]); the solver works plane-major
 // ([l][iz][iy][ix]).  A session keeps S, J and B_0 in the caller's layout for the pointwise steps (the update and
 // the rates kernels of the Voronoi session, unchanged) and one plane-major copy of S for the solves; J is reduced
-// plane-major and transposed once per iteration, S_new once (32 x 32 LDS tiles: four passes over nλ n doubles).
+// plane-major and transposed once per iteration, S_new once (32 x 32 LDS tiles: four passes over nλ n doubles).  S and J
+// in both layouts, and the order of those steps, are RasterStore's (vrt_raster_store.h).
 //
 // Chunking.  Solve g = a nλ + l runs over the active angles a (dirs != 0) with the wavelength fastest.  The solves go
 // through in chunks whose workspace (α_tot and I of the chunk, the row-march coefficients) stays under
@@ -31,7 +32,7 @@
 
 #include "vrt_device.h"
 #include "vrt_line_case.h"
-#include "vrt_regular.h"
+#include "vrt_raster_store.h"
 #include "vrt_voigt.h"
 
 namespace vrt {
@@ -299,11 +300,10 @@ struct vrt_regular_lambda {
     Stream st;
     // per point, Julia order
     LineCaseDev line;                   // the uploaded case, γ, the line strength and R (vrt_line_case.h)
-    DevBuf<double> d_B0, d_J;
-    DevBuf<double> d_pops[2], d_S[2];   // [cur]: the current populations, the last S_new
-    int pc = 0, sc = 0;
-    // plane-major, wavelength slowest
-    DevBuf<double> d_S_pl, d_J_pl, d_I0_pl, d_zero;
+    RasterStore sj;                     // S and J, rows and planes, and what the solves start from (vrt_raster_store.h)
+    DevBuf<double> d_B0;
+    DevBuf<double> d_pops[2];           // [pc]: the current populations
+    int pc = 0;
     DevBuf<unsigned long long> d_scalars;
     int64_t iterations = 0;
     NgState ng;                         // vrt_regular_lambda_set_acceleration (off: nothing allocated, nothing run)
@@ -383,33 +383,23 @@ int vrt_regular_lambda_create(vrt_regular *r, int64_t n_angles, const double *k,
         s->r = r;
         s->device = r->device;
         s->n_sweeps = n_sweeps;
-        const int64_t vol = r->nz * r->nx * r->ny, plane = r->nx * r->ny;
+        const int64_t vol = r->nz * r->nx * r->ny;
         s->n = vol;
         s->nlam = nlam;
         if ((rc = line_solves_init(s->ls, r, n_angles, k, dirs, weights, nlam))) return rc;
         if ((rc = s->st.create())) return rc;
-        const size_t n = (size_t)vol, nl = (size_t)nlam, nS = n * nl;
+        const size_t n = (size_t)vol, nS = n * (size_t)nlam;
         hipStream_t st = s->st;
 #define VRT_S(expr) do { if ((rc = (expr))) return rc; } while (0)
         VRT_S(s->line.create(lc, vol, st));
         VRT_S(upload(s->d_B0, lc->B0, nS, st));
         VRT_S(upload(s->d_pops[0], lc->lte_populations, 3 * n, st));        // populations = copy(LTE_pops), :127
-        VRT_S(upload(s->d_S[0], lc->B0, nS, st));                           // S_new = B_0, :150
+        VRT_S(s->sj.create(r, nlam, s->d_B0, st));           // S_new = B_0, :150; I_0 = B_λ(λ_l, T[1, :, :]), :38
         VRT_S(s->d_pops[1].alloc(3 * n));
-        VRT_S(s->d_S[1].alloc(nS));
-        VRT_S(s->d_J.alloc(nS));
-        VRT_S(s->d_S_pl.alloc(nS));
-        VRT_S(s->d_J_pl.alloc(nS));
-        VRT_S(s->d_I0_pl.alloc((size_t)plane * nl));
-        VRT_S(s->d_zero.alloc((size_t)plane));
         VRT_S(s->d_scalars.alloc(kUpdateWords));
-        // (J, R and γ are those of "no iteration yet": zeros)
-        VRT_HIP_TRY(hipMemsetAsync(s->d_J, 0, sizeof(double) * nS, st));
+        // (R and γ, like the store's J, are those of "no iteration yet": zeros)
         VRT_HIP_TRY(hipMemsetAsync(s->line.d_R, 0, sizeof(double) * 9 * n, st));
         VRT_HIP_TRY(hipMemsetAsync(s->line.d_gamma, 0, sizeof(double) * n, st));
-        VRT_HIP_TRY(hipMemsetAsync(s->d_zero, 0, sizeof(double) * (size_t)plane, st));
-        VRT_S(launch_to_planes(r, nlam, s->d_B0, s->d_S_pl, st));
-        VRT_S(launch_bottom_planes(r, nlam, s->d_B0, s->d_I0_pl, st));    // I_0 = B_λ(λ_l, T[1, :, :]), :38
 #undef VRT_S
         VRT_HIP_TRY(hipStreamSynchronize(st));               // the host arrays may go after return
         *out = s.release();
@@ -424,8 +414,8 @@ int vrt_regular_lambda_iterate(vrt_regular_lambda *s, double *max_rel_change)
         int rc = use_device(s->device);
         if (rc) return rc;
         hipStream_t st = s->st;
-        vrt_regular *r = s->r;
         const int64_t n = s->n, nlam = s->nlam;
+        RasterStore &sj = s->sj;
         // γ and the line strength of the current populations (:13-16, line.jl:219-225)
         LineCaseDev &line = s->line;
         if ((rc = line.terms(s->d_pops[s->pc], st))) return rc;
@@ -435,44 +425,28 @@ int vrt_regular_lambda_iterate(vrt_regular_lambda *s, double *max_rel_change)
         lp.gamma = line.d_gamma; lp.strength = line.d_strength; lp.alpha_cont = line.d_alpha_cont; lp.lambda0 = line.k.lambda0;
         lp.c0 = line.k.c0;
         // (with the operator on also Λ* of that α, formed beside the solves that read the same workspace)
-        if ((rc = line_J_pass(r, s->ls, lp, s->d_S_pl, s->d_I0_pl, s->d_zero, s->n_sweeps, s->d_J_pl, st,
+        if ((rc = line_J_pass(s->r, s->ls, lp, sj.S_planes(), sj.I0_planes(), sj.zero_plane(), s->n_sweeps, sj.J_planes(), st,
                               s->op ? s->d_diag_pl.get() : nullptr)))
             return rc;
-        if ((rc = launch_from_planes(r, nlam, s->d_J_pl, s->d_J, st))) return rc;
-        if (s->op && (rc = launch_from_planes(r, nlam, s->d_diag_pl, s->d_diag, st))) return rc;
+        if ((rc = sj.J_home(st))) return rc;
+        if (s->op && (rc = sj.rows_from_planes(s->d_diag_pl, s->d_diag, st))) return rc;
         // S_new = (1 - ε) J + ε B_0 (:169-171) and the criterion's scalar; S_new also plane-major for the next solves.  With
         // the operator on (d_diag is NULL otherwise): the ALI update
-        if ((rc = launch_lambda_update(n, nlam, nlam, s->d_J, s->d_B0, line.d_eps, s->d_S[s->sc], s->d_S[s->sc ^ 1], s->d_scalars, st,
+        if ((rc = launch_lambda_update(n, nlam, nlam, sj.J_rows(), s->d_B0, line.d_eps, sj.S_rows(), sj.S_next(), s->d_scalars, st,
                                        s->op ? s->d_diag.get() : nullptr)))
             return rc;
-        s->sc ^= 1;
-        if ((rc = launch_to_planes(r, nlam, s->d_S[s->sc], s->d_S_pl, st))) return rc;
+        if ((rc = sj.S_written(st))) return rc;
         // R, populations (:176, :181)
-        if ((rc = launch_rates_populations(line.rates_in(), RatesJ::from_rows(s->d_J, nlam), line.d_R, s->d_pops[s->pc ^ 1], st)))
+        if ((rc = launch_rates_populations(line.rates_in(), RatesJ::from_rows(sj.J_rows(), nlam), line.d_R, s->d_pops[s->pc ^ 1], st)))
             return rc;
         s->pc ^= 1;
-        unsigned long long h[kUpdateWords] = {0, 0, 0};      // (the third word: the ALI update's, in the same copy)
-        VRT_HIP_TRY(hipMemcpyAsync(h, s->d_scalars, (s->op ? 3 : 2) * sizeof(h[0]), hipMemcpyDeviceToHost, st));
-        VRT_HIP_TRY(hipStreamSynchronize(st));
-        double d;
-        std::memcpy(&d, &h[0], sizeof(double));
-        *max_rel_change = h[1] ? std::nan("") : d;
-        s->fallback_last = (int64_t)h[2];
-        r->timed = false;                                    // (the handle's events saw only the last chunk)
+        // (the third word: the ALI update's, in the same copy; with the operator off fallback_last is 0 and stays)
+        if ((rc = read_criterion(s->d_scalars, s->op ? 3 : 2, st, max_rel_change, &s->fallback_last))) return rc;
+        s->r->timed = false;                                 // (the handle's events saw only the last chunk)
         s->iterations++;
-        if (s->ng.order) {
-            // history copy or Ng step on the S of the plain update; an accepted x_acc becomes d_S[sc], and the plane-major
-            // copy the next solves read is made again from it
-            NgRange rg;
-            rg.dense = (n * nlam) & ~(int64_t)1; rg.tail = (n * nlam) & 1; rg.tstride = 1;
-            if ((rc = ng_after_iterate(s->ng, s->iterations, s->d_S[s->sc], (size_t)(n * nlam), rg, st))) return rc;
-            if (s->ng.last_applied == 1) {
-                if ((rc = launch_to_planes(r, nlam, s->d_S[s->sc], s->d_S_pl, st))) return rc;
-                VRT_HIP_TRY(hipStreamSynchronize(st));
-            }
-        } else
-            s->ng.last_applied = 0;
-        return VRT_OK;
+        // history copy or Ng step on the S of the plain update; an accepted x_acc becomes the store's S, and the plane-major
+        // copy the next solves read is made again from it
+        return ng_after_update(s->ng, s->iterations, sj, st);
     });
 }
 
@@ -484,7 +458,7 @@ int vrt_regular_lambda_set_acceleration(vrt_regular_lambda *s, int order, int st
     return guarded([&] {
         if ((rc = use_device(s->device))) return rc;
         VRT_HIP_TRY(hipStreamSynchronize(s->st));
-        return ng_configure(s->ng, order, start, period, (size_t)(s->n * s->nlam));
+        return ng_configure(s->ng, order, start, period, s->sj.ng_count());
     });
 }
 
@@ -604,10 +578,8 @@ int vrt_regular_lambda_get(vrt_regular_lambda *s, double *J, double *S, double *
     return guarded([&] {
         int rc = use_device(s->device);
         if (rc) return rc;
-        const size_t n = (size_t)s->n, nS = n * (size_t)s->nlam;
-        VRT_HIP_TRY(hipStreamSynchronize(s->st));
-        if (J) VRT_HIP_TRY(hipMemcpy(J, s->d_J, sizeof(double) * nS, hipMemcpyDeviceToHost));
-        if (S) VRT_HIP_TRY(hipMemcpy(S, s->d_S[s->sc], sizeof(double) * nS, hipMemcpyDeviceToHost));
+        const size_t n = (size_t)s->n;
+        if ((rc = s->sj.download(J, S, s->st))) return rc;   // (synchronises the stream)
         if (populations) VRT_HIP_TRY(hipMemcpy(populations, s->d_pops[s->pc], sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
         if (R) VRT_HIP_TRY(hipMemcpy(R, s->line.d_R, sizeof(double) * 9 * n, hipMemcpyDeviceToHost));
         if (gamma) VRT_HIP_TRY(hipMemcpy(gamma, s->line.d_gamma, sizeof(double) * n, hipMemcpyDeviceToHost));
@@ -622,23 +594,17 @@ int vrt_regular_lambda_set_state(vrt_regular_lambda *s, const double *S, const d
     return guarded([&] {
         if ((rc = use_device(s->device))) return rc;
         hipStream_t st = s->st;
-        const size_t n = (size_t)s->n, nS = n * (size_t)s->nlam;
+        const size_t n = (size_t)s->n;
         // staged copies beside the session: it is untouched until every one of them is complete
-        DevBuf<double> S_new, S_pl, pops;
-        if (S) {
-            if ((rc = S_new.alloc(nS)) || (rc = S_pl.alloc(nS))) return rc;
-            VRT_HIP_TRY(hipMemcpyAsync(S_new, S, sizeof(double) * nS, hipMemcpyHostToDevice, st));
-            if ((rc = launch_to_planes(s->r, s->nlam, S_new, S_pl, st))) return rc;      // what the next solves read
-        }
+        RasterStore::Staged staged;
+        DevBuf<double> pops;
+        if (S && (rc = s->sj.stage(S, staged, st))) return rc;
         if (populations) {
             if ((rc = pops.alloc(3 * n))) return rc;
             VRT_HIP_TRY(hipMemcpyAsync(pops, populations, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
         }
         VRT_HIP_TRY(hipStreamSynchronize(st));               // the host arrays may go after return
-        if (S) {
-            std::swap(s->d_S[s->sc], S_new);
-            std::swap(s->d_S_pl, S_pl);
-        }
+        if (S) s->sj.adopt(staged);
         if (populations) std::swap(s->d_pops[s->pc], pops);
         s->ng.have = 0;                                      // iterates of another state are no history of this one
         s->ng.last_applied = 0;

@@ -218,6 +218,12 @@ struct SourceStore {
     NgRange ng_range() const { return ng_S_range(n_, nlam_, form_ != kRows); }
     // after an accepted step (two_orders() only): the down-order copy rewritten from the up-order one, enqueued on `st`
     int mirror_down(hipStream_t st) { return launch_ng_mirror(p_->g, nlam_, S_[0], S_[1], st); }
+    // ... as ng_after_update (vrt_internal.h) asks for it: rows have nothing that follows S, and queue nothing
+    int ng_refresh(hipStream_t st, bool *queued)
+    {
+        *queued = two_orders();
+        return *queued ? mirror_down(st) : VRT_OK;
+    }
 
 private:
     vrt_plan *p_ = nullptr;             // borrowed, as the session borrows it

@@ -477,6 +477,20 @@ def regular_line_case(nz: int, nx: int, ny: int, seed: int, nbb: int = 21, nbf: 
     return z, periodic_axis(atm["x"]), periodic_axis(atm["y"]), case
 
 
+def three_wavelength_line_case(nz: int, nx: int, ny: int, seed: int):
+    """`regular_line_case` at the smallest odd wavelength count a line case can have: 22.8 nm, 91.2 nm and the line centre.
+    Every block needs two wavelengths, so the three overlap: both bound-free blocks are [0, 2), the line block is [1, 3).
+    Not an atom anyone would model, but a valid input, with positive S and populations over the iterates, whose n nλ is
+    odd whenever n is."""
+    z, x, y, case = regular_line_case(nz, nx, ny, seed, nbb=1, nbf=1)
+    order = np.argsort(case["lam"])
+    lam = case["lam"][order]
+    case.update(lam=lam, planck2=case["planck2"][order], B0=np.ascontiguousarray(case["B0"][:, order]),
+                blocks=np.array([1, 3, 0, 2, 0, 2], dtype=np.int64), sigma_bf1=1e-21 * (lam[:2] / lam[1]) ** 3,
+                sigma_bf2=2e-21 * (lam[:2] / lam[1]) ** 3)
+    return z, x, y, case
+
+
 # ---------------------------------------------------------------------------------------------
 # the continuum scattering case (src/lambda_continuum.jl)
 # ---------------------------------------------------------------------------------------------
