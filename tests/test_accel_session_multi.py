@@ -28,10 +28,10 @@ pytestmark = pytest.mark.gpu
 class _World:
     """a vrt_multi of W handles on device 0 with the case, and a factory of sessions on it"""
 
-    def __init__(self, voro_small, W):
+    def __init__(self, voro_small, W, case=None):
         pos, nbr, bounds = voro_small
         self.pos, self.nbr, self.bounds = pos, nbr, bounds
-        self.case = _lambda_case(pos, bounds, 11)
+        self.case = case if case is not None else _lambda_case(pos, bounds, 11)
         self.w, th, ph, _ = vrt.read_quadrature(QUAD)
         dirs = [1 if t > 90 else -1 for t in th]
         self.mp = vrt.MultiDevicePlan(pos, nbr, bounds, vrt.quadrature_directions(th, ph), dirs=dirs, devices=(0,) * W)
@@ -106,6 +106,22 @@ def test_gpu_multi_session_takes_an_ng_step(W, worlds, oracle_sites):
         _check_session_step(plain, acc, lambda S, pops: _voronoi_oracle_step(world.case, so, S, pops), f"multi W={W}")
     finally:
         world.release()
+
+
+def test_gpu_multi_session_takes_an_ng_step_with_one_wavelength_per_member(voro_small, oracle_sites):
+    """the same checks on seven wavelengths (tests/test_resume_host.py's small_lambda_case with nbb = 3, nbf = 2) over
+    W = 8: seven members hold one wavelength -- a single pair plane with its padding, all of it the stride-2 tail of the
+    member's range -- and one holds none, keeps no history and adds no sums"""
+    from test_resume_host import small_lambda_case
+    assert os.environ.get("VRT_LAMBDA_NATIVE", "1") == "1"
+    pos, nbr, bounds = voro_small
+    world = _World(voro_small, 8, case=small_lambda_case(pos, bounds, 11, 3, 2))
+    assert world.nlam == 7
+    try:
+        _check_session_step(world.make(), world.make(), lambda S, pops: _voronoi_oracle_step(world.case, oracle_sites, S, pops),
+                            "multi W=8, 7 wavelengths")
+    finally:
+        world.close()
 
 
 # ---- 2: both layouts ----------------------------------------------------------------------------------------------------------

@@ -893,6 +893,33 @@ def test_multi_device_object_of_the_c_abi(voro_small, devices):
         vrt.MultiDevicePlan(pos, nbr, bounds, vrt.quadrature_directions(th, ph), dirs=dirs, devices=(0, 97))
 
 
+def test_angle_sharding_with_a_member_that_holds_no_angle(voro_small):
+    """Three directions -- one up, one down, one horizontal (dirs 1, -1, 0; the horizontal one is dealt to nobody) -- over
+    three handles of device 0 in angle mode: the first holds the up angle, the last the down angle and the middle one
+    none, so its partial J is the zeros the sum reads.  α per (site, λ), two wavelengths.  J is the one-handle J to
+    summation order: the 1e-13 of test_multi_device_object_of_the_c_abi's angle-shard comparison."""
+    pos, nbr, bounds = voro_small
+    n = pos.shape[0]
+    w, th, ph, nq = vrt.read_quadrature("ul7n12.dat")
+    up, down = int(np.argmax(np.asarray(th) > 90)), int(np.argmax(np.asarray(th) < 90))
+    k = vrt.quadrature_directions([th[up], th[down], 90.0], [ph[up], ph[down], 30.0])
+    dirs, wq = [1, -1, 0], np.array([w[up], w[down], 0.25])
+    rng = np.random.default_rng(8)
+    nlam = 2
+    S = 1 + rng.random((n, nlam))
+    al = 5 * 10 ** rng.uniform(-2, 2, (n, 1)) * (1 + rng.random((n, nlam)))
+    one = vrt.MultiDevicePlan(pos, nbr, bounds, k, dirs=dirs, devices=(0,))
+    J1 = one.execute(S, al, wq)
+    one.close()
+    assert np.isfinite(J1).all() and J1.max() > 0
+    mp = vrt.MultiDevicePlan(pos, nbr, bounds, k, dirs=dirs, devices=(0, 0, 0))
+    mp.set_shard("angle")
+    Ja = mp.execute(S, al, wq)
+    assert mp.last_shard == "angle"
+    mp.close()
+    assert _rel(Ja, J1) < 1e-13
+
+
 def test_degenerate_grids_and_plans(path):
     """Edge cases on every device path: a single-layer grid (every cell touches the wall: no sweep
     at all, I = I_0 except the never-visited last site), a two-layer grid, one angle / one

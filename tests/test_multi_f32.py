@@ -371,6 +371,68 @@ def test_members_with_one_wavelength_and_with_none(voro_small, plans):
     assert all(np.isfinite(h) for h in hist)
 
 
+@pytest.mark.parametrize("storage", ["f64", "f32"])
+def test_eight_members_with_one_wavelength_each_and_one_without(voro_small, plans, runs, storage):
+    """Seven wavelengths (tests/test_resume_host.py's small_lambda_case with nbb = 3, nbf = 2) over eight members of
+    device 0: blocks 1, 1, 1, 1, 1, 1, 1, 0, in double storage in sweep order and in float storage.  Three iterates against
+    the one-device session of the same storage, as test_session_is_the_one_device_float_session_block_by_block compares
+    them: iterate 1 bit for bit; later iterates by the conditions of oracle/f32_model.py and 4 x the model's perturbation
+    (float storage), or by the 1e-12 of the regrouped rate sums (double storage: REGROUPING, the bound of
+    tests/test_physics.py's multi-device session against the one-device one).  Then the one-device state after iterate 3
+    through set_state and one more iterate: the same S and populations go in, and every wavelength is solved by one
+    member, so J, S and the criterion are the one-device session's fourth bit for bit; the populations behind them differ
+    by the regrouping again."""
+    from test_resume_host import small_lambda_case as lambda_case_of
+    pos, nbr, bounds = voro_small
+    f32s = storage == "f32"
+    assert os.environ.get("VRT_LAMBDA_NATIVE", "1") == "1"           # (double storage: sweep-order planes)
+    case = lambda_case_of(pos, bounds, 11, 3, 2)
+    assert [b - a for a, b in partition(7, 8)] == [1, 1, 1, 1, 1, 1, 1, 0]
+    one = _Single(plans("default"), case, f32_storage=f32s)
+    assert one.rc == 0 and one.storage() == (4 if f32s else 8)
+    ref, ref_hist = one.run(4)
+    one.close()
+    pert = max(deviations(a, b)[2] for a, b in zip(runs["perturbed"], runs["model"]))
+    B0, eps = f32(case.B0), np.asarray(case.eps)[:, None]
+
+    def compare(k, got, d):
+        J, S, pops = got
+        assert np.isfinite(J).all() and np.isfinite(S).all() and (pops > 0).all()
+        dp = float(np.abs(pops / ref[k][2] - 1).max())
+        if f32s:
+            assert np.array_equal(f32(J), J) and np.array_equal(f32(S), S)
+            assert np.array_equal(S, f32((1.0 - eps) * J + eps * B0))
+            figs = [within_conditions(got[q], ref[k][q]) for q in range(2)]
+            print(f"float storage, iterate {k + 1}: J differs in {figs[0][1]} of {figs[0][2]} ({figs[0][3]:g} ulp), S in "
+                  f"{figs[1][1]} ({figs[1][3]:g} ulp), populations {dp:.2e} (bound 4 x {pert:.2e}), criterion {d:.17g} "
+                  f"against {ref_hist[k]:.17g}")
+            assert figs[0][0] and figs[1][0], (k, figs)
+            assert dp <= 4 * pert, (k, dp, pert)
+        else:
+            dJ = float(np.abs(J - ref[k][0]).max() / np.abs(ref[k][0]).max())     # (J is 0 at the never-solved site)
+            dS = float(np.abs(S / ref[k][1] - 1).max())
+            print(f"double storage, iterate {k + 1}: J {dJ:.2e}, S {dS:.2e}, populations {dp:.2e}, criterion {d:.17g} against "
+                  f"{ref_hist[k]:.17g}")
+            assert max(dJ, dS, dp) <= REGROUPING, (k, dJ, dS, dp)
+
+    mp = _multi_plan(voro_small, 8)
+    s = _Multi(mp, case, f32_storage=f32s)
+    try:
+        assert s.rc == 0 and s.storage() == (4 if f32s else 8)
+        states, hist = s.run(3)
+        assert np.array_equal(states[0][0], ref[0][0]) and np.array_equal(states[0][1], ref[0][1]) and hist[0] == ref_hist[0]
+        for k in range(3):
+            compare(k, states[k], hist[k])
+        assert s.set_state(ref[2][1], ref[2][2]) == 0
+        d4 = s.iterate()
+        got4 = s.get()
+        assert d4 == ref_hist[3] and np.array_equal(got4[0], ref[3][0]) and np.array_equal(got4[1], ref[3][1])
+        compare(3, got4, d4)
+    finally:
+        s.close()
+        mp.close()
+
+
 # ---- 5. state and refusals ---------------------------------------------------------------------------------------------------
 def test_state_and_refusals(voro_small, runs, multi, monkeypatch):
     case = runs["case"]

@@ -7,11 +7,13 @@ runs eight iterates each of: plain, diagonal operator, Ng (4, 4), diagonal + Ng,
 state through *_set_state / *_set_source into a FRESH session, five more there).  Per iterate it prints the criterion as a
 hex double, Ng's (applied, sums, coeffs), the line sessions' fallback count and the SHA-256 of every array *_get returns.
 The raster has 7 x 6 x 5 ghosted points and 3 wavelengths; the Voronoi grid is tests/golden/voro2k (9 line, 3 continuum
-wavelengths).
+wavelengths).  With --multi it runs the multi-device line session (vrt_multi_lambda_*) instead, over 1, 2 and 3 handles of
+device 0 (9 wavelengths in blocks of 9; 5, 4; 3, 3, 3) on the 1500-site grid of the tests: double storage in sweep order and
+in rows, float storage, and double storage in sweep order with Ng (4, 4); plain and resumed each.
 
-    python tools/session_bits.py [--voronoi] > branch.txt
-    VRT_LIB_PATH=/path/to/parent/libvrt_hip.so python tools/session_bits.py [--voronoi] > parent.txt
-    diff parent.txt branch.txt          # must be empty (profiles/raster_store/INDEX.md)
+    python tools/session_bits.py [--voronoi | --multi] > branch.txt
+    VRT_LIB_PATH=/path/to/parent/libvrt_hip.so python tools/session_bits.py [--voronoi | --multi] > parent.txt
+    diff parent.txt branch.txt          # must be empty (profiles/raster_store/INDEX.md, profiles/multi_members/INDEX.md)
 """
 import argparse
 import ctypes
@@ -29,6 +31,7 @@ from voronoirt_amd import _lib, api, synth      # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--voronoi", action="store_true", help="the Voronoi line and continuum sessions on voro2k instead")
+ap.add_argument("--multi", action="store_true", help="the multi-device line session over 1, 2 and 3 handles of device 0 instead")
 args = ap.parse_args()
 
 QUAD = "ul7n12.dat"
@@ -43,8 +46,9 @@ hexes = lambda xs: " ".join(float(x).hex() for x in xs)
 class Session:
     """one of the four sessions through the C entries; `line`: five arrays come home and the state has populations"""
 
-    def __init__(self, prefix, create, n, nlam, line):
+    def __init__(self, prefix, create, n, nlam, line, has_operator=None):
         self.prefix, self.n, self.nlam, self.line = prefix, n, nlam, line
+        self.has_operator = line if has_operator is None else has_operator      # (the multi-device session has none)
         self.h = ctypes.c_void_p()
         api.check(create(ctypes.byref(self.h)))
 
@@ -77,7 +81,7 @@ class Session:
         applied, sums, coeffs = ctypes.c_int(9), np.zeros(5), np.zeros(2)
         api.check(self.fn("last_acceleration")(self.h, ctypes.byref(applied), d(sums), d(coeffs)))
         words = [f"{it}", crit.value.hex(), f"ng {applied.value} [{hexes(sums)}] [{hexes(coeffs)}]"]
-        if self.line:
+        if self.has_operator:
             op, fallback = ctypes.c_int(), ctypes.c_int64(-1)
             api.check(self.fn("get_operator")(self.h, ctypes.byref(op), ctypes.byref(fallback)))
             words.append(f"op {op.value} fallback {fallback.value}")
@@ -88,8 +92,8 @@ class Session:
         self.fn("destroy")(self.h)
 
 
-def run_all(label, make):
-    for name, op, ng in MODES:
+def run_all(label, make, modes=MODES):
+    for name, op, ng in modes:
         s = make()
         if op:
             s.operator(op)
@@ -181,7 +185,26 @@ def voronoi_sessions():
         sites.close()
 
 
-if args.voronoi:
+def multi_sessions():
+    pos, nbr, bounds = synth.voronoi_grid(1500, seed=5, bounds=(0.0, 2.0, 0.0, 1.0, 0.0, 1.0), scale_height=0.7)
+    lc, keep = voronoi_line_case(pos, bounds).c_struct()
+    w, th, ph, _ = vrt.read_quadrature(QUAD)
+    wd = np.ascontiguousarray(w, dtype=np.float64)
+    k, dirs = vrt.quadrature_directions(th, ph), [1 if t > 90 else -1 for t in th]
+    variants = (("planes", "1", L.vrt_multi_lambda_create, MODES[:1]), ("rows", "0", L.vrt_multi_lambda_create, MODES[:1]),
+                ("float planes", "1", L.vrt_multi_lambda_create_f32, MODES[:1]), ("planes", "1", L.vrt_multi_lambda_create, MODES[2:3]))
+    for W in (1, 2, 3):
+        for form, native, entry, modes in variants:
+            os.environ["VRT_LAMBDA_NATIVE"] = native               # read when the members' plans are made
+            mp = vrt.MultiDevicePlan(pos, nbr, bounds, k, dirs=dirs, devices=(0,) * W)
+            create = lambda out: entry(mp._h, ctypes.byref(lc), d(wd), out)
+            run_all(f"multi W={W} line x 9, {form}", lambda: Session("vrt_multi_lambda", create, pos.shape[0], 9, True, has_operator=False), modes)
+            mp.close()
+
+
+if args.multi:
+    multi_sessions()
+elif args.voronoi:
     voronoi_sessions()
 else:
     raster_sessions()

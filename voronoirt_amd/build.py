@@ -14,7 +14,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvrt_hip.so")
 SOURCES = ["vrt_api.cpp", "vrt_grid.cpp", "vrt_schedule.cpp", "vrt_patch.cpp", "vrt_lambda.cpp", "vrt_multi.cpp", "vrt_tessellate.cpp", "vrt_kernels.hip", "vrt_tables.hip", "vrt_layers.hip", "vrt_patch.hip", "vrt_regular.hip", "vrt_regular_lambda.hip", "vrt_physics.hip", "vrt_raster.hip", "vrt_synth.hip", "vrt_accel.hip", "vrt_continuum.hip", "vrt_line_ali.hip"]
-HEADERS = [os.path.join(CSRC, h) for h in ("vrt_internal.h", "vrt_source_store.h", "vrt_raster_store.h", "vrt_line_case.h", "vrt_device.h", "vrt_weights.h", "vrt_regular.h", "vrt_voigt.h", "vrt_layout_kernels.h", "vrt_tile_kernels.h", "vrt_step_kernels.h")] + [os.path.join(ROOT, "include", h) for h in ("voronoirt.h", "voronoirt_multi_accel.h")]
+HEADERS = [os.path.join(CSRC, h) for h in ("vrt_internal.h", "vrt_source_store.h", "vrt_raster_store.h", "vrt_line_case.h", "vrt_line_block.h", "vrt_multi_members.h", "vrt_device.h", "vrt_weights.h", "vrt_regular.h", "vrt_voigt.h", "vrt_layout_kernels.h", "vrt_tile_kernels.h", "vrt_step_kernels.h")] + [os.path.join(ROOT, "include", h) for h in ("voronoirt.h", "voronoirt_multi_accel.h")]
 
 
 def _hipcc() -> str:

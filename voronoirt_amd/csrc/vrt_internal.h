@@ -135,6 +135,26 @@ struct DevWork {
     operator T *() const { return buf.p; }
 };
 
+// Columns [l0, l1) of host rows (rows, ld) into the dense device block (rows, l1 - l0) at `d`, enqueued on `st`
+// (a template only so that a host program which never stages anything need not fake the 2D copy)
+template <typename T>
+inline int copy_cols(T *d, const T *h, size_t rows, int64_t ld, int64_t l0, int64_t l1, hipStream_t st)
+{
+    const size_t w = sizeof(T) * (size_t)(l1 - l0);
+    if (!w || !rows) return VRT_OK;
+    VRT_HIP_TRY(hipMemcpy2DAsync(d, w, h + l0, sizeof(T) * (size_t)ld, w, rows, hipMemcpyHostToDevice, st));
+    return VRT_OK;
+}
+// ... with `d` made large enough first: a DevBuf is allocated, a DevWork grows
+template <typename T> inline int reserve(DevBuf<T> &d, size_t count) { return d.alloc(count); }
+template <typename T> inline int reserve(DevWork<T> &d, size_t count) { return d.grow(count); }
+template <typename Buf>
+inline int upload_cols(Buf &d, const double *h, size_t rows, int64_t ld, int64_t l0, int64_t l1, hipStream_t st)
+{
+    const int rc = reserve(d, rows * (size_t)(l1 - l0));
+    return rc ? rc : copy_cols<double>(d, h, rows, ld, l0, l1, st);
+}
+
 // Pinned (or, with hipHostMallocMapped, mapped) host memory.
 template <typename T>
 struct HostBuf {

@@ -4,9 +4,9 @@
 //   vrt_plan_execute_line  the body of J_λ_voronoi, line case (src/lambda_iteration.jl:72-111): per-site line
 //                          vectors + S in, J out; α_tot is made on the device and never exists on the host
 //   vrt_lambda_*           Λ_voronoi's loop (src/lambda_iteration.jl:205-300) with library-owned device state:
-//                          per iteration only the criterion's scalar comes back.  S and J live in a SourceStore
-//                          (vrt_source_store.h: rows, sweep-order planes or float planes); the session sees the form
-//                          only where vrt_lambda_iterate picks the update and rate kernels
+//                          per iteration only the criterion's scalar comes back.  S, J, B_0, I_0 and the native α of
+//                          all wavelengths are ONE LineBlock (vrt_line_block.h), which also runs an iterate up to the
+//                          update; the session follows with the rates, the populations and the criterion
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -16,8 +16,7 @@
 #include <thread>
 
 #include "vrt_internal.h"
-#include "vrt_line_case.h"
-#include "vrt_source_store.h"
+#include "vrt_line_block.h"
 
 using namespace vrt;
 
@@ -133,15 +132,12 @@ struct vrt_lambda {
     std::vector<double> weights;
     // device state
     LineCaseDev line;                   // the uploaded case, γ, the line strength and R (vrt_line_case.h)
-    DevBuf<double> d_B0, d_pops, d_pops_new;
-    DevBuf<double> d_I0, d_native;
+    DevBuf<double> d_pops, d_pops_new;
     DevBuf<unsigned long long> d_scalars;
     int iterations = 0;
-    // S and J, in rows or in sweep order (VRT_LAMBDA_NATIVE, default); B_0 stands in d_B0 in the store's order: rows, or its
-    // up-order plane set.  Float storage (vrt_lambda_create_f32): f_B0, f_I0 and f_native replace d_B0, d_I0 and d_native --
-    // no double array of size nλ·n or nλ·n·angles exists in such a session
-    SourceStore sj;
-    DevBuf<float> f_B0, f_I0, f_native;
+    // every wavelength: S and J in rows or in sweep order (VRT_LAMBDA_NATIVE, default), B_0, I_0 and the native α.  Float
+    // storage (vrt_lambda_create_f32): no double array of size nλ·n or nλ·n·angles exists in such a session
+    LineBlock blk;
     NgState ng;                         // vrt_lambda_set_acceleration (off: nothing allocated, nothing run)
     // vrt_lambda_use_operator (0: nothing allocated, nothing run): Λ* of the current iterate's α in the store's form
     // (rows, or one up-order plane set), rewritten by every iterate -- no operator state survives an iterate
@@ -288,43 +284,21 @@ static int lambda_create(vrt_plan *p, const vrt_line_case *lc, const double *wei
         vrt_grid *g = p->g;
         int rc = use_device(g->device);
         if (rc) return rc;
-        if ((rc = line_path_ok(p, "the line session"))) return rc;
-        if (p->A != (int)p->n_angles_user)
-            return fail(VRT_EINVAL, "per-angle alpha needs every angle active (no θ = 90 direction)");
-        if (f32) {                                      // float planes exist on the patch path only: no fp64 fallback
-            if ((rc = native_planes_ok(p, true))) return rc;
-            if (p->tune.lambda_native == 0 || (p->tune.path != 0 && p->tune.path != 4))
-                return fail(VRT_EINVAL, "the float-storage line session keeps S and J in the patch path's sweep order: not with VRT_LAMBDA_NATIVE=0 or a VRT_PATH other than patches");
-        }
+        if ((rc = line_session_plan_ok(p, f32))) return rc;
         std::unique_ptr<vrt_lambda, LambdaDelete> s(new vrt_lambda());
         s->p = p;
         s->device = g->device;
         s->n = g->n;
         s->nlam = nlam;
         s->weights.assign(weights, weights + p->n_angles_user);
-        const size_t n = (size_t)g->n, nl = (size_t)nlam;
+        const size_t n = (size_t)g->n;
         hipStream_t st = g->stream;
-#define VRT_S(expr) do { if ((rc = (expr))) return rc; } while (0)
-        VRT_S(s->line.create(lc, g->n, st));
-        VRT_S(upload(s->d_B0, lc->B0, n * nl, st));
-        VRT_S(upload(s->d_pops, lc->lte_populations, 3 * n, st));        // populations = copy(LTE_pops), :232
         const SourceStore::Form form = f32 ? SourceStore::kPlanesF32
                                            : SourceStore::plan_keeps_planes(p) ? SourceStore::kPlanes : SourceStore::kRows;
-        VRT_S(s->sj.create(p, nlam, form, s->d_B0, st));                 // S_new = B_0, S_old = zero(S_new), :236-240
-        // I_0 = B_λ(λ_l, T) of the bottom layer (:99-101) and α_tot of every angle, in the sweep's storage type
-        if (f32) {
-            VRT_S(s->f_I0.alloc((size_t)g->up.n1 * nl));
-            VRT_S(launch_gather_rows_f32(g->up.n1, nlam, nlam, g->up.d_order, s->d_B0, s->f_I0, st));
-            VRT_S(s->f_native.alloc((size_t)vrt_plan_native_alpha_count(p, nlam)));
-        } else {
-            VRT_S(s->d_I0.alloc((size_t)g->up.n1 * nl));
-            VRT_S(launch_gather_rows(g->up.n1, nlam, nlam, g->up.d_order, s->d_B0, s->d_I0, st));
-            VRT_S(s->d_native.alloc((size_t)vrt_plan_native_alpha_count(p, nlam)));
-        }
-        VRT_S(s->sj.to_up_order(s->d_B0, s->f_B0, st));
-        VRT_S(s->d_pops_new.alloc(3 * n));
-        VRT_S(s->d_scalars.alloc(kUpdateWords));
-#undef VRT_S
+        if ((rc = s->line.create(lc, g->n, st)) || (rc = s->blk.create(p, lc->B0, nlam, 0, nlam, form, st)) ||
+            (rc = upload(s->d_pops, lc->lte_populations, 3 * n, st)) ||      // populations = copy(LTE_pops), :232
+            (rc = s->d_pops_new.alloc(3 * n)) || (rc = s->d_scalars.alloc(kUpdateWords)))
+            return rc;
         if (hipStreamSynchronize(st) != hipSuccess)                         // the host arrays may go after return
             return fail(VRT_ENODEVICE, "uploading the line case failed");
         *out = s.release();
@@ -344,7 +318,7 @@ int vrt_lambda_create_f32(vrt_plan *p, const vrt_line_case *lc, const double *we
 
 int vrt_lambda_storage(const vrt_lambda *s)
 {
-    return !s ? fail(VRT_EINVAL, "NULL session") : s->sj.form() == SourceStore::kPlanesF32 ? 4 : 8;
+    return !s ? fail(VRT_EINVAL, "NULL session") : s->blk.sj.form() == SourceStore::kPlanesF32 ? 4 : 8;
 }
 
 int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
@@ -357,44 +331,9 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
         int rc = use_device(g->device);
         if (rc) return rc;
         hipStream_t st = g->stream;
-        const int64_t n = s->n, nlam = s->nlam;
-        SourceStore &sj = s->sj;
-        const bool f32 = sj.form() == SourceStore::kPlanesF32;
-        if (sj.form() == SourceStore::kRows)                 // S_old = copy(S_new), :258
-            VRT_HIP_TRY(hipMemcpyAsync(sj.S_old(), sj.S_new(), sizeof(double) * (size_t)n * (size_t)nlam, hipMemcpyDeviceToDevice, st));
-        // γ and the line strength of the current populations (:72-75, line.jl:219-225), α_tot of every angle (:89-96)
-        if ((rc = s->line.terms(s->d_pops, st))) return rc;
-        void *alpha = f32 ? (void *)s->f_native.get() : (void *)s->d_native.get();
-        if ((rc = s->line.opacity(p, nlam, 0, alpha, st, f32))) return rc;
-        // Λ* of this iterate's α (vrt_line_ali.hip), beside the sweep that reads the same buffer
-        if (s->op && (rc = launch_line_lambda_diagonal(p, nlam, s->d_native, s->weights.data(), nlam,
-                                                       sj.form() == SourceStore::kRows ? s->d_diag.get() : nullptr,
-                                                       sj.form() == SourceStore::kRows ? nullptr : s->d_diag.get(), st)))
-            return rc;
-        // J_λ (:84-111) from S, in the store's form
-        const void *I0 = f32 ? (const void *)s->f_I0.get() : (const void *)s->d_I0.get();
-        if ((rc = execute_locked(p, sj.exec_args(alpha, VRT_ALPHA_ANGLE_NATIVE, I0, s->weights.data(), st)))) return rc;
-        // S_new = (1 - ε) J + ε B_0 and the criterion's scalar (:261-263, :325-349); in sweep order the old S is read from the
-        // plane the new one is written to.  With the operator on (d_diag is NULL otherwise): the ALI update
+        // α, Λ* with the operator on (d_diag is NULL otherwise), the sweep and the update: the block's
         RatesJ J;
-        switch (sj.form()) {
-        case SourceStore::kPlanesF32:                        // (the roundings: include/voronoirt.h)
-            rc = launch_lambda_update_native_f32(p, nlam, sj.J_plane<float>(0), sj.J_plane<float>(1), s->f_B0, s->line.d_eps,
-                                                 sj.S_plane<float>(0), sj.S_plane<float>(1), s->d_scalars, st);
-            J = RatesJ::from_planes_f32(p, sj.J_plane<float>(0), sj.J_plane<float>(1));
-            break;
-        case SourceStore::kPlanes:
-            rc = launch_lambda_update_native(g, nlam, sj.J_plane(0), sj.J_plane(1), s->d_B0, s->line.d_eps, sj.S_plane(0),
-                                             sj.S_plane(1), s->d_scalars, st, s->d_diag);
-            J = RatesJ::from_planes(g, sj.J_plane(0), sj.J_plane(1));
-            break;
-        case SourceStore::kRows:
-            rc = launch_lambda_update(n, nlam, nlam, sj.J_rows(), s->d_B0, s->line.d_eps, sj.S_old(), sj.S_new(), s->d_scalars, st,
-                                      s->d_diag);
-            J = RatesJ::from_rows(sj.J_rows(), nlam);
-            break;
-        }
-        if (rc) return rc;
+        if ((rc = s->blk.step(p, s->line, s->d_pops, s->weights.data(), s->d_scalars, s->d_diag, st, &J))) return rc;
         // R, populations (:269, :274) from the same J
         if ((rc = launch_rates_populations(s->line.rates_in(), J, s->line.d_R, s->d_pops_new, st))) return rc;
         std::swap(s->d_pops, s->d_pops_new);
@@ -407,7 +346,7 @@ int vrt_lambda_iterate(vrt_lambda *s, double *max_rel_change)
         s->iterations++;
         // history copy or Ng step on the S of the plain update (the up-order copy); an accepted x_acc becomes that copy and
         // the down-order copy is rewritten from it, value for value
-        return ng_after_update(s->ng, s->iterations, sj, st);
+        return ng_after_update(s->ng, s->iterations, s->blk.sj, st);
     });
 }
 
@@ -419,8 +358,8 @@ int vrt_lambda_set_acceleration(vrt_lambda *s, int order, int start, int period)
     return guarded([&] {
         vrt_plan *p = s->p;
         std::lock_guard<std::mutex> lock(p->mu);
-        if ((rc = s->sj.ng_check()) || (rc = use_device(p->g->device))) return rc;
-        return ng_configure(s->ng, order, start, period, s->sj.ng_count());
+        if ((rc = s->blk.sj.ng_check()) || (rc = use_device(p->g->device))) return rc;
+        return ng_configure(s->ng, order, start, period, s->blk.sj.ng_count());
     });
 }
 
@@ -431,13 +370,13 @@ int vrt_lambda_use_operator(vrt_lambda *s, int op)
     return guarded([&] {
         vrt_plan *p = s->p;
         std::lock_guard<std::mutex> lock(p->mu);
-        if (s->sj.form() == SourceStore::kPlanesF32)
+        if (s->blk.sj.form() == SourceStore::kPlanesF32)
             return fail(VRT_EINVAL, "vrt_lambda_use_operator: not on a float-storage session (the ALI update works on double arrays)");
         int rc = use_device(p->g->device);
         if (rc) return rc;
         if (op == s->op) return (int)VRT_OK;
         if (op) {
-            if ((rc = s->sj.alloc_beside(s->d_diag))) return rc;
+            if ((rc = s->blk.sj.alloc_beside(s->d_diag))) return rc;
         } else
             s->d_diag.reset();
         s->op = op;
@@ -469,7 +408,7 @@ int vrt_lambda_get(vrt_lambda *s, double *J, double *S, double *populations, dou
         int rc = use_device(p->g->device);
         if (rc) return rc;
         const size_t n = (size_t)s->n;
-        if ((rc = s->sj.download(J, S, s->nlam, 0, p->g->stream))) return rc;
+        if ((rc = s->blk.sj.download(J, S, s->nlam, 0, p->g->stream))) return rc;
         if (populations) VRT_HIP_TRY(hipMemcpy(populations, s->d_pops, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
         if (R) VRT_HIP_TRY(hipMemcpy(R, s->line.d_R, sizeof(double) * 9 * n, hipMemcpyDeviceToHost));
         if (gamma) VRT_HIP_TRY(hipMemcpy(gamma, s->line.d_gamma, sizeof(double) * n, hipMemcpyDeviceToHost));
@@ -489,10 +428,10 @@ int vrt_lambda_set_state(vrt_lambda *s, const double *S, const double *populatio
         // staged copies beside the session: it is untouched until every one of them is complete
         SourceStore::Staged staged;
         DevBuf<double> pops;
-        if (S && (rc = s->sj.stage(S, s->nlam, 0, staged, st))) return rc;
+        if (S && (rc = s->blk.sj.stage(S, s->nlam, 0, staged, st))) return rc;
         if (populations && (rc = upload(pops, populations, 3 * (size_t)s->n, st))) return rc;
         VRT_HIP_TRY(hipStreamSynchronize(st));               // the host arrays may go after return
-        if (S) s->sj.adopt(staged);
+        if (S) s->blk.sj.adopt(staged);
         if (populations) std::swap(s->d_pops, pops);
         s->ng.have = 0;                                      // iterates of another state are no history of this one
         s->ng.last_applied = 0;

@@ -2,7 +2,8 @@
 // and reads in every iterate.  vrt_lambda (vrt_lambda.cpp), every member of vrt_multi_lambda (vrt_multi.cpp) and
 // vrt_regular_lambda (vrt_regular_lambda.hip) keep theirs in a LineCaseDev; the argument checks, the layout of the
 // wavelength-sized vector and the named arguments of the rate launches (vrt_physics.hip) stand here too, once.
-// What is NOT here: B_0, I_0 and the native α (their shape differs per session), the populations, the criterion's
+// What is NOT here: B_0, I_0 and the native α (their shape differs per session; the Voronoi sessions keep them in a
+// LineBlock, vrt_line_block.h, beside S and J), the populations, the criterion's
 // scalars, the shares, events and Ng state, and every step of an iterate beyond the two launches that read nothing but
 // this data and the current populations.  Inline host code, like vrt_source_store.h: tests/probes/line_case_main.cpp
 // compiles it against a fake runtime.

@@ -8,6 +8,11 @@
 //   "angle"   nλ < devices (or forced): the angles are dealt to the devices (ups and downs separately), the
 //             partial J's are summed by ONE RCCL all-reduce -- the north star's scheme
 // Two handles on the SAME device (rehearsal on a one-GPU box; RCCL refuses that) sum through a kernel instead.
+// Every piece of per-device work -- create, the two executes, the session's create, iterate, set_state and the Ng phases --
+// is a body handed to on_members (vrt_multi_members.h): a host thread per member, its device current, its plan locked
+// where the body sweeps, the first failing member reported as "device N: ...".  Both collectives go through rccl_group,
+// host columns reach a device through upload_cols (vrt_internal.h), and a session member's wavelengths are a LineBlock
+// (vrt_line_block.h), the one the single-device session holds.
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -15,11 +20,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <thread>
 
 #include "vrt_internal.h"
-#include "vrt_line_case.h"
-#include "vrt_source_store.h"
+#include "vrt_line_block.h"
+#include "vrt_multi_members.h"
 
 using namespace vrt;
 
@@ -73,8 +77,9 @@ struct Member {
     DevWork<double> dS, dA, dU, dD, dJ, dV;
     ncclComm_t comm = nullptr;             // RCCL rank of this device (NULL: the same-device rehearsal, or one device)
     ncclResult_t (*comm_destroy)(ncclComm_t) = nullptr;
-    int rc = VRT_OK;
+    int rc = VRT_OK;                       // on_members: of the last piece of work here, and its text
     std::string err;
+    std::mutex &plan_mutex() { return plan_all->mu; }
     ~Member()
     {
         if (!grid && !stream) return;      // never got a device (creation failed there)
@@ -109,6 +114,37 @@ static void block_of(int64_t n_units, int world, int rank, int64_t &start, int64
     stop = start + base + (rank < extra ? 1 : 0);
 }
 
+// ONE RCCL group call over every member: call(d, member) -> ncclResult_t queues the member's collective (`what`, for the
+// error text) with its device current.  Nothing returns between GroupStart and GroupEnd: an open group poisons every
+// later call.
+template <typename Call>
+static int rccl_group(vrt_multi *mm, const char *what, Call call)
+{
+    ncclResult_t r = mm->rccl.GroupStart();
+    hipError_t he = hipSuccess;
+    for (size_t d = 0; d < mm->m.size() && r == ncclSuccess && he == hipSuccess; d++) {
+        he = hipSetDevice(mm->m[d].device);
+        if (he == hipSuccess) r = call((int)d, mm->m[d]);
+    }
+    const ncclResult_t r2 = mm->rccl.GroupEnd();
+    if (he != hipSuccess) return fail(VRT_ENODEVICE, std::string("hipSetDevice: ") + hipGetErrorString(he));
+    if (r != ncclSuccess || r2 != ncclSuccess)
+        return fail(VRT_ENODEVICE, std::string(what) + ": " + mm->rccl.GetErrorString(r != ncclSuccess ? r : r2));
+    return VRT_OK;
+}
+
+// I_0 of one sweep direction for an execute: columns [l0, l1) of the host rows (n1, nlam) into the member's workspace;
+// *dev stays NULL without the array or without sites that take it
+static int stage_I0(DevWork<double> &d, const double *I0, int64_t n1, int64_t nlam, int64_t l0, int64_t l1, hipStream_t st,
+                    double **dev)
+{
+    *dev = nullptr;
+    if (!I0 || !n1) return VRT_OK;
+    const int rc = upload_cols(d, I0, (size_t)n1, nlam, l0, l1, st);
+    if (!rc) *dev = d;
+    return rc;
+}
+
 extern "C" {
 
 int vrt_multi_create(int n_devices, const int *devices, int64_t n, const double *pos_zxy, const int64_t *nbr, int64_t D1,
@@ -137,21 +173,18 @@ int vrt_multi_create(int n_devices, const int *devices, int64_t n, const double 
                 if (devices[e] == devices[d]) mm->distinct = false;
         }
         // one grid + all-angle plan per device, built concurrently (plan creation is host-side schedule work)
-        if (!run_workers(n_devices, [&](int d) {
-                Member &me = mm->m[(size_t)d];
-                vrt_grid *grid = nullptr;
-                vrt_plan *plan = nullptr;
-                me.rc = vrt_grid_create(n, pos_zxy, nbr, D1, bounds, me.device, &grid);
-                me.grid.reset(grid);
-                if (!me.rc) me.rc = vrt_plan_create_ex(grid, n_angles, k, mm->dirs.data(), n_sweeps, &plan);
-                me.plan_all.reset(plan);
-                if (!me.rc && (hipSetDevice(me.device) != hipSuccess || me.stream.create()))
-                    me.rc = fail(VRT_ENODEVICE, "cannot create a stream");
-                if (me.rc) me.err = vrt_last_error();
-            }))
-            return fail(VRT_ENOMEM, "out of host memory while creating the per-device plans");
-        for (const Member &me : mm->m)
-            if (me.rc) return fail(me.rc, "device " + std::to_string(me.device) + ": " + me.err);
+        // (kNoDevice: vrt_grid_create is the call that finds out whether the device exists)
+        int rc = on_members(mm->m, kNoDevice, every_member, [&](int, Member &me) {
+            vrt_grid *grid = nullptr;
+            vrt_plan *plan = nullptr;
+            int r = vrt_grid_create(n, pos_zxy, nbr, D1, bounds, me.device, &grid);
+            me.grid.reset(grid);
+            if (!r) r = vrt_plan_create_ex(grid, n_angles, k, mm->dirs.data(), n_sweeps, &plan);
+            me.plan_all.reset(plan);
+            if (!r && (hipSetDevice(me.device) != hipSuccess || me.stream.create())) r = fail(VRT_ENODEVICE, "cannot create a stream");
+            return r;
+        });
+        if (rc) return rc;
         // angles of the "angle" mode: ups and downs dealt round-robin separately (distributed.angle_assignment)
         {
             int ju = 0, jd = 0;
@@ -228,101 +261,61 @@ int vrt_multi_execute(vrt_multi *mm, int64_t nlam, int64_t ld, const double *S, 
                     me.plan_part.reset(part);
                     if (rc) return rc;
                 }
-        auto work = [&](int d) {
-            Member &me = mm->m[(size_t)d];
-            me.rc = VRT_OK;
-            auto chk = [&](hipError_t e, const char *what) {
-                if (e != hipSuccess && !me.rc) {
-                    me.rc = VRT_ENODEVICE;
-                    me.err = std::string(what) + ": " + hipGetErrorString(e);
-                }
-            };
-            chk(hipSetDevice(me.device), "hipSetDevice");
-            if (me.rc) return;
-            hipStream_t st = me.stream;
-            int64_t l0 = 0, l1 = nlam;
+        // lambda mode: the member's block of the wavelengths (a member without one sits the call out); angle mode: all of them
+        auto block = [&](int d, int64_t &l0, int64_t &l1) {
+            l0 = 0, l1 = nlam;
             if (shard == 1) block_of(nlam, W, d, l0, l1);
-            const int64_t nb = l1 - l0;
-            const size_t w8 = sizeof(double);
-            if (nb <= 0 || (shard == 2 && me.my_angles.empty())) {       // nothing to do here: contributes zeros in angle mode
-                if (shard == 2) {
-                    if ((me.rc = me.dJ.grow((size_t)n * (size_t)nlam))) { me.err = vrt_last_error(); return; }
-                    chk(hipMemsetAsync(me.dJ, 0, w8 * (size_t)n * (size_t)nlam, st), "hipMemsetAsync");
-                    chk(hipStreamSynchronize(st), "hipStreamSynchronize");      // another member's stream reads these zeros
-                }
-                return;
+            return l1 > l0;
+        };
+        int rc = on_members(mm->m, 0, [&](int d) { int64_t l0, l1; return !block(d, l0, l1); }, [&](int d, Member &me) {
+            hipStream_t st = me.stream;
+            int64_t l0, l1;
+            block(d, l0, l1);
+            const size_t sn = (size_t)n, nb = (size_t)(l1 - l0), w8 = sizeof(double);
+            int rc;
+            if (shard == 2 && me.my_angles.empty()) {                    // no angle here: its partial J is zero
+                if ((rc = me.dJ.grow(sn * nb))) return rc;
+                VRT_HIP_TRY(hipMemsetAsync(me.dJ, 0, w8 * sn * nb, st));
+                VRT_HIP_TRY(hipStreamSynchronize(st));                   // another member's stream reads these zeros
+                return (int)VRT_OK;
             }
             vrt_plan *plan = shard == 1 ? me.plan_all.get() : me.plan_part.get();
-            const int64_t nA = shard == 1 ? A : (int64_t)me.my_angles.size();
-            // S block (nb, n) dense on the device
-            if ((me.rc = me.dS.grow((size_t)n * (size_t)nb)) || (me.rc = me.dJ.grow((size_t)n * (size_t)nb))) {
-                me.err = vrt_last_error();
-                return;
-            }
-            chk(hipMemcpy2DAsync(me.dS, w8 * (size_t)nb, S + l0, w8 * (size_t)ld, w8 * (size_t)nb, (size_t)n, hipMemcpyHostToDevice, st), "upload S");
-            // alpha
-            const double *dA = nullptr;
-            if (alpha_mode == VRT_ALPHA_SITE) {
-                if ((me.rc = me.dA.grow((size_t)n))) { me.err = vrt_last_error(); return; }
-                chk(hipMemcpyAsync(me.dA, alpha, w8 * (size_t)n, hipMemcpyHostToDevice, st), "upload alpha");
-            } else if (alpha_mode == VRT_ALPHA_SITE_LAM) {
-                if ((me.rc = me.dA.grow((size_t)n * (size_t)nb))) { me.err = vrt_last_error(); return; }
-                chk(hipMemcpy2DAsync(me.dA, w8 * (size_t)nb, alpha + l0, w8 * (size_t)ld, w8 * (size_t)nb, (size_t)n, hipMemcpyHostToDevice, st), "upload alpha");
-            } else {
-                if ((me.rc = me.dA.grow((size_t)nA * (size_t)n * (size_t)nb))) { me.err = vrt_last_error(); return; }
-                for (int64_t j = 0; j < nA; j++) {
-                    const int64_t a = shard == 1 ? j : me.my_angles[(size_t)j];
-                    chk(hipMemcpy2DAsync(me.dA + (size_t)j * (size_t)n * (size_t)nb, w8 * (size_t)nb,
-                                         alpha + (size_t)a * (size_t)n * (size_t)ld + l0, w8 * (size_t)ld, w8 * (size_t)nb, (size_t)n,
-                                         hipMemcpyHostToDevice, st), "upload alpha");
+            const size_t nA = shard == 1 ? (size_t)A : me.my_angles.size();
+            // the block (nb, n) of S and of α dense on the device
+            if ((rc = upload_cols(me.dS, S, sn, ld, l0, l1, st)) || (rc = me.dJ.grow(sn * nb))) return rc;
+            if (alpha_mode == VRT_ALPHA_SITE) rc = upload_cols(me.dA, alpha, 1, (int64_t)sn, 0, (int64_t)sn, st);
+            else if (alpha_mode == VRT_ALPHA_SITE_LAM) rc = upload_cols(me.dA, alpha, sn, ld, l0, l1, st);
+            else {
+                rc = me.dA.grow(nA * sn * nb);
+                for (size_t j = 0; j < nA && !rc; j++) {
+                    const size_t a = shard == 1 ? j : (size_t)me.my_angles[j];
+                    rc = copy_cols<double>(me.dA + j * sn * nb, alpha + a * sn * (size_t)ld, sn, ld, l0, l1, st);
                 }
             }
-            dA = me.dA;
-            double *dU = nullptr, *dD = nullptr;
-            if (I0_up && n1u) {
-                if ((me.rc = me.dU.grow((size_t)n1u * (size_t)nb))) { me.err = vrt_last_error(); return; }
-                chk(hipMemcpy2DAsync(me.dU, w8 * (size_t)nb, I0_up + l0, w8 * (size_t)nlam, w8 * (size_t)nb, (size_t)n1u, hipMemcpyHostToDevice, st), "upload I0");
-                dU = me.dU;
-            }
-            if (I0_down && n1d) {
-                if ((me.rc = me.dD.grow((size_t)n1d * (size_t)nb))) { me.err = vrt_last_error(); return; }
-                chk(hipMemcpy2DAsync(me.dD, w8 * (size_t)nb, I0_down + l0, w8 * (size_t)nlam, w8 * (size_t)nb, (size_t)n1d, hipMemcpyHostToDevice, st), "upload I0");
-                dD = me.dD;
-            }
-            if (me.rc) return;
+            double *dU, *dD;
+            if (rc || (rc = stage_I0(me.dU, I0_up, n1u, nlam, l0, l1, st, &dU)) || (rc = stage_I0(me.dD, I0_down, n1d, nlam, l0, l1, st, &dD)))
+                return rc;
             std::vector<double> wv;
             if (shard == 1) wv.assign(weights, weights + A);
             else
                 for (int a : me.my_angles) wv.push_back(weights[a]);
-            me.rc = vrt_plan_execute_dev(plan, nb, nb, me.dS, dA, alpha_mode, dU, dD, wv.data(), me.dJ, nullptr, st);
-            if (me.rc) { me.err = vrt_last_error(); return; }
+            if ((rc = vrt_plan_execute_dev(plan, (int64_t)nb, (int64_t)nb, me.dS, me.dA, alpha_mode, dU, dD, wv.data(), me.dJ, nullptr, st)))
+                return rc;
             if (shard == 1)     // the device owns rows l0..l1 of J: straight home
-                chk(hipMemcpy2DAsync(J + l0, w8 * (size_t)ld, me.dJ, w8 * (size_t)nb, w8 * (size_t)nb, (size_t)n, hipMemcpyDeviceToHost, st), "download J");
-            chk(hipStreamSynchronize(st), "hipStreamSynchronize");
-            // (a chained sweep that gave up waiting: reported by THIS call, whose J it spoiled)
-            if (!me.rc && (me.rc = patch_chain_check(plan))) me.err = vrt_last_error();
-        };
-        if (!run_workers(W, work)) return fail(VRT_ENOMEM, "out of host memory in a device worker");
-        for (const Member &me : mm->m)
-            if (me.rc) return fail(me.rc, "device " + std::to_string(me.device) + ": " + me.err);
+                VRT_HIP_TRY(hipMemcpy2DAsync(J + l0, w8 * (size_t)ld, me.dJ, w8 * nb, w8 * nb, sn, hipMemcpyDeviceToHost, st));
+            VRT_HIP_TRY(hipStreamSynchronize(st));
+            return patch_chain_check(plan);      // (a chained sweep that gave up waiting: reported by THIS call, whose J it spoiled)
+        });
+        if (rc) return rc;
         if (shard == 2) {
             // J = Σ over the devices' partial sums, wanted on ONE device only (the host array is filled from device 0):
             // one RCCL reduce to rank 0 over xGMI -- half the bytes of an all-reduce -- or, on a shared device, adds
             const size_t cnt = (size_t)n * (size_t)nlam;
             if (mm->uses_rccl()) {
-                // (nothing may return between GroupStart and GroupEnd: an open group poisons every later call)
-                ncclResult_t r = mm->rccl.GroupStart();
-                hipError_t he = hipSuccess;
-                for (int d = 0; d < W && r == ncclSuccess && he == hipSuccess; d++) {
-                    Member &me = mm->m[(size_t)d];
-                    he = hipSetDevice(me.device);
-                    if (he == hipSuccess)
-                        r = mm->rccl.Reduce(me.dJ, me.dJ, cnt, ncclDouble, ncclSum, 0, mm->m[(size_t)d].comm, me.stream);
-                }
-                const ncclResult_t r2 = mm->rccl.GroupEnd();
-                if (he != hipSuccess) return fail(VRT_ENODEVICE, std::string("hipSetDevice: ") + hipGetErrorString(he));
-                if (r != ncclSuccess || r2 != ncclSuccess)
-                    return fail(VRT_ENODEVICE, std::string("ncclReduce: ") + mm->rccl.GetErrorString(r != ncclSuccess ? r : r2));
+                if ((rc = rccl_group(mm, "ncclReduce", [&](int, Member &me) {
+                        return mm->rccl.Reduce(me.dJ, me.dJ, cnt, ncclDouble, ncclSum, 0, me.comm, me.stream);
+                    })))
+                    return rc;
                 for (Member &me : mm->m) {
                     VRT_HIP_TRY(hipSetDevice(me.device));
                     VRT_HIP_TRY(hipStreamSynchronize(me.stream));
@@ -364,66 +357,36 @@ int vrt_multi_execute_line(vrt_multi *mm, int64_t nlam, int64_t ld, const double
         const int64_t n = mm->n;
         const int64_t n1u = mm->m[0].grid->up.n1, n1d = mm->m[0].grid->down.n1;
         mm->last_shard = 1;
-        auto work = [&](int d) {
-            Member &me = mm->m[(size_t)d];
-            me.rc = VRT_OK;
-            auto chk = [&](hipError_t e, const char *what) {
-                if (e != hipSuccess && !me.rc) {
-                    me.rc = VRT_ENODEVICE;
-                    me.err = std::string(what) + ": " + hipGetErrorString(e);
-                }
-            };
-            int64_t l0, l1;
+        auto block = [&](int d, int64_t &l0, int64_t &l1) {
             block_of(nlam, W, d, l0, l1);
-            const int64_t nb = l1 - l0;
-            if (nb <= 0) return;
-            chk(hipSetDevice(me.device), "hipSetDevice");
-            if (me.rc) return;
+            return l1 > l0;
+        };
+        return on_members(mm->m, kLockPlan, [&](int d) { int64_t l0, l1; return !block(d, l0, l1); }, [&](int d, Member &me) {
             hipStream_t st = me.stream;
             vrt_plan *plan = me.plan_all.get();
-            std::lock_guard<std::mutex> plock(plan->mu);
-            const size_t w8 = sizeof(double), sn = (size_t)n;
-            const size_t nnat = (size_t)vrt_plan_native_alpha_count(plan, nb);
+            int64_t l0, l1;
+            block(d, l0, l1);
+            const size_t w8 = sizeof(double), sn = (size_t)n, nb = (size_t)(l1 - l0);
             // S | seven per-site vectors + the block's wavelengths | native alpha | J
-            if ((me.rc = me.dS.grow(sn * (size_t)nb)) || (me.rc = me.dJ.grow(sn * (size_t)nb)) ||
-                (me.rc = me.dA.grow(nnat)) || (me.rc = me.dV.grow(7 * sn + (size_t)nb))) {
-                me.err = vrt_last_error();
-                return;
-            }
+            int rc;
+            if ((rc = upload_cols(me.dS, S, sn, ld, l0, l1, st)) || (rc = me.dJ.grow(sn * nb)) ||
+                (rc = me.dA.grow((size_t)vrt_plan_native_alpha_count(plan, (int64_t)nb))) || (rc = me.dV.grow(7 * sn + nb)))
+                return rc;
             double *d_vel = me.dV, *d_dop = me.dV + 3 * sn, *d_gam = me.dV + 4 * sn, *d_str = me.dV + 5 * sn, *d_ac = me.dV + 6 * sn,
                    *d_lam = me.dV + 7 * sn;
-            chk(hipMemcpy2DAsync(me.dS, w8 * (size_t)nb, S + l0, w8 * (size_t)ld, w8 * (size_t)nb, sn, hipMemcpyHostToDevice, st), "upload S");
-            chk(hipMemcpyAsync(d_vel, velocity, w8 * 3 * sn, hipMemcpyHostToDevice, st), "upload velocity");
-            chk(hipMemcpyAsync(d_dop, doppler_width, w8 * sn, hipMemcpyHostToDevice, st), "upload doppler");
-            chk(hipMemcpyAsync(d_gam, gamma, w8 * sn, hipMemcpyHostToDevice, st), "upload gamma");
-            chk(hipMemcpyAsync(d_str, line_strength, w8 * sn, hipMemcpyHostToDevice, st), "upload strength");
-            chk(hipMemcpyAsync(d_ac, alpha_cont, w8 * sn, hipMemcpyHostToDevice, st), "upload alpha_cont");
-            chk(hipMemcpyAsync(d_lam, lambda + l0, w8 * (size_t)nb, hipMemcpyHostToDevice, st), "upload lambda");
-            double *dU = nullptr, *dD = nullptr;
-            if (I0_up && n1u) {
-                if ((me.rc = me.dU.grow((size_t)n1u * (size_t)nb))) { me.err = vrt_last_error(); return; }
-                chk(hipMemcpy2DAsync(me.dU, w8 * (size_t)nb, I0_up + l0, w8 * (size_t)nlam, w8 * (size_t)nb, (size_t)n1u, hipMemcpyHostToDevice, st), "upload I0");
-                dU = me.dU;
-            }
-            if (I0_down && n1d) {
-                if ((me.rc = me.dD.grow((size_t)n1d * (size_t)nb))) { me.err = vrt_last_error(); return; }
-                chk(hipMemcpy2DAsync(me.dD, w8 * (size_t)nb, I0_down + l0, w8 * (size_t)nlam, w8 * (size_t)nb, (size_t)n1d, hipMemcpyHostToDevice, st), "upload I0");
-                dD = me.dD;
-            }
-            if (me.rc) return;
-            if ((me.rc = launch_line_opacity(plan, nb, d_lam, lambda0, c0, d_vel, d_dop, d_gam, d_str, d_ac, me.dA, st)) ||
-                (me.rc = execute_locked(plan, caller_args(nb, nb, me.dS, me.dA, VRT_ALPHA_ANGLE_NATIVE, dU, dD, weights, me.dJ, nullptr, st, false)))) {
-                me.err = vrt_last_error();
-                return;
-            }
-            chk(hipMemcpy2DAsync(J + l0, w8 * (size_t)ld, me.dJ, w8 * (size_t)nb, w8 * (size_t)nb, sn, hipMemcpyDeviceToHost, st), "download J");
-            chk(hipStreamSynchronize(st), "hipStreamSynchronize");
-            if (!me.rc && (me.rc = patch_chain_check(plan))) me.err = vrt_last_error();
-        };
-        if (!run_workers(W, work)) return fail(VRT_ENOMEM, "out of host memory in a device worker");
-        for (const Member &me : mm->m)
-            if (me.rc) return fail(me.rc, "device " + std::to_string(me.device) + ": " + me.err);
-        return VRT_OK;
+            const struct { double *dev; const double *host; size_t count; } vectors[] = {
+                {d_vel, velocity, 3 * sn}, {d_dop, doppler_width, sn}, {d_gam, gamma, sn}, {d_str, line_strength, sn},
+                {d_ac, alpha_cont, sn}, {d_lam, lambda + l0, nb}};
+            for (const auto &v : vectors) VRT_HIP_TRY(hipMemcpyAsync(v.dev, v.host, w8 * v.count, hipMemcpyHostToDevice, st));
+            double *dU, *dD;
+            if ((rc = stage_I0(me.dU, I0_up, n1u, nlam, l0, l1, st, &dU)) || (rc = stage_I0(me.dD, I0_down, n1d, nlam, l0, l1, st, &dD)) ||
+                (rc = launch_line_opacity(plan, (int64_t)nb, d_lam, lambda0, c0, d_vel, d_dop, d_gam, d_str, d_ac, me.dA, st)) ||
+                (rc = execute_locked(plan, caller_args((int64_t)nb, (int64_t)nb, me.dS, me.dA, VRT_ALPHA_ANGLE_NATIVE, dU, dD, weights, me.dJ, nullptr, st, false))))
+                return rc;
+            VRT_HIP_TRY(hipMemcpy2DAsync(J + l0, w8 * (size_t)ld, me.dJ, w8 * nb, w8 * nb, sn, hipMemcpyDeviceToHost, st));
+            VRT_HIP_TRY(hipStreamSynchronize(st));
+            return patch_chain_check(plan);
+        });
     });
 }
 
@@ -435,22 +398,18 @@ int vrt_multi_execute_line(vrt_multi *mm, int64_t nlam, int64_t ld, const double
 // angle, the sweep, S_new with its share of the convergence maximum, and its share of the six λ-integrals of the
 // radiative rates (rates.jl:154-201).  The shares are summed by ONE all-reduce of 6 n doubles over xGMI (SURVEY 8e:
 // "only R and one scalar are reduced"); J never travels.  Every device then solves the statistical equilibrium of
-// every site itself (populations.jl:191-221), so the next iteration's opacity needs no further exchange.  A member's S and
-// J live in a SourceStore (vrt_source_store.h), in rows or in sweep order, all members alike.  Float storage
-// (vrt_multi_lambda_create_f32): every member's store is kPlanesF32 and f_B0, f_I0 and f_native replace d_B0, d_I0 and
-// d_native -- no member holds a double array of size nλ_block·n or nλ_block·n·angles; the shares, the all-reduce and the
-// statistical equilibrium are the same doubles.
+// every site itself (populations.jl:191-221), so the next iteration's opacity needs no further exchange.  A member's
+// wavelengths are a LineBlock (vrt_line_block.h) -- S and J in rows or in sweep order, B_0, I_0 and the native α, all
+// members alike -- and LineBlock::step is its iterate up to the update, the one the single-device session runs.  Float
+// storage (vrt_multi_lambda_create_f32): no member holds a double array of size nλ_block·n or nλ_block·n·angles; the
+// shares, the all-reduce and the statistical equilibrium are the same doubles.
 struct LambdaMember {
     int device = 0;
-    int64_t l0 = 0, l1 = 0;
     LineCaseDev line;                   // the whole case (every site, ALL wavelengths), γ, the line strength and R (vrt_line_case.h)
-    DevBuf<double> d_B0, d_I0, d_native;   // this block's columns (B_0 in the store's order: rows, or its up-order plane set)
-    DevBuf<float> f_B0, f_I0, f_native;    // float storage: B_0 rounded once in the up order, I_0, the native α
+    LineBlock blk;                      // this device's wavelengths [blk.l0, blk.l1) (none: placeholders and no store)
     DevBuf<double> d_pops, d_shares;
     DevBuf<unsigned long long> d_scalars;
     Event ev;
-    SourceStore sj;                     // the block's S and J, as the one-device session keeps them (a member without
-                                        // wavelengths: never created, holds nothing)
     NgState ng;                         // this block's history and workspace (vrt_multi_lambda_set_acceleration; off: nothing)
     ~LambdaMember() { (void)hipSetDevice(device); }    // (its own copy: the vrt_multi may be gone already); then the members go
 };
@@ -468,38 +427,15 @@ struct vrt_multi_lambda {
 
 namespace {
 
-// columns [l0, l1) of a host array (rows, nlam) into a dense device block (rows, l1 - l0)
-int dupload_cols(DevBuf<double> &d, const double *h, size_t rows, int64_t nlam, int64_t l0, int64_t l1, hipStream_t st)
-{
-    const size_t nb = (size_t)(l1 - l0);
-    int rc = d.alloc(rows * nb);
-    if (rc || nb == 0) return rc;
-    VRT_HIP_TRY(hipMemcpy2DAsync(d, sizeof(double) * nb, h + l0, sizeof(double) * (size_t)nlam, sizeof(double) * nb, rows, hipMemcpyHostToDevice, st));
-    return VRT_OK;
-}
-
 // ---- Ng acceleration of the session (vrt_multi_lambda_set_acceleration): the phases of vrt_internal.h, each over every
 // member that holds wavelengths, on the S of its store.
 
-// body(d, member, its share of the session) -> rc on every member with wavelengths, one host thread each, the member's
-// device current and its plan locked
+// body(d, member, its share of the session) -> rc on every member with wavelengths, its plan locked (on_members)
 template <typename Body>
 int ng_on_members(vrt_multi_lambda *s, Body body)
 {
-    vrt_multi *mm = s->mm;
-    auto work = [&](int d) {
-        Member &me = mm->m[(size_t)d];
-        LambdaMember &l = s->lm[(size_t)d];
-        me.rc = VRT_OK;
-        if (l.l1 <= l.l0) return;
-        if (hipSetDevice(me.device) != hipSuccess) { me.rc = VRT_ENODEVICE; me.err = "hipSetDevice"; return; }
-        std::lock_guard<std::mutex> plock(me.plan_all->mu);
-        if ((me.rc = body(d, me, l))) me.err = vrt_last_error();
-    };
-    if (!run_workers((int)mm->m.size(), work)) return fail(VRT_ENOMEM, "out of host memory in a device worker");
-    for (const Member &me : mm->m)
-        if (me.rc) return fail(me.rc, "device " + std::to_string(me.device) + ": " + me.err);
-    return VRT_OK;
+    return on_members(s->mm->m, kLockPlan, [&](int d) { return s->lm[(size_t)d].blk.nb() == 0; },
+                      [&](int d, Member &me) { return body(d, me, s->lm[(size_t)d]); });
 }
 
 // After the plain update of iterate s->iterations (every stream is synchronised, mm->mu is held).  A due step: every member's
@@ -513,17 +449,17 @@ int multi_ng_after_iterate(vrt_multi_lambda *s)
     if (due == kNgNothing) return VRT_OK;
     if (due != kNgStep)
         return ng_on_members(s, [&](int, Member &me, LambdaMember &l) {
-            int rc = ng_record(l.ng, due, l.sj.ng_S(), l.sj.ng_count(), me.stream);
+            int rc = ng_record(l.ng, due, l.blk.sj.ng_S(), l.blk.sj.ng_count(), me.stream);
             if (!rc && hipStreamSynchronize(me.stream) != hipSuccess) rc = fail(VRT_ENODEVICE, "copying S into the history failed");
             return rc;
         });
     bool complete = true;
     for (LambdaMember &l : s->lm)
-        if (l.l1 > l.l0 && !ng_take_history(l.ng)) complete = false;
+        if (l.blk.nb() > 0 && !ng_take_history(l.ng)) complete = false;
     if (!complete) return VRT_OK;               // switched on too late for this one, or the state was replaced: nothing due
     std::vector<double> part(5 * (size_t)W, 0.0);
     int rc = ng_on_members(s, [&](int d, Member &me, LambdaMember &l) {
-        return ng_sums(l.sj.ng_range(), l.sj.ng_S(), l.ng.hist[0], l.ng.hist[1], l.ng.hist[2],
+        return ng_sums(l.blk.sj.ng_range(), l.blk.sj.ng_S(), l.ng.hist[0], l.ng.hist[1], l.ng.hist[2],
                        l.ng.d_ws, &part[5 * (size_t)d], me.stream);
     });
     if (rc) return rc;
@@ -532,26 +468,26 @@ int multi_ng_after_iterate(vrt_multi_lambda *s)
     std::vector<int> piece_of((size_t)W, -1);
     for (int d = 0; d < W; d++) {
         LambdaMember &l = s->lm[(size_t)d];
-        if (l.l1 <= l.l0) continue;
+        if (l.blk.nb() == 0) continue;
         ng_add_sums(s->ng.last_sums, &part[5 * (size_t)d], pieces.empty());
         piece_of[(size_t)d] = (int)pieces.size();
-        pieces.push_back(NgPiece{&l.ng, &l.sj.ng_S(), false});
+        pieces.push_back(NgPiece{&l.ng, &l.blk.sj.ng_S(), false});
     }
     s->ng.last_applied = -1;
     const bool valid = ng_coefficients(s->ng.last_sums, s->ng.last_coeffs);
     if (valid) {
         const double a = s->ng.last_coeffs[0], b = s->ng.last_coeffs[1];
         rc = ng_on_members(s, [&](int d, Member &me, LambdaMember &l) {
-            return ng_apply(l.sj.ng_range(), a, b, l.sj.ng_S(), l.ng.hist[0], l.ng.hist[1], l.ng.hist[2],
+            return ng_apply(l.blk.sj.ng_range(), a, b, l.blk.sj.ng_S(), l.ng.hist[0], l.ng.hist[1], l.ng.hist[2],
                             l.ng.d_ws, &pieces[(size_t)piece_of[(size_t)d]].good, me.stream);
         });
         if (rc) return rc;
     }
     if (!ng_commit(pieces.data(), (int)pieces.size(), valid)) return VRT_OK;
-    if (s->lm[0].sj.two_orders()) {             // (every member with wavelengths keeps the form of the first)
+    if (s->lm[0].blk.sj.two_orders()) {             // (every member with wavelengths keeps the form of the first)
         // the down-order copies from the new up-order ones, value for value
         rc = ng_on_members(s, [&](int, Member &me, LambdaMember &l) {
-            int r = l.sj.mirror_down(me.stream);
+            int r = l.blk.sj.mirror_down(me.stream);
             if (!r && hipStreamSynchronize(me.stream) != hipSuccess) r = fail(VRT_ENODEVICE, "rewriting the down-order S failed");
             return r;
         });
@@ -578,17 +514,8 @@ static int multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const dou
     return guarded([&] {
         std::lock_guard<std::mutex> lock(mm->mu);
         const int W = (int)mm->m.size();
-        for (const Member &me : mm->m) {
-            const vrt_plan *p = me.plan_all.get();
-            if (int rc = line_path_ok(p, "the line session")) return rc;
-            if (p->A != (int)p->n_angles_user)
-                return fail(VRT_EINVAL, "per-angle alpha needs every angle active (no θ = 90 direction)");
-            if (f32) {                                  // float planes exist on the patch path only: no fp64 fallback
-                if (int rc = native_planes_ok(p, true)) return rc;
-                if (p->tune.lambda_native == 0 || (p->tune.path != 0 && p->tune.path != 4))
-                    return fail(VRT_EINVAL, "the float-storage line session keeps S and J in the patch path's sweep order: not with VRT_LAMBDA_NATIVE=0 or a VRT_PATH other than patches");
-            }
-        }
+        for (const Member &me : mm->m)
+            if (int rc = line_session_plan_ok(me.plan_all.get(), f32)) return rc;
         std::unique_ptr<vrt_multi_lambda> s(new vrt_multi_lambda());
         s->mm = mm;
         s->f32 = f32;
@@ -601,53 +528,22 @@ static int multi_lambda_create(vrt_multi *mm, const vrt_line_case *lc, const dou
         for (const Member &me : mm->m)
             if (!f32 && !SourceStore::plan_keeps_planes(me.plan_all.get())) form = SourceStore::kRows;
         const size_t n = (size_t)mm->n;
-        std::vector<int> rcs((size_t)W, VRT_OK);
-        std::vector<std::string> errs((size_t)W);
-        auto work = [&](int d) {
-            Member &me = mm->m[(size_t)d];
+        for (int d = 0; d < W; d++) s->lm[(size_t)d].device = mm->m[(size_t)d].device;      // (what a member's destructor needs)
+        int rc = on_members(mm->m, 0, every_member, [&](int d, Member &me) {
             LambdaMember &l = s->lm[(size_t)d];
-            l.device = me.device;
-            block_of(nlam, W, d, l.l0, l.l1);
-            const size_t nb = (size_t)(l.l1 - l.l0);
-            int rc = VRT_OK;
-            if (hipSetDevice(me.device) != hipSuccess) { rcs[(size_t)d] = VRT_ENODEVICE; errs[(size_t)d] = "hipSetDevice"; return; }
             hipStream_t st = me.stream;
-            vrt_grid *g = me.grid.get();
-#define VRT_S(expr) do { if (!rc) rc = (expr); } while (0)
-            VRT_S(l.line.create(lc, mm->n, st));
-            VRT_S(upload(l.d_pops, lc->lte_populations, 3 * n, st));               // populations = copy(LTE_pops), :232
-            VRT_S(dupload_cols(l.d_B0, lc->B0, n, nlam, l.l0, l.l1, st));
-            if (nb) VRT_S(l.sj.create(me.plan_all.get(), (int64_t)nb, form, l.d_B0, st));      // S_new = B_0, S_old = zero(S_new), :236-240
-            VRT_S(l.d_shares.alloc(6 * n));
-            VRT_S(l.d_scalars.alloc(2));
-            VRT_S(l.ev.create(hipEventDisableTiming));
-            // I_0 = B_λ of the bottom layer (:99-101) and α_tot of every angle in the sweep's storage type; B_0 into the store's order
-            const size_t nnat = nb ? (size_t)vrt_plan_native_alpha_count(me.plan_all.get(), (int64_t)nb) : 1;
-            if (f32) {
-                VRT_S(l.f_I0.alloc((size_t)g->up.n1 * nb));
-                VRT_S(l.f_native.alloc(nnat));
-                if (nb) {
-                    VRT_S(launch_gather_rows_f32(g->up.n1, (int64_t)nb, (int64_t)nb, g->up.d_order, l.d_B0, l.f_I0, st));
-                    VRT_S(l.sj.to_up_order(l.d_B0, l.f_B0, st));         // (rounded once; the staged doubles go)
-                }
-            } else {
-                VRT_S(l.d_I0.alloc((size_t)g->up.n1 * nb));
-                VRT_S(l.d_native.alloc(nnat));
-                if (nb) {
-                    VRT_S(launch_gather_rows(g->up.n1, (int64_t)nb, (int64_t)nb, g->up.d_order, l.d_B0, l.d_I0, st));
-                    VRT_S(l.sj.to_up_order(l.d_B0, st));
-                }
-            }
-#undef VRT_S
-            if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(VRT_ENODEVICE, "uploading the line case failed");
-            if (rc) { rcs[(size_t)d] = rc; errs[(size_t)d] = vrt_last_error(); }
-        };
-        const bool ok = run_workers(W, work);
-        for (int d = 0; d < W; d++)
-            if (!ok || rcs[(size_t)d]) {
-                const int rc = ok ? rcs[(size_t)d] : VRT_ENOMEM;
-                return fail(rc, ok ? "device " + std::to_string(mm->m[(size_t)d].device) + ": " + errs[(size_t)d] : "out of host memory");
-            }
+            int64_t l0, l1;
+            block_of(nlam, W, d, l0, l1);
+            int rc;
+            if ((rc = l.line.create(lc, mm->n, st)) ||
+                (rc = upload(l.d_pops, lc->lte_populations, 3 * n, st)) ||           // populations = copy(LTE_pops), :232
+                (rc = l.blk.create(me.plan_all.get(), lc->B0, nlam, l0, l1, form, st)) || (rc = l.d_shares.alloc(6 * n)) ||
+                (rc = l.d_scalars.alloc(2)) || (rc = l.ev.create(hipEventDisableTiming)))
+                return rc;
+            if (hipStreamSynchronize(st) != hipSuccess) return fail(VRT_ENODEVICE, "uploading the line case failed");
+            return (int)VRT_OK;
+        });
+        if (rc) return rc;
         *out = s.release();
         return VRT_OK;
     });
@@ -680,66 +576,26 @@ int vrt_multi_lambda_iterate(vrt_multi_lambda *s, double *max_rel_change)
         const int W = (int)mm->m.size();
         const int64_t n = s->n;
         // ---- every device: its wavelengths' share of the iteration, enqueued on its stream ----------------------------
-        auto work = [&](int d) {
-            Member &me = mm->m[(size_t)d];
+        int rc = on_members(mm->m, kLockPlan, every_member, [&](int d, Member &me) {
             LambdaMember &l = s->lm[(size_t)d];
-            me.rc = VRT_OK;
-            const int64_t nb = l.l1 - l.l0;
-            if (hipSetDevice(me.device) != hipSuccess) { me.rc = VRT_ENODEVICE; me.err = "hipSetDevice"; return; }
             hipStream_t st = me.stream;
-            vrt_plan *p = me.plan_all.get();
-            vrt_grid *g = me.grid.get();
-            std::lock_guard<std::mutex> plock(p->mu);
-            int rc = VRT_OK;
-            SourceStore &sj = l.sj;
-            if (nb == 0 && hipMemsetAsync(l.d_scalars, 0, 2 * sizeof(unsigned long long), st) != hipSuccess)
-                rc = fail(VRT_ENODEVICE, "hipMemsetAsync");
-            if (nb > 0 && sj.form() == SourceStore::kRows &&
-                hipMemcpyAsync(sj.S_old(), sj.S_new(), sizeof(double) * (size_t)n * (size_t)nb, hipMemcpyDeviceToDevice, st) != hipSuccess)
-                rc = fail(VRT_ENODEVICE, "hipMemcpyAsync");                                                      // S_old = copy(S_new), :258
-            // γ and the line strength of the current populations (:72-75, line.jl:219-225), α_tot of every angle (:89-96)
-            if (!rc) rc = l.line.terms(l.d_pops, st);
-            if (!rc && nb > 0) {
-                void *alpha = s->f32 ? (void *)l.f_native.get() : (void *)l.d_native.get();
-                const void *I0 = s->f32 ? (const void *)l.f_I0.get() : (const void *)l.d_I0.get();
-                rc = l.line.opacity(p, nb, l.l0, alpha, st, s->f32);
-                // J_λ of this block (:84-111)
-                if (!rc) rc = execute_locked(p, sj.exec_args(alpha, VRT_ALPHA_ANGLE_NATIVE, I0, s->weights.data(), st));
-                // S_new = (1 - ε) J + ε B_0 and this block's share of the criterion (:261-263, :325-349); in sweep order the
-                // update reads the old S where it writes the new
-                if (!rc && sj.form() == SourceStore::kPlanesF32)      // (the roundings: include/voronoirt.h)
-                    rc = launch_lambda_update_native_f32(p, nb, sj.J_plane<float>(0), sj.J_plane<float>(1), l.f_B0, l.line.d_eps,
-                                                         sj.S_plane<float>(0), sj.S_plane<float>(1), l.d_scalars, st);
-                else if (!rc && sj.form() == SourceStore::kPlanes)
-                    rc = launch_lambda_update_native(g, nb, sj.J_plane(0), sj.J_plane(1), l.d_B0, l.line.d_eps, sj.S_plane(0), sj.S_plane(1), l.d_scalars, st);
-                else if (!rc)
-                    rc = launch_lambda_update(n, nb, nb, sj.J_rows(), l.d_B0, l.line.d_eps, sj.S_old(), sj.S_new(), l.d_scalars, st);
-            }
-            // this block's share of the six rate integrals (rates.jl:154-201), from J in rows or in its planes
-            // (a member without wavelengths: an empty range of rows)
-            const RatesJ J = sj.form() == SourceStore::kPlanesF32 ? RatesJ::from_planes_f32(p, sj.J_plane<float>(0), sj.J_plane<float>(1))
-                             : sj.form() == SourceStore::kPlanes ? RatesJ::from_planes(g, sj.J_plane(0), sj.J_plane(1))
-                                                                 : RatesJ::from_rows(sj.J_rows(), std::max<int64_t>(nb, 1));
-            if (!rc) rc = launch_rates_partial(l.line.rates_in(), J, l.l0, l.l1, l.d_shares, st);
-            if (rc) { me.rc = rc; me.err = vrt_last_error(); }
-        };
-        if (!run_workers(W, work)) return fail(VRT_ENOMEM, "out of host memory in a device worker");
-        for (const Member &me : mm->m)
-            if (me.rc) return fail(me.rc, "device " + std::to_string(me.device) + ": " + me.err);
+            if (l.blk.nb() == 0)                 // no update writes its words
+                VRT_HIP_TRY(hipMemsetAsync(l.d_scalars, 0, 2 * sizeof(unsigned long long), st));
+            // α of the current populations, the sweep and the update with this block's share of the criterion: the block's
+            RatesJ J;
+            int rc = l.blk.step(me.plan_all.get(), l.line, l.d_pops, s->weights.data(), l.d_scalars, nullptr, st, &J);
+            // this block's share of the six rate integrals (rates.jl:154-201), from J in the store's form
+            return rc ? rc : launch_rates_partial(l.line.rates_in(), J, l.blk.l0, l.blk.l1, l.d_shares, st);
+        });
+        if (rc) return rc;
         // ---- the shares summed over the devices: ONE all-reduce of 6 n doubles (in place), stream-ordered ---------------
         const size_t cnt = 6 * (size_t)n;
         if (mm->uses_rccl()) {
-            ncclResult_t r = mm->rccl.GroupStart();
-            hipError_t he = hipSuccess;
-            for (int d = 0; d < W && r == ncclSuccess && he == hipSuccess; d++) {
-                he = hipSetDevice(mm->m[(size_t)d].device);
-                if (he == hipSuccess)
-                    r = mm->rccl.AllReduce(s->lm[(size_t)d].d_shares, s->lm[(size_t)d].d_shares, cnt, ncclDouble, ncclSum, mm->m[(size_t)d].comm, mm->m[(size_t)d].stream);
-            }
-            const ncclResult_t r2 = mm->rccl.GroupEnd();
-            if (he != hipSuccess) return fail(VRT_ENODEVICE, std::string("hipSetDevice: ") + hipGetErrorString(he));
-            if (r != ncclSuccess || r2 != ncclSuccess)
-                return fail(VRT_ENODEVICE, std::string("ncclAllReduce: ") + mm->rccl.GetErrorString(r != ncclSuccess ? r : r2));
+            if ((rc = rccl_group(mm, "ncclAllReduce", [&](int d, Member &me) {
+                    double *shares = s->lm[(size_t)d].d_shares;
+                    return mm->rccl.AllReduce(shares, shares, cnt, ncclDouble, ncclSum, me.comm, me.stream);
+                })))
+                return rc;
         } else if (W > 1) {
             // handles on ONE device (rehearsal): member 0 adds the others' shares behind their streams, the others copy the sum
             Member &m0 = mm->m[0];
@@ -803,10 +659,10 @@ int vrt::multi_lambda_set_acceleration(vrt_multi_lambda *s, int order, int start
         for (int d = 0; d < W && !rc; d++) {
             Member &me = mm->m[(size_t)d];
             LambdaMember &l = s->lm[(size_t)d];
-            if (l.l1 <= l.l0) continue;
+            if (l.blk.nb() == 0) continue;
             if (hipSetDevice(me.device) != hipSuccess) { rc = fail(VRT_ENODEVICE, "hipSetDevice failed"); break; }
             std::lock_guard<std::mutex> plock(me.plan_all->mu);
-            rc = ng_configure(l.ng, order, start, period, l.sj.ng_count());
+            rc = ng_configure(l.ng, order, start, period, l.blk.sj.ng_count());
         }
         if (rc) {
             // one member could not: no member keeps a history, and the session goes on as a plain one
@@ -843,7 +699,7 @@ int vrt_multi_lambda_get(vrt_multi_lambda *s, double *J, double *S, double *popu
             VRT_HIP_TRY(hipSetDevice(mm->m[d].device));
             {   // this block's columns, in the caller's layout
                 std::lock_guard<std::mutex> plock(mm->m[d].plan_all->mu);
-                if (int rc = l.sj.download(J, S, s->nlam, l.l0, mm->m[d].stream)) return rc;
+                if (int rc = l.blk.sj.download(J, S, s->nlam, l.blk.l0, mm->m[d].stream)) return rc;
             }
             if (d == 0) {
                 if (populations) VRT_HIP_TRY(hipMemcpy(populations, l.d_pops, w8 * 3 * n, hipMemcpyDeviceToHost));
@@ -872,34 +728,22 @@ int vrt_multi_lambda_set_state(vrt_multi_lambda *s, const double *S, const doubl
             ~Staged() { (void)hipSetDevice(device); }        // then the members go, on their device
         };
         std::vector<Staged> staged((size_t)W);
-        std::vector<int> rcs((size_t)W, VRT_OK);
-        std::vector<std::string> errs((size_t)W);
-        auto work = [&](int d) {
-            Member &me = mm->m[(size_t)d];
-            const LambdaMember &l = s->lm[(size_t)d];
+        for (int d = 0; d < W; d++) staged[(size_t)d].device = mm->m[(size_t)d].device;
+        rc = on_members(mm->m, kLockPlan, every_member, [&](int d, Member &me) {
+            const LineBlock &b = s->lm[(size_t)d].blk;
             Staged &sg = staged[(size_t)d];
-            sg.device = me.device;
-            const int64_t nb = l.l1 - l.l0;
-            if (hipSetDevice(me.device) != hipSuccess) { rcs[(size_t)d] = VRT_ENODEVICE; errs[(size_t)d] = "hipSetDevice"; return; }
             hipStream_t st = me.stream;
-            vrt_plan *p = me.plan_all.get();
-            std::lock_guard<std::mutex> plock(p->mu);
             int rc = VRT_OK;
-            if (S && nb > 0) rc = l.sj.stage(S, s->nlam, l.l0, sg.S, st);      // this block's columns
+            if (S && b.nb() > 0) rc = b.sj.stage(S, s->nlam, b.l0, sg.S, st);            // this block's columns
             if (!rc && populations) rc = upload(sg.pops, populations, 3 * n, st);       // every device holds a full copy
             if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(VRT_ENODEVICE, "uploading the state failed");
-            if (rc) { rcs[(size_t)d] = rc; errs[(size_t)d] = vrt_last_error(); }
-        };
-        const bool ok = run_workers(W, work);
-        for (int d = 0; d < W; d++)
-            if (!ok || rcs[(size_t)d]) {
-                const int rc = ok ? rcs[(size_t)d] : VRT_ENOMEM;
-                return fail(rc, ok ? "device " + std::to_string(mm->m[(size_t)d].device) + ": " + errs[(size_t)d] : "out of host memory");
-            }
+            return rc;
+        });
+        if (rc) return rc;
         for (int d = 0; d < W; d++) {
             LambdaMember &l = s->lm[(size_t)d];
             Staged &sg = staged[(size_t)d];
-            if (S && l.l1 > l.l0) l.sj.adopt(sg.S);
+            if (S && l.blk.nb() > 0) l.blk.sj.adopt(sg.S);
             if (populations) std::swap(l.d_pops, sg.pops);
             l.ng.have = 0;                                   // iterates of another state are no history of this one
         }

@@ -1,6 +1,6 @@
 // The source function S and the mean intensity J of a device-resident Λ-iteration session on a vrt_plan: vrt_lambda
-// (vrt_lambda.cpp), vrt_continuum (vrt_continuum.hip) and every member of vrt_multi_lambda (vrt_multi.cpp) keep theirs in
-// a SourceStore.  The storage form is chosen once, at create, and is the store's business from then on:
+// (vrt_lambda.cpp) and every member of vrt_multi_lambda (vrt_multi.cpp) -- inside their LineBlock, vrt_line_block.h -- and
+// vrt_continuum (vrt_continuum.hip) keep theirs in a SourceStore.  The storage form is chosen once, at create, and is the store's business from then on:
 //   kRows       the caller's layout, (n, nlam) rows of doubles: S_new, S_old and J (VRT_LAMBDA_NATIVE=0, or a plan without
 //               sweep-order planes: two layout changes per sweep)
 //   kPlanes     sweep order, doubles: one plane set ([pairs][n][2], vrt_plan_native_plane_count) of S and of J per
