@@ -99,6 +99,41 @@ int vrt_tessellate(int64_t n, const double *pos_zxy, const double bounds[6], int
 /* writes such a matrix as the voro++ "%i %n" text file read_cell parses (one line per cell) */
 int vrt_write_neighbours_file(const char *path, int64_t n, const int64_t *nbr, int64_t D1);
 
+/* ---- the same tessellation on the device (csrc/vrt_tessellate.hip): bounds check, search grid, one cell per wave and
+ * the rows are built on `device`; vrt_tessellate's matrix for sites in general position, element for element.
+ * THE ROW, exactly (both the host and the device entries): the walls first, -5 before -6; then the neighbours in
+ * ascending (s, d2, j) of the periodic image of site j that made the surviving face -- s the Chebyshev distance, in
+ * cells of the search grid, between the image's grid cell and the site's (the shell vrt_tessellate found it in),
+ * d2 = dx*dx + dy*dy + dz*dz of (x_j + shift_x - x_i, y_j + shift_y - y_i, z_j - z_i), j the site id.  Left out: the
+ * faces of the periodic start box, the site's own images, faces of area <= 1e-14 Lx Ly, and a second image of a
+ * neighbour already listed.  Column 0 holds the count, the entries beyond it are zero.
+ *   A cell that does not fit the kernel's fixed capacities (64 planes, 128 vertices at a time), or whose vertex list
+ *   stops being a closed surface (exactly degenerate input: lattices), is recomputed by vrt_tessellate's host code, that
+ *   site only; *host_sites (may be NULL) receives how many were.  On exactly degenerate input the listed slivers depend on
+ *   rounding and may differ between the entries.
+ *   n >= 1 (a single site has the row 2, -5, -6); a site outside the closed box is VRT_EINVAL naming the lowest such
+ *   site, a row of more than D1 - 1 entries VRT_EGRID, both with vrt_tessellate's messages.  Every argument is checked
+ *   before the device is touched.  Both entries are synchronous.
+ * vrt_tessellate_gpu: host arrays; a refused or failed call leaves nbr as it was.
+ * vrt_tessellate_dev: d_pos_zxy (n, 3) and d_nbr (n, D1) are device pointers on `device` (vrt_sample_sites_dev's output
+ *   goes in directly); the kernels run on `stream`, which is synchronised; the positions are downloaded only if a site
+ *   has to be recomputed on the host.  After a failed call d_nbr is undefined. */
+int vrt_tessellate_gpu(int device, int64_t n, const double *pos_zxy, const double bounds[6], int64_t D1,
+                       int64_t *nbr, int64_t *max_count, int64_t *host_sites);
+int vrt_tessellate_dev(int device, int64_t n, const double *d_pos_zxy, const double bounds[6], int64_t D1,
+                       int64_t *d_nbr, int64_t *max_count, int64_t *host_sites, void *stream);
+/* event times of this process's last device tessellation (tools/tessellate_probe.py): sites, then milliseconds of the
+ * grid build (bounds check included), the cell kernel, and the row assembly with any host recomputation; any of the four
+ * may be NULL, all four is VRT_EINVAL */
+int vrt_tessellate_last_phases(int64_t *n, double *grid_ms, double *cells_ms, double *rows_ms);
+/* planes a cell holds at once in this build of the device tessellation (64; the tests' variant library lowers it) */
+int64_t vrt_tessellate_capacity(void);
+/* vrt_tessellate's cells for the m listed sites only (1-based ids, any order, no repeats): their rows of nbr (n, D1) are
+ * written, the others left as they are; *max_count: the largest count among the listed.  Host code; what the device
+ * entries recompute a site with. */
+int vrt_tessellate_sites(int64_t n, const double *pos_zxy, const double bounds[6], int64_t D1, int64_t m,
+                         const int64_t *sites, int64_t *nbr, int64_t *max_count);
+
 /* introspection (parity tests; all values exactly as the reference's Julia fields, 1-based) */
 int64_t vrt_grid_n(const vrt_grid *g);
 int64_t vrt_grid_max_neighbours(const vrt_grid *g);             /* D = size(neighbours,2)-1   */

@@ -803,9 +803,12 @@ end
 # Reads the sites file the driver has just written (write_arrays, src/io.jl:16-20: "id\tx\ty\tz"),
 # tessellates with vrt_tessellate and writes the "%i %n" neighbours file read_cell parses, so the
 # driver's own `voro(...); read_cell(...)` sequence (compare_line.jl:100-103) runs unchanged.
+# device = nothing: the host code (vrt_tessellate); device = ordinal: the same matrix from the device tessellation
+# (vrt_tessellate_gpu; a site it cannot hold is recomputed by the host code) -- the keyword is unrun: Julia is not
+# installed where the library is built.
 function voro_inprocess(sites_file::String, neighbours_file::String,
                         x_min::Float64, x_max::Float64, y_min::Float64, y_max::Float64,
-                        z_min::Float64, z_max::Float64)
+                        z_min::Float64, z_max::Float64; device::Union{Nothing,Integer}=nothing)
     rows = [split(l) for l in eachline(sites_file) if !isempty(strip(l))]
     n = length(rows)
     pos = Matrix{Float64}(undef, 3, n)                      # (3, n) rows z, x, y
@@ -818,9 +821,15 @@ function voro_inprocess(sites_file::String, neighbours_file::String,
     nbr = zeros(Int64, n, D1)
     mx = Ref{Int64}(0)
     GC.@preserve pos bounds nbr begin
-        check(ccall((:vrt_tessellate, libvrt), Cint,
-                    (Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Int64}, Ref{Int64}),
-                    n, pos, bounds, D1, nbr, mx))
+        if device === nothing
+            check(ccall((:vrt_tessellate, libvrt), Cint,
+                        (Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Int64}, Ref{Int64}),
+                        n, pos, bounds, D1, nbr, mx))
+        else
+            check(ccall((:vrt_tessellate_gpu, libvrt), Cint,
+                        (Cint, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Int64}, Ref{Int64}, Ptr{Int64}),
+                        device, n, pos, bounds, D1, nbr, mx, C_NULL))
+        end
         check(ccall((:vrt_write_neighbours_file, libvrt), Cint, (Cstring, Int64, Ptr{Int64}, Int64),
                     neighbours_file, n, nbr, D1))
     end
@@ -939,8 +948,9 @@ VoronoiRT.Λ_regular(ϵ::AbstractFloat, maxiter::Integer, atmos::VoronoiRT.Atmos
 # path is ignored, the tessellation runs inside the library
 VoronoiRT.voro(voro_executable::String, sites_file::String, neighbours_file::String,
                x_min::Float64, x_max::Float64, y_min::Float64, y_max::Float64,
-               z_min::Float64, z_max::Float64) =
-    VoronoiRTHip.voro_inprocess(sites_file, neighbours_file, x_min, x_max, y_min, y_max, z_min, z_max)
+               z_min::Float64, z_max::Float64; device::Union{Nothing,Integer}=nothing) =
+    VoronoiRTHip.voro_inprocess(sites_file, neighbours_file, x_min, x_max, y_min, y_max, z_min, z_max; device=device)
+# (device = an ordinal: the tessellation on that device, vrt_tessellate_gpu; the keyword is unrun)
 # single solves (compare_searchlight.jl:113,129,434)
 VoronoiRT.Delaunay_upII(k::Vector{Float64}, S, I_0, α, sites::VoronoiRT.VoronoiSites, n_sweeps::Int) =
     VoronoiRTHip.solve(true, k, S, I_0, α, sites, n_sweeps)

@@ -6,7 +6,7 @@ sharding of the angle x wavelength loop (distributed.py).  Importing this packag
 load the shared library; the first call does, and fails loudly if it is missing.
 """
 from .api import (Delaunay_downII, Delaunay_upII, FormalPlan, J_lambda_voronoi, VoronoiSites,  # noqa: F401
-                  direction, quadrature_directions, read_cell, read_quadrature, voro, QUADRATURE_DIR,
+                  direction, quadrature_directions, read_cell, read_quadrature, voro, voro_dev, QUADRATURE_DIR,
                   short_characteristics_batch, short_characteristics_down, short_characteristics_up,
                   RegularSolver, LineCase, Lambda_voronoi, Lambda_voronoi_host, J_lambda_voronoi_line, MultiDevicePlan,
                   Lambda_regular, J_lambda_regular_line,
@@ -20,7 +20,7 @@ from .api import (Delaunay_downII, Delaunay_upII, FormalPlan, J_lambda_voronoi, 
 from ._lib import VrtError  # noqa: F401
 
 __all__ = ["Delaunay_upII", "Delaunay_downII", "FormalPlan", "J_lambda_voronoi", "VoronoiSites",
-           "direction", "quadrature_directions", "read_cell", "read_quadrature", "voro", "VrtError",
+           "direction", "quadrature_directions", "read_cell", "read_quadrature", "voro", "voro_dev", "VrtError",
            "QUADRATURE_DIR", "short_characteristics_up", "short_characteristics_down",
            "short_characteristics_batch", "RegularSolver", "LineCase", "Lambda_voronoi", "Lambda_voronoi_host",
            "J_lambda_voronoi_line", "MultiDevicePlan", "Lambda_regular", "J_lambda_regular_line", "nearest_sites", "Voronoi_to_Raster",

@@ -56,6 +56,11 @@ PROTOTYPES = {
                                                  ctypes.c_int, ctypes.POINTER(vp)]),
     "vrt_grid_destroy": (None, [vp]),
     "vrt_tessellate": (ctypes.c_int, [c_i64, p_dbl, p_dbl, c_i64, p_i64, p_i64]),
+    "vrt_tessellate_gpu": (ctypes.c_int, [ctypes.c_int, c_i64, p_dbl, p_dbl, c_i64, p_i64, p_i64, p_i64]),
+    "vrt_tessellate_dev": (ctypes.c_int, [ctypes.c_int, c_i64, vp, p_dbl, c_i64, vp, p_i64, p_i64, vp]),
+    "vrt_tessellate_last_phases": (ctypes.c_int, [p_i64, p_dbl, p_dbl, p_dbl]),
+    "vrt_tessellate_capacity": (c_i64, []),
+    "vrt_tessellate_sites": (ctypes.c_int, [c_i64, p_dbl, p_dbl, c_i64, c_i64, p_i64, p_i64, p_i64]),
     "vrt_write_neighbours_file": (ctypes.c_int, [ctypes.c_char_p, c_i64, p_i64, c_i64]),
     "vrt_grid_n": (c_i64, [vp]),
     "vrt_grid_max_neighbours": (c_i64, [vp]),

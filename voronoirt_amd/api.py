@@ -170,22 +170,58 @@ class VoronoiSites:
             pass
 
 
-def voro(positions, bounds, neighbours_file: str | None = None, max_guess: int = 70) -> np.ndarray:
+def _device_ordinal(device) -> int:
+    """A device ordinal given as an int (bool and everything else: ValueError), checked before the library is loaded."""
+    if isinstance(device, bool) or not isinstance(device, (int, np.integer)):
+        raise ValueError(f"device must be None (host) or a device ordinal, not {device!r}")
+    return int(device)
+
+
+def voro(positions, bounds, neighbours_file: str | None = None, max_guess: int = 70, device=None) -> np.ndarray:
     """The reference's `voro` step (src/functions.jl:13-23: run the voro++ wrapper on the sites file)
     in-process: Voronoi neighbours of `positions` (n, 3) [z, x, y] in `bounds` = (z_min, z_max,
     x_min, x_max, y_min, y_max), periodic in x and y, walls -5 / -6 in z.  Returns the (D+1, n)
     matrix `read_cell` builds; with `neighbours_file` also writes the voro++ "%i %n" text file.
-    Host code (no GPU needed)."""
+    device=None: host code (no GPU needed).  device=<ordinal>: the same matrix from the device
+    tessellation (`vrt_tessellate_gpu`; sites it cannot hold are recomputed by the host code)."""
+    dev = None if device is None else _device_ordinal(device)
     L = _lib.load()
     pos = _f64(positions)
     n = pos.shape[0]
     b = np.array([float(v) for v in bounds], dtype=np.float64)
     M = np.zeros((max_guess + 1, n), dtype=np.int64)
     mx = ctypes.c_int64()
-    check(L.vrt_tessellate(n, _d(pos), _d(b), max_guess + 1, _i(M), ctypes.byref(mx)))
+    if dev is None:
+        check(L.vrt_tessellate(n, _d(pos), _d(b), max_guess + 1, _i(M), ctypes.byref(mx)))
+    else:
+        check(L.vrt_tessellate_gpu(dev, n, _d(pos), _d(b), max_guess + 1, _i(M), ctypes.byref(mx), None))
     if neighbours_file is not None:
         check(L.vrt_write_neighbours_file(neighbours_file.encode(), n, _i(M), max_guess + 1))
     return np.ascontiguousarray(M[: mx.value + 1])
+
+
+def voro_dev(pos_tensor, bounds, max_guess: int = 70):
+    """`voro` on positions that are on the device already (`vrt_tessellate_dev`): pos_tensor is a contiguous float64
+    torch tensor (n, 3) [z, x, y] on a GPU, e.g. what rejection_sampling_dev filled.  Returns (M, host_sites): M the
+    (max_guess + 1, n) int64 matrix on that device (row 0 the counts, zeros beyond a site's count), host_sites the
+    sites the host code had to recompute.  Runs on torch's current stream of that device and synchronises it."""
+    import torch
+
+    if not isinstance(pos_tensor, torch.Tensor) or pos_tensor.dtype != torch.float64:
+        raise ValueError("pos_tensor must be a float64 torch tensor")
+    if pos_tensor.dim() != 2 or pos_tensor.shape[1] != 3 or not pos_tensor.is_contiguous():
+        raise ValueError("pos_tensor must be contiguous with shape (n, 3)")
+    if pos_tensor.device.type != "cuda":
+        raise ValueError("pos_tensor must be on a GPU")
+    L = _lib.load()
+    dev = pos_tensor.device
+    n = pos_tensor.shape[0]
+    b = np.array([float(v) for v in bounds], dtype=np.float64)
+    M = torch.empty((max_guess + 1, n), dtype=torch.int64, device=dev)
+    mx, hs = ctypes.c_int64(), ctypes.c_int64()
+    check(L.vrt_tessellate_dev(dev.index or 0, n, pos_tensor.data_ptr(), _d(b), max_guess + 1, M.data_ptr(), ctypes.byref(mx),
+                               ctypes.byref(hs), torch.cuda.current_stream(dev).cuda_stream or None))
+    return M, hs.value
 
 
 def read_cell(fname: str, n_sites: int, positions, bounds, device: int = 0) -> VoronoiSites:

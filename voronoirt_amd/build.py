@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvrt_hip.so")
-SOURCES = ["vrt_api.cpp", "vrt_grid.cpp", "vrt_schedule.cpp", "vrt_patch.cpp", "vrt_lambda.cpp", "vrt_multi.cpp", "vrt_tessellate.cpp", "vrt_kernels.hip", "vrt_tables.hip", "vrt_layers.hip", "vrt_patch.hip", "vrt_regular.hip", "vrt_regular_lambda.hip", "vrt_physics.hip", "vrt_raster.hip", "vrt_synth.hip", "vrt_accel.hip", "vrt_continuum.hip", "vrt_line_ali.hip"]
+SOURCES = ["vrt_api.cpp", "vrt_grid.cpp", "vrt_schedule.cpp", "vrt_patch.cpp", "vrt_lambda.cpp", "vrt_multi.cpp", "vrt_tessellate.cpp", "vrt_tessellate.hip", "vrt_kernels.hip", "vrt_tables.hip", "vrt_layers.hip", "vrt_patch.hip", "vrt_regular.hip", "vrt_regular_lambda.hip", "vrt_physics.hip", "vrt_raster.hip", "vrt_synth.hip", "vrt_accel.hip", "vrt_continuum.hip", "vrt_line_ali.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("vrt_internal.h", "vrt_source_store.h", "vrt_raster_store.h", "vrt_line_case.h", "vrt_line_block.h", "vrt_multi_members.h", "vrt_device.h", "vrt_weights.h", "vrt_regular.h", "vrt_voigt.h", "vrt_layout_kernels.h", "vrt_tile_kernels.h", "vrt_step_kernels.h")] + [os.path.join(ROOT, "include", h) for h in ("voronoirt.h", "voronoirt_multi_accel.h")]
 
 
@@ -90,6 +90,24 @@ def build_probe(force: bool = False, verbose: bool = False) -> str:
     if not force and os.path.exists(PROBE_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(PROBE_LIB) for d in deps):
         return PROBE_LIB
     return _build(PROBE_LIB, [], verbose, sources=[PROBE_SRC])
+
+
+TESS_SRC = os.path.join(CSRC, "vrt_tessellate.hip")
+TESS_VARIANT_LIB = os.path.join(HERE, "libvrt_tess_faces16.so")
+
+
+def build_tess_variant(force: bool = False) -> str:
+    """Test infrastructure only: csrc/vrt_tessellate.hip with the face capacity lowered to 16 (-DVRT_TESS_FACES=16), so that
+    tests/test_tessellate_device.py sees sites fall back to the host code.  Built by tools/build_variant.sh into
+    voronoirt_amd/libvrt_tess_faces16.so, which links the libvrt_hip.so beside it for everything else; the package
+    never loads it."""
+    deps = [TESS_SRC, LIB] + HEADERS
+    if not force and os.path.exists(TESS_VARIANT_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(TESS_VARIANT_LIB) for d in deps):
+        return TESS_VARIANT_LIB
+    env = dict(os.environ, VRT_VARIANT_UNITS="vrt_tessellate.hip", HIPCC=_hipcc())
+    subprocess.check_call(["bash", os.path.join(ROOT, "tools", "build_variant.sh"), os.path.basename(TESS_VARIANT_LIB),
+                           "-DVRT_TESS_FACES=16"], env=env)
+    return TESS_VARIANT_LIB
 
 
 if __name__ == "__main__":

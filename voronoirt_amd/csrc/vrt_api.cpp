@@ -840,9 +840,28 @@ int vrt_tessellate(int64_t n, const double *pos_zxy, const double bounds[6], int
     if (n < 2 || n >= ((int64_t)1 << 30)) return fail(VRT_EINVAL, "n must be in [2, 2^30)");
     if (D1 < 5) return fail(VRT_EINVAL, "D1 must leave room for at least four neighbours");
     return guarded([&] {
-        unsigned hw = std::thread::hardware_concurrency();
-        const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(hw ? hw : 4), 64, n / 256 + 1}));
-        return tessellate_host(n, pos_zxy, bounds, D1, nbr, max_count, nthr);
+        return tessellate_host(n, pos_zxy, bounds, D1, nbr, max_count, tessellate_threads(n));
+    });
+}
+
+int vrt_tessellate_sites(int64_t n, const double *pos_zxy, const double bounds[6], int64_t D1, int64_t m,
+                         const int64_t *sites, int64_t *nbr, int64_t *max_count)
+{
+    if (!pos_zxy || !bounds || !nbr || !sites) return fail(VRT_EINVAL, "NULL argument");
+    if (n < 1 || n >= ((int64_t)1 << 30)) return fail(VRT_EINVAL, "n must be in [1, 2^30)");
+    if (D1 < 5) return fail(VRT_EINVAL, "D1 must leave room for at least four neighbours");
+    if (m < 0 || m > n) return fail(VRT_EINVAL, "m must be in [0, n]");
+    return guarded([&] {
+        std::vector<int64_t> ids((size_t)m), rows((size_t)m * (size_t)D1);
+        for (int64_t k = 0; k < m; k++) {
+            if (sites[k] < 1 || sites[k] > n) return fail(VRT_EINVAL, "site id out of range");
+            ids[(size_t)k] = sites[k] - 1;
+        }
+        int rc = tessellate_host_sites(n, pos_zxy, bounds, D1, m, ids.data(), rows.data(), max_count, tessellate_threads(m));
+        if (rc) return rc;
+        for (int64_t k = 0; k < m; k++)
+            for (int64_t q = 0; q < D1; q++) nbr[ids[(size_t)k] + n * q] = rows[(size_t)k + (size_t)m * (size_t)q];
+        return (int)VRT_OK;
     });
 }
 

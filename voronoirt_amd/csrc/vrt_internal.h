@@ -592,6 +592,16 @@ int build_grid_host(vrt_grid *g, int64_t n, const double *pos, const int64_t *nb
 // ---- in-process tessellation (vrt_tessellate.cpp) ------------------------------------------------
 int tessellate_host(int64_t n, const double *pos, const double bounds[6], int64_t D1, int64_t *nbr_out,
                     int64_t *max_count, int nthreads);
+// host threads for `count` cells: the hardware's, at most 64, at least one per 256 cells
+inline int tessellate_threads(int64_t count)
+{
+    const unsigned hw = std::thread::hardware_concurrency();
+    return (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(hw ? hw : 4), 64, count / 256 + 1}));
+}
+// the same cells for the m listed sites only (0-based ids, any order): rows_out (m, D1) column-major, row k of sites[k];
+// what the device tessellation (vrt_tessellate.hip) recomputes its flagged sites with
+int tessellate_host_sites(int64_t n, const double *pos, const double bounds[6], int64_t D1, int64_t m, const int64_t *sites,
+                          int64_t *rows_out, int64_t *max_count, int nthreads);
 
 // ---- schedule (vrt_schedule.cpp) -------------------------------------------------------------
 struct AngleSchedule {

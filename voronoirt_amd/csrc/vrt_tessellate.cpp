@@ -146,6 +146,149 @@ struct SearchGrid {
     }
 };
 
+// The search grid and the constants of one tessellation; site() builds one cell and writes its row.
+struct HostTess {
+    int64_t n = 0, D1 = 0;
+    const double *pos = nullptr;
+    double z_min = 0, z_max = 0, x_min = 0, y_min = 0, Lx = 0, Ly = 0, Lz = 0, eps = 0;
+    SearchGrid G;
+
+    int build(int64_t n_, const double *pos_, const double bounds[6], int64_t D1_)
+    {
+        n = n_; pos = pos_; D1 = D1_;
+        z_min = bounds[0]; z_max = bounds[1]; x_min = bounds[2]; y_min = bounds[4];
+        const double x_max = bounds[3], y_max = bounds[5];
+        Lz = z_max - z_min; Lx = x_max - x_min; Ly = y_max - y_min;
+        if (!(Lz > 0 && Lx > 0 && Ly > 0)) return fail(VRT_EINVAL, "empty box");
+        // search grid with ~4 sites per cell
+        const double vol = Lx * Ly * Lz, h = std::cbrt(vol * 4.0 / (double)std::max<int64_t>(n, 1));
+        G.gx = std::max(1, (int)(Lx / h)); G.gy = std::max(1, (int)(Ly / h)); G.gz = std::max(1, (int)(Lz / h));
+        G.x0 = x_min; G.y0 = y_min; G.z0 = z_min; G.Lx = Lx; G.Ly = Ly; G.Lz = Lz;
+        G.cx = Lx / G.gx; G.cy = Ly / G.gy; G.cz = Lz / G.gz;
+        const size_t ncell = (size_t)G.gx * G.gy * G.gz;
+        G.start.assign(ncell + 1, 0);
+        std::vector<int32_t> cell_of_site((size_t)n);
+        for (int64_t i = 0; i < n; i++) {
+            const double z = pos[3 * i], x = pos[3 * i + 1], y = pos[3 * i + 2];
+            if (!(z >= z_min && z <= z_max && x >= x_min && x <= x_max && y >= y_min && y <= y_max))
+                return fail(VRT_EINVAL, "site " + std::to_string(i + 1) + " lies outside the box");
+            const int c = (G.cell_of(x, x_min, G.cx, G.gx) * G.gy + G.cell_of(y, y_min, G.cy, G.gy)) * G.gz +
+                          G.cell_of(z, z_min, G.cz, G.gz);
+            cell_of_site[(size_t)i] = c;
+            G.start[(size_t)c + 1]++;
+        }
+        for (size_t c = 0; c < ncell; c++) G.start[c + 1] += G.start[c];
+        G.item.resize((size_t)n);
+        {
+            std::vector<int32_t> cur(G.start.begin(), G.start.end() - 1);
+            for (int64_t i = 0; i < n; i++) G.item[(size_t)cur[(size_t)cell_of_site[(size_t)i]]++] = (int32_t)i;
+        }
+        eps = 1e-11 * std::max({Lx, Ly, Lz});
+        return VRT_OK;
+    }
+
+    using Cand = std::vector<std::pair<double, std::pair<int32_t, V3>>>;
+
+    // The cell of site i; its row goes to row[0] (count), row[stride], row[2 stride], ... (zero-filled by the caller).
+    // Returns the count; *overflow: the row does not fit D1 - 1 entries.
+    int64_t site(int64_t i, Cell &cell, Cand &cand, int64_t *row, size_t stride, bool *overflow) const
+    {
+        const double zi = pos[3 * i], xi = pos[3 * i + 1], yi = pos[3 * i + 2];
+        // periodic in x, y: a cell cannot reach beyond half a period; walls in z
+        cell.box(0.5 * Lx, 0.5 * Ly, z_min - zi, z_max - zi);
+        const int ix = G.cell_of(xi, x_min, G.cx, G.gx), iy = G.cell_of(yi, y_min, G.cy, G.gy),
+                  iz = G.cell_of(zi, z_min, G.cz, G.gz);
+        // shells of grid cells at Chebyshev distance s; stop when the nearest point of the next
+        // shell is farther than twice the farthest vertex
+        const int smax = std::max({G.gx, G.gy, G.gz});
+        for (int s = 0; s <= smax; s++) {
+            if (s > 0) {
+                const double reach = (s - 1) * std::min({G.cx, G.cy, G.cz});   // lower bound of the distance to shell s
+                if (reach * reach > 4.0 * cell.r2max) break;
+            }
+            cand.clear();
+            for (int dx = -s; dx <= s; dx++) {
+                for (int dy = -s; dy <= s; dy++) {
+                    for (int dz = -s; dz <= s; dz++) {
+                        if (std::max({std::abs(dx), std::abs(dy), std::abs(dz)}) != s) continue;
+                        const int cz = iz + dz;
+                        if (cz < 0 || cz >= G.gz) continue;
+                        int cxw = ix + dx, cyw = iy + dy;
+                        double sx = 0, sy = 0;                     // shift of the periodic image
+                        while (cxw < 0) { cxw += G.gx; sx -= Lx; }
+                        while (cxw >= G.gx) { cxw -= G.gx; sx += Lx; }
+                        while (cyw < 0) { cyw += G.gy; sy -= Ly; }
+                        while (cyw >= G.gy) { cyw -= G.gy; sy += Ly; }
+                        const size_t c = ((size_t)cxw * G.gy + cyw) * G.gz + cz;
+                        for (int32_t e = G.start[c]; e < G.start[c + 1]; e++) {
+                            const int32_t j = G.item[(size_t)e];
+                            if (j == i && sx == 0 && sy == 0) continue;
+                            const V3 dlt = {pos[3 * j + 1] + sx - xi, pos[3 * j + 2] + sy - yi, pos[3 * j] - zi};
+                            cand.push_back({dot(dlt, dlt), {j, dlt}});
+                        }
+                    }
+                }
+            }
+            std::sort(cand.begin(), cand.end(), [](const auto &a, const auto &b) {
+                return a.first < b.first || (a.first == b.first && a.second.first < b.second.first);
+            });
+            for (const auto &cd : cand) {
+                if (cd.first > 4.0 * cell.r2max) break;           // cannot cut: bisector beyond every vertex
+                cell.cut(cd.second.second, 0.5 * cd.first, (int64_t)cd.second.first + 1, eps);
+            }
+        }
+        // the row: walls first, then neighbours by increasing distance (= order of the cuts)
+        int64_t cnt = 0;
+        const double amin = 1e-14 * (Lx * Ly);
+        // A face of the start box that survives (id 0), or a cut by one of the site's own periodic
+        // images, is a face towards the site ITSELF across the period (sparse sites in a small
+        // box): not a neighbour, left out of the row.
+        for (int pass = 0; pass < 2; pass++)
+            for (const Face &f : cell.faces) {
+                if (f.id == 0 || f.id == i + 1) continue;
+                if ((pass == 0) != (f.id < 0)) continue;
+                if (Cell::area(f) <= amin) continue;
+                bool dup = false;                                  // two images of one neighbour: keep one entry
+                for (int64_t q = 1; q <= cnt; q++)
+                    if (row[stride * (size_t)q] == f.id) dup = true;
+                if (dup) continue;
+                if (cnt + 1 >= D1) { *overflow = true; break; }
+                cnt++;
+                row[stride * (size_t)cnt] = f.id;
+            }
+        row[0] = cnt;
+        return cnt;
+    }
+
+    // Sites site_of(k), k = 0 .. m-1, on nthreads host threads; the row of the k-th goes to row_of(k) with `stride`.
+    template <typename SiteOf, typename RowOf>
+    int run(int64_t m, SiteOf site_of, RowOf row_of, size_t stride, int64_t *max_count, int nthreads) const
+    {
+        std::vector<int64_t> worst((size_t)nthreads, 0);
+        std::vector<int64_t> bad((size_t)nthreads, -1);
+        auto work_body = [&](int t) {
+            Cell cell;
+            Cand cand;
+            for (int64_t k = t; k < m; k += nthreads) {
+                const int64_t i = site_of(k);
+                bool overflow = false;
+                const int64_t cnt = site(i, cell, cand, row_of(k), stride, &overflow);
+                worst[(size_t)t] = std::max(worst[(size_t)t], cnt);
+                if (overflow && bad[(size_t)t] < 0) bad[(size_t)t] = i;
+            }
+        };
+        if (!run_workers(nthreads, work_body)) return fail(VRT_ENOMEM, "out of host memory in the tessellation");
+        int64_t mx = 0;
+        for (int t = 0; t < nthreads; t++) {
+            mx = std::max(mx, worst[(size_t)t]);
+            if (bad[(size_t)t] >= 0)
+                return fail(VRT_EGRID, "site " + std::to_string(bad[(size_t)t] + 1) + " has more neighbours than the matrix holds");
+        }
+        if (max_count) *max_count = mx;
+        return VRT_OK;
+    }
+};
+
 }  // namespace
 
 // nbr_out: (n, D1) column-major like read_cell's matrix (column 0 = count), zero-filled here;
@@ -153,120 +296,22 @@ struct SearchGrid {
 int tessellate_host(int64_t n, const double *pos, const double bounds[6], int64_t D1, int64_t *nbr_out,
                     int64_t *max_count, int nthreads)
 {
-    const double z_min = bounds[0], z_max = bounds[1], x_min = bounds[2], x_max = bounds[3], y_min = bounds[4],
-                 y_max = bounds[5];
-    const double Lz = z_max - z_min, Lx = x_max - x_min, Ly = y_max - y_min;
-    if (!(Lz > 0 && Lx > 0 && Ly > 0)) return fail(VRT_EINVAL, "empty box");
-    // search grid with ~4 sites per cell
-    SearchGrid G;
-    const double vol = Lx * Ly * Lz, h = std::cbrt(vol * 4.0 / (double)std::max<int64_t>(n, 1));
-    G.gx = std::max(1, (int)(Lx / h)); G.gy = std::max(1, (int)(Ly / h)); G.gz = std::max(1, (int)(Lz / h));
-    G.x0 = x_min; G.y0 = y_min; G.z0 = z_min; G.Lx = Lx; G.Ly = Ly; G.Lz = Lz;
-    G.cx = Lx / G.gx; G.cy = Ly / G.gy; G.cz = Lz / G.gz;
-    const size_t ncell = (size_t)G.gx * G.gy * G.gz;
-    G.start.assign(ncell + 1, 0);
-    std::vector<int32_t> cell_of_site((size_t)n);
-    for (int64_t i = 0; i < n; i++) {
-        const double z = pos[3 * i], x = pos[3 * i + 1], y = pos[3 * i + 2];
-        if (!(z >= z_min && z <= z_max && x >= x_min && x <= x_max && y >= y_min && y <= y_max))
-            return fail(VRT_EINVAL, "site " + std::to_string(i + 1) + " lies outside the box");
-        const int c = (G.cell_of(x, x_min, G.cx, G.gx) * G.gy + G.cell_of(y, y_min, G.cy, G.gy)) * G.gz +
-                      G.cell_of(z, z_min, G.cz, G.gz);
-        cell_of_site[(size_t)i] = c;
-        G.start[(size_t)c + 1]++;
-    }
-    for (size_t c = 0; c < ncell; c++) G.start[c + 1] += G.start[c];
-    G.item.resize((size_t)n);
-    {
-        std::vector<int32_t> cur(G.start.begin(), G.start.end() - 1);
-        for (int64_t i = 0; i < n; i++) G.item[(size_t)cur[(size_t)cell_of_site[(size_t)i]]++] = (int32_t)i;
-    }
+    HostTess T;
+    if (int rc = T.build(n, pos, bounds, D1)) return rc;
     std::fill(nbr_out, nbr_out + (size_t)n * (size_t)D1, (int64_t)0);
-    const double eps = 1e-11 * std::max({Lx, Ly, Lz});
-    std::vector<int64_t> worst((size_t)nthreads, 0);
-    std::vector<int64_t> bad((size_t)nthreads, -1);
-    auto work_body = [&](int t) {
-        Cell cell;
-        std::vector<std::pair<double, std::pair<int32_t, V3>>> cand;
-        for (int64_t i = t; i < n; i += nthreads) {
-            const double zi = pos[3 * i], xi = pos[3 * i + 1], yi = pos[3 * i + 2];
-            // periodic in x, y: a cell cannot reach beyond half a period; walls in z
-            cell.box(0.5 * Lx, 0.5 * Ly, z_min - zi, z_max - zi);
-            const int ix = G.cell_of(xi, x_min, G.cx, G.gx), iy = G.cell_of(yi, y_min, G.cy, G.gy),
-                      iz = G.cell_of(zi, z_min, G.cz, G.gz);
-            // shells of grid cells at Chebyshev distance s; stop when the nearest point of the next
-            // shell is farther than twice the farthest vertex
-            const int smax = std::max({G.gx, G.gy, G.gz});
-            for (int s = 0; s <= smax; s++) {
-                if (s > 0) {
-                    const double reach = (s - 1) * std::min({G.cx, G.cy, G.cz});   // lower bound of the distance to shell s
-                    if (reach * reach > 4.0 * cell.r2max) break;
-                }
-                cand.clear();
-                for (int dx = -s; dx <= s; dx++) {
-                    for (int dy = -s; dy <= s; dy++) {
-                        for (int dz = -s; dz <= s; dz++) {
-                            if (std::max({std::abs(dx), std::abs(dy), std::abs(dz)}) != s) continue;
-                            const int cz = iz + dz;
-                            if (cz < 0 || cz >= G.gz) continue;
-                            int cxw = ix + dx, cyw = iy + dy;
-                            double sx = 0, sy = 0;                     // shift of the periodic image
-                            while (cxw < 0) { cxw += G.gx; sx -= Lx; }
-                            while (cxw >= G.gx) { cxw -= G.gx; sx += Lx; }
-                            while (cyw < 0) { cyw += G.gy; sy -= Ly; }
-                            while (cyw >= G.gy) { cyw -= G.gy; sy += Ly; }
-                            const size_t c = ((size_t)cxw * G.gy + cyw) * G.gz + cz;
-                            for (int32_t e = G.start[c]; e < G.start[c + 1]; e++) {
-                                const int32_t j = G.item[(size_t)e];
-                                if (j == i && sx == 0 && sy == 0) continue;
-                                const V3 dlt = {pos[3 * j + 1] + sx - xi, pos[3 * j + 2] + sy - yi, pos[3 * j] - zi};
-                                cand.push_back({dot(dlt, dlt), {j, dlt}});
-                            }
-                        }
-                    }
-                }
-                std::sort(cand.begin(), cand.end(), [](const auto &a, const auto &b) {
-                    return a.first < b.first || (a.first == b.first && a.second.first < b.second.first);
-                });
-                for (const auto &cd : cand) {
-                    if (cd.first > 4.0 * cell.r2max) break;           // cannot cut: bisector beyond every vertex
-                    cell.cut(cd.second.second, 0.5 * cd.first, (int64_t)cd.second.first + 1, eps);
-                }
-            }
-            // the row: walls first, then neighbours by increasing distance (= order of the cuts)
-            int64_t cnt = 0;
-            const double amin = 1e-14 * (Lx * Ly);
-            // A face of the start box that survives (id 0), or a cut by one of the site's own periodic
-            // images, is a face towards the site ITSELF across the period (sparse sites in a small
-            // box): not a neighbour, left out of the row.
-            bool overflow = false;
-            for (int pass = 0; pass < 2; pass++)
-                for (const Face &f : cell.faces) {
-                    if (f.id == 0 || f.id == i + 1) continue;
-                    if ((pass == 0) != (f.id < 0)) continue;
-                    if (Cell::area(f) <= amin) continue;
-                    bool dup = false;                                  // two images of one neighbour: keep one entry
-                    for (int64_t q = 1; q <= cnt; q++)
-                        if (nbr_out[(size_t)i + (size_t)n * (size_t)q] == f.id) dup = true;
-                    if (dup) continue;
-                    if (cnt + 1 >= D1) { overflow = true; break; }
-                    cnt++;
-                    nbr_out[(size_t)i + (size_t)n * (size_t)cnt] = f.id;
-                }
-            nbr_out[(size_t)i] = cnt;
-            worst[(size_t)t] = std::max(worst[(size_t)t], cnt);
-            if (overflow && bad[(size_t)t] < 0) bad[(size_t)t] = i;
-        }
-    };
-    if (!run_workers(nthreads, work_body)) return fail(VRT_ENOMEM, "out of host memory in the tessellation");
-    int64_t mx = 0;
-    for (int t = 0; t < nthreads; t++) {
-        mx = std::max(mx, worst[(size_t)t]);
-        if (bad[(size_t)t] >= 0)
-            return fail(VRT_EGRID, "site " + std::to_string(bad[(size_t)t] + 1) + " has more neighbours than the matrix holds");
-    }
-    if (max_count) *max_count = mx;
-    return VRT_OK;
+    return T.run(n, [](int64_t k) { return k; }, [&](int64_t k) { return nbr_out + k; }, (size_t)n, max_count, nthreads);
+}
+
+// The same cells for the m listed sites only (0-based ids, any order, each < n): rows_out is (m, D1) column-major, row k
+// the row of sites[k]; *max_count the largest count among them.  What the device tessellation falls back to.
+int tessellate_host_sites(int64_t n, const double *pos, const double bounds[6], int64_t D1, int64_t m, const int64_t *sites,
+                          int64_t *rows_out, int64_t *max_count, int nthreads)
+{
+    HostTess T;
+    if (int rc = T.build(n, pos, bounds, D1)) return rc;
+    std::fill(rows_out, rows_out + (size_t)m * (size_t)D1, (int64_t)0);
+    return T.run(m, [&](int64_t k) { return sites[k]; }, [&](int64_t k) { return rows_out + k; }, (size_t)m, max_count,
+                 nthreads);
 }
 
 }  // namespace vrt
