@@ -13,32 +13,20 @@ import numpy as np
 
 import voronoirt_amd as vrt
 from oracle import oracle as orc
+from oracle import update_ref
 from oracle.f32_model import EXP_EPS, PATH_MODEL
+from oracle.update_ref import f32
 
 QUADRATURE = "ul7n12.dat"
 ALPHA_EPS = 1e-13               # the coarsest error of the device opacity the project quotes (EXP_EPS: of its exponential)
 
 
-def f32(a):
-    """the float rounding of a float64 array, as float64"""
-    return np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64)
-
-
 def update_model(J_up, J_down, B, S_old, eps, nlam=None):
     """numpy model of vrt_lambda_update_native_dev_f32 on caller-layout float32 arrays (n, nlam) (either J may be None):
-    (J, S_new as float32, the criterion's scalar).  Separate multiply and add, as the build's -ffp-contract=off."""
-    e = np.asarray(eps, dtype=np.float64)[:, None]
-    j = np.zeros(np.asarray(B).shape)
-    if J_up is not None:
-        j = np.asarray(J_up, dtype=np.float64)
-    if J_down is not None:
-        j = j + np.asarray(J_down, dtype=np.float64)
-    J = j.astype(np.float32)
-    S_new = ((1.0 - e) * J.astype(np.float64) + e * np.asarray(B, dtype=np.float64)).astype(np.float32)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        d = np.abs(1.0 - np.asarray(S_old, dtype=np.float64) / S_new.astype(np.float64))
-    scalar = float("nan") if np.isnan(d).any() else float(d.max())
-    return J, S_new, scalar
+    (J, S_new as float32, the criterion's scalar).  It is the "line_f32" kind of oracle/update_ref.py, which holds the
+    operations."""
+    u = update_ref.update_model("line_f32", J_up, B, eps, S_old, J_down=J_down, nlam=nlam)
+    return u.parts["J"].astype(np.float32), u.S_new.astype(np.float32), u.scalar
 
 
 def model_lambda_iteration(case, so, maxiter, exp_eps=0.0, alpha_eps=0.0):

@@ -5,7 +5,7 @@ oracle-driven ALI loop of tests/test_ali_host.py.
 
 Tolerances: Λ* against its numpy restatement 1e-12 relative (device arithmetic against a CPU restatement of the same
 formula: <= 24 terms of a few ulp each); the session against the oracle loop as tests/test_continuum.py (J and S 1e-9,
-the history rtol 1e-8); the standalone update against numpy 1e-14 relative (five operations of one rounding each)."""
+the history rtol 1e-8); the standalone update against oracle/update_ref.py bit for bit (the build is -ffp-contract=off)."""
 import ctypes
 
 import numpy as np
@@ -13,6 +13,7 @@ import pytest
 
 import voronoirt_amd as vrt
 from oracle import oracle as orc
+from oracle import update_ref
 from voronoirt_amd import _lib, api, synth
 from test_continuum_host import QUAD, bcc_case, oracle_J_voronoi, oracle_loop
 from test_continuum import _against_oracle
@@ -277,7 +278,9 @@ def test_gpu_ali_update_on_hand_made_arrays(bcc, nlam, ld):
 
     diff, cnt, S_new = run(B)
     ref = ((1 - eps) * (J - diag * S_old) + eps * B) / (1 - (1 - eps) * diag)
-    assert np.abs(S_new[:, :nlam] / ref[:, :nlam] - 1).max() <= 1e-14 and (S_new[:, nlam:] == -7.0).all()
+    model = update_ref.update_model("continuum_ali", J, B, eps, S_old, diag=diag, eps_thick=1e-4, nlam=nlam)
+    assert np.array_equal(S_new[:, :nlam], model.S_new[:, :nlam]) and np.array_equal(model.S_new[:, :nlam], ref[:, :nlam])
+    assert (S_new[:, nlam:] == -7.0).all()
     rel = np.abs(1 - S_old / S_new)[:, :nlam]                  # (the criterion of the S the device wrote: exact)
     assert cnt == int(thick.sum()) and 0 < cnt < n * nlam
     assert diff == rel[thick].max() and diff != rel.max()

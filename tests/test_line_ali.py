@@ -4,7 +4,7 @@ continuum operator's kernel (bit for bit, angle by angle), the numpy restatement
 of tests/test_line_ali_host.py.
 
 Tolerances: Λ* against vrt_plan_lambda_diagonal: equality of bits; against its numpy restatement the two-tier 1e-12 rule of
-tests/test_ali.py; the standalone updates against numpy 1e-14 relative as there (five operations of one rounding each);
+tests/test_ali.py; the standalone updates against oracle/update_ref.py bit for bit (the build is -ffp-contract=off);
 the session against the oracle loop as tests/test_physics.py has the plain session (J, S, populations 1e-9, the history
 rtol 1e-8); distances between converged runs: the δ / (1 - ρ) terms of the CPU oracle runs (BOUND_TERMS of
 tests/test_line_ali_host.py); iterate caps: the oracle's counts plus two."""
@@ -15,6 +15,7 @@ import pytest
 
 import voronoirt_amd as vrt
 from oracle import oracle as orc
+from oracle import update_ref
 from voronoirt_amd import _lib, api, synth
 from test_accel import _Session
 from test_ali_host import lambda_star_ref, oracle_table, updated_mask
@@ -192,7 +193,8 @@ def test_gpu_line_ali_updates_on_hand_made_arrays(grids, nlam):
 
     d, c, S_new = rows(B)
     assert c == 1 and S_new[at] == plain[at] and (S_new[:, nlam:] == -7.0).all()
-    assert np.abs(S_new[:, :nlam] / ref[:, :nlam] - 1).max() <= 1e-14
+    model = update_ref.update_model("line_ali", J, B, eps, S_old, diag=diag, nlam=nlam)
+    assert np.array_equal(S_new[:, :nlam], model.S_new[:, :nlam]) and np.array_equal(model.S_new[:, :nlam], ref[:, :nlam])
     assert d == np.abs(1 - S_old / S_new)[:, :nlam].max()      # (the criterion of the S the device wrote: exact)
     Bn = B.copy()
     Bn[5, 0] = np.nan
