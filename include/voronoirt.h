@@ -338,11 +338,25 @@ int vrt_plan_patch_layout(const vrt_plan *p, int64_t *out);
  * order (x first): role (0 patch, 1 reduction), XCD lane, work-list row, split, sibling, share in pair steps -- a
  * reduction block: 1, its index among the reduction blocks, zeros. */
 int vrt_patch_dispatch_map(int order, int nrow, int nsplit, int lg_siblings, int64_t nred, int steps, int64_t *dims, int32_t *blocks);
+/* which pair elements the blocks of a launch's patch grid reduce when the J reduction rides in them (option
+ * VRT_PATCH_REDUCE_RIDE; introspection for the tests only; host only): the patch grid of vrt_patch_dispatch_map(order, nrow,
+ * nsplit, lg_siblings, 0 reduction blocks), storage position ranges [lo[r], hi[r]) (r = 0, 1; an empty range: none) of a grid
+ * of n sites, npair wavelength pairs in pair blocks of 1 << lg_block, NT threads per block.  dims[4] = blocks of the patch
+ * grid, chunks (NT elements) of range 0, of range 1, and 1 where the launch rides -- 0: four chunks per block do not cover
+ * the ranges, the launch keeps its reduction rows, nothing else is written.  elems (or NULL) = for the blocks
+ * [first_block, first_block + nblocks) of the grid's linear order 4 x NT numbers each ([round][thread]): the index of the
+ * pair element in the plane set [npair][n], | 1 << 62 for range 1; -1: nothing. */
+int vrt_patch_ride_map(int order, int nrow, int nsplit, int lg_siblings, int npair, int lg_block, int NT, int64_t n, const int32_t *lo,
+                       const int32_t *hi, int64_t first_block, int64_t nblocks, int64_t *dims, int64_t *elems);
+/* the riding form in the last sweep of a plan (introspection for the tests only): out[0] = per-layer launches whose
+ * reduction rode in their patch blocks, out[1] = the most chunks a block of such a launch took (0: none rode) */
+int vrt_plan_patch_ride_stats(const vrt_plan *p, int64_t *out);
 /* timeline of the last sweep's per-layer patch launches (diagnostics build of the library with option VRT_PATCH_TIMELINE=1
  * only; VRT_EINVAL otherwise): waits for the device, then launches[12 per launch] = layer, stream group, gridDim.x,
  * gridDim.y, work-list rows, splits, log2 siblings, order, patch rows, reduction blocks, first block, pair steps of an
  * item; stamps[3 per block, linear grid order] = start, end (wall clock ticks), share in pair steps (| 1 << 32: a
- * reduction block); counts[3] = launches, blocks, wall clock rate in kHz */
+ * reduction block; a patch block that reduced a riding slice: bits 33-46 its elements, bits 48-63 the ticks from its start
+ * to its J store); counts[3] = launches, blocks, wall clock rate in kHz */
 int vrt_plan_patch_timeline(vrt_plan *p, int64_t cap_launches, int64_t cap_blocks, int64_t *launches, uint64_t *stamps, int64_t *counts);
 /* VRT_OK, or the give-up of a chained patch launch that has finished since the last check (VRT_ENODEVICE: the results of
  * that execute are invalid).  The entry points that synchronise themselves (vrt_plan_execute, vrt_plan_execute_line,
@@ -364,6 +378,8 @@ int vrt_plan_last_path(const vrt_plan *p);
  *   VRT_PATCH_ORDER = 0 | 1                    dispatch order of the workgroups of a per-layer patch launch: an item's
  *                                              workgroups side by side, or share-major -- every item's longest share of
  *                                              wavelength-pair steps first (default 1)
+ *   VRT_PATCH_REDUCE_RIDE = 0 | 1              the J reduction of a per-layer launch in reduction blocks of their own behind
+ *                                              its patch blocks (default 0), or inside the patch blocks' start-up (1)
  *   VRT_PATCH_K, VRT_PATCH_NT, VRT_PATCH_OWN  entries per thread, threads, owned sites per patch (creation only)
  *   VRT_PATCH_LEAN = 0 | 1                     the 64-register patch kernel, four workgroups per CU (default 1)
  *   VRT_PATCH_CHAIN = 0 | 1 | 2                every layer inside ONE launch, ordered by the data's own dependencies: never

@@ -11,8 +11,10 @@ LAST step into per-launch figures:
   last-ender   share of the block that ended last, whether it was a late one, and the longest share of the launch
   patch blocks when the patch blocks start (median, 90 %, last), how many of them late, how long a longest / shortest share runs
   fill         slot time used: sum of the blocks' durations over (--slots x the launch's duration)
+  riding       with the J reduction riding in the patch blocks (VRT_PATCH_REDUCE_RIDE=1): the blocks that took a slice, their
+               elements (chunks x threads), and when they stored J_dir, from their own start
 usage: VRT_LIB_PATH=voronoirt_amd/libvrt_hip_diag.so python tools/patch_timeline.py [--workload C4] [--nlam L] [--order 0|1]
-       [--split S] [--steps 3] [--slots 512] [--csv per_launch.csv]"""
+       [--split S] [--ride 0|1] [--steps 3] [--slots 512] [--csv per_launch.csv]"""
 import argparse
 import ctypes
 import os
@@ -35,6 +37,7 @@ def main():
     ap.add_argument("--nlam", type=int, default=0)
     ap.add_argument("--order", type=int, default=-1, help="VRT_PATCH_ORDER (-1: the library's default)")
     ap.add_argument("--split", type=int, default=0, help="VRT_PATCH_SPLIT (0: the split rule)")
+    ap.add_argument("--ride", type=int, default=-1, help="VRT_PATCH_REDUCE_RIDE (-1: the library's default)")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--slots", type=int, default=512, help="workgroup slots a launch is measured against (a stream's half of 1024)")
     ap.add_argument("--csv", default="")
@@ -54,6 +57,8 @@ def main():
         plan.set_option("VRT_PATCH_ORDER", args.order)
     if args.split > 0:
         plan.set_option("VRT_PATCH_SPLIT", args.split)
+    if args.ride >= 0:
+        plan.set_option("VRT_PATCH_REDUCE_RIDE", args.ride)
     # the fields of bench.py (synthetic stratified atmosphere, a line profile per angle)
     gen = torch.Generator(device=dev)
     gen.manual_seed(seed)
@@ -110,9 +115,11 @@ def main():
         layer, group, gx, gy, nrow, nsplit, lgs, order, prow, nred, first, steps = (int(v) for v in L)
         s = stamps[first:first + gx * gy]
         t0, t1, sh = s[:, 0].astype(np.int64), s[:, 1].astype(np.int64), s[:, 2]
-        is_red = (sh >> np.uint64(32)) != 0
+        is_red = ((sh >> np.uint64(32)) & np.uint64(1)) != 0
         share = (sh & np.uint64(0xFFFFFFFF)).astype(np.int64)
-        work = is_red | (share > 0)                    # blocks that did something (padding returns at once)
+        rode = ((sh >> np.uint64(33)) & np.uint64(0x3FFF)).astype(np.int64)      # elements of a riding slice (BlockStamp::rode)
+        rode_at = (sh >> np.uint64(48)).astype(np.int64)                         #   and the ticks from the block's start to its J store
+        work = is_red | (share > 0) | (rode > 0)       # blocks that did something (padding returns at once)
         if not work.any():
             continue
         begin = t0.min()
@@ -135,6 +142,10 @@ def main():
                          run_long=float(((t1 - t0)[patch & (share == share[patch].max())]).mean() * us) if patch.any() else 0.0,
                          run_short=float(((t1 - t0)[patch & (share == share[patch].min())]).mean() * us) if patch.any() else 0.0,
                          fill=float(((t1 - t0)[work]).sum() * us / (args.slots * dur)) if dur > 0 else 0.0,
+                         rode_blocks=int((rode > 0).sum()), rode_elements=int(rode.max()),
+                         rode_idle=int(((rode > 0) & (share == 0)).sum()),
+                         rode_at_p50=float(np.percentile(rode_at[rode > 0], 50) * us) if (rode > 0).any() else 0.0,
+                         rode_at_max=float(rode_at[rode > 0].max() * us) if (rode > 0).any() else 0.0,
                          begin=begin * us, end=t1.max() * us))
     if args.csv:
         import csv
@@ -157,6 +168,10 @@ def main():
         print(f"  patch blocks: start at {mean('start_p50', rs):.2f} us (median) / {mean('start_p90', rs):.2f} (90 %) / {mean('start_max', rs):.2f} (last), "
               f"{mean('late_patch', rs):.1f} of them late; a longest share runs {mean('run_long', rs):.2f} us, a shortest {mean('run_short', rs):.2f} us")
         print(f"  the last-ending block started at {mean('last_ender_start', rs):.2f} us and ran {mean('last_ender_run', rs):.2f} us")
+        if any(r["rode_blocks"] for r in rs):
+            print(f"  riding reduction: {mean('rode_blocks', rs):.0f} blocks took a slice ({mean('rode_idle', rs):.1f} of them with no pair step), at most "
+                  f"{max(r['rode_elements'] for r in rs)} elements a block; J stored {mean('rode_at_p50', rs):.2f} us (median) / "
+                  f"{max(r['rode_at_max'] for r in rs):.2f} us (latest) after the block's start")
         if uneven:
             print(f"  last-ending block, {len(uneven)} launches with uneven shares: longest share in {np.mean([r['last_share'] == r['max_share'] and not r['last_is_red'] for r in uneven]):.2f}, "
                   f"a late block in {np.mean([r['last_is_late'] for r in uneven]):.2f}, late AND longest in "

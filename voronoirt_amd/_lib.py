@@ -143,6 +143,8 @@ PROTOTYPES = {
     "vrt_plan_last_sweep_timing": (ctypes.c_int, [vp, p_dbl, p_i64]),
     "vrt_plan_patch_layout": (ctypes.c_int, [vp, p_i64]),
     "vrt_patch_dispatch_map": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64, ctypes.c_int, p_i64, p_i32]),
+    "vrt_plan_patch_ride_stats": (ctypes.c_int, [ctypes.c_void_p, p_i64]),
+    "vrt_patch_ride_map": (ctypes.c_int, [ctypes.c_int] * 7 + [c_i64, p_i32, p_i32, c_i64, c_i64, p_i64, p_i64]),
     "vrt_plan_patch_timeline": (ctypes.c_int, [vp, c_i64, c_i64, p_i64, ctypes.POINTER(ctypes.c_uint64), p_i64]),
     "vrt_plan_last_path": (ctypes.c_int, [vp]),
     "vrt_plan_set_option": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_char_p]),

@@ -437,6 +437,14 @@ class FormalPlan:
         return {"patches": out[0], "fewest_per_angle_layer": out[1], "work_slots": out[2], "padding_slots": out[3]}
 
     @property
+    def patch_ride_stats(self) -> dict:
+        """The riding J reduction (VRT_PATCH_REDUCE_RIDE=1) in the last sweep: per-layer launches that reduced in their
+        patch blocks, and the most chunks a block of them took (0, 0: every launch kept its reduction rows)."""
+        out = (ctypes.c_int64 * 2)()
+        check(_lib.load().vrt_plan_patch_ride_stats(self._h, out))
+        return {"launches": int(out[0]), "max_chunks": int(out[1])}
+
+    @property
     def last_launches(self) -> int:
         """Kernel launches of the last execute's sweep (1: the chained patch launch); waits for it to finish and
         raises if a chained launch gave up waiting for a dependency."""

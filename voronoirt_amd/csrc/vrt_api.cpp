@@ -54,7 +54,7 @@ void tuning_from_env(Tuning &t)
     static const char *names[] = {"VRT_PATH", "VRT_STEP_K", "VRT_STEP_SINGLE", "VRT_STEP_PAIRS", "VRT_STEP_XCD",
                                   "VRT_STEP_STREAMS", "VRT_STEP_LEVEL_MAP", "VRT_STEP_GROUP_DIR", "VRT_TILE_WIDE",
                                   "VRT_TILE_PRE", "VRT_PATCH_K", "VRT_PATCH_NT", "VRT_PATCH_OWN",
-                                  "VRT_PATCH_Q", "VRT_PATCH_TARGET", "VRT_PATCH_SPLIT", "VRT_PATCH_ORDER", "VRT_PATCH_TIMELINE", "VRT_PAIR_BLOCK", "VRT_PATCH_QUAD", "VRT_PATCH_LEAN", "VRT_PATCH_CHAIN", "VRT_CHAIN_PAIRS", "VRT_CHAIN_SPIN", "VRT_CHAIN_DATAFLAG", "VRT_CHAIN_STATIC", "VRT_LAMBDA_NATIVE", "VRT_DEBUG_FLAGS", "VRT_DEBUG_SKIP_LEVELS",
+                                  "VRT_PATCH_Q", "VRT_PATCH_TARGET", "VRT_PATCH_SPLIT", "VRT_PATCH_ORDER", "VRT_PATCH_REDUCE_RIDE", "VRT_PATCH_TIMELINE", "VRT_PAIR_BLOCK", "VRT_PATCH_QUAD", "VRT_PATCH_LEAN", "VRT_PATCH_CHAIN", "VRT_CHAIN_PAIRS", "VRT_CHAIN_SPIN", "VRT_CHAIN_DATAFLAG", "VRT_CHAIN_STATIC", "VRT_LAMBDA_NATIVE", "VRT_DEBUG_FLAGS", "VRT_DEBUG_SKIP_LEVELS",
                                   "VRT_TILE_DEBUG"};
     for (const char *nm : names) {
         const char *e = std::getenv(nm);
@@ -95,6 +95,7 @@ int tuning_set(Tuning &t, const char *name, const char *value, bool created)
         {"VRT_PATCH_K", &t.patch_K, 1, 8, true}, {"VRT_PATCH_NT", &t.patch_NT, 64, 1024, true},
         {"VRT_PATCH_OWN", &t.patch_own, 0, 65535, true}, {"VRT_PATCH_Q", &t.patch_Q, 1, 4, false},
         {"VRT_PATCH_TARGET", &t.patch_target, 0, 1 << 20, false}, {"VRT_PATCH_SPLIT", &t.patch_split, 0, 4096, false}, {"VRT_PATCH_ORDER", &t.patch_order, 0, 1, false},
+        {"VRT_PATCH_REDUCE_RIDE", &t.patch_reduce_ride, 0, 1, false},
         {"VRT_PATCH_TIMELINE", &t.patch_timeline, 0, 1, false}, {"VRT_PAIR_BLOCK", &t.pair_block, 1, 16, true},
         {"VRT_PATCH_QUAD", &t.patch_quad, 0, 1, true}, {"VRT_PATCH_LEAN", &t.patch_lean, 0, 1, false},
         {"VRT_PATCH_CHAIN", &t.patch_chain, 0, 2, false}, {"VRT_CHAIN_PAIRS", &t.chain_pairs, 1, 256, false},
@@ -1402,6 +1403,20 @@ int vrt_plan_patch_layout(const vrt_plan *p, int64_t *out)
 int vrt_patch_dispatch_map(int order, int nrow, int nsplit, int lg_siblings, int64_t nred, int steps, int64_t *dims, int32_t *blocks)
 {
     return guarded([&] { return patch_dispatch_map(order, nrow, nsplit, lg_siblings, nred, steps, dims, blocks); });
+}
+
+int vrt_patch_ride_map(int order, int nrow, int nsplit, int lg_siblings, int npair, int lg_block, int NT, int64_t n, const int32_t *lo,
+                       const int32_t *hi, int64_t first_block, int64_t nblocks, int64_t *dims, int64_t *elems)
+{
+    return guarded([&] { return patch_ride_map(order, nrow, nsplit, lg_siblings, npair, lg_block, NT, n, lo, hi, first_block, nblocks, dims, elems); });
+}
+
+int vrt_plan_patch_ride_stats(const vrt_plan *p, int64_t *out)
+{
+    if (!p || !out) return fail(VRT_EINVAL, "NULL plan or output");
+    out[0] = p->patch_rode_launches;
+    out[1] = p->patch_rode_chunks;
+    return VRT_OK;
 }
 
 int vrt_plan_patch_timeline(vrt_plan *p, int64_t cap_launches, int64_t cap_blocks, int64_t *launches, uint64_t *stamps, int64_t *counts)

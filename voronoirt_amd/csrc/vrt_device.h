@@ -215,6 +215,16 @@ struct PatchReduce {
     double w[kMaxAngles];            // quadrature weight per ACTIVE angle
     int32_t angles[2][kMaxAngles];   // active angles of the range's direction, in the reference's order
 };
+// Launch constants of the riding form of that reduction (vrt_patch.hip: ride_slice; option VRT_PATCH_REDUCE_RIDE): no
+// reduction blocks -- every block of the patch grid reduces, in its own start-up, up to four NT-element chunks of the
+// ranges' pair elements.  The kernels of a launch that rides are instantiations of their own: the default kernels hold
+// none of this.
+struct PatchRide {
+    int on = 0;                      // 1: this launch reduces in its patch blocks (PatchReduce::nred = 0: no reduction rows)
+    unsigned blocks = 0;             // blocks of the patch grid: gridDim.x x patch rows
+    unsigned chunks[2] = {0, 0};     // chunks of range 0 / 1: ceil((hi - lo) x npair / NT)
+    unsigned rcp[2] = {0, 0};        // rcp32_of(hi - lo): an element's pair without a division (div_by_rcp)
+};
 
 
 }  // namespace vrt

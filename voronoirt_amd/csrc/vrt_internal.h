@@ -327,6 +327,10 @@ struct Tuning {
     int patch_order = 1;          // VRT_PATCH_ORDER: dispatch order of the patch blocks of a per-layer launch: 0 = the workgroups of an
                                   //   item side by side (interleaved), 1 = share-major, every item's longest share first
                                   //   (vrt_patch.hip: patch_block_of; default since profiles/order/INDEX.md)
+    int patch_reduce_ride = 0;    // VRT_PATCH_REDUCE_RIDE: 1 = the J reduction of a per-layer launch in its patch blocks' start-up (a
+                                  //   launch without patch rows, or whose patch grid cannot take it at four elements per
+                                  //   thread, keeps its reduction rows), 0 = reduction rows always (vrt_patch.hip: ride_slice).
+                                  //   Default 0: on C4 riding runs at 6.849 ms against 6.613 with rows (profiles/reduce_ride/INDEX.md)
     int patch_timeline = 0;       // VRT_PATCH_TIMELINE: the blocks of the per-layer launches leave their start and end stamps
                                   //   (-DVRT_DIAG build only: tools/patch_timeline.py)
     int chain_static = 1;         // VRT_CHAIN_STATIC: the progress-word form of the chained launch maps block -> item statically (0: tickets)
@@ -559,6 +563,8 @@ struct vrt_plan {
     vrt::DevBuf<unsigned long long> d_patch_tl;   // timeline of the -DVRT_DIAG build (VRT_PATCH_TIMELINE): three words per block
     std::vector<int64_t> patch_tl_launches;       //   kPatchTimelineRec numbers per recorded launch of the last sweep
     int64_t patch_tl_blocks = 0;                  //   blocks recorded so far
+    int64_t patch_rode_launches = 0, patch_rode_chunks = 0;   // per-layer launches of the last sweep whose reduction rode in their
+                                                  //   patch blocks, and the most chunks a block of them took (vrt_plan_patch_ride_stats)
     vrt::Stream step_stream[4];
     vrt::Event step_fork, step_join[4];
     int last_path = 0;                   // path of the last execute (vrt_plan_last_path): 1 levels, 2 tiles, 3 steps, 4 patches
@@ -800,6 +806,9 @@ void patch_timeline_begin(vrt_plan *p);          // a sweep of per-layer launche
 int patch_timeline_read(vrt_plan *p, int64_t cap_launches, int64_t cap_blocks, int64_t *launches, uint64_t *stamps, int64_t *counts);
 // the grid of a per-layer launch and, with `blocks`, what each of its blocks does (vrt_patch_dispatch_map)
 int patch_dispatch_map(int order, int nrow, int nsplit, int lg_siblings, int64_t nred, int steps, int64_t *dims, int32_t *blocks);
+// which pair elements the blocks of a launch's patch grid reduce in the riding form (vrt_patch_ride_map)
+int patch_ride_map(int order, int nrow, int nsplit, int lg_siblings, int npair, int lg_block, int NT, int64_t n, const int32_t *lo,
+                   const int32_t *hi, int64_t first_block, int64_t nblocks, int64_t *dims, int64_t *elems);
 // ctrl_zeroed: the launch's control words (chain_ctrl_words() of them at p->chain.ctrl_words()) were zeroed on `st` by the caller
 int launch_patch_chain(vrt_plan *p, const TileArgs &ta, int npair, const PatchShape &shape, hipStream_t st, bool f32,
                        const PatchReduce *reduce, bool ctrl_zeroed = false);

@@ -767,6 +767,7 @@ static int run_patch_layers(vrt_plan *p, const ExecArgs &x, LayerRun &r)
     if ((rc = fork_streams(p, st, G))) return rc;
     r.launches = 0;
     if (kDiag) patch_timeline_begin(p);
+    p->patch_rode_launches = p->patch_rode_chunks = 0;
     for (int layer = 2; layer <= Lmax; layer++)
         for (int gi = 0; gi < G; gi++) {
             hipStream_t sg = gi == 0 ? st : p->step_stream[gi];     // group 0 on the caller's stream: one hardware queue less

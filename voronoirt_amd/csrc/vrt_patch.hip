@@ -72,6 +72,9 @@ struct PatchArgs {
     const int32_t *e_pos, *e_u1, *e_u2;     // per entry: storage position of the site and of its two upwinds
     const uint32_t *e_vis, *e_loc;           //   packed visit levels; patch-local tile slots of the upwinds
     const double *e_w1, *e_w2, *e_r1, *e_r2; //   weights and path lengths (irregular_ray_tracing.jl:51,66)
+    // (behind everything the patch blocks read: the records above lie where they always lay)
+    unsigned rows_rcp[2] = {0, 0};           // rcp32_of(reduction blocks a full-width pair block of range 0 / 1 takes): patch_reduce_role
+    PatchRide ride;                          // the riding form of the reduction (its kernels only)
 };
 
 // entry tables of one angle from its storage-order tables
@@ -202,6 +205,81 @@ static PatchGrid patch_grid(int order, int nrow, int nsplit, int lgS, int64_t nr
     g.gy = nrow + (nred + g.gx - 1) / g.gx;
     return g;
 }
+// ---- a quotient by a launch constant without a division (the reduction rows and the riding form) ------------------------
+// f / len by a multiply-high with rcp = min(floor(2^32 / len), 2^32 - 1): rcp len = 2^32 - rho with 0 <= rho < len (len = 1:
+// rho = 1), so f rcp / 2^32 = f / len - f rho / (len 2^32) > f / len - 1 for every f < 2^32: the estimate is the quotient
+// or one below it, and one correction makes it exact.  No condition on f len (an element count times a range length
+// passes 2^32 long before a grid is full).
+__host__ __device__ __forceinline__ unsigned rcp32_of(unsigned len)
+{
+    return len <= 1u ? 0xFFFFFFFFu : (unsigned)(((unsigned long long)1 << 32) / len);
+}
+__host__ __device__ __forceinline__ unsigned div_by_rcp(unsigned f, unsigned len, unsigned rcp)
+{
+    unsigned t = (unsigned)(((unsigned long long)f * rcp) >> 32);
+    if (f - t * len >= len) t++;
+    return t;
+}
+// ---- the reduction riding in the patch blocks (PatchRide) ----------------------------------------------------------------
+// The slice map: which pair elements block `lin` of the patch grid (its number in the grid's linear order) reduces.
+// The pair elements of range r are numbered f = 0 .. len_r npair - 1 pair block after pair block -- block [k0, k0 + 2^lw)
+// holds f in [len_r k0, len_r (k0 + 2^lw)), one contiguous run of the plane from k0 n + (lo_r << lw) -- and cut into chunks
+// of NT (a range's last chunk may be short: a chunk never holds elements of two ranges, so its angle list is the
+// workgroup's).  The chunks of range 0, then those of range 1, are dealt round robin: block lin takes chunks
+// lin, lin + blocks, lin + 2 blocks, lin + 3 blocks (as far as they exist); thread tid takes element tid of each.
+// A launch rides when four rounds cover its chunks (ride_fits).  f / len_r is the element's pair, hence its pair block.
+struct RideSlice {
+    int r;                 // range of the chunk; -1: no such chunk for this block
+    bool ok;               // this thread has an element in it (false: the short last chunk of a range; e is a valid one all the same)
+    size_t e;              // the element: index into the J_dir / intensity plane set
+};
+__host__ __device__ __forceinline__ unsigned ride_chunks_of(const PatchRide &rd, unsigned lin)   // chunks of block lin: 0 .. 4
+{
+    const unsigned total = rd.chunks[0] + rd.chunks[1];
+    if (lin >= rd.blocks) return 0u;
+    unsigned rounds = 0;
+    for (unsigned i = 0; i < 4u; i++) rounds += lin + i * rd.blocks < total ? 1u : 0u;
+    return rounds;
+}
+__host__ __device__ __forceinline__ RideSlice ride_slice(const PatchReduce &red, const PatchRide &rd, int npair, int lgB, int64_t n, unsigned NT,
+                                                         unsigned lin, unsigned round, unsigned tid)
+{
+    RideSlice s;
+    s.r = -1; s.ok = false; s.e = 0;
+    if (lin >= rd.blocks) return s;
+    unsigned c = lin + round * rd.blocks;
+    if (c >= rd.chunks[0] + rd.chunks[1]) return s;
+    s.r = c >= rd.chunks[0] ? 1 : 0;
+    if (s.r) c -= rd.chunks[0];
+    const unsigned len = (unsigned)(red.hi[s.r] - red.lo[s.r]);
+    const unsigned count = len * (unsigned)npair;               // < 2^31 (ride_fits)
+    unsigned f = c * NT + tid;
+    s.ok = f < count;
+    if (!s.ok) f = count - 1;
+    int k0, lw;
+    pair_block_at((int)div_by_rcp(f, len, rd.rcp[s.r]), npair, lgB, k0, lw);
+    s.e = (size_t)k0 * (size_t)n + ((size_t)red.lo[s.r] << lw) + (size_t)(f - len * (unsigned)k0);
+    return s;
+}
+// host: whether a launch of `blocks` patch-grid blocks can take the reduction at four chunks per block, and its constants
+static bool ride_fits(const PatchReduce &red, PatchRide &rd, int npair, int NT, int64_t blocks)
+{
+    rd = PatchRide{};
+    int64_t chunks = 0;
+    for (int r = 0; r < 2; r++) {
+        const int64_t len = (red.count[r] > 0 && red.Jd[r]) ? std::max(0, red.hi[r] - red.lo[r]) : 0;
+        const int64_t count = len * npair;
+        if (count > (int64_t)INT32_MAX - 4096) return false;
+        rd.chunks[r] = (unsigned)((count + NT - 1) / NT);
+        rd.rcp[r] = rcp32_of((unsigned)len);
+        chunks += rd.chunks[r];
+    }
+    // (blocks < 2^29: lin + 3 blocks stays a 32-bit number)
+    if (chunks == 0 || blocks < 1 || blocks >= ((int64_t)1 << 29) || chunks > 4 * blocks) return false;
+    rd.on = 1;
+    rd.blocks = (unsigned)blocks;
+    return true;
+}
 __device__ __forceinline__ int reduce_block_index(const PatchArgs &pa)      // >= 0: this block reduces
 {
     const int rows = (int)gridDim.y - pa.prow;                // reduction rows
@@ -218,7 +296,8 @@ __device__ __forceinline__ int patch_row(const PatchArgs &pa) { return patch_blo
 // Timeline of the -DVRT_DIAG build (VRT_PATCH_TIMELINE=1, tools/patch_timeline.py): every block of a per-layer launch
 // leaves {start stamp, end stamp, share} at its place in the grid's linear order -- wall_clock64() when the kernel is
 // entered and when thread 0 leaves it, whichever return it takes; share = pair steps of a patch block, | 1 << 32 for a
-// reduction block (0 steps: padding, or nothing of the item for this block).  In the product build the object is empty.
+// reduction block (0 steps: padding, or nothing of the item for this block); a patch block that rode a slice of the
+// reduction adds its elements and the time of its J_dir store (rode).  In the product build the object is empty.
 struct BlockStamp {
     unsigned long long *slot = nullptr;
     unsigned long long t0 = 0, share = 0;
@@ -231,11 +310,20 @@ struct BlockStamp {
     }
     __device__ __forceinline__ void steps(const PatchArgs &pa, int b0, int b1)
     {
-        if (kDiag) share = (unsigned long long)((b1 - b0 + pa.Q - 1) / pa.Q);
+        if (kDiag) share |= (unsigned long long)((b1 - b0 + pa.Q - 1) / pa.Q);
     }
     __device__ __forceinline__ void reduces()
     {
         if (kDiag) share = 1ull << 32;
+    }
+    // a patch block that reduced a slice in its start-up (ride_finish): bits 33-46 its elements (chunks x NT), bits 48-63
+    // when it stored J_dir, in wall-clock ticks from its start
+    __device__ __forceinline__ void rode(unsigned elements)
+    {
+        if (kDiag && slot) {
+            const unsigned long long dt = wall_clock64() - t0;
+            share |= ((unsigned long long)(elements & 0x3FFFu) << 33) | ((dt < 0xFFFFull ? dt : 0xFFFFull) << 48);
+        }
     }
     __device__ __forceinline__ ~BlockStamp()
     {
@@ -259,14 +347,30 @@ __device__ __forceinline__ void patch_reduce_role(const PatchArgs &pa)
     // the range's pair elements of a pair block [k0, k0 + 2^lw) are one contiguous run of the plane,
     // (hi - lo) << lw long: blocks are dealt per pair block (size_reduce counts them the same way)
     const int len = pa.red.hi[r] - pa.red.lo[r];
-    const int per = NT * pa.red.ppb;
-    const int nblock = pair_block_count(pa.npair, pa.lgB);
-    int k0 = 0, lw = 0;
-    for (int k = 0; k < nblock; k++) {
-        pair_block_of(k, pa.npair, pa.lgB, k0, lw);
-        const int cnt = (int)((((int64_t)len << lw) + per - 1) / per);
-        if (b < cnt) break;
-        b -= cnt;
+    // its pair block without a search: the full-width blocks take the same number of reduction blocks each (a quotient by
+    // that launch constant: div_by_rcp), behind them at most lgB narrower ones; NT x ppb is a power of two
+    static_assert((NT & (NT - 1)) == 0, "blocks per pair block are counted with a shift");
+    const int lgper = (31 - __builtin_clz((unsigned)NT)) + (pa.red.ppb == 4 ? 2 : 0);
+    const int nfull = pa.npair >> pa.lgB;
+    int k0 = 0, lw = pa.lgB;
+    {
+        const unsigned cnt = (unsigned)((((unsigned long long)len << lw) + ((1u << lgper) - 1)) >> lgper);
+        const unsigned k = div_by_rcp((unsigned)b, cnt, pa.rows_rcp[r]);
+        if ((int)k < nfull) {
+            k0 = (int)k << pa.lgB;
+            b -= (int)(k * cnt);
+        } else {
+            b -= (int)((unsigned)nfull * cnt);
+            k0 = nfull << pa.lgB;
+            const int rest = pa.npair - k0;
+            for (lw = pa.lgB - 1; lw > 0; lw--)               // the bits of the rest, widest block first
+                if (rest & (1 << lw)) {
+                    const int c = (int)((((unsigned long long)len << lw) + ((1u << lgper) - 1)) >> lgper);
+                    if (b < c) break;
+                    b -= c;
+                    k0 += 1 << lw;
+                }
+        }
     }
     const int64_t nn = ta.n;
     const size_t run = (size_t)len << lw;
@@ -317,6 +421,98 @@ __device__ __forceinline__ void patch_reduce_role(const PatchArgs &pa)
     }
 }
 
+// ---- the riding form: a patch block's slice of the launch's reduction, in the shadow of its own start-up ------------------
+// A patch block waits twice before its first pair: for its item's record (a scalar load) and for the nine loads of the
+// entry table, whose addresses the record decides.  Every register of the pair loop is dead until then.  The slice's
+// addresses depend on blockIdx, threadIdx and launch constants alone (ride_slice): ride_issue sends the loads of the
+// block's first chunk ahead of the record -- one element per thread, its first kEarly angles in flight together in
+// registers -- and ride_finish forms the sums behind the parked table: per element the statements of patch_reduce_role,
+// the angles in the reference's order.  A block with more chunks (four at most) takes the others there, one after the
+// other in the same way.  kEarly is what the 64 registers of k_patch_lean hold beside the table's own nine loads
+// without scratch memory: five pairs of doubles (a sixth costs 20 bytes of scratch per lane), six pairs of floats; the
+// angles behind them (C4, doubles: the sixth of a direction) are read in ride_finish.
+// NOT the default (VRT_PATCH_REDUCE_RIDE=1 selects it): bit for bit the reduction rows' J, but in this form -- one chunk's
+// first angles ahead of the record, not every angle of four elements, which the registers do not hold -- the slice does
+// not hide: a block with a slice stores J 7 us after its start and C4 runs at 6.849 ms against 6.613 with reduction rows
+// (profiles/reduce_ride/INDEX.md: ab_c4.txt, timeline_ride.txt; no other workload was measured).  Supposed, not measured:
+// its loads are intensities other XCDs stored in the previous launch and the table's loads queue behind them.  It stays
+// for that A/B and its tests, in
+// kernels of its own (k_ride_lean, k_ride_quad, k_ride_solve: the bodies below with RIDE = true); k_patch_lean, k_patch_quad
+// and k_patch_solve are the parent's kernels instruction for instruction but for the reduction blocks' pair-block arithmetic.
+template <typename T>
+struct RideLoads {
+    static constexpr int kEarly = sizeof(T) == 8 ? 5 : 6;
+    // (scalars, written one by one: a pair assigned as a whole is a 16-byte copy, and two such copies that the compiler
+    // merges into one with a choice of destinations keep the whole record in scratch memory)
+    T x0, y0, x1, y1, x2, y2, x3, y3, x4, y4, x5, y5;
+    unsigned chunks = 0;       // chunks of this block (0: it reduces nothing)
+};
+// the first kRideEarly angles of element s into the registers
+template <typename T>
+__device__ __forceinline__ void ride_load(const PatchArgs &pa, RideLoads<T> &rl, const RideSlice &s)
+{
+    typedef typename Pair<T>::type T2;
+    const T2 *I0 = reinterpret_cast<const T2 *>(pa.ta.I);
+    const size_t plane = (size_t)pa.npair * (size_t)pa.ta.n;
+    const int cnt = pa.red.count[s.r];
+    constexpr int kRideEarly = RideLoads<T>::kEarly;
+#define VRT_RIDE_LOAD(K) \
+    if (K < kRideEarly && K < cnt) { \
+        const T2 t = I0[(size_t)pa.red.angles[s.r][K] * plane + s.e]; \
+        rl.x##K = t.x; rl.y##K = t.y; \
+    }
+    VRT_RIDE_LOAD(0) VRT_RIDE_LOAD(1) VRT_RIDE_LOAD(2) VRT_RIDE_LOAD(3) VRT_RIDE_LOAD(4) VRT_RIDE_LOAD(5)
+#undef VRT_RIDE_LOAD
+}
+// J_dir of element s from them and from the angles behind them
+template <typename T>
+__device__ __forceinline__ void ride_sum(const PatchArgs &pa, const RideLoads<T> &rl, const RideSlice &s)
+{
+    typedef typename Pair<T>::type T2;
+    const T2 *I0 = reinterpret_cast<const T2 *>(pa.ta.I);
+    const size_t plane = (size_t)pa.npair * (size_t)pa.ta.n;
+    const int cnt = pa.red.count[s.r];
+    double ax = 0.0, ay = 0.0;
+    constexpr int kRideEarly = RideLoads<T>::kEarly;
+    // the reference's angle order (lambda_iteration.jl:84,102,107)
+#define VRT_RIDE_SUM(J) \
+    if (J < kRideEarly && J < cnt) { \
+        const int a = pa.red.angles[s.r][J]; \
+        ax += pa.red.w[a] * (double)rl.x##J; \
+        ay += pa.red.w[a] * (double)rl.y##J; \
+    }
+    VRT_RIDE_SUM(0) VRT_RIDE_SUM(1) VRT_RIDE_SUM(2) VRT_RIDE_SUM(3) VRT_RIDE_SUM(4) VRT_RIDE_SUM(5)
+#undef VRT_RIDE_SUM
+    for (int j = kRideEarly; j < cnt; j++) {
+        const int a = pa.red.angles[s.r][j];
+        const double2 v = to_d2(I0[(size_t)a * plane + s.e]);
+        ax += pa.red.w[a] * v.x;
+        ay += pa.red.w[a] * v.y;
+    }
+    if (s.ok) reinterpret_cast<T2 *>(pa.red.Jd[s.r])[s.e] = from_d2<T>(make_double2(ax, ay));
+}
+template <typename T, int NT>
+__device__ __forceinline__ void ride_issue(const PatchArgs &pa, RideLoads<T> &rl)
+{
+    if (diag(pa.dbg, kDiagNoReduce)) return;                   // (a launch of these kernels rides: pa.ride.on)
+    const unsigned lin = blockIdx.y * gridDim.x + blockIdx.x;
+    rl.chunks = ride_chunks_of(pa.ride, lin);
+    if (rl.chunks == 0) return;
+    ride_load<T>(pa, rl, ride_slice(pa.red, pa.ride, pa.npair, pa.lgB, pa.ta.n, NT, lin, 0, threadIdx.x));
+}
+template <typename T, int NT>
+__device__ __forceinline__ void ride_finish(const PatchArgs &pa, RideLoads<T> &rl, BlockStamp &stamp)
+{
+    if (rl.chunks == 0) return;
+    const unsigned lin = blockIdx.y * gridDim.x + blockIdx.x;
+    for (unsigned round = 0; round < rl.chunks; round++) {
+        const RideSlice s = ride_slice(pa.red, pa.ride, pa.npair, pa.lgB, pa.ta.n, NT, lin, round, threadIdx.x);
+        if (round > 0) ride_load<T>(pa, rl, s);
+        ride_sum<T>(pa, rl, s);
+    }
+    stamp.rode(rl.chunks * NT);
+}
+
 // T: storage type of S, α, I; AM: alpha mode (VRT_ALPHA_SITE, _SITE_LAM, _ANGLE_SITE_LAM); K entries per thread;
 // Q wavelength pairs solved at a time; NT threads.  A workgroup walks `ppw` wavelength pairs with ONE read of its
 // patch's entry table, Q pairs at a time.
@@ -325,9 +521,10 @@ __device__ __forceinline__ void patch_reduce_role(const PatchArgs &pa)
 #else
 #define VRT_WPE_ATTR
 #endif
-template <typename T, int AM, int K, int Q, int NT>
-__global__ void __launch_bounds__(NT) VRT_WPE_ATTR
-k_patch_solve(PatchArgs pa)
+// RIDE: the body of a launch whose reduction rides in its patch blocks (ride_issue / ride_finish) -- the kernels k_ride_solve,
+// k_ride_lean, k_ride_quad; the kernels of every other launch (k_patch_*) hold nothing of that form.
+template <typename T, int AM, int K, int Q, int NT, bool RIDE>
+__device__ __forceinline__ void patch_solve_body(const PatchArgs &pa)
 {
     typedef typename Pair<T>::type T2;
     extern __shared__ __attribute__((aligned(16))) double2 ptile[];
@@ -342,23 +539,34 @@ k_patch_solve(PatchArgs pa)
         patch_reduce_role<T, NT>(pa);
         return;
     }
+    RideLoads<T> ride;
+    if constexpr (RIDE) ride_issue<T, NT>(pa, ride);
     const PatchBlock blk = patch_block(pa, pa.lgB);
     const int x = blk.lane, sj = blk.row;
     // (this kernel of the non-default shapes keeps its two vector loads of the record and its table loop as they were:
     // the start-up work of patch_item / EntryTable went into the kernels the defaults run)
     const int4 rec = pa.wrec[2 * (sj * 8 + x)], rec2 = pa.wrec[2 * (sj * 8 + x) + 1];
-    if (rec.y <= 0) return;
+    if (rec.y <= 0) {
+        if constexpr (RIDE) ride_finish<T, NT>(pa, ride, stamp);
+        return;
+    }
     // sibling sib solves pair k0 + sib of every block [k0, k0 + 2^lw) with 2^lw > sib among blocks b0 .. b1-1: the
     // 2^lgB siblings of an item run side by side on one XCD and use a gathered line (one site's pairs) whole
     const int sib = blk.sib;
     const int nblock = pair_block_count(pa.npair, pa.lgB);
     int b0, b1;
     split_blocks(pa, blk.split, nblock, b0, b1);
-    if (b0 >= b1) return;
+    if (b0 >= b1) {
+        if constexpr (RIDE) ride_finish<T, NT>(pa, ride, stamp);
+        return;
+    }
     {
         int k0, lw;
         pair_block_of(b0, pa.npair, pa.lgB, k0, lw);
-        if (sib >= (1 << lw)) return;                           // block widths only shrink: nothing for this sibling
+        if (sib >= (1 << lw)) {                                 // block widths only shrink: nothing for this sibling
+            if constexpr (RIDE) ride_finish<T, NT>(pa, ride, stamp);
+            return;
+        }
     }
     stamp.steps(pa, b0, b1);
     const int ent_off = rec.x, n_ent = rec.y, own_lo = rec.z, own_cnt = rec.w;
@@ -391,6 +599,7 @@ k_patch_solve(PatchArgs pa)
         s_loc[i] = (l1 == 0xFFFFu ? (uint32_t)n_ent : l1) | ((l2 == 0xFFFFu ? (uint32_t)n_ent : l2) << 16);
         s_w1[i] = pa.e_w1[e]; s_w2[i] = pa.e_w2[e]; s_r1[i] = pa.e_r1[e]; s_r2[i] = pa.e_r2[e];
     }
+    if constexpr (RIDE) ride_finish<T, NT>(pa, ride, stamp);
     if (tid == 0) {
 #pragma unroll
         for (int qi = 0; qi < Q; qi++) ptile[qi * stride + n_ent] = make_double2(0.0, 0.0);   // the zero slot
@@ -515,6 +724,19 @@ k_patch_solve(PatchArgs pa)
     }
 }
 
+
+template <typename T, int AM, int K, int Q, int NT>
+__global__ void __launch_bounds__(NT) VRT_WPE_ATTR
+k_patch_solve(PatchArgs pa)
+{
+    patch_solve_body<T, AM, K, Q, NT, false>(pa);
+}
+template <typename T, int AM, int K, int Q, int NT>
+__global__ void __launch_bounds__(NT) VRT_WPE_ATTR
+k_ride_solve(PatchArgs pa)
+{
+    patch_solve_body<T, AM, K, Q, NT, true>(pa);
+}
 
 // ---- what the one-entry-per-thread kernels (k_patch_lean, k_patch_quad, k_patch_chain) share --------------------------
 // the work of this workgroup: patch, sibling number inside a pair block, blocks [b0, b1), the patch's record
@@ -1032,9 +1254,8 @@ __device__ __forceinline__ void lean_pairs(const PairIO &pa, const PatchItem &it
     }
 }
 
-template <typename T, int AM, int NT>
-__global__ void __launch_bounds__(NT) VRT_LEAN_ATTR
-k_patch_lean(PatchArgs pa)
+template <typename T, int AM, int NT, bool RIDE>
+__device__ __forceinline__ void patch_lean_body(const PatchArgs &pa)
 {
     extern __shared__ __attribute__((aligned(16))) double2 ptile[];
     const int tid = threadIdx.x;
@@ -1048,17 +1269,35 @@ k_patch_lean(PatchArgs pa)
     typename EntryTable<NT>::Regs early{};
     if (diag(pa.dbg, kDiagDirectTable))                         // diagnostics: SOME table, at an address no load decides
         early = EntryTable<NT>::load(pa, min(pa.dbg_ent0 + (patch_row(pa) * 8 + ((int)blockIdx.x & 7)) * pa.dbg_ent_stride + tid, pa.dbg_ent_last));
+    RideLoads<T> ride;
+    if constexpr (RIDE) ride_issue<T, NT>(pa, ride);            // (the slice of the reduction this block rides: in flight from here)
     PatchItem it;
-    if (!patch_item(pa, pa.lgB, it)) return;
+    if (!patch_item(pa, pa.lgB, it)) {
+        if constexpr (RIDE) ride_finish<T, NT>(pa, ride, stamp);
+        return;
+    }
     stamp.steps(pa, it.b0, it.b1);
     if (diag(pa.dbg, kDiagNoPairLoop)) it.b1 = it.b0;           // diagnostics: the item's overhead alone
     const EntryTable<NT> tab(ptile, 1);
     if (tid == 0) ptile[it.n_ent] = make_double2(0.0, 0.0);  // the zero slot
     if (diag(pa.dbg, kDiagDirectTable)) tab.store(early, it, tid);
     else tab.park(pa, it, tid);
+    if constexpr (RIDE) ride_finish<T, NT>(pa, ride, stamp);
     exp2_table_store(e2);
     __syncthreads();
     lean_pairs<T, AM, NT, 0>(pair_io<AM>(pa, it.d), it, tab, ptile);
+}
+template <typename T, int AM, int NT>
+__global__ void __launch_bounds__(NT) VRT_LEAN_ATTR
+k_patch_lean(PatchArgs pa)
+{
+    patch_lean_body<T, AM, NT, false>(pa);
+}
+template <typename T, int AM, int NT>
+__global__ void __launch_bounds__(NT) VRT_LEAN_ATTR
+k_ride_lean(PatchArgs pa)
+{
+    patch_lean_body<T, AM, NT, true>(pa);
 }
 
 
@@ -1198,9 +1437,8 @@ __device__ __forceinline__ void quad_pairs(const PairIO &pa, const PatchItem &it
 #ifndef VRT_QUAD_ATTR            // 80 VGPRs = three 512-thread workgroups per CU (no scratch at that budget)
 #define VRT_QUAD_ATTR __attribute__((amdgpu_waves_per_eu(6, 6)))
 #endif
-template <int AM, int NT>
-__global__ void __launch_bounds__(NT) VRT_QUAD_ATTR
-k_patch_quad(PatchArgs pa)
+template <int AM, int NT, bool RIDE>
+__device__ __forceinline__ void patch_quad_body(const PatchArgs &pa)
 {
     extern __shared__ __attribute__((aligned(16))) double2 ptile[];
     const int tid = threadIdx.x;
@@ -1212,8 +1450,13 @@ k_patch_quad(PatchArgs pa)
     }
     // workgroup (item, sib2, split): the pairs 2 sib2, 2 sib2 + 1 of every block among blocks b0 .. b1-1
     const double e2 = exp2_table_load();                     // (in flight beside the item's record and entry table)
+    RideLoads<float> ride;
+    if constexpr (RIDE) ride_issue<float, NT>(pa, ride);     // (the slice of the reduction this block rides: in flight from here)
     PatchItem it;
-    if (!patch_item(pa, pa.lgB - 1, it)) return;
+    if (!patch_item(pa, pa.lgB - 1, it)) {
+        if constexpr (RIDE) ride_finish<float, NT>(pa, ride, stamp);
+        return;
+    }
     stamp.steps(pa, it.b0, it.b1);
     const EntryTable<NT> tab(ptile, 2);
     if (tid == 0) {
@@ -1221,9 +1464,22 @@ k_patch_quad(PatchArgs pa)
         ptile[NT + 1 + it.n_ent] = make_double2(0.0, 0.0);
     }
     tab.park(pa, it, tid);
+    if constexpr (RIDE) ride_finish<float, NT>(pa, ride, stamp);
     exp2_table_store(e2);
     __syncthreads();
     quad_pairs<AM, NT, false>(pair_io<AM>(pa, it.d), it, tab, ptile);
+}
+template <int AM, int NT>
+__global__ void __launch_bounds__(NT) VRT_QUAD_ATTR
+k_patch_quad(PatchArgs pa)
+{
+    patch_quad_body<AM, NT, false>(pa);
+}
+template <int AM, int NT>
+__global__ void __launch_bounds__(NT) VRT_QUAD_ATTR
+k_ride_quad(PatchArgs pa)
+{
+    patch_quad_body<AM, NT, true>(pa);
 }
 
 
@@ -1507,29 +1763,45 @@ k_patch_chain_quad(ChainDev ca, const ChainDev *cd, uint32_t base)
 #define VRT_PATCH_SHAPES(X) \
     X(1, 1, 256) X(1, 1, 512) X(1, 1, 1024) X(2, 1, 256) X(2, 1, 512) X(1, 2, 256) X(1, 2, 512) X(1, 2, 1024) X(2, 2, 512)
 
-template <typename T, int AM>
+template <typename T, int AM, bool RIDE>
 static int launch_shape(int K, int Q, int NT, dim3 grid, size_t lds, hipStream_t st, const PatchArgs &pa)
 {
     if constexpr (sizeof(T) == 4) {
         if (pa.quad) {
             switch (NT) {
-            case 256: hipLaunchKernelGGL((k_patch_quad<AM, 256>), grid, dim3(256), lds, st, pa); return VRT_OK;
-            case 512: hipLaunchKernelGGL((k_patch_quad<AM, 512>), grid, dim3(512), lds, st, pa); return VRT_OK;
-            case 1024: hipLaunchKernelGGL((k_patch_quad<AM, 1024>), grid, dim3(1024), lds, st, pa); return VRT_OK;
+            case 256: if constexpr (RIDE) hipLaunchKernelGGL((k_ride_quad<AM, 256>), grid, dim3(256), lds, st, pa);
+                      else hipLaunchKernelGGL((k_patch_quad<AM, 256>), grid, dim3(256), lds, st, pa);
+                      return VRT_OK;
+            case 512: if constexpr (RIDE) hipLaunchKernelGGL((k_ride_quad<AM, 512>), grid, dim3(512), lds, st, pa);
+                      else hipLaunchKernelGGL((k_patch_quad<AM, 512>), grid, dim3(512), lds, st, pa);
+                      return VRT_OK;
+            case 1024: if constexpr (RIDE) hipLaunchKernelGGL((k_ride_quad<AM, 1024>), grid, dim3(1024), lds, st, pa);
+                      else hipLaunchKernelGGL((k_patch_quad<AM, 1024>), grid, dim3(1024), lds, st, pa);
+                      return VRT_OK;
             default: break;
             }
         }
     }
     if (pa.lean && K == 1 && Q == 1) {
         switch (NT) {
-        case 256: hipLaunchKernelGGL((k_patch_lean<T, AM, 256>), grid, dim3(256), lds, st, pa); return VRT_OK;
-        case 512: hipLaunchKernelGGL((k_patch_lean<T, AM, 512>), grid, dim3(512), lds, st, pa); return VRT_OK;
-        case 1024: hipLaunchKernelGGL((k_patch_lean<T, AM, 1024>), grid, dim3(1024), lds, st, pa); return VRT_OK;
+        case 256: if constexpr (RIDE) hipLaunchKernelGGL((k_ride_lean<T, AM, 256>), grid, dim3(256), lds, st, pa);
+                  else hipLaunchKernelGGL((k_patch_lean<T, AM, 256>), grid, dim3(256), lds, st, pa);
+                  return VRT_OK;
+        case 512: if constexpr (RIDE) hipLaunchKernelGGL((k_ride_lean<T, AM, 512>), grid, dim3(512), lds, st, pa);
+                  else hipLaunchKernelGGL((k_patch_lean<T, AM, 512>), grid, dim3(512), lds, st, pa);
+                  return VRT_OK;
+        case 1024: if constexpr (RIDE) hipLaunchKernelGGL((k_ride_lean<T, AM, 1024>), grid, dim3(1024), lds, st, pa);
+                  else hipLaunchKernelGGL((k_patch_lean<T, AM, 1024>), grid, dim3(1024), lds, st, pa);
+                  return VRT_OK;
         default: break;
         }
     }
 #define VRT_PATCH_CASE(k, q, nt) \
-    if (K == k && Q == q && NT == nt) { hipLaunchKernelGGL((k_patch_solve<T, AM, k, q, nt>), grid, dim3(nt), lds, st, pa); return VRT_OK; }
+    if (K == k && Q == q && NT == nt) { \
+        if constexpr (RIDE) hipLaunchKernelGGL((k_ride_solve<T, AM, k, q, nt>), grid, dim3(nt), lds, st, pa); \
+        else hipLaunchKernelGGL((k_patch_solve<T, AM, k, q, nt>), grid, dim3(nt), lds, st, pa); \
+        return VRT_OK; \
+    }
     VRT_PATCH_SHAPES(VRT_PATCH_CASE)
 #undef VRT_PATCH_CASE
     return fail(VRT_EINVAL, "no patch kernel for this (entries per thread, pairs, threads) shape");
@@ -1538,10 +1810,18 @@ static int launch_shape(int K, int Q, int NT, dim3 grid, size_t lds, hipStream_t
 template <typename T>
 static int launch_mode(int am, int K, int Q, int NT, dim3 grid, size_t lds, hipStream_t st, const PatchArgs &pa)
 {
+    // (a launch whose reduction rides in its patch blocks runs kernels of its own: the others carry nothing of that form)
+    if (pa.ride.on) {
+        switch (am) {
+        case VRT_ALPHA_SITE: return launch_shape<T, VRT_ALPHA_SITE, true>(K, Q, NT, grid, lds, st, pa);
+        case VRT_ALPHA_SITE_LAM: return launch_shape<T, VRT_ALPHA_SITE_LAM, true>(K, Q, NT, grid, lds, st, pa);
+        default: return launch_shape<T, VRT_ALPHA_ANGLE_SITE_LAM, true>(K, Q, NT, grid, lds, st, pa);
+        }
+    }
     switch (am) {
-    case VRT_ALPHA_SITE: return launch_shape<T, VRT_ALPHA_SITE>(K, Q, NT, grid, lds, st, pa);
-    case VRT_ALPHA_SITE_LAM: return launch_shape<T, VRT_ALPHA_SITE_LAM>(K, Q, NT, grid, lds, st, pa);
-    default: return launch_shape<T, VRT_ALPHA_ANGLE_SITE_LAM>(K, Q, NT, grid, lds, st, pa);
+    case VRT_ALPHA_SITE: return launch_shape<T, VRT_ALPHA_SITE, false>(K, Q, NT, grid, lds, st, pa);
+    case VRT_ALPHA_SITE_LAM: return launch_shape<T, VRT_ALPHA_SITE_LAM, false>(K, Q, NT, grid, lds, st, pa);
+    default: return launch_shape<T, VRT_ALPHA_ANGLE_SITE_LAM, false>(K, Q, NT, grid, lds, st, pa);
     }
 }
 
@@ -1575,7 +1855,7 @@ int ensure_patch_work(vrt_plan *p, int G, const std::vector<int32_t> &group_angl
 
 // one layer of one stream group
 // fills the block counts of a reduction request for NT-thread blocks
-static void size_reduce(PatchReduce &red, int npair, int lgB, int NT)
+static void size_reduce(PatchReduce &red, unsigned rows_rcp[2], int npair, int lgB, int NT)
 {
     red.nred = 0;
     // elements per thread: one while the whole reduction is a fraction of a round of workgroups (a launch of a small
@@ -1589,6 +1869,7 @@ static void size_reduce(PatchReduce &red, int npair, int lgB, int NT)
     for (int r = 0; r < 2; r++) {
         const int64_t len = red.hi[r] - red.lo[r];
         red.nblk[r] = 0;
+        rows_rcp[r] = rcp32_of((unsigned)((((uint64_t)std::max<int64_t>(len, 0) << lgB) + (uint64_t)per - 1) / (uint64_t)per));
         if (len > 0 && red.count[r] > 0 && red.Jd[r])
             for (int k = 0; k < nblock; k++) {
                 int k0, lw;
@@ -1612,7 +1893,7 @@ int launch_patch_layer(vrt_plan *p, const TileArgs &ta, int npair, int layer, in
     PatchArgs pa;
     if (reduce) {
         pa.red = *reduce;
-        size_reduce(pa.red, npair, shape.lgB, p->patch_NT);
+        size_reduce(pa.red, pa.rows_rcp, npair, shape.lgB, p->patch_NT);
     }
     if (w1 <= w0 && pa.red.nred == 0) return VRT_OK;
     pa.ta = ta;
@@ -1676,6 +1957,16 @@ int launch_patch_layer(vrt_plan *p, const TileArgs &ta, int npair, int layer, in
     pa.e_w1 = p->e_w1; pa.e_w2 = p->e_w2; pa.e_r1 = p->e_r1; pa.e_r2 = p->e_r2;
     // the grid (patch_grid): the patch blocks in the plan's dispatch order, the reduction rows behind them
     pa.nrow = (int)((w1 - w0) / 8);
+    // the reduction rides in the patch blocks (VRT_PATCH_REDUCE_RIDE) where the launch has patch rows and four chunks per
+    // block of its patch grid cover it; otherwise it keeps its reduction rows -- never both forms in one launch
+    if (pa.red.nred > 0 && p->tune.patch_reduce_ride > 0 && pa.nrow > 0) {
+        const PatchGrid pg0 = patch_grid(p->tune.patch_order, pa.nrow, pa.nsplit, lgS, 0);
+        if (pg0.gy <= 65535 && ride_fits(pa.red, pa.ride, npair, p->patch_NT, pg0.gx * (int64_t)pg0.prow)) {
+            pa.red.nred = pa.red.nblk[0] = pa.red.nblk[1] = 0;
+            p->patch_rode_launches += 1;
+            p->patch_rode_chunks = std::max<int64_t>(p->patch_rode_chunks, ((int64_t)pa.ride.chunks[0] + pa.ride.chunks[1] + pa.ride.blocks - 1) / pa.ride.blocks);
+        }
+    }
     const PatchGrid pg = patch_grid(p->tune.patch_order, pa.nrow, pa.nsplit, lgS, pa.red.nred);
     pa.order = pg.order;
     pa.prow = pg.prow;
@@ -1761,6 +2052,50 @@ int patch_dispatch_map(int order, int nrow, int nsplit, int lg_siblings, int64_t
             split_blocks(sp, b.split, steps, b0, b1);
             o[1] = b.lane; o[2] = b.row; o[3] = b.split; o[4] = b.sib; o[5] = b1 - b0;
         }
+    return VRT_OK;
+}
+
+// The riding reduction of a launch (ride_fits, ride_chunks_of, ride_slice: what the launcher and the kernels go through), for
+// ranges [lo[r], hi[r]) of a grid of n sites, npair pairs in blocks of 1 << lg_block, NT threads, on the patch grid of
+// patch_grid(order, nrow, nsplit, lg_siblings, 0).  dims = {blocks of the patch grid, chunks of range 0, of range 1, rides};
+// rides = 0: four chunks per block do not cover the ranges, the launch keeps its reduction rows and nothing else is
+// written.  elems (or NULL): for the blocks [first_block, first_block + nblocks) of the grid's linear order, 4 NT entries
+// each ([round][thread]): the element's index in the plane set, | 1 << 62 for range 1; -1: nothing
+int patch_ride_map(int order, int nrow, int nsplit, int lg_siblings, int npair, int lg_block, int NT, int64_t n, const int32_t *lo,
+                   const int32_t *hi, int64_t first_block, int64_t nblocks, int64_t *dims, int64_t *elems)
+{
+    if (!dims || !lo || !hi) return fail(VRT_EINVAL, "NULL argument");
+    if (order < 0 || order > 1 || nrow < 1 || nrow > 65535 || nsplit < 1 || nsplit > 4096 || lg_siblings < 0 || lg_siblings > 4 ||
+        npair < 1 || lg_block < 0 || lg_block > 4 || NT < 64 || NT > 1024 || (NT & (NT - 1)) || n < 1 || n >= ((int64_t)1 << 28))
+        return fail(VRT_EINVAL, "ride map: argument out of range");
+    for (int r = 0; r < 2; r++)
+        if (lo[r] < 0 || hi[r] < lo[r] || hi[r] > n) return fail(VRT_EINVAL, "ride map: range outside the grid");
+    const PatchGrid pg = patch_grid(order, nrow, nsplit, lg_siblings, 0);
+    if (pg.gy > 65535) return fail(VRT_EINVAL, "more than 65535 rows of patch blocks");
+    const int64_t blocks = pg.gx * (int64_t)pg.prow;
+    PatchReduce red;
+    static double plane_tag;                          // (ride_fits counts a range that has angles and a J plane)
+    for (int r = 0; r < 2; r++) {
+        red.lo[r] = lo[r]; red.hi[r] = hi[r];
+        red.count[r] = hi[r] > lo[r] ? 1 : 0;
+        red.Jd[r] = hi[r] > lo[r] ? &plane_tag : nullptr;
+    }
+    PatchRide rd;
+    const bool rides = ride_fits(red, rd, npair, NT, blocks);
+    dims[0] = blocks; dims[1] = rd.chunks[0]; dims[2] = rd.chunks[1]; dims[3] = rides ? 1 : 0;
+    if (!rides || !elems) return VRT_OK;
+    if (first_block < 0 || nblocks < 0 || first_block + nblocks > blocks) return fail(VRT_EINVAL, "ride map: no such blocks");
+    for (int64_t b = 0; b < nblocks; b++) {
+        const unsigned lin = (unsigned)(first_block + b), chunks = ride_chunks_of(rd, lin);
+        for (unsigned i = 0; i < 4; i++)
+            for (unsigned t = 0; t < (unsigned)NT; t++) {
+                int64_t &o = elems[(b * 4 + i) * NT + t];
+                o = -1;
+                if (i >= chunks) continue;
+                const RideSlice s = ride_slice(red, rd, npair, lg_block, n, (unsigned)NT, lin, i, t);
+                if (s.r >= 0 && s.ok) o = (int64_t)s.e | ((int64_t)s.r << 62);
+            }
+    }
     return VRT_OK;
 }
 
